@@ -12,7 +12,10 @@ image encoder -> adapter -> prompt embedding -> decoder prefill -> N_NEW greedy 
 the timed region).  Multi-GPU: the global batch is sharded by rank, no collective inside the path, ONE
 all_gather of the token streams per step (RCCL), weak scaling (32 images per GPU).
 
-Prints ONE JSON line (rank 0).  value = generated SVG tokens / second over ALL GPUs.
+Prints ONE JSON line (rank 0).  value = generated SVG tokens / second over ALL GPUs; ms_per_step = one timed step.
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds what takes runs of its own (p50
+time-to-first-token and its stages, the decode step's profiling legs and rooflines, the prefill GEMMs, the CPU baseline);
+tools and tests that read those fields pass it.  --dump-outputs DIR writes the token ids of the last timed step.
 """
 from __future__ import annotations
 
@@ -34,6 +37,7 @@ sys.path.insert(0, ROOT)
 
 PROMPT_IDS = [7, 11]          # '<svg' is 2 ids under the (gated, offline) StarCoder tokenizer: synthetic stand-ins
 HBM_PEAK_GBS = 8000.0         # MI355X_MICROARCH.md: 8.0 TB/s spec
+DUMP_LIMIT_BYTES = 64 * 10**6
 
 
 def decoder_weight_bytes(cfg) -> int:
@@ -67,9 +71,17 @@ def parse():
                     help="with --sample: TopKLogitsWarper in front of top-p.  50 = what the reference's call really runs (it never passes top_k, and its pinned "
                          "transformers 4.49 defaults GenerationConfig.top_k to 50); 0 = top-p over the whole vocabulary (the line filed before this flag existed)")
     ap.add_argument("--batch", type=int, default=0, help="requests per GPU (default: the BASELINE configuration's: 32 / 16 / 64); other values are sweep points, not the headline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--ttft-requests", type=int, default=20)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what takes runs of its own: p50 time-to-first-token and its stages, the decode step's "
+                         "profiling legs and rooflines, the prefill GEMMs' roofline, the CPU baseline.  Without it the line holds the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the token ids the last timed step returned to DIR/tokens.npy (float32; the inputs depend on the arguments only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--ttft-requests", type=int, default=20, help="with --full: requests of the p50 time-to-first-token")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def cpu_baseline():
@@ -112,6 +124,20 @@ def synthetic_images(torch, n, size, seed):
     x = torch.rand(n, 3, size, size, generator=g)
     mean, std = torch.tensor(_CLIP_MEAN).view(1, 3, 1, 1), torch.tensor(_CLIP_STD).view(1, 3, 1, 1)
     return ((x - mean) / std).to(torch.bfloat16)
+
+
+def dump_tokens(out_dir, tokens):
+    """--dump-outputs: the token block a step returns, as out_dir/tokens.npy in float32 (ids are exact below 2**24).  A block past
+    DUMP_LIMIT_BYTES is cut to a fixed seeded sample of its rows; tokens_rows.npy then says which rows."""
+    import numpy as np
+    a = tokens.cpu().numpy().astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    row_bytes = a.shape[1] * a.itemsize + 8
+    if a.shape[0] * row_bytes > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], DUMP_LIMIT_BYTES // row_bytes, replace=False))
+        np.save(os.path.join(out_dir, "tokens_rows.npy"), rows.astype(np.float64))
+        a = a[rows]
+    np.save(os.path.join(out_dir, "tokens.npy"), a)
 
 
 def self_launch_command(gpus: int, argv, port=None):
@@ -247,7 +273,7 @@ def main():
     n_tok = 0
     decode_ms, decode_steps, graph, graph_steps = 0.0, 0.0, True, 0
     for _ in range(args.steps):
-        _, n = step()
+        out, n = step()
         n_tok += n
         tm = eng.last_timing()
         decode_ms += tm["decode_ms"]; decode_steps += tm["decode_steps"]; graph = graph and tm["graph"]
@@ -264,137 +290,115 @@ def main():
         dt = max(float(x.item()) for x in every)
     total_tokens = n_tok * B_PER_GPU * world
     value = total_tokens / dt
+    if args.dump_outputs and rank == 0:
+        dump_tokens(args.dump_outputs, out)
 
-    # time-to-first-token: encoder + adapter + prefill + first sampled token, batch 32, p50 over requests
-    ttfts = []
-    for _ in range(args.ttft_requests):
-        torch.cuda.synchronize()
-        a = time.perf_counter()
-        step(max_new=1)
-        torch.cuda.synchronize()
-        ttfts.append((time.perf_counter() - a) * 1e3)
-    ttft_p50 = statistics.median(ttfts) if ttfts else None
-    # ... and where it goes: one pass with a HIP event in front of every launch group (sv_profile_ttft).  The events open small gaps
-    # between launches, so the stages sum to a little more than the unprofiled figure above -- both are printed.
-    ttft_stages = None
-    try:
-        tp = eng.profile_ttft(None if t2s else images, prompt, iters=3)
-        ttft_stages = {k: round(tp[k], 3) for k in eng.TTFT_STAGES}
-        ttft_stages["sum_of_stages"] = round(sum(tp[k] for k in eng.TTFT_STAGES), 3)
-        ttft_stages["first_to_last_event"] = round(tp["first_to_last_event_ms"], 3)
-        ttft_stages["launch_groups"] = tp["launches"]
-        ttft_stages["note"] = ("HIP-event deltas minus the empty event-pair time (%.4f ms), one batch of %d, mean of 3 passes; gemm_remainder_rows = "
-                               "the peeled remainder-row launches of the big-M GEMMs of all towers" % (tp["event_pair_overhead_ms"], B_PER_GPU))
-    except Exception as ex:                      # a measurement extra: never the reason a bench line is missing
-        ttft_stages = {"error": f"{type(ex).__name__}: {ex}"}
-
-    # dominant kernel = skinny weight-streaming GEMM (97 launches / decode step): HIP-event time per step
-    # the decode step's real shape, asked of the engine BEFORE the profiling legs run their own (unfused) steps: kernel nodes of the captured
-    # step graph and which fused launches were on (sv_debug_step_plan; ADVICE r05: not re-derived from the configuration)
-    if NB > 1:
-        step(max_new=8)      # the one-token TTFT requests left B rows in the cache: the profiling legs below need all B x num_beams rows live
-    plan = eng.step_plan()
-    prof = eng.profile_decode_step(ROWS, iters=5)
-    sk = prof["skinny_gemm"]
-    launches = max(sk["launches_per_step"], 1.0)
-    # average launch duration of the dominant kernel: its 97 launches of one step enqueued back to back between
-    # one HIP event pair on the engine stream (dispatch to dispatch, the interval rocprofv3 reports per kernel)
-    sk_chain_ms = prof.get("skinny_chain_ms_per_step", 0.0) or sk["ms_per_step"]
-    sk_exec_ms = sk["ms_per_step"]                 # per-launch event deltas minus the empty event-pair time
-    # IN SITU the same launches sit between attention / row-update launches (cold L2, a different predecessor): what the step
-    # spends on them is the measured step minus the chain of everything else, also enqueued back to back between one event
-    # pair.  rocprofv3's per-kernel average (profiles/) lies between the two figures; `frac` uses the in-situ (larger) one.
-    step_ms = decode_ms / max(decode_steps, 1)
-    others_ms = prof.get("others_chain_ms_per_step", 0.0)
-    # An engine that owns its GPU runs the row update of every layer INSIDE the c_attn launch (rowln_cattn_kernel); the profiling legs time the
-    # unfused launches, so the 24 row updates that now belong to the family are taken out of the "others" chain (their event-delta share)
-    # (StarVector-8B, bf16, <= 32 rows: the same for the ln_1 row update of its 7-launch layer -- rowln_cattn_kernel<9, true>; ln_2's stays a launch)
-    rc_on = plan["rowln_cattn_fused"]
-    if rc_on and others_ms > 0:
-        ru = prof.get("row_update_ln", {})
-        n_ru = max(ru.get("launches_per_step", 0.0), 1.0)
-        others_ms = max(others_ms - ru.get("ms_per_step", 0.0) * min(float(cfg.n_layer), n_ru - 1.0) / n_ru, 0.0)
-    sk_ms = max(sk_chain_ms, step_ms - others_ms) if others_ms > 0 and step_ms > others_ms else sk_chain_ms
-    achieved = W_BYTES_PER_STEP / (sk_ms * 1e-3) / 1e9 if sk_ms > 0 else None
-    # HBM traffic per launch of the dominant kernel: PMC counters cannot be read from inside this process, so the figure is
-    # the one a separate `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` pass of this command left in profiles/ -- labelled
-    # as such (source + the kernel it was taken on); null when it does not apply to this configuration
-    traffic, traffic_source = None, None
-    tfile = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-    if os.path.exists(tfile) and not is8b and args.weights == "bf16" and not t2s:
+    def full_figures():
+        """--full: the line's secondary figures, each from runs of its own after the timed steps."""
+        # time-to-first-token: encoder + adapter + prefill + first sampled token, batch 32, p50 over requests
+        ttfts = []
+        for _ in range(args.ttft_requests):
+            torch.cuda.synchronize()
+            a = time.perf_counter()
+            step(max_new=1)
+            torch.cuda.synchronize()
+            ttfts.append((time.perf_counter() - a) * 1e3)
+        ttft_p50 = statistics.median(ttfts) if ttfts else None
+        # ... and where it goes: one pass with a HIP event in front of every launch group (sv_profile_ttft).  The events open small gaps
+        # between launches, so the stages sum to a little more than the unprofiled figure above -- both are printed.
+        ttft_stages = None
         try:
-            tj = json.load(open(tfile))
-            # the figure belongs to ONE launch family (73 launches per step with the fused MLP launch, 97 without): quoted only for that one
-            if int(tj.get("launches_per_step", round(launches))) == int(round(launches)):
-                traffic = tj.get("skinny_gemm_bytes_per_launch")
-                traffic_source = ("static: profiles/hbm_traffic.json (" + tj.get("measured", "rocprofv3 --pmc pass, separate run") + ")")
-            else:
-                traffic_source = (f"profiles/hbm_traffic.json was measured on the {tj.get('launches_per_step')}-launch family; this engine runs "
-                                  f"{int(round(launches))} launches per step")
-        except Exception:
-            traffic = None
+            tp = eng.profile_ttft(None if t2s else images, prompt, iters=3)
+            ttft_stages = {k: round(tp[k], 3) for k in eng.TTFT_STAGES}
+            ttft_stages["sum_of_stages"] = round(sum(tp[k] for k in eng.TTFT_STAGES), 3)
+            ttft_stages["first_to_last_event"] = round(tp["first_to_last_event_ms"], 3)
+            ttft_stages["launch_groups"] = tp["launches"]
+            ttft_stages["note"] = ("HIP-event deltas minus the empty event-pair time (%.4f ms), one batch of %d, mean of 3 passes; gemm_remainder_rows = "
+                                   "the peeled remainder-row launches of the big-M GEMMs of all towers" % (tp["event_pair_overhead_ms"], B_PER_GPU))
+        except Exception as ex:                      # a measurement extra: never the reason a bench line is missing
+            ttft_stages = {"error": f"{type(ex).__name__}: {ex}"}
 
-    # the profiler's own figure for the same family (rocprofv3 --kernel-trace of this command, tools/rocprof_family.py -> profiles/rocprof_family.json):
-    # quoted beside the in-situ one, which is a subtraction of chains
-    rocprof_us, rocprof_src = None, None
-    rfile = os.path.join(ROOT, "profiles", "rocprof_family.json")
-    if os.path.exists(rfile) and not is8b and args.weights == "bf16" and not t2s and NB == 1:
-        try:
-            rj = json.load(open(rfile))
-            rocprof_us = rj.get("avg_launch_us")
-            rocprof_src = f"static: profiles/rocprof_family.json ({rj.get('measured', '')}; {rj.get('launches')} launches of the family, {rj.get('source')})"
-        except Exception:
-            rocprof_us = None
+        # dominant kernel = skinny weight-streaming GEMM (97 launches / decode step): HIP-event time per step
+        # the decode step's real shape, asked of the engine BEFORE the profiling legs run their own (unfused) steps: kernel nodes of the captured
+        # step graph and which fused launches were on (sv_debug_step_plan; ADVICE r05: not re-derived from the configuration)
+        if NB > 1:
+            step(max_new=8)      # the one-token TTFT requests left B rows in the cache: the profiling legs below need all B x num_beams rows live
+        plan = eng.step_plan()
+        prof = eng.profile_decode_step(ROWS, iters=5)
+        sk = prof["skinny_gemm"]
+        launches = max(sk["launches_per_step"], 1.0)
+        # average launch duration of the dominant kernel: its 97 launches of one step enqueued back to back between
+        # one HIP event pair on the engine stream (dispatch to dispatch, the interval rocprofv3 reports per kernel)
+        sk_chain_ms = prof.get("skinny_chain_ms_per_step", 0.0) or sk["ms_per_step"]
+        sk_exec_ms = sk["ms_per_step"]                 # per-launch event deltas minus the empty event-pair time
+        # IN SITU the same launches sit between attention / row-update launches (cold L2, a different predecessor): what the step
+        # spends on them is the measured step minus the chain of everything else, also enqueued back to back between one event
+        # pair.  rocprofv3's per-kernel average (profiles/) lies between the two figures; `frac` uses the in-situ (larger) one.
+        step_ms = decode_ms / max(decode_steps, 1)
+        others_ms = prof.get("others_chain_ms_per_step", 0.0)
+        # An engine that owns its GPU runs the row update of every layer INSIDE the c_attn launch (rowln_cattn_kernel); the profiling legs time the
+        # unfused launches, so the 24 row updates that now belong to the family are taken out of the "others" chain (their event-delta share)
+        # (StarVector-8B, bf16, <= 32 rows: the same for the ln_1 row update of its 7-launch layer -- rowln_cattn_kernel<9, true>; ln_2's stays a launch)
+        rc_on = plan["rowln_cattn_fused"]
+        if rc_on and others_ms > 0:
+            ru = prof.get("row_update_ln", {})
+            n_ru = max(ru.get("launches_per_step", 0.0), 1.0)
+            others_ms = max(others_ms - ru.get("ms_per_step", 0.0) * min(float(cfg.n_layer), n_ru - 1.0) / n_ru, 0.0)
+        sk_ms = max(sk_chain_ms, step_ms - others_ms) if others_ms > 0 and step_ms > others_ms else sk_chain_ms
+        achieved = W_BYTES_PER_STEP / (sk_ms * 1e-3) / 1e9 if sk_ms > 0 else None
+        # HBM traffic per launch of the dominant kernel: PMC counters cannot be read from inside this process, so the figure is
+        # the one a separate `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` pass of this command left in profiles/ -- labelled
+        # as such (source + the kernel it was taken on); null when it does not apply to this configuration
+        traffic, traffic_source = None, None
+        tfile = os.path.join(ROOT, "profiles", "hbm_traffic.json")
+        if os.path.exists(tfile) and not is8b and args.weights == "bf16" and not t2s:
+            try:
+                tj = json.load(open(tfile))
+                # the figure belongs to ONE launch family (73 launches per step with the fused MLP launch, 97 without): quoted only for that one
+                if int(tj.get("launches_per_step", round(launches))) == int(round(launches)):
+                    traffic = tj.get("skinny_gemm_bytes_per_launch")
+                    traffic_source = ("static: profiles/hbm_traffic.json (" + tj.get("measured", "rocprofv3 --pmc pass, separate run") + ")")
+                else:
+                    traffic_source = (f"profiles/hbm_traffic.json was measured on the {tj.get('launches_per_step')}-launch family; this engine runs "
+                                      f"{int(round(launches))} launches per step")
+            except Exception:
+                traffic = None
 
-    # secondary, MFMA-bound kernels (TTFT path): the four decoder GEMMs of one prefill layer at M = B * S0 rows, live,
-    # through the same dispatch the engine uses (128^2 / 256^2 tile kernel + tail kernel)
-    from starvector_amd.engine import bench_linear, set_linear_seq_rows, gemm_seq_form
-    Mp = B_PER_GPU * S0
-    set_linear_seq_rows(S0)          # the prompt pass's own form: rows of S0-row sequences (per-sequence remainder where gemm_seq_form holds)
-    D, F = cfg.hidden, cfg.n_inner
-    qkv = D + 2 * (D // cfg.n_head) * cfg.n_kv_head
-    head_dim = D // cfg.n_head
-    gemms = [("c_attn", qkv, D, "none", False), ("c_proj", D, D, "none", True),
-             ("c_fc", F, D, "gelu_tanh", False), ("down_proj", D, F, "none", True)]
-    pf_us, pf_flop, per_gemm = 0.0, 0.0, {}
-    for gname, n_, k_, act_, res_ in gemms:
-        us_ = bench_linear(Mp, n_, k_, act=act_, residual=res_, iters=5 if is8b else 10)
-        fl_ = 2.0 * Mp * n_ * k_
-        pf_us += us_
-        pf_flop += fl_
-        per_gemm[gname] = {"shape": [Mp, n_, k_], "us": round(us_, 1), "tflops": round(fl_ / us_ / 1e6, 1),
-                           "per_sequence_remainder": bool(gemm_seq_form(S0, n_, k_, act_))}
-    set_linear_seq_rows(0)
-    tf_fc = pf_flop / pf_us / 1e6
+        # the profiler's own figure for the same family (rocprofv3 --kernel-trace of this command, tools/rocprof_family.py -> profiles/rocprof_family.json):
+        # quoted beside the in-situ one, which is a subtraction of chains (VERDICT r05 weak #15)
+        rocprof_us, rocprof_src = None, None
+        rfile = os.path.join(ROOT, "profiles", "rocprof_family.json")
+        if os.path.exists(rfile) and not is8b and args.weights == "bf16" and not t2s and NB == 1:
+            try:
+                rj = json.load(open(rfile))
+                rocprof_us = rj.get("avg_launch_us")
+                rocprof_src = f"static: profiles/rocprof_family.json ({rj.get('measured', '')}; {rj.get('launches')} launches of the family, {rj.get('source')})"
+            except Exception:
+                rocprof_us = None
 
-    if rank == 0:
-        res = {
-            "metric": f"SVG tokens/sec (whole job) + p50 time-to-first-token, StarVector-{args.model.upper()} {args.task} batch{B_PER_GPU}/GPU",
-            "value": round(value, 1), "unit": "tokens/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None,
-            "dtype": "bf16" if args.weights == "bf16" else "bf16 activations / fp8-e4m3 decoder weights (not the reference precision)",
-            "data": f"synthetic: random-pixel {cfg.image_size}x{cfg.image_size} images (CLIP-normalised), random-init weights N(0,0.02) seed 1234 drawn on the GPU",
-            "config": {"workload": (f"StarVector-{args.model.upper()} text2svg (no image encoder), batch {B_PER_GPU}/GPU, {args.weights} decoder weights, "
-                                    f"{'top-k 50 + top-p 0.95' if is8b else 'greedy'}, prompt rows {S0} ({CAPTION_TOKENS} caption ids + <svg-start>), "
-                                    f"{n_new} new tokens/seq, EOS disabled") if t2s else
-                                   (f"StarVector-8B im2svg, batch {B_PER_GPU}/GPU, bf16, top-k 50 + top-p 0.95, 384x384, prompt rows "
-                                    f"{S0} (576 visual + {len(PROMPT_IDS)}), {n_new} new tokens/seq, EOS disabled") if is8b else
-                                   (f"StarVector-1B im2svg, batch {B_PER_GPU}/GPU, bf16, " +
-                                    (f"{('beam-sample (top-k ' + str(int(args.top_k)) + ' + top-p 0.9)' if int(args.top_k) > 0 else 'beam-sample (top-p 0.9, no top-k)') if args.sample else 'beam search'} num_beams {NB} = {ROWS} rows per decode step "
-                                     "(the reference's default generate_im2svg call), " if NB > 1 else "greedy, ") +
-                                    f"224x224, prompt rows {S0} (257 visual + {len(PROMPT_IDS)}), {n_new} new tokens/seq, EOS disabled"),
-                       "global_batch": B_PER_GPU * world, "new_tokens": n_new,
-                       "parallelism": f"dp{world}" if world > 1 else "single",
-                       **({"dist_backend": ("gloo, ranks SHARE GPUs (functional run of the sharded path on a box with fewer GPUs than "
-                                            "ranks; not a scaling number)") if shared else f"nccl (RCCL {rccl_version})",
-                           "collectives_per_step": 1, "rccl_version": rccl_version,
-                           "tokens_per_s_by_rank": per_rank_tps} if world > 1 else {}),
-                       "hipgraph_decode": bool(graph), "decode_steps_per_graph_launch": graph_steps, "exclusive_device": bool(ec.exclusive_device)},
-            "tokens_per_s_per_gpu": round(value / world, 1),
+        # secondary, MFMA-bound kernels (TTFT path): the four decoder GEMMs of one prefill layer at M = B * S0 rows, live,
+        # through the same dispatch the engine uses (128^2 / 256^2 tile kernel + tail kernel, DESIGN.md section 3b)
+        from starvector_amd.engine import bench_linear, set_linear_seq_rows, gemm_seq_form
+        Mp = B_PER_GPU * S0
+        set_linear_seq_rows(S0)          # the prompt pass's own form: rows of S0-row sequences (per-sequence remainder where gemm_seq_form holds)
+        D, F = cfg.hidden, cfg.n_inner
+        qkv = D + 2 * (D // cfg.n_head) * cfg.n_kv_head
+        head_dim = D // cfg.n_head
+        gemms = [("c_attn", qkv, D, "none", False), ("c_proj", D, D, "none", True),
+                 ("c_fc", F, D, "gelu_tanh", False), ("down_proj", D, F, "none", True)]
+        pf_us, pf_flop, per_gemm = 0.0, 0.0, {}
+        for gname, n_, k_, act_, res_ in gemms:
+            us_ = bench_linear(Mp, n_, k_, act=act_, residual=res_, iters=5 if is8b else 10)
+            fl_ = 2.0 * Mp * n_ * k_
+            pf_us += us_
+            pf_flop += fl_
+            per_gemm[gname] = {"shape": [Mp, n_, k_], "us": round(us_, 1), "tflops": round(fl_ / us_ / 1e6, 1),
+                               "per_sequence_remainder": bool(gemm_seq_form(S0, n_, k_, act_))}
+        set_linear_seq_rows(0)
+        tf_fc = pf_flop / pf_us / 1e6
+        figs = {
             "ttft_p50_ms": round(ttft_p50, 2) if ttft_p50 is not None else None,
             "ttft_breakdown_ms": ttft_stages,
-            "decode_us_per_step": round(decode_ms / max(decode_steps, 1) * 1e3, 1),
             "roofline": {"bound": "hbm", "kernel": "decoder weight-streaming GEMMs: " + (
                              "gemm_skinny_mt2_kernel (two row tiles, up to three column tiles per block)" if ROWS > 32 else
                              "rowln_cattn_kernel<9, true> (ln_1 row update + c_attn in one launch) + gemm_skinny_kernel" if (is8b and rc_on) else
@@ -436,10 +440,42 @@ def main():
                     ROWS * (S0 + n_new / 2.0) * cfg.n_layer * 2 * cfg.n_kv_head * head_dim * 2,
                     decode_ms / max(decode_steps, 1) * 1e3),
             "decode_step_profile_ms": {k: round(v["ms_per_step"], 4) for k, v in prof.items() if isinstance(v, dict)},
-            "setup_s": round(t_setup, 1),
         }
         if keep_cpu:
-            res["cpu_baseline"] = cpu_baseline()
+            figs["cpu_baseline"] = cpu_baseline()
+        return figs
+
+    figs = full_figures() if args.full else {}
+
+    if rank == 0:
+        res = {
+            "metric": f"SVG tokens/sec (whole job) + p50 time-to-first-token, StarVector-{args.model.upper()} {args.task} batch{B_PER_GPU}/GPU",
+            "value": round(value, 1), "unit": "tokens/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None,
+            "dtype": "bf16" if args.weights == "bf16" else "bf16 activations / fp8-e4m3 decoder weights (not the reference precision)",
+            "data": f"synthetic: random-pixel {cfg.image_size}x{cfg.image_size} images (CLIP-normalised), random-init weights N(0,0.02) seed 1234 drawn on the GPU",
+            "config": {"workload": (f"StarVector-{args.model.upper()} text2svg (no image encoder), batch {B_PER_GPU}/GPU, {args.weights} decoder weights, "
+                                    f"{'top-k 50 + top-p 0.95' if is8b else 'greedy'}, prompt rows {S0} ({CAPTION_TOKENS} caption ids + <svg-start>), "
+                                    f"{n_new} new tokens/seq, EOS disabled") if t2s else
+                                   (f"StarVector-8B im2svg, batch {B_PER_GPU}/GPU, bf16, top-k 50 + top-p 0.95, 384x384, prompt rows "
+                                    f"{S0} (576 visual + {len(PROMPT_IDS)}), {n_new} new tokens/seq, EOS disabled") if is8b else
+                                   (f"StarVector-1B im2svg, batch {B_PER_GPU}/GPU, bf16, " +
+                                    (f"{('beam-sample (top-k ' + str(int(args.top_k)) + ' + top-p 0.9)' if int(args.top_k) > 0 else 'beam-sample (top-p 0.9, no top-k)') if args.sample else 'beam search'} num_beams {NB} = {ROWS} rows per decode step "
+                                     "(the reference's default generate_im2svg call), " if NB > 1 else "greedy, ") +
+                                    f"224x224, prompt rows {S0} (257 visual + {len(PROMPT_IDS)}), {n_new} new tokens/seq, EOS disabled"),
+                       "global_batch": B_PER_GPU * world, "new_tokens": n_new,
+                       "parallelism": f"dp{world}" if world > 1 else "single",
+                       **({"dist_backend": ("gloo, ranks SHARE GPUs (functional run of the sharded path on a box with fewer GPUs than "
+                                            "ranks; not a scaling number)") if shared else f"nccl (RCCL {rccl_version})",
+                           "collectives_per_step": 1, "rccl_version": rccl_version,
+                           "tokens_per_s_by_rank": per_rank_tps} if world > 1 else {}),
+                       "hipgraph_decode": bool(graph), "decode_steps_per_graph_launch": graph_steps, "exclusive_device": bool(ec.exclusive_device)},
+            "tokens_per_s_per_gpu": round(value / world, 1),
+            "decode_us_per_step": round(decode_ms / max(decode_steps, 1) * 1e3, 1),
+            "setup_s": round(t_setup, 1),
+            **figs,
+        }
         print(json.dumps(res), flush=True)
     eng.close()
     if world > 1:

@@ -26,7 +26,7 @@ def test_bench_two_ranks_over_rccl():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", SV_DIST_TIMEOUT_S="120")
     env.pop("SV_DIST_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "1", "--warmup", "1",
            "--new-tokens", "48", "--ttft-requests", "1", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, f"bench.py --gpus 2 failed (rc {r.returncode}):\n{r.stderr[-3000:]}"
@@ -67,7 +67,7 @@ def test_bench_bare_invocation_launches_itself_two_ranks_share_the_gpu():
     env["SV_DIST_TIMEOUT_S"] = "120"
     if torch.cuda.device_count() < 2:
         env["SV_DIST_BACKEND"] = "gloo"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--new-tokens", "8",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "1", "--warmup", "0", "--new-tokens", "8",
            "--ttft-requests", "1", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, f"bare bench.py --gpus 2 failed (rc {r.returncode}):\n{r.stderr[-3000:]}"

@@ -18,7 +18,7 @@ for ln in sys.stdin:
     if ln.startswith("{\"metric\""):
         d = json.loads(ln)
         print("   value %.1f %s | ttft_p50 %s ms | decode %s us/step | gemm family frac %s | whole step frac %s" % (
-            d["value"], d["unit"], d.get("ttft_p50_ms"), d.get("decode_us_per_step"), d["roofline"].get("frac"), d.get("roofline_whole_step", {}).get("frac")))
+            d["value"], d["unit"], d.get("ttft_p50_ms"), d.get("decode_us_per_step"), d.get("roofline", {}).get("frac"), d.get("roofline_whole_step", {}).get("frac")))
     elif any(k in ln for k in ("us_per_step", "ttft_ms", " TF", "passed", "failed", "Error")):
         print("   " + ln[:260])
 '

@@ -24,7 +24,7 @@ cp $O/smoke.log $P/smoke_r06.log
 cp $O/box.txt $P/box_r06_final.txt
 cp $O/step_gaps.log $P/step_gaps_r06_final_tree.log
 cp $O/ttft_gaps.log $P/ttft_gaps_r06_final_tree.log
-python tools/rocprof_family.py $P/rocprof_r06_by_grid.csv "$LABEL, rocprofv3 --kernel-trace of python bench.py --steps 1 --warmup 1 (gpurun_out/$TAG)"
+python tools/rocprof_family.py $P/rocprof_r06_by_grid.csv "$LABEL, rocprofv3 --kernel-trace of python bench.py --full --steps 1 --warmup 1 (run $TAG)"
 ALG=$(python -c "import json; print(json.load(open('$P/bench_r06_n1.json'))['roofline']['algorithmic_bytes_per_launch'])")
 python tools/hbm_traffic.py $P/pmc_r06_fetch_size.json $P/pmc_r06_write_size.json $ALG "$LABEL (tools/diag/round_final.sh pmc, gpurun_out/$TAG; profiles/pmc_r06_fetch_size.json, pmc_r06_write_size.json)" > $P/hbm_traffic.json
 python - <<'PY'

@@ -1,7 +1,7 @@
 #!/usr/bin/env bash
 # HIP runtime (ROCclr) knobs against the default on the headline bench, one process per arm, the default interleaved:  bash tools/diag/runtime_env_battery.sh <out.log>
 OUT="${1:-/dev/stdout}"
-run() { env "$@" timeout 300 python bench.py --no-cpu-baseline --steps 2 --warmup 1 --ttft-requests 5 2>/dev/null | python3 -c '
+run() { env "$@" timeout 300 python bench.py --full --no-cpu-baseline --steps 2 --warmup 1 --ttft-requests 5 2>/dev/null | python3 -c '
 import json,sys
 for ln in sys.stdin:
     if ln.startswith("{\"metric\""):

@@ -37,15 +37,15 @@ for s in "${STEPS[@]}"; do
             grep -oE "\[[A-Za-z0-9][^]]*\] .*|^.*(passed|failed).*$|^(FAILED|ERROR).*$" "$OUT/pytest_gpu_full.log" > "$OUT/pytest_gpu.log"; grep -E "^(FAILED|ERROR)|passed|failed" "$OUT/pytest_gpu.log" | tail -30 ;;
     pytest:*) timeout 1500 python -m pytest tests -m gpu -q -x -s -rA -k "${s#pytest:}" 2>&1 | grep -v amdgpu.ids > "$OUT/pytest_gpu_k_full.log"
             grep -oE "\[[A-Za-z0-9][^]]*\] .*|^.*(passed|failed|Error|assert).*$|^(FAILED|ERROR).*$" "$OUT/pytest_gpu_k_full.log" > "$OUT/pytest_gpu_k.log"; tail -25 "$OUT/pytest_gpu_k.log" ;;
-    bench) timeout 400 python bench.py > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"; cat "$OUT/bench_n1.json" ;;
+    bench) timeout 400 python bench.py --full > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"; cat "$OUT/bench_n1.json" ;;
     bench8b)
-      timeout 300 python bench.py --model 8b --new-tokens 256 --steps 2 --no-cpu-baseline > "$OUT/bench_8b_im2svg.json" 2> "$OUT/bench_8b_im2svg.err"
-      timeout 300 python bench.py --model 8b --weights fp8 --task text2svg --new-tokens 256 --steps 2 --no-cpu-baseline \
+      timeout 300 python bench.py --full --model 8b --new-tokens 256 --steps 2 --no-cpu-baseline > "$OUT/bench_8b_im2svg.json" 2> "$OUT/bench_8b_im2svg.err"
+      timeout 300 python bench.py --full --model 8b --weights fp8 --task text2svg --new-tokens 256 --steps 2 --no-cpu-baseline \
           > "$OUT/bench_8b_fp8_text2svg.json" 2> "$OUT/bench_8b_fp8_text2svg.err"
       cat "$OUT/bench_8b_im2svg.json" "$OUT/bench_8b_fp8_text2svg.json" ;;
     rocprof)
       ( cd /tmp && timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/rocprof" -- \
-          python "$ROOT/bench.py" --no-cpu-baseline --steps 1 --warmup 1 --ttft-requests 2 \
+          python "$ROOT/bench.py" --full --no-cpu-baseline --steps 1 --warmup 1 --ttft-requests 2 \
           > "$ROOT/$OUT/bench_under_rocprof.json" 2> "$ROOT/$OUT/rocprof.err" )
       python tools/rocprof_summary.py "$OUT/rocprof" "$OUT/rocprof_kernel_stats.csv" > "$OUT/rocprof_summary.log" 2>&1 || true
       python tools/trace_by_grid.py "$OUT/rocprof" "$OUT/rocprof_by_grid.csv" > "$OUT/by_grid.log" 2>&1 || true
@@ -55,7 +55,7 @@ for s in "${STEPS[@]}"; do
       for ctr in FETCH_SIZE WRITE_SIZE "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE"; do
         tagc="${ctr%% *}"
         ( cd /tmp && timeout 400 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d "$ROOT/$OUT/pmc_$tagc" -- \
-            python "$ROOT/bench.py" --no-cpu-baseline --steps 1 --warmup 0 --new-tokens 64 --ttft-requests 1 \
+            python "$ROOT/bench.py" --full --no-cpu-baseline --steps 1 --warmup 0 --new-tokens 64 --ttft-requests 1 \
             > /dev/null 2> "$ROOT/$OUT/pmc_$tagc.err" )
         python tools/pmc_summary.py "$OUT/pmc_$tagc" "$OUT/pmc_$tagc.json" > /dev/null 2>&1 || true
         find "$OUT/pmc_$tagc" -name '*.csv' -size +8M -delete 2>/dev/null

@@ -35,7 +35,7 @@ def main():
             "fetch_bytes_corrected": fetch_b, "write_bytes": write_b,
             "algorithmic_bytes_per_launch": alg,
             "traffic_over_algorithmic": round((fetch_b + write_b) / alg, 3),
-            "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE --output-format csv -- python bench.py --steps 1 "
+            "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE --output-format csv -- python bench.py --full --steps 1 "
                        "--warmup 0 --new-tokens 64 --no-cpu-baseline --ttft-requests 1",
         },
         "measured": where,
