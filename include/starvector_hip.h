@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define SV_ABI_VERSION 8
+#define SV_ABI_VERSION 9
 #define SV_WEIGHT_BF16 0
 #define SV_WEIGHT_FP8_E4M3 1
 
@@ -262,6 +262,19 @@ typedef struct sv_cb_request {
     float   repetition_penalty;
     int32_t n_stop;            /* 0..16 */
     int32_t stop_ids[16];
+    /* ABI 9, appended.  All zero = the fields above alone (HF semantics, unchanged).  semantics = 1 selects vLLM 0.5.5's
+     * sampler for this request: logit_bias -> min_tokens hold (eos_token_id and stop_any_ids -> -inf while fewer than
+     * min_new_tokens were emitted) -> repetition_penalty over prompt_ids and the output ids (l > 0 ? l / rp : l * rp) ->
+     * frequency_penalty * count -> presence_penalty * (count > 0), counts over the output ids only -> greedy argmax when
+     * do_sample = 0, else temperature -> top-k -> top-p -> min_p -> one draw.  Every field below is rejected (SV_EINVAL) unless
+     * semantics = 1, so none is lost silently.  Host arrays are read during sv_cb_admit only. */
+    int32_t semantics;         /* 0 = HF, 1 = vLLM */
+    float   presence_penalty, frequency_penalty, min_p;      /* min_p in [0, 1], 0 = off */
+    int32_t n_prompt_ids; const int32_t* prompt_ids;          /* token ids of the text prompt: seed the repetition set */
+    int32_t n_logit_bias;      /* 0..128, distinct ids; values clamped to [-100, 100] */
+    const int32_t* logit_bias_ids; const float* logit_bias_values;
+    int32_t n_stop_any;        /* 0..8: emitting any one of these ids ends the request */
+    int32_t stop_any_ids[8];
 } sv_cb_request;
 int  sv_cb_admit(sv_engine* e, const void* dev_embeds, int32_t n, int32_t S0, const sv_cb_request* reqs, int32_t* slots_out,
                  sv_stream stream);

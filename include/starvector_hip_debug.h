@@ -192,6 +192,12 @@ int  sv_op_plane_layernorm(const void* x, const void* gamma, const void* beta, v
 int  sv_op_argmax(const float* logits, int32_t B, int32_t V, int32_t ld, int32_t* out, sv_stream stream);
 int  sv_op_sample_top_p(const float* logits, int32_t B, int32_t V, int32_t ld, float temperature,
                         float top_p, uint64_t seed, int32_t step, int32_t* out, sv_stream stream);
+/* the continuous-batching selection (cb_step_kernel, the same device code) on caller-given rows: row b of dev_logits [B][ld]
+ * (ld a multiple of 4; not modified: the kernel works on a copy) is request reqs[b] after host_hist_len[b] output tokens
+ * host_history[b][0 .. host_hist_len[b]) (row stride ld_hist): that is its step (random stream, min_new_tokens hold), its output
+ * counts and, with the prompt ids, its repetition set.  host_out [B] = the token each row takes. */
+int  sv_op_cb_select(const float* dev_logits, int32_t B, int32_t V, int32_t ld, const sv_cb_request* reqs,
+                     const int32_t* host_history, int32_t ld_hist, const int32_t* host_hist_len, int32_t* host_out, sv_stream stream);
 /* temperature -> top-k (0 = off) -> top-p -> one multinomial draw per row */
 int  sv_op_sample(const float* logits, int32_t B, int32_t V, int32_t ld, float temperature, int32_t top_k,
                   float top_p, uint64_t seed, int32_t step, int32_t* out, sv_stream stream);

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(HERE, "libstarvector_hip.so")
 HEADER_PATH = os.path.normpath(os.path.join(HERE, "..", "include", "starvector_hip.h"))
 DEBUG_HEADER_PATH = os.path.normpath(os.path.join(HERE, "..", "include", "starvector_hip_debug.h"))
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 SV_DTYPE_BF16, SV_DTYPE_F32 = 0, 1
 SV_NORM_LAYER, SV_NORM_BATCH = 0, 1
 SV_ARCH_V1, SV_ARCH_V2 = 0, 1
@@ -54,7 +54,14 @@ class SvCbRequest(C.Structure):
         ("seed", C.c_uint64), ("max_new_tokens", C.c_int32), ("eos_token_id", C.c_int32), ("pad_token_id", C.c_int32),
         ("min_new_tokens", C.c_int32), ("repetition_penalty", C.c_float), ("n_stop", C.c_int32),
         ("stop_ids", C.c_int32 * 16),
+        # ABI 9: vLLM sampler semantics (semantics = 1); all zero = HF, as before
+        ("semantics", C.c_int32), ("presence_penalty", C.c_float), ("frequency_penalty", C.c_float), ("min_p", C.c_float),
+        ("n_prompt_ids", C.c_int32), ("prompt_ids", C.POINTER(C.c_int32)),
+        ("n_logit_bias", C.c_int32), ("logit_bias_ids", C.POINTER(C.c_int32)), ("logit_bias_values", C.POINTER(C.c_float)),
+        ("n_stop_any", C.c_int32), ("stop_any_ids", C.c_int32 * 8),
     ]
+
+CB_MAX_LOGIT_BIAS, CB_MAX_STOP_ANY = 128, 8
 
 
 class SvBeamConfig(C.Structure):
@@ -150,6 +157,7 @@ DEBUG_PROTOTYPES = {
     "sv_op_argmax": (_I, [_P, _I, _I, _I, _P, _P]),
     "sv_op_sample_top_p": (_I, [_P, _I, _I, _I, _F, _F, C.c_uint64, _I, _P, _P]),
     "sv_op_sample": (_I, [_P, _I, _I, _I, _F, _I, _F, C.c_uint64, _I, _P, _P]),
+    "sv_op_cb_select": (_I, [_P, _I, _I, _I, C.POINTER(SvCbRequest), C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(_I), _P]),
 }
 
 PROTOTYPES = {**PRODUCT_PROTOTYPES, **DEBUG_PROTOTYPES}

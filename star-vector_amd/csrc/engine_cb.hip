@@ -1,4 +1,6 @@
 // Host driver, part 4 of 5: continuous batching (sv_cb_*): requests are rows ("slots") of one decode loop.
+#include <algorithm>
+#include <cmath>
 #include "engine_internal.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -20,7 +22,66 @@ static void cb_step_args(sv_engine* e, CbStepArgs& a, const int32_t* map) {
     a.logits = e->logits; a.ld = e->Vpad; a.V = e->cfg.vocab; a.slots = e->cb_slots; a.slot_map = map;
     a.cur_tok = e->cur_tok; a.positions = e->positions; a.out_tokens = e->out_tok; a.ld_out = e->out_ld;
     a.seen = e->seen; a.seen_words = e->seen_words; a.n_live = e->cb_nlive; a.events = e->cb_events; a.bad = e->d_bad;
+    a.counts = e->cb_counts; a.ld_counts = e->Vpad; a.bias = e->cb_bias;
 }
+
+namespace sveng {
+int cb_check_request(const sv_cb_request& r, int V, int i, const char* who) {
+    if (r.semantics != 0 && r.semantics != 1) return fail(SV_EINVAL, "%s: request %d: semantics %d (0 = HF, 1 = vLLM)", who, i, r.semantics);
+    if (r.n_stop < 0 || r.n_stop > SV_CB_MAXSTOP) return fail(SV_EINVAL, "%s: request %d: stop sequence length %d unsupported (0..%d)", who, i, r.n_stop, SV_CB_MAXSTOP);
+    if (r.do_sample && !(r.temperature > 0.f && r.top_p > 0.f)) return fail(SV_EINVAL, "%s: request %d: temperature and top_p must be > 0", who, i);
+    if (r.semantics == 0) {
+        // the vLLM fields act in vLLM mode only: a caller that set one under HF semantics would lose it silently
+        const char* set = r.presence_penalty != 0.f ? "presence_penalty" : r.frequency_penalty != 0.f ? "frequency_penalty"
+                        : r.min_p != 0.f ? "min_p" : (r.n_prompt_ids || r.prompt_ids) ? "prompt_ids"
+                        : (r.n_logit_bias || r.logit_bias_ids || r.logit_bias_values) ? "logit_bias" : r.n_stop_any ? "stop_any_ids" : nullptr;
+        if (set) return fail(SV_EINVAL, "%s: request %d: %s is a vLLM-semantics field (set semantics = 1)", who, i, set);
+        return 0;
+    }
+    if (!std::isfinite(r.presence_penalty) || !std::isfinite(r.frequency_penalty))
+        return fail(SV_EINVAL, "%s: request %d: presence / frequency penalty must be finite", who, i);
+    if (!(r.min_p >= 0.f && r.min_p <= 1.f)) return fail(SV_EINVAL, "%s: request %d: min_p %g outside [0, 1]", who, i, (double)r.min_p);
+    if (!(r.repetition_penalty >= 0.f) || !std::isfinite(r.repetition_penalty))
+        return fail(SV_EINVAL, "%s: request %d: repetition_penalty must be > 0 (0 = off)", who, i);
+    if (r.eos_token_id >= V) return fail(SV_EINVAL, "%s: request %d: eos_token_id %d outside the vocabulary (%d; negative = none)", who, i, r.eos_token_id, V);
+    if (r.max_new_tokens > 65535) return fail(SV_EINVAL, "%s: request %d: max_new_tokens %d: vLLM mode counts tokens in 16 bits (< 65536)", who, i, r.max_new_tokens);
+    if (r.n_prompt_ids < 0 || (r.n_prompt_ids > 0 && !r.prompt_ids)) return fail(SV_EINVAL, "%s: request %d: bad prompt_ids", who, i);
+    for (int k = 0; k < r.n_prompt_ids; ++k)
+        if (r.prompt_ids[k] < 0 || r.prompt_ids[k] >= V) return fail(SV_EINVAL, "%s: request %d: prompt id %d outside the vocabulary (%d)", who, i, r.prompt_ids[k], V);
+    if (r.n_logit_bias < 0 || r.n_logit_bias > SV_CB_MAXBIAS) return fail(SV_EINVAL, "%s: request %d: %d logit_bias entries (0..%d)", who, i, r.n_logit_bias, SV_CB_MAXBIAS);
+    if (r.n_logit_bias > 0 && (!r.logit_bias_ids || !r.logit_bias_values)) return fail(SV_EINVAL, "%s: request %d: null logit_bias arrays", who, i);
+    for (int k = 0; k < r.n_logit_bias; ++k) {
+        const int id = r.logit_bias_ids[k];
+        if (id < 0 || id >= V) return fail(SV_EINVAL, "%s: request %d: logit_bias id %d outside the vocabulary (%d)", who, i, id, V);
+        if (std::isnan(r.logit_bias_values[k])) return fail(SV_EINVAL, "%s: request %d: logit_bias value of id %d is NaN", who, i, id);
+        for (int j = 0; j < k; ++j)
+            if (r.logit_bias_ids[j] == id) return fail(SV_EINVAL, "%s: request %d: logit_bias id %d given twice", who, i, id);
+    }
+    if (r.n_stop_any < 0 || r.n_stop_any > SV_CB_MAXANY) return fail(SV_EINVAL, "%s: request %d: %d stop_any_ids (0..%d)", who, i, r.n_stop_any, SV_CB_MAXANY);
+    for (int k = 0; k < r.n_stop_any; ++k)
+        if (r.stop_any_ids[k] < 0 || r.stop_any_ids[k] >= V) return fail(SV_EINVAL, "%s: request %d: stop id %d outside the vocabulary (%d)", who, i, r.stop_any_ids[k], V);
+    return 0;
+}
+
+void cb_fill_slot(const sv_cb_request& r, CbSlot& h, CbBias& bias, std::vector<uint32_t>& seen_row, int seen_words) {
+    memset(&h, 0, sizeof(h));
+    memset(&bias, 0, sizeof(bias));
+    h.live = 1; h.step = 0; h.budget = r.max_new_tokens; h.do_sample = r.do_sample ? 1 : 0; h.temperature = r.temperature;
+    h.top_p = r.top_p; h.top_k = r.top_k; h.eos = r.eos_token_id; h.pad = r.pad_token_id; h.min_new = r.min_new_tokens;
+    h.penalty = r.repetition_penalty > 0.f ? r.repetition_penalty : 1.0f; h.n_stop = r.n_stop; h.seed = r.seed;
+    for (int k = 0; k < r.n_stop; ++k) h.stop[k] = r.stop_ids[k];
+    seen_row.assign(seen_words, 0u);
+    if (r.semantics != 1) return;
+    h.vllm = 1; h.presence = r.presence_penalty; h.frequency = r.frequency_penalty; h.min_p = r.min_p;
+    h.n_bias = r.n_logit_bias; h.n_any = r.n_stop_any;
+    for (int k = 0; k < r.n_stop_any; ++k) h.any[k] = r.stop_any_ids[k];
+    for (int k = 0; k < r.n_logit_bias; ++k) {
+        bias.id[k] = r.logit_bias_ids[k];
+        bias.val[k] = std::min(100.f, std::max(-100.f, r.logit_bias_values[k]));      // the OpenAI server's clamp
+    }
+    for (int k = 0; k < r.n_prompt_ids; ++k) seen_row[r.prompt_ids[k] >> 5] |= 1u << (r.prompt_ids[k] & 31);
+}
+}  // namespace sveng
 
 static int cb_begin(sv_engine* e, hipStream_t st) {
     if (e->cb_active) return 0;
@@ -53,8 +114,7 @@ extern "C" int sv_cb_admit(sv_engine* e, const void* dev_embeds, int32_t n, int3
         const sv_cb_request& r = reqs[i];
         if (r.max_new_tokens < 1 || S0 + r.max_new_tokens > c.max_seq_len)
             return fail(SV_EINVAL, "sv_cb_admit: request %d: prompt %d + max_new_tokens %d out of range (max_seq_len %d)", i, S0, r.max_new_tokens, c.max_seq_len);
-        if (r.n_stop < 0 || r.n_stop > SV_CB_MAXSTOP) return fail(SV_EINVAL, "sv_cb_admit: request %d: stop sequence length %d unsupported (0..%d)", i, r.n_stop, SV_CB_MAXSTOP);
-        if (r.do_sample && !(r.temperature > 0.f && r.top_p > 0.f)) return fail(SV_EINVAL, "sv_cb_admit: request %d: temperature and top_p must be > 0", i);
+        SVCHECK(cb_check_request(r, c.vocab, i, "sv_cb_admit"));
     }
     std::lock_guard<std::mutex> lk(e->mu);
     HIPCHECK(hipSetDevice(c.device));
@@ -72,6 +132,8 @@ extern "C" int sv_cb_admit(sv_engine* e, const void* dev_embeds, int32_t n, int3
                     n, n, need_pages, slots.size(), e->free_pages.size());
     std::vector<int32_t> rows((size_t)n * e->pages_per_seq, e->trash_page);
     std::vector<CbSlot> hs(n);
+    std::vector<CbBias> hb(n);
+    std::vector<std::vector<uint32_t>> seen_rows(n);
     std::vector<int32_t> map(n), pos(n, S0 - 1);
     const bool any_pen = [&] { for (int i = 0; i < n; ++i) if (reqs[i].repetition_penalty > 0.f && reqs[i].repetition_penalty != 1.0f) return true; return false; }();
     for (int i = 0; i < n; ++i) {
@@ -85,12 +147,7 @@ extern "C" int sv_cb_admit(sv_engine* e, const void* dev_embeds, int32_t n, int3
             e->free_pages.pop_back();
         }
         e->cb_used[s2] = 1;
-        CbSlot& h = hs[i];
-        memset(&h, 0, sizeof(h));
-        h.live = 1; h.step = 0; h.budget = r.max_new_tokens; h.do_sample = r.do_sample ? 1 : 0; h.temperature = r.temperature;
-        h.top_p = r.top_p; h.top_k = r.top_k; h.eos = r.eos_token_id; h.pad = r.pad_token_id; h.min_new = r.min_new_tokens;
-        h.penalty = r.repetition_penalty > 0.f ? r.repetition_penalty : 1.0f; h.n_stop = r.n_stop; h.seed = r.seed;
-        for (int k = 0; k < r.n_stop; ++k) h.stop[k] = r.stop_ids[k];
+        cb_fill_slot(r, hs[i], hb[i], seen_rows[i], e->seen_words);
         map[i] = s2;
         slots_out[i] = s2;
     }
@@ -104,7 +161,15 @@ extern "C" int sv_cb_admit(sv_engine* e, const void* dev_embeds, int32_t n, int3
                                 e->pages_per_seq * sizeof(int32_t), hipMemcpyHostToDevice, st));
         HIPCHECK(hipMemcpyAsync(e->cb_slots + s2, &hs[i], sizeof(CbSlot), hipMemcpyHostToDevice, st));
         HIPCHECK(hipMemcpyAsync(e->positions + s2, &pos[i], sizeof(int32_t), hipMemcpyHostToDevice, st));
-        if (any_pen) HIPCHECK(hipMemsetAsync(e->seen + (size_t)s2 * e->seen_words, 0, e->seen_words * sizeof(uint32_t), st));
+        if (reqs[i].semantics == 1) {
+            // vLLM mode: the repetition set starts as the prompt ids, the output counts at zero -- before the first-token step below
+            HIPCHECK(hipMemcpyAsync(e->seen + (size_t)s2 * e->seen_words, seen_rows[i].data(), e->seen_words * sizeof(uint32_t),
+                                    hipMemcpyHostToDevice, st));
+            HIPCHECK(hipMemsetAsync(e->cb_counts + (size_t)s2 * e->Vpad, 0, (size_t)e->Vpad * sizeof(uint16_t), st));
+            if (hs[i].n_bias) HIPCHECK(hipMemcpyAsync(e->cb_bias + s2, &hb[i], sizeof(CbBias), hipMemcpyHostToDevice, st));
+        } else if (any_pen) {
+            HIPCHECK(hipMemsetAsync(e->seen + (size_t)s2 * e->seen_words, 0, e->seen_words * sizeof(uint32_t), st));
+        }
     }
     HIPCHECK(hipMemcpyAsync(e->cb_table_pf, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemcpyAsync(e->cb_map, map.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, st));

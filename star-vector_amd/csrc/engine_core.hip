@@ -533,6 +533,8 @@ extern "C" int sv_create(const sv_config* cfg, sv_engine** out) {
     A(dalloc(e, &e->block_table, (size_t)c.max_batch * e->pages_per_seq));
     A(dalloc(e, &e->cb_table_pf, (size_t)c.max_batch * e->pages_per_seq));
     A(dalloc(e, &e->cb_slots, (size_t)R));
+    A(dalloc(e, &e->cb_bias, (size_t)c.max_batch));
+    A(dalloc(e, &e->cb_counts, (size_t)c.max_batch * e->Vpad));     // 98 KB per slot at StarVector's vocabulary
     A(dalloc(e, &e->cb_map, (size_t)R));
     A(dalloc(e, &e->cb_nlive, 4));
     A(dalloc(e, &e->cb_events, 4));

@@ -181,6 +181,8 @@ struct sv_engine {
     std::vector<char> cb_used;                    // slot in use (admitted, not yet released)
     std::vector<std::vector<int>> cb_pages;       // pages held by each slot
     CbSlot* cb_slots = nullptr;                   // device [max_batch]
+    CbBias* cb_bias = nullptr;                    // device [max_batch]: logit bias of vLLM-mode slots
+    uint16_t* cb_counts = nullptr;                // device [max_batch][Vpad]: output-token counts of vLLM-mode slots
     int32_t *cb_map = nullptr, *cb_nlive = nullptr, *cb_events = nullptr, *cb_table_pf = nullptr;
     int trash_page = 0;                           // what the block-table rows of free slots point at
     std::unordered_map<int, std::pair<hipGraph_t, hipGraphExec_t>> cb_graphs;      // one captured step per row bucket
@@ -232,6 +234,10 @@ int prefill_forward(sv_engine* e, const bf16_t* embeds, int B, int S0, hipStream
 void decode_forward(sv_engine* e, int B, hipStream_t st);
 void attn_decode_args(sv_engine* e, int layer, int B, const float* ws, int splitk, const bf16_t* bias, bf16_t* out_xp, AttnDecodeArgs& ad);
 int check_ready(sv_engine* e);
+// continuous batching (engine_cb.hip): validation of one request (SV_EINVAL + message) and its device state -- the slot, its
+// logit bias, its repetition bitmap row (seen_words words: the prompt ids in vLLM mode, cleared otherwise)
+int cb_check_request(const sv_cb_request& r, int V, int i, const char* who);
+void cb_fill_slot(const sv_cb_request& r, CbSlot& h, CbBias& bias, std::vector<uint32_t>& seen_row, int seen_words);
 int cb_guard(sv_engine* e, const char* who);
 int prefill_locked(sv_engine* e, const void* dev_embeds, int B, int S0, int total_len, hipStream_t st, bool set_positions = true);
 // engine_generate.hip

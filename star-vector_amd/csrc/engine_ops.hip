@@ -776,6 +776,79 @@ extern "C" int sv_op_argmax(const float* logits, int32_t B, int32_t V, int32_t l
     return 0;
 }
 
+// the continuous-batching selection on caller-given rows: cb_step_kernel itself, one block per row (slot b = row b), on a copy of the
+// logits (vLLM-mode rows are rewritten in place) with each row's step, output counts and repetition set rebuilt from its history
+extern "C" int sv_op_cb_select(const float* logits, int32_t B, int32_t V, int32_t ld, const sv_cb_request* reqs,
+                               const int32_t* history, int32_t ld_hist, const int32_t* hist_len, int32_t* out, sv_stream stream) {
+    if (!logits || !reqs || !hist_len || !out || B < 1 || B > 4096 || V < 1 || ld < V || (ld & 3) || ld_hist < 0)
+        return fail(SV_EINVAL, "sv_op_cb_select: bad argument");
+    int max_len = 0;
+    for (int b = 0; b < B; ++b) {
+        if (hist_len[b] < 0 || hist_len[b] > ld_hist || (hist_len[b] > 0 && !history))
+            return fail(SV_EINVAL, "sv_op_cb_select: row %d: history length %d (ld_hist %d)", b, hist_len[b], ld_hist);
+        for (int t = 0; t < hist_len[b]; ++t)
+            if (history[(size_t)b * ld_hist + t] < 0 || history[(size_t)b * ld_hist + t] >= V)
+                return fail(SV_EINVAL, "sv_op_cb_select: row %d: history id outside the vocabulary", b);
+        max_len = std::max(max_len, (int)hist_len[b]);
+        SVCHECK(cb_check_request(reqs[b], V, b, "sv_op_cb_select"));
+    }
+    const int words = (ld + 31) / 32, ld_out = max_len + 1;
+    std::vector<CbSlot> hs(B);
+    std::vector<CbBias> hb(B);
+    std::vector<uint32_t> seen((size_t)B * words, 0u), row;
+    std::vector<uint16_t> counts((size_t)B * ld, 0);
+    for (int b = 0; b < B; ++b) {
+        const sv_cb_request& r = reqs[b];
+        cb_fill_slot(r, hs[b], hb[b], row, words);
+        hs[b].step = hist_len[b];
+        const bool track = r.semantics == 1 || (r.repetition_penalty > 0.f && r.repetition_penalty != 1.0f);
+        for (int t = 0; t < hist_len[b]; ++t) {
+            const int id = history[(size_t)b * ld_hist + t];
+            if (track) row[id >> 5] |= 1u << (id & 31);
+            if (r.semantics == 1) counts[(size_t)b * ld + id] += 1;
+        }
+        std::copy(row.begin(), row.end(), seen.begin() + (size_t)b * words);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    TmpBufs tmp;
+    float* lg;
+    CbSlot* dslots;
+    CbBias* dbias;
+    uint32_t* dseen;
+    uint16_t* dcounts;
+    int32_t *dout, *dcur, *dpos, *dctr;
+    SVCHECK(tmp.get(&lg, (size_t)B * ld));
+    SVCHECK(tmp.get(&dslots, (size_t)B));
+    SVCHECK(tmp.get(&dbias, (size_t)B));
+    SVCHECK(tmp.get(&dseen, seen.size()));
+    SVCHECK(tmp.get(&dcounts, counts.size()));
+    SVCHECK(tmp.get(&dout, (size_t)B * ld_out));
+    SVCHECK(tmp.get(&dcur, (size_t)B));
+    SVCHECK(tmp.get(&dpos, (size_t)B));
+    SVCHECK(tmp.get(&dctr, 3));
+    HIPCHECK(hipMemcpyAsync(lg, logits, (size_t)B * ld * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIPCHECK(hipMemcpyAsync(dslots, hs.data(), hs.size() * sizeof(CbSlot), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(dbias, hb.data(), hb.size() * sizeof(CbBias), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(dseen, seen.data(), seen.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(dcounts, counts.data(), counts.size() * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemsetAsync(dout, 0, (size_t)B * ld_out * sizeof(int32_t), st));
+    HIPCHECK(hipMemsetAsync(dcur, 0, (size_t)B * sizeof(int32_t), st));
+    HIPCHECK(hipMemsetAsync(dpos, 0, (size_t)B * sizeof(int32_t), st));
+    HIPCHECK(hipMemsetAsync(dctr, 0, 3 * sizeof(int32_t), st));
+    CbStepArgs a;
+    a.logits = lg; a.ld = ld; a.V = V; a.slots = dslots; a.slot_map = nullptr;
+    a.cur_tok = dcur; a.positions = dpos; a.out_tokens = dout; a.ld_out = ld_out;
+    a.seen = dseen; a.seen_words = words; a.n_live = dctr; a.events = dctr + 1; a.bad = dctr + 2;
+    a.counts = dcounts; a.ld_counts = ld; a.bias = dbias;
+    launch_cb_step(a, B, st);
+    HIPCHECK(hipGetLastError());
+    std::vector<int32_t> ho((size_t)B * ld_out);
+    HIPCHECK(hipMemcpyAsync(ho.data(), dout, ho.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    for (int b = 0; b < B; ++b) out[b] = ho[(size_t)b * ld_out + hist_len[b]];
+    return 0;
+}
+
 extern "C" int sv_op_sample(const float* logits, int32_t B, int32_t V, int32_t ld, float temperature, int32_t top_k,
                             float top_p, uint64_t seed, int32_t step, int32_t* out, sv_stream stream);
 extern "C" int sv_op_sample_top_p(const float* logits, int32_t B, int32_t V, int32_t ld, float temperature, float top_p,

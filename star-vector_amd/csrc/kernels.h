@@ -342,6 +342,8 @@ __device__ __forceinline__ void finish_step_call(const FinishArgs& p, int t, int
 
 // ---- continuous batching: one request per row ("slot"), everything per row (sampling.hip) ---------------------------
 #define SV_CB_MAXSTOP 16
+#define SV_CB_MAXANY 8
+#define SV_CB_MAXBIAS 128
 struct CbSlot {                  // device-resident, one per slot
     int32_t live;                // 1 = generating
     int32_t step;                // tokens emitted so far
@@ -351,7 +353,15 @@ struct CbSlot {                  // device-resident, one per slot
     int32_t n_stop; int32_t stop[SV_CB_MAXSTOP];
     int32_t pad_[1];
     uint64_t seed;
+    // vLLM 0.5.5 sampler semantics (vllm = 1): before the selection the slot's block rewrites its logits row in place with
+    // logit_bias (CbBias), the min_tokens hold (eos and every `any` id -> -inf), repetition over the seen bitmap (prompt ids
+    // seeded at admit, output ids added per step), frequency and presence over the output counts; min_p after top-p
+    int32_t vllm;
+    float presence, frequency, min_p;            // min_p 0 = off
+    int32_t n_bias, n_any;
+    int32_t any[SV_CB_MAXANY];                   // stop_token_ids: any one of them ends the request (not a sequence)
 };
+struct CbBias { int32_t id[SV_CB_MAXBIAS]; float val[SV_CB_MAXBIAS]; };     // device-resident, one per slot
 struct CbStepArgs {
     const float* logits; int ld; int V;
     CbSlot* slots; const int32_t* slot_map;      // block b works for slot slot_map[b] (nullptr: b) on logits row b
@@ -359,6 +369,10 @@ struct CbStepArgs {
     uint32_t* seen; int seen_words;
     int32_t* n_live; int32_t* events;           // device counters: live slots, finished-slot events
     int32_t* bad;                               // raised when a slot has no valid token (all logits NaN); the id becomes 0
+    // vLLM-mode slots only: output-token counts [slot][ld_counts] (uint16: any budget below 65 536 tokens, checked at admit)
+    // and the logit bias entries per slot.  The logits rows are rewritten in place for those slots.
+    uint16_t* counts; int ld_counts;
+    const CbBias* bias;
 };
 void launch_cb_step(const CbStepArgs& a, int nblocks, hipStream_t st);
 

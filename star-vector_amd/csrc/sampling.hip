@@ -88,7 +88,8 @@ void launch_argmax(const float* logits, int ld, int V, int32_t* out, float* pval
 //   5. softmax over the survivors; TopP: F(c) = the mass of survivors with p <= p_c, v0 = the smallest p_c with F(c) > 1 - top_p,
 //      keep p >= v0 (the maximum always: min_tokens_to_keep = 1) -- warp.h's rule, evaluated on the ~k survivors
 //   6. one multinomial draw over the kept tokens in INDEX order: the token with the largest index whose exclusive prefix mass is
-//      <= u (the same counter-based uniform as the general path)
+//      <= u (the same counter-based uniform as the general path); vLLM's min_p (minp_log = log(min_p), -inf = off) drops the
+//      survivors below its threshold first, so the draw renormalises over what is left
 // Deterministic (fixed summation orders).  Returns -1 when the row is outside its scope (no finite score, too many candidates).
 // ------------------------------------------------------------------------------------------------
 #define TK_CAP 2048
@@ -108,7 +109,7 @@ __device__ __forceinline__ TopkSmem& topk_smem() {
 }
 
 template <class F>
-__device__ int sample_row_topk(F lg, int V, int k, float top_p, uint64_t seed, uint32_t step, uint32_t rowid, float* red) {
+__device__ int sample_row_topk(F lg, int V, int k, float top_p, float minp_log, uint64_t seed, uint32_t step, uint32_t rowid, float* red) {
     TopkSmem& sm = topk_smem();
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float mt = -INFINITY;
@@ -267,6 +268,16 @@ __device__ int sample_row_topk(F lg, int V, int k, float top_p, uint64_t seed, u
         __syncthreads();
     }
 
+    if (minp_log > -INFINITY) {                                       // min_p after top-p (block-uniform)
+        const float thr = wp_minp_thr(mx, minp_log);
+#pragma unroll
+        for (int q = 0; q < (TK_CAP + SP_THREADS - 1) / SP_THREADS; ++q) {
+            const int c = tid + q * SP_THREADS;
+            if (c < n && e[q] > 0.f && !(wp_unkey(sm.key[c]) >= thr)) { e[q] = 0.f; sm.p[c] = 0.f; }
+        }
+        __syncthreads();
+    }
+
     // ---- 6. multinomial over the kept tokens, index order ----
     float ts = 0.f;
 #pragma unroll
@@ -292,15 +303,17 @@ __device__ int sample_row_topk(F lg, int V, int k, float top_p, uint64_t seed, u
 
 // one multinomial draw from softmax(warped scores) of a row, by the whole 1024-thread block; `lg(i)` = the row's score after
 // processors and temperature.  The random number is a pure function of (seed, step, row).  Every thread returns the token.
+// minp_log = log(min_p) of vLLM's min_p (applied after top-p), -inf = off.
 template <class F>
-__device__ int sample_row(F lg, int V, int top_k, float top_p, uint64_t seed, uint32_t step, uint32_t rowid, float* red,
-                          float* scan, int* result) {
+__device__ int sample_row(F lg, int V, int top_k, float top_p, float minp_log, uint64_t seed, uint32_t step, uint32_t rowid,
+                          float* red, float* scan, int* result) {
     const int tid = threadIdx.x;
     if (top_k > 0 && top_k <= 256 && top_k < V) {                                        // the reference's default: top_k = 50
-        const int t = sample_row_topk(lg, V, top_k, top_p, seed, step, rowid, red);
+        const int t = sample_row_topk(lg, V, top_k, top_p, minp_log, seed, step, rowid, red);
         if (t >= 0) return t;                                                            // -1: outside its scope (block-uniform)
     }
-    const WarpStats w = row_warp_stats(lg, V, top_k, top_p, 1, red);                     // TopK -> TopP thresholds
+    WarpStats w = row_warp_stats(lg, V, top_k, top_p, 1, red);                           // TopK -> TopP thresholds
+    w.mthr = wp_minp_thr(w.mx, minp_log);                                                // -> min_p
     // multinomial over the survivors, in index order: per-thread contiguous ranges + block scan
     const int per = (V + SP_THREADS - 1) / SP_THREADS;
     const int beg = tid * per, end = min(beg + per, V);
@@ -355,7 +368,7 @@ __global__ __launch_bounds__(SP_THREADS) void sample_top_p_kernel(SampleArgs p) 
     const uint32_t* srow = p.seen ? p.seen + (size_t)blockIdx.x * p.seen_words : nullptr;
     const float invT = 1.0f / p.temperature;
     auto lg = [&](int i) { return rep_penalty(row[i], i, srow, p.penalty) * invT; };     // processors, then temperature
-    const int tok = sample_row(lg, p.V, p.top_k, p.top_p, p.seed, (uint32_t)p.step[0], (uint32_t)blockIdx.x, red, scan, &result);
+    const int tok = sample_row(lg, p.V, p.top_k, p.top_p, -INFINITY, p.seed, (uint32_t)p.step[0], (uint32_t)blockIdx.x, red, scan, &result);
     if (threadIdx.x == 0) p.out[blockIdx.x] = tok;
 }
 void launch_sample_top_p(const SampleArgs& a, hipStream_t st) {
@@ -400,7 +413,52 @@ void launch_finish_step(const FinishArgs& a, hipStream_t st) {
 // so the reference's row-0 stop (starvector_base.py:9-20: right for ONE request per generate call) becomes each request's
 // own stop.  The random stream of a slot depends on (its seed, its own step, row 0): a request produces the same tokens
 // as when it runs alone through sv_generate.
+// vLLM-mode slots (CbSlot::vllm, vLLM 0.5.5's sampler order) first rewrite their logits row in place -- logit_bias, the min_tokens
+// hold of eos and the stop ids, repetition over prompt + output ids, frequency and presence over the output counts -- and then
+// take the same selection as an HF slot (greedy argmax, or temperature -> top-k -> top-p -> min_p -> one draw) with the HF
+// processors off.  The logits buffer is the engine's own and the next lm_head overwrites it, so the rewrite is safe.
 // ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void cb_vllm_process(const CbStepArgs& p, const CbSlot& sl, int s, float* row) {
+    const int tid = threadIdx.x;
+    if (tid < sl.n_bias) {                                          // 1. logit_bias (distinct ids: checked at admit)
+        const CbBias& bb = p.bias[s];
+        row[bb.id[tid]] += bb.val[tid];
+    }
+    __syncthreads();
+    if (sl.step < sl.min_new) {                                     // 2. min_tokens: eos and every stop id -> -inf (after the bias)
+        if (tid == 0 && sl.eos >= 0) row[sl.eos] = -INFINITY;
+        if (tid >= 1 && tid <= sl.n_any) row[sl.any[tid - 1]] = -INFINITY;
+    }
+    __syncthreads();
+    const float rp = sl.penalty, fp = sl.frequency, pp = sl.presence;
+    if (rp == 1.0f && fp == 0.f && pp == 0.f) return;              // 3. penalties (-inf stays -inf through all three)
+    const uint32_t* srow = p.seen + (size_t)s * p.seen_words;
+    const uint16_t* crow = p.counts + (size_t)s * p.ld_counts;
+    for (int i = tid * 4; i < p.V; i += SP_THREADS * 4) {          // ld and ld_counts are multiples of 4: aligned vector accesses
+        float4 v = *reinterpret_cast<const float4*>(row + i);
+        const ushort4 c = *reinterpret_cast<const ushort4*>(crow + i);
+        const uint32_t bits = srow[i >> 5] >> (i & 31);
+        float a[4] = {v.x, v.y, v.z, v.w};
+        const float cn[4] = {(float)c.x, (float)c.y, (float)c.z, (float)c.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float l = a[e];
+            if ((bits >> e) & 1u) l = l > 0.f ? l / rp : l * rp;   // vLLM: repetition over prompt ids and output ids
+            l -= fp * cn[e];
+            l -= cn[e] > 0.f ? pp : 0.f;
+            a[e] = l;
+        }
+        v = make_float4(a[0], a[1], a[2], a[3]);
+        if (i + 3 < p.V) {
+            *reinterpret_cast<float4*>(row + i) = v;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) if (i + e < p.V) row[i + e] = a[e];
+        }
+    }
+    __syncthreads();
+}
+
 __global__ __launch_bounds__(SP_THREADS) void cb_step_kernel(CbStepArgs p) {
     __shared__ float red[SP_THREADS / 64];
     __shared__ float scan[SP_THREADS];
@@ -416,13 +474,16 @@ __global__ __launch_bounds__(SP_THREADS) void cb_step_kernel(CbStepArgs p) {
     if (!sl.live) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* row = p.logits + (size_t)b * p.ld;
-    const uint32_t* srow = (p.seen && sl.penalty > 0.f && sl.penalty != 1.0f) ? p.seen + (size_t)s * p.seen_words : nullptr;
-    const bool hold_eos = sl.step < sl.min_new;                     // MinLengthLogitsProcessor
+    const bool vl = sl.vllm != 0;
+    if (vl) cb_vllm_process(p, sl, s, const_cast<float*>(row));    // block-uniform; rewrites the row in place
+    const uint32_t* srow = (!vl && p.seen && sl.penalty > 0.f && sl.penalty != 1.0f) ? p.seen + (size_t)s * p.seen_words : nullptr;
+    const bool hold_eos = !vl && sl.step < sl.min_new;              // MinLengthLogitsProcessor
     int tok;
     if (sl.do_sample) {
         const float invT = 1.0f / sl.temperature;
+        const float minp_log = sl.min_p > 0.f ? __logf(sl.min_p) : -INFINITY;
         auto lg = [&](int i) { return (hold_eos && i == sl.eos) ? -INFINITY : rep_penalty(row[i], i, srow, sl.penalty) * invT; };
-        tok = sample_row(lg, p.V, sl.top_k, sl.top_p, sl.seed, (uint32_t)sl.step, 0u, red, scan, &result);
+        tok = sample_row(lg, p.V, sl.top_k, sl.top_p, minp_log, sl.seed, (uint32_t)sl.step, 0u, red, scan, &result);
     } else {
         float best = -INFINITY;
         int bi = 0x7fffffff;
@@ -460,6 +521,13 @@ __global__ __launch_bounds__(SP_THREADS) void cb_step_kernel(CbStepArgs p) {
     p.positions[s] += 1;
     if (srow) atomicOr(p.seen + (size_t)s * p.seen_words + (tok >> 5), 1u << (tok & 31));
     bool fin = tok == sl.eos || t + 1 >= sl.budget;
+    if (vl) {                                                       // the slot's only writer: plain read-modify-write of its count
+        uint16_t* c = p.counts + (size_t)s * p.ld_counts + tok;
+        *c = (uint16_t)(*c + 1);
+        atomicOr(p.seen + (size_t)s * p.seen_words + (tok >> 5), 1u << (tok & 31));
+        for (int i = 0; i < sl.n_any; ++i)
+            if (tok == p.slots[s].any[i]) fin = true;
+    }
     if (!fin && sl.n_stop > 0 && t + 1 >= sl.n_stop) {
         fin = true;
         for (int i = 0; i < sl.n_stop; ++i)

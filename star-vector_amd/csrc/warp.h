@@ -10,6 +10,8 @@
 //   v0   : smallest probability whose at-or-below mass exceeds 1 - top_p, probabilities renormalised over the top-k
 //          survivors                          -> TopP keeps p >= v0
 //   smin : the min_tokens_to_keep-th largest score (1 for sampling, 2 under beam search) -> always kept
+//   mthr : vLLM's min_p, applied AFTER top-p: keep exp(s - mx) >= min_p, i.e. s >= mx + log(min_p) (-inf = off: every path
+//          without min_p keeps exactly what it kept before)
 #pragma once
 #include "common.h"
 
@@ -17,7 +19,13 @@ namespace sv {
 
 #define WP_THREADS 1024
 
-struct WarpStats { float kth, mx, invZ, v0, smin; };
+struct WarpStats { float kth, mx, invZ, v0, smin, mthr = -INFINITY; };
+
+// min_p's threshold in scaled-score space; the 2^-18 relative slack of wp_keep's top-p test, as a log: a token that close to the
+// threshold is kept.  minp_log = log(min_p), -inf when min_p is off.
+__device__ __forceinline__ float wp_minp_thr(float mx, float minp_log) {
+    return minp_log > -INFINITY ? mx + minp_log - 3.8147e-6f : -INFINITY;
+}
 
 __device__ __forceinline__ uint32_t wp_key(float f) {          // order-preserving float -> uint
     const uint32_t u = __float_as_uint(f);
@@ -55,7 +63,7 @@ __device__ __forceinline__ float wp_block_max(float v, float* red) {
 // second place may round one ulp lower (different fma contraction around __expf), which would drop exactly that token.
 // A relative slack of 2^-18 restores it; a token that close to the threshold is inside HF's own float-cumsum noise.
 __device__ __forceinline__ bool wp_keep(const WarpStats& w, float s) {
-    if (!(s >= w.kth)) return false;
+    if (!(s >= w.kth) || !(s >= w.mthr)) return false;
     return __expf(s - w.mx) * w.invZ >= w.v0 * 0.99999619f || s >= w.smin;
 }
 __device__ __forceinline__ float wp_prob(const WarpStats& w, float s) { return __expf(s - w.mx) * w.invZ; }

@@ -288,27 +288,17 @@ class HipEngine:
         """Prompt pass of len(requests) new requests (inputs_embeds [n, S0, D] bf16, equal prompt length) into free slots while
         the live slots keep their KV cache; samples their first token.  Each request: dict(max_new_tokens, do_sample=False,
         temperature=1, top_p=1, top_k=0, seed=0, eos_token_id=0, pad_token_id=0, stop_ids=None, repetition_penalty=1,
-        min_new_tokens=0).  Returns the slot ids.  Raises StarVectorBusy when slots or KV pages are short."""
+        min_new_tokens=0), plus the vLLM-semantics keys (include/starvector_hip.h, ABI 9; they need semantics="vllm"):
+        presence_penalty=0, frequency_penalty=0, min_p=0, prompt_ids=None, logit_bias=None ({id: bias}), stop_any_ids=None.
+        Returns the slot ids.  Raises StarVectorBusy when slots or KV pages are short."""
         x = _need(inputs_embeds, torch.bfloat16, "inputs_embeds")
         n, S0, D = x.shape
         if D != self.cfg.hidden or n != len(requests):
             raise ValueError("inputs_embeds / requests mismatch")
-        arr = (_lib.SvCbRequest * n)()
-        for i, r in enumerate(requests):
-            stops = list(r.get("stop_ids") or [])
-            if len(stops) > 16:
-                raise ValueError("stop sequence longer than 16 ids")
-            a = arr[i]
-            a.do_sample = int(bool(r.get("do_sample", False))); a.temperature = float(r.get("temperature", 1.0))
-            a.top_p = float(r.get("top_p", 1.0)); a.top_k = int(r.get("top_k", 0) or 0)
-            a.seed = int(r.get("seed", 0)) & 0xFFFFFFFFFFFFFFFF; a.max_new_tokens = int(r["max_new_tokens"])
-            a.eos_token_id = int(r.get("eos_token_id", 0)); a.pad_token_id = int(r.get("pad_token_id", 0))
-            a.min_new_tokens = int(r.get("min_new_tokens", 0) or 0); a.repetition_penalty = float(r.get("repetition_penalty", 1.0) or 1.0)
-            a.n_stop = len(stops)
-            for k, t in enumerate(stops):
-                a.stop_ids[k] = int(t)
+        arr, keep = cb_requests(requests)
         slots = (C.c_int32 * n)()
         check(self.lib.sv_cb_admit(self._h, _ptr(x), n, S0, arr, slots, _stream()), "sv_cb_admit")
+        del keep
         return list(slots)
 
     def cb_step(self, n_steps: int = 8) -> int:
@@ -443,6 +433,55 @@ class HipEngine:
         res["event_pair_overhead_ms"] = buf[22]
         res["first_to_last_event_ms"] = buf[23]
         return res
+
+
+def cb_requests(requests: Sequence[dict]):
+    """The sv_cb_request array of `HipEngine.cb_admit`'s request dicts, and the host arrays its pointers refer to (keep them alive
+    for the duration of the call)."""
+    n = len(requests)
+    arr = (_lib.SvCbRequest * n)()
+    keep = []
+    for i, r in enumerate(requests):
+        stops = list(r.get("stop_ids") or [])
+        if len(stops) > 16:
+            raise ValueError("stop sequence longer than 16 ids")
+        a = arr[i]
+        a.do_sample = int(bool(r.get("do_sample", False))); a.temperature = float(r.get("temperature", 1.0))
+        a.top_p = float(r.get("top_p", 1.0)); a.top_k = int(r.get("top_k", 0) or 0)
+        a.seed = int(r.get("seed", 0)) & 0xFFFFFFFFFFFFFFFF; a.max_new_tokens = int(r["max_new_tokens"])
+        a.eos_token_id = int(r.get("eos_token_id", 0)); a.pad_token_id = int(r.get("pad_token_id", 0))
+        a.min_new_tokens = int(r.get("min_new_tokens", 0) or 0); a.repetition_penalty = float(r.get("repetition_penalty", 1.0) or 1.0)
+        a.n_stop = len(stops)
+        for k, t in enumerate(stops):
+            a.stop_ids[k] = int(t)
+        sem = r.get("semantics", "hf")
+        if sem not in ("hf", "vllm", 0, 1):
+            raise ValueError(f"semantics must be 'hf' or 'vllm', not {sem!r}")
+        a.semantics = 1 if sem in ("vllm", 1) else 0
+        a.presence_penalty = float(r.get("presence_penalty", 0.0) or 0.0)
+        a.frequency_penalty = float(r.get("frequency_penalty", 0.0) or 0.0)
+        a.min_p = float(r.get("min_p", 0.0) or 0.0)
+        prompt = [int(t) for t in (r.get("prompt_ids") or [])]
+        if prompt:
+            buf = (C.c_int32 * len(prompt))(*prompt)
+            keep.append(buf)
+            a.n_prompt_ids, a.prompt_ids = len(prompt), C.cast(buf, C.POINTER(C.c_int32))
+        bias = dict(r.get("logit_bias") or {})
+        if len(bias) > _lib.CB_MAX_LOGIT_BIAS:
+            raise ValueError(f"{len(bias)} logit_bias entries (at most {_lib.CB_MAX_LOGIT_BIAS})")
+        if bias:
+            ids = (C.c_int32 * len(bias))(*[int(k) for k in bias])
+            vals = (C.c_float * len(bias))(*[float(v) for v in bias.values()])
+            keep += [ids, vals]
+            a.n_logit_bias = len(bias)
+            a.logit_bias_ids, a.logit_bias_values = C.cast(ids, C.POINTER(C.c_int32)), C.cast(vals, C.POINTER(C.c_float))
+        anys = [int(t) for t in (r.get("stop_any_ids") or [])]
+        if len(anys) > _lib.CB_MAX_STOP_ANY:
+            raise ValueError(f"{len(anys)} stop_any_ids (at most {_lib.CB_MAX_STOP_ANY})")
+        a.n_stop_any = len(anys)
+        for k, t in enumerate(anys):
+            a.stop_any_ids[k] = t
+    return arr, keep
 
 
 def token_callback(on_tokens):
@@ -690,6 +729,33 @@ def op_argmax(logits):
     out = torch.empty(B, dtype=torch.int32, device=logits.device)
     check(lib.sv_op_argmax(_ptr(logits), B, V, V, _ptr(out), _stream()))
     return out
+
+
+def op_cb_select(logits, requests: Sequence[dict], history=None):
+    """The continuous-batching selection (cb_step_kernel) on caller-given fp32 rows [B, V]: row b is request requests[b] (the
+    `cb_admit` dict) after the output ids history[b] (a list; its length is the step).  Returns int32 [B] on the host."""
+    lib = _lib.load()
+    logits = _need(logits, torch.float32, "logits")
+    B, V = logits.shape
+    ld = (V + 3) // 4 * 4
+    if ld != V:
+        pad = torch.full((B, ld), -float("inf"), dtype=torch.float32, device=logits.device)
+        pad[:, :V] = logits
+        logits = pad
+    history = [list(map(int, h)) for h in (history or [[]] * B)]
+    if len(history) != B or len(requests) != B:
+        raise ValueError("one request and one history per row")
+    ld_hist = max(1, max(len(h) for h in history))
+    hist = (C.c_int32 * (B * ld_hist))()
+    for b, h in enumerate(history):
+        for t, x in enumerate(h):
+            hist[b * ld_hist + t] = x
+    lens = (C.c_int32 * B)(*[len(h) for h in history])
+    arr, keep = cb_requests(requests)
+    out = (C.c_int32 * B)()
+    check(lib.sv_op_cb_select(_ptr(logits), B, V, ld, arr, hist, ld_hist, lens, out, _stream()), "sv_op_cb_select")
+    del keep
+    return torch.tensor(list(out), dtype=torch.int32)
 
 
 def op_preprocess_image(pixels: torch.Tensor, size: int, mean, std, recipe: str = "starvector") -> torch.Tensor:
