@@ -81,6 +81,10 @@ int  sv_debug_set_col_tiles(int32_t col_tiles);
  *                             count: the default), 2 / 3 = that kernel's two-blocks-per-CU / one-block-per-CU form wherever the shape allows.
  *                             SV_EXP bits 131072 / 262144 / 524288 select 0 / 2 / 3 at sv_create and in sv_debug_set_exp */
 int  sv_debug_set_skinny_form(int32_t form);
+/*   sv_debug_tailsplit_launches  how many times, process-wide since the library was loaded, a decode GEMM took the tail split (gemm.hip
+ *                             gemm_skinny_tailsplit_kernel: StarVector-8B's c_fc at <= 32 rows); counted on the host at launch (a captured
+ *                             graph counts once, at capture).  Lets a test prove which kernel ran. */
+int  sv_debug_tailsplit_launches(int64_t* count);
 /*   sv_debug_set_gemm_form    process-wide: every big-M GEMM launch takes ONE form -- 0 = 128x128 tiles, 1 = 256x256 tiles (rows not peeled),
      2 = 256x256 tiles + the row remainder over a multiple of 256 through the one-wave-per-tile tail kernel; -1 = the tuned choice (default).
      The forms give the same bits; the tests compare them through this switch. */

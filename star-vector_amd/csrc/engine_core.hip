@@ -519,7 +519,7 @@ extern "C" int sv_create(const sv_config* cfg, sv_engine** out) {
     e->d_nemit = e->d_step + 2;
     e->d_bad = e->d_step + 3;         // raised by the selection kernels when a row has no finite logit
     A(dalloc(e, &e->d_stop, 64));
-    A(dalloc(e, &e->tail_ws, (size_t)SV_TAIL_TILES * 4 * 16 * 64));
+    A(dalloc(e, &e->tail_ws, (size_t)SV_TAIL_TILES * 8 * 16 * 64));
     A(dalloc(e, &e->tail_cnt, (size_t)SV_TAIL_TILES));          // zeroed: the tickets re-arm themselves
     A(dalloc(e, &e->fin_cnt, 64));                               // zeroed: SkinnyArgs::fin_cnt
 

@@ -229,6 +229,12 @@ extern "C" int sv_debug_set_col_tiles(int32_t col_tiles) {
     return 0;
 }
 
+extern "C" int sv_debug_tailsplit_launches(int64_t* count) {
+    if (!count) return fail(SV_EINVAL, "sv_debug_tailsplit_launches: null argument");
+    *count = (int64_t)tailsplit_launches();
+    return 0;
+}
+
 extern "C" int sv_debug_set_skinny_form(int32_t form) {
     if (form < 0 || form > 3) return fail(SV_EINVAL, "sv_debug_set_skinny_form: 0..3");
     set_mt2x(form);
@@ -593,7 +599,7 @@ extern "C" int sv_op_linear_skinny_epi(const void* x, const void* W, const void*
         a.out_mode = SK_OUT_PACKED_ACT; a.bias = (const bf16_t*)bias; a.act = act; a.out_xp = oxp; a.out_KS = Npad / 16;
         // the engine's scratch for the tiles beyond the first round of blocks (gemm_skinny_tailsplit_kernel; taken only where launch_gemm_skinny's rule says so)
         float* tws; unsigned* tcnt;
-        SVCHECK(tmp.get(&tws, (size_t)SV_TAIL_TILES * 4 * 16 * 64));
+        SVCHECK(tmp.get(&tws, (size_t)SV_TAIL_TILES * 8 * 16 * 64));
         SVCHECK(tmp.get(&tcnt, (size_t)SV_TAIL_TILES));
         HIPCHECK(hipMemsetAsync(tcnt, 0, (size_t)SV_TAIL_TILES * sizeof(unsigned), st));
         a.tail_ws = tws; a.tail_cnt = tcnt;

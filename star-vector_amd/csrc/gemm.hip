@@ -1762,62 +1762,63 @@ __global__ __launch_bounds__(512) void gemm_head_persist_kernel(const bf16_t* Wp
 // gemm_skinny_tailsplit_kernel (round 6, fourth session): the column tiles of a whole-K skinny GEMM that do not fit the first round of blocks.
 // StarVector-8B's c_fc at <= 32 rows is 576 one-tile blocks on 512 block slots (two 8-wave blocks per CU): the second "round" is 64 blocks that each stream
 // 288 KiB alone (~30 GB/s per lone CU): ~10 of the launch's 36 us for 11 % of its bytes (rocprof by grid, profiles/rocprof_r06_8b_im2svg_by_grid.csv).
-// Here the first 512 tiles stay one launch of the ordinary kernel and the T left-over tiles go to 4 T blocks of this one: block (tile, q) takes the q-th
-// quarter of K (8 waves x KS / 32 k-steps, all requested up front), reduces across its waves as the ordinary kernel does, leaves its 32 x 32 fp32 partial in
-// the engine's scratch through write-through stores and draws an arrival ticket; the last of the four sums the partials in q order and runs the epilogue
-// (bias + activation -> packed activations).  The hand-off is the decode attention's (sc1 stores, every wave drains, one relaxed agent-scope ticket, sc1 loads
-// in the last arriver, ticket re-armed): no fences, nobody waits.  The sum order of those tiles' columns is (quarter, wave) instead of wave: other roundings
-// than the one-tile kernel for T / n_tiles of the columns, the same for every batch <= 32 (one kernel, one order: batch-independent).
+// Here the first 2 x CUs tiles stay one launch of the ordinary kernel and the T left-over tiles go to 4 T two-wave blocks of this one.  The K split is the
+// one-tile kernel's own (gemm_skinny_kernel<8>): 8 ranges of KS / 8 k-steps, each ONE MFMA chain started from zero and run in k order by one wave --
+// block (tile, q) runs ranges 2q and 2q + 1.  Every wave leaves its raw accumulator (the one-tile kernel's red[wave]) in the engine's scratch through
+// write-through stores, the block draws an arrival ticket, and the last of the four sums the 8 ranges in range order (t = r0; t += r1; ... t += r7: the
+// one-tile kernel's cross-wave sum) and runs the same epilogue (bias + activation -> packed activations).  Same k ranges, same MFMA chains, same sum
+// order: the one-tile kernel's bits for every column, whatever the CU count -- so a row gets the same bits at <= 32 rows (this split) as at 33..64
+// (the two-row-tile kernels, bit-identical to the one-tile kernel).  The hand-off is the decode attention's (sc1 stores, every wave drains, one relaxed
+// agent-scope ticket, sc1 loads in the last arriver, ticket re-armed): no fences, nobody waits.
 // ------------------------------------------------------------------------------------------------
-template <int KPW>                                           // k-steps per wave (KS / 32): 9 for StarVector-8B
-__global__ __launch_bounds__(512) void gemm_skinny_tailsplit_kernel(const bf16_t* Wp_, const bf16_t* xp_, int KS_, int tile0_, int flags_, SkinnyArgs p_unused) {
-    constexpr int WAVES = 8, RPW = 2;
-    extern __shared__ __attribute__((aligned(16))) char sk_smem[];
-    float (*red)[16][64] = reinterpret_cast<float (*)[16][64]>(sk_smem);          // [WAVES][16][64]
+template <int KPW>                                           // k-steps per range (KS / 8): 36 for StarVector-8B
+__global__ __launch_bounds__(128) void gemm_skinny_tailsplit_kernel(const bf16_t* Wp_, const bf16_t* xp_, int KS_, int tile0_, int flags_, SkinnyArgs p_unused) {
+    constexpr int RANGES = 8, RPW = 8;                       // RPW: accumulator rows each of the last arriver's two waves finishes
     __shared__ int last_s;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m = lane & 31, half = lane >> 5;
-    const int tt = blockIdx.x >> 2, q = blockIdx.x & 3;        // left-over tile, K quarter
+    const int tt = blockIdx.x >> 2, q = blockIdx.x & 3;        // left-over tile, pair of K ranges
+    const int g = 2 * q + wave;                                // this wave's K range = wave g of the one-tile kernel
     const int nt = tile0_ + tt, KS = KS_;
-    const int ks0 = q * (KS >> 2) + wave * KPW;
+    const int ks0 = g * KPW;
     (void)flags_;
     const u32x4* wptr = reinterpret_cast<const u32x4*>(Wp_) + ((size_t)nt * KS + ks0) * 64 + lane;
     const u32x4* xptr = reinterpret_cast<const u32x4*>(xp_) + (size_t)ks0 * 64 + lane;
-    u32x4 w[KPW], x[KPW];
+    // The range's 36 KiB of weights are all requested up front (144 VGPRs); the activations (L2-resident, read by every tile) come in four chunks of
+    // KPW / 4 k-steps through two register buffers, the next chunk requested while the current one is consumed: 216 VGPRs, no spills.  The
+    // scheduling barriers keep that order (without them the scheduler sinks every load next to its MFMA: ~4 k-steps in flight per wave).
+    constexpr int CX = KPW / 4;
+    static_assert(KPW % 4 == 0, "four activation chunks per range");
+    u32x4 w[KPW], xc[2][CX];
+    auto load_x = [&](u32x4* dst, int c) {
+#pragma unroll
+        for (int u = 0; u < CX; ++u) dst[u] = xptr[(size_t)(c * CX + u) * 64];
+    };
+    load_x(xc[0], 0);
 #pragma unroll
     for (int u = 0; u < KPW; ++u) w[u] = __builtin_nontemporal_load(wptr + (size_t)u * 64);
-#pragma unroll
-    for (int u = 0; u < KPW; ++u) x[u] = xptr[(size_t)u * 64];
+    load_x(xc[1], 1);
+    __builtin_amdgcn_sched_barrier(0);
     SkinnyArgs p = sv_late_args<SkinnyArgs>(offsetof(SkinnyKernarg, p));
-    float bias_d[RPW];
-    sk_bias<RPW>(p, bias_d, wave * RPW, nt, half);
-    sk_settle<RPW>(bias_d);
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
-    for (int u = 0; u < KPW; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag4(w[u]), as_frag4(x[u]), acc, 0, 0, 0);
+    for (int c = 0; c < 4; ++c) {                            // one MFMA chain over the range, k order
 #pragma unroll
-    for (int r = 0; r < 16; ++r) red[wave][r][lane] = acc[r];
-    __syncthreads();
-    float v[RPW];
-#pragma unroll
-    for (int i = 0; i < RPW; ++i) {
-        const int r = wave * RPW + i;
-        float t = red[0][r][lane];
-#pragma unroll
-        for (int g = 1; g < WAVES; ++g) t += red[g][r][lane];
-        v[i] = t;
+        for (int u = 0; u < CX; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag4(w[c * CX + u]), as_frag4(xc[c & 1][u]), acc, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (c + 2 < 4) load_x(xc[c & 1], c + 2);
+        __builtin_amdgcn_sched_barrier(0);
     }
-    // partial of (tile, quarter): [16 accumulator rows][64 lanes] floats, write-through; every wave drains, then one ticket per block
-    const unsigned bytes = (unsigned)SV_TAIL_TILES * 4u * 16u * 64u * 4u;
+    // raw accumulator of (tile, range): [16 accumulator rows][64 lanes] floats, write-through; every wave drains, then one ticket per block
+    const unsigned bytes = (unsigned)SV_TAIL_TILES * (unsigned)RANGES * 16u * 64u * 4u;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(p.tail_ws, 0, bytes, 0x00020000);
 #pragma unroll
-    for (int i = 0; i < RPW; ++i) {
-        const int r = wave * RPW + i;
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[i]), rs, (int)(((((unsigned)tt * 4u + (unsigned)q) * 16u + (unsigned)r) * 64u + (unsigned)lane) * 4u), 0, 16);     // sc1
-    }
+    for (int r = 0; r < 16; ++r)
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[r]), rs,
+                                              (int)(((((unsigned)tt * RANGES + (unsigned)g) * 16u + (unsigned)r) * 64u + (unsigned)lane) * 4u), 0, 16);     // sc1
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0) {
@@ -1826,21 +1827,31 @@ __global__ __launch_bounds__(512) void gemm_skinny_tailsplit_kernel(const bf16_t
     }
     __syncthreads();
     if (!last_s) return;
-    float part[RPW][4];
+    float part[RPW][RANGES];
 #pragma unroll
     for (int i = 0; i < RPW; ++i) {
         const int r = wave * RPW + i;
 #pragma unroll
-        for (int g = 0; g < 4; ++g)
-            part[i][g] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)(((((unsigned)tt * 4u + (unsigned)g) * 16u + (unsigned)r) * 64u + (unsigned)lane) * 4u), 0, 16));   // sc1: L1 bypass
+        for (int h = 0; h < RANGES; ++h)
+            part[i][h] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)(((((unsigned)tt * RANGES + (unsigned)h) * 16u + (unsigned)r) * 64u + (unsigned)lane) * 4u), 0, 16));   // sc1: L1 bypass
     }
+    float bias_d[RPW];
+    sk_bias<RPW>(p, bias_d, wave * RPW, nt, half);
+    float v[RPW];
 #pragma unroll
-    for (int i = 0; i < RPW; ++i) v[i] = ((part[i][0] + part[i][1]) + part[i][2]) + part[i][3];          // quarter order
+    for (int i = 0; i < RPW; ++i) {
+        float t = part[i][0];
+#pragma unroll
+        for (int h = 1; h < RANGES; ++h) t += part[i][h];       // range (= the one-tile kernel's wave) order
+        v[i] = t;
+    }
     if (tid == 0) __hip_atomic_store(p.tail_cnt + tt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-arm
     sk_store<RPW>(p, v, bias_d, wave * RPW, nt, 0, 0, m, half);
 }
-std::atomic<int> g_tailsplit{1};
+std::atomic<int> g_tailsplit{0};     // off by default: the bit-identical split ties with the one launch (profiles/tailsplit_r06_ab.log); SV_TAILSPLIT=1 = on
 void set_tailsplit(int on) { g_tailsplit = on; }
+std::atomic<long long> g_tailsplit_launches{0};     // host-side count of tail-split launches (sv_debug_tailsplit_launches)
+long long tailsplit_launches() { return g_tailsplit_launches.load(std::memory_order_relaxed); }
 
 std::atomic<int> g_head_persist{1};     // 1: the lm_head of a one-row-tile step through gemm_head_persist_kernel where it applies; 0: the one-tile kernel (A/B)
 void set_head_persist(int on) { g_head_persist = on; }
@@ -2774,7 +2785,7 @@ static bool launch_skinny_tailsplit(const SkinnyArgs& a, hipStream_t st) {
     if (!on || !a.tail_ws || !a.tail_cnt) return false;
     if (a.out_mode != SK_OUT_PACKED_ACT || a.MT != 1 || a.Wq || a.fold_c1 || a.splitk != 1) return false;
     const int KS = a.K / 16, n_tiles = a.Npad / 32;
-    if (KS % 32 || KS / 32 != 9 || skinny_waves(a.Npad, KS, 1) != 8) return false;      // the one instantiation: 9 k-steps per wave and quarter (K = 4608)
+    if (KS != 8 * 36 || skinny_waves(a.Npad, KS, 1) != 8) return false;      // the one instantiation: the one-tile kernel's 8 ranges of 36 k-steps (K = 4608)
     static int cus = 0;
     if (!cus) {
         int dev = 0; hipDeviceProp_t pr;
@@ -2784,7 +2795,8 @@ static bool launch_skinny_tailsplit(const SkinnyArgs& a, hipStream_t st) {
     const int slots = 2 * cus, T = n_tiles - slots;           // two 8-wave blocks of the ordinary kernel per CU
     if (T <= 0 || T > SV_TAIL_TILES || 4 * T > slots) return false;
     gemm_skinny_kernel<8, false><<<dim3(slots, 1, 1), 512, skinny_smem(8), st>>>(a.Wp, a.xp, KS, KS, 0, a);
-    gemm_skinny_tailsplit_kernel<9><<<4 * T, 512, 8 * 16 * 64 * 4, st>>>(a.Wp, a.xp, KS, slots, 0, a);
+    gemm_skinny_tailsplit_kernel<36><<<4 * T, 128, 0, st>>>(a.Wp, a.xp, KS, slots, 0, a);
+    g_tailsplit_launches.fetch_add(1, std::memory_order_relaxed);
     return true;
 }
 
@@ -2792,7 +2804,7 @@ void launch_gemm_skinny(const SkinnyArgs& a, hipStream_t st) {
     if (launch_head_persist(a, st)) return;                      // the lm_head of a <= 32-row step: one round of blocks over several column tiles each
     if (launch_gemm_skinny_mt2(a, st)) return;                  // 33..64 rows: two row tiles per block, weights streamed once
     if (a.Wq && launch_gemm_skinny_fp8(a, st)) return;       // fp8 weights: its own kernel (falls through if unsupported)
-    if (launch_skinny_tailsplit(a, st)) return;                 // whole-K tiles beyond the first round of blocks: split four ways along K (StarVector-8B's c_fc)
+    if (launch_skinny_tailsplit(a, st)) return;                 // whole-K tiles beyond the first round of blocks: the 8 K ranges spread over 4 blocks (StarVector-8B's c_fc)
     dim3 grid(a.Npad / 32, a.splitk, a.MT);
     switch (skinny_waves(a.Npad, a.K / 16, a.splitk)) {
         case 16: launch_sk<16>(a, grid, st); break;

@@ -53,6 +53,7 @@ void launch_gemm(const GemmArgs& a, hipStream_t st);
 // one fixed configuration (kernel256: 0 = 128^2 tiles, 1 = 256^2; peel: the row remainder over a multiple of 256 in its own launch), no tuning
 void launch_gemm_fixed(const GemmArgs& a, int kernel256, int peel, hipStream_t st);
 void set_mt2x(int on);                // 33..64-row decode GEMMs: 1 = activations through a wave-private LDS ring (gemm_skinny_mt2x_kernel, default), 0 = both operands in registers
+long long tailsplit_launches();        // host-side count of gemm_skinny_tailsplit_kernel launches since load (sv_debug_tailsplit_launches)
 void set_gemm_form(int form);         // -1: tuned (default); 0 / 1: every big-M launch takes that form, rows not peeled
 // what launch_gemm decides for a shape (host arithmetic only; tail_on: 0 never peel, 1 cost model, 2 always)
 struct GemmPlan { int peel, tail_rows, tail_by_tiles, main_256; double est_us; };
@@ -88,9 +89,10 @@ struct SkinnyArgs {
     // F32 mode (lm_head), one-row-tile bf16 kernel only: a buffer the launch fills with the 0xFFFF'FFFF pattern through write-through
     // stores, 16 bytes per thread (the LayerNorm output buffer of the fused row-update + c_attn launch of the NEXT decode step)
     void* poison; unsigned poison_bytes;
-    // PACKED_ACT, one row tile, whole K (StarVector-8B's c_fc: 576 column tiles on 512 block slots): the tiles beyond the first round of blocks are split four
-    // ways along K by a second launch whose blocks leave fp32 partials here and elect a last arriver through `tail_cnt` (gemm_skinny_tailsplit_kernel).
-    // Per-engine scratch: [SV_TAIL_TILES][4][16][64] floats + [SV_TAIL_TILES] zeroed counters; nullptr: off.
+    // PACKED_ACT, one row tile, whole K (StarVector-8B's c_fc: 576 column tiles on 512 block slots): the tiles beyond the first round of blocks go to a second
+    // launch that runs the one-tile kernel's 8 K ranges on 4 blocks per tile; every range leaves its raw fp32 accumulator here and a last arriver elected
+    // through `tail_cnt` sums them in range order (gemm_skinny_tailsplit_kernel).
+    // Per-engine scratch: [SV_TAIL_TILES][8][16][64] floats + [SV_TAIL_TILES] zeroed counters; nullptr: off.
     float* tail_ws; unsigned* tail_cnt;
     // The step's bookkeeping (finish_step_kernel) folded into the lm_head launch of a greedy step whose selection is folded already (`amax`; persistent-block
     // kernel only): every block drains its key atomics and draws a ticket from `fin_cnt` (zeroed, re-armed by the last arriver); the last block's first wave

@@ -623,6 +623,13 @@ def set_op_col_tiles(col_tiles: int) -> None:
     check(_lib.load().sv_debug_set_col_tiles(int(col_tiles)))
 
 
+def tailsplit_launches() -> int:
+    """Process-wide count of tail-split launches (StarVector-8B's c_fc at <= 32 rows; sv_debug_tailsplit_launches)."""
+    n = C.c_int64(0)
+    check(_lib.load().sv_debug_tailsplit_launches(C.byref(n)), "sv_debug_tailsplit_launches")
+    return n.value
+
+
 def op_linear_skinny(x, W, bias=None, splitk=1):
     lib = _lib.load()
     x = _need(x, torch.bfloat16, "x"); W = _need(W, torch.bfloat16, "W")
