@@ -239,6 +239,30 @@ int  sv_decode_step(sv_engine* e, const int32_t* dev_tokens, int32_t B, float* d
  * columns are left untouched.  Blocks until generation has finished (polls a device flag). */
 int  sv_generate(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const sv_sampling* sp,
                  int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream);
+
+/* Per-step outputs of a generate call (HF return_dict_in_generate with output_scores / output_logits, transformers 4.49
+ * generation/utils.py _sample and _beam_search).  rows = batch for greedy / sampling, batch * num_beams for beam search; step t
+ * of row r lives at slab[(t * rows + r) * ld].  Only the first *n_generated steps are written; the rest are left untouched.
+ *   dev_logits   raw fp32 logits of each step, before any processor (the bf16-rounded values of the lm_head)
+ *   dev_scores   greedy / sampling: RepetitionPenalty -> MinLength hold -> (do_sample) s / temperature, TopK, TopP with the
+ *                removed tokens at -inf;  beam search: log_softmax -> RepetitionPenalty -> MinLength -> (beam-sample) the warpers
+ *                with min_tokens_to_keep = 2: the processed log-probs the scorer ranks
+ *   host_sequences_scores   [batch]: the best hypothesis' length-penalised score (beam search only)
+ *   host_beam_indices       [batch][max_new]: the flat row (b * num_beams + beam) of step t's scores the hypothesis took its
+ *                           token from, -1 after the hypothesis ends (beam search only)
+ * Every pointer may be NULL.  Capturing costs 2 x rows x vocab fp32 stores per decode step; with the slabs NULL no extra kernel runs. */
+typedef struct sv_generate_outputs {
+    float*   dev_scores;             /* [max_new][rows][ld] fp32, or NULL */
+    float*   dev_logits;             /* [max_new][rows][ld] fp32, or NULL */
+    int64_t  ld;                     /* >= vocab */
+    float*   host_sequences_scores;  /* [batch], beam search only, or NULL */
+    int64_t* host_beam_indices;      /* [batch][max_new], beam search only, or NULL */
+} sv_generate_outputs;
+
+/* sv_generate with per-step outputs; sv_generate(...) == sv_generate_ex(..., outs = NULL, ...).  SV_EINVAL for ld < vocab with a
+ * slab, and for the beam-only pointers without num_beams > 1. */
+int  sv_generate_ex(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const sv_sampling* sp,
+                    const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream);
 /* ---- continuous batching (the reference worker's 5 concurrent requests, serve/model_worker.py:161-172,
  * 216-229, as ONE decode loop).  Every row ("slot") of the engine's batch is an independent request: own sampling parameters,
  * budget, EOS, stop sequence (the reference's row-0 stop, starvector_base.py:9-20, is right for one request per generate call

@@ -74,6 +74,14 @@ class SvBeamConfig(C.Structure):
     ]
 
 
+class SvGenerateOutputs(C.Structure):
+    # sv_generate_ex: per-step outputs (HF output_scores / output_logits, beam search's sequences_scores / beam_indices)
+    _fields_ = [
+        ("dev_scores", C.c_void_p), ("dev_logits", C.c_void_p), ("ld", C.c_int64),
+        ("host_sequences_scores", C.POINTER(C.c_float)), ("host_beam_indices", C.POINTER(C.c_int64)),
+    ]
+
+
 _P = C.c_void_p
 _I = C.c_int32
 _F = C.c_float
@@ -103,6 +111,7 @@ PRODUCT_PROTOTYPES = {
     "sv_forward_logits": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "sv_decode_step": (_I, [_P, _P, _I, _P, _P]),
     "sv_generate": (_I, [_P, _P, _I, _I, C.POINTER(SvSampling), _P, C.POINTER(_I), _P]),
+    "sv_generate_ex": (_I, [_P, _P, _I, _I, C.POINTER(SvSampling), C.POINTER(SvGenerateOutputs), _P, C.POINTER(_I), _P]),
     "sv_cb_admit": (_I, [_P, _P, _I, _I, C.POINTER(SvCbRequest), C.POINTER(_I), _P]),
     "sv_cb_step": (_I, [_P, _I, C.POINTER(_I), _P]),
     "sv_cb_poll": (_I, [_P, C.POINTER(_I), C.POINTER(_I), _I]),

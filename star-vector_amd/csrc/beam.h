@@ -11,6 +11,8 @@
 
 namespace sv {
 
+struct CaptureDesc;      // kernels.h: the caller's output slabs of sv_generate_ex
+
 #define BM_SPLIT 8       // a logits row is scanned by this many blocks (one CU streams only ~25 GB/s)
 #define BM_MAXNB 8       // num_beams <= 8
 #define BM_MAXK 16       // candidates kept per request = 2 * num_beams (one EOS id)
@@ -62,13 +64,18 @@ struct BeamScorer {
     bool own_scalars = false;
     std::vector<void*> allocs;
     float* h_lenpow = nullptr;
+    // sv_generate_ex: when set, every step also writes its raw rows and processed log-probs into the slabs the descriptor names
+    const CaptureDesc* cap = nullptr;
+    float cap_temp = 1.f;           // beam-sample: the temperature the captured log-probs are divided by (HF's warper)
 
     // ext_*: engine-owned buffers to drive (nullptr: the scorer allocates its own)
     int init(const BeamConfig& cfg, int32_t* ext_cur_tok, int32_t* ext_positions, int32_t* ext_step, int32_t* ext_done);
     int reset(hipStream_t st);                                      // initial search state
     void enqueue_step(const float* logits, int ld, int logit_div, hipStream_t st);
-    // best hypothesis per request: tokens [B][max_new] (filled with pad-or-eos), common length L, scores [B]
-    int finalize(hipStream_t st, std::vector<int64_t>& tokens, int& L, std::vector<float>& scores);
+    // best hypothesis per request: tokens [B][max_new] (filled with pad-or-eos), common length L, scores [B]; beam_idx (optional):
+    // [B][max_new], the flat row (b * nb + beam) each token of the hypothesis was chosen from, -1 after its end
+    int finalize(hipStream_t st, std::vector<int64_t>& tokens, int& L, std::vector<float>& scores,
+                 std::vector<int64_t>* beam_idx = nullptr);
     void destroy();
     bool matches(const BeamConfig& o) const {
         return R > 0 && c.B == o.B && c.nb == o.nb && c.V == o.V && c.max_new == o.max_new;

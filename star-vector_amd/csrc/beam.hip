@@ -158,6 +158,46 @@ __global__ __launch_bounds__(WP_THREADS) void beam_row_warp_kernel(BeamDev p) {
     if (threadIdx.x == 0) { o[0] = w.kth; o[1] = w.mx; o[2] = w.invZ; o[3] = w.v0; o[4] = w.smin; o[5] = 0.f; }
 }
 
+// sv_generate_ex outputs: the raw logits row of every beam row and the processed log-probs the scorer ranks -- log_softmax from the row
+// statistics beam_row_stats_kernel left, RepetitionPenalty, the min-length hold, and (beam-sample) the warper thresholds of beam_row_warp_kernel
+// (min_tokens_to_keep = 2): kept tokens are reported as lp / T (HF's TemperatureLogitsWarper), the rest as -inf.  Grid (R, row chunks).
+#define BM_CAP_QPB 1024
+__global__ __launch_bounds__(256) void beam_capture_kernel(BeamDev p, const CaptureDesc* desc, float temperature) {
+    if (*p.done) return;
+    const CaptureDesc d = *desc;
+    const int t = *p.step;
+    const int row = blockIdx.x;
+    if (t < 0 || t >= d.max_new || row >= d.rows) return;
+    const float* x = p.logits + (size_t)(row / p.logit_div) * p.ld;
+    const size_t off = ((size_t)t * d.rows + row) * (size_t)d.ld;
+    const int q0 = blockIdx.y * BM_CAP_QPB, q1 = q0 + BM_CAP_QPB;
+    const bool edges = blockIdx.y == 0;
+    if (d.logits) capture_store_row(d.logits + off, p.V, q0, q1, edges, [&](int j) { return x[j]; });
+    if (!d.scores) return;
+    float M, logS;
+    bm_row_lse(p, row, M, logS);
+    const uint32_t* seen = p.seen ? p.seen + (size_t)row * p.seen_words : nullptr;
+    const int eos = t < p.min_new ? p.eos : -1;
+    const float pen = p.penalty;
+    auto lp_of = [&](int j) {                      // bm_logprob, with the step-dependent hold hoisted
+        float lp = (x[j] - M) - logS;
+        if (seen && ((seen[j >> 5] >> (j & 31)) & 1u)) lp = lp < 0.f ? lp * pen : lp / pen;
+        return j == eos ? -INFINITY : lp;
+    };
+    if (p.do_sample) {
+        const float* o = p.warp + (size_t)row * 8;
+        WarpStats w;
+        w.kth = o[0]; w.mx = o[1]; w.invZ = o[2]; w.v0 = o[3]; w.smin = o[4];
+        const float inv_temp = p.inv_temp;
+        capture_store_row(d.scores + off, p.V, q0, q1, edges, [&](int j) {
+            const float lp = lp_of(j);
+            return wp_keep(w, lp * inv_temp) ? lp / temperature : -INFINITY;
+        });
+    } else {
+        capture_store_row(d.scores + off, p.V, q0, q1, edges, lp_of);
+    }
+}
+
 __global__ __launch_bounds__(256) void beam_row_topk_kernel(BeamDev p) {
     extern __shared__ float sl[];                  // the slice's ranking keys
     __shared__ float rv[4];
@@ -511,13 +551,15 @@ void BeamScorer::enqueue_step(const float* logits, int ld, int logit_div, hipStr
         if (sel) beam_row_warp_kernel<true><<<R, WP_THREADS, 0, st>>>(a);
         else beam_row_warp_kernel<false><<<R, WP_THREADS, 0, st>>>(a);
     }
+    if (cap) beam_capture_kernel<<<dim3(R, (c.V + 4 * BM_CAP_QPB - 1) / (4 * BM_CAP_QPB)), 256, 0, st>>>(a, cap, cap_temp);
     beam_row_topk_kernel<<<dim3(R, BM_SPLIT), 256, (size_t)per * sizeof(float), st>>>(a);
     beam_merge_kernel<<<c.B, 64, 0, st>>>(a);
     beam_update_kernel<<<1, ((c.B + 63) / 64) * 64, 0, st>>>(a);
     if (pen) beam_seen_gather_kernel<<<c.B, 256, (size_t)c.nb * a.seen_words * sizeof(uint32_t), st>>>(a);
 }
 
-int BeamScorer::finalize(hipStream_t st, std::vector<int64_t>& tokens, int& L, std::vector<float>& scores) {
+int BeamScorer::finalize(hipStream_t st, std::vector<int64_t>& tokens, int& L, std::vector<float>& scores,
+                         std::vector<int64_t>* beam_idx) {
     int32_t n_steps = 0;
     BMCHK(hipMemcpyAsync(&n_steps, d.step, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     BMCHK(hipStreamSynchronize(st));
@@ -535,6 +577,7 @@ int BeamScorer::finalize(hipStream_t st, std::vector<int64_t>& tokens, int& L, s
     const int64_t fill = c.pad > 0 ? c.pad : c.eos;
     tokens.assign((size_t)c.B * c.max_new, fill);
     scores.assign(c.B, 0.f);
+    if (beam_idx) beam_idx->assign((size_t)c.B * c.max_new, -1);
     L = 0;
     for (int b = 0; b < c.B; ++b) {
         const int slot = b * c.nb;                 // slot 0 = best finished hypothesis
@@ -543,10 +586,13 @@ int BeamScorer::finalize(hipStream_t st, std::vector<int64_t>& tokens, int& L, s
         int64_t* row = tokens.data() + (size_t)b * c.max_new;
         row[t_end] = ft[slot];
         int x = fp[slot];
+        int64_t* bi = beam_idx ? beam_idx->data() + (size_t)b * c.max_new : nullptr;
+        if (bi) bi[t_end] = slot + x;              // the finished token was chosen from running beam x's row of that step
         for (int s = t_end - 1; s >= 0; --s) {
             if (x < 0 || x >= c.nb) return -3;
             row[s] = ht[(size_t)s * R + slot + x];
             x = hp[(size_t)s * R + slot + x];
+            if (bi) bi[s] = slot + x;              // ... and its step-s token from its parent's row of step s
         }
         if (t_end + 1 > L) L = t_end + 1;
         scores[b] = fsc[slot];

@@ -18,8 +18,22 @@ static FinishArgs make_finish_args(sv_engine* e, int B, const sv_sampling& sp, i
     f.V = e->cfg.vocab; f.bad = e->d_bad;
     return f;
 }
+// sv_generate_ex outputs: the step's raw row and processed row, BEFORE suppress_token rewrites the EOS logit in place
+static void capture_step(sv_engine* e, int B, const sv_sampling& sp, hipStream_t st) {
+    const bool pen = sp.repetition_penalty > 0.f && sp.repetition_penalty != 1.0f;
+    CaptureArgs c;
+    c.desc = e->cap_desc; c.src = e->logits; c.ld_src = e->Vpad; c.V = e->cfg.vocab; c.B = B;
+    c.step = e->d_step; c.done = e->d_done;
+    c.seen = pen ? e->seen : nullptr; c.seen_words = e->seen_words; c.penalty = sp.repetition_penalty;
+    c.eos = sp.eos_token_id;
+    c.min_new = (sp.min_new_tokens > 0 && sp.eos_token_id >= 0 && sp.eos_token_id < e->cfg.vocab) ? sp.min_new_tokens : 0;
+    c.do_sample = sp.do_sample ? 1 : 0; c.temperature = sp.temperature; c.top_p = sp.top_p; c.top_k = sp.top_k;
+    c.warp = (sp.do_sample && e->cap_host.scores) ? e->cap_warp : nullptr;
+    launch_capture_rows(c, st);
+}
 static void sample_and_finish(sv_engine* e, int B, const sv_sampling& sp, int max_new, hipStream_t st, bool fused = false) {
     if (fused && e->fin_folded) { e->fin_folded = false; return; }      // the lm_head launch in front did the selection AND the bookkeeping (SkinnyArgs::finish)
+    if (e->cap_on) capture_step(e, B, sp, st);                          // (a capturing call never folds: fused is off for it)
     const bool pen = sp.repetition_penalty > 0.f && sp.repetition_penalty != 1.0f;
     const uint32_t* seen = pen ? e->seen : nullptr;
     if (sp.min_new_tokens > 0 && sp.eos_token_id >= 0 && sp.eos_token_id < e->cfg.vocab)
@@ -65,7 +79,7 @@ static void beam_step(sv_engine* e, const BeamKvArgs& kv, int logit_div, hipStre
 }
 
 static int generate_beam(sv_engine* e, const void* dev_embeds, int B, int S0, const sv_sampling* sp, int max_new,
-                         int64_t* dev_out_tokens, int32_t* n_generated, hipStream_t st) {
+                         const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, hipStream_t st) {
     const sv_config& c = e->cfg;
     const int nb = sp->num_beams, R = B * nb;
     if (nb > BM_MAXNB) return fail(SV_EINVAL, "num_beams %d unsupported (2..%d)", nb, BM_MAXNB);
@@ -92,6 +106,9 @@ static int generate_beam(sv_engine* e, const void* dev_embeds, int B, int S0, co
         if (r) return fail(SV_ENOMEM, "beam scorer allocation failed (hip error %d)", r);
     }
     e->beam.c = bc;
+    struct BeamCap { BeamScorer* s; ~BeamCap() { s->cap = nullptr; } } beam_cap{&e->beam};
+    e->beam.cap = e->cap_on ? e->cap_desc : nullptr;           // every beam_step below (eager and captured) writes the outputs
+    e->beam.cap_temp = sp->temperature;
     // prompt pass over the B requests, written into the pages of each request's first beam row
     SVCHECK(upload_beam_table(e, B, nb, need, 0, true, st));
     SVCHECK(prefill_forward(e, (const bf16_t*)dev_embeds, B, S0, st));
@@ -156,13 +173,16 @@ static int generate_beam(sv_engine* e, const void* dev_embeds, int B, int S0, co
     // built from void logits
     SVCHECK(check_finite_logits(e, st, "sv_generate (beam search)"));
     if (!e->h_flags[0]) return fail(SV_EHIP, "beam search did not terminate within its budget");
-    std::vector<int64_t> toks;
+    std::vector<int64_t> toks, bidx;
     std::vector<float> scores;
     int L = 0;
+    const bool want_bidx = outs && outs->host_beam_indices;
     {
-        int r = e->beam.finalize(st, toks, L, scores);
+        int r = e->beam.finalize(st, toks, L, scores, want_bidx ? &bidx : nullptr);
         if (r) return fail(SV_EHIP, "beam search bookkeeping failed (code %d)", r);
     }
+    if (want_bidx) memcpy(outs->host_beam_indices, bidx.data(), bidx.size() * sizeof(int64_t));
+    if (outs && outs->host_sequences_scores) memcpy(outs->host_sequences_scores, scores.data(), scores.size() * sizeof(float));
     HIPCHECK(hipMemcpy2DAsync(dev_out_tokens, (size_t)max_new * sizeof(int64_t), toks.data(), (size_t)max_new * sizeof(int64_t),
                               (size_t)L * sizeof(int64_t), B, hipMemcpyHostToDevice, st));
     HIPCHECK(hipStreamSynchronize(st));
@@ -226,27 +246,54 @@ int sveng::report_bad_logits(sv_engine* e, hipStream_t st, const char* who, int 
 }
 
 static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const sv_sampling* sp,
-                            int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream);
+                            const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream);
 
 // sv_config.exclusive_device = 2: OPTIMISTIC ownership.  The fused launches run as if the engine owned its GPU; if one gives up (another process
 // holds CUs: the bounded wait of rowops.hip / gemm.hip, never a hang, never tokens) the engine switches them off for good (report_bad_logits) and
 // THIS call is run again from its prompt pass.  The kernels with and without the fused launches are bit-identical (tests/test_gpu_e2e.py), the
 // sampler's random stream is a function of (seed, step, row): the second attempt re-derives exactly the columns the first one had already handed
 // to a streaming callback, and skips them.
-extern "C" int sv_generate(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const sv_sampling* sp,
-                           int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
+// (the second attempt runs every step again: the capture slabs of sv_generate_ex are rewritten completely)
+extern "C" int sv_generate_ex(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const sv_sampling* sp,
+                              const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
     if (e) { e->last_giveup = 0; e->stream_skip = 0; }
-    int rc = generate_attempt(e, dev_embeds, B, S0, sp, dev_out_tokens, n_generated, stream);
+    int rc = generate_attempt(e, dev_embeds, B, S0, sp, outs, dev_out_tokens, n_generated, stream);
     if (rc != 0 && e && e->cfg.exclusive_device == 2 && e->last_giveup && e->fused_off) {
         e->last_giveup = 0;
-        rc = generate_attempt(e, dev_embeds, B, S0, sp, dev_out_tokens, n_generated, stream);
+        rc = generate_attempt(e, dev_embeds, B, S0, sp, outs, dev_out_tokens, n_generated, stream);
     }
     if (e) e->stream_skip = 0;
     return rc;
 }
+extern "C" int sv_generate(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const sv_sampling* sp,
+                           int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
+    return sv_generate_ex(e, dev_embeds, B, S0, sp, nullptr, dev_out_tokens, n_generated, stream);
+}
+
+// validation of sv_generate_ex's outputs, and the descriptor of the call's slabs (allocated on first use, rewritten on the call's stream in front
+// of everything the call enqueues: a kept graph reads the new slab addresses)
+static int setup_capture(sv_engine* e, const sv_sampling* sp, const sv_generate_outputs* outs, int rows, int max_new, hipStream_t st) {
+    e->cap_on = false;
+    if (!outs) return 0;
+    const bool beam = sp->num_beams > 1;
+    if (!beam && (outs->host_sequences_scores || outs->host_beam_indices))
+        return fail(SV_EINVAL, "sv_generate_ex: host_sequences_scores / host_beam_indices are beam-search outputs (num_beams > 1)");
+    if (!outs->dev_scores && !outs->dev_logits) return 0;
+    if (outs->ld < e->cfg.vocab || outs->ld > ((int64_t)1 << 31))
+        return fail(SV_EINVAL, "sv_generate_ex: ld %lld must be >= vocab %d", (long long)outs->ld, e->cfg.vocab);
+    if (!e->cap_desc) {
+        SVCHECK(dalloc(e, &e->cap_desc, 1));
+        SVCHECK(dalloc(e, &e->cap_warp, (size_t)e->cfg.max_batch * 8));
+    }
+    e->cap_host.scores = outs->dev_scores; e->cap_host.logits = outs->dev_logits; e->cap_host.ld = (long long)outs->ld;
+    e->cap_host.rows = rows; e->cap_host.max_new = max_new;
+    HIPCHECK(hipMemcpyAsync(e->cap_desc, &e->cap_host, sizeof(CaptureDesc), hipMemcpyHostToDevice, st));
+    e->cap_on = true;
+    return 0;
+}
 
 static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const sv_sampling* sp,
-                            int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
+                            const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
     SVCHECK(check_ready(e));
     if (!sp || !dev_out_tokens || !n_generated) return fail(SV_EINVAL, "sv_generate: null argument");
     const int max_new = sp->max_length - S0;     // HF: with inputs_embeds, max_length includes the prompt
@@ -263,10 +310,12 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t B, int
     HIPCHECK(hipStreamWaitEvent(st, e->gen_event, 0));
 
     SVCHECK(cb_guard(e, "sv_generate"));
+    struct CapOff { sv_engine* e; ~CapOff() { e->cap_on = false; } } cap_off{e};
+    SVCHECK(setup_capture(e, sp, outs, sp->num_beams > 1 ? B * sp->num_beams : B, max_new, st));
     if (sp->num_beams > 1) {
         if (sp->on_tokens) return fail(SV_EINVAL, "streaming is not supported with beam search (hypotheses are only final at the end; HF refuses too)");
         if (sp->n_stop > 0 && !sp->stop_ids) return fail(SV_EINVAL, "n_stop > 0 but stop_ids is null");
-        return generate_beam(e, dev_embeds, B, S0, sp, max_new, dev_out_tokens, n_generated, st);
+        return generate_beam(e, dev_embeds, B, S0, sp, max_new, outs, dev_out_tokens, n_generated, st);
     }
 
     auto t0 = std::chrono::steady_clock::now();
@@ -280,7 +329,10 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t B, int
         int waves = 1, two = 0;
         skinny_plan(e->lm_head.Npad, e->lm_head.Kpad, 1, e->lm_head.fp8 ? 1 : 0, (B + 31) / 32, &waves, &two);
         const bool pen = sp->repetition_penalty > 0.f && sp->repetition_penalty != 1.0f;
-        fused_sel = !sp->do_sample && !pen && sp->min_new_tokens <= 0 && B <= 32 && !e->lm_head.fp8 && waves > 1 && !two && !(e->exp & 1024);
+        // a capturing call (sv_generate_ex) takes the separate selection launch: the capture must read the logits row between the lm_head and
+        // the selection, and the tokens are bit-identical either way (tests/test_gpu_e2e.py)
+        fused_sel = !sp->do_sample && !pen && sp->min_new_tokens <= 0 && B <= 32 && !e->lm_head.fp8 && waves > 1 && !two && !(e->exp & 1024) &&
+                    !e->cap_on;
     }
     // generation state, one launch: positions = S0 - 1 (finish_step adds 1), unfinished = 1, {step, done, n_emitted} = 0, the folded selection's key slots = 0
     gen_state_init(e->positions, S0 - 1, e->unfinished, B, e->d_step, e->amax, fused_sel ? 64 * SV_AMAX_STRIDE : 0, st);
@@ -339,6 +391,8 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t B, int
         snprintf(key, sizeof(key), "B%d|n%d|ds%d|T%a|p%a|k%d|seed%llu|eos%d|pad%d|ns%d|rp%a|mn%d|x%d|fo%d|ff%d", B, max_new, sp->do_sample,
                  sp->temperature, sp->top_p, sp->top_k, (unsigned long long)sp->seed, sp->eos_token_id, sp->pad_token_id, sp->n_stop,
                  sp->repetition_penalty, sp->min_new_tokens, e->exp, e->fused_off ? 1 : 0, e->fin_fold ? 1 : 0);
+        if (e->cap_on)       // capturing steps carry more launches (never the same graph as a plain call's); the slabs are read through cap_desc
+            snprintf(key + strlen(key), sizeof(key) - strlen(key), "|cap%d", (e->cap_host.scores ? 1 : 0) | (e->cap_host.logits ? 2 : 0));
         if (e->gen_gexec && e->gen_graph_key == key) {
             gexec = e->gen_gexec;
         } else {

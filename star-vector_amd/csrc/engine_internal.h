@@ -195,6 +195,12 @@ struct sv_engine {
     hipGraph_t gen_graph_multi = nullptr;
     hipGraphExec_t gen_gexec_multi = nullptr;
     int gen_multi_steps = 0;
+    // sv_generate_ex outputs: the device descriptor of the caller's slabs (rewritten for every call, never baked into a graph), its host image,
+    // per-row warper thresholds of the sampling capture; cap_on = the current call captures (set and cleared by sv_generate_ex)
+    CaptureDesc* cap_desc = nullptr;
+    CaptureDesc cap_host = {};
+    float* cap_warp = nullptr;
+    bool cap_on = false;
     // optional per-kernel HIP-event profiling of the decode step (bench.py roofline leg)
     bool prof_on = false;
     std::vector<hipEvent_t> prof_ev;

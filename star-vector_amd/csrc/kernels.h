@@ -309,6 +309,50 @@ struct FinishArgs {
                                   // fed to the next step is then 0, never an out-of-range row of the embedding table
 };
 void launch_finish_step(const FinishArgs& a, hipStream_t st);
+
+// ---- per-step outputs of sv_generate_ex (HF output_scores / output_logits) ------------------------------------------
+// Device-resident descriptor of the caller's slabs, rewritten by the host for every call: a captured decode graph keeps only
+// the descriptor's address, so two calls with different output tensors replay the same graph correctly.
+struct CaptureDesc {
+    float* scores;                 // [max_new][rows][ld] processed row (nullptr: not requested)
+    float* logits;                 // [max_new][rows][ld] raw row (nullptr: not requested)
+    long long ld;                  // >= V
+    int rows, max_new;
+};
+// greedy / sampling: row b of `src` at the device step t = *step (nothing once *done or t >= max_new).  The processed row is what the
+// selection ranks: RepetitionPenalty over the seen bitmap, the min-length EOS hold, and (do_sample) temperature as s / T with the
+// tokens outside TopK -> TopP at -inf.  Runs BEFORE suppress_token rewrites the EOS logit in place.
+struct CaptureArgs {
+    const CaptureDesc* desc;
+    const float* src; int ld_src; int V; int B;
+    const int32_t* step; const int32_t* done;
+    const uint32_t* seen; int seen_words; float penalty;             // seen = nullptr: penalty off
+    int eos, min_new;                                                // min_new <= 0: hold off
+    int do_sample; float temperature, top_p; int top_k;
+    float* warp;                                                     // [B][8] per-row warper thresholds (do_sample)
+};
+void launch_capture_rows(const CaptureArgs& a, hipStream_t st);
+#ifdef __HIPCC__
+// one thread block's share of a captured row: out[j] = f(j) for j in [0, V), with 16-byte stores wherever `out` allows (the slab
+// rows are ld floats apart, ld need not be a multiple of 4); the block takes quads [q0, q1) of the aligned body, block 0 the
+// unaligned head and the tail (< 4 elements each)
+template <class F>
+__device__ __forceinline__ void capture_store_row(float* out, int V, int q0, int q1, bool edges, F f) {
+    const int head = min((int)((4u - (unsigned)(((uintptr_t)out >> 2) & 3u)) & 3u), V);
+    const int nq = (V - head) >> 2;
+    const int tail0 = head + 4 * nq;
+    q1 = min(q1, nq);
+    for (int q = q0 + (int)threadIdx.x; q < q1; q += (int)blockDim.x) {
+        const int j = head + 4 * q;
+        *reinterpret_cast<float4*>(out + j) = make_float4(f(j), f(j + 1), f(j + 2), f(j + 3));
+    }
+    if (edges) {
+        const int i = (int)threadIdx.x;
+        if (i < head) out[i] = f(i);
+        if (tail0 + i < V && i < 4) out[tail0 + i] = f(tail0 + i);
+    }
+}
+#endif
 #ifdef __HIPCC__
 // the per-row part of the bookkeeping (row b takes token `nxt` at step t): returns whether the row is still generating
 __device__ __forceinline__ int finish_step_row(const FinishArgs& p, int b, int t, int nxt) {

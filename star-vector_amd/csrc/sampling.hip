@@ -375,6 +375,67 @@ void launch_sample_top_p(const SampleArgs& a, hipStream_t st) {
     sample_top_p_kernel<<<a.B, SP_THREADS, 0, st>>>(a);
 }
 
+// ------------------------------------------------------------------------------------------------
+// sv_generate_ex outputs (HF output_scores / output_logits): the raw row and the processed row of step t = *step, written by a
+// wide grid of 16-byte stores (2 x rows x V fp32 per step).  Sampling first takes the row's TopK -> TopP thresholds with the SAME
+// score functor and warp.h code the sampler's fallback path uses (one 1024-thread block per row, thresholds to p.warp).
+// ------------------------------------------------------------------------------------------------
+#define CAP_QPB 1024                       // 16-byte quads per block of the write grid (4096 floats)
+
+__global__ __launch_bounds__(SP_THREADS) void capture_warp_kernel(CaptureArgs p) {
+    __shared__ float red[SP_THREADS / 64];
+    if (*p.done) return;
+    const int t = *p.step;
+    if (t < 0 || t >= p.desc->max_new) return;
+    const int b = blockIdx.x;
+    const float* row = p.src + (size_t)b * p.ld_src;
+    const uint32_t* srow = p.seen ? p.seen + (size_t)b * p.seen_words : nullptr;
+    const float invT = 1.0f / p.temperature;
+    const bool hold = t < p.min_new;
+    const int eos = p.eos;
+    auto lg = [&](int i) { return (hold && i == eos) ? -INFINITY : rep_penalty(row[i], i, srow, p.penalty) * invT; };
+    const WarpStats w = row_warp_stats<false, true>(lg, p.V, p.top_k, p.top_p, 1, red);
+    if (threadIdx.x == 0) {
+        float* o = p.warp + (size_t)b * 8;
+        o[0] = w.kth; o[1] = w.mx; o[2] = w.invZ; o[3] = w.v0; o[4] = w.smin;
+    }
+}
+
+__global__ __launch_bounds__(256) void capture_write_kernel(CaptureArgs p) {
+    if (*p.done) return;
+    const CaptureDesc d = *p.desc;
+    const int t = *p.step;
+    const int b = blockIdx.x;
+    if (t < 0 || t >= d.max_new || b >= d.rows) return;
+    const float* row = p.src + (size_t)b * p.ld_src;
+    const size_t off = ((size_t)t * d.rows + b) * (size_t)d.ld;
+    const int q0 = blockIdx.y * CAP_QPB, q1 = q0 + CAP_QPB;
+    const bool edges = blockIdx.y == 0;
+    if (d.logits) capture_store_row(d.logits + off, p.V, q0, q1, edges, [&](int j) { return row[j]; });
+    if (!d.scores) return;
+    const uint32_t* srow = p.seen ? p.seen + (size_t)b * p.seen_words : nullptr;
+    const int eos = t < p.min_new ? p.eos : -1;                      // MinLength: the EOS id at -inf while held
+    const float pen = p.penalty;
+    if (p.do_sample) {
+        const float* o = p.warp + (size_t)b * 8;
+        WarpStats w;
+        w.kth = o[0]; w.mx = o[1]; w.invZ = o[2]; w.v0 = o[3]; w.smin = o[4];
+        const float T = p.temperature, invT = 1.0f / T;
+        // kept: the sampler's test on the sampler's value (s * invT); reported: HF's TemperatureLogitsWarper, s / T
+        capture_store_row(d.scores + off, p.V, q0, q1, edges, [&](int j) {
+            const float s = j == eos ? -INFINITY : rep_penalty(row[j], j, srow, pen);
+            return wp_keep(w, s * invT) ? s / T : -INFINITY;
+        });
+    } else {
+        capture_store_row(d.scores + off, p.V, q0, q1, edges,
+                          [&](int j) { return j == eos ? -INFINITY : rep_penalty(row[j], j, srow, pen); });
+    }
+}
+void launch_capture_rows(const CaptureArgs& a, hipStream_t st) {
+    if (a.do_sample && a.warp) capture_warp_kernel<<<a.B, SP_THREADS, 0, st>>>(a);
+    capture_write_kernel<<<dim3(a.B, (a.V + 4 * CAP_QPB - 1) / (4 * CAP_QPB)), 256, 0, st>>>(a);
+}
+
 __global__ void finish_step_kernel(FinishArgs p) {
     __shared__ int any_unf;
     if (*p.done) return;

@@ -251,13 +251,19 @@ class HipEngine:
                  temperature: float = 1.0, top_p: float = 1.0, eos_token_id: int = 0, pad_token_id: int = 0,
                  stop_ids: Optional[Sequence[int]] = None, seed: int = 0, sync_every: int = 32,
                  repetition_penalty: float = 1.0, num_beams: int = 1, length_penalty: float = 1.0,
-                 early_stopping=False, top_k: int = 0, on_tokens=None, min_new_tokens: int = 0) -> torch.Tensor:
+                 early_stopping=False, top_k: int = 0, on_tokens=None, min_new_tokens: int = 0,
+                 scores_out: Optional[torch.Tensor] = None, logits_out: Optional[torch.Tensor] = None,
+                 return_outputs: bool = False):
         """HF ``generate`` semantics for inputs_embeds: returns ONLY the new tokens, int64 [B, N].
         ``num_beams`` > 1 runs HF's beam search on device (``early_stopping``: False, True or "never"); with
         ``do_sample`` it is HF's beam-sample.  ``top_k`` (0 = off) is HF's TopKLogitsWarper, applied before top-p.
         ``on_tokens(tokens [B, n] int64 cpu, first_col)``: streaming callback, called every ``sync_every`` steps with the
         columns that became final and once more at the end.  ``min_new_tokens``: HF's MinLengthLogitsProcessor after the
-        prompt length has been subtracted from ``min_length`` (EOS cannot be chosen before that many new tokens)."""
+        prompt length has been subtracted from ``min_length`` (EOS cannot be chosen before that many new tokens).
+        Per-step outputs (sv_generate_ex): ``scores_out`` / ``logits_out`` are fp32 device tensors [max_new, rows, ld] (rows = B, or
+        B * num_beams under beam search; ld >= vocab) that receive HF's processed scores / raw logits of every generated column.
+        ``return_outputs=True`` returns a dict {"sequences", "n_generated"} plus, under beam search, "sequences_scores" [B] and
+        "beam_indices" [B, n] int64 instead of the bare token tensor."""
         x = _need(inputs_embeds, torch.bfloat16, "inputs_embeds")
         B, S0, D = x.shape
         if D != self.cfg.hidden:
@@ -278,10 +284,45 @@ class HipEngine:
             sp.on_tokens = C.cast(cb, C.c_void_p)
         out = torch.empty(B, max_new, dtype=torch.int64, device=x.device)
         n = C.c_int32(0)
-        check(self.lib.sv_generate(self._h, _ptr(x), B, S0, C.byref(sp), _ptr(out), C.byref(n), _stream()), "sv_generate")
+        if scores_out is None and logits_out is None and not return_outputs:
+            check(self.lib.sv_generate(self._h, _ptr(x), B, S0, C.byref(sp), _ptr(out), C.byref(n), _stream()), "sv_generate")
+            if cb_errors:
+                raise cb_errors[0]
+            return out[:, : n.value]
+        rows = B * int(num_beams) if int(num_beams) > 1 else B
+        outs = _lib.SvGenerateOutputs()
+        ld = None
+        for name, t in (("scores_out", scores_out), ("logits_out", logits_out)):
+            if t is None:
+                continue
+            if t.is_cuda and not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous (the engine writes into it)")
+            t = _need(t, torch.float32, name)
+            if t.dim() != 3 or t.shape[0] < max_new or t.shape[1] != rows or t.shape[2] < self.cfg.vocab:
+                raise ValueError(f"{name} must be [>= {max_new}, {rows}, >= {self.cfg.vocab}] fp32, got {list(t.shape)}")
+            if ld is not None and t.shape[2] != ld:
+                raise ValueError("scores_out and logits_out must have the same last dimension")
+            ld = t.shape[2]
+            setattr(outs, "dev_scores" if name == "scores_out" else "dev_logits", _ptr(t))
+        outs.ld = int(ld or 0)
+        beam = int(num_beams) > 1
+        seq_scores = (C.c_float * B)() if beam else None
+        beam_idx = (C.c_int64 * (B * max_new))() if beam else None
+        if beam:
+            outs.host_sequences_scores = C.cast(seq_scores, C.POINTER(C.c_float))
+            outs.host_beam_indices = C.cast(beam_idx, C.POINTER(C.c_int64))
+        check(self.lib.sv_generate_ex(self._h, _ptr(x), B, S0, C.byref(sp), C.byref(outs), _ptr(out), C.byref(n), _stream()),
+              "sv_generate_ex")
         if cb_errors:
             raise cb_errors[0]
-        return out[:, : n.value]
+        L = n.value
+        if not return_outputs:
+            return out[:, :L]
+        res = {"sequences": out[:, :L], "n_generated": L}
+        if beam:
+            res["sequences_scores"] = torch.tensor(list(seq_scores), dtype=torch.float32)
+            res["beam_indices"] = torch.tensor(list(beam_idx), dtype=torch.int64).view(B, max_new)[:, :L].contiguous()
+        return res
 
     # ---- continuous batching: one request per row of the engine's batch (include/starvector_hip.h, sv_cb_*) ----------------
     def cb_admit(self, inputs_embeds: torch.Tensor, requests: Sequence[dict]) -> List[int]:
@@ -333,6 +374,10 @@ class HipEngine:
         check(self.lib.sv_beam_history(self._h, par, tok, n.value, C.byref(n), C.byref(rows)), "sv_beam_history")
         shape = (n.value, rows.value)
         return torch.tensor(list(par), dtype=torch.int32).view(shape), torch.tensor(list(tok), dtype=torch.int32).view(shape)
+
+    def mem_free_bytes(self) -> int:
+        """Free memory on the engine's GPU (what a generate call with per-step outputs checks its slabs against)."""
+        return int(torch.cuda.mem_get_info(self.device)[0])
 
     def last_timing(self) -> Dict[str, float]:
         buf = (C.c_double * 4)()

@@ -35,6 +35,30 @@ _EXCLUSIVE = threading.local()
 def _in_exclusive_job() -> bool:
     return bool(getattr(_EXCLUSIVE, "active", False))
 
+class _GenerateOutput(dict):
+    """Stand-in for transformers' Generate*DecoderOnlyOutput when transformers is not importable: the same field names, read as
+    attributes or as keys."""
+
+    def __getattr__(self, name):
+        try:
+            return self[name]
+        except KeyError:
+            raise AttributeError(name) from None
+
+
+_DECODER_ONLY_FIELDS = ("sequences", "scores", "logits", "attentions", "hidden_states", "past_key_values")
+_BEAM_FIELDS = ("sequences", "sequences_scores", "scores", "logits", "beam_indices", "attentions", "hidden_states", "past_key_values")
+
+
+def generate_output(beam: bool, **fields):
+    """HF's GenerateDecoderOnlyOutput / GenerateBeamDecoderOnlyOutput (generation/utils.py) with `fields`, the rest None."""
+    try:
+        from transformers.generation.utils import GenerateBeamDecoderOnlyOutput, GenerateDecoderOnlyOutput
+        return (GenerateBeamDecoderOnlyOutput if beam else GenerateDecoderOnlyOutput)(**fields)
+    except ImportError:
+        return _GenerateOutput({k: fields.get(k) for k in (_BEAM_FIELDS if beam else _DECODER_ONLY_FIELDS)})
+
+
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)   # data/util.py:33-38
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 
@@ -539,11 +563,23 @@ class HipCausalLM(_EngineModule):
                  length_penalty: float = 1.0, use_cache: bool = True, stopping_criteria=None,
                  early_stopping: bool = False, pad_token_id: Optional[int] = None, eos_token_id: Optional[int] = None,
                  num_return_sequences: int = 1, top_k: Optional[int] = 50, streamer=None, seed: Optional[int] = None,
-                 **unused) -> torch.Tensor:
+                 return_dict_in_generate: bool = False, output_scores: bool = False, output_logits: bool = False,
+                 **unused):
         # top_k: the reference never passes it; its pinned transformers==4.49.0 (pyproject.toml:18) defaults
         # GenerationConfig.top_k to 50, so every do_sample call there is top-k 50 followed by top-p.  Same default here.
         if inputs_embeds is None:
             raise ValueError("inputs_embeds is required (the reference always generates from embeddings)")
+        # HF structured outputs (return_dict_in_generate): without it output_scores / output_logits are ignored, as HF ignores them
+        want = False
+        if return_dict_in_generate:
+            if unused.get("output_attentions") or unused.get("output_hidden_states"):
+                raise NotImplementedError("output_attentions / output_hidden_states are not built: the decode step keeps neither")
+            want = bool(output_scores or output_logits)
+            if want and attention_mask is not None and not bool((attention_mask == 1).all()):
+                raise NotImplementedError("output_scores / output_logits with a padded attention_mask are not built: padded rows "
+                                          "are generated group by group, without HF's common step axis")
+        outputs = dict(return_dict_in_generate=True, output_scores=output_scores, output_logits=output_logits) \
+            if return_dict_in_generate else {}
         # Random stream: HF draws from torch's global generator, so repeated calls differ and torch.manual_seed controls them.
         # The device sampler is a pure function of (seed, step, row): the per-call seed is therefore DRAWN from torch's
         # generator (same reproducibility contract), unless the caller pins it with `seed=` (tests, data-parallel ranks).
@@ -575,11 +611,12 @@ class HipCausalLM(_EngineModule):
             # HF masks the padded keys and numbers positions by cumsum(mask), so a padded row behaves exactly like the same row
             # with its padding removed (checked against HF for left and right padding, GPTBigCode and StarCoder2).  The engine
             # takes rectangular all-ones prompts, so rows are grouped by their real length and generated group by group.
-            return self._generate_padded(inputs_embeds, attention_mask, dict(
+            seqs = self._generate_padded(inputs_embeds, attention_mask, dict(
                 do_sample=do_sample, top_p=top_p, temperature=temperature, num_beams=num_beams, max_length=max_length,
                 min_length=min_length, repetition_penalty=repetition_penalty, length_penalty=length_penalty,
                 use_cache=use_cache, stopping_criteria=stopping_criteria, early_stopping=early_stopping,
                 pad_token_id=pad_token_id, eos_token_id=eos_token_id, top_k=top_k, seed=seed))
+            return generate_output(num_beams > 1, sequences=seqs) if return_dict_in_generate else seqs
         S0 = inputs_embeds.shape[1]
         # HF (_prepare_generated_length): with inputs_embeds min_length is reduced by the prompt length -- 0 on the im2svg path
         # (SURVEY.md 8a-a11), positive only for a text2svg caption shorter than min_length; MinLengthLogitsProcessor then
@@ -599,7 +636,7 @@ class HipCausalLM(_EngineModule):
                 for c in range(tokens.shape[1]):
                     streamer.put(tokens[:, c])
         batcher = getattr(self, "batcher", None)
-        if batcher is not None and not (num_beams == 1 and inputs_embeds.shape[0] == 1) and not _in_exclusive_job():
+        if batcher is not None and (want or not (num_beams == 1 and inputs_embeds.shape[0] == 1)) and not _in_exclusive_job():
             # beam search / a multi-row HF batch while requests share the engine: run it with the engine to itself, in turn
             def call():
                 _EXCLUSIVE.active = True          # thread-local: only the scheduler thread running this job sees it
@@ -609,7 +646,7 @@ class HipCausalLM(_EngineModule):
                                          min_length=min_length, repetition_penalty=repetition_penalty,
                                          length_penalty=length_penalty, use_cache=use_cache, stopping_criteria=stopping_criteria,
                                          early_stopping=early_stopping, pad_token_id=pad_token_id, eos_token_id=eos_token_id,
-                                         top_k=top_k, streamer=streamer, seed=seed)
+                                         top_k=top_k, streamer=streamer, seed=seed, **outputs)
                 finally:
                     _EXCLUSIVE.active = False
             return batcher.run_exclusive(call)
@@ -630,19 +667,79 @@ class HipCausalLM(_EngineModule):
                 min_new_tokens=min_new), on_chunk if on_tokens is not None else None).to(inputs_embeds.device)
             if streamer is not None:
                 streamer.end()
-            return out
+            return generate_output(False, sequences=out) if return_dict_in_generate else out
+        extra, slabs = {}, {}
+        if return_dict_in_generate and (want or num_beams > 1):
+            extra, slabs = self._output_slabs(inputs_embeds, max_length, num_beams, output_scores, output_logits)
         lock = getattr(self._engine, "call_lock", None) or contextlib.nullcontext()
         with lock:          # the same lock the slot path holds: a classic generate never lands between its cb_reset / cb_admit
             out = self._classic_generate(inputs_embeds, max_length, do_sample, temperature, top_p, eos_token_id, pad_token_id,
                                          stopping_criteria, seed, repetition_penalty, num_beams, length_penalty, early_stopping,
-                                         top_k, on_tokens, streamer, min_new)
+                                         top_k, on_tokens, streamer, min_new, **extra)
         if streamer is not None:
             streamer.end()
+        if not return_dict_in_generate:
+            return out
+        if not extra:
+            return generate_output(False, sequences=out)
+        L = int(out["n_generated"])
+        fields = dict(sequences=out["sequences"],
+                      scores=tuple(slabs["scores_out"][t] for t in range(L)) if "scores_out" in slabs else None,
+                      logits=tuple(slabs["logits_out"][t] for t in range(L)) if "logits_out" in slabs else None)
+        if num_beams > 1:
+            dev = out["sequences"].device
+            fields["beam_indices"] = out["beam_indices"].to(dev)
+            fields["sequences_scores"] = out["sequences_scores"].to(dev) if output_scores else None
+        return generate_output(num_beams > 1, **fields)
+
+    def _output_slabs(self, inputs_embeds, max_length, num_beams, output_scores, output_logits):
+        """[max_new, rows, V] fp32 slabs for output_scores / output_logits on the engine's device, after checking they fit (the engine
+        writes step t of every row into slab[t])."""
+        eng = self._engine
+        B, S0 = inputs_embeds.shape[0], inputs_embeds.shape[1]
+        rows, max_new, V = B * max(int(num_beams), 1), int(max_length) - S0, int(eng.cfg.vocab)
+        names = [n for n, on in (("scores_out", output_scores), ("logits_out", output_logits)) if on]
+        extra = dict(return_outputs=True)
+        if not names or max_new <= 0:
+            return extra, {}
+        need = len(names) * max_new * rows * V * 4
+        free_fn = getattr(eng, "mem_free_bytes", None)
+        free = free_fn() if free_fn is not None else None
+        if free is not None and need > free:
+            raise MemoryError(f"output_scores / output_logits need {need / 1e9:.2f} GB ({len(names)} x {max_new} steps x {rows} rows x "
+                              f"{V} fp32) on the GPU, {free / 1e9:.2f} GB are free: lower max_length or the batch")
+        dev = getattr(eng, "_dev", None) or inputs_embeds.device
+        slabs = {n: torch.empty(max_new, rows, V, dtype=torch.float32, device=dev) for n in names}
+        extra.update(slabs)
+        return extra, slabs
+
+    def compute_transition_scores(self, sequences: torch.Tensor, scores, beam_indices: Optional[torch.Tensor] = None,
+                                  normalize_logits: bool = False) -> torch.Tensor:
+        """HF GenerationMixin.compute_transition_scores (generation/utils.py) with the engine's vocabulary size: the score of each
+        generated token at its step ([batch, steps]; beam search: along the returned hypothesis, 0 after its end)."""
+        V = int(self._engine.cfg.vocab)
+        if beam_indices is None:
+            beam_indices = torch.arange(scores[0].shape[0]).view(-1, 1).to(sequences.device)
+            beam_indices = beam_indices.expand(-1, len(scores))
+        stacked = torch.stack(scores).reshape(len(scores), -1).transpose(0, 1)
+        if normalize_logits:
+            stacked = stacked.reshape(-1, V, stacked.shape[-1])
+            stacked = torch.nn.functional.log_softmax(stacked, dim=1)
+            stacked = stacked.reshape(-1, stacked.shape[-1])
+        mask = beam_indices < 0
+        max_beam_length = (1 - mask.long()).sum(-1).max()
+        beam_indices = beam_indices.clone()[:, :max_beam_length]
+        mask = mask[:, :max_beam_length]
+        beam_indices[mask] = 0
+        cut = sequences.shape[-1] - max_beam_length
+        indices = sequences[:, cut:] + beam_indices * V
+        out = stacked.gather(0, indices)
+        out[mask] = 0
         return out
 
     def _classic_generate(self, inputs_embeds, max_length, do_sample, temperature, top_p, eos_token_id, pad_token_id,
                           stopping_criteria, seed, repetition_penalty, num_beams, length_penalty, early_stopping, top_k,
-                          on_tokens, streamer, min_new):
+                          on_tokens, streamer, min_new, **outputs):
         return self._engine.generate(
             inputs_embeds.to(torch.bfloat16), max_length=int(max_length), do_sample=bool(do_sample),
             temperature=float(temperature if temperature is not None else 1.0),
@@ -653,7 +750,7 @@ class HipCausalLM(_EngineModule):
             repetition_penalty=float(repetition_penalty if repetition_penalty is not None else 1.0),
             num_beams=num_beams, length_penalty=float(length_penalty if length_penalty is not None else 1.0),
             early_stopping=early_stopping, top_k=int(top_k or 0), on_tokens=on_tokens,
-            sync_every=8 if streamer is not None else 32, **({"min_new_tokens": min_new} if min_new else {}))
+            sync_every=8 if streamer is not None else 32, **({"min_new_tokens": min_new} if min_new else {}), **outputs)
 
 
 class StoppingCriteriaSub:
