@@ -230,6 +230,18 @@ int  sv_prefill(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, flo
  * filled like sv_prefill. */
 int  sv_forward_logits(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S, int32_t n_keep,
                        void* dev_logits_bf16, sv_stream stream);
+/* Scoring forward that keeps no logits: the decoder over inputs_embeds [B,S,hidden] bf16 exactly as sv_forward_logits,
+ * then for row (b, j), j < n_keep, = position S - n_keep + j: the log-probability of dev_targets[b][j] under
+ * softmax(logits / temperature), where logits are the bf16 values sv_forward_logits would have returned for that row
+ * (fp32 arithmetic over them).  dev_targets int32 [B][n_keep]; -100 = ignore (logprob 0).  Outputs fp32 / int32
+ * [B][n_keep], each may be NULL (not all): logprob, logsumexp of logits / temperature, entropy of the softmax, argmax =
+ * the lowest index holding the row's maximum.  temperature > 0.  The lm_head runs over the rows in chunks: device
+ * memory does not grow with B x n_keep x vocab.  A target outside [0, vocab) that is not -100: SV_EINVAL naming the
+ * row (its logprob is NaN, everything else is written).  Blocks until the pass has finished.  KV side effects as
+ * sv_forward_logits. */
+int  sv_forward_logprobs(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S, int32_t n_keep,
+                         const int32_t* dev_targets, float temperature, float* dev_logprob, float* dev_logsumexp,
+                         float* dev_entropy, int32_t* dev_argmax, sv_stream stream);
 
 /* One autoregressive step for tokens [B] int32 (device) appended after the cached context. */
 int  sv_decode_step(sv_engine* e, const int32_t* dev_tokens, int32_t B, float* dev_logits, sv_stream stream);

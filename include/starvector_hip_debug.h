@@ -202,6 +202,17 @@ int  sv_op_sample_top_p(const float* logits, int32_t B, int32_t V, int32_t ld, f
  * counts and, with the prompt ids, its repetition set.  host_out [B] = the token each row takes. */
 int  sv_op_cb_select(const float* dev_logits, int32_t B, int32_t V, int32_t ld, const sv_cb_request* reqs,
                      const int32_t* host_history, int32_t ld_hist, const int32_t* host_hist_len, int32_t* host_out, sv_stream stream);
+/* the kernel of sv_forward_logprobs (score.hip logprob_rows_kernel) on caller-given rows: dev_logits_bf16 [R][ld] bf16 (16-byte aligned,
+ * ld a multiple of 8), V valid columns, dev_targets int32 [R] (-100 = ignore: logprob 0).  fp32 over x_i = float(logit_i) / temperature:
+ * logsumexp, logprob = x_target - logsumexp, entropy of softmax(x) (an x_i = -inf adds 0), argmax = the lowest index holding the maximum.
+ * Outputs are device arrays [R]; each may be NULL.  host_flag2 (optional, HOST int32[2]): [0] = 1 if a target was outside [0, V) and not
+ * -100 (its logprob is NaN) | 2 if a row had no finite logit (its outputs are NaN, argmax -1), [1] = the first such row, -1 if none. */
+int  sv_op_logprob_rows(const void* dev_logits_bf16, int32_t R, int32_t V, int32_t ld, const int32_t* dev_targets, float temperature,
+                        float* dev_logprob, float* dev_logsumexp, float* dev_entropy, int32_t* dev_argmax, int32_t* host_flag2,
+                        sv_stream stream);
+/*   sv_debug_set_score_chunk_rows  sv_forward_logprobs runs its lm_head over `rows` rows at a time from the next call on (a multiple of 256;
+     0 = the default, 4096): lets a test force many chunks on a tiny model.  The outputs do not depend on it, bit for bit. */
+int  sv_debug_set_score_chunk_rows(sv_engine* e, int32_t rows);
 /* temperature -> top-k (0 = off) -> top-p -> one multinomial draw per row */
 int  sv_op_sample(const float* logits, int32_t B, int32_t V, int32_t ld, float temperature, int32_t top_k,
                   float top_p, uint64_t seed, int32_t step, int32_t* out, sv_stream stream);

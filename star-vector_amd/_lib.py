@@ -109,6 +109,7 @@ PRODUCT_PROTOTYPES = {
                                   C.POINTER(_F), _P, _P, C.c_int64, _P]),
     "sv_prefill": (_I, [_P, _P, _I, _I, _P, _P]),
     "sv_forward_logits": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "sv_forward_logprobs": (_I, [_P, _P, _I, _I, _I, _P, _F, _P, _P, _P, _P, _P]),
     "sv_decode_step": (_I, [_P, _P, _I, _P, _P]),
     "sv_generate": (_I, [_P, _P, _I, _I, C.POINTER(SvSampling), _P, C.POINTER(_I), _P]),
     "sv_generate_ex": (_I, [_P, _P, _I, _I, C.POINTER(SvSampling), C.POINTER(SvGenerateOutputs), _P, C.POINTER(_I), _P]),
@@ -167,6 +168,8 @@ DEBUG_PROTOTYPES = {
     "sv_op_argmax": (_I, [_P, _I, _I, _I, _P, _P]),
     "sv_op_sample_top_p": (_I, [_P, _I, _I, _I, _F, _F, C.c_uint64, _I, _P, _P]),
     "sv_op_sample": (_I, [_P, _I, _I, _I, _F, _I, _F, C.c_uint64, _I, _P, _P]),
+    "sv_op_logprob_rows": (_I, [_P, _I, _I, _I, _P, _F, _P, _P, _P, _P, C.POINTER(_I), _P]),
+    "sv_debug_set_score_chunk_rows": (_I, [_P, _I]),
     "sv_op_cb_select": (_I, [_P, _I, _I, _I, C.POINTER(SvCbRequest), C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(_I), _P]),
 }
 

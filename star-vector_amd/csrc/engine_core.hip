@@ -328,6 +328,7 @@ extern "C" int sv_destroy(sv_engine* e) {
     if (e->gen_gexec_multi) (void)hipGraphExecDestroy(e->gen_gexec_multi);
     if (e->gen_graph_multi) (void)hipGraphDestroy(e->gen_graph_multi);
     if (e->score_ws) (void)hipFree(e->score_ws);
+    if (e->score_chunk_ws) (void)hipFree(e->score_chunk_ws);
     if (e->h_flags) (void)hipHostFree(e->h_flags);
     if (e->h_table) (void)hipHostFree(e->h_table);
     if (e->table_ev) (void)hipEventDestroy(e->table_ev);

@@ -1,5 +1,7 @@
 // Host driver, part 2 of 5: the op graphs -- vision tower, adapter, prompt pass, one decode step -- and the forward entry
-// points of the C ABI (sv_encode_image, sv_adapter, sv_embed_tokens, sv_prefill, sv_forward_logits, sv_decode_step).
+// points of the C ABI (sv_encode_image, sv_adapter, sv_embed_tokens, sv_prefill, sv_forward_logits, sv_forward_logprobs, sv_decode_step).
+#include <algorithm>
+#include <cmath>
 #include "engine_internal.h"
 
 namespace sveng {
@@ -28,7 +30,7 @@ static void tail_mark_cb(void* c, hipStream_t st) { prof_mark(static_cast<TailMa
 // the rows a sequence leaves over its 256-row tiles go through the split-K remainder kernel (gemm.hip); last_rows: the M rows are the LAST
 // rows of such sequences (compact) and take the kernel they take inside the full problem
 static void gemm(sv_engine* e, int kind, const bf16_t* A, int lda, const Linear& l, const bf16_t* R, int ldr, void* C, int ldc, int M,
-                 int act, int out_f32, hipStream_t st, int seq_rows = 0, int last_rows = 0) {
+                 int act, int out_f32, hipStream_t st, int seq_rows = 0, int last_rows = 0, int tune_in_place = 0) {
     TailMarkCtx tc{e};
     prof_mark(e, kind, st);
     GemmArgs g;
@@ -38,6 +40,7 @@ static void gemm(sv_engine* e, int kind, const bf16_t* A, int lda, const Linear&
     g.cscale = l.fp8 ? l.wscale : nullptr;
     g.seq_rows = (e->exp & 4194304) ? 0 : seq_rows;          // SV_EXP bit 4194304: A/B, the batch-level remainder of rounds 2-5
     g.splitk_rows = (e->exp & 4194304) ? 0 : last_rows;
+    g.tune_in_place = tune_in_place;
     launch_gemm(g, st);
 }
 
@@ -181,7 +184,7 @@ static void lm_head_logits(sv_engine* e, int MT, const bf16_t* xp, hipStream_t s
 }
 
 int sveng::prefill_forward(sv_engine* e, const bf16_t* embeds, int B, int S0, hipStream_t st, int n_keep,
-                           bf16_t* dev_scores, const int32_t* table) {
+                           bf16_t* dev_scores, const int32_t* table, const ScoreLogprobs* lp) {
     if (!table) table = e->block_table;           // continuous batching prefills NEW requests through a table of their slots' pages
     const sv_config& c = e->cfg;
     const int D = c.hidden, dh = e->dh, F = c.n_inner, M = B * S0, QKV = e->QKV, nkv = e->nkv;
@@ -249,7 +252,8 @@ int sveng::prefill_forward(sv_engine* e, const bf16_t* embeds, int B, int S0, hi
         // big-M GEMM; bf16 logits like the reference's bf16 lm_head.  The GEMM writes rows of Vpad columns (the packed
         // weight's padding), the caller's tensor has `vocab` columns.
         const size_t rows = (size_t)B * n_keep;
-        const size_t need = rows * (size_t)D * 2 + rows * (size_t)e->Vpad;      // [rows][D] hidden, [rows][D] ln_f, [rows][Vpad]
+        // [rows][D] hidden, [rows][D] ln_f, [rows][Vpad] logits -- the log-prob form keeps its logits in the chunk workspace instead
+        const size_t need = rows * (size_t)D * 2 + (lp ? 0 : rows * (size_t)e->Vpad);
         if (need > e->score_elems) {
             if (e->score_ws) (void)hipFree(e->score_ws);
             e->score_ws = nullptr; e->score_elems = 0;
@@ -262,9 +266,40 @@ int sveng::prefill_forward(sv_engine* e, const bf16_t* embeds, int B, int S0, hi
         prof_mark(e, PK_PF_ROWS, st);
         launch_gather_tail_rows(e->ph, hk, B, S0, n_keep, D, st);
         launch_layernorm_rows(hk, D, e->ln_f.g, e->ln_f.b, hn, D, (int)rows, D, c.ln_eps, st);
-        gemm(e, PK_PF_GEMM, hn, D, e->lm_head, nullptr, 0, lg, e->Vpad, (int)rows, ACT_NONE, 0, st);
-        HIPCHECK(hipMemcpy2DAsync(dev_scores, (size_t)c.vocab * sizeof(bf16_t), lg, (size_t)e->Vpad * sizeof(bf16_t),
-                                  (size_t)c.vocab * sizeof(bf16_t), rows, hipMemcpyDeviceToDevice, st));
+        if (lp) {
+            // sv_forward_logprobs: the same lm_head over the same ln_f rows, `chunk` rows at a time into a workspace that does not grow
+            // with rows x vocab, logprob_rows over each chunk while it is still in the last-level cache.  The logits underneath are the
+            // bits sv_forward_logits returns whatever the chunk size: this call hands the dispatch no sequence structure, so a chunk can
+            // only reach the tile kernels and the one-wave-per-tile kernel, which compute a row with the same MFMA, operand roles and
+            // ascending k (tests/test_gpu_ops.py::test_linear_big_m_kernels_agree_bitwise); the split-K remainder kernels with their own
+            // K order are never chosen here.  Chunks are multiples of 256 rows: the rows in front of a boundary are whole tiles.
+            const int chunk = e->score_chunk_rows > 0 ? e->score_chunk_rows : SV_SCORE_CHUNK_ROWS;
+            if (e->score_chunk_alloc != chunk) {
+                if (e->score_chunk_ws) (void)hipFree(e->score_chunk_ws);
+                e->score_chunk_ws = nullptr; e->score_chunk_alloc = 0;
+                HIPCHECK(hipMalloc(reinterpret_cast<void**>(&e->score_chunk_ws), (size_t)chunk * e->Vpad * sizeof(bf16_t) + 16));
+                e->score_chunk_alloc = chunk;
+            }
+            int32_t* flag = reinterpret_cast<int32_t*>(e->score_chunk_ws + (size_t)chunk * e->Vpad);
+            fill_i32(flag, 0, 1, st);
+            fill_i32(flag + 1, 0x7fffffff, 1, st);
+            for (size_t r0 = 0; r0 < rows; r0 += (size_t)chunk) {
+                const int n = (int)std::min<size_t>((size_t)chunk, rows - r0);
+                gemm(e, PK_PF_GEMM, hn + r0 * D, D, e->lm_head, nullptr, 0, e->score_chunk_ws, e->Vpad, n, ACT_NONE, 0, st, 0, 0, 1);
+                LogprobArgs a;
+                a.logits = e->score_chunk_ws; a.ld = e->Vpad; a.V = c.vocab; a.R = n; a.inv_t = lp->inv_t;
+                a.targets = lp->targets + r0;
+                a.logprob = lp->logprob ? lp->logprob + r0 : nullptr; a.lse = lp->lse ? lp->lse + r0 : nullptr;
+                a.entropy = lp->entropy ? lp->entropy + r0 : nullptr; a.argmax = lp->argmax ? lp->argmax + r0 : nullptr;
+                a.bad = flag; a.row0 = (int)r0;
+                prof_mark(e, PK_PF_ROWS, st);
+                launch_logprob_rows(a, st);
+            }
+        } else {
+            gemm(e, PK_PF_GEMM, hn, D, e->lm_head, nullptr, 0, lg, e->Vpad, (int)rows, ACT_NONE, 0, st);
+            HIPCHECK(hipMemcpy2DAsync(dev_scores, (size_t)c.vocab * sizeof(bf16_t), lg, (size_t)e->Vpad * sizeof(bf16_t),
+                                      (size_t)c.vocab * sizeof(bf16_t), rows, hipMemcpyDeviceToDevice, st));
+        }
     }
     // only the last prompt row feeds ln_f + lm_head (HF computes all rows; same result)
     prof_mark(e, PK_PF_ROWS, st);
@@ -577,6 +612,40 @@ extern "C" int sv_forward_logits(sv_engine* e, const void* dev_embeds, int32_t B
     fill_i32(e->positions, S, B, st);
     e->cached_B = B;
     HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sv_forward_logprobs(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S, int32_t n_keep,
+                                   const int32_t* dev_targets, float temperature, float* dev_logprob, float* dev_logsumexp,
+                                   float* dev_entropy, int32_t* dev_argmax, sv_stream stream) {
+    // (the checks that need no engine come first: they are the same on a machine without a GPU)
+    if (!dev_embeds || !dev_targets) return fail(SV_EINVAL, "sv_forward_logprobs: null embeds / targets");
+    if (!dev_logprob && !dev_logsumexp && !dev_entropy && !dev_argmax) return fail(SV_EINVAL, "sv_forward_logprobs: every output pointer is null");
+    if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail(SV_EINVAL, "sv_forward_logprobs: temperature must be finite and > 0");
+    if (S < 1 || n_keep < 1 || n_keep > S) return fail(SV_EINVAL, "sv_forward_logprobs: n_keep=%d must be in 1..S (S=%d)", n_keep, S);
+    SVCHECK(check_ready(e));
+    if (B < 1 || B > e->cfg.max_batch) return fail(SV_EINVAL, "sv_forward_logprobs: bad B=%d (max_batch %d)", B, e->cfg.max_batch);
+    if (S > e->cfg.max_seq_len) return fail(SV_EINVAL, "sv_forward_logprobs: S=%d out of range (max_seq_len %d)", S, e->cfg.max_seq_len);
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIPCHECK(hipSetDevice(e->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    SVCHECK(cb_guard(e, "sv_forward_logprobs"));
+    SVCHECK(assign_pages(e, B, S, st));
+    const ScoreLogprobs lp{dev_targets, 1.0f / temperature, dev_logprob, dev_logsumexp, dev_entropy, dev_argmax};
+    SVCHECK(prefill_forward(e, (const bf16_t*)dev_embeds, B, S, st, n_keep, nullptr, nullptr, &lp));
+    fill_i32(e->positions, S, B, st);
+    e->cached_B = B;
+    HIPCHECK(hipGetLastError());
+    // the kernel's flag: a target outside the vocabulary (its logprob is NaN) / a row without a finite logit (all of its outputs are NaN)
+    int32_t flag[2] = {0, 0};
+    HIPCHECK(hipMemcpyAsync(flag, e->score_chunk_ws + (size_t)e->score_chunk_alloc * e->Vpad, sizeof(flag), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    if (flag[0] & 2)
+        return fail(SV_EHIP, "sv_forward_logprobs: a row of logits had no finite value (NaN / Inf in the weights or inputs?); first at row %d "
+                             "(sequence %d, kept position %d)", flag[1], flag[1] / n_keep, flag[1] % n_keep);
+    if (flag[0] & 1)
+        return fail(SV_EINVAL, "sv_forward_logprobs: a target id outside [0, %d) that is not -100; first at row %d (sequence %d, kept position %d)",
+                    e->cfg.vocab, flag[1], flag[1] / n_keep, flag[1] % n_keep);
     return 0;
 }
 

@@ -167,6 +167,11 @@ struct sv_engine {
     BeamScorer beam;
     bf16_t* score_ws = nullptr;      // scoring forward: kept hidden rows, their ln_f, bf16 logits [rows][Vpad]
     size_t score_elems = 0;
+    // sv_forward_logprobs: the lm_head runs over the kept rows in chunks of score_chunk_rows rows into this workspace ([chunk][Vpad] bf16 + the kernel's
+    // int32[2] flag behind it), logprob_rows reads the chunk back; allocated on first use, a function of the chunk size alone -- never of B x n_keep
+    bf16_t* score_chunk_ws = nullptr;
+    int score_chunk_alloc = 0;       // rows the workspace holds
+    int score_chunk_rows = 0;        // sv_debug_set_score_chunk_rows; 0 = SV_SCORE_CHUNK_ROWS
     int cached_B = 0;
     int dbg_pos_hi = 0;             // sv_debug_kv_load / sv_debug_attn_decode: upper bound of positions[] (host side), kept below max_seq_len
     int num_cus = 256;
@@ -235,8 +240,13 @@ void prof_mark(sv_engine* e, int kind, hipStream_t st);
 int attn_max_splits_of(int max_batch, int nkv, int num_cus);
 int attn_groups_per_block_of(int max_batch, int nkv, int num_cus);
 int assign_pages(sv_engine* e, int B, int total_len, hipStream_t st);
+// rows per lm_head chunk of sv_forward_logprobs: a multiple of 256 (the big-M tile height: a chunk boundary never cuts a tile); 4096 rows x Vpad ~ 49.2 k
+// bf16 = 403 MB at StarVector's vocabulary -- the fastest of 512 / 1024 / 2048 / 4096 measured (profiles/score_logprobs.md; DESIGN.md "Scoring without logits")
+#define SV_SCORE_CHUNK_ROWS 4096
+// what sv_forward_logprobs asks of the scoring pass instead of the logits: [B][n_keep] each, any output may be nullptr
+struct ScoreLogprobs { const int32_t* targets; float inv_t; float* logprob; float* lse; float* entropy; int32_t* argmax; };
 int prefill_forward(sv_engine* e, const bf16_t* embeds, int B, int S0, hipStream_t st, int n_keep = 0,
-                    bf16_t* dev_scores = nullptr, const int32_t* table = nullptr);
+                    bf16_t* dev_scores = nullptr, const int32_t* table = nullptr, const ScoreLogprobs* lp = nullptr);
 void decode_forward(sv_engine* e, int B, hipStream_t st);
 void attn_decode_args(sv_engine* e, int layer, int B, const float* ws, int splitk, const bf16_t* bias, bf16_t* out_xp, AttnDecodeArgs& ad);
 int check_ready(sv_engine* e);

@@ -1,5 +1,6 @@
 // Host driver, part 5 of 5: host-side planning probes (callable without a GPU), the pre-processing ABI, decode-step profiling
 // and the single-operator test surfaces (sv_op_*, sv_bench_*).
+#include <cmath>
 #include "engine_internal.h"
 
 struct TmpBufs {
@@ -852,6 +853,42 @@ extern "C" int sv_op_cb_select(const float* logits, int32_t B, int32_t V, int32_
     HIPCHECK(hipMemcpyAsync(ho.data(), dout, ho.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
     for (int b = 0; b < B; ++b) out[b] = ho[(size_t)b * ld_out + hist_len[b]];
+    return 0;
+}
+
+// sv_forward_logprobs runs its lm_head over `rows` rows at a time (0 = the default); the workspace follows at the next call
+extern "C" int sv_debug_set_score_chunk_rows(sv_engine* e, int32_t rows) {
+    if (rows < 0 || rows > 65536 || rows % 256) return fail(SV_EINVAL, "sv_debug_set_score_chunk_rows: rows=%d must be 0 or a multiple of 256 up to 65536", rows);
+    if (!e) return fail(SV_EINVAL, "null engine");
+    std::lock_guard<std::mutex> lk(e->mu);
+    e->score_chunk_rows = rows;
+    return 0;
+}
+
+// logprob_rows_kernel (score.hip) on caller-given rows
+extern "C" int sv_op_logprob_rows(const void* dev_logits_bf16, int32_t R, int32_t V, int32_t ld, const int32_t* dev_targets, float temperature,
+                                  float* dev_logprob, float* dev_logsumexp, float* dev_entropy, int32_t* dev_argmax, int32_t* host_flag2,
+                                  sv_stream stream) {
+    if (!dev_logits_bf16 || R < 1 || R > (1 << 22) || V < 1 || ld < V || (ld & 7) || ((uintptr_t)dev_logits_bf16 & 15))
+        return fail(SV_EINVAL, "sv_op_logprob_rows: bad argument (rows 16-byte aligned, ld a multiple of 8 and >= V)");
+    if (!dev_logprob && !dev_logsumexp && !dev_entropy && !dev_argmax) return fail(SV_EINVAL, "sv_op_logprob_rows: every output pointer is null");
+    if (dev_logprob && !dev_targets) return fail(SV_EINVAL, "sv_op_logprob_rows: logprob asked for without targets");
+    if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail(SV_EINVAL, "sv_op_logprob_rows: temperature must be finite and > 0");
+    hipStream_t st = (hipStream_t)stream;
+    TmpBufs tmp;
+    int32_t* flag;
+    SVCHECK(tmp.get(&flag, 2));
+    const int32_t flag0[2] = {0, 0x7fffffff};
+    HIPCHECK(hipMemcpy(flag, flag0, sizeof(flag0), hipMemcpyHostToDevice));
+    LogprobArgs a;
+    a.logits = (const bf16_t*)dev_logits_bf16; a.ld = ld; a.V = V; a.R = R; a.targets = dev_targets; a.inv_t = 1.0f / temperature;
+    a.logprob = dev_logprob; a.lse = dev_logsumexp; a.entropy = dev_entropy; a.argmax = dev_argmax; a.bad = flag; a.row0 = 0;
+    launch_logprob_rows(a, st);
+    HIPCHECK(hipGetLastError());
+    int32_t hf[2] = {0, 0};
+    HIPCHECK(hipMemcpyAsync(hf, flag, sizeof(hf), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    if (host_flag2) { host_flag2[0] = hf[0]; host_flag2[1] = hf[0] ? hf[1] : -1; }
     return 0;
 }
 

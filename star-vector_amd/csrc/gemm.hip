@@ -1082,13 +1082,14 @@ static int autotune_gemm(const GemmArgs& a, hipStream_t st, const GemmPlan& mode
     int dev_id = 0;
     if (hipGetDevice(&dev_id) != hipSuccess) { (void)hipGetLastError(); return fallback; }
     TuneScratch& ts = g_tune_scratch[dev_id];           // (the caller holds g_tune_mu)
-    if (need > ts.bytes) {
+    const bool in_place = a.tune_in_place && !a.R;      // nothing reads C: the timing runs may write it (no scratch: GemmArgs::tune_in_place)
+    if (!in_place && need > ts.bytes) {
         void* bigger = nullptr;
         if (hipMalloc(&bigger, need + need / 2) != hipSuccess) { (void)hipGetLastError(); return fallback; }
         if (ts.p) (void)hipFree(ts.p);
         ts.p = bigger; ts.bytes = need + need / 2;
     }
-    void* scratch = ts.p;
+    void* scratch = in_place ? a.C : ts.p;
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return fallback;
     GemmArgs t = a;
@@ -1168,7 +1169,8 @@ static int autotune_small(const GemmArgs& a, hipStream_t st, const GemmPlan& mod
     int dev_id = 0;
     if (hipGetDevice(&dev_id) != hipSuccess) { (void)hipGetLastError(); return 0; }
     TuneScratch& ts = g_tune_scratch[dev_id];           // (the caller holds g_tune_mu)
-    if (need > ts.bytes) {
+    const bool in_place = a.tune_in_place && !a.R;
+    if (!in_place && need > ts.bytes) {
         void* bigger = nullptr;
         if (hipMalloc(&bigger, need + need / 2) != hipSuccess) { (void)hipGetLastError(); return 0; }
         if (ts.p) (void)hipFree(ts.p);
@@ -1177,7 +1179,7 @@ static int autotune_small(const GemmArgs& a, hipStream_t st, const GemmPlan& mod
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return 0;
     GemmArgs t = a;
-    t.C = ts.p;
+    t.C = in_place ? a.C : ts.p;
     t.tail_mark = nullptr;
     float ms[2] = {1e30f, 1e30f};
     for (int form = 0; form < 2; ++form) {

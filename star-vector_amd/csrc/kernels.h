@@ -43,6 +43,8 @@ struct GemmArgs {
     int seq_tail = 0;                // set by the launcher for the remainder launch: row i -> (i / seq_tail) * seq_rows + seq_rows - seq_tail + i % seq_tail
     int splitk_rows = 0;             // 1: the M rows (compact, contiguous) are LAST rows of sequences of seq_rows rows (the pruned last prompt layer): they take
                                      //    the kernel the same rows take inside the full problem (split-K remainder kernel where gemm_seq_form holds)
+    int tune_in_place = 0;           // 1 (and no residual operand): the tuner's timing runs write C itself instead of a scratch output of M x ldc elements
+                                     //    (the chunked lm_head of the scoring forward: its footprint must not grow with rows x vocab; C is overwritten anyway)
 };
 // r = rows a sequence of S rows leaves over its 256-row tiles when that is a handful (32 sequences leave at most 96 rows) and a full tile exists; else 0
 inline int seq_peel_rows(int S) { const int r = S % 256; return (S > 256 && r >= 1 && r <= 3) ? r : 0; }
@@ -421,6 +423,18 @@ struct CbStepArgs {
     const CbBias* bias;
 };
 void launch_cb_step(const CbStepArgs& a, int nblocks, hipStream_t st);
+
+// ---- per-token log-probabilities of the scoring forward (score.hip): one block per row of bf16 logits, fp32 arithmetic over
+// x_i = float(logit_i) * inv_t.  logits rows start 16-byte aligned and ld % 8 == 0.  Every output may be nullptr.
+struct LogprobArgs {
+    const bf16_t* logits; int ld; int V; int R;     // [R][ld], V valid columns
+    const int32_t* targets;                         // [R]; -100 = ignore (logprob 0); nullptr = every row ignored
+    float inv_t;                                    // 1 / temperature, > 0
+    float* logprob; float* lse; float* entropy; int32_t* argmax;      // [R]: x_target - lse | lse | entropy | first maximal index
+    int32_t* bad;                                   // device int32[2] or nullptr: [0] |= 1 (a target outside [0, V) and not -100: logprob NaN) / 2 (a row
+    int row0;                                       //   without a finite logit: all outputs NaN, argmax -1); [1] = min(row0 + row) over such rows
+};
+void launch_logprob_rows(const LogprobArgs& a, hipStream_t st);
 
 // ---- image pre-processing (preprocess.hip): uint8 HWC (3 or 4 channels) -> float32 [3][S][S], returns a hipError_t value
 int preprocess_image(const uint8_t* dev_pixels, int width, int height, int channels, int out_size, int recipe,

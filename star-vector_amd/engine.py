@@ -4,7 +4,7 @@ from __future__ import annotations
 import ctypes as C
 import threading
 from dataclasses import dataclass
-from typing import Dict, Iterable, List, Optional, Sequence, Tuple
+from typing import Dict, Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -53,6 +53,14 @@ class EngineConfig:
                             n_layer=32, n_head=36, n_inner=18432, vocab=49152 + 5, n_positions=16384,
                             max_batch=max_batch, max_seq_len=max_seq_len, arch="v2", n_kv_head=4, rope_theta=1e6,
                             vit_mlp=4096, vit_eps=1e-6, sliding_window=4096)
+
+
+class TokenLogprobs(NamedTuple):
+    """`HipEngine.forward_logprobs`: [B, n] tensors; `entropy` / `argmax` are None unless asked for."""
+    logprobs: torch.Tensor                     # float32: log softmax(logits / temperature) at the target id; 0 where the target is -100
+    logsumexp: torch.Tensor                    # float32: logsumexp(logits / temperature)
+    entropy: Optional[torch.Tensor] = None     # float32: entropy of softmax(logits / temperature)
+    argmax: Optional[torch.Tensor] = None      # int32: the lowest index holding the row's maximum
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -239,6 +247,33 @@ class HipEngine:
         out = torch.empty(B, n, self.cfg.vocab, dtype=torch.bfloat16, device=x.device)
         check(self.lib.sv_forward_logits(self._h, _ptr(x), B, S, n, _ptr(out), _stream()), "sv_forward_logits")
         return out
+
+    def forward_logprobs(self, inputs_embeds: torch.Tensor, targets: torch.Tensor, num_logits_to_keep: int = 0,
+                         temperature: float = 1.0, entropy: bool = False, argmax: bool = False) -> TokenLogprobs:
+        """Scoring forward without logits: for each of the last n = num_logits_to_keep positions (0 = all) the log-probability of
+        targets[b, j] under softmax(logits / temperature), the logits being the bf16 rows `forward_logits` returns, in fp32
+        (sv_forward_logprobs).  targets: integer [B, n]; -100 = ignore (log-prob 0).  Device memory does not grow with B * n * vocab."""
+        x = _need(inputs_embeds, torch.bfloat16, "inputs_embeds")
+        B, S, D = x.shape
+        if D != self.cfg.hidden:
+            raise ValueError("inputs_embeds hidden size mismatch")
+        n = int(num_logits_to_keep) if num_logits_to_keep and num_logits_to_keep > 0 else S
+        if tuple(targets.shape) != (B, n):
+            raise ValueError(f"targets must be [B, n] = [{B}, {n}], got {tuple(targets.shape)}")
+        if targets.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"targets must be int32 or int64, got {targets.dtype}")
+        t = _need(targets.to(torch.int32), torch.int32, "targets")
+        lp = torch.empty(B, n, dtype=torch.float32, device=x.device)
+        lse = torch.empty(B, n, dtype=torch.float32, device=x.device)
+        ent = torch.empty(B, n, dtype=torch.float32, device=x.device) if entropy else None
+        am = torch.empty(B, n, dtype=torch.int32, device=x.device) if argmax else None
+        check(self.lib.sv_forward_logprobs(self._h, _ptr(x), B, S, n, _ptr(t), float(temperature), _ptr(lp), _ptr(lse), _ptr(ent),
+                                           _ptr(am), _stream()), "sv_forward_logprobs")
+        return TokenLogprobs(lp, lse, ent, am)
+
+    def set_score_chunk_rows(self, rows: int) -> None:
+        """Rows per lm_head chunk of `forward_logprobs` (a multiple of 256; 0 = default).  Test surface: the outputs do not depend on it."""
+        check(self.lib.sv_debug_set_score_chunk_rows(self._h, int(rows)), "sv_debug_set_score_chunk_rows")
 
     def decode_step(self, tokens: torch.Tensor) -> torch.Tensor:
         tokens = _need(tokens.to(torch.int32), torch.int32, "tokens")
@@ -781,6 +816,25 @@ def op_argmax(logits):
     out = torch.empty(B, dtype=torch.int32, device=logits.device)
     check(lib.sv_op_argmax(_ptr(logits), B, V, V, _ptr(out), _stream()))
     return out
+
+
+def op_logprob_rows(logits, targets, temperature: float = 1.0, valid: Optional[int] = None):
+    """logprob_rows_kernel on caller-given bf16 rows [R, ld] (ld a multiple of 8), `valid` = V columns count (default ld); targets
+    int32 [R].  Returns (logprob, logsumexp, entropy, argmax, (flag, first flagged row))."""
+    lib = _lib.load()
+    logits = _need(logits, torch.bfloat16, "logits")
+    R, ld = logits.shape
+    V = ld if valid is None else int(valid)
+    targets = _need(targets.to(torch.int32), torch.int32, "targets")
+    if targets.numel() != R:
+        raise ValueError("one target per row")
+    dev = logits.device
+    lp, lse, ent = (torch.empty(R, dtype=torch.float32, device=dev) for _ in range(3))
+    am = torch.empty(R, dtype=torch.int32, device=dev)
+    flag = (C.c_int32 * 2)()
+    check(lib.sv_op_logprob_rows(_ptr(logits), R, V, ld, _ptr(targets), float(temperature), _ptr(lp), _ptr(lse), _ptr(ent), _ptr(am),
+                                 flag, _stream()), "sv_op_logprob_rows")
+    return lp, lse, ent, am, (int(flag[0]), int(flag[1]))
 
 
 def op_cb_select(logits, requests: Sequence[dict], history=None):

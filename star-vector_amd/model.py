@@ -969,6 +969,51 @@ class StarVectorForCausalLM(nn.Module):
                     "byte_tokenizer_fallback=True to use the byte-level stand-in (synthetic weights only)")
         return cls(cfg, state_dict=sd, tokenizer=tokenizer)
 
+    @staticmethod
+    def _scoring_mask_lead(attention_mask, shape):
+        """The mask analysis of the scoring passes (`forward`, `completion_logprobs`): None when no row has leading pads, else the
+        number of leading pads per row.  Raises for masks that are not left / right padding."""
+        if attention_mask is None or bool((attention_mask == 1).all()):
+            return None
+        # Right padding (completions padded after their EOS, what a GRPO trainer passes): under the causal mask a real
+        # position never sees a later key and HF's positions (cumsum(mask) - 1) equal the plain index for it, so the
+        # logits of every real position are those of the unmasked run.  Rows at padded positions are unspecified (HF's
+        # differ there too from any unpadded run; the caller multiplies them away with the same mask).
+        # Left padding: the pinned transformers (4.49; gpt_bigcode/modeling_gpt_bigcode.py:980-983) masks the padded keys and
+        # numbers positions by cumsum(mask) - 1 inside the model's forward, i.e. a left-padded row IS the same row with its
+        # padding removed (pinned against HF: oracle/make_golden.py::run_forward_case, tests/golden/tiny_forward) -> rows are
+        # grouped by their number of leading pads, scored without them, and their logits put back at the real positions.
+        m = attention_mask.to(torch.bool)
+        if m.shape != tuple(shape):
+            raise ValueError(f"attention_mask {tuple(m.shape)} does not cover inputs_embeds {tuple(shape)}")
+        lead = (m.cumsum(1) == 0).sum(1)                                  # leading pads per row
+        if bool((lead >= m.shape[1]).any()):
+            empty = (lead >= m.shape[1]).nonzero().flatten().tolist()
+            raise ValueError(f"attention_mask rows {empty} are all zeros: a row needs at least one real position to be scored")
+        idx = torch.arange(m.shape[1], device=m.device).unsqueeze(0)
+        real = idx >= lead.unsqueeze(1)
+        if bool((m[:, 1:] & ~m[:, :-1] & real[:, :-1]).any()):            # a 1 after a 0 behind the leading pads
+            raise NotImplementedError("attention masks with holes are not built for the scoring forward (left / right padding only)")
+        return lead if bool(lead.any()) else None
+
+    def _run_scoring(self, fn):
+        """One engine call of a scoring pass: queued as an exclusive job when a ContinuousBatcher shares the engine, else under the
+        engine's call lock."""
+        lm = getattr(getattr(self.model, "svg_transformer", None), "transformer", None)
+        batcher = getattr(lm, "batcher", None)
+        if batcher is not None and not _in_exclusive_job():
+            # requests share the engine's decode loop: the scoring pass wants the engine to itself (it would fail with SV_ESTATE
+            # while slots are live) -> queue it as an exclusive job, FIFO with the generation requests
+            def call():
+                _EXCLUSIVE.active = True
+                try:
+                    return fn()
+                finally:
+                    _EXCLUSIVE.active = False
+            return batcher.run_exclusive(call)
+        with (getattr(self.engine, "call_lock", None) or contextlib.nullcontext()):
+            return fn()
+
     @torch.no_grad()
     def forward(self, vision_embeds, input_ids, num_generations, attention_mask, num_logits_to_keep):
         """starvector_arch.py:161-184, inference mode (no autograd graph: the engine holds no torch parameters): logits of
@@ -976,46 +1021,11 @@ class StarVectorForCausalLM(nn.Module):
         completion_embeds = self.model._get_embeddings(input_ids)
         inputs_embeds = torch.cat([vision_embeds.repeat(num_generations, 1, 1).to(completion_embeds.dtype),
                                    completion_embeds], dim=1)
-        lead = None
-        if attention_mask is not None and not bool((attention_mask == 1).all()):
-            # Right padding (completions padded after their EOS, what a GRPO trainer passes): under the causal mask a real
-            # position never sees a later key and HF's positions (cumsum(mask) - 1) equal the plain index for it, so the
-            # logits of every real position are those of the unmasked run.  Rows at padded positions are unspecified (HF's
-            # differ there too from any unpadded run; the caller multiplies them away with the same mask).
-            # Left padding: the pinned transformers (4.49; gpt_bigcode/modeling_gpt_bigcode.py:980-983) masks the padded keys and
-            # numbers positions by cumsum(mask) - 1 inside the model's forward, i.e. a left-padded row IS the same row with its
-            # padding removed (pinned against HF: oracle/make_golden.py::run_forward_case, tests/golden/tiny_forward) -> rows are
-            # grouped by their number of leading pads, scored without them, and their logits put back at the real positions.
-            m = attention_mask.to(torch.bool)
-            if m.shape != inputs_embeds.shape[:2]:
-                raise ValueError(f"attention_mask {tuple(m.shape)} does not cover inputs_embeds {tuple(inputs_embeds.shape[:2])}")
-            lead = (m.cumsum(1) == 0).sum(1)                                  # leading pads per row
-            if bool((lead >= m.shape[1]).any()):
-                empty = (lead >= m.shape[1]).nonzero().flatten().tolist()
-                raise ValueError(f"attention_mask rows {empty} are all zeros: a row needs at least one real position to be scored")
-            idx = torch.arange(m.shape[1], device=m.device).unsqueeze(0)
-            real = idx >= lead.unsqueeze(1)
-            if bool((m[:, 1:] & ~m[:, :-1] & real[:, :-1]).any()):            # a 1 after a 0 behind the leading pads
-                raise NotImplementedError("attention masks with holes are not built for the scoring forward (left / right padding only)")
-            if not bool(lead.any()):
-                lead = None
+        lead = self._scoring_mask_lead(attention_mask, inputs_embeds.shape[:2])
         emb16, keep = inputs_embeds.to(torch.bfloat16), int(num_logits_to_keep or 0)
-        lm = getattr(getattr(self.model, "svg_transformer", None), "transformer", None)
-        batcher = getattr(lm, "batcher", None)
 
         def score(e16):
-            if batcher is not None and not _in_exclusive_job():
-                # requests share the engine's decode loop: the scoring pass wants the engine to itself (it would fail with SV_ESTATE
-                # while slots are live) -> queue it as an exclusive job, FIFO with the generation requests
-                def call():
-                    _EXCLUSIVE.active = True
-                    try:
-                        return self.engine.forward_logits(e16, keep)
-                    finally:
-                        _EXCLUSIVE.active = False
-                return batcher.run_exclusive(call)
-            with (getattr(self.engine, "call_lock", None) or contextlib.nullcontext()):
-                return self.engine.forward_logits(e16, keep)
+            return self._run_scoring(lambda: self.engine.forward_logits(e16, keep))
 
         if lead is None:
             logits = score(emb16)
@@ -1038,6 +1048,59 @@ class StarVectorForCausalLM(nn.Module):
             import types
             return types.SimpleNamespace(loss=None, logits=logits, past_key_values=None, hidden_states=None,
                                          attentions=None, cross_attentions=None)
+
+    @torch.no_grad()
+    def completion_logprobs(self, vision_embeds, input_ids, num_generations, attention_mask, num_logits_to_keep,
+                            temperature: float = 1.0, return_entropy: bool = False):
+        """What a GRPO trainer computes from `forward`'s logits, without the logits: float32 [B, n], out[b, j] = the log-probability
+        of input_ids[b, -n + j] given everything before it -- selective_log_softmax(forward(...).logits[:, :-1] / temperature, ids)
+        with the softmax in fp32 over the bf16 logits (sv_forward_logprobs: device memory does not grow with B * n * vocab).
+        n = num_logits_to_keep (0 / None: every completion token that has a position before it).  Padding as in `forward`: an
+        entry whose token is right padding is 0; left-padded rows are scored without their pads; masks with holes raise
+        NotImplementedError.  return_entropy: also the entropy [B, n] of the distribution each token was drawn from (0 at pads)."""
+        completion_embeds = self.model._get_embeddings(input_ids)
+        inputs_embeds = torch.cat([vision_embeds.repeat(num_generations, 1, 1).to(completion_embeds.dtype),
+                                   completion_embeds], dim=1)
+        B, S = inputs_embeds.shape[:2]
+        L = input_ids.shape[1]
+        n = int(num_logits_to_keep or 0) or (L if S > L else L - 1)
+        if n < 1 or n > L or n + 1 > S:
+            raise ValueError(f"num_logits_to_keep ({n}) must be in 1..{min(L, S - 1)}: every scored token needs a position before it")
+        if attention_mask is not None and tuple(attention_mask.shape) != (B, S):
+            raise ValueError(f"attention_mask {tuple(attention_mask.shape)} does not cover inputs_embeds {(B, S)}")
+        lead = self._scoring_mask_lead(attention_mask, (B, S))
+        if lead is not None and int(lead.max()) + n + 1 > S:
+            raise ValueError(f"num_logits_to_keep ({n}) reaches into the left padding of a row ({int(lead.max())} pads of {S})")
+        emb16 = inputs_embeds.to(torch.bfloat16)
+        # n + 1 rows are kept: row i predicts the token at position S - n + i; the last row predicts nothing (-100)
+        targets = torch.full((B, n + 1), -100, dtype=torch.int32, device=emb16.device)
+        targets[:, :n] = input_ids[:, L - n:].to(device=emb16.device, dtype=torch.int32)
+        if attention_mask is not None:
+            pad = ~attention_mask.to(torch.bool)[:, S - n:].to(emb16.device)       # the token itself is padding
+            targets[:, :n] = targets[:, :n].masked_fill(pad, -100)
+
+        def score(e16, tg):
+            r = self._run_scoring(lambda: self.engine.forward_logprobs(e16, tg, n + 1, temperature, return_entropy))
+            return r.logprobs, r.entropy
+
+        if lead is None:
+            lp, ent = score(emb16, targets)
+        else:
+            lp = torch.zeros(B, n + 1, dtype=torch.float32, device=emb16.device)
+            ent = torch.zeros_like(lp) if return_entropy else None
+            for pads in sorted(set(lead.tolist())):
+                rows = (lead == pads).nonzero().flatten().to(emb16.device)
+                a, h = score(emb16[rows, pads:].contiguous(), targets[rows].contiguous())
+                lp[rows] = a
+                if return_entropy:
+                    ent[rows] = h
+        lp = lp[:, :n].contiguous()
+        if not return_entropy:
+            return lp
+        ent = ent[:, :n]
+        if attention_mask is not None:
+            ent = ent.masked_fill(pad, 0.0)
+        return lp, ent.contiguous()
 
     def generate_im2svg(self, batch, **kwargs):           # starvector_arch.py:186-187
         return self.model.generate_im2svg(batch, **kwargs)
