@@ -223,6 +223,21 @@ int  sv_preprocess_images(const uint8_t* const* dev_pixels, const int32_t* width
  * bf16 lm_head produces). */
 int  sv_prefill(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, float* dev_logits,
                 sv_stream stream);
+/* ---- ragged prompt pass: B sequences of DIFFERENT lengths in one pass.  dev_embeds_packed: the sequences' inputs_embeds back to back,
+ * [sum(host_lens)][hidden] bf16 -- no padding row is computed or stored; host_lens: int32 [B] on the host, each in 1 .. max_seq_len.
+ * Contract: for every sequence the last-row logits, the K / V entries in its pages and every token generated afterwards are BIT-IDENTICAL
+ * to the same sequence alone through the rectangular entry point with S0 = host_lens[b]; with all lengths equal the ragged entry points
+ * return exactly what the rectangular ones return.
+ *   sv_prefill_ragged    sv_prefill: logits [B, vocab] fp32 of every sequence's last row; sv_decode_step continues every row at its own position
+ *   sv_generate_ragged   sv_generate_ex with HF's padded-batch semantics: sp->max_length counts from the LONGEST prompt (HF counts the budget
+ *                        from the padded length), so every row gets max_new = max_length - max(host_lens) new tokens.  Greedy, sampling,
+ *                        repetition_penalty, the row-0 stop, EOS / pad, streaming, outs, and num_beams 2..8 (beam search / beam-sample; the
+ *                        shared prompt pages and the cached length are per request).  outs may be NULL.
+ *   sv_cb_admit_ragged   sv_cb_admit for n requests of prompt lengths host_lens[i] in ONE prompt pass; SV_EBUSY (nothing admitted) when
+ *                        slots or KV pages are short.
+ * SV_EINVAL before any device work for null pointers, B out of range, a length < 1 or > max_seq_len, max(len) + max_new > max_seq_len. */
+int  sv_prefill_ragged(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, float* dev_logits,
+                       sv_stream stream);
 /* Scoring forward = `StarVectorForCausalLM.forward(vision_embeds, input_ids, ..., num_logits_to_keep)`
  * (starvector_arch.py:161-184; GRPO's log-prob pass, inference mode): the decoder over inputs_embeds [B,S,hidden] bf16
  * (all-ones mask) and the lm_head over the LAST n_keep positions of every sequence.
@@ -275,6 +290,8 @@ typedef struct sv_generate_outputs {
  * slab, and for the beam-only pointers without num_beams > 1. */
 int  sv_generate_ex(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const sv_sampling* sp,
                     const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream);
+int  sv_generate_ragged(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, const sv_sampling* sp,
+                        const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream);
 /* ---- continuous batching (the reference worker's 5 concurrent requests, serve/model_worker.py:161-172,
  * 216-229, as ONE decode loop).  Every row ("slot") of the engine's batch is an independent request: own sampling parameters,
  * budget, EOS, stop sequence (the reference's row-0 stop, starvector_base.py:9-20, is right for one request per generate call
@@ -314,6 +331,8 @@ typedef struct sv_cb_request {
 } sv_cb_request;
 int  sv_cb_admit(sv_engine* e, const void* dev_embeds, int32_t n, int32_t S0, const sv_cb_request* reqs, int32_t* slots_out,
                  sv_stream stream);
+int  sv_cb_admit_ragged(sv_engine* e, const void* dev_embeds_packed, int32_t n, const int32_t* host_lens, const sv_cb_request* reqs,
+                        int32_t* slots_out, sv_stream stream);
 int  sv_cb_step(sv_engine* e, int32_t n_steps, int32_t* n_live, sv_stream stream);
 int  sv_cb_poll(sv_engine* e, int32_t* host_live, int32_t* host_steps, int32_t capacity);
 int  sv_cb_read(sv_engine* e, int32_t slot, int32_t first, int32_t count, int64_t* host_tokens);

@@ -99,6 +99,16 @@ int  sv_debug_set_linear_seq_rows(int32_t seq_rows);
 /*   sv_debug_gemm_seq_form    1 / 0: does the projection (N, K, act) take that per-sequence form for sequences of S rows?  Host arithmetic only
      (callable without a GPU); a function of S and the projection alone, never of the batch: a sequence's tokens do not depend on its neighbours. */
 int  sv_debug_gemm_seq_form(int32_t S, int32_t N, int32_t K, int32_t act);
+/*   sv_debug_ragged_plan      what the RAGGED prompt pass (sv_prefill_ragged and friends) decides for B sequences of lengths lens[0..B), packed back
+     to back, at the projection (N, K, act).  Host arithmetic only.  rows_out [capacity]: the packed row indices (ascending) that go through the
+     split-K remainder kernel -- the last S % 256 rows of every sequence for which sv_debug_gemm_seq_form(S, N, K, act) holds; every other row takes an
+     ascending-k kernel.  last_out [capacity]: the sequences whose LAST row is such a row (the compact rows of the pruned last layer).  out4 =
+     {rows listed, sequences listed, attention blocks of q_tile query rows counted from each sequence's first row, 32-token KV-write blocks}.
+     capacity >= 3 * B; q_tile 32 or 128 (grouped-query heads in fours / one head per block). */
+int  sv_debug_ragged_plan(const int32_t* lens, int32_t B, int32_t N, int32_t K, int32_t act, int32_t q_tile, int32_t* rows_out,
+                          int32_t* last_out, int32_t capacity, int32_t* out4);
+/*   sv_debug_prompt_passes    prompt passes (rectangular and ragged, continuous-batching admits included) this engine has run so far */
+int  sv_debug_prompt_passes(sv_engine* e, int64_t* out);
 /* The decode attention (gpt_bigcode/modeling_gpt_bigcode.py:151-285, llm/starcoder2.py:22-27 sliding window) on
  * its own, over the engine's real paged KV pool, block table and context-split plan.  Test surface: the caller chooses q / K / V.
  *   sv_debug_kv_load     dev_kv bf16 [B][S][2*n_kv*head_dim] (k heads | v heads, K as cached = after RoPE) -> pages of `layer`;

@@ -106,7 +106,8 @@ class ContinuousBatcher:
 
     # ---- scheduler thread ----------------------------------------------------------------------------------------------
     def _admit(self) -> int:
-        """Move waiting requests into free slots, one `cb_admit` per prompt length (the prompt pass is rectangular).
+        """Move waiting requests into free slots: ONE `cb_admit` -- one ragged prompt pass -- for all of them whatever their prompt
+        lengths where the engine offers it (`prefill_ragged`), else one `cb_admit` per prompt length (the rectangular prompt pass).
         Returns how many requests left the queue (admitted, or failed alone)."""
         moved = 0
         with self._lock:
@@ -115,15 +116,19 @@ class ContinuousBatcher:
                 if r.exclusive is not None:
                     break
                 waiting.append(r)
+        ragged = hasattr(self.engine, "prefill_ragged")
         by_len: Dict[int, List[_Request]] = {}
         for r in waiting:
-            by_len.setdefault(int(r.emb.shape[1]), []).append(r)
+            by_len.setdefault(0 if ragged else int(r.emb.shape[1]), []).append(r)
         for S0, group in by_len.items():
             room = self.engine.cfg.max_batch - len(self._active)
             group = group[:room]
             while group:
                 try:
-                    slots = self.engine.cb_admit(torch.cat([r.emb for r in group], 0), [r.params for r in group])
+                    if ragged:
+                        slots = self.engine.cb_admit([r.emb[0] for r in group], [r.params for r in group])
+                    else:
+                        slots = self.engine.cb_admit(torch.cat([r.emb for r in group], 0), [r.params for r in group])
                 except StarVectorBusy:
                     group = group[:-1]              # KV pages are short: try fewer, the rest waits for a release
                     continue

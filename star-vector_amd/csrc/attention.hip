@@ -26,7 +26,9 @@ __device__ __forceinline__ int swap23(int x) { return (x & ~0xC) | ((x & 4) << 1
 // 1.04 vs 0.96 ms of TTFT on a box whose GEMMs ran 8 % slower).  The launch is bound by instruction issue per SIMD -- per 32 x 64 tile pair ~300 VALU
 // instructions of mask / exp / rescale / pack next to 16 MFMAs -- not by the global -> LDS -> barrier chain the restructure removed; 45 of those
 // tile pairs cover 257 x 257 scores where 32.3 would do (the 257th key and the 257th row each cost a whole tile).  profiles/SUMMARY_r05.md; removed.)
-template <int D, int HPB>
+// RAG: the ragged form (AttnPrefillArgs::rag_seq / ::rag_blocks) -- block x works for entry x of the host-built (sequence, query tile) list;
+// the sequence's first packed row and its length come from its descriptor, everything below is the rectangular kernel's code with those two values
+template <int D, int HPB, bool RAG = false>
 __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnPrefillArgs p) {      // two blocks per CU: <= 256 registers
 
     constexpr int KSTR = D + 8;          // K tile row stride (elements): +16 B pad -> conflict-free b128
@@ -39,12 +41,21 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnPrefillArgs p)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c = lane >> 5;
-    const int b = blockIdx.z;
-    const int S = p.S;
+    int S, qtile;
+    size_t row0;                         // first row of the block's sequence in the token-major buffers
+    if constexpr (RAG) {
+        const int sq = p.rag_blocks[2 * blockIdx.x];
+        qtile = p.rag_blocks[2 * blockIdx.x + 1];
+        row0 = (size_t)p.rag_seq[2 * sq];
+        S = p.rag_seq[2 * sq + 1];
+    } else {
+        S = p.S;
+        qtile = blockIdx.x + p.q_tile0;
+        row0 = (size_t)blockIdx.z * S;
+    }
     int head, q0, qblock_end;
     // (q_tile0 > 0: only the trailing query tiles, e.g. the last prompt row's.  Round 6 numbered the causal tiles longest-first -- the last query tile walks 5 key tiles,
     // the first 1 -- so that the short ones fill the end of the launch: 41.4 vs 40.8 us per layer, nothing; profiles/prefill_small_r06.log.)
-    const int qtile = blockIdx.x + p.q_tile0;
     if (HPB == 1) {
         head = blockIdx.y;
         q0 = qtile * 128 + wave * 32;
@@ -61,7 +72,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnPrefillArgs p)
     // Q fragments (B operand): lane (q = l&31, c = l>>5) holds Q[q][16 s + 8 c .. +8]
     bf16x8 qf[NKS];
     {
-        const bf16_t* qp = p.q + ((size_t)b * S + qrow) * p.q_row_stride + (size_t)head * p.q_head_stride + c * 8;
+        const bf16_t* qp = p.q + (row0 + qrow) * p.q_row_stride + (size_t)head * p.q_head_stride + c * 8;
 #pragma unroll
         for (int s = 0; s < NKS; ++s) qf[s] = as_frag(*reinterpret_cast<const uint4*>(qp + s * 16));
     }
@@ -81,8 +92,8 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnPrefillArgs p)
     const int win = p.causal ? p.window : 0;
     const int qfirst = HPB == 1 ? qtile * 128 : q0;
     const int kt0 = (win > 0 && qfirst - win + 1 > 0) ? (qfirst - win + 1) / 64 : 0;
-    const bf16_t* kbase = p.k + (size_t)b * S * p.kv_row_stride + (size_t)kvh * p.kv_head_stride;
-    const bf16_t* vbase = p.v + (size_t)b * S * p.kv_row_stride + (size_t)kvh * p.kv_head_stride;
+    const bf16_t* kbase = p.k + row0 * p.kv_row_stride + (size_t)kvh * p.kv_head_stride;
+    const bf16_t* vbase = p.v + row0 * p.kv_row_stride + (size_t)kvh * p.kv_head_stride;
 
     // K / V tiles go global -> registers -> LDS, one tile AHEAD: the loads of tile kt + 1 are issued before the MFMAs of tile kt
     // and land while they run.  (Loading inside the tile loop, V chunk by chunk with the transposing LDS writes in between,
@@ -221,7 +232,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnPrefillArgs p)
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = 1.0f / l_tot;
     if (qabs < S) {
-        bf16_t* op = p.o + ((size_t)b * S + qabs) * p.o_row_stride + (size_t)head * D;
+        bf16_t* op = p.o + (row0 + qabs) * p.o_row_stride + (size_t)head * D;
 #pragma unroll
         for (int t = 0; t < NDV; ++t)
 #pragma unroll
@@ -240,6 +251,19 @@ void launch_attn_prefill(const AttnPrefillArgs& a_in, hipStream_t st) {
     // last_rows > 0: only the query tiles that hold the last `last_rows` rows of every sequence (same bits for those rows: a row's
     // online softmax walks the key tiles in the same order whatever other query tiles are launched)
     AttnPrefillArgs a = a_in;
+    if (a.rag_blocks) {                  // ragged: one block per listed (sequence, query tile), causal by construction of the caller
+        if (a.rag_nblocks < 1) return;
+        if (mqa4) {
+            dim3 grid(a.rag_nblocks, a.H / 4, 1);
+            if (a.head_dim == 128) attn_prefill_kernel<128, 4, true><<<grid, 256, 0, st>>>(a);
+            else attn_prefill_kernel<64, 4, true><<<grid, 256, 0, st>>>(a);
+        } else {
+            dim3 grid(a.rag_nblocks, a.H, 1);
+            if (a.head_dim == 128) attn_prefill_kernel<128, 1, true><<<grid, 256, 0, st>>>(a);
+            else attn_prefill_kernel<64, 1, true><<<grid, 256, 0, st>>>(a);
+        }
+        return;
+    }
     const int qt = mqa4_tile(a) ? 32 : 128;
     const int tiles_all = (a.S + qt - 1) / qt;
     a.q_tile0 = a.last_rows > 0 ? (a.S - (a.last_rows < a.S ? a.last_rows : a.S)) / qt : 0;
@@ -276,20 +300,32 @@ __device__ __forceinline__ size_t kv_v_offset(int D, int t64, int dv) {
 // through LDS and leave as whole 16-byte fragment pieces (8 tokens of one dv column each) -- the first form stored V element by element, eight 2-byte
 // stores per thread: 8.7 us per layer for 8.5 MB of traffic.  Tokens of the group behind the prompt get V = 0 (a V column is only ever read for keys the
 // attention admits; zero is what the decode attention leaves behind a sequence's position as well).
+// RAG: block x works for entry x of the host-built {sequence, 32-token group} list; the rows of sequence b start at its descriptor's first packed row
+template <bool RAG>
 __global__ __launch_bounds__(256) void kv_write_prefill_kernel(const bf16_t* __restrict__ qkv, int row_stride, int k_off, int v_off,
                                                                char* __restrict__ pool, const int32_t* __restrict__ table,
-                                                               int max_pages, int B, int S0, int D) {
+                                                               int max_pages, int B, int S0, int D, const int32_t* __restrict__ rag_seq,
+                                                               const int32_t* __restrict__ rag_blocks) {
     extern __shared__ __attribute__((aligned(16))) char kvw_smem[];
     bf16_t* Vs = reinterpret_cast<bf16_t*>(kvw_smem);                 // [32][D + 8]
     const int VST = D + 8;
-    const int b = blockIdx.y, tok0 = blockIdx.x * 32, NC = D >> 3;
+    int b, tok0;
+    size_t row0;
+    if constexpr (RAG) {
+        b = rag_blocks[2 * blockIdx.x]; tok0 = rag_blocks[2 * blockIdx.x + 1] * 32;
+        row0 = (size_t)rag_seq[2 * b]; S0 = rag_seq[2 * b + 1];
+    } else {
+        b = blockIdx.y; tok0 = blockIdx.x * 32;
+        row0 = (size_t)b * S0;
+    }
+    const int NC = D >> 3;
     const int page_bytes = kv_page_bytes(D);
     char* page = pool + (size_t)table[b * max_pages + (tok0 >> 6)] * page_bytes;
     for (int i = threadIdx.x; i < 32 * NC; i += 256) {
         const int r = i / NC, ch = i - r * NC, tok = tok0 + r;
         uint4 kq = make_uint4(0u, 0u, 0u, 0u), vq = kq;
         if (tok < S0) {
-            const bf16_t* src = qkv + ((size_t)b * S0 + tok) * row_stride;
+            const bf16_t* src = qkv + (row0 + tok) * row_stride;
             kq = *reinterpret_cast<const uint4*>(src + k_off + ch * 8);
             vq = *reinterpret_cast<const uint4*>(src + v_off + ch * 8);
             *reinterpret_cast<uint4*>(page + kv_k_offset(D, tok & 63, ch * 8)) = kq;
@@ -312,7 +348,7 @@ __global__ __launch_bounds__(256) void kv_write_prefill_kernel(const bf16_t* __r
 }
 // rotary embedding over the prompt rows (Starcoder2: apply_rotary_pos_emb on q and k before the cache / attention)
 __global__ void rope_prefill_kernel(bf16_t* __restrict__ qkv, int row_stride, int rows, int S0, int n_heads, int D,
-                                    const float* __restrict__ cos_t, const float* __restrict__ sin_t) {
+                                    const float* __restrict__ cos_t, const float* __restrict__ sin_t, const int32_t* __restrict__ row_pos) {
     const int half = D >> 1;
     const size_t total = (size_t)rows * n_heads * half;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -320,7 +356,7 @@ __global__ void rope_prefill_kernel(bf16_t* __restrict__ qkv, int row_stride, in
         const size_t t = i / half;
         const int hd = (int)(t % n_heads);
         const size_t row = t / n_heads;
-        const int pos = (int)(row % S0);
+        const int pos = row_pos ? row_pos[row] : (int)(row % S0);      // (ragged prompt pass: positions restart in every packed sequence)
         bf16_t* pnt = qkv + row * row_stride + (size_t)hd * D;
         const float x1 = bf2f(pnt[d]), x2 = bf2f(pnt[d + half]);
         const float cs = cos_t[(size_t)pos * half + d], sn = sin_t[(size_t)pos * half + d];
@@ -329,19 +365,26 @@ __global__ void rope_prefill_kernel(bf16_t* __restrict__ qkv, int row_stride, in
     }
 }
 void launch_rope_prefill(bf16_t* qkv, int row_stride, int rows, int S0, int n_heads, int head_dim, const float* cos_t,
-                         const float* sin_t, hipStream_t st) {
+                         const float* sin_t, hipStream_t st, const int32_t* row_pos) {
     size_t total = (size_t)rows * n_heads * (head_dim / 2);
     int blocks = (int)((total + 255) / 256);
     if (blocks > 16384) blocks = 16384;
-    rope_prefill_kernel<<<blocks, 256, 0, st>>>(qkv, row_stride, rows, S0, n_heads, head_dim, cos_t, sin_t);
+    rope_prefill_kernel<<<blocks, 256, 0, st>>>(qkv, row_stride, rows, S0, n_heads, head_dim, cos_t, sin_t, row_pos);
 }
 
 void launch_kv_write_prefill(const bf16_t* qkv, int row_stride, int k_off, int v_off, char* pool_layer,
                              const int32_t* block_table, int max_pages, int B, int S0, int head_dim,
                              hipStream_t st) {
     dim3 grid((S0 + 31) / 32, B);
-    kv_write_prefill_kernel<<<grid, 256, (size_t)32 * (head_dim + 8) * 2, st>>>(qkv, row_stride, k_off, v_off, pool_layer, block_table,
-                                                                               max_pages, B, S0, head_dim);
+    kv_write_prefill_kernel<false><<<grid, 256, (size_t)32 * (head_dim + 8) * 2, st>>>(qkv, row_stride, k_off, v_off, pool_layer, block_table,
+                                                                                      max_pages, B, S0, head_dim, nullptr, nullptr);
+}
+void launch_kv_write_prefill_ragged(const bf16_t* qkv, int row_stride, int k_off, int v_off, char* pool_layer,
+                                    const int32_t* block_table, int max_pages, const int32_t* rag_seq, const int32_t* rag_blocks,
+                                    int n_blocks, int head_dim, hipStream_t st) {
+    if (n_blocks < 1) return;
+    kv_write_prefill_kernel<true><<<n_blocks, 256, (size_t)32 * (head_dim + 8) * 2, st>>>(qkv, row_stride, k_off, v_off, pool_layer, block_table,
+                                                                                         max_pages, 0, 0, head_dim, rag_seq, rag_blocks);
 }
 
 // ------------------------------------------------------------------------------------------------

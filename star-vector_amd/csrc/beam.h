@@ -91,6 +91,8 @@ struct BeamKvArgs {
     const int32_t* parent;                     // [R] flat parent rows
     const int32_t* step; const int32_t* done;  // device scalars
     int S0, L_fixed;                           // cached length L = L_fixed >= 0 ? L_fixed : S0 + *step - 1
+    const int32_t* rag_seq = nullptr;          // ragged prompt pass: per-request descriptors {first packed row, prompt length}; request b's prompt
+                                               // length is rag_seq[2 b + 1] instead of S0 (and instead of a non-negative L_fixed)
     int B, nb;
     char* kv_pool; size_t layer_stride, kv_head_stride; int n_layer, n_kv, page_bytes;
 };

@@ -609,14 +609,17 @@ void BeamScorer::destroy() {
 // ------------------------------------------------------------------------------------------------
 // KV cache: block-table reorder + tail-page copy
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int bm_cached_len(const BeamKvArgs& a) { return a.L_fixed >= 0 ? a.L_fixed : a.S0 + *a.step - 1; }
+__device__ __forceinline__ int bm_cached_len(const BeamKvArgs& a, int b) {
+    if (a.rag_seq) return a.rag_seq[2 * b + 1] + (a.L_fixed >= 0 ? 0 : *a.step - 1);       // per request: prompts of different lengths
+    return a.L_fixed >= 0 ? a.L_fixed : a.S0 + *a.step - 1;
+}
 
 // one block per request: beam j's full pages become its parent's (the permutation is staged through LDS)
 __global__ __launch_bounds__(256) void beam_table_reorder_kernel(BeamKvArgs a) {
     extern __shared__ int32_t tab[];               // [nb][pi]
     if (*a.done) return;
-    const int pi = bm_cached_len(a) / SV_PAGE_TOKENS;     // index of the tail page = number of full pages
     const int b = blockIdx.x, nb = a.nb, tid = threadIdx.x;
+    const int pi = bm_cached_len(a, b) / SV_PAGE_TOKENS;  // index of the tail page = number of full pages
     int32_t* rows = a.block_table + (size_t)b * nb * a.max_pages;
     for (int i = tid; i < nb * pi; i += 256) tab[i] = rows[(size_t)(i / pi) * a.max_pages + (i % pi)];
     __syncthreads();
@@ -634,9 +637,9 @@ __global__ __launch_bounds__(256) void beam_table_reorder_kernel(BeamKvArgs a) {
 #define BM_TAIL_Z 4
 __global__ __launch_bounds__(256) void beam_tail_copy_kernel(BeamKvArgs a) {
     if (*a.done) return;
-    const int L = bm_cached_len(a);
-    if (L % SV_PAGE_TOKENS == 0) return;           // the tail page is empty
     const int b = blockIdx.x, nb = a.nb;
+    const int L = bm_cached_len(a, b);
+    if (L % SV_PAGE_TOKENS == 0) return;           // the tail page is empty
     int src[BM_MAXNB];
     bool any = false;
 #pragma unroll

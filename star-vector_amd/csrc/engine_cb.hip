@@ -103,19 +103,12 @@ static int cb_begin(sv_engine* e, hipStream_t st) {
     return 0;
 }
 
-extern "C" int sv_cb_admit(sv_engine* e, const void* dev_embeds, int32_t n, int32_t S0, const sv_cb_request* reqs,
-                           int32_t* slots_out, sv_stream stream) {
-    SVCHECK(check_ready(e));
-    if (!dev_embeds || !reqs || !slots_out || n < 1) return fail(SV_EINVAL, "sv_cb_admit: null argument or empty batch");
+// lens == nullptr: n requests of the common prompt length S0_all (sv_cb_admit, the rectangular prompt pass); otherwise request i has lens[i] prompt rows,
+// packed back to back, and the new requests share ONE ragged prompt pass (sv_cb_admit_ragged)
+static int cb_admit_impl(sv_engine* e, const void* dev_embeds, int32_t n, int32_t S0_all, const int32_t* lens, const sv_cb_request* reqs,
+                         int32_t* slots_out, sv_stream stream) {
     const sv_config& c = e->cfg;
-    if (n > c.max_batch) return fail(SV_EINVAL, "sv_cb_admit: %d requests exceed max_batch %d", n, c.max_batch);
-    if (S0 < 1) return fail(SV_EINVAL, "sv_cb_admit: bad prompt length %d", S0);
-    for (int i = 0; i < n; ++i) {
-        const sv_cb_request& r = reqs[i];
-        if (r.max_new_tokens < 1 || S0 + r.max_new_tokens > c.max_seq_len)
-            return fail(SV_EINVAL, "sv_cb_admit: request %d: prompt %d + max_new_tokens %d out of range (max_seq_len %d)", i, S0, r.max_new_tokens, c.max_seq_len);
-        SVCHECK(cb_check_request(r, c.vocab, i, "sv_cb_admit"));
-    }
+    auto S0_of = [&](int i) { return lens ? lens[i] : S0_all; };
     std::lock_guard<std::mutex> lk(e->mu);
     HIPCHECK(hipSetDevice(c.device));
     HIPCHECK(hipEventRecord(e->gen_event, (hipStream_t)stream));
@@ -126,7 +119,7 @@ extern "C" int sv_cb_admit(sv_engine* e, const void* dev_embeds, int32_t n, int3
     std::vector<int> slots;
     size_t need_pages = 0;
     for (int s2 = 0; s2 < c.max_batch && (int)slots.size() < n; ++s2) if (!e->cb_used[s2]) slots.push_back(s2);
-    for (int i = 0; i < n; ++i) need_pages += (size_t)(S0 + reqs[i].max_new_tokens + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS;
+    for (int i = 0; i < n; ++i) need_pages += (size_t)(S0_of(i) + reqs[i].max_new_tokens + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS;
     if ((int)slots.size() < n || need_pages > e->free_pages.size())
         return fail(SV_EBUSY, "sv_cb_admit: %d requests need %d slots / %zu KV pages, %zu / %zu are free (release finished slots first)",
                     n, n, need_pages, slots.size(), e->free_pages.size());
@@ -134,12 +127,13 @@ extern "C" int sv_cb_admit(sv_engine* e, const void* dev_embeds, int32_t n, int3
     std::vector<CbSlot> hs(n);
     std::vector<CbBias> hb(n);
     std::vector<std::vector<uint32_t>> seen_rows(n);
-    std::vector<int32_t> map(n), pos(n, S0 - 1);
+    std::vector<int32_t> map(n), pos(n);
+    for (int i = 0; i < n; ++i) pos[i] = S0_of(i) - 1;
     const bool any_pen = [&] { for (int i = 0; i < n; ++i) if (reqs[i].repetition_penalty > 0.f && reqs[i].repetition_penalty != 1.0f) return true; return false; }();
     for (int i = 0; i < n; ++i) {
         const int s2 = slots[i];
         const sv_cb_request& r = reqs[i];
-        const int need = (S0 + r.max_new_tokens + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS;
+        const int need = (S0_of(i) + r.max_new_tokens + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS;
         e->cb_pages[s2].clear();
         for (int k = 0; k < need; ++k) {
             rows[(size_t)i * e->pages_per_seq + k] = e->free_pages.back();
@@ -176,7 +170,8 @@ extern "C" int sv_cb_admit(sv_engine* e, const void* dev_embeds, int32_t n, int3
     add_i32(e->cb_nlive, n, 1, st);
     nlive_added = true;
     // prompt pass of the NEW requests only (their pages through cb_table_pf); the live slots keep decoding afterwards
-    SVCHECK(prefill_forward(e, (const bf16_t*)dev_embeds, n, S0, st, 0, nullptr, e->cb_table_pf));
+    if (lens) SVCHECK(prefill_forward_ragged(e, (const bf16_t*)dev_embeds, n, lens, st, e->cb_table_pf));
+    else SVCHECK(prefill_forward(e, (const bf16_t*)dev_embeds, n, S0_all, st, 0, nullptr, e->cb_table_pf));
     CbStepArgs a;
     cb_step_args(e, a, e->cb_map);
     launch_cb_step(a, n, st);                              // first token of every new request, from the prefill logits
@@ -207,6 +202,41 @@ extern "C" int sv_cb_admit(sv_engine* e, const void* dev_embeds, int32_t n, int3
         return rc;
     }
     return 0;
+}
+
+extern "C" int sv_cb_admit(sv_engine* e, const void* dev_embeds, int32_t n, int32_t S0, const sv_cb_request* reqs,
+                           int32_t* slots_out, sv_stream stream) {
+    SVCHECK(check_ready(e));
+    if (!dev_embeds || !reqs || !slots_out || n < 1) return fail(SV_EINVAL, "sv_cb_admit: null argument or empty batch");
+    const sv_config& c = e->cfg;
+    if (n > c.max_batch) return fail(SV_EINVAL, "sv_cb_admit: %d requests exceed max_batch %d", n, c.max_batch);
+    if (S0 < 1) return fail(SV_EINVAL, "sv_cb_admit: bad prompt length %d", S0);
+    for (int i = 0; i < n; ++i) {
+        const sv_cb_request& r = reqs[i];
+        if (r.max_new_tokens < 1 || S0 + r.max_new_tokens > c.max_seq_len)
+            return fail(SV_EINVAL, "sv_cb_admit: request %d: prompt %d + max_new_tokens %d out of range (max_seq_len %d)", i, S0, r.max_new_tokens, c.max_seq_len);
+        SVCHECK(cb_check_request(r, c.vocab, i, "sv_cb_admit"));
+    }
+    return cb_admit_impl(e, dev_embeds, n, S0, nullptr, reqs, slots_out, stream);
+}
+
+extern "C" int sv_cb_admit_ragged(sv_engine* e, const void* dev_embeds_packed, int32_t n, const int32_t* host_lens, const sv_cb_request* reqs,
+                                  int32_t* slots_out, sv_stream stream) {
+    // (the checks that need no engine come first: they are the same on a machine without a GPU)
+    if (!dev_embeds_packed || !host_lens || !reqs || !slots_out || n < 1) return fail(SV_EINVAL, "sv_cb_admit_ragged: null argument or empty batch");
+    for (int i = 0; i < n; ++i)
+        if (host_lens[i] < 1) return fail(SV_EINVAL, "sv_cb_admit_ragged: request %d: bad prompt length %d", i, host_lens[i]);
+    SVCHECK(check_ready(e));
+    const sv_config& c = e->cfg;
+    if (n > c.max_batch) return fail(SV_EINVAL, "sv_cb_admit_ragged: %d requests exceed max_batch %d", n, c.max_batch);
+    for (int i = 0; i < n; ++i) {
+        const sv_cb_request& r = reqs[i];
+        if (r.max_new_tokens < 1 || host_lens[i] > c.max_seq_len || host_lens[i] + r.max_new_tokens > c.max_seq_len)
+            return fail(SV_EINVAL, "sv_cb_admit_ragged: request %d: prompt %d + max_new_tokens %d out of range (max_seq_len %d)", i, host_lens[i], r.max_new_tokens,
+                        c.max_seq_len);
+        SVCHECK(cb_check_request(r, c.vocab, i, "sv_cb_admit_ragged"));
+    }
+    return cb_admit_impl(e, dev_embeds_packed, n, 0, host_lens, reqs, slots_out, stream);
 }
 
 extern "C" int sv_cb_step(sv_engine* e, int32_t n_steps, int32_t* n_live_out, sv_stream stream) {

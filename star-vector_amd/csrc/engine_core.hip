@@ -331,6 +331,10 @@ extern "C" int sv_destroy(sv_engine* e) {
     if (e->score_chunk_ws) (void)hipFree(e->score_chunk_ws);
     if (e->h_flags) (void)hipHostFree(e->h_flags);
     if (e->h_table) (void)hipHostFree(e->h_table);
+    if (e->h_rag) (void)hipHostFree(e->h_rag);
+    if (e->d_rag) (void)hipFree(e->d_rag);
+    if (e->rag_row_pos) (void)hipFree(e->rag_row_pos);
+    if (e->rag_ev) (void)hipEventDestroy(e->rag_ev);
     if (e->table_ev) (void)hipEventDestroy(e->table_ev);
     for (hipEvent_t ev : e->prof_ev) (void)hipEventDestroy(ev);
     if (e->gen_event) (void)hipEventDestroy(e->gen_event);

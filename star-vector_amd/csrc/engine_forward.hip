@@ -44,6 +44,19 @@ static void gemm(sv_engine* e, int kind, const bf16_t* A, int lda, const Linear&
     launch_gemm(g, st);
 }
 
+// the same GEMM over packed rows of sequences of different lengths: `rows` (device, n_rows of them) take the split-K remainder kernel (launch_gemm_ragged)
+static void gemm_ragged(sv_engine* e, int kind, const bf16_t* A, int lda, const Linear& l, const bf16_t* R, int ldr, void* C, int ldc, int M,
+                        int act, hipStream_t st, const int32_t* rows, int n_rows) {
+    TailMarkCtx tc{e};
+    prof_mark(e, kind, st);
+    GemmArgs g;
+    if (e->prof_on) { g.tail_mark = tail_mark_cb; g.tail_ctx = &tc; }
+    g.A = A; g.lda = lda; g.Wp = l.Wp; g.bias = l.bias; g.R = R; g.ldr = ldr; g.C = C; g.ldc = ldc;
+    g.M = M; g.N = l.N; g.K = l.Kpad; g.act = act; g.out_f32 = 0;
+    g.cscale = l.fp8 ? l.wscale : nullptr;
+    launch_gemm_ragged(g, rows, n_rows, e->rag_rsave, st);
+}
+
 // Context splits of the decode attention: a constant of the engine (sized for the engine's max_batch), NOT of the batch of the
 // call, so that a sequence's partial results are merged in the same grouping whatever shares the batch with it: a row is
 // bit-identical alone, inside a batch and inside a continuous batch at any context length.
@@ -190,6 +203,7 @@ int sveng::prefill_forward(sv_engine* e, const bf16_t* embeds, int B, int S0, hi
     const int D = c.hidden, dh = e->dh, F = c.n_inner, M = B * S0, QKV = e->QKV, nkv = e->nkv;
     const int QD = c.n_head * dh;                      // width of the query block (= D for both model families)
     SVCHECK(ensure_prefill_ws(e, (size_t)M));
+    ++e->prompt_passes;
     prof_mark(e, PK_PF_ROWS, st);
     if (e->v2)      // StarCoder2: no learned positions (rotary), hidden = inputs_embeds
         HIPCHECK(hipMemcpyAsync(e->ph, embeds, (size_t)M * D * sizeof(bf16_t), hipMemcpyDeviceToDevice, st));
@@ -304,6 +318,201 @@ int sveng::prefill_forward(sv_engine* e, const bf16_t* embeds, int B, int S0, hi
     // only the last prompt row feeds ln_f + lm_head (HF computes all rows; same result)
     prof_mark(e, PK_PF_ROWS, st);
     launch_gather_last_rows(e->ph, e->hl, B, S0, D, st);
+    launch_layernorm_rows_packed(e->hl, D, e->ln_f.g, e->ln_f.b, e->xp_f, B, D, c.ln_eps, st);
+    prof_mark(e, PK_PF_LMHEAD, st);
+    lm_head_logits(e, (B + 31) / 32, e->xp_f, st);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The ragged prompt pass: B sequences of lengths lens[b], embeddings packed [sum(lens)][hidden], no padding row computed or stored.
+// Contract: for every sequence the last-row logits and every K / V entry are BIT-IDENTICAL to the sequence alone through prefill_forward
+// with S0 = lens[b].  Per stage: LayerNorm is per row; the GEMMs send a row to the split-K remainder kernel exactly when its solo run
+// does (ragged_gemm_rows) and to an ascending-k kernel otherwise; the attention keeps query-tile and key-tile origins at the sequence's
+// first row (ragged_blocks); positions, pages and slots come from the row's own sequence.
+// ------------------------------------------------------------------------------------------------
+void sveng::ragged_gemm_rows(const int32_t* lens, int B, int N, int K, int act, std::vector<int32_t>& rows, std::vector<int32_t>& last) {
+    rows.clear(); last.clear();
+    int r0 = 0;
+    for (int b = 0; b < B; ++b) {
+        const int S = lens[b], r = seq_peel_rows(S);
+        if (r > 0 && gemm_seq_form(S, N, K, act)) {
+            for (int j = S - r; j < S; ++j) rows.push_back(r0 + j);
+            last.push_back(b);
+        }
+        r0 += S;
+    }
+}
+void sveng::ragged_blocks(const int32_t* lens, int B, int tile, bool last_only, std::vector<int32_t>& out) {
+    out.clear();
+    for (int b = 0; b < B; ++b) {
+        const int n = (lens[b] + tile - 1) / tile;
+        for (int t = last_only ? n - 1 : 0; t < n; ++t) { out.push_back(b); out.push_back(t); }
+    }
+}
+int sveng::ragged_check_lens(const sv_engine* e, const int32_t* lens, int B, const char* who, int* max_len, long long* total) {
+    int mx = 0;
+    long long sum = 0;
+    for (int b = 0; b < B; ++b) {
+        if (lens[b] < 1 || lens[b] > e->cfg.max_seq_len)
+            return fail(SV_EINVAL, "%s: length %d of sequence %d out of range (1..max_seq_len %d)", who, lens[b], b, e->cfg.max_seq_len);
+        mx = lens[b] > mx ? lens[b] : mx;
+        sum += lens[b];
+    }
+    if (max_len) *max_len = mx;
+    if (total) *total = sum;
+    return 0;
+}
+
+// pages per sequence for lens[b] + extra tokens (extra < 0: the whole max_seq_len, as sv_prefill hands out)
+int sveng::assign_pages_ragged(sv_engine* e, int B, const int32_t* lens, int extra, hipStream_t st) {
+    e->free_pages.clear();
+    for (int p = e->num_pages - 1; p >= 0; --p) e->free_pages.push_back(p);
+    if (e->table_pending) { HIPCHECK(hipEventSynchronize(e->table_ev)); e->table_pending = false; }
+    const size_t n = (size_t)e->cfg.max_batch * e->pages_per_seq;
+    int32_t* table = e->h_table;
+    memset(table, 0, n * sizeof(int32_t));
+    for (int b = 0; b < B; ++b) {
+        const int total = extra < 0 ? e->cfg.max_seq_len : lens[b] + extra;
+        const int need = (total + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS;
+        if (need > e->pages_per_seq) return fail(SV_EINVAL, "sequence length %d exceeds max_seq_len %d", total, e->cfg.max_seq_len);
+        for (int i = 0; i < need; ++i) {
+            table[(size_t)b * e->pages_per_seq + i] = e->free_pages.back();
+            e->free_pages.pop_back();
+        }
+    }
+    HIPCHECK(hipMemcpyAsync(e->block_table, table, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipEventRecord(e->table_ev, st));
+    e->table_pending = true;
+    return 0;
+}
+
+__global__ void ragged_positions_kernel(int32_t* positions, const int32_t* rag_seq, int n, int rep, int delta) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) positions[i] = rag_seq[2 * (i / rep) + 1] + delta;
+}
+void sveng::ragged_positions(sv_engine* e, int B, int rep, int delta, hipStream_t st) {
+    const int n = B * rep;
+    ragged_positions_kernel<<<(n + 63) / 64, 64, 0, st>>>(e->positions, e->d_rag, n, rep, delta);
+}
+
+int sveng::prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, const int32_t* lens, hipStream_t st, const int32_t* table) {
+    if (!table) table = e->block_table;
+    const sv_config& c = e->cfg;
+    const int D = c.hidden, dh = e->dh, F = c.n_inner, QKV = e->QKV, nkv = e->nkv;
+    const int QD = c.n_head * dh;
+    long long total = 0;
+    for (int b = 0; b < B; ++b) total += lens[b];
+    const int M = (int)total;
+    // (the pruned last layer keeps [B][QD] + [B][D] compact rows inside the LayerNorm workspace: at least 2 B rows)
+    SVCHECK(ensure_prefill_ws(e, (size_t)std::max(M, 2 * B)));
+    ++e->prompt_passes;
+    if (!e->rag_rsave) SVCHECK(dalloc(e, &e->rag_rsave, (size_t)3 * c.max_batch * D));
+    if ((size_t)M > e->rag_pos_rows) {
+        if (e->rag_row_pos) (void)hipFree(e->rag_row_pos);
+        e->rag_row_pos = nullptr; e->rag_pos_rows = 0;
+        HIPCHECK(hipMalloc(reinterpret_cast<void**>(&e->rag_row_pos), (size_t)M * sizeof(int32_t)));
+        e->rag_pos_rows = (size_t)M;
+    }
+    // ---- the plan of this call: descriptors | attention blocks | last-tile blocks | KV-write blocks | remainder rows of the four projections
+    const int qt = attn_prefill_q_tile(c.n_head, nkv);
+    std::vector<int32_t> ab, al, kb, rows[4], last[4];
+    ragged_blocks(lens, B, qt, false, ab);
+    ragged_blocks(lens, B, qt, true, al);
+    ragged_blocks(lens, B, 32, false, kb);
+    const Linear* proj[4] = {&e->dec[0].c_attn, &e->dec[0].c_proj, &e->dec[0].c_fc, &e->dec[0].c_proj2};
+    const int acts[4] = {ACT_NONE, ACT_NONE, ACT_GELU_TANH, ACT_NONE};
+    if (!(e->exp & 4194304))            // SV_EXP bit 4194304: no per-sequence remainder (as in the rectangular pass)
+        for (int i = 0; i < 4; ++i) ragged_gemm_rows(lens, B, proj[i]->N, proj[i]->Kpad, acts[i], rows[i], last[i]);
+    size_t need = (size_t)2 * B + ab.size() + al.size() + kb.size();
+    for (int i = 0; i < 4; ++i) need += rows[i].size() + last[i].size();
+    if (need > e->rag_cap) {
+        if (e->rag_pending) { HIPCHECK(hipEventSynchronize(e->rag_ev)); e->rag_pending = false; }
+        if (e->h_rag) (void)hipHostFree(e->h_rag);
+        if (e->d_rag) (void)hipFree(e->d_rag);
+        e->h_rag = nullptr; e->d_rag = nullptr; e->rag_cap = 0;
+        const size_t cap = need + need / 2 + 256;
+        HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&e->h_rag), cap * sizeof(int32_t), hipHostMallocDefault));
+        HIPCHECK(hipMalloc(reinterpret_cast<void**>(&e->d_rag), cap * sizeof(int32_t)));
+        if (!e->rag_ev) HIPCHECK(hipEventCreateWithFlags(&e->rag_ev, hipEventDisableTiming));
+        e->rag_cap = cap;
+    }
+    // pinned image, no stream synchronise: rewritten only after its last upload has completed (an event, normally long past)
+    if (e->rag_pending) { HIPCHECK(hipEventSynchronize(e->rag_ev)); e->rag_pending = false; }
+    size_t off = 0;
+    auto put = [&](const std::vector<int32_t>& v) { const size_t o = off; if (!v.empty()) memcpy(e->h_rag + off, v.data(), v.size() * sizeof(int32_t)); off += v.size(); return o; };
+    {
+        int r0 = 0;
+        for (int b = 0; b < B; ++b) { e->h_rag[2 * b] = r0; e->h_rag[2 * b + 1] = lens[b]; r0 += lens[b]; }
+        off = (size_t)2 * B;
+    }
+    const int32_t* d_seq = e->d_rag;
+    const int32_t* d_ab = e->d_rag + put(ab);
+    const int32_t* d_al = e->d_rag + put(al);
+    const int32_t* d_kb = e->d_rag + put(kb);
+    const int32_t *d_rows[4], *d_last[4];
+    for (int i = 0; i < 4; ++i) { d_rows[i] = e->d_rag + put(rows[i]); d_last[i] = e->d_rag + put(last[i]); }
+    HIPCHECK(hipMemcpyAsync(e->d_rag, e->h_rag, off * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipEventRecord(e->rag_ev, st));
+    e->rag_pending = true;
+
+    prof_mark(e, PK_PF_ROWS, st);
+    if (e->v2) {
+        HIPCHECK(hipMemcpyAsync(e->ph, embeds, (size_t)M * D * sizeof(bf16_t), hipMemcpyDeviceToDevice, st));
+        launch_ragged_row_pos(d_seq, B, e->rag_row_pos, st);                  // rotary positions
+    } else {
+        launch_ragged_row_pos(d_seq, B, e->rag_row_pos, st);                  // learned positions restart at 0 in every sequence
+        launch_dec_embed(embeds, e->wpe, e->ph, 1, M, D, st, e->rag_row_pos);
+    }
+    AttnPrefillArgs at;
+    at.q = e->pqkv; at.k = e->pqkv + QD; at.v = e->pqkv + QD + nkv * dh;
+    at.q_row_stride = QKV; at.kv_row_stride = QKV; at.q_head_stride = dh; at.kv_head_stride = nkv > 1 ? dh : 0;
+    at.o = e->pattn; at.o_row_stride = QD; at.B = B; at.S = 0; at.H = c.n_head; at.head_dim = dh;
+    at.kv_group = c.n_head / nkv; at.causal = 1; at.scale = 1.0f / sqrtf((float)dh);
+    at.window = c.sliding_window > 0 ? c.sliding_window : 0;
+    at.rag_seq = d_seq;
+    const bool prune_last = !(e->exp & 32768);
+    for (int i = 0; i < c.n_layer; ++i) {
+        DecLayer& L = e->dec[i];
+        prof_mark(e, PK_PF_ROWS, st);
+        launch_layernorm_rows(e->ph, D, L.ln1.g, L.ln1.b, e->pln, D, M, D, c.ln_eps, st);
+        gemm_ragged(e, PK_PF_GEMM, e->pln, D, L.c_attn, nullptr, 0, e->pqkv, QKV, M, ACT_NONE, st, d_rows[0], (int)rows[0].size());
+        prof_mark(e, PK_PF_ATTN, st);
+        if (e->v2) launch_rope_prefill(e->pqkv, QKV, M, M, c.n_head + nkv, dh, e->rope_cos, e->rope_sin, st, e->rag_row_pos);
+        for (int kh = 0; kh < nkv; ++kh)
+            launch_kv_write_prefill_ragged(e->pqkv, QKV, QD + kh * dh, QD + nkv * dh + kh * dh,
+                                           e->kv_pool + (size_t)i * e->layer_stride + (size_t)kh * e->kv_head_stride,
+                                           table, e->pages_per_seq, d_seq, d_kb, (int)kb.size() / 2, dh, st);
+        if (prune_last && i + 1 == c.n_layer) {
+            // only the last row of every sequence goes on (see prefill_forward): its query tile, then B compact rows
+            at.rag_blocks = d_al; at.rag_nblocks = (int)al.size() / 2;
+            launch_attn_prefill(at, st);
+            bf16_t* pa_l = e->pln;
+            bf16_t* ln_l = e->pln + (size_t)B * QD;
+            prof_mark(e, PK_PF_ROWS, st);
+            launch_gather_last_rows(e->pattn, pa_l, B, 0, QD, st, d_seq);
+            launch_gather_last_rows(e->ph, e->hl, B, 0, D, st, d_seq);
+            gemm_ragged(e, PK_PF_GEMM, pa_l, QD, L.c_proj, e->hl, D, e->hl, D, B, ACT_NONE, st, d_last[1], (int)last[1].size());
+            prof_mark(e, PK_PF_ROWS, st);
+            launch_layernorm_rows(e->hl, D, L.ln2.g, L.ln2.b, ln_l, D, B, D, c.ln_eps, st);
+            gemm_ragged(e, PK_PF_GEMM, ln_l, D, L.c_fc, nullptr, 0, e->pmlp, F, B, ACT_GELU_TANH, st, d_last[2], (int)last[2].size());
+            gemm_ragged(e, PK_PF_GEMM, e->pmlp, F, L.c_proj2, e->hl, D, e->hl, D, B, ACT_NONE, st, d_last[3], (int)last[3].size());
+            prof_mark(e, PK_PF_ROWS, st);
+            launch_layernorm_rows_packed(e->hl, D, e->ln_f.g, e->ln_f.b, e->xp_f, B, D, c.ln_eps, st);
+            prof_mark(e, PK_PF_LMHEAD, st);
+            lm_head_logits(e, (B + 31) / 32, e->xp_f, st);
+            return 0;
+        }
+        at.rag_blocks = d_ab; at.rag_nblocks = (int)ab.size() / 2;
+        launch_attn_prefill(at, st);
+        gemm_ragged(e, PK_PF_GEMM, e->pattn, QD, L.c_proj, e->ph, D, e->ph, D, M, ACT_NONE, st, d_rows[1], (int)rows[1].size());
+        prof_mark(e, PK_PF_ROWS, st);
+        launch_layernorm_rows(e->ph, D, L.ln2.g, L.ln2.b, e->pln, D, M, D, c.ln_eps, st);
+        gemm_ragged(e, PK_PF_GEMM, e->pln, D, L.c_fc, nullptr, 0, e->pmlp, F, M, ACT_GELU_TANH, st, d_rows[2], (int)rows[2].size());
+        gemm_ragged(e, PK_PF_GEMM, e->pmlp, F, L.c_proj2, e->ph, D, e->ph, D, M, ACT_NONE, st, d_rows[3], (int)rows[3].size());
+    }
+    prof_mark(e, PK_PF_ROWS, st);
+    launch_gather_last_rows(e->ph, e->hl, B, 0, D, st, d_seq);
     launch_layernorm_rows_packed(e->hl, D, e->ln_f.g, e->ln_f.b, e->xp_f, B, D, c.ln_eps, st);
     prof_mark(e, PK_PF_LMHEAD, st);
     lm_head_logits(e, (B + 31) / 32, e->xp_f, st);
@@ -592,6 +801,29 @@ extern "C" int sv_prefill(sv_engine* e, const void* dev_embeds, int32_t B, int32
     HIPCHECK(hipSetDevice(e->cfg.device));
     hipStream_t st = (hipStream_t)stream;
     SVCHECK(prefill_locked(e, dev_embeds, B, S0, e->cfg.max_seq_len, st));
+    SVCHECK(copy_logits_out(e, B, dev_logits, st));
+    return 0;
+}
+
+extern "C" int sv_prefill_ragged(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, float* dev_logits,
+                                 sv_stream stream) {
+    // (the checks that need no engine come first: they are the same on a machine without a GPU)
+    if (!dev_embeds_packed || !host_lens || !dev_logits) return fail(SV_EINVAL, "sv_prefill_ragged: null embeds / lengths / logits pointer");
+    if (B < 1) return fail(SV_EINVAL, "sv_prefill_ragged: bad B=%d", B);
+    for (int b = 0; b < B; ++b)
+        if (host_lens[b] < 1) return fail(SV_EINVAL, "sv_prefill_ragged: length %d of sequence %d (must be >= 1)", host_lens[b], b);
+    SVCHECK(check_ready(e));
+    if (B > e->cfg.max_batch) return fail(SV_EINVAL, "sv_prefill_ragged: bad B=%d (max_batch %d)", B, e->cfg.max_batch);
+    SVCHECK(ragged_check_lens(e, host_lens, B, "sv_prefill_ragged", nullptr, nullptr));
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIPCHECK(hipSetDevice(e->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    SVCHECK(cb_guard(e, "sv_prefill_ragged"));
+    SVCHECK(assign_pages_ragged(e, B, host_lens, -1, st));
+    SVCHECK(prefill_forward_ragged(e, (const bf16_t*)dev_embeds_packed, B, host_lens, st));
+    ragged_positions(e, B, 1, 0, st);
+    e->cached_B = B;
+    HIPCHECK(hipGetLastError());
     SVCHECK(copy_logits_out(e, B, dev_logits, st));
     return 0;
 }

@@ -57,7 +57,8 @@ static void sample_and_finish(sv_engine* e, int B, const sv_sampling& sp, int ma
 // request: its full KV pages are shared by all beams through the block table, only the partially filled tail page
 // is private to a beam (HF expands the prompt to B * num_beams rows and prefills every copy).
 // ------------------------------------------------------------------------------------------------
-static int upload_beam_table(sv_engine* e, int B, int nb, int need, int shared_pages, bool prefill_rows, hipStream_t st) {
+// lens (ragged prompt pass): the prompt pages the beams of request b share are lens[b] / SV_PAGE_TOKENS instead of shared_pages
+static int upload_beam_table(sv_engine* e, int B, int nb, int need, int shared_pages, bool prefill_rows, hipStream_t st, const int32_t* lens = nullptr) {
     std::vector<int32_t> table((size_t)e->cfg.max_batch * e->pages_per_seq, 0);
     if (prefill_rows) {
         for (int b = 0; b < B; ++b)             // request b writes its prompt into the pages of beam row b * nb
@@ -65,7 +66,7 @@ static int upload_beam_table(sv_engine* e, int B, int nb, int need, int shared_p
     } else {
         for (int r = 0; r < B * nb; ++r)
             for (int i = 0; i < need; ++i)
-                table[(size_t)r * e->pages_per_seq + i] = (i < shared_pages ? (r / nb) * nb : r) * need + i;
+                table[(size_t)r * e->pages_per_seq + i] = (i < (lens ? lens[r / nb] / SV_PAGE_TOKENS : shared_pages) ? (r / nb) * nb : r) * need + i;
     }
     HIPCHECK(hipMemcpyAsync(e->block_table, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIPCHECK(hipStreamSynchronize(st));
@@ -78,7 +79,8 @@ static void beam_step(sv_engine* e, const BeamKvArgs& kv, int logit_div, hipStre
     launch_beam_tail_copy(kv, st);
 }
 
-static int generate_beam(sv_engine* e, const void* dev_embeds, int B, int S0, const sv_sampling* sp, int max_new,
+// lens != nullptr: the ragged form (sv_generate_ragged) -- S0 is the longest prompt, request b has lens[b] prompt rows
+static int generate_beam(sv_engine* e, const void* dev_embeds, int B, int S0, const int32_t* lens, const sv_sampling* sp, int max_new,
                          const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, hipStream_t st) {
     const sv_config& c = e->cfg;
     const int nb = sp->num_beams, R = B * nb;
@@ -111,17 +113,20 @@ static int generate_beam(sv_engine* e, const void* dev_embeds, int B, int S0, co
     e->beam.cap_temp = sp->temperature;
     // prompt pass over the B requests, written into the pages of each request's first beam row
     SVCHECK(upload_beam_table(e, B, nb, need, 0, true, st));
-    SVCHECK(prefill_forward(e, (const bf16_t*)dev_embeds, B, S0, st));
-    SVCHECK(upload_beam_table(e, B, nb, need, S0 / SV_PAGE_TOKENS, false, st));
+    if (lens) SVCHECK(prefill_forward_ragged(e, (const bf16_t*)dev_embeds, B, lens, st));
+    else SVCHECK(prefill_forward(e, (const bf16_t*)dev_embeds, B, S0, st));
+    SVCHECK(upload_beam_table(e, B, nb, need, S0 / SV_PAGE_TOKENS, false, st, lens));
     e->cached_B = R;
     {
         int r = e->beam.reset(st);
         if (r) return fail(SV_EHIP, "beam scorer reset failed (hip error %d)", r);
     }
-    fill_i32(e->positions, S0 - 1, R, st);      // beam_update adds 1
+    if (lens) ragged_positions(e, B, nb, -1, st);
+    else fill_i32(e->positions, S0 - 1, R, st);      // beam_update adds 1
     BeamKvArgs kv;
     kv.block_table = e->block_table; kv.max_pages = e->pages_per_seq; kv.need = need; kv.parent = e->beam.d.parent;
     kv.step = e->d_step; kv.done = e->d_done; kv.S0 = S0; kv.L_fixed = S0; kv.B = B; kv.nb = nb;
+    kv.rag_seq = lens ? e->d_rag : nullptr;     // (the descriptors prefill_forward_ragged uploaded: they live until the next ragged pass)
     kv.kv_pool = e->kv_pool; kv.layer_stride = e->layer_stride; kv.kv_head_stride = e->kv_head_stride;
     kv.n_layer = c.n_layer; kv.n_kv = e->nkv; kv.page_bytes = e->page_bytes;
     launch_beam_tail_copy(kv, st);              // the prompt's tail page fans out to beams 1.. (parent = first beam row)
@@ -245,8 +250,19 @@ int sveng::report_bad_logits(sv_engine* e, hipStream_t st, const char* who, int 
     }
 }
 
-static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const sv_sampling* sp,
+static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const int32_t* lens, const sv_sampling* sp,
                             const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream);
+static int generate_retry(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const int32_t* lens, const sv_sampling* sp,
+                          const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
+    if (e) { e->last_giveup = 0; e->stream_skip = 0; }
+    int rc = generate_attempt(e, dev_embeds, B, S0, lens, sp, outs, dev_out_tokens, n_generated, stream);
+    if (rc != 0 && e && e->cfg.exclusive_device == 2 && e->last_giveup && e->fused_off) {
+        e->last_giveup = 0;
+        rc = generate_attempt(e, dev_embeds, B, S0, lens, sp, outs, dev_out_tokens, n_generated, stream);
+    }
+    if (e) e->stream_skip = 0;
+    return rc;
+}
 
 // sv_config.exclusive_device = 2: OPTIMISTIC ownership.  The fused launches run as if the engine owned its GPU; if one gives up (another process
 // holds CUs: the bounded wait of rowops.hip / gemm.hip, never a hang, never tokens) the engine switches them off for good (report_bad_logits) and
@@ -256,14 +272,20 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t B, int
 // (the second attempt runs every step again: the capture slabs of sv_generate_ex are rewritten completely)
 extern "C" int sv_generate_ex(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const sv_sampling* sp,
                               const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
-    if (e) { e->last_giveup = 0; e->stream_skip = 0; }
-    int rc = generate_attempt(e, dev_embeds, B, S0, sp, outs, dev_out_tokens, n_generated, stream);
-    if (rc != 0 && e && e->cfg.exclusive_device == 2 && e->last_giveup && e->fused_off) {
-        e->last_giveup = 0;
-        rc = generate_attempt(e, dev_embeds, B, S0, sp, outs, dev_out_tokens, n_generated, stream);
+    return generate_retry(e, dev_embeds, B, S0, nullptr, sp, outs, dev_out_tokens, n_generated, stream);
+}
+// The ragged form: sequences of lengths host_lens[b], packed.  HF's padded-batch semantics: the budget counts from the longest prompt.
+extern "C" int sv_generate_ragged(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, const sv_sampling* sp,
+                                  const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
+    // (the checks that need no engine come first: they are the same on a machine without a GPU)
+    if (!dev_embeds_packed || !host_lens || !sp || !dev_out_tokens || !n_generated) return fail(SV_EINVAL, "sv_generate_ragged: null argument");
+    if (B < 1) return fail(SV_EINVAL, "sv_generate_ragged: bad B=%d", B);
+    int longest = 0;
+    for (int b = 0; b < B; ++b) {
+        if (host_lens[b] < 1) return fail(SV_EINVAL, "sv_generate_ragged: length %d of sequence %d (must be >= 1)", host_lens[b], b);
+        longest = host_lens[b] > longest ? host_lens[b] : longest;
     }
-    if (e) e->stream_skip = 0;
-    return rc;
+    return generate_retry(e, dev_embeds_packed, B, longest, host_lens, sp, outs, dev_out_tokens, n_generated, stream);
 }
 extern "C" int sv_generate(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const sv_sampling* sp,
                            int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
@@ -292,9 +314,14 @@ static int setup_capture(sv_engine* e, const sv_sampling* sp, const sv_generate_
     return 0;
 }
 
-static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const sv_sampling* sp,
+// lens != nullptr: the ragged form -- S0 is the longest prompt (the budget counts from it), sequence b has lens[b] rows
+static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const int32_t* lens, const sv_sampling* sp,
                             const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
     SVCHECK(check_ready(e));
+    if (lens) {
+        if (B > e->cfg.max_batch) return fail(SV_EINVAL, "sv_generate_ragged: bad B=%d (max_batch %d)", B, e->cfg.max_batch);
+        SVCHECK(ragged_check_lens(e, lens, B, "sv_generate_ragged", nullptr, nullptr));
+    }
     if (!sp || !dev_out_tokens || !n_generated) return fail(SV_EINVAL, "sv_generate: null argument");
     const int max_new = sp->max_length - S0;     // HF: with inputs_embeds, max_length includes the prompt
     if (max_new <= 0) return fail(SV_EINVAL, "max_length (%d) must exceed the prompt length (%d)", sp->max_length, S0);
@@ -315,12 +342,19 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t B, int
     if (sp->num_beams > 1) {
         if (sp->on_tokens) return fail(SV_EINVAL, "streaming is not supported with beam search (hypotheses are only final at the end; HF refuses too)");
         if (sp->n_stop > 0 && !sp->stop_ids) return fail(SV_EINVAL, "n_stop > 0 but stop_ids is null");
-        return generate_beam(e, dev_embeds, B, S0, sp, max_new, outs, dev_out_tokens, n_generated, st);
+        return generate_beam(e, dev_embeds, B, S0, lens, sp, max_new, outs, dev_out_tokens, n_generated, st);
     }
 
     auto t0 = std::chrono::steady_clock::now();
     HIPCHECK(hipMemsetAsync(e->d_bad, 0, sizeof(int32_t), st));         // a flag left by an earlier, failed call is not this call's
-    SVCHECK(prefill_locked(e, dev_embeds, B, S0, S0 + max_new, st, false));
+    if (lens) {                              // pages per sequence for lens[b] + max_new, one ragged prompt pass
+        SVCHECK(assign_pages_ragged(e, B, lens, max_new, st));
+        SVCHECK(prefill_forward_ragged(e, (const bf16_t*)dev_embeds, B, lens, st));
+        e->cached_B = B;
+        HIPCHECK(hipGetLastError());
+    } else {
+        SVCHECK(prefill_locked(e, dev_embeds, B, S0, S0 + max_new, st, false));
+    }
     // Plain greedy decode (no repetition penalty, no min_length hold, one row tile, bf16 lm_head with the K split over the waves of a
     // block): the selection rides in the lm_head epilogue of every decode step -- one launch less per step, same tokens bit for bit.
     // SV_EXP bit 1024 = the separate argmax launch (A/B).
@@ -336,6 +370,7 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t B, int
     }
     // generation state, one launch: positions = S0 - 1 (finish_step adds 1), unfinished = 1, {step, done, n_emitted} = 0, the folded selection's key slots = 0
     gen_state_init(e->positions, S0 - 1, e->unfinished, B, e->d_step, e->amax, fused_sel ? 64 * SV_AMAX_STRIDE : 0, st);
+    if (lens) ragged_positions(e, B, 1, -1, st);         // every row continues at its own length
     if (sp->repetition_penalty > 0.f && sp->repetition_penalty != 1.0f)
         HIPCHECK(hipMemsetAsync(e->seen, 0, (size_t)((B + 31) / 32) * 32 * e->seen_words * sizeof(uint32_t), st));
     if (sp->n_stop > 0) {

@@ -157,6 +157,15 @@ struct sv_engine {
     int32_t* h_table = nullptr;   // pinned host image of block_table (assign_pages); table_ev = its last upload
     hipEvent_t table_ev = nullptr;
     bool table_pending = false;
+    // ragged prompt pass (engine_forward.hip, RaggedPlan): the per-sequence descriptors, block lists and remainder-row lists of the call, written into a
+    // pinned host image and uploaded without a stream synchronise like the block table; grown on demand
+    int32_t *h_rag = nullptr, *d_rag = nullptr;
+    size_t rag_cap = 0;                           // int32 elements either holds
+    hipEvent_t rag_ev = nullptr;
+    bool rag_pending = false;
+    int32_t* rag_row_pos = nullptr; size_t rag_pos_rows = 0;      // [packed rows] position of a row inside its sequence
+    bf16_t* rag_rsave = nullptr;                  // [3 * max_batch][hidden] residual rows of a GEMM's remainder launch (launch_gemm_ragged)
+    long long prompt_passes = 0;                  // prompt passes run so far, rectangular and ragged (sv_debug_prompt_passes)
     // KV pool
     char* kv_pool = nullptr;
     size_t layer_stride = 0;
@@ -256,6 +265,18 @@ int cb_check_request(const sv_cb_request& r, int V, int i, const char* who);
 void cb_fill_slot(const sv_cb_request& r, CbSlot& h, CbBias& bias, std::vector<uint32_t>& seen_row, int seen_words);
 int cb_guard(sv_engine* e, const char* who);
 int prefill_locked(sv_engine* e, const void* dev_embeds, int B, int S0, int total_len, hipStream_t st, bool set_positions = true);
+// The ragged prompt pass: B sequences of lengths lens[0..B) (host), embeddings packed back to back.  What the dispatch decides for a set of lengths is
+// host arithmetic (ragged_gemm_rows, ragged_blocks: sv_debug_ragged_plan states it for the CPU tests).
+//   ragged_gemm_rows  the packed rows the projection (N, K, act) sends through the split-K remainder kernel -- the last seq_peel_rows(len) rows of every
+//                     sequence with gemm_seq_form(len, N, K, act) -- and the sequences whose LAST row is one of them (the pruned last layer's compact rows)
+//   ragged_blocks     {sequence, tile} pairs of `tile` rows counted from each sequence's first row (last_only: each sequence's last tile alone)
+void ragged_gemm_rows(const int32_t* lens, int B, int N, int K, int act, std::vector<int32_t>& rows, std::vector<int32_t>& last);
+void ragged_blocks(const int32_t* lens, int B, int tile, bool last_only, std::vector<int32_t>& out);
+int ragged_check_lens(const sv_engine* e, const int32_t* lens, int B, const char* who, int* max_len, long long* total);
+int assign_pages_ragged(sv_engine* e, int B, const int32_t* lens, int extra, hipStream_t st);
+int prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, const int32_t* lens, hipStream_t st, const int32_t* table = nullptr);
+// positions[i] = lens[i / rep] + delta for i < B * rep, from the descriptors the last prefill_forward_ragged uploaded
+void ragged_positions(sv_engine* e, int B, int rep, int delta, hipStream_t st);
 // engine_generate.hip
 int check_finite_logits(sv_engine* e, hipStream_t st, const char* who);
 int report_bad_logits(sv_engine* e, hipStream_t st, const char* who, int what);      // what = the d_bad code already read (0: fine)

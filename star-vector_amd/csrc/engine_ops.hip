@@ -248,6 +248,29 @@ extern "C" int sv_debug_gemm_seq_form(int32_t S, int32_t N, int32_t K, int32_t a
     return gemm_seq_form(S, N, K, act) ? 1 : 0;
 }
 
+extern "C" int sv_debug_ragged_plan(const int32_t* lens, int32_t B, int32_t N, int32_t K, int32_t act, int32_t q_tile, int32_t* rows_out,
+                                    int32_t* last_out, int32_t capacity, int32_t* out4) {
+    if (!lens || !rows_out || !last_out || !out4) return fail(SV_EINVAL, "sv_debug_ragged_plan: null argument");
+    if (B < 1 || N < 1 || K < 1 || (q_tile != 32 && q_tile != 128)) return fail(SV_EINVAL, "sv_debug_ragged_plan: bad argument (B %d, N %d, K %d, q_tile %d)", B, N, K, q_tile);
+    if (capacity < 3 * B) return fail(SV_EINVAL, "sv_debug_ragged_plan: capacity %d < 3 * B", capacity);
+    for (int b = 0; b < B; ++b)
+        if (lens[b] < 1) return fail(SV_EINVAL, "sv_debug_ragged_plan: length %d of sequence %d", lens[b], b);
+    std::vector<int32_t> rows, last, ab, kb;
+    ragged_gemm_rows(lens, B, N, K, act, rows, last);
+    ragged_blocks(lens, B, q_tile, false, ab);
+    ragged_blocks(lens, B, 32, false, kb);
+    for (size_t i = 0; i < rows.size(); ++i) rows_out[i] = rows[i];
+    for (size_t i = 0; i < last.size(); ++i) last_out[i] = last[i];
+    out4[0] = (int32_t)rows.size(); out4[1] = (int32_t)last.size(); out4[2] = (int32_t)ab.size() / 2; out4[3] = (int32_t)kb.size() / 2;
+    return 0;
+}
+extern "C" int sv_debug_prompt_passes(sv_engine* e, int64_t* out) {
+    if (!e || !out) return fail(SV_EINVAL, "sv_debug_prompt_passes: null argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    *out = e->prompt_passes;
+    return 0;
+}
+
 extern "C" int sv_debug_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t act, int32_t* out5) {
     if (!out5 || M < 1 || N < 1 || K < 1) return fail(SV_EINVAL, "sv_debug_gemm_plan: bad argument");
     const GemmPlan pl = gemm_plan(M, N, K, act, 1);

@@ -887,7 +887,8 @@ __global__ __launch_bounds__(GTK_WAVES * 64) void gemm_tailk_kernel(GemmArgs p) 
     int i = mt * 32 + (lane & 31);
     const bool rok = i < p.M;
     i = rok ? i : p.M - 1;
-    const int row = p.seq_tail ? (i / p.seq_tail) * p.seq_rows + (p.seq_rows - p.seq_tail) + i % p.seq_tail : i;
+    // (row_list: the ragged prompt pass hands the rows over explicitly -- sequences of different lengths have no arithmetic map)
+    const int row = p.row_list ? p.row_list[i] : p.seq_tail ? (i / p.seq_tail) * p.seq_rows + (p.seq_rows - p.seq_tail) + i % p.seq_tail : i;
     const bf16_t* xrow = p.A + (size_t)row * p.lda + 8 * (lane >> 5) + c0 * 64;
     const bf16_t* wfr = p.Wp + (((size_t)nt * KS + c0 * 4) * 64 + lane) * 8;
     f32x16 acc;
@@ -931,7 +932,7 @@ __global__ __launch_bounds__(GTK_WAVES * 64) void gemm_tailk_kernel(GemmArgs p) 
     const int ncol = nt * 32 + rg * 8 + half * 4;
     if (ncol >= p.N) return;              // N % 4 == 0
     const uint2 bq = p.bias ? *reinterpret_cast<const uint2*>(p.bias + ncol) : make_uint2(0u, 0u);
-    const uint2 rq = p.R ? *reinterpret_cast<const uint2*>(p.R + (size_t)m * p.ldr + ncol) : make_uint2(0u, 0u);
+    const uint2 rq = p.R ? *reinterpret_cast<const uint2*>(p.R + (size_t)(p.r_compact ? i : m) * p.ldr + ncol) : make_uint2(0u, 0u);
     const float4 c4 = p.cscale ? *reinterpret_cast<const float4*>(p.cscale + ncol) : make_float4(1.f, 1.f, 1.f, 1.f);
     const float cs[4] = {c4.x, c4.y, c4.z, c4.w};
     const float bj[4] = {__uint_as_float(bq.x << 16), __uint_as_float(bq.x & 0xffff0000u), __uint_as_float(bq.y << 16), __uint_as_float(bq.y & 0xffff0000u)};
@@ -1254,6 +1255,22 @@ void launch_gemm(const GemmArgs& a0, hipStream_t st) {
         if (cfg & 16) { launch_gemm_rows_by_tail(a, st); return; }
     }
     launch_gemm_model(a, pl, st);
+}
+
+// The ragged prompt pass's GEMM (kernels.h): every row through an ascending-k kernel of the dispatch's choice, then the listed rows again through the
+// split-K remainder kernel -- the kernel they take in their sequence's solo run -- over the first pass's result.  The listed rows are at most three
+// per sequence, so computing them twice costs nothing next to a masked epilogue in the tile kernels.
+void launch_gemm_ragged(const GemmArgs& a0, const int32_t* rows, int n_rows, bf16_t* r_save, hipStream_t st) {
+    GemmArgs a = a0;
+    a.seq_rows = 0; a.splitk_rows = 0; a.seq_tail = 0; a.row_list = nullptr; a.r_compact = 0;
+    if (n_rows > 0 && a.R) launch_gather_listed_rows(a.R, a.ldr, rows, n_rows, r_save, a.N, st);
+    launch_gemm(a, st);
+    if (n_rows <= 0) return;
+    GemmArgs t = a;
+    t.M = n_rows; t.row_list = rows;
+    if (a.R) { t.R = r_save; t.ldr = a.N; t.r_compact = 1; }
+    if (a.tail_mark) a.tail_mark(a.tail_ctx, st);
+    launch_gemm_tailk(t, st);
 }
 
 // the untuned choice: the cost model's tile kernel, its peel decision, the per-sequence remainder

@@ -43,6 +43,11 @@ struct GemmArgs {
     int seq_tail = 0;                // set by the launcher for the remainder launch: row i -> (i / seq_tail) * seq_rows + seq_rows - seq_tail + i % seq_tail
     int splitk_rows = 0;             // 1: the M rows (compact, contiguous) are LAST rows of sequences of seq_rows rows (the pruned last prompt layer): they take
                                      //    the kernel the same rows take inside the full problem (split-K remainder kernel where gemm_seq_form holds)
+    // Ragged prompt pass (launch_gemm_ragged): the remainder launch takes an EXPLICIT row list instead of the arithmetic map -- element i of the launch
+    // reads row row_list[i] of A and writes row row_list[i] of C; r_compact = 1: its residual row is row i of R (saved aside before the first pass
+    // added the residual in place)
+    const int32_t* row_list = nullptr;
+    int r_compact = 0;
     int tune_in_place = 0;           // 1 (and no residual operand): the tuner's timing runs write C itself instead of a scratch output of M x ldc elements
                                      //    (the chunked lm_head of the scoring forward: its footprint must not grow with rows x vocab; C is overwritten anyway)
 };
@@ -52,6 +57,12 @@ inline int seq_peel_rows(int S) { const int r = S % 256; return (S > 256 && r >=
 // (never of the batch): where the dispatch's cost model peels the row remainder of a 32-sequence batch (gemm.hip gemm_plan).
 bool gemm_seq_form(int S, int N, int K, int act);
 void launch_gemm(const GemmArgs& a, hipStream_t st);
+// Rows of sequences of DIFFERENT lengths, packed back to back (the ragged prompt pass).  Which kernel computes a row stays a function of the row's
+// position in its own sequence: rows[0..n_rows) (device int32, built on the host from the lengths: the last seq_peel_rows(len) rows of every sequence
+// for which gemm_seq_form(len, N, K, act) holds) go through the split-K remainder kernel, every other row through an ascending-k kernel (any of them:
+// they agree bitwise, so tiles may straddle sequences).  In-place residual (R == C): the listed rows' residual is saved to r_save [n_rows][N] first,
+// so the remainder launch adds the ORIGINAL residual and every row ends up written with the value of its solo run.
+void launch_gemm_ragged(const GemmArgs& a, const int32_t* rows, int n_rows, bf16_t* r_save, hipStream_t st);
 // one fixed configuration (kernel256: 0 = 128^2 tiles, 1 = 256^2; peel: the row remainder over a multiple of 256 in its own launch), no tuning
 void launch_gemm_fixed(const GemmArgs& a, int kernel256, int peel, hipStream_t st);
 void set_mt2x(int on);                // 33..64-row decode GEMMs: 1 = activations through a wave-private LDS ring (gemm_skinny_mt2x_kernel, default), 0 = both operands in registers
@@ -206,10 +217,16 @@ void launch_im2col(const bf16_t* img, bf16_t* out, int B, int img_size, int patc
 void launch_vit_embed_lnpre(const bf16_t* patch_out, int ldp, const bf16_t* cls, const bf16_t* pos,
                             const bf16_t* g, const bf16_t* b, bf16_t* x, int B, int NP, int Dv, float eps,
                             hipStream_t st);
-void launch_dec_embed(const bf16_t* emb, const bf16_t* wpe, bf16_t* h, int B, int S0, int D, hipStream_t st);
+// row_pos (ragged prompt pass, B * S0 = packed rows): the position of every row inside its own sequence; nullptr: row % S0
+void launch_dec_embed(const bf16_t* emb, const bf16_t* wpe, bf16_t* h, int B, int S0, int D, hipStream_t st, const int32_t* row_pos = nullptr);
 // per_seq > 0: row r goes to out + (r / per_seq) * seq_stride + (r % per_seq) * D (token rows written behind the visual rows of a prefill buffer)
 void launch_gather_rows(const bf16_t* table, const int64_t* ids, bf16_t* out, int n, int D, hipStream_t st, int per_seq = 0, size_t seq_stride = 0);
-void launch_gather_last_rows(const bf16_t* h, bf16_t* out, int B, int S0, int D, hipStream_t st);
+// rag_seq (ragged prompt pass): per-sequence descriptors {first packed row, length}; nullptr: sequences of S0 rows
+void launch_gather_last_rows(const bf16_t* h, bf16_t* out, int B, int S0, int D, hipStream_t st, const int32_t* rag_seq = nullptr);
+// out[i][:] = x[rows[i]][:] (D % 8 == 0)
+void launch_gather_listed_rows(const bf16_t* x, int ldx, const int32_t* rows, int n, bf16_t* out, int D, hipStream_t st);
+// ragged prompt pass: row_pos[first row of b + j] = j for j < len[b], from the descriptors {first packed row, length} [B]
+void launch_ragged_row_pos(const int32_t* rag_seq, int B, int32_t* row_pos, hipStream_t st);
 void launch_gather_tail_rows(const bf16_t* h, bf16_t* out, int B, int S0, int n_keep, int D, hipStream_t st);
 
 // ---- adapter norm -------------------------------------------------------------------------------
@@ -230,7 +247,15 @@ struct AttnPrefillArgs {
     int window = 0;                                       // causal only: query q sees keys q - window < k <= q (StarCoder2); 0 = all
     int last_rows = 0;                                    // > 0: only the query tiles holding the last `last_rows` rows of every sequence are launched
     int q_tile0 = 0;                                      //   (set by the launcher: first query tile of the grid)
+    // Ragged form (causal prompt pass over packed sequences of different lengths): rag_seq [n_seq] = {first packed row, length}, rag_blocks
+    // [rag_nblocks] = {sequence, query tile} -- one block per entry (x heads), query tiles counted from the sequence's first row and key tiles from
+    // its key 0, exactly as in the sequence's solo launch; a block never covers rows of two sequences.  B / S / last_rows are unused then (the
+    // pruned last layer passes the list of every sequence's last query tile).
+    const int32_t* rag_seq = nullptr;
+    const int32_t* rag_blocks = nullptr;
+    int rag_nblocks = 0;
 };
+inline int attn_prefill_q_tile(int n_head, int n_kv_head) { const int g = n_head / (n_kv_head > 0 ? n_kv_head : 1); return (g % 4 == 0 && n_head % 4 == 0) ? 32 : 128; }
 void launch_attn_prefill(const AttnPrefillArgs& a, hipStream_t st);
 
 // paged KV cache geometry (one layer):  page = 64 tokens, K|V in MFMA-fragment order, 32 KiB
@@ -242,6 +267,10 @@ __host__ __device__ inline int kv_page_bytes(int head_dim) { return SV_PAGE_TOKE
 void launch_kv_write_prefill(const bf16_t* qkv, int row_stride, int k_off, int v_off, char* pool_layer,
                              const int32_t* block_table, int max_pages, int B, int S0, int head_dim,
                              hipStream_t st);
+// ragged form: rag_blocks [n_blocks] = {sequence, 32-token group of that sequence}; page and slot from the row's own sequence and position
+void launch_kv_write_prefill_ragged(const bf16_t* qkv, int row_stride, int k_off, int v_off, char* pool_layer,
+                                    const int32_t* block_table, int max_pages, const int32_t* rag_seq, const int32_t* rag_blocks,
+                                    int n_blocks, int head_dim, hipStream_t st);
 
 struct AttnDecodeArgs {
     const float* ws; int splitk; int ldws; int rows_ws;   // c_attn output as fp32 split-K slabs [splitk][rows][ldws], summed here in slab order
@@ -269,7 +298,7 @@ struct AttnDecodeArgs {
 };
 // in-place rotary embedding of the q and k heads of a prefill c_attn output (rotate_half convention)
 void launch_rope_prefill(bf16_t* qkv, int row_stride, int rows, int S0, int n_heads, int head_dim,
-                         const float* cos_t, const float* sin_t, hipStream_t st);
+                         const float* cos_t, const float* sin_t, hipStream_t st, const int32_t* row_pos = nullptr);
 void launch_attn_decode(const AttnDecodeArgs& a, hipStream_t st);
 // XCC_ID of every block of a 1-D launch of `blocks` 8-wave blocks (heavy = 1: with the decode attention's LDS footprint and 10 us of residence)
 int launch_xcc_probe(int32_t* out, int blocks, int heavy, hipStream_t st);

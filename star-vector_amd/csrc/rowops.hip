@@ -828,14 +828,14 @@ void launch_vit_embed_lnpre(const bf16_t* patch_out, int ldp, const bf16_t* cls,
 // decoder prefill input: h = bf(inputs_embeds + wpe[0..S0-1])   (gpt_bigcode :980-985,1060-1063)
 // ------------------------------------------------------------------------------------------------
 __global__ void dec_embed_kernel(const bf16_t* __restrict__ emb, const bf16_t* __restrict__ wpe,
-                                 bf16_t* __restrict__ h, int B, int S0, int D) {
+                                 bf16_t* __restrict__ h, int B, int S0, int D, const int32_t* __restrict__ row_pos) {
     const int NC = D >> 3;
     const size_t total = (size_t)B * S0 * NC;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (size_t)gridDim.x * blockDim.x) {
         const int c = (int)(i % NC);
         const size_t row = i / NC;
-        const int t = (int)(row % S0);
+        const int t = row_pos ? row_pos[row] : (int)(row % S0);
         float a[8], w[8];
         unpack8(*reinterpret_cast<const uint4*>(emb + row * D + c * 8), a);
         unpack8(*reinterpret_cast<const uint4*>(wpe + (size_t)t * D + c * 8), w);
@@ -844,11 +844,11 @@ __global__ void dec_embed_kernel(const bf16_t* __restrict__ emb, const bf16_t* _
         *reinterpret_cast<uint4*>(h + row * D + c * 8) = pack8(a);
     }
 }
-void launch_dec_embed(const bf16_t* emb, const bf16_t* wpe, bf16_t* h, int B, int S0, int D, hipStream_t st) {
+void launch_dec_embed(const bf16_t* emb, const bf16_t* wpe, bf16_t* h, int B, int S0, int D, hipStream_t st, const int32_t* row_pos) {
     size_t total = (size_t)B * S0 * (D / 8);
     int blocks = (int)((total + 255) / 256);
     if (blocks > 16384) blocks = 16384;
-    dec_embed_kernel<<<blocks, 256, 0, st>>>(emb, wpe, h, B, S0, D);
+    dec_embed_kernel<<<blocks, 256, 0, st>>>(emb, wpe, h, B, S0, D, row_pos);
 }
 
 // wte lookup (starvector_v1.py:16-18): out[i][:] = table[ids[i]][:]
@@ -876,12 +876,12 @@ void launch_gather_rows(const bf16_t* table, const int64_t* ids, bf16_t* out, in
 
 // last prompt row of every sequence (only that row feeds ln_f + lm_head in prefill)
 __global__ void gather_last_rows_kernel(const bf16_t* __restrict__ h, bf16_t* __restrict__ out, int B, int S0,
-                                        int D) {
+                                        int D, const int32_t* __restrict__ rag_seq) {
     const int NC = D >> 3;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B * NC; i += gridDim.x * blockDim.x) {
         const int c = i % NC, b = i / NC;
-        *reinterpret_cast<uint4*>(out + (size_t)b * D + c * 8) =
-            *reinterpret_cast<const uint4*>(h + ((size_t)b * S0 + S0 - 1) * D + c * 8);
+        const size_t last = rag_seq ? (size_t)(rag_seq[2 * b] + rag_seq[2 * b + 1] - 1) : (size_t)b * S0 + S0 - 1;
+        *reinterpret_cast<uint4*>(out + (size_t)b * D + c * 8) = *reinterpret_cast<const uint4*>(h + last * D + c * 8);
     }
 }
 // the last n_keep rows of every sequence, packed [B * n_keep][D] (scoring forward: logits of the kept positions only)
@@ -903,9 +903,30 @@ void launch_gather_tail_rows(const bf16_t* h, bf16_t* out, int B, int S0, int n_
     if (blocks > 16384) blocks = 16384;
     gather_tail_rows_kernel<<<blocks, 256, 0, st>>>(h, out, B, S0, n_keep, D);
 }
-void launch_gather_last_rows(const bf16_t* h, bf16_t* out, int B, int S0, int D, hipStream_t st) {
+void launch_gather_last_rows(const bf16_t* h, bf16_t* out, int B, int S0, int D, hipStream_t st, const int32_t* rag_seq) {
     int total = B * (D / 8);
-    gather_last_rows_kernel<<<(total + 255) / 256, 256, 0, st>>>(h, out, B, S0, D);
+    gather_last_rows_kernel<<<(total + 255) / 256, 256, 0, st>>>(h, out, B, S0, D, rag_seq);
+}
+// the listed rows of x, packed (the residual rows a ragged GEMM's remainder launch adds: saved before the first pass updates them in place)
+__global__ void gather_listed_rows_kernel(const bf16_t* __restrict__ x, int ldx, const int32_t* __restrict__ rows, int n, bf16_t* __restrict__ out, int D) {
+    const int NC = D >> 3;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n * NC; i += gridDim.x * blockDim.x) {
+        const int c = i % NC, r = i / NC;
+        *reinterpret_cast<uint4*>(out + (size_t)r * D + c * 8) = *reinterpret_cast<const uint4*>(x + (size_t)rows[r] * ldx + c * 8);
+    }
+}
+void launch_gather_listed_rows(const bf16_t* x, int ldx, const int32_t* rows, int n, bf16_t* out, int D, hipStream_t st) {
+    if (n < 1) return;
+    const int total = n * (D / 8);
+    gather_listed_rows_kernel<<<(total + 255) / 256, 256, 0, st>>>(x, ldx, rows, n, out, D);
+}
+// ragged prompt pass: one block per sequence writes the positions 0 .. len - 1 of its packed rows
+__global__ void ragged_row_pos_kernel(const int32_t* __restrict__ rag_seq, int32_t* __restrict__ row_pos) {
+    const int r0 = rag_seq[2 * blockIdx.x], len = rag_seq[2 * blockIdx.x + 1];
+    for (int j = threadIdx.x; j < len; j += blockDim.x) row_pos[r0 + j] = j;
+}
+void launch_ragged_row_pos(const int32_t* rag_seq, int B, int32_t* row_pos, hipStream_t st) {
+    ragged_row_pos_kernel<<<B, 256, 0, st>>>(rag_seq, row_pos);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -237,6 +237,46 @@ class HipEngine:
         check(self.lib.sv_prefill(self._h, _ptr(x), B, S0, _ptr(logits), _stream()), "sv_prefill")
         return logits
 
+    def _packed(self, embeds, lengths=None):
+        """A ragged batch as (packed [sum(len), D] bf16, ctypes int32 lengths, list of lengths): from a list of [S_i, D] tensors, or from
+        an already packed tensor and its lengths."""
+        if lengths is None:
+            seqs = [t.reshape(-1, t.shape[-1]) for t in embeds]
+            if not seqs:
+                raise ValueError("empty ragged batch")
+            lens = [int(t.shape[0]) for t in seqs]
+            x = torch.cat(seqs, dim=0) if len(seqs) > 1 else seqs[0]
+        else:
+            lens = [int(v) for v in lengths]
+            x = embeds
+        x = _need(x, torch.bfloat16, "inputs_embeds")
+        if x.dim() != 2 or x.shape[1] != self.cfg.hidden:
+            raise ValueError(f"packed inputs_embeds must be [sum(lengths), {self.cfg.hidden}], got {list(x.shape)}")
+        if not lens or min(lens) < 1 or sum(lens) != x.shape[0]:
+            raise ValueError(f"lengths {lens} do not describe the {x.shape[0]} packed rows (each >= 1)")
+        return x, (C.c_int32 * len(lens))(*lens), lens
+
+    def prefill_ragged(self, embeds, lengths=None) -> torch.Tensor:
+        """One prompt pass over sequences of different lengths (sv_prefill_ragged): `embeds` a list of [S_i, D] tensors, or a packed
+        [sum(lengths), D] tensor with `lengths`.  Returns the last-row logits [B, vocab]; every row's logits and KV entries are the bits
+        of `prefill` on that sequence alone, and `decode_step` continues every row at its own position."""
+        x, arr, lens = self._packed(embeds, lengths)
+        logits = torch.empty(len(lens), self.cfg.vocab, dtype=torch.float32, device=x.device)
+        check(self.lib.sv_prefill_ragged(self._h, _ptr(x), len(lens), arr, _ptr(logits), _stream()), "sv_prefill_ragged")
+        return logits
+
+    def generate_ragged(self, embeds, max_length: int, lengths=None, **kw):
+        """`generate` over prompts of different lengths in ONE prompt pass (sv_generate_ragged): HF's padded-batch semantics, `max_length`
+        counts from the longest prompt, every row gets max_length - max(lengths) new tokens.  Same keywords and return value as `generate`."""
+        x, _arr, lens = self._packed(embeds, lengths)
+        return self.generate(x, max_length, lengths=lens, **kw)
+
+    def prompt_passes(self) -> int:
+        """Prompt passes (rectangular and ragged, admits included) this engine has run so far (sv_debug_prompt_passes)."""
+        n = C.c_int64(0)
+        check(self.lib.sv_debug_prompt_passes(self._h, C.byref(n)), "sv_debug_prompt_passes")
+        return int(n.value)
+
     def forward_logits(self, inputs_embeds: torch.Tensor, num_logits_to_keep: int = 0) -> torch.Tensor:
         """Scoring forward: bf16 logits [B, n, vocab] of the last n = num_logits_to_keep positions (0 = all positions)."""
         x = _need(inputs_embeds, torch.bfloat16, "inputs_embeds")
@@ -288,8 +328,10 @@ class HipEngine:
                  repetition_penalty: float = 1.0, num_beams: int = 1, length_penalty: float = 1.0,
                  early_stopping=False, top_k: int = 0, on_tokens=None, min_new_tokens: int = 0,
                  scores_out: Optional[torch.Tensor] = None, logits_out: Optional[torch.Tensor] = None,
-                 return_outputs: bool = False):
+                 return_outputs: bool = False, lengths: Optional[Sequence[int]] = None):
         """HF ``generate`` semantics for inputs_embeds: returns ONLY the new tokens, int64 [B, N].
+        ``lengths``: the ragged form -- inputs_embeds is packed [sum(lengths), D], one prompt pass for all of them, ``max_length`` counts from
+        the longest prompt (see ``generate_ragged``).
         ``num_beams`` > 1 runs HF's beam search on device (``early_stopping``: False, True or "never"); with
         ``do_sample`` it is HF's beam-sample.  ``top_k`` (0 = off) is HF's TopKLogitsWarper, applied before top-p.
         ``on_tokens(tokens [B, n] int64 cpu, first_col)``: streaming callback, called every ``sync_every`` steps with the
@@ -299,8 +341,13 @@ class HipEngine:
         B * num_beams under beam search; ld >= vocab) that receive HF's processed scores / raw logits of every generated column.
         ``return_outputs=True`` returns a dict {"sequences", "n_generated"} plus, under beam search, "sequences_scores" [B] and
         "beam_indices" [B, n] int64 instead of the bare token tensor."""
-        x = _need(inputs_embeds, torch.bfloat16, "inputs_embeds")
-        B, S0, D = x.shape
+        lens_arr = None
+        if lengths is not None:
+            x, lens_arr, lens = self._packed(inputs_embeds, lengths)
+            B, S0, D = len(lens), max(lens), x.shape[1]
+        else:
+            x = _need(inputs_embeds, torch.bfloat16, "inputs_embeds")
+            B, S0, D = x.shape
         if D != self.cfg.hidden:
             raise ValueError("inputs_embeds hidden size mismatch")
         max_new = max_length - S0
@@ -320,7 +367,11 @@ class HipEngine:
         out = torch.empty(B, max_new, dtype=torch.int64, device=x.device)
         n = C.c_int32(0)
         if scores_out is None and logits_out is None and not return_outputs:
-            check(self.lib.sv_generate(self._h, _ptr(x), B, S0, C.byref(sp), _ptr(out), C.byref(n), _stream()), "sv_generate")
+            if lens_arr is not None:
+                check(self.lib.sv_generate_ragged(self._h, _ptr(x), B, lens_arr, C.byref(sp), None, _ptr(out), C.byref(n), _stream()),
+                      "sv_generate_ragged")
+            else:
+                check(self.lib.sv_generate(self._h, _ptr(x), B, S0, C.byref(sp), _ptr(out), C.byref(n), _stream()), "sv_generate")
             if cb_errors:
                 raise cb_errors[0]
             return out[:, : n.value]
@@ -346,8 +397,12 @@ class HipEngine:
         if beam:
             outs.host_sequences_scores = C.cast(seq_scores, C.POINTER(C.c_float))
             outs.host_beam_indices = C.cast(beam_idx, C.POINTER(C.c_int64))
-        check(self.lib.sv_generate_ex(self._h, _ptr(x), B, S0, C.byref(sp), C.byref(outs), _ptr(out), C.byref(n), _stream()),
-              "sv_generate_ex")
+        if lens_arr is not None:
+            check(self.lib.sv_generate_ragged(self._h, _ptr(x), B, lens_arr, C.byref(sp), C.byref(outs), _ptr(out), C.byref(n), _stream()),
+                  "sv_generate_ragged")
+        else:
+            check(self.lib.sv_generate_ex(self._h, _ptr(x), B, S0, C.byref(sp), C.byref(outs), _ptr(out), C.byref(n), _stream()),
+                  "sv_generate_ex")
         if cb_errors:
             raise cb_errors[0]
         L = n.value
@@ -367,6 +422,17 @@ class HipEngine:
         min_new_tokens=0), plus the vLLM-semantics keys (include/starvector_hip.h, ABI 9; they need semantics="vllm"):
         presence_penalty=0, frequency_penalty=0, min_p=0, prompt_ids=None, logit_bias=None ({id: bias}), stop_any_ids=None.
         Returns the slot ids.  Raises StarVectorBusy when slots or KV pages are short."""
+        if isinstance(inputs_embeds, (list, tuple)):
+            # per-request embeddings [S_i, D] of different lengths: ONE ragged prompt pass for all of them (sv_cb_admit_ragged)
+            x, lens_arr, lens = self._packed(inputs_embeds)
+            n = len(lens)
+            if n != len(requests):
+                raise ValueError("inputs_embeds / requests mismatch")
+            arr, keep = cb_requests(requests)
+            slots = (C.c_int32 * n)()
+            check(self.lib.sv_cb_admit_ragged(self._h, _ptr(x), n, lens_arr, arr, slots, _stream()), "sv_cb_admit_ragged")
+            del keep
+            return list(slots)
         x = _need(inputs_embeds, torch.bfloat16, "inputs_embeds")
         n, S0, D = x.shape
         if D != self.cfg.hidden or n != len(requests):
@@ -691,6 +757,19 @@ def gemm_seq_form(S: int, N: int, K: int, act: str = "none") -> bool:
     if rc < 0:
         check(rc, "sv_debug_gemm_seq_form")
     return rc == 1
+
+
+def ragged_plan(lengths: Sequence[int], N: int, K: int, act: str = "none", q_tile: int = 32) -> Dict[str, object]:
+    """What the ragged prompt pass decides for sequences of these lengths at the projection (N, K, act) (sv_debug_ragged_plan; host
+    arithmetic): the packed rows that take the split-K remainder kernel, the sequences whose last row is one of them, and the sizes of
+    the attention / KV-write block lists."""
+    lens = [int(v) for v in lengths]
+    B = len(lens)
+    cap = max(3 * B, 1)
+    rows, last, out = (C.c_int32 * cap)(), (C.c_int32 * cap)(), (C.c_int32 * 4)()
+    check(_lib.load().sv_debug_ragged_plan((C.c_int32 * max(B, 1))(*lens), B, int(N), int(K), _lib.ACT[act], int(q_tile), rows, last, cap, out),
+          "sv_debug_ragged_plan")
+    return {"rows": list(rows)[: out[0]], "last": list(last)[: out[1]], "attn_blocks": out[2], "kv_blocks": out[3]}
 
 
 def set_skinny_form(form: int) -> None:

@@ -471,7 +471,12 @@ class HipCausalLM(_EngineModule):
         mask = attention_mask.to(torch.bool)
         B, S, _ = inputs_embeds.shape
         if not bool(mask[:, -1].all()):
-            raise ValueError("the last prompt position of every row must be a real token (generation continues from it)")
+            # right padding: only the ragged route takes it (every row runs with its padding removed, wherever the padding sits); the
+            # rectangular length-group route continues from the last position and needs a real token there
+            if not hasattr(self._engine, "prefill_ragged"):
+                raise ValueError("the last prompt position of every row must be a real token (generation continues from it)")
+            if not bool(mask.any(dim=1).all()):
+                raise ValueError("every row needs at least one real prompt position")
         budget = int(kw["max_length"]) - S                         # HF counts the budget from the PADDED prompt length
         if budget <= 0:
             raise ValueError(f"max_length ({kw['max_length']}) must exceed the prompt length ({S})")
@@ -482,6 +487,9 @@ class HipCausalLM(_EngineModule):
         if (int(kw.get("num_beams") or 1) == 1 and hasattr(eng, "cb_admit") and B <= eng.cfg.max_batch
                 and (getattr(self, "batcher", None) is None or _in_exclusive_job())):
             return self._generate_padded_slots(inputs_embeds, mask, lengths, budget, pad, stop, kw)
+        nb = int(kw.get("num_beams") or 1)
+        if nb > 1 and hasattr(eng, "generate_ragged") and B * nb <= eng.cfg.max_batch:
+            return self._generate_padded_beams(inputs_embeds, mask, lengths, budget, pad, stop, kw)
         outs, fired_at = [None] * B, None
         for n in sorted(set(lengths)):
             rows = [b for b in range(B) if lengths[b] == n]
@@ -502,9 +510,45 @@ class HipCausalLM(_EngineModule):
             res[b, :k] = t[:k]
         return res
 
+    def _generate_padded_beams(self, inputs_embeds, mask, lengths, budget, pad, stop, kw):
+        """Beam search / beam-sample over a padded batch as ONE ragged engine call (sv_generate_ragged): one prompt pass over the rows
+        with their padding removed and one search for all requests, instead of a complete serial generate call per length group.  The
+        engine follows HF's padded-batch semantics itself: the budget counts from the longest prompt (so max_length = longest + the budget
+        HF derives from the padded length), the row-0 stop ends every request, finished hypotheses are padded."""
+        eng = self._engine
+        S = inputs_embeds.shape[1]
+        seqs = [inputs_embeds[b][mask[b]].to(torch.bfloat16).contiguous() for b in range(inputs_embeds.shape[0])]
+        min_new = max(int(kw.get("min_length") or 0) - S, 0)
+
+        def call():
+            lock = getattr(eng, "call_lock", None) or contextlib.nullcontext()
+            with lock:
+                return eng.generate_ragged(
+                    seqs, max_length=max(lengths) + budget, do_sample=bool(kw.get("do_sample")),
+                    temperature=float(kw.get("temperature") if kw.get("temperature") is not None else 1.0),
+                    top_p=float(kw.get("top_p") if kw.get("top_p") is not None else 1.0),
+                    eos_token_id=int(self.eos_token_id if kw.get("eos_token_id") is None else kw["eos_token_id"]), pad_token_id=pad,
+                    stop_ids=stop, seed=int(kw.get("seed") or 0), repetition_penalty=float(kw.get("repetition_penalty") or 1.0),
+                    num_beams=int(kw["num_beams"]), length_penalty=float(kw.get("length_penalty") if kw.get("length_penalty") is not None else 1.0),
+                    early_stopping=kw.get("early_stopping") or False, top_k=int(kw.get("top_k") or 0),
+                    **({"min_new_tokens": min_new} if min_new else {}))
+        batcher = getattr(self, "batcher", None)
+        if batcher is not None and not _in_exclusive_job():
+            def job():                            # requests share the engine: the search runs with the engine to itself, in turn
+                _EXCLUSIVE.active = True
+                try:
+                    return call()
+                finally:
+                    _EXCLUSIVE.active = False
+            toks = batcher.run_exclusive(job)
+        else:
+            toks = call()
+        return toks.to(inputs_embeds.device)
+
     def _generate_padded_slots(self, inputs_embeds, mask, lengths, budget, pad, stop, kw):
         """Rows of different real length in ONE decode loop: every row is a slot of the engine's continuous batch (own prompt
-        length, positions and KV pages), prompt passes run per length group (they are rectangular), and all rows then decode
+        length, positions and KV pages), the prompt pass is ONE ragged pass over all rows where the engine offers it
+        (`prefill_ragged`; else prompt passes run per length group: they are rectangular), and all rows then decode
         together -- instead of one full generate call per length group.  HF semantics of the padded batch are restored on
         the host: the reference's row-0 stop ends every row at row 0's step, finished rows are padded."""
         eng = self._engine
@@ -532,7 +576,14 @@ class HipCausalLM(_EngineModule):
         B = inputs_embeds.shape[0]
         eng.cb_reset()
         try:
-            for n in sorted(set(lengths)):
+            if hasattr(eng, "prefill_ragged"):
+                # one ragged prompt pass for all rows; the per-row seeds are those of the length-group route: same tokens
+                embs = [inputs_embeds[b][mask[b]].to(torch.bfloat16).contiguous() for b in range(B)]
+                reqs = [dict(base, seed=(seed + 0x9E3779B97F4A7C15 * b) & (2 ** 63 - 1), stop_ids=stop if b == 0 else None)
+                        for b in range(B)]
+                for b, s_ in enumerate(eng.cb_admit(embs, reqs)):
+                    slot_of[b] = s_
+            for n in ([] if hasattr(eng, "prefill_ragged") else sorted(set(lengths))):
                 rows = [b for b in range(B) if lengths[b] == n]
                 emb = torch.stack([inputs_embeds[b][mask[b]] for b in rows], 0).to(torch.bfloat16).contiguous()
                 reqs = [dict(base, seed=(seed + 0x9E3779B97F4A7C15 * b) & (2 ** 63 - 1), stop_ids=stop if b == 0 else None)
