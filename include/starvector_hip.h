@@ -292,6 +292,23 @@ int  sv_generate_ex(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0,
                     const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream);
 int  sv_generate_ragged(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, const sv_sampling* sp,
                         const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream);
+/* ---- several samples of ONE prompt from one prompt pass (GRPO roll-outs: num_return_sequences = G; vLLM: SamplingParams.n).
+ * sv_generate_shared: B prompts -- host_lens NULL: dev_embeds_packed is [B][S0][hidden]; otherwise the ragged form, prompts of host_lens[b] rows
+ * packed back to back (S0 ignored) -- and n_samples continuations of each: B * n_samples <= max_batch decode rows, row b * n_samples + j = sample j
+ * of prompt b, the row order of repeat_interleave.  The prompt pass runs over the B prompts only; the rows of a prompt share its full 64-token KV
+ * pages through the block table and own every page from the prompt's partially filled tail page on (copied once, on device, before the first
+ * token).  Contract: tokens, *n_generated and the per-step outputs are BIT-IDENTICAL to sv_generate_ex / sv_generate_ragged over the prompts
+ * repeated n_samples times each (the sampler draws from (seed, step, row)).  dev_out_tokens [B * n_samples][max_new]; outs rows = B * n_samples;
+ * streaming delivers B * n_samples rows; n_samples = 1 is sv_generate_ex / sv_generate_ragged.  num_beams > 1 with n_samples > 1: SV_ENOTSUP.
+ * sv_cb_admit_shared: the group admit of a continuous batch -- n_prompts prompts (ragged, packed), n requests, request i samples prompt
+ * host_group[i] and keeps its own sv_cb_request (seed, budget, sampler, stop ids).  Prompts are numbered in the order their first request appears
+ * (host_group[0] = 0, host_group[i] <= max(host_group[0..i)) + 1, every prompt used).  One prompt pass over the prompts; each request's tokens are
+ * those of its solo sv_cb_admit.  A prompt's full pages are held once and reference-counted: sv_cb_release of a sample returns its own pages at once
+ * and a shared page when its last holder lets go.  SV_EBUSY (nothing admitted) when n slots or
+ * sum_u len_u / 64 + sum_i (ceil((len + budget_i) / 64) - len / 64) pages are not free.  SV_EINVAL before any device work for null pointers,
+ * n_samples < 1, a length < 1, host_group[i] out of range or out of order. */
+int  sv_generate_shared(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, int32_t S0, int32_t n_samples,
+                        const sv_sampling* sp, const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream);
 /* ---- continuous batching (the reference worker's 5 concurrent requests, serve/model_worker.py:161-172,
  * 216-229, as ONE decode loop).  Every row ("slot") of the engine's batch is an independent request: own sampling parameters,
  * budget, EOS, stop sequence (the reference's row-0 stop, starvector_base.py:9-20, is right for one request per generate call
@@ -333,6 +350,8 @@ int  sv_cb_admit(sv_engine* e, const void* dev_embeds, int32_t n, int32_t S0, co
                  sv_stream stream);
 int  sv_cb_admit_ragged(sv_engine* e, const void* dev_embeds_packed, int32_t n, const int32_t* host_lens, const sv_cb_request* reqs,
                         int32_t* slots_out, sv_stream stream);
+int  sv_cb_admit_shared(sv_engine* e, const void* dev_embeds_packed, int32_t n_prompts, const int32_t* host_lens, int32_t n,
+                        const int32_t* host_group, const sv_cb_request* reqs, int32_t* slots_out, sv_stream stream);
 int  sv_cb_step(sv_engine* e, int32_t n_steps, int32_t* n_live, sv_stream stream);
 int  sv_cb_poll(sv_engine* e, int32_t* host_live, int32_t* host_steps, int32_t capacity);
 int  sv_cb_read(sv_engine* e, int32_t slot, int32_t first, int32_t count, int64_t* host_tokens);

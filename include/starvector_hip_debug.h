@@ -107,6 +107,19 @@ int  sv_debug_gemm_seq_form(int32_t S, int32_t N, int32_t K, int32_t act);
      capacity >= 3 * B; q_tile 32 or 128 (grouped-query heads in fours / one head per block). */
 int  sv_debug_ragged_plan(const int32_t* lens, int32_t B, int32_t N, int32_t K, int32_t act, int32_t q_tile, int32_t* rows_out,
                           int32_t* last_out, int32_t capacity, int32_t* out4);
+/*   sv_debug_shared_plan      the page plan of a shared prompt pass (sv_generate_shared, sv_cb_admit_shared): n requests over n_prompts prompts of
+     lengths lens[u], request i samples prompt group[i] with a budget of budgets[i] new tokens.  Host arithmetic only.  shared_out [n]: the leading
+     block-table entries of request i that are its prompt's full pages, lens[group[i]] / 64, held ONCE per prompt; private_out [n]: the pages the
+     request owns, ceil((len + budget) / 64) - len / 64 (the prompt's partially filled tail page included); *total_out = the pages the admit takes =
+     sum over prompts of len / 64 + sum over requests of private.  SV_EINVAL for the arguments sv_cb_admit_shared rejects: a length or budget < 1,
+     group[i] outside [0, n_prompts), prompts not numbered in the order their first request appears, a prompt no request references.
+     sv_debug_block_table      the block-table row of a decode row / slot as the device holds it -> host_out [capacity >= pages per sequence]; returns
+     the number of entries (> 0).  Needs a GPU.
+     sv_debug_free_pages       pages on the host allocator's free list / pages of the pool, after the last generate call or admit / release */
+int  sv_debug_shared_plan(const int32_t* lens, int32_t n_prompts, const int32_t* group, const int32_t* budgets, int32_t n,
+                          int32_t* shared_out, int32_t* private_out, int64_t* total_out);
+int  sv_debug_block_table(sv_engine* e, int32_t row, int32_t* host_out, int32_t capacity);
+int  sv_debug_free_pages(sv_engine* e, int32_t* free_out, int32_t* total_out);
 /*   sv_debug_prompt_passes    prompt passes (rectangular and ragged, continuous-batching admits included) this engine has run so far */
 int  sv_debug_prompt_passes(sv_engine* e, int64_t* out);
 /* The decode attention (gpt_bigcode/modeling_gpt_bigcode.py:151-285, llm/starcoder2.py:22-27 sliding window) on

@@ -110,6 +110,8 @@ PRODUCT_PROTOTYPES = {
     "sv_prefill": (_I, [_P, _P, _I, _I, _P, _P]),
     "sv_prefill_ragged": (_I, [_P, _P, _I, C.POINTER(_I), _P, _P]),
     "sv_generate_ragged": (_I, [_P, _P, _I, C.POINTER(_I), C.POINTER(SvSampling), C.POINTER(SvGenerateOutputs), _P, C.POINTER(_I), _P]),
+    "sv_generate_shared": (_I, [_P, _P, _I, C.POINTER(_I), _I, _I, C.POINTER(SvSampling), C.POINTER(SvGenerateOutputs), _P, C.POINTER(_I), _P]),
+    "sv_cb_admit_shared": (_I, [_P, _P, _I, C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(SvCbRequest), C.POINTER(_I), _P]),
     "sv_cb_admit_ragged": (_I, [_P, _P, _I, C.POINTER(_I), C.POINTER(SvCbRequest), C.POINTER(_I), _P]),
     "sv_forward_logits": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "sv_forward_logprobs": (_I, [_P, _P, _I, _I, _I, _P, _F, _P, _P, _P, _P, _P]),
@@ -144,6 +146,9 @@ DEBUG_PROTOTYPES = {
     "sv_debug_gemm_seq_form": (_I, [_I, _I, _I, _I]),
     "sv_debug_ragged_plan": (_I, [C.POINTER(_I), _I, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, C.POINTER(_I)]),
     "sv_debug_prompt_passes": (_I, [_P, C.POINTER(C.c_int64)]),
+    "sv_debug_shared_plan": (_I, [C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_int64)]),
+    "sv_debug_block_table": (_I, [_P, _I, C.POINTER(_I), _I]),
+    "sv_debug_free_pages": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
     "sv_debug_attn_plan": (_I, [_I, _I, _I, C.POINTER(_I)]),
     "sv_debug_rowln_plan": (_I, [_I, _I, _I, _I, _I, C.POINTER(_I)]),
     "sv_debug_rowln_occupancy": (_I, [_I, C.POINTER(_I)]),

@@ -27,6 +27,7 @@ class _Request:
     def __init__(self, emb: Optional[torch.Tensor], params: dict, on_tokens: Optional[Callable], exclusive: Optional[Callable] = None):
         self.emb, self.params, self.on_tokens = emb, params, on_tokens
         self.exclusive = exclusive         # a callable that needs the engine to itself (beam search, scoring forward)
+        self.group = None                  # submit_group: the requests that sample the same prompt carry the same token
         self.value = None
         self.slot: Optional[int] = None
         self.sent = 0                      # tokens already handed over
@@ -78,6 +79,27 @@ class ContinuousBatcher:
             self._lock.notify_all()
         return req
 
+    def submit_group(self, inputs_embeds: torch.Tensor, params_list, on_tokens: Optional[Callable] = None) -> List[_Request]:
+        """Several samples of ONE prompt: inputs_embeds [1, S0, D], one params dict per sample (own seed, budget, sampler).  Returns one
+        handle per sample, each what `submit` returns.  Where the engine offers `cb_admit_shared` the samples that are admitted together
+        share one prompt pass and the prompt's full KV pages; a group larger than the free slots (or than max_batch) is admitted in parts
+        as slots and pages come free -- each part shares among itself -- so it never waits for all its slots at once."""
+        if inputs_embeds.dim() != 3 or inputs_embeds.shape[0] != 1:
+            raise ValueError("one prompt per group: inputs_embeds must be [1, S0, D]")
+        params_list = [dict(p) for p in params_list]
+        if not params_list or any(int(p.get("max_new_tokens", 0)) < 1 for p in params_list):
+            raise ValueError("a group needs at least one sample, each with max_new_tokens >= 1")
+        token = object()
+        reqs = [_Request(inputs_embeds, p, on_tokens) for p in params_list]
+        for r in reqs:
+            r.group = token
+        with self._lock:
+            if self._closing:
+                raise RuntimeError("the batcher is closed")
+            self._pending.extend(reqs)
+            self._lock.notify_all()
+        return reqs
+
     def generate(self, inputs_embeds: torch.Tensor, params: dict, on_tokens: Optional[Callable] = None,
                  timeout: Optional[float] = None) -> torch.Tensor:
         return self.submit(inputs_embeds, params, on_tokens).result(timeout)
@@ -125,7 +147,14 @@ class ContinuousBatcher:
             group = group[:room]
             while group:
                 try:
-                    if ragged:
+                    keys = [id(r) if r.group is None else id(r.group) for r in group]
+                    prompts = list(dict.fromkeys(keys))         # in the order of their first request
+                    if ragged and len(prompts) < len(group) and hasattr(self.engine, "cb_admit_shared"):
+                        # samples of one prompt among them: one prompt pass per PROMPT, its full KV pages shared (sv_cb_admit_shared)
+                        first = {k: r for r, k in reversed(list(zip(group, keys)))}
+                        slots = self.engine.cb_admit_shared([first[k].emb[0] for k in prompts], None, [prompts.index(k) for k in keys],
+                                                            [r.params for r in group])
+                    elif ragged:
                         slots = self.engine.cb_admit([r.emb[0] for r in group], [r.params for r in group])
                     else:
                         slots = self.engine.cb_admit(torch.cat([r.emb for r in group], 0), [r.params for r in group])

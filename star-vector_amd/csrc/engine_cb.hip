@@ -89,6 +89,7 @@ static int cb_begin(sv_engine* e, hipStream_t st) {
     for (int p = e->num_pages - 1; p >= 0; --p) e->free_pages.push_back(p);
     std::fill(e->cb_used.begin(), e->cb_used.end(), 0);
     for (auto& v : e->cb_pages) v.clear();
+    e->page_refs.assign((size_t)e->num_pages + 1, 0);
     const size_t R = (size_t)e->MT * 32;
     std::vector<int32_t> table((size_t)e->cfg.max_batch * e->pages_per_seq, e->trash_page);
     HIPCHECK(hipMemcpyAsync(e->block_table, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -239,6 +240,184 @@ extern "C" int sv_cb_admit_ragged(sv_engine* e, const void* dev_embeds_packed, i
     return cb_admit_impl(e, dev_embeds_packed, n, 0, host_lens, reqs, slots_out, stream);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Group admit (sv_cb_admit_shared): n requests over n_prompts prompts, request i samples prompt group[i].  One ragged prompt pass over the
+// PROMPTS, the fork launch into the n slots (fork.hip), the first-token step.  Page plan as sv_generate_shared's: the slots of a prompt share its
+// full pages (held once, reference-counted in page_refs), every slot owns its pages from the prompt's tail page on.  Shared pages are never written
+// after the prompt pass: a decode step writes at its slot's own position, i.e. into a private page.
+// ------------------------------------------------------------------------------------------------
+namespace sveng {
+// Prompts are numbered in the order their first request appears: group[0] = 0, group[i] <= max(group[0..i)) + 1, every prompt used -- so that
+// group[i] <= i, which the in-place fan-out of the logits rows needs (fork.hip).
+int shared_check_group(const char* who, const int32_t* lens, int n_prompts, const int32_t* group, int n) {
+    if (!lens || !group) return fail(SV_EINVAL, "%s: null host_lens / host_group", who);
+    if (n_prompts < 1 || n < 1 || n_prompts > n) return fail(SV_EINVAL, "%s: bad n_prompts=%d / n=%d (1 <= n_prompts <= n)", who, n_prompts, n);
+    for (int u = 0; u < n_prompts; ++u)
+        if (lens[u] < 1) return fail(SV_EINVAL, "%s: prompt %d: bad prompt length %d", who, u, lens[u]);
+    int hi = -1;
+    for (int i = 0; i < n; ++i) {
+        if (group[i] < 0 || group[i] >= n_prompts) return fail(SV_EINVAL, "%s: group[%d] = %d outside [0, n_prompts = %d)", who, i, group[i], n_prompts);
+        if (group[i] > hi + 1)
+            return fail(SV_EINVAL, "%s: group[%d] = %d: prompts are numbered in the order their first request appears (prompt %d has none before it)", who, i,
+                        group[i], hi + 1);
+        hi = group[i] > hi ? group[i] : hi;
+    }
+    if (hi + 1 != n_prompts) return fail(SV_EINVAL, "%s: prompt %d is referenced by no request", who, hi + 1);
+    return 0;
+}
+// pages of request i: the first shared[i] entries of its block-table row are its prompt's (held once per prompt), private_[i] are its own;
+// returns what the admit takes from the free list: sum over prompts of len / 64 + sum over requests of ceil((len + budget) / 64) - len / 64
+long long shared_page_plan(const int32_t* lens, int n_prompts, const int32_t* group, const int32_t* budgets, int n, int32_t* shared, int32_t* private_) {
+    long long total = 0;
+    for (int u = 0; u < n_prompts; ++u) total += lens[u] / SV_PAGE_TOKENS;
+    for (int i = 0; i < n; ++i) {
+        const int len = lens[group[i]], sh = len / SV_PAGE_TOKENS;
+        const int pv = (len + budgets[i] + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS - sh;
+        if (shared) shared[i] = sh;
+        if (private_) private_[i] = pv;
+        total += pv;
+    }
+    return total;
+}
+}  // namespace sveng
+
+static int cb_admit_shared_impl(sv_engine* e, const void* dev_embeds, int32_t U, const int32_t* lens, int32_t n, const int32_t* group,
+                                const sv_cb_request* reqs, int32_t* slots_out, sv_stream stream) {
+    const sv_config& c = e->cfg;
+    const int mp = e->pages_per_seq, mb = c.max_batch;
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIPCHECK(hipSetDevice(c.device));
+    HIPCHECK(hipEventRecord(e->gen_event, (hipStream_t)stream));
+    hipStream_t st = e->gen_stream;
+    HIPCHECK(hipStreamWaitEvent(st, e->gen_event, 0));
+    SVCHECK(cb_begin(e, st));
+    if (!e->fork_desc) SVCHECK(dalloc(e, &e->fork_desc, 6 * (size_t)mb));
+    std::vector<int> slots;
+    for (int s2 = 0; s2 < mb && (int)slots.size() < n; ++s2) if (!e->cb_used[s2]) slots.push_back(s2);
+    std::vector<int32_t> budgets(n), n_sh(n), n_pv(n);
+    for (int i = 0; i < n; ++i) budgets[i] = reqs[i].max_new_tokens;
+    const size_t need_pages = (size_t)shared_page_plan(lens, U, group, budgets.data(), n, n_sh.data(), n_pv.data());
+    if ((int)slots.size() < n || need_pages > e->free_pages.size())
+        return fail(SV_EBUSY, "sv_cb_admit_shared: %d requests over %d prompts need %d slots / %zu KV pages, %zu / %zu are free (release finished slots first)",
+                    n, U, n, need_pages, slots.size(), e->free_pages.size());
+    // host bookkeeping; `taken` = the pages in the order they left the free list (a failed admit puts them back in reverse)
+    std::vector<int> taken;
+    auto take = [&]() { const int pg = e->free_pages.back(); e->free_pages.pop_back(); taken.push_back(pg); return pg; };
+    std::vector<int32_t> rows((size_t)n * mp, e->trash_page), pf((size_t)U * mp, e->trash_page), desc(6 * (size_t)mb, 0);
+    std::vector<std::vector<int>> prompt_pages(U);
+    std::vector<int> owner(U, -1), n_dst(U, 0);
+    for (int u = 0; u < U; ++u)
+        for (int k = 0; k < lens[u] / SV_PAGE_TOKENS; ++k) prompt_pages[u].push_back(take());
+    std::vector<CbSlot> hs(n);
+    std::vector<CbBias> hb(n);
+    std::vector<std::vector<uint32_t>> seen_rows(n);
+    std::vector<int32_t> map(n), pos(n);
+    const bool any_pen = [&] { for (int i = 0; i < n; ++i) if (reqs[i].repetition_penalty > 0.f && reqs[i].repetition_penalty != 1.0f) return true; return false; }();
+    for (int i = 0; i < n; ++i) {
+        const int s2 = slots[i], u = group[i];
+        e->cb_pages[s2].clear();
+        for (int k = 0; k < n_sh[i]; ++k) {
+            rows[(size_t)i * mp + k] = prompt_pages[u][k];
+            e->cb_pages[s2].push_back(prompt_pages[u][k]);
+            ++e->page_refs[prompt_pages[u][k]];
+        }
+        for (int k = 0; k < n_pv[i]; ++k) {
+            const int pg = take();
+            rows[(size_t)i * mp + n_sh[i] + k] = pg;
+            e->cb_pages[s2].push_back(pg);
+        }
+        if (owner[u] < 0) owner[u] = i;          // the prompt pass writes prompt u through the pages of its first request
+        else ++n_dst[u];
+        e->cb_used[s2] = 1;
+        cb_fill_slot(reqs[i], hs[i], hb[i], seen_rows[i], e->seen_words);
+        map[i] = s2; pos[i] = lens[u] - 1; slots_out[i] = s2;
+        desc[5 * (size_t)mb + i] = u;            // logits row of the prompt (u <= i: shared_check_group)
+    }
+    for (int u = 0, d0 = 0; u < U; ++u) {
+        const int o = owner[u];
+        for (int k = 0; k < (lens[u] + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS; ++k) pf[(size_t)u * mp + k] = rows[(size_t)o * mp + k];
+        desc[4 * u] = slots[o]; desc[4 * u + 1] = lens[u]; desc[4 * u + 2] = d0; desc[4 * u + 3] = n_dst[u];
+        for (int i = 0; i < n; ++i) if (group[i] == u && i != o) desc[4 * (size_t)mb + d0++] = slots[i];
+    }
+    bool nlive_added = false;
+    const int rc = [&]() -> int {
+    for (int i = 0; i < n; ++i) {
+        const int s2 = slots[i];
+        HIPCHECK(hipMemcpyAsync(e->block_table + (size_t)s2 * mp, rows.data() + (size_t)i * mp, mp * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(e->cb_slots + s2, &hs[i], sizeof(CbSlot), hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(e->positions + s2, &pos[i], sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (reqs[i].semantics == 1) {
+            HIPCHECK(hipMemcpyAsync(e->seen + (size_t)s2 * e->seen_words, seen_rows[i].data(), e->seen_words * sizeof(uint32_t),
+                                    hipMemcpyHostToDevice, st));
+            HIPCHECK(hipMemsetAsync(e->cb_counts + (size_t)s2 * e->Vpad, 0, (size_t)e->Vpad * sizeof(uint16_t), st));
+            if (hs[i].n_bias) HIPCHECK(hipMemcpyAsync(e->cb_bias + s2, &hb[i], sizeof(CbBias), hipMemcpyHostToDevice, st));
+        } else if (any_pen) {
+            HIPCHECK(hipMemsetAsync(e->seen + (size_t)s2 * e->seen_words, 0, e->seen_words * sizeof(uint32_t), st));
+        }
+    }
+    HIPCHECK(hipMemcpyAsync(e->cb_table_pf, pf.data(), pf.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(e->cb_map, map.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(e->fork_desc, desc.data(), desc.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    add_i32(e->cb_nlive, n, 1, st);
+    nlive_added = true;
+    // ONE prompt pass over the U prompts (their pages through cb_table_pf), then the fork launch: tail pages to the other slots of each prompt,
+    // logits row i <- row group[i]; the live slots keep decoding afterwards
+    SVCHECK(prefill_forward_ragged(e, (const bf16_t*)dev_embeds, U, lens, st, e->cb_table_pf));
+    ForkArgs f;
+    fork_args(e, U, n, f);
+    launch_fork_prompt(f, st);
+    CbStepArgs a;
+    cb_step_args(e, a, e->cb_map);
+    launch_cb_step(a, n, st);                              // first token of every new request, from its prompt's logits
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));                    // the staging vectors above are host temporaries
+    return 0;
+    }();
+    if (rc) {
+        const std::string why = g_err;                      // keep the first error's text
+        (void)hipStreamSynchronize(st);
+        (void)hipGetLastError();
+        std::vector<int32_t> trash(mp, e->trash_page);
+        for (int i = n - 1; i >= 0; --i) {
+            const int s2 = slots[i];
+            e->cb_pages[s2].clear();
+            e->cb_used[s2] = 0;
+            slots_out[i] = -1;
+            (void)hipMemsetAsync(e->cb_slots + s2, 0, sizeof(CbSlot), st);
+            (void)hipMemcpyAsync(e->block_table + (size_t)s2 * mp, trash.data(), trash.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
+        }
+        for (size_t k = taken.size(); k-- > 0;) {           // pages go back in reverse order, no holder left: the free list is as it was
+            e->page_refs[taken[k]] = 0;
+            e->free_pages.push_back(taken[k]);
+        }
+        if (nlive_added) add_i32(e->cb_nlive, -n, 1, st);
+        (void)hipStreamSynchronize(st);
+        (void)hipGetLastError();
+        g_err = why;
+        return rc;
+    }
+    return 0;
+}
+
+extern "C" int sv_cb_admit_shared(sv_engine* e, const void* dev_embeds_packed, int32_t n_prompts, const int32_t* host_lens, int32_t n,
+                                  const int32_t* host_group, const sv_cb_request* reqs, int32_t* slots_out, sv_stream stream) {
+    // (the checks that need no engine come first: they are the same on a machine without a GPU)
+    if (!dev_embeds_packed || !host_lens || !host_group || !reqs || !slots_out) return fail(SV_EINVAL, "sv_cb_admit_shared: null argument");
+    SVCHECK(shared_check_group("sv_cb_admit_shared", host_lens, n_prompts, host_group, n));
+    SVCHECK(check_ready(e));
+    const sv_config& c = e->cfg;
+    if (n > c.max_batch) return fail(SV_EINVAL, "sv_cb_admit_shared: %d requests exceed max_batch %d", n, c.max_batch);
+    for (int i = 0; i < n; ++i) {
+        const sv_cb_request& r = reqs[i];
+        const int len = host_lens[host_group[i]];
+        if (r.max_new_tokens < 1 || len > c.max_seq_len || len + r.max_new_tokens > c.max_seq_len)
+            return fail(SV_EINVAL, "sv_cb_admit_shared: request %d: prompt %d + max_new_tokens %d out of range (max_seq_len %d)", i, len, r.max_new_tokens,
+                        c.max_seq_len);
+        SVCHECK(cb_check_request(r, c.vocab, i, "sv_cb_admit_shared"));
+    }
+    return cb_admit_shared_impl(e, dev_embeds_packed, n_prompts, host_lens, n, host_group, reqs, slots_out, stream);
+}
+
 extern "C" int sv_cb_step(sv_engine* e, int32_t n_steps, int32_t* n_live_out, sv_stream stream) {
     SVCHECK(check_ready(e));
     if (n_steps < 1 || !n_live_out) return fail(SV_EINVAL, "sv_cb_step: bad argument");
@@ -349,7 +528,11 @@ static int cb_release_locked(sv_engine* e, int slot, hipStream_t st) {
     HIPCHECK(hipMemsetAsync(e->positions + slot, 0, sizeof(int32_t), st));
     HIPCHECK(hipMemsetAsync(e->cur_tok + slot, 0, sizeof(int32_t), st));
     fill_i32(e->block_table + (size_t)slot * e->pages_per_seq, e->trash_page, e->pages_per_seq, st);
-    for (int pg : e->cb_pages[slot]) e->free_pages.push_back(pg);
+    for (int pg : e->cb_pages[slot]) {
+        // a shared prompt page (sv_cb_admit_shared) goes back when its last holder lets go; a private page at once
+        if (e->page_refs[pg] > 0 && --e->page_refs[pg] > 0) continue;
+        e->free_pages.push_back(pg);
+    }
     e->cb_pages[slot].clear();
     e->cb_used[slot] = 0;
     HIPCHECK(hipGetLastError());
@@ -372,6 +555,7 @@ extern "C" int sv_cb_reset(sv_engine* e) {
     for (int s2 = 0; s2 < e->cfg.max_batch; ++s2)
         if (e->cb_used[s2]) SVCHECK(cb_release_locked(e, s2, e->gen_stream));
     HIPCHECK(hipStreamSynchronize(e->gen_stream));
+    std::fill(e->page_refs.begin(), e->page_refs.end(), 0);
     e->cb_active = false;
     return 0;
 }

@@ -331,6 +331,7 @@ extern "C" int sv_destroy(sv_engine* e) {
     if (e->score_chunk_ws) (void)hipFree(e->score_chunk_ws);
     if (e->h_flags) (void)hipHostFree(e->h_flags);
     if (e->h_table) (void)hipHostFree(e->h_table);
+    if (e->h_fork) (void)hipHostFree(e->h_fork);
     if (e->h_rag) (void)hipHostFree(e->h_rag);
     if (e->d_rag) (void)hipFree(e->d_rag);
     if (e->rag_row_pos) (void)hipFree(e->rag_row_pos);

@@ -250,15 +250,16 @@ int sveng::report_bad_logits(sv_engine* e, hipStream_t st, const char* who, int 
     }
 }
 
+// G: samples per prompt (1: sv_generate / sv_generate_ragged; > 1: sv_generate_shared -- one prompt pass over the B prompts, B * G decode rows)
 static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const int32_t* lens, const sv_sampling* sp,
-                            const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream);
+                            const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream, int G);
 static int generate_retry(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const int32_t* lens, const sv_sampling* sp,
-                          const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
+                          const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream, int G = 1) {
     if (e) { e->last_giveup = 0; e->stream_skip = 0; }
-    int rc = generate_attempt(e, dev_embeds, B, S0, lens, sp, outs, dev_out_tokens, n_generated, stream);
+    int rc = generate_attempt(e, dev_embeds, B, S0, lens, sp, outs, dev_out_tokens, n_generated, stream, G);
     if (rc != 0 && e && e->cfg.exclusive_device == 2 && e->last_giveup && e->fused_off) {
         e->last_giveup = 0;
-        rc = generate_attempt(e, dev_embeds, B, S0, lens, sp, outs, dev_out_tokens, n_generated, stream);
+        rc = generate_attempt(e, dev_embeds, B, S0, lens, sp, outs, dev_out_tokens, n_generated, stream, G);
     }
     if (e) e->stream_skip = 0;
     return rc;
@@ -287,6 +288,28 @@ extern "C" int sv_generate_ragged(sv_engine* e, const void* dev_embeds_packed, i
     }
     return generate_retry(e, dev_embeds_packed, B, longest, host_lens, sp, outs, dev_out_tokens, n_generated, stream);
 }
+// n_samples continuations of every prompt from ONE prompt pass.  host_lens == NULL: B prompts of S0 rows each; otherwise the ragged form (S0 unused).
+// Row b * n_samples + j of the outputs is sample j of prompt b: the rows, tokens and random draws of sv_generate / sv_generate_ragged over the
+// prompts repeated n_samples times each.
+extern "C" int sv_generate_shared(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, int32_t S0, int32_t n_samples,
+                                  const sv_sampling* sp, const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated,
+                                  sv_stream stream) {
+    // (the checks that need no engine come first: they are the same on a machine without a GPU)
+    if (!dev_embeds_packed || !sp || !dev_out_tokens || !n_generated) return fail(SV_EINVAL, "sv_generate_shared: null argument");
+    if (B < 1) return fail(SV_EINVAL, "sv_generate_shared: bad B=%d", B);
+    if (n_samples < 1) return fail(SV_EINVAL, "sv_generate_shared: bad n_samples=%d (must be >= 1)", n_samples);
+    int longest = S0;
+    if (host_lens) {
+        longest = 0;
+        for (int b = 0; b < B; ++b) {
+            if (host_lens[b] < 1) return fail(SV_EINVAL, "sv_generate_shared: length %d of sequence %d (must be >= 1)", host_lens[b], b);
+            longest = host_lens[b] > longest ? host_lens[b] : longest;
+        }
+    } else if (S0 < 1) {
+        return fail(SV_EINVAL, "sv_generate_shared: bad S0=%d", S0);
+    }
+    return generate_retry(e, dev_embeds_packed, B, longest, host_lens, sp, outs, dev_out_tokens, n_generated, stream, n_samples);
+}
 extern "C" int sv_generate(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const sv_sampling* sp,
                            int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
     return sv_generate_ex(e, dev_embeds, B, S0, sp, nullptr, dev_out_tokens, n_generated, stream);
@@ -314,13 +337,84 @@ static int setup_capture(sv_engine* e, const sv_sampling* sp, const sv_generate_
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Shared prompt pass (sv_generate_shared): B prompts, G samples each, ONE prompt pass over the B prompts.
+// ------------------------------------------------------------------------------------------------
+static int ensure_fork_buffers(sv_engine* e) {
+    const size_t mb = (size_t)e->cfg.max_batch;
+    if (!e->h_fork) HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&e->h_fork), (mb * e->pages_per_seq + 6 * mb) * sizeof(int32_t), hipHostMallocDefault));
+    return e->fork_desc ? 0 : dalloc(e, &e->fork_desc, 6 * mb);      // (the group admit of a continuous batch may have allocated the device side)
+}
+void sveng::fork_args(sv_engine* e, int n_prompts, int n_rows, ForkArgs& f) {
+    const int mb = e->cfg.max_batch;
+    f.prompts = e->fork_desc; f.dst_rows = e->fork_desc + 4 * mb; f.lsrc = e->fork_desc + 5 * mb; f.n_prompts = n_prompts; f.n_rows = n_rows;
+    f.block_table = e->block_table; f.max_pages = e->pages_per_seq;
+    f.kv_pool = e->kv_pool; f.layer_stride = e->layer_stride; f.kv_head_stride = e->kv_head_stride; f.n_layer = e->cfg.n_layer; f.n_kv = e->nkv;
+    f.page_bytes = e->page_bytes; f.logits = e->logits; f.ld = e->Vpad;
+}
+// The page plan (static, like the beam path's): the G rows of prompt b share block-table entries 0 .. len_b / 64 - 1 -- the prompt's FULL pages,
+// written by the prompt pass through the table of row b * G and by nobody afterwards: a decode step writes K / V at its row's own position only,
+// which lies in a page from len_b / 64 on, and the decode attention clears the stale rows of a key group in registers (attention.hip, process()),
+// never in memory.  From entry len_b / 64 (the partially filled tail page, if any) up to the end of the budget every row owns its pages; the fork
+// launch copies the tail page from row b * G to the other rows and hands every row its prompt's logits.  No host round trip in between.
+static int shared_prefill_fork(sv_engine* e, const void* dev_embeds, int B, int G, int S0, const int32_t* lens, int max_new, hipStream_t st) {
+    const sv_config& c = e->cfg;
+    const int R = B * G, mp = e->pages_per_seq, mb = c.max_batch;
+    if (!dev_embeds) return fail(SV_EINVAL, "sv_generate_shared: null inputs_embeds");
+    if (S0 < 1 || S0 > c.max_seq_len) return fail(SV_EINVAL, "sv_generate_shared: S0=%d out of range (max_seq_len %d)", S0, c.max_seq_len);
+    SVCHECK(ensure_fork_buffers(e));
+    e->free_pages.clear();
+    for (int p = e->num_pages - 1; p >= 0; --p) e->free_pages.push_back(p);
+    if (e->table_pending) { HIPCHECK(hipEventSynchronize(e->table_ev)); e->table_pending = false; }      // (guards both pinned images)
+    int32_t* table = e->h_table;                       // decode rows
+    int32_t* pf = e->h_fork;                           // prompt pass: row b = the pages of decode row b * G
+    int32_t* desc = e->h_fork + (size_t)mb * mp;
+    memset(table, 0, (size_t)mb * mp * sizeof(int32_t));
+    memset(pf, 0, ((size_t)mb * mp + 6 * (size_t)mb) * sizeof(int32_t));
+    for (int b = 0; b < B; ++b) {
+        const int len = lens ? lens[b] : S0, sh = len / SV_PAGE_TOKENS;
+        const int need = (len + max_new + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS;
+        if (need > mp) return fail(SV_EINVAL, "sequence length %d exceeds max_seq_len %d", len + max_new, c.max_seq_len);
+        const int32_t* first = table + (size_t)b * G * mp;
+        for (int j = 0; j < G; ++j) {
+            int32_t* row = table + (size_t)(b * G + j) * mp;
+            for (int i = 0; i < need; ++i) {
+                if (j > 0 && i < sh) { row[i] = first[i]; continue; }
+                row[i] = e->free_pages.back();
+                e->free_pages.pop_back();
+            }
+            desc[5 * mb + b * G + j] = b;              // logits row of the prompt
+            if (j > 0) desc[4 * mb + b * (G - 1) + j - 1] = b * G + j;
+        }
+        for (int i = 0; i < (len + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS; ++i) pf[(size_t)b * mp + i] = first[i];
+        desc[4 * b] = b * G; desc[4 * b + 1] = len; desc[4 * b + 2] = b * (G - 1); desc[4 * b + 3] = G - 1;
+    }
+    HIPCHECK(hipMemcpyAsync(e->block_table, table, (size_t)mb * mp * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(e->cb_table_pf, pf, (size_t)mb * mp * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(e->fork_desc, desc, 6 * (size_t)mb * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipEventRecord(e->table_ev, st));
+    e->table_pending = true;
+    if (lens) SVCHECK(prefill_forward_ragged(e, (const bf16_t*)dev_embeds, B, lens, st, e->cb_table_pf));
+    else SVCHECK(prefill_forward(e, (const bf16_t*)dev_embeds, B, S0, st, 0, nullptr, e->cb_table_pf));
+    ForkArgs f;
+    fork_args(e, B, R, f);
+    launch_fork_prompt(f, st);
+    e->cached_B = R;
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
 // lens != nullptr: the ragged form -- S0 is the longest prompt (the budget counts from it), sequence b has lens[b] rows
-static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const int32_t* lens, const sv_sampling* sp,
-                            const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
+static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t Bp, int32_t S0, const int32_t* lens, const sv_sampling* sp,
+                            const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream, int G) {
     SVCHECK(check_ready(e));
+    const bool shared = G > 1;
+    if (shared && (Bp < 1 || (long long)Bp * G > e->cfg.max_batch))
+        return fail(SV_EINVAL, "sv_generate_shared: B %d x n_samples %d exceeds engine max_batch %d", Bp, G, e->cfg.max_batch);
+    const int B = Bp * G;        // decode rows: row b * G + j is sample j of prompt b (the row order of repeat_interleave)
     if (lens) {
-        if (B > e->cfg.max_batch) return fail(SV_EINVAL, "sv_generate_ragged: bad B=%d (max_batch %d)", B, e->cfg.max_batch);
-        SVCHECK(ragged_check_lens(e, lens, B, "sv_generate_ragged", nullptr, nullptr));
+        if (Bp > e->cfg.max_batch) return fail(SV_EINVAL, "sv_generate_ragged: bad B=%d (max_batch %d)", Bp, e->cfg.max_batch);
+        SVCHECK(ragged_check_lens(e, lens, Bp, shared ? "sv_generate_shared" : "sv_generate_ragged", nullptr, nullptr));
     }
     if (!sp || !dev_out_tokens || !n_generated) return fail(SV_EINVAL, "sv_generate: null argument");
     const int max_new = sp->max_length - S0;     // HF: with inputs_embeds, max_length includes the prompt
@@ -329,6 +423,8 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t B, int
     if (sp->n_stop < 0 || sp->n_stop > 16) return fail(SV_EINVAL, "stop sequence length %d unsupported (0..16)", sp->n_stop);
     if (sp->do_sample && !(sp->temperature > 0.f && sp->top_p > 0.f)) return fail(SV_EINVAL, "temperature and top_p must be > 0");
     if (sp->num_beams < 0) return fail(SV_EINVAL, "num_beams must be >= 1");
+    if (sp->num_beams > 1 && shared)
+        return fail(SV_ENOTSUP, "sv_generate_shared: n_samples %d with num_beams %d is not built (several returned sequences under beam search)", G, sp->num_beams);
     std::lock_guard<std::mutex> lk(e->mu);
     HIPCHECK(hipSetDevice(e->cfg.device));
     // order the engine stream after everything already queued on the caller's stream
@@ -347,7 +443,9 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t B, int
 
     auto t0 = std::chrono::steady_clock::now();
     HIPCHECK(hipMemsetAsync(e->d_bad, 0, sizeof(int32_t), st));         // a flag left by an earlier, failed call is not this call's
-    if (lens) {                              // pages per sequence for lens[b] + max_new, one ragged prompt pass
+    if (shared) {                            // one prompt pass over the Bp prompts, then the fork launch: B rows from here on
+        SVCHECK(shared_prefill_fork(e, dev_embeds, Bp, G, S0, lens, max_new, st));
+    } else if (lens) {                       // pages per sequence for lens[b] + max_new, one ragged prompt pass
         SVCHECK(assign_pages_ragged(e, B, lens, max_new, st));
         SVCHECK(prefill_forward_ragged(e, (const bf16_t*)dev_embeds, B, lens, st));
         e->cached_B = B;
@@ -370,7 +468,7 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t B, int
     }
     // generation state, one launch: positions = S0 - 1 (finish_step adds 1), unfinished = 1, {step, done, n_emitted} = 0, the folded selection's key slots = 0
     gen_state_init(e->positions, S0 - 1, e->unfinished, B, e->d_step, e->amax, fused_sel ? 64 * SV_AMAX_STRIDE : 0, st);
-    if (lens) ragged_positions(e, B, 1, -1, st);         // every row continues at its own length
+    if (lens) ragged_positions(e, Bp, G, -1, st);        // every row continues at its own prompt's length
     if (sp->repetition_penalty > 0.f && sp->repetition_penalty != 1.0f)
         HIPCHECK(hipMemsetAsync(e->seen, 0, (size_t)((B + 31) / 32) * 32 * e->seen_words * sizeof(uint32_t), st));
     if (sp->n_stop > 0) {

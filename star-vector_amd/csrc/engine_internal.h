@@ -172,6 +172,12 @@ struct sv_engine {
     int pages_per_seq = 0, num_pages = 0, page_bytes = 0;
     int32_t* block_table = nullptr;
     std::vector<int> free_pages;
+    // shared prompt pass (sv_generate_shared / sv_cb_admit_shared): pinned image of the prompt-pass table + the fork launch's descriptors, their
+    // device copy ([6 * max_batch]: prompts | other rows | logits source rows), both allocated on first use; holders of every SHARED page of a
+    // continuous batch (0: the page is private to one slot, or free)
+    int32_t* h_fork = nullptr;
+    int32_t* fork_desc = nullptr;
+    std::vector<int> page_refs;
     // beam search (num_beams > 1): device scorer
     BeamScorer beam;
     bf16_t* score_ws = nullptr;      // scoring forward: kept hidden rows, their ln_f, bf16 logits [rows][Vpad]
@@ -263,6 +269,9 @@ int check_ready(sv_engine* e);
 // logit bias, its repetition bitmap row (seen_words words: the prompt ids in vLLM mode, cleared otherwise)
 int cb_check_request(const sv_cb_request& r, int V, int i, const char* who);
 void cb_fill_slot(const sv_cb_request& r, CbSlot& h, CbBias& bias, std::vector<uint32_t>& seen_row, int seen_words);
+// group admit (sv_cb_admit_shared): validation of (lens, group) and the page plan -- host arithmetic, stated by sv_debug_shared_plan for the CPU tests
+int shared_check_group(const char* who, const int32_t* lens, int n_prompts, const int32_t* group, int n);
+long long shared_page_plan(const int32_t* lens, int n_prompts, const int32_t* group, const int32_t* budgets, int n, int32_t* shared, int32_t* private_);
 int cb_guard(sv_engine* e, const char* who);
 int prefill_locked(sv_engine* e, const void* dev_embeds, int B, int S0, int total_len, hipStream_t st, bool set_positions = true);
 // The ragged prompt pass: B sequences of lengths lens[0..B) (host), embeddings packed back to back.  What the dispatch decides for a set of lengths is
@@ -278,6 +287,7 @@ int prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, const int3
 // positions[i] = lens[i / rep] + delta for i < B * rep, from the descriptors the last prefill_forward_ragged uploaded
 void ragged_positions(sv_engine* e, int B, int rep, int delta, hipStream_t st);
 // engine_generate.hip
+void fork_args(sv_engine* e, int n_prompts, int n_rows, ForkArgs& f);      // the fork launch over e->fork_desc, the engine's block table, pool and logits
 int check_finite_logits(sv_engine* e, hipStream_t st, const char* who);
 int report_bad_logits(sv_engine* e, hipStream_t st, const char* who, int what);      // what = the d_bad code already read (0: fine)
 }  // namespace sveng

@@ -271,6 +271,33 @@ extern "C" int sv_debug_prompt_passes(sv_engine* e, int64_t* out) {
     return 0;
 }
 
+extern "C" int sv_debug_shared_plan(const int32_t* lens, int32_t n_prompts, const int32_t* group, const int32_t* budgets, int32_t n,
+                                    int32_t* shared_out, int32_t* private_out, int64_t* total_out) {
+    if (!budgets || !shared_out || !private_out || !total_out) return fail(SV_EINVAL, "sv_debug_shared_plan: null argument");
+    SVCHECK(shared_check_group("sv_debug_shared_plan", lens, n_prompts, group, n));
+    for (int i = 0; i < n; ++i)
+        if (budgets[i] < 1) return fail(SV_EINVAL, "sv_debug_shared_plan: budgets[%d] = %d (must be >= 1)", i, budgets[i]);
+    *total_out = shared_page_plan(lens, n_prompts, group, budgets, n, shared_out, private_out);
+    return 0;
+}
+extern "C" int sv_debug_block_table(sv_engine* e, int32_t row, int32_t* host_out, int32_t capacity) {
+    if (!e || !host_out) return fail(SV_EINVAL, "sv_debug_block_table: null argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (row < 0 || row >= e->cfg.max_batch) return fail(SV_EINVAL, "sv_debug_block_table: row %d outside [0, max_batch %d)", row, e->cfg.max_batch);
+    if (capacity < e->pages_per_seq) return fail(SV_EINVAL, "sv_debug_block_table: capacity %d < %d pages per sequence", capacity, e->pages_per_seq);
+    HIPCHECK(hipSetDevice(e->cfg.device));
+    HIPCHECK(hipMemcpyAsync(host_out, e->block_table + (size_t)row * e->pages_per_seq, e->pages_per_seq * sizeof(int32_t), hipMemcpyDeviceToHost, e->gen_stream));
+    HIPCHECK(hipStreamSynchronize(e->gen_stream));
+    return e->pages_per_seq;
+}
+extern "C" int sv_debug_free_pages(sv_engine* e, int32_t* free_out, int32_t* total_out) {
+    if (!e || !free_out || !total_out) return fail(SV_EINVAL, "sv_debug_free_pages: null argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    *free_out = (int32_t)e->free_pages.size();
+    *total_out = e->num_pages;
+    return 0;
+}
+
 extern "C" int sv_debug_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t act, int32_t* out5) {
     if (!out5 || M < 1 || N < 1 || K < 1) return fail(SV_EINVAL, "sv_debug_gemm_plan: bad argument");
     const GemmPlan pl = gemm_plan(M, N, K, act, 1);

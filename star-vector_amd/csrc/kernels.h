@@ -453,6 +453,21 @@ struct CbStepArgs {
 };
 void launch_cb_step(const CbStepArgs& a, int nblocks, hipStream_t st);
 
+// ---- shared prompt pass (fork.hip): one prompt, several samples.  Between the prompt pass and the first selection, on the engine stream:
+//   (a) the partially filled tail page of prompt u (len % 64 != 0) fans out from the row that took the prompt pass to the other rows of the prompt,
+//       for every layer and KV head (the full prompt pages are shared through the block table and never copied);
+//   (b) logits row i becomes logits row lsrc[i] (in place): every sample selects its first token from its prompt's prefill logits.
+// Descriptors (device int32): prompts [n_prompts][4] = {row holding the prompt, prompt length, first entry in dst_rows, entries}; dst_rows = the
+// other rows of each prompt; lsrc [n_rows] with lsrc[i] <= i (the in-place fan-out walks the rows downwards: a row is read before any row
+// above it is written).  Rows index block_table ([rows][max_pages]): decode rows of sv_generate_shared, slots of sv_cb_admit_shared.
+struct ForkArgs {
+    const int32_t* prompts; const int32_t* dst_rows; int n_prompts;
+    const int32_t* block_table; int max_pages;
+    char* kv_pool; size_t layer_stride, kv_head_stride; int n_layer, n_kv; int page_bytes;
+    float* logits; int ld; const int32_t* lsrc; int n_rows;
+};
+void launch_fork_prompt(const ForkArgs& a, hipStream_t st);
+
 // ---- per-token log-probabilities of the scoring forward (score.hip): one block per row of bf16 logits, fp32 arithmetic over
 // x_i = float(logit_i) * inv_t.  logits rows start 16-byte aligned and ld % 8 == 0.  Every output may be nullptr.
 struct LogprobArgs {

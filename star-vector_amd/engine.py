@@ -271,6 +271,31 @@ class HipEngine:
         x, _arr, lens = self._packed(embeds, lengths)
         return self.generate(x, max_length, lengths=lens, **kw)
 
+    def generate_shared(self, embeds, max_length: int, n_samples: int, lengths=None, **kw):
+        """``n_samples`` continuations of every prompt from ONE prompt pass over the un-repeated prompts (sv_generate_shared): ``embeds`` is
+        [B, S0, D], or a list of [S_i, D] prompts / a packed tensor with ``lengths`` (the ragged form, budget from the longest prompt).  Returns
+        B * n_samples rows, row b * n_samples + j = sample j of prompt b -- bit for bit what ``generate`` / ``generate_ragged`` return for
+        the prompts repeated with ``repeat_interleave(n_samples, dim=0)``; the rows of a prompt share its full KV pages.  Same keywords and
+        return value as ``generate``."""
+        if lengths is not None or isinstance(embeds, (list, tuple)):
+            x, _arr, lens = self._packed(embeds, lengths)
+            return self.generate(x, max_length, lengths=lens, n_samples=n_samples, **kw)
+        return self.generate(embeds, max_length, n_samples=n_samples, **kw)
+
+    def block_table_row(self, row: int) -> List[int]:
+        """The block-table row of a decode row / slot as the device holds it (sv_debug_block_table)."""
+        buf = (C.c_int32 * 4096)()
+        n = self.lib.sv_debug_block_table(self._h, int(row), buf, 4096)
+        if n < 0:
+            check(n, "sv_debug_block_table")
+        return list(buf)[:n]
+
+    def free_pages(self) -> Tuple[int, int]:
+        """(free KV pages, pages of the pool) of the host allocator after the last generate call or admit / release (sv_debug_free_pages)."""
+        f, t = C.c_int32(0), C.c_int32(0)
+        check(self.lib.sv_debug_free_pages(self._h, C.byref(f), C.byref(t)), "sv_debug_free_pages")
+        return int(f.value), int(t.value)
+
     def prompt_passes(self) -> int:
         """Prompt passes (rectangular and ragged, admits included) this engine has run so far (sv_debug_prompt_passes)."""
         n = C.c_int64(0)
@@ -328,7 +353,7 @@ class HipEngine:
                  repetition_penalty: float = 1.0, num_beams: int = 1, length_penalty: float = 1.0,
                  early_stopping=False, top_k: int = 0, on_tokens=None, min_new_tokens: int = 0,
                  scores_out: Optional[torch.Tensor] = None, logits_out: Optional[torch.Tensor] = None,
-                 return_outputs: bool = False, lengths: Optional[Sequence[int]] = None):
+                 return_outputs: bool = False, lengths: Optional[Sequence[int]] = None, n_samples: int = 1):
         """HF ``generate`` semantics for inputs_embeds: returns ONLY the new tokens, int64 [B, N].
         ``lengths``: the ragged form -- inputs_embeds is packed [sum(lengths), D], one prompt pass for all of them, ``max_length`` counts from
         the longest prompt (see ``generate_ragged``).
@@ -337,6 +362,8 @@ class HipEngine:
         ``on_tokens(tokens [B, n] int64 cpu, first_col)``: streaming callback, called every ``sync_every`` steps with the
         columns that became final and once more at the end.  ``min_new_tokens``: HF's MinLengthLogitsProcessor after the
         prompt length has been subtracted from ``min_length`` (EOS cannot be chosen before that many new tokens).
+        ``n_samples`` > 1: that many continuations of every prompt from ONE prompt pass (sv_generate_shared, see ``generate_shared``); the
+        outputs have B * n_samples rows, row b * n_samples + j = sample j of prompt b.
         Per-step outputs (sv_generate_ex): ``scores_out`` / ``logits_out`` are fp32 device tensors [max_new, rows, ld] (rows = B, or
         B * num_beams under beam search; ld >= vocab) that receive HF's processed scores / raw logits of every generated column.
         ``return_outputs=True`` returns a dict {"sequences", "n_generated"} plus, under beam search, "sequences_scores" [B] and
@@ -350,6 +377,13 @@ class HipEngine:
             B, S0, D = x.shape
         if D != self.cfg.hidden:
             raise ValueError("inputs_embeds hidden size mismatch")
+        G = int(n_samples)
+        if G < 1:
+            raise ValueError(f"n_samples must be >= 1, got {n_samples}")
+        if G > 1 and int(num_beams) > 1:
+            raise NotImplementedError("n_samples > 1 under beam search (num_beams > 1) is not built")
+        if G > 1:
+            n_prompts, B = B, B * G                     # B: the decode rows from here on
         max_new = max_length - S0
         if max_new <= 0:
             raise ValueError(f"max_length ({max_length}) must exceed the prompt length ({S0})")
@@ -367,7 +401,10 @@ class HipEngine:
         out = torch.empty(B, max_new, dtype=torch.int64, device=x.device)
         n = C.c_int32(0)
         if scores_out is None and logits_out is None and not return_outputs:
-            if lens_arr is not None:
+            if G > 1:
+                check(self.lib.sv_generate_shared(self._h, _ptr(x), n_prompts, lens_arr, S0, G, C.byref(sp), None, _ptr(out), C.byref(n), _stream()),
+                      "sv_generate_shared")
+            elif lens_arr is not None:
                 check(self.lib.sv_generate_ragged(self._h, _ptr(x), B, lens_arr, C.byref(sp), None, _ptr(out), C.byref(n), _stream()),
                       "sv_generate_ragged")
             else:
@@ -397,7 +434,10 @@ class HipEngine:
         if beam:
             outs.host_sequences_scores = C.cast(seq_scores, C.POINTER(C.c_float))
             outs.host_beam_indices = C.cast(beam_idx, C.POINTER(C.c_int64))
-        if lens_arr is not None:
+        if G > 1:
+            check(self.lib.sv_generate_shared(self._h, _ptr(x), n_prompts, lens_arr, S0, G, C.byref(sp), C.byref(outs), _ptr(out), C.byref(n),
+                                              _stream()), "sv_generate_shared")
+        elif lens_arr is not None:
             check(self.lib.sv_generate_ragged(self._h, _ptr(x), B, lens_arr, C.byref(sp), C.byref(outs), _ptr(out), C.byref(n), _stream()),
                   "sv_generate_ragged")
         else:
@@ -440,6 +480,33 @@ class HipEngine:
         arr, keep = cb_requests(requests)
         slots = (C.c_int32 * n)()
         check(self.lib.sv_cb_admit(self._h, _ptr(x), n, S0, arr, slots, _stream()), "sv_cb_admit")
+        del keep
+        return list(slots)
+
+    def cb_admit_shared(self, embeds, lengths, group: Sequence[int], requests: Sequence[dict]) -> List[int]:
+        """Group admit (sv_cb_admit_shared): ``embeds`` a list of [S_u, D] prompts (``lengths`` None) or a packed tensor with ``lengths``;
+        request i samples prompt ``group[i]`` with its own parameters (the dicts of ``cb_admit``).  ONE prompt pass over the prompts; the
+        requests of a prompt share its full KV pages.  Prompts may come in any order here: they are renumbered in the order their first
+        request appears, as the C entry point wants them.  Returns the slot ids; raises StarVectorBusy when slots or pages are short."""
+        group = [int(g) for g in group]
+        if len(group) != len(requests) or not group:
+            raise ValueError("group / requests mismatch")
+        if lengths is None:
+            seqs = [t.reshape(-1, t.shape[-1]) for t in embeds]
+        else:
+            seqs = list(torch.split(embeds, [int(v) for v in lengths], dim=0))
+        if min(group) < 0 or max(group) >= len(seqs):
+            raise ValueError(f"group entries must lie in [0, {len(seqs)})")
+        order = list(dict.fromkeys(group))               # prompts in the order of their first request
+        if len(order) != len(seqs):
+            raise ValueError("every prompt needs at least one request")
+        rank = {u: k for k, u in enumerate(order)}
+        x, lens_arr, lens = self._packed([seqs[u] for u in order])
+        n = len(group)
+        arr, keep = cb_requests(requests)
+        slots = (C.c_int32 * n)()
+        check(self.lib.sv_cb_admit_shared(self._h, _ptr(x), len(lens), lens_arr, n, (C.c_int32 * n)(*[rank[g] for g in group]), arr, slots,
+                                          _stream()), "sv_cb_admit_shared")
         del keep
         return list(slots)
 
@@ -770,6 +837,16 @@ def ragged_plan(lengths: Sequence[int], N: int, K: int, act: str = "none", q_til
     check(_lib.load().sv_debug_ragged_plan((C.c_int32 * max(B, 1))(*lens), B, int(N), int(K), _lib.ACT[act], int(q_tile), rows, last, cap, out),
           "sv_debug_ragged_plan")
     return {"rows": list(rows)[: out[0]], "last": list(last)[: out[1]], "attn_blocks": out[2], "kv_blocks": out[3]}
+
+
+def shared_plan(lengths: Sequence[int], group: Sequence[int], budgets: Sequence[int]) -> Dict[str, object]:
+    """The page plan of a shared prompt pass (sv_debug_shared_plan; host arithmetic, no GPU): per request the shared and the private
+    block-table entries, and the pages the admit takes in all."""
+    U, n = len(lengths), len(group)
+    sh, pv, tot = (C.c_int32 * max(n, 1))(), (C.c_int32 * max(n, 1))(), C.c_int64(0)
+    check(_lib.load().sv_debug_shared_plan((C.c_int32 * max(U, 1))(*[int(v) for v in lengths]), U, (C.c_int32 * max(n, 1))(*[int(v) for v in group]),
+                                           (C.c_int32 * max(n, 1))(*[int(v) for v in budgets]), n, sh, pv, C.byref(tot)), "sv_debug_shared_plan")
+    return {"shared": list(sh)[:n], "private": list(pv)[:n], "total": int(tot.value)}
 
 
 def set_skinny_form(form: int) -> None:

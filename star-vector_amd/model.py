@@ -19,6 +19,7 @@ from __future__ import annotations
 import json
 import os
 import contextlib
+import functools
 import threading
 from typing import Dict, List, Optional, Sequence
 
@@ -469,7 +470,10 @@ class HipCausalLM(_EngineModule):
 
     def _generate_padded(self, inputs_embeds, attention_mask, kw):
         mask = attention_mask.to(torch.bool)
-        B, S, _ = inputs_embeds.shape
+        G = int(kw.get("n_samples") or 1)               # > 1: the shared form -- inputs_embeds holds the un-repeated prompts, row r samples prompt r // G
+        if G > 1:
+            mask = mask.repeat_interleave(G, dim=0)
+        B, S = mask.shape[0], inputs_embeds.shape[1]
         if not bool(mask[:, -1].all()):
             # right padding: only the ragged route takes it (every row runs with its padding removed, wherever the padding sits); the
             # rectangular length-group route continues from the last position and needs a real token there
@@ -484,7 +488,7 @@ class HipCausalLM(_EngineModule):
         pad = int(self.pad_token_id if kw.get("pad_token_id") is None else kw["pad_token_id"])
         stop = self._stop_ids(kw.get("stopping_criteria"))
         eng = self._engine
-        if (int(kw.get("num_beams") or 1) == 1 and hasattr(eng, "cb_admit") and B <= eng.cfg.max_batch
+        if G > 1 or (int(kw.get("num_beams") or 1) == 1 and hasattr(eng, "cb_admit") and B <= eng.cfg.max_batch
                 and (getattr(self, "batcher", None) is None or _in_exclusive_job())):
             return self._generate_padded_slots(inputs_embeds, mask, lengths, budget, pad, stop, kw)
         nb = int(kw.get("num_beams") or 1)
@@ -552,7 +556,7 @@ class HipCausalLM(_EngineModule):
         together -- instead of one full generate call per length group.  HF semantics of the padded batch are restored on
         the host: the reference's row-0 stop ends every row at row 0's step, finished rows are padded."""
         eng = self._engine
-        B, S, _ = inputs_embeds.shape
+        B, S = mask.shape[0], inputs_embeds.shape[1]
         eos = int(self.eos_token_id if kw.get("eos_token_id") is None else kw["eos_token_id"])
         min_new = max(int(kw.get("min_length") or 0) - S, 0)
         seed = int(kw.get("seed") or 0)
@@ -563,7 +567,7 @@ class HipCausalLM(_EngineModule):
         slot_of = [None] * B
         lock = getattr(eng, "call_lock", None) or contextlib.nullcontext()
         with lock:            # from the first cb_reset to the last: another thread's generate must not reset or admit in between
-            outs, fired_len = self._run_slots(eng, inputs_embeds, mask, lengths, base, seed, stop, slot_of)
+            outs, fired_len = self._run_slots(eng, inputs_embeds, mask, lengths, base, seed, stop, slot_of, int(kw.get("n_samples") or 1))
         L = fired_len if fired_len is not None else max(t.shape[0] for t in outs)
         res = torch.full((B, L), pad, dtype=torch.long, device=inputs_embeds.device)
         for b, t in enumerate(outs):
@@ -572,18 +576,26 @@ class HipCausalLM(_EngineModule):
         return res
 
     @staticmethod
-    def _run_slots(eng, inputs_embeds, mask, lengths, base, seed, stop, slot_of):
-        B = inputs_embeds.shape[0]
+    def _run_slots(eng, inputs_embeds, mask, lengths, base, seed, stop, slot_of, n_samples=1):
+        B, G = mask.shape[0], n_samples
         eng.cb_reset()
         try:
-            if hasattr(eng, "prefill_ragged"):
+            if G > 1:
+                # the shared form: one ragged prompt pass over the B / G prompts, row r is a request of prompt r // G with the seed row r
+                # has on the repeated route (sv_cb_admit_shared): same tokens
+                embs = [inputs_embeds[b // G][mask[b]].to(torch.bfloat16).contiguous() for b in range(0, B, G)]
+                reqs = [dict(base, seed=(seed + 0x9E3779B97F4A7C15 * b) & (2 ** 63 - 1), stop_ids=stop if b == 0 else None)
+                        for b in range(B)]
+                for b, s_ in enumerate(eng.cb_admit_shared(embs, None, [b // G for b in range(B)], reqs)):
+                    slot_of[b] = s_
+            elif hasattr(eng, "prefill_ragged"):
                 # one ragged prompt pass for all rows; the per-row seeds are those of the length-group route: same tokens
                 embs = [inputs_embeds[b][mask[b]].to(torch.bfloat16).contiguous() for b in range(B)]
                 reqs = [dict(base, seed=(seed + 0x9E3779B97F4A7C15 * b) & (2 ** 63 - 1), stop_ids=stop if b == 0 else None)
                         for b in range(B)]
                 for b, s_ in enumerate(eng.cb_admit(embs, reqs)):
                     slot_of[b] = s_
-            for n in ([] if hasattr(eng, "prefill_ragged") else sorted(set(lengths))):
+            for n in ([] if G > 1 or hasattr(eng, "prefill_ragged") else sorted(set(lengths))):
                 rows = [b for b in range(B) if lengths[b] == n]
                 emb = torch.stack([inputs_embeds[b][mask[b]] for b in rows], 0).to(torch.bfloat16).contiguous()
                 reqs = [dict(base, seed=(seed + 0x9E3779B97F4A7C15 * b) & (2 ** 63 - 1), stop_ids=stop if b == 0 else None)
@@ -615,7 +627,7 @@ class HipCausalLM(_EngineModule):
                  early_stopping: bool = False, pad_token_id: Optional[int] = None, eos_token_id: Optional[int] = None,
                  num_return_sequences: int = 1, top_k: Optional[int] = 50, streamer=None, seed: Optional[int] = None,
                  return_dict_in_generate: bool = False, output_scores: bool = False, output_logits: bool = False,
-                 **unused):
+                 share_prompt: bool = True, **unused):
         # top_k: the reference never passes it; its pinned transformers==4.49.0 (pyproject.toml:18) defaults
         # GenerationConfig.top_k to 50, so every do_sample call there is top-k 50 followed by top-p.  Same default here.
         if inputs_embeds is None:
@@ -653,8 +665,24 @@ class HipCausalLM(_EngineModule):
             if num_beams > 1:
                 raise NotImplementedError("num_return_sequences > 1 with beam search is not built "
                                           "(the reference sets num_beams=1 on this path)")
-            inputs_embeds = inputs_embeds.repeat_interleave(num_return_sequences, dim=0)
-            attention_mask = None if attention_mask is None else attention_mask.repeat_interleave(num_return_sequences, dim=0)
+        # Several samples of one prompt: where the engine offers the shared call, the un-repeated prompts go down and the engine runs ONE
+        # prompt pass per prompt (sv_generate_shared; a padded batch: sv_cb_admit_shared) -- rows, tokens and random draws are those of the
+        # repeated route, which stays for engines without it and for share_prompt=False (A/B, the equality tests).
+        G = 1
+        if num_return_sequences > 1:
+            eng = self._engine
+            padded = attention_mask is not None and not bool((attention_mask == 1).all())
+            rows = inputs_embeds.shape[0] * num_return_sequences
+            if padded:
+                can = (hasattr(eng, "cb_admit_shared") and rows <= eng.cfg.max_batch and not want
+                       and (getattr(self, "batcher", None) is None or _in_exclusive_job()))
+            else:
+                can = hasattr(eng, "generate_shared")
+            if share_prompt and can:
+                G = num_return_sequences
+            else:
+                inputs_embeds = inputs_embeds.repeat_interleave(num_return_sequences, dim=0)
+                attention_mask = None if attention_mask is None else attention_mask.repeat_interleave(num_return_sequences, dim=0)
         if repetition_penalty is not None and not repetition_penalty > 0:
             raise ValueError("`repetition_penalty` has to be a strictly positive float")   # HF's own check
         if attention_mask is not None and not bool((attention_mask == 1).all()):
@@ -666,7 +694,7 @@ class HipCausalLM(_EngineModule):
                 do_sample=do_sample, top_p=top_p, temperature=temperature, num_beams=num_beams, max_length=max_length,
                 min_length=min_length, repetition_penalty=repetition_penalty, length_penalty=length_penalty,
                 use_cache=use_cache, stopping_criteria=stopping_criteria, early_stopping=early_stopping,
-                pad_token_id=pad_token_id, eos_token_id=eos_token_id, top_k=top_k, seed=seed))
+                pad_token_id=pad_token_id, eos_token_id=eos_token_id, top_k=top_k, seed=seed, n_samples=G))
             return generate_output(num_beams > 1, sequences=seqs) if return_dict_in_generate else seqs
         S0 = inputs_embeds.shape[1]
         # HF (_prepare_generated_length): with inputs_embeds min_length is reduced by the prompt length -- 0 on the im2svg path
@@ -681,13 +709,13 @@ class HipCausalLM(_EngineModule):
             # Tokens arrive in bursts of `sync_every` steps: the decode loop does not return to the host every token.
             if num_beams > 1:
                 raise ValueError("`streamer` cannot be used with beam search")          # HF's own check
-            streamer.put(torch.empty(inputs_embeds.shape[0], 0, dtype=torch.long))     # no prompt ids with inputs_embeds
+            streamer.put(torch.empty(inputs_embeds.shape[0] * G, 0, dtype=torch.long))     # no prompt ids with inputs_embeds
 
             def on_tokens(tokens, first_col):
                 for c in range(tokens.shape[1]):
                     streamer.put(tokens[:, c])
         batcher = getattr(self, "batcher", None)
-        if batcher is not None and (want or not (num_beams == 1 and inputs_embeds.shape[0] == 1)) and not _in_exclusive_job():
+        if batcher is not None and (want or not (num_beams == 1 and inputs_embeds.shape[0] * G == 1)) and not _in_exclusive_job():
             # beam search / a multi-row HF batch while requests share the engine: run it with the engine to itself, in turn
             def call():
                 _EXCLUSIVE.active = True          # thread-local: only the scheduler thread running this job sees it
@@ -697,11 +725,12 @@ class HipCausalLM(_EngineModule):
                                          min_length=min_length, repetition_penalty=repetition_penalty,
                                          length_penalty=length_penalty, use_cache=use_cache, stopping_criteria=stopping_criteria,
                                          early_stopping=early_stopping, pad_token_id=pad_token_id, eos_token_id=eos_token_id,
-                                         top_k=top_k, streamer=streamer, seed=seed, **outputs)
+                                         top_k=top_k, streamer=streamer, seed=seed, num_return_sequences=G, share_prompt=share_prompt,
+                                         **outputs)
                 finally:
                     _EXCLUSIVE.active = False
             return batcher.run_exclusive(call)
-        if batcher is not None and num_beams == 1 and inputs_embeds.shape[0] == 1 and not _in_exclusive_job():
+        if batcher is not None and num_beams == 1 and inputs_embeds.shape[0] * G == 1 and not _in_exclusive_job():
             # serving: one request per call (serve/model_worker.py:120-181), many calls in flight -> they share the engine's
             # decode loop instead of taking turns; the tokens are those of the solo call below
             def on_chunk(toks, first):
@@ -721,12 +750,12 @@ class HipCausalLM(_EngineModule):
             return generate_output(False, sequences=out) if return_dict_in_generate else out
         extra, slabs = {}, {}
         if return_dict_in_generate and (want or num_beams > 1):
-            extra, slabs = self._output_slabs(inputs_embeds, max_length, num_beams, output_scores, output_logits)
+            extra, slabs = self._output_slabs(inputs_embeds, max_length, num_beams, output_scores, output_logits, G)
         lock = getattr(self._engine, "call_lock", None) or contextlib.nullcontext()
         with lock:          # the same lock the slot path holds: a classic generate never lands between its cb_reset / cb_admit
             out = self._classic_generate(inputs_embeds, max_length, do_sample, temperature, top_p, eos_token_id, pad_token_id,
                                          stopping_criteria, seed, repetition_penalty, num_beams, length_penalty, early_stopping,
-                                         top_k, on_tokens, streamer, min_new, **extra)
+                                         top_k, on_tokens, streamer, min_new, n_samples=G, **extra)
         if streamer is not None:
             streamer.end()
         if not return_dict_in_generate:
@@ -743,12 +772,12 @@ class HipCausalLM(_EngineModule):
             fields["sequences_scores"] = out["sequences_scores"].to(dev) if output_scores else None
         return generate_output(num_beams > 1, **fields)
 
-    def _output_slabs(self, inputs_embeds, max_length, num_beams, output_scores, output_logits):
+    def _output_slabs(self, inputs_embeds, max_length, num_beams, output_scores, output_logits, n_samples=1):
         """[max_new, rows, V] fp32 slabs for output_scores / output_logits on the engine's device, after checking they fit (the engine
         writes step t of every row into slab[t])."""
         eng = self._engine
         B, S0 = inputs_embeds.shape[0], inputs_embeds.shape[1]
-        rows, max_new, V = B * max(int(num_beams), 1), int(max_length) - S0, int(eng.cfg.vocab)
+        rows, max_new, V = B * max(int(num_beams), 1) * n_samples, int(max_length) - S0, int(eng.cfg.vocab)
         names = [n for n, on in (("scores_out", output_scores), ("logits_out", output_logits)) if on]
         extra = dict(return_outputs=True)
         if not names or max_new <= 0:
@@ -790,8 +819,10 @@ class HipCausalLM(_EngineModule):
 
     def _classic_generate(self, inputs_embeds, max_length, do_sample, temperature, top_p, eos_token_id, pad_token_id,
                           stopping_criteria, seed, repetition_penalty, num_beams, length_penalty, early_stopping, top_k,
-                          on_tokens, streamer, min_new, **outputs):
-        return self._engine.generate(
+                          on_tokens, streamer, min_new, n_samples=1, **outputs):
+        # (n_samples > 1: the shared call -- one prompt pass over these prompts, n_samples rows each)
+        call = self._engine.generate if n_samples == 1 else functools.partial(self._engine.generate_shared, n_samples=n_samples)
+        return call(
             inputs_embeds.to(torch.bfloat16), max_length=int(max_length), do_sample=bool(do_sample),
             temperature=float(temperature if temperature is not None else 1.0),
             top_p=float(top_p if top_p is not None else 1.0),
@@ -949,6 +980,8 @@ class StarVectorStarCoder(nn.Module):
         if num_return_sequences > 1:                                   # :273-276
             generation_kwargs["num_return_sequences"] = num_return_sequences
             generation_kwargs["num_beams"] = 1
+            if "share_prompt" in kwargs:                               # extension: False = the repeated prompts (A/B)
+                generation_kwargs["share_prompt"] = kwargs["share_prompt"]
         outputs = self.svg_transformer.transformer.generate(**generation_kwargs)
         outputs = torch.cat([prompt_tokens.input_ids.repeat(num_return_sequences, 1), outputs], dim=1)    # :279
         raw_svg = self.svg_transformer.tokenizer.batch_decode(outputs, skip_special_tokens=True)

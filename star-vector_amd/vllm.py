@@ -10,6 +10,9 @@ else temperature -> top-k -> top-p -> min_p -> one draw.  All of it runs on devi
 (sampling.hip, cb_step_kernel); this module maps the parameters, queues the requests on a `ContinuousBatcher` and builds the
 outputs.  Deviations from the StarVector vLLM fork: the prompt ids are the token ids of the request's TEXT prompt (image
 positions carry no id here and count as none), and draws are distributional (vLLM's exponential-race RNG is not reproduced).
+The n samples of an input (`SamplingParams.n`, the validator's `num_generations`) go in as ONE group: the image encoder and adapter
+run once per input, and the samples admitted together share one prompt pass and the prompt's full KV pages (`sv_cb_admit_shared`;
+`generate(..., share_prompt=False)` queues every sample on its own, the same tokens).
 Not built: logprobs, best_of > n, stop strings, beam search.
 """
 from __future__ import annotations
@@ -288,16 +291,23 @@ class LLM:
                                  params=request_params(sp, seed, max_new, ids, eos, pad, vocab)))
         return jobs
 
-    def generate(self, inputs, sampling_params=None, use_tqdm: bool = True, **kwargs) -> List[RequestOutput]:
+    def generate(self, inputs, sampling_params=None, use_tqdm: bool = True, share_prompt: bool = True, **kwargs) -> List[RequestOutput]:
         """One RequestOutput per input, in input order, each with its n CompletionOutputs.  Every (input, sample) pair is one
-        request of the engine's continuous batch; more of them than `max_num_seqs` wait in its queue."""
+        request of the engine's continuous batch; more of them than `max_num_seqs` wait in its queue.  The samples of an input are
+        submitted as one group (one prompt pass for those admitted together); share_prompt=False submits each on its own."""
         if kwargs.get("lora_request") is not None or kwargs.get("prompt_adapter_request") is not None:
             raise NotImplementedError("LoRA / prompt adapters are not built")
         from .batching import ContinuousBatcher
         jobs = self.prepare(inputs, sampling_params)
         batcher = ContinuousBatcher(self.engine)
         try:
-            handles = [batcher.submit(j["emb"], j["params"]) for j in jobs]
+            handles = []
+            for _, grp in itertools.groupby(jobs, key=lambda j: j["input"]):
+                grp = list(grp)
+                if share_prompt and len(grp) > 1:
+                    handles += batcher.submit_group(grp[0]["emb"], [j["params"] for j in grp])
+                else:
+                    handles += [batcher.submit(j["emb"], j["params"]) for j in grp]
             toks = [h.result().view(-1).tolist() for h in handles]
         finally:
             batcher.close()
