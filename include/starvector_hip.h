@@ -16,6 +16,8 @@
  *   sv_generate            replaces  svg_transformer.transformer.generate(**generation_kwargs)
  *                                    starvector/model/models/starvector_base.py:228-241,255
  *                                    incl. StoppingCriteriaSub (starvector_base.py:9-20)
+ *   sv_generate_processed  the same call with the HF generate arguments the reference's callers add for a decoder that loops or emits
+ *                                    a forbidden token: no_repeat_ngram_size, bad_words_ids, min_p (sv_logits_processors below)
  *   sv_load_weight         ingests the reference state_dict keys (train/util.py:71 naming;
  *                          SURVEY.md section 8b "Weight names")
  *
@@ -309,6 +311,34 @@ int  sv_generate_ragged(sv_engine* e, const void* dev_embeds_packed, int32_t B, 
  * n_samples < 1, a length < 1, host_group[i] out of range or out of order. */
 int  sv_generate_shared(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, int32_t S0, int32_t n_samples,
                         const sv_sampling* sp, const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream);
+/* ---- HF logits processors that change tokens, on device (transformers 4.49 generation/logits_process.py): what HF generate's
+ * no_repeat_ngram_size, bad_words_ids and min_p arguments do.  The history g[0 .. t-1] of a row is its GENERATED ids only (with inputs_embeds
+ * HF's input_ids start empty); a finished row keeps receiving pads and they count, as in HF.
+ *   no_repeat_ngram_size n   NoRepeatNGramLogitsProcessor: at step t every id g[j+n-1], 0 <= j <= t-n, with g[j .. j+n-2] == g[t-n+1 .. t-1] is
+ *                            banned (nothing while t < n-1; n = 1 bans every earlier id)
+ *   bad words                NoBadWordsLogitsProcessor: a sequence of one id is always banned; the last id of a sequence of L > 1 ids is banned
+ *                            when t >= L and g[t-L+1 .. t-1] are its first L-1 ids (HF ignores a sequence "longer than the context", L > t).
+ *                            At most 64 sequences of at most 8 ids, every id inside the vocabulary: anything else is SV_EINVAL, nothing is
+ *                            truncated
+ *   min_p                    MinPLogitsWarper, after temperature, top-k and top-p: tokens with p < min_p * p_max are dropped, the maximum
+ *                            always stays; used when do_sample only; 0 = off, at most 1
+ * A banned id's score is -inf in the fp32 logits row before the repetition penalty, the min-length hold and the selection see it; of the
+ * per-step outputs dev_logits stays raw and dev_scores shows the -inf, as in HF.
+ * sv_generate_processed = sv_generate_shared (rectangular or ragged prompts through host_lens, n_samples continuations of each) with such a set.
+ * lp NULL or all zero: exactly sv_generate_shared, the same captured decode step.  An active ban adds one launch per step (ban_tokens_kernel,
+ * inside the captured step, and in front of the first selection after the prompt pass) and takes the separate selection launch, like a
+ * repetition penalty.  num_beams > 1 with any processor set: SV_EINVAL (beam rows reorder their histories; not built).  The host arrays are
+ * read during the call only. */
+typedef struct sv_logits_processors {
+    int32_t no_repeat_ngram_size;      /* 0 = off, 1..8 */
+    int32_t n_bad_words;               /* 0..64 */
+    const int32_t* bad_word_lens;      /* host [n_bad_words], each 1..8 */
+    const int32_t* bad_word_ids;       /* host, the sequences back to back: sum(bad_word_lens) ids */
+    float min_p;                       /* 0 = off, (0, 1] */
+} sv_logits_processors;
+int  sv_generate_processed(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, int32_t S0, int32_t n_samples,
+                           const sv_sampling* sp, const sv_logits_processors* lp, const sv_generate_outputs* outs, int64_t* dev_out_tokens,
+                           int32_t* n_generated, sv_stream stream);
 /* ---- continuous batching (the reference worker's 5 concurrent requests, serve/model_worker.py:161-172,
  * 216-229, as ONE decode loop).  Every row ("slot") of the engine's batch is an independent request: own sampling parameters,
  * budget, EOS, stop sequence (the reference's row-0 stop, starvector_base.py:9-20, is right for one request per generate call

@@ -225,6 +225,12 @@ int  sv_op_sample_top_p(const float* logits, int32_t B, int32_t V, int32_t ld, f
  * counts and, with the prompt ids, its repetition set.  host_out [B] = the token each row takes. */
 int  sv_op_cb_select(const float* dev_logits, int32_t B, int32_t V, int32_t ld, const sv_cb_request* reqs,
                      const int32_t* host_history, int32_t ld_hist, const int32_t* host_hist_len, int32_t* host_out, sv_stream stream);
+/* the kernel of sv_generate_processed's token bans (processors.hip ban_tokens_kernel) on caller-given rows: row b of dev_logits [B][ld] fp32
+ * (device, V valid columns) is a row whose generated ids so far are host_hist[b][0 .. host_hist_len[b]) (HOST, row stride ld_hist, ids inside
+ * the vocabulary).  The ids lp->no_repeat_ngram_size and lp's bad words ban at that point are set to -inf IN PLACE; every other value is left
+ * as it is.  lp->min_p is ignored (it is no ban).  The limits of sv_logits_processors apply (SV_EINVAL before any device work). */
+int  sv_op_ban_tokens(float* dev_logits, int32_t B, int32_t V, int32_t ld, const int32_t* host_hist, int32_t ld_hist,
+                      const int32_t* host_hist_len, const sv_logits_processors* lp, sv_stream stream);
 /* the kernel of sv_forward_logprobs (score.hip logprob_rows_kernel) on caller-given rows: dev_logits_bf16 [R][ld] bf16 (16-byte aligned,
  * ld a multiple of 8), V valid columns, dev_targets int32 [R] (-100 = ignore: logprob 0).  fp32 over x_i = float(logit_i) / temperature:
  * logsumexp, logprob = x_target - logsumexp, entropy of softmax(x) (an x_i = -inf adds 0), argmax = the lowest index holding the maximum.

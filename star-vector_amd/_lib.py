@@ -82,6 +82,16 @@ class SvGenerateOutputs(C.Structure):
     ]
 
 
+class SvLogitsProcessors(C.Structure):
+    # sv_generate_processed: HF's no_repeat_ngram_size / bad_words_ids / min_p (all zero = none)
+    _fields_ = [
+        ("no_repeat_ngram_size", C.c_int32), ("n_bad_words", C.c_int32),
+        ("bad_word_lens", C.POINTER(C.c_int32)), ("bad_word_ids", C.POINTER(C.c_int32)), ("min_p", C.c_float),
+    ]
+
+LP_MAX_NGRAM, LP_MAX_BAD_WORDS, LP_MAX_BAD_WORD_LEN = 8, 64, 8
+
+
 _P = C.c_void_p
 _I = C.c_int32
 _F = C.c_float
@@ -111,6 +121,8 @@ PRODUCT_PROTOTYPES = {
     "sv_prefill_ragged": (_I, [_P, _P, _I, C.POINTER(_I), _P, _P]),
     "sv_generate_ragged": (_I, [_P, _P, _I, C.POINTER(_I), C.POINTER(SvSampling), C.POINTER(SvGenerateOutputs), _P, C.POINTER(_I), _P]),
     "sv_generate_shared": (_I, [_P, _P, _I, C.POINTER(_I), _I, _I, C.POINTER(SvSampling), C.POINTER(SvGenerateOutputs), _P, C.POINTER(_I), _P]),
+    "sv_generate_processed": (_I, [_P, _P, _I, C.POINTER(_I), _I, _I, C.POINTER(SvSampling), C.POINTER(SvLogitsProcessors),
+                                   C.POINTER(SvGenerateOutputs), _P, C.POINTER(_I), _P]),
     "sv_cb_admit_shared": (_I, [_P, _P, _I, C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(SvCbRequest), C.POINTER(_I), _P]),
     "sv_cb_admit_ragged": (_I, [_P, _P, _I, C.POINTER(_I), C.POINTER(SvCbRequest), C.POINTER(_I), _P]),
     "sv_forward_logits": (_I, [_P, _P, _I, _I, _I, _P, _P]),
@@ -180,6 +192,7 @@ DEBUG_PROTOTYPES = {
     "sv_op_sample": (_I, [_P, _I, _I, _I, _F, _I, _F, C.c_uint64, _I, _P, _P]),
     "sv_op_logprob_rows": (_I, [_P, _I, _I, _I, _P, _F, _P, _P, _P, _P, C.POINTER(_I), _P]),
     "sv_debug_set_score_chunk_rows": (_I, [_P, _I]),
+    "sv_op_ban_tokens": (_I, [_P, _I, _I, _I, C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(SvLogitsProcessors), _P]),
     "sv_op_cb_select": (_I, [_P, _I, _I, _I, C.POINTER(SvCbRequest), C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(_I), _P]),
 }
 

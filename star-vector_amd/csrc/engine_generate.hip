@@ -19,7 +19,8 @@ static FinishArgs make_finish_args(sv_engine* e, int B, const sv_sampling& sp, i
     return f;
 }
 // sv_generate_ex outputs: the step's raw row and processed row, BEFORE suppress_token rewrites the EOS logit in place
-static void capture_step(sv_engine* e, int B, const sv_sampling& sp, hipStream_t st) {
+// what: 1 = the raw row, 2 = the processed row, 3 = both (CaptureArgs::what)
+static void capture_step(sv_engine* e, int B, const sv_sampling& sp, hipStream_t st, int what = 3) {
     const bool pen = sp.repetition_penalty > 0.f && sp.repetition_penalty != 1.0f;
     CaptureArgs c;
     c.desc = e->cap_desc; c.src = e->logits; c.ld_src = e->Vpad; c.V = e->cfg.vocab; c.B = B;
@@ -29,11 +30,22 @@ static void capture_step(sv_engine* e, int B, const sv_sampling& sp, hipStream_t
     c.min_new = (sp.min_new_tokens > 0 && sp.eos_token_id >= 0 && sp.eos_token_id < e->cfg.vocab) ? sp.min_new_tokens : 0;
     c.do_sample = sp.do_sample ? 1 : 0; c.temperature = sp.temperature; c.top_p = sp.top_p; c.top_k = sp.top_k;
     c.warp = (sp.do_sample && e->cap_host.scores) ? e->cap_warp : nullptr;
+    c.minp_log = e->minp_log; c.what = what;
     launch_capture_rows(c, st);
 }
 static void sample_and_finish(sv_engine* e, int B, const sv_sampling& sp, int max_new, hipStream_t st, bool fused = false) {
     if (fused && e->fin_folded) { e->fin_folded = false; return; }      // the lm_head launch in front did the selection AND the bookkeeping (SkinnyArgs::finish)
-    if (e->cap_on) capture_step(e, B, sp, st);                          // (a capturing call never folds: fused is off for it)
+    if (e->ban_ngram > 0 || e->ban_nwords > 0) {
+        // sv_generate_processed with a ban: the raw row goes out first, the banned ids become -inf in e->logits, then everything below -- the score
+        // capture, the min-length hold, the repetition penalty, the selection -- reads the banned row (-inf stays -inf through all of them)
+        if (e->cap_on && e->cap_host.logits) capture_step(e, B, sp, st, 1);
+        BanArgs ba;
+        ba.logits = e->logits; ba.ld = e->Vpad; ba.V = e->cfg.vocab; ba.B = B;
+        ba.hist = e->out_tok; ba.ld_hist = e->out_ld; ba.step = e->d_step; ba.hist_len = nullptr; ba.done = e->d_done;
+        ba.ngram = e->ban_ngram; ba.words = e->ban_words; ba.n_words = e->ban_nwords;
+        launch_ban_tokens(ba, st);
+        if (e->cap_on && e->cap_host.scores) capture_step(e, B, sp, st, 2);
+    } else if (e->cap_on) capture_step(e, B, sp, st);                   // (a capturing call never folds: fused is off for it)
     const bool pen = sp.repetition_penalty > 0.f && sp.repetition_penalty != 1.0f;
     const uint32_t* seen = pen ? e->seen : nullptr;
     if (sp.min_new_tokens > 0 && sp.eos_token_id >= 0 && sp.eos_token_id < e->cfg.vocab)
@@ -43,6 +55,7 @@ static void sample_and_finish(sv_engine* e, int B, const sv_sampling& sp, int ma
         sa.logits = e->logits; sa.ld = e->Vpad; sa.V = e->cfg.vocab; sa.B = B; sa.temperature = sp.temperature;
         sa.top_p = sp.top_p; sa.top_k = sp.top_k; sa.seed = sp.seed; sa.step = e->d_step; sa.out = e->next_tok; sa.scratch = e->sample_scratch;
         sa.seen = seen; sa.seen_words = e->seen_words; sa.penalty = sp.repetition_penalty;
+        sa.minp_log = e->minp_log;
         launch_sample_top_p(sa, st);
     } else if (!fused) {
         launch_argmax_partial(e->logits, e->Vpad, e->cfg.vocab, e->am_val, e->am_idx, B, seen, e->seen_words,
@@ -252,14 +265,16 @@ int sveng::report_bad_logits(sv_engine* e, hipStream_t st, const char* who, int 
 
 // G: samples per prompt (1: sv_generate / sv_generate_ragged; > 1: sv_generate_shared -- one prompt pass over the B prompts, B * G decode rows)
 static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const int32_t* lens, const sv_sampling* sp,
-                            const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream, int G);
+                            const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream, int G,
+                            const sv_logits_processors* lp);
 static int generate_retry(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const int32_t* lens, const sv_sampling* sp,
-                          const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream, int G = 1) {
+                          const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream, int G = 1,
+                          const sv_logits_processors* lp = nullptr) {
     if (e) { e->last_giveup = 0; e->stream_skip = 0; }
-    int rc = generate_attempt(e, dev_embeds, B, S0, lens, sp, outs, dev_out_tokens, n_generated, stream, G);
+    int rc = generate_attempt(e, dev_embeds, B, S0, lens, sp, outs, dev_out_tokens, n_generated, stream, G, lp);
     if (rc != 0 && e && e->cfg.exclusive_device == 2 && e->last_giveup && e->fused_off) {
         e->last_giveup = 0;
-        rc = generate_attempt(e, dev_embeds, B, S0, lens, sp, outs, dev_out_tokens, n_generated, stream, G);
+        rc = generate_attempt(e, dev_embeds, B, S0, lens, sp, outs, dev_out_tokens, n_generated, stream, G, lp);
     }
     if (e) e->stream_skip = 0;
     return rc;
@@ -313,6 +328,78 @@ extern "C" int sv_generate_shared(sv_engine* e, const void* dev_embeds_packed, i
 extern "C" int sv_generate(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const sv_sampling* sp,
                            int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
     return sv_generate_ex(e, dev_embeds, B, S0, sp, nullptr, dev_out_tokens, n_generated, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// sv_generate_processed: HF's no_repeat_ngram_size / bad_words_ids / min_p
+// ------------------------------------------------------------------------------------------------
+int sveng::check_logits_processors(const sv_logits_processors* lp, int V, const char* who) {
+    if (!lp) return 0;
+    if (lp->no_repeat_ngram_size < 0 || lp->no_repeat_ngram_size > SV_BAN_MAXNGRAM)
+        return fail(SV_EINVAL, "%s: no_repeat_ngram_size %d unsupported (0..%d)", who, lp->no_repeat_ngram_size, SV_BAN_MAXNGRAM);
+    if (lp->n_bad_words < 0 || lp->n_bad_words > SV_BAN_MAXWORDS)
+        return fail(SV_EINVAL, "%s: %d bad-word sequences (at most %d)", who, lp->n_bad_words, SV_BAN_MAXWORDS);
+    if (lp->n_bad_words > 0 && (!lp->bad_word_lens || !lp->bad_word_ids)) return fail(SV_EINVAL, "%s: n_bad_words > 0 but bad_word_lens / bad_word_ids is null", who);
+    if (!(lp->min_p >= 0.f && lp->min_p <= 1.f)) return fail(SV_EINVAL, "%s: min_p must lie in [0, 1]", who);
+    size_t off = 0;
+    for (int i = 0; i < lp->n_bad_words; ++i) {
+        const int L = lp->bad_word_lens[i];
+        if (L < 1 || L > SV_BAN_MAXLEN) return fail(SV_EINVAL, "%s: bad-word sequence %d has %d ids (1..%d)", who, i, L, SV_BAN_MAXLEN);
+        for (int k = 0; k < L; ++k) {
+            const int id = lp->bad_word_ids[off + k];
+            if (id < 0 || (V > 0 && id >= V)) return fail(SV_EINVAL, "%s: bad-word sequence %d: id %d outside the vocabulary", who, i, id);
+        }
+        off += (size_t)L;
+    }
+    return 0;
+}
+void sveng::ban_word_table(const sv_logits_processors& lp, std::vector<BanWord>& out) {
+    out.assign((size_t)(lp.n_bad_words > 0 ? lp.n_bad_words : 1), BanWord{});
+    size_t off = 0;
+    for (int i = 0; i < lp.n_bad_words; ++i) {
+        out[i].len = lp.bad_word_lens[i];
+        for (int k = 0; k < out[i].len; ++k) out[i].id[k] = lp.bad_word_ids[off + k];
+        off += (size_t)out[i].len;
+    }
+}
+// the call's processors into the engine (cleared again by generate_attempt's guard); the ids are checked against the engine's vocabulary here
+static int setup_processors(sv_engine* e, const sv_sampling* sp, const sv_logits_processors* lp, hipStream_t st) {
+    if (!lp) return 0;
+    SVCHECK(check_logits_processors(lp, e->cfg.vocab, "sv_generate_processed"));
+    if (lp->n_bad_words > 0) {
+        if (!e->ban_words) SVCHECK(dalloc(e, &e->ban_words, (size_t)SV_BAN_MAXWORDS));
+        ban_word_table(*lp, e->ban_host);
+        HIPCHECK(hipMemcpyAsync(e->ban_words, e->ban_host.data(), (size_t)lp->n_bad_words * sizeof(BanWord), hipMemcpyHostToDevice, st));
+    }
+    e->ban_ngram = lp->no_repeat_ngram_size;
+    e->ban_nwords = lp->n_bad_words;
+    e->minp_log = (sp->do_sample && lp->min_p > 0.f) ? logf(lp->min_p) : -INFINITY;
+    return 0;
+}
+extern "C" int sv_generate_processed(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, int32_t S0, int32_t n_samples,
+                                     const sv_sampling* sp, const sv_logits_processors* lp, const sv_generate_outputs* outs,
+                                     int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
+    const bool any = lp && (lp->no_repeat_ngram_size != 0 || lp->n_bad_words != 0 || lp->min_p != 0.f);
+    if (!any) return sv_generate_shared(e, dev_embeds_packed, B, host_lens, S0, n_samples, sp, outs, dev_out_tokens, n_generated, stream);
+    // (the checks that need no engine come first: they are the same on a machine without a GPU)
+    if (!dev_embeds_packed || !sp || !dev_out_tokens || !n_generated) return fail(SV_EINVAL, "sv_generate_processed: null argument");
+    SVCHECK(check_logits_processors(lp, 0, "sv_generate_processed"));
+    if (sp->num_beams > 1)
+        return fail(SV_EINVAL, "sv_generate_processed: no_repeat_ngram_size / bad words / min_p with num_beams %d is not built (beam rows reorder their histories)",
+                    sp->num_beams);
+    if (B < 1) return fail(SV_EINVAL, "sv_generate_processed: bad B=%d", B);
+    if (n_samples < 1) return fail(SV_EINVAL, "sv_generate_processed: bad n_samples=%d (must be >= 1)", n_samples);
+    int longest = S0;
+    if (host_lens) {
+        longest = 0;
+        for (int b = 0; b < B; ++b) {
+            if (host_lens[b] < 1) return fail(SV_EINVAL, "sv_generate_processed: length %d of sequence %d (must be >= 1)", host_lens[b], b);
+            longest = host_lens[b] > longest ? host_lens[b] : longest;
+        }
+    } else if (S0 < 1) {
+        return fail(SV_EINVAL, "sv_generate_processed: bad S0=%d", S0);
+    }
+    return generate_retry(e, dev_embeds_packed, B, longest, host_lens, sp, outs, dev_out_tokens, n_generated, stream, n_samples, lp);
 }
 
 // validation of sv_generate_ex's outputs, and the descriptor of the call's slabs (allocated on first use, rewritten on the call's stream in front
@@ -406,7 +493,8 @@ static int shared_prefill_fork(sv_engine* e, const void* dev_embeds, int B, int 
 
 // lens != nullptr: the ragged form -- S0 is the longest prompt (the budget counts from it), sequence b has lens[b] rows
 static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t Bp, int32_t S0, const int32_t* lens, const sv_sampling* sp,
-                            const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream, int G) {
+                            const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream, int G,
+                            const sv_logits_processors* lp) {
     SVCHECK(check_ready(e));
     const bool shared = G > 1;
     if (shared && (Bp < 1 || (long long)Bp * G > e->cfg.max_batch))
@@ -433,6 +521,9 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t Bp, in
     HIPCHECK(hipStreamWaitEvent(st, e->gen_event, 0));
 
     SVCHECK(cb_guard(e, "sv_generate"));
+    struct ProcOff { sv_engine* e; ~ProcOff() { e->ban_ngram = 0; e->ban_nwords = 0; e->minp_log = -INFINITY; } } proc_off{e};
+    SVCHECK(setup_processors(e, sp, lp, st));
+    const bool ban = e->ban_ngram > 0 || e->ban_nwords > 0;
     struct CapOff { sv_engine* e; ~CapOff() { e->cap_on = false; } } cap_off{e};
     SVCHECK(setup_capture(e, sp, outs, sp->num_beams > 1 ? B * sp->num_beams : B, max_new, st));
     if (sp->num_beams > 1) {
@@ -463,8 +554,9 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t Bp, in
         const bool pen = sp->repetition_penalty > 0.f && sp->repetition_penalty != 1.0f;
         // a capturing call (sv_generate_ex) takes the separate selection launch: the capture must read the logits row between the lm_head and
         // the selection, and the tokens are bit-identical either way (tests/test_gpu_e2e.py)
+        // (a ban rewrites the logits row between the lm_head and the selection: the separate launch as well)
         fused_sel = !sp->do_sample && !pen && sp->min_new_tokens <= 0 && B <= 32 && !e->lm_head.fp8 && waves > 1 && !two && !(e->exp & 1024) &&
-                    !e->cap_on;
+                    !e->cap_on && !ban;
     }
     // generation state, one launch: positions = S0 - 1 (finish_step adds 1), unfinished = 1, {step, done, n_emitted} = 0, the folded selection's key slots = 0
     gen_state_init(e->positions, S0 - 1, e->unfinished, B, e->d_step, e->amax, fused_sel ? 64 * SV_AMAX_STRIDE : 0, st);
@@ -520,12 +612,14 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t Bp, in
         // engine and reused by the next call whose batch, budget and sampling parameters are the same (a serving request
         // stream, the benchmark), so a short request does not pay a 172-node capture + instantiate; a call with other
         // parameters replaces it.  Owned by the engine: no early return below can leak it.
-        char key[256];
+        char key[384];
         snprintf(key, sizeof(key), "B%d|n%d|ds%d|T%a|p%a|k%d|seed%llu|eos%d|pad%d|ns%d|rp%a|mn%d|x%d|fo%d|ff%d", B, max_new, sp->do_sample,
                  sp->temperature, sp->top_p, sp->top_k, (unsigned long long)sp->seed, sp->eos_token_id, sp->pad_token_id, sp->n_stop,
                  sp->repetition_penalty, sp->min_new_tokens, e->exp, e->fused_off ? 1 : 0, e->fin_fold ? 1 : 0);
         if (e->cap_on)       // capturing steps carry more launches (never the same graph as a plain call's); the slabs are read through cap_desc
             snprintf(key + strlen(key), sizeof(key) - strlen(key), "|cap%d", (e->cap_host.scores ? 1 : 0) | (e->cap_host.logits ? 2 : 0));
+        if (ban || e->minp_log > -INFINITY)      // the ban launch / the sampler's min_p argument (the bad-word ids live in device memory, not in the graph);
+            snprintf(key + strlen(key), sizeof(key) - strlen(key), "|ng%d|bw%d|mp%a", e->ban_ngram, e->ban_nwords, e->minp_log);      // neither: the plain call's key and graph
         if (e->gen_gexec && e->gen_graph_key == key) {
             gexec = e->gen_gexec;
         } else {

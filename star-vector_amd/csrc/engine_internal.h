@@ -221,6 +221,13 @@ struct sv_engine {
     CaptureDesc cap_host = {};
     float* cap_warp = nullptr;
     bool cap_on = false;
+    // sv_generate_processed: the HF logits processors of the current call (set and cleared by it).  A ban (no_repeat_ngram_size, bad words) adds
+    // one launch between the lm_head and the selection (processors.hip); min_p rides in the sampler's arguments.  The bad-word table is device
+    // memory of the engine, uploaded once per call (ban_host = its host image, kept alive for the upload)
+    int ban_ngram = 0, ban_nwords = 0;
+    float minp_log = -INFINITY;
+    BanWord* ban_words = nullptr;
+    std::vector<BanWord> ban_host;
     // optional per-kernel HIP-event profiling of the decode step (bench.py roofline leg)
     bool prof_on = false;
     std::vector<hipEvent_t> prof_ev;
@@ -288,6 +295,10 @@ int prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, const int3
 void ragged_positions(sv_engine* e, int B, int rep, int delta, hipStream_t st);
 // engine_generate.hip
 void fork_args(sv_engine* e, int n_prompts, int n_rows, ForkArgs& f);      // the fork launch over e->fork_desc, the engine's block table, pool and logits
+// validation of a processor set against a vocabulary of V ids (V <= 0: the ids are only checked for >= 0) -- host arithmetic, no device -- and
+// the bad-word table it describes
+int check_logits_processors(const sv_logits_processors* lp, int V, const char* who);
+void ban_word_table(const sv_logits_processors& lp, std::vector<BanWord>& out);
 int check_finite_logits(sv_engine* e, hipStream_t st, const char* who);
 int report_bad_logits(sv_engine* e, hipStream_t st, const char* who, int what);      // what = the d_bad code already read (0: fine)
 }  // namespace sveng

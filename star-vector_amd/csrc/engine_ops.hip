@@ -906,6 +906,41 @@ extern "C" int sv_op_cb_select(const float* logits, int32_t B, int32_t V, int32_
     return 0;
 }
 
+// ban_tokens_kernel (processors.hip) on caller-given rows and histories: rewrites dev_logits in place
+extern "C" int sv_op_ban_tokens(float* dev_logits, int32_t B, int32_t V, int32_t ld, const int32_t* hist, int32_t ld_hist, const int32_t* hist_len,
+                                const sv_logits_processors* lp, sv_stream stream) {
+    if (!dev_logits || !hist_len || !lp || B < 1 || B > 4096 || V < 1 || ld < V || ld_hist < 0) return fail(SV_EINVAL, "sv_op_ban_tokens: bad argument");
+    SVCHECK(check_logits_processors(lp, V, "sv_op_ban_tokens"));
+    for (int b = 0; b < B; ++b) {
+        if (hist_len[b] < 0 || hist_len[b] > ld_hist || (hist_len[b] > 0 && !hist))
+            return fail(SV_EINVAL, "sv_op_ban_tokens: row %d: history length %d (ld_hist %d)", b, hist_len[b], ld_hist);
+        for (int t = 0; t < hist_len[b]; ++t)
+            if (hist[(size_t)b * ld_hist + t] < 0 || hist[(size_t)b * ld_hist + t] >= V)
+                return fail(SV_EINVAL, "sv_op_ban_tokens: row %d: history id outside the vocabulary", b);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    TmpBufs tmp;
+    int32_t *dhist, *dlen;
+    BanWord* dwords;
+    std::vector<BanWord> words;
+    ban_word_table(*lp, words);
+    const size_t nh = (size_t)B * (size_t)(ld_hist > 0 ? ld_hist : 1);
+    SVCHECK(tmp.get(&dhist, nh));
+    SVCHECK(tmp.get(&dlen, (size_t)B));
+    SVCHECK(tmp.get(&dwords, words.size()));
+    if (ld_hist > 0 && hist) HIPCHECK(hipMemcpyAsync(dhist, hist, (size_t)B * ld_hist * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(dlen, hist_len, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(dwords, words.data(), words.size() * sizeof(BanWord), hipMemcpyHostToDevice, st));
+    BanArgs a;
+    a.logits = dev_logits; a.ld = ld; a.V = V; a.B = B;
+    a.hist = dhist; a.ld_hist = ld_hist; a.step = nullptr; a.hist_len = dlen; a.done = nullptr;
+    a.ngram = lp->no_repeat_ngram_size; a.words = dwords; a.n_words = lp->n_bad_words;
+    launch_ban_tokens(a, st);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
 // sv_forward_logprobs runs its lm_head over `rows` rows at a time (0 = the default); the workspace follows at the next call
 extern "C" int sv_debug_set_score_chunk_rows(sv_engine* e, int32_t rows) {
     if (rows < 0 || rows > 65536 || rows % 256) return fail(SV_EINVAL, "sv_debug_set_score_chunk_rows: rows=%d must be 0 or a multiple of 256 up to 65536", rows);

@@ -318,6 +318,7 @@ struct SampleArgs {
     uint64_t seed; const int32_t* step;                              // device step counter
     int32_t* out; float* scratch;                                    // scratch >= B*4 floats
     const uint32_t* seen; int seen_words; float penalty;             // repetition penalty (nullptr = off)
+    float minp_log = -INFINITY;                                      // HF MinPLogitsWarper after top-p: log(min_p), -inf = off
 };
 void launch_sample_top_p(const SampleArgs& a, hipStream_t st);
 
@@ -361,6 +362,9 @@ struct CaptureArgs {
     int eos, min_new;                                                // min_new <= 0: hold off
     int do_sample; float temperature, top_p; int top_k;
     float* warp;                                                     // [B][8] per-row warper thresholds (do_sample)
+    float minp_log = -INFINITY;                                      // do_sample: min_p after top-p (log(min_p), -inf = off)
+    int what = 3;                                                    // 1 = the raw row, 2 = the processed row, 3 = both (a call with token bans
+                                                                     //   takes them apart: raw row -> ban_tokens_kernel -> processed row)
 };
 void launch_capture_rows(const CaptureArgs& a, hipStream_t st);
 #ifdef __HIPCC__
@@ -416,6 +420,23 @@ __device__ __forceinline__ void finish_step_call(const FinishArgs& p, int t, int
     }
 }
 #endif
+
+// ---- HF logits processors that ban tokens (processors.hip): NoRepeatNGramLogitsProcessor and NoBadWordsLogitsProcessor over a row's
+// generated ids.  One block per row writes -inf at the banned ids of the row's fp32 logits, in place, between the lm_head and the selection.
+#define SV_BAN_MAXNGRAM 8
+#define SV_BAN_MAXWORDS 64
+#define SV_BAN_MAXLEN 8
+struct BanWord { int32_t len; int32_t id[SV_BAN_MAXLEN]; };          // device-resident table entry: one bad-word sequence
+struct BanArgs {
+    float* logits; int ld; int V; int B;                             // [B][ld] fp32 rows, V valid columns
+    const int32_t* hist; int ld_hist;                                // [B][ld_hist] generated ids of every row (the engine's out_tok)
+    const int32_t* step;                                             // device scalar: ids generated so far, the same for every row ...
+    const int32_t* hist_len;                                         //   ... or [B] lengths, one per row (the operator's test surface); nullptr: *step
+    const int32_t* done;                                             // device scalar or nullptr: nothing is written once it is set
+    int ngram;                                                       // no_repeat_ngram_size: 0 = off, 1 .. SV_BAN_MAXNGRAM
+    const BanWord* words; int n_words;                               // bad-word table, 0 .. SV_BAN_MAXWORDS entries
+};
+void launch_ban_tokens(const BanArgs& a, hipStream_t st);
 
 // ---- continuous batching: one request per row ("slot"), everything per row (sampling.hip) ---------------------------
 #define SV_CB_MAXSTOP 16

@@ -368,7 +368,7 @@ __global__ __launch_bounds__(SP_THREADS) void sample_top_p_kernel(SampleArgs p) 
     const uint32_t* srow = p.seen ? p.seen + (size_t)blockIdx.x * p.seen_words : nullptr;
     const float invT = 1.0f / p.temperature;
     auto lg = [&](int i) { return rep_penalty(row[i], i, srow, p.penalty) * invT; };     // processors, then temperature
-    const int tok = sample_row(lg, p.V, p.top_k, p.top_p, -INFINITY, p.seed, (uint32_t)p.step[0], (uint32_t)blockIdx.x, red, scan, &result);
+    const int tok = sample_row(lg, p.V, p.top_k, p.top_p, p.minp_log, p.seed, (uint32_t)p.step[0], (uint32_t)blockIdx.x, red, scan, &result);
     if (threadIdx.x == 0) p.out[blockIdx.x] = tok;
 }
 void launch_sample_top_p(const SampleArgs& a, hipStream_t st) {
@@ -397,7 +397,7 @@ __global__ __launch_bounds__(SP_THREADS) void capture_warp_kernel(CaptureArgs p)
     const WarpStats w = row_warp_stats<false, true>(lg, p.V, p.top_k, p.top_p, 1, red);
     if (threadIdx.x == 0) {
         float* o = p.warp + (size_t)b * 8;
-        o[0] = w.kth; o[1] = w.mx; o[2] = w.invZ; o[3] = w.v0; o[4] = w.smin;
+        o[0] = w.kth; o[1] = w.mx; o[2] = w.invZ; o[3] = w.v0; o[4] = w.smin; o[5] = wp_minp_thr(w.mx, p.minp_log);
     }
 }
 
@@ -411,15 +411,15 @@ __global__ __launch_bounds__(256) void capture_write_kernel(CaptureArgs p) {
     const size_t off = ((size_t)t * d.rows + b) * (size_t)d.ld;
     const int q0 = blockIdx.y * CAP_QPB, q1 = q0 + CAP_QPB;
     const bool edges = blockIdx.y == 0;
-    if (d.logits) capture_store_row(d.logits + off, p.V, q0, q1, edges, [&](int j) { return row[j]; });
-    if (!d.scores) return;
+    if (d.logits && (p.what & 1)) capture_store_row(d.logits + off, p.V, q0, q1, edges, [&](int j) { return row[j]; });
+    if (!d.scores || !(p.what & 2)) return;
     const uint32_t* srow = p.seen ? p.seen + (size_t)b * p.seen_words : nullptr;
     const int eos = t < p.min_new ? p.eos : -1;                      // MinLength: the EOS id at -inf while held
     const float pen = p.penalty;
     if (p.do_sample) {
         const float* o = p.warp + (size_t)b * 8;
         WarpStats w;
-        w.kth = o[0]; w.mx = o[1]; w.invZ = o[2]; w.v0 = o[3]; w.smin = o[4];
+        w.kth = o[0]; w.mx = o[1]; w.invZ = o[2]; w.v0 = o[3]; w.smin = o[4]; w.mthr = o[5];
         const float T = p.temperature, invT = 1.0f / T;
         // kept: the sampler's test on the sampler's value (s * invT); reported: HF's TemperatureLogitsWarper, s / T
         capture_store_row(d.scores + off, p.V, q0, q1, edges, [&](int j) {
@@ -432,7 +432,7 @@ __global__ __launch_bounds__(256) void capture_write_kernel(CaptureArgs p) {
     }
 }
 void launch_capture_rows(const CaptureArgs& a, hipStream_t st) {
-    if (a.do_sample && a.warp) capture_warp_kernel<<<a.B, SP_THREADS, 0, st>>>(a);
+    if (a.do_sample && a.warp && (a.what & 2)) capture_warp_kernel<<<a.B, SP_THREADS, 0, st>>>(a);
     capture_write_kernel<<<dim3(a.B, (a.V + 4 * CAP_QPB - 1) / (4 * CAP_QPB)), 256, 0, st>>>(a);
 }
 

@@ -282,6 +282,19 @@ class HipEngine:
             return self.generate(x, max_length, lengths=lens, n_samples=n_samples, **kw)
         return self.generate(embeds, max_length, n_samples=n_samples, **kw)
 
+    def generate_processed(self, embeds, max_length: int, no_repeat_ngram_size: int = 0, bad_words_ids=None, min_p: float = 0.0,
+                           lengths=None, n_samples: int = 1, **kw):
+        """``generate`` with HF's token-changing processors on device (sv_generate_processed): ``no_repeat_ngram_size`` (1..8: no n-gram of the
+        generated ids repeats), ``bad_words_ids`` (at most 64 id sequences of at most 8 ids: never completed) and ``min_p`` (with do_sample:
+        tokens below min_p * p_max are dropped after top-k / top-p).  ``embeds`` as in ``generate`` / ``generate_ragged`` / ``generate_shared``
+        (``lengths``, ``n_samples``); same keywords and return value.  All three off: exactly ``generate``'s tokens.  ValueError beyond the
+        limits or with num_beams > 1."""
+        lp = logits_processors(no_repeat_ngram_size, bad_words_ids, min_p, vocab=self.cfg.vocab)
+        if lengths is not None or isinstance(embeds, (list, tuple)):
+            x, _arr, lens = self._packed(embeds, lengths)
+            return self.generate(x, max_length, lengths=lens, n_samples=n_samples, logits_processors=lp, **kw)
+        return self.generate(embeds, max_length, n_samples=n_samples, logits_processors=lp, **kw)
+
     def block_table_row(self, row: int) -> List[int]:
         """The block-table row of a decode row / slot as the device holds it (sv_debug_block_table)."""
         buf = (C.c_int32 * 4096)()
@@ -353,7 +366,8 @@ class HipEngine:
                  repetition_penalty: float = 1.0, num_beams: int = 1, length_penalty: float = 1.0,
                  early_stopping=False, top_k: int = 0, on_tokens=None, min_new_tokens: int = 0,
                  scores_out: Optional[torch.Tensor] = None, logits_out: Optional[torch.Tensor] = None,
-                 return_outputs: bool = False, lengths: Optional[Sequence[int]] = None, n_samples: int = 1):
+                 return_outputs: bool = False, lengths: Optional[Sequence[int]] = None, n_samples: int = 1,
+                 logits_processors=None):
         """HF ``generate`` semantics for inputs_embeds: returns ONLY the new tokens, int64 [B, N].
         ``lengths``: the ragged form -- inputs_embeds is packed [sum(lengths), D], one prompt pass for all of them, ``max_length`` counts from
         the longest prompt (see ``generate_ragged``).
@@ -367,7 +381,8 @@ class HipEngine:
         Per-step outputs (sv_generate_ex): ``scores_out`` / ``logits_out`` are fp32 device tensors [max_new, rows, ld] (rows = B, or
         B * num_beams under beam search; ld >= vocab) that receive HF's processed scores / raw logits of every generated column.
         ``return_outputs=True`` returns a dict {"sequences", "n_generated"} plus, under beam search, "sequences_scores" [B] and
-        "beam_indices" [B, n] int64 instead of the bare token tensor."""
+        "beam_indices" [B, n] int64 instead of the bare token tensor.
+        ``logits_processors``: what ``logits_processors(...)`` returns; the call then goes through sv_generate_processed (see ``generate_processed``)."""
         lens_arr = None
         if lengths is not None:
             x, lens_arr, lens = self._packed(inputs_embeds, lengths)
@@ -380,6 +395,12 @@ class HipEngine:
         G = int(n_samples)
         if G < 1:
             raise ValueError(f"n_samples must be >= 1, got {n_samples}")
+        lp = None
+        if logits_processors is not None:
+            lp, _lp_keep = logits_processors              # the struct and the host arrays its pointers refer to
+            if int(num_beams) > 1:
+                raise ValueError("no_repeat_ngram_size / bad_words_ids / min_p with num_beams > 1 is not built")
+        n_prompts = B
         if G > 1 and int(num_beams) > 1:
             raise NotImplementedError("n_samples > 1 under beam search (num_beams > 1) is not built")
         if G > 1:
@@ -401,7 +422,10 @@ class HipEngine:
         out = torch.empty(B, max_new, dtype=torch.int64, device=x.device)
         n = C.c_int32(0)
         if scores_out is None and logits_out is None and not return_outputs:
-            if G > 1:
+            if lp is not None:
+                check(self.lib.sv_generate_processed(self._h, _ptr(x), n_prompts, lens_arr, S0, G, C.byref(sp), C.byref(lp), None, _ptr(out),
+                                                     C.byref(n), _stream()), "sv_generate_processed")
+            elif G > 1:
                 check(self.lib.sv_generate_shared(self._h, _ptr(x), n_prompts, lens_arr, S0, G, C.byref(sp), None, _ptr(out), C.byref(n), _stream()),
                       "sv_generate_shared")
             elif lens_arr is not None:
@@ -434,7 +458,10 @@ class HipEngine:
         if beam:
             outs.host_sequences_scores = C.cast(seq_scores, C.POINTER(C.c_float))
             outs.host_beam_indices = C.cast(beam_idx, C.POINTER(C.c_int64))
-        if G > 1:
+        if lp is not None:
+            check(self.lib.sv_generate_processed(self._h, _ptr(x), n_prompts, lens_arr, S0, G, C.byref(sp), C.byref(lp), C.byref(outs), _ptr(out),
+                                                 C.byref(n), _stream()), "sv_generate_processed")
+        elif G > 1:
             check(self.lib.sv_generate_shared(self._h, _ptr(x), n_prompts, lens_arr, S0, G, C.byref(sp), C.byref(outs), _ptr(out), C.byref(n),
                                               _stream()), "sv_generate_shared")
         elif lens_arr is not None:
@@ -646,6 +673,33 @@ class HipEngine:
         res["event_pair_overhead_ms"] = buf[22]
         res["first_to_last_event_ms"] = buf[23]
         return res
+
+
+def logits_processors(no_repeat_ngram_size=0, bad_words_ids=None, min_p=0.0, vocab: Optional[int] = None):
+    """The sv_logits_processors struct of HF's no_repeat_ngram_size / bad_words_ids / min_p and the host arrays its pointers refer to (keep the
+    pair alive for the duration of the call).  The limits of include/starvector_hip.h are checked here too -- ValueError, nothing is truncated:
+    n-grams of at most 8 ids, at most 64 bad-word sequences of 1..8 ids, every id in [0, vocab), min_p in [0, 1]."""
+    n = int(no_repeat_ngram_size or 0)
+    if n < 0 or n > _lib.LP_MAX_NGRAM:
+        raise ValueError(f"no_repeat_ngram_size {n} unsupported (0..{_lib.LP_MAX_NGRAM})")
+    words = [[int(t) for t in w] for w in (bad_words_ids or [])]
+    if len(words) > _lib.LP_MAX_BAD_WORDS:
+        raise ValueError(f"{len(words)} bad-word sequences (at most {_lib.LP_MAX_BAD_WORDS})")
+    for i, w in enumerate(words):
+        if not 1 <= len(w) <= _lib.LP_MAX_BAD_WORD_LEN:
+            raise ValueError(f"bad-word sequence {i} has {len(w)} ids (1..{_lib.LP_MAX_BAD_WORD_LEN})")
+        for t in w:
+            if t < 0 or (vocab is not None and t >= int(vocab)):
+                raise ValueError(f"bad-word sequence {i}: id {t} outside the vocabulary")
+    mp = float(min_p or 0.0)
+    if not 0.0 <= mp <= 1.0:
+        raise ValueError(f"min_p must lie in [0, 1], got {min_p}")
+    lens = (C.c_int32 * max(len(words), 1))(*[len(w) for w in words])
+    flat = [t for w in words for t in w]
+    ids = (C.c_int32 * max(len(flat), 1))(*flat)
+    lp = _lib.SvLogitsProcessors(n, len(words), C.cast(lens, C.POINTER(C.c_int32)) if words else None,
+                                 C.cast(ids, C.POINTER(C.c_int32)) if words else None, mp)
+    return lp, (lens, ids)
 
 
 def cb_requests(requests: Sequence[dict]):
@@ -1018,6 +1072,31 @@ def op_cb_select(logits, requests: Sequence[dict], history=None):
     check(lib.sv_op_cb_select(_ptr(logits), B, V, ld, arr, hist, ld_hist, lens, out, _stream()), "sv_op_cb_select")
     del keep
     return torch.tensor(list(out), dtype=torch.int32)
+
+
+def op_ban_tokens(logits, history, no_repeat_ngram_size=0, bad_words_ids=None):
+    """The token-ban kernel of `generate_processed` (ban_tokens_kernel) on caller-given fp32 rows [B, V]: row b has generated the ids
+    history[b] (a list) so far.  The kernel works in place on a copy whose row stride is V rounded up to 4 (padding columns zero).  Returns
+    (rows [B, V], padding columns [B, ld - V]): the rows with the ids NoRepeatNGram(no_repeat_ngram_size) and NoBadWords(bad_words_ids) ban at
+    that point set to -inf and every other value untouched, and the padding as the kernel left it."""
+    lib = _lib.load()
+    logits = _need(logits, torch.float32, "logits")
+    B, V = logits.shape
+    ld = (V + 3) // 4 * 4
+    buf = torch.zeros(B, ld, dtype=torch.float32, device=logits.device)
+    buf[:, :V] = logits
+    history = [list(map(int, h)) for h in history]
+    if len(history) != B:
+        raise ValueError("one history per row")
+    ld_hist = max(1, max(len(h) for h in history))
+    hist = (C.c_int32 * (B * ld_hist))()
+    for b, h in enumerate(history):
+        hist[b * ld_hist: b * ld_hist + len(h)] = h
+    lens = (C.c_int32 * B)(*[len(h) for h in history])
+    lp, keep = logits_processors(no_repeat_ngram_size, bad_words_ids, 0.0, vocab=V)
+    check(lib.sv_op_ban_tokens(_ptr(buf), B, V, ld, hist, ld_hist, lens, C.byref(lp), _stream()), "sv_op_ban_tokens")
+    del keep
+    return buf[:, :V].clone(), buf[:, V:].clone()
 
 
 def op_preprocess_image(pixels: torch.Tensor, size: int, mean, std, recipe: str = "starvector") -> torch.Tensor:

@@ -20,6 +20,7 @@ import json
 import os
 import contextlib
 import functools
+import numbers
 import threading
 from typing import Dict, List, Optional, Sequence
 
@@ -627,7 +628,8 @@ class HipCausalLM(_EngineModule):
                  early_stopping: bool = False, pad_token_id: Optional[int] = None, eos_token_id: Optional[int] = None,
                  num_return_sequences: int = 1, top_k: Optional[int] = 50, streamer=None, seed: Optional[int] = None,
                  return_dict_in_generate: bool = False, output_scores: bool = False, output_logits: bool = False,
-                 share_prompt: bool = True, **unused):
+                 share_prompt: bool = True, no_repeat_ngram_size: int = 0, bad_words_ids=None, min_p: Optional[float] = None,
+                 **unused):
         # top_k: the reference never passes it; its pinned transformers==4.49.0 (pyproject.toml:18) defaults
         # GenerationConfig.top_k to 50, so every do_sample call there is top-k 50 followed by top-p.  Same default here.
         if inputs_embeds is None:
@@ -643,6 +645,16 @@ class HipCausalLM(_EngineModule):
                                           "are generated group by group, without HF's common step axis")
         outputs = dict(return_dict_in_generate=True, output_scores=output_scores, output_logits=output_logits) \
             if return_dict_in_generate else {}
+        # HF's token-changing processors, on device (sv_generate_processed): NoRepeatNGram, NoBadWords, MinP.  Set = the call goes through
+        # HipEngine.generate_processed; where that route is not built the call raises, it never drops the argument.
+        proc = self._processor_args(no_repeat_ngram_size, bad_words_ids, min_p, do_sample, eos_token_id)
+        if proc:
+            if int(num_beams) > 1:
+                raise NotImplementedError("no_repeat_ngram_size / bad_words_ids / min_p with num_beams > 1 are not built: beam rows reorder "
+                                          "their histories")
+            if attention_mask is not None and not bool((attention_mask == 1).all()):
+                raise NotImplementedError("no_repeat_ngram_size / bad_words_ids / min_p with a padded attention_mask are not built: padded "
+                                          "rows run as continuous-batching slots, whose requests carry no such processors")
         # Random stream: HF draws from torch's global generator, so repeated calls differ and torch.manual_seed controls them.
         # The device sampler is a pure function of (seed, step, row): the per-call seed is therefore DRAWN from torch's
         # generator (same reproducibility contract), unless the caller pins it with `seed=` (tests, data-parallel ranks).
@@ -715,7 +727,7 @@ class HipCausalLM(_EngineModule):
                 for c in range(tokens.shape[1]):
                     streamer.put(tokens[:, c])
         batcher = getattr(self, "batcher", None)
-        if batcher is not None and (want or not (num_beams == 1 and inputs_embeds.shape[0] * G == 1)) and not _in_exclusive_job():
+        if batcher is not None and (want or proc or not (num_beams == 1 and inputs_embeds.shape[0] * G == 1)) and not _in_exclusive_job():
             # beam search / a multi-row HF batch while requests share the engine: run it with the engine to itself, in turn
             def call():
                 _EXCLUSIVE.active = True          # thread-local: only the scheduler thread running this job sees it
@@ -726,7 +738,7 @@ class HipCausalLM(_EngineModule):
                                          length_penalty=length_penalty, use_cache=use_cache, stopping_criteria=stopping_criteria,
                                          early_stopping=early_stopping, pad_token_id=pad_token_id, eos_token_id=eos_token_id,
                                          top_k=top_k, streamer=streamer, seed=seed, num_return_sequences=G, share_prompt=share_prompt,
-                                         **outputs)
+                                         no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids, min_p=min_p, **outputs)
                 finally:
                     _EXCLUSIVE.active = False
             return batcher.run_exclusive(call)
@@ -755,7 +767,7 @@ class HipCausalLM(_EngineModule):
         with lock:          # the same lock the slot path holds: a classic generate never lands between its cb_reset / cb_admit
             out = self._classic_generate(inputs_embeds, max_length, do_sample, temperature, top_p, eos_token_id, pad_token_id,
                                          stopping_criteria, seed, repetition_penalty, num_beams, length_penalty, early_stopping,
-                                         top_k, on_tokens, streamer, min_new, n_samples=G, **extra)
+                                         top_k, on_tokens, streamer, min_new, n_samples=G, processors=proc, **extra)
         if streamer is not None:
             streamer.end()
         if not return_dict_in_generate:
@@ -771,6 +783,38 @@ class HipCausalLM(_EngineModule):
             fields["beam_indices"] = out["beam_indices"].to(dev)
             fields["sequences_scores"] = out["sequences_scores"].to(dev) if output_scores else None
         return generate_output(num_beams > 1, **fields)
+
+    def _processor_args(self, no_repeat_ngram_size, bad_words_ids, min_p, do_sample, eos_token_id):
+        """HF's own checks of no_repeat_ngram_size / bad_words_ids / min_p (generation/logits_process.py, transformers 4.49), then the
+        engine's limits; returns the keywords of HipEngine.generate_processed, {} when none of the three is set."""
+        n = no_repeat_ngram_size
+        if n is None:
+            n = 0
+        if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 0:
+            raise ValueError(f"`no_repeat_ngram_size` has to be an integer >= 0, but is {no_repeat_ngram_size}")
+        words = None
+        if bad_words_ids is not None:
+            if not isinstance(bad_words_ids, (list, tuple)) or len(bad_words_ids) == 0:
+                raise ValueError(f"`bad_words_ids` has to be a non-empty list, but is {bad_words_ids}.")
+            if any(not isinstance(w, (list, tuple)) or len(w) == 0 for w in bad_words_ids):
+                raise ValueError(f"`bad_words_ids` has to be a list of non-empty lists, but is {bad_words_ids}.")
+            if any(isinstance(t, bool) or not isinstance(t, numbers.Integral) or t < 0 for w in bad_words_ids for t in w):
+                raise ValueError(f"Each list in `bad_words_ids` has to be a list of positive integers, but is {bad_words_ids}.")
+            # HF drops a bad word that is exactly [eos_token_id] (NoBadWordsLogitsProcessor.__init__)
+            eos = int(self.eos_token_id if eos_token_id is None else eos_token_id)
+            words = [[int(t) for t in w] for w in bad_words_ids if [int(t) for t in w] != [eos]]
+        if min_p is not None:
+            min_p = float(min_p)
+            if not 0.0 <= min_p <= 1.0:
+                raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {min_p}")
+            if not do_sample:
+                min_p = None                    # a warper: HF builds it for sampling calls only
+        if n == 0 and words is None and min_p is None:
+            return {}
+        from .engine import logits_processors
+        vocab = getattr(getattr(self._engine, "cfg", None), "vocab", None)
+        logits_processors(n, words, min_p or 0.0, vocab=vocab)          # the limits: ValueError here, before any engine call
+        return dict(no_repeat_ngram_size=int(n), bad_words_ids=words or None, min_p=float(min_p or 0.0))
 
     def _output_slabs(self, inputs_embeds, max_length, num_beams, output_scores, output_logits, n_samples=1):
         """[max_new, rows, V] fp32 slabs for output_scores / output_logits on the engine's device, after checking they fit (the engine
@@ -819,9 +863,11 @@ class HipCausalLM(_EngineModule):
 
     def _classic_generate(self, inputs_embeds, max_length, do_sample, temperature, top_p, eos_token_id, pad_token_id,
                           stopping_criteria, seed, repetition_penalty, num_beams, length_penalty, early_stopping, top_k,
-                          on_tokens, streamer, min_new, n_samples=1, **outputs):
+                          on_tokens, streamer, min_new, n_samples=1, processors=None, **outputs):
         # (n_samples > 1: the shared call -- one prompt pass over these prompts, n_samples rows each)
         call = self._engine.generate if n_samples == 1 else functools.partial(self._engine.generate_shared, n_samples=n_samples)
+        if processors:      # no_repeat_ngram_size / bad_words_ids / min_p: the processed call (rectangular and shared prompts alike)
+            call = functools.partial(self._engine.generate_processed, n_samples=n_samples, **processors)
         return call(
             inputs_embeds.to(torch.bfloat16), max_length=int(max_length), do_sample=bool(do_sample),
             temperature=float(temperature if temperature is not None else 1.0),
