@@ -40,9 +40,30 @@ extern "C" {
  *                             32-row tiles (33..64 rows: the weights are streamed once)} */
 int  sv_debug_resample_coeffs(int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* taps, int32_t cap);
 int  sv_debug_skinny_plan(int32_t rows, int32_t N, int32_t K, int32_t splitk, int32_t fp8, int32_t* out2);
-/*   sv_debug_set_exp          the experiment bit mask of a live engine (what the environment variable SV_EXP sets at sv_create):
- *                             in-process A/B runs of the round's experiments (tools/ab_exp.py) */
+/* The A/B switches of an engine: one bit each of the mask that the environment variable SV_EXP sets at sv_create and sv_debug_set_exp sets
+ * on a live engine.  Mask 0 is the product path; every switch computes the same tokens unless its line says otherwise.
+ * The values are stable: logs under profiles/ name them by number.  star-vector_amd/engine.py mirrors the enum as the IntFlag `Exp`. */
+enum sv_exp_bits {
+    SV_EXP_NO_LN_FOLD        = 2,        /* the 7-launch decode layer where the 6-launch one (ln_2 folded into c_fc) is the default; the fold re-rounds
+                                            gamma * W, so logits move within bf16 noise (test_gpu_e2e: test_seven_launch_layer_mask_matches_the_golden) */
+    SV_EXP_MLP_FUSED_FORCE   = 128,      /* c_fc + down projection as ONE launch without exclusive_device (test_fused_mlp_launch_equals_the_two_launches_bit_for_bit) */
+    SV_EXP_MLP_FUSED_OFF     = 512,      /* never that launch (test_gpu_safety: test_continuous_batching_on_an_engine_that_owns_its_gpu_equals_solo_runs) */
+    SV_EXP_SEPARATE_ARGMAX   = 1024,     /* greedy selection as its own launch, not in the lm_head epilogue (test_folded_greedy_selection_equals_the_argmax_launch_token_for_token) */
+    SV_EXP_ROWLN_CATTN_OFF   = 8192,     /* never the row update + c_attn as one launch (test_gpu_safety, the same test as SV_EXP_MLP_FUSED_OFF) */
+    SV_EXP_ROWLN_CATTN_FORCE = 16384,    /* that launch without exclusive_device (test_row_update_and_c_attn_as_one_launch_bit_for_bit) */
+    SV_EXP_NO_PRUNE_LAST     = 32768,    /* the last prompt layer over all rows, not the last row of each sequence
+                                            (test_prompts_of_259_rows_are_batch_independent_with_the_per_sequence_remainder) */
+    SV_EXP_BATCH_REMAINDER   = 4194304,  /* big-M GEMMs peel the row remainder of the batch, not of each sequence: other kernels for those rows,
+                                            so their bits may move (the same test as SV_EXP_NO_PRUNE_LAST) */
+    SV_EXP_KNOWN = SV_EXP_NO_LN_FOLD | SV_EXP_MLP_FUSED_FORCE | SV_EXP_MLP_FUSED_OFF | SV_EXP_SEPARATE_ARGMAX | SV_EXP_ROWLN_CATTN_OFF |
+                   SV_EXP_ROWLN_CATTN_FORCE | SV_EXP_NO_PRUNE_LAST | SV_EXP_BATCH_REMAINDER
+};
+/*   sv_debug_set_exp          sets that mask on a live engine (in-process A/B runs: tools/ab_exp.py).  A mask with a bit outside SV_EXP_KNOWN
+ *                             is SV_EINVAL (the message names the bits) and leaves the engine as it was; sv_create fails the same way on such
+ *                             an SV_EXP.  A removed switch is therefore an error, never a silent comparison of the default with itself.
+ *   sv_debug_exp_known        SV_EXP_KNOWN of this build; host only, no GPU */
 int  sv_debug_set_exp(sv_engine* e, int32_t mask);
+int  sv_debug_exp_known(void);
 int  sv_debug_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t act, int32_t* out5);
 /*   sv_debug_decode_plan      what sv_create decides for a decoder Linear W [N][K] when the engine decodes `rows` (<= 64) rows at a
  *                             time on a GPU with `num_cus` CUs: out2 = {split-K factor (1 when whole_k: c_fc / lm_head keep the whole
@@ -79,8 +100,11 @@ int  sv_debug_set_col_tiles(int32_t col_tiles);
  *                             0 = gemm_skinny_mt2_kernel (both operands of the stream in registers, rounds 2-5), 1 = gemm_skinny_mt2x_kernel
  *                             (activations through a wave-private LDS ring, weights by hand-counted register loads; chunk depth by block
  *                             count: the default), 2 / 3 = that kernel's two-blocks-per-CU / one-block-per-CU form wherever the shape allows.
- *                             SV_EXP bits 131072 / 262144 / 524288 select 0 / 2 / 3 at sv_create and in sv_debug_set_exp */
+ *                             This call is the only handle on the form: it holds until the next call, across sv_create and sv_debug_set_exp
+ *                             (which used to reset it from mask bits 131072 / 262144 / 524288, now removed).
+ *   sv_debug_skinny_form      the form in force (0..3); host only */
 int  sv_debug_set_skinny_form(int32_t form);
+int  sv_debug_skinny_form(void);
 /*   sv_debug_tailsplit_launches  how many times, process-wide since the library was loaded, a decode GEMM took the tail split (gemm.hip
  *                             gemm_skinny_tailsplit_kernel: StarVector-8B's c_fc at <= 32 rows); counted on the host at launch (a captured
  *                             graph counts once, at capture).  Lets a test prove which kernel ran. */
@@ -128,7 +152,7 @@ int  sv_debug_prompt_passes(sv_engine* e, int64_t* out);
  *                        positions[b] = S for every row, or dev_lens[b] (int32 [B], <= S; NULL = S): a ragged batch
  *   sv_debug_attn_decode dev_qkv_f32 fp32 [B][n_head*head_dim + 2*n_kv*head_dim] (the new token's c_attn output, before RoPE) ->
  *                        dev_out bf16 [B][n_head*head_dim]; appends the new K/V row at positions[b]; advance != 0: positions += 1 */
-/*   sv_debug_mlp_trace   (engine created with SV_MLP_TRACE=1) 100 MHz wall-clock stamps of the fused MLP launch (SV_EXP bit 128) of the
+/*   sv_debug_mlp_trace   (engine created with SV_MLP_TRACE=1) 100 MHz wall-clock stamps of the fused MLP launch (SV_EXP_MLP_FUSED_FORCE) of the
  *                        middle layer of the last decode step: host_out [blocks][8] = {start, c_fc loop done, tile published, slice
  *                        complete, end, XCC id, 0, 0}; returns the block count or a negative error code */
 /*   sv_debug_attn_trace  (engine created with SV_ATTN_TRACE=1) the same for the decode attention launch of the middle layer: host_out

@@ -18,7 +18,7 @@ if int(_os.environ.get("WORLD_SIZE", "1") or "1") > 1 and "HSA_ENABLE_IPC_MODE_L
         print("[starvector_amd] WORLD_SIZE > 1: set HSA_ENABLE_IPC_MODE_LEGACY=0 (dmabuf IPC for RCCL)", file=_sys.stderr)
 
 from ._lib import StarVectorHipError, LIB_PATH, HEADER_PATH  # noqa: F401
-from .engine import EngineConfig, HipEngine  # noqa: F401
+from .engine import EngineConfig, Exp, HipEngine  # noqa: F401
 from .model import (  # noqa: F401
     StarVectorConfig, StarVectorForCausalLM, StarVectorStarCoder, StarVectorStarCoder2, StarCoderModel, ImageEncoder, Adapter,
     HipCausalLM, StoppingCriteriaSub, ImageTrainProcessor, SimpleStarVectorProcessor, ByteTokenizer,

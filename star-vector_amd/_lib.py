@@ -150,8 +150,10 @@ DEBUG_PROTOTYPES = {
     "sv_debug_gemm_plan": (_I, [_I, _I, _I, _I, C.POINTER(_I)]),
     "sv_debug_skinny_plan": (_I, [_I, _I, _I, _I, _I, C.POINTER(_I)]),
     "sv_debug_set_exp": (_I, [_P, _I]),
+    "sv_debug_exp_known": (_I, []),
     "sv_debug_set_col_tiles": (_I, [_I]),
     "sv_debug_set_skinny_form": (_I, [_I]),
+    "sv_debug_skinny_form": (_I, []),
     "sv_debug_tailsplit_launches": (_I, [C.POINTER(C.c_int64)]),
     "sv_debug_set_gemm_form": (_I, [_I]),
     "sv_debug_set_linear_seq_rows": (_I, [_I]),

@@ -682,9 +682,9 @@ __global__ __launch_bounds__(AD_WAVES * 64) void attn_decode_kernel(const int32_
     // block owns 4 groups, waves 4-7 carry (m, l, O) = (-inf, 0, 0) -- terms that add exactly zero, so the result is bit-identical -- and used to
     // cost half of the merge's LDS traffic (64 KiB written, every output thread reading 8 x 20 bytes instead of 4 x).  Two fully unrolled
     // instantiations (4 / 8 waves) picked by a block-uniform branch: a run-time loop bound measured SLOWER than the old form (LDS reads behind
-    // branches: +1.2 us at context 1283).  p.merge_all (SV_EXP bit 2097152) = always 8.
+    // branches: +1.2 us at context 1283).
     int nwa = (ngroups - g0 - split + act - 1) / act;
-    nwa = p.merge_all ? AD_WAVES : (nwa < 1 ? 1 : (nwa > AD_WAVES ? AD_WAVES : nwa));
+    nwa = nwa < 1 ? 1 : (nwa > AD_WAVES ? AD_WAVES : nwa);
     float l_tot = l_run + __shfl_xor(l_run, 16, 64);
     l_tot += __shfl_xor(l_tot, 32, 64);
     // each thread owns 4 consecutive outputs (same head): 16-byte stores for the partial / 8-byte for the result

@@ -428,7 +428,13 @@ extern "C" int sv_cb_step(sv_engine* e, int32_t n_steps, int32_t* n_live_out, sv
     const int Bb = cb_bucket(e);
     hipGraphExec_t gexec = nullptr;
     int per_launch = 1;
-    if (getenv("SV_NO_GRAPH") == nullptr) {
+    const auto one_step = [&]() {
+        decode_forward(e, Bb, st);
+        CbStepArgs a;
+        cb_step_args(e, a, nullptr);
+        launch_cb_step(a, Bb, st);
+    };
+    if (graph_enabled()) {
         // one graph per (bucket, steps per launch), kept for the life of the engine: every argument is engine-owned.  The scheduler asks for the same
         // n_steps call after call, so the whole call is ONE graph of n_steps copies of the step (engine_generate.hip: the GPU idles 8.6 us between two
         // graph launches and not at all between two kernels of one graph); key = bucket + 1024 * copies (0: the one-step graph).
@@ -438,45 +444,20 @@ extern "C" int sv_cb_step(sv_engine* e, int32_t n_steps, int32_t* n_live_out, sv
             if (it != e->cb_graphs.end()) { *out = it->second.second; return 0; }
             hipGraph_t g = nullptr;
             hipGraphExec_t ge = nullptr;
-            hipError_t ce = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed);
-            if (ce == hipSuccess) {
-                for (int u = 0; u < copies; ++u) {
-                    decode_forward(e, Bb, st);
-                    CbStepArgs a;
-                    cb_step_args(e, a, nullptr);
-                    launch_cb_step(a, Bb, st);
-                }
-                ce = hipStreamEndCapture(st, &g);
-                if (ce == hipSuccess && g) ce = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-            }
-            if (ce != hipSuccess) {
-                (void)hipGetLastError();
-                if (ge) (void)hipGraphExecDestroy(ge);
-                if (g) (void)hipGraphDestroy(g);
-                if (getenv("SV_REQUIRE_GRAPH")) return fail(SV_EHIP, "hipGraph capture failed: %s", hipGetErrorString(ce));
-                *out = nullptr;
-                return 0;
-            }
-            e->cb_graphs[key] = {g, ge};
+            SVCHECK(capture_steps(st, copies, one_step, &g, &ge));
+            if (ge) e->cb_graphs[key] = {g, ge};
             *out = ge;
             return 0;
         };
-        static const int cap = getenv("SV_GRAPH_STEPS") ? atoi(getenv("SV_GRAPH_STEPS")) : 32;
-        if (n_steps >= 2 && n_steps <= cap) {
+        if (n_steps >= 2 && n_steps <= graph_steps_cap()) {
             SVCHECK(capture(n_steps, &gexec));
             if (gexec) per_launch = n_steps;
         }
         if (!gexec) SVCHECK(capture(1, &gexec));
     }
     for (int i = 0; i < n_steps; i += per_launch) {
-        if (gexec) {
-            HIPCHECK(hipGraphLaunch(gexec, st));
-        } else {
-            decode_forward(e, Bb, st);
-            CbStepArgs a;
-            cb_step_args(e, a, nullptr);
-            launch_cb_step(a, Bb, st);
-        }
+        if (gexec) HIPCHECK(hipGraphLaunch(gexec, st));
+        else one_step();
     }
     // the live count and the give-up / non-finite flag in one round trip
     HIPCHECK(hipMemcpyAsync(&e->h_flags[3], e->cb_nlive, sizeof(int32_t), hipMemcpyDeviceToHost, st));

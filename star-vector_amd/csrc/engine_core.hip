@@ -133,6 +133,38 @@ int dev_alloc(sv_engine* e, void** p, size_t bytes, bool zero) {
     e->allocs.push_back(*p);
     return 0;
 }
+
+int check_exp_mask(int mask, const char* who) {
+    const unsigned bad = (unsigned)mask & ~(unsigned)SV_EXP_KNOWN;
+    if (!bad) return 0;
+    std::string bits;
+    for (unsigned b = 1; b; b <<= 1)
+        if (bad & b) bits += (bits.empty() ? "" : " ") + std::to_string(b);
+    return fail(SV_EINVAL, "%s: mask %d has bits that are no switch of this build: %s (the switches: sv_exp_bits in starvector_hip_debug.h)", who, mask,
+                bits.c_str());
+}
+
+bool graph_enabled() { return getenv("SV_NO_GRAPH") == nullptr; }
+int graph_steps_cap() {
+    static const char* const v = getenv("SV_GRAPH_STEPS");
+    static const int cap = v ? atoi(v) : 32;
+    return cap;
+}
+int capture_steps(hipStream_t st, int copies, const std::function<void()>& one_step, hipGraph_t* g, hipGraphExec_t* ge, bool required) {
+    *g = nullptr; *ge = nullptr;
+    hipError_t ce = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed);
+    if (ce == hipSuccess) {
+        for (int u = 0; u < copies; ++u) one_step();
+        ce = hipStreamEndCapture(st, g);
+        if (ce == hipSuccess) ce = *g ? hipGraphInstantiate(ge, *g, nullptr, nullptr, 0) : hipErrorUnknown;
+    }
+    if (ce == hipSuccess && *ge) return 0;
+    (void)hipGetLastError();
+    if (*ge) { (void)hipGraphExecDestroy(*ge); *ge = nullptr; }
+    if (*g) { (void)hipGraphDestroy(*g); *g = nullptr; }
+    if (required && getenv("SV_REQUIRE_GRAPH")) return fail(SV_EHIP, "hipGraph capture failed: %s", hipGetErrorString(ce));
+    return 0;
+}
 }  // namespace sveng
 
 static void reg_linear(sv_engine* e, const std::string& base, Linear* l, int N, int K, int Kalign, bool has_bias) {
@@ -165,12 +197,11 @@ static void reg_ln(sv_engine* e, const std::string& base, LNp* ln, size_t n) {
 // the time is ceil(NT * s / #CU) rounds of one block, i.e. the busiest CU's share -- NOT the average (8B down-projection at
 // split 2: 288 blocks = one full round + 32 blocks at 2 x 590 KB per busy CU: 45.8 us measured against 31 us for the bytes).
 // Pick the s <= 8 (the slab buffer and the consumers' limit) with the best fill, preferring fewer slabs on near-ties; each
-// block keeps >= 16 k-steps so that its 8 waves still have a stream to pipeline.  `legacy` = the round 1-2 rule (smallest
-// power of two that reaches one block per CU) kept for the A/B mask.
-static int pick_splitk(int n_tiles, int KS, int num_cus, bool fp8, bool legacy) {
+// block keeps >= 16 k-steps so that its 8 waves still have a stream to pipeline.
+static int pick_splitk(int n_tiles, int KS, int num_cus, bool fp8) {
     // small GEMMs (StarVector-1B's c_attn / attention c_proj: < 40 KB per CU) are one latency-bound round trip per wave: the fill
-    // model does not describe them, and more slabs only cost their consumer -> the old rule
-    if (legacy || (long)n_tiles * KS < 24L * 1024) {
+    // model does not describe them, and more slabs only cost their consumer -> the smallest power of two that reaches one block per CU
+    if ((long)n_tiles * KS < 24L * 1024) {
         int want = (256 + n_tiles - 1) / n_tiles;
         int s = 1;
         while (s < want && s < 8) s <<= 1;
@@ -197,11 +228,11 @@ static int pick_splitk(int n_tiles, int KS, int num_cus, bool fp8, bool legacy) 
 // of L2 and the L2 -> CU side bounds the launch (tools/diag/mem_mix.hip), so a block may carry two or three column tiles per loaded
 // activation fragment.  (column tiles per block, split-K) are picked together: modelled time = the busiest CU's bytes (weights + activations
 // over its blocks) relative to an even spread, plus the slab cost.  Only shapes the two-row-tile kernel takes are candidates.
-void sveng::pick_decode_plan(const Linear& l, int MT, int num_cus, bool fp8, bool legacy, bool whole_k, int* splitk, int* col_tiles) {
+void sveng::pick_decode_plan(const Linear& l, int MT, int num_cus, bool fp8, bool whole_k, int* splitk, int* col_tiles) {
     const int tiles = l.Npad / 32, KS = l.Kpad / 16;
     *col_tiles = 1;
-    if (MT != 2 || legacy || (long)tiles * KS < 24L * 1024) {
-        *splitk = whole_k ? 1 : pick_splitk(tiles, KS, num_cus, fp8, legacy);
+    if (MT != 2 || (long)tiles * KS < 24L * 1024) {
+        *splitk = whole_k ? 1 : pick_splitk(tiles, KS, num_cus, fp8);
         return;
     }
     const double wb = fp8 ? 512.0 : 1024.0, ab = 1024.0 * MT;
@@ -221,7 +252,7 @@ void sveng::pick_decode_plan(const Linear& l, int MT, int num_cus, bool fp8, boo
             const double cost = (double)rounds * per * (nt * wb + ab) / ideal + 0.015 * s;
             if (cost < best_cost - 1e-9) { best_cost = cost; best_s = s; best_nt = nt; }
         }
-    if (!best_s) { *splitk = whole_k ? 1 : pick_splitk(tiles, KS, num_cus, fp8, legacy); return; }
+    if (!best_s) { *splitk = whole_k ? 1 : pick_splitk(tiles, KS, num_cus, fp8); return; }
     *splitk = best_s;
     *col_tiles = best_nt;
 }
@@ -366,6 +397,8 @@ extern "C" int sv_create(const sv_config* cfg, sv_engine** out) {
         return fail(SV_EINVAL, "sliding_window must be >= 0 (and 0 for the GPTBigCode decoder)");
     if (c.max_batch < 1 || c.max_seq_len < 2 || c.max_seq_len > c.n_positions)
         return fail(SV_EINVAL, "bad max_batch / max_seq_len");
+    const int exp = getenv("SV_EXP") ? atoi(getenv("SV_EXP")) : 0;          // checked here, in front of every allocation
+    SVCHECK(check_exp_mask(exp, "sv_create (SV_EXP)"));
     hipError_t r = hipSetDevice(c.device);
     if (r != hipSuccess) return fail(SV_EHIP, "hipSetDevice(%d): %s", c.device, hipGetErrorString(r));
 
@@ -375,6 +408,7 @@ extern "C" int sv_create(const sv_config* cfg, sv_engine** out) {
 
     sv_engine* e = new sv_engine();
     e->cfg = c;
+    e->exp = exp;
     e->vdh = vdh; e->dh = dh; e->v2 = v2; e->nkv = nkv;
     const int G = c.image_size / c.patch_size;
     e->NP = G * G; e->T = e->NP + (v2 ? 0 : 1);
@@ -445,16 +479,15 @@ extern "C" int sv_create(const sv_config* cfg, sv_engine** out) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, c.device) == hipSuccess && prop.multiProcessorCount > 0) e->num_cus = prop.multiProcessorCount;
         const bool fp8 = c.weight_dtype == SV_WEIGHT_FP8_E4M3;
-        const bool legacy = getenv("SV_EXP") && (atoi(getenv("SV_EXP")) & 8);          // A/B: the round 1-2 split rule
         if (fp8) e->lm_head.fp8 = true;                  // decoder Linears + lm_head stream as fp8 at decode time
-        { int sk1 = 1; pick_decode_plan(e->lm_head, (c.max_batch + 31) / 32, e->num_cus, fp8, legacy, true, &sk1, &e->lm_head.col_tiles); }
+        { int sk1 = 1; pick_decode_plan(e->lm_head, (c.max_batch + 31) / 32, e->num_cus, fp8, true, &sk1, &e->lm_head.col_tiles); }
         const bool plan_log = getenv("SV_GEMM_AUTOTUNE_LOG") && atoi(getenv("SV_GEMM_AUTOTUNE_LOG"));
         for (DecLayer& L : e->dec) {
             Linear* ls[4] = {&L.c_attn, &L.c_proj, &L.c_fc, &L.c_proj2};
             for (Linear* l : ls) {
                 l->fp8 = fp8;
                 const int KS = l->Kpad / 16;
-                pick_decode_plan(*l, (c.max_batch + 31) / 32, e->num_cus, fp8, legacy, l == &L.c_fc, &l->splitk, &l->col_tiles);
+                pick_decode_plan(*l, (c.max_batch + 31) / 32, e->num_cus, fp8, l == &L.c_fc, &l->splitk, &l->col_tiles);
                 if (fp8) {
                     // the fp8 kernel wants an even number (>= 2 per wave pair) of k-steps per wave: shrink split-K until it fits
                     while (l->splitk > 1 && (KS % l->splitk != 0 || (KS / l->splitk) % 4 != 0)) --l->splitk;
@@ -582,19 +615,16 @@ extern "C" int sv_create(const sv_config* cfg, sv_engine** out) {
                     hipMemcpy(e->rope_sin, hs.data(), hs.size() * 4, hipMemcpyHostToDevice) != hipSuccess))
             rc = fail(SV_EHIP, "rope table upload failed");
     }
-    if (getenv("SV_EXP")) e->exp = atoi(getenv("SV_EXP"));
-    set_mt2x((e->exp & 131072) ? 0 : (e->exp & 262144) ? 2 : (e->exp & 524288) ? 3 : 1);      // 33..64-row decode GEMM form (process-wide: gemm.hip g_mt2x)
     if (!rc && getenv("SV_ATTN_TRACE")) rc = dalloc(e, &e->attn_trace, R * (size_t)nkv * 16 * 16);
-    // 6 launches per layer (decode_cols.hip): bf16 weights, at most one 32-row tile per launch; SV_EXP bit 2 = A/B, the 7-launch layer.
+    // 6 launches per layer (decode_cols.hip): bf16 weights, at most one 32-row tile per launch; SV_EXP_NO_LN_FOLD = A/B, the 7-launch layer.
     // Hidden sizes above 2048 keep the 7-launch layer: every block of the whole-K projection re-reads 32 x K activations from L2,
     // and at StarVector-8B's K = 4608 that costs what the removed row update saves (16 columns per block: 4227 vs 4178 us per
-    // step; 18 columns = 256 blocks: 3933 vs 3932, profiles/fold6_r03_8b_ab.log); SV_EXP bit 4 = A/B, the 6-launch layer at any size.
-    e->fold6 = c.weight_dtype == SV_WEIGHT_BF16 && e->MT == 1 && (c.n_head * dh) % 32 == 0 && D % 32 == 0 &&
-               (c.n_head * dh <= 2048 || (e->exp & 4));
+    // step; 18 columns = 256 blocks: 3933 vs 3932, profiles/fold6_r03_8b_ab.log).
+    e->fold6 = c.weight_dtype == SV_WEIGHT_BF16 && e->MT == 1 && (c.n_head * dh) % 32 == 0 && D % 32 == 0 && c.n_head * dh <= 2048;
     if (!rc && e->fold6) {
         const int cpb = cols_pick_cpb(D, c.n_head * dh);
         for (DecLayer& L : e->dec) L.c_proj.cpb = cpb;
-        // the fused MLP launch (SV_EXP bit 128) needs its F / 32 blocks resident at once (one 8-wave block per CU) and the exact
+        // the fused MLP launch (SV_EXP_MLP_FUSED_FORCE) needs its F / 32 blocks resident at once (one 8-wave block per CU) and the exact
         // (tile, K slice) geometry of the two kernels it replaces: 16 k-steps per wave in both phases
         const Linear& fc = e->dec[0].c_fc; const Linear& dn = e->dec[0].c_proj2;
         const int T1 = fc.Npad / 32;

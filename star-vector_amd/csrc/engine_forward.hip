@@ -38,8 +38,8 @@ static void gemm(sv_engine* e, int kind, const bf16_t* A, int lda, const Linear&
     g.A = A; g.lda = lda; g.Wp = l.Wp; g.bias = l.bias; g.R = R; g.ldr = ldr; g.C = C; g.ldc = ldc;
     g.M = M; g.N = l.N; g.K = l.Kpad; g.act = act; g.out_f32 = out_f32;
     g.cscale = l.fp8 ? l.wscale : nullptr;
-    g.seq_rows = (e->exp & 4194304) ? 0 : seq_rows;          // SV_EXP bit 4194304: A/B, the batch-level remainder of rounds 2-5
-    g.splitk_rows = (e->exp & 4194304) ? 0 : last_rows;
+    g.seq_rows = (e->exp & SV_EXP_BATCH_REMAINDER) ? 0 : seq_rows;          // A/B: the batch-level remainder of rounds 2-5
+    g.splitk_rows = (e->exp & SV_EXP_BATCH_REMAINDER) ? 0 : last_rows;
     g.tune_in_place = tune_in_place;
     launch_gemm(g, st);
 }
@@ -74,9 +74,7 @@ static int attn_max_splits(const sv_engine* e) { return attn_max_splits_of(e->cf
 int sveng::attn_groups_per_block_of(int max_batch, int nkv, int num_cus) {
     return (max_batch < 64 ? max_batch : 64) * nkv >= num_cus ? 8 : 4;
 }
-static int attn_groups_per_block(const sv_engine* e) {
-    return (e->exp & 64) ? 4 : attn_groups_per_block_of(e->cfg.max_batch, e->nkv, e->num_cus);       // SV_EXP bit 64: A/B, always 4
-}
+static int attn_groups_per_block(const sv_engine* e) { return attn_groups_per_block_of(e->cfg.max_batch, e->nkv, e->num_cus); }
 
 static int vision_forward(sv_engine* e, const bf16_t* img, int B, bf16_t* out, hipStream_t st) {
     const sv_config& c = e->cfg;
@@ -176,8 +174,8 @@ int sveng::assign_pages(sv_engine* e, int B, int total_len, hipStream_t st) {
 //  sv_generate call of bench.py: a stale line of the buffer in some XCD's L2.)
 static bool rc_enabled(const sv_engine* e) {
     // the 6-launch layer (fold6: residual stream in fragment order) or the 7-launch layer of the wide model (row-major residual stream)
-    const bool layer_ok = e->fold6 ? (e->fold_ready && !(e->exp & 2)) : e->cfg.hidden > 2048;
-    return layer_ok && e->rc_fused_ok && !(e->exp & 8192) && (e->cfg.exclusive_device || (e->exp & 16384)) && !e->fused_off;
+    const bool layer_ok = e->fold6 ? (e->fold_ready && !(e->exp & SV_EXP_NO_LN_FOLD)) : e->cfg.hidden > 2048;
+    return layer_ok && e->rc_fused_ok && !(e->exp & SV_EXP_ROWLN_CATTN_OFF) && (e->cfg.exclusive_device || (e->exp & SV_EXP_ROWLN_CATTN_FORCE)) && !e->fused_off;
 }
 // the lm_head launch stores the pattern 16 bytes per thread from its first blocks: its grid must cover the buffer (a tiny-vocabulary
 // configuration would arm only part of it: then layer 0 of the next step takes the two launches)
@@ -219,8 +217,8 @@ int sveng::prefill_forward(sv_engine* e, const bf16_t* embeds, int B, int S0, hi
     // the last prompt row, which alone feeds ln_f + lm_head.  So after its attention only the last row of every sequence goes on:
     // attention over the last query tile, then c_proj / ln_2 / c_fc / down-proj on B rows instead of B * S0 (HF computes all rows and
     // reads logits[:, -1]; a row's GEMM / attention result does not depend on the rows around it: bit-identical, test_gpu_e2e.py).
-    // SV_EXP bit 32768 = off (A/B).
-    const bool prune_last = n_keep == 0 && S0 >= 2 && !(e->exp & 32768);
+    // SV_EXP_NO_PRUNE_LAST = off (A/B).
+    const bool prune_last = n_keep == 0 && S0 >= 2 && !(e->exp & SV_EXP_NO_PRUNE_LAST);
     // the last prompt row may be one of the rows its sequence leaves over its 256-row tiles: the launcher gives it the kernel it takes in the full layers
     for (int i = 0; i < c.n_layer; ++i) {
         DecLayer& L = e->dec[i];
@@ -422,7 +420,7 @@ int sveng::prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, con
     ragged_blocks(lens, B, 32, false, kb);
     const Linear* proj[4] = {&e->dec[0].c_attn, &e->dec[0].c_proj, &e->dec[0].c_fc, &e->dec[0].c_proj2};
     const int acts[4] = {ACT_NONE, ACT_NONE, ACT_GELU_TANH, ACT_NONE};
-    if (!(e->exp & 4194304))            // SV_EXP bit 4194304: no per-sequence remainder (as in the rectangular pass)
+    if (!(e->exp & SV_EXP_BATCH_REMAINDER))            // set: no per-sequence remainder (as in the rectangular pass)
         for (int i = 0; i < 4; ++i) ragged_gemm_rows(lens, B, proj[i]->N, proj[i]->Kpad, acts[i], rows[i], last[i]);
     size_t need = (size_t)2 * B + ab.size() + al.size() + kb.size();
     for (int i = 0; i < 4; ++i) need += rows[i].size() + last[i].size();
@@ -471,7 +469,7 @@ int sveng::prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, con
     at.kv_group = c.n_head / nkv; at.causal = 1; at.scale = 1.0f / sqrtf((float)dh);
     at.window = c.sliding_window > 0 ? c.sliding_window : 0;
     at.rag_seq = d_seq;
-    const bool prune_last = !(e->exp & 32768);
+    const bool prune_last = !(e->exp & SV_EXP_NO_PRUNE_LAST);
     for (int i = 0; i < c.n_layer; ++i) {
         DecLayer& L = e->dec[i];
         prof_mark(e, PK_PF_ROWS, st);
@@ -535,7 +533,6 @@ void sveng::attn_decode_args(sv_engine* e, int layer, int B, const float* ws, in
     ad.max_splits = attn_max_splits(e);
     ad.groups_per_block = attn_groups_per_block(e);
     ad.n_kv = e->nkv; ad.kv_head_stride = e->kv_head_stride; ad.rope_cos = e->rope_cos; ad.rope_sin = e->rope_sin;
-    ad.merge_all = (e->exp & 2097152) ? 1 : 0;
 }
 
 // One autoregressive step: consumes cur_tok / positions, leaves logits in e->logits.  6 launches per layer + 2 (bf16 weights,
@@ -552,9 +549,9 @@ void sveng::decode_forward(sv_engine* e, int B, hipStream_t st) {
     float* wsB = e->ws2;
     RowUpdateArgs ru;
     memset(&ru, 0, sizeof(ru));
-    const bool fold6 = e->fold6 && e->fold_ready && !(e->exp & 2);
+    const bool fold6 = e->fold6 && e->fold_ready && !(e->exp & SV_EXP_NO_LN_FOLD);
     // Row update + c_attn as ONE launch (rowops.hip rowln_cattn_kernel): on when the engine owns its GPU (like the fused MLP launch: its
-    // blocks wait for blocks of the same launch); SV_EXP bit 8192 = off, 16384 = on without exclusive_device (A/B).  The GEMM blocks
+    // blocks wait for blocks of the same launch); SV_EXP_ROWLN_CATTN_OFF = off, SV_EXP_ROWLN_CATTN_FORCE = on without exclusive_device (A/B).  The GEMM blocks
     // recognise unwritten activations by the 0xFFFF'FFFF pattern: xp_a gets it from the lm_head launch of the step (or prompt pass) before
     // (layer 0) and from the attention launch of layer i for layer i + 1 -- which must have room for it: 16 bytes per thread of its grid
     // (B >= 10 at StarVector-1B's shapes).  Not inside the profiling legs (they time the row updates and the GEMMs apart).  A call that
@@ -591,8 +588,8 @@ void sveng::decode_forward(sv_engine* e, int B, hipStream_t st) {
             a.splitk = l.splitk; a.ws = ws; a.ldws = e->ldws;
             const int NT = l.Npad / 32;
             // XCD-aware (tile, K slice) assignment: every XCD pulls one K slice of the activations into its L2, not all of them
-            // (profiles/skinny_r03_xcd_slice_remap_ab.log: 1121 -> 1110 us per step, tokens identical); SV_EXP bit 16 = off (A/B)
-            a.xcd_remap = (!(e->exp & 16) && MT == 1 && l.splitk > 1 && 8 % l.splitk == 0 && (NT * l.splitk) % 8 == 0 &&
+            // (profiles/skinny_r03_xcd_slice_remap_ab.log: 1121 -> 1110 us per step, tokens identical)
+            a.xcd_remap = (MT == 1 && l.splitk > 1 && 8 % l.splitk == 0 && (NT * l.splitk) % 8 == 0 &&
                            NT % (8 / l.splitk) == 0) ? 1 : 0;
         }
         else if (out_mode == SK_OUT_PACKED_ACT) { a.splitk = 1; a.bias = l.bias; a.act = ACT_GELU_TANH; a.out_xp = e->xp_mlp; a.out_KS = F / 16;
@@ -629,10 +626,10 @@ void sveng::decode_forward(sv_engine* e, int B, hipStream_t st) {
             ru.xp_out = xp_ln;
         }
         // c_fc + down projection in ONE launch (gemm.hip mlp_fused_kernel): on when the engine owns its GPU (sv_config.exclusive_device);
-        // SV_EXP bit 128 forces it on, bit 512 off (in-process A/B, tools/ab_exp.py).  It recognises unwritten activations by a pattern
+        // SV_EXP_MLP_FUSED_FORCE forces it on, SV_EXP_MLP_FUSED_OFF off (in-process A/B, tools/ab_exp.py).  It recognises unwritten activations by a pattern
         // that an EARLIER launch of the layer leaves in the buffer: the attention launch (16 bytes per thread: free in a latency-bound
         // kernel), or -- grid too small, or the profiling leg without attention -- the projection kernel (+0.5 us there)
-        const bool fused = fold6 && e->mlp_fused_ok && !(e->exp & 512) && (c.exclusive_device || (e->exp & 128)) && !e->fused_off;
+        const bool fused = fold6 && e->mlp_fused_ok && !(e->exp & SV_EXP_MLP_FUSED_OFF) && (c.exclusive_device || (e->exp & SV_EXP_MLP_FUSED_FORCE)) && !e->fused_off;
         const size_t pat_bytes = (size_t)(F / 16) * 1024;
         const size_t poison_cap = (size_t)B * e->nkv * attn_max_splits(e) * 512 * 16;      // 16 bytes per thread of the attention launch
         const bool attn_poisons = fused && !e->only_skinny && pat_bytes + (rc ? xpa_bytes : 0u) <= poison_cap;

@@ -153,21 +153,8 @@ static int generate_beam(sv_engine* e, const void* dev_embeds, int B, int S0, co
     const int chunk = sp->sync_every > 0 ? sp->sync_every : 32;
     hipGraph_t graph = nullptr;
     hipGraphExec_t gexec = nullptr;
-    if (!e->h_flags[0] && getenv("SV_NO_GRAPH") == nullptr) {
-        hipError_t ce = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed);
-        if (ce == hipSuccess) {
-            decode_forward(e, R, st);
-            beam_step(e, kv, 1, st);
-            ce = hipStreamEndCapture(st, &graph);
-            if (ce == hipSuccess && graph) ce = hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0);
-        }
-        if (ce != hipSuccess) {
-            (void)hipGetLastError();
-            if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
-            if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }
-            if (getenv("SV_REQUIRE_GRAPH")) return fail(SV_EHIP, "hipGraph capture failed: %s", hipGetErrorString(ce));
-        }
-    }
+    if (!e->h_flags[0] && graph_enabled())
+        SVCHECK(capture_steps(st, 1, [&]() { decode_forward(e, R, st); beam_step(e, kv, 1, st); }, &graph, &gexec));
     while (!e->h_flags[0]) {
         int n = max_new - 1 - steps;
         if (n <= 0) break;
@@ -255,7 +242,7 @@ int sveng::report_bad_logits(sv_engine* e, hipStream_t st, const char* who, int 
     if (what == 3 || what == 4)
         return fail(SV_EHIP, "%s: a block of a fused decode launch (code %d: 3 = MLP pair, 4 = row update + c_attn) gave up waiting for its producers (its blocks were not all resident at "
                              "once?  another process or engine on this GPU?); the tokens of this call are void -- create the engine with "
-                             "exclusive_device = 0 (SV_EXP bit 512) there", who, what);
+                             "exclusive_device = 0 (SV_EXP_MLP_FUSED_OFF) there", who, what);
     {
         int32_t stepv = -1;
         (void)hipMemcpy(&stepv, e->d_step, sizeof(stepv), hipMemcpyDeviceToHost);
@@ -546,7 +533,7 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t Bp, in
     }
     // Plain greedy decode (no repetition penalty, no min_length hold, one row tile, bf16 lm_head with the K split over the waves of a
     // block): the selection rides in the lm_head epilogue of every decode step -- one launch less per step, same tokens bit for bit.
-    // SV_EXP bit 1024 = the separate argmax launch (A/B).
+    // SV_EXP_SEPARATE_ARGMAX = the separate argmax launch (A/B).
     bool fused_sel = false;
     {
         int waves = 1, two = 0;
@@ -555,7 +542,7 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t Bp, in
         // a capturing call (sv_generate_ex) takes the separate selection launch: the capture must read the logits row between the lm_head and
         // the selection, and the tokens are bit-identical either way (tests/test_gpu_e2e.py)
         // (a ban rewrites the logits row between the lm_head and the selection: the separate launch as well)
-        fused_sel = !sp->do_sample && !pen && sp->min_new_tokens <= 0 && B <= 32 && !e->lm_head.fp8 && waves > 1 && !two && !(e->exp & 1024) &&
+        fused_sel = !sp->do_sample && !pen && sp->min_new_tokens <= 0 && B <= 32 && !e->lm_head.fp8 && waves > 1 && !two && !(e->exp & SV_EXP_SEPARATE_ARGMAX) &&
                     !e->cap_on && !ban;
     }
     // generation state, one launch: positions = S0 - 1 (finish_step adds 1), unfinished = 1, {step, done, n_emitted} = 0, the folded selection's key slots = 0
@@ -599,8 +586,9 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t Bp, in
         streamed = n_cols_final;
         return 0;
     };
-    const bool use_graph = getenv("SV_NO_GRAPH") == nullptr;
+    const bool use_graph = graph_enabled();
     hipGraphExec_t gexec = nullptr;
+    const auto one_step = [&]() { decode_forward(e, B, st); sample_and_finish(e, B, *sp, max_new, st, fused_sel); };
     auto drop_multi = [&]() {
         if (e->gen_gexec_multi) { (void)hipGraphExecDestroy(e->gen_gexec_multi); e->gen_gexec_multi = nullptr; }
         if (e->gen_graph_multi) { (void)hipGraphDestroy(e->gen_graph_multi); e->gen_graph_multi = nullptr; }
@@ -627,19 +615,8 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t Bp, in
             if (e->gen_graph) { (void)hipGraphDestroy(e->gen_graph); e->gen_graph = nullptr; }
             drop_multi();
             e->gen_graph_key.clear();
-            hipError_t ce = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed);
-            if (ce == hipSuccess) {
-                decode_forward(e, B, st);
-                sample_and_finish(e, B, *sp, max_new, st, fused_sel);
-                ce = hipStreamEndCapture(st, &e->gen_graph);
-                if (ce == hipSuccess && e->gen_graph) ce = hipGraphInstantiate(&e->gen_gexec, e->gen_graph, nullptr, nullptr, 0);
-            }
-            if (ce != hipSuccess) {          // fall back to plain launches of the SAME kernels
-                (void)hipGetLastError();
-                if (e->gen_gexec) { (void)hipGraphExecDestroy(e->gen_gexec); e->gen_gexec = nullptr; }
-                if (e->gen_graph) { (void)hipGraphDestroy(e->gen_graph); e->gen_graph = nullptr; }
-                if (getenv("SV_REQUIRE_GRAPH")) return fail(SV_EHIP, "hipGraph capture failed: %s", hipGetErrorString(ce));
-            } else {
+            SVCHECK(capture_steps(st, 1, one_step, &e->gen_graph, &e->gen_gexec));
+            if (e->gen_gexec) {              // (else: plain launches of the SAME kernels)
                 e->gen_graph_key = key;
                 gexec = e->gen_gexec;
                 size_t nn = 0;                     // sv_debug_step_plan: the step's launches, counted on the captured graph itself
@@ -666,24 +643,15 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t Bp, in
     hipGraphExec_t gexec_multi = nullptr;
     int U = 0;
     if (gexec) {
-        static const int cap = getenv("SV_GRAPH_STEPS") ? atoi(getenv("SV_GRAPH_STEPS")) : 32;
-        U = chunk < cap ? chunk : cap;
+        U = chunk < graph_steps_cap() ? chunk : graph_steps_cap();
         if (U >= 2 && max_new - 1 >= 4 * U) {
             if (e->gen_gexec_multi && e->gen_multi_steps == U) {
                 gexec_multi = e->gen_gexec_multi;
             } else {
                 drop_multi();
-                hipError_t ce = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed);
-                if (ce == hipSuccess) {
-                    for (int u = 0; u < U; ++u) {
-                        decode_forward(e, B, st);
-                        sample_and_finish(e, B, *sp, max_new, st, fused_sel);
-                    }
-                    ce = hipStreamEndCapture(st, &e->gen_graph_multi);
-                    if (ce == hipSuccess && e->gen_graph_multi) ce = hipGraphInstantiate(&e->gen_gexec_multi, e->gen_graph_multi, nullptr, nullptr, 0);
-                }
-                if (ce != hipSuccess || !e->gen_gexec_multi) { (void)hipGetLastError(); drop_multi(); }      // the one-step graph carries the call
-                else { e->gen_multi_steps = U; gexec_multi = e->gen_gexec_multi; }
+                // (not required: on a failure the one-step graph carries the call, whatever SV_REQUIRE_GRAPH says)
+                (void)capture_steps(st, U, one_step, &e->gen_graph_multi, &e->gen_gexec_multi, false);
+                if (e->gen_gexec_multi) { e->gen_multi_steps = U; gexec_multi = e->gen_gexec_multi; }
             }
         }
     }

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -129,17 +130,7 @@ struct sv_engine {
     long long* mlp_trace = nullptr; // SV_MLP_TRACE=1: wall-clock stamps of the LAST fused MLP launch, [F / 32][8] (sv_debug_mlp_trace)
     bool only_skinny = false;       // profiling: enqueue only the weight-streaming GEMMs of a step
     bool skip_skinny = false;       // profiling: enqueue everything BUT the weight-streaming GEMMs
-    int exp = 0;                    // SV_EXP bit mask, read once at sv_create (A/B switches of the round's experiments):
-                                    //   2 the 7-launch layer (no LayerNorm fold);
-                                    //   (1: was the row update as one wave per row: 0.218 vs 0.131 ms per step, removed)
-                                    //   8 (at sv_create only) the round 1-2 split-K rule of the decode GEMMs
-                                    //   8192 / 16384 (round 5) the row update and c_attn as ONE launch (rowln_cattn_kernel) forced off / on; default: on iff exclusive_device
-                                    //   1024 (round 5) greedy selection as its own launch again (argmax_kernel), not folded into the lm_head epilogue
-                                    //   128 / 512 (round 4) the MLP half of a layer as ONE launch (mlp_fused_kernel) forced on / off; default:
-                                    //       on iff sv_config.exclusive_device
-                                    //   (16 / 32 / 64: 2 / 6 / 8 key groups per attention block: 1186 / 1169 / 1175 vs 1171 us, removed)
-                                    //   (1, 2: XCD-aligned weight prefetch by attention's idle waves / spare row-update blocks; 4: one key
-                                    //    group per attention block -- all measured slower, profiles/prefetch_r03_*.log, removed)
+    int exp = 0;                    // A/B switches: a mask of sv_exp_bits (include/starvector_hip_debug.h), from SV_EXP at sv_create or sv_debug_set_exp
     float *ws = nullptr, *ws2 = nullptr, *logits = nullptr, *sample_scratch = nullptr, *attn_part = nullptr;
     unsigned* attn_cnt = nullptr;
     float* am_val = nullptr; int32_t* am_idx = nullptr;
@@ -256,7 +247,14 @@ template <typename T>
 inline int dalloc(sv_engine* e, T** p, size_t count, bool zero = true) {
     return dev_alloc(e, reinterpret_cast<void**>(p), count * sizeof(T), zero);
 }
-void pick_decode_plan(const Linear& l, int MT, int num_cus, bool fp8, bool legacy, bool whole_k, int* splitk, int* col_tiles);
+void pick_decode_plan(const Linear& l, int MT, int num_cus, bool fp8, bool whole_k, int* splitk, int* col_tiles);
+int check_exp_mask(int mask, const char* who);      // SV_EINVAL (naming the bits) unless mask is a subset of SV_EXP_KNOWN
+// hipGraph capture of decode steps, shared by sv_generate (greedy and beam) and sv_cb_step.  capture_steps: relaxed capture of `copies` calls of
+// one_step on `st` -> *g, instantiated -> *ge.  On failure the sticky HIP error is cleared, both handles are destroyed and nulled, and the
+// result is SV_EHIP if `required` and SV_REQUIRE_GRAPH is set, else 0 with *ge == nullptr: the caller runs plain launches of the same kernels.
+bool graph_enabled();       // SV_NO_GRAPH unset (read per call: the tests switch it inside one process)
+int graph_steps_cap();      // SV_GRAPH_STEPS (read once per process), 32 by default: most steps in one graph
+int capture_steps(hipStream_t st, int copies, const std::function<void()>& one_step, hipGraph_t* g, hipGraphExec_t* ge, bool required = true);
 // engine_forward.hip: the op graphs
 void prof_mark(sv_engine* e, int kind, hipStream_t st);
 int attn_max_splits_of(int max_batch, int nkv, int num_cus);

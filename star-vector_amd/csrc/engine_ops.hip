@@ -20,9 +20,9 @@ struct TmpBufs {
 // A/B tool surface (tools/ab_exp.py): change the experiment mask of a live engine; captured graphs are keyed on it
 extern "C" int sv_debug_set_exp(sv_engine* e, int32_t mask) {
     if (!e) return fail(SV_EINVAL, "null engine");
+    SVCHECK(check_exp_mask(mask, "sv_debug_set_exp"));
     std::lock_guard<std::mutex> lk(e->mu);
     e->exp = mask;
-    set_mt2x((mask & 131072) ? 0 : (mask & 262144) ? 2 : (mask & 524288) ? 3 : 1);      // process-wide (the launcher has no engine): the A/B tools run one engine
     e->xpa_armed = false;                    // another mask may have run plain stores through xp_a: the next step re-arms it
     for (auto& kv : e->cb_graphs) {          // the continuous-batching step graphs were captured with the old mask
         if (kv.second.second) (void)hipGraphExecDestroy(kv.second.second);
@@ -31,6 +31,8 @@ extern "C" int sv_debug_set_exp(sv_engine* e, int32_t mask) {
     e->cb_graphs.clear();
     return 0;
 }
+
+extern "C" int sv_debug_exp_known(void) { return SV_EXP_KNOWN; }
 
 extern "C" int sv_debug_step_plan(sv_engine* e, int32_t* out4) {
     if (!e || !out4) return fail(SV_EINVAL, "sv_debug_step_plan: null argument");
@@ -65,7 +67,7 @@ extern "C" int sv_debug_decode_plan(int32_t rows, int32_t N, int32_t K, int32_t 
     Linear l;
     l.N = N; l.K = K; l.Npad = round_up(N, 32); l.Kpad = K;
     int sk = 1, ct = 1;
-    pick_decode_plan(l, (rows + 31) / 32, num_cus, fp8 != 0, false, whole_k != 0, &sk, &ct);
+    pick_decode_plan(l, (rows + 31) / 32, num_cus, fp8 != 0, whole_k != 0, &sk, &ct);
     if (fp8) while (sk > 1 && ((K / 16) % sk != 0 || ((K / 16) / sk) % 4 != 0)) --sk;          // as sv_create does
     out2[0] = sk; out2[1] = ct;
     return 0;
@@ -241,6 +243,7 @@ extern "C" int sv_debug_set_skinny_form(int32_t form) {
     set_mt2x(form);
     return 0;
 }
+extern "C" int sv_debug_skinny_form(void) { return get_mt2x(); }
 
 // 1 / 0: does the projection (N, K, act) take the per-sequence remainder form for sequences of S rows (host arithmetic only; < 0: bad argument)
 extern "C" int sv_debug_gemm_seq_form(int32_t S, int32_t N, int32_t K, int32_t act) {

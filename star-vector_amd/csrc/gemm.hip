@@ -1867,20 +1867,15 @@ __global__ __launch_bounds__(128) void gemm_skinny_tailsplit_kernel(const bf16_t
     if (tid == 0) __hip_atomic_store(p.tail_cnt + tt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-arm
     sk_store<RPW>(p, v, bias_d, wave * RPW, nt, 0, 0, m, half);
 }
-std::atomic<int> g_tailsplit{0};     // off by default: the bit-identical split ties with the one launch (profiles/tailsplit_r06_ab.log); SV_TAILSPLIT=1 = on
-void set_tailsplit(int on) { g_tailsplit = on; }
 std::atomic<long long> g_tailsplit_launches{0};     // host-side count of tail-split launches (sv_debug_tailsplit_launches)
 long long tailsplit_launches() { return g_tailsplit_launches.load(std::memory_order_relaxed); }
 
-std::atomic<int> g_head_persist{1};     // 1: the lm_head of a one-row-tile step through gemm_head_persist_kernel where it applies; 0: the one-tile kernel (A/B)
-void set_head_persist(int on) { g_head_persist = on; }
-// false: outside the kernel's scope
 // G = blocks of the persistent lm_head launch for `a`; 0: outside the kernel's scope
 static int head_persist_grid(const SkinnyArgs& a) {
-    const char* ev = getenv("SV_HEAD_PERSIST");             // read per call (A/B in one process; a captured graph keeps its choice)
-    const int env = ev ? atoi(ev) : -1;
-    const int on = env >= 0 ? env : g_head_persist.load(std::memory_order_relaxed);
-    if (!on) return 0;
+    // on by default: the lm_head of a one-row-tile step through gemm_head_persist_kernel where it applies; SV_HEAD_PERSIST=0 = the one-tile kernel
+    // (read per call: A/B in one process; a captured graph keeps its choice)
+    const char* ev = getenv("SV_HEAD_PERSIST");
+    if (ev && atoi(ev) == 0) return 0;
     const int n_tiles = a.Npad / 32;
     if (a.out_mode != SK_OUT_F32 || a.MT < 1 || a.MT > 2 || a.Wq || a.splitk != 1 || a.K / 16 != 128 || n_tiles < 512 || a.fold_c1) return 0;
     if (a.MT == 2 && (a.amax || a.poison)) return 0;      // (the folded selection and the pattern stores belong to one-row-tile steps)
@@ -1918,7 +1913,7 @@ static bool launch_head_persist(const SkinnyArgs& a_, hipStream_t st) {
 // mlp_fused_kernel: the MLP half of a decode layer (gpt_bigcode/modeling_gpt_bigcode.py:645-660: c_fc -> GELU-tanh -> c_proj) as ONE
 // launch of F/32 co-resident blocks (256 for StarVector-1B, one 8-wave block per CU), instead of gemm_skinny_kernel<8, true> (folded
 // c_fc) and gemm_skinny_kernel<8, false> (down projection, split-K slabs) with a kernel boundary between them.  Round 4; on for an
-// engine that owns its GPU (sv_config.exclusive_device), SV_EXP bit 128 / 512 = forced on / off.  Measured in process on one MI355X,
+// engine that owns its GPU (sv_config.exclusive_device), SV_EXP_MLP_FUSED_FORCE / SV_EXP_MLP_FUSED_OFF = forced on / off.  Measured in process on one MI355X,
 // BASELINE config 2: 1079 vs 1111 us per decode step, tokens bit-identical (every version's A/B and wall-clock
 // trace: profiles/mlp_fused_r04_ab.log).
 //
@@ -2698,6 +2693,7 @@ __global__ __launch_bounds__(512, CH == 2 ? 4 : 2) void gemm_skinny_mt2x_kernel(
 #define MT2X_SMEM(ch) (8 * 2 * (ch) * 2048 + 2 * 3 * 32 * 4)      // the ring / reduction buffer + [NT <= 3][32] scales + biases
 std::atomic<int> g_mt2x{1};             // 33..64 rows: 0 = gemm_skinny_mt2_kernel, 1 = the LDS-ring form (chunk depth by block count), 2 / 3 = its CH = 2 / 4 form always
 void set_mt2x(int on) { g_mt2x = on; }
+int get_mt2x() { return g_mt2x.load(std::memory_order_relaxed); }
 
 std::atomic<int> g_op_col_tiles{0};     // op-level entry points only (SkinnyArgs.col_tiles == 0); engines always pass their plan
 static int init_mt2_attrs() {
@@ -2799,9 +2795,10 @@ void skinny_plan(int Npad, int K, int splitk, int fp8, int MT, int* waves, int* 
 
 // false: outside the scope of the tail split (see gemm_skinny_tailsplit_kernel)
 static bool launch_skinny_tailsplit(const SkinnyArgs& a, hipStream_t st) {
-    const char* ev = getenv("SV_TAILSPLIT");                 // read per call (A/B in one process; a captured graph keeps its choice)
-    const int on = ev ? atoi(ev) : g_tailsplit.load(std::memory_order_relaxed);
-    if (!on || !a.tail_ws || !a.tail_cnt) return false;
+    // off by default: the bit-identical split ties with the one launch (profiles/tailsplit_r06_ab.log); SV_TAILSPLIT=1 = on
+    // (read per call: A/B in one process; a captured graph keeps its choice)
+    const char* ev = getenv("SV_TAILSPLIT");
+    if (!ev || !atoi(ev) || !a.tail_ws || !a.tail_cnt) return false;
     if (a.out_mode != SK_OUT_PACKED_ACT || a.MT != 1 || a.Wq || a.fold_c1 || a.splitk != 1) return false;
     const int KS = a.K / 16, n_tiles = a.Npad / 32;
     if (KS != 8 * 36 || skinny_waves(a.Npad, KS, 1) != 8) return false;      // the one instantiation: the one-tile kernel's 8 ranges of 36 k-steps (K = 4608)

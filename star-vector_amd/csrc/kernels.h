@@ -65,7 +65,8 @@ void launch_gemm(const GemmArgs& a, hipStream_t st);
 void launch_gemm_ragged(const GemmArgs& a, const int32_t* rows, int n_rows, bf16_t* r_save, hipStream_t st);
 // one fixed configuration (kernel256: 0 = 128^2 tiles, 1 = 256^2; peel: the row remainder over a multiple of 256 in its own launch), no tuning
 void launch_gemm_fixed(const GemmArgs& a, int kernel256, int peel, hipStream_t st);
-void set_mt2x(int on);                // 33..64-row decode GEMMs: 1 = activations through a wave-private LDS ring (gemm_skinny_mt2x_kernel, default), 0 = both operands in registers
+int get_mt2x();
+void set_mt2x(int on);                // (sv_debug_set_skinny_form / sv_debug_skinny_form) 33..64-row decode GEMMs: 1 = activations through a wave-private LDS ring (gemm_skinny_mt2x_kernel, default), 0 = both operands in registers
 long long tailsplit_launches();        // host-side count of gemm_skinny_tailsplit_kernel launches since load (sv_debug_tailsplit_launches)
 void set_gemm_form(int form);         // -1: tuned (default); 0 / 1: every big-M launch takes that form, rows not peeled
 // what launch_gemm decides for a shape (host arithmetic only; tail_on: 0 never peel, 1 cost model, 2 always)
@@ -136,7 +137,7 @@ int init_gemm_kernels();        // hipFuncSetAttribute for the large-LDS variant
 
 void launch_cvt_bf16_hw(const float* x, bf16_t* y, size_t n, hipStream_t st);
 
-// ---- the MLP half of a decode layer as one launch (gemm.hip: mlp_fused_kernel; round-4 experiment, SV_EXP bit 128) ----
+// ---- the MLP half of a decode layer as one launch (gemm.hip: mlp_fused_kernel; round-4 experiment, SV_EXP_MLP_FUSED_FORCE) ----
 struct MlpFusedArgs {
     const bf16_t* W1; const bf16_t* x1;      // folded c_fc image W' [N1pad/32][K1/16][64][8], raw residual stream in fragment order
     int N1, N1pad, K1;
@@ -289,7 +290,6 @@ struct AttnDecodeArgs {
     int window;                                            // sliding window: keys pos - window < j <= pos (0 = all)
     int groups_per_block;                                  // 32-key groups a block takes before another context split joins (0 = 4)
     long long* trace;                                      // optional [B * n_kv * max_splits][16] wall-clock stamps (tools/attn_trace.py); nullptr in production
-    int merge_all;                                         // 1: every wave takes part in the block's LDS merge (rounds 1-5); 0: only the waves that had a key group
     void* poison2; unsigned poison2_bytes;                 // a second buffer filled the same way, by the threads behind those of the first (the next layer's
                                                            // LayerNorm output buffer: rowln_cattn_kernel)
     void* poison; unsigned poison_bytes;                   // optional: a buffer the launch fills with 0xFF bytes, 16 per thread, before anything else (the

@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import enum
 import threading
 from dataclasses import dataclass
 from typing import Dict, Iterable, List, NamedTuple, Optional, Sequence, Tuple
@@ -10,6 +11,47 @@ import torch
 
 from . import _lib
 from ._lib import SvConfig, SvSampling, check
+
+
+class Exp(enum.IntFlag):
+    """The A/B switches of an engine (`HipEngine.set_exp`, the SV_EXP environment variable): mirror of `enum sv_exp_bits` in
+    include/starvector_hip_debug.h, where each switch is described; tests/test_native_host_logic.py pins it against the library."""
+    NO_LN_FOLD = 2
+    MLP_FUSED_FORCE = 128
+    MLP_FUSED_OFF = 512
+    SEPARATE_ARGMAX = 1024
+    ROWLN_CATTN_OFF = 8192
+    ROWLN_CATTN_FORCE = 16384
+    NO_PRUNE_LAST = 32768
+    BATCH_REMAINDER = 4194304
+
+    @classmethod
+    def known(cls) -> int:
+        mask = 0
+        for m in cls:
+            mask |= int(m)
+        return mask
+
+    @classmethod
+    def parse(cls, text) -> "Exp":
+        """A mask from names and / or numbers joined by '+', '|' or ',' ("MLP_FUSED_FORCE+16384", "SV_EXP_NO_LN_FOLD", "0");
+        ValueError for a name or a bit that is no switch."""
+        mask = 0
+        for part in str(text).replace("|", "+").replace(",", "+").split("+"):
+            part = part.strip()
+            name = part.upper()[7:] if part.upper().startswith("SV_EXP_") else part.upper()
+            if name in cls.__members__:
+                mask |= int(cls.__members__[name])
+            else:
+                try:
+                    mask |= int(part, 0)
+                except ValueError:
+                    raise ValueError(f"unknown switch {part!r}; the switches: {', '.join(cls.__members__)}") from None
+        bad = mask & ~cls.known()
+        if mask < 0 or bad:
+            raise ValueError(f"mask {mask}: bits {[1 << i for i in range(32) if bad >> i & 1]} are no switch of this build "
+                             f"(the switches: {', '.join(f'{m.name} = {int(m)}' for m in cls)})")
+        return cls(mask)
 
 
 @dataclass
@@ -587,7 +629,8 @@ class HipEngine:
         return {"graph_kernel_nodes": int(buf[0]), "rowln_cattn_fused": bool(buf[1]), "greedy_in_lm_head": bool(buf[2]), "mlp_fused": bool(buf[3])}
 
     def set_exp(self, mask: int) -> None:
-        """Experiment bit mask (SV_EXP) of the live engine: in-process A/B runs (tools/ab_exp.py)."""
+        """A/B switches of the live engine: a mask of `Exp` members, 0 = the product path (in-process A/B runs: tools/ab_exp.py).
+        ValueError for a bit that is no switch; the engine keeps its mask then."""
         check(self.lib.sv_debug_set_exp(self._h, int(mask)), "sv_debug_set_exp")
 
     def debug_attn_trace(self) -> torch.Tensor:
@@ -906,6 +949,11 @@ def shared_plan(lengths: Sequence[int], group: Sequence[int], budgets: Sequence[
 def set_skinny_form(form: int) -> None:
     """Kernel of the 33..64-row decode GEMMs (sv_debug_set_skinny_form): 0 registers only, 1 LDS ring (default), 2 / 3 its fixed depths."""
     check(_lib.load().sv_debug_set_skinny_form(int(form)))
+
+
+def skinny_form() -> int:
+    """The form `set_skinny_form` left in force, process-wide (creating an engine does not touch it)."""
+    return int(_lib.load().sv_debug_skinny_form())
 
 
 def set_op_col_tiles(col_tiles: int) -> None:

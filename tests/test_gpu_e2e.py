@@ -91,6 +91,64 @@ def test_against_reference_goldens(name, norm):
     eng.close()
 
 
+def test_seven_launch_layer_mask_matches_the_golden():
+    """SV_EXP_NO_LN_FOLD on the tiny golden engine, which takes the 6-launch layer by default (bf16, 3 rows, widths multiples of 32): the
+    captured step grows by launches, and the 7-launch layer meets what the default mask meets in test_against_reference_goldens -- the
+    oracle's logits within LOGIT_TOL at every teacher-forced step and HF generate's tokens.  Not compared bit for bit with mask 0: the fold
+    re-rounds gamma * W."""
+    g = _golden("tiny_b3")
+    seed, B, n_new = [int(x) for x in g["meta"]]
+    cfg = O.OracleConfig.tiny()
+    w = O.apply_fixture_weights(O.make_weights(cfg, seed=seed), cfg, g)
+    eng = build_engine(cfg, w, max_batch=4, max_seq_len=64)
+    emb = torch.cat([eng.adapter(eng.encode_image(bf(g["image"]))), eng.embed_tokens(g["prompt_ids"].to(dev()))], 1)
+    kw = dict(max_length=emb.shape[1] + n_new, eos_token_id=cfg.eos_token_id, pad_token_id=cfg.pad_token_id)
+    assert torch.equal(eng.generate(emb, **kw).cpu(), g["tokens"])
+    nodes6 = eng.step_plan()["graph_kernel_nodes"]
+    eng.set_exp(E.Exp.NO_LN_FOLD)
+    toks = eng.generate(emb, **kw).cpu()
+    nodes7 = eng.step_plan()["graph_kernel_nodes"]
+    print(f"[NO_LN_FOLD] kernel nodes per step: {nodes6} by default, {nodes7} with the switch ({cfg.n_layer} layers)")
+    assert 0 < nodes6 < nodes7, "the tiny engine does not take the 6-launch layer by default"
+    worst, scale, checked, near, o_toks, margin = _teacher_forced_check(eng, emb, w, cfg, n_new)
+    print(f"[NO_LN_FOLD] logits max|err| {worst:.3e} (scale {scale:.3e}); {checked} token positions checked exactly")
+    assert checked == B * n_new and near == 0
+    assert torch.equal(toks, g["tokens"])
+    eng.close()
+
+
+def test_unknown_switch_bits_are_refused_and_the_skinny_form_survives_engine_creation():
+    """sv_debug_set_exp with a bit that is no switch (a removed one; one past the known set) is SV_EINVAL and leaves the engine's mask as it
+    was: the same tokens and the same step afterwards, under mask 0 and under a mask whose effect shows in the step plan.  The process-wide
+    form of the 33..64-row decode GEMMs belongs to sv_debug_set_skinny_form alone: creating an engine no longer resets it."""
+    cfg = O.OracleConfig.tiny()
+    w = O.make_weights(cfg, seed=21)
+    gen = torch.Generator().manual_seed(5)
+    x = torch.randn(33, 256, generator=gen).bfloat16().float()
+    W = (torch.randn(96, 256, generator=gen) / 16).bfloat16().float()
+    known = int(E.Exp.known())
+    try:
+        E.set_skinny_form(0)
+        before = E.op_linear_skinny(bf(x), bf(W), None, splitk=2)
+        eng = build_engine(cfg, w, 4, 64)                                   # sv_create in between
+        assert E.skinny_form() == 0, "sv_create changed the form sv_debug_set_skinny_form set"
+        assert torch.equal(E.op_linear_skinny(bf(x), bf(W), None, splitk=2), before)
+        emb = torch.cat([eng.adapter(eng.encode_image(bf(O.synthetic_images(2, cfg.image_size, seed=22)))),
+                         eng.embed_tokens(torch.tensor([[7, 11]] * 2, device=dev()))], 1)
+        kw = dict(max_length=emb.shape[1] + 8, eos_token_id=-1, pad_token_id=cfg.pad_token_id)
+        for mask in (E.Exp(0), E.Exp.SEPARATE_ARGMAX | E.Exp.NO_LN_FOLD):
+            eng.set_exp(mask)
+            toks, plan = eng.generate(emb, **kw).cpu(), eng.step_plan()
+            for bad in (16, known | (1 << 20)):
+                with pytest.raises(ValueError, match=str(bad & ~known)):    # the message names the offending bit
+                    eng.set_exp(bad)
+                assert torch.equal(eng.generate(emb, **kw).cpu(), toks) and eng.step_plan() == plan, (mask, bad)
+        assert E.skinny_form() == 0                                         # nor does sv_debug_set_exp touch it
+        eng.close()
+    finally:
+        E.set_skinny_form(1)
+
+
 def test_generate_semantics_eos_pad_stop_on_device():
     """HF semantics restated on device: pad after EOS, the row-0 stop sequence ends the WHOLE batch, only new
     tokens are returned.  The golden comes from HF generate + the reference's StoppingCriteriaSub."""

@@ -6,6 +6,7 @@
     profiles/gemm_r01_dispatch_ab.log."""
 import ctypes as C
 import math
+import re
 
 import numpy as np
 import pytest
@@ -187,3 +188,36 @@ def test_fused_row_update_c_attn_launch_shapes(lib):
     assert plan(1024, 1152, 2)[0] == 1 and plan(1024, 1152, 2)[1] == 4      # another narrow width with 4 k-steps per wave
     out = (C.c_int32 * 3)()
     assert lib.sv_debug_rowln_plan(0, 2304, 4, 4, 256, out) == -22
+
+
+def test_switch_mask_python_mirror_equals_the_library(lib):
+    """The named A/B switches (enum sv_exp_bits, include/starvector_hip_debug.h): starvector_amd.Exp lists the library's bits, value for
+    value, and the bits removed with their closed experiments are gone from both."""
+    from starvector_amd.engine import Exp
+    known = lib.sv_debug_exp_known()
+    union = 0
+    for m in Exp:
+        union |= int(m)
+    assert known == union == Exp.known()
+    for removed in (4, 8, 16, 64, 131072, 262144, 524288, 2097152):
+        assert not known & removed, removed
+    header = open(_lib.DEBUG_HEADER_PATH).read()
+    for m in Exp:                                               # names and values as the header spells them
+        assert len(re.findall(r"\bSV_EXP_%s\s*=\s*%d\b" % (m.name, int(m)), header)) == 1, m
+    assert Exp.parse("0") == 0 and Exp.parse("NO_LN_FOLD") == 2 and Exp.parse("SV_EXP_MLP_FUSED_OFF+8192") == 512 + 8192
+    assert Exp.parse("mlp_fused_force|0x4000") == Exp.MLP_FUSED_FORCE | Exp.ROWLN_CATTN_FORCE
+    for bad in ("16", "2+4", "MERGE_ALL", str(known | 1 << 20), "-1"):
+        with pytest.raises(ValueError):
+            Exp.parse(bad)
+    assert lib.sv_debug_set_exp(None, 0) == -22                 # no engine: nothing to set
+
+
+def test_sv_create_refuses_an_unknown_switch_in_the_environment(lib, monkeypatch):
+    """SV_EXP with a removed bit ends sv_create with SV_EINVAL and the bit's number, in front of any device work or allocation (so it is
+    checked here, without a GPU): an A/B arm that names a switch this build does not have cannot silently run the default."""
+    cfg, h = _lib.SvConfig(), C.c_void_p()
+    lib.sv_config_default_1b(C.byref(cfg))
+    monkeypatch.setenv("SV_EXP", str(16 | 2))
+    assert lib.sv_create(C.byref(cfg), C.byref(h)) == -22 and not h.value
+    msg = lib.sv_last_error().decode()
+    assert "SV_EXP" in msg and " 16 " in msg and " 2 " not in msg, msg

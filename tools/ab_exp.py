@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""In-process A/B of the experiment masks (SV_EXP bits) on BASELINE config 2's decode loop:
-    python tools/ab_exp.py [--new-tokens 512] [--reps 2] 0 1 2 3 ...
+"""In-process A/B of the engine's switches (starvector_amd.Exp) on BASELINE config 2's decode loop:
+    python tools/ab_exp.py [--new-tokens 512] [--reps 2] 0 NO_LN_FOLD MLP_FUSED_OFF+ROWLN_CATTN_OFF 1024 ...
+A mask is names and / or numbers joined by '+'; one that is no switch of this build is refused before anything runs.
 One engine, the masks interleaved `reps` times; prints us per decode step, the per-class HIP-event profile and whether the
 token stream equals mask 0's."""
 import argparse
@@ -16,7 +17,7 @@ import starvector_amd as sva  # noqa: E402
 from bench import synthetic_images  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("masks", nargs="*", type=int, default=[0, 1, 2, 3])
+ap.add_argument("masks", nargs="*", type=sva.Exp.parse, default=[sva.Exp(0), sva.Exp.NO_LN_FOLD])
 ap.add_argument("--new-tokens", type=int, default=512)
 ap.add_argument("--reps", type=int, default=2)
 ap.add_argument("--batch", type=int, default=32)
@@ -44,7 +45,7 @@ for rep in range(a.reps + 1):                      # rep 0 = warm-up (graph capt
         if rep == 0:
             continue
         prof = eng.profile_decode_step(B, iters=3)
-        print(json.dumps({"exp": m, "rep": rep, "us_per_step": round(tm["decode_ms"] / max(tm["decode_steps"], 1) * 1e3, 1),
+        print(json.dumps({"exp": int(m), "rep": rep, "us_per_step": round(tm["decode_ms"] / max(tm["decode_steps"], 1) * 1e3, 1),
                           "tokens_equal_first_mask": bool(torch.equal(toks, ref)),
                           "event_ms": {k: round(v["ms_per_step"], 4) for k, v in prof.items() if isinstance(v, dict)},
                           "gemm_chain_ms": round(prof["skinny_chain_ms_per_step"], 4),

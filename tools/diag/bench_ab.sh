@@ -2,11 +2,11 @@
 # ONE same-box A/B driver for the GPU box (replaces the fourteen one-off r05_*.sh / rc_*.sh / r06_*.sh scripts of rounds 5-6).
 # Every arm runs in its own process on the SAME box, arms interleaved `reps` times; a bench.py JSON line is summarised, other output is passed
 # through for the lines that carry a number (us_per_step, ttft_ms, TF, passed / failed).  From the repo root:
-#   bash tools/diag/bench_ab.sh env   VAR "v1 v2 ..." [reps] -- <command ...>     the command under VAR=v1, VAR=v2, ...   (SV_EXP masks, SV_RC_DELAY, SV_TAIL_RING ...)
+#   bash tools/diag/bench_ab.sh env   VAR "v1 v2 ..." [reps] -- <command ...>     the command under VAR=v1, VAR=v2, ...   (SV_EXP = a numeric mask of sv_exp_bits, include/starvector_hip_debug.h: sv_create refuses any other bit; SV_RC_DELAY, SV_TAIL_RING ...)
 #   bash tools/diag/bench_ab.sh tree  DIR [reps] -- <bench.py arguments>          another checkout (DIR, built) against this one, python bench.py <arguments>
 #   bash tools/diag/bench_ab.sh build "FLAGS_A" "FLAGS_B" [reps] -- <command ...> two builds of the library (SV_HIPCC_FLAGS), rebuilt on the box before each arm
 #   bash tools/diag/bench_ab.sh swap  FILE ALT [reps] -- <command ...>            the tree's FILE against the file ALT (rebuilt before each arm): a source-level A/B
-# Examples (round 6):  env SV_EXP "131072 0 262144 524288" -- python bench.py --model 8b --weights fp8 --task text2svg --new-tokens 256 --steps 2 --no-cpu-baseline
+# Examples:            env SV_EXP "0 512 8192 8704" -- python bench.py --new-tokens 256 --steps 2 --no-cpu-baseline      (the fused launches off, one by one and both)
 #                      swap star-vector_amd/csrc/attention.hip /tmp/attention_before.hip 2 -- python tools/ab_exp.py --new-tokens 1024 --reps 2 0 0
 set -u
 mode="${1:?mode: env | tree | build | swap}"; shift

@@ -13,7 +13,7 @@
 #     skinny      tools/bench_skinny.py                             -> bench_skinny.log
 #     memmix      tools/diag/mem_mix.hip: weight stream + shared-operand re-reads without MFMA (what bounds the decode GEMMs) -> mem_mix.log
 #     xcd         tools/diag/xcd_map.hip: block -> XCD placement inside a replayed graph  -> xcd_map.log
-#     ab:<args>   tools/ab_exp.py <args> (in-process A/B of SV_EXP masks)           -> ab_exp.log
+#     ab:<args>   tools/ab_exp.py <args> (in-process A/B of the named switches, starvector_amd.Exp)         -> ab_exp.log
 #     run:<name>:<script args>  python <script args> -> <name>.log
 #     rebuild:<K=V>  rebuild the library on the box with K=V in the environment (build-flag A/B, e.g. SV_NO_KERNARG_PRELOAD=1)
 #     env:<K=V>   export K=V for the steps that follow (experiment switches)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Where the time of the fused MLP launch goes (SV_EXP bit 128): per-block wall-clock stamps of one launch in the middle of a decode
+"""Where the time of the fused MLP launch goes (SV_EXP_MLP_FUSED_FORCE = 128): per-block wall-clock stamps of one launch in the middle of a decode
 step of BASELINE config 2 (B = 32, context ~400), printed as distributions in microseconds relative to the earliest block start."""
 import os
 import sys
@@ -12,6 +12,8 @@ sys.path.insert(0, ROOT)
 import starvector_amd as sva  # noqa: E402
 from bench import synthetic_images  # noqa: E402
 
+# the switches to run under, by name or number (refused here, before the engine exists, if it is no switch of this build)
+mask = sva.Exp.parse(sys.argv[1] if len(sys.argv) > 1 else "MLP_FUSED_FORCE")
 dev = torch.device("cuda", 0)
 B = 32
 eng = sva.HipEngine(sva.EngineConfig(max_batch=B, max_seq_len=259 + 160))
@@ -19,9 +21,8 @@ eng.load_random_weights(seed=1234)
 img = synthetic_images(torch, B, 224, seed=0).to(dev)
 prompt = torch.tensor([[7, 11]] * B, dtype=torch.long, device=dev)
 emb = torch.cat([eng.adapter(eng.encode_image(img)), eng.embed_tokens(prompt)], 1)
-mask = int(sys.argv[1]) if len(sys.argv) > 1 else 128       # SV_EXP mask: 128 = the fused launch
 eng.set_exp(mask)
-print(f"=== SV_EXP {mask}")
+print(f"=== SV_EXP {int(mask)} ({mask!r})")
 for rep in range(3):
     eng.generate(emb, max_length=emb.shape[1] + 128, eos_token_id=-1, pad_token_id=49152)
     tr = eng.debug_mlp_trace().double()

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""In-process A/B of the experiment masks (SV_EXP bits) on BASELINE config 2's time to first token:
-    python tools/ttft_ab.py [--reps 15] [--batch 32] 0 32768 ...
+"""In-process A/B of the engine's switches (starvector_amd.Exp) on BASELINE config 2's time to first token:
+    python tools/ttft_ab.py [--reps 15] [--batch 32] 0 NO_PRUNE_LAST ...
+A mask is names and / or numbers joined by '+'; one that is no switch of this build is refused before anything runs.
 One engine, the masks interleaved; a request = encoder + adapter + prompt pass + first token (bench.py's `step(max_new=1)`), host wall
 clock around a synchronised call.  Prints the median / min per mask and whether the first tokens equal mask 0's."""
 import argparse
@@ -18,7 +19,7 @@ import starvector_amd as sva  # noqa: E402
 from bench import synthetic_images  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("masks", nargs="*", type=int, default=[0, 32768])
+ap.add_argument("masks", nargs="*", type=sva.Exp.parse, default=[sva.Exp(0), sva.Exp.NO_PRUNE_LAST])
 ap.add_argument("--reps", type=int, default=15)
 ap.add_argument("--batch", type=int, default=32)
 ap.add_argument("--stages", action="store_true", help="also print sv_profile_ttft's stage table per mask")
@@ -52,7 +53,7 @@ for rep in range(a.reps + 2):                      # reps 0-1 = warm-up (GEMM tu
             ms[m].append(dt)
         first.setdefault(m, tok.cpu())
 for m in a.masks:
-    line = {"exp": m, "ttft_ms_median": round(statistics.median(ms[m]), 3), "ttft_ms_min": round(min(ms[m]), 3), "n": len(ms[m]),
+    line = {"exp": int(m), "ttft_ms_median": round(statistics.median(ms[m]), 3), "ttft_ms_min": round(min(ms[m]), 3), "n": len(ms[m]),
             "first_tokens_equal_first_mask": bool(torch.equal(first[m], first[a.masks[0]]))}
     if a.stages:
         eng.set_exp(m)
