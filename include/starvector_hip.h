@@ -18,6 +18,8 @@
  *                                    incl. StoppingCriteriaSub (starvector_base.py:9-20)
  *   sv_generate_processed  the same call with the HF generate arguments the reference's callers add for a decoder that loops or emits
  *                                    a forbidden token: no_repeat_ngram_size, bad_words_ids, min_p (sv_logits_processors below)
+ *   sv_generate_stats      the same call, also returning each generated token's log-prob, processed log-prob and entropy (what a GRPO
+ *                                    trainer otherwise gets from a second pass over prompt + completion; sv_token_stats below)
  *   sv_load_weight         ingests the reference state_dict keys (train/util.py:71 naming;
  *                          SURVEY.md section 8b "Weight names")
  *
@@ -339,6 +341,33 @@ typedef struct sv_logits_processors {
 int  sv_generate_processed(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, int32_t S0, int32_t n_samples,
                            const sv_sampling* sp, const sv_logits_processors* lp, const sv_generate_outputs* outs, int64_t* dev_out_tokens,
                            int32_t* n_generated, sv_stream stream);
+/* ---- per-token statistics of a roll-out, from the decode loop itself (GRPO's old-policy log-probs, best-of-n reranking, confidence filters):
+ * sv_generate_stats = sv_generate_processed plus, for the token tok that row r emits in column t, three fp32 values at [r][t] of the caller's
+ * device buffers ([rows][ld] each, rows = B * n_samples, ld >= max_new = max_length - prompt length; any may be NULL, not all three):
+ *   dev_logprob            log_softmax(x / T)[tok]; x = the step's raw lm_head row (what sv_generate_outputs.dev_logits holds: before bans, the
+ *                          min-length hold and the repetition penalty), T = temperature when do_sample, else 1 -- the quantity
+ *                          sv_forward_logprobs(..., temperature = T) returns for that position
+ *   dev_entropy            entropy of softmax(x / T)
+ *   dev_logprob_processed  log_softmax(s)[tok]; s = the processed row (what dev_scores holds: bans -> repetition penalty -> min-length hold ->
+ *                          with do_sample / T, top-k, top-p, min_p, removed ids at -inf; the kept set is the one dev_scores shows) -- HF's
+ *                          compute_transition_scores(..., normalize_logits = True)
+ * A row that had finished before column t gets 0 in all three (columns >= *n_generated are not written).  No [rows][vocab] output exists: the
+ * cost is one launch per step (one 1024-thread block per row, fp32 reductions) between the selection and the bookkeeping, two when the step
+ * rewrites the raw row in place (a token ban, the min-length hold: the raw row's sums are then taken in front of the rewrite).  A call with
+ * statistics takes the separate selection launch, like a repetition penalty or a capture; its captured step is keyed on the statistics, so a
+ * plain call afterwards replays the plain step and the other way round, and a kept graph writes each call's own buffers (device descriptor).
+ * Tokens and *n_generated are those of sv_generate_processed bit for bit.  stats NULL: exactly sv_generate_processed, the same captured step.
+ * SV_EINVAL before any device work for ld < max_new, for all three pointers NULL and for num_beams > 1 (beam search reports
+ * sequences_scores; beam rows reorder). */
+typedef struct sv_token_stats {
+    float* dev_logprob;                /* [rows][ld] fp32, or NULL */
+    float* dev_logprob_processed;      /* [rows][ld] fp32, or NULL */
+    float* dev_entropy;                /* [rows][ld] fp32, or NULL */
+    int64_t ld;                        /* >= max_new */
+} sv_token_stats;
+int  sv_generate_stats(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, int32_t S0, int32_t n_samples,
+                       const sv_sampling* sp, const sv_logits_processors* lp, const sv_generate_outputs* outs, const sv_token_stats* stats,
+                       int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream);
 /* ---- continuous batching (the reference worker's 5 concurrent requests, serve/model_worker.py:161-172,
  * 216-229, as ONE decode loop).  Every row ("slot") of the engine's batch is an independent request: own sampling parameters,
  * budget, EOS, stop sequence (the reference's row-0 stop, starvector_base.py:9-20, is right for one request per generate call

@@ -89,6 +89,13 @@ class SvLogitsProcessors(C.Structure):
         ("bad_word_lens", C.POINTER(C.c_int32)), ("bad_word_ids", C.POINTER(C.c_int32)), ("min_p", C.c_float),
     ]
 
+class SvTokenStats(C.Structure):
+    # sv_generate_stats: per-token log-prob / processed log-prob / entropy of the roll-out, device fp32 [rows][ld] each (any may be NULL, not all)
+    _fields_ = [
+        ("dev_logprob", C.c_void_p), ("dev_logprob_processed", C.c_void_p), ("dev_entropy", C.c_void_p), ("ld", C.c_int64),
+    ]
+
+
 LP_MAX_NGRAM, LP_MAX_BAD_WORDS, LP_MAX_BAD_WORD_LEN = 8, 64, 8
 
 
@@ -123,6 +130,8 @@ PRODUCT_PROTOTYPES = {
     "sv_generate_shared": (_I, [_P, _P, _I, C.POINTER(_I), _I, _I, C.POINTER(SvSampling), C.POINTER(SvGenerateOutputs), _P, C.POINTER(_I), _P]),
     "sv_generate_processed": (_I, [_P, _P, _I, C.POINTER(_I), _I, _I, C.POINTER(SvSampling), C.POINTER(SvLogitsProcessors),
                                    C.POINTER(SvGenerateOutputs), _P, C.POINTER(_I), _P]),
+    "sv_generate_stats": (_I, [_P, _P, _I, C.POINTER(_I), _I, _I, C.POINTER(SvSampling), C.POINTER(SvLogitsProcessors),
+                               C.POINTER(SvGenerateOutputs), C.POINTER(SvTokenStats), _P, C.POINTER(_I), _P]),
     "sv_cb_admit_shared": (_I, [_P, _P, _I, C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(SvCbRequest), C.POINTER(_I), _P]),
     "sv_cb_admit_ragged": (_I, [_P, _P, _I, C.POINTER(_I), C.POINTER(SvCbRequest), C.POINTER(_I), _P]),
     "sv_forward_logits": (_I, [_P, _P, _I, _I, _I, _P, _P]),

@@ -33,8 +33,27 @@ static void capture_step(sv_engine* e, int B, const sv_sampling& sp, hipStream_t
     c.minp_log = e->minp_log; c.what = what;
     launch_capture_rows(c, st);
 }
+// sv_generate_stats: the statistics of the token this step emits (TokenStatsArgs::what: 1 = the raw row's sums, 2 = the outputs, 3 = both)
+static void token_stats_step(sv_engine* e, int B, const sv_sampling& sp, hipStream_t st, int what) {
+    const bool pen = sp.repetition_penalty > 0.f && sp.repetition_penalty != 1.0f;
+    TokenStatsArgs a;
+    a.desc = e->ts_desc; a.src = e->logits; a.ld_src = e->Vpad; a.V = e->cfg.vocab; a.B = B;
+    a.step = e->d_step; a.done = e->d_done; a.unfinished = e->unfinished;
+    a.next = e->next_tok; a.pval = sp.do_sample ? nullptr : e->am_val; a.pidx = sp.do_sample ? nullptr : e->am_idx;
+    a.seen = pen ? e->seen : nullptr; a.seen_words = e->seen_words; a.penalty = sp.repetition_penalty;
+    a.eos = sp.eos_token_id;
+    a.min_new = (sp.min_new_tokens > 0 && sp.eos_token_id >= 0 && sp.eos_token_id < e->cfg.vocab) ? sp.min_new_tokens : 0;
+    a.do_sample = sp.do_sample ? 1 : 0; a.temperature = sp.temperature; a.top_p = sp.top_p; a.top_k = sp.top_k;
+    a.minp_log = e->minp_log; a.raw = e->ts_raw; a.what = what;
+    launch_token_stats(a, st);
+}
 static void sample_and_finish(sv_engine* e, int B, const sv_sampling& sp, int max_new, hipStream_t st, bool fused = false) {
     if (fused && e->fin_folded) { e->fin_folded = false; return; }      // the lm_head launch in front did the selection AND the bookkeeping (SkinnyArgs::finish)
+    // sv_generate_stats: one launch between the selection and the bookkeeping; a step that rewrites the raw row in place (a ban, the min-length
+    // hold) takes the raw row's sums in a launch of their own in front of the rewrite (a statistics call never folds: fused is off for it)
+    const bool ts_split = e->ts_on && (e->ban_ngram > 0 || e->ban_nwords > 0 ||
+                                       (sp.min_new_tokens > 0 && sp.eos_token_id >= 0 && sp.eos_token_id < e->cfg.vocab));
+    if (ts_split) token_stats_step(e, B, sp, st, 1);
     if (e->ban_ngram > 0 || e->ban_nwords > 0) {
         // sv_generate_processed with a ban: the raw row goes out first, the banned ids become -inf in e->logits, then everything below -- the score
         // capture, the min-length hold, the repetition penalty, the selection -- reads the banned row (-inf stays -inf through all of them)
@@ -61,6 +80,7 @@ static void sample_and_finish(sv_engine* e, int B, const sv_sampling& sp, int ma
         launch_argmax_partial(e->logits, e->Vpad, e->cfg.vocab, e->am_val, e->am_idx, B, seen, e->seen_words,
                               sp.repetition_penalty, st);
     }
+    if (e->ts_on) token_stats_step(e, B, sp, st, ts_split ? 2 : 3);
     const FinishArgs f = make_finish_args(e, B, sp, max_new, fused);
     launch_finish_step(f, st);
 }
@@ -253,15 +273,15 @@ int sveng::report_bad_logits(sv_engine* e, hipStream_t st, const char* who, int 
 // G: samples per prompt (1: sv_generate / sv_generate_ragged; > 1: sv_generate_shared -- one prompt pass over the B prompts, B * G decode rows)
 static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const int32_t* lens, const sv_sampling* sp,
                             const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream, int G,
-                            const sv_logits_processors* lp);
+                            const sv_logits_processors* lp, const sv_token_stats* ts);
 static int generate_retry(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const int32_t* lens, const sv_sampling* sp,
                           const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream, int G = 1,
-                          const sv_logits_processors* lp = nullptr) {
+                          const sv_logits_processors* lp = nullptr, const sv_token_stats* ts = nullptr) {
     if (e) { e->last_giveup = 0; e->stream_skip = 0; }
-    int rc = generate_attempt(e, dev_embeds, B, S0, lens, sp, outs, dev_out_tokens, n_generated, stream, G, lp);
+    int rc = generate_attempt(e, dev_embeds, B, S0, lens, sp, outs, dev_out_tokens, n_generated, stream, G, lp, ts);
     if (rc != 0 && e && e->cfg.exclusive_device == 2 && e->last_giveup && e->fused_off) {
-        e->last_giveup = 0;
-        rc = generate_attempt(e, dev_embeds, B, S0, lens, sp, outs, dev_out_tokens, n_generated, stream, G, lp);
+        e->last_giveup = 0;      // (the second attempt runs every step again: the statistics columns are rewritten completely, like the capture slabs)
+        rc = generate_attempt(e, dev_embeds, B, S0, lens, sp, outs, dev_out_tokens, n_generated, stream, G, lp, ts);
     }
     if (e) e->stream_skip = 0;
     return rc;
@@ -411,6 +431,55 @@ static int setup_capture(sv_engine* e, const sv_sampling* sp, const sv_generate_
     return 0;
 }
 
+// sv_generate_stats: the descriptor of the call's three buffers (allocated on first use, rewritten on the call's stream in front of everything the
+// call enqueues: a kept graph reads the new addresses).  The argument checks that need no engine are sv_generate_stats's own.
+static int setup_token_stats(sv_engine* e, const sv_sampling* sp, const sv_token_stats* ts, int rows, int max_new, hipStream_t st) {
+    e->ts_on = false;
+    if (!ts) return 0;
+    if (sp->num_beams > 1) return fail(SV_EINVAL, "sv_generate_stats: token statistics with num_beams %d are not built", sp->num_beams);
+    if (ts->ld < max_new) return fail(SV_EINVAL, "sv_generate_stats: ld %lld must be >= max_new %d", (long long)ts->ld, max_new);
+    if (!e->ts_desc) {
+        SVCHECK(dalloc(e, &e->ts_desc, 1));
+        SVCHECK(dalloc(e, &e->ts_raw, (size_t)e->cfg.max_batch * 4));
+    }
+    e->ts_host.logprob = ts->dev_logprob; e->ts_host.processed = ts->dev_logprob_processed; e->ts_host.entropy = ts->dev_entropy;
+    e->ts_host.ld = (long long)ts->ld; e->ts_host.rows = rows; e->ts_host.max_new = max_new;
+    HIPCHECK(hipMemcpyAsync(e->ts_desc, &e->ts_host, sizeof(TokenStatsDesc), hipMemcpyHostToDevice, st));
+    e->ts_on = true;
+    return 0;
+}
+// sv_generate_processed plus the per-token statistics of the roll-out (include/starvector_hip.h): stats NULL = exactly sv_generate_processed.
+extern "C" int sv_generate_stats(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, int32_t S0, int32_t n_samples,
+                                 const sv_sampling* sp, const sv_logits_processors* lp, const sv_generate_outputs* outs, const sv_token_stats* stats,
+                                 int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
+    if (!stats) return sv_generate_processed(e, dev_embeds_packed, B, host_lens, S0, n_samples, sp, lp, outs, dev_out_tokens, n_generated, stream);
+    // (the checks that need no engine come first: they are the same on a machine without a GPU)
+    if (!dev_embeds_packed || !sp || !dev_out_tokens || !n_generated) return fail(SV_EINVAL, "sv_generate_stats: null argument");
+    if (!stats->dev_logprob && !stats->dev_logprob_processed && !stats->dev_entropy)
+        return fail(SV_EINVAL, "sv_generate_stats: dev_logprob, dev_logprob_processed and dev_entropy are all NULL (pass stats = NULL for a call without statistics)");
+    if (sp->num_beams > 1)
+        return fail(SV_EINVAL, "sv_generate_stats: token statistics with num_beams %d are not built (beam search reports sequences_scores; beam rows reorder)",
+                    sp->num_beams);
+    if (B < 1) return fail(SV_EINVAL, "sv_generate_stats: bad B=%d", B);
+    if (n_samples < 1) return fail(SV_EINVAL, "sv_generate_stats: bad n_samples=%d (must be >= 1)", n_samples);
+    int longest = S0;
+    if (host_lens) {
+        longest = 0;
+        for (int b = 0; b < B; ++b) {
+            if (host_lens[b] < 1) return fail(SV_EINVAL, "sv_generate_stats: length %d of sequence %d (must be >= 1)", host_lens[b], b);
+            longest = host_lens[b] > longest ? host_lens[b] : longest;
+        }
+    } else if (S0 < 1) {
+        return fail(SV_EINVAL, "sv_generate_stats: bad S0=%d", S0);
+    }
+    if (sp->max_length - longest > 0 && stats->ld < (int64_t)(sp->max_length - longest))
+        return fail(SV_EINVAL, "sv_generate_stats: ld %lld must be >= max_new %d (max_length %d - prompt length %d)", (long long)stats->ld,
+                    sp->max_length - longest, sp->max_length, longest);
+    const bool any = lp && (lp->no_repeat_ngram_size != 0 || lp->n_bad_words != 0 || lp->min_p != 0.f);
+    if (any) SVCHECK(check_logits_processors(lp, 0, "sv_generate_stats"));
+    return generate_retry(e, dev_embeds_packed, B, longest, host_lens, sp, outs, dev_out_tokens, n_generated, stream, n_samples, any ? lp : nullptr, stats);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Shared prompt pass (sv_generate_shared): B prompts, G samples each, ONE prompt pass over the B prompts.
 // ------------------------------------------------------------------------------------------------
@@ -481,7 +550,7 @@ static int shared_prefill_fork(sv_engine* e, const void* dev_embeds, int B, int 
 // lens != nullptr: the ragged form -- S0 is the longest prompt (the budget counts from it), sequence b has lens[b] rows
 static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t Bp, int32_t S0, const int32_t* lens, const sv_sampling* sp,
                             const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream, int G,
-                            const sv_logits_processors* lp) {
+                            const sv_logits_processors* lp, const sv_token_stats* ts) {
     SVCHECK(check_ready(e));
     const bool shared = G > 1;
     if (shared && (Bp < 1 || (long long)Bp * G > e->cfg.max_batch))
@@ -513,6 +582,8 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t Bp, in
     const bool ban = e->ban_ngram > 0 || e->ban_nwords > 0;
     struct CapOff { sv_engine* e; ~CapOff() { e->cap_on = false; } } cap_off{e};
     SVCHECK(setup_capture(e, sp, outs, sp->num_beams > 1 ? B * sp->num_beams : B, max_new, st));
+    struct StatsOff { sv_engine* e; ~StatsOff() { e->ts_on = false; } } stats_off{e};
+    SVCHECK(setup_token_stats(e, sp, ts, B, max_new, st));
     if (sp->num_beams > 1) {
         if (sp->on_tokens) return fail(SV_EINVAL, "streaming is not supported with beam search (hypotheses are only final at the end; HF refuses too)");
         if (sp->n_stop > 0 && !sp->stop_ids) return fail(SV_EINVAL, "n_stop > 0 but stop_ids is null");
@@ -543,7 +614,7 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t Bp, in
         // the selection, and the tokens are bit-identical either way (tests/test_gpu_e2e.py)
         // (a ban rewrites the logits row between the lm_head and the selection: the separate launch as well)
         fused_sel = !sp->do_sample && !pen && sp->min_new_tokens <= 0 && B <= 32 && !e->lm_head.fp8 && waves > 1 && !two && !(e->exp & SV_EXP_SEPARATE_ARGMAX) &&
-                    !e->cap_on && !ban;
+                    !e->cap_on && !ban && !e->ts_on;      // (the statistics launch reads the row and the slice winners between the lm_head and the bookkeeping)
     }
     // generation state, one launch: positions = S0 - 1 (finish_step adds 1), unfinished = 1, {step, done, n_emitted} = 0, the folded selection's key slots = 0
     gen_state_init(e->positions, S0 - 1, e->unfinished, B, e->d_step, e->amax, fused_sel ? 64 * SV_AMAX_STRIDE : 0, st);
@@ -608,6 +679,8 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t Bp, in
             snprintf(key + strlen(key), sizeof(key) - strlen(key), "|cap%d", (e->cap_host.scores ? 1 : 0) | (e->cap_host.logits ? 2 : 0));
         if (ban || e->minp_log > -INFINITY)      // the ban launch / the sampler's min_p argument (the bad-word ids live in device memory, not in the graph);
             snprintf(key + strlen(key), sizeof(key) - strlen(key), "|ng%d|bw%d|mp%a", e->ban_ngram, e->ban_nwords, e->minp_log);      // neither: the plain call's key and graph
+        if (e->ts_on)        // a statistics step carries one or two launches more; the buffers (and which of them are asked for) are read through ts_desc
+            snprintf(key + strlen(key), sizeof(key) - strlen(key), "|ts");
         if (e->gen_gexec && e->gen_graph_key == key) {
             gexec = e->gen_gexec;
         } else {

@@ -212,6 +212,12 @@ struct sv_engine {
     CaptureDesc cap_host = {};
     float* cap_warp = nullptr;
     bool cap_on = false;
+    // sv_generate_stats: the device descriptor of the caller's three [rows][ld] buffers (rewritten for every call, like cap_desc), its host image, the
+    // raw row's {max, log-sum, entropy} per row; ts_on = the current call asks for statistics (set and cleared by it)
+    TokenStatsDesc* ts_desc = nullptr;
+    TokenStatsDesc ts_host = {};
+    float* ts_raw = nullptr;
+    bool ts_on = false;
     // sv_generate_processed: the HF logits processors of the current call (set and cleared by it).  A ban (no_repeat_ngram_size, bad words) adds
     // one launch between the lm_head and the selection (processors.hip); min_p rides in the sampler's arguments.  The bad-word table is device
     // memory of the engine, uploaded once per call (ban_host = its host image, kept alive for the upload)

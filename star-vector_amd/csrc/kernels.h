@@ -367,6 +367,38 @@ struct CaptureArgs {
                                                                      //   takes them apart: raw row -> ban_tokens_kernel -> processed row)
 };
 void launch_capture_rows(const CaptureArgs& a, hipStream_t st);
+
+// ---- per-token statistics of sv_generate_stats: for the token row b emits at the device step t = *step, three fp32 values at [b][t] of the
+// caller's [rows][ld] buffers (reached through a device-resident descriptor, like CaptureDesc: a kept graph writes each call's own buffers)
+//   logprob   = log_softmax(x / T)[tok], x the raw lm_head row, T = temperature when do_sample, else 1
+//   entropy   = entropy of softmax(x / T)                                   (score.hip's definition)
+//   processed = log_softmax(s)[tok], s the row the selection ranks -- bans, repetition penalty, min-length hold, and (do_sample) s / T with the
+//               ids outside TopK -> TopP -> min_p at -inf.  The kept set is the CAPTURE's (capture_warp_kernel: the sampler's score functor through
+//               row_warp_stats and wp_keep), so the value is log_softmax of the dev_scores row bit for bit in its inputs; with 0 < top_k <= 256 the
+//               sampler itself draws through sample_row_topk, whose top-p test has no round-off slack -- its kept set lies inside this one
+// A row that had finished before step t gets 0 in all three.  The launch sits BETWEEN the selection and finish_step_kernel: the token is known
+// (next, or the AM_SPLIT slice winners of the greedy path), while *step, *done, unfinished[] and the seen bitmap still describe step t.
+struct TokenStatsDesc {
+    float* logprob; float* processed; float* entropy;    // [rows][ld] each, nullptr: not requested
+    long long ld;                                        // >= max_new
+    int rows, max_new;
+};
+struct TokenStatsArgs {
+    const TokenStatsDesc* desc;
+    const float* src; int ld_src; int V; int B;
+    const int32_t* step; const int32_t* done; const int32_t* unfinished;
+    const int32_t* next;                                             // sampling: [B] drawn ids
+    const float* pval; const int32_t* pidx;                          // greedy: [B][8] slice winners (nullptr when sampling)
+    const uint32_t* seen; int seen_words; float penalty;             // seen = nullptr: penalty off
+    int eos, min_new;                                                // min_new <= 0: hold off
+    int do_sample; float temperature, top_p; int top_k;
+    float minp_log = -INFINITY;
+    float* raw;                                                      // [B][4] {max, log sum exp(x - max), entropy} of the raw row
+    int what = 3;                                                    // 1 = the raw row's statistics into `raw` (a call whose step rewrites the row in place -- a
+                                                                     //   ban, the min-length hold -- takes them in front of the rewrite), 2 = the outputs, from
+                                                                     //   `raw` and the row as the selection saw it, 3 = both in one launch
+};
+void launch_token_stats(const TokenStatsArgs& a, hipStream_t st);
 #ifdef __HIPCC__
 // one thread block's share of a captured row: out[j] = f(j) for j in [0, V), with 16-byte stores wherever `out` allows (the slab
 // rows are ld floats apart, ld need not be a multiple of 4); the block takes quads [q0, q1) of the aligned body, block 0 the

@@ -436,6 +436,99 @@ void launch_capture_rows(const CaptureArgs& a, hipStream_t st) {
     capture_write_kernel<<<dim3(a.B, (a.V + 4 * CAP_QPB - 1) / (4 * CAP_QPB)), 256, 0, st>>>(a);
 }
 
+// ------------------------------------------------------------------------------------------------
+// sv_generate_stats: log-prob, processed log-prob and entropy of the token each row emits (TokenStatsArgs, kernels.h).  One 1024-thread block per
+// row, every reduction in fp32 and in a fixed order (a thread's columns ascending, xor butterfly inside a wave, waves in wave order).
+//   max-shifted sums, as score.hip: m = max x, s = sum exp(x - m), u = sum exp(x - m) (x - m);  lse = m + log s, entropy = log s - u / s
+// ------------------------------------------------------------------------------------------------
+template <class F>
+__device__ __forceinline__ void ts_row_sums(F x, int V, float* red, float& m, float& ls, float& ent) {
+    const int tid = threadIdx.x;
+    float mx = -INFINITY;
+    for (int i = tid; i < V; i += SP_THREADS) mx = fmaxf(mx, x(i));
+    mx = wp_block_max(mx, red);
+    float s = 0.f, u = 0.f;
+    for (int i = tid; i < V; i += SP_THREADS) {
+        const float d = x(i) - mx;
+        const float ex = expf(d);
+        s += ex;
+        u += ex > 0.f ? ex * d : 0.f;                                // a term with e = 0 (x = -inf included) adds 0
+    }
+    s = wp_block_sum(s, red);
+    u = wp_block_sum(u, red);
+    m = mx;
+    ls = logf(s);
+    ent = ls - u / s;
+}
+
+__global__ __launch_bounds__(SP_THREADS) void token_stats_kernel(TokenStatsArgs p) {
+    __shared__ float red[SP_THREADS / 64];
+    if (*p.done) return;
+    const TokenStatsDesc d = *p.desc;
+    const int t = *p.step;
+    const int b = blockIdx.x;
+    if (t < 0 || t >= d.max_new || b >= d.rows) return;
+    const bool live = p.unfinished[b] != 0;                          // block-uniform
+    const float* row = p.src + (size_t)b * p.ld_src;
+    float* raw = p.raw + (size_t)b * 4;
+    const float T = p.do_sample ? p.temperature : 1.0f;
+    const size_t o = (size_t)b * (size_t)d.ld + (size_t)t;
+    if (!live) {                                                     // finished before this step: 0, what completion_logprobs returns at pads
+        if ((p.what & 2) && threadIdx.x == 0) {
+            if (d.logprob) d.logprob[o] = 0.f;
+            if (d.processed) d.processed[o] = 0.f;
+            if (d.entropy) d.entropy[o] = 0.f;
+        }
+        return;
+    }
+    float m, ls, ent;
+    if (p.what & 1) {
+        ts_row_sums([&](int i) { return row[i] / T; }, p.V, red, m, ls, ent);
+        if (!(p.what & 2)) {
+            if (threadIdx.x == 0) { raw[0] = m; raw[1] = ls; raw[2] = ent; }
+            return;
+        }
+    } else {
+        m = raw[0]; ls = raw[1]; ent = raw[2];
+    }
+    int tok;
+    if (p.pval) {                                                    // greedy: the merge finish_step_kernel does
+        float best = -INFINITY;
+        tok = 0x7fffffff;
+        for (int s = 0; s < AM_SPLIT; ++s) argmax_pair(best, tok, p.pval[b * AM_SPLIT + s], p.pidx[b * AM_SPLIT + s]);
+    } else {
+        tok = p.next[b];
+    }
+    if ((unsigned)tok >= (unsigned)p.V) tok = 0;                     // no finite logit: finish_step_row emits 0 and raises the call's flag
+    // the emitted id is never a banned or held one: row[tok] is still its raw value after the in-place rewrites
+    if (threadIdx.x == 0) {
+        if (d.logprob) d.logprob[o] = (row[tok] / T - m) - ls;
+        if (d.entropy) d.entropy[o] = ent;
+    }
+    if (!d.processed) return;
+    const uint32_t* srow = p.seen ? p.seen + (size_t)b * p.seen_words : nullptr;
+    const int eos = t < p.min_new ? p.eos : -1;                      // MinLength: the EOS id at -inf while held
+    const float pen = p.penalty;
+    auto base = [&](int i) { return i == eos ? -INFINITY : rep_penalty(row[i], i, srow, pen); };
+    float pm, pls, pent, stok;
+    if (p.do_sample) {
+        // the capture's thresholds (capture_warp_kernel): the sampler's score functor through row_warp_stats; kept = the sampler's test on the
+        // sampler's value (s * invT), the value that is normalised = HF's TemperatureLogitsWarper, s / T (capture_write_kernel)
+        const float invT = 1.0f / p.temperature;
+        WarpStats w = row_warp_stats<false, true>([&](int i) { return base(i) * invT; }, p.V, p.top_k, p.top_p, 1, red);
+        w.mthr = wp_minp_thr(w.mx, p.minp_log);
+        ts_row_sums([&](int i) { const float s = base(i); return wp_keep(w, s * invT) ? s / T : -INFINITY; }, p.V, red, pm, pls, pent);
+        stok = base(tok) / T;
+    } else {
+        ts_row_sums(base, p.V, red, pm, pls, pent);
+        stok = base(tok);
+    }
+    if (threadIdx.x == 0) d.processed[o] = (stok - pm) - pls;
+}
+void launch_token_stats(const TokenStatsArgs& a, hipStream_t st) {
+    token_stats_kernel<<<a.B, SP_THREADS, 0, st>>>(a);
+}
+
 __global__ void finish_step_kernel(FinishArgs p) {
     __shared__ int any_unf;
     if (*p.done) return;

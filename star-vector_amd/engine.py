@@ -105,6 +105,9 @@ class TokenLogprobs(NamedTuple):
     argmax: Optional[torch.Tensor] = None      # int32: the lowest index holding the row's maximum
 
 
+TOKEN_STATS = ("token_logprobs", "token_logprobs_processed", "token_entropies")      # HipEngine.generate(token_stats=...), sv_token_stats's order
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
@@ -409,7 +412,7 @@ class HipEngine:
                  early_stopping=False, top_k: int = 0, on_tokens=None, min_new_tokens: int = 0,
                  scores_out: Optional[torch.Tensor] = None, logits_out: Optional[torch.Tensor] = None,
                  return_outputs: bool = False, lengths: Optional[Sequence[int]] = None, n_samples: int = 1,
-                 logits_processors=None):
+                 logits_processors=None, token_stats: bool = False):
         """HF ``generate`` semantics for inputs_embeds: returns ONLY the new tokens, int64 [B, N].
         ``lengths``: the ragged form -- inputs_embeds is packed [sum(lengths), D], one prompt pass for all of them, ``max_length`` counts from
         the longest prompt (see ``generate_ragged``).
@@ -424,7 +427,14 @@ class HipEngine:
         B * num_beams under beam search; ld >= vocab) that receive HF's processed scores / raw logits of every generated column.
         ``return_outputs=True`` returns a dict {"sequences", "n_generated"} plus, under beam search, "sequences_scores" [B] and
         "beam_indices" [B, n] int64 instead of the bare token tensor.
-        ``logits_processors``: what ``logits_processors(...)`` returns; the call then goes through sv_generate_processed (see ``generate_processed``)."""
+        ``logits_processors``: what ``logits_processors(...)`` returns; the call then goes through sv_generate_processed (see ``generate_processed``).
+        ``token_stats=True`` (sv_generate_stats; greedy and sampling, not beam search): the call returns the ``return_outputs`` dict with three
+        more fp32 device tensors [rows, n_generated] -- "token_logprobs" (log_softmax(raw logits / T) at the emitted token, T = temperature when
+        do_sample, else 1), "token_logprobs_processed" (log_softmax of the processed scores at it: HF's compute_transition_scores with
+        normalize_logits=True) and "token_entropies" (entropy of softmax(raw logits / T)); 0 after a row has finished.  The tokens are those of
+        the call without it; one more launch per decode step (two with a token ban or min_new_tokens), no [rows, vocab] output.  A tuple of
+        those three names instead of True asks for them alone: without "token_logprobs_processed" the launch skips the warper thresholds and
+        the second sweep of the row."""
         lens_arr = None
         if lengths is not None:
             x, lens_arr, lens = self._packed(inputs_embeds, lengths)
@@ -442,6 +452,8 @@ class HipEngine:
             lp, _lp_keep = logits_processors              # the struct and the host arrays its pointers refer to
             if int(num_beams) > 1:
                 raise ValueError("no_repeat_ngram_size / bad_words_ids / min_p with num_beams > 1 is not built")
+        if token_stats and int(num_beams) > 1:
+            raise ValueError("token_stats with num_beams > 1 is not built (beam search reports sequences_scores; beam rows reorder)")
         n_prompts = B
         if G > 1 and int(num_beams) > 1:
             raise NotImplementedError("n_samples > 1 under beam search (num_beams > 1) is not built")
@@ -463,7 +475,7 @@ class HipEngine:
             sp.on_tokens = C.cast(cb, C.c_void_p)
         out = torch.empty(B, max_new, dtype=torch.int64, device=x.device)
         n = C.c_int32(0)
-        if scores_out is None and logits_out is None and not return_outputs:
+        if scores_out is None and logits_out is None and not return_outputs and not token_stats:
             if lp is not None:
                 check(self.lib.sv_generate_processed(self._h, _ptr(x), n_prompts, lens_arr, S0, G, C.byref(sp), C.byref(lp), None, _ptr(out),
                                                      C.byref(n), _stream()), "sv_generate_processed")
@@ -500,7 +512,16 @@ class HipEngine:
         if beam:
             outs.host_sequences_scores = C.cast(seq_scores, C.POINTER(C.c_float))
             outs.host_beam_indices = C.cast(beam_idx, C.POINTER(C.c_int64))
-        if lp is not None:
+        stats = None
+        if token_stats:
+            names = TOKEN_STATS if token_stats is True else tuple(token_stats)
+            if not names or any(k not in TOKEN_STATS for k in names):
+                raise ValueError(f"token_stats must be True or a non-empty tuple of {TOKEN_STATS}, got {token_stats!r}")
+            stats = {k: torch.empty(B, max_new, dtype=torch.float32, device=x.device) for k in TOKEN_STATS if k in names}
+            ts = _lib.SvTokenStats(*[_ptr(stats.get(k)) for k in TOKEN_STATS], max_new)
+            check(self.lib.sv_generate_stats(self._h, _ptr(x), n_prompts, lens_arr, S0, G, C.byref(sp), C.byref(lp) if lp is not None else None,
+                                             C.byref(outs), C.byref(ts), _ptr(out), C.byref(n), _stream()), "sv_generate_stats")
+        elif lp is not None:
             check(self.lib.sv_generate_processed(self._h, _ptr(x), n_prompts, lens_arr, S0, G, C.byref(sp), C.byref(lp), C.byref(outs), _ptr(out),
                                                  C.byref(n), _stream()), "sv_generate_processed")
         elif G > 1:
@@ -515,9 +536,11 @@ class HipEngine:
         if cb_errors:
             raise cb_errors[0]
         L = n.value
-        if not return_outputs:
+        if not return_outputs and stats is None:
             return out[:, :L]
         res = {"sequences": out[:, :L], "n_generated": L}
+        if stats is not None:
+            res.update({k: v[:, :L] for k, v in stats.items()})
         if beam:
             res["sequences_scores"] = torch.tensor(list(seq_scores), dtype=torch.float32)
             res["beam_indices"] = torch.tensor(list(beam_idx), dtype=torch.int64).view(B, max_new)[:, :L].contiguous()

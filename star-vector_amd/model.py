@@ -629,7 +629,7 @@ class HipCausalLM(_EngineModule):
                  num_return_sequences: int = 1, top_k: Optional[int] = 50, streamer=None, seed: Optional[int] = None,
                  return_dict_in_generate: bool = False, output_scores: bool = False, output_logits: bool = False,
                  share_prompt: bool = True, no_repeat_ngram_size: int = 0, bad_words_ids=None, min_p: Optional[float] = None,
-                 **unused):
+                 output_token_logprobs: bool = False, **unused):
         # top_k: the reference never passes it; its pinned transformers==4.49.0 (pyproject.toml:18) defaults
         # GenerationConfig.top_k to 50, so every do_sample call there is top-k 50 followed by top-p.  Same default here.
         if inputs_embeds is None:
@@ -645,6 +645,20 @@ class HipCausalLM(_EngineModule):
                                           "are generated group by group, without HF's common step axis")
         outputs = dict(return_dict_in_generate=True, output_scores=output_scores, output_logits=output_logits) \
             if return_dict_in_generate else {}
+        # output_token_logprobs (an extension, not an HF argument; read with return_dict_in_generate like output_scores): the returned object
+        # also carries token_logprobs, token_logprobs_processed and token_entropies [rows, n_new], computed inside the decode loop
+        # (sv_generate_stats) -- no [steps, rows, vocab] slab.  Where that route is not built the call raises, it never drops the argument.
+        stats = bool(return_dict_in_generate and output_token_logprobs)
+        if stats:
+            if int(num_beams) > 1:
+                raise NotImplementedError("output_token_logprobs with num_beams > 1 is not built: beam search reports sequences_scores, and "
+                                          "beam rows reorder")
+            if attention_mask is not None and not bool((attention_mask == 1).all()):
+                raise NotImplementedError("output_token_logprobs with a padded attention_mask is not built: padded rows run as "
+                                          "continuous-batching slots, which keep no per-token statistics")
+            if getattr(self, "batcher", None) is not None:
+                raise NotImplementedError("output_token_logprobs with a batcher attached is not built: its requests run as "
+                                          "continuous-batching slots, which keep no per-token statistics")
         # HF's token-changing processors, on device (sv_generate_processed): NoRepeatNGram, NoBadWords, MinP.  Set = the call goes through
         # HipEngine.generate_processed; where that route is not built the call raises, it never drops the argument.
         proc = self._processor_args(no_repeat_ngram_size, bad_words_ids, min_p, do_sample, eos_token_id)
@@ -761,8 +775,10 @@ class HipCausalLM(_EngineModule):
                 streamer.end()
             return generate_output(False, sequences=out) if return_dict_in_generate else out
         extra, slabs = {}, {}
-        if return_dict_in_generate and (want or num_beams > 1):
+        if return_dict_in_generate and (want or num_beams > 1 or stats):
             extra, slabs = self._output_slabs(inputs_embeds, max_length, num_beams, output_scores, output_logits, G)
+            if stats:       # True: all three; a tuple of the field names: those alone (generate_im2svg_grpo leaves the processed log-prob out)
+                extra["token_stats"] = True if output_token_logprobs is True else tuple(output_token_logprobs)
         lock = getattr(self._engine, "call_lock", None) or contextlib.nullcontext()
         with lock:          # the same lock the slot path holds: a classic generate never lands between its cb_reset / cb_admit
             out = self._classic_generate(inputs_embeds, max_length, do_sample, temperature, top_p, eos_token_id, pad_token_id,
@@ -782,7 +798,13 @@ class HipCausalLM(_EngineModule):
             dev = out["sequences"].device
             fields["beam_indices"] = out["beam_indices"].to(dev)
             fields["sequences_scores"] = out["sequences_scores"].to(dev) if output_scores else None
-        return generate_output(num_beams > 1, **fields)
+        if not stats:
+            return generate_output(num_beams > 1, **fields)
+        # the extension's three fields beside HF's: HF's output dataclass has no place for them, so the object is the stand-in with the same
+        # field names, read as attributes or as keys
+        res = _GenerateOutput({k: fields.get(k) for k in _DECODER_ONLY_FIELDS})
+        res.update({k: out.get(k) for k in ("token_logprobs", "token_logprobs_processed", "token_entropies")})
+        return res
 
     def _processor_args(self, no_repeat_ngram_size, bad_words_ids, min_p, do_sample, eos_token_id):
         """HF's own checks of no_repeat_ngram_size / bad_words_ids / min_p (generation/logits_process.py, transformers 4.49), then the
@@ -879,6 +901,16 @@ class HipCausalLM(_EngineModule):
             num_beams=num_beams, length_penalty=float(length_penalty if length_penalty is not None else 1.0),
             early_stopping=early_stopping, top_k=int(top_k or 0), on_tokens=on_tokens,
             sync_every=8 if streamer is not None else 32, **({"min_new_tokens": min_new} if min_new else {}), **outputs)
+
+
+def completion_mask(new_tokens: torch.Tensor, eos_token_id: int) -> torch.Tensor:
+    """[rows, n_new] int64: 1 up to and including the token that ended the row -- its first EOS; the last column for a row that ran to the end
+    of the call (the budget, or the stop sequence on row 0, which ends every row at that column) -- and 0 on the pads behind an EOS."""
+    n = new_tokens.shape[1]
+    cols = torch.arange(n, device=new_tokens.device).unsqueeze(0)
+    is_eos = new_tokens == int(eos_token_id)
+    first = torch.where(is_eos.any(dim=1), is_eos.int().argmax(dim=1), torch.full_like(new_tokens[:, 0], n - 1).to(torch.int64))
+    return (cols <= first.unsqueeze(1)).to(torch.int64)
 
 
 class StoppingCriteriaSub:
@@ -1028,10 +1060,24 @@ class StarVectorStarCoder(nn.Module):
             generation_kwargs["num_beams"] = 1
             if "share_prompt" in kwargs:                               # extension: False = the repeated prompts (A/B)
                 generation_kwargs["share_prompt"] = kwargs["share_prompt"]
-        outputs = self.svg_transformer.transformer.generate(**generation_kwargs)
-        outputs = torch.cat([prompt_tokens.input_ids.repeat(num_return_sequences, 1), outputs], dim=1)    # :279
+        if not kwargs.get("return_logprobs"):
+            outputs = self.svg_transformer.transformer.generate(**generation_kwargs)
+            outputs = torch.cat([prompt_tokens.input_ids.repeat(num_return_sequences, 1), outputs], dim=1)    # :279
+            raw_svg = self.svg_transformer.tokenizer.batch_decode(outputs, skip_special_tokens=True)
+            return {"raw_svg": raw_svg, "outputs": outputs, "inputs_embeds": inputs_embeds}
+        # extension (return_logprobs=True): the roll-out policy's own per-token log-probs and entropies from the decode loop (GRPO's old
+        # log-probs: log_softmax(logits / temperature) at every sampled token, what completion_logprobs returns for the same weights), and the
+        # mask of the columns that belong to each completion
+        gen = self.svg_transformer.transformer.generate(**generation_kwargs, return_dict_in_generate=True,
+                                                      output_token_logprobs=("token_logprobs", "token_entropies"))
+        new = gen["sequences"]
+        lm = self.svg_transformer.transformer
+        eos = generation_kwargs.get("eos_token_id")
+        outputs = torch.cat([prompt_tokens.input_ids.repeat(num_return_sequences, 1), new], dim=1)    # :279
         raw_svg = self.svg_transformer.tokenizer.batch_decode(outputs, skip_special_tokens=True)
-        return {"raw_svg": raw_svg, "outputs": outputs, "inputs_embeds": inputs_embeds}
+        return {"raw_svg": raw_svg, "outputs": outputs, "inputs_embeds": inputs_embeds,
+                "logprobs": gen["token_logprobs"], "entropies": gen["token_entropies"],
+                "completion_mask": completion_mask(new, int(lm.eos_token_id if eos is None else eos))}
 
 
 class StarVectorStarCoder2(StarVectorStarCoder):
