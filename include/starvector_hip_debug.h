@@ -238,6 +238,16 @@ int  sv_op_cvt_bf16_hw(const float* x, void* y, int64_t n, sv_stream stream);
 int  sv_op_attention(const void* q, const void* k, const void* v, void* out, int32_t B, int32_t S,
                      int32_t H, int32_t Hkv, int32_t head_dim, int32_t causal, float scale,
                      sv_stream stream);
+/* The same kernel in the forms the engine's prompt pass launches: q, k, v are the column ranges [q_off, q_off + H*D), [k_off, k_off + Hkv*D),
+ * [v_off, v_off + Hkv*D) of ONE bf16 token-major buffer qkv [rows][row_stride] (offsets and stride in elements, multiples of 8; MQA reads its
+ * single KV head with head stride 0); out [rows][H*D].  window > 0 (causal only): query i sees keys i - window < j <= i.  host_lens == NULL:
+ * B sequences of S rows, last_rows > 0 launches only the query tiles that hold the last `last_rows` rows of every sequence (the other rows of
+ * `out` are not written).  host_lens != NULL (HOST array of B lengths >= 1, causal only; S ignored): the ragged form over packed rows, block
+ * lists from the engine's own planner, last_rows > 0 = each sequence's last query tile alone.  Every argument is checked before any device
+ * work (SV_EINVAL). */
+int  sv_op_attention_prefill(const void* qkv, int32_t q_off, int32_t k_off, int32_t v_off, int32_t row_stride, void* out, int32_t B,
+                             int32_t S, const int32_t* host_lens, int32_t H, int32_t Hkv, int32_t head_dim, int32_t causal,
+                             float scale, int32_t window, int32_t last_rows, sv_stream stream);
 int  sv_op_plane_layernorm(const void* x, const void* gamma, const void* beta, void* y, int32_t B,
                            int32_t QD, float eps, sv_stream stream);
 int  sv_op_argmax(const float* logits, int32_t B, int32_t V, int32_t ld, int32_t* out, sv_stream stream);

@@ -197,6 +197,7 @@ DEBUG_PROTOTYPES = {
     "sv_bench_decode_linear": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(C.c_double), _P]),
     "sv_op_cvt_bf16_hw": (_I, [_P, _P, C.c_int64, _P]),
     "sv_op_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
+    "sv_op_attention_prefill": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, C.POINTER(_I), _I, _I, _I, _I, _F, _I, _I, _P]),
     "sv_op_plane_layernorm": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
     "sv_op_argmax": (_I, [_P, _I, _I, _I, _P, _P]),
     "sv_op_sample_top_p": (_I, [_P, _I, _I, _I, _F, _F, C.c_uint64, _I, _P, _P]),

@@ -815,6 +815,70 @@ extern "C" int sv_op_attention(const void* q, const void* k, const void* v, void
     return 0;
 }
 
+// attn_prefill_kernel in the forms the engine launches it: q / k / v as column ranges of ONE token-major buffer (the c_attn output), MQA with
+// kv_head_stride 0, the sliding window, the trailing query tiles alone (last_rows) and the ragged form (host_lens).  The arguments are filled
+// as prefill_forward / prefill_forward_ragged fill them; everything is checked on the host first, so that what passes keeps every access of
+// the kernel inside rows * row_stride elements of `qkv` and rows * H * head_dim elements of `out` (the kernel clamps rows to the last row of
+// their sequence, a 16-byte load starts at a multiple of 8 elements inside its head, and an output row is written only when it exists).
+extern "C" int sv_op_attention_prefill(const void* qkv, int32_t q_off, int32_t k_off, int32_t v_off, int32_t row_stride, void* out, int32_t B,
+                                       int32_t S, const int32_t* host_lens, int32_t H, int32_t Hkv, int32_t head_dim, int32_t causal,
+                                       float scale, int32_t window, int32_t last_rows, sv_stream stream) {
+    const char* who = "sv_op_attention_prefill";
+    if (!qkv || !out) return fail(SV_EINVAL, "%s: null pointer", who);
+    if (B < 1 || H < 1 || Hkv < 1 || H > 4096) return fail(SV_EINVAL, "%s: bad shape (B %d, H %d, Hkv %d)", who, B, H, Hkv);
+    if (H % Hkv) return fail(SV_EINVAL, "%s: %d query heads are not a multiple of %d KV heads", who, H, Hkv);
+    if (head_dim != 64 && head_dim != 128) return fail(SV_EINVAL, "%s: head_dim %d unsupported (64|128)", who, head_dim);
+    if (q_off < 0 || k_off < 0 || v_off < 0 || row_stride < 8 || (q_off | k_off | v_off | row_stride) % 8)
+        return fail(SV_EINVAL, "%s: offsets %d / %d / %d and row stride %d must be non-negative multiples of 8 elements (16-byte loads)", who,
+                    q_off, k_off, v_off, row_stride);
+    if ((long long)q_off + (long long)H * head_dim > row_stride || (long long)k_off + (long long)Hkv * head_dim > row_stride ||
+        (long long)v_off + (long long)Hkv * head_dim > row_stride)
+        return fail(SV_EINVAL, "%s: q / k / v columns (%d + %d x %d, %d + %d x %d, %d + %d x %d) reach beyond the row stride %d", who, q_off,
+                    H, head_dim, k_off, Hkv, head_dim, v_off, Hkv, head_dim, row_stride);
+    if (!(scale > 0.f) || std::isinf(scale)) return fail(SV_EINVAL, "%s: scale must be positive and finite", who);
+    if (window < 0) return fail(SV_EINVAL, "%s: window %d < 0", who, window);
+    if (window > 0 && !causal) return fail(SV_EINVAL, "%s: a window needs causal = 1", who);
+    if (host_lens && !causal) return fail(SV_EINVAL, "%s: the ragged form (lengths) needs causal = 1", who);
+    if (last_rows < 0) return fail(SV_EINVAL, "%s: last_rows %d < 0", who, last_rows);
+    long long rows = 0;
+    if (host_lens) {
+        for (int b = 0; b < B; ++b) {
+            if (host_lens[b] < 1) return fail(SV_EINVAL, "%s: length %d of sequence %d (must be >= 1)", who, host_lens[b], b);
+            rows += host_lens[b];
+        }
+    } else {
+        if (S < 1) return fail(SV_EINVAL, "%s: S %d < 1", who, S);
+        rows = (long long)B * S;
+    }
+    if (rows > (1 << 24) || B > 65535) return fail(SV_EINVAL, "%s: %lld rows / %d sequences: more than this test surface takes", who, rows, B);
+
+    hipStream_t st = (hipStream_t)stream;
+    AttnPrefillArgs a;
+    a.q = (const bf16_t*)qkv + q_off; a.k = (const bf16_t*)qkv + k_off; a.v = (const bf16_t*)qkv + v_off;
+    a.q_row_stride = row_stride; a.kv_row_stride = row_stride; a.q_head_stride = head_dim; a.kv_head_stride = Hkv > 1 ? head_dim : 0;
+    a.o = (bf16_t*)out; a.o_row_stride = H * head_dim; a.B = B; a.S = host_lens ? 0 : S; a.H = H; a.head_dim = head_dim;
+    a.kv_group = H / Hkv; a.causal = causal ? 1 : 0; a.scale = scale; a.window = window;
+    TmpBufs tmp;
+    if (host_lens) {
+        // descriptors {first packed row, length} | the engine's own block list (every query tile, or each sequence's last one)
+        std::vector<int32_t> plan((size_t)2 * B), blocks;
+        int r0 = 0;
+        for (int b = 0; b < B; ++b) { plan[2 * b] = r0; plan[2 * b + 1] = host_lens[b]; r0 += host_lens[b]; }
+        ragged_blocks(host_lens, B, attn_prefill_q_tile(H, Hkv), last_rows > 0, blocks);
+        plan.insert(plan.end(), blocks.begin(), blocks.end());
+        int32_t* d_plan;
+        SVCHECK(tmp.get(&d_plan, plan.size()));
+        HIPCHECK(hipMemcpyAsync(d_plan, plan.data(), plan.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        a.rag_seq = d_plan; a.rag_blocks = d_plan + (size_t)2 * B; a.rag_nblocks = (int)blocks.size() / 2;
+    } else {
+        a.last_rows = last_rows;
+    }
+    launch_attn_prefill(a, st);
+    HIPCHECK(hipGetLastError());
+    if (host_lens) HIPCHECK(hipStreamSynchronize(st));          // the plan is freed on return
+    return 0;
+}
+
 extern "C" int sv_op_plane_layernorm(const void* x, const void* gamma, const void* beta, void* y, int32_t B, int32_t QD,
                                      float eps, sv_stream stream) {
     if (!x || !gamma || !beta || !y || B < 1 || QD < 8 || QD % 8) return fail(SV_EINVAL, "sv_op_plane_layernorm: bad argument");

@@ -1080,6 +1080,40 @@ def op_attention(q, k, v, n_head, n_kv_head, causal, scale=None):
     return out
 
 
+def op_attention_prefill(qkv, q_off, k_off, v_off, n_head, n_kv_head, head_dim, *, B=None, S=None, lens=None, causal=True,
+                         window=0, last_rows=0, scale=None, out=None):
+    """The prompt-pass attention as the engine launches it: q / k / v are column ranges (element offsets) of the rows of ONE bf16
+    buffer `qkv` [rows, row_stride].  Either (B, S) or `lens` (a list of lengths: the ragged form over packed rows).  `out`
+    ([rows, n_head * head_dim], bf16, contiguous) may be handed in pre-filled: with last_rows > 0 only the trailing query tiles
+    are written.  Returns `out`."""
+    lib = _lib.load()
+    if not qkv.is_cuda or qkv.dtype != torch.bfloat16 or qkv.dim() != 2 or not qkv.is_contiguous():
+        raise ValueError("qkv must be a contiguous 2-D bfloat16 CUDA(HIP) tensor [rows, row_stride]")
+    if (lens is None) == (B is None or S is None):
+        raise ValueError("give either B and S or lens")
+    if lens is not None:
+        lens = [int(x) for x in lens]
+        B, S = len(lens), 0
+        rows = sum(max(x, 0) for x in lens)
+        c_lens = (C.c_int32 * max(B, 1))(*lens)
+    else:
+        B, S = int(B), int(S)
+        rows = max(B, 0) * max(S, 0)
+        c_lens = None
+    stride, width = qkv.shape[1], int(n_head) * int(head_dim)
+    # the kernel addresses rows * row_stride elements of qkv and rows * n_head * head_dim of out: both must lie inside the tensors
+    if rows > qkv.shape[0]:
+        raise ValueError(f"qkv holds {qkv.shape[0]} rows, the call addresses {rows}")
+    if out is None:
+        out = torch.empty(rows, width, dtype=torch.bfloat16, device=qkv.device)
+    elif not out.is_cuda or out.dtype != torch.bfloat16 or not out.is_contiguous() or out.numel() < rows * width:
+        raise ValueError(f"out must be a contiguous bfloat16 CUDA(HIP) tensor of at least {rows} x {width} elements")
+    check(lib.sv_op_attention_prefill(_ptr(qkv), int(q_off), int(k_off), int(v_off), stride, _ptr(out), B, S, c_lens, int(n_head),
+                                      int(n_kv_head), int(head_dim), int(bool(causal)), float(scale if scale is not None else head_dim ** -0.5),
+                                      int(window), int(last_rows), _stream()), "sv_op_attention_prefill")
+    return out
+
+
 def op_plane_layernorm(x, gamma, beta, eps=1e-5):
     lib = _lib.load()
     x = _need(x, torch.bfloat16, "x"); B = x.shape[0]; QD = x[0].numel()
