@@ -20,6 +20,8 @@
  *                                    a forbidden token: no_repeat_ngram_size, bad_words_ids, min_p (sv_logits_processors below)
  *   sv_generate_stats      the same call, also returning each generated token's log-prob, processed log-prob and entropy (what a GRPO
  *                                    trainer otherwise gets from a second pass over prompt + completion; sv_token_stats below)
+ *   sv_generate_topk       the same call, also returning the k most likely ids of every step, their log-probs and the emitted token's rank
+ *                                    (sv_token_topk below); sv_forward_topk does the same for the scoring pass
  *   sv_load_weight         ingests the reference state_dict keys (train/util.py:71 naming;
  *                          SURVEY.md section 8b "Weight names")
  *
@@ -368,6 +370,47 @@ typedef struct sv_token_stats {
 int  sv_generate_stats(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, int32_t S0, int32_t n_samples,
                        const sv_sampling* sp, const sv_logits_processors* lp, const sv_generate_outputs* outs, const sv_token_stats* stats,
                        int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream);
+/* ---- the k most likely ids of every step's distribution, their log-probs, and the rank of the emitted token (distillation from roll-outs,
+ * a confidence read-out, best-of-n diagnostics) without a [steps][rows][vocab] slab: sv_generate_topk = sv_generate_stats plus, for the token
+ * that row r emits in column t, k ids and k fp32 log-probs at [r][t][0..k) and the token's rank at [r][t] of the caller's device buffers.
+ *   source 0  the distribution of sv_token_stats.dev_logprob: log_softmax(x / T) over the step's raw row
+ *   source 1  the distribution of dev_logprob_processed: the processed row, the ids outside the kept set at -inf (they are never listed)
+ * Order: descending by value, equal values by ascending id (slot 0 is what greedy selection picks).  The key is the value BEFORE the division
+ * by T, so rounding after it never reorders or merges entries.  NaN and -inf never enter; with fewer than k ids that do (vocab < k, a kept
+ * set smaller than k) the tail slots hold id -1 and log-prob -inf.  A slot's log-prob is the expression that yields dev_logprob /
+ * dev_logprob_processed: the slot of the emitted id equals that statistic bit for bit.  rank = 1 + #{ i : x_i > x_tok } (vLLM's definition,
+ * NaN compares false).  A row that had finished before column t: ids -1, log-probs 0, rank 0.  A row without a comparable value: ids -1,
+ * rank 0, log-probs NaN.  A row's output depends on that row alone: the same bits in any batch and launch.
+ * Cost: one launch per step (one 1024-thread block per row) beside the statistics launch; with source 0 on a step that rewrites the raw row in
+ * place (a token ban, the min-length hold) it runs in front of the rewrite, where the token is not yet known -- dev_rank with source 0 and such a
+ * processor is SV_EINVAL (use source 1, or pass no dev_rank).  The captured step is keyed on (k, source, rank asked for); the buffers travel
+ * through a device descriptor, so a kept graph writes each call's own buffers and a plain or statistics call afterwards replays its own step.
+ * Tokens, *n_generated and the statistics are those of sv_generate_stats bit for bit.  topk NULL: exactly sv_generate_stats (stats may be
+ * NULL as well: sv_generate_processed).  SV_EINVAL before any device work for k outside 1..SV_TOPK_MAX, a NULL dev_ids / dev_logprobs,
+ * ld < max_new, num_beams > 1, source outside {0, 1} and the rank combination above. */
+#define SV_TOPK_MAX 32
+typedef struct sv_token_topk {
+    int32_t  k;              /* 1..SV_TOPK_MAX */
+    int32_t  source;         /* 0 = log_softmax(raw / T), 1 = processed scores */
+    int32_t* dev_ids;        /* [rows][ld][k] */
+    float*   dev_logprobs;   /* [rows][ld][k] */
+    int32_t* dev_rank;       /* [rows][ld], or NULL */
+    int64_t  ld;             /* >= max_new */
+} sv_token_topk;
+int  sv_generate_topk(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, int32_t S0, int32_t n_samples,
+                      const sv_sampling* sp, const sv_logits_processors* lp, const sv_generate_outputs* outs, const sv_token_stats* stats,
+                      const sv_token_topk* topk, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream);
+/* sv_forward_logprobs plus, for every kept position, the k best ids of softmax(logits / temperature) over the bf16 row, their log-probs
+ * (dev_topk_ids int32 / dev_topk_logprobs fp32, [B][n_keep][k]) and the rank of the target (dev_rank int32 [B][n_keep], may be NULL; target
+ * -100: rank 0).  Order, ties, the (-1, -inf) tail and the rank as in sv_generate_topk, keyed on the bf16 logit; a slot holds
+ * float(logit) * (1 / temperature) - logsumexp, the expression behind dev_logprob: the slot of the target equals dev_logprob bit for bit and
+ * slot 0's id is dev_argmax.  Computed chunk by chunk from the lm_head workspace like the log-probs: device memory does not grow with
+ * B x n_keep x vocab.  k = 0: exactly sv_forward_logprobs (the three new pointers are ignored).  The four outputs of sv_forward_logprobs may
+ * all be NULL when k > 0.  SV_EINVAL before any device work for k outside 0..SV_TOPK_MAX and for k > 0 with a NULL dev_topk_ids /
+ * dev_topk_logprobs. */
+int  sv_forward_topk(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S, int32_t n_keep, const int32_t* dev_targets, float temperature,
+                     float* dev_logprob, float* dev_logsumexp, float* dev_entropy, int32_t* dev_argmax, int32_t k, int32_t* dev_topk_ids,
+                     float* dev_topk_logprobs, int32_t* dev_rank, sv_stream stream);
 /* ---- continuous batching (the reference worker's 5 concurrent requests, serve/model_worker.py:161-172,
  * 216-229, as ONE decode loop).  Every row ("slot") of the engine's batch is an independent request: own sampling parameters,
  * budget, EOS, stop sequence (the reference's row-0 stop, starvector_base.py:9-20, is right for one request per generate call

@@ -273,6 +273,17 @@ int  sv_op_ban_tokens(float* dev_logits, int32_t B, int32_t V, int32_t ld, const
 int  sv_op_logprob_rows(const void* dev_logits_bf16, int32_t R, int32_t V, int32_t ld, const int32_t* dev_targets, float temperature,
                         float* dev_logprob, float* dev_logsumexp, float* dev_entropy, int32_t* dev_argmax, int32_t* host_flag2,
                         sv_stream stream);
+/* the kernel of sv_forward_topk (score.hip topk_rows_bf16_kernel) on the same rows: dev_logsumexp [R] is what sv_op_logprob_rows returned for
+ * them at the same temperature.  dev_topk_ids int32 / dev_topk_logprobs fp32 [R][k], 1 <= k <= SV_TOPK_MAX; dev_rank int32 [R] or NULL: the
+ * rank of dev_targets[r] (dev_targets NULL or -100: 0). */
+int  sv_op_topk_rows_bf16(const void* dev_logits_bf16, int32_t R, int32_t V, int32_t ld, const int32_t* dev_targets, float temperature,
+                          const float* dev_logsumexp, int32_t k, int32_t* dev_topk_ids, float* dev_topk_logprobs, int32_t* dev_rank,
+                          sv_stream stream);
+/* sv_generate_topk's source 0 on caller-given rows (sampling.hip token_topk_rows_kernel, the row function of the decode step): dev_logits
+ * [B][ld] fp32, V valid columns, one token per row (dev_tokens int32 [B]; NULL or an entry < 0: no rank, 0 is written).  Outputs: dev_ids int32 /
+ * dev_logprobs fp32 [B][k] = the k best ids of log_softmax(row / temperature) and their log-probs, dev_rank int32 [B] or NULL. */
+int  sv_op_token_topk(const float* dev_logits, int32_t B, int32_t V, int32_t ld, float temperature, const int32_t* dev_tokens, int32_t k,
+                      int32_t* dev_ids, float* dev_logprobs, int32_t* dev_rank, sv_stream stream);
 /*   sv_debug_set_score_chunk_rows  sv_forward_logprobs runs its lm_head over `rows` rows at a time from the next call on (a multiple of 256;
      0 = the default, 4096): lets a test force many chunks on a tiny model.  The outputs do not depend on it, bit for bit. */
 int  sv_debug_set_score_chunk_rows(sv_engine* e, int32_t rows);

@@ -96,6 +96,15 @@ class SvTokenStats(C.Structure):
     ]
 
 
+class SvTokenTopk(C.Structure):
+    # sv_generate_topk: the k best ids / log-probs of every step, device [rows][ld][k], and the emitted token's rank [rows][ld] (may be NULL)
+    _fields_ = [
+        ("k", C.c_int32), ("source", C.c_int32), ("dev_ids", C.c_void_p), ("dev_logprobs", C.c_void_p), ("dev_rank", C.c_void_p),
+        ("ld", C.c_int64),
+    ]
+
+
+TOPK_MAX = 32      # SV_TOPK_MAX
 LP_MAX_NGRAM, LP_MAX_BAD_WORDS, LP_MAX_BAD_WORD_LEN = 8, 64, 8
 
 
@@ -132,6 +141,9 @@ PRODUCT_PROTOTYPES = {
                                    C.POINTER(SvGenerateOutputs), _P, C.POINTER(_I), _P]),
     "sv_generate_stats": (_I, [_P, _P, _I, C.POINTER(_I), _I, _I, C.POINTER(SvSampling), C.POINTER(SvLogitsProcessors),
                                C.POINTER(SvGenerateOutputs), C.POINTER(SvTokenStats), _P, C.POINTER(_I), _P]),
+    "sv_generate_topk": (_I, [_P, _P, _I, C.POINTER(_I), _I, _I, C.POINTER(SvSampling), C.POINTER(SvLogitsProcessors),
+                              C.POINTER(SvGenerateOutputs), C.POINTER(SvTokenStats), C.POINTER(SvTokenTopk), _P, C.POINTER(_I), _P]),
+    "sv_forward_topk": (_I, [_P, _P, _I, _I, _I, _P, _F, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "sv_cb_admit_shared": (_I, [_P, _P, _I, C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(SvCbRequest), C.POINTER(_I), _P]),
     "sv_cb_admit_ragged": (_I, [_P, _P, _I, C.POINTER(_I), C.POINTER(SvCbRequest), C.POINTER(_I), _P]),
     "sv_forward_logits": (_I, [_P, _P, _I, _I, _I, _P, _P]),
@@ -204,6 +216,8 @@ DEBUG_PROTOTYPES = {
     "sv_op_sample": (_I, [_P, _I, _I, _I, _F, _I, _F, C.c_uint64, _I, _P, _P]),
     "sv_op_logprob_rows": (_I, [_P, _I, _I, _I, _P, _F, _P, _P, _P, _P, C.POINTER(_I), _P]),
     "sv_debug_set_score_chunk_rows": (_I, [_P, _I]),
+    "sv_op_topk_rows_bf16": (_I, [_P, _I, _I, _I, _P, _F, _P, _I, _P, _P, _P, _P]),
+    "sv_op_token_topk": (_I, [_P, _I, _I, _I, _F, _P, _I, _P, _P, _P, _P]),
     "sv_op_ban_tokens": (_I, [_P, _I, _I, _I, C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(SvLogitsProcessors), _P]),
     "sv_op_cb_select": (_I, [_P, _I, _I, _I, C.POINTER(SvCbRequest), C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(_I), _P]),
 }

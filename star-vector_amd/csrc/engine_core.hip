@@ -360,6 +360,7 @@ extern "C" int sv_destroy(sv_engine* e) {
     if (e->gen_graph_multi) (void)hipGraphDestroy(e->gen_graph_multi);
     if (e->score_ws) (void)hipFree(e->score_ws);
     if (e->score_chunk_ws) (void)hipFree(e->score_chunk_ws);
+    if (e->score_lse_ws) (void)hipFree(e->score_lse_ws);
     if (e->h_flags) (void)hipHostFree(e->h_flags);
     if (e->h_table) (void)hipHostFree(e->h_table);
     if (e->h_fork) (void)hipHostFree(e->h_fork);

@@ -292,6 +292,12 @@ int sveng::prefill_forward(sv_engine* e, const bf16_t* embeds, int B, int S0, hi
                 HIPCHECK(hipMalloc(reinterpret_cast<void**>(&e->score_chunk_ws), (size_t)chunk * e->Vpad * sizeof(bf16_t) + 16));
                 e->score_chunk_alloc = chunk;
             }
+            if (lp->k > 0 && !lp->lse && e->score_lse_alloc < chunk) {     // the chunk's lse travels from logprob_rows to topk_rows through this
+                if (e->score_lse_ws) (void)hipFree(e->score_lse_ws);
+                e->score_lse_ws = nullptr; e->score_lse_alloc = 0;
+                HIPCHECK(hipMalloc(reinterpret_cast<void**>(&e->score_lse_ws), (size_t)chunk * sizeof(float)));
+                e->score_lse_alloc = chunk;
+            }
             int32_t* flag = reinterpret_cast<int32_t*>(e->score_chunk_ws + (size_t)chunk * e->Vpad);
             fill_i32(flag, 0, 1, st);
             fill_i32(flag + 1, 0x7fffffff, 1, st);
@@ -304,8 +310,16 @@ int sveng::prefill_forward(sv_engine* e, const bf16_t* embeds, int B, int S0, hi
                 a.logprob = lp->logprob ? lp->logprob + r0 : nullptr; a.lse = lp->lse ? lp->lse + r0 : nullptr;
                 a.entropy = lp->entropy ? lp->entropy + r0 : nullptr; a.argmax = lp->argmax ? lp->argmax + r0 : nullptr;
                 a.bad = flag; a.row0 = (int)r0;
+                if (lp->k > 0 && !a.lse) a.lse = e->score_lse_ws;
                 prof_mark(e, PK_PF_ROWS, st);
                 launch_logprob_rows(a, st);
+                if (lp->k > 0) {                 // sv_forward_topk: the list and the rank from the same chunk, with the lse just written
+                    TopkRowsArgs tk;
+                    tk.logits = e->score_chunk_ws; tk.ld = e->Vpad; tk.V = c.vocab; tk.R = n; tk.targets = lp->targets + r0; tk.inv_t = lp->inv_t;
+                    tk.lse = a.lse; tk.k = lp->k; tk.ids = lp->topk_ids + r0 * (size_t)lp->k; tk.logprobs = lp->topk_logprobs + r0 * (size_t)lp->k;
+                    tk.rank = lp->rank ? lp->rank + r0 : nullptr;
+                    launch_topk_rows_bf16(tk, st);
+                }
             }
         } else {
             gemm(e, PK_PF_GEMM, hn, D, e->lm_head, nullptr, 0, lg, e->Vpad, (int)rows, ACT_NONE, 0, st);
@@ -844,23 +858,46 @@ extern "C" int sv_forward_logits(sv_engine* e, const void* dev_embeds, int32_t B
     return 0;
 }
 
+// sv_forward_logprobs and sv_forward_topk: k = 0 is the former, to the letter
+static int forward_logprobs(const char* who, sv_engine* e, const void* dev_embeds, int32_t B, int32_t S, int32_t n_keep,
+                            const int32_t* dev_targets, float temperature, float* dev_logprob, float* dev_logsumexp,
+                            float* dev_entropy, int32_t* dev_argmax, int32_t k, int32_t* dev_topk_ids, float* dev_topk_logprobs,
+                            int32_t* dev_rank, sv_stream stream);
 extern "C" int sv_forward_logprobs(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S, int32_t n_keep,
                                    const int32_t* dev_targets, float temperature, float* dev_logprob, float* dev_logsumexp,
                                    float* dev_entropy, int32_t* dev_argmax, sv_stream stream) {
+    return forward_logprobs("sv_forward_logprobs", e, dev_embeds, B, S, n_keep, dev_targets, temperature, dev_logprob, dev_logsumexp, dev_entropy,
+                            dev_argmax, 0, nullptr, nullptr, nullptr, stream);
+}
+extern "C" int sv_forward_topk(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S, int32_t n_keep, const int32_t* dev_targets,
+                               float temperature, float* dev_logprob, float* dev_logsumexp, float* dev_entropy, int32_t* dev_argmax, int32_t k,
+                               int32_t* dev_topk_ids, float* dev_topk_logprobs, int32_t* dev_rank, sv_stream stream) {
+    if (k == 0)
+        return forward_logprobs("sv_forward_logprobs", e, dev_embeds, B, S, n_keep, dev_targets, temperature, dev_logprob, dev_logsumexp, dev_entropy,
+                                dev_argmax, 0, nullptr, nullptr, nullptr, stream);
+    if (k < 0 || k > SV_TOPK_MAX) return fail(SV_EINVAL, "sv_forward_topk: k=%d must be in 0..%d", k, SV_TOPK_MAX);
+    if (!dev_topk_ids || !dev_topk_logprobs) return fail(SV_EINVAL, "sv_forward_topk: k=%d with a null dev_topk_ids / dev_topk_logprobs", k);
+    return forward_logprobs("sv_forward_topk", e, dev_embeds, B, S, n_keep, dev_targets, temperature, dev_logprob, dev_logsumexp, dev_entropy,
+                            dev_argmax, k, dev_topk_ids, dev_topk_logprobs, dev_rank, stream);
+}
+static int forward_logprobs(const char* who, sv_engine* e, const void* dev_embeds, int32_t B, int32_t S, int32_t n_keep,
+                            const int32_t* dev_targets, float temperature, float* dev_logprob, float* dev_logsumexp,
+                            float* dev_entropy, int32_t* dev_argmax, int32_t k, int32_t* dev_topk_ids, float* dev_topk_logprobs,
+                            int32_t* dev_rank, sv_stream stream) {
     // (the checks that need no engine come first: they are the same on a machine without a GPU)
-    if (!dev_embeds || !dev_targets) return fail(SV_EINVAL, "sv_forward_logprobs: null embeds / targets");
-    if (!dev_logprob && !dev_logsumexp && !dev_entropy && !dev_argmax) return fail(SV_EINVAL, "sv_forward_logprobs: every output pointer is null");
-    if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail(SV_EINVAL, "sv_forward_logprobs: temperature must be finite and > 0");
-    if (S < 1 || n_keep < 1 || n_keep > S) return fail(SV_EINVAL, "sv_forward_logprobs: n_keep=%d must be in 1..S (S=%d)", n_keep, S);
+    if (!dev_embeds || !dev_targets) return fail(SV_EINVAL, "%s: null embeds / targets", who);
+    if (k == 0 && !dev_logprob && !dev_logsumexp && !dev_entropy && !dev_argmax) return fail(SV_EINVAL, "%s: every output pointer is null", who);
+    if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail(SV_EINVAL, "%s: temperature must be finite and > 0", who);
+    if (S < 1 || n_keep < 1 || n_keep > S) return fail(SV_EINVAL, "%s: n_keep=%d must be in 1..S (S=%d)", who, n_keep, S);
     SVCHECK(check_ready(e));
-    if (B < 1 || B > e->cfg.max_batch) return fail(SV_EINVAL, "sv_forward_logprobs: bad B=%d (max_batch %d)", B, e->cfg.max_batch);
-    if (S > e->cfg.max_seq_len) return fail(SV_EINVAL, "sv_forward_logprobs: S=%d out of range (max_seq_len %d)", S, e->cfg.max_seq_len);
+    if (B < 1 || B > e->cfg.max_batch) return fail(SV_EINVAL, "%s: bad B=%d (max_batch %d)", who, B, e->cfg.max_batch);
+    if (S > e->cfg.max_seq_len) return fail(SV_EINVAL, "%s: S=%d out of range (max_seq_len %d)", who, S, e->cfg.max_seq_len);
     std::lock_guard<std::mutex> lk(e->mu);
     HIPCHECK(hipSetDevice(e->cfg.device));
     hipStream_t st = (hipStream_t)stream;
-    SVCHECK(cb_guard(e, "sv_forward_logprobs"));
+    SVCHECK(cb_guard(e, who));
     SVCHECK(assign_pages(e, B, S, st));
-    const ScoreLogprobs lp{dev_targets, 1.0f / temperature, dev_logprob, dev_logsumexp, dev_entropy, dev_argmax};
+    const ScoreLogprobs lp{dev_targets, 1.0f / temperature, dev_logprob, dev_logsumexp, dev_entropy, dev_argmax, k, dev_topk_ids, dev_topk_logprobs, dev_rank};
     SVCHECK(prefill_forward(e, (const bf16_t*)dev_embeds, B, S, st, n_keep, nullptr, nullptr, &lp));
     fill_i32(e->positions, S, B, st);
     e->cached_B = B;
@@ -870,11 +907,11 @@ extern "C" int sv_forward_logprobs(sv_engine* e, const void* dev_embeds, int32_t
     HIPCHECK(hipMemcpyAsync(flag, e->score_chunk_ws + (size_t)e->score_chunk_alloc * e->Vpad, sizeof(flag), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
     if (flag[0] & 2)
-        return fail(SV_EHIP, "sv_forward_logprobs: a row of logits had no finite value (NaN / Inf in the weights or inputs?); first at row %d "
-                             "(sequence %d, kept position %d)", flag[1], flag[1] / n_keep, flag[1] % n_keep);
+        return fail(SV_EHIP, "%s: a row of logits had no finite value (NaN / Inf in the weights or inputs?); first at row %d "
+                             "(sequence %d, kept position %d)", who, flag[1], flag[1] / n_keep, flag[1] % n_keep);
     if (flag[0] & 1)
-        return fail(SV_EINVAL, "sv_forward_logprobs: a target id outside [0, %d) that is not -100; first at row %d (sequence %d, kept position %d)",
-                    e->cfg.vocab, flag[1], flag[1] / n_keep, flag[1] % n_keep);
+        return fail(SV_EINVAL, "%s: a target id outside [0, %d) that is not -100; first at row %d (sequence %d, kept position %d)",
+                    who, e->cfg.vocab, flag[1], flag[1] / n_keep, flag[1] % n_keep);
     return 0;
 }
 

@@ -47,13 +47,32 @@ static void token_stats_step(sv_engine* e, int B, const sv_sampling& sp, hipStre
     a.minp_log = e->minp_log; a.raw = e->ts_raw; a.what = what;
     launch_token_stats(a, st);
 }
+// sv_generate_topk: the k best ids of this step's distribution and the rank of the emitted token (TokenTopkArgs, kernels.h)
+static_assert(SV_TOPK_MAX == SV_TOPK_MAX_DEV, "topk.h's list length is the ABI's");
+static void token_topk_step(sv_engine* e, int B, const sv_sampling& sp, hipStream_t st, bool want_rank) {
+    const bool pen = sp.repetition_penalty > 0.f && sp.repetition_penalty != 1.0f;
+    TokenTopkArgs a;
+    a.desc = e->tk_desc; a.src = e->logits; a.ld_src = e->Vpad; a.V = e->cfg.vocab; a.B = B;
+    a.step = e->d_step; a.done = e->d_done; a.unfinished = e->unfinished;
+    a.next = e->next_tok; a.pval = sp.do_sample ? nullptr : e->am_val; a.pidx = sp.do_sample ? nullptr : e->am_idx;
+    a.seen = pen ? e->seen : nullptr; a.seen_words = e->seen_words; a.penalty = sp.repetition_penalty;
+    a.eos = sp.eos_token_id;
+    a.min_new = (sp.min_new_tokens > 0 && sp.eos_token_id >= 0 && sp.eos_token_id < e->cfg.vocab) ? sp.min_new_tokens : 0;
+    a.do_sample = sp.do_sample ? 1 : 0; a.temperature = sp.temperature; a.top_p = sp.top_p; a.top_k = sp.top_k;
+    a.minp_log = e->minp_log; a.k = e->tk_k; a.source = e->tk_source; a.want_rank = want_rank ? 1 : 0;
+    launch_token_topk(a, st);
+}
 static void sample_and_finish(sv_engine* e, int B, const sv_sampling& sp, int max_new, hipStream_t st, bool fused = false) {
     if (fused && e->fin_folded) { e->fin_folded = false; return; }      // the lm_head launch in front did the selection AND the bookkeeping (SkinnyArgs::finish)
     // sv_generate_stats: one launch between the selection and the bookkeeping; a step that rewrites the raw row in place (a ban, the min-length
     // hold) takes the raw row's sums in a launch of their own in front of the rewrite (a statistics call never folds: fused is off for it)
-    const bool ts_split = e->ts_on && (e->ban_ngram > 0 || e->ban_nwords > 0 ||
-                                       (sp.min_new_tokens > 0 && sp.eos_token_id >= 0 && sp.eos_token_id < e->cfg.vocab));
+    const bool rewrite = e->ban_ngram > 0 || e->ban_nwords > 0 || (sp.min_new_tokens > 0 && sp.eos_token_id >= 0 && sp.eos_token_id < e->cfg.vocab);
+    const bool ts_split = e->ts_on && rewrite;
     if (ts_split) token_stats_step(e, B, sp, st, 1);
+    // sv_generate_topk, source 0 on such a step: the raw list is taken here as well, without the rank (the token is not known yet; a request for
+    // it was refused before the call began)
+    const bool tk_front = e->tk_on && e->tk_source == 0 && rewrite;
+    if (tk_front) token_topk_step(e, B, sp, st, false);
     if (e->ban_ngram > 0 || e->ban_nwords > 0) {
         // sv_generate_processed with a ban: the raw row goes out first, the banned ids become -inf in e->logits, then everything below -- the score
         // capture, the min-length hold, the repetition penalty, the selection -- reads the banned row (-inf stays -inf through all of them)
@@ -81,6 +100,7 @@ static void sample_and_finish(sv_engine* e, int B, const sv_sampling& sp, int ma
                               sp.repetition_penalty, st);
     }
     if (e->ts_on) token_stats_step(e, B, sp, st, ts_split ? 2 : 3);
+    if (e->tk_on && !tk_front) token_topk_step(e, B, sp, st, e->tk_rank);
     const FinishArgs f = make_finish_args(e, B, sp, max_new, fused);
     launch_finish_step(f, st);
 }
@@ -273,15 +293,15 @@ int sveng::report_bad_logits(sv_engine* e, hipStream_t st, const char* who, int 
 // G: samples per prompt (1: sv_generate / sv_generate_ragged; > 1: sv_generate_shared -- one prompt pass over the B prompts, B * G decode rows)
 static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const int32_t* lens, const sv_sampling* sp,
                             const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream, int G,
-                            const sv_logits_processors* lp, const sv_token_stats* ts);
+                            const sv_logits_processors* lp, const sv_token_stats* ts, const sv_token_topk* tk);
 static int generate_retry(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const int32_t* lens, const sv_sampling* sp,
                           const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream, int G = 1,
-                          const sv_logits_processors* lp = nullptr, const sv_token_stats* ts = nullptr) {
+                          const sv_logits_processors* lp = nullptr, const sv_token_stats* ts = nullptr, const sv_token_topk* tk = nullptr) {
     if (e) { e->last_giveup = 0; e->stream_skip = 0; }
-    int rc = generate_attempt(e, dev_embeds, B, S0, lens, sp, outs, dev_out_tokens, n_generated, stream, G, lp, ts);
+    int rc = generate_attempt(e, dev_embeds, B, S0, lens, sp, outs, dev_out_tokens, n_generated, stream, G, lp, ts, tk);
     if (rc != 0 && e && e->cfg.exclusive_device == 2 && e->last_giveup && e->fused_off) {
         e->last_giveup = 0;      // (the second attempt runs every step again: the statistics columns are rewritten completely, like the capture slabs)
-        rc = generate_attempt(e, dev_embeds, B, S0, lens, sp, outs, dev_out_tokens, n_generated, stream, G, lp, ts);
+        rc = generate_attempt(e, dev_embeds, B, S0, lens, sp, outs, dev_out_tokens, n_generated, stream, G, lp, ts, tk);
     }
     if (e) e->stream_skip = 0;
     return rc;
@@ -480,6 +500,68 @@ extern "C" int sv_generate_stats(sv_engine* e, const void* dev_embeds_packed, in
     return generate_retry(e, dev_embeds_packed, B, longest, host_lens, sp, outs, dev_out_tokens, n_generated, stream, n_samples, any ? lp : nullptr, stats);
 }
 
+// sv_generate_topk: the checks that need no engine (the same on a machine without a GPU); max_new <= 0 is refused later, by the call itself
+static int check_token_topk(const sv_sampling* sp, const sv_logits_processors* lp, const sv_token_topk* tk, int max_new) {
+    if (tk->k < 1 || tk->k > SV_TOPK_MAX) return fail(SV_EINVAL, "sv_generate_topk: k=%d must be in 1..%d", tk->k, SV_TOPK_MAX);
+    if (tk->source != 0 && tk->source != 1)
+        return fail(SV_EINVAL, "sv_generate_topk: source=%d must be 0 (log_softmax(raw / T)) or 1 (the processed scores)", tk->source);
+    if (!tk->dev_ids || !tk->dev_logprobs) return fail(SV_EINVAL, "sv_generate_topk: dev_ids / dev_logprobs is NULL (pass topk = NULL for a call without the lists)");
+    if (sp->num_beams > 1)
+        return fail(SV_EINVAL, "sv_generate_topk: top-k lists with num_beams %d are not built (beam search reports sequences_scores; beam rows reorder)",
+                    sp->num_beams);
+    if (max_new > 0 && tk->ld < (int64_t)max_new)
+        return fail(SV_EINVAL, "sv_generate_topk: ld %lld must be >= max_new %d", (long long)tk->ld, max_new);
+    // (no engine here, so no vocabulary bound: sample_and_finish holds the EOS id only when it is < vocab, and a min_new_tokens call whose
+    //  EOS id lies outside the vocabulary is refused its raw rank although nothing would be rewritten -- conservative, and such a call has no EOS)
+    const bool rewrite = (lp && (lp->no_repeat_ngram_size != 0 || lp->n_bad_words != 0)) || (sp->min_new_tokens > 0 && sp->eos_token_id >= 0);
+    if (tk->source == 0 && tk->dev_rank && rewrite)
+        return fail(SV_EINVAL, "sv_generate_topk: dev_rank with source 0 and a processor that rewrites the raw row (no_repeat_ngram_size, bad words, "
+                               "min_new_tokens): the raw list is taken in front of the rewrite, where the token is not known yet -- use source 1, or pass no dev_rank");
+    return 0;
+}
+static int setup_token_topk(sv_engine* e, const sv_sampling* sp, const sv_token_topk* tk, int rows, int max_new, hipStream_t st) {
+    e->tk_on = false;
+    if (!tk) return 0;
+    SVCHECK(check_token_topk(sp, nullptr, tk, max_new));
+    if (!e->tk_desc) SVCHECK(dalloc(e, &e->tk_desc, 1));
+    e->tk_host.ids = tk->dev_ids; e->tk_host.logprobs = tk->dev_logprobs; e->tk_host.rank = tk->dev_rank;
+    e->tk_host.ld = (long long)tk->ld; e->tk_host.rows = rows; e->tk_host.max_new = max_new;
+    HIPCHECK(hipMemcpyAsync(e->tk_desc, &e->tk_host, sizeof(TokenTopkDesc), hipMemcpyHostToDevice, st));
+    e->tk_k = tk->k; e->tk_source = tk->source; e->tk_rank = tk->dev_rank != nullptr;
+    e->tk_on = true;
+    return 0;
+}
+// sv_generate_stats plus the top-k lists (include/starvector_hip.h): topk NULL = exactly sv_generate_stats.
+extern "C" int sv_generate_topk(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, int32_t S0, int32_t n_samples,
+                                const sv_sampling* sp, const sv_logits_processors* lp, const sv_generate_outputs* outs, const sv_token_stats* stats,
+                                const sv_token_topk* topk, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
+    if (!topk) return sv_generate_stats(e, dev_embeds_packed, B, host_lens, S0, n_samples, sp, lp, outs, stats, dev_out_tokens, n_generated, stream);
+    // (the checks that need no engine come first: they are the same on a machine without a GPU)
+    if (!dev_embeds_packed || !sp || !dev_out_tokens || !n_generated) return fail(SV_EINVAL, "sv_generate_topk: null argument");
+    if (stats && !stats->dev_logprob && !stats->dev_logprob_processed && !stats->dev_entropy)
+        return fail(SV_EINVAL, "sv_generate_topk: dev_logprob, dev_logprob_processed and dev_entropy are all NULL (pass stats = NULL for a call without statistics)");
+    if (B < 1) return fail(SV_EINVAL, "sv_generate_topk: bad B=%d", B);
+    if (n_samples < 1) return fail(SV_EINVAL, "sv_generate_topk: bad n_samples=%d (must be >= 1)", n_samples);
+    int longest = S0;
+    if (host_lens) {
+        longest = 0;
+        for (int b = 0; b < B; ++b) {
+            if (host_lens[b] < 1) return fail(SV_EINVAL, "sv_generate_topk: length %d of sequence %d (must be >= 1)", host_lens[b], b);
+            longest = host_lens[b] > longest ? host_lens[b] : longest;
+        }
+    } else if (S0 < 1) {
+        return fail(SV_EINVAL, "sv_generate_topk: bad S0=%d", S0);
+    }
+    SVCHECK(check_token_topk(sp, lp, topk, sp->max_length - longest));
+    if (stats && sp->max_length - longest > 0 && stats->ld < (int64_t)(sp->max_length - longest))
+        return fail(SV_EINVAL, "sv_generate_topk: stats ld %lld must be >= max_new %d (max_length %d - prompt length %d)", (long long)stats->ld,
+                    sp->max_length - longest, sp->max_length, longest);
+    const bool any = lp && (lp->no_repeat_ngram_size != 0 || lp->n_bad_words != 0 || lp->min_p != 0.f);
+    if (any) SVCHECK(check_logits_processors(lp, 0, "sv_generate_topk"));
+    return generate_retry(e, dev_embeds_packed, B, longest, host_lens, sp, outs, dev_out_tokens, n_generated, stream, n_samples, any ? lp : nullptr, stats,
+                          topk);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Shared prompt pass (sv_generate_shared): B prompts, G samples each, ONE prompt pass over the B prompts.
 // ------------------------------------------------------------------------------------------------
@@ -550,7 +632,7 @@ static int shared_prefill_fork(sv_engine* e, const void* dev_embeds, int B, int 
 // lens != nullptr: the ragged form -- S0 is the longest prompt (the budget counts from it), sequence b has lens[b] rows
 static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t Bp, int32_t S0, const int32_t* lens, const sv_sampling* sp,
                             const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream, int G,
-                            const sv_logits_processors* lp, const sv_token_stats* ts) {
+                            const sv_logits_processors* lp, const sv_token_stats* ts, const sv_token_topk* tk) {
     SVCHECK(check_ready(e));
     const bool shared = G > 1;
     if (shared && (Bp < 1 || (long long)Bp * G > e->cfg.max_batch))
@@ -584,6 +666,8 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t Bp, in
     SVCHECK(setup_capture(e, sp, outs, sp->num_beams > 1 ? B * sp->num_beams : B, max_new, st));
     struct StatsOff { sv_engine* e; ~StatsOff() { e->ts_on = false; } } stats_off{e};
     SVCHECK(setup_token_stats(e, sp, ts, B, max_new, st));
+    struct TopkOff { sv_engine* e; ~TopkOff() { e->tk_on = false; } } topk_off{e};
+    SVCHECK(setup_token_topk(e, sp, tk, B, max_new, st));
     if (sp->num_beams > 1) {
         if (sp->on_tokens) return fail(SV_EINVAL, "streaming is not supported with beam search (hypotheses are only final at the end; HF refuses too)");
         if (sp->n_stop > 0 && !sp->stop_ids) return fail(SV_EINVAL, "n_stop > 0 but stop_ids is null");
@@ -614,7 +698,7 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t Bp, in
         // the selection, and the tokens are bit-identical either way (tests/test_gpu_e2e.py)
         // (a ban rewrites the logits row between the lm_head and the selection: the separate launch as well)
         fused_sel = !sp->do_sample && !pen && sp->min_new_tokens <= 0 && B <= 32 && !e->lm_head.fp8 && waves > 1 && !two && !(e->exp & SV_EXP_SEPARATE_ARGMAX) &&
-                    !e->cap_on && !ban && !e->ts_on;      // (the statistics launch reads the row and the slice winners between the lm_head and the bookkeeping)
+                    !e->cap_on && !ban && !e->ts_on && !e->tk_on;      // (the statistics / top-k launches read the row and the slice winners between the lm_head and the bookkeeping)
     }
     // generation state, one launch: positions = S0 - 1 (finish_step adds 1), unfinished = 1, {step, done, n_emitted} = 0, the folded selection's key slots = 0
     gen_state_init(e->positions, S0 - 1, e->unfinished, B, e->d_step, e->amax, fused_sel ? 64 * SV_AMAX_STRIDE : 0, st);
@@ -681,6 +765,8 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t Bp, in
             snprintf(key + strlen(key), sizeof(key) - strlen(key), "|ng%d|bw%d|mp%a", e->ban_ngram, e->ban_nwords, e->minp_log);      // neither: the plain call's key and graph
         if (e->ts_on)        // a statistics step carries one or two launches more; the buffers (and which of them are asked for) are read through ts_desc
             snprintf(key + strlen(key), sizeof(key) - strlen(key), "|ts");
+        if (e->tk_on)        // the top-k launch: k, the source and whether the rank is taken are launch arguments; the buffers are read through tk_desc
+            snprintf(key + strlen(key), sizeof(key) - strlen(key), "|tk%d.%d.%d", e->tk_k, e->tk_source, e->tk_rank ? 1 : 0);
         if (e->gen_gexec && e->gen_graph_key == key) {
             gexec = e->gen_gexec;
         } else {

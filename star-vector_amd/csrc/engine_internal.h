@@ -178,6 +178,8 @@ struct sv_engine {
     bf16_t* score_chunk_ws = nullptr;
     int score_chunk_alloc = 0;       // rows the workspace holds
     int score_chunk_rows = 0;        // sv_debug_set_score_chunk_rows; 0 = SV_SCORE_CHUNK_ROWS
+    float* score_lse_ws = nullptr;   // sv_forward_topk without a caller's logsumexp: [score_lse_alloc] fp32, the chunk's lse between the two kernels
+    int score_lse_alloc = 0;
     int cached_B = 0;
     int dbg_pos_hi = 0;             // sv_debug_kv_load / sv_debug_attn_decode: upper bound of positions[] (host side), kept below max_seq_len
     int num_cus = 256;
@@ -218,6 +220,12 @@ struct sv_engine {
     TokenStatsDesc ts_host = {};
     float* ts_raw = nullptr;
     bool ts_on = false;
+    // sv_generate_topk: the device descriptor of the caller's top-k buffers (rewritten for every call), its host image, and the request the step is
+    // keyed on; tk_on = the current call asks for the lists (set and cleared by it)
+    TokenTopkDesc* tk_desc = nullptr;
+    TokenTopkDesc tk_host = {};
+    int tk_k = 0, tk_source = 0;
+    bool tk_rank = false, tk_on = false;
     // sv_generate_processed: the HF logits processors of the current call (set and cleared by it).  A ban (no_repeat_ngram_size, bad words) adds
     // one launch between the lm_head and the selection (processors.hip); min_p rides in the sampler's arguments.  The bad-word table is device
     // memory of the engine, uploaded once per call (ban_host = its host image, kept alive for the upload)
@@ -270,7 +278,9 @@ int assign_pages(sv_engine* e, int B, int total_len, hipStream_t st);
 // bf16 = 403 MB at StarVector's vocabulary -- the fastest of 512 / 1024 / 2048 / 4096 measured (profiles/score_logprobs.md; DESIGN.md "Scoring without logits")
 #define SV_SCORE_CHUNK_ROWS 4096
 // what sv_forward_logprobs asks of the scoring pass instead of the logits: [B][n_keep] each, any output may be nullptr
-struct ScoreLogprobs { const int32_t* targets; float inv_t; float* logprob; float* lse; float* entropy; int32_t* argmax; };
+// (sv_forward_topk: k > 0 adds [B][n_keep][k] ids and log-probs and the [B][n_keep] rank of the target, rank may be nullptr)
+struct ScoreLogprobs { const int32_t* targets; float inv_t; float* logprob; float* lse; float* entropy; int32_t* argmax;
+                       int k = 0; int32_t* topk_ids = nullptr; float* topk_logprobs = nullptr; int32_t* rank = nullptr; };
 int prefill_forward(sv_engine* e, const bf16_t* embeds, int B, int S0, hipStream_t st, int n_keep = 0,
                     bf16_t* dev_scores = nullptr, const int32_t* table = nullptr, const ScoreLogprobs* lp = nullptr);
 void decode_forward(sv_engine* e, int B, hipStream_t st);

@@ -1044,6 +1044,41 @@ extern "C" int sv_op_logprob_rows(const void* dev_logits_bf16, int32_t R, int32_
     return 0;
 }
 
+// topk_rows_bf16_kernel (score.hip) on caller-given rows and the lse sv_op_logprob_rows left for them
+extern "C" int sv_op_topk_rows_bf16(const void* dev_logits_bf16, int32_t R, int32_t V, int32_t ld, const int32_t* dev_targets, float temperature,
+                                    const float* dev_logsumexp, int32_t k, int32_t* dev_topk_ids, float* dev_topk_logprobs, int32_t* dev_rank,
+                                    sv_stream stream) {
+    if (!dev_logits_bf16 || R < 1 || R > (1 << 22) || V < 1 || ld < V || (ld & 7) || ((uintptr_t)dev_logits_bf16 & 15))
+        return fail(SV_EINVAL, "sv_op_topk_rows_bf16: bad argument (rows 16-byte aligned, ld a multiple of 8 and >= V)");
+    if (k < 1 || k > SV_TOPK_MAX) return fail(SV_EINVAL, "sv_op_topk_rows_bf16: k=%d must be in 1..%d", k, SV_TOPK_MAX);
+    if (!dev_logsumexp || !dev_topk_ids || !dev_topk_logprobs) return fail(SV_EINVAL, "sv_op_topk_rows_bf16: null dev_logsumexp / dev_topk_ids / dev_topk_logprobs");
+    if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail(SV_EINVAL, "sv_op_topk_rows_bf16: temperature must be finite and > 0");
+    hipStream_t st = (hipStream_t)stream;
+    TopkRowsArgs a;
+    a.logits = (const bf16_t*)dev_logits_bf16; a.ld = ld; a.V = V; a.R = R; a.targets = dev_targets; a.inv_t = 1.0f / temperature;
+    a.lse = dev_logsumexp; a.k = k; a.ids = dev_topk_ids; a.logprobs = dev_topk_logprobs; a.rank = dev_rank;
+    launch_topk_rows_bf16(a, st);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));
+    return 0;
+}
+// token_topk_rows_kernel (sampling.hip): the source-0 row function of sv_generate_topk on caller-given rows
+extern "C" int sv_op_token_topk(const float* dev_logits, int32_t B, int32_t V, int32_t ld, float temperature, const int32_t* dev_tokens, int32_t k,
+                                int32_t* dev_ids, float* dev_logprobs, int32_t* dev_rank, sv_stream stream) {
+    if (!dev_logits || B < 1 || B > (1 << 22) || V < 1 || ld < V) return fail(SV_EINVAL, "sv_op_token_topk: bad argument (B >= 1, V >= 1, ld >= V)");
+    if (k < 1 || k > SV_TOPK_MAX) return fail(SV_EINVAL, "sv_op_token_topk: k=%d must be in 1..%d", k, SV_TOPK_MAX);
+    if (!dev_ids || !dev_logprobs) return fail(SV_EINVAL, "sv_op_token_topk: null dev_ids / dev_logprobs");
+    if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail(SV_EINVAL, "sv_op_token_topk: temperature must be finite and > 0");
+    hipStream_t st = (hipStream_t)stream;
+    TokenTopkRowsArgs a;
+    a.rows = dev_logits; a.ld = ld; a.V = V; a.B = B; a.temperature = temperature; a.tokens = dev_tokens; a.k = k;
+    a.ids = dev_ids; a.logprobs = dev_logprobs; a.rank = dev_rank;
+    launch_token_topk_rows(a, st);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
 extern "C" int sv_op_sample(const float* logits, int32_t B, int32_t V, int32_t ld, float temperature, int32_t top_k,
                             float top_p, uint64_t seed, int32_t step, int32_t* out, sv_stream stream);
 extern "C" int sv_op_sample_top_p(const float* logits, int32_t B, int32_t V, int32_t ld, float temperature, float top_p,

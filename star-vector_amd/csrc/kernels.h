@@ -399,6 +399,42 @@ struct TokenStatsArgs {
                                                                      //   `raw` and the row as the selection saw it, 3 = both in one launch
 };
 void launch_token_stats(const TokenStatsArgs& a, hipStream_t st);
+
+// ---- the k best ids of the distribution behind each generated token, and the token's rank (sv_generate_topk; topk.h row_topk).  For the device step
+// t = *step, row b writes k ids and k log-probs at [b][t][0..k) and its rank at [b][t] of the caller's buffers (device descriptor, as above).
+//   source 0  the distribution of TokenStatsDesc::logprob: log_softmax(x / T) over the raw row.  When the step rewrites the raw row in place (a ban,
+//             the min-length hold) the launch sits in front of the rewrite, where the token is not known yet: no rank then (want_rank = 0)
+//   source 1  the distribution of TokenStatsDesc::processed: the processed row with the capture's kept set, removed ids at -inf (they never enter)
+// Descending by value, equal values by ascending id; a slot's log-prob is the expression token_stats_kernel writes for that id, bit for bit.  Fewer
+// than k ids that enter: the tail holds (-1, -inf).  A row that had finished before step t: ids -1, log-probs 0, rank 0.  A row without a
+// comparable value: ids -1, rank 0, log-probs NaN.  k, source and want_rank are launch arguments (the captured step is keyed on them).
+#define SV_TOPK_MAX_DEV 32                                   // == SV_TOPK_MAX (include/starvector_hip.h; static_assert in engine_generate.hip)
+struct TokenTopkDesc {
+    int32_t* ids; float* logprobs;                       // [rows][ld][k]
+    int32_t* rank;                                       // [rows][ld], nullptr: not requested
+    long long ld;                                        // >= max_new
+    int rows, max_new;
+};
+struct TokenTopkArgs {
+    const TokenTopkDesc* desc;
+    const float* src; int ld_src; int V; int B;
+    const int32_t* step; const int32_t* done; const int32_t* unfinished;
+    const int32_t* next;                                             // sampling: [B] drawn ids
+    const float* pval; const int32_t* pidx;                          // greedy: [B][8] slice winners (nullptr when sampling)
+    const uint32_t* seen; int seen_words; float penalty;             // seen = nullptr: penalty off
+    int eos, min_new;                                                // min_new <= 0: hold off
+    int do_sample; float temperature, top_p; int top_k;
+    float minp_log = -INFINITY;
+    int k, source, want_rank;
+};
+void launch_token_topk(const TokenTopkArgs& a, hipStream_t st);
+// the source-0 row function on caller-given rows (sv_op_token_topk): rows [B][ld] fp32, tokens [B] or nullptr (no rank), outputs [B][k] / [B]
+struct TokenTopkRowsArgs {
+    const float* rows; int ld; int V; int B; float temperature;
+    const int32_t* tokens; int k;
+    int32_t* ids; float* logprobs; int32_t* rank;
+};
+void launch_token_topk_rows(const TokenTopkRowsArgs& a, hipStream_t st);
 #ifdef __HIPCC__
 // one thread block's share of a captured row: out[j] = f(j) for j in [0, V), with 16-byte stores wherever `out` allows (the slab
 // rows are ld floats apart, ld need not be a multiple of 4); the block takes quads [q0, q1) of the aligned body, block 0 the
@@ -532,6 +568,20 @@ struct LogprobArgs {
     int row0;                                       //   without a finite logit: all outputs NaN, argmax -1); [1] = min(row0 + row) over such rows
 };
 void launch_logprob_rows(const LogprobArgs& a, hipStream_t st);
+// the k best columns of the same rows and the rank of the target (sv_forward_topk; topk.h row_topk): one 1024-thread block per row, after
+// launch_logprob_rows has left the row's lse.  Slot j holds float(logit) * inv_t - lse of its column -- logprob_rows' own expression: the slot of the
+// target equals LogprobArgs::logprob bit for bit; slot 0's id is LogprobArgs::argmax.  Target -100 (or outside the vocabulary): rank 0.  A row whose
+// lse is NaN because it has no comparable value: ids -1, log-probs NaN, rank 0.
+struct TopkRowsArgs {
+    const bf16_t* logits; int ld; int V; int R;     // [R][ld], V valid columns
+    const int32_t* targets;                         // [R] or nullptr
+    float inv_t;
+    const float* lse;                               // [R], from launch_logprob_rows over the same rows and inv_t
+    int k;                                          // 1 .. 32
+    int32_t* ids; float* logprobs;                  // [R][k]
+    int32_t* rank;                                  // [R] or nullptr
+};
+void launch_topk_rows_bf16(const TopkRowsArgs& a, hipStream_t st);
 
 // ---- image pre-processing (preprocess.hip): uint8 HWC (3 or 4 channels) -> float32 [3][S][S], returns a hipError_t value
 int preprocess_image(const uint8_t* dev_pixels, int width, int height, int channels, int out_size, int recipe,

@@ -6,6 +6,7 @@
 //                   (starvector_base.py:9-20), max-length budget -> device "done" flag
 #include "kernels.h"
 #include "warp.h"
+#include "topk.h"
 
 namespace sv {
 
@@ -527,6 +528,106 @@ __global__ __launch_bounds__(SP_THREADS) void token_stats_kernel(TokenStatsArgs 
 }
 void launch_token_stats(const TokenStatsArgs& a, hipStream_t st) {
     token_stats_kernel<<<a.B, SP_THREADS, 0, st>>>(a);
+}
+
+// ------------------------------------------------------------------------------------------------
+// sv_generate_topk: the k best ids of the distribution behind the token each row emits, and the token's rank (TokenTopkArgs, kernels.h; the list is
+// topk.h's row_topk).  The sums are ts_row_sums over the functors of token_stats_kernel and a slot's log-prob is that kernel's expression for its
+// id: the slot of the emitted id equals dev_logprob / dev_logprob_processed bit for bit.  Every thread of the block calls these.
+// ------------------------------------------------------------------------------------------------
+// the list of one row to ids[0..k) / lps[0..k) and *rank: n slots found; a row without a comparable value reads -1 / NaN / 0
+__device__ __forceinline__ void topk_store(int n, int k, float nolp, bool wr, int rk, int32_t* ids, float* lps, int32_t* rank) {
+    const RowTopkSmem& sm = row_topk_smem();
+    if ((int)threadIdx.x < k) {
+        ids[threadIdx.x] = sm.id[threadIdx.x];
+        lps[threadIdx.x] = n > 0 ? sm.lp[threadIdx.x] : nolp;
+    }
+    if (rank && threadIdx.x == 0) *rank = (wr && n > 0) ? rk : 0;
+}
+// source 0 on one fp32 row: log_softmax(row / T), keyed on row[i]; tok < 0: no rank.  A continuous-batching launch can call it as it is.
+__device__ __forceinline__ void token_topk_raw_row(const float* row, int V, float T, int k, int tok, float* red, int32_t* ids, float* lps,
+                                                   int32_t* rank) {
+    float m, ls, ent;
+    ts_row_sums([&](int i) { return row[i] / T; }, V, red, m, ls, ent);
+    const bool wr = rank != nullptr && tok >= 0;
+    int rk = 0;
+    const int n = row_topk([&](int i) { return row[i]; }, V, k, [&](float v) { return (v / T - m) - ls; }, red, wr,
+                           wr ? row[tok] : __uint_as_float(0x7fc00000u), &rk);
+    topk_store(n, k, (row[0] / T - m) - ls, wr, rk, ids, lps, rank);       // (no comparable value: m = -inf or NaN, the NaN dev_logprob holds)
+}
+
+// SOURCE is a template argument: the raw form carries none of the warper's registers (row_warp_stats holds the row's 49 values per thread)
+template <int SOURCE>
+__global__ __launch_bounds__(SP_THREADS) void token_topk_kernel(TokenTopkArgs p) {
+    __shared__ float red[SP_THREADS / 64];
+    if (*p.done) return;
+    const TokenTopkDesc d = *p.desc;
+    const int t = *p.step;
+    const int b = blockIdx.x;
+    if (t < 0 || t >= d.max_new || b >= d.rows) return;
+    const int k = p.k;
+    const size_t o = (size_t)b * (size_t)d.ld + (size_t)t;
+    int32_t* ids = d.ids + o * (size_t)k;
+    float* lps = d.logprobs + o * (size_t)k;
+    int32_t* rank = (p.want_rank && d.rank) ? d.rank + o : nullptr;
+    if (!p.unfinished[b]) {                                          // finished before this step (block-uniform): what the statistics read there
+        if ((int)threadIdx.x < k) { ids[threadIdx.x] = -1; lps[threadIdx.x] = 0.f; }
+        if (rank && threadIdx.x == 0) *rank = 0;
+        return;
+    }
+    const float* row = p.src + (size_t)b * p.ld_src;
+    const float T = p.do_sample ? p.temperature : 1.0f;
+    int tok = -1;
+    if (rank) {                                                      // the token, as token_stats_kernel reads it
+        if (p.pval) {
+            float best = -INFINITY;
+            tok = 0x7fffffff;
+            for (int s = 0; s < AM_SPLIT; ++s) argmax_pair(best, tok, p.pval[b * AM_SPLIT + s], p.pidx[b * AM_SPLIT + s]);
+        } else {
+            tok = p.next[b];
+        }
+        if ((unsigned)tok >= (unsigned)p.V) tok = 0;
+    }
+    if constexpr (SOURCE == 0) {
+        token_topk_raw_row(row, p.V, T, k, tok, red, ids, lps, rank);
+        return;
+    }
+    // source 1: the processed row (token_stats_kernel's functors; greedy: T = 1 and x / 1 = x, the sums and the expression are that kernel's)
+    const uint32_t* srow = p.seen ? p.seen + (size_t)b * p.seen_words : nullptr;
+    const int eos = t < p.min_new ? p.eos : -1;
+    const float pen = p.penalty;
+    auto base = [&](int i) { return i == eos ? -INFINITY : rep_penalty(row[i], i, srow, pen); };
+    const bool wr = rank != nullptr;
+    const float qnan = __uint_as_float(0x7fc00000u);
+    float pm, pls, pent;
+    int rk = 0, n;
+    if (p.do_sample) {
+        const float invT = 1.0f / p.temperature;
+        WarpStats w = row_warp_stats<false, true>([&](int i) { return base(i) * invT; }, p.V, p.top_k, p.top_p, 1, red);
+        w.mthr = wp_minp_thr(w.mx, p.minp_log);
+        auto kept = [&](int i) { const float s = base(i); return wp_keep(w, s * invT) ? s : -INFINITY; };      // the key: before the division by T
+        ts_row_sums([&](int i) { const float s = base(i); return wp_keep(w, s * invT) ? s / T : -INFINITY; }, p.V, red, pm, pls, pent);
+        n = row_topk(kept, p.V, k, [&](float v) { return (v / T - pm) - pls; }, red, wr, wr ? kept(tok) : qnan, &rk);
+    } else {
+        ts_row_sums(base, p.V, red, pm, pls, pent);
+        n = row_topk(base, p.V, k, [&](float v) { return (v - pm) - pls; }, red, wr, wr ? base(tok) : qnan, &rk);
+    }
+    topk_store(n, k, qnan, wr, rk, ids, lps, rank);
+}
+void launch_token_topk(const TokenTopkArgs& a, hipStream_t st) {
+    if (a.source == 0) token_topk_kernel<0><<<a.B, SP_THREADS, 0, st>>>(a);
+    else token_topk_kernel<1><<<a.B, SP_THREADS, 0, st>>>(a);
+}
+__global__ __launch_bounds__(SP_THREADS) void token_topk_rows_kernel(TokenTopkRowsArgs p) {
+    __shared__ float red[SP_THREADS / 64];
+    const int b = blockIdx.x;
+    int tok = p.tokens ? p.tokens[b] : -1;
+    if (tok >= p.V) tok = -1;
+    token_topk_raw_row(p.rows + (size_t)b * p.ld, p.V, p.temperature, p.k, tok, red, p.ids + (size_t)b * p.k, p.logprobs + (size_t)b * p.k,
+                       p.rank ? p.rank + b : nullptr);
+}
+void launch_token_topk_rows(const TokenTopkRowsArgs& a, hipStream_t st) {
+    token_topk_rows_kernel<<<a.B, SP_THREADS, 0, st>>>(a);
 }
 
 __global__ void finish_step_kernel(FinishArgs p) {

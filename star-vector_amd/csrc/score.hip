@@ -3,6 +3,7 @@
 // straight from the bf16 rows the lm_head GEMM leaves in its workspace, so that no [rows][vocab] tensor ever reaches the caller.
 #include <math.h>
 #include "kernels.h"
+#include "topk.h"
 
 namespace sv {
 
@@ -13,6 +14,9 @@ namespace sv {
 __device__ __forceinline__ void lp_argmax_pair(float& v, int& i, float ov, int oi) {
     if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
 }
+
+// the log-prob of a column whose bf16 logit is x: ONE expression for logprob_rows_kernel's target and for every slot of topk_rows_bf16_kernel
+__device__ __forceinline__ float lp_value(float x, float it, float lse) { return x * it - lse; }
 
 // One block per row, two passes over the row (196 KiB of fp32 would not fit a block's registers; 96 KiB of bf16 comes back out
 // of L2 / the last-level cache the second time): (1) maximum + first maximal index, (2) sum exp(x - max) and sum exp(x - max) (x - max).
@@ -101,7 +105,7 @@ __global__ __launch_bounds__(LP_THREADS) void logprob_rows_kernel(LogprobArgs p)
         const int t = p.targets ? p.targets[r] : -100;
         float lp;
         if (t == -100) lp = 0.f;                                        // HF's ignore index
-        else if (t >= 0 && t < V) lp = bf2f(row[t]) * it - lse;
+        else if (t >= 0 && t < V) lp = lp_value(bf2f(row[t]), it, lse);
         else {
             lp = __uint_as_float(0x7fc00000u);
             if (p.bad) { atomicOr(p.bad, 1); atomicMin(p.bad + 1, p.row0 + r); }
@@ -113,6 +117,30 @@ __global__ __launch_bounds__(LP_THREADS) void logprob_rows_kernel(LogprobArgs p)
 void launch_logprob_rows(const LogprobArgs& a, hipStream_t st) {
     if (a.R < 1) return;
     logprob_rows_kernel<<<dim3((unsigned)a.R), LP_THREADS, 0, st>>>(a);
+}
+
+// sv_forward_topk: the k best columns of a row and the rank of its target (TopkRowsArgs, kernels.h; topk.h's row_topk keyed on the bf16 logit itself,
+// before the product with inv_t).  The row's lse is the one logprob_rows_kernel left: every slot is that kernel's log-prob of its column.
+__global__ __launch_bounds__(WP_THREADS) void topk_rows_bf16_kernel(TopkRowsArgs p) {
+    __shared__ float red[WP_THREADS / 64];
+    const int r = blockIdx.x, V = p.V, k = p.k;
+    const bf16_t* row = p.logits + (size_t)r * p.ld;
+    const float it = p.inv_t, lse = p.lse[r];
+    const int t = p.targets ? p.targets[r] : -100;
+    const bool wr = p.rank != nullptr && t >= 0 && t < V;           // -100 / an id outside the vocabulary: rank 0
+    int rk = 0;
+    const int n = row_topk([&](int i) { return bf2f(row[i]); }, V, k, [&](float v) { return lp_value(v, it, lse); }, red, wr,
+                           wr ? bf2f(row[t]) : __uint_as_float(0x7fc00000u), &rk);
+    const RowTopkSmem& sm = row_topk_smem();
+    if ((int)threadIdx.x < k) {
+        p.ids[(size_t)r * k + threadIdx.x] = sm.id[threadIdx.x];
+        p.logprobs[(size_t)r * k + threadIdx.x] = n > 0 ? sm.lp[threadIdx.x] : __uint_as_float(0x7fc00000u);
+    }
+    if (p.rank && threadIdx.x == 0) p.rank[r] = (wr && n > 0) ? rk : 0;
+}
+void launch_topk_rows_bf16(const TopkRowsArgs& a, hipStream_t st) {
+    if (a.R < 1) return;
+    topk_rows_bf16_kernel<<<dim3((unsigned)a.R), WP_THREADS, 0, st>>>(a);
 }
 
 }  // namespace sv

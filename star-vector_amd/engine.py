@@ -105,7 +105,35 @@ class TokenLogprobs(NamedTuple):
     argmax: Optional[torch.Tensor] = None      # int32: the lowest index holding the row's maximum
 
 
+class TokenTopLogprobs(NamedTuple):
+    """`HipEngine.forward_logprobs(..., top_k=k)`: the fields of `TokenLogprobs` and the lists (a type of its own: code that walks the four
+    fields of `TokenLogprobs` keeps meeting four)."""
+    logprobs: torch.Tensor
+    logsumexp: torch.Tensor
+    entropy: Optional[torch.Tensor]
+    argmax: Optional[torch.Tensor]
+    top_token_ids: torch.Tensor                # int32 [B, n, k]: the k most likely ids, best first (-1 where fewer exist)
+    top_logprobs: torch.Tensor                 # float32 [B, n, k]: their log-probs (-inf where the id is -1)
+    token_ranks: torch.Tensor                  # int32 [B, n]: 1 + the ids with a larger logit than the target; 0 where the target is -100
+
+
 TOKEN_STATS = ("token_logprobs", "token_logprobs_processed", "token_entropies")      # HipEngine.generate(token_stats=...), sv_token_stats's order
+TOPK_MAX = 32                                   # SV_TOPK_MAX
+TOPK_SOURCES = ("raw", "processed")             # sv_token_topk.source 0 / 1
+
+
+def token_topk_request(token_topk):
+    """`HipEngine.generate(token_topk=...)`: an int k, or dict(k=, source="raw" | "processed", rank=True) -> (k, source index, rank)."""
+    req = {"k": token_topk} if not isinstance(token_topk, dict) else dict(token_topk)
+    unknown = set(req) - {"k", "source", "rank"}
+    if unknown or "k" not in req:
+        raise ValueError(f"token_topk must be an int or dict(k=, source=, rank=), got {token_topk!r}")
+    k, source, rank = req["k"], req.get("source", "raw"), req.get("rank", True)
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= TOPK_MAX:
+        raise ValueError(f"token_topk: k must be an int in 1..{TOPK_MAX}, got {k!r}")
+    if source not in TOPK_SOURCES:
+        raise ValueError(f"token_topk: source must be one of {TOPK_SOURCES}, got {source!r}")
+    return k, TOPK_SOURCES.index(source), bool(rank)
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -372,10 +400,15 @@ class HipEngine:
         return out
 
     def forward_logprobs(self, inputs_embeds: torch.Tensor, targets: torch.Tensor, num_logits_to_keep: int = 0,
-                         temperature: float = 1.0, entropy: bool = False, argmax: bool = False) -> TokenLogprobs:
+                         temperature: float = 1.0, entropy: bool = False, argmax: bool = False, top_k: int = 0):
         """Scoring forward without logits: for each of the last n = num_logits_to_keep positions (0 = all) the log-probability of
         targets[b, j] under softmax(logits / temperature), the logits being the bf16 rows `forward_logits` returns, in fp32
-        (sv_forward_logprobs).  targets: integer [B, n]; -100 = ignore (log-prob 0).  Device memory does not grow with B * n * vocab."""
+        (sv_forward_logprobs).  targets: integer [B, n]; -100 = ignore (log-prob 0).  Device memory does not grow with B * n * vocab.
+        ``top_k`` = k in 1..32 (sv_forward_topk) returns a ``TokenTopLogprobs``, which also holds ``top_token_ids`` / ``top_logprobs`` [B, n, k] -- the k most likely ids of every
+        position, best first, equal logits by ascending id, and their log-probs; the slot holding the target equals ``logprobs`` bit for bit --
+        and ``token_ranks`` [B, n], 1 + the number of ids with a larger logit than the target (0 where the target is -100)."""
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 0 <= top_k <= TOPK_MAX:
+            raise ValueError(f"top_k must be an int in 0..{TOPK_MAX}, got {top_k!r}")
         x = _need(inputs_embeds, torch.bfloat16, "inputs_embeds")
         B, S, D = x.shape
         if D != self.cfg.hidden:
@@ -390,6 +423,13 @@ class HipEngine:
         lse = torch.empty(B, n, dtype=torch.float32, device=x.device)
         ent = torch.empty(B, n, dtype=torch.float32, device=x.device) if entropy else None
         am = torch.empty(B, n, dtype=torch.int32, device=x.device) if argmax else None
+        if top_k:
+            ids = torch.empty(B, n, top_k, dtype=torch.int32, device=x.device)
+            tlp = torch.empty(B, n, top_k, dtype=torch.float32, device=x.device)
+            rank = torch.empty(B, n, dtype=torch.int32, device=x.device)
+            check(self.lib.sv_forward_topk(self._h, _ptr(x), B, S, n, _ptr(t), float(temperature), _ptr(lp), _ptr(lse), _ptr(ent), _ptr(am),
+                                           top_k, _ptr(ids), _ptr(tlp), _ptr(rank), _stream()), "sv_forward_topk")
+            return TokenTopLogprobs(lp, lse, ent, am, ids, tlp, rank)
         check(self.lib.sv_forward_logprobs(self._h, _ptr(x), B, S, n, _ptr(t), float(temperature), _ptr(lp), _ptr(lse), _ptr(ent),
                                            _ptr(am), _stream()), "sv_forward_logprobs")
         return TokenLogprobs(lp, lse, ent, am)
@@ -412,7 +452,7 @@ class HipEngine:
                  early_stopping=False, top_k: int = 0, on_tokens=None, min_new_tokens: int = 0,
                  scores_out: Optional[torch.Tensor] = None, logits_out: Optional[torch.Tensor] = None,
                  return_outputs: bool = False, lengths: Optional[Sequence[int]] = None, n_samples: int = 1,
-                 logits_processors=None, token_stats: bool = False):
+                 logits_processors=None, token_stats: bool = False, token_topk=None):
         """HF ``generate`` semantics for inputs_embeds: returns ONLY the new tokens, int64 [B, N].
         ``lengths``: the ragged form -- inputs_embeds is packed [sum(lengths), D], one prompt pass for all of them, ``max_length`` counts from
         the longest prompt (see ``generate_ragged``).
@@ -434,7 +474,19 @@ class HipEngine:
         normalize_logits=True) and "token_entropies" (entropy of softmax(raw logits / T)); 0 after a row has finished.  The tokens are those of
         the call without it; one more launch per decode step (two with a token ban or min_new_tokens), no [rows, vocab] output.  A tuple of
         those three names instead of True asks for them alone: without "token_logprobs_processed" the launch skips the warper thresholds and
-        the second sweep of the row."""
+        the second sweep of the row.
+        ``token_topk=k`` or ``dict(k=, source="raw" | "processed", rank=True)`` (sv_generate_topk; k in 1..32, greedy and sampling, alone or with
+        ``token_stats``): the dict gains "top_token_ids" int32 and "top_logprobs" fp32 [rows, n_generated, k] -- the k most likely ids of every
+        step's distribution, best first, equal values by ascending id, (-1, -inf) where fewer than k exist -- and, with ``rank``,
+        "token_ranks" int32 [rows, n_generated] = 1 + the ids more likely than the emitted one.  "raw" is the distribution of "token_logprobs",
+        "processed" that of "token_logprobs_processed"; the slot of the emitted id equals that statistic bit for bit.  After a row has
+        finished: -1 / 0 / 0.  "raw" with ``rank`` and a processor that rewrites the row (a token ban, min_new_tokens) is a ValueError: the raw
+        list is then taken before the token is known -- ask for "processed", or rank=False."""
+        tk_req = None
+        if token_topk is not None and token_topk is not False:
+            tk_req = token_topk_request(token_topk)
+            if int(num_beams) > 1:
+                raise ValueError("token_topk with num_beams > 1 is not built (beam search reports sequences_scores; beam rows reorder)")
         lens_arr = None
         if lengths is not None:
             x, lens_arr, lens = self._packed(inputs_embeds, lengths)
@@ -475,7 +527,7 @@ class HipEngine:
             sp.on_tokens = C.cast(cb, C.c_void_p)
         out = torch.empty(B, max_new, dtype=torch.int64, device=x.device)
         n = C.c_int32(0)
-        if scores_out is None and logits_out is None and not return_outputs and not token_stats:
+        if scores_out is None and logits_out is None and not return_outputs and not token_stats and tk_req is None:
             if lp is not None:
                 check(self.lib.sv_generate_processed(self._h, _ptr(x), n_prompts, lens_arr, S0, G, C.byref(sp), C.byref(lp), None, _ptr(out),
                                                      C.byref(n), _stream()), "sv_generate_processed")
@@ -512,13 +564,24 @@ class HipEngine:
         if beam:
             outs.host_sequences_scores = C.cast(seq_scores, C.POINTER(C.c_float))
             outs.host_beam_indices = C.cast(beam_idx, C.POINTER(C.c_int64))
-        stats = None
+        stats, ts, topk = None, None, None
         if token_stats:
             names = TOKEN_STATS if token_stats is True else tuple(token_stats)
             if not names or any(k not in TOKEN_STATS for k in names):
                 raise ValueError(f"token_stats must be True or a non-empty tuple of {TOKEN_STATS}, got {token_stats!r}")
             stats = {k: torch.empty(B, max_new, dtype=torch.float32, device=x.device) for k in TOKEN_STATS if k in names}
             ts = _lib.SvTokenStats(*[_ptr(stats.get(k)) for k in TOKEN_STATS], max_new)
+        if tk_req is not None:
+            k, source, want_rank = tk_req
+            topk = {"top_token_ids": torch.empty(B, max_new, k, dtype=torch.int32, device=x.device),
+                    "top_logprobs": torch.empty(B, max_new, k, dtype=torch.float32, device=x.device)}
+            if want_rank:
+                topk["token_ranks"] = torch.empty(B, max_new, dtype=torch.int32, device=x.device)
+            tk = _lib.SvTokenTopk(k, source, _ptr(topk["top_token_ids"]), _ptr(topk["top_logprobs"]), _ptr(topk.get("token_ranks")), max_new)
+            check(self.lib.sv_generate_topk(self._h, _ptr(x), n_prompts, lens_arr, S0, G, C.byref(sp), C.byref(lp) if lp is not None else None,
+                                            C.byref(outs), C.byref(ts) if ts is not None else None, C.byref(tk), _ptr(out), C.byref(n), _stream()),
+                  "sv_generate_topk")
+        elif token_stats:
             check(self.lib.sv_generate_stats(self._h, _ptr(x), n_prompts, lens_arr, S0, G, C.byref(sp), C.byref(lp) if lp is not None else None,
                                              C.byref(outs), C.byref(ts), _ptr(out), C.byref(n), _stream()), "sv_generate_stats")
         elif lp is not None:
@@ -536,11 +599,13 @@ class HipEngine:
         if cb_errors:
             raise cb_errors[0]
         L = n.value
-        if not return_outputs and stats is None:
+        if not return_outputs and stats is None and topk is None:
             return out[:, :L]
         res = {"sequences": out[:, :L], "n_generated": L}
         if stats is not None:
             res.update({k: v[:, :L] for k, v in stats.items()})
+        if topk is not None:
+            res.update({k: v[:, :L] for k, v in topk.items()})
         if beam:
             res["sequences_scores"] = torch.tensor(list(seq_scores), dtype=torch.float32)
             res["beam_indices"] = torch.tensor(list(beam_idx), dtype=torch.int64).view(B, max_new)[:, :L].contiguous()
@@ -1150,6 +1215,44 @@ def op_logprob_rows(logits, targets, temperature: float = 1.0, valid: Optional[i
     check(lib.sv_op_logprob_rows(_ptr(logits), R, V, ld, _ptr(targets), float(temperature), _ptr(lp), _ptr(lse), _ptr(ent), _ptr(am),
                                  flag, _stream()), "sv_op_logprob_rows")
     return lp, lse, ent, am, (int(flag[0]), int(flag[1]))
+
+
+def op_topk_rows_bf16(logits, targets, logsumexp, k: int, temperature: float = 1.0, valid: Optional[int] = None):
+    """topk_rows_bf16_kernel (sv_forward_topk's kernel) on the rows of `op_logprob_rows` and the logsumexp it returned for them.  Returns
+    (ids int32 [R, k], logprobs fp32 [R, k], ranks int32 [R])."""
+    lib = _lib.load()
+    logits = _need(logits, torch.bfloat16, "logits")
+    R, ld = logits.shape
+    V = ld if valid is None else int(valid)
+    targets = _need(targets.to(torch.int32), torch.int32, "targets")
+    lse = _need(logsumexp, torch.float32, "logsumexp")
+    if targets.numel() != R or lse.numel() != R:
+        raise ValueError("one target and one logsumexp per row")
+    ids = torch.empty(R, max(int(k), 1), dtype=torch.int32, device=logits.device)
+    lps = torch.empty(R, max(int(k), 1), dtype=torch.float32, device=logits.device)
+    rank = torch.empty(R, dtype=torch.int32, device=logits.device)
+    check(lib.sv_op_topk_rows_bf16(_ptr(logits), R, V, ld, _ptr(targets), float(temperature), _ptr(lse), int(k), _ptr(ids), _ptr(lps), _ptr(rank),
+                                   _stream()), "sv_op_topk_rows_bf16")
+    return ids, lps, rank
+
+
+def op_token_topk(logits, tokens, k: int, temperature: float = 1.0, valid: Optional[int] = None):
+    """sv_generate_topk's raw-source row function on caller-given fp32 rows [B, ld], `valid` = V columns (default ld); tokens int32 [B] or None
+    (no rank).  Returns (ids int32 [B, k], logprobs fp32 [B, k], ranks int32 [B])."""
+    lib = _lib.load()
+    logits = _need(logits, torch.float32, "logits")
+    B, ld = logits.shape
+    V = ld if valid is None else int(valid)
+    if tokens is not None:
+        tokens = _need(tokens.to(torch.int32), torch.int32, "tokens")
+        if tokens.numel() != B:
+            raise ValueError("one token per row")
+    ids = torch.empty(B, max(int(k), 1), dtype=torch.int32, device=logits.device)
+    lps = torch.empty(B, max(int(k), 1), dtype=torch.float32, device=logits.device)
+    rank = torch.empty(B, dtype=torch.int32, device=logits.device)
+    check(lib.sv_op_token_topk(_ptr(logits), B, V, ld, float(temperature), _ptr(tokens), int(k), _ptr(ids), _ptr(lps), _ptr(rank), _stream()),
+          "sv_op_token_topk")
+    return ids, lps, rank
 
 
 def op_cb_select(logits, requests: Sequence[dict], history=None):

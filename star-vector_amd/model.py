@@ -629,7 +629,8 @@ class HipCausalLM(_EngineModule):
                  num_return_sequences: int = 1, top_k: Optional[int] = 50, streamer=None, seed: Optional[int] = None,
                  return_dict_in_generate: bool = False, output_scores: bool = False, output_logits: bool = False,
                  share_prompt: bool = True, no_repeat_ngram_size: int = 0, bad_words_ids=None, min_p: Optional[float] = None,
-                 output_token_logprobs: bool = False, **unused):
+                 output_token_logprobs: bool = False, output_top_logprobs: Optional[int] = None, top_logprobs_source: str = "raw",
+                 **unused):
         # top_k: the reference never passes it; its pinned transformers==4.49.0 (pyproject.toml:18) defaults
         # GenerationConfig.top_k to 50, so every do_sample call there is top-k 50 followed by top-p.  Same default here.
         if inputs_embeds is None:
@@ -659,6 +660,26 @@ class HipCausalLM(_EngineModule):
             if getattr(self, "batcher", None) is not None:
                 raise NotImplementedError("output_token_logprobs with a batcher attached is not built: its requests run as "
                                           "continuous-batching slots, which keep no per-token statistics")
+        # output_top_logprobs = k (an extension, sv_generate_topk): the returned object also carries top_token_ids / top_logprobs [rows, n_new, k]
+        # -- the k most likely ids of every step and their log-probs, best first -- and token_ranks [rows, n_new], under the distribution
+        # top_logprobs_source names ("raw": that of token_logprobs, "processed": that of token_logprobs_processed).  It raises wherever
+        # output_token_logprobs raises, and without return_dict_in_generate (there is no object to carry the fields): never dropped.
+        topk = None
+        if output_top_logprobs is not None and output_top_logprobs is not False:
+            from .engine import token_topk_request
+            token_topk_request(dict(k=output_top_logprobs, source=top_logprobs_source))      # ValueError: k outside 1..32, an unknown source
+            if not return_dict_in_generate:
+                raise ValueError("output_top_logprobs needs return_dict_in_generate=True: the lists travel on the returned object")
+            if int(num_beams) > 1:
+                raise NotImplementedError("output_top_logprobs with num_beams > 1 is not built: beam search reports sequences_scores, and "
+                                          "beam rows reorder")
+            if attention_mask is not None and not bool((attention_mask == 1).all()):
+                raise NotImplementedError("output_top_logprobs with a padded attention_mask is not built: padded rows run as "
+                                          "continuous-batching slots, which keep no per-token lists")
+            if getattr(self, "batcher", None) is not None:
+                raise NotImplementedError("output_top_logprobs with a batcher attached is not built: its requests run as "
+                                          "continuous-batching slots, which keep no per-token lists")
+            topk = dict(k=int(output_top_logprobs), source=top_logprobs_source)
         # HF's token-changing processors, on device (sv_generate_processed): NoRepeatNGram, NoBadWords, MinP.  Set = the call goes through
         # HipEngine.generate_processed; where that route is not built the call raises, it never drops the argument.
         proc = self._processor_args(no_repeat_ngram_size, bad_words_ids, min_p, do_sample, eos_token_id)
@@ -775,10 +796,12 @@ class HipCausalLM(_EngineModule):
                 streamer.end()
             return generate_output(False, sequences=out) if return_dict_in_generate else out
         extra, slabs = {}, {}
-        if return_dict_in_generate and (want or num_beams > 1 or stats):
+        if return_dict_in_generate and (want or num_beams > 1 or stats or topk):
             extra, slabs = self._output_slabs(inputs_embeds, max_length, num_beams, output_scores, output_logits, G)
             if stats:       # True: all three; a tuple of the field names: those alone (generate_im2svg_grpo leaves the processed log-prob out)
                 extra["token_stats"] = True if output_token_logprobs is True else tuple(output_token_logprobs)
+            if topk:        # (the keyword goes down only when asked for: an engine without it is never handed it)
+                extra["token_topk"] = topk
         lock = getattr(self._engine, "call_lock", None) or contextlib.nullcontext()
         with lock:          # the same lock the slot path holds: a classic generate never lands between its cb_reset / cb_admit
             out = self._classic_generate(inputs_embeds, max_length, do_sample, temperature, top_p, eos_token_id, pad_token_id,
@@ -798,12 +821,15 @@ class HipCausalLM(_EngineModule):
             dev = out["sequences"].device
             fields["beam_indices"] = out["beam_indices"].to(dev)
             fields["sequences_scores"] = out["sequences_scores"].to(dev) if output_scores else None
-        if not stats:
+        if not stats and not topk:
             return generate_output(num_beams > 1, **fields)
         # the extension's three fields beside HF's: HF's output dataclass has no place for them, so the object is the stand-in with the same
         # field names, read as attributes or as keys
         res = _GenerateOutput({k: fields.get(k) for k in _DECODER_ONLY_FIELDS})
-        res.update({k: out.get(k) for k in ("token_logprobs", "token_logprobs_processed", "token_entropies")})
+        if stats:
+            res.update({k: out.get(k) for k in ("token_logprobs", "token_logprobs_processed", "token_entropies")})
+        if topk:
+            res.update({k: out.get(k) for k in ("top_token_ids", "top_logprobs", "token_ranks")})
         return res
 
     def _processor_args(self, no_repeat_ngram_size, bad_words_ids, min_p, do_sample, eos_token_id):
@@ -1060,7 +1086,8 @@ class StarVectorStarCoder(nn.Module):
             generation_kwargs["num_beams"] = 1
             if "share_prompt" in kwargs:                               # extension: False = the repeated prompts (A/B)
                 generation_kwargs["share_prompt"] = kwargs["share_prompt"]
-        if not kwargs.get("return_logprobs"):
+        top_k = kwargs.get("return_top_logprobs")
+        if not kwargs.get("return_logprobs") and not top_k:
             outputs = self.svg_transformer.transformer.generate(**generation_kwargs)
             outputs = torch.cat([prompt_tokens.input_ids.repeat(num_return_sequences, 1), outputs], dim=1)    # :279
             raw_svg = self.svg_transformer.tokenizer.batch_decode(outputs, skip_special_tokens=True)
@@ -1068,16 +1095,26 @@ class StarVectorStarCoder(nn.Module):
         # extension (return_logprobs=True): the roll-out policy's own per-token log-probs and entropies from the decode loop (GRPO's old
         # log-probs: log_softmax(logits / temperature) at every sampled token, what completion_logprobs returns for the same weights), and the
         # mask of the columns that belong to each completion
-        gen = self.svg_transformer.transformer.generate(**generation_kwargs, return_dict_in_generate=True,
-                                                      output_token_logprobs=("token_logprobs", "token_entropies"))
+        # return_top_logprobs=k: the k most likely ids of every step, their log-probs and the sampled token's rank under the same distribution
+        # (on-policy distillation targets); alone or beside return_logprobs
+        ask = {}
+        if kwargs.get("return_logprobs"):
+            ask["output_token_logprobs"] = ("token_logprobs", "token_entropies")
+        if top_k:
+            ask.update(output_top_logprobs=top_k, top_logprobs_source=kwargs.get("top_logprobs_source", "raw"))
+        gen = self.svg_transformer.transformer.generate(**generation_kwargs, return_dict_in_generate=True, **ask)
         new = gen["sequences"]
         lm = self.svg_transformer.transformer
         eos = generation_kwargs.get("eos_token_id")
         outputs = torch.cat([prompt_tokens.input_ids.repeat(num_return_sequences, 1), new], dim=1)    # :279
         raw_svg = self.svg_transformer.tokenizer.batch_decode(outputs, skip_special_tokens=True)
-        return {"raw_svg": raw_svg, "outputs": outputs, "inputs_embeds": inputs_embeds,
-                "logprobs": gen["token_logprobs"], "entropies": gen["token_entropies"],
-                "completion_mask": completion_mask(new, int(lm.eos_token_id if eos is None else eos))}
+        res = {"raw_svg": raw_svg, "outputs": outputs, "inputs_embeds": inputs_embeds}
+        if kwargs.get("return_logprobs"):
+            res.update(logprobs=gen["token_logprobs"], entropies=gen["token_entropies"])
+        res["completion_mask"] = completion_mask(new, int(lm.eos_token_id if eos is None else eos))
+        if top_k:
+            res.update({k: gen[k] for k in ("top_token_ids", "top_logprobs", "token_ranks")})
+        return res
 
 
 class StarVectorStarCoder2(StarVectorStarCoder):
@@ -1227,13 +1264,17 @@ class StarVectorForCausalLM(nn.Module):
 
     @torch.no_grad()
     def completion_logprobs(self, vision_embeds, input_ids, num_generations, attention_mask, num_logits_to_keep,
-                            temperature: float = 1.0, return_entropy: bool = False):
+                            temperature: float = 1.0, return_entropy: bool = False, top_logprobs: int = 0):
         """What a GRPO trainer computes from `forward`'s logits, without the logits: float32 [B, n], out[b, j] = the log-probability
         of input_ids[b, -n + j] given everything before it -- selective_log_softmax(forward(...).logits[:, :-1] / temperature, ids)
         with the softmax in fp32 over the bf16 logits (sv_forward_logprobs: device memory does not grow with B * n * vocab).
         n = num_logits_to_keep (0 / None: every completion token that has a position before it).  Padding as in `forward`: an
         entry whose token is right padding is 0; left-padded rows are scored without their pads; masks with holes raise
-        NotImplementedError.  return_entropy: also the entropy [B, n] of the distribution each token was drawn from (0 at pads)."""
+        NotImplementedError.  return_entropy: also the entropy [B, n] of the distribution each token was drawn from (0 at pads).
+        top_logprobs = k in 1..32 (sv_forward_topk; teacher-forced distillation targets): the result is a dict instead -- "logprobs" [B, n],
+        "entropies" when asked for, and "top_token_ids" / "top_logprobs" [B, n, k] (the k most likely ids of every position, best first, and
+        their log-probs) and "token_ranks" [B, n] (the rank of the token itself, 0 at pads)."""
+        k = int(top_logprobs or 0)
         completion_embeds = self.model._get_embeddings(input_ids)
         inputs_embeds = torch.cat([vision_embeds.repeat(num_generations, 1, 1).to(completion_embeds.dtype),
                                    completion_embeds], dim=1)
@@ -1256,27 +1297,44 @@ class StarVectorForCausalLM(nn.Module):
             targets[:, :n] = targets[:, :n].masked_fill(pad, -100)
 
         def score(e16, tg):
-            r = self._run_scoring(lambda: self.engine.forward_logprobs(e16, tg, n + 1, temperature, return_entropy))
-            return r.logprobs, r.entropy
+            # (top_k goes down only when asked for: an engine without it is never handed it)
+            r = self._run_scoring(lambda: self.engine.forward_logprobs(e16, tg, n + 1, temperature, return_entropy, **({"top_k": k} if k else {})))
+            return r.logprobs, r.entropy, ((r.top_token_ids, r.top_logprobs, r.token_ranks) if k else None)
 
         if lead is None:
-            lp, ent = score(emb16, targets)
+            lp, ent, top = score(emb16, targets)
         else:
             lp = torch.zeros(B, n + 1, dtype=torch.float32, device=emb16.device)
             ent = torch.zeros_like(lp) if return_entropy else None
+            top = None
+            if k:
+                top = (torch.full((B, n + 1, k), -1, dtype=torch.int32, device=emb16.device),
+                       torch.zeros(B, n + 1, k, dtype=torch.float32, device=emb16.device),
+                       torch.zeros(B, n + 1, dtype=torch.int32, device=emb16.device))
             for pads in sorted(set(lead.tolist())):
                 rows = (lead == pads).nonzero().flatten().to(emb16.device)
-                a, h = score(emb16[rows, pads:].contiguous(), targets[rows].contiguous())
+                a, h, t3 = score(emb16[rows, pads:].contiguous(), targets[rows].contiguous())
                 lp[rows] = a
                 if return_entropy:
                     ent[rows] = h
+                if k:
+                    for dst, src in zip(top, t3):
+                        dst[rows] = src
         lp = lp[:, :n].contiguous()
+        if return_entropy:
+            ent = ent[:, :n]
+            if attention_mask is not None:
+                ent = ent.masked_fill(pad, 0.0)
+            ent = ent.contiguous()
+        if k:
+            res = {"logprobs": lp, "top_token_ids": top[0][:, :n].contiguous(), "top_logprobs": top[1][:, :n].contiguous(),
+                   "token_ranks": top[2][:, :n].contiguous()}
+            if return_entropy:
+                res["entropies"] = ent
+            return res
         if not return_entropy:
             return lp
-        ent = ent[:, :n]
-        if attention_mask is not None:
-            ent = ent.masked_fill(pad, 0.0)
-        return lp, ent.contiguous()
+        return lp, ent
 
     def generate_im2svg(self, batch, **kwargs):           # starvector_arch.py:186-187
         return self.model.generate_im2svg(batch, **kwargs)
