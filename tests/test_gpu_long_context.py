@@ -38,10 +38,10 @@ def _r(t):
     return t.to(torch.bfloat16).to(torch.float32)
 
 
-def _attn_engine(n_head, n_kv, max_batch, max_seq_len, window=0):
-    """An engine with the decoder's attention geometry (head_dim 128) and everything else small: the attention test surface needs no
-    weights (the caller supplies q / K / V)."""
-    hidden = n_head * 128
+def _attn_engine(n_head, n_kv, max_batch, max_seq_len, window=0, dh=128):
+    """An engine with the decoder's attention geometry (head_dim `dh`: 128, or 64 in tests/test_gpu_decoder_head_dim64.py) and everything
+    else small: the attention test surface needs no weights (the caller supplies q / K / V)."""
+    hidden = n_head * dh
     ec = sva.EngineConfig(image_size=28, patch_size=14, vit_width=128, vit_layers=1, vit_heads=2, hidden=hidden, n_layer=1,
                           n_head=n_head, n_inner=256, vocab=512, n_positions=max_seq_len, max_batch=max_batch,
                           max_seq_len=max_seq_len, arch="v2" if n_kv > 1 or window else "v1", n_kv_head=n_kv,
@@ -82,11 +82,11 @@ def _ref_attention(q, K, V, pos, window):
     return _r(torch.einsum("bhl,bhld->bhd", pr, vv).reshape(B, H * dh))
 
 
-def _peaked_case(B, H, nkv, L, sharp, seed):
+def _peaked_case(B, H, nkv, L, sharp, seed, dh=128):
     g = torch.Generator(device=dev()).manual_seed(seed)
-    K = _r(torch.randn(B, nkv, L, 128, generator=g, device=dev()))
-    V = _r(torch.randn(B, nkv, L, 128, generator=g, device=dev()))
-    q = torch.randn(B, H, 128, generator=g, device=dev()) * sharp           # scores ~ N(0, sharp^2): a few keys carry the mass
+    K = _r(torch.randn(B, nkv, L, dh, generator=g, device=dev()))
+    V = _r(torch.randn(B, nkv, L, dh, generator=g, device=dev()))
+    q = torch.randn(B, H, dh, generator=g, device=dev()) * sharp            # scores ~ N(0, sharp^2): a few keys carry the mass
     return q, K, V
 
 
