@@ -459,6 +459,39 @@ int  sv_cb_poll(sv_engine* e, int32_t* host_live, int32_t* host_steps, int32_t c
 int  sv_cb_read(sv_engine* e, int32_t slot, int32_t first, int32_t count, int64_t* host_tokens);
 int  sv_cb_release(sv_engine* e, int32_t slot);
 int  sv_cb_reset(sv_engine* e);
+/* Per-request log-probs on the continuous batch (entry points appended; SV_ABI_VERSION and sv_cb_request are unchanged).
+ * sv_cb_admit_logprobs is sv_cb_admit_shared -- packed prompts, request i samples prompt host_group[i] -- plus lps [n], parallel to reqs: what
+ * request i records for every token it emits, the first one (selected inside the admit from the prompt's logits) being column 0.  lps NULL or
+ * every enable 0: exactly sv_cb_admit_shared, same tokens and launches.  A recording slot keeps, per column, the emitted token's log-prob and
+ * rank and the k best ids with their log-probs; the definitions are sv_generate_topk's for the same k and source (descending by the value before
+ * the division by T, equal values by ascending id, tail (-1, -inf), rank = 1 + #{ x_i > x_tok }, the slot of the emitted id equals the token's
+ * log-prob bit for bit, a row without a comparable value reads ids -1 / rank 0 / log-probs NaN), and an HF-semantics slot's record equals its
+ * solo sv_generate_topk output bit for bit:
+ *   source 0   log_softmax(raw / T), T = the slot's temperature when it samples, else 1.  HF slots only: a vLLM-semantics slot has rewritten
+ *              its raw row in place by then (SV_EINVAL at admit)
+ *   source 1   the processed row.  HF: repetition penalty, the min-length hold of EOS, the sampler's kept set, removed ids at -inf.  vLLM: what
+ *              vLLM 0.5.5's Sampler reports -- log_softmax over the row after logit_bias, the min_tokens hold and the repetition / frequency /
+ *              presence penalties; a sampling slot divides by its temperature and applies its top-k / top-p / min_p masks first, a greedy
+ *              slot uses T = 1 and no mask.  The rank is taken over the same vector.
+ * The record is written inside the slot's own selection block (after the token is known, before the slot's repetition set and counts take it),
+ * so it depends on that slot alone: the same bits whether other slots record or not, in any row bucket, however many steps a sv_cb_step call
+ * runs.  A batch with a recording slot runs the recording form of the selection kernel (its captured step graphs are kept beside the plain
+ * ones); a batch in which nobody records replays exactly the graphs it replayed before.
+ * Memory: the first admit that asks allocates, for the life of the engine, max_batch x max_seq_len x (8 + 8 x SV_TOPK_MAX) bytes = 264 B per
+ * slot column (64 slots x 8192 columns: 138 MB); an engine that never asks allocates nothing.
+ * sv_cb_read_logprobs copies columns [first, first + count) of a slot to the host: host_logprob / host_rank [count], host_ids / host_lps
+ * [count][k] with the slot's own k (each may be NULL).  Only columns the slot has emitted (< its steps in sv_cb_poll) exist: anything beyond, a
+ * slot admitted without enable and a slot not in use are SV_EINVAL -- a reused slot never shows its predecessor's columns.
+ * SV_EINVAL before any device work for an enabled entry with k outside 0..SV_TOPK_MAX, a source outside {0, 1}, or source 0 with semantics 1. */
+typedef struct sv_cb_logprobs {
+    int32_t enable;            /* 0: this request records nothing and costs nothing */
+    int32_t k;                 /* 0..SV_TOPK_MAX: 0 = the emitted token's log-prob and rank only */
+    int32_t source;            /* 0 raw, 1 processed */
+} sv_cb_logprobs;
+int  sv_cb_admit_logprobs(sv_engine* e, const void* dev_embeds_packed, int32_t n_prompts, const int32_t* host_lens, int32_t n,
+                          const int32_t* host_group, const sv_cb_request* reqs, const sv_cb_logprobs* lps, int32_t* slots_out, sv_stream stream);
+int  sv_cb_read_logprobs(sv_engine* e, int32_t slot, int32_t first, int32_t count, float* host_logprob, int32_t* host_rank, int32_t* host_ids,
+                         float* host_lps);
 
 /* beam scorer: one step consumes dev_logits [batch * num_beams][ld] (row r = request r / num_beams, beam r % num_beams)
  * and reports (host arrays, each batch * num_beams long, may be NULL) the flat parent row, the token and the running

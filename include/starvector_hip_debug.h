@@ -259,6 +259,13 @@ int  sv_op_sample_top_p(const float* logits, int32_t B, int32_t V, int32_t ld, f
  * counts and, with the prompt ids, its repetition set.  host_out [B] = the token each row takes. */
 int  sv_op_cb_select(const float* dev_logits, int32_t B, int32_t V, int32_t ld, const sv_cb_request* reqs,
                      const int32_t* host_history, int32_t ld_hist, const int32_t* host_hist_len, int32_t* host_out, sv_stream stream);
+/* sv_op_cb_select plus one sv_cb_logprobs per row (the recording form of cb_step_kernel: the device code behind sv_cb_admit_logprobs): row b
+ * records what lps[b] asks.  Host outputs: host_out [B] tokens (those of sv_op_cb_select on the same rows), host_logprob / host_rank [B],
+ * host_ids / host_lps [B][ld_k] with ld_k >= every enabled row's k -- row b's first k entries are its list, the rest (-1, -inf); a row with
+ * enable = 0 reads log-prob NaN, rank 0 and an empty list. */
+int  sv_op_cb_logprobs(const float* dev_logits, int32_t B, int32_t V, int32_t ld, const sv_cb_request* reqs, const sv_cb_logprobs* lps,
+                       const int32_t* host_history, int32_t ld_hist, const int32_t* host_hist_len, int32_t* host_out, float* host_logprob,
+                       int32_t* host_rank, int32_t* host_ids, float* host_lps, int32_t ld_k, sv_stream stream);
 /* the kernel of sv_generate_processed's token bans (processors.hip ban_tokens_kernel) on caller-given rows: row b of dev_logits [B][ld] fp32
  * (device, V valid columns) is a row whose generated ids so far are host_hist[b][0 .. host_hist_len[b]) (HOST, row stride ld_hist, ids inside
  * the vocabulary).  The ids lp->no_repeat_ngram_size and lp's bad words ban at that point are set to -inf IN PLACE; every other value is left

@@ -64,6 +64,12 @@ class SvCbRequest(C.Structure):
 CB_MAX_LOGIT_BIAS, CB_MAX_STOP_ANY = 128, 8
 
 
+class SvCbLogprobs(C.Structure):
+    # sv_cb_admit_logprobs: what one request of a continuous batch records per emitted token (parallel to the sv_cb_request array)
+    _fields_ = [("enable", C.c_int32), ("k", C.c_int32), ("source", C.c_int32)]
+
+
+
 class SvBeamConfig(C.Structure):
     _fields_ = [
         ("batch", C.c_int32), ("num_beams", C.c_int32), ("vocab", C.c_int32), ("max_new", C.c_int32),
@@ -157,6 +163,8 @@ PRODUCT_PROTOTYPES = {
     "sv_cb_read": (_I, [_P, _I, _I, _I, C.POINTER(C.c_int64)]),
     "sv_cb_release": (_I, [_P, _I]),
     "sv_cb_reset": (_I, [_P]),
+    "sv_cb_admit_logprobs": (_I, [_P, _P, _I, C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(SvCbRequest), C.POINTER(SvCbLogprobs), C.POINTER(_I), _P]),
+    "sv_cb_read_logprobs": (_I, [_P, _I, _I, _I, C.POINTER(_F), C.POINTER(_I), C.POINTER(_I), C.POINTER(_F)]),
     "sv_beam_create": (_I, [C.POINTER(SvBeamConfig), C.POINTER(_P)]),
     "sv_beam_destroy": (_I, [_P]),
     "sv_beam_step": (_I, [_P, _P, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_F), _P]),
@@ -220,6 +228,8 @@ DEBUG_PROTOTYPES = {
     "sv_op_token_topk": (_I, [_P, _I, _I, _I, _F, _P, _I, _P, _P, _P, _P]),
     "sv_op_ban_tokens": (_I, [_P, _I, _I, _I, C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(SvLogitsProcessors), _P]),
     "sv_op_cb_select": (_I, [_P, _I, _I, _I, C.POINTER(SvCbRequest), C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(_I), _P]),
+    "sv_op_cb_logprobs": (_I, [_P, _I, _I, _I, C.POINTER(SvCbRequest), C.POINTER(SvCbLogprobs), C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(_I),
+                               C.POINTER(_F), C.POINTER(_I), C.POINTER(_I), C.POINTER(_F), _I, _P]),
 }
 
 PROTOTYPES = {**PRODUCT_PROTOTYPES, **DEBUG_PROTOTYPES}

@@ -9,6 +9,10 @@ Here concurrent requests share ONE decode loop: `ContinuousBatcher` owns a sched
   * advances every live slot by a few decode steps per iteration (`sv_cb_step`: one captured hipGraph per row bucket),
   * hands each request the tokens that became final since the last look (streaming) and frees the slots of finished requests.
 
+A request whose params carry ``logprobs`` (k, 0..32) records on device, per emitted token, the token's log-prob and rank and the k most
+likely ids (`sv_cb_admit_logprobs`; ``logprob_source`` "raw" | "processed", default: processed under vLLM semantics, raw otherwise); the
+record arrives with the tokens and `_Request.logprobs` holds it.  Requests without the key are queued and admitted as before.
+
 Every slot has its own sampling parameters, budget, EOS, stop sequence and random stream, so a request's tokens are exactly
 what a solo `HipEngine.generate` call would return for it (tests/test_gpu_serving.py).  No kernels here: host logic only.
 """
@@ -16,11 +20,27 @@ from __future__ import annotations
 
 import threading
 from collections import deque
-from typing import Callable, Deque, Dict, List, Optional
+from typing import Callable, Deque, Dict, List, NamedTuple, Optional
 
 import torch
 
 from ._lib import StarVectorBusy
+
+
+class TokenLogprobs(NamedTuple):
+    """The record of a request that asked for ``logprobs``, N = tokens emitted: log-prob and rank of each, the k best ids and their log-probs."""
+    logprobs: torch.Tensor           # fp32 [N]
+    ranks: torch.Tensor              # int32 [N]
+    top_ids: torch.Tensor            # int32 [N, k], -1 past the ids that enter
+    top_logprobs: torch.Tensor       # fp32 [N, k], -inf there
+
+
+def _logprobs_of(params: dict) -> Optional[dict]:
+    """What a request's params ask the engine to record: None, or the `HipEngine.cb_admit` logprobs entry."""
+    k = params.get("logprobs")
+    if k is None or k is False:
+        return None
+    return dict(k=int(k), source=params.get("logprob_source"))
 
 
 class _Request:
@@ -32,6 +52,8 @@ class _Request:
         self.slot: Optional[int] = None
         self.sent = 0                      # tokens already handed over
         self.chunks: List[torch.Tensor] = []
+        self.lp = _logprobs_of(params)     # None: the request records no log-probs
+        self.lp_chunks: List[tuple] = []
         self.done = threading.Event()
         self.error: Optional[BaseException] = None
 
@@ -45,6 +67,16 @@ class _Request:
             return self.value
         toks = torch.cat(self.chunks) if self.chunks else torch.empty(0, dtype=torch.int64)
         return toks.view(1, -1)
+
+    @property
+    def logprobs(self) -> Optional[TokenLogprobs]:
+        """The record delivered so far (complete once `result` returns); None for a request that did not ask."""
+        if self.lp is None:
+            return None
+        if not self.lp_chunks:
+            k = self.lp["k"]
+            return TokenLogprobs(torch.empty(0), torch.empty(0, dtype=torch.int32), torch.empty(0, k, dtype=torch.int32), torch.empty(0, k))
+        return TokenLogprobs(*[torch.cat(c) for c in zip(*self.lp_chunks)])
 
 
 class ContinuousBatcher:
@@ -147,17 +179,19 @@ class ContinuousBatcher:
             group = group[:room]
             while group:
                 try:
+                    # the requests that record log-probs ride in a keyword the engine sees only when one of them asks
+                    kw = dict(logprobs=[r.lp for r in group]) if any(r.lp is not None for r in group) else {}
                     keys = [id(r) if r.group is None else id(r.group) for r in group]
                     prompts = list(dict.fromkeys(keys))         # in the order of their first request
                     if ragged and len(prompts) < len(group) and hasattr(self.engine, "cb_admit_shared"):
                         # samples of one prompt among them: one prompt pass per PROMPT, its full KV pages shared (sv_cb_admit_shared)
                         first = {k: r for r, k in reversed(list(zip(group, keys)))}
                         slots = self.engine.cb_admit_shared([first[k].emb[0] for k in prompts], None, [prompts.index(k) for k in keys],
-                                                            [r.params for r in group])
+                                                            [r.params for r in group], **kw)
                     elif ragged:
-                        slots = self.engine.cb_admit([r.emb[0] for r in group], [r.params for r in group])
+                        slots = self.engine.cb_admit([r.emb[0] for r in group], [r.params for r in group], **kw)
                     else:
-                        slots = self.engine.cb_admit(torch.cat([r.emb for r in group], 0), [r.params for r in group])
+                        slots = self.engine.cb_admit(torch.cat([r.emb for r in group], 0), [r.params for r in group], **kw)
                 except StarVectorBusy:
                     group = group[:-1]              # KV pages are short: try fewer, the rest waits for a release
                     continue
@@ -191,6 +225,8 @@ class ContinuousBatcher:
             n = steps[s]
             if n > req.sent:
                 toks = self.engine.cb_read(s, req.sent, n - req.sent)
+                if req.lp is not None:              # before the tokens are handed over: a consumer that sees a token finds its record
+                    req.lp_chunks.append(self.engine.cb_read_logprobs(s, req.sent, n - req.sent))
                 req.chunks.append(toks)
                 first, req.sent = req.sent, n
                 if req.on_tokens is not None:

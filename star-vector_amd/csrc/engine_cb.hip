@@ -18,11 +18,53 @@ static int cb_bucket(const sv_engine* e) {
     return b > e->cfg.max_batch ? e->cfg.max_batch : b;
 }
 
-static void cb_step_args(sv_engine* e, CbStepArgs& a, const int32_t* map) {
+// record: some slot of the launch records log-probs (the recording kernel; the descriptors decide per slot)
+static void cb_step_args(sv_engine* e, CbStepArgs& a, const int32_t* map, bool record) {
     a.logits = e->logits; a.ld = e->Vpad; a.V = e->cfg.vocab; a.slots = e->cb_slots; a.slot_map = map;
     a.cur_tok = e->cur_tok; a.positions = e->positions; a.out_tokens = e->out_tok; a.ld_out = e->out_ld;
     a.seen = e->seen; a.seen_words = e->seen_words; a.n_live = e->cb_nlive; a.events = e->cb_events; a.bad = e->d_bad;
     a.counts = e->cb_counts; a.ld_counts = e->Vpad; a.bias = e->cb_bias;
+    a.lp = record ? e->cb_lp : nullptr;
+}
+
+// ---- per-slot log-prob records (sv_cb_admit_logprobs / sv_cb_read_logprobs) ----
+// a slot in use that records: the step of such a batch is the recording kernel, under a graph key of its own (a finished slot that has not been
+// released yet still counts: the host learns of the finish at the next poll)
+static bool cb_any_records(const sv_engine* e) {
+    if (!e->cb_lp) return false;
+    for (int s2 = 0; s2 < e->cfg.max_batch; ++s2) if (e->cb_used[s2] && e->cb_lp_host[s2].enable) return true;
+    return false;
+}
+// first use: the descriptors and the four buffers; slot s2 owns columns [s2 * out_ld, (s2 + 1) * out_ld) of each
+static int cb_lp_alloc(sv_engine* e) {
+    if (e->cb_lp) return 0;
+    const size_t mb = (size_t)e->cfg.max_batch, cols = mb * (size_t)e->out_ld;
+    float *lp = nullptr, *lps = nullptr;
+    int32_t *rank = nullptr, *ids = nullptr;
+    CbLogprobs* d = nullptr;
+    SVCHECK(dalloc(e, &lp, cols, false));
+    SVCHECK(dalloc(e, &rank, cols, false));
+    SVCHECK(dalloc(e, &ids, cols * SV_TOPK_MAX, false));
+    SVCHECK(dalloc(e, &lps, cols * SV_TOPK_MAX, false));
+    SVCHECK(dalloc(e, &d, mb));
+    e->cb_lp_host.assign(mb, CbLogprobs{});
+    for (size_t s2 = 0; s2 < mb; ++s2) {
+        CbLogprobs& h = e->cb_lp_host[s2];
+        h.logprob = lp + s2 * e->out_ld; h.rank = rank + s2 * e->out_ld;
+        h.ids = ids + s2 * e->out_ld * SV_TOPK_MAX; h.lps = lps + s2 * e->out_ld * SV_TOPK_MAX;
+    }
+    e->cb_lp = d;
+    return 0;
+}
+// the descriptor of slot s2 <- what request i asks (lp == nullptr: nothing); the host image is a member, so the copy may stay in flight
+static int cb_lp_set(sv_engine* e, int s2, const sv_cb_logprobs* lp, hipStream_t st) {
+    if (!e->cb_lp) return 0;
+    CbLogprobs& h = e->cb_lp_host[s2];
+    const bool on = lp && lp->enable;
+    if (!on && !h.enable) return 0;                          // off on both sides already
+    h.enable = on ? 1 : 0; h.k = on ? lp->k : 0; h.source = on ? lp->source : 0;
+    HIPCHECK(hipMemcpyAsync(e->cb_lp + s2, &h, sizeof(CbLogprobs), hipMemcpyHostToDevice, st));
+    return 0;
 }
 
 namespace sveng {
@@ -63,6 +105,20 @@ int cb_check_request(const sv_cb_request& r, int V, int i, const char* who) {
     return 0;
 }
 
+int cb_check_logprobs(const sv_cb_request* reqs, const sv_cb_logprobs* lps, int n, const char* who) {
+    for (int i = 0; lps && i < n; ++i) {
+        const sv_cb_logprobs& l = lps[i];
+        if (!l.enable) continue;
+        if (l.k < 0 || l.k > SV_TOPK_MAX) return fail(SV_EINVAL, "%s: request %d: logprobs k=%d must be in 0..%d", who, i, l.k, SV_TOPK_MAX);
+        if (l.source != 0 && l.source != 1)
+            return fail(SV_EINVAL, "%s: request %d: logprobs source=%d must be 0 (log_softmax(raw / T)) or 1 (the processed row)", who, i, l.source);
+        if (reqs[i].semantics == 1 && l.source == 0)
+            return fail(SV_EINVAL, "%s: request %d: logprobs source 0 on a vLLM-semantics request (its processors rewrite the raw row in place: use source 1)",
+                        who, i);
+    }
+    return 0;
+}
+
 void cb_fill_slot(const sv_cb_request& r, CbSlot& h, CbBias& bias, std::vector<uint32_t>& seen_row, int seen_words) {
     memset(&h, 0, sizeof(h));
     memset(&bias, 0, sizeof(bias));
@@ -98,6 +154,7 @@ static int cb_begin(sv_engine* e, hipStream_t st) {
     HIPCHECK(hipMemsetAsync(e->cur_tok, 0, R * sizeof(int32_t), st));
     HIPCHECK(hipMemsetAsync(e->cb_nlive, 0, sizeof(int32_t), st));
     HIPCHECK(hipMemsetAsync(e->cb_events, 0, sizeof(int32_t), st));
+    for (int s2 = 0; s2 < e->cfg.max_batch; ++s2) SVCHECK(cb_lp_set(e, s2, nullptr, st));      // (every slot is free: nobody records)
     HIPCHECK(hipStreamSynchronize(st));                  // `table` is a host temporary
     e->cb_active = true;
     e->cached_B = 0;
@@ -174,7 +231,7 @@ static int cb_admit_impl(sv_engine* e, const void* dev_embeds, int32_t n, int32_
     if (lens) SVCHECK(prefill_forward_ragged(e, (const bf16_t*)dev_embeds, n, lens, st, e->cb_table_pf));
     else SVCHECK(prefill_forward(e, (const bf16_t*)dev_embeds, n, S0_all, st, 0, nullptr, e->cb_table_pf));
     CbStepArgs a;
-    cb_step_args(e, a, e->cb_map);
+    cb_step_args(e, a, e->cb_map, false);                  // (a request that records comes in through sv_cb_admit_logprobs: none of these does)
     launch_cb_step(a, n, st);                              // first token of every new request, from the prefill logits
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(st));                    // the staging vectors above are host temporaries
@@ -281,8 +338,9 @@ long long shared_page_plan(const int32_t* lens, int n_prompts, const int32_t* gr
 }
 }  // namespace sveng
 
+// lps: what each request records (sv_cb_admit_logprobs), nullptr = nothing
 static int cb_admit_shared_impl(sv_engine* e, const void* dev_embeds, int32_t U, const int32_t* lens, int32_t n, const int32_t* group,
-                                const sv_cb_request* reqs, int32_t* slots_out, sv_stream stream) {
+                                const sv_cb_request* reqs, const sv_cb_logprobs* lps, int32_t* slots_out, sv_stream stream) {
     const sv_config& c = e->cfg;
     const int mp = e->pages_per_seq, mb = c.max_batch;
     std::lock_guard<std::mutex> lk(e->mu);
@@ -292,6 +350,8 @@ static int cb_admit_shared_impl(sv_engine* e, const void* dev_embeds, int32_t U,
     HIPCHECK(hipStreamWaitEvent(st, e->gen_event, 0));
     SVCHECK(cb_begin(e, st));
     if (!e->fork_desc) SVCHECK(dalloc(e, &e->fork_desc, 6 * (size_t)mb));
+    const bool record = [&] { for (int i = 0; lps && i < n; ++i) if (lps[i].enable) return true; return false; }();
+    if (record) SVCHECK(cb_lp_alloc(e));
     std::vector<int> slots;
     for (int s2 = 0; s2 < mb && (int)slots.size() < n; ++s2) if (!e->cb_used[s2]) slots.push_back(s2);
     std::vector<int32_t> budgets(n), n_sh(n), n_pv(n);
@@ -354,6 +414,7 @@ static int cb_admit_shared_impl(sv_engine* e, const void* dev_embeds, int32_t U,
         } else if (any_pen) {
             HIPCHECK(hipMemsetAsync(e->seen + (size_t)s2 * e->seen_words, 0, e->seen_words * sizeof(uint32_t), st));
         }
+        if (record) SVCHECK(cb_lp_set(e, s2, lps + i, st));
     }
     HIPCHECK(hipMemcpyAsync(e->cb_table_pf, pf.data(), pf.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemcpyAsync(e->cb_map, map.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -367,8 +428,8 @@ static int cb_admit_shared_impl(sv_engine* e, const void* dev_embeds, int32_t U,
     fork_args(e, U, n, f);
     launch_fork_prompt(f, st);
     CbStepArgs a;
-    cb_step_args(e, a, e->cb_map);
-    launch_cb_step(a, n, st);                              // first token of every new request, from its prompt's logits
+    cb_step_args(e, a, e->cb_map, record);
+    launch_cb_step(a, n, st);                              // first token of every new request, from its prompt's logits (column 0 of its record)
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(st));                    // the staging vectors above are host temporaries
     return 0;
@@ -385,6 +446,7 @@ static int cb_admit_shared_impl(sv_engine* e, const void* dev_embeds, int32_t U,
             slots_out[i] = -1;
             (void)hipMemsetAsync(e->cb_slots + s2, 0, sizeof(CbSlot), st);
             (void)hipMemcpyAsync(e->block_table + (size_t)s2 * mp, trash.data(), trash.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
+            (void)cb_lp_set(e, s2, nullptr, st);
         }
         for (size_t k = taken.size(); k-- > 0;) {           // pages go back in reverse order, no holder left: the free list is as it was
             e->page_refs[taken[k]] = 0;
@@ -415,7 +477,29 @@ extern "C" int sv_cb_admit_shared(sv_engine* e, const void* dev_embeds_packed, i
                         c.max_seq_len);
         SVCHECK(cb_check_request(r, c.vocab, i, "sv_cb_admit_shared"));
     }
-    return cb_admit_shared_impl(e, dev_embeds_packed, n_prompts, host_lens, n, host_group, reqs, slots_out, stream);
+    return cb_admit_shared_impl(e, dev_embeds_packed, n_prompts, host_lens, n, host_group, reqs, nullptr, slots_out, stream);
+}
+
+// sv_cb_admit_shared plus what each request records; lps == NULL or every enable == 0: sv_cb_admit_shared's tokens and launches
+extern "C" int sv_cb_admit_logprobs(sv_engine* e, const void* dev_embeds_packed, int32_t n_prompts, const int32_t* host_lens, int32_t n,
+                                    const int32_t* host_group, const sv_cb_request* reqs, const sv_cb_logprobs* lps, int32_t* slots_out,
+                                    sv_stream stream) {
+    // (the checks that need no engine come first: they are the same on a machine without a GPU)
+    if (!dev_embeds_packed || !host_lens || !host_group || !reqs || !slots_out) return fail(SV_EINVAL, "sv_cb_admit_logprobs: null argument");
+    SVCHECK(shared_check_group("sv_cb_admit_logprobs", host_lens, n_prompts, host_group, n));
+    SVCHECK(cb_check_logprobs(reqs, lps, n, "sv_cb_admit_logprobs"));
+    SVCHECK(check_ready(e));
+    const sv_config& c = e->cfg;
+    if (n > c.max_batch) return fail(SV_EINVAL, "sv_cb_admit_logprobs: %d requests exceed max_batch %d", n, c.max_batch);
+    for (int i = 0; i < n; ++i) {
+        const sv_cb_request& r = reqs[i];
+        const int len = host_lens[host_group[i]];
+        if (r.max_new_tokens < 1 || len > c.max_seq_len || len + r.max_new_tokens > c.max_seq_len)
+            return fail(SV_EINVAL, "sv_cb_admit_logprobs: request %d: prompt %d + max_new_tokens %d out of range (max_seq_len %d)", i, len, r.max_new_tokens,
+                        c.max_seq_len);
+        SVCHECK(cb_check_request(r, c.vocab, i, "sv_cb_admit_logprobs"));
+    }
+    return cb_admit_shared_impl(e, dev_embeds_packed, n_prompts, host_lens, n, host_group, reqs, lps, slots_out, stream);
 }
 
 extern "C" int sv_cb_step(sv_engine* e, int32_t n_steps, int32_t* n_live_out, sv_stream stream) {
@@ -426,20 +510,22 @@ extern "C" int sv_cb_step(sv_engine* e, int32_t n_steps, int32_t* n_live_out, sv
     HIPCHECK(hipSetDevice(e->cfg.device));
     hipStream_t st = e->gen_stream;
     const int Bb = cb_bucket(e);
+    const bool record = cb_any_records(e);
     hipGraphExec_t gexec = nullptr;
     int per_launch = 1;
     const auto one_step = [&]() {
         decode_forward(e, Bb, st);
         CbStepArgs a;
-        cb_step_args(e, a, nullptr);
+        cb_step_args(e, a, nullptr, record);
         launch_cb_step(a, Bb, st);
     };
     if (graph_enabled()) {
         // one graph per (bucket, steps per launch), kept for the life of the engine: every argument is engine-owned.  The scheduler asks for the same
         // n_steps call after call, so the whole call is ONE graph of n_steps copies of the step (engine_generate.hip: the GPU idles 8.6 us between two
-        // graph launches and not at all between two kernels of one graph); key = bucket + 1024 * copies (0: the one-step graph).
+        // graph launches and not at all between two kernels of one graph); key = bucket + 1024 * copies (0: the one-step graph) + 2^24 when a slot
+        // records log-probs (the recording kernel: a batch in which nobody asks replays the plain graphs).
         auto capture = [&](int copies, hipGraphExec_t* out) -> int {
-            const int key = Bb + 1024 * (copies > 1 ? copies : 0);
+            const int key = Bb + 1024 * (copies > 1 ? copies : 0) + (record ? 1 << 24 : 0);
             auto it = e->cb_graphs.find(key);
             if (it != e->cb_graphs.end()) { *out = it->second.second; return 0; }
             hipGraph_t g = nullptr;
@@ -499,6 +585,33 @@ extern "C" int sv_cb_read(sv_engine* e, int32_t slot, int32_t first, int32_t cou
     return 0;
 }
 
+// columns [first, first + count) of a recording slot's record; only what the slot has emitted (< its step) exists
+extern "C" int sv_cb_read_logprobs(sv_engine* e, int32_t slot, int32_t first, int32_t count, float* host_logprob, int32_t* host_rank,
+                                   int32_t* host_ids, float* host_lps) {
+    if (!e) return fail(SV_EINVAL, "sv_cb_read_logprobs: null engine");
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!e->cb_active || slot < 0 || slot >= e->cfg.max_batch || !e->cb_used[slot]) return fail(SV_EINVAL, "sv_cb_read_logprobs: slot %d is not in use", slot);
+    if (!e->cb_lp || !e->cb_lp_host[slot].enable)
+        return fail(SV_EINVAL, "sv_cb_read_logprobs: slot %d records no log-probs (admit it through sv_cb_admit_logprobs with enable = 1)", slot);
+    if (first < 0 || count < 0) return fail(SV_EINVAL, "sv_cb_read_logprobs: columns [%d, %d) out of range", first, first + count);
+    HIPCHECK(hipSetDevice(e->cfg.device));
+    hipStream_t st = e->gen_stream;
+    int32_t steps = 0;
+    HIPCHECK(hipMemcpyAsync(&steps, &e->cb_slots[slot].step, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    if ((long long)first + count > steps)
+        return fail(SV_EINVAL, "sv_cb_read_logprobs: columns [%d, %d) of slot %d: it has emitted %d tokens", first, first + count, slot, steps);
+    if (count == 0) return 0;
+    const CbLogprobs& h = e->cb_lp_host[slot];
+    const size_t k = (size_t)h.k;
+    if (host_logprob) HIPCHECK(hipMemcpyAsync(host_logprob, h.logprob + first, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (host_rank) HIPCHECK(hipMemcpyAsync(host_rank, h.rank + first, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (host_ids && k) HIPCHECK(hipMemcpyAsync(host_ids, h.ids + (size_t)first * k, (size_t)count * k * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (host_lps && k) HIPCHECK(hipMemcpyAsync(host_lps, h.lps + (size_t)first * k, (size_t)count * k * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
 static int cb_release_locked(sv_engine* e, int slot, hipStream_t st) {
     // a slot released while still generating is stopped first (live -> 0, live counter adjusted on the host's view)
     CbSlot h;
@@ -508,6 +621,7 @@ static int cb_release_locked(sv_engine* e, int slot, hipStream_t st) {
     HIPCHECK(hipMemsetAsync(e->cb_slots + slot, 0, sizeof(CbSlot), st));
     HIPCHECK(hipMemsetAsync(e->positions + slot, 0, sizeof(int32_t), st));
     HIPCHECK(hipMemsetAsync(e->cur_tok + slot, 0, sizeof(int32_t), st));
+    SVCHECK(cb_lp_set(e, slot, nullptr, st));            // a free slot records nothing: the next holder starts from enable = 0
     fill_i32(e->block_table + (size_t)slot * e->pages_per_seq, e->trash_page, e->pages_per_seq, st);
     for (int pg : e->cb_pages[slot]) {
         // a shared prompt page (sv_cb_admit_shared) goes back when its last holder lets go; a private page at once

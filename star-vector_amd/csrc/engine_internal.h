@@ -197,7 +197,12 @@ struct sv_engine {
     CbBias* cb_bias = nullptr;                    // device [max_batch]: logit bias of vLLM-mode slots
     uint16_t* cb_counts = nullptr;                // device [max_batch][Vpad]: output-token counts of vLLM-mode slots
     int32_t *cb_map = nullptr, *cb_nlive = nullptr, *cb_events = nullptr, *cb_table_pf = nullptr;
-    int trash_page = 0;                           // what the block-table rows of free slots point at
+    // sv_cb_admit_logprobs: the per-slot record descriptors (device [max_batch]) and their host image (enable = 0 for every slot that is free or
+    // did not ask), over four engine-owned buffers of max_batch x max_seq_len columns (log-prob, rank: 4 B each; ids, log-probs: SV_TOPK_MAX x 4 B
+    // each).  All of it is allocated by the first admit that asks: cb_lp == nullptr on an engine that never did.
+    CbLogprobs* cb_lp = nullptr;
+    std::vector<CbLogprobs> cb_lp_host;
+    int trash_page = 0;                       // what the block-table rows of free slots point at
     std::unordered_map<int, std::pair<hipGraph_t, hipGraphExec_t>> cb_graphs;      // one captured step per row bucket
     // sv_generate: the captured decode step is kept while the next call has the same shape and sampling parameters
     std::string gen_graph_key;
@@ -290,6 +295,9 @@ int check_ready(sv_engine* e);
 // logit bias, its repetition bitmap row (seen_words words: the prompt ids in vLLM mode, cleared otherwise)
 int cb_check_request(const sv_cb_request& r, int V, int i, const char* who);
 void cb_fill_slot(const sv_cb_request& r, CbSlot& h, CbBias& bias, std::vector<uint32_t>& seen_row, int seen_words);
+// the log-prob requests of n requests (lps may be nullptr: nobody asks): SV_EINVAL + message for an entry with enable != 0 and k outside
+// 0..SV_TOPK_MAX, a source outside {0, 1}, or source 0 on a vLLM-semantics request -- host arithmetic, no device
+int cb_check_logprobs(const sv_cb_request* reqs, const sv_cb_logprobs* lps, int n, const char* who);
 // group admit (sv_cb_admit_shared): validation of (lens, group) and the page plan -- host arithmetic, stated by sv_debug_shared_plan for the CPU tests
 int shared_check_group(const char* who, const int32_t* lens, int n_prompts, const int32_t* group, int n);
 long long shared_page_plan(const int32_t* lens, int n_prompts, const int32_t* group, const int32_t* budgets, int n, int32_t* shared, int32_t* private_);

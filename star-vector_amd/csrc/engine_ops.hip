@@ -902,19 +902,27 @@ extern "C" int sv_op_argmax(const float* logits, int32_t B, int32_t V, int32_t l
 
 // the continuous-batching selection on caller-given rows: cb_step_kernel itself, one block per row (slot b = row b), on a copy of the
 // logits (vLLM-mode rows are rewritten in place) with each row's step, output counts and repetition set rebuilt from its history
-extern "C" int sv_op_cb_select(const float* logits, int32_t B, int32_t V, int32_t ld, const sv_cb_request* reqs,
-                               const int32_t* history, int32_t ld_hist, const int32_t* hist_len, int32_t* out, sv_stream stream) {
+// lps != nullptr (sv_op_cb_logprobs): row b records what lps[b] asks, one column, into out_logprob / out_rank [B] and out_ids / out_lps [B][ld_k]
+static int op_cb_select_impl(const char* who, const float* logits, int32_t B, int32_t V, int32_t ld, const sv_cb_request* reqs,
+                             const int32_t* history, int32_t ld_hist, const int32_t* hist_len, int32_t* out, const sv_cb_logprobs* lps,
+                             float* out_logprob, int32_t* out_rank, int32_t* out_ids, float* out_lps, int32_t ld_k, sv_stream stream) {
     if (!logits || !reqs || !hist_len || !out || B < 1 || B > 4096 || V < 1 || ld < V || (ld & 3) || ld_hist < 0)
-        return fail(SV_EINVAL, "sv_op_cb_select: bad argument");
+        return fail(SV_EINVAL, "%s: bad argument", who);
     int max_len = 0;
     for (int b = 0; b < B; ++b) {
         if (hist_len[b] < 0 || hist_len[b] > ld_hist || (hist_len[b] > 0 && !history))
-            return fail(SV_EINVAL, "sv_op_cb_select: row %d: history length %d (ld_hist %d)", b, hist_len[b], ld_hist);
+            return fail(SV_EINVAL, "%s: row %d: history length %d (ld_hist %d)", who, b, hist_len[b], ld_hist);
         for (int t = 0; t < hist_len[b]; ++t)
             if (history[(size_t)b * ld_hist + t] < 0 || history[(size_t)b * ld_hist + t] >= V)
-                return fail(SV_EINVAL, "sv_op_cb_select: row %d: history id outside the vocabulary", b);
+                return fail(SV_EINVAL, "%s: row %d: history id outside the vocabulary", who, b);
         max_len = std::max(max_len, (int)hist_len[b]);
-        SVCHECK(cb_check_request(reqs[b], V, b, "sv_op_cb_select"));
+        SVCHECK(cb_check_request(reqs[b], V, b, who));
+    }
+    if (lps) {
+        if (!out_logprob || !out_rank || !out_ids || !out_lps || ld_k < 1) return fail(SV_EINVAL, "%s: null output or ld_k < 1", who);
+        SVCHECK(cb_check_logprobs(reqs, lps, B, who));
+        for (int b = 0; b < B; ++b)
+            if (lps[b].enable && lps[b].k > ld_k) return fail(SV_EINVAL, "%s: row %d: k=%d exceeds ld_k=%d", who, b, lps[b].k, ld_k);
     }
     const int words = (ld + 31) / 32, ld_out = max_len + 1;
     std::vector<CbSlot> hs(B);
@@ -964,13 +972,60 @@ extern "C" int sv_op_cb_select(const float* logits, int32_t B, int32_t V, int32_
     a.cur_tok = dcur; a.positions = dpos; a.out_tokens = dout; a.ld_out = ld_out;
     a.seen = dseen; a.seen_words = words; a.n_live = dctr; a.events = dctr + 1; a.bad = dctr + 2;
     a.counts = dcounts; a.ld_counts = ld; a.bias = dbias;
+    // the record of row b: column hist_len[b] (its step) of buffers that hold ld_out columns per row, as the engine's hold out_ld
+    CbLogprobs* dlp = nullptr;
+    float *dlogprob = nullptr, *dlps = nullptr;
+    int32_t *drank = nullptr, *dids = nullptr;
+    if (lps) {
+        const size_t cols = (size_t)B * ld_out;
+        SVCHECK(tmp.get(&dlp, (size_t)B));
+        SVCHECK(tmp.get(&dlogprob, cols));
+        SVCHECK(tmp.get(&drank, cols));
+        SVCHECK(tmp.get(&dids, cols * SV_TOPK_MAX));
+        SVCHECK(tmp.get(&dlps, cols * SV_TOPK_MAX));
+        std::vector<CbLogprobs> hl(B);
+        for (int b = 0; b < B; ++b) {
+            CbLogprobs& h = hl[b];
+            h.enable = lps[b].enable ? 1 : 0; h.k = h.enable ? lps[b].k : 0; h.source = h.enable ? lps[b].source : 0; h.pad_ = 0;
+            h.logprob = dlogprob + (size_t)b * ld_out; h.rank = drank + (size_t)b * ld_out;
+            h.ids = dids + (size_t)b * ld_out * SV_TOPK_MAX; h.lps = dlps + (size_t)b * ld_out * SV_TOPK_MAX;
+        }
+        HIPCHECK(hipMemcpyAsync(dlp, hl.data(), hl.size() * sizeof(CbLogprobs), hipMemcpyHostToDevice, st));
+        HIPCHECK(hipStreamSynchronize(st));                 // `hl` is a host temporary
+        a.lp = dlp;
+    }
     launch_cb_step(a, B, st);
     HIPCHECK(hipGetLastError());
     std::vector<int32_t> ho((size_t)B * ld_out);
     HIPCHECK(hipMemcpyAsync(ho.data(), dout, ho.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
     for (int b = 0; b < B; ++b) out[b] = ho[(size_t)b * ld_out + hist_len[b]];
+    if (!lps) return 0;
+    for (int b = 0; b < B; ++b) {                           // a row that records nothing reads (NaN, 0) and an empty list
+        out_logprob[b] = std::nanf(""); out_rank[b] = 0;
+        for (int j = 0; j < ld_k; ++j) { out_ids[(size_t)b * ld_k + j] = -1; out_lps[(size_t)b * ld_k + j] = -INFINITY; }
+        if (!lps[b].enable) continue;
+        const size_t t = (size_t)hist_len[b], k = (size_t)lps[b].k;
+        HIPCHECK(hipMemcpy(out_logprob + b, dlogprob + (size_t)b * ld_out + t, sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(out_rank + b, drank + (size_t)b * ld_out + t, sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (!k) continue;
+        HIPCHECK(hipMemcpy(out_ids + (size_t)b * ld_k, dids + (size_t)b * ld_out * SV_TOPK_MAX + t * k, k * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(out_lps + (size_t)b * ld_k, dlps + (size_t)b * ld_out * SV_TOPK_MAX + t * k, k * sizeof(float), hipMemcpyDeviceToHost));
+    }
     return 0;
+}
+extern "C" int sv_op_cb_select(const float* logits, int32_t B, int32_t V, int32_t ld, const sv_cb_request* reqs,
+                               const int32_t* history, int32_t ld_hist, const int32_t* hist_len, int32_t* out, sv_stream stream) {
+    return op_cb_select_impl("sv_op_cb_select", logits, B, V, ld, reqs, history, ld_hist, hist_len, out, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
+                             stream);
+}
+// sv_op_cb_select plus one sv_cb_logprobs per row: the recording form of cb_step_kernel, the device code of sv_cb_admit_logprobs' slots
+extern "C" int sv_op_cb_logprobs(const float* logits, int32_t B, int32_t V, int32_t ld, const sv_cb_request* reqs, const sv_cb_logprobs* lps,
+                                 const int32_t* history, int32_t ld_hist, const int32_t* hist_len, int32_t* out, float* out_logprob,
+                                 int32_t* out_rank, int32_t* out_ids, float* out_lps, int32_t ld_k, sv_stream stream) {
+    if (!lps) return fail(SV_EINVAL, "sv_op_cb_logprobs: null lps");
+    return op_cb_select_impl("sv_op_cb_logprobs", logits, B, V, ld, reqs, history, ld_hist, hist_len, out, lps, out_logprob, out_rank, out_ids, out_lps,
+                             ld_k, stream);
 }
 
 // ban_tokens_kernel (processors.hip) on caller-given rows and histories: rewrites dev_logits in place

@@ -528,6 +528,19 @@ struct CbSlot {                  // device-resident, one per slot
     int32_t any[SV_CB_MAXANY];                   // stop_token_ids: any one of them ends the request (not a sequence)
 };
 struct CbBias { int32_t id[SV_CB_MAXBIAS]; float val[SV_CB_MAXBIAS]; };     // device-resident, one per slot
+// Per-slot log-prob record (device-resident, one per slot; the buffers are the engine's, allocated at the first admit that asks): at its step t a
+// recording slot writes the emitted token's log-prob and rank at [t] and the k best ids / log-probs of the step's distribution at [t][0..k), all
+// inside the selection's own block -- after the token is known, before the seen bitmap and the counts take it.  The definitions are those of
+// sv_generate_topk (TokenTopkArgs above): source 0 = log_softmax(raw / T) (HF slots only: a vLLM slot has rewritten its row by then), source 1 =
+// the row the selection saw with the sampler's kept set, removed ids at -inf.  The step graph holds the address of this array, never a buffer's.
+struct CbLogprobs {
+    int32_t enable;              // 0: the slot records nothing (and runs none of the code)
+    int32_t k;                   // 0..SV_TOPK_MAX_DEV list entries per step
+    int32_t source;              // 0 raw, 1 processed
+    int32_t pad_;
+    float* logprob; int32_t* rank;       // [budget]
+    int32_t* ids; float* lps;            // [budget][k]
+};
 struct CbStepArgs {
     const float* logits; int ld; int V;
     CbSlot* slots; const int32_t* slot_map;      // block b works for slot slot_map[b] (nullptr: b) on logits row b
@@ -539,6 +552,8 @@ struct CbStepArgs {
     // and the logit bias entries per slot.  The logits rows are rewritten in place for those slots.
     uint16_t* counts; int ld_counts;
     const CbBias* bias;
+    // per-slot log-prob records (sv_cb_admit_logprobs): nullptr = nobody records, the plain kernel runs -- the launch of every batch without them
+    const CbLogprobs* lp = nullptr;
 };
 void launch_cb_step(const CbStepArgs& a, int nblocks, hipStream_t st);
 

@@ -714,6 +714,71 @@ __device__ __forceinline__ void cb_vllm_process(const CbStepArgs& p, const CbSlo
     __syncthreads();
 }
 
+// rank of a column whose value is x_tok, without a list (k = 0): row_topk's count, 1 + #{ x(i) > x_tok }; 0 when x_tok is NaN or no column enters
+template <class F>
+__device__ __forceinline__ int cb_row_rank(F x, int V, float x_tok, float* red) {
+    float above = 0.f, any = 0.f;
+    for (int i = threadIdx.x; i < V; i += SP_THREADS) {
+        const float v = x(i);
+        above += v > x_tok ? 1.f : 0.f;
+        any = v > -INFINITY ? 1.f : any;
+    }
+    above = wp_block_sum(above, red);                                // exact: counts < 2^24
+    any = wp_block_max(any, red);
+    return (x_tok == x_tok && any > 0.f) ? 1 + (int)above : 0;
+}
+
+// The log-prob record of one recording slot at its step (CbLogprobs, kernels.h), by every thread of the slot's block: `tok` is the token the
+// selection took (block-uniform, inside the vocabulary), `row` the row as the selection saw it (a vLLM slot has rewritten it), srow / hold_eos the
+// selection's own processors; the seen bitmap and the counts have not taken `tok` yet.  The functors, the sums and the log-prob expressions are
+// token_topk_kernel's, so an HF slot's record equals its solo sv_generate_topk output bit for bit.  A vLLM slot is source 1 with the HF
+// processors off: log_softmax over its rewritten row, for a sampling slot divided by T under the top-k / top-p / min_p kept set.
+__device__ __forceinline__ void cb_record(const CbSlot& sl, const CbLogprobs& d, const float* row, int V, const uint32_t* srow, bool hold_eos,
+                                          int tok, float* red) {
+    const int k = d.k, t = sl.step;
+    const float T = sl.do_sample ? sl.temperature : 1.0f;
+    int32_t* ids = d.ids + (size_t)t * k;
+    float* lps = d.lps + (size_t)t * k;
+    const float qnan = __uint_as_float(0x7fc00000u);
+    float m, ls, ent, lp_tok, nolp = qnan;
+    int rk = 0, n = 0;
+    if (d.source == 0) {
+        ts_row_sums([&](int i) { return row[i] / T; }, V, red, m, ls, ent);
+        auto key = [&](int i) { return row[i]; };
+        lp_tok = (row[tok] / T - m) - ls;
+        nolp = (row[0] / T - m) - ls;
+        if (k > 0) n = row_topk(key, V, k, [&](float v) { return (v / T - m) - ls; }, red, true, row[tok], &rk);
+        else rk = cb_row_rank(key, V, row[tok], red);
+    } else {
+        const int eos = sl.eos;
+        const float pen = sl.penalty;
+        auto base = [&](int i) { return (hold_eos && i == eos) ? -INFINITY : rep_penalty(row[i], i, srow, pen); };
+        if (sl.do_sample) {
+            const float invT = 1.0f / sl.temperature;
+            WarpStats w = row_warp_stats<false, true>([&](int i) { return base(i) * invT; }, V, sl.top_k, sl.top_p, 1, red);
+            w.mthr = wp_minp_thr(w.mx, sl.min_p > 0.f ? __logf(sl.min_p) : -INFINITY);
+            auto kept = [&](int i) { const float s = base(i); return wp_keep(w, s * invT) ? s : -INFINITY; };      // the key: before the division by T
+            ts_row_sums([&](int i) { const float s = base(i); return wp_keep(w, s * invT) ? s / T : -INFINITY; }, V, red, m, ls, ent);
+            const float xt = kept(tok);
+            lp_tok = (xt / T - m) - ls;
+            if (k > 0) n = row_topk(kept, V, k, [&](float v) { return (v / T - m) - ls; }, red, true, xt, &rk);
+            else rk = cb_row_rank(kept, V, xt, red);
+        } else {
+            ts_row_sums(base, V, red, m, ls, ent);
+            const float xt = base(tok);
+            lp_tok = (xt - m) - ls;
+            if (k > 0) n = row_topk(base, V, k, [&](float v) { return (v - m) - ls; }, red, true, xt, &rk);
+            else rk = cb_row_rank(base, V, xt, red);
+        }
+    }
+    if (k > 0) topk_store(n, k, nolp, true, rk, ids, lps, d.rank + t);
+    else if (threadIdx.x == 0) d.rank[t] = rk;
+    if (threadIdx.x == 0) d.logprob[t] = lp_tok;
+}
+
+// LP = "some slot of this launch records log-probs" (CbStepArgs::lp): the record sits between the selection and the bookkeeping.  LP = false is
+// the kernel of every batch in which nobody asks -- none of the record's registers, scratch or LDS.
+template <bool LP>
 __global__ __launch_bounds__(SP_THREADS) void cb_step_kernel(CbStepArgs p) {
     __shared__ float red[SP_THREADS / 64];
     __shared__ float scan[SP_THREADS];
@@ -764,6 +829,10 @@ __global__ __launch_bounds__(SP_THREADS) void cb_step_kernel(CbStepArgs p) {
         __syncthreads();
         tok = result;
     }
+    if constexpr (LP) {
+        const CbLogprobs& d = p.lp[s];
+        if (d.enable) cb_record(sl, d, row, p.V, srow, hold_eos, (unsigned)tok >= (unsigned)p.V ? 0 : tok, red);       // block-uniform
+    }
     if (tid != 0) return;
     if ((unsigned)tok >= (unsigned)p.V) {               // no finite logit: never index the embedding table with the sentinel
         tok = 0;
@@ -796,7 +865,8 @@ __global__ __launch_bounds__(SP_THREADS) void cb_step_kernel(CbStepArgs p) {
     }
 }
 void launch_cb_step(const CbStepArgs& a, int nblocks, hipStream_t st) {
-    cb_step_kernel<<<nblocks, SP_THREADS, 0, st>>>(a);
+    if (a.lp) cb_step_kernel<true><<<nblocks, SP_THREADS, 0, st>>>(a);
+    else cb_step_kernel<false><<<nblocks, SP_THREADS, 0, st>>>(a);
 }
 
 }  // namespace sv

@@ -188,6 +188,7 @@ class HipEngine:
         # generate, a scoring forward.  The library serialises single calls with its own mutex; THIS lock keeps two host
         # threads from interleaving their call sequences (thread B's cb_reset would release thread A's slots).
         self.call_lock = threading.RLock()
+        self._cb_lp_k = {}                   # slot -> the k its current holder records with (cb_read_logprobs sizes its buffers by it)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -612,13 +613,19 @@ class HipEngine:
         return res
 
     # ---- continuous batching: one request per row of the engine's batch (include/starvector_hip.h, sv_cb_*) ----------------
-    def cb_admit(self, inputs_embeds: torch.Tensor, requests: Sequence[dict]) -> List[int]:
+    def cb_admit(self, inputs_embeds: torch.Tensor, requests: Sequence[dict], logprobs: Optional[Sequence] = None) -> List[int]:
         """Prompt pass of len(requests) new requests (inputs_embeds [n, S0, D] bf16, equal prompt length) into free slots while
         the live slots keep their KV cache; samples their first token.  Each request: dict(max_new_tokens, do_sample=False,
         temperature=1, top_p=1, top_k=0, seed=0, eos_token_id=0, pad_token_id=0, stop_ids=None, repetition_penalty=1,
         min_new_tokens=0), plus the vLLM-semantics keys (include/starvector_hip.h, ABI 9; they need semantics="vllm"):
         presence_penalty=0, frequency_penalty=0, min_p=0, prompt_ids=None, logit_bias=None ({id: bias}), stop_any_ids=None.
+        ``logprobs``: one entry per request, None or dict(k=0..32, source="raw" | "processed") -- the request records, for every token it
+        emits, the token's log-prob and rank and the k most likely ids (`cb_read_logprobs`; sv_cb_admit_logprobs).  None, or every entry
+        None: the call below, unchanged.
         Returns the slot ids.  Raises StarVectorBusy when slots or KV pages are short."""
+        if logprobs is not None and any(l is not None for l in logprobs):
+            seqs = list(inputs_embeds) if isinstance(inputs_embeds, (list, tuple)) else list(_need(inputs_embeds, torch.bfloat16, "inputs_embeds"))
+            return self.cb_admit_shared(seqs, None, list(range(len(seqs))), requests, logprobs=logprobs)
         if isinstance(inputs_embeds, (list, tuple)):
             # per-request embeddings [S_i, D] of different lengths: ONE ragged prompt pass for all of them (sv_cb_admit_ragged)
             x, lens_arr, lens = self._packed(inputs_embeds)
@@ -640,11 +647,12 @@ class HipEngine:
         del keep
         return list(slots)
 
-    def cb_admit_shared(self, embeds, lengths, group: Sequence[int], requests: Sequence[dict]) -> List[int]:
+    def cb_admit_shared(self, embeds, lengths, group: Sequence[int], requests: Sequence[dict], logprobs: Optional[Sequence] = None) -> List[int]:
         """Group admit (sv_cb_admit_shared): ``embeds`` a list of [S_u, D] prompts (``lengths`` None) or a packed tensor with ``lengths``;
         request i samples prompt ``group[i]`` with its own parameters (the dicts of ``cb_admit``).  ONE prompt pass over the prompts; the
         requests of a prompt share its full KV pages.  Prompts may come in any order here: they are renumbered in the order their first
-        request appears, as the C entry point wants them.  Returns the slot ids; raises StarVectorBusy when slots or pages are short."""
+        request appears, as the C entry point wants them.  ``logprobs``: as in `cb_admit`, one entry per request (every sample of a prompt may
+        ask for its own k).  Returns the slot ids; raises StarVectorBusy when slots or pages are short."""
         group = [int(g) for g in group]
         if len(group) != len(requests) or not group:
             raise ValueError("group / requests mismatch")
@@ -662,10 +670,30 @@ class HipEngine:
         n = len(group)
         arr, keep = cb_requests(requests)
         slots = (C.c_int32 * n)()
-        check(self.lib.sv_cb_admit_shared(self._h, _ptr(x), len(lens), lens_arr, n, (C.c_int32 * n)(*[rank[g] for g in group]), arr, slots,
-                                          _stream()), "sv_cb_admit_shared")
+        grp = (C.c_int32 * n)(*[rank[g] for g in group])
+        lps = cb_logprobs(requests, logprobs)
+        if lps is None:
+            check(self.lib.sv_cb_admit_shared(self._h, _ptr(x), len(lens), lens_arr, n, grp, arr, slots, _stream()), "sv_cb_admit_shared")
+        else:
+            check(self.lib.sv_cb_admit_logprobs(self._h, _ptr(x), len(lens), lens_arr, n, grp, arr, lps, slots, _stream()), "sv_cb_admit_logprobs")
+            for s_, l in zip(slots, lps):
+                self._cb_lp_k[int(s_)] = int(l.k) if l.enable else None
         del keep
         return list(slots)
+
+    def cb_read_logprobs(self, slot: int, first: int, count: int):
+        """Columns [first, first + count) of a recording slot's record (sv_cb_read_logprobs), host tensors: (token log-probs fp32 [count],
+        ranks int32 [count], ids int32 [count, k], log-probs fp32 [count, k]) with the slot's own k.  Only columns the slot has emitted
+        exist; a slot that records nothing raises ValueError."""
+        k = self._cb_lp_k.get(int(slot)) or 0
+        n = max(int(count), 1)
+        lp, rk = (C.c_float * n)(), (C.c_int32 * n)()
+        ids, lps = (C.c_int32 * max(n * k, 1))(), (C.c_float * max(n * k, 1))()
+        check(self.lib.sv_cb_read_logprobs(self._h, int(slot), int(first), int(count), lp, rk, ids, lps), "sv_cb_read_logprobs")
+        count = int(count)
+        return (torch.tensor(list(lp)[:count], dtype=torch.float32), torch.tensor(list(rk)[:count], dtype=torch.int32),
+                torch.tensor(list(ids)[:count * k], dtype=torch.int32).view(count, k),
+                torch.tensor(list(lps)[:count * k], dtype=torch.float32).view(count, k))
 
     def cb_step(self, n_steps: int = 8) -> int:
         """n_steps decode steps for every live slot (hipGraph replay); returns how many slots are still generating."""
@@ -880,6 +908,26 @@ def cb_requests(requests: Sequence[dict]):
         for k, t in enumerate(anys):
             a.stop_any_ids[k] = t
     return arr, keep
+
+
+def cb_logprobs(requests: Sequence[dict], logprobs: Optional[Sequence]):
+    """The sv_cb_logprobs array parallel to `cb_requests(requests)`: entry i from logprobs[i] = None | dict(k=, source=) (source 0 / "raw",
+    1 / "processed"; default: processed for a vLLM-semantics request, whose raw row no longer exists, raw otherwise).  None when nobody asks."""
+    if logprobs is None or all(l is None for l in logprobs):
+        return None
+    if len(logprobs) != len(requests):
+        raise ValueError("one logprobs entry per request")
+    arr = (_lib.SvCbLogprobs * len(requests))()
+    for i, (r, l) in enumerate(zip(requests, logprobs)):
+        if l is None:
+            continue
+        vl = r.get("semantics", "hf") in ("vllm", 1)
+        src = l.get("source")
+        src = ("processed" if vl else "raw") if src is None else src
+        if src not in ("raw", "processed", 0, 1):
+            raise ValueError(f"logprobs source must be 'raw' or 'processed', not {src!r}")
+        arr[i].enable, arr[i].k, arr[i].source = 1, int(l.get("k", 0) or 0), 1 if src in ("processed", 1) else 0
+    return arr
 
 
 def token_callback(on_tokens):
@@ -1280,6 +1328,41 @@ def op_cb_select(logits, requests: Sequence[dict], history=None):
     check(lib.sv_op_cb_select(_ptr(logits), B, V, ld, arr, hist, ld_hist, lens, out, _stream()), "sv_op_cb_select")
     del keep
     return torch.tensor(list(out), dtype=torch.int32)
+
+
+def op_cb_logprobs(logits, requests: Sequence[dict], logprobs: Sequence, history=None):
+    """`op_cb_select` plus one logprobs entry per row (None | dict(k=, source=), as `HipEngine.cb_admit` takes them): the recording form of
+    cb_step_kernel on caller-given rows.  Returns host tensors (tokens int32 [B], token log-probs fp32 [B], ranks int32 [B], ids int32 [B, K],
+    log-probs fp32 [B, K]) with K = the largest k asked (at least 1); a row's entries past its own k read (-1, -inf), a row that records nothing
+    reads (NaN, 0) and an empty list."""
+    lib = _lib.load()
+    logits = _need(logits, torch.float32, "logits")
+    B, V = logits.shape
+    ld = (V + 3) // 4 * 4
+    if ld != V:
+        pad = torch.full((B, ld), -float("inf"), dtype=torch.float32, device=logits.device)
+        pad[:, :V] = logits
+        logits = pad
+    history = [list(map(int, h)) for h in (history or [[]] * B)]
+    if len(history) != B or len(requests) != B or len(logprobs) != B:
+        raise ValueError("one request, one logprobs entry and one history per row")
+    ld_hist = max(1, max(len(h) for h in history))
+    hist = (C.c_int32 * (B * ld_hist))()
+    for b, h in enumerate(history):
+        for t, x in enumerate(h):
+            hist[b * ld_hist + t] = x
+    lens = (C.c_int32 * B)(*[len(h) for h in history])
+    arr, keep = cb_requests(requests)
+    lps = cb_logprobs(requests, logprobs)
+    if lps is None:
+        lps = (_lib.SvCbLogprobs * B)()
+    K = max([1] + [int(l.k) for l in lps if l.enable])
+    out, lp, rk = (C.c_int32 * B)(), (C.c_float * B)(), (C.c_int32 * B)()
+    ids, vals = (C.c_int32 * (B * K))(), (C.c_float * (B * K))()
+    check(lib.sv_op_cb_logprobs(_ptr(logits), B, V, ld, arr, lps, hist, ld_hist, lens, out, lp, rk, ids, vals, K, _stream()), "sv_op_cb_logprobs")
+    del keep
+    return (torch.tensor(list(out), dtype=torch.int32), torch.tensor(list(lp), dtype=torch.float32), torch.tensor(list(rk), dtype=torch.int32),
+            torch.tensor(list(ids), dtype=torch.int32).view(B, K), torch.tensor(list(vals), dtype=torch.float32).view(B, K))
 
 
 def op_ban_tokens(logits, history, no_repeat_ngram_size=0, bad_words_ids=None):

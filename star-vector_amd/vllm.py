@@ -13,7 +13,11 @@ positions carry no id here and count as none), and draws are distributional (vLL
 The n samples of an input (`SamplingParams.n`, the validator's `num_generations`) go in as ONE group: the image encoder and adapter
 run once per input, and the samples admitted together share one prompt pass and the prompt's full KV pages (`sv_cb_admit_shared`;
 `generate(..., share_prompt=False)` queues every sample on its own, the same tokens).
-Not built: logprobs, best_of > n, stop strings, beam search.
+Log-probs come through a keyword of `LLM.generate`: `generate(..., logprobs=k)` fills, for every request of the call,
+`CompletionOutput.logprobs` (one {token id: Logprob} dict per token: the k most likely ids with ranks 1..k plus the sampled token with its own
+rank) and `cumulative_logprob`, from the record the continuous batch keeps on device (`sv_cb_admit_logprobs`, source "processed": the
+distribution vLLM's Sampler reports).  `SamplingParams(logprobs=...)` itself still raises, as do the fields below.
+Not built: prompt_logprobs (image positions carry no token id), best_of > n, stop strings, beam search.
 """
 from __future__ import annotations
 
@@ -117,6 +121,14 @@ class SamplingParams:
 
 
 @dataclass
+class Logprob:
+    """vLLM's `Logprob`: one entry of a position's {token id: Logprob} dict."""
+    logprob: float
+    rank: Optional[int] = None
+    decoded_token: Optional[str] = None
+
+
+@dataclass
 class CompletionOutput:
     index: int
     text: str
@@ -209,6 +221,27 @@ def finish_of(token_ids: List[int], sp: SamplingParams, eos_token_id: int):
     return "length", None, len(token_ids)
 
 
+def completion_logprobs(token_ids: Sequence[int], token_logprobs, ranks, top_ids, top_logprobs, decode=None):
+    """vLLM's per-token dicts from a request's record (`batching.TokenLogprobs`; tensors or nested lists): position t maps the listed ids
+    (ids of -1 dropped) to Logprob(log-prob, rank = list position + 1) and holds the sampled token with its own log-prob and rank when the list
+    does not -- vLLM's own order: the sampled entry first, the list on top of it.  Returns (dicts, cumulative_logprob = the sum of the sampled
+    tokens' log-probs).  decode(id) -> the entry's decoded_token (None: left unset)."""
+    as_list = lambda x: x.tolist() if hasattr(x, "tolist") else list(x)
+    token_logprobs, ranks, top_ids, top_logprobs = map(as_list, (token_logprobs, ranks, top_ids, top_logprobs))
+    if not (len(token_ids) == len(token_logprobs) == len(ranks) == len(top_ids) == len(top_logprobs)):
+        raise ValueError("one record column per token")
+    text = (lambda t: None) if decode is None else decode
+    out, total = [], 0.0
+    for t, tok in enumerate(token_ids):
+        d = {int(tok): Logprob(float(token_logprobs[t]), int(ranks[t]), text(int(tok)))}
+        for j, (i, lp) in enumerate(zip(top_ids[t], top_logprobs[t])):
+            if int(i) >= 0:
+                d[int(i)] = Logprob(float(lp), j + 1, text(int(i)))
+        out.append(d)
+        total += float(token_logprobs[t])
+    return out, total
+
+
 class LLM:
     """vLLM's offline `LLM` over the HIP engine.  `model` is a LOCAL checkpoint directory in the reference's format, loaded by
     `StarVectorForCausalLM.from_pretrained` (hub names fail there: no download).  `max_num_seqs` = the engine's batch rows (the
@@ -291,14 +324,22 @@ class LLM:
                                  params=request_params(sp, seed, max_new, ids, eos, pad, vocab)))
         return jobs
 
-    def generate(self, inputs, sampling_params=None, use_tqdm: bool = True, share_prompt: bool = True, **kwargs) -> List[RequestOutput]:
+    def generate(self, inputs, sampling_params=None, use_tqdm: bool = True, share_prompt: bool = True, logprobs: Optional[int] = None,
+                 **kwargs) -> List[RequestOutput]:
         """One RequestOutput per input, in input order, each with its n CompletionOutputs.  Every (input, sample) pair is one
         request of the engine's continuous batch; more of them than `max_num_seqs` wait in its queue.  The samples of an input are
-        submitted as one group (one prompt pass for those admitted together); share_prompt=False submits each on its own."""
+        submitted as one group (one prompt pass for those admitted together); share_prompt=False submits each on its own.
+        logprobs = k (0..32), for every request of the call: `CompletionOutput.logprobs` (per token {id: Logprob} over the k most likely ids
+        and the sampled one) and `cumulative_logprob`, as vLLM's `SamplingParams.logprobs` would; None: neither, and the requests run as before."""
         if kwargs.get("lora_request") is not None or kwargs.get("prompt_adapter_request") is not None:
             raise NotImplementedError("LoRA / prompt adapters are not built")
+        if logprobs is not None and not 0 <= int(logprobs) <= 32:
+            raise ValueError(f"logprobs must lie in 0..32, got {logprobs}.")
         from .batching import ContinuousBatcher
         jobs = self.prepare(inputs, sampling_params)
+        if logprobs is not None:
+            for j in jobs:
+                j["params"] = dict(j["params"], logprobs=int(logprobs), logprob_source="processed")
         batcher = ContinuousBatcher(self.engine)
         try:
             handles = []
@@ -309,17 +350,21 @@ class LLM:
                 else:
                     handles += [batcher.submit(j["emb"], j["params"]) for j in grp]
             toks = [h.result().view(-1).tolist() for h in handles]
+            recs = [h.logprobs for h in handles]
         finally:
             batcher.close()
         eos = int(self.tokenizer.eos_token_id)
         outs: Dict[int, RequestOutput] = {}
-        for j, t in zip(jobs, toks):
+        for j, t, rec in zip(jobs, toks, recs):
             ro = outs.get(j["input"])
             if ro is None:
                 ro = outs[j["input"]] = RequestOutput(str(next(self._ids)), j["prompt"], list(j["prompt_ids"]))
             reason, stop_reason, n_text = finish_of(t, j["sp"], eos)
             text = self.tokenizer.decode(t[:n_text], skip_special_tokens=j["sp"].skip_special_tokens)
-            ro.outputs.append(CompletionOutput(j["index"], text, t, finish_reason=reason, stop_reason=stop_reason))
+            comp = CompletionOutput(j["index"], text, t, finish_reason=reason, stop_reason=stop_reason)
+            if rec is not None:
+                comp.logprobs, comp.cumulative_logprob = completion_logprobs(t, *rec, decode=lambda i: self.tokenizer.decode([i]))
+            ro.outputs.append(comp)
         return [outs[i] for i in sorted(outs)]
 
     def close(self) -> None:
