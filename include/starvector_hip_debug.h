@@ -4,7 +4,7 @@
  * Compiled into the same shared object as the product ABI (include/starvector_hip.h, included below), kept apart so that a
  * reference-side binding sees only what it has to bind:
  *   sv_op_*                 single operators, one per row of SURVEY.md section 8a: the parity tests put each HIP kernel next to the
- *                           oracle through them (tests/test_gpu_ops.py, tests/test_gpu_fp8.py)
+ *                           oracle through them (tests/test_gpu_ops.py, tests/test_gpu_row_kernels.py, tests/test_gpu_fp8.py)
  *   sv_debug_*_plan,
  *   sv_debug_resample_coeffs  host-side decisions of the library (dispatch, split-K, context splits, Pillow's tap tables), callable
  *                           WITHOUT a GPU: the CPU suite pins them
@@ -250,6 +250,50 @@ int  sv_op_attention_prefill(const void* qkv, int32_t q_off, int32_t k_off, int3
                              float scale, int32_t window, int32_t last_rows, sv_stream stream);
 int  sv_op_plane_layernorm(const void* x, const void* gamma, const void* beta, void* y, int32_t B,
                            int32_t QD, float eps, sv_stream stream);
+/* the same kernel writing plane b at y + b * y_batch_stride (elements, a multiple of 8, >= QD): the form the engine launches, straight
+ * into a [B][S0][D] prompt buffer.  Nothing between the planes is written. */
+int  sv_op_plane_layernorm_strided(const void* x, const void* gamma, const void* beta, void* y, int32_t B, int32_t QD, float eps,
+                                   int64_t y_batch_stride, sv_stream stream);
+/* ---- the row kernels that assemble the prompt and carry the decode residual stream, each on its own (tests/test_gpu_row_kernels.py).
+ * Device pointers, bf16 unless noted.  Shapes a kernel cannot do are SV_EINVAL; the sizes of the caller's buffers cannot be checked here:
+ * each line says what the call reads and writes.
+ *   sv_op_im2col            img [B][3][S][S] -> out [B * (S/P)^2][Kpad], column k = c*P*P + ky*P + kx, columns 3*P*P .. Kpad-1 zero (Kpad % 8 == 0)
+ *   sv_op_vit_embed_lnpre   CLIP token assembly + ln_pre: x [B][NP+1][Dv] = LN(bf16(cat(cls [Dv], patch_out [B*NP][ldp]) + pos [NP+1][Dv])); Dv % 8 == 0, Dv <= 2048
+ *   sv_op_dec_embed         h [B*S0][D] = bf16(emb + table[t]), t = row % S0, or dev_row_pos[row] (int32 [B*S0]) when given
+ *   sv_op_gather_rows       out row r = table[dev_ids[r]] (int64 [n]); per_seq > 0: row r goes to out + (r / per_seq) * seq_stride + (r % per_seq) * D
+ *   sv_op_gather_last_rows  out [B][D] = row b*S0 + S0-1 of h, or row first + len - 1 with descriptors dev_rag_seq int32 [B][2] = {first packed row, length}
+ *   sv_op_gather_tail_rows  out [B*n_keep][D] = the last n_keep rows of each of the B sequences of S0 rows of h
+ *   sv_op_gather_listed_rows  out [n][D] = x[dev_rows[i]] (int32 [n]), x rows ldx elements apart
+ *   sv_op_ragged_row_pos    dev_row_pos[first + j] = j for j < len, for each of the B descriptors {first packed row, length}
+ *   sv_op_ragged_positions  dev_positions[i] = length of descriptor i / rep, + delta, for i < B * rep
+ *   sv_op_token_batchnorm   nn.BatchNorm1d(Q) in eval over x [B][Q][D] (w, b, running_mean, running_var: [Q]); batch b at y + b * y_batch_stride
+ *   sv_op_layernorm_packed  sv_op_layernorm with y in fragment order ("xp", csrc/common.h): ceil(M/32) tiles of 32 x D, rows >= M not written; D % 16 == 0
+ *   sv_op_pack_rows / sv_op_unpack_rows   row-major [M][ldx] <-> fragment order, K % 16 == 0
+ *   sv_op_row_update_ln     the decode row update (csrc/kernels.h RowUpdateArgs, field for field).  ws == NULL: h = bf16(wte[tok] + wpe[pos]) (wpe NULL:
+ *                           wte[tok]); else h = bf16(h + bf16(sum over the splitk slabs ws [splitk][rows_ws][ldws] fp32, in slab order, + bias)).  h is row-major
+ *                           [M][ldh] or, ldh == 0, fragment order; xp_out = LN(h) in fragment order.  D % 16 == 0; 256 threads per row up to D = 2048,
+ *                           1024 above */
+int  sv_op_im2col(const void* img, void* out, int32_t B, int32_t img_size, int32_t patch, int32_t Kpad, sv_stream stream);
+int  sv_op_vit_embed_lnpre(const void* patch_out, int32_t ldp, const void* cls, const void* pos, const void* gamma, const void* beta,
+                           void* x, int32_t B, int32_t NP, int32_t Dv, float eps, sv_stream stream);
+int  sv_op_dec_embed(const void* emb, const void* table, void* h, int32_t B, int32_t S0, int32_t D, const int32_t* dev_row_pos,
+                     sv_stream stream);
+int  sv_op_gather_rows(const void* table, const int64_t* dev_ids, void* out, int32_t n, int32_t D, int32_t per_seq, int64_t seq_stride,
+                       sv_stream stream);
+int  sv_op_gather_last_rows(const void* h, void* out, int32_t B, int32_t S0, int32_t D, const int32_t* dev_rag_seq, sv_stream stream);
+int  sv_op_gather_tail_rows(const void* h, void* out, int32_t B, int32_t S0, int32_t n_keep, int32_t D, sv_stream stream);
+int  sv_op_gather_listed_rows(const void* x, int32_t ldx, const int32_t* dev_rows, int32_t n, void* out, int32_t D, sv_stream stream);
+int  sv_op_ragged_row_pos(const int32_t* dev_rag_seq, int32_t B, int32_t* dev_row_pos, sv_stream stream);
+int  sv_op_ragged_positions(int32_t* dev_positions, const int32_t* dev_rag_seq, int32_t B, int32_t rep, int32_t delta, sv_stream stream);
+int  sv_op_token_batchnorm(const void* x, const void* w, const void* b, const void* running_mean, const void* running_var, void* y,
+                           int32_t B, int32_t Q, int32_t D, float eps, int64_t y_batch_stride, sv_stream stream);
+int  sv_op_layernorm_packed(const void* x, const void* gamma, const void* beta, void* y_xp, int32_t M, int32_t D, float eps,
+                            sv_stream stream);
+int  sv_op_pack_rows(const void* x, int32_t ldx, void* xp, int32_t M, int32_t K, sv_stream stream);
+int  sv_op_unpack_rows(const void* xp, void* x, int32_t ldx, int32_t M, int32_t K, sv_stream stream);
+int  sv_op_row_update_ln(const float* ws, int32_t splitk, int32_t ldws, int32_t rows_ws, const void* bias, void* h, int32_t ldh,
+                         const void* wte, const void* wpe, const int32_t* dev_tokens, const int32_t* dev_positions, const void* gamma,
+                         const void* beta, float eps, void* xp_out, int32_t M, int32_t D, sv_stream stream);
 int  sv_op_argmax(const float* logits, int32_t B, int32_t V, int32_t ld, int32_t* out, sv_stream stream);
 int  sv_op_sample_top_p(const float* logits, int32_t B, int32_t V, int32_t ld, float temperature,
                         float top_p, uint64_t seed, int32_t step, int32_t* out, sv_stream stream);

@@ -219,6 +219,21 @@ DEBUG_PROTOTYPES = {
     "sv_op_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "sv_op_attention_prefill": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, C.POINTER(_I), _I, _I, _I, _I, _F, _I, _I, _P]),
     "sv_op_plane_layernorm": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
+    "sv_op_plane_layernorm_strided": (_I, [_P, _P, _P, _P, _I, _I, _F, C.c_int64, _P]),
+    "sv_op_im2col": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "sv_op_vit_embed_lnpre": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),
+    "sv_op_dec_embed": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
+    "sv_op_gather_rows": (_I, [_P, _P, _P, _I, _I, _I, C.c_int64, _P]),
+    "sv_op_gather_last_rows": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "sv_op_gather_tail_rows": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "sv_op_gather_listed_rows": (_I, [_P, _I, _P, _I, _P, _I, _P]),
+    "sv_op_ragged_row_pos": (_I, [_P, _I, _P, _P]),
+    "sv_op_ragged_positions": (_I, [_P, _P, _I, _I, _I, _P]),
+    "sv_op_token_batchnorm": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, C.c_int64, _P]),
+    "sv_op_layernorm_packed": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
+    "sv_op_pack_rows": (_I, [_P, _I, _P, _I, _I, _P]),
+    "sv_op_unpack_rows": (_I, [_P, _P, _I, _I, _I, _P]),
+    "sv_op_row_update_ln": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _P]),
     "sv_op_argmax": (_I, [_P, _I, _I, _I, _P, _P]),
     "sv_op_sample_top_p": (_I, [_P, _I, _I, _I, _F, _F, C.c_uint64, _I, _P, _P]),
     "sv_op_sample": (_I, [_P, _I, _I, _I, _F, _I, _F, C.c_uint64, _I, _P, _P]),

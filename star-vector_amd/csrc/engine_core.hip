@@ -391,6 +391,8 @@ extern "C" int sv_create(const sv_config* cfg, sv_engine** out) {
     if (nkv < 1 || c.n_head % nkv) return fail(SV_EINVAL, "n_head %% n_kv_head != 0");
     if (c.n_head / nkv > 16) return fail(SV_EINVAL, "decode attention supports <= 16 query heads per KV head");
     if (c.vit_width % 64 || c.hidden % 64 || c.n_inner % 64) return fail(SV_EINVAL, "dims must be multiples of 64");
+    // vit_embed_lnpre_kernel (CLIP token assembly + ln_pre) keeps a row in 4 chunks of 8 columns per lane: wider rows would be cut short
+    if (!v2 && c.vit_width > 2048) return fail(SV_EINVAL, "vit_width %d: the CLIP (v1) tower takes vit_width <= 2048", c.vit_width);
     if (v2 && (c.vit_mlp < 64 || c.vit_mlp % 64 || !(c.rope_theta > 1.f))) return fail(SV_EINVAL, "bad vit_mlp / rope_theta");
     if (c.weight_dtype != SV_WEIGHT_BF16 && c.weight_dtype != SV_WEIGHT_FP8_E4M3)
         return fail(SV_EINVAL, "weight_dtype must be SV_WEIGHT_BF16 (0) or SV_WEIGHT_FP8_E4M3 (1)");

@@ -404,8 +404,10 @@ __global__ void ragged_positions_kernel(int32_t* positions, const int32_t* rag_s
     if (i < n) positions[i] = rag_seq[2 * (i / rep) + 1] + delta;
 }
 void sveng::ragged_positions(sv_engine* e, int B, int rep, int delta, hipStream_t st) {
-    const int n = B * rep;
-    ragged_positions_kernel<<<(n + 63) / 64, 64, 0, st>>>(e->positions, e->d_rag, n, rep, delta);
+    launch_ragged_positions(e->positions, e->d_rag, B * rep, rep, delta, st);
+}
+void sveng::launch_ragged_positions(int32_t* positions, const int32_t* rag_seq, int n, int rep, int delta, hipStream_t st) {
+    ragged_positions_kernel<<<(n + 63) / 64, 64, 0, st>>>(positions, rag_seq, n, rep, delta);
 }
 
 int sveng::prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, const int32_t* lens, hipStream_t st, const int32_t* table) {

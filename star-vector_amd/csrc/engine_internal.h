@@ -315,6 +315,8 @@ int assign_pages_ragged(sv_engine* e, int B, const int32_t* lens, int extra, hip
 int prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, const int32_t* lens, hipStream_t st, const int32_t* table = nullptr);
 // positions[i] = lens[i / rep] + delta for i < B * rep, from the descriptors the last prefill_forward_ragged uploaded
 void ragged_positions(sv_engine* e, int B, int rep, int delta, hipStream_t st);
+// the launch behind it: positions[i] = rag_seq[2 * (i / rep) + 1] + delta for i < n, descriptors {first packed row, length}
+void launch_ragged_positions(int32_t* positions, const int32_t* rag_seq, int n, int rep, int delta, hipStream_t st);
 // engine_generate.hip
 void fork_args(sv_engine* e, int n_prompts, int n_rows, ForkArgs& f);      // the fork launch over e->fork_desc, the engine's block table, pool and logits
 // validation of a processor set against a vocabulary of V ids (V <= 0: the ids are only checked for >= 0) -- host arithmetic, no device -- and

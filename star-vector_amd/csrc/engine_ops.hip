@@ -888,6 +888,159 @@ extern "C" int sv_op_plane_layernorm(const void* x, const void* gamma, const voi
     return 0;
 }
 
+extern "C" int sv_op_plane_layernorm_strided(const void* x, const void* gamma, const void* beta, void* y, int32_t B, int32_t QD, float eps,
+                                             int64_t y_batch_stride, sv_stream stream) {
+    if (!x || !gamma || !beta || !y || B < 1 || QD < 8 || QD % 8) return fail(SV_EINVAL, "sv_op_plane_layernorm_strided: bad argument");
+    if (y_batch_stride < QD || y_batch_stride % 8)
+        return fail(SV_EINVAL, "sv_op_plane_layernorm_strided: y_batch_stride %lld must be a multiple of 8 and >= QD %d", (long long)y_batch_stride, QD);
+    launch_plane_layernorm((const bf16_t*)x, (const bf16_t*)gamma, (const bf16_t*)beta, (bf16_t*)y, B, QD, eps, (hipStream_t)stream,
+                           (size_t)y_batch_stride);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// ---- the row kernels that assemble the prompt and carry the decode residual stream, each on its own (tests/test_gpu_row_kernels.py).
+// The entry points check shapes only: the caller's buffers must hold what the comment in the header says each call addresses.
+static bool rows_ok(int64_t rows) { return rows >= 1 && rows <= (1 << 24); }
+
+extern "C" int sv_op_im2col(const void* img, void* out, int32_t B, int32_t img_size, int32_t patch, int32_t Kpad, sv_stream stream) {
+    if (!img || !out || B < 1 || patch < 1 || img_size < patch || img_size > 4096) return fail(SV_EINVAL, "sv_op_im2col: bad argument");
+    if (img_size % patch) return fail(SV_EINVAL, "sv_op_im2col: image_size %d %% patch %d != 0", img_size, patch);
+    if (Kpad % 8 || Kpad < 3 * patch * patch) return fail(SV_EINVAL, "sv_op_im2col: Kpad %d must be a multiple of 8 and >= 3 * patch^2 = %d", Kpad, 3 * patch * patch);
+    if (!rows_ok((int64_t)B * (img_size / patch) * (img_size / patch))) return fail(SV_EINVAL, "sv_op_im2col: too many patch rows");
+    launch_im2col((const bf16_t*)img, (bf16_t*)out, B, img_size, patch, Kpad, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sv_op_vit_embed_lnpre(const void* patch_out, int32_t ldp, const void* cls, const void* pos, const void* gamma, const void* beta,
+                                     void* x, int32_t B, int32_t NP, int32_t Dv, float eps, sv_stream stream) {
+    if (!patch_out || !cls || !pos || !gamma || !beta || !x || B < 1 || NP < 1) return fail(SV_EINVAL, "sv_op_vit_embed_lnpre: bad argument");
+    if (Dv < 8 || Dv % 8 || Dv > 2048) return fail(SV_EINVAL, "sv_op_vit_embed_lnpre: Dv %d must be a multiple of 8 in 8..2048 (4 chunks of 8 columns per lane)", Dv);
+    if (ldp < Dv || ldp % 8) return fail(SV_EINVAL, "sv_op_vit_embed_lnpre: ldp %d must be a multiple of 8 and >= Dv %d", ldp, Dv);
+    if (!rows_ok((int64_t)B * (NP + 1))) return fail(SV_EINVAL, "sv_op_vit_embed_lnpre: too many rows");
+    launch_vit_embed_lnpre((const bf16_t*)patch_out, ldp, (const bf16_t*)cls, (const bf16_t*)pos, (const bf16_t*)gamma, (const bf16_t*)beta,
+                           (bf16_t*)x, B, NP, Dv, eps, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sv_op_dec_embed(const void* emb, const void* table, void* h, int32_t B, int32_t S0, int32_t D, const int32_t* dev_row_pos,
+                               sv_stream stream) {
+    if (!emb || !table || !h || B < 1 || S0 < 1 || D < 8 || D % 8 || !rows_ok((int64_t)B * S0)) return fail(SV_EINVAL, "sv_op_dec_embed: bad argument (D %% 8 == 0)");
+    launch_dec_embed((const bf16_t*)emb, (const bf16_t*)table, (bf16_t*)h, B, S0, D, (hipStream_t)stream, dev_row_pos);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sv_op_gather_rows(const void* table, const int64_t* dev_ids, void* out, int32_t n, int32_t D, int32_t per_seq, int64_t seq_stride,
+                                 sv_stream stream) {
+    if (!table || !dev_ids || !out || !rows_ok(n) || D < 8 || D % 8 || per_seq < 0) return fail(SV_EINVAL, "sv_op_gather_rows: bad argument (D %% 8 == 0)");
+    if (per_seq > 0 && (n % per_seq || seq_stride < (int64_t)per_seq * D || seq_stride % 8))
+        return fail(SV_EINVAL, "sv_op_gather_rows: n %d must be a multiple of per_seq %d, seq_stride %lld a multiple of 8 and >= per_seq * D", n, per_seq,
+                    (long long)seq_stride);
+    launch_gather_rows((const bf16_t*)table, dev_ids, (bf16_t*)out, n, D, (hipStream_t)stream, per_seq, (size_t)(per_seq > 0 ? seq_stride : 0));
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sv_op_gather_last_rows(const void* h, void* out, int32_t B, int32_t S0, int32_t D, const int32_t* dev_rag_seq, sv_stream stream) {
+    if (!h || !out || B < 1 || D < 8 || D % 8 || (!dev_rag_seq && S0 < 1) || !rows_ok((int64_t)B * (S0 > 0 ? S0 : 1)))
+        return fail(SV_EINVAL, "sv_op_gather_last_rows: bad argument (D %% 8 == 0, S0 >= 1 without descriptors)");
+    launch_gather_last_rows((const bf16_t*)h, (bf16_t*)out, B, S0, D, (hipStream_t)stream, dev_rag_seq);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sv_op_gather_tail_rows(const void* h, void* out, int32_t B, int32_t S0, int32_t n_keep, int32_t D, sv_stream stream) {
+    if (!h || !out || B < 1 || S0 < 1 || n_keep < 1 || n_keep > S0 || D < 8 || D % 8 || !rows_ok((int64_t)B * S0))
+        return fail(SV_EINVAL, "sv_op_gather_tail_rows: bad argument (1 <= n_keep <= S0, D %% 8 == 0)");
+    launch_gather_tail_rows((const bf16_t*)h, (bf16_t*)out, B, S0, n_keep, D, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sv_op_gather_listed_rows(const void* x, int32_t ldx, const int32_t* dev_rows, int32_t n, void* out, int32_t D, sv_stream stream) {
+    if (!x || !dev_rows || !out || !rows_ok(n) || D < 8 || D % 8 || ldx < D || ldx % 8)
+        return fail(SV_EINVAL, "sv_op_gather_listed_rows: bad argument (D %% 8 == 0, ldx %% 8 == 0, ldx >= D)");
+    launch_gather_listed_rows((const bf16_t*)x, ldx, dev_rows, n, (bf16_t*)out, D, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sv_op_ragged_row_pos(const int32_t* dev_rag_seq, int32_t B, int32_t* dev_row_pos, sv_stream stream) {
+    if (!dev_rag_seq || !dev_row_pos || B < 1 || B > 65535) return fail(SV_EINVAL, "sv_op_ragged_row_pos: bad argument");
+    launch_ragged_row_pos(dev_rag_seq, B, dev_row_pos, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sv_op_ragged_positions(int32_t* dev_positions, const int32_t* dev_rag_seq, int32_t B, int32_t rep, int32_t delta, sv_stream stream) {
+    if (!dev_positions || !dev_rag_seq || B < 1 || rep < 1 || !rows_ok((int64_t)B * rep)) return fail(SV_EINVAL, "sv_op_ragged_positions: bad argument");
+    launch_ragged_positions(dev_positions, dev_rag_seq, B * rep, rep, delta, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sv_op_token_batchnorm(const void* x, const void* w, const void* b, const void* running_mean, const void* running_var, void* y,
+                                     int32_t B, int32_t Q, int32_t D, float eps, int64_t y_batch_stride, sv_stream stream) {
+    if (!x || !w || !b || !running_mean || !running_var || !y || B < 1 || Q < 1 || D < 8 || D % 8 || !rows_ok((int64_t)B * Q))
+        return fail(SV_EINVAL, "sv_op_token_batchnorm: bad argument (D %% 8 == 0)");
+    if (y_batch_stride < (int64_t)Q * D || y_batch_stride % 8)
+        return fail(SV_EINVAL, "sv_op_token_batchnorm: y_batch_stride %lld must be a multiple of 8 and >= Q * D", (long long)y_batch_stride);
+    launch_token_batchnorm((const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)b, (const bf16_t*)running_mean, (const bf16_t*)running_var,
+                           (bf16_t*)y, B, Q, D, eps, (hipStream_t)stream, (size_t)y_batch_stride);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sv_op_layernorm_packed(const void* x, const void* gamma, const void* beta, void* y_xp, int32_t M, int32_t D, float eps,
+                                      sv_stream stream) {
+    if (!x || !gamma || !beta || !y_xp || !rows_ok(M) || D < 16 || D % 16) return fail(SV_EINVAL, "sv_op_layernorm_packed: bad argument (D %% 16 == 0)");
+    launch_layernorm_rows_packed((const bf16_t*)x, D, (const bf16_t*)gamma, (const bf16_t*)beta, (bf16_t*)y_xp, M, D, eps, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sv_op_pack_rows(const void* x, int32_t ldx, void* xp, int32_t M, int32_t K, sv_stream stream) {
+    if (!x || !xp || !rows_ok(M) || K < 16 || K % 16 || ldx < K || ldx % 8 || (int64_t)M * (K / 8) > INT32_MAX)
+        return fail(SV_EINVAL, "sv_op_pack_rows: bad argument (K %% 16 == 0, ldx %% 8 == 0, ldx >= K)");
+    pack_rows((const bf16_t*)x, ldx, (bf16_t*)xp, M, K, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sv_op_unpack_rows(const void* xp, void* x, int32_t ldx, int32_t M, int32_t K, sv_stream stream) {
+    if (!x || !xp || !rows_ok(M) || K < 16 || K % 16 || ldx < K || ldx % 8 || (int64_t)M * (K / 8) > INT32_MAX)
+        return fail(SV_EINVAL, "sv_op_unpack_rows: bad argument (K %% 16 == 0, ldx %% 8 == 0, ldx >= K)");
+    unpack_rows((const bf16_t*)xp, (bf16_t*)x, ldx, M, K, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// row_update_ln_kernel<256> (D <= 2048) / <1024>: the fields of RowUpdateArgs; ws == NULL selects the embedding mode
+extern "C" int sv_op_row_update_ln(const float* ws, int32_t splitk, int32_t ldws, int32_t rows_ws, const void* bias, void* h, int32_t ldh,
+                                   const void* wte, const void* wpe, const int32_t* dev_tokens, const int32_t* dev_positions, const void* gamma,
+                                   const void* beta, float eps, void* xp_out, int32_t M, int32_t D, sv_stream stream) {
+    if (!h || !gamma || !beta || !xp_out || M < 1 || M > 65535) return fail(SV_EINVAL, "sv_op_row_update_ln: bad argument");
+    if (D < 16 || D % 16 || D > 12288) return fail(SV_EINVAL, "sv_op_row_update_ln: D %d must be a multiple of 16 in 16..12288 (the row sits in LDS as fp32: 48 KiB)", D);
+    if (ldh != 0 && (ldh < D || ldh % 8)) return fail(SV_EINVAL, "sv_op_row_update_ln: ldh %d must be 0 (fragment order) or a multiple of 8 and >= D", ldh);
+    if (ws) {
+        if (!bias || splitk < 1 || splitk > 64 || rows_ws < M || ldws < D || ldws % 4)
+            return fail(SV_EINVAL, "sv_op_row_update_ln: residual mode needs a bias, 1 <= splitk <= 64, rows_ws >= M, ldws %% 4 == 0 and ldws >= D");
+    } else if (!wte || !dev_tokens || !dev_positions) {
+        return fail(SV_EINVAL, "sv_op_row_update_ln: embedding mode needs wte, tokens and positions");
+    }
+    RowUpdateArgs a;
+    memset(&a, 0, sizeof(a));
+    a.ws = ws; a.splitk = splitk; a.ldws = ldws; a.rows_ws = rows_ws; a.bias = (const bf16_t*)bias; a.h = (bf16_t*)h; a.ldh = ldh;
+    a.wte = (const bf16_t*)wte; a.wpe = (const bf16_t*)wpe; a.tokens = dev_tokens; a.positions = dev_positions;
+    a.g = (const bf16_t*)gamma; a.b = (const bf16_t*)beta; a.eps = eps; a.xp_out = (bf16_t*)xp_out; a.M = M; a.D = D;
+    launch_row_update_ln(a, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
 extern "C" int sv_op_argmax(const float* logits, int32_t B, int32_t V, int32_t ld, int32_t* out, sv_stream stream) {
     if (!logits || !out || B < 1 || V < 1 || ld < V || ld % 4) return fail(SV_EINVAL, "sv_op_argmax: bad argument (ld must be a multiple of 4)");
     TmpBufs tmp;

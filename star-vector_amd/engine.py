@@ -1227,13 +1227,270 @@ def op_attention_prefill(qkv, q_off, k_off, v_off, n_head, n_kv_head, head_dim, 
     return out
 
 
-def op_plane_layernorm(x, gamma, beta, eps=1e-5):
+def op_plane_layernorm(x, gamma, beta, eps=1e-5, y_batch_stride=None, out=None):
+    """y_batch_stride (elements): plane b goes to out.flatten()[b * y_batch_stride:] -- the form the engine launches; `out` may be handed in pre-filled."""
     lib = _lib.load()
     x = _need(x, torch.bfloat16, "x"); B = x.shape[0]; QD = x[0].numel()
-    y = torch.empty_like(x)
-    check(lib.sv_op_plane_layernorm(_ptr(x), _ptr(_need(gamma, torch.bfloat16, "gamma")),
-                                    _ptr(_need(beta, torch.bfloat16, "beta")), _ptr(y), B, QD, eps, _stream()))
+    g, b = _need(gamma, torch.bfloat16, "gamma"), _need(beta, torch.bfloat16, "beta")
+    _op_size(g, QD, "gamma"); _op_size(b, QD, "beta")
+    if y_batch_stride is None:
+        y = torch.empty_like(x) if out is None else _op_out(out, torch.bfloat16, B * QD)
+        check(lib.sv_op_plane_layernorm(_ptr(x), _ptr(g), _ptr(b), _ptr(y), B, QD, eps, _stream()))
+        return y
+    stride = int(y_batch_stride)
+    need = (B - 1) * stride + QD
+    y = torch.empty(need, dtype=torch.bfloat16, device=x.device) if out is None else _op_out(out, torch.bfloat16, need)
+    check(lib.sv_op_plane_layernorm_strided(_ptr(x), _ptr(g), _ptr(b), _ptr(y), B, QD, eps, stride, _stream()), "sv_op_plane_layernorm_strided")
     return y
+
+
+# ---- the row kernels of the prompt side and the decode residual stream (sv_op_* of the same names).  The C entry points see pointers
+# only, so every wrapper checks here that the tensors hold what the kernel will address; `out` may be handed in pre-filled, so that a
+# test can see what a kernel leaves alone.
+def _op_out(out, dtype, need: int):
+    if not out.is_cuda or out.dtype != dtype or not out.is_contiguous() or out.numel() < need:
+        raise ValueError(f"out must be a contiguous {dtype} CUDA(HIP) tensor of at least {need} elements, got {tuple(out.shape)} {out.dtype}")
+    return out
+
+
+def _op_size(t, need: int, what: str):
+    if t.numel() < need:
+        raise ValueError(f"{what} holds {t.numel()} elements, the call addresses {need}")
+    return t
+
+
+def _op_index(t, dtype, n: int, lo: int, hi: int, what: str):
+    """An index tensor of the device: `n` entries of `dtype`, every one in [lo, hi)."""
+    t = _need(t, dtype, what)
+    if t.numel() != n:
+        raise ValueError(f"{what} must hold {n} entries, got {t.numel()}")
+    if n and (int(t.min()) < lo or int(t.max()) >= hi):
+        raise ValueError(f"{what} has an entry outside [{lo}, {hi})")
+    return t
+
+
+def xp_elems(M: int, K: int) -> int:
+    """Elements of a fragment-order ("xp", csrc/common.h) buffer of M rows of K columns: whole tiles of 32 rows."""
+    return (int(M) + 31) // 32 * 32 * int(K)
+
+
+def op_im2col(img, patch: int, Kpad: int, out=None):
+    lib = _lib.load()
+    img = _need(img, torch.bfloat16, "img")
+    B, Cc, S, S2 = img.shape
+    if Cc != 3 or S != S2 or S % patch:
+        raise ValueError("img must be [B, 3, S, S] with S a multiple of patch")
+    rows = B * (S // patch) ** 2
+    out = torch.empty(rows, Kpad, dtype=torch.bfloat16, device=img.device) if out is None else _op_out(out, torch.bfloat16, rows * Kpad)
+    check(lib.sv_op_im2col(_ptr(img), _ptr(out), B, S, int(patch), int(Kpad), _stream()), "sv_op_im2col")
+    return out
+
+
+def op_vit_embed_lnpre(patch_out, cls, pos, gamma, beta, B: int, NP: int, Dv: int, eps=1e-5, out=None):
+    """patch_out: [B * NP, ldp] with ldp >= Dv (the row stride is taken from its shape)."""
+    lib = _lib.load()
+    t = lambda v, n: _need(v, torch.bfloat16, n)
+    patch_out, cls, pos, gamma, beta = t(patch_out, "patch_out"), t(cls, "cls"), t(pos, "pos"), t(gamma, "gamma"), t(beta, "beta")
+    if patch_out.dim() != 2 or patch_out.shape[0] < B * NP:
+        raise ValueError(f"patch_out must be [>= {B * NP}, ldp]")
+    ldp = patch_out.shape[1]
+    _op_size(cls, Dv, "cls"); _op_size(pos, (NP + 1) * Dv, "pos"); _op_size(gamma, Dv, "gamma"); _op_size(beta, Dv, "beta")
+    need = B * (NP + 1) * Dv
+    out = torch.empty(B, NP + 1, Dv, dtype=torch.bfloat16, device=patch_out.device) if out is None else _op_out(out, torch.bfloat16, need)
+    check(lib.sv_op_vit_embed_lnpre(_ptr(patch_out), ldp, _ptr(cls), _ptr(pos), _ptr(gamma), _ptr(beta), _ptr(out), B, NP, Dv, float(eps),
+                                    _stream()), "sv_op_vit_embed_lnpre")
+    return out
+
+
+def op_dec_embed(emb, table, row_pos=None, out=None):
+    """emb [B, S0, D] + table[t]: t = the row's index inside its sequence, or row_pos[row] (int32 [B * S0])."""
+    lib = _lib.load()
+    emb, table = _need(emb, torch.bfloat16, "emb"), _need(table, torch.bfloat16, "table")
+    B, S0, D = emb.shape
+    if table.dim() != 2 or table.shape[1] != D:
+        raise ValueError("table must be [positions, D]")
+    if row_pos is not None:
+        row_pos = _op_index(row_pos, torch.int32, B * S0, 0, table.shape[0], "row_pos")
+    elif table.shape[0] < S0:
+        raise ValueError(f"table holds {table.shape[0]} positions, S0 is {S0}")
+    out = torch.empty_like(emb) if out is None else _op_out(out, torch.bfloat16, emb.numel())
+    check(lib.sv_op_dec_embed(_ptr(emb), _ptr(table), _ptr(out), B, S0, D, _ptr(row_pos), _stream()), "sv_op_dec_embed")
+    return out
+
+
+def op_gather_rows(table, ids, per_seq: int = 0, seq_stride: int = 0, out=None):
+    """out row r = table[ids[r]]; per_seq > 0: row r is written at element (r // per_seq) * seq_stride + (r % per_seq) * D of `out`."""
+    lib = _lib.load()
+    table = _need(table, torch.bfloat16, "table")
+    V, D = table.shape
+    n = ids.numel()
+    ids = _op_index(ids, torch.int64, n, 0, V, "ids")
+    if per_seq:
+        if per_seq < 0 or n % per_seq or seq_stride < per_seq * D:
+            raise ValueError("n must be a multiple of per_seq and seq_stride >= per_seq * D")
+        need = (n // per_seq - 1) * int(seq_stride) + per_seq * D
+    else:
+        need = n * D
+    out = torch.empty(need, dtype=torch.bfloat16, device=table.device) if out is None else _op_out(out, torch.bfloat16, need)
+    check(lib.sv_op_gather_rows(_ptr(table), _ptr(ids), _ptr(out), n, D, int(per_seq), int(seq_stride), _stream()), "sv_op_gather_rows")
+    return out
+
+
+def _rag_seq(lens, device):
+    """Descriptors {first packed row, length} of sequences packed back to back."""
+    lens = [int(x) for x in lens]
+    if not lens or min(lens) < 1:
+        raise ValueError("lens must be a non-empty list of lengths >= 1")
+    first, desc = 0, []
+    for n in lens:
+        desc += [first, n]
+        first += n
+    return torch.tensor(desc, dtype=torch.int32, device=device), first
+
+
+def op_gather_last_rows(h, B: Optional[int] = None, S0: Optional[int] = None, lens=None, out=None):
+    """h [rows, D]: the last row of each of B sequences of S0 rows, or (lens) of each sequence of the packed ragged form."""
+    lib = _lib.load()
+    h = _need(h, torch.bfloat16, "h")
+    rows, D = h.shape
+    if lens is not None:
+        desc, total = _rag_seq(lens, h.device)
+        B, S0 = len(lens), 0
+    else:
+        desc, total = None, int(B) * int(S0)
+    if total > rows:
+        raise ValueError(f"h holds {rows} rows, the call addresses {total}")
+    out = torch.empty(B, D, dtype=torch.bfloat16, device=h.device) if out is None else _op_out(out, torch.bfloat16, B * D)
+    check(lib.sv_op_gather_last_rows(_ptr(h), _ptr(out), int(B), int(S0), D, _ptr(desc), _stream()), "sv_op_gather_last_rows")
+    torch.cuda.current_stream().synchronize()                  # `desc` is a temporary
+    return out
+
+
+def op_gather_tail_rows(h, n_keep: int, out=None):
+    lib = _lib.load()
+    h = _need(h, torch.bfloat16, "h")
+    B, S0, D = h.shape
+    if not 1 <= n_keep <= S0:
+        raise ValueError("1 <= n_keep <= S0")
+    out = torch.empty(B * n_keep, D, dtype=torch.bfloat16, device=h.device) if out is None else _op_out(out, torch.bfloat16, B * n_keep * D)
+    check(lib.sv_op_gather_tail_rows(_ptr(h), _ptr(out), B, S0, int(n_keep), D, _stream()), "sv_op_gather_tail_rows")
+    return out
+
+
+def op_gather_listed_rows(x, rows, D: int, out=None):
+    """x [R, ldx] (ldx >= D): out[i] = x[rows[i], :D]."""
+    lib = _lib.load()
+    x = _need(x, torch.bfloat16, "x")
+    R, ldx = x.shape
+    if D > ldx:
+        raise ValueError("D > ldx")
+    n = rows.numel()
+    rows = _op_index(rows, torch.int32, n, 0, R, "rows")
+    out = torch.empty(n, D, dtype=torch.bfloat16, device=x.device) if out is None else _op_out(out, torch.bfloat16, n * D)
+    check(lib.sv_op_gather_listed_rows(_ptr(x), ldx, _ptr(rows), n, _ptr(out), int(D), _stream()), "sv_op_gather_listed_rows")
+    return out
+
+
+def op_ragged_row_pos(lens, out):
+    """out (int32, at least sum(lens) entries, handed in by the caller): out[first_b + j] = j."""
+    lib = _lib.load()
+    desc, total = _rag_seq(lens, out.device)
+    _op_out(out, torch.int32, total)
+    check(lib.sv_op_ragged_row_pos(_ptr(desc), len(lens), _ptr(out), _stream()), "sv_op_ragged_row_pos")
+    torch.cuda.current_stream().synchronize()
+    return out
+
+
+def op_ragged_positions(lens, rep: int, delta: int, out):
+    """out (int32, at least len(lens) * rep entries): out[i] = lens[i // rep] + delta."""
+    lib = _lib.load()
+    desc, _ = _rag_seq(lens, out.device)
+    if rep < 1:
+        raise ValueError("rep >= 1")
+    _op_out(out, torch.int32, len(lens) * int(rep))
+    check(lib.sv_op_ragged_positions(_ptr(out), _ptr(desc), len(lens), int(rep), int(delta), _stream()), "sv_op_ragged_positions")
+    torch.cuda.current_stream().synchronize()
+    return out
+
+
+def op_token_batchnorm(x, w, b, running_mean, running_var, eps=1e-5, y_batch_stride=None, out=None):
+    lib = _lib.load()
+    t = lambda v, n: _need(v, torch.bfloat16, n)
+    x, w, b, rm, rv = t(x, "x"), t(w, "w"), t(b, "b"), t(running_mean, "running_mean"), t(running_var, "running_var")
+    B, Q, D = x.shape
+    for v, n in ((w, "w"), (b, "b"), (rm, "running_mean"), (rv, "running_var")):
+        _op_size(v, Q, n)
+    stride = Q * D if y_batch_stride is None else int(y_batch_stride)
+    need = (B - 1) * stride + Q * D
+    out = torch.empty(need, dtype=torch.bfloat16, device=x.device) if out is None else _op_out(out, torch.bfloat16, need)
+    check(lib.sv_op_token_batchnorm(_ptr(x), _ptr(w), _ptr(b), _ptr(rm), _ptr(rv), _ptr(out), B, Q, D, float(eps), stride, _stream()),
+          "sv_op_token_batchnorm")
+    return out
+
+
+def op_layernorm_packed(x, gamma, beta, eps=1e-5, out=None):
+    """LayerNorm of x [M, D] written in fragment order: a flat buffer of xp_elems(M, D) elements (rows >= M are not written)."""
+    lib = _lib.load()
+    x = _need(x, torch.bfloat16, "x"); M, D = x.shape
+    g, b = _need(gamma, torch.bfloat16, "gamma"), _need(beta, torch.bfloat16, "beta")
+    _op_size(g, D, "gamma"); _op_size(b, D, "beta")
+    need = xp_elems(M, D)
+    out = torch.empty(need, dtype=torch.bfloat16, device=x.device) if out is None else _op_out(out, torch.bfloat16, need)
+    check(lib.sv_op_layernorm_packed(_ptr(x), _ptr(g), _ptr(b), _ptr(out), M, D, float(eps), _stream()), "sv_op_layernorm_packed")
+    return out
+
+
+def op_pack_rows(x, out=None):
+    """x [M, K] row-major -> fragment order (flat, xp_elems(M, K) elements)."""
+    lib = _lib.load()
+    x = _need(x, torch.bfloat16, "x"); M, K = x.shape
+    need = xp_elems(M, K)
+    out = torch.empty(need, dtype=torch.bfloat16, device=x.device) if out is None else _op_out(out, torch.bfloat16, need)
+    check(lib.sv_op_pack_rows(_ptr(x), K, _ptr(out), M, K, _stream()), "sv_op_pack_rows")
+    return out
+
+
+def op_unpack_rows(xp, M: int, K: int, out=None):
+    lib = _lib.load()
+    xp = _need(xp, torch.bfloat16, "xp")
+    _op_size(xp, xp_elems(M, K), "xp")
+    out = torch.empty(M, K, dtype=torch.bfloat16, device=xp.device) if out is None else _op_out(out, torch.bfloat16, M * K)
+    check(lib.sv_op_unpack_rows(_ptr(xp), _ptr(out), K, int(M), int(K), _stream()), "sv_op_unpack_rows")
+    return out
+
+
+def op_row_update_ln(h, gamma, beta, xp_out, M: int, D: int, eps=1e-5, *, ws=None, bias=None, ldh: int = 0,
+                     wte=None, wpe=None, tokens=None, positions=None):
+    """The decode row update on its own (csrc/kernels.h RowUpdateArgs).  `h` (in / out) is row-major with row stride ldh, or, ldh == 0,
+    fragment order; `xp_out` receives LayerNorm(h) in fragment order; both are the caller's buffers.  Residual mode: ws fp32
+    [splitk, rows_ws, ldws] and bias [D].  Embedding mode (ws None): wte [V, D], optional wpe [P, D], tokens / positions int32 [M]."""
+    lib = _lib.load()
+    t = lambda v, n: _need(v, torch.bfloat16, n)
+    h, gamma, beta, xp_out = t(h, "h"), t(gamma, "gamma"), t(beta, "beta"), t(xp_out, "xp_out")
+    M, D, ldh = int(M), int(D), int(ldh)
+    _op_size(gamma, D, "gamma"); _op_size(beta, D, "beta"); _op_size(xp_out, xp_elems(M, D), "xp_out")
+    _op_size(h, (M - 1) * ldh + D if ldh else xp_elems(M, D), "h")
+    if ws is not None:
+        ws = _need(ws, torch.float32, "ws")
+        if ws.dim() != 3 or ws.shape[1] < M or ws.shape[2] < D or bias is None:
+            raise ValueError("residual mode: ws must be [splitk, rows_ws >= M, ldws >= D] and bias given")
+        splitk, rows_ws, ldws_ = ws.shape
+        bias = _op_size(t(bias, "bias"), D, "bias")
+        check(lib.sv_op_row_update_ln(_ptr(ws), splitk, ldws_, rows_ws, _ptr(bias), _ptr(h), ldh, None, None, None, None, _ptr(gamma), _ptr(beta),
+                                      float(eps), _ptr(xp_out), M, D, _stream()), "sv_op_row_update_ln")
+        return h, xp_out
+    wte = t(wte, "wte")
+    if wte.dim() != 2 or wte.shape[1] != D:
+        raise ValueError("wte must be [V, D]")
+    tokens = _op_index(tokens, torch.int32, M, 0, wte.shape[0], "tokens")
+    if wpe is not None:
+        wpe = t(wpe, "wpe")
+        if wpe.dim() != 2 or wpe.shape[1] != D:
+            raise ValueError("wpe must be [P, D]")
+    positions = _op_index(positions, torch.int32, M, 0, wpe.shape[0] if wpe is not None else 1 << 30, "positions")
+    check(lib.sv_op_row_update_ln(None, 0, 0, 0, None, _ptr(h), ldh, _ptr(wte), _ptr(wpe), _ptr(tokens), _ptr(positions), _ptr(gamma), _ptr(beta),
+                                  float(eps), _ptr(xp_out), M, D, _stream()), "sv_op_row_update_ln")
+    return h, xp_out
 
 
 def op_argmax(logits):

@@ -168,6 +168,29 @@ def test_argument_validation_precedes_any_device_work(lib):
         lib.sv_config_default_1b(C.byref(c))
         setattr(c, field, val)
         assert lib.sv_create(C.byref(c), C.byref(h)) == -22 and msg in err(), (field, err())
+    # the CLIP tower's token assembly keeps a row in 4 chunks of 8 columns per lane: wider rows would be cut short without a word
+    c = SvConfig()
+    lib.sv_config_default_1b(C.byref(c))
+    c.vit_width, c.vit_heads = 4096, 32
+    assert lib.sv_create(C.byref(c), C.byref(h)) == -22 and "vit_width <= 2048" in err(), err()
+    # ... and so do the single-operator entry points of the row kernels (shapes a kernel cannot do; no pointer is dereferenced)
+    assert lib.sv_op_vit_embed_lnpre(p, 2056, p, p, p, p, p, 1, 1, 2056, 1e-5, None) == -22 and "2048" in err()
+    assert lib.sv_op_vit_embed_lnpre(p, 64, p, p, p, p, p, 1, 1, 128, 1e-5, None) == -22 and "ldp" in err()
+    assert lib.sv_op_im2col(p, p, 1, 28, 14, 584, None) == -22 and "Kpad" in err()
+    assert lib.sv_op_im2col(p, p, 1, 30, 14, 640, None) == -22
+    assert lib.sv_op_dec_embed(p, p, p, 1, 4, 60, None, None) == -22
+    assert lib.sv_op_gather_rows(p, p, p, 6, 64, 2, 64, None) == -22 and "seq_stride" in err()
+    assert lib.sv_op_gather_last_rows(p, p, 2, 0, 64, None, None) == -22
+    assert lib.sv_op_gather_tail_rows(p, p, 2, 4, 5, 64, None) == -22
+    assert lib.sv_op_gather_listed_rows(p, 56, p, 3, p, 64, None) == -22
+    assert lib.sv_op_ragged_row_pos(None, 1, p, None) == -22 and lib.sv_op_ragged_positions(p, p, 1, 0, 0, None) == -22
+    assert lib.sv_op_token_batchnorm(p, p, p, p, p, p, 1, 4, 64, 1e-5, 128, None) == -22 and "y_batch_stride" in err()
+    assert lib.sv_op_plane_layernorm_strided(p, p, p, p, 2, 256, 1e-5, 128, None) == -22 and "y_batch_stride" in err()
+    assert lib.sv_op_layernorm_packed(p, p, p, p, 4, 40, 1e-5, None) == -22
+    assert lib.sv_op_pack_rows(p, 40, p, 4, 40, None) == -22 and lib.sv_op_unpack_rows(p, p, 64, 4, 72, None) == -22
+    assert lib.sv_op_row_update_ln(p, 4, 64, 32, p, p, 64, None, None, None, None, p, p, 1e-5, p, 4, 72, None) == -22 and "multiple of 16" in err()
+    assert lib.sv_op_row_update_ln(p, 4, 64, 32, p, p, 64, None, None, None, None, p, p, 1e-5, p, 33, 64, None) == -22 and "rows_ws" in err()
+    assert lib.sv_op_row_update_ln(None, 0, 0, 0, None, p, 0, p, None, None, p, p, p, 1e-5, p, 4, 64, None) == -22 and "tokens" in err()
     # the measurement / A-B surfaces validate before they touch the device as well
     assert lib.sv_debug_set_gemm_form(3) == -22 and lib.sv_debug_set_gemm_form(-2) == -22
     assert lib.sv_debug_set_gemm_form(1) == 0 and lib.sv_debug_set_gemm_form(-1) == 0

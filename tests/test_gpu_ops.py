@@ -1,5 +1,8 @@
-"""-m gpu: every kernel of the path, called through the C ABI (sv_op_*), against a plain float32
-restatement of the same operator on the same bf16-exact inputs.
+"""-m gpu: the GEMMs, the prompt-pass attention, the lm_head, the samplers, the pre-processing and the folded decode layer,
+called through the C ABI (sv_op_*), against a plain float32 restatement of the same operator on the same bf16-exact inputs.
+Which test holds which kernel of csrc/ to a reference -- the row kernels, the decode attention, the beam scorer and the
+log-prob kernels have files of their own -- is the table of tests/test_kernel_coverage_host.py, which fails for a kernel
+that no test names.
 
 Tolerances (stated, floating point): bf16 outputs must sit within ONE bf16 rounding of the float32
 result -> |err| <= 2^-8 * max|ref| (plus the second rounding where the reference rounds an
