@@ -241,9 +241,24 @@ int  sv_prefill(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, flo
  *                        shared prompt pages and the cached length are per request).  outs may be NULL.
  *   sv_cb_admit_ragged   sv_cb_admit for n requests of prompt lengths host_lens[i] in ONE prompt pass; SV_EBUSY (nothing admitted) when
  *                        slots or KV pages are short.
- * SV_EINVAL before any device work for null pointers, B out of range, a length < 1 or > max_seq_len, max(len) + max_new > max_seq_len. */
+ *   sv_forward_logprobs_ragged   sv_forward_topk (below) over sequences of different lengths, each with its own number of kept rows: host_keep
+ *                        int32 [B] on the host, host_keep[b] in 1 .. host_lens[b] = the LAST rows of sequence b that are scored.  dev_targets and
+ *                        every output are packed [sum(host_keep)], the lists [sum(host_keep)][k]: each sequence's kept rows are contiguous, in
+ *                        sequence order.  Target -100, temperature, the outputs that may be NULL, k (0 = no lists), the order / ties / (-1, -inf)
+ *                        tail / rank of the lists and the two failures (a target outside the vocabulary: SV_EINVAL; a row without a finite
+ *                        logit: SV_EHIP -- the message names the sequence and the kept position inside it) are those of sv_forward_topk.  No
+ *                        padding row goes through a layer or the lm_head.  Blocks until the pass has finished; leaves the engine as
+ *                        sv_prefill_ragged does (sv_decode_step continues every row at its own position).
+ *                        Contract: for every sequence b every output of its kept rows is BIT-IDENTICAL to sv_forward_topk on that sequence
+ *                        alone (B = 1, S = host_lens[b], n_keep = host_keep[b]), whatever the other sequences, their order and the lm_head
+ *                        chunk size.  (Not to the rows of a PADDED rectangular call: there a row takes its GEMM kernels by the padded S.)
+ * SV_EINVAL before any device work for null pointers, B out of range, a length < 1 or > max_seq_len, max(len) + max_new > max_seq_len, a keep
+ * outside 1 .. its length. */
 int  sv_prefill_ragged(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, float* dev_logits,
                        sv_stream stream);
+int  sv_forward_logprobs_ragged(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, const int32_t* host_keep,
+                                const int32_t* dev_targets, float temperature, float* dev_logprob, float* dev_logsumexp, float* dev_entropy,
+                                int32_t* dev_argmax, int32_t k, int32_t* dev_topk_ids, float* dev_topk_logprobs, int32_t* dev_rank, sv_stream stream);
 /* Scoring forward = `StarVectorForCausalLM.forward(vision_embeds, input_ids, ..., num_logits_to_keep)`
  * (starvector_arch.py:161-184; GRPO's log-prob pass, inference mode): the decoder over inputs_embeds [B,S,hidden] bf16
  * (all-ones mask) and the lm_head over the LAST n_keep positions of every sequence.

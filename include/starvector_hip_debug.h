@@ -263,6 +263,10 @@ int  sv_op_plane_layernorm_strided(const void* x, const void* gamma, const void*
  *   sv_op_gather_rows       out row r = table[dev_ids[r]] (int64 [n]); per_seq > 0: row r goes to out + (r / per_seq) * seq_stride + (r % per_seq) * D
  *   sv_op_gather_last_rows  out [B][D] = row b*S0 + S0-1 of h, or row first + len - 1 with descriptors dev_rag_seq int32 [B][2] = {first packed row, length}
  *   sv_op_gather_tail_rows  out [B*n_keep][D] = the last n_keep rows of each of the B sequences of S0 rows of h
+ *   sv_op_gather_tail_rows_ragged  the same kernel over packed sequences of different lengths, each keeping its own number of rows: descriptors
+ *                           dev_rag_keep int32 [B][4] = {first packed row, length, keep, first output row} with keep in 1..length and first output
+ *                           row = the sum of the keeps in front; out [total_keep][D], total_keep = sum(keep): rows first + length - keep ..
+ *                           first + length - 1 of sequence b go to output rows first output row ..
  *   sv_op_gather_listed_rows  out [n][D] = x[dev_rows[i]] (int32 [n]), x rows ldx elements apart
  *   sv_op_ragged_row_pos    dev_row_pos[first + j] = j for j < len, for each of the B descriptors {first packed row, length}
  *   sv_op_ragged_positions  dev_positions[i] = length of descriptor i / rep, + delta, for i < B * rep
@@ -282,6 +286,8 @@ int  sv_op_gather_rows(const void* table, const int64_t* dev_ids, void* out, int
                        sv_stream stream);
 int  sv_op_gather_last_rows(const void* h, void* out, int32_t B, int32_t S0, int32_t D, const int32_t* dev_rag_seq, sv_stream stream);
 int  sv_op_gather_tail_rows(const void* h, void* out, int32_t B, int32_t S0, int32_t n_keep, int32_t D, sv_stream stream);
+int  sv_op_gather_tail_rows_ragged(const void* h, void* out, int32_t B, int32_t D, const int32_t* dev_rag_keep, int32_t total_keep,
+                                   sv_stream stream);
 int  sv_op_gather_listed_rows(const void* x, int32_t ldx, const int32_t* dev_rows, int32_t n, void* out, int32_t D, sv_stream stream);
 int  sv_op_ragged_row_pos(const int32_t* dev_rag_seq, int32_t B, int32_t* dev_row_pos, sv_stream stream);
 int  sv_op_ragged_positions(int32_t* dev_positions, const int32_t* dev_rag_seq, int32_t B, int32_t rep, int32_t delta, sv_stream stream);

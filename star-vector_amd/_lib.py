@@ -150,6 +150,7 @@ PRODUCT_PROTOTYPES = {
     "sv_generate_topk": (_I, [_P, _P, _I, C.POINTER(_I), _I, _I, C.POINTER(SvSampling), C.POINTER(SvLogitsProcessors),
                               C.POINTER(SvGenerateOutputs), C.POINTER(SvTokenStats), C.POINTER(SvTokenTopk), _P, C.POINTER(_I), _P]),
     "sv_forward_topk": (_I, [_P, _P, _I, _I, _I, _P, _F, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "sv_forward_logprobs_ragged": (_I, [_P, _P, _I, C.POINTER(_I), C.POINTER(_I), _P, _F, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "sv_cb_admit_shared": (_I, [_P, _P, _I, C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(SvCbRequest), C.POINTER(_I), _P]),
     "sv_cb_admit_ragged": (_I, [_P, _P, _I, C.POINTER(_I), C.POINTER(SvCbRequest), C.POINTER(_I), _P]),
     "sv_forward_logits": (_I, [_P, _P, _I, _I, _I, _P, _P]),
@@ -226,6 +227,7 @@ DEBUG_PROTOTYPES = {
     "sv_op_gather_rows": (_I, [_P, _P, _P, _I, _I, _I, C.c_int64, _P]),
     "sv_op_gather_last_rows": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "sv_op_gather_tail_rows": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "sv_op_gather_tail_rows_ragged": (_I, [_P, _P, _I, _I, _P, _I, _P]),
     "sv_op_gather_listed_rows": (_I, [_P, _I, _P, _I, _P, _I, _P]),
     "sv_op_ragged_row_pos": (_I, [_P, _I, _P, _P]),
     "sv_op_ragged_positions": (_I, [_P, _P, _I, _I, _I, _P]),

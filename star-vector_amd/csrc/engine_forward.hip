@@ -1,5 +1,6 @@
 // Host driver, part 2 of 5: the op graphs -- vision tower, adapter, prompt pass, one decode step -- and the forward entry
-// points of the C ABI (sv_encode_image, sv_adapter, sv_embed_tokens, sv_prefill, sv_forward_logits, sv_forward_logprobs, sv_decode_step).
+// points of the C ABI (sv_encode_image, sv_adapter, sv_embed_tokens, sv_prefill, sv_forward_logits, sv_forward_logprobs, sv_forward_logprobs_ragged,
+// sv_decode_step).
 #include <algorithm>
 #include <cmath>
 #include "engine_internal.h"
@@ -194,6 +195,67 @@ static void lm_head_logits(sv_engine* e, int MT, const bf16_t* xp, hipStream_t s
     launch_gemm_skinny(a, st);
 }
 
+// scoring workspace for `rows` kept rows: [rows][D] hidden, [rows][D] ln_f, [rows][Vpad] logits -- the log-prob form keeps its logits in the chunk
+// workspace instead
+static int ensure_score_ws(sv_engine* e, size_t rows, bool with_logits) {
+    const size_t need = rows * (size_t)e->cfg.hidden * 2 + (with_logits ? rows * (size_t)e->Vpad : 0);
+    if (need > e->score_elems) {
+        if (e->score_ws) (void)hipFree(e->score_ws);
+        e->score_ws = nullptr; e->score_elems = 0;
+        HIPCHECK(hipMalloc(reinterpret_cast<void**>(&e->score_ws), need * sizeof(bf16_t)));
+        e->score_elems = need;
+    }
+    return 0;
+}
+// sv_forward_logprobs: the lm_head over the ln_f rows hn [rows][D], `chunk` rows at a time into a workspace that does not grow
+// with rows x vocab, logprob_rows over each chunk while it is still in the last-level cache.  The logits underneath are the
+// bits sv_forward_logits returns whatever the chunk size: this call hands the dispatch no sequence structure, so a chunk can
+// only reach the tile kernels and the one-wave-per-tile kernel, which compute a row with the same MFMA, operand roles and
+// ascending k (tests/test_gpu_ops.py::test_linear_big_m_kernels_agree_bitwise); the split-K remainder kernels with their own
+// K order are never chosen here.  Chunks are multiples of 256 rows: the rows in front of a boundary are whole tiles.  For the
+// same reason a row's outputs do not depend on the rows around it: the ragged scoring pass runs this loop over sum(keep) rows.
+static int score_logprob_chunks(sv_engine* e, const bf16_t* hn, size_t rows, const ScoreLogprobs* lp, hipStream_t st) {
+    const sv_config& c = e->cfg;
+    const int D = c.hidden;
+    const int chunk = e->score_chunk_rows > 0 ? e->score_chunk_rows : SV_SCORE_CHUNK_ROWS;
+    if (e->score_chunk_alloc != chunk) {
+        if (e->score_chunk_ws) (void)hipFree(e->score_chunk_ws);
+        e->score_chunk_ws = nullptr; e->score_chunk_alloc = 0;
+        HIPCHECK(hipMalloc(reinterpret_cast<void**>(&e->score_chunk_ws), (size_t)chunk * e->Vpad * sizeof(bf16_t) + 16));
+        e->score_chunk_alloc = chunk;
+    }
+    if (lp->k > 0 && !lp->lse && e->score_lse_alloc < chunk) {     // the chunk's lse travels from logprob_rows to topk_rows through this
+        if (e->score_lse_ws) (void)hipFree(e->score_lse_ws);
+        e->score_lse_ws = nullptr; e->score_lse_alloc = 0;
+        HIPCHECK(hipMalloc(reinterpret_cast<void**>(&e->score_lse_ws), (size_t)chunk * sizeof(float)));
+        e->score_lse_alloc = chunk;
+    }
+    int32_t* flag = reinterpret_cast<int32_t*>(e->score_chunk_ws + (size_t)chunk * e->Vpad);
+    fill_i32(flag, 0, 1, st);
+    fill_i32(flag + 1, 0x7fffffff, 1, st);
+    for (size_t r0 = 0; r0 < rows; r0 += (size_t)chunk) {
+        const int n = (int)std::min<size_t>((size_t)chunk, rows - r0);
+        gemm(e, PK_PF_GEMM, hn + r0 * D, D, e->lm_head, nullptr, 0, e->score_chunk_ws, e->Vpad, n, ACT_NONE, 0, st, 0, 0, 1);
+        LogprobArgs a;
+        a.logits = e->score_chunk_ws; a.ld = e->Vpad; a.V = c.vocab; a.R = n; a.inv_t = lp->inv_t;
+        a.targets = lp->targets + r0;
+        a.logprob = lp->logprob ? lp->logprob + r0 : nullptr; a.lse = lp->lse ? lp->lse + r0 : nullptr;
+        a.entropy = lp->entropy ? lp->entropy + r0 : nullptr; a.argmax = lp->argmax ? lp->argmax + r0 : nullptr;
+        a.bad = flag; a.row0 = (int)r0;
+        if (lp->k > 0 && !a.lse) a.lse = e->score_lse_ws;
+        prof_mark(e, PK_PF_ROWS, st);
+        launch_logprob_rows(a, st);
+        if (lp->k > 0) {                 // sv_forward_topk: the list and the rank from the same chunk, with the lse just written
+            TopkRowsArgs tk;
+            tk.logits = e->score_chunk_ws; tk.ld = e->Vpad; tk.V = c.vocab; tk.R = n; tk.targets = lp->targets + r0; tk.inv_t = lp->inv_t;
+            tk.lse = a.lse; tk.k = lp->k; tk.ids = lp->topk_ids + r0 * (size_t)lp->k; tk.logprobs = lp->topk_logprobs + r0 * (size_t)lp->k;
+            tk.rank = lp->rank ? lp->rank + r0 : nullptr;
+            launch_topk_rows_bf16(tk, st);
+        }
+    }
+    return 0;
+}
+
 int sveng::prefill_forward(sv_engine* e, const bf16_t* embeds, int B, int S0, hipStream_t st, int n_keep,
                            bf16_t* dev_scores, const int32_t* table, const ScoreLogprobs* lp) {
     if (!table) table = e->block_table;           // continuous batching prefills NEW requests through a table of their slots' pages
@@ -264,14 +326,7 @@ int sveng::prefill_forward(sv_engine* e, const bf16_t* embeds, int B, int S0, hi
         // big-M GEMM; bf16 logits like the reference's bf16 lm_head.  The GEMM writes rows of Vpad columns (the packed
         // weight's padding), the caller's tensor has `vocab` columns.
         const size_t rows = (size_t)B * n_keep;
-        // [rows][D] hidden, [rows][D] ln_f, [rows][Vpad] logits -- the log-prob form keeps its logits in the chunk workspace instead
-        const size_t need = rows * (size_t)D * 2 + (lp ? 0 : rows * (size_t)e->Vpad);
-        if (need > e->score_elems) {
-            if (e->score_ws) (void)hipFree(e->score_ws);
-            e->score_ws = nullptr; e->score_elems = 0;
-            HIPCHECK(hipMalloc(reinterpret_cast<void**>(&e->score_ws), need * sizeof(bf16_t)));
-            e->score_elems = need;
-        }
+        SVCHECK(ensure_score_ws(e, rows, !lp));
         bf16_t* hk = e->score_ws;
         bf16_t* hn = hk + rows * D;
         bf16_t* lg = hn + rows * D;
@@ -279,48 +334,7 @@ int sveng::prefill_forward(sv_engine* e, const bf16_t* embeds, int B, int S0, hi
         launch_gather_tail_rows(e->ph, hk, B, S0, n_keep, D, st);
         launch_layernorm_rows(hk, D, e->ln_f.g, e->ln_f.b, hn, D, (int)rows, D, c.ln_eps, st);
         if (lp) {
-            // sv_forward_logprobs: the same lm_head over the same ln_f rows, `chunk` rows at a time into a workspace that does not grow
-            // with rows x vocab, logprob_rows over each chunk while it is still in the last-level cache.  The logits underneath are the
-            // bits sv_forward_logits returns whatever the chunk size: this call hands the dispatch no sequence structure, so a chunk can
-            // only reach the tile kernels and the one-wave-per-tile kernel, which compute a row with the same MFMA, operand roles and
-            // ascending k (tests/test_gpu_ops.py::test_linear_big_m_kernels_agree_bitwise); the split-K remainder kernels with their own
-            // K order are never chosen here.  Chunks are multiples of 256 rows: the rows in front of a boundary are whole tiles.
-            const int chunk = e->score_chunk_rows > 0 ? e->score_chunk_rows : SV_SCORE_CHUNK_ROWS;
-            if (e->score_chunk_alloc != chunk) {
-                if (e->score_chunk_ws) (void)hipFree(e->score_chunk_ws);
-                e->score_chunk_ws = nullptr; e->score_chunk_alloc = 0;
-                HIPCHECK(hipMalloc(reinterpret_cast<void**>(&e->score_chunk_ws), (size_t)chunk * e->Vpad * sizeof(bf16_t) + 16));
-                e->score_chunk_alloc = chunk;
-            }
-            if (lp->k > 0 && !lp->lse && e->score_lse_alloc < chunk) {     // the chunk's lse travels from logprob_rows to topk_rows through this
-                if (e->score_lse_ws) (void)hipFree(e->score_lse_ws);
-                e->score_lse_ws = nullptr; e->score_lse_alloc = 0;
-                HIPCHECK(hipMalloc(reinterpret_cast<void**>(&e->score_lse_ws), (size_t)chunk * sizeof(float)));
-                e->score_lse_alloc = chunk;
-            }
-            int32_t* flag = reinterpret_cast<int32_t*>(e->score_chunk_ws + (size_t)chunk * e->Vpad);
-            fill_i32(flag, 0, 1, st);
-            fill_i32(flag + 1, 0x7fffffff, 1, st);
-            for (size_t r0 = 0; r0 < rows; r0 += (size_t)chunk) {
-                const int n = (int)std::min<size_t>((size_t)chunk, rows - r0);
-                gemm(e, PK_PF_GEMM, hn + r0 * D, D, e->lm_head, nullptr, 0, e->score_chunk_ws, e->Vpad, n, ACT_NONE, 0, st, 0, 0, 1);
-                LogprobArgs a;
-                a.logits = e->score_chunk_ws; a.ld = e->Vpad; a.V = c.vocab; a.R = n; a.inv_t = lp->inv_t;
-                a.targets = lp->targets + r0;
-                a.logprob = lp->logprob ? lp->logprob + r0 : nullptr; a.lse = lp->lse ? lp->lse + r0 : nullptr;
-                a.entropy = lp->entropy ? lp->entropy + r0 : nullptr; a.argmax = lp->argmax ? lp->argmax + r0 : nullptr;
-                a.bad = flag; a.row0 = (int)r0;
-                if (lp->k > 0 && !a.lse) a.lse = e->score_lse_ws;
-                prof_mark(e, PK_PF_ROWS, st);
-                launch_logprob_rows(a, st);
-                if (lp->k > 0) {                 // sv_forward_topk: the list and the rank from the same chunk, with the lse just written
-                    TopkRowsArgs tk;
-                    tk.logits = e->score_chunk_ws; tk.ld = e->Vpad; tk.V = c.vocab; tk.R = n; tk.targets = lp->targets + r0; tk.inv_t = lp->inv_t;
-                    tk.lse = a.lse; tk.k = lp->k; tk.ids = lp->topk_ids + r0 * (size_t)lp->k; tk.logprobs = lp->topk_logprobs + r0 * (size_t)lp->k;
-                    tk.rank = lp->rank ? lp->rank + r0 : nullptr;
-                    launch_topk_rows_bf16(tk, st);
-                }
-            }
+            SVCHECK(score_logprob_chunks(e, hn, rows, lp, st));
         } else {
             gemm(e, PK_PF_GEMM, hn, D, e->lm_head, nullptr, 0, lg, e->Vpad, (int)rows, ACT_NONE, 0, st);
             HIPCHECK(hipMemcpy2DAsync(dev_scores, (size_t)c.vocab * sizeof(bf16_t), lg, (size_t)e->Vpad * sizeof(bf16_t),
@@ -410,7 +424,11 @@ void sveng::launch_ragged_positions(int32_t* positions, const int32_t* rag_seq, 
     ragged_positions_kernel<<<(n + 63) / 64, 64, 0, st>>>(positions, rag_seq, n, rep, delta);
 }
 
-int sveng::prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, const int32_t* lens, hipStream_t st, const int32_t* table) {
+// Scoring mode (keep + lp, sv_forward_logprobs_ragged): the counterpart of prefill_forward(..., n_keep, ..., lp).  The last layer runs on all packed
+// rows with the per-sequence remainder rows of the layers in front -- a solo scoring pass never prunes it either --, the last keep[b] rows of every
+// sequence are gathered into [sum(keep)][D] and go through ln_f and the chunked lm_head + logprob_rows (+ topk_rows) of the rectangular pass.
+int sveng::prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, const int32_t* lens, hipStream_t st, const int32_t* table,
+                                  const int32_t* keep, const ScoreLogprobs* lp) {
     if (!table) table = e->block_table;
     const sv_config& c = e->cfg;
     const int D = c.hidden, dh = e->dh, F = c.n_inner, QKV = e->QKV, nkv = e->nkv;
@@ -428,9 +446,17 @@ int sveng::prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, con
         HIPCHECK(hipMalloc(reinterpret_cast<void**>(&e->rag_row_pos), (size_t)M * sizeof(int32_t)));
         e->rag_pos_rows = (size_t)M;
     }
-    // ---- the plan of this call: descriptors | attention blocks | last-tile blocks | KV-write blocks | remainder rows of the four projections
+    // ---- the plan of this call: descriptors | attention blocks | last-tile blocks | KV-write blocks | remainder rows of the four projections |
+    // kept-row descriptors (scoring mode)
     const int qt = attn_prefill_q_tile(c.n_head, nkv);
-    std::vector<int32_t> ab, al, kb, rows[4], last[4];
+    std::vector<int32_t> ab, al, kb, rows[4], last[4], kd;
+    int kept = 0;                                      // scoring mode: {first packed row, length, keep, first output row} per sequence
+    if (keep)
+        for (int b = 0, r0 = 0; b < B; ++b) {
+            const int32_t d[4] = {r0, lens[b], keep[b], kept};
+            kd.insert(kd.end(), d, d + 4);
+            r0 += lens[b]; kept += keep[b];
+        }
     ragged_blocks(lens, B, qt, false, ab);
     ragged_blocks(lens, B, qt, true, al);
     ragged_blocks(lens, B, 32, false, kb);
@@ -438,7 +464,7 @@ int sveng::prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, con
     const int acts[4] = {ACT_NONE, ACT_NONE, ACT_GELU_TANH, ACT_NONE};
     if (!(e->exp & SV_EXP_BATCH_REMAINDER))            // set: no per-sequence remainder (as in the rectangular pass)
         for (int i = 0; i < 4; ++i) ragged_gemm_rows(lens, B, proj[i]->N, proj[i]->Kpad, acts[i], rows[i], last[i]);
-    size_t need = (size_t)2 * B + ab.size() + al.size() + kb.size();
+    size_t need = (size_t)2 * B + ab.size() + al.size() + kb.size() + kd.size();
     for (int i = 0; i < 4; ++i) need += rows[i].size() + last[i].size();
     if (need > e->rag_cap) {
         if (e->rag_pending) { HIPCHECK(hipEventSynchronize(e->rag_ev)); e->rag_pending = false; }
@@ -466,6 +492,7 @@ int sveng::prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, con
     const int32_t* d_kb = e->d_rag + put(kb);
     const int32_t *d_rows[4], *d_last[4];
     for (int i = 0; i < 4; ++i) { d_rows[i] = e->d_rag + put(rows[i]); d_last[i] = e->d_rag + put(last[i]); }
+    const int32_t* d_keep = e->d_rag + put(kd);
     HIPCHECK(hipMemcpyAsync(e->d_rag, e->h_rag, off * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIPCHECK(hipEventRecord(e->rag_ev, st));
     e->rag_pending = true;
@@ -485,7 +512,7 @@ int sveng::prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, con
     at.kv_group = c.n_head / nkv; at.causal = 1; at.scale = 1.0f / sqrtf((float)dh);
     at.window = c.sliding_window > 0 ? c.sliding_window : 0;
     at.rag_seq = d_seq;
-    const bool prune_last = !(e->exp & SV_EXP_NO_PRUNE_LAST);
+    const bool prune_last = !keep && !(e->exp & SV_EXP_NO_PRUNE_LAST);
     for (int i = 0; i < c.n_layer; ++i) {
         DecLayer& L = e->dec[i];
         prof_mark(e, PK_PF_ROWS, st);
@@ -524,6 +551,15 @@ int sveng::prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, con
         launch_layernorm_rows(e->ph, D, L.ln2.g, L.ln2.b, e->pln, D, M, D, c.ln_eps, st);
         gemm_ragged(e, PK_PF_GEMM, e->pln, D, L.c_fc, nullptr, 0, e->pmlp, F, M, ACT_GELU_TANH, st, d_rows[2], (int)rows[2].size());
         gemm_ragged(e, PK_PF_GEMM, e->pmlp, F, L.c_proj2, e->ph, D, e->ph, D, M, ACT_NONE, st, d_rows[3], (int)rows[3].size());
+    }
+    if (keep) {
+        SVCHECK(ensure_score_ws(e, (size_t)kept, false));
+        bf16_t* hk = e->score_ws;
+        bf16_t* hn = hk + (size_t)kept * D;
+        prof_mark(e, PK_PF_ROWS, st);
+        launch_gather_tail_rows(e->ph, hk, B, 0, 0, D, st, d_keep, kept);
+        launch_layernorm_rows(hk, D, e->ln_f.g, e->ln_f.b, hn, D, kept, D, c.ln_eps, st);
+        SVCHECK(score_logprob_chunks(e, hn, (size_t)kept, lp, st));
     }
     prof_mark(e, PK_PF_ROWS, st);
     launch_gather_last_rows(e->ph, e->hl, B, 0, D, st, d_seq);
@@ -914,6 +950,54 @@ static int forward_logprobs(const char* who, sv_engine* e, const void* dev_embed
     if (flag[0] & 1)
         return fail(SV_EINVAL, "%s: a target id outside [0, %d) that is not -100; first at row %d (sequence %d, kept position %d)",
                     who, e->cfg.vocab, flag[1], flag[1] / n_keep, flag[1] % n_keep);
+    return 0;
+}
+
+// sv_forward_topk over packed sequences of different lengths, each keeping its own number of rows
+extern "C" int sv_forward_logprobs_ragged(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, const int32_t* host_keep,
+                                          const int32_t* dev_targets, float temperature, float* dev_logprob, float* dev_logsumexp, float* dev_entropy,
+                                          int32_t* dev_argmax, int32_t k, int32_t* dev_topk_ids, float* dev_topk_logprobs, int32_t* dev_rank,
+                                          sv_stream stream) {
+    const char* who = "sv_forward_logprobs_ragged";
+    // (the checks that need no engine come first: they are the same on a machine without a GPU)
+    if (!dev_embeds_packed || !host_lens || !host_keep || !dev_targets) return fail(SV_EINVAL, "%s: null embeds / lengths / keep / targets pointer", who);
+    if (B < 1) return fail(SV_EINVAL, "%s: bad B=%d", who, B);
+    for (int b = 0; b < B; ++b) {
+        if (host_lens[b] < 1) return fail(SV_EINVAL, "%s: length %d of sequence %d (must be >= 1)", who, host_lens[b], b);
+        if (host_keep[b] < 1 || host_keep[b] > host_lens[b])
+            return fail(SV_EINVAL, "%s: keep %d of sequence %d must be in 1..its length %d", who, host_keep[b], b, host_lens[b]);
+    }
+    if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail(SV_EINVAL, "%s: temperature must be finite and > 0", who);
+    if (k < 0 || k > SV_TOPK_MAX) return fail(SV_EINVAL, "%s: k=%d must be in 0..%d", who, k, SV_TOPK_MAX);
+    if (k > 0 && (!dev_topk_ids || !dev_topk_logprobs)) return fail(SV_EINVAL, "%s: k=%d with a null dev_topk_ids / dev_topk_logprobs", who, k);
+    if (k == 0 && !dev_logprob && !dev_logsumexp && !dev_entropy && !dev_argmax) return fail(SV_EINVAL, "%s: every output pointer is null", who);
+    SVCHECK(check_ready(e));
+    if (B > e->cfg.max_batch) return fail(SV_EINVAL, "%s: bad B=%d (max_batch %d)", who, B, e->cfg.max_batch);
+    SVCHECK(ragged_check_lens(e, host_lens, B, who, nullptr, nullptr));
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIPCHECK(hipSetDevice(e->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    SVCHECK(cb_guard(e, who));
+    SVCHECK(assign_pages_ragged(e, B, host_lens, 0, st));
+    const ScoreLogprobs lp{dev_targets, 1.0f / temperature, dev_logprob, dev_logsumexp, dev_entropy, dev_argmax, k,
+                           k > 0 ? dev_topk_ids : nullptr, k > 0 ? dev_topk_logprobs : nullptr, k > 0 ? dev_rank : nullptr};
+    SVCHECK(prefill_forward_ragged(e, (const bf16_t*)dev_embeds_packed, B, host_lens, st, nullptr, host_keep, &lp));
+    ragged_positions(e, B, 1, 0, st);
+    e->cached_B = B;
+    HIPCHECK(hipGetLastError());
+    // the kernel's flag, as in forward_logprobs; the packed row it names is found through the prefix sums of keep
+    int32_t flag[2] = {0, 0};
+    HIPCHECK(hipMemcpyAsync(flag, e->score_chunk_ws + (size_t)e->score_chunk_alloc * e->Vpad, sizeof(flag), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    if (flag[0] & 3) {
+        int b = 0, first = 0;
+        while (b + 1 < B && first + host_keep[b] <= flag[1]) first += host_keep[b++];
+        if (flag[0] & 2)
+            return fail(SV_EHIP, "%s: a row of logits had no finite value (NaN / Inf in the weights or inputs?); first at row %d "
+                                 "(sequence %d, kept position %d)", who, flag[1], b, flag[1] - first);
+        return fail(SV_EINVAL, "%s: a target id outside [0, %d) that is not -100; first at row %d (sequence %d, kept position %d)",
+                    who, e->cfg.vocab, flag[1], b, flag[1] - first);
+    }
     return 0;
 }
 

@@ -312,7 +312,10 @@ void ragged_gemm_rows(const int32_t* lens, int B, int N, int K, int act, std::ve
 void ragged_blocks(const int32_t* lens, int B, int tile, bool last_only, std::vector<int32_t>& out);
 int ragged_check_lens(const sv_engine* e, const int32_t* lens, int B, const char* who, int* max_len, long long* total);
 int assign_pages_ragged(sv_engine* e, int B, const int32_t* lens, int extra, hipStream_t st);
-int prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, const int32_t* lens, hipStream_t st, const int32_t* table = nullptr);
+// keep + lp (both or neither): the scoring mode -- the last keep[b] (host, 1..lens[b]) rows of every sequence through ln_f, the chunked lm_head and
+// logprob_rows / topk_rows, outputs packed [sum(keep)] in sequence order; no layer is pruned
+int prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, const int32_t* lens, hipStream_t st, const int32_t* table = nullptr,
+                           const int32_t* keep = nullptr, const ScoreLogprobs* lp = nullptr);
 // positions[i] = lens[i / rep] + delta for i < B * rep, from the descriptors the last prefill_forward_ragged uploaded
 void ragged_positions(sv_engine* e, int B, int rep, int delta, hipStream_t st);
 // the launch behind it: positions[i] = rag_seq[2 * (i / rep) + 1] + delta for i < n, descriptors {first packed row, length}

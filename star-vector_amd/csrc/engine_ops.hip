@@ -960,6 +960,15 @@ extern "C" int sv_op_gather_tail_rows(const void* h, void* out, int32_t B, int32
     return 0;
 }
 
+extern "C" int sv_op_gather_tail_rows_ragged(const void* h, void* out, int32_t B, int32_t D, const int32_t* dev_rag_keep, int32_t total_keep,
+                                             sv_stream stream) {
+    if (!h || !out || !dev_rag_keep || B < 1 || total_keep < B || D < 8 || D % 8 || !rows_ok(total_keep))
+        return fail(SV_EINVAL, "sv_op_gather_tail_rows_ragged: bad argument (descriptors given, B >= 1, total_keep >= B, D %% 8 == 0)");
+    launch_gather_tail_rows((const bf16_t*)h, (bf16_t*)out, B, 0, 0, D, (hipStream_t)stream, dev_rag_keep, total_keep);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
 extern "C" int sv_op_gather_listed_rows(const void* x, int32_t ldx, const int32_t* dev_rows, int32_t n, void* out, int32_t D, sv_stream stream) {
     if (!x || !dev_rows || !out || !rows_ok(n) || D < 8 || D % 8 || ldx < D || ldx % 8)
         return fail(SV_EINVAL, "sv_op_gather_listed_rows: bad argument (D %% 8 == 0, ldx %% 8 == 0, ldx >= D)");

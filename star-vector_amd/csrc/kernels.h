@@ -228,7 +228,10 @@ void launch_gather_last_rows(const bf16_t* h, bf16_t* out, int B, int S0, int D,
 void launch_gather_listed_rows(const bf16_t* x, int ldx, const int32_t* rows, int n, bf16_t* out, int D, hipStream_t st);
 // ragged prompt pass: row_pos[first row of b + j] = j for j < len[b], from the descriptors {first packed row, length} [B]
 void launch_ragged_row_pos(const int32_t* rag_seq, int B, int32_t* row_pos, hipStream_t st);
-void launch_gather_tail_rows(const bf16_t* h, bf16_t* out, int B, int S0, int n_keep, int D, hipStream_t st);
+// rag_keep (ragged scoring pass): per-sequence descriptors {first packed row, length, keep, first output row}, rag_rows = sum(keep) output rows;
+// nullptr: the last n_keep rows of B sequences of S0 rows
+void launch_gather_tail_rows(const bf16_t* h, bf16_t* out, int B, int S0, int n_keep, int D, hipStream_t st, const int32_t* rag_keep = nullptr,
+                             int rag_rows = 0);
 
 // ---- adapter norm -------------------------------------------------------------------------------
 // y_batch_stride (elements, 0 = planes back to back): the planes may be written straight into a [B][S0][D] prefill buffer

@@ -885,23 +885,38 @@ __global__ void gather_last_rows_kernel(const bf16_t* __restrict__ h, bf16_t* __
     }
 }
 // the last n_keep rows of every sequence, packed [B * n_keep][D] (scoring forward: logits of the kept positions only)
+// rag_keep (ragged scoring pass): sequences of different lengths packed back to back, each keeping its own number of rows -- descriptors int32
+// [B][4] = {first packed row, length, keep, first output row}, keep in 1..length, first output row = the sum of the keeps in front (strictly
+// ascending: an output row finds its sequence by bisection); rag_rows = sum(keep) output rows
 __global__ void gather_tail_rows_kernel(const bf16_t* __restrict__ h, bf16_t* __restrict__ out, int B, int S0, int n_keep,
-                                        int D) {
+                                        int D, const int32_t* __restrict__ rag_keep, int rag_rows) {
     const int NC = D >> 3;
-    const size_t total = (size_t)B * n_keep * NC;
+    const size_t total = rag_keep ? (size_t)rag_rows * NC : (size_t)B * n_keep * NC;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int c = (int)(i % NC);
         const size_t r = i / NC;
-        const int j = (int)(r % n_keep), b = (int)(r / n_keep);
-        *reinterpret_cast<uint4*>(out + r * D + c * 8) =
-            *reinterpret_cast<const uint4*>(h + ((size_t)b * S0 + S0 - n_keep + j) * D + c * 8);
+        size_t src;
+        if (rag_keep) {
+            int lo = 0, hi = B - 1;                   // the last sequence whose first output row is <= r
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if ((size_t)rag_keep[4 * mid + 3] <= r) lo = mid; else hi = mid - 1;
+            }
+            const int32_t* d = rag_keep + 4 * lo;
+            src = (size_t)(d[0] + d[1] - d[2]) + (r - (size_t)d[3]);
+        } else {
+            const int j = (int)(r % n_keep), b = (int)(r / n_keep);
+            src = (size_t)b * S0 + S0 - n_keep + j;
+        }
+        *reinterpret_cast<uint4*>(out + r * D + c * 8) = *reinterpret_cast<const uint4*>(h + src * D + c * 8);
     }
 }
-void launch_gather_tail_rows(const bf16_t* h, bf16_t* out, int B, int S0, int n_keep, int D, hipStream_t st) {
-    size_t total = (size_t)B * n_keep * (D / 8);
+void launch_gather_tail_rows(const bf16_t* h, bf16_t* out, int B, int S0, int n_keep, int D, hipStream_t st, const int32_t* rag_keep,
+                             int rag_rows) {
+    size_t total = (rag_keep ? (size_t)rag_rows : (size_t)B * n_keep) * (D / 8);
     int blocks = (int)((total + 255) / 256);
     if (blocks > 16384) blocks = 16384;
-    gather_tail_rows_kernel<<<blocks, 256, 0, st>>>(h, out, B, S0, n_keep, D);
+    gather_tail_rows_kernel<<<blocks, 256, 0, st>>>(h, out, B, S0, n_keep, D, rag_keep, rag_rows);
 }
 void launch_gather_last_rows(const bf16_t* h, bf16_t* out, int B, int S0, int D, hipStream_t st, const int32_t* rag_seq) {
     int total = B * (D / 8);

@@ -435,6 +435,39 @@ class HipEngine:
                                            _ptr(am), _stream()), "sv_forward_logprobs")
         return TokenLogprobs(lp, lse, ent, am)
 
+    def forward_logprobs_ragged(self, embeds, targets, keep, lengths=None, temperature: float = 1.0, entropy: bool = False,
+                                argmax: bool = False, top_k: int = 0):
+        """`forward_logprobs` over sequences of different lengths in ONE prompt pass, no padding row computed (sv_forward_logprobs_ragged):
+        `embeds` a list of [S_i, D] tensors, or a packed [sum(lengths), D] tensor with `lengths`; keep[b] in 1..S_b = the last rows of sequence b
+        that are scored; targets: integer [sum(keep)], each sequence's kept rows back to back in sequence order, -100 = ignore.  Returns
+        the result types of `forward_logprobs` with packed tensors ([sum(keep)], lists [sum(keep), k]).  Every sequence's slice holds the
+        bits of `forward_logprobs(x_b[None], targets_b[None], keep[b], ...)` on that sequence alone, whatever shares the call with it."""
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 0 <= top_k <= TOPK_MAX:
+            raise ValueError(f"top_k must be an int in 0..{TOPK_MAX}, got {top_k!r}")
+        x, arr, lens = self._packed(embeds, lengths)
+        keep = [int(v) for v in keep]
+        if len(keep) != len(lens) or any(not 1 <= k <= n for k, n in zip(keep, lens)):
+            raise ValueError(f"keep {keep} must hold one count in 1..length for each of the lengths {lens}")
+        n = sum(keep)
+        if tuple(targets.shape) != (n,):
+            raise ValueError(f"targets must be [sum(keep)] = [{n}], got {tuple(targets.shape)}")
+        if targets.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"targets must be int32 or int64, got {targets.dtype}")
+        t = _need(targets.to(torch.int32), torch.int32, "targets")
+        lp = torch.empty(n, dtype=torch.float32, device=x.device)
+        lse = torch.empty(n, dtype=torch.float32, device=x.device)
+        ent = torch.empty(n, dtype=torch.float32, device=x.device) if entropy else None
+        am = torch.empty(n, dtype=torch.int32, device=x.device) if argmax else None
+        ids = torch.empty(n, top_k, dtype=torch.int32, device=x.device) if top_k else None
+        tlp = torch.empty(n, top_k, dtype=torch.float32, device=x.device) if top_k else None
+        rank = torch.empty(n, dtype=torch.int32, device=x.device) if top_k else None
+        check(self.lib.sv_forward_logprobs_ragged(self._h, _ptr(x), len(lens), arr, (C.c_int32 * len(keep))(*keep), _ptr(t), float(temperature),
+                                                  _ptr(lp), _ptr(lse), _ptr(ent), _ptr(am), top_k, _ptr(ids), _ptr(tlp), _ptr(rank), _stream()),
+              "sv_forward_logprobs_ragged")
+        if top_k:
+            return TokenTopLogprobs(lp, lse, ent, am, ids, tlp, rank)
+        return TokenLogprobs(lp, lse, ent, am)
+
     def set_score_chunk_rows(self, rows: int) -> None:
         """Rows per lm_head chunk of `forward_logprobs` (a multiple of 256; 0 = default).  Test surface: the outputs do not depend on it."""
         check(self.lib.sv_debug_set_score_chunk_rows(self._h, int(rows)), "sv_debug_set_score_chunk_rows")
@@ -1374,6 +1407,28 @@ def op_gather_tail_rows(h, n_keep: int, out=None):
         raise ValueError("1 <= n_keep <= S0")
     out = torch.empty(B * n_keep, D, dtype=torch.bfloat16, device=h.device) if out is None else _op_out(out, torch.bfloat16, B * n_keep * D)
     check(lib.sv_op_gather_tail_rows(_ptr(h), _ptr(out), B, S0, int(n_keep), D, _stream()), "sv_op_gather_tail_rows")
+    return out
+
+
+def op_gather_tail_rows_ragged(h, lens, keep, out=None):
+    """h [rows, D], sequences of `lens` rows packed back to back: the last keep[b] rows of every sequence, packed [sum(keep), D]."""
+    lib = _lib.load()
+    h = _need(h, torch.bfloat16, "h")
+    rows, D = h.shape
+    lens, keep = [int(x) for x in lens], [int(x) for x in keep]
+    if not lens or len(keep) != len(lens) or any(not 1 <= k <= n for k, n in zip(keep, lens)):
+        raise ValueError("lens and keep must be non-empty lists of equal size with 1 <= keep[b] <= lens[b]")
+    if sum(lens) > rows:
+        raise ValueError(f"h holds {rows} rows, the call addresses {sum(lens)}")
+    first, total, desc = 0, 0, []
+    for n, k in zip(lens, keep):
+        desc += [first, n, k, total]
+        first += n
+        total += k
+    desc = torch.tensor(desc, dtype=torch.int32, device=h.device)
+    out = torch.empty(total, D, dtype=torch.bfloat16, device=h.device) if out is None else _op_out(out, torch.bfloat16, total * D)
+    check(lib.sv_op_gather_tail_rows_ragged(_ptr(h), _ptr(out), len(lens), D, _ptr(desc), total, _stream()), "sv_op_gather_tail_rows_ragged")
+    torch.cuda.current_stream().synchronize()                  # `desc` is a temporary
     return out
 
 

@@ -1264,7 +1264,7 @@ class StarVectorForCausalLM(nn.Module):
 
     @torch.no_grad()
     def completion_logprobs(self, vision_embeds, input_ids, num_generations, attention_mask, num_logits_to_keep,
-                            temperature: float = 1.0, return_entropy: bool = False, top_logprobs: int = 0):
+                            temperature: float = 1.0, return_entropy: bool = False, top_logprobs: int = 0, unpadded: bool = False):
         """What a GRPO trainer computes from `forward`'s logits, without the logits: float32 [B, n], out[b, j] = the log-probability
         of input_ids[b, -n + j] given everything before it -- selective_log_softmax(forward(...).logits[:, :-1] / temperature, ids)
         with the softmax in fp32 over the bf16 logits (sv_forward_logprobs: device memory does not grow with B * n * vocab).
@@ -1273,7 +1273,13 @@ class StarVectorForCausalLM(nn.Module):
         NotImplementedError.  return_entropy: also the entropy [B, n] of the distribution each token was drawn from (0 at pads).
         top_logprobs = k in 1..32 (sv_forward_topk; teacher-forced distillation targets): the result is a dict instead -- "logprobs" [B, n],
         "entropies" when asked for, and "top_token_ids" / "top_logprobs" [B, n, k] (the k most likely ids of every position, best first, and
-        their log-probs) and "token_ranks" [B, n] (the rank of the token itself, 0 at pads)."""
+        their log-probs) and "token_ranks" [B, n] (the rank of the token itself, 0 at pads).
+        unpadded=True (sv_forward_logprobs_ragged): with a mask that has pads, every row is stripped of its left and right pads and all rows go
+        down in ONE ragged pass -- no pad goes through a layer or the lm_head, and there is one prompt pass whatever the pad counts.  The values
+        equal scoring each row alone without its pads, bit for bit; they are NOT the bits of the padded call (unpadded=False), where a
+        right-padded row takes its GEMM kernels by the padded length S, not by its own.  Entries at pads hold the fill values: 0 for log-prob,
+        entropy and rank, id -1 / log-prob 0 in the lists.  A mask without pads takes the rectangular call; an engine without
+        `forward_logprobs_ragged` raises NotImplementedError."""
         k = int(top_logprobs or 0)
         completion_embeds = self.model._get_embeddings(input_ids)
         inputs_embeds = torch.cat([vision_embeds.repeat(num_generations, 1, 1).to(completion_embeds.dtype),
@@ -1295,6 +1301,8 @@ class StarVectorForCausalLM(nn.Module):
         if attention_mask is not None:
             pad = ~attention_mask.to(torch.bool)[:, S - n:].to(emb16.device)       # the token itself is padding
             targets[:, :n] = targets[:, :n].masked_fill(pad, -100)
+        if unpadded and attention_mask is not None and not bool((attention_mask == 1).all()):
+            return self._completion_logprobs_unpadded(emb16, targets, attention_mask, n, temperature, return_entropy, k)
 
         def score(e16, tg):
             # (top_k goes down only when asked for: an engine without it is never handed it)
@@ -1335,6 +1343,43 @@ class StarVectorForCausalLM(nn.Module):
         if not return_entropy:
             return lp
         return lp, ent
+
+    def _completion_logprobs_unpadded(self, emb16, targets, attention_mask, n, temperature, return_entropy, k):
+        """`completion_logprobs(unpadded=True)` behind the mask checks: targets [B, n + 1] holds -100 at pads and in its last column.  Row b's
+        real positions are lead .. end - 1 (no holes); its scored tokens sit at S - n .. end - 1 (entries 0 .. c - 1 of the output, c of them,
+        none when the row ends before S - n), so its last c + 1 rows are kept: row S - n - 1 + j predicts entry j, the last row nothing."""
+        fn = getattr(self.engine, "forward_logprobs_ragged", None)
+        if fn is None:
+            raise NotImplementedError("completion_logprobs(unpadded=True) needs an engine with forward_logprobs_ragged")
+        B, S = emb16.shape[:2]
+        m = attention_mask.to(torch.bool).to(emb16.device)
+        lens = m.sum(1).tolist()
+        lead = (m.cumsum(1) == 0).sum(1).tolist()
+        count = [max(0, lead[b] + lens[b] - (S - n)) for b in range(B)]
+        keep = [c + 1 for c in count]
+        packed_targets = torch.cat([torch.cat([targets[b, :c], targets[b, n:]]) for b, c in enumerate(count)])
+        r = self._run_scoring(lambda: fn(emb16[m], packed_targets, keep, lengths=lens, temperature=temperature, entropy=return_entropy,
+                                         **({"top_k": k} if k else {})))
+        # scatter: entry j < count[b] of row b comes from packed row first[b] + j (the -100 row behind every sequence's entries is dropped)
+        first = torch.tensor([sum(keep[:b]) for b in range(B)], device=emb16.device).unsqueeze(1)
+        j = torch.arange(n, device=emb16.device).unsqueeze(0)
+        scored = j < torch.tensor(count, device=emb16.device).unsqueeze(1)
+        src = (first + j)[scored]
+
+        def dense(packed, fill, *tail):
+            out = torch.full((B, n, *tail), fill, dtype=packed.dtype, device=packed.device)
+            out[scored] = packed[src]
+            return out
+
+        lp = dense(r.logprobs, 0.0)
+        ent = dense(r.entropy, 0.0) if return_entropy else None
+        if k:
+            res = {"logprobs": lp, "top_token_ids": dense(r.top_token_ids, -1, k), "top_logprobs": dense(r.top_logprobs, 0.0, k),
+                   "token_ranks": dense(r.token_ranks, 0)}
+            if return_entropy:
+                res["entropies"] = ent
+            return res
+        return (lp, ent) if return_entropy else lp
 
     def generate_im2svg(self, batch, **kwargs):           # starvector_arch.py:186-187
         return self.model.generate_im2svg(batch, **kwargs)
