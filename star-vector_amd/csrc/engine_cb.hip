@@ -141,8 +141,7 @@ void cb_fill_slot(const sv_cb_request& r, CbSlot& h, CbBias& bias, std::vector<u
 
 static int cb_begin(sv_engine* e, hipStream_t st) {
     if (e->cb_active) return 0;
-    e->free_pages.clear();
-    for (int p = e->num_pages - 1; p >= 0; --p) e->free_pages.push_back(p);
+    reset_free_pages(e);
     std::fill(e->cb_used.begin(), e->cb_used.end(), 0);
     for (auto& v : e->cb_pages) v.clear();
     e->page_refs.assign((size_t)e->num_pages + 1, 0);
@@ -161,140 +160,39 @@ static int cb_begin(sv_engine* e, hipStream_t st) {
     return 0;
 }
 
-// lens == nullptr: n requests of the common prompt length S0_all (sv_cb_admit, the rectangular prompt pass); otherwise request i has lens[i] prompt rows,
-// packed back to back, and the new requests share ONE ragged prompt pass (sv_cb_admit_ragged)
-static int cb_admit_impl(sv_engine* e, const void* dev_embeds, int32_t n, int32_t S0_all, const int32_t* lens, const sv_cb_request* reqs,
-                         int32_t* slots_out, sv_stream stream) {
-    const sv_config& c = e->cfg;
-    auto S0_of = [&](int i) { return lens ? lens[i] : S0_all; };
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIPCHECK(hipSetDevice(c.device));
-    HIPCHECK(hipEventRecord(e->gen_event, (hipStream_t)stream));
-    hipStream_t st = e->gen_stream;
-    HIPCHECK(hipStreamWaitEvent(st, e->gen_event, 0));
-    SVCHECK(cb_begin(e, st));
-    // free slots (lowest first: keeps the row bucket of the decode graph small) and pages for the whole budget
-    std::vector<int> slots;
+// What an admit stages on the host for its n requests before anything goes to the device.  The two plans below fill the page side -- they take
+// pages from the free list in different orders, which block_table_row and free_pages show --, cb_admit_impl the rest.
+struct AdmitPlan {
+    std::vector<int> slots;                          // request i -> its slot (lowest free first: keeps the row bucket of the decode graph small)
+    std::vector<int32_t> rows;                       // [n][pages_per_seq]: the block-table rows of the slots
+    std::vector<int32_t> pf;                         // the prompt pass's table, one row per prompt
+    std::vector<int> taken;                          // the pages in the order they left the free list (a failed admit puts them back in reverse)
+    std::vector<int32_t> map, pos;                   // slot and last prompt position of request i
+    std::vector<int32_t> fork;                       // the fork launch's descriptor (group admit); empty: no fork launch
+    std::vector<CbSlot> hs;
+    std::vector<CbBias> hb;
+    std::vector<std::vector<uint32_t>> seen_rows;
+    bool record = false;                             // some request records log-probs
+    int take(sv_engine* e) { const int pg = e->free_pages.back(); e->free_pages.pop_back(); taken.push_back(pg); return pg; }
+};
+
+// sv_cb_admit / sv_cb_admit_ragged: every request owns the pages of its whole budget, taken request by request (lens == nullptr: all prompts S0_all rows)
+static int plan_plain(sv_engine* e, int n, int S0_all, const int32_t* lens, const sv_cb_request* reqs, AdmitPlan& p) {
+    const int mp = e->pages_per_seq;
+    auto need_of = [&](int i) { return ((lens ? lens[i] : S0_all) + reqs[i].max_new_tokens + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS; };
     size_t need_pages = 0;
-    for (int s2 = 0; s2 < c.max_batch && (int)slots.size() < n; ++s2) if (!e->cb_used[s2]) slots.push_back(s2);
-    for (int i = 0; i < n; ++i) need_pages += (size_t)(S0_of(i) + reqs[i].max_new_tokens + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS;
-    if ((int)slots.size() < n || need_pages > e->free_pages.size())
+    for (int i = 0; i < n; ++i) need_pages += (size_t)need_of(i);
+    if ((int)p.slots.size() < n || need_pages > e->free_pages.size())
         return fail(SV_EBUSY, "sv_cb_admit: %d requests need %d slots / %zu KV pages, %zu / %zu are free (release finished slots first)",
-                    n, n, need_pages, slots.size(), e->free_pages.size());
-    std::vector<int32_t> rows((size_t)n * e->pages_per_seq, e->trash_page);
-    std::vector<CbSlot> hs(n);
-    std::vector<CbBias> hb(n);
-    std::vector<std::vector<uint32_t>> seen_rows(n);
-    std::vector<int32_t> map(n), pos(n);
-    for (int i = 0; i < n; ++i) pos[i] = S0_of(i) - 1;
-    const bool any_pen = [&] { for (int i = 0; i < n; ++i) if (reqs[i].repetition_penalty > 0.f && reqs[i].repetition_penalty != 1.0f) return true; return false; }();
+                    n, n, need_pages, p.slots.size(), e->free_pages.size());
     for (int i = 0; i < n; ++i) {
-        const int s2 = slots[i];
-        const sv_cb_request& r = reqs[i];
-        const int need = (S0_of(i) + r.max_new_tokens + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS;
-        e->cb_pages[s2].clear();
-        for (int k = 0; k < need; ++k) {
-            rows[(size_t)i * e->pages_per_seq + k] = e->free_pages.back();
-            e->cb_pages[s2].push_back(e->free_pages.back());
-            e->free_pages.pop_back();
-        }
-        e->cb_used[s2] = 1;
-        cb_fill_slot(r, hs[i], hb[i], seen_rows[i], e->seen_words);
-        map[i] = s2;
-        slots_out[i] = s2;
+        p.pos[i] = (lens ? lens[i] : S0_all) - 1;
+        std::vector<int>& held = e->cb_pages[p.slots[i]];
+        held.clear();
+        for (int k = 0; k < need_of(i); ++k) held.push_back(p.rows[(size_t)i * mp + k] = p.take(e));
     }
-    // Device side.  Any failure below rolls the host bookkeeping back (slots, pages) and parks the slots' device state, so a
-    // failed admit leaks nothing and the caller may simply retry: the slots it was told about are NOT in use on error.
-    bool nlive_added = false;
-    const int rc = [&]() -> int {
-    for (int i = 0; i < n; ++i) {
-        const int s2 = slots[i];
-        HIPCHECK(hipMemcpyAsync(e->block_table + (size_t)s2 * e->pages_per_seq, rows.data() + (size_t)i * e->pages_per_seq,
-                                e->pages_per_seq * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(e->cb_slots + s2, &hs[i], sizeof(CbSlot), hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(e->positions + s2, &pos[i], sizeof(int32_t), hipMemcpyHostToDevice, st));
-        if (reqs[i].semantics == 1) {
-            // vLLM mode: the repetition set starts as the prompt ids, the output counts at zero -- before the first-token step below
-            HIPCHECK(hipMemcpyAsync(e->seen + (size_t)s2 * e->seen_words, seen_rows[i].data(), e->seen_words * sizeof(uint32_t),
-                                    hipMemcpyHostToDevice, st));
-            HIPCHECK(hipMemsetAsync(e->cb_counts + (size_t)s2 * e->Vpad, 0, (size_t)e->Vpad * sizeof(uint16_t), st));
-            if (hs[i].n_bias) HIPCHECK(hipMemcpyAsync(e->cb_bias + s2, &hb[i], sizeof(CbBias), hipMemcpyHostToDevice, st));
-        } else if (any_pen) {
-            HIPCHECK(hipMemsetAsync(e->seen + (size_t)s2 * e->seen_words, 0, e->seen_words * sizeof(uint32_t), st));
-        }
-    }
-    HIPCHECK(hipMemcpyAsync(e->cb_table_pf, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(e->cb_map, map.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    add_i32(e->cb_nlive, n, 1, st);
-    nlive_added = true;
-    // prompt pass of the NEW requests only (their pages through cb_table_pf); the live slots keep decoding afterwards
-    if (lens) SVCHECK(prefill_forward_ragged(e, (const bf16_t*)dev_embeds, n, lens, st, e->cb_table_pf));
-    else SVCHECK(prefill_forward(e, (const bf16_t*)dev_embeds, n, S0_all, st, 0, nullptr, e->cb_table_pf));
-    CbStepArgs a;
-    cb_step_args(e, a, e->cb_map, false);                  // (a request that records comes in through sv_cb_admit_logprobs: none of these does)
-    launch_cb_step(a, n, st);                              // first token of every new request, from the prefill logits
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(st));                    // the staging vectors above are host temporaries
+    p.pf = p.rows;      // prompt i is written through the pages of request i
     return 0;
-    }();
-    if (rc) {
-        const std::string why = g_err;                      // keep the first error's text
-        (void)hipStreamSynchronize(st);
-        (void)hipGetLastError();
-        std::vector<int32_t> trash(e->pages_per_seq, e->trash_page);
-        for (int i = n - 1; i >= 0; --i) {                  // pages go back in reverse order: the free list is as it was
-            const int s2 = slots[i];
-            for (size_t k = e->cb_pages[s2].size(); k-- > 0;) e->free_pages.push_back(e->cb_pages[s2][k]);
-            e->cb_pages[s2].clear();
-            e->cb_used[s2] = 0;
-            slots_out[i] = -1;
-            // best effort on the device: the slot is dead and its block-table row points at the trash page again
-            (void)hipMemsetAsync(e->cb_slots + s2, 0, sizeof(CbSlot), st);
-            (void)hipMemcpyAsync(e->block_table + (size_t)s2 * e->pages_per_seq, trash.data(), trash.size() * sizeof(int32_t),
-                                 hipMemcpyHostToDevice, st);
-        }
-        if (nlive_added) add_i32(e->cb_nlive, -n, 1, st);
-        (void)hipStreamSynchronize(st);
-        (void)hipGetLastError();
-        g_err = why;
-        return rc;
-    }
-    return 0;
-}
-
-extern "C" int sv_cb_admit(sv_engine* e, const void* dev_embeds, int32_t n, int32_t S0, const sv_cb_request* reqs,
-                           int32_t* slots_out, sv_stream stream) {
-    SVCHECK(check_ready(e));
-    if (!dev_embeds || !reqs || !slots_out || n < 1) return fail(SV_EINVAL, "sv_cb_admit: null argument or empty batch");
-    const sv_config& c = e->cfg;
-    if (n > c.max_batch) return fail(SV_EINVAL, "sv_cb_admit: %d requests exceed max_batch %d", n, c.max_batch);
-    if (S0 < 1) return fail(SV_EINVAL, "sv_cb_admit: bad prompt length %d", S0);
-    for (int i = 0; i < n; ++i) {
-        const sv_cb_request& r = reqs[i];
-        if (r.max_new_tokens < 1 || S0 + r.max_new_tokens > c.max_seq_len)
-            return fail(SV_EINVAL, "sv_cb_admit: request %d: prompt %d + max_new_tokens %d out of range (max_seq_len %d)", i, S0, r.max_new_tokens, c.max_seq_len);
-        SVCHECK(cb_check_request(r, c.vocab, i, "sv_cb_admit"));
-    }
-    return cb_admit_impl(e, dev_embeds, n, S0, nullptr, reqs, slots_out, stream);
-}
-
-extern "C" int sv_cb_admit_ragged(sv_engine* e, const void* dev_embeds_packed, int32_t n, const int32_t* host_lens, const sv_cb_request* reqs,
-                                  int32_t* slots_out, sv_stream stream) {
-    // (the checks that need no engine come first: they are the same on a machine without a GPU)
-    if (!dev_embeds_packed || !host_lens || !reqs || !slots_out || n < 1) return fail(SV_EINVAL, "sv_cb_admit_ragged: null argument or empty batch");
-    for (int i = 0; i < n; ++i)
-        if (host_lens[i] < 1) return fail(SV_EINVAL, "sv_cb_admit_ragged: request %d: bad prompt length %d", i, host_lens[i]);
-    SVCHECK(check_ready(e));
-    const sv_config& c = e->cfg;
-    if (n > c.max_batch) return fail(SV_EINVAL, "sv_cb_admit_ragged: %d requests exceed max_batch %d", n, c.max_batch);
-    for (int i = 0; i < n; ++i) {
-        const sv_cb_request& r = reqs[i];
-        if (r.max_new_tokens < 1 || host_lens[i] > c.max_seq_len || host_lens[i] + r.max_new_tokens > c.max_seq_len)
-            return fail(SV_EINVAL, "sv_cb_admit_ragged: request %d: prompt %d + max_new_tokens %d out of range (max_seq_len %d)", i, host_lens[i], r.max_new_tokens,
-                        c.max_seq_len);
-        SVCHECK(cb_check_request(r, c.vocab, i, "sv_cb_admit_ragged"));
-    }
-    return cb_admit_impl(e, dev_embeds_packed, n, 0, host_lens, reqs, slots_out, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -338,168 +236,201 @@ long long shared_page_plan(const int32_t* lens, int n_prompts, const int32_t* gr
 }
 }  // namespace sveng
 
-// lps: what each request records (sv_cb_admit_logprobs), nullptr = nothing
-static int cb_admit_shared_impl(sv_engine* e, const void* dev_embeds, int32_t U, const int32_t* lens, int32_t n, const int32_t* group,
-                                const sv_cb_request* reqs, const sv_cb_logprobs* lps, int32_t* slots_out, sv_stream stream) {
-    const sv_config& c = e->cfg;
-    const int mp = e->pages_per_seq, mb = c.max_batch;
+// sv_cb_admit_shared / sv_cb_admit_logprobs: every prompt's shared pages first (held once, counted in page_refs), then each request's private ones
+static int plan_group(sv_engine* e, int U, const int32_t* lens, int n, const int32_t* group, const sv_cb_request* reqs, AdmitPlan& p) {
+    const int mp = e->pages_per_seq, mb = e->cfg.max_batch;
+    std::vector<int32_t> budgets(n), n_sh(n), n_pv(n);
+    for (int i = 0; i < n; ++i) budgets[i] = reqs[i].max_new_tokens;
+    const size_t need_pages = (size_t)shared_page_plan(lens, U, group, budgets.data(), n, n_sh.data(), n_pv.data());
+    if ((int)p.slots.size() < n || need_pages > e->free_pages.size())
+        return fail(SV_EBUSY, "sv_cb_admit_shared: %d requests over %d prompts need %d slots / %zu KV pages, %zu / %zu are free (release finished slots first)",
+                    n, U, n, need_pages, p.slots.size(), e->free_pages.size());
+    p.pf.assign((size_t)U * mp, e->trash_page);
+    p.fork.assign(6 * (size_t)mb, 0);
+    std::vector<std::vector<int>> prompt_pages(U);
+    std::vector<int> owner(U, -1), n_dst(U, 0);
+    for (int u = 0; u < U; ++u)
+        for (int k = 0; k < lens[u] / SV_PAGE_TOKENS; ++k) prompt_pages[u].push_back(p.take(e));
+    for (int i = 0; i < n; ++i) {
+        const int u = group[i];
+        std::vector<int>& held = e->cb_pages[p.slots[i]];
+        held.clear();
+        for (int k = 0; k < n_sh[i]; ++k) {
+            held.push_back(p.rows[(size_t)i * mp + k] = prompt_pages[u][k]);
+            ++e->page_refs[prompt_pages[u][k]];
+        }
+        for (int k = 0; k < n_pv[i]; ++k) held.push_back(p.rows[(size_t)i * mp + n_sh[i] + k] = p.take(e));
+        if (owner[u] < 0) owner[u] = i;          // the prompt pass writes prompt u through the pages of its first request
+        else ++n_dst[u];
+        p.pos[i] = lens[u] - 1;
+        p.fork[5 * (size_t)mb + i] = u;          // logits row of the prompt (u <= i: shared_check_group)
+    }
+    for (int u = 0, d0 = 0; u < U; ++u) {
+        const int o = owner[u];
+        for (int k = 0; k < (lens[u] + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS; ++k) p.pf[(size_t)u * mp + k] = p.rows[(size_t)o * mp + k];
+        p.fork[4 * u] = p.slots[o]; p.fork[4 * u + 1] = lens[u]; p.fork[4 * u + 2] = d0; p.fork[4 * u + 3] = n_dst[u];
+        for (int i = 0; i < n; ++i) if (group[i] == u && i != o) p.fork[4 * (size_t)mb + d0++] = p.slots[i];
+    }
+    return 0;
+}
+
+// The device side of an admit: the slots' state, ONE prompt pass over the U new prompts (their pages through cb_table_pf; rectangular when
+// lens == nullptr), the fork launch when the plan has a descriptor (tail pages to the other slots of each prompt, logits row i <- row group[i]) and
+// the first-token step; the live slots keep decoding afterwards.  Any failure rolls the host bookkeeping back (slots, pages) and parks the slots'
+// device state, so a failed admit leaks nothing and the caller may simply retry: the slots it was told about are NOT in use on error.
+static int cb_admit_commit(sv_engine* e, const void* dev_embeds, int U, int S0_all, const int32_t* lens, const sv_cb_request* reqs,
+                           const sv_cb_logprobs* lps, const AdmitPlan& p, int32_t* slots_out, hipStream_t st) {
+    const int n = (int)p.slots.size(), mp = e->pages_per_seq;
+    const bool any_pen = [&] { for (int i = 0; i < n; ++i) if (reqs[i].repetition_penalty > 0.f && reqs[i].repetition_penalty != 1.0f) return true; return false; }();
+    bool nlive_added = false;
+    const int rc = [&]() -> int {
+    for (int i = 0; i < n; ++i) {
+        const int s2 = p.slots[i];
+        HIPCHECK(hipMemcpyAsync(e->block_table + (size_t)s2 * mp, p.rows.data() + (size_t)i * mp, mp * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(e->cb_slots + s2, &p.hs[i], sizeof(CbSlot), hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemcpyAsync(e->positions + s2, &p.pos[i], sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (reqs[i].semantics == 1) {
+            // vLLM mode: the repetition set starts as the prompt ids, the output counts at zero -- before the first-token step below
+            HIPCHECK(hipMemcpyAsync(e->seen + (size_t)s2 * e->seen_words, p.seen_rows[i].data(), e->seen_words * sizeof(uint32_t),
+                                    hipMemcpyHostToDevice, st));
+            HIPCHECK(hipMemsetAsync(e->cb_counts + (size_t)s2 * e->Vpad, 0, (size_t)e->Vpad * sizeof(uint16_t), st));
+            if (p.hs[i].n_bias) HIPCHECK(hipMemcpyAsync(e->cb_bias + s2, &p.hb[i], sizeof(CbBias), hipMemcpyHostToDevice, st));
+        } else if (any_pen) {
+            HIPCHECK(hipMemsetAsync(e->seen + (size_t)s2 * e->seen_words, 0, e->seen_words * sizeof(uint32_t), st));
+        }
+        if (p.record) SVCHECK(cb_lp_set(e, s2, lps + i, st));
+    }
+    HIPCHECK(hipMemcpyAsync(e->cb_table_pf, p.pf.data(), p.pf.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(e->cb_map, p.map.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (!p.fork.empty()) HIPCHECK(hipMemcpyAsync(e->fork_desc, p.fork.data(), p.fork.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    add_i32(e->cb_nlive, n, 1, st);
+    nlive_added = true;
+    if (lens) SVCHECK(prefill_forward_ragged(e, (const bf16_t*)dev_embeds, U, lens, st, e->cb_table_pf));
+    else SVCHECK(prefill_forward(e, (const bf16_t*)dev_embeds, U, S0_all, st, 0, nullptr, e->cb_table_pf));
+    if (!p.fork.empty()) {
+        ForkArgs f;
+        fork_args(e, U, n, f);
+        launch_fork_prompt(f, st);
+    }
+    CbStepArgs a;
+    cb_step_args(e, a, e->cb_map, p.record);
+    launch_cb_step(a, n, st);                              // first token of every new request, from its prompt's logits (column 0 of its record)
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));                    // the plan's vectors are host temporaries
+    return 0;
+    }();
+    if (!rc) return 0;
+    const std::string why = g_err;                          // keep the first error's text
+    (void)hipStreamSynchronize(st);
+    (void)hipGetLastError();
+    std::vector<int32_t> trash(mp, e->trash_page);
+    for (int i = n - 1; i >= 0; --i) {
+        const int s2 = p.slots[i];
+        e->cb_pages[s2].clear();
+        e->cb_used[s2] = 0;
+        slots_out[i] = -1;
+        // best effort on the device: the slot is dead, records nothing and its block-table row points at the trash page again
+        (void)hipMemsetAsync(e->cb_slots + s2, 0, sizeof(CbSlot), st);
+        (void)hipMemcpyAsync(e->block_table + (size_t)s2 * mp, trash.data(), trash.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
+        (void)cb_lp_set(e, s2, nullptr, st);
+    }
+    for (size_t k = p.taken.size(); k-- > 0;) {             // pages go back in reverse order, no holder left: the free list is as it was
+        e->page_refs[p.taken[k]] = 0;
+        e->free_pages.push_back(p.taken[k]);
+    }
+    if (nlive_added) add_i32(e->cb_nlive, -n, 1, st);
+    (void)hipStreamSynchronize(st);
+    (void)hipGetLastError();
+    g_err = why;
+    return rc;
+}
+
+// group == nullptr: n requests, one prompt each (U == n; lens == nullptr: the common length S0_all and the rectangular prompt pass); otherwise the
+// group admit: request i samples prompt group[i] of the U prompts.  lps: what each request records (sv_cb_admit_logprobs), nullptr = nothing.
+static int cb_admit_impl(sv_engine* e, const void* dev_embeds, int32_t U, int32_t S0_all, const int32_t* lens, int32_t n, const int32_t* group,
+                         const sv_cb_request* reqs, const sv_cb_logprobs* lps, int32_t* slots_out, sv_stream stream) {
+    const int mp = e->pages_per_seq, mb = e->cfg.max_batch;
     std::lock_guard<std::mutex> lk(e->mu);
-    HIPCHECK(hipSetDevice(c.device));
+    HIPCHECK(hipSetDevice(e->cfg.device));
     HIPCHECK(hipEventRecord(e->gen_event, (hipStream_t)stream));
     hipStream_t st = e->gen_stream;
     HIPCHECK(hipStreamWaitEvent(st, e->gen_event, 0));
     SVCHECK(cb_begin(e, st));
-    if (!e->fork_desc) SVCHECK(dalloc(e, &e->fork_desc, 6 * (size_t)mb));
-    const bool record = [&] { for (int i = 0; lps && i < n; ++i) if (lps[i].enable) return true; return false; }();
-    if (record) SVCHECK(cb_lp_alloc(e));
-    std::vector<int> slots;
-    for (int s2 = 0; s2 < mb && (int)slots.size() < n; ++s2) if (!e->cb_used[s2]) slots.push_back(s2);
-    std::vector<int32_t> budgets(n), n_sh(n), n_pv(n);
-    for (int i = 0; i < n; ++i) budgets[i] = reqs[i].max_new_tokens;
-    const size_t need_pages = (size_t)shared_page_plan(lens, U, group, budgets.data(), n, n_sh.data(), n_pv.data());
-    if ((int)slots.size() < n || need_pages > e->free_pages.size())
-        return fail(SV_EBUSY, "sv_cb_admit_shared: %d requests over %d prompts need %d slots / %zu KV pages, %zu / %zu are free (release finished slots first)",
-                    n, U, n, need_pages, slots.size(), e->free_pages.size());
-    // host bookkeeping; `taken` = the pages in the order they left the free list (a failed admit puts them back in reverse)
-    std::vector<int> taken;
-    auto take = [&]() { const int pg = e->free_pages.back(); e->free_pages.pop_back(); taken.push_back(pg); return pg; };
-    std::vector<int32_t> rows((size_t)n * mp, e->trash_page), pf((size_t)U * mp, e->trash_page), desc(6 * (size_t)mb, 0);
-    std::vector<std::vector<int>> prompt_pages(U);
-    std::vector<int> owner(U, -1), n_dst(U, 0);
-    for (int u = 0; u < U; ++u)
-        for (int k = 0; k < lens[u] / SV_PAGE_TOKENS; ++k) prompt_pages[u].push_back(take());
-    std::vector<CbSlot> hs(n);
-    std::vector<CbBias> hb(n);
-    std::vector<std::vector<uint32_t>> seen_rows(n);
-    std::vector<int32_t> map(n), pos(n);
-    const bool any_pen = [&] { for (int i = 0; i < n; ++i) if (reqs[i].repetition_penalty > 0.f && reqs[i].repetition_penalty != 1.0f) return true; return false; }();
+    if (group && !e->fork_desc) SVCHECK(dalloc(e, &e->fork_desc, 6 * (size_t)mb));
+    AdmitPlan p;
+    p.record = [&] { for (int i = 0; lps && i < n; ++i) if (lps[i].enable) return true; return false; }();
+    if (p.record) SVCHECK(cb_lp_alloc(e));
+    for (int s2 = 0; s2 < mb && (int)p.slots.size() < n; ++s2) if (!e->cb_used[s2]) p.slots.push_back(s2);
+    p.rows.assign((size_t)n * mp, e->trash_page);
+    p.map.resize(n); p.pos.resize(n); p.hs.resize(n); p.hb.resize(n); p.seen_rows.resize(n);
+    SVCHECK(group ? plan_group(e, U, lens, n, group, reqs, p) : plan_plain(e, n, S0_all, lens, reqs, p));
     for (int i = 0; i < n; ++i) {
-        const int s2 = slots[i], u = group[i];
-        e->cb_pages[s2].clear();
-        for (int k = 0; k < n_sh[i]; ++k) {
-            rows[(size_t)i * mp + k] = prompt_pages[u][k];
-            e->cb_pages[s2].push_back(prompt_pages[u][k]);
-            ++e->page_refs[prompt_pages[u][k]];
-        }
-        for (int k = 0; k < n_pv[i]; ++k) {
-            const int pg = take();
-            rows[(size_t)i * mp + n_sh[i] + k] = pg;
-            e->cb_pages[s2].push_back(pg);
-        }
-        if (owner[u] < 0) owner[u] = i;          // the prompt pass writes prompt u through the pages of its first request
-        else ++n_dst[u];
+        const int s2 = p.slots[i];
         e->cb_used[s2] = 1;
-        cb_fill_slot(reqs[i], hs[i], hb[i], seen_rows[i], e->seen_words);
-        map[i] = s2; pos[i] = lens[u] - 1; slots_out[i] = s2;
-        desc[5 * (size_t)mb + i] = u;            // logits row of the prompt (u <= i: shared_check_group)
+        cb_fill_slot(reqs[i], p.hs[i], p.hb[i], p.seen_rows[i], e->seen_words);
+        p.map[i] = s2;
+        slots_out[i] = s2;
     }
-    for (int u = 0, d0 = 0; u < U; ++u) {
-        const int o = owner[u];
-        for (int k = 0; k < (lens[u] + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS; ++k) pf[(size_t)u * mp + k] = rows[(size_t)o * mp + k];
-        desc[4 * u] = slots[o]; desc[4 * u + 1] = lens[u]; desc[4 * u + 2] = d0; desc[4 * u + 3] = n_dst[u];
-        for (int i = 0; i < n; ++i) if (group[i] == u && i != o) desc[4 * (size_t)mb + d0++] = slots[i];
-    }
-    bool nlive_added = false;
-    const int rc = [&]() -> int {
-    for (int i = 0; i < n; ++i) {
-        const int s2 = slots[i];
-        HIPCHECK(hipMemcpyAsync(e->block_table + (size_t)s2 * mp, rows.data() + (size_t)i * mp, mp * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(e->cb_slots + s2, &hs[i], sizeof(CbSlot), hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(e->positions + s2, &pos[i], sizeof(int32_t), hipMemcpyHostToDevice, st));
-        if (reqs[i].semantics == 1) {
-            HIPCHECK(hipMemcpyAsync(e->seen + (size_t)s2 * e->seen_words, seen_rows[i].data(), e->seen_words * sizeof(uint32_t),
-                                    hipMemcpyHostToDevice, st));
-            HIPCHECK(hipMemsetAsync(e->cb_counts + (size_t)s2 * e->Vpad, 0, (size_t)e->Vpad * sizeof(uint16_t), st));
-            if (hs[i].n_bias) HIPCHECK(hipMemcpyAsync(e->cb_bias + s2, &hb[i], sizeof(CbBias), hipMemcpyHostToDevice, st));
-        } else if (any_pen) {
-            HIPCHECK(hipMemsetAsync(e->seen + (size_t)s2 * e->seen_words, 0, e->seen_words * sizeof(uint32_t), st));
-        }
-        if (record) SVCHECK(cb_lp_set(e, s2, lps + i, st));
-    }
-    HIPCHECK(hipMemcpyAsync(e->cb_table_pf, pf.data(), pf.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(e->cb_map, map.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(e->fork_desc, desc.data(), desc.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    add_i32(e->cb_nlive, n, 1, st);
-    nlive_added = true;
-    // ONE prompt pass over the U prompts (their pages through cb_table_pf), then the fork launch: tail pages to the other slots of each prompt,
-    // logits row i <- row group[i]; the live slots keep decoding afterwards
-    SVCHECK(prefill_forward_ragged(e, (const bf16_t*)dev_embeds, U, lens, st, e->cb_table_pf));
-    ForkArgs f;
-    fork_args(e, U, n, f);
-    launch_fork_prompt(f, st);
-    CbStepArgs a;
-    cb_step_args(e, a, e->cb_map, record);
-    launch_cb_step(a, n, st);                              // first token of every new request, from its prompt's logits (column 0 of its record)
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(st));                    // the staging vectors above are host temporaries
-    return 0;
-    }();
-    if (rc) {
-        const std::string why = g_err;                      // keep the first error's text
-        (void)hipStreamSynchronize(st);
-        (void)hipGetLastError();
-        std::vector<int32_t> trash(mp, e->trash_page);
-        for (int i = n - 1; i >= 0; --i) {
-            const int s2 = slots[i];
-            e->cb_pages[s2].clear();
-            e->cb_used[s2] = 0;
-            slots_out[i] = -1;
-            (void)hipMemsetAsync(e->cb_slots + s2, 0, sizeof(CbSlot), st);
-            (void)hipMemcpyAsync(e->block_table + (size_t)s2 * mp, trash.data(), trash.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
-            (void)cb_lp_set(e, s2, nullptr, st);
-        }
-        for (size_t k = taken.size(); k-- > 0;) {           // pages go back in reverse order, no holder left: the free list is as it was
-            e->page_refs[taken[k]] = 0;
-            e->free_pages.push_back(taken[k]);
-        }
-        if (nlive_added) add_i32(e->cb_nlive, -n, 1, st);
-        (void)hipStreamSynchronize(st);
-        (void)hipGetLastError();
-        g_err = why;
-        return rc;
-    }
-    return 0;
+    return cb_admit_commit(e, dev_embeds, U, S0_all, lens, reqs, lps, p, slots_out, st);
 }
 
-extern "C" int sv_cb_admit_shared(sv_engine* e, const void* dev_embeds_packed, int32_t n_prompts, const int32_t* host_lens, int32_t n,
-                                  const int32_t* host_group, const sv_cb_request* reqs, int32_t* slots_out, sv_stream stream) {
-    // (the checks that need no engine come first: they are the same on a machine without a GPU)
-    if (!dev_embeds_packed || !host_lens || !host_group || !reqs || !slots_out) return fail(SV_EINVAL, "sv_cb_admit_shared: null argument");
-    SVCHECK(shared_check_group("sv_cb_admit_shared", host_lens, n_prompts, host_group, n));
-    SVCHECK(check_ready(e));
+// the per-request checks behind the engine check: the budget against max_seq_len and the request itself; len_of(i) = the prompt rows of request i
+template <class LenOf>
+static int cb_check_requests(const sv_engine* e, const char* who, int n, const sv_cb_request* reqs, LenOf len_of) {
     const sv_config& c = e->cfg;
-    if (n > c.max_batch) return fail(SV_EINVAL, "sv_cb_admit_shared: %d requests exceed max_batch %d", n, c.max_batch);
     for (int i = 0; i < n; ++i) {
         const sv_cb_request& r = reqs[i];
-        const int len = host_lens[host_group[i]];
+        const int len = len_of(i);
         if (r.max_new_tokens < 1 || len > c.max_seq_len || len + r.max_new_tokens > c.max_seq_len)
-            return fail(SV_EINVAL, "sv_cb_admit_shared: request %d: prompt %d + max_new_tokens %d out of range (max_seq_len %d)", i, len, r.max_new_tokens,
-                        c.max_seq_len);
-        SVCHECK(cb_check_request(r, c.vocab, i, "sv_cb_admit_shared"));
+            return fail(SV_EINVAL, "%s: request %d: prompt %d + max_new_tokens %d out of range (max_seq_len %d)", who, i, len, r.max_new_tokens, c.max_seq_len);
+        SVCHECK(cb_check_request(r, c.vocab, i, who));
     }
-    return cb_admit_shared_impl(e, dev_embeds_packed, n_prompts, host_lens, n, host_group, reqs, nullptr, slots_out, stream);
+    return 0;
 }
 
-// sv_cb_admit_shared plus what each request records; lps == NULL or every enable == 0: sv_cb_admit_shared's tokens and launches
+extern "C" int sv_cb_admit(sv_engine* e, const void* dev_embeds, int32_t n, int32_t S0, const sv_cb_request* reqs,
+                           int32_t* slots_out, sv_stream stream) {
+    SVCHECK(check_ready(e));
+    if (!dev_embeds || !reqs || !slots_out || n < 1) return fail(SV_EINVAL, "sv_cb_admit: null argument or empty batch");
+    if (n > e->cfg.max_batch) return fail(SV_EINVAL, "sv_cb_admit: %d requests exceed max_batch %d", n, e->cfg.max_batch);
+    if (S0 < 1) return fail(SV_EINVAL, "sv_cb_admit: bad prompt length %d", S0);
+    SVCHECK(cb_check_requests(e, "sv_cb_admit", n, reqs, [&](int) { return S0; }));
+    return cb_admit_impl(e, dev_embeds, n, S0, nullptr, n, nullptr, reqs, nullptr, slots_out, stream);
+}
+
+extern "C" int sv_cb_admit_ragged(sv_engine* e, const void* dev_embeds_packed, int32_t n, const int32_t* host_lens, const sv_cb_request* reqs,
+                                  int32_t* slots_out, sv_stream stream) {
+    // (the checks that need no engine come first: they are the same on a machine without a GPU)
+    if (!dev_embeds_packed || !host_lens || !reqs || !slots_out || n < 1) return fail(SV_EINVAL, "sv_cb_admit_ragged: null argument or empty batch");
+    for (int i = 0; i < n; ++i)
+        if (host_lens[i] < 1) return fail(SV_EINVAL, "sv_cb_admit_ragged: request %d: bad prompt length %d", i, host_lens[i]);
+    SVCHECK(check_ready(e));
+    if (n > e->cfg.max_batch) return fail(SV_EINVAL, "sv_cb_admit_ragged: %d requests exceed max_batch %d", n, e->cfg.max_batch);
+    SVCHECK(cb_check_requests(e, "sv_cb_admit_ragged", n, reqs, [&](int i) { return host_lens[i]; }));
+    return cb_admit_impl(e, dev_embeds_packed, n, 0, host_lens, n, nullptr, reqs, nullptr, slots_out, stream);
+}
+
+// sv_cb_admit_shared, and sv_cb_admit_logprobs = that plus what each request records (lps == NULL or every enable == 0: sv_cb_admit_shared's tokens
+// and launches)
+static int cb_admit_group(const char* who, sv_engine* e, const void* dev_embeds_packed, int32_t n_prompts, const int32_t* host_lens, int32_t n,
+                          const int32_t* host_group, const sv_cb_request* reqs, const sv_cb_logprobs* lps, int32_t* slots_out, sv_stream stream) {
+    // (the checks that need no engine come first: they are the same on a machine without a GPU)
+    if (!dev_embeds_packed || !host_lens || !host_group || !reqs || !slots_out) return fail(SV_EINVAL, "%s: null argument", who);
+    SVCHECK(shared_check_group(who, host_lens, n_prompts, host_group, n));
+    SVCHECK(cb_check_logprobs(reqs, lps, n, who));
+    SVCHECK(check_ready(e));
+    if (n > e->cfg.max_batch) return fail(SV_EINVAL, "%s: %d requests exceed max_batch %d", who, n, e->cfg.max_batch);
+    SVCHECK(cb_check_requests(e, who, n, reqs, [&](int i) { return host_lens[host_group[i]]; }));
+    return cb_admit_impl(e, dev_embeds_packed, n_prompts, 0, host_lens, n, host_group, reqs, lps, slots_out, stream);
+}
+extern "C" int sv_cb_admit_shared(sv_engine* e, const void* dev_embeds_packed, int32_t n_prompts, const int32_t* host_lens, int32_t n,
+                                  const int32_t* host_group, const sv_cb_request* reqs, int32_t* slots_out, sv_stream stream) {
+    return cb_admit_group("sv_cb_admit_shared", e, dev_embeds_packed, n_prompts, host_lens, n, host_group, reqs, nullptr, slots_out, stream);
+}
 extern "C" int sv_cb_admit_logprobs(sv_engine* e, const void* dev_embeds_packed, int32_t n_prompts, const int32_t* host_lens, int32_t n,
                                     const int32_t* host_group, const sv_cb_request* reqs, const sv_cb_logprobs* lps, int32_t* slots_out,
                                     sv_stream stream) {
-    // (the checks that need no engine come first: they are the same on a machine without a GPU)
-    if (!dev_embeds_packed || !host_lens || !host_group || !reqs || !slots_out) return fail(SV_EINVAL, "sv_cb_admit_logprobs: null argument");
-    SVCHECK(shared_check_group("sv_cb_admit_logprobs", host_lens, n_prompts, host_group, n));
-    SVCHECK(cb_check_logprobs(reqs, lps, n, "sv_cb_admit_logprobs"));
-    SVCHECK(check_ready(e));
-    const sv_config& c = e->cfg;
-    if (n > c.max_batch) return fail(SV_EINVAL, "sv_cb_admit_logprobs: %d requests exceed max_batch %d", n, c.max_batch);
-    for (int i = 0; i < n; ++i) {
-        const sv_cb_request& r = reqs[i];
-        const int len = host_lens[host_group[i]];
-        if (r.max_new_tokens < 1 || len > c.max_seq_len || len + r.max_new_tokens > c.max_seq_len)
-            return fail(SV_EINVAL, "sv_cb_admit_logprobs: request %d: prompt %d + max_new_tokens %d out of range (max_seq_len %d)", i, len, r.max_new_tokens,
-                        c.max_seq_len);
-        SVCHECK(cb_check_request(r, c.vocab, i, "sv_cb_admit_logprobs"));
-    }
-    return cb_admit_shared_impl(e, dev_embeds_packed, n_prompts, host_lens, n, host_group, reqs, lps, slots_out, stream);
+    return cb_admit_group("sv_cb_admit_logprobs", e, dev_embeds_packed, n_prompts, host_lens, n, host_group, reqs, lps, slots_out, stream);
 }
 
 extern "C" int sv_cb_step(sv_engine* e, int32_t n_steps, int32_t* n_live_out, sv_stream stream) {

@@ -142,13 +142,14 @@ static int ensure_prefill_ws(sv_engine* e, size_t rows) {
     return 0;
 }
 
-int sveng::assign_pages(sv_engine* e, int B, int total_len, hipStream_t st) {
-    // page allocator: hand every sequence the pages for its whole budget up front (the decode loop
-    // runs without host round-trips, so pages cannot be added mid-flight)
-    const int need = (total_len + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS;
-    if (need > e->pages_per_seq) return fail(SV_EINVAL, "sequence length %d exceeds max_seq_len %d", total_len, e->cfg.max_seq_len);
+void sveng::reset_free_pages(sv_engine* e) {
     e->free_pages.clear();
     for (int p = e->num_pages - 1; p >= 0; --p) e->free_pages.push_back(p);
+}
+// page allocator: hand every sequence the pages for its whole budget up front (the decode loop runs without host round-trips, so pages cannot be
+// added mid-flight): lens[b] + extra tokens for sequence b (lens == nullptr: extra tokens each; extra < 0: the whole max_seq_len, as sv_prefill hands out)
+int sveng::assign_pages_ragged(sv_engine* e, int B, const int32_t* lens, int extra, hipStream_t st) {
+    reset_free_pages(e);
     // The table goes up from a PINNED host image without a stream synchronise (the pageable copy + hipStreamSynchronize of rounds 1-5 drained the
     // stream in front of every prompt pass: ~25 us of idle GPU on the way to the first token); the image is rewritten only after the upload
     // before it has completed (an event, normally long past).
@@ -156,15 +157,25 @@ int sveng::assign_pages(sv_engine* e, int B, int total_len, hipStream_t st) {
     const size_t n = (size_t)e->cfg.max_batch * e->pages_per_seq;
     int32_t* table = e->h_table;
     memset(table, 0, n * sizeof(int32_t));
-    for (int b = 0; b < B; ++b)
+    for (int b = 0; b < B; ++b) {
+        const int total = extra < 0 ? e->cfg.max_seq_len : (lens ? lens[b] : 0) + extra;
+        const int need = (total + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS;
+        if (need > e->pages_per_seq) return fail(SV_EINVAL, "sequence length %d exceeds max_seq_len %d", total, e->cfg.max_seq_len);
         for (int i = 0; i < need; ++i) {
             table[(size_t)b * e->pages_per_seq + i] = e->free_pages.back();
             e->free_pages.pop_back();
         }
+    }
     HIPCHECK(hipMemcpyAsync(e->block_table, table, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIPCHECK(hipEventRecord(e->table_ev, st));
     e->table_pending = true;
     return 0;
+}
+int sveng::assign_pages(sv_engine* e, int B, int total_len, hipStream_t st) {
+    // (a common length that does not fit is refused before the free list is touched)
+    if ((total_len + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS > e->pages_per_seq)
+        return fail(SV_EINVAL, "sequence length %d exceeds max_seq_len %d", total_len, e->cfg.max_seq_len);
+    return assign_pages_ragged(e, B, nullptr, total_len, st);
 }
 
 // lm_head -> e->logits; xp holds ln_f(h) in fragment order
@@ -387,29 +398,6 @@ int sveng::ragged_check_lens(const sv_engine* e, const int32_t* lens, int B, con
     }
     if (max_len) *max_len = mx;
     if (total) *total = sum;
-    return 0;
-}
-
-// pages per sequence for lens[b] + extra tokens (extra < 0: the whole max_seq_len, as sv_prefill hands out)
-int sveng::assign_pages_ragged(sv_engine* e, int B, const int32_t* lens, int extra, hipStream_t st) {
-    e->free_pages.clear();
-    for (int p = e->num_pages - 1; p >= 0; --p) e->free_pages.push_back(p);
-    if (e->table_pending) { HIPCHECK(hipEventSynchronize(e->table_ev)); e->table_pending = false; }
-    const size_t n = (size_t)e->cfg.max_batch * e->pages_per_seq;
-    int32_t* table = e->h_table;
-    memset(table, 0, n * sizeof(int32_t));
-    for (int b = 0; b < B; ++b) {
-        const int total = extra < 0 ? e->cfg.max_seq_len : lens[b] + extra;
-        const int need = (total + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS;
-        if (need > e->pages_per_seq) return fail(SV_EINVAL, "sequence length %d exceeds max_seq_len %d", total, e->cfg.max_seq_len);
-        for (int i = 0; i < need; ++i) {
-            table[(size_t)b * e->pages_per_seq + i] = e->free_pages.back();
-            e->free_pages.pop_back();
-        }
-    }
-    HIPCHECK(hipMemcpyAsync(e->block_table, table, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipEventRecord(e->table_ev, st));
-    e->table_pending = true;
     return 0;
 }
 
@@ -877,6 +865,46 @@ extern "C" int sv_prefill_ragged(sv_engine* e, const void* dev_embeds_packed, in
     return 0;
 }
 
+// the packed kept row a scoring kernel flagged -> (sequence, kept position): n_keep rows per sequence, or the prefix sums of keep
+static void score_row_owner(int row, int B, int n_keep, const int32_t* keep, int* seq, int* pos) {
+    int b = 0, first = 0;
+    if (!keep) { b = row / n_keep; first = b * n_keep; }
+    else while (b + 1 < B && first + keep[b] <= row) first += keep[b++];
+    *seq = b; *pos = row - first;
+}
+// One scoring-mode prompt pass under the engine lock: pages for exactly the rows given, the pass, positions = the lengths, and -- with lp -- the
+// kernels' flag.  lens == nullptr: B sequences of S rows, the last n_keep kept (into dev_scores or lp); otherwise the ragged pass over (lens, keep).
+static int score_pass(sv_engine* e, const char* who, const void* embeds, int B, int S, int n_keep, const int32_t* lens, const int32_t* keep,
+                      bf16_t* dev_scores, const ScoreLogprobs* lp, hipStream_t st) {
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIPCHECK(hipSetDevice(e->cfg.device));
+    SVCHECK(cb_guard(e, who));
+    if (lens) {
+        SVCHECK(assign_pages_ragged(e, B, lens, 0, st));
+        SVCHECK(prefill_forward_ragged(e, (const bf16_t*)embeds, B, lens, st, nullptr, keep, lp));
+        ragged_positions(e, B, 1, 0, st);
+    } else {
+        SVCHECK(assign_pages(e, B, S, st));
+        SVCHECK(prefill_forward(e, (const bf16_t*)embeds, B, S, st, n_keep, dev_scores, nullptr, lp));
+        fill_i32(e->positions, S, B, st);
+    }
+    e->cached_B = B;
+    HIPCHECK(hipGetLastError());
+    if (!lp) return 0;
+    // the kernel's flag: a target outside the vocabulary (its logprob is NaN) / a row without a finite logit (all of its outputs are NaN)
+    int32_t flag[2] = {0, 0};
+    HIPCHECK(hipMemcpyAsync(flag, e->score_chunk_ws + (size_t)e->score_chunk_alloc * e->Vpad, sizeof(flag), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    if (!(flag[0] & 3)) return 0;
+    int seq = 0, pos = 0;
+    score_row_owner(flag[1], B, n_keep, lens ? keep : nullptr, &seq, &pos);
+    if (flag[0] & 2)
+        return fail(SV_EHIP, "%s: a row of logits had no finite value (NaN / Inf in the weights or inputs?); first at row %d "
+                             "(sequence %d, kept position %d)", who, flag[1], seq, pos);
+    return fail(SV_EINVAL, "%s: a target id outside [0, %d) that is not -100; first at row %d (sequence %d, kept position %d)",
+                who, e->cfg.vocab, flag[1], seq, pos);
+}
+
 extern "C" int sv_forward_logits(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S, int32_t n_keep,
                                  void* dev_logits_bf16, sv_stream stream) {
     SVCHECK(check_ready(e));
@@ -884,121 +912,86 @@ extern "C" int sv_forward_logits(sv_engine* e, const void* dev_embeds, int32_t B
     if (B < 1 || B > e->cfg.max_batch) return fail(SV_EINVAL, "sv_forward_logits: bad B=%d (max_batch %d)", B, e->cfg.max_batch);
     if (S < 1 || S > e->cfg.max_seq_len) return fail(SV_EINVAL, "sv_forward_logits: S=%d out of range (max_seq_len %d)", S, e->cfg.max_seq_len);
     if (n_keep < 1 || n_keep > S) return fail(SV_EINVAL, "sv_forward_logits: n_keep=%d must be in 1..S", n_keep);
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIPCHECK(hipSetDevice(e->cfg.device));
-    hipStream_t st = (hipStream_t)stream;
-    SVCHECK(cb_guard(e, "sv_forward_logits"));
-    SVCHECK(assign_pages(e, B, S, st));
-    SVCHECK(prefill_forward(e, (const bf16_t*)dev_embeds, B, S, st, n_keep, (bf16_t*)dev_logits_bf16));
-    fill_i32(e->positions, S, B, st);
-    e->cached_B = B;
-    HIPCHECK(hipGetLastError());
-    return 0;
+    return score_pass(e, "sv_forward_logits", dev_embeds, B, S, n_keep, nullptr, nullptr, (bf16_t*)dev_logits_bf16, nullptr, (hipStream_t)stream);
 }
 
-// sv_forward_logprobs and sv_forward_topk: k = 0 is the former, to the letter
-static int forward_logprobs(const char* who, sv_engine* e, const void* dev_embeds, int32_t B, int32_t S, int32_t n_keep,
-                            const int32_t* dev_targets, float temperature, float* dev_logprob, float* dev_logsumexp,
-                            float* dev_entropy, int32_t* dev_argmax, int32_t k, int32_t* dev_topk_ids, float* dev_topk_logprobs,
-                            int32_t* dev_rank, sv_stream stream);
+// A scoring call with a ScoreLogprobs, as sv_forward_logprobs / sv_forward_topk (B sequences of S rows, the last n_keep kept) or
+// sv_forward_logprobs_ragged (lens, keep) describes it
+struct ScoreCall {
+    const char* who;
+    bool ragged;
+    const void* embeds;
+    int32_t B, S, n_keep;
+    const int32_t *lens, *keep;
+    float temperature;
+    ScoreLogprobs lp;
+};
+// The checks that need no engine (they come first: they are the same on a machine without a GPU).  Every check is stated once; the two forms
+// have always asked in different orders, and which of two violations is reported is part of each one's contract.
+static int check_score_call(const ScoreCall& c) {
+    const char* who = c.who;
+    const auto nulls = [&]() -> int {
+        if (c.ragged && (!c.embeds || !c.lens || !c.keep || !c.lp.targets)) return fail(SV_EINVAL, "%s: null embeds / lengths / keep / targets pointer", who);
+        if (!c.embeds || !c.lp.targets) return fail(SV_EINVAL, "%s: null embeds / targets", who);
+        return 0;
+    };
+    const auto shape = [&]() -> int {
+        if (!c.ragged) return (c.S < 1 || c.n_keep < 1 || c.n_keep > c.S) ? fail(SV_EINVAL, "%s: n_keep=%d must be in 1..S (S=%d)", who, c.n_keep, c.S) : 0;
+        if (c.B < 1) return fail(SV_EINVAL, "%s: bad B=%d", who, c.B);
+        for (int b = 0; b < c.B; ++b) {
+            if (c.lens[b] < 1) return fail(SV_EINVAL, "%s: length %d of sequence %d (must be >= 1)", who, c.lens[b], b);
+            if (c.keep[b] < 1 || c.keep[b] > c.lens[b])
+                return fail(SV_EINVAL, "%s: keep %d of sequence %d must be in 1..its length %d", who, c.keep[b], b, c.lens[b]);
+        }
+        return 0;
+    };
+    const auto temperature = [&]() -> int {
+        return (!(c.temperature > 0.f) || !std::isfinite(c.temperature)) ? fail(SV_EINVAL, "%s: temperature must be finite and > 0", who) : 0;
+    };
+    const auto lists = [&]() -> int {
+        if (c.lp.k < 0 || c.lp.k > SV_TOPK_MAX) return fail(SV_EINVAL, "%s: k=%d must be in 0..%d", who, c.lp.k, SV_TOPK_MAX);
+        if (c.lp.k > 0 && (!c.lp.topk_ids || !c.lp.topk_logprobs)) return fail(SV_EINVAL, "%s: k=%d with a null dev_topk_ids / dev_topk_logprobs", who, c.lp.k);
+        return 0;
+    };
+    const auto outputs = [&]() -> int {
+        if (c.lp.k == 0 && !c.lp.logprob && !c.lp.lse && !c.lp.entropy && !c.lp.argmax) return fail(SV_EINVAL, "%s: every output pointer is null", who);
+        return 0;
+    };
+    if (c.ragged) { SVCHECK(nulls()); SVCHECK(shape()); SVCHECK(temperature()); SVCHECK(lists()); return outputs(); }
+    SVCHECK(lists()); SVCHECK(nulls()); SVCHECK(outputs()); SVCHECK(temperature()); return shape();
+}
+static int score_call(sv_engine* e, ScoreCall c, sv_stream stream) {
+    SVCHECK(check_score_call(c));
+    SVCHECK(check_ready(e));
+    if (c.B < 1 || c.B > e->cfg.max_batch) return fail(SV_EINVAL, "%s: bad B=%d (max_batch %d)", c.who, c.B, e->cfg.max_batch);
+    if (c.ragged) SVCHECK(ragged_check_lens(e, c.lens, c.B, c.who, nullptr, nullptr));
+    else if (c.S > e->cfg.max_seq_len) return fail(SV_EINVAL, "%s: S=%d out of range (max_seq_len %d)", c.who, c.S, e->cfg.max_seq_len);
+    if (c.lp.k == 0) { c.lp.topk_ids = nullptr; c.lp.topk_logprobs = nullptr; c.lp.rank = nullptr; }
+    return score_pass(e, c.who, c.embeds, c.B, c.S, c.n_keep, c.ragged ? c.lens : nullptr, c.keep, nullptr, &c.lp, (hipStream_t)stream);
+}
+
 extern "C" int sv_forward_logprobs(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S, int32_t n_keep,
                                    const int32_t* dev_targets, float temperature, float* dev_logprob, float* dev_logsumexp,
                                    float* dev_entropy, int32_t* dev_argmax, sv_stream stream) {
-    return forward_logprobs("sv_forward_logprobs", e, dev_embeds, B, S, n_keep, dev_targets, temperature, dev_logprob, dev_logsumexp, dev_entropy,
-                            dev_argmax, 0, nullptr, nullptr, nullptr, stream);
+    return score_call(e, {"sv_forward_logprobs", false, dev_embeds, B, S, n_keep, nullptr, nullptr, temperature,
+                          {dev_targets, 1.0f / temperature, dev_logprob, dev_logsumexp, dev_entropy, dev_argmax}}, stream);
 }
+// k == 0 is sv_forward_logprobs, to the letter
 extern "C" int sv_forward_topk(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S, int32_t n_keep, const int32_t* dev_targets,
                                float temperature, float* dev_logprob, float* dev_logsumexp, float* dev_entropy, int32_t* dev_argmax, int32_t k,
                                int32_t* dev_topk_ids, float* dev_topk_logprobs, int32_t* dev_rank, sv_stream stream) {
-    if (k == 0)
-        return forward_logprobs("sv_forward_logprobs", e, dev_embeds, B, S, n_keep, dev_targets, temperature, dev_logprob, dev_logsumexp, dev_entropy,
-                                dev_argmax, 0, nullptr, nullptr, nullptr, stream);
-    if (k < 0 || k > SV_TOPK_MAX) return fail(SV_EINVAL, "sv_forward_topk: k=%d must be in 0..%d", k, SV_TOPK_MAX);
-    if (!dev_topk_ids || !dev_topk_logprobs) return fail(SV_EINVAL, "sv_forward_topk: k=%d with a null dev_topk_ids / dev_topk_logprobs", k);
-    return forward_logprobs("sv_forward_topk", e, dev_embeds, B, S, n_keep, dev_targets, temperature, dev_logprob, dev_logsumexp, dev_entropy,
-                            dev_argmax, k, dev_topk_ids, dev_topk_logprobs, dev_rank, stream);
+    return score_call(e, {k == 0 ? "sv_forward_logprobs" : "sv_forward_topk", false, dev_embeds, B, S, n_keep, nullptr, nullptr, temperature,
+                          {dev_targets, 1.0f / temperature, dev_logprob, dev_logsumexp, dev_entropy, dev_argmax, k, dev_topk_ids, dev_topk_logprobs, dev_rank}},
+                      stream);
 }
-static int forward_logprobs(const char* who, sv_engine* e, const void* dev_embeds, int32_t B, int32_t S, int32_t n_keep,
-                            const int32_t* dev_targets, float temperature, float* dev_logprob, float* dev_logsumexp,
-                            float* dev_entropy, int32_t* dev_argmax, int32_t k, int32_t* dev_topk_ids, float* dev_topk_logprobs,
-                            int32_t* dev_rank, sv_stream stream) {
-    // (the checks that need no engine come first: they are the same on a machine without a GPU)
-    if (!dev_embeds || !dev_targets) return fail(SV_EINVAL, "%s: null embeds / targets", who);
-    if (k == 0 && !dev_logprob && !dev_logsumexp && !dev_entropy && !dev_argmax) return fail(SV_EINVAL, "%s: every output pointer is null", who);
-    if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail(SV_EINVAL, "%s: temperature must be finite and > 0", who);
-    if (S < 1 || n_keep < 1 || n_keep > S) return fail(SV_EINVAL, "%s: n_keep=%d must be in 1..S (S=%d)", who, n_keep, S);
-    SVCHECK(check_ready(e));
-    if (B < 1 || B > e->cfg.max_batch) return fail(SV_EINVAL, "%s: bad B=%d (max_batch %d)", who, B, e->cfg.max_batch);
-    if (S > e->cfg.max_seq_len) return fail(SV_EINVAL, "%s: S=%d out of range (max_seq_len %d)", who, S, e->cfg.max_seq_len);
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIPCHECK(hipSetDevice(e->cfg.device));
-    hipStream_t st = (hipStream_t)stream;
-    SVCHECK(cb_guard(e, who));
-    SVCHECK(assign_pages(e, B, S, st));
-    const ScoreLogprobs lp{dev_targets, 1.0f / temperature, dev_logprob, dev_logsumexp, dev_entropy, dev_argmax, k, dev_topk_ids, dev_topk_logprobs, dev_rank};
-    SVCHECK(prefill_forward(e, (const bf16_t*)dev_embeds, B, S, st, n_keep, nullptr, nullptr, &lp));
-    fill_i32(e->positions, S, B, st);
-    e->cached_B = B;
-    HIPCHECK(hipGetLastError());
-    // the kernel's flag: a target outside the vocabulary (its logprob is NaN) / a row without a finite logit (all of its outputs are NaN)
-    int32_t flag[2] = {0, 0};
-    HIPCHECK(hipMemcpyAsync(flag, e->score_chunk_ws + (size_t)e->score_chunk_alloc * e->Vpad, sizeof(flag), hipMemcpyDeviceToHost, st));
-    HIPCHECK(hipStreamSynchronize(st));
-    if (flag[0] & 2)
-        return fail(SV_EHIP, "%s: a row of logits had no finite value (NaN / Inf in the weights or inputs?); first at row %d "
-                             "(sequence %d, kept position %d)", who, flag[1], flag[1] / n_keep, flag[1] % n_keep);
-    if (flag[0] & 1)
-        return fail(SV_EINVAL, "%s: a target id outside [0, %d) that is not -100; first at row %d (sequence %d, kept position %d)",
-                    who, e->cfg.vocab, flag[1], flag[1] / n_keep, flag[1] % n_keep);
-    return 0;
-}
-
 // sv_forward_topk over packed sequences of different lengths, each keeping its own number of rows
 extern "C" int sv_forward_logprobs_ragged(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, const int32_t* host_keep,
                                           const int32_t* dev_targets, float temperature, float* dev_logprob, float* dev_logsumexp, float* dev_entropy,
                                           int32_t* dev_argmax, int32_t k, int32_t* dev_topk_ids, float* dev_topk_logprobs, int32_t* dev_rank,
                                           sv_stream stream) {
-    const char* who = "sv_forward_logprobs_ragged";
-    // (the checks that need no engine come first: they are the same on a machine without a GPU)
-    if (!dev_embeds_packed || !host_lens || !host_keep || !dev_targets) return fail(SV_EINVAL, "%s: null embeds / lengths / keep / targets pointer", who);
-    if (B < 1) return fail(SV_EINVAL, "%s: bad B=%d", who, B);
-    for (int b = 0; b < B; ++b) {
-        if (host_lens[b] < 1) return fail(SV_EINVAL, "%s: length %d of sequence %d (must be >= 1)", who, host_lens[b], b);
-        if (host_keep[b] < 1 || host_keep[b] > host_lens[b])
-            return fail(SV_EINVAL, "%s: keep %d of sequence %d must be in 1..its length %d", who, host_keep[b], b, host_lens[b]);
-    }
-    if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail(SV_EINVAL, "%s: temperature must be finite and > 0", who);
-    if (k < 0 || k > SV_TOPK_MAX) return fail(SV_EINVAL, "%s: k=%d must be in 0..%d", who, k, SV_TOPK_MAX);
-    if (k > 0 && (!dev_topk_ids || !dev_topk_logprobs)) return fail(SV_EINVAL, "%s: k=%d with a null dev_topk_ids / dev_topk_logprobs", who, k);
-    if (k == 0 && !dev_logprob && !dev_logsumexp && !dev_entropy && !dev_argmax) return fail(SV_EINVAL, "%s: every output pointer is null", who);
-    SVCHECK(check_ready(e));
-    if (B > e->cfg.max_batch) return fail(SV_EINVAL, "%s: bad B=%d (max_batch %d)", who, B, e->cfg.max_batch);
-    SVCHECK(ragged_check_lens(e, host_lens, B, who, nullptr, nullptr));
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIPCHECK(hipSetDevice(e->cfg.device));
-    hipStream_t st = (hipStream_t)stream;
-    SVCHECK(cb_guard(e, who));
-    SVCHECK(assign_pages_ragged(e, B, host_lens, 0, st));
-    const ScoreLogprobs lp{dev_targets, 1.0f / temperature, dev_logprob, dev_logsumexp, dev_entropy, dev_argmax, k,
-                           k > 0 ? dev_topk_ids : nullptr, k > 0 ? dev_topk_logprobs : nullptr, k > 0 ? dev_rank : nullptr};
-    SVCHECK(prefill_forward_ragged(e, (const bf16_t*)dev_embeds_packed, B, host_lens, st, nullptr, host_keep, &lp));
-    ragged_positions(e, B, 1, 0, st);
-    e->cached_B = B;
-    HIPCHECK(hipGetLastError());
-    // the kernel's flag, as in forward_logprobs; the packed row it names is found through the prefix sums of keep
-    int32_t flag[2] = {0, 0};
-    HIPCHECK(hipMemcpyAsync(flag, e->score_chunk_ws + (size_t)e->score_chunk_alloc * e->Vpad, sizeof(flag), hipMemcpyDeviceToHost, st));
-    HIPCHECK(hipStreamSynchronize(st));
-    if (flag[0] & 3) {
-        int b = 0, first = 0;
-        while (b + 1 < B && first + host_keep[b] <= flag[1]) first += host_keep[b++];
-        if (flag[0] & 2)
-            return fail(SV_EHIP, "%s: a row of logits had no finite value (NaN / Inf in the weights or inputs?); first at row %d "
-                                 "(sequence %d, kept position %d)", who, flag[1], b, flag[1] - first);
-        return fail(SV_EINVAL, "%s: a target id outside [0, %d) that is not -100; first at row %d (sequence %d, kept position %d)",
-                    who, e->cfg.vocab, flag[1], b, flag[1] - first);
-    }
-    return 0;
+    return score_call(e, {"sv_forward_logprobs_ragged", true, dev_embeds_packed, B, 0, 0, host_lens, host_keep, temperature,
+                          {dev_targets, 1.0f / temperature, dev_logprob, dev_logsumexp, dev_entropy, dev_argmax, k, dev_topk_ids, dev_topk_logprobs, dev_rank}},
+                      stream);
 }
 
 extern "C" int sv_decode_step(sv_engine* e, const int32_t* dev_tokens, int32_t B, float* dev_logits, sv_stream stream) {

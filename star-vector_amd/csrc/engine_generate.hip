@@ -290,18 +290,79 @@ int sveng::report_bad_logits(sv_engine* e, hipStream_t st, const char* who, int 
     }
 }
 
-// G: samples per prompt (1: sv_generate / sv_generate_ragged; > 1: sv_generate_shared -- one prompt pass over the B prompts, B * G decode rows)
-static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const int32_t* lens, const sv_sampling* sp,
-                            const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream, int G,
-                            const sv_logits_processors* lp, const sv_token_stats* ts, const sv_token_topk* tk);
-static int generate_retry(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const int32_t* lens, const sv_sampling* sp,
-                          const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream, int G = 1,
-                          const sv_logits_processors* lp = nullptr, const sv_token_stats* ts = nullptr, const sv_token_topk* tk = nullptr) {
+// One generate call as its entry point describes it (internal: the public header knows nothing of it).  `who` is the entry point whose checks run
+// and whose name their messages carry: a call handed over (topk NULL -> sv_generate_stats, stats NULL -> sv_generate_processed, an all-zero lp ->
+// sv_generate_shared) is described again by the entry point that takes it.
+enum : unsigned {
+    GC_ARGS = 1,         // the checks that need no engine run (sv_generate_ex: none, everything is the engine's)
+    GC_LENS = 2,         // host_lens is required (sv_generate_ragged)
+    GC_LP_FIRST = 4,     // the processors are checked right behind the pointers (sv_generate_processed), not last (sv_generate_stats / _topk)
+};
+struct GenCall {
+    const char* who;
+    unsigned checks;
+    const void* embeds;
+    int32_t B, S0;                    // behind check_gen_call S0 is the longest prompt: the budget counts from it
+    const int32_t* lens;              // nullptr: B prompts of S0 rows each
+    int32_t n_samples;                // G: samples per prompt -- one prompt pass over the B prompts, B * G decode rows
+    const sv_sampling* sp;
+    const sv_logits_processors* lp;   // nullptr unless some processor is set
+    const sv_generate_outputs* outs;
+    const sv_token_stats* stats;
+    const sv_token_topk* topk;
+    int64_t* dev_out_tokens;
+    int32_t* n_generated;
+    sv_stream stream;
+};
+static bool lp_any(const sv_logits_processors* lp) { return lp && (lp->no_repeat_ngram_size != 0 || lp->n_bad_words != 0 || lp->min_p != 0.f); }
+static int check_token_topk(const sv_sampling* sp, const sv_logits_processors* lp, const sv_token_topk* tk, int max_new);
+// The checks that need no engine (they come first: they are the same on a machine without a GPU), in the order the entry points have always
+// run them, and the longest prompt.  max_new <= 0 is refused later, by the call itself.
+static int check_gen_call(GenCall& c) {
+    if (!(c.checks & GC_ARGS)) return 0;
+    const char* who = c.who;
+    const sv_sampling* sp = c.sp;
+    if (!c.embeds || ((c.checks & GC_LENS) && !c.lens) || !sp || !c.dev_out_tokens || !c.n_generated) return fail(SV_EINVAL, "%s: null argument", who);
+    if (c.stats && !c.stats->dev_logprob && !c.stats->dev_logprob_processed && !c.stats->dev_entropy)
+        return fail(SV_EINVAL, "%s: dev_logprob, dev_logprob_processed and dev_entropy are all NULL (pass stats = NULL for a call without statistics)", who);
+    if (c.checks & GC_LP_FIRST) SVCHECK(check_logits_processors(c.lp, 0, who));
+    if (sp->num_beams > 1 && !c.topk) {      // (a top-k call refuses beams among its own checks, below)
+        if (c.stats)
+            return fail(SV_EINVAL, "%s: token statistics with num_beams %d are not built (beam search reports sequences_scores; beam rows reorder)", who,
+                        sp->num_beams);
+        if (c.lp)
+            return fail(SV_EINVAL, "%s: no_repeat_ngram_size / bad words / min_p with num_beams %d is not built (beam rows reorder their histories)", who,
+                        sp->num_beams);
+    }
+    if (c.B < 1) return fail(SV_EINVAL, "%s: bad B=%d", who, c.B);
+    if (c.n_samples < 1) return fail(SV_EINVAL, "%s: bad n_samples=%d (must be >= 1)", who, c.n_samples);
+    int longest = c.S0;
+    if (c.lens) {
+        longest = 0;
+        for (int b = 0; b < c.B; ++b) {
+            if (c.lens[b] < 1) return fail(SV_EINVAL, "%s: length %d of sequence %d (must be >= 1)", who, c.lens[b], b);
+            longest = c.lens[b] > longest ? c.lens[b] : longest;
+        }
+    } else if (c.S0 < 1) {
+        return fail(SV_EINVAL, "%s: bad S0=%d", who, c.S0);
+    }
+    const int max_new = sp->max_length - longest;
+    if (c.topk) SVCHECK(check_token_topk(sp, c.lp, c.topk, max_new));
+    if (c.stats && max_new > 0 && c.stats->ld < (int64_t)max_new)
+        return fail(SV_EINVAL, "%s: %sld %lld must be >= max_new %d (max_length %d - prompt length %d)", who, c.topk ? "stats " : "", (long long)c.stats->ld,
+                    max_new, sp->max_length, longest);
+    if (!(c.checks & GC_LP_FIRST)) SVCHECK(check_logits_processors(c.lp, 0, who));
+    c.S0 = longest;
+    return 0;
+}
+
+static int generate_attempt(sv_engine* e, const GenCall& c);
+static int generate_retry(sv_engine* e, const GenCall& c) {
     if (e) { e->last_giveup = 0; e->stream_skip = 0; }
-    int rc = generate_attempt(e, dev_embeds, B, S0, lens, sp, outs, dev_out_tokens, n_generated, stream, G, lp, ts, tk);
+    int rc = generate_attempt(e, c);
     if (rc != 0 && e && e->cfg.exclusive_device == 2 && e->last_giveup && e->fused_off) {
         e->last_giveup = 0;      // (the second attempt runs every step again: the statistics columns are rewritten completely, like the capture slabs)
-        rc = generate_attempt(e, dev_embeds, B, S0, lens, sp, outs, dev_out_tokens, n_generated, stream, G, lp, ts, tk);
+        rc = generate_attempt(e, c);
     }
     if (e) e->stream_skip = 0;
     return rc;
@@ -315,20 +376,17 @@ static int generate_retry(sv_engine* e, const void* dev_embeds, int32_t B, int32
 // (the second attempt runs every step again: the capture slabs of sv_generate_ex are rewritten completely)
 extern "C" int sv_generate_ex(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const sv_sampling* sp,
                               const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
-    return generate_retry(e, dev_embeds, B, S0, nullptr, sp, outs, dev_out_tokens, n_generated, stream);
+    GenCall c{"sv_generate_ex", 0, dev_embeds, B, S0, nullptr, 1, sp, nullptr, outs, nullptr, nullptr, dev_out_tokens, n_generated, stream};
+    SVCHECK(check_gen_call(c));
+    return generate_retry(e, c);
 }
 // The ragged form: sequences of lengths host_lens[b], packed.  HF's padded-batch semantics: the budget counts from the longest prompt.
 extern "C" int sv_generate_ragged(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, const sv_sampling* sp,
                                   const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
-    // (the checks that need no engine come first: they are the same on a machine without a GPU)
-    if (!dev_embeds_packed || !host_lens || !sp || !dev_out_tokens || !n_generated) return fail(SV_EINVAL, "sv_generate_ragged: null argument");
-    if (B < 1) return fail(SV_EINVAL, "sv_generate_ragged: bad B=%d", B);
-    int longest = 0;
-    for (int b = 0; b < B; ++b) {
-        if (host_lens[b] < 1) return fail(SV_EINVAL, "sv_generate_ragged: length %d of sequence %d (must be >= 1)", host_lens[b], b);
-        longest = host_lens[b] > longest ? host_lens[b] : longest;
-    }
-    return generate_retry(e, dev_embeds_packed, B, longest, host_lens, sp, outs, dev_out_tokens, n_generated, stream);
+    GenCall c{"sv_generate_ragged", GC_ARGS | GC_LENS, dev_embeds_packed, B, 0, host_lens, 1, sp, nullptr, outs, nullptr, nullptr, dev_out_tokens,
+              n_generated, stream};
+    SVCHECK(check_gen_call(c));
+    return generate_retry(e, c);
 }
 // n_samples continuations of every prompt from ONE prompt pass.  host_lens == NULL: B prompts of S0 rows each; otherwise the ragged form (S0 unused).
 // Row b * n_samples + j of the outputs is sample j of prompt b: the rows, tokens and random draws of sv_generate / sv_generate_ragged over the
@@ -336,21 +394,10 @@ extern "C" int sv_generate_ragged(sv_engine* e, const void* dev_embeds_packed, i
 extern "C" int sv_generate_shared(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, int32_t S0, int32_t n_samples,
                                   const sv_sampling* sp, const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated,
                                   sv_stream stream) {
-    // (the checks that need no engine come first: they are the same on a machine without a GPU)
-    if (!dev_embeds_packed || !sp || !dev_out_tokens || !n_generated) return fail(SV_EINVAL, "sv_generate_shared: null argument");
-    if (B < 1) return fail(SV_EINVAL, "sv_generate_shared: bad B=%d", B);
-    if (n_samples < 1) return fail(SV_EINVAL, "sv_generate_shared: bad n_samples=%d (must be >= 1)", n_samples);
-    int longest = S0;
-    if (host_lens) {
-        longest = 0;
-        for (int b = 0; b < B; ++b) {
-            if (host_lens[b] < 1) return fail(SV_EINVAL, "sv_generate_shared: length %d of sequence %d (must be >= 1)", host_lens[b], b);
-            longest = host_lens[b] > longest ? host_lens[b] : longest;
-        }
-    } else if (S0 < 1) {
-        return fail(SV_EINVAL, "sv_generate_shared: bad S0=%d", S0);
-    }
-    return generate_retry(e, dev_embeds_packed, B, longest, host_lens, sp, outs, dev_out_tokens, n_generated, stream, n_samples);
+    GenCall c{"sv_generate_shared", GC_ARGS, dev_embeds_packed, B, S0, host_lens, n_samples, sp, nullptr, outs, nullptr, nullptr, dev_out_tokens,
+              n_generated, stream};
+    SVCHECK(check_gen_call(c));
+    return generate_retry(e, c);
 }
 extern "C" int sv_generate(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S0, const sv_sampling* sp,
                            int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
@@ -406,27 +453,11 @@ static int setup_processors(sv_engine* e, const sv_sampling* sp, const sv_logits
 extern "C" int sv_generate_processed(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, int32_t S0, int32_t n_samples,
                                      const sv_sampling* sp, const sv_logits_processors* lp, const sv_generate_outputs* outs,
                                      int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
-    const bool any = lp && (lp->no_repeat_ngram_size != 0 || lp->n_bad_words != 0 || lp->min_p != 0.f);
-    if (!any) return sv_generate_shared(e, dev_embeds_packed, B, host_lens, S0, n_samples, sp, outs, dev_out_tokens, n_generated, stream);
-    // (the checks that need no engine come first: they are the same on a machine without a GPU)
-    if (!dev_embeds_packed || !sp || !dev_out_tokens || !n_generated) return fail(SV_EINVAL, "sv_generate_processed: null argument");
-    SVCHECK(check_logits_processors(lp, 0, "sv_generate_processed"));
-    if (sp->num_beams > 1)
-        return fail(SV_EINVAL, "sv_generate_processed: no_repeat_ngram_size / bad words / min_p with num_beams %d is not built (beam rows reorder their histories)",
-                    sp->num_beams);
-    if (B < 1) return fail(SV_EINVAL, "sv_generate_processed: bad B=%d", B);
-    if (n_samples < 1) return fail(SV_EINVAL, "sv_generate_processed: bad n_samples=%d (must be >= 1)", n_samples);
-    int longest = S0;
-    if (host_lens) {
-        longest = 0;
-        for (int b = 0; b < B; ++b) {
-            if (host_lens[b] < 1) return fail(SV_EINVAL, "sv_generate_processed: length %d of sequence %d (must be >= 1)", host_lens[b], b);
-            longest = host_lens[b] > longest ? host_lens[b] : longest;
-        }
-    } else if (S0 < 1) {
-        return fail(SV_EINVAL, "sv_generate_processed: bad S0=%d", S0);
-    }
-    return generate_retry(e, dev_embeds_packed, B, longest, host_lens, sp, outs, dev_out_tokens, n_generated, stream, n_samples, lp);
+    if (!lp_any(lp)) return sv_generate_shared(e, dev_embeds_packed, B, host_lens, S0, n_samples, sp, outs, dev_out_tokens, n_generated, stream);
+    GenCall c{"sv_generate_processed", GC_ARGS | GC_LP_FIRST, dev_embeds_packed, B, S0, host_lens, n_samples, sp, lp, outs, nullptr, nullptr,
+              dev_out_tokens, n_generated, stream};
+    SVCHECK(check_gen_call(c));
+    return generate_retry(e, c);
 }
 
 // validation of sv_generate_ex's outputs, and the descriptor of the call's slabs (allocated on first use, rewritten on the call's stream in front
@@ -473,31 +504,10 @@ extern "C" int sv_generate_stats(sv_engine* e, const void* dev_embeds_packed, in
                                  const sv_sampling* sp, const sv_logits_processors* lp, const sv_generate_outputs* outs, const sv_token_stats* stats,
                                  int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
     if (!stats) return sv_generate_processed(e, dev_embeds_packed, B, host_lens, S0, n_samples, sp, lp, outs, dev_out_tokens, n_generated, stream);
-    // (the checks that need no engine come first: they are the same on a machine without a GPU)
-    if (!dev_embeds_packed || !sp || !dev_out_tokens || !n_generated) return fail(SV_EINVAL, "sv_generate_stats: null argument");
-    if (!stats->dev_logprob && !stats->dev_logprob_processed && !stats->dev_entropy)
-        return fail(SV_EINVAL, "sv_generate_stats: dev_logprob, dev_logprob_processed and dev_entropy are all NULL (pass stats = NULL for a call without statistics)");
-    if (sp->num_beams > 1)
-        return fail(SV_EINVAL, "sv_generate_stats: token statistics with num_beams %d are not built (beam search reports sequences_scores; beam rows reorder)",
-                    sp->num_beams);
-    if (B < 1) return fail(SV_EINVAL, "sv_generate_stats: bad B=%d", B);
-    if (n_samples < 1) return fail(SV_EINVAL, "sv_generate_stats: bad n_samples=%d (must be >= 1)", n_samples);
-    int longest = S0;
-    if (host_lens) {
-        longest = 0;
-        for (int b = 0; b < B; ++b) {
-            if (host_lens[b] < 1) return fail(SV_EINVAL, "sv_generate_stats: length %d of sequence %d (must be >= 1)", host_lens[b], b);
-            longest = host_lens[b] > longest ? host_lens[b] : longest;
-        }
-    } else if (S0 < 1) {
-        return fail(SV_EINVAL, "sv_generate_stats: bad S0=%d", S0);
-    }
-    if (sp->max_length - longest > 0 && stats->ld < (int64_t)(sp->max_length - longest))
-        return fail(SV_EINVAL, "sv_generate_stats: ld %lld must be >= max_new %d (max_length %d - prompt length %d)", (long long)stats->ld,
-                    sp->max_length - longest, sp->max_length, longest);
-    const bool any = lp && (lp->no_repeat_ngram_size != 0 || lp->n_bad_words != 0 || lp->min_p != 0.f);
-    if (any) SVCHECK(check_logits_processors(lp, 0, "sv_generate_stats"));
-    return generate_retry(e, dev_embeds_packed, B, longest, host_lens, sp, outs, dev_out_tokens, n_generated, stream, n_samples, any ? lp : nullptr, stats);
+    GenCall c{"sv_generate_stats", GC_ARGS, dev_embeds_packed, B, S0, host_lens, n_samples, sp, lp_any(lp) ? lp : nullptr, outs, stats, nullptr,
+              dev_out_tokens, n_generated, stream};
+    SVCHECK(check_gen_call(c));
+    return generate_retry(e, c);
 }
 
 // sv_generate_topk: the checks that need no engine (the same on a machine without a GPU); max_new <= 0 is refused later, by the call itself
@@ -536,30 +546,10 @@ extern "C" int sv_generate_topk(sv_engine* e, const void* dev_embeds_packed, int
                                 const sv_sampling* sp, const sv_logits_processors* lp, const sv_generate_outputs* outs, const sv_token_stats* stats,
                                 const sv_token_topk* topk, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream) {
     if (!topk) return sv_generate_stats(e, dev_embeds_packed, B, host_lens, S0, n_samples, sp, lp, outs, stats, dev_out_tokens, n_generated, stream);
-    // (the checks that need no engine come first: they are the same on a machine without a GPU)
-    if (!dev_embeds_packed || !sp || !dev_out_tokens || !n_generated) return fail(SV_EINVAL, "sv_generate_topk: null argument");
-    if (stats && !stats->dev_logprob && !stats->dev_logprob_processed && !stats->dev_entropy)
-        return fail(SV_EINVAL, "sv_generate_topk: dev_logprob, dev_logprob_processed and dev_entropy are all NULL (pass stats = NULL for a call without statistics)");
-    if (B < 1) return fail(SV_EINVAL, "sv_generate_topk: bad B=%d", B);
-    if (n_samples < 1) return fail(SV_EINVAL, "sv_generate_topk: bad n_samples=%d (must be >= 1)", n_samples);
-    int longest = S0;
-    if (host_lens) {
-        longest = 0;
-        for (int b = 0; b < B; ++b) {
-            if (host_lens[b] < 1) return fail(SV_EINVAL, "sv_generate_topk: length %d of sequence %d (must be >= 1)", host_lens[b], b);
-            longest = host_lens[b] > longest ? host_lens[b] : longest;
-        }
-    } else if (S0 < 1) {
-        return fail(SV_EINVAL, "sv_generate_topk: bad S0=%d", S0);
-    }
-    SVCHECK(check_token_topk(sp, lp, topk, sp->max_length - longest));
-    if (stats && sp->max_length - longest > 0 && stats->ld < (int64_t)(sp->max_length - longest))
-        return fail(SV_EINVAL, "sv_generate_topk: stats ld %lld must be >= max_new %d (max_length %d - prompt length %d)", (long long)stats->ld,
-                    sp->max_length - longest, sp->max_length, longest);
-    const bool any = lp && (lp->no_repeat_ngram_size != 0 || lp->n_bad_words != 0 || lp->min_p != 0.f);
-    if (any) SVCHECK(check_logits_processors(lp, 0, "sv_generate_topk"));
-    return generate_retry(e, dev_embeds_packed, B, longest, host_lens, sp, outs, dev_out_tokens, n_generated, stream, n_samples, any ? lp : nullptr, stats,
-                          topk);
+    GenCall c{"sv_generate_topk", GC_ARGS, dev_embeds_packed, B, S0, host_lens, n_samples, sp, lp_any(lp) ? lp : nullptr, outs, stats, topk,
+              dev_out_tokens, n_generated, stream};
+    SVCHECK(check_gen_call(c));
+    return generate_retry(e, c);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -588,8 +578,7 @@ static int shared_prefill_fork(sv_engine* e, const void* dev_embeds, int B, int 
     if (!dev_embeds) return fail(SV_EINVAL, "sv_generate_shared: null inputs_embeds");
     if (S0 < 1 || S0 > c.max_seq_len) return fail(SV_EINVAL, "sv_generate_shared: S0=%d out of range (max_seq_len %d)", S0, c.max_seq_len);
     SVCHECK(ensure_fork_buffers(e));
-    e->free_pages.clear();
-    for (int p = e->num_pages - 1; p >= 0; --p) e->free_pages.push_back(p);
+    reset_free_pages(e);
     if (e->table_pending) { HIPCHECK(hipEventSynchronize(e->table_ev)); e->table_pending = false; }      // (guards both pinned images)
     int32_t* table = e->h_table;                       // decode rows
     int32_t* pf = e->h_fork;                           // prompt pass: row b = the pages of decode row b * G
@@ -630,9 +619,14 @@ static int shared_prefill_fork(sv_engine* e, const void* dev_embeds, int B, int 
 }
 
 // lens != nullptr: the ragged form -- S0 is the longest prompt (the budget counts from it), sequence b has lens[b] rows
-static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t Bp, int32_t S0, const int32_t* lens, const sv_sampling* sp,
-                            const sv_generate_outputs* outs, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream, int G,
-                            const sv_logits_processors* lp, const sv_token_stats* ts, const sv_token_topk* tk) {
+static int generate_attempt(sv_engine* e, const GenCall& c) {
+    const void* dev_embeds = c.embeds;
+    const int32_t Bp = c.B, S0 = c.S0, G = c.n_samples;
+    const int32_t* lens = c.lens;
+    const sv_sampling* sp = c.sp;
+    const sv_generate_outputs* outs = c.outs;
+    int64_t* dev_out_tokens = c.dev_out_tokens;
+    int32_t* n_generated = c.n_generated;
     SVCHECK(check_ready(e));
     const bool shared = G > 1;
     if (shared && (Bp < 1 || (long long)Bp * G > e->cfg.max_batch))
@@ -654,20 +648,20 @@ static int generate_attempt(sv_engine* e, const void* dev_embeds, int32_t Bp, in
     std::lock_guard<std::mutex> lk(e->mu);
     HIPCHECK(hipSetDevice(e->cfg.device));
     // order the engine stream after everything already queued on the caller's stream
-    HIPCHECK(hipEventRecord(e->gen_event, (hipStream_t)stream));
+    HIPCHECK(hipEventRecord(e->gen_event, (hipStream_t)c.stream));
     hipStream_t st = e->gen_stream;
     HIPCHECK(hipStreamWaitEvent(st, e->gen_event, 0));
 
     SVCHECK(cb_guard(e, "sv_generate"));
     struct ProcOff { sv_engine* e; ~ProcOff() { e->ban_ngram = 0; e->ban_nwords = 0; e->minp_log = -INFINITY; } } proc_off{e};
-    SVCHECK(setup_processors(e, sp, lp, st));
+    SVCHECK(setup_processors(e, sp, c.lp, st));
     const bool ban = e->ban_ngram > 0 || e->ban_nwords > 0;
     struct CapOff { sv_engine* e; ~CapOff() { e->cap_on = false; } } cap_off{e};
     SVCHECK(setup_capture(e, sp, outs, sp->num_beams > 1 ? B * sp->num_beams : B, max_new, st));
     struct StatsOff { sv_engine* e; ~StatsOff() { e->ts_on = false; } } stats_off{e};
-    SVCHECK(setup_token_stats(e, sp, ts, B, max_new, st));
+    SVCHECK(setup_token_stats(e, sp, c.stats, B, max_new, st));
     struct TopkOff { sv_engine* e; ~TopkOff() { e->tk_on = false; } } topk_off{e};
-    SVCHECK(setup_token_topk(e, sp, tk, B, max_new, st));
+    SVCHECK(setup_token_topk(e, sp, c.topk, B, max_new, st));
     if (sp->num_beams > 1) {
         if (sp->on_tokens) return fail(SV_EINVAL, "streaming is not supported with beam search (hypotheses are only final at the end; HF refuses too)");
         if (sp->n_stop > 0 && !sp->stop_ids) return fail(SV_EINVAL, "n_stop > 0 but stop_ids is null");

@@ -278,7 +278,8 @@ int capture_steps(hipStream_t st, int copies, const std::function<void()>& one_s
 void prof_mark(sv_engine* e, int kind, hipStream_t st);
 int attn_max_splits_of(int max_batch, int nkv, int num_cus);
 int attn_groups_per_block_of(int max_batch, int nkv, int num_cus);
-int assign_pages(sv_engine* e, int B, int total_len, hipStream_t st);
+void reset_free_pages(sv_engine* e);      // every page of the pool is free again, lowest page handed out first
+int assign_pages(sv_engine* e, int B, int total_len, hipStream_t st);      // assign_pages_ragged without lengths: total_len tokens per sequence
 // rows per lm_head chunk of sv_forward_logprobs: a multiple of 256 (the big-M tile height: a chunk boundary never cuts a tile); 4096 rows x Vpad ~ 49.2 k
 // bf16 = 403 MB at StarVector's vocabulary -- the fastest of 512 / 1024 / 2048 / 4096 measured (profiles/score_logprobs.md; DESIGN.md "Scoring without logits")
 #define SV_SCORE_CHUNK_ROWS 4096

@@ -408,32 +408,35 @@ class HipEngine:
         ``top_k`` = k in 1..32 (sv_forward_topk) returns a ``TokenTopLogprobs``, which also holds ``top_token_ids`` / ``top_logprobs`` [B, n, k] -- the k most likely ids of every
         position, best first, equal logits by ascending id, and their log-probs; the slot holding the target equals ``logprobs`` bit for bit --
         and ``token_ranks`` [B, n], 1 + the number of ids with a larger logit than the target (0 where the target is -100)."""
-        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 0 <= top_k <= TOPK_MAX:
-            raise ValueError(f"top_k must be an int in 0..{TOPK_MAX}, got {top_k!r}")
         x = _need(inputs_embeds, torch.bfloat16, "inputs_embeds")
         B, S, D = x.shape
         if D != self.cfg.hidden:
             raise ValueError("inputs_embeds hidden size mismatch")
         n = int(num_logits_to_keep) if num_logits_to_keep and num_logits_to_keep > 0 else S
-        if tuple(targets.shape) != (B, n):
-            raise ValueError(f"targets must be [B, n] = [{B}, {n}], got {tuple(targets.shape)}")
+        t, res = self._score_outputs(x, targets, (B, n), "[B, n]", entropy, argmax, top_k)
+        if top_k:
+            check(self.lib.sv_forward_topk(self._h, _ptr(x), B, S, n, _ptr(t), float(temperature), *map(_ptr, res[:4]), top_k,
+                                           *map(_ptr, res[4:]), _stream()), "sv_forward_topk")
+        else:
+            check(self.lib.sv_forward_logprobs(self._h, _ptr(x), B, S, n, _ptr(t), float(temperature), *map(_ptr, res), _stream()),
+                  "sv_forward_logprobs")
+        return res
+
+    @staticmethod
+    def _score_outputs(x, targets, shape, what, entropy, argmax, top_k):
+        """What `forward_logprobs` and `forward_logprobs_ragged` share: the ``top_k`` and ``targets`` checks, the int32 targets and the result
+        tuple of empty output tensors of `shape` ([B, n] or [sum(keep)]; the lists one dimension more) -- a ``TokenTopLogprobs`` with ``top_k``."""
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 0 <= top_k <= TOPK_MAX:
+            raise ValueError(f"top_k must be an int in 0..{TOPK_MAX}, got {top_k!r}")
+        if tuple(targets.shape) != tuple(shape):
+            raise ValueError(f"targets must be {what} = {list(shape)}, got {tuple(targets.shape)}")
         if targets.dtype not in (torch.int32, torch.int64):
             raise ValueError(f"targets must be int32 or int64, got {targets.dtype}")
-        t = _need(targets.to(torch.int32), torch.int32, "targets")
-        lp = torch.empty(B, n, dtype=torch.float32, device=x.device)
-        lse = torch.empty(B, n, dtype=torch.float32, device=x.device)
-        ent = torch.empty(B, n, dtype=torch.float32, device=x.device) if entropy else None
-        am = torch.empty(B, n, dtype=torch.int32, device=x.device) if argmax else None
+        new = lambda dtype, *more: torch.empty(*shape, *more, dtype=dtype, device=x.device)
+        res = TokenLogprobs(new(torch.float32), new(torch.float32), new(torch.float32) if entropy else None, new(torch.int32) if argmax else None)
         if top_k:
-            ids = torch.empty(B, n, top_k, dtype=torch.int32, device=x.device)
-            tlp = torch.empty(B, n, top_k, dtype=torch.float32, device=x.device)
-            rank = torch.empty(B, n, dtype=torch.int32, device=x.device)
-            check(self.lib.sv_forward_topk(self._h, _ptr(x), B, S, n, _ptr(t), float(temperature), _ptr(lp), _ptr(lse), _ptr(ent), _ptr(am),
-                                           top_k, _ptr(ids), _ptr(tlp), _ptr(rank), _stream()), "sv_forward_topk")
-            return TokenTopLogprobs(lp, lse, ent, am, ids, tlp, rank)
-        check(self.lib.sv_forward_logprobs(self._h, _ptr(x), B, S, n, _ptr(t), float(temperature), _ptr(lp), _ptr(lse), _ptr(ent),
-                                           _ptr(am), _stream()), "sv_forward_logprobs")
-        return TokenLogprobs(lp, lse, ent, am)
+            res = TokenTopLogprobs(*res, new(torch.int32, top_k), new(torch.float32, top_k), new(torch.int32))
+        return _need(targets.to(torch.int32), torch.int32, "targets"), res
 
     def forward_logprobs_ragged(self, embeds, targets, keep, lengths=None, temperature: float = 1.0, entropy: bool = False,
                                 argmax: bool = False, top_k: int = 0):
@@ -442,31 +445,15 @@ class HipEngine:
         that are scored; targets: integer [sum(keep)], each sequence's kept rows back to back in sequence order, -100 = ignore.  Returns
         the result types of `forward_logprobs` with packed tensors ([sum(keep)], lists [sum(keep), k]).  Every sequence's slice holds the
         bits of `forward_logprobs(x_b[None], targets_b[None], keep[b], ...)` on that sequence alone, whatever shares the call with it."""
-        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 0 <= top_k <= TOPK_MAX:
-            raise ValueError(f"top_k must be an int in 0..{TOPK_MAX}, got {top_k!r}")
         x, arr, lens = self._packed(embeds, lengths)
         keep = [int(v) for v in keep]
         if len(keep) != len(lens) or any(not 1 <= k <= n for k, n in zip(keep, lens)):
             raise ValueError(f"keep {keep} must hold one count in 1..length for each of the lengths {lens}")
-        n = sum(keep)
-        if tuple(targets.shape) != (n,):
-            raise ValueError(f"targets must be [sum(keep)] = [{n}], got {tuple(targets.shape)}")
-        if targets.dtype not in (torch.int32, torch.int64):
-            raise ValueError(f"targets must be int32 or int64, got {targets.dtype}")
-        t = _need(targets.to(torch.int32), torch.int32, "targets")
-        lp = torch.empty(n, dtype=torch.float32, device=x.device)
-        lse = torch.empty(n, dtype=torch.float32, device=x.device)
-        ent = torch.empty(n, dtype=torch.float32, device=x.device) if entropy else None
-        am = torch.empty(n, dtype=torch.int32, device=x.device) if argmax else None
-        ids = torch.empty(n, top_k, dtype=torch.int32, device=x.device) if top_k else None
-        tlp = torch.empty(n, top_k, dtype=torch.float32, device=x.device) if top_k else None
-        rank = torch.empty(n, dtype=torch.int32, device=x.device) if top_k else None
+        t, res = self._score_outputs(x, targets, (sum(keep),), "[sum(keep)]", entropy, argmax, top_k)
+        lists = res[4:] if top_k else (None, None, None)
         check(self.lib.sv_forward_logprobs_ragged(self._h, _ptr(x), len(lens), arr, (C.c_int32 * len(keep))(*keep), _ptr(t), float(temperature),
-                                                  _ptr(lp), _ptr(lse), _ptr(ent), _ptr(am), top_k, _ptr(ids), _ptr(tlp), _ptr(rank), _stream()),
-              "sv_forward_logprobs_ragged")
-        if top_k:
-            return TokenTopLogprobs(lp, lse, ent, am, ids, tlp, rank)
-        return TokenLogprobs(lp, lse, ent, am)
+                                                  *map(_ptr, res[:4]), top_k, *map(_ptr, lists), _stream()), "sv_forward_logprobs_ragged")
+        return res
 
     def set_score_chunk_rows(self, rows: int) -> None:
         """Rows per lm_head chunk of `forward_logprobs` (a multiple of 256; 0 = default).  Test surface: the outputs do not depend on it."""
@@ -561,21 +548,8 @@ class HipEngine:
             sp.on_tokens = C.cast(cb, C.c_void_p)
         out = torch.empty(B, max_new, dtype=torch.int64, device=x.device)
         n = C.c_int32(0)
-        if scores_out is None and logits_out is None and not return_outputs and not token_stats and tk_req is None:
-            if lp is not None:
-                check(self.lib.sv_generate_processed(self._h, _ptr(x), n_prompts, lens_arr, S0, G, C.byref(sp), C.byref(lp), None, _ptr(out),
-                                                     C.byref(n), _stream()), "sv_generate_processed")
-            elif G > 1:
-                check(self.lib.sv_generate_shared(self._h, _ptr(x), n_prompts, lens_arr, S0, G, C.byref(sp), None, _ptr(out), C.byref(n), _stream()),
-                      "sv_generate_shared")
-            elif lens_arr is not None:
-                check(self.lib.sv_generate_ragged(self._h, _ptr(x), B, lens_arr, C.byref(sp), None, _ptr(out), C.byref(n), _stream()),
-                      "sv_generate_ragged")
-            else:
-                check(self.lib.sv_generate(self._h, _ptr(x), B, S0, C.byref(sp), _ptr(out), C.byref(n), _stream()), "sv_generate")
-            if cb_errors:
-                raise cb_errors[0]
-            return out[:, : n.value]
+        # a call that asks for nothing beyond the tokens passes no sv_generate_outputs (and takes no beam-search host buffers)
+        need_outs = not (scores_out is None and logits_out is None and not return_outputs and not token_stats and tk_req is None)
         rows = B * int(num_beams) if int(num_beams) > 1 else B
         outs = _lib.SvGenerateOutputs()
         ld = None
@@ -592,13 +566,13 @@ class HipEngine:
             ld = t.shape[2]
             setattr(outs, "dev_scores" if name == "scores_out" else "dev_logits", _ptr(t))
         outs.ld = int(ld or 0)
-        beam = int(num_beams) > 1
+        beam = need_outs and int(num_beams) > 1
         seq_scores = (C.c_float * B)() if beam else None
         beam_idx = (C.c_int64 * (B * max_new))() if beam else None
         if beam:
             outs.host_sequences_scores = C.cast(seq_scores, C.POINTER(C.c_float))
             outs.host_beam_indices = C.cast(beam_idx, C.POINTER(C.c_int64))
-        stats, ts, topk = None, None, None
+        stats, ts, topk, tk = None, None, None, None
         if token_stats:
             names = TOKEN_STATS if token_stats is True else tuple(token_stats)
             if not names or any(k not in TOKEN_STATS for k in names):
@@ -612,24 +586,25 @@ class HipEngine:
             if want_rank:
                 topk["token_ranks"] = torch.empty(B, max_new, dtype=torch.int32, device=x.device)
             tk = _lib.SvTokenTopk(k, source, _ptr(topk["top_token_ids"]), _ptr(topk["top_logprobs"]), _ptr(topk.get("token_ranks")), max_new)
-            check(self.lib.sv_generate_topk(self._h, _ptr(x), n_prompts, lens_arr, S0, G, C.byref(sp), C.byref(lp) if lp is not None else None,
-                                            C.byref(outs), C.byref(ts) if ts is not None else None, C.byref(tk), _ptr(out), C.byref(n), _stream()),
-                  "sv_generate_topk")
-        elif token_stats:
-            check(self.lib.sv_generate_stats(self._h, _ptr(x), n_prompts, lens_arr, S0, G, C.byref(sp), C.byref(lp) if lp is not None else None,
-                                             C.byref(outs), C.byref(ts), _ptr(out), C.byref(n), _stream()), "sv_generate_stats")
+        # the entry point is the first whose argument the call has: each takes the arguments of the one below it and one more
+        ref = lambda s: C.byref(s) if s is not None else None
+        outs = outs if need_outs else None
+        group = (n_prompts, lens_arr, S0, G, C.byref(sp))
+        if tk is not None:
+            name, args = "sv_generate_topk", group + (ref(lp), ref(outs), ref(ts), C.byref(tk))
+        elif ts is not None:
+            name, args = "sv_generate_stats", group + (ref(lp), ref(outs), C.byref(ts))
         elif lp is not None:
-            check(self.lib.sv_generate_processed(self._h, _ptr(x), n_prompts, lens_arr, S0, G, C.byref(sp), C.byref(lp), C.byref(outs), _ptr(out),
-                                                 C.byref(n), _stream()), "sv_generate_processed")
+            name, args = "sv_generate_processed", group + (C.byref(lp), ref(outs))
         elif G > 1:
-            check(self.lib.sv_generate_shared(self._h, _ptr(x), n_prompts, lens_arr, S0, G, C.byref(sp), C.byref(outs), _ptr(out), C.byref(n),
-                                              _stream()), "sv_generate_shared")
+            name, args = "sv_generate_shared", group + (ref(outs),)
         elif lens_arr is not None:
-            check(self.lib.sv_generate_ragged(self._h, _ptr(x), B, lens_arr, C.byref(sp), C.byref(outs), _ptr(out), C.byref(n), _stream()),
-                  "sv_generate_ragged")
+            name, args = "sv_generate_ragged", (B, lens_arr, C.byref(sp), ref(outs))
+        elif need_outs:
+            name, args = "sv_generate_ex", (B, S0, C.byref(sp), ref(outs))
         else:
-            check(self.lib.sv_generate_ex(self._h, _ptr(x), B, S0, C.byref(sp), C.byref(outs), _ptr(out), C.byref(n), _stream()),
-                  "sv_generate_ex")
+            name, args = "sv_generate", (B, S0, C.byref(sp))
+        check(getattr(self.lib, name)(self._h, _ptr(x), *args, _ptr(out), C.byref(n), _stream()), name)
         if cb_errors:
             raise cb_errors[0]
         L = n.value
