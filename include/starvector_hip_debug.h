@@ -151,7 +151,10 @@ int  sv_debug_prompt_passes(sv_engine* e, int64_t* out);
  *   sv_debug_kv_load     dev_kv bf16 [B][S][2*n_kv*head_dim] (k heads | v heads, K as cached = after RoPE) -> pages of `layer`;
  *                        positions[b] = S for every row, or dev_lens[b] (int32 [B], <= S; NULL = S): a ragged batch
  *   sv_debug_attn_decode dev_qkv_f32 fp32 [B][n_head*head_dim + 2*n_kv*head_dim] (the new token's c_attn output, before RoPE) ->
- *                        dev_out bf16 [B][n_head*head_dim]; appends the new K/V row at positions[b]; advance != 0: positions += 1 */
+ *                        dev_out bf16 [B][n_head*head_dim]; appends the new K/V row at positions[b]; advance != 0: positions += 1
+ *   sv_debug_attn_decode_slabs  the same launch fed as a decode step feeds it: dev_slabs_f32 fp32 [splitk][B][QKV], the split-K slabs of
+ *                        the c_attn GEMM (splitk 1, 2, 4 or 8), and dev_bias bf16 [QKV] (NULL = zero); the kernel sums the slabs in slab
+ *                        order in fp32, then adds the bias */
 /*   sv_debug_mlp_trace   (engine created with SV_MLP_TRACE=1) 100 MHz wall-clock stamps of the fused MLP launch (SV_EXP_MLP_FUSED_FORCE) of the
  *                        middle layer of the last decode step: host_out [blocks][8] = {start, c_fc loop done, tile published, slice
  *                        complete, end, XCC id, 0, 0}; returns the block count or a negative error code */
@@ -177,6 +180,8 @@ int  sv_debug_kv_load(sv_engine* e, int32_t layer, const void* dev_kv, int32_t B
                       sv_stream stream);
 int  sv_debug_attn_decode(sv_engine* e, int32_t layer, const float* dev_qkv_f32, int32_t B, void* dev_out, int32_t advance,
                           sv_stream stream);
+int  sv_debug_attn_decode_slabs(sv_engine* e, int32_t layer, const float* dev_slabs_f32, int32_t splitk, const void* dev_bias, int32_t B,
+                                void* dev_out, int32_t advance, sv_stream stream);
 
 /* HIP-event timing of one decode step by kernel class, on the cache state left by the last
  * sv_generate / sv_prefill (bench.py roofline leg).  out: 10 doubles, [2k] = ms per step in class k

@@ -204,6 +204,7 @@ DEBUG_PROTOTYPES = {
     "sv_debug_gemm_trace": (_I, [_I, _I, _I, _I, _I, C.POINTER(C.c_int64), _I]),
     "sv_debug_kv_load": (_I, [_P, _I, _P, _I, _I, _P, _P]),
     "sv_debug_attn_decode": (_I, [_P, _I, _P, _I, _P, _I, _P]),
+    "sv_debug_attn_decode_slabs": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P]),
     "sv_debug_decode_plan": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     "sv_profile_decode_step": (_I, [_P, _I, _I, C.POINTER(C.c_double), _P]),
     "sv_profile_ttft": (_I, [_P, _P, _I, _P, _I, _I, C.POINTER(C.c_double), _P]),

@@ -434,36 +434,121 @@ __device__ __forceinline__ unsigned xcc_id() {
     return x & 15u;
 }
 
-// Leading scalar parameters: what the first loads (position, block table, KV fragments, c_attn slabs) need; they arrive
-// preloaded in SGPRs with the dispatch (see gemm_skinny_kernel), the struct is read later.
-struct AttnDecodeKernarg { const int32_t* positions; const int32_t* block_table; char* pool_layer; const float* ws; size_t kv_head_stride;
-                           int max_pages, n_kv, max_splits, window, gpb; AttnDecodeArgs p; };     // the kernarg segment
-template <int D>
-__global__ __launch_bounds__(AD_WAVES * 64) void attn_decode_kernel(const int32_t* positions_, const int32_t* block_table_, char* pool_layer_,
-                                                                     const float* ws_, size_t kv_head_stride_, int max_pages_, int n_kv_,
-                                                                     int max_splits_, int window_, int gpb_, AttnDecodeArgs p_unused) {
+// Leading scalar parameters: what the first loads (c_attn slabs and bias, position, block table) need; they arrive preloaded in
+// SGPRs with the dispatch (see gemm_skinny_kernel): 14 SGPRs are preloaded, so the small shape fields travel packed --
+//   geom = n_kv | max_splits << 8 | groups per block << 16 | splitk << 24,   rows_heads = rows_ws | H << 16
+// -- what only the KV request needs (kv_head_stride, window) follows as ordinary parameters (their scalar load has the position's
+// round trip to land in), and the struct is read later.
+struct AttnDecodeKernarg { const float* ws; const bf16_t* bias; const int32_t* positions; const int32_t* block_table; char* pool_layer;
+                           int max_pages; unsigned geom; int ldws; unsigned rows_heads; size_t kv_head_stride; int window;
+                           AttnDecodeArgs p; };     // the kernarg segment
+// NS: the slabs a thread requests (4 or 8, the launcher's choice for splitk <= 4 / <= 8): a compile-time count of loads in flight.
+template <int D, int NS>
+__global__ __launch_bounds__(AD_WAVES * 64) void attn_decode_kernel(const float* ws_, const bf16_t* bias_, const int32_t* positions_, const int32_t* block_table_,
+                                                                     char* pool_layer_, int max_pages_, unsigned geom_, int ldws_, unsigned rows_heads_,
+                                                                     size_t kv_head_stride_, int window_, AttnDecodeArgs p_unused) {
     constexpr int NKS = D / 32;          // k-steps of S^T (over head_dim)
     constexpr int NDV = D / 16;          // dv tiles of O^T
     constexpr int PART = 32 + 16 * D;    // floats per partial: m[16], l[16], O[16][D]
     const long long t_start = wall_clock64();         // 100 MHz; stored only when the trace buffer is on (tools/attn_trace.py)
+    const int n_kv_ = (int)(geom_ & 255u), max_splits_ = (int)((geom_ >> 8) & 255u), gpb_ = (int)((geom_ >> 16) & 255u);
+    const int splitk_ = (int)(geom_ >> 24), rows_ws_ = (int)(rows_heads_ & 0xffffu);
+    const int H = (int)(rows_heads_ >> 16);  // all query heads of the model
     const int bx = blockIdx.x;               // (sequence, KV head)
     const int b = bx / n_kv_;
     const int kvh = bx % n_kv_;
     const int split = blockIdx.y;
-    // the first 64 entries of this sequence's block-table row (4096 tokens) are requested together with the position: the
-    // page of a key group is then a cross-lane read instead of a second dependent global round trip (position -> table -> KV)
+    const int G = H / n_kv_;                 // query heads sharing this KV head (<= 16): the MFMA N side
+    const int HD = G * D;                    // output columns owned by this block
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // the position is a block-uniform value: a scalar load, so that no wave's wait for it is a wait for its vector loads
+    const int pos = *reinterpret_cast<const int32_t __attribute__((address_space(4)))*>(reinterpret_cast<uintptr_t>(positions_ + b));
+
+    // q / k_new / v_new of this sequence: the fp32 split-K slabs of the c_attn GEMM, summed in slab order + bias.  Nothing in a slab
+    // address depends on the position, so the requests go out at block start -- from waves 4-7 only: the upper half of the block owns no
+    // key group while the block has at most 4 (up to 1024 keys at 8 splits), and the lower half's memory queue holds the block table and
+    // the KV stream and nothing else (a wave's loads return in order: a slab value requested behind 16 KiB of KV arrives behind it).
+    // Thread t of the 256 takes the q quads t, t + 256, ... (16 * D / 4 of them) and the column t of k_new | v_new; every load is in
+    // flight before the first add: one memory round trip.  A slab index above splitk repeats the last slab (the same line again), so
+    // that the number of loads in flight is the compile-time NS and the waits below are counted.
+    constexpr int SLT = (AD_WAVES / 2) * 64;     // slab threads
+    constexpr int QQ = 16 * D / 4 / SLT;         // q quads per slab thread (2 at head_dim 128, 1 at 64)
+    static_assert(QQ * SLT * 4 == 16 * D && 2 * D <= SLT && (2 * D & (2 * D - 1)) == 0, "slab work does not tile the upper half of the block");
+    const bool slab_wave = wave >= AD_WAVES / 2;
+    const unsigned st = (unsigned)tid & (SLT - 1);
+    f32x4 sq[QQ][NS];
+    float sk[NS];
+    uint2 bq[QQ];
+    unsigned bk = 0;
+    const unsigned kc = st & (2 * D - 1);        // column of k_new | v_new (head_dim 64: the threads above 2 * D repeat and do not write)
+    const unsigned kcol = (unsigned)(H * D + kvh * D) + (kc < D ? 0u : (unsigned)(n_kv_ * D)) + (kc & (D - 1));
+    auto qcol = [&](int i) -> unsigned {         // column of the c_attn output of q quad i (rows >= G of the tile are zero: row 0's address, unused)
+        const unsigned n = (st + i * SLT) * 4, r = n / D;
+        return (unsigned)(kvh * G * D) + (r < (unsigned)G ? r * D : 0u) + n % D;
+    };
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    bf16_t* q_s = reinterpret_cast<bf16_t*>(smem);                       // [16][D]
+    bf16_t* kv_new = q_s + 16 * D;                                       // [2][D]
+    float* m_s = reinterpret_cast<float*>(kv_new + 2 * D);               // [AD_WAVES][16]
+    float* l_s = m_s + AD_WAVES * 16;                                    // [AD_WAVES][16]
+    float* O_s = l_s + AD_WAVES * 16;                                    // [AD_WAVES][16][D]
+    int* flag_s = reinterpret_cast<int*>(O_s + AD_WAVES * 16 * D);       // [4]
+    auto slab_issue = [&]() {
+        const unsigned slab = (unsigned)rows_ws_ * (unsigned)ldws_;       // floats per slab (the whole buffer is far below 2^32 bytes)
+#pragma unroll
+        for (int sp = 0; sp < NS; ++sp) {
+            const float* row = ws_ + ((unsigned)(sp < splitk_ ? sp : splitk_ - 1) * slab + (unsigned)b * (unsigned)ldws_);
+#pragma unroll
+            for (int i = 0; i < QQ; ++i) sq[i][sp] = *reinterpret_cast<const f32x4*>(row + qcol(i));
+            sk[sp] = row[kcol];
+        }
+#pragma unroll
+        for (int i = 0; i < QQ; ++i) bq[i] = *reinterpret_cast<const uint2*>(bias_ + qcol(i));
+        bk = bias_[kcol];
+    };
+    // the slab values of this thread, summed in slab order (0 .. splitk - 1, then the bias) -> LDS (bf16)
+    // (the empty asm statements pin each value's first use -- and with it the wait for its load -- to this place: left alone, the
+    //  compiler moves the first adds up to the requests, and a wait with them)
+    auto slab_sum = [&]() {
+#pragma unroll
+        for (int i = 0; i < QQ; ++i) {
+            f32x4 a = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int sp = 0; sp < NS; ++sp) {
+                asm volatile("" : "+v"(sq[i][sp]));
+                if (sp < splitk_) a += sq[i][sp];
+            }
+            asm volatile("" : "+v"(bq[i].x), "+v"(bq[i].y));
+            const unsigned n = (st + i * SLT) * 4;           // LDS slot: q rows [0, 16 * D) (rows >= G are zero)
+            const unsigned live = n / D < (unsigned)G ? 0xffffffffu : 0u;
+            uint2 o;
+            o.x = pack2bf(a[0] + __uint_as_float(bq[i].x << 16), a[1] + __uint_as_float(bq[i].x & 0xffff0000u)) & live;
+            o.y = pack2bf(a[2] + __uint_as_float(bq[i].y << 16), a[3] + __uint_as_float(bq[i].y & 0xffff0000u)) & live;
+            *reinterpret_cast<uint2*>(q_s + n) = o;
+        }
+        float a = 0.f;
+#pragma unroll
+        for (int sp = 0; sp < NS; ++sp) {
+            asm volatile("" : "+v"(sk[sp]));
+            if (sp < splitk_) a += sk[sp];
+        }
+        asm volatile("" : "+v"(bk));
+        if (2 * D == SLT || st < 2 * D) kv_new[kc] = f2bf(a + __uint_as_float(bk << 16));          // k_new [0, D) | v_new [D, 2 * D)
+    };
+
     const int32_t* table = block_table_ + (size_t)b * max_pages_;
-    const int tl = threadIdx.x & 63;
-    const int tpre = tl < max_pages_ ? table[tl] : 0;
-    const int pos = positions_[b];
-    const int L = pos + 1;
-    const int ngroups = (L + 31) >> 5;
-    // StarCoder2 sliding window: only keys win0 <= j <= pos are visible; whole groups (and pages) below are skipped
-    const int win0 = (window_ > 0 && L > window_) ? L - window_ : 0;
-    const int g0 = win0 >> 5;
-    int act = (ngroups - g0 + gpb_ - 1) / gpb_;         // gpb_: 32-key groups a block takes before another context split joins
-    act = act > max_splits_ ? max_splits_ : act;      // host cap: B * act <= #CUs (one block per CU) and <= AD_SPLIT
-    act = act < 1 ? 1 : act;
+    const int page_bytes = kv_page_bytes(D);
+    char* pool = nullptr;
+    int tpre = 0;
+    auto page_of = [&](int grp) -> int {                   // grp is wave-uniform
+        const int pi = grp >> 1;                           // 64-token pages, 32-key groups
+        return pi < 64 ? __builtin_amdgcn_readlane(tpre, pi) : table[pi];
+    };
+    int L = 0, ngroups = 0, win0 = 0, g0 = 0, act = 1, stride = AD_WAVES, g = 0;
+    KvFrags<D> fa, fb;
+    long long t_kvreq = 0;                             // position + table landed, first KV group requested
+    AttnDecodeArgs p;
     // AttnDecodeArgs::poison: every block of the launch stores 16 bytes per thread of the pattern -- the inactive splits before they
     // leave, the active ones once their KV stream is in flight (the arguments are read late in both cases: off the critical path)
     // (poison2 = the next layer's LayerNorm output buffer: only ever touched with write-through stores and L1-bypassing loads -- by this
@@ -483,69 +568,65 @@ __global__ __launch_bounds__(AD_WAVES * 64) void attn_decode_kernel(const int32_
             if (off < q.poison2_bytes) poison2_store(q, off);
         }
     };
-    if (split >= act) {
-        poison(sv_late_args<AttnDecodeArgs>(offsetof(AttnDecodeKernarg, p)));
-        return;
-    }
-
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    bf16_t* q_s = reinterpret_cast<bf16_t*>(smem);                       // [16][D]
-    bf16_t* kv_new = q_s + 16 * D;                                       // [2][D]
-    float* m_s = reinterpret_cast<float*>(kv_new + 2 * D);               // [AD_WAVES][16]
-    float* l_s = m_s + AD_WAVES * 16;                                    // [AD_WAVES][16]
-    float* O_s = l_s + AD_WAVES * 16;                                    // [AD_WAVES][16][D]
-    int* flag_s = reinterpret_cast<int*>(O_s + AD_WAVES * 16 * D);       // [4]
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    char* const pool = pool_layer_ + (size_t)kvh * kv_head_stride_;
-
-    const int page_bytes = kv_page_bytes(D);
-    auto page_of = [&](int grp) -> int {                   // grp is wave-uniform
-        const int pi = grp >> 1;                           // 64-token pages, 32-key groups
-        return pi < 64 ? __builtin_amdgcn_readlane(tpre, pi) : table[pi];
-    };
-    // the KV stream does not depend on q: request the first group before anything else
-    const int stride = act * AD_WAVES;
-    int g = g0 + split + act * wave;
-    KvFrags<D> fa, fb;
-    if (g < ngroups) load_group<D>(fa, pool, page_of(g), page_bytes, g, lane);
-    const long long t_kvreq = wall_clock64();          // position + table landed, first KV group requested
-
-    // the KV stream is in flight: now the rest of the arguments (common.h sv_late_args)
-    const AttnDecodeArgs p = sv_late_args<AttnDecodeArgs>(offsetof(AttnDecodeKernarg, p));
-    poison(p);
-    const int H = p.H;                       // all query heads of the model
-    const int G = H / n_kv_;                 // query heads sharing this KV head (<= 16): the MFMA N side
-    const int HD = G * D;                    // output columns owned by this block
-
-    // q / k_new / v_new of this sequence -> LDS (bf16): the fp32 split-K slabs of the c_attn GEMM, summed here in slab order + bias.
-    // 4 columns per thread and every load issued before the first add: one memory round trip.
-    for (int c4 = tid; c4 < (16 * D + 2 * D) / 4; c4 += AD_WAVES * 64) {
-        const int n = c4 * 4;                    // LDS slot: q rows [0,16*D) (rows >= G are zero), k_new, v_new
-        int col;                                 // column of the c_attn output: q heads | k heads | v heads
-        if (n < 16 * D) col = (n / D) < G ? (kvh * G + n / D) * D + n % D : -1;
-        else if (n < 17 * D) col = H * D + kvh * D + (n - 16 * D);
-        else col = H * D + p.n_kv * D + kvh * D + (n - 17 * D);
-        uint2 o = make_uint2(0u, 0u);
-        if (col >= 0) {
-            {
-                float4 acc4[8];
-                const uint2 bb = *reinterpret_cast<const uint2*>(p.bias + col);
-#pragma unroll
-                for (int sp = 0; sp < 8; ++sp)
-                    if (sp < p.splitk)
-                        acc4[sp] = *reinterpret_cast<const float4*>(ws_ + ((size_t)sp * p.rows_ws + b) * p.ldws + col);
-                float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-                for (int sp = 0; sp < 8; ++sp)
-                    if (sp < p.splitk) { a.x += acc4[sp].x; a.y += acc4[sp].y; a.z += acc4[sp].z; a.w += acc4[sp].w; }
-                o.x = pack2bf(a.x + __uint_as_float(bb.x << 16), a.y + __uint_as_float(bb.x & 0xffff0000u));
-                o.y = pack2bf(a.z + __uint_as_float(bb.y << 16), a.w + __uint_as_float(bb.y & 0xffff0000u));
-            }
+    // The front of the block up to the barrier, once per half of the block (SLAB: waves 4-7) -- two copies of the code, so that a wave's
+    // requests and the waits for them stand on ONE path: where the two halves share instructions behind a join, every wait is placed for
+    // the half with fewer loads in flight and becomes a wait for everything (the pattern stores stand inside for the same reason: behind
+    // the join, the registers they use count as targets of loads in flight).  False: an inactive split.
+    auto front = [&](auto slab_tag) -> bool {
+        constexpr bool SLAB = decltype(slab_tag)::value;
+        if constexpr (SLAB) slab_issue();
+        // the first 64 entries of this sequence's block-table row (4096 tokens) are requested with the position: the page of a key
+        // group is then a cross-lane read instead of a second dependent global round trip (position -> table -> KV).  Waves 0-3: their
+        // first request; waves 4-7: behind their slabs (they need it only once they own a key group)
+        // (no lane-dependent branch anywhere in this front: lanes past the row read its last entry, which no key group of theirs maps to.
+        //  With one, the compiler restructures the whole region, and its waits then count loads of paths that no wave can take)
+        tpre = table[lane < max_pages_ ? lane : max_pages_ - 1];
+        // (what arrives by scalar load -- position, KV head stride, window -- is first looked at here: the compiler shares the arithmetic of
+        //  the two copies in front of the branch otherwise, and its wait with it)
+        size_t kv_head_stride = kv_head_stride_;
+        int window = window_, posv = pos;
+        asm volatile("; first requests out" : "+s"(kv_head_stride), "+s"(window), "+s"(posv) : : "memory");
+        pool = pool_layer_ + (size_t)kvh * kv_head_stride;
+        L = posv + 1;
+        ngroups = (L + 31) >> 5;
+        // StarCoder2 sliding window: only keys win0 <= j <= pos are visible; whole groups (and pages) below are skipped
+        win0 = (window > 0 && L > window) ? L - window : 0;
+        g0 = win0 >> 5;
+        act = (ngroups - g0 + gpb_ - 1) / gpb_;           // gpb_: 32-key groups a block takes before another context split joins
+        act = act > max_splits_ ? max_splits_ : act;      // host cap: B * act <= #CUs (one block per CU) and <= AD_SPLIT
+        act = act < 1 ? 1 : act;
+        // an inactive split leaves as soon as the position has landed: its upper waves have slab requests in flight (lines that the
+        // active splits of the sequence read as well) and do not wait for them
+        if (split >= act) {
+            poison(sv_late_args<AttnDecodeArgs>(offsetof(AttnDecodeKernarg, p)));
+            return false;
         }
-        *reinterpret_cast<uint2*>(q_s + n) = o;
-    }
+        // the KV stream does not depend on q: waves 0-3 request their first group before anything else.  An upper wave that owns one
+        // (more than 4 groups in the block) needs its table entry, which was requested behind the slabs and returns behind them: its
+        // KV request goes out when the slabs are there, and the sum that follows waits for nothing.  The rest of the arguments
+        // (common.h sv_late_args) are requested once the KV stream is in flight.  The sum and the stores stand in both arms, in
+        // front of their join, so that no wait of theirs is placed for the arm with fewer loads in flight (the ISA of this front was
+        // read: between the KV request and the barrier no wave waits for a vector load).
+        stride = act * AD_WAVES;
+        g = g0 + split + act * wave;
+        if (g < ngroups) {
+            load_group<D>(fa, pool, page_of(g), page_bytes, g, lane);
+            t_kvreq = wall_clock64();
+            p = sv_late_args<AttnDecodeArgs>(offsetof(AttnDecodeKernarg, p));
+            if constexpr (SLAB) slab_sum();
+            poison(p);
+            asm volatile("; key group requested" ::: "memory");
+        } else {
+            t_kvreq = wall_clock64();
+            p = sv_late_args<AttnDecodeArgs>(offsetof(AttnDecodeKernarg, p));
+            if constexpr (SLAB) slab_sum();
+            poison(p);
+            asm volatile("; no key group" ::: "memory");
+        }
+        return true;
+    };
+    const bool active = slab_wave ? front(std::true_type{}) : front(std::false_type{});
+    if (!active) return;
     __syncthreads();
     if (p.rope_cos) {
         // rotary embedding of the G query rows and of k_new at position `pos` (rotate_half convention; the
@@ -832,12 +913,25 @@ static size_t attn_decode_smem(int D) {
 // dynamic LDS above the 64 KiB default needs an explicit opt-in.  Done once at engine creation (never
 // inside a stream capture)
 int init_attention_kernels() {
-    hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_decode_kernel<128>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_decode_smem(128));
-    if (r != hipSuccess) return (int)r;
-    r = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_decode_kernel<64>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_decode_smem(64));
-    return (int)r;
+    const void* k128[2] = {reinterpret_cast<const void*>(&attn_decode_kernel<128, 4>), reinterpret_cast<const void*>(&attn_decode_kernel<128, 8>)};
+    const void* k64[2] = {reinterpret_cast<const void*>(&attn_decode_kernel<64, 4>), reinterpret_cast<const void*>(&attn_decode_kernel<64, 8>)};
+    for (int i = 0; i < 2; ++i) {
+        hipError_t r = hipFuncSetAttribute(k128[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_decode_smem(128));
+        if (r != hipSuccess) return (int)r;
+        r = hipFuncSetAttribute(k64[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_decode_smem(64));
+        if (r != hipSuccess) return (int)r;
+    }
+    return 0;
+}
+
+template <int D, int NS>
+static void launch_attn_decode_as(const AttnDecodeArgs& a, dim3 grid, size_t smem, hipStream_t st) {
+    const int gpb = a.groups_per_block > 0 ? a.groups_per_block : AD_GROUPS_PER_BLOCK;
+    // the packed leading parameters (AttnDecodeKernarg): 8 bits each for n_kv, the split cap, the groups per block and splitk, 16 for rows_ws and H
+    const unsigned geom = (unsigned)a.n_kv | (unsigned)grid.y << 8 | (unsigned)gpb << 16 | (unsigned)(a.splitk < 1 ? 1 : a.splitk) << 24;
+    const unsigned rows_heads = (unsigned)a.rows_ws | (unsigned)a.H << 16;
+    attn_decode_kernel<D, NS><<<grid, AD_WAVES * 64, smem, st>>>(a.ws, a.bias, a.positions, a.block_table, a.pool_layer, a.max_pages, geom, a.ldws, rows_heads,
+                                                                  a.kv_head_stride, a.window, a);
 }
 
 void launch_attn_decode(const AttnDecodeArgs& a, hipStream_t st) {
@@ -845,13 +939,13 @@ void launch_attn_decode(const AttnDecodeArgs& a, hipStream_t st) {
     // grid.y = the engine's split cap, not AD_SPLIT: the splits above it never work, and dispatching 8-wave blocks that exit
     // at once is not free (B = 32: 256 of 512 blocks)
     dim3 grid(a.B * a.n_kv, a.max_splits < 1 ? 1 : (a.max_splits > AD_SPLIT ? AD_SPLIT : a.max_splits));
-    const int gpb = a.groups_per_block > 0 ? a.groups_per_block : AD_GROUPS_PER_BLOCK;
-    if (a.head_dim == 128)
-        attn_decode_kernel<128><<<grid, AD_WAVES * 64, smem, st>>>(a.positions, a.block_table, a.pool_layer, a.ws, a.kv_head_stride,
-                                                                    a.max_pages, a.n_kv, a.max_splits, a.window, gpb, a);
-    else
-        attn_decode_kernel<64><<<grid, AD_WAVES * 64, smem, st>>>(a.positions, a.block_table, a.pool_layer, a.ws, a.kv_head_stride,
-                                                                   a.max_pages, a.n_kv, a.max_splits, a.window, gpb, a);
+    if (a.head_dim == 128) {
+        if (a.splitk <= 4) launch_attn_decode_as<128, 4>(a, grid, smem, st);
+        else launch_attn_decode_as<128, 8>(a, grid, smem, st);
+    } else {
+        if (a.splitk <= 4) launch_attn_decode_as<64, 4>(a, grid, smem, st);
+        else launch_attn_decode_as<64, 8>(a, grid, smem, st);
+    }
 }
 
 // which XCD each block of a 1-D launch runs on (XCC_ID), with the footprint of the decode attention when asked: `lds_bytes` of dynamic

@@ -124,34 +124,52 @@ extern "C" int sv_debug_kv_load(sv_engine* e, int32_t layer, const void* dev_kv,
 // included, before RoPE); dev_out: bf16 [B][n_head*head_dim].  Runs attn_decode_kernel of `layer` exactly as a decode step does
 // (same grid, split cap, groups per block, window, RoPE tables; the new K/V row is appended to the cache at positions[b]);
 // advance != 0 steps positions[b] afterwards, so consecutive calls walk a sequence across page boundaries.
-extern "C" int sv_debug_attn_decode(sv_engine* e, int32_t layer, const float* dev_qkv_f32, int32_t B, void* dev_out, int32_t advance,
-                                    sv_stream stream) {
-    if (!e || !dev_qkv_f32 || !dev_out) return fail(SV_EINVAL, "sv_debug_attn_decode: null argument");
+// One body for the two entries: `splitk` slabs dev_slabs fp32 [splitk][B][QKV] and an optional bf16 bias [QKV] (nullptr: zero).
+static int debug_attn_decode(sv_engine* e, const char* who, int32_t layer, const float* dev_slabs, int32_t splitk, const void* dev_bias, int32_t B,
+                             void* dev_out, int32_t advance, sv_stream stream) {
+    if (!e || !dev_slabs || !dev_out) return fail(SV_EINVAL, "%s: null argument", who);
     const sv_config& c = e->cfg;
-    if (layer < 0 || layer >= c.n_layer) return fail(SV_EINVAL, "sv_debug_attn_decode: bad layer %d", layer);
+    if (layer < 0 || layer >= c.n_layer) return fail(SV_EINVAL, "%s: bad layer %d", who, layer);
+    if (splitk != 1 && splitk != 2 && splitk != 4 && splitk != 8) return fail(SV_EINVAL, "%s: splitk %d is not 1, 2, 4 or 8", who, splitk);
     std::lock_guard<std::mutex> lk(e->mu);
-    SVCHECK(cb_guard(e, "sv_debug_attn_decode"));
-    if (B != e->cached_B) return fail(SV_ESTATE, "sv_debug_attn_decode: B=%d but the cache holds %d sequences", B, e->cached_B);
+    SVCHECK(cb_guard(e, who));
+    if (B != e->cached_B) return fail(SV_ESTATE, "%s: B=%d but the cache holds %d sequences", who, B, e->cached_B);
     // the kernel appends the new K/V row at positions[b] and indexes the block table with it: repeated advancing calls must not walk
     // past the sequence's allocation
     if (e->dbg_pos_hi >= c.max_seq_len)
-        return fail(SV_EINVAL, "sv_debug_attn_decode: position %d would reach max_seq_len %d", e->dbg_pos_hi, c.max_seq_len);
+        return fail(SV_EINVAL, "%s: position %d would reach max_seq_len %d", who, e->dbg_pos_hi, c.max_seq_len);
     HIPCHECK(hipSetDevice(c.device));
     hipStream_t st = (hipStream_t)stream;
     TmpBufs tmp;
-    bf16_t* zero_bias;
-    SVCHECK(tmp.get(&zero_bias, (size_t)e->ldws));
-    HIPCHECK(hipMemsetAsync(zero_bias, 0, (size_t)e->ldws * sizeof(bf16_t), st));
-    HIPCHECK(hipMemcpy2DAsync(e->ws, (size_t)e->ldws * sizeof(float), dev_qkv_f32, (size_t)e->QKV * sizeof(float),
-                              (size_t)e->QKV * sizeof(float), B, hipMemcpyDeviceToDevice, st));
+    bf16_t* bias;
+    SVCHECK(tmp.get(&bias, (size_t)e->ldws));
+    HIPCHECK(hipMemsetAsync(bias, 0, (size_t)e->ldws * sizeof(bf16_t), st));
+    if (dev_bias) HIPCHECK(hipMemcpyAsync(bias, dev_bias, (size_t)e->QKV * sizeof(bf16_t), hipMemcpyDeviceToDevice, st));
+    // e->ws holds 8 slabs of rows_ws x ldws floats (sv_create): slab s of the caller lands where the c_attn GEMM's K slice s writes
+    const int rows_ws = ((B + 31) / 32) * 32;
+    for (int s = 0; s < splitk; ++s)
+        HIPCHECK(hipMemcpy2DAsync(e->ws + (size_t)s * rows_ws * e->ldws, (size_t)e->ldws * sizeof(float), dev_slabs + (size_t)s * B * e->QKV,
+                                  (size_t)e->QKV * sizeof(float), (size_t)e->QKV * sizeof(float), B, hipMemcpyDeviceToDevice, st));
     AttnDecodeArgs ad;
-    attn_decode_args(e, layer, B, e->ws, 1, zero_bias, e->xp_attn, ad);
+    attn_decode_args(e, layer, B, e->ws, splitk, bias, e->xp_attn, ad);
     launch_attn_decode(ad, st);
     unpack_rows(e->xp_attn, (bf16_t*)dev_out, c.n_head * e->dh, B, c.n_head * e->dh, st);
     if (advance) { add_i32(e->positions, 1, B, st); e->dbg_pos_hi += 1; }
     HIPCHECK(hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(st));          // `zero_bias` is freed on return
+    HIPCHECK(hipStreamSynchronize(st));          // `bias` is freed on return
     return 0;
+}
+
+extern "C" int sv_debug_attn_decode(sv_engine* e, int32_t layer, const float* dev_qkv_f32, int32_t B, void* dev_out, int32_t advance,
+                                    sv_stream stream) {
+    return debug_attn_decode(e, "sv_debug_attn_decode", layer, dev_qkv_f32, 1, nullptr, B, dev_out, advance, stream);
+}
+
+// The same launch fed as a decode step feeds it: dev_slabs_f32 fp32 [splitk][B][QKV] = the split-K slabs of the c_attn GEMM (splitk 1, 2, 4
+// or 8) and dev_bias bf16 [QKV] (NULL: zero); the kernel sums the slabs in slab order, then adds the bias.
+extern "C" int sv_debug_attn_decode_slabs(sv_engine* e, int32_t layer, const float* dev_slabs_f32, int32_t splitk, const void* dev_bias, int32_t B,
+                                          void* dev_out, int32_t advance, sv_stream stream) {
+    return debug_attn_decode(e, "sv_debug_attn_decode_slabs", layer, dev_slabs_f32, splitk, dev_bias, B, dev_out, advance, stream);
 }
 
 // SV_MLP_TRACE=1 at sv_create: wall-clock stamps (100 MHz ticks) of the fused MLP launch of the middle layer of the LAST decode step,

@@ -812,6 +812,21 @@ class HipEngine:
               "sv_debug_attn_decode")
         return out
 
+    def debug_attn_decode_slabs(self, layer: int, slabs: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                                advance: bool = True) -> torch.Tensor:
+        """debug_attn_decode fed as a decode step feeds the launch: slabs [splitk, B, QKV] float32 (the split-K slabs of the c_attn
+        GEMM, splitk 1, 2, 4 or 8) and bias [QKV] bf16 (None: zero); the kernel sums the slabs in slab order, then adds the bias."""
+        slabs = _need(slabs, torch.float32, "slabs")
+        splitk, B = slabs.shape[0], slabs.shape[1]
+        if bias is not None:
+            bias = _need(bias, torch.bfloat16, "bias")
+            if bias.numel() != slabs.shape[2]:
+                raise ValueError("bias must be bf16 [QKV]")
+        out = torch.empty(B, self.cfg.hidden, dtype=torch.bfloat16, device=slabs.device)   # n_head * head_dim == hidden
+        check(self.lib.sv_debug_attn_decode_slabs(self._h, int(layer), _ptr(slabs), splitk, _ptr(bias), B, _ptr(out),
+                                                  int(bool(advance)), _stream()), "sv_debug_attn_decode_slabs")
+        return out
+
     def profile_decode_step(self, B: int, iters: int = 5) -> Dict[str, Dict[str, float]]:
         """HIP-event time per decode step by kernel class (eager launches of the graph's kernels)."""
         buf = (C.c_double * 10)()
