@@ -4,7 +4,9 @@
  * Compiled into the same shared object as the product ABI (include/starvector_hip.h, included below), kept apart so that a
  * reference-side binding sees only what it has to bind:
  *   sv_op_*                 single operators, one per row of SURVEY.md section 8a: the parity tests put each HIP kernel next to the
- *                           oracle through them (tests/test_gpu_ops.py, tests/test_gpu_row_kernels.py, tests/test_gpu_fp8.py)
+ *                           oracle through them (tests/test_gpu_ops.py, tests/test_gpu_row_kernels.py, tests/test_gpu_fp8.py); the fp8-weight
+ *                           forms (sv_op_pack_weight_fp8, sv_op_linear_fp8, sv_op_linear_skinny_epi_fp8: the quantiser's raw images, the big-M
+ *                           kernels' column-scale epilogues, the decode GEMM's c_fc / lm_head epilogues) in tests/test_gpu_fp8_ops.py
  *   sv_debug_*_plan,
  *   sv_debug_resample_coeffs  host-side decisions of the library (dispatch, split-K, context splits, Pillow's tap tables), callable
  *                           WITHOUT a GPU: the CPU suite pins them
@@ -220,6 +222,23 @@ int  sv_op_linear_skinny_fp8(const void* x, const void* W, const void* bias, voi
  * (the c_fc form, N %% 8 == 0); out_f32 != 0: float32 rows of x W^T holding bf16-rounded values, bias ignored (the lm_head form) */
 int  sv_op_linear_skinny_epi(const void* x, const void* W, const void* bias, void* y, int32_t M, int32_t N, int32_t K,
                              int32_t act, int32_t out_f32, sv_stream stream);
+/* sv_op_linear_skinny_epi with the weight quantised to fp8 e4m3 as in sv_op_linear_skinny_fp8 (the SkinnyArgs of an fp8 engine's c_fc and
+ * lm_head launches); K % 64 == 0; scale_out [N] (device, optional) receives the row scales.  Honours sv_debug_set_col_tiles /
+ * sv_debug_set_skinny_form like its bf16 sibling. */
+int  sv_op_linear_skinny_epi_fp8(const void* x, const void* W, const void* bias, void* y, float* scale_out, int32_t M, int32_t N, int32_t K,
+                                 int32_t act, int32_t out_f32, sv_stream stream);
+/* sv_op_linear with the weight quantised the same way: the big-M kernels run on the bf16 image of the quantised values and apply the row
+ * scales to the accumulator (GemmArgs::cscale), as an fp8 engine's prompt pass does; K % 64 == 0; scale_out [N] optional.  Honours
+ * sv_debug_set_gemm_form and sv_debug_set_linear_seq_rows like sv_op_linear. */
+int  sv_op_linear_fp8(const void* x, const void* W, const void* bias, const void* residual, void* y, float* scale_out, int32_t M, int32_t N,
+                      int32_t K, int32_t act, int32_t out_f32, sv_stream stream);
+/* the fp8 quantiser on its own, as sv_load_weight runs it: W [N][K] row-major (bf16; fp32 when w_is_f32 != 0), K % 64 == 0, Npad = N rounded
+ * up to 32.  scale_out fp32 [Npad]: max_k |W[n][k]| / 448, 1 for an all-zero row and for rows >= N.  wq_out [Npad * K] bytes: the decode image
+ * [Npad/32][K/32][64 lanes][16 B] -- lane l of tile nt holds row nt*32 + (l & 31), bytes 8h .. 8h+7 = k = 32*ks2 + 16*h + 8*(l >> 5) + 0..7.
+ * wp_out bf16 [Npad * K]: the same values in the packed layout of the bf16 weights [Npad/32][K/16][64 lanes][8] -- lane l, k-step ks:
+ * k = 16*ks + 8*(l >> 5) + 0..7.  Rows >= N are zero in both images. */
+int  sv_op_pack_weight_fp8(const void* W, int32_t w_is_f32, int32_t N, int32_t K, float* scale_out, void* wq_out, void* wp_out,
+                           sv_stream stream);
 /* the lm_head form with the greedy selection folded into its epilogue (what a plain greedy sv_generate runs per decode step): y_f32 [M][N]
  * (optional, device) = bf16-rounded fp32 logits, host_idx [M] (HOST) = arg-max column per row -- lowest index on ties, NaN never wins,
  * 0x7fffffff when a row has no comparable score; M <= 32 */

@@ -468,15 +468,21 @@ extern "C" int sv_op_layernorm(const void* x, const void* gamma, const void* bet
     return 0;
 }
 
-extern "C" int sv_op_linear(const void* x, const void* W, const void* bias, const void* residual, void* y, int32_t M,
-                            int32_t N, int32_t K, int32_t act, int32_t out_f32, sv_stream stream) {
-    if (!x || !W || !y || M < 1 || N < 4 || N % 4 || K < 1) return fail(SV_EINVAL, "sv_op_linear: bad argument");
-    hipStream_t st = (hipStream_t)stream;
+// the big-M Linear behind sv_op_linear (fp8 == 0) and sv_op_linear_fp8 (fp8 != 0: the weight quantised as sv_load_weight does it, the GEMM on the
+// bf16 image of the quantised values with the row scales as GemmArgs::cscale -- what an fp8 engine's prompt pass launches)
+static int op_linear_run(const void* x, const void* W, const void* bias, const void* residual, void* y, float* scale_out, int M, int N, int K,
+                         int act, int out_f32, bool fp8, hipStream_t st) {
     TmpBufs tmp;
     const int Npad = round_up(N, 32), Kpad = round_up(K, 64);
     bf16_t* Wp;
+    float* sc = nullptr;
     SVCHECK(tmp.get(&Wp, (size_t)Npad * Kpad));
-    launch_pack_weight(W, 0, Wp, N, K, Npad, Kpad, st);
+    if (fp8) {
+        uint8_t* Wq;
+        SVCHECK(tmp.get(&Wq, (size_t)Npad * Kpad));
+        SVCHECK(tmp.get(&sc, (size_t)Npad));
+        launch_pack_weight_fp8(W, 0, Wp, Wq, sc, N, K, Npad, Kpad, st);
+    } else launch_pack_weight(W, 0, Wp, N, K, Npad, Kpad, st);
     const bf16_t* A = (const bf16_t*)x;
     int lda = K;
     if (Kpad != K) {
@@ -489,9 +495,40 @@ extern "C" int sv_op_linear(const void* x, const void* W, const void* bias, cons
     GemmArgs g;
     g.A = A; g.lda = lda; g.Wp = Wp; g.bias = (const bf16_t*)bias; g.R = (const bf16_t*)residual; g.ldr = N;
     g.C = y; g.ldc = N; g.M = M; g.N = N; g.K = Kpad; g.act = act; g.out_f32 = out_f32;
+    g.cscale = sc;
     g.seq_rows = g_op_seq_rows.load();
     if (g.seq_rows < 0) { g.seq_rows = -g.seq_rows; g.splitk_rows = 1; }      // the rows are the last rows of sequences of |S| rows
     launch_gemm(g, st);
+    if (scale_out) HIPCHECK(hipMemcpyAsync(scale_out, sc, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int sv_op_linear(const void* x, const void* W, const void* bias, const void* residual, void* y, int32_t M,
+                            int32_t N, int32_t K, int32_t act, int32_t out_f32, sv_stream stream) {
+    if (!x || !W || !y || M < 1 || N < 4 || N % 4 || K < 1) return fail(SV_EINVAL, "sv_op_linear: bad argument");
+    return op_linear_run(x, W, bias, residual, y, nullptr, M, N, K, act, out_f32, false, (hipStream_t)stream);
+}
+
+// sv_op_linear with fp8 (e4m3) weights: the six cscale sites of the big-M kernels (gemm_bf16_kernel / gemm256_kernel: LDS strip and register
+// epilogue; gemm_tail_kernel; gemm_tailk_kernel) on their own.  scale_out [N] (optional) returns the row scales.
+extern "C" int sv_op_linear_fp8(const void* x, const void* W, const void* bias, const void* residual, void* y, float* scale_out, int32_t M,
+                                int32_t N, int32_t K, int32_t act, int32_t out_f32, sv_stream stream) {
+    if (!x || !W || !y || M < 1 || N < 4 || N % 4 || K < 64 || K % 64)
+        return fail(SV_EINVAL, "sv_op_linear_fp8: bad argument (N %% 4 == 0 and K %% 64 == 0 required)");
+    return op_linear_run(x, W, bias, residual, y, scale_out, M, N, K, act, out_f32, true, (hipStream_t)stream);
+}
+
+// the fp8 quantiser on its own, exactly as sv_load_weight calls it: W [N][K] (bf16, or fp32 when w_is_f32) -> scale_out fp32 [Npad] (Npad = N rounded up
+// to 32; 1 for an all-zero row and for the padding rows), wq_out [Npad * K] bytes (the decode image: [Npad/32][K/32][64 lanes][16 B], a lane's two
+// consecutive k-steps of 8 e4m3 codes each) and wp_out bf16 [Npad * K] (the SAME values in the packed layout of the bf16 weights: [Npad/32][K/16][64][8]).
+extern "C" int sv_op_pack_weight_fp8(const void* W, int32_t w_is_f32, int32_t N, int32_t K, float* scale_out, void* wq_out, void* wp_out,
+                                     sv_stream stream) {
+    if (!W || !scale_out || !wq_out || !wp_out || N < 1 || K < 64 || K % 64)
+        return fail(SV_EINVAL, "sv_op_pack_weight_fp8: bad argument (K %% 64 == 0 required)");
+    hipStream_t st = (hipStream_t)stream;
+    launch_pack_weight_fp8(W, w_is_f32 != 0, (bf16_t*)wp_out, (uint8_t*)wq_out, scale_out, N, K, round_up(N, 32), K, st);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(st));
     return 0;
@@ -647,25 +684,27 @@ extern "C" int sv_op_linear_skinny_fp8(const void* x, const void* W, const void*
 
 // the decode GEMM's two fused epilogues on their own (split-K 1): out_f32 == 0: y[M,N] = act(bf16(x W^T + bias)) as bf16 rows
 // (c_fc: N %% 8 == 0); out_f32 != 0: fp32 rows of x W^T rounded to bf16 values, no bias (lm_head)
-extern "C" int sv_op_linear_skinny_epi(const void* x, const void* W, const void* bias, void* y, int32_t M, int32_t N, int32_t K,
-                                       int32_t act, int32_t out_f32, sv_stream stream) {
-    if (!x || !W || !y || M < 1 || N < 1 || K < 16 || K % 16) return fail(SV_EINVAL, "sv_op_linear_skinny_epi: bad argument");
-    if (!out_f32 && N % 8) return fail(SV_EINVAL, "bf16 output needs N %% 8 == 0");
-    hipStream_t st = (hipStream_t)stream;
+static int op_linear_skinny_epi_run(const void* x, const void* W, const void* bias, void* y, float* scale_out, int M, int N, int K, int act,
+                                    int out_f32, bool fp8, hipStream_t st) {
     TmpBufs tmp;
     const int Npad = round_up(N, 32), MT = (M + 31) / 32, R = MT * 32;
     bf16_t *Wp, *xp, *oxp;
-    float* of;
+    uint8_t* Wq = nullptr;
+    float *of, *sc = nullptr;
     SVCHECK(tmp.get(&Wp, (size_t)Npad * K));
     SVCHECK(tmp.get(&xp, (size_t)R * K));
     SVCHECK(tmp.get(&oxp, (size_t)R * Npad));
     SVCHECK(tmp.get(&of, (size_t)R * Npad));
     HIPCHECK(hipMemsetAsync(xp, 0, (size_t)R * K * 2, st));
-    launch_pack_weight(W, 0, Wp, N, K, Npad, K, st);
+    if (fp8) {
+        SVCHECK(tmp.get(&Wq, (size_t)Npad * K));
+        SVCHECK(tmp.get(&sc, (size_t)Npad));
+        launch_pack_weight_fp8(W, 0, Wp, Wq, sc, N, K, Npad, K, st);
+    } else launch_pack_weight(W, 0, Wp, N, K, Npad, K, st);
     pack_rows((const bf16_t*)x, K, xp, M, K, st);
     SkinnyArgs a;
     memset(&a, 0, sizeof(a));
-    a.xp = xp; a.Wp = Wp; a.MT = MT; a.Npad = Npad; a.K = K; a.splitk = 1; a.N = N;
+    a.xp = xp; a.Wp = Wp; a.Wq = Wq; a.wscale = sc; a.MT = MT; a.Npad = Npad; a.K = K; a.splitk = 1; a.N = N;
     if (out_f32) { a.out_mode = SK_OUT_F32; a.out_f32 = of; a.ldo = Npad; a.round_bf16 = 1; }
     else {
         a.out_mode = SK_OUT_PACKED_ACT; a.bias = (const bf16_t*)bias; a.act = act; a.out_xp = oxp; a.out_KS = Npad / 16;
@@ -678,10 +717,36 @@ extern "C" int sv_op_linear_skinny_epi(const void* x, const void* W, const void*
     }
     launch_gemm_skinny(a, st);
     if (out_f32) HIPCHECK(hipMemcpy2DAsync(y, (size_t)N * 4, of, (size_t)Npad * 4, (size_t)N * 4, M, hipMemcpyDeviceToDevice, st));
-    else unpack_rows(oxp, (bf16_t*)y, N, M, N, st);
+    else if (N == Npad) unpack_rows(oxp, (bf16_t*)y, N, M, N, st);
+    else {
+        // the kernel wrote row tiles of out_KS = Npad / 16 k-steps: unpack that width (unpacking N columns would look for the second row tile
+        // at 32 * N elements instead of 32 * Npad), then keep the N valid columns
+        bf16_t* yp;
+        SVCHECK(tmp.get(&yp, (size_t)M * Npad));
+        unpack_rows(oxp, yp, Npad, M, Npad, st);
+        HIPCHECK(hipMemcpy2DAsync(y, (size_t)N * 2, yp, (size_t)Npad * 2, (size_t)N * 2, M, hipMemcpyDeviceToDevice, st));
+    }
+    if (scale_out) HIPCHECK(hipMemcpyAsync(scale_out, sc, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, st));
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(st));
     return 0;
+}
+
+extern "C" int sv_op_linear_skinny_epi(const void* x, const void* W, const void* bias, void* y, int32_t M, int32_t N, int32_t K,
+                                       int32_t act, int32_t out_f32, sv_stream stream) {
+    if (!x || !W || !y || M < 1 || N < 1 || K < 16 || K % 16) return fail(SV_EINVAL, "sv_op_linear_skinny_epi: bad argument");
+    if (!out_f32 && N % 8) return fail(SV_EINVAL, "bf16 output needs N %% 8 == 0");
+    return op_linear_skinny_epi_run(x, W, bias, y, nullptr, M, N, K, act, out_f32, false, (hipStream_t)stream);
+}
+
+// the same two epilogues with fp8 (e4m3) weights, the SkinnyArgs of an fp8 engine's c_fc and lm_head (engine_forward.hip): the weight quantised as
+// sv_load_weight does it, Wq / wscale set; scale_out [N] (optional) returns the row scales
+extern "C" int sv_op_linear_skinny_epi_fp8(const void* x, const void* W, const void* bias, void* y, float* scale_out, int32_t M, int32_t N,
+                                           int32_t K, int32_t act, int32_t out_f32, sv_stream stream) {
+    if (!x || !W || !y || M < 1 || N < 1 || K < 64 || K % 64)
+        return fail(SV_EINVAL, "sv_op_linear_skinny_epi_fp8: bad argument (K %% 64 == 0 required)");
+    if (!out_f32 && N % 8) return fail(SV_EINVAL, "sv_op_linear_skinny_epi_fp8: bf16 output needs N %% 8 == 0");
+    return op_linear_skinny_epi_run(x, W, bias, y, scale_out, M, N, K, act, out_f32, true, (hipStream_t)stream);
 }
 
 // the lm_head form of the decode GEMM with the greedy selection folded into its epilogue (gemm.hip, SkinnyArgs::amax): y_f32 [M][N]

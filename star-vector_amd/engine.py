@@ -1162,6 +1162,52 @@ def op_linear_skinny_epi(x, W, bias=None, act="none", out_f32=False):
     return y
 
 
+def op_linear_skinny_epi_fp8(x, W, bias=None, act="none", out_f32=False):
+    """`op_linear_skinny_epi` with the weight quantised to fp8 e4m3 on device (an fp8 engine's c_fc / lm_head launch): returns
+    (y, row scales fp32 [N])."""
+    lib = _lib.load()
+    x = _need(x, torch.bfloat16, "x"); W = _need(W, torch.bfloat16, "W")
+    M, K = x.shape; N = W.shape[0]
+    y = torch.empty(M, N, dtype=torch.float32 if out_f32 else torch.bfloat16, device=x.device)
+    sc = torch.empty(N, dtype=torch.float32, device=x.device)
+    b = _need(bias, torch.bfloat16, "bias") if bias is not None else None
+    check(lib.sv_op_linear_skinny_epi_fp8(_ptr(x), _ptr(W), _ptr(b), _ptr(y), _ptr(sc), M, N, K, _lib.ACT[act], int(out_f32), _stream()),
+          "sv_op_linear_skinny_epi_fp8")
+    return y, sc
+
+
+def op_linear_fp8(x, W, bias=None, residual=None, act="none", out_f32=False):
+    """`op_linear` with the weight quantised to fp8 e4m3 on device: the big-M kernels on the bf16 image of the quantised values, the row
+    scales applied to the accumulator (an fp8 engine's prompt pass).  Returns (y, row scales fp32 [N])."""
+    lib = _lib.load()
+    x = _need(x, torch.bfloat16, "x"); W = _need(W, torch.bfloat16, "W")
+    M, K = x.shape; N = W.shape[0]
+    y = torch.empty(M, N, dtype=torch.float32 if out_f32 else torch.bfloat16, device=x.device)
+    sc = torch.empty(N, dtype=torch.float32, device=x.device)
+    b = _need(bias, torch.bfloat16, "bias") if bias is not None else None
+    r = _need(residual, torch.bfloat16, "residual") if residual is not None else None
+    check(lib.sv_op_linear_fp8(_ptr(x), _ptr(W), _ptr(b), _ptr(r), _ptr(y), _ptr(sc), M, N, K, _lib.ACT[act], int(out_f32), _stream()),
+          "sv_op_linear_fp8")
+    return y, sc
+
+
+def op_pack_weight_fp8(W):
+    """The fp8 quantiser as sv_load_weight runs it, W [N, K] bf16 or float32: returns the raw images (scales fp32 [Npad], the decode image
+    uint8 [Npad * K], the bf16 image [Npad * K]); their layouts are stated in starvector_hip_debug.h."""
+    lib = _lib.load()
+    if W.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("W must be bfloat16 or float32")
+    W = _need(W, W.dtype, "W")
+    N, K = W.shape
+    Npad = (N + 31) // 32 * 32
+    sc = torch.empty(Npad, dtype=torch.float32, device=W.device)
+    wq = torch.empty(Npad * K, dtype=torch.uint8, device=W.device)
+    wp = torch.empty(Npad * K, dtype=torch.bfloat16, device=W.device)
+    check(lib.sv_op_pack_weight_fp8(_ptr(W), int(W.dtype == torch.float32), N, K, _ptr(sc), _ptr(wq), _ptr(wp), _stream()),
+          "sv_op_pack_weight_fp8")
+    return sc, wq, wp
+
+
 def op_lm_head_argmax(x, W):
     """The lm_head form of the decode GEMM with the greedy selection folded into its epilogue (what a plain greedy generate
     runs per step): returns (logits float32 [M, N] holding bf16-rounded values, arg-max column per row as an int64 cpu tensor)."""

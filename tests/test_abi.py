@@ -191,6 +191,19 @@ def test_argument_validation_precedes_any_device_work(lib):
     assert lib.sv_op_row_update_ln(p, 4, 64, 32, p, p, 64, None, None, None, None, p, p, 1e-5, p, 4, 72, None) == -22 and "multiple of 16" in err()
     assert lib.sv_op_row_update_ln(p, 4, 64, 32, p, p, 64, None, None, None, None, p, p, 1e-5, p, 33, 64, None) == -22 and "rows_ws" in err()
     assert lib.sv_op_row_update_ln(None, 0, 0, 0, None, p, 0, p, None, None, p, p, p, 1e-5, p, 4, 64, None) == -22 and "tokens" in err()
+    # the fp8-weight operators: K a multiple of 64 (a lane's 16 bytes of the decode image hold two k-steps), the layout rules of their bf16 siblings
+    assert lib.sv_op_linear_skinny_fp8(p, p, None, p, None, 4, 64, 96, 1, None) == -22 and "K % 64" in err()
+    assert lib.sv_op_linear_skinny_fp8(p, p, None, p, None, 4, 64, 128, 4, None) == -22
+    assert lib.sv_op_linear_skinny_epi_fp8(p, p, None, p, None, 4, 64, 96, 0, 1, None) == -22 and "K % 64" in err()
+    assert lib.sv_op_linear_skinny_epi_fp8(p, p, None, p, None, 4, 60, 128, 0, 0, None) == -22 and "N % 8" in err()
+    assert lib.sv_op_linear_skinny_epi_fp8(p, p, None, None, None, 4, 64, 128, 0, 0, None) == -22
+    assert lib.sv_op_linear_skinny_epi_fp8(p, p, None, p, None, 0, 64, 128, 0, 1, None) == -22
+    assert lib.sv_op_linear_fp8(p, p, None, None, p, None, 4, 64, 96, 0, 0, None) == -22 and "K % 64" in err()
+    assert lib.sv_op_linear_fp8(p, p, None, None, p, None, 4, 62, 128, 0, 0, None) == -22 and "N % 4" in err()
+    assert lib.sv_op_linear_fp8(None, p, None, None, p, None, 4, 64, 128, 0, 0, None) == -22
+    assert lib.sv_op_pack_weight_fp8(p, 0, 33, 96, p, p, p, None) == -22 and "K % 64" in err()
+    assert lib.sv_op_pack_weight_fp8(p, 0, 0, 64, p, p, p, None) == -22
+    assert lib.sv_op_pack_weight_fp8(p, 1, 33, 64, p, None, p, None) == -22 and lib.sv_op_pack_weight_fp8(p, 1, 33, 64, None, p, p, None) == -22
     # the measurement / A-B surfaces validate before they touch the device as well
     assert lib.sv_debug_set_gemm_form(3) == -22 and lib.sv_debug_set_gemm_form(-2) == -22
     assert lib.sv_debug_set_gemm_form(1) == 0 and lib.sv_debug_set_gemm_form(-1) == 0

@@ -285,7 +285,8 @@ def test_linear_skinny_two_row_tiles_per_block_is_bitwise_the_one_tile_kernel(M,
 
 
 @pytest.mark.parametrize("M,N,K,act", [(32, 8192, 2048, "gelu_tanh"), (5, 512, 256, "none"), (40, 256, 1024, "gelu_tanh"),
-                                        (3, 96, 64, "swish"), (64, 18432, 4608, "gelu_tanh"), (17, 40, 32, "quickgelu")])
+                                        (3, 96, 64, "swish"), (64, 18432, 4608, "gelu_tanh"), (17, 40, 32, "quickgelu"),
+                                        (40, 520, 256, "gelu_tanh")])          # two row tiles AND N % 32 != 0: the padded width of a row tile
 def test_linear_skinny_fused_activation_epilogue(M, N, K, act):
     """The c_fc form of the decode GEMM: bias, round to bf16 (the reference's Linear output), activation, round -- in the kernel's
     epilogue, fragment-order output."""

@@ -22,11 +22,17 @@ E2E = "test_gpu_e2e.py::"
 BEAM = "test_gpu_beam.py::"
 LONG = "test_gpu_long_context.py::"
 DH64 = "test_gpu_decoder_head_dim64.py::"
+FP8 = "test_gpu_fp8_ops.py::"
 
 _ROW_UPDATE = (ROWS + "test_row_update_residual_mode_sums_the_slabs_in_order", ROWS + "test_row_update_embedding_mode", ROWS + "test_eps_row_update")
 _BIG_M = (OPS + "test_linear_mfma", OPS + "test_linear_big_m_kernels_agree_bitwise",
           OPS + "test_linear_tile_kernels_and_the_tuned_choice_agree_at_the_prefill_shapes")
 _SKINNY = (OPS + "test_linear_skinny_weight_streaming", OPS + "test_linear_skinny_fused_activation_epilogue", OPS + "test_linear_skinny_logits_epilogue")
+# fp8 weights: the quantiser's images, the big-M kernels' column-scale epilogues (bits of the bf16 operator on exactly quantisable weights +
+# float64 on dequant(quant(W))), the decode GEMM's c_fc / lm_head epilogues in every kernel form
+_FP8_QUANT = (FP8 + "test_quantiser_images_are_torchs_cast_in_the_stated_layouts",)
+_FP8_BIG_M = (FP8 + "test_big_m_kernels_apply_the_column_scale", FP8 + "test_big_m_tuned_choice_with_the_column_scale")
+_FP8_DECODE = (FP8 + "test_decode_epilogues_with_fp8_weights_small_shapes", FP8 + "test_decode_epilogues_with_fp8_weights_engine_shapes")
 _FOLD = (OPS + "test_decode_output_projection_and_folded_layernorm", OPS + "test_folded_layernorm_with_a_large_common_offset_per_row",
          ROWS + "test_eps_folded_layernorm_of_the_six_launch_layer")
 _BEAM_STEP = (BEAM + "test_beam_scorer_matches_oracle", BEAM + "test_beam_scorer_full_vocab_penalty_and_pad_zero")
@@ -80,19 +86,20 @@ COVERAGE = {
     # ---- gemm.hip
     "pack_weight_kernel": (OPS + "test_linear_mfma", OPS + "test_linear_transpose_detecting"),
     "convert_bf16_kernel": (E2E + "test_against_reference_goldens",),     # (engine) sv_load_weight
-    "fp8_row_scale_kernel": ("test_gpu_fp8.py::test_fp8_skinny_gemm_matches_torch_fake_quant",),
-    "pack_weight_fp8_kernel": ("test_gpu_fp8.py::test_fp8_skinny_gemm_matches_torch_fake_quant",),
-    "gemm_skinny_fp8_kernel": ("test_gpu_fp8.py::test_fp8_skinny_gemm_matches_torch_fake_quant",),
-    "gemm_bf16_kernel": _BIG_M,
-    "gemm256_kernel": _BIG_M,
-    "gemm_tail_kernel": (OPS + "test_remainder_row_kernels_agree_with_the_tile_kernels_bitwise",) + _BIG_M,
-    "gemm_tailk_kernel": (OPS + "test_linear_rows_a_sequence_leaves_over_its_tiles",),
+    "fp8_row_scale_kernel": _FP8_QUANT + ("test_gpu_fp8.py::test_fp8_skinny_gemm_matches_torch_fake_quant",),
+    "pack_weight_fp8_kernel": _FP8_QUANT + ("test_gpu_fp8.py::test_fp8_skinny_gemm_matches_torch_fake_quant",),
+    "gemm_skinny_fp8_kernel": _FP8_DECODE + ("test_gpu_fp8.py::test_fp8_skinny_gemm_matches_torch_fake_quant",),
+    "gemm_bf16_kernel": _BIG_M + _FP8_BIG_M,
+    "gemm256_kernel": _BIG_M + _FP8_BIG_M,
+    "gemm_tail_kernel": (OPS + "test_remainder_row_kernels_agree_with_the_tile_kernels_bitwise",) + _BIG_M + _FP8_BIG_M[:1],
+    "gemm_tailk_kernel": (OPS + "test_linear_rows_a_sequence_leaves_over_its_tiles",
+                          FP8 + "test_big_m_rows_a_sequence_leaves_over_its_tiles_with_the_column_scale"),
     "gemm_skinny_kernel": _SKINNY,
     "gemm_head_persist_kernel": (OPS + "test_lm_head_persistent_blocks_bit_identical_to_one_tile_blocks", OPS + "test_lm_head_persistent_blocks_two_row_tiles",
                                  OPS + "test_lm_head_with_folded_greedy_selection"),
     "gemm_skinny_tailsplit_kernel": (OPS + "test_linear_skinny_tail_split_gives_the_one_launch_bits",) + _SKINNY,
-    "gemm_skinny_mt2_kernel": (OPS + "test_linear_skinny_two_row_tiles_per_block_is_bitwise_the_one_tile_kernel",) + _SKINNY,
-    "gemm_skinny_mt2x_kernel": (OPS + "test_linear_skinny_two_row_tiles_per_block_is_bitwise_the_one_tile_kernel",) + _SKINNY,
+    "gemm_skinny_mt2_kernel": (OPS + "test_linear_skinny_two_row_tiles_per_block_is_bitwise_the_one_tile_kernel",) + _SKINNY + _FP8_DECODE,
+    "gemm_skinny_mt2x_kernel": (OPS + "test_linear_skinny_two_row_tiles_per_block_is_bitwise_the_one_tile_kernel",) + _SKINNY + _FP8_DECODE,
     "mlp_fused_kernel": (E2E + "test_fused_mlp_launch_equals_the_two_launches_bit_for_bit",) + _SKINNY,
     "cvt_bf16_hw_kernel": (OPS + "test_bf16_rounding_is_rne",),
     # ---- preprocess.hip
