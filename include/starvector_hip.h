@@ -415,6 +415,27 @@ typedef struct sv_token_topk {
 int  sv_generate_topk(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, int32_t S0, int32_t n_samples,
                       const sv_sampling* sp, const sv_logits_processors* lp, const sv_generate_outputs* outs, const sv_token_stats* stats,
                       const sv_token_topk* topk, int64_t* dev_out_tokens, int32_t* n_generated, sv_stream stream);
+/* ---- prompt-lookup speculative decoding for greedy generate (HF's generate(..., prompt_lookup_num_tokens = K); entry point appended,
+ * SV_ABI_VERSION unchanged).  A decode step costs the same for 1 row as for 32, so one step VERIFIES K drafted tokens of every sequence: B x (K + 1)
+ * rows, row j of a sequence carrying its j-th draft at position ctx + j, all of them on the sequence's own KV pages.  The drafts come from an
+ * n-gram lookup over the ids the sequence has generated so far (for n = max_ngram .. min_ngram: the latest earlier occurrence of the last n
+ * ids, then the ids that followed it) -- no draft model.  A step emits the accepted drafts and one token more.  Greedy verification is
+ * exact: tokens and *n_generated are those of sv_generate / sv_generate_ragged BIT FOR BIT, for every B, including the reference's row-0 stop
+ * sequence (which ends the batch at row 0's column for every row), EOS / pad and min_new_tokens.
+ * host_counts3 (may be NULL): {verification steps, drafts verified, drafts accepted}.  lookup NULL or num_draft_tokens == 0: this IS
+ * sv_generate_ragged (host_lens given) / sv_generate.  Streaming works with B == 1.
+ * SV_EINVAL before any device work: NULL arguments, num_draft_tokens outside 0..SV_LOOKUP_MAX_DRAFT, max_ngram outside 0..SV_LOOKUP_MAX_NGRAM,
+ * min_ngram outside 0..max_ngram.  SV_ENOTSUP, naming the offender: do_sample, num_beams > 1, repetition_penalty != 1, streaming with
+ * B > 1, B x (K + 1) > max_batch.  Continuous batching (sv_cb_*) does not draft. */
+#define SV_LOOKUP_MAX_DRAFT 15
+#define SV_LOOKUP_MAX_NGRAM 8
+typedef struct sv_lookup {
+    int32_t num_draft_tokens;   /* K: 1..SV_LOOKUP_MAX_DRAFT (0: a plain call) */
+    int32_t max_ngram;          /* 1..SV_LOOKUP_MAX_NGRAM, 0 = 3 */
+    int32_t min_ngram;          /* 1..max_ngram, 0 = 1 */
+} sv_lookup;
+int  sv_generate_lookup(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, int32_t S0, const sv_sampling* sp,
+                        const sv_lookup* lookup, int64_t* dev_out_tokens, int32_t* n_generated, int32_t* host_counts3, sv_stream stream);
 /* sv_forward_logprobs plus, for every kept position, the k best ids of softmax(logits / temperature) over the bf16 row, their log-probs
  * (dev_topk_ids int32 / dev_topk_logprobs fp32, [B][n_keep][k]) and the rank of the target (dev_rank int32 [B][n_keep], may be NULL; target
  * -100: rank 0).  Order, ties, the (-1, -inf) tail and the rank as in sv_generate_topk, keyed on the bf16 logit; a slot holds

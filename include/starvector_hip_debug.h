@@ -184,6 +184,34 @@ int  sv_debug_attn_decode(sv_engine* e, int32_t layer, const float* dev_qkv_f32,
                           sv_stream stream);
 int  sv_debug_attn_decode_slabs(sv_engine* e, int32_t layer, const float* dev_slabs_f32, int32_t splitk, const void* dev_bias, int32_t B,
                                 void* dev_out, int32_t advance, sv_stream stream);
+/* Prompt-lookup decoding (sv_generate_lookup), piece by piece.
+ *   sv_debug_attn_decode_draft  what a verification step does around ONE attention launch, on the real paged cache: after sv_debug_kv_load of
+ *                        n_seq sequences, the block table and the positions are expanded to n_seq x K1 rows (row s * K1 + j: sequence s's pages,
+ *                        position pos_s + j), every row's k_new | v_new is pre-written into its page slot (lookup_kv_write_kernel) and the attention
+ *                        runs over all rows; dev_slabs_f32 fp32 [splitk][n_seq * K1][QKV], dev_out bf16 [n_seq * K1][n_head*head_dim].
+ *                        Afterwards the engine is back in the n_seq-row layout with every position advanced by K1 -- the state K1 calls of
+ *                        sv_debug_attn_decode_slabs(..., advance = 1) leave, which must give the same bits.
+ *   sv_debug_set_lookup_drafts  draft j of sequence b is host_stream[b][n_emit_b + j] (ids inside the vocabulary) instead of the lookup, for
+ *                        every sv_generate_lookup call that follows with that B; NULL clears it.
+ *   sv_op_lookup_accept  one lookup_step_kernel launch on given state, no engine: host_winners [n_seq * (K + 1)] = the id every row chose,
+ *                        host_rows the ids the rows carried (d_0 .. d_K per sequence); in / out: host_hist [n_seq][ld] generated ids,
+ *                        host_state [n_seq][4] = {n_emit, finished, prompt length, live drafts}, host_call [8] = {limit, done, n_emitted, bad,
+ *                        steps, drafted, accepted, 0}, host_next_positions [n_seq * (K + 1)] the rows' positions (a finished sequence keeps its rows);
+ *                        out: host_next_rows, the next step's ids.  A winner outside [0, vocab) stands for a row without a finite logit.
+ *   sv_op_lookup_draft   the lookup alone on one history host_hist [L]: the drafts (at most K, and at most max_new - L - 1) and their count.
+ *   sv_op_lookup_hold    the min-length hold on caller-given rows: dev_logits fp32 [rows][ld], row r belongs to sequence r / K1 with
+ *                        host_n_emit [rows / K1] ids emitted; logits[r][eos] = -inf while n_emit + r % K1 < min_new. */
+int  sv_debug_attn_decode_draft(sv_engine* e, int32_t layer, const float* dev_slabs_f32, int32_t splitk, const void* dev_bias, int32_t n_seq,
+                                int32_t K1, void* dev_out, sv_stream stream);
+int  sv_debug_set_lookup_drafts(sv_engine* e, const int32_t* host_stream, int32_t B, int32_t ld);
+int  sv_op_lookup_accept(const int32_t* host_winners, const int32_t* host_rows, int32_t n_seq, int32_t K, int32_t max_ngram, int32_t min_ngram,
+                         int32_t* host_hist, int32_t ld, int32_t* host_state, int32_t* host_call, const int32_t* stop_ids, int32_t n_stop,
+                         int32_t eos, int32_t pad, int32_t max_new, int32_t vocab, int32_t* host_next_rows, int32_t* host_next_positions,
+                         sv_stream stream);
+int  sv_op_lookup_draft(const int32_t* host_hist, int32_t L, int32_t K, int32_t max_ngram, int32_t min_ngram, int32_t max_new,
+                        int32_t* host_drafts, int32_t* n_drafts, sv_stream stream);
+int  sv_op_lookup_hold(float* dev_logits, int32_t ld, int32_t rows, int32_t K1, int32_t eos, int32_t min_new, const int32_t* host_n_emit,
+                       sv_stream stream);
 
 /* HIP-event timing of one decode step by kernel class, on the cache state left by the last
  * sv_generate / sv_prefill (bench.py roofline leg).  out: 10 doubles, [2k] = ms per step in class k

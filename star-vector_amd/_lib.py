@@ -110,6 +110,12 @@ class SvTokenTopk(C.Structure):
     ]
 
 
+class SvLookup(C.Structure):
+    # sv_generate_lookup: K drafted tokens per sequence and step, from an n-gram lookup over the generated ids (0 = the default of a field)
+    _fields_ = [("num_draft_tokens", C.c_int32), ("max_ngram", C.c_int32), ("min_ngram", C.c_int32)]
+
+
+LOOKUP_MAX_DRAFT, LOOKUP_MAX_NGRAM = 15, 8      # SV_LOOKUP_MAX_DRAFT, SV_LOOKUP_MAX_NGRAM
 TOPK_MAX = 32      # SV_TOPK_MAX
 LP_MAX_NGRAM, LP_MAX_BAD_WORDS, LP_MAX_BAD_WORD_LEN = 8, 64, 8
 
@@ -149,6 +155,7 @@ PRODUCT_PROTOTYPES = {
                                C.POINTER(SvGenerateOutputs), C.POINTER(SvTokenStats), _P, C.POINTER(_I), _P]),
     "sv_generate_topk": (_I, [_P, _P, _I, C.POINTER(_I), _I, _I, C.POINTER(SvSampling), C.POINTER(SvLogitsProcessors),
                               C.POINTER(SvGenerateOutputs), C.POINTER(SvTokenStats), C.POINTER(SvTokenTopk), _P, C.POINTER(_I), _P]),
+    "sv_generate_lookup": (_I, [_P, _P, _I, C.POINTER(_I), _I, C.POINTER(SvSampling), C.POINTER(SvLookup), _P, C.POINTER(_I), C.POINTER(_I), _P]),
     "sv_forward_topk": (_I, [_P, _P, _I, _I, _I, _P, _F, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "sv_forward_logprobs_ragged": (_I, [_P, _P, _I, C.POINTER(_I), C.POINTER(_I), _P, _F, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "sv_cb_admit_shared": (_I, [_P, _P, _I, C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(SvCbRequest), C.POINTER(_I), _P]),
@@ -205,6 +212,12 @@ DEBUG_PROTOTYPES = {
     "sv_debug_kv_load": (_I, [_P, _I, _P, _I, _I, _P, _P]),
     "sv_debug_attn_decode": (_I, [_P, _I, _P, _I, _P, _I, _P]),
     "sv_debug_attn_decode_slabs": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P]),
+    "sv_debug_attn_decode_draft": (_I, [_P, _I, _P, _I, _P, _I, _I, _P, _P]),
+    "sv_debug_set_lookup_drafts": (_I, [_P, C.POINTER(_I), _I, _I]),
+    "sv_op_lookup_accept": (_I, [C.POINTER(_I), C.POINTER(_I), _I, _I, _I, _I, C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _I,
+                                 _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _P]),
+    "sv_op_lookup_draft": (_I, [C.POINTER(_I), _I, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _P]),
+    "sv_op_lookup_hold": (_I, [_P, _I, _I, _I, _I, _I, C.POINTER(_I), _P]),
     "sv_debug_decode_plan": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     "sv_profile_decode_step": (_I, [_P, _I, _I, C.POINTER(C.c_double), _P]),
     "sv_profile_ttft": (_I, [_P, _P, _I, _P, _I, _I, C.POINTER(C.c_double), _P]),

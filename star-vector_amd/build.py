@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libstarvector_hip.so")
-SOURCES = ["gemm.hip", "decode_cols.hip", "rowops.hip", "attention.hip", "sampling.hip", "processors.hip", "score.hip", "beam.hip", "fork.hip", "preprocess.hip", "engine_core.hip", "engine_forward.hip", "engine_generate.hip", "engine_cb.hip", "engine_ops.hip"]
+SOURCES = ["gemm.hip", "decode_cols.hip", "rowops.hip", "attention.hip", "sampling.hip", "processors.hip", "score.hip", "beam.hip", "fork.hip", "preprocess.hip", os.path.join("lookup", "lookup.hip"), "engine_core.hip", "engine_forward.hip", "engine_generate.hip", "engine_cb.hip", "engine_ops.hip"]
 HEADERS = ["common.h", "kernels.h", "beam.h", "warp.h", "engine_internal.h", os.path.join("..", "..", "include", "starvector_hip.h"),
            os.path.join("..", "..", "include", "starvector_hip_debug.h")]
 # -amdgpu-kernarg-preload-count: leading scalar / pointer kernel parameters arrive in SGPRs with the dispatch (gfx950) instead
@@ -36,6 +36,11 @@ def _newer(target: str, deps) -> bool:
     return all(os.path.getmtime(d) <= t for d in deps)
 
 
+def _obj_name(source: str) -> str:
+    """csrc/lookup/lookup.hip -> lookup.o: the objects of every source directory share csrc/build"""
+    return os.path.basename(source).replace(".hip", ".o")
+
+
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
@@ -48,7 +53,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     jobs = []
     for s in SOURCES:
         src = os.path.join(CSRC, s)
-        obj = os.path.join(OBJ, s.replace(".hip", ".o"))
+        obj = os.path.join(OBJ, _obj_name(s))
         if force or not _newer(obj, [src] + hdrs):
             jobs.append((src, obj))
 
@@ -67,7 +72,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
             list(ex.map(compile_one, jobs))
     with open(stamp, "w") as f:
         f.write(flags_now)
-    objs = [os.path.join(OBJ, s.replace(".hip", ".o")) for s in SOURCES]
+    objs = [os.path.join(OBJ, _obj_name(s)) for s in SOURCES]
     if force or jobs or not _newer(LIB, objs):
         cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
         r = subprocess.run(cmd, capture_output=True, text=True)

@@ -358,6 +358,8 @@ extern "C" int sv_destroy(sv_engine* e) {
     if (e->gen_graph) (void)hipGraphDestroy(e->gen_graph);
     if (e->gen_gexec_multi) (void)hipGraphExecDestroy(e->gen_gexec_multi);
     if (e->gen_graph_multi) (void)hipGraphDestroy(e->gen_graph_multi);
+    if (e->lk_gexec) (void)hipGraphExecDestroy(e->lk_gexec);
+    if (e->lk_graph) (void)hipGraphDestroy(e->lk_graph);
     if (e->score_ws) (void)hipFree(e->score_ws);
     if (e->score_chunk_ws) (void)hipFree(e->score_chunk_ws);
     if (e->score_lse_ws) (void)hipFree(e->score_lse_ws);

@@ -575,6 +575,17 @@ void sveng::attn_decode_args(sv_engine* e, int layer, int B, const float* ws, in
     ad.n_kv = e->nkv; ad.kv_head_stride = e->kv_head_stride; ad.rope_cos = e->rope_cos; ad.rope_sin = e->rope_sin;
 }
 
+// the K / V pre-write of a verification step (lookup/lookup.hip) over exactly what the attention launch `ad` reads
+LookupKvArgs sveng::lookup_kv_args(const AttnDecodeArgs& ad) {
+    LookupKvArgs ka;
+    memset(&ka, 0, sizeof(ka));
+    ka.ws = ad.ws; ka.splitk = ad.splitk; ka.ldws = ad.ldws; ka.rows_ws = ad.rows_ws; ka.bias = ad.bias;
+    ka.pool_layer = ad.pool_layer; ka.block_table = ad.block_table; ka.max_pages = ad.max_pages; ka.positions = ad.positions;
+    ka.rows = ad.B; ka.H = ad.H; ka.head_dim = ad.head_dim; ka.n_kv = ad.n_kv; ka.kv_head_stride = ad.kv_head_stride;
+    ka.rope_cos = ad.rope_cos; ka.rope_sin = ad.rope_sin;
+    return ka;
+}
+
 // One autoregressive step: consumes cur_tok / positions, leaves logits in e->logits.  6 launches per layer + 2 (bf16 weights,
 // <= 32 rows):
 //   row update (embedding | + bias + residual of the previous down-proj, LN1) | c_attn -> fp32 slabs | attention (sums the
@@ -681,6 +692,7 @@ void sveng::decode_forward(sv_engine* e, int B, hipStream_t st) {
             if (i == c.n_layer / 2) ad.trace = e->attn_trace;             // SV_ATTN_TRACE=1: one layer in the middle of the step
             if (attn_poisons) { ad.poison = e->xp_mlp; ad.poison_bytes = (unsigned)pat_bytes; }
             if (attn_poisons_xpa) { ad.poison2 = e->xp_a; ad.poison2_bytes = xpa_bytes; }     // the next layer's rowln_cattn launch
+            if (e->lookup_on) launch_lookup_kv_write(lookup_kv_args(ad), st);      // sv_generate_lookup: the rows of a sequence see their siblings' K / V through the cache
             prof_mark(e, PK_ATTN, st);
             launch_attn_decode(ad, st);
         }

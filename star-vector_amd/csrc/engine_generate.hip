@@ -313,6 +313,8 @@ struct GenCall {
     int64_t* dev_out_tokens;
     int32_t* n_generated;
     sv_stream stream;
+    const sv_lookup* lookup = nullptr;      // sv_generate_lookup: the call verifies drafts (lookup_attempt), defaults resolved
+    int32_t* counts3 = nullptr;             //   its {steps, drafted, accepted}, or nullptr
 };
 static bool lp_any(const sv_logits_processors* lp) { return lp && (lp->no_repeat_ngram_size != 0 || lp->n_bad_words != 0 || lp->min_p != 0.f); }
 static int check_token_topk(const sv_sampling* sp, const sv_logits_processors* lp, const sv_token_topk* tk, int max_new);
@@ -618,8 +620,190 @@ static int shared_prefill_fork(sv_engine* e, const void* dev_embeds, int B, int 
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// sv_generate_lookup: greedy generate that verifies K drafted tokens per sequence and step (lookup/lookup.hip; DESIGN.md "Prompt-lookup decoding")
+// ------------------------------------------------------------------------------------------------
+static void lookup_args(sv_engine* e, int n_seq, const sv_lookup& lk, const sv_sampling& sp, int max_new, LookupArgs& a) {
+    const int mb = e->cfg.max_batch;
+    memset(&a, 0, sizeof(a));
+    a.counts = e->lk_state; a.n_emit = a.counts + 3; a.fin = a.n_emit + mb; a.base = a.fin + mb; a.n_draft = a.base + mb;
+    a.limit = a.n_draft + mb; a.ticket = reinterpret_cast<unsigned*>(a.limit + 1);
+    a.n_seq = n_seq; a.K = lk.num_draft_tokens; a.max_ngram = lk.max_ngram; a.min_ngram = lk.min_ngram;
+    a.cur_tok = e->cur_tok; a.positions = e->positions; a.unfinished = e->unfinished;
+    a.out_tok = e->out_tok; a.ld_out = e->out_ld; a.pval = e->am_val; a.pidx = e->am_idx;
+    a.done = e->d_done; a.n_emitted = e->d_nemit; a.bad = e->d_bad;
+    a.stop_ids = e->d_stop; a.n_stop = sp.n_stop; a.eos = sp.eos_token_id; a.pad = sp.pad_token_id; a.max_new = max_new; a.V = e->cfg.vocab;
+    if (e->lk_forced && e->lk_forced_B == n_seq) { a.forced = e->lk_forced; a.forced_ld = e->lk_forced_ld; }
+}
+// The driver beside generate_attempt (same GenCall, same retry): prompt pass and first token exactly as the plain call takes them, then
+// verification steps -- decode_forward over B x (K + 1) rows with the K / V pre-write in front of every attention launch, the min-length
+// hold, the slice argmax, lookup_step_kernel -- captured once and replayed.
+static int lookup_attempt(sv_engine* e, const GenCall& c) {
+    const sv_sampling* sp = c.sp;
+    const sv_lookup& lk = *c.lookup;
+    const int32_t B = c.B, S0 = c.S0, K1 = lk.num_draft_tokens + 1;
+    const int32_t* lens = c.lens;
+    SVCHECK(check_ready(e));
+    if ((long long)B * K1 > e->cfg.max_batch || B > 64)
+        return fail(SV_ENOTSUP, "sv_generate_lookup: B %d x (num_draft_tokens %d + 1) rows exceed engine max_batch %d", B, K1 - 1, e->cfg.max_batch);
+    const int rows = B * K1;
+    if (lens) SVCHECK(ragged_check_lens(e, lens, B, "sv_generate_lookup", nullptr, nullptr));
+    const int max_new = sp->max_length - S0;
+    if (max_new <= 0) return fail(SV_EINVAL, "max_length (%d) must exceed the prompt length (%d)", sp->max_length, S0);
+    if (S0 + max_new > e->cfg.max_seq_len) return fail(SV_EINVAL, "max_length %d exceeds engine max_seq_len %d", sp->max_length, e->cfg.max_seq_len);
+    if (sp->n_stop < 0 || sp->n_stop > 16) return fail(SV_EINVAL, "stop sequence length %d unsupported (0..16)", sp->n_stop);
+    if (sp->n_stop > 0 && !sp->stop_ids) return fail(SV_EINVAL, "n_stop > 0 but stop_ids is null");
+    std::lock_guard<std::mutex> lk_mu(e->mu);
+    HIPCHECK(hipSetDevice(e->cfg.device));
+    HIPCHECK(hipEventRecord(e->gen_event, (hipStream_t)c.stream));
+    hipStream_t st = e->gen_stream;
+    HIPCHECK(hipStreamWaitEvent(st, e->gen_event, 0));
+    SVCHECK(cb_guard(e, "sv_generate_lookup"));
+    if (!e->lk_state) SVCHECK(dalloc(e, &e->lk_state, (size_t)4 * e->cfg.max_batch + 8));
+
+    auto t0 = std::chrono::steady_clock::now();
+    HIPCHECK(hipMemsetAsync(e->d_bad, 0, sizeof(int32_t), st));
+    if (lens) {
+        SVCHECK(assign_pages_ragged(e, B, lens, max_new, st));
+        SVCHECK(prefill_forward_ragged(e, (const bf16_t*)c.embeds, B, lens, st));
+        HIPCHECK(hipGetLastError());
+    } else {
+        SVCHECK(prefill_locked(e, c.embeds, B, S0, S0 + max_new, st, false));
+    }
+    gen_state_init(e->positions, S0 - 1, e->unfinished, B, e->d_step, e->amax, 0, st);
+    if (lens) ragged_positions(e, B, 1, -1, st);
+    if (sp->n_stop > 0) HIPCHECK(hipMemcpyAsync(e->d_stop, sp->stop_ids, sp->n_stop * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    sample_and_finish(e, B, *sp, max_new, st);       // the first token, from the prompt pass's logits, by the plain call's own launches
+    HIPCHECK(hipMemcpyAsync(&e->h_flags[8], e->d_step, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    e->h_flags[0] = e->h_flags[9];
+    e->h_flags[12] = e->h_flags[13] = e->h_flags[14] = 0; e->h_flags[15] = 1;
+    auto t1 = std::chrono::steady_clock::now();
+
+    struct LookupOff { sv_engine* e; ~LookupOff() { e->lookup_on = false; } } lookup_off{e};
+    int streamed = e->stream_skip;
+    struct SkipSave { sv_engine* e; int* s; ~SkipSave() { e->stream_skip = *s; } } skip_save{e, &streamed};
+    std::vector<int32_t> stream_buf;
+    auto stream_upto = [&](int n_cols_final) -> int {        // (B == 1: the columns below n_emit[0] are final)
+        if (!sp->on_tokens || n_cols_final <= streamed) return 0;
+        const int n = n_cols_final - streamed;
+        stream_buf.resize((size_t)n);
+        HIPCHECK(hipMemcpyAsync(stream_buf.data(), e->out_tok + streamed, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));
+        sp->on_tokens(sp->user_data, stream_buf.data(), 1, streamed, n);
+        streamed = n_cols_final;
+        return 0;
+    };
+    int steps = 0;
+    hipGraphExec_t gexec = nullptr;
+    if (!e->h_flags[0]) {
+        // rows s * K1 + j of the block table = sequence s's row: the K1 rows of a sequence alias the same pages, tail page included (descending:
+        // a row is read before it is overwritten)
+        if (e->table_pending) { HIPCHECK(hipEventSynchronize(e->table_ev)); e->table_pending = false; }
+        const size_t mp = (size_t)e->pages_per_seq;
+        for (int r = rows - 1; r > 0; --r)
+            if (r / K1 != r) memcpy(e->h_table + (size_t)r * mp, e->h_table + (size_t)(r / K1) * mp, mp * sizeof(int32_t));
+        HIPCHECK(hipMemcpyAsync(e->block_table, e->h_table, (size_t)rows * mp * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIPCHECK(hipEventRecord(e->table_ev, st));
+        e->table_pending = true;
+        e->cached_B = 0;                         // the cache is in no layout sv_decode_step could continue
+        LookupArgs la;
+        lookup_args(e, B, lk, *sp, max_new, la);
+        launch_lookup_begin(la, st);
+        e->lookup_on = true;
+        const bool hold = sp->min_new_tokens > 0 && sp->eos_token_id >= 0 && sp->eos_token_id < e->cfg.vocab;
+        const auto one_step = [&]() {
+            decode_forward(e, rows, st);
+            if (hold) launch_lookup_hold_eos(e->logits, e->Vpad, sp->eos_token_id, la.n_emit, K1, sp->min_new_tokens, rows, st);
+            launch_argmax_partial(e->logits, e->Vpad, e->cfg.vocab, e->am_val, e->am_idx, rows, nullptr, e->seen_words, 1.f, st);
+            launch_lookup_step(la, st);
+        };
+        if (graph_enabled()) {
+            char key[320];
+            snprintf(key, sizeof(key), "B%d|K%d|ng%d.%d|n%d|eos%d|pad%d|ns%d|mn%d|x%d|fo%d|f%p.%d", B, K1 - 1, lk.max_ngram, lk.min_ngram, max_new,
+                     sp->eos_token_id, sp->pad_token_id, sp->n_stop, sp->min_new_tokens, e->exp, e->fused_off ? 1 : 0, (const void*)la.forced, la.forced_ld);
+            if (e->lk_gexec && e->lk_graph_key == key) {
+                gexec = e->lk_gexec;
+            } else {
+                if (e->lk_gexec) { (void)hipGraphExecDestroy(e->lk_gexec); e->lk_gexec = nullptr; }
+                if (e->lk_graph) { (void)hipGraphDestroy(e->lk_graph); e->lk_graph = nullptr; }
+                e->lk_graph_key.clear();
+                SVCHECK(capture_steps(st, 1, one_step, &e->lk_graph, &e->lk_gexec));
+                if (e->lk_gexec) { e->lk_graph_key = key; gexec = e->lk_gexec; }
+            }
+        }
+        // The end is data-dependent (a step emits 1 .. K + 1 tokens per sequence), so the device block is polled after EVERY chunk.  Chunk length
+        // 8 unless sync_every says otherwise: the steps a chunk runs past the end of the call are wasted (they find *done set and change
+        // nothing) -- at most 7 of ~1 ms, where the plain loop's 32 would waste up to 31 -- while a poll idles the GPU for ~0.1 ms, ~1 % of 8 steps.
+        // Never more steps than the budget has tokens left: every step emits at least one token per live sequence.
+        const int chunk = sp->sync_every > 0 ? sp->sync_every : 8;
+        while (!e->h_flags[0]) {
+            int n = max_new - 1 - steps;
+            if (n <= 0) break;
+            if (n > chunk) n = chunk;
+            for (int i = 0; i < n; ++i) {
+                if (gexec) HIPCHECK(hipGraphLaunch(gexec, st));
+                else one_step();
+            }
+            steps += n;
+            HIPCHECK(hipMemcpyAsync(&e->h_flags[8], e->d_step, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));      // {step, done, n_emitted, bad}
+            HIPCHECK(hipMemcpyAsync(&e->h_flags[12], e->lk_state, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));   // {steps, drafted, accepted, n_emit[0]}
+            HIPCHECK(hipStreamSynchronize(st));
+            e->h_flags[0] = e->h_flags[9];
+            if (e->h_flags[11]) break;
+            if (!e->h_flags[0] && B == 1) SVCHECK(stream_upto(e->h_flags[15]));
+        }
+    }
+    e->h_flags[1] = e->h_flags[10];
+    SVCHECK(report_bad_logits(e, st, "sv_generate_lookup", e->h_flags[11]));
+    if (!e->h_flags[0]) return fail(SV_EHIP, "sv_generate_lookup: the call did not end within its budget (%d steps)", steps);
+    const int n_emit = e->h_flags[1];
+    if (n_emit < 1 || n_emit > max_new) return fail(SV_EHIP, "generation bookkeeping failed (n_emitted=%d)", n_emit);
+    if (B == 1) SVCHECK(stream_upto(n_emit));
+    tokens_to_i64(e->out_tok, e->out_ld, c.dev_out_tokens, B, n_emit, max_new, st);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));
+    auto t2 = std::chrono::steady_clock::now();
+    *c.n_generated = n_emit;
+    if (c.counts3) { c.counts3[0] = e->h_flags[12]; c.counts3[1] = e->h_flags[13]; c.counts3[2] = e->h_flags[14]; }
+    e->timing[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    e->timing[1] = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    e->timing[2] = (double)e->h_flags[12];
+    e->timing_graph = gexec ? 1.0 : 0.0;
+    return 0;
+}
+extern "C" int sv_generate_lookup(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, int32_t S0, const sv_sampling* sp,
+                                  const sv_lookup* lookup, int64_t* dev_out_tokens, int32_t* n_generated, int32_t* host_counts3, sv_stream stream) {
+    if (!lookup || lookup->num_draft_tokens == 0) {
+        if (host_counts3) host_counts3[0] = host_counts3[1] = host_counts3[2] = 0;
+        if (host_lens) return sv_generate_ragged(e, dev_embeds_packed, B, host_lens, sp, nullptr, dev_out_tokens, n_generated, stream);
+        return sv_generate(e, dev_embeds_packed, B, S0, sp, dev_out_tokens, n_generated, stream);
+    }
+    const char* who = "sv_generate_lookup";
+    sv_lookup lk = *lookup;
+    if (lk.num_draft_tokens < 0 || lk.num_draft_tokens > SV_LOOKUP_MAX_DRAFT)
+        return fail(SV_EINVAL, "%s: num_draft_tokens %d unsupported (0..%d)", who, lk.num_draft_tokens, SV_LOOKUP_MAX_DRAFT);
+    if (lk.max_ngram < 0 || lk.max_ngram > SV_LOOKUP_MAX_NGRAM)
+        return fail(SV_EINVAL, "%s: max_ngram %d unsupported (1..%d, 0 = 3)", who, lk.max_ngram, SV_LOOKUP_MAX_NGRAM);
+    if (lk.max_ngram == 0) lk.max_ngram = 3;
+    if (lk.min_ngram < 0 || lk.min_ngram > lk.max_ngram)
+        return fail(SV_EINVAL, "%s: min_ngram %d must lie in 1..max_ngram %d (0 = 1)", who, lk.min_ngram, lk.max_ngram);
+    if (lk.min_ngram == 0) lk.min_ngram = 1;
+    GenCall c{who, GC_ARGS, dev_embeds_packed, B, S0, host_lens, 1, sp, nullptr, nullptr, nullptr, nullptr, dev_out_tokens, n_generated, stream};
+    SVCHECK(check_gen_call(c));
+    if (sp->do_sample) return fail(SV_ENOTSUP, "%s: do_sample is not built (verification is greedy: the drafts are compared with the arg-max)", who);
+    if (sp->num_beams > 1) return fail(SV_ENOTSUP, "%s: num_beams %d is not built (beam rows reorder their caches)", who, sp->num_beams);
+    if (sp->repetition_penalty > 0.f && sp->repetition_penalty != 1.0f)
+        return fail(SV_ENOTSUP, "%s: repetition_penalty %g is not built (a draft row's penalty depends on the drafts in front of it)", who, sp->repetition_penalty);
+    if (sp->on_tokens && B > 1) return fail(SV_ENOTSUP, "%s: streaming (on_tokens) with B %d > 1 is not built (the sequences advance at different rates)", who, B);
+    c.lookup = &lk;
+    c.counts3 = host_counts3;
+    return generate_retry(e, c);
+}
+
 // lens != nullptr: the ragged form -- S0 is the longest prompt (the budget counts from it), sequence b has lens[b] rows
 static int generate_attempt(sv_engine* e, const GenCall& c) {
+    if (c.lookup) return lookup_attempt(e, c);
     const void* dev_embeds = c.embeds;
     const int32_t Bp = c.B, S0 = c.S0, G = c.n_samples;
     const int32_t* lens = c.lens;

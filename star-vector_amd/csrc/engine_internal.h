@@ -238,6 +238,18 @@ struct sv_engine {
     float minp_log = -INFINITY;
     BanWord* ban_words = nullptr;
     std::vector<BanWord> ban_host;
+    // sv_generate_lookup (engine_generate.hip): lookup_on = decode_forward runs the K/V pre-write in front of every attention launch (set and
+    // cleared by the call).  lk_state (device, allocated by the first such call): counts[3] | n_emit | fin | base | n_draft [max_batch each] |
+    // limit | ticket.  The captured verification step has a cache slot of its own: a plain call after a lookup call replays the graph it kept.
+    // lk_forced (sv_debug_set_lookup_drafts): [lk_forced_B][lk_forced_ld] forced drafts on the device (allocated once, [max_batch][max_seq_len]);
+    // lk_forced_B = 0: the lookup.
+    bool lookup_on = false;
+    int32_t* lk_state = nullptr;
+    int32_t* lk_forced = nullptr;
+    int lk_forced_B = 0, lk_forced_ld = 0;
+    std::string lk_graph_key;
+    hipGraph_t lk_graph = nullptr;
+    hipGraphExec_t lk_gexec = nullptr;
     // optional per-kernel HIP-event profiling of the decode step (bench.py roofline leg)
     bool prof_on = false;
     std::vector<hipEvent_t> prof_ev;
@@ -291,6 +303,7 @@ int prefill_forward(sv_engine* e, const bf16_t* embeds, int B, int S0, hipStream
                     bf16_t* dev_scores = nullptr, const int32_t* table = nullptr, const ScoreLogprobs* lp = nullptr);
 void decode_forward(sv_engine* e, int B, hipStream_t st);
 void attn_decode_args(sv_engine* e, int layer, int B, const float* ws, int splitk, const bf16_t* bias, bf16_t* out_xp, AttnDecodeArgs& ad);
+LookupKvArgs lookup_kv_args(const AttnDecodeArgs& ad);      // the pre-write of a verification step in front of the attention launch `ad`
 int check_ready(sv_engine* e);
 // continuous batching (engine_cb.hip): validation of one request (SV_EINVAL + message) and its device state -- the slot, its
 // logit bias, its repetition bitmap row (seen_words words: the prompt ids in vLLM mode, cleared otherwise)

@@ -172,6 +172,178 @@ extern "C" int sv_debug_attn_decode_slabs(sv_engine* e, int32_t layer, const flo
     return debug_attn_decode(e, "sv_debug_attn_decode_slabs", layer, dev_slabs_f32, splitk, dev_bias, B, dev_out, advance, stream);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Prompt-lookup decoding piece by piece (include/starvector_hip_debug.h)
+// ------------------------------------------------------------------------------------------------
+// What a verification step does around one attention launch, on the cache sv_debug_kv_load left: n_seq sequences -> n_seq x K1 rows (table rows
+// copied, positions pos_s + j), the pre-write, ONE attention launch; then back to n_seq rows with every position advanced by K1.
+extern "C" int sv_debug_attn_decode_draft(sv_engine* e, int32_t layer, const float* dev_slabs, int32_t splitk, const void* dev_bias, int32_t n_seq,
+                                          int32_t K1, void* dev_out, sv_stream stream) {
+    const char* who = "sv_debug_attn_decode_draft";
+    if (!e || !dev_slabs || !dev_out) return fail(SV_EINVAL, "%s: null argument", who);
+    const sv_config& c = e->cfg;
+    if (layer < 0 || layer >= c.n_layer) return fail(SV_EINVAL, "%s: bad layer %d", who, layer);
+    if (splitk != 1 && splitk != 2 && splitk != 4 && splitk != 8) return fail(SV_EINVAL, "%s: splitk %d is not 1, 2, 4 or 8", who, splitk);
+    if (n_seq < 1 || K1 < 1 || K1 > SV_LOOKUP_MAX_DRAFT + 1 || (long long)n_seq * K1 > c.max_batch)
+        return fail(SV_EINVAL, "%s: n_seq %d x K1 %d rows (K1 1..%d, max_batch %d)", who, n_seq, K1, SV_LOOKUP_MAX_DRAFT + 1, c.max_batch);
+    std::lock_guard<std::mutex> lk(e->mu);
+    SVCHECK(cb_guard(e, who));
+    if (n_seq != e->cached_B) return fail(SV_ESTATE, "%s: n_seq=%d but the cache holds %d sequences", who, n_seq, e->cached_B);
+    if (e->dbg_pos_hi + K1 > c.max_seq_len) return fail(SV_EINVAL, "%s: position %d would reach max_seq_len %d", who, e->dbg_pos_hi + K1 - 1, c.max_seq_len);
+    HIPCHECK(hipSetDevice(c.device));
+    hipStream_t st = (hipStream_t)stream;
+    const int rows = n_seq * K1;
+    const size_t mp = (size_t)e->pages_per_seq;
+    if (e->table_pending) { HIPCHECK(hipEventSynchronize(e->table_ev)); e->table_pending = false; }
+    std::vector<int32_t> table((size_t)rows * mp), pos0((size_t)n_seq), pos((size_t)rows);
+    HIPCHECK(hipMemcpyAsync(pos0.data(), e->positions, (size_t)n_seq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    for (int r = 0; r < rows; ++r) {
+        memcpy(table.data() + (size_t)r * mp, e->h_table + (size_t)(r / K1) * mp, mp * sizeof(int32_t));
+        pos[r] = pos0[r / K1] + r % K1;
+        if (pos[r] < 0 || pos[r] >= c.max_seq_len) return fail(SV_ESTATE, "%s: position %d of row %d outside the sequence's pages", who, pos[r], r);
+    }
+    for (int s = 0; s < n_seq; ++s) pos0[s] += K1;
+    HIPCHECK(hipMemcpyAsync(e->block_table, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(e->positions, pos.data(), pos.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    TmpBufs tmp;
+    bf16_t* bias;
+    SVCHECK(tmp.get(&bias, (size_t)e->ldws));
+    HIPCHECK(hipMemsetAsync(bias, 0, (size_t)e->ldws * sizeof(bf16_t), st));
+    if (dev_bias) HIPCHECK(hipMemcpyAsync(bias, dev_bias, (size_t)e->QKV * sizeof(bf16_t), hipMemcpyDeviceToDevice, st));
+    const int rows_ws = ((rows + 31) / 32) * 32;
+    for (int s = 0; s < splitk; ++s)
+        HIPCHECK(hipMemcpy2DAsync(e->ws + (size_t)s * rows_ws * e->ldws, (size_t)e->ldws * sizeof(float), dev_slabs + (size_t)s * rows * e->QKV,
+                                  (size_t)e->QKV * sizeof(float), (size_t)e->QKV * sizeof(float), rows, hipMemcpyDeviceToDevice, st));
+    AttnDecodeArgs ad;
+    attn_decode_args(e, layer, rows, e->ws, splitk, bias, e->xp_attn, ad);
+    launch_lookup_kv_write(lookup_kv_args(ad), st);
+    launch_attn_decode(ad, st);
+    unpack_rows(e->xp_attn, (bf16_t*)dev_out, c.n_head * e->dh, rows, c.n_head * e->dh, st);
+    // back to the n_seq-row layout (the host image still holds it), K1 positions further
+    HIPCHECK(hipMemcpyAsync(e->block_table, e->h_table, (size_t)rows * mp * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(e->positions, pos0.data(), (size_t)n_seq * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    e->dbg_pos_hi += K1;
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));
+    return 0;
+}
+extern "C" int sv_debug_set_lookup_drafts(sv_engine* e, const int32_t* host_stream, int32_t B, int32_t ld) {
+    if (!e) return fail(SV_EINVAL, "null engine");
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIPCHECK(hipSetDevice(e->cfg.device));
+    HIPCHECK(hipDeviceSynchronize());                // no step in flight reads the buffer that goes
+    e->lk_forced_B = 0; e->lk_forced_ld = 0;         // (the buffer stays: a kept graph of a forced call names its address)
+    if (!host_stream) return 0;
+    if (B < 1 || B > e->cfg.max_batch || ld < 1 || ld > e->cfg.max_seq_len)
+        return fail(SV_EINVAL, "sv_debug_set_lookup_drafts: bad B %d / ld %d (max_batch %d, max_seq_len %d)", B, ld, e->cfg.max_batch, e->cfg.max_seq_len);
+    for (size_t i = 0; i < (size_t)B * ld; ++i)      // a draft is fed to the embedding table
+        if (host_stream[i] < 0 || host_stream[i] >= e->cfg.vocab)
+            return fail(SV_EINVAL, "sv_debug_set_lookup_drafts: id %d outside the vocabulary (%d)", host_stream[i], e->cfg.vocab);
+    if (!e->lk_forced) SVCHECK(dalloc(e, &e->lk_forced, (size_t)e->cfg.max_batch * e->cfg.max_seq_len));
+    HIPCHECK(hipMemcpy(e->lk_forced, host_stream, (size_t)B * ld * sizeof(int32_t), hipMemcpyHostToDevice));
+    e->lk_forced_B = B; e->lk_forced_ld = ld;
+    return 0;
+}
+extern "C" int sv_op_lookup_accept(const int32_t* host_winners, const int32_t* host_rows, int32_t n_seq, int32_t K, int32_t max_ngram,
+                                   int32_t min_ngram, int32_t* host_hist, int32_t ld, int32_t* host_state, int32_t* host_call,
+                                   const int32_t* stop_ids, int32_t n_stop, int32_t eos, int32_t pad, int32_t max_new, int32_t vocab,
+                                   int32_t* host_next_rows, int32_t* host_next_positions, sv_stream stream) {
+    const char* who = "sv_op_lookup_accept";
+    if (!host_winners || !host_rows || !host_hist || !host_state || !host_call || !host_next_rows || !host_next_positions)
+        return fail(SV_EINVAL, "%s: null argument", who);
+    if (n_seq < 1 || n_seq > 64 || K < 0 || K > SV_LOOKUP_MAX_DRAFT || max_ngram < 1 || max_ngram > SV_LOOKUP_MAX_NGRAM || min_ngram < 1 ||
+        min_ngram > max_ngram || max_new < 1 || ld < max_new || vocab < 1 || n_stop < 0 || n_stop > 16 || (n_stop > 0 && !stop_ids))
+        return fail(SV_EINVAL, "%s: bad shape (n_seq %d, K %d, n-grams %d..%d, max_new %d, ld %d, vocab %d, n_stop %d)", who, n_seq, K, min_ngram,
+                    max_ngram, max_new, ld, vocab, n_stop);
+    const int K1 = K + 1, rows = n_seq * K1;
+    for (int s = 0; s < n_seq; ++s) {
+        const int32_t* q = host_state + 4 * s;
+        if (q[0] < 0 || q[0] > max_new || q[3] < 0 || q[3] > K || (!q[1] && q[0] + q[3] + 1 > max_new))
+            return fail(SV_EINVAL, "%s: sequence %d: n_emit %d with %d live drafts does not fit max_new %d", who, s, q[0], q[3], max_new);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    TmpBufs tmp;
+    int32_t *d_i;
+    float* d_val;
+    // one int32 block: state (counts[3] | n_emit | fin | base | n_draft | limit | ticket) | call {step, done, n_emitted, bad} | rows | positions | pidx | hist | stop
+    const size_t o_call = 4 * (size_t)n_seq + 8, o_rows = o_call + 4, o_pos = o_rows + rows, o_idx = o_pos + rows, o_hist = o_idx + (size_t)rows * 8,
+                 o_stop = o_hist + (size_t)n_seq * ld, total = o_stop + 16;
+    SVCHECK(tmp.get(&d_i, total));
+    SVCHECK(tmp.get(&d_val, (size_t)rows * 8));
+    std::vector<int32_t> h(total, 0);
+    std::vector<float> hv((size_t)rows * 8, -INFINITY);
+    int32_t* n_emit = h.data() + 3;
+    for (int s = 0; s < n_seq; ++s) {
+        n_emit[s] = host_state[4 * s]; n_emit[n_seq + s] = host_state[4 * s + 1]; n_emit[2 * n_seq + s] = host_state[4 * s + 2];
+        n_emit[3 * n_seq + s] = host_state[4 * s + 3];
+    }
+    h[0] = host_call[4]; h[1] = host_call[5]; h[2] = host_call[6];
+    h[3 + 4 * (size_t)n_seq] = host_call[0];
+    h[o_call + 1] = host_call[1]; h[o_call + 2] = host_call[2]; h[o_call + 3] = host_call[3];
+    for (int r = 0; r < rows; ++r) {
+        h[o_rows + r] = host_rows[r];
+        h[o_pos + r] = host_next_positions[r];          // in / out: a sequence that is finished keeps its rows as they are
+        for (int i = 0; i < 8; ++i) h[o_idx + (size_t)r * 8 + i] = 0x7fffffff;
+        h[o_idx + (size_t)r * 8 + (r & 7)] = host_winners[r];          // the winner sits in some slice, the others hold nothing
+        hv[(size_t)r * 8 + (r & 7)] = 1.f;
+    }
+    memcpy(h.data() + o_hist, host_hist, (size_t)n_seq * ld * sizeof(int32_t));
+    for (int i = 0; i < n_stop; ++i) h[o_stop + i] = stop_ids[i];
+    HIPCHECK(hipMemcpyAsync(d_i, h.data(), total * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_val, hv.data(), hv.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    LookupArgs a;
+    memset(&a, 0, sizeof(a));
+    a.counts = d_i; a.n_emit = d_i + 3; a.fin = a.n_emit + n_seq; a.base = a.fin + n_seq; a.n_draft = a.base + n_seq; a.limit = a.n_draft + n_seq;
+    a.ticket = reinterpret_cast<unsigned*>(a.limit + 1);
+    a.n_seq = n_seq; a.K = K; a.max_ngram = max_ngram; a.min_ngram = min_ngram;
+    a.cur_tok = d_i + o_rows; a.positions = d_i + o_pos; a.out_tok = d_i + o_hist; a.ld_out = ld; a.pval = d_val; a.pidx = d_i + o_idx;
+    a.done = d_i + o_call + 1; a.n_emitted = d_i + o_call + 2; a.bad = d_i + o_call + 3;
+    a.stop_ids = d_i + o_stop; a.n_stop = n_stop; a.eos = eos; a.pad = pad; a.max_new = max_new; a.V = vocab;
+    launch_lookup_step(a, st);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(h.data(), d_i, total * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    for (int s = 0; s < n_seq; ++s) {
+        host_state[4 * s] = n_emit[s]; host_state[4 * s + 1] = n_emit[n_seq + s]; host_state[4 * s + 2] = n_emit[2 * n_seq + s];
+        host_state[4 * s + 3] = n_emit[3 * n_seq + s];
+    }
+    host_call[0] = h[3 + 4 * (size_t)n_seq]; host_call[1] = h[o_call + 1]; host_call[2] = h[o_call + 2]; host_call[3] = h[o_call + 3];
+    host_call[4] = h[0]; host_call[5] = h[1]; host_call[6] = h[2]; host_call[7] = 0;
+    memcpy(host_next_rows, h.data() + o_rows, (size_t)rows * sizeof(int32_t));
+    memcpy(host_next_positions, h.data() + o_pos, (size_t)rows * sizeof(int32_t));
+    memcpy(host_hist, h.data() + o_hist, (size_t)n_seq * ld * sizeof(int32_t));
+    return 0;
+}
+// the lookup alone: one step that re-emits the history's last id with no draft in flight, then drafts behind the L ids
+extern "C" int sv_op_lookup_draft(const int32_t* host_hist, int32_t L, int32_t K, int32_t max_ngram, int32_t min_ngram, int32_t max_new,
+                                  int32_t* host_drafts, int32_t* n_drafts, sv_stream stream) {
+    if (!host_hist || !host_drafts || !n_drafts) return fail(SV_EINVAL, "sv_op_lookup_draft: null argument");
+    if (L < 1 || L > max_new || K < 1 || K > SV_LOOKUP_MAX_DRAFT) return fail(SV_EINVAL, "sv_op_lookup_draft: bad L %d / K %d (max_new %d)", L, K, max_new);
+    std::vector<int32_t> hist(host_hist, host_hist + L), win((size_t)K + 1, host_hist[L - 1]), rows((size_t)K + 1, 0), nrows((size_t)K + 1), npos((size_t)K + 1);
+    hist.resize((size_t)max_new, 0);
+    int32_t state[4] = {L - 1, 0, 0, 0}, call[8] = {max_new, 0, 0, 0, 0, 0, 0, 0};
+    SVCHECK(sv_op_lookup_accept(win.data(), rows.data(), 1, K, max_ngram, min_ngram, hist.data(), max_new, state, call, nullptr, 0, -1, 0, max_new,
+                                0x7fffffff, nrows.data(), npos.data(), stream));
+    *n_drafts = state[3];
+    for (int j = 0; j < state[3]; ++j) host_drafts[j] = nrows[(size_t)j + 1];
+    return 0;
+}
+extern "C" int sv_op_lookup_hold(float* dev_logits, int32_t ld, int32_t rows, int32_t K1, int32_t eos, int32_t min_new, const int32_t* host_n_emit,
+                                 sv_stream stream) {
+    if (!dev_logits || !host_n_emit) return fail(SV_EINVAL, "sv_op_lookup_hold: null argument");
+    if (rows < 1 || K1 < 1 || rows % K1 != 0 || eos < 0 || eos >= ld) return fail(SV_EINVAL, "sv_op_lookup_hold: bad rows %d / K1 %d / eos %d (ld %d)", rows, K1, eos, ld);
+    hipStream_t st = (hipStream_t)stream;
+    TmpBufs tmp;
+    int32_t* d_n;
+    SVCHECK(tmp.get(&d_n, (size_t)(rows / K1)));
+    HIPCHECK(hipMemcpyAsync(d_n, host_n_emit, (size_t)(rows / K1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    launch_lookup_hold_eos(dev_logits, ld, eos, d_n, K1, min_new, rows, st);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
 // SV_MLP_TRACE=1 at sv_create: wall-clock stamps (100 MHz ticks) of the fused MLP launch of the middle layer of the LAST decode step,
 // host_out [blocks][8] = {start, c_fc loop done, tile published, slice complete, end, XCC id, 0, 0}; returns the number of blocks
 extern "C" int sv_debug_mlp_trace(sv_engine* e, int64_t* host_out, int32_t capacity_blocks) {

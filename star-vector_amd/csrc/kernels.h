@@ -611,4 +611,36 @@ int preprocess_images(const uint8_t* const* dev_pixels, const int32_t* widths, c
                       int n, int out_size, int recipe, const float* mean3, const float* std3, float* dev_out, void* workspace,
                       size_t workspace_bytes, hipStream_t st);
 
+// ---- prompt-lookup speculative decoding (lookup/lookup.hip; DESIGN.md "Prompt-lookup decoding").  One verification step is a decode step over
+// n_seq x (K + 1) rows: row s * (K + 1) + j carries sequence s's last accepted token (j = 0) or its j-th draft, at position ctx_s + j, and its
+// block-table row is a copy of sequence s's -- all K + 1 rows alias the same pages.
+// The pre-write, per layer, between c_attn and the decode attention: EVERY row's k_new | v_new goes into its page slot with the arithmetic of
+// attn_decode_kernel (slabs summed in slab order, + bias, bf16; RoPE at the row's position with the same one-by-one bf16 roundings), so that
+// the unmodified attention kernel reads from the cache, for the siblings in front of a row, the bits a sequential decode would have left there.
+struct LookupKvArgs {
+    const float* ws; int splitk; int ldws; int rows_ws; const bf16_t* bias;      // the c_attn slabs, as AttnDecodeArgs has them
+    char* pool_layer; const int32_t* block_table; int max_pages; const int32_t* positions;
+    int rows, H, head_dim, n_kv; size_t kv_head_stride;
+    const float* rope_cos; const float* rope_sin;                                // nullptr: no rotary embedding
+};
+void launch_lookup_kv_write(const LookupKvArgs& a, hipStream_t st);
+// The call's state on the device.  Per sequence: tokens emitted, finished, prompt length, live drafts of the step in flight.  Per call: counts =
+// {verification steps, drafts verified, drafts accepted}; limit = the column count row 0's stop sequence allows (max_new until it fires);
+// ticket = arrivals of lookup_step_kernel's blocks (zero between launches).
+struct LookupArgs {
+    int32_t *n_emit, *fin, *base, *n_draft, *counts, *limit; unsigned* ticket;
+    int n_seq, K, max_ngram, min_ngram;
+    int32_t* cur_tok; int32_t* positions;           // [n_seq * (K + 1)] the next step's input rows
+    const int32_t* unfinished;                      // lookup_begin: [n_seq] as the first token's bookkeeping left it
+    int32_t* out_tok; int ld_out;                   // [n_seq][ld_out] every sequence's generated ids, at its own column
+    const float* pval; const int32_t* pidx;         // [rows][8] slice winners of launch_argmax_partial
+    int32_t *done, *n_emitted, *bad;                // the call's device scalars (FinishArgs)
+    const int32_t* stop_ids; int n_stop; int eos, pad, max_new, V;
+    const int32_t* forced; int forced_ld;           // sv_debug_set_lookup_drafts: draft j of sequence s is forced[s][n_emit_s + j]; nullptr: the lookup
+};
+void launch_lookup_begin(const LookupArgs& a, hipStream_t st);       // after the first token: rows 0 .. n_seq of cur_tok / positions -> the row layout
+void launch_lookup_step(const LookupArgs& a, hipStream_t st);        // accept, emit, stop / EOS / budget, draft the next step
+// the min-length hold of a verification step: logits[row][eos] = -inf while n_emit[row / K1] + row % K1 < min_new (in front of the argmax)
+void launch_lookup_hold_eos(float* logits, int ld, int eos, const int32_t* n_emit, int K1, int min_new, int rows, hipStream_t st);
+
 }  // namespace sv

@@ -369,6 +369,69 @@ class HipEngine:
             return self.generate(x, max_length, lengths=lens, n_samples=n_samples, logits_processors=lp, **kw)
         return self.generate(embeds, max_length, n_samples=n_samples, logits_processors=lp, **kw)
 
+    def generate_lookup(self, embeds, max_length: int, num_draft_tokens: int, max_ngram: int = 0, min_ngram: int = 0, lengths=None,
+                        eos_token_id: int = 0, pad_token_id: int = 0, stop_ids: Optional[Sequence[int]] = None, sync_every: int = 0,
+                        on_tokens=None, min_new_tokens: int = 0, return_counts: bool = False, **refused):
+        """Greedy ``generate`` with prompt-lookup speculative decoding (sv_generate_lookup; HF's ``prompt_lookup_num_tokens``): every step
+        verifies ``num_draft_tokens`` (1..15) drafted tokens of each sequence, drafted by an n-gram lookup (``max_ngram`` .. ``min_ngram``,
+        0 = 3 and 1) over the ids the sequence has generated, and emits the accepted ones plus one more.  The tokens are those of
+        ``generate`` / ``generate_ragged`` bit for bit.  ``embeds`` as there ([B, S0, D], or a list / packed tensor with ``lengths``).
+        ``num_draft_tokens=0`` is the plain call.  ``return_counts=True``: (tokens, dict(steps, drafted, accepted)).  Sampling, beam search, a
+        repetition penalty, processors, per-step outputs, statistics, top-k lists and n_samples > 1 raise NotImplementedError; so does
+        streaming (``on_tokens``) with more than one row."""
+        for name, off in (("do_sample", False), ("num_beams", 1), ("repetition_penalty", 1.0), ("logits_processors", None), ("scores_out", None),
+                          ("logits_out", None), ("return_outputs", False), ("token_stats", False), ("token_topk", None), ("n_samples", 1)):
+            if name in refused:
+                v = refused.pop(name)
+                if v is not None and v != off:
+                    raise NotImplementedError(f"generate_lookup: {name}={v!r} is not built with prompt-lookup decoding (greedy verification, tokens only)")
+        if refused:
+            raise TypeError(f"generate_lookup: unexpected arguments {sorted(refused)}")
+        lens_arr = None
+        if lengths is not None or isinstance(embeds, (list, tuple)):
+            x, lens_arr, lens = self._packed(embeds, lengths)
+            B, S0, D = len(lens), max(lens), x.shape[1]
+        else:
+            x = _need(embeds, torch.bfloat16, "inputs_embeds")
+            B, S0, D = x.shape
+        if D != self.cfg.hidden:
+            raise ValueError("inputs_embeds hidden size mismatch")
+        max_new = max_length - S0
+        if max_new <= 0:
+            raise ValueError(f"max_length ({max_length}) must exceed the prompt length ({S0})")
+        stops = list(stop_ids) if stop_ids else []
+        arr = (C.c_int32 * max(len(stops), 1))(*stops) if stops else None
+        sp = SvSampling(0, 1.0, 1.0, int(max_length), int(eos_token_id), int(pad_token_id), len(stops),
+                        C.cast(arr, C.POINTER(C.c_int32)) if stops else None, 0, int(sync_every), 1.0, 1, 1.0, 0, 0, None, None,
+                        max(int(min_new_tokens or 0), 0))
+        cb, cb_errors = None, []
+        if on_tokens is not None:
+            cb, cb_errors = token_callback(on_tokens)
+            sp.on_tokens = C.cast(cb, C.c_void_p)
+        lk = _lib.SvLookup(int(num_draft_tokens), int(max_ngram), int(min_ngram))
+        out = torch.empty(B, max_new, dtype=torch.int64, device=x.device)
+        n, counts = C.c_int32(0), (C.c_int32 * 3)()
+        check(self.lib.sv_generate_lookup(self._h, _ptr(x), B, lens_arr, S0, C.byref(sp), C.byref(lk), _ptr(out), C.byref(n), counts, _stream()),
+              "sv_generate_lookup")
+        if cb_errors:
+            raise cb_errors[0]
+        toks = out[:, :n.value]
+        if return_counts:
+            return toks, dict(steps=counts[0], drafted=counts[1], accepted=counts[2])
+        return toks
+
+    def set_lookup_drafts(self, stream) -> None:
+        """Test surface (sv_debug_set_lookup_drafts): draft j of sequence b of the generate_lookup calls that follow is stream[b][n_emit_b + j]
+        instead of the lookup; ``None`` clears it."""
+        if stream is None:
+            check(self.lib.sv_debug_set_lookup_drafts(self._h, None, 0, 0), "sv_debug_set_lookup_drafts")
+            return
+        t = torch.as_tensor(stream, dtype=torch.int32).cpu().contiguous()
+        if t.dim() == 1:
+            t = t.view(1, -1)
+        arr = (C.c_int32 * t.numel())(*t.flatten().tolist())
+        check(self.lib.sv_debug_set_lookup_drafts(self._h, arr, t.shape[0], t.shape[1]), "sv_debug_set_lookup_drafts")
+
     def block_table_row(self, row: int) -> List[int]:
         """The block-table row of a decode row / slot as the device holds it (sv_debug_block_table)."""
         buf = (C.c_int32 * 4096)()
@@ -825,6 +888,24 @@ class HipEngine:
         out = torch.empty(B, self.cfg.hidden, dtype=torch.bfloat16, device=slabs.device)   # n_head * head_dim == hidden
         check(self.lib.sv_debug_attn_decode_slabs(self._h, int(layer), _ptr(slabs), splitk, _ptr(bias), B, _ptr(out),
                                                   int(bool(advance)), _stream()), "sv_debug_attn_decode_slabs")
+        return out
+
+    def debug_attn_decode_draft(self, layer: int, slabs: torch.Tensor, n_seq: int, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """What a verification step of generate_lookup does around one attention launch (sv_debug_attn_decode_draft): slabs
+        [splitk, n_seq * K1, QKV] float32, row s * K1 + j = the c_attn output of sequence s's j-th next token.  The rows of a sequence share its
+        pages at positions pos_s + j, every row's K / V is pre-written, ONE attention launch runs over all rows; returns
+        [n_seq * K1, n_head * head_dim] bf16 and leaves the engine where K1 advancing ``debug_attn_decode_slabs`` calls leave it."""
+        slabs = _need(slabs, torch.float32, "slabs")
+        splitk, rows = slabs.shape[0], slabs.shape[1]
+        if rows % int(n_seq):
+            raise ValueError(f"{rows} rows are not n_seq={n_seq} sequences of equally many rows")
+        if bias is not None:
+            bias = _need(bias, torch.bfloat16, "bias")
+            if bias.numel() != slabs.shape[2]:
+                raise ValueError("bias must be bf16 [QKV]")
+        out = torch.empty(rows, self.cfg.hidden, dtype=torch.bfloat16, device=slabs.device)
+        check(self.lib.sv_debug_attn_decode_draft(self._h, int(layer), _ptr(slabs), splitk, _ptr(bias), int(n_seq), rows // int(n_seq),
+                                                  _ptr(out), _stream()), "sv_debug_attn_decode_draft")
         return out
 
     def profile_decode_step(self, B: int, iters: int = 5) -> Dict[str, Dict[str, float]]:
@@ -1787,3 +1868,48 @@ def op_sample_top_p(logits, temperature, top_p, seed, step, top_k=0):
     check(lib.sv_op_sample(_ptr(logits), B, V, V, float(temperature), int(top_k), float(top_p), int(seed), int(step),
                            _ptr(out), _stream()))
     return out
+
+
+def op_lookup_draft(hist: Sequence[int], K: int, max_ngram: int = 3, min_ngram: int = 1, max_new: Optional[int] = None) -> List[int]:
+    """The n-gram lookup of generate_lookup on one history (sv_op_lookup_draft; lookup.draft is its restatement)."""
+    lib = _lib.load()
+    L = len(hist)
+    max_new = int(max_new if max_new is not None else L + K + 1)
+    h = (C.c_int32 * max(L, 1))(*[int(t) for t in hist])
+    out, n = (C.c_int32 * 16)(), C.c_int32(0)
+    check(lib.sv_op_lookup_draft(h, L, int(K), int(max_ngram), int(min_ngram), max_new, out, C.byref(n), _stream()), "sv_op_lookup_draft")
+    return [out[j] for j in range(n.value)]
+
+
+def op_lookup_accept(state, winners) -> None:
+    """One lookup_step_kernel launch (sv_op_lookup_accept) on a lookup.LookupState, updated in place as LookupState.step(winners) updates it."""
+    lib = _lib.load()
+    n_seq, K1, ld = state.n_seq, state.K + 1, state.max_new
+    flat = lambda rows: (C.c_int32 * (n_seq * K1))(*[int(t) for r in rows for t in r])
+    hist = (C.c_int32 * (n_seq * ld))(*[int(t) for h in state.hist for t in h])
+    st = (C.c_int32 * (4 * n_seq))(*[int(v) for s in range(n_seq)
+                                     for v in (state.n_emit[s], state.finished[s], state.base[s], state.n_draft[s])])
+    call = (C.c_int32 * 8)(state.limit, int(state.done), state.n_emitted, state.bad, state.steps, state.drafted, state.accepted, 0)
+    stop = (C.c_int32 * max(len(state.stop), 1))(*[int(t) for t in state.stop])
+    nrows, npos = (C.c_int32 * (n_seq * K1))(), flat(state.positions)
+    check(lib.sv_op_lookup_accept(flat(winners), flat(state.rows), n_seq, state.K, state.max_ngram, state.min_ngram, hist, ld, st, call,
+                                  stop if state.stop else None, len(state.stop), int(state.eos), int(state.pad), state.max_new, int(state.vocab),
+                                  nrows, npos, _stream()), "sv_op_lookup_accept")
+    for s in range(n_seq):
+        state.hist[s] = [hist[s * ld + c] for c in range(ld)]
+        state.n_emit[s], state.finished[s], state.base[s], state.n_draft[s] = st[4 * s], bool(st[4 * s + 1]), st[4 * s + 2], st[4 * s + 3]
+        state.rows[s] = [nrows[s * K1 + j] for j in range(K1)]
+        state.positions[s] = [npos[s * K1 + j] for j in range(K1)]
+    state.limit, state.done, state.n_emitted, state.bad, state.steps, state.drafted, state.accepted = \
+        call[0], bool(call[1]), call[2], call[3], call[4], call[5], call[6]
+
+
+def op_lookup_hold(logits: torch.Tensor, K1: int, eos: int, min_new: int, n_emit: Sequence[int]) -> torch.Tensor:
+    """The min-length hold of a verification step on caller-given rows (sv_op_lookup_hold): a copy of logits [rows, ld] fp32 with
+    [r, eos] = -inf wherever n_emit[r // K1] + r % K1 < min_new."""
+    lib = _lib.load()
+    x = _need(logits, torch.float32, "logits").clone()
+    rows, ld = x.shape
+    arr = (C.c_int32 * len(n_emit))(*[int(v) for v in n_emit])
+    check(lib.sv_op_lookup_hold(_ptr(x), ld, rows, int(K1), int(eos), int(min_new), arr, _stream()), "sv_op_lookup_hold")
+    return x

@@ -630,6 +630,7 @@ class HipCausalLM(_EngineModule):
                  return_dict_in_generate: bool = False, output_scores: bool = False, output_logits: bool = False,
                  share_prompt: bool = True, no_repeat_ngram_size: int = 0, bad_words_ids=None, min_p: Optional[float] = None,
                  output_token_logprobs: bool = False, output_top_logprobs: Optional[int] = None, top_logprobs_source: str = "raw",
+                 prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None,
                  **unused):
         # top_k: the reference never passes it; its pinned transformers==4.49.0 (pyproject.toml:18) defaults
         # GenerationConfig.top_k to 50, so every do_sample call there is top-k 50 followed by top-p.  Same default here.
@@ -732,6 +733,13 @@ class HipCausalLM(_EngineModule):
                 attention_mask = None if attention_mask is None else attention_mask.repeat_interleave(num_return_sequences, dim=0)
         if repetition_penalty is not None and not repetition_penalty > 0:
             raise ValueError("`repetition_penalty` has to be a strictly positive float")   # HF's own check
+        # HF's prompt lookup decoding (prompt_lookup_num_tokens = K, max_matching_ngram_size): greedy generate that verifies K drafted tokens
+        # per step (sv_generate_lookup) -- the tokens are those of the call without it.  What the engine does not build raises, naming it.
+        if prompt_lookup_num_tokens:
+            return self._generate_lookup(inputs_embeds, attention_mask, prompt_lookup_num_tokens, max_matching_ngram_size, dict(
+                do_sample=do_sample, num_beams=num_beams, repetition_penalty=repetition_penalty, processors=proc, outputs=want, stats=stats,
+                topk=topk, num_return_sequences=num_return_sequences), max_length, min_length, eos_token_id, pad_token_id, stopping_criteria,
+                streamer, return_dict_in_generate)
         if attention_mask is not None and not bool((attention_mask == 1).all()):
             # Padded prompts (text2svg with captions of different lengths; the v2 tokenizer pads on the left, llm/starcoder2.py:53).
             # HF masks the padded keys and numbers positions by cumsum(mask), so a padded row behaves exactly like the same row
@@ -831,6 +839,45 @@ class HipCausalLM(_EngineModule):
         if topk:
             res.update({k: out.get(k) for k in ("top_token_ids", "top_logprobs", "token_ranks")})
         return res
+
+    def _generate_lookup(self, inputs_embeds, attention_mask, num_tokens, ngram, asked, max_length, min_length, eos_token_id, pad_token_id,
+                         stopping_criteria, streamer, return_dict):
+        K = int(num_tokens)
+        if K < 1:
+            raise ValueError(f"`prompt_lookup_num_tokens` has to be a positive integer, but is {num_tokens}")
+        refused = [name for name, on in (
+            ("do_sample", bool(asked["do_sample"])), ("num_beams > 1", int(asked["num_beams"]) > 1),
+            ("repetition_penalty != 1", asked["repetition_penalty"] is not None and float(asked["repetition_penalty"]) != 1.0),
+            ("no_repeat_ngram_size / bad_words_ids / min_p", bool(asked["processors"])), ("output_scores / output_logits", bool(asked["outputs"])),
+            ("output_token_logprobs", bool(asked["stats"])), ("output_top_logprobs", bool(asked["topk"])),
+            ("num_return_sequences > 1", int(asked["num_return_sequences"]) > 1),
+            ("a padded attention_mask", attention_mask is not None and not bool((attention_mask == 1).all())),
+            ("a batcher (continuous batching does not draft)", getattr(self, "batcher", None) is not None and not _in_exclusive_job()),
+            ("a streamer with more than one row", streamer is not None and inputs_embeds.shape[0] > 1)) if on]
+        if refused:
+            raise NotImplementedError("prompt_lookup_num_tokens with " + ", ".join(refused) + " is not built: greedy verification of drafted "
+                                      "tokens (sv_generate_lookup) takes greedy calls without per-step outputs")
+        eng = self._engine
+        if not hasattr(eng, "generate_lookup"):
+            raise NotImplementedError("prompt_lookup_num_tokens: this engine has no generate_lookup")
+        on_tokens = None
+        if streamer is not None:
+            streamer.put(torch.empty(inputs_embeds.shape[0], 0, dtype=torch.long))
+
+            def on_tokens(tokens, first_col):
+                for c in range(tokens.shape[1]):
+                    streamer.put(tokens[:, c])
+        min_new = max(int(min_length or 0) - inputs_embeds.shape[1], 0)
+        lock = getattr(eng, "call_lock", None) or contextlib.nullcontext()
+        with lock:
+            out = eng.generate_lookup(
+                inputs_embeds.to(torch.bfloat16), max_length=int(max_length), num_draft_tokens=K, max_ngram=int(ngram or 0),
+                eos_token_id=int(self.eos_token_id if eos_token_id is None else eos_token_id),
+                pad_token_id=int(self.pad_token_id if pad_token_id is None else pad_token_id),
+                stop_ids=self._stop_ids(stopping_criteria), on_tokens=on_tokens, **({"min_new_tokens": min_new} if min_new else {}))
+        if streamer is not None:
+            streamer.end()
+        return generate_output(False, sequences=out) if return_dict else out
 
     def _processor_args(self, no_repeat_ngram_size, bad_words_ids, min_p, do_sample, eos_token_id):
         """HF's own checks of no_repeat_ngram_size / bad_words_ids / min_p (generation/logits_process.py, transformers 4.49), then the
@@ -1041,6 +1088,9 @@ class StarVectorStarCoder(nn.Module):
             # extension: pins the device sampler's random stream (default: drawn per call from torch's generator, so that
             # `torch.manual_seed` reproduces a run and repeated calls differ, as with HF's torch.multinomial)
             "seed": base_kwargs.get("seed"),
+            # HF's prompt lookup decoding, off unless asked for (HipCausalLM.generate)
+            "prompt_lookup_num_tokens": base_kwargs.get("prompt_lookup_num_tokens"),
+            "max_matching_ngram_size": base_kwargs.get("max_matching_ngram_size"),
         }
 
     def _get_im2svg_specific_kwargs(self, kwargs):                    # starvector_base.py:289-295
