@@ -436,6 +436,18 @@ typedef struct sv_lookup {
 } sv_lookup;
 int  sv_generate_lookup(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, int32_t S0, const sv_sampling* sp,
                         const sv_lookup* lookup, int64_t* dev_out_tokens, int32_t* n_generated, int32_t* host_counts3, sv_stream stream);
+/* sv_generate_lookup with the selection the call's sv_sampling asks for (entry point appended, SV_ABI_VERSION unchanged): do_sample 0 or 1 with
+ * temperature / top_k / top_p / seed, and any repetition_penalty.  Still token-exact, per seed: the sampler's random number is a pure function
+ * of (seed, step, row), so row j of sequence s draws with the triple sv_generate uses at column n_emit_s + j of row s, over the same logits
+ * bits; a draft is accepted when it equals the token DRAWN in front of it (what HF does for do_sample with prompt_lookup_num_tokens: draw at
+ * every position, match against the drafts).  The repetition penalty of row j sees the sequence's generated ids plus the drafts d_1 .. d_j in
+ * front of the row -- the plain call's set at that column once those drafts are accepted.  Tokens and *n_generated are those of
+ * sv_generate / sv_generate_ragged with the same sv_sampling, BIT FOR BIT; rectangular and ragged prompts, EOS / pad, min_new_tokens, the row-0
+ * stop sequence, streaming with B == 1.  lookup NULL or num_draft_tokens == 0: the plain call.
+ * SV_ENOTSUP, naming the offender: num_beams > 1, streaming with B > 1, B x (K + 1) > max_batch, live continuous-batching slots (SV_ESTATE as
+ * every generate call).  The signature carries no n_samples, processors, per-step outputs, statistics or top-k lists: none is built with it. */
+int  sv_generate_lookup_sampled(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, int32_t S0, const sv_sampling* sp,
+                                const sv_lookup* lookup, int64_t* dev_out_tokens, int32_t* n_generated, int32_t* host_counts3, sv_stream stream);
 /* sv_forward_logprobs plus, for every kept position, the k best ids of softmax(logits / temperature) over the bf16 row, their log-probs
  * (dev_topk_ids int32 / dev_topk_logprobs fp32, [B][n_keep][k]) and the rank of the target (dev_rank int32 [B][n_keep], may be NULL; target
  * -100: rank 0).  Order, ties, the (-1, -inf) tail and the rank as in sv_generate_topk, keyed on the bf16 logit; a slot holds

@@ -200,7 +200,17 @@ int  sv_debug_attn_decode_slabs(sv_engine* e, int32_t layer, const float* dev_sl
  *                        out: host_next_rows, the next step's ids.  A winner outside [0, vocab) stands for a row without a finite logit.
  *   sv_op_lookup_draft   the lookup alone on one history host_hist [L]: the drafts (at most K, and at most max_new - L - 1) and their count.
  *   sv_op_lookup_hold    the min-length hold on caller-given rows: dev_logits fp32 [rows][ld], row r belongs to sequence r / K1 with
- *                        host_n_emit [rows / K1] ids emitted; logits[r][eos] = -inf while n_emit + r % K1 < min_new. */
+ *                        host_n_emit [rows / K1] ids emitted; logits[r][eos] = -inf while n_emit + r % K1 < min_new.
+ *   sv_op_lookup_sample  one lookup_sample_kernel launch (sv_generate_lookup_sampled's draw) on caller-given rows: dev_logits fp32 [rows][ld],
+ *                        row r = s * K1 + j draws with (seed, host_n_emit[s] + j, s) -- what sv_op_sample draws for that row placed at row
+ *                        index s with step = host_n_emit[s] + j.  host_seen (may be NULL) [rows][seen_words]: one bitmap per ROW, with penalty.
+ *                        Out: host_tokens [rows], the id lookup_step_kernel reads from the row's slices (0x7fffffff: no finite score), and,
+ *                        if not NULL, the slices themselves host_pval8 / host_pidx8 [rows][8].
+ *   sv_op_lookup_seen    one lookup_seen_kernel launch on given state: host_hist [n_seq][ld] generated ids, in / out host_seq_seen
+ *                        [n_seq][words] = the sequences' bitmaps over columns [0, L_before), host_L_before / host_L_after [n_seq] the columns
+ *                        in front of and behind the step, host_n_draft [n_seq] and host_rows [n_seq * K1] the NEXT step's live drafts and ids.
+ *                        Out: host_row_seen [n_seq * K1][words], row s * K1 + j = the sequence's set plus rows 1 .. j (dead rows: row 0's).
+ *                        sv_debug_set_lookup_drafts applies to sv_generate_lookup_sampled as it does to sv_generate_lookup. */
 int  sv_debug_attn_decode_draft(sv_engine* e, int32_t layer, const float* dev_slabs_f32, int32_t splitk, const void* dev_bias, int32_t n_seq,
                                 int32_t K1, void* dev_out, sv_stream stream);
 int  sv_debug_set_lookup_drafts(sv_engine* e, const int32_t* host_stream, int32_t B, int32_t ld);
@@ -212,6 +222,12 @@ int  sv_op_lookup_draft(const int32_t* host_hist, int32_t L, int32_t K, int32_t 
                         int32_t* host_drafts, int32_t* n_drafts, sv_stream stream);
 int  sv_op_lookup_hold(float* dev_logits, int32_t ld, int32_t rows, int32_t K1, int32_t eos, int32_t min_new, const int32_t* host_n_emit,
                        sv_stream stream);
+int  sv_op_lookup_sample(const float* dev_logits, int32_t rows, int32_t V, int32_t ld, int32_t K1, const int32_t* host_n_emit, float temperature,
+                         int32_t top_k, float top_p, uint64_t seed, const uint32_t* host_seen, int32_t seen_words, float penalty,
+                         int32_t* host_tokens, float* host_pval8, int32_t* host_pidx8, sv_stream stream);
+int  sv_op_lookup_seen(const int32_t* host_hist, int32_t ld, int32_t n_seq, int32_t K1, int32_t words, const int32_t* host_L_before,
+                       const int32_t* host_L_after, const int32_t* host_n_draft, const int32_t* host_rows, uint32_t* host_seq_seen,
+                       uint32_t* host_row_seen, sv_stream stream);
 
 /* HIP-event timing of one decode step by kernel class, on the cache state left by the last
  * sv_generate / sv_prefill (bench.py roofline leg).  out: 10 doubles, [2k] = ms per step in class k

@@ -156,6 +156,8 @@ PRODUCT_PROTOTYPES = {
     "sv_generate_topk": (_I, [_P, _P, _I, C.POINTER(_I), _I, _I, C.POINTER(SvSampling), C.POINTER(SvLogitsProcessors),
                               C.POINTER(SvGenerateOutputs), C.POINTER(SvTokenStats), C.POINTER(SvTokenTopk), _P, C.POINTER(_I), _P]),
     "sv_generate_lookup": (_I, [_P, _P, _I, C.POINTER(_I), _I, C.POINTER(SvSampling), C.POINTER(SvLookup), _P, C.POINTER(_I), C.POINTER(_I), _P]),
+    "sv_generate_lookup_sampled": (_I, [_P, _P, _I, C.POINTER(_I), _I, C.POINTER(SvSampling), C.POINTER(SvLookup), _P, C.POINTER(_I), C.POINTER(_I),
+                                        _P]),
     "sv_forward_topk": (_I, [_P, _P, _I, _I, _I, _P, _F, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "sv_forward_logprobs_ragged": (_I, [_P, _P, _I, C.POINTER(_I), C.POINTER(_I), _P, _F, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "sv_cb_admit_shared": (_I, [_P, _P, _I, C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(SvCbRequest), C.POINTER(_I), _P]),
@@ -218,6 +220,10 @@ DEBUG_PROTOTYPES = {
                                  _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _P]),
     "sv_op_lookup_draft": (_I, [C.POINTER(_I), _I, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _P]),
     "sv_op_lookup_hold": (_I, [_P, _I, _I, _I, _I, _I, C.POINTER(_I), _P]),
+    "sv_op_lookup_sample": (_I, [_P, _I, _I, _I, _I, C.POINTER(_I), _F, _I, _F, C.c_uint64, C.POINTER(C.c_uint32), _I, _F, C.POINTER(_I),
+                                 C.POINTER(_F), C.POINTER(_I), _P]),
+    "sv_op_lookup_seen": (_I, [C.POINTER(_I), _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_uint32),
+                               C.POINTER(C.c_uint32), _P]),
     "sv_debug_decode_plan": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     "sv_profile_decode_step": (_I, [_P, _I, _I, C.POINTER(C.c_double), _P]),
     "sv_profile_ttft": (_I, [_P, _P, _I, _P, _I, _I, C.POINTER(C.c_double), _P]),

@@ -638,6 +638,10 @@ static void lookup_args(sv_engine* e, int n_seq, const sv_lookup& lk, const sv_s
 // The driver beside generate_attempt (same GenCall, same retry): prompt pass and first token exactly as the plain call takes them, then
 // verification steps -- decode_forward over B x (K + 1) rows with the K / V pre-write in front of every attention launch, the min-length
 // hold, the slice argmax, lookup_step_kernel -- captured once and replayed.
+// sv_generate_lookup_sampled comes through here with the selection switch: do_sample replaces the slice argmax by lookup_sample_kernel (the
+// plain sampler's code with the plain call's (seed, column, sequence) triple, handed over as slice winners), a repetition penalty gives every
+// ROW its own bitmap in e->seen (lookup_seen_kernel behind lookup_step_kernel) and both selections read it by row.  The sampler's stream does
+// not depend on the attempt: the rerun after an ownership fall-back returns the same tokens.
 static int lookup_attempt(sv_engine* e, const GenCall& c) {
     const sv_sampling* sp = c.sp;
     const sv_lookup& lk = *c.lookup;
@@ -645,24 +649,35 @@ static int lookup_attempt(sv_engine* e, const GenCall& c) {
     const int32_t* lens = c.lens;
     SVCHECK(check_ready(e));
     if ((long long)B * K1 > e->cfg.max_batch || B > 64)
-        return fail(SV_ENOTSUP, "sv_generate_lookup: B %d x (num_draft_tokens %d + 1) rows exceed engine max_batch %d", B, K1 - 1, e->cfg.max_batch);
+        return fail(SV_ENOTSUP, "%s: B %d x (num_draft_tokens %d + 1) rows exceed engine max_batch %d", c.who, B, K1 - 1, e->cfg.max_batch);
     const int rows = B * K1;
-    if (lens) SVCHECK(ragged_check_lens(e, lens, B, "sv_generate_lookup", nullptr, nullptr));
+    if (lens) SVCHECK(ragged_check_lens(e, lens, B, c.who, nullptr, nullptr));
     const int max_new = sp->max_length - S0;
     if (max_new <= 0) return fail(SV_EINVAL, "max_length (%d) must exceed the prompt length (%d)", sp->max_length, S0);
     if (S0 + max_new > e->cfg.max_seq_len) return fail(SV_EINVAL, "max_length %d exceeds engine max_seq_len %d", sp->max_length, e->cfg.max_seq_len);
     if (sp->n_stop < 0 || sp->n_stop > 16) return fail(SV_EINVAL, "stop sequence length %d unsupported (0..16)", sp->n_stop);
     if (sp->n_stop > 0 && !sp->stop_ids) return fail(SV_EINVAL, "n_stop > 0 but stop_ids is null");
+    // sv_generate_lookup_sampled: the selection the call asks for (sv_generate_lookup refuses both in front of this driver)
+    const bool sample = sp->do_sample != 0;
+    const bool pen = sp->repetition_penalty > 0.f && sp->repetition_penalty != 1.0f;
+    if (sample && !(sp->temperature > 0.f && sp->top_p > 0.f)) return fail(SV_EINVAL, "temperature and top_p must be > 0");
+    if (pen && (size_t)e->seen_words * sizeof(uint32_t) > 65536)
+        return fail(SV_ENOTSUP, "%s: repetition_penalty with a vocabulary of %d ids is not built (a sequence's bitmap must fit 64 KB of LDS)", c.who, e->cfg.vocab);
     std::lock_guard<std::mutex> lk_mu(e->mu);
     HIPCHECK(hipSetDevice(e->cfg.device));
     HIPCHECK(hipEventRecord(e->gen_event, (hipStream_t)c.stream));
     hipStream_t st = e->gen_stream;
     HIPCHECK(hipStreamWaitEvent(st, e->gen_event, 0));
-    SVCHECK(cb_guard(e, "sv_generate_lookup"));
+    SVCHECK(cb_guard(e, c.who));
     if (!e->lk_state) SVCHECK(dalloc(e, &e->lk_state, (size_t)4 * e->cfg.max_batch + 8));
+    if (pen && !e->lk_seen) {
+        SVCHECK(dalloc(e, &e->lk_seen, (size_t)64 * e->seen_words));
+        SVCHECK(dalloc(e, &e->lk_seen_cols, (size_t)64));
+    }
 
     auto t0 = std::chrono::steady_clock::now();
     HIPCHECK(hipMemsetAsync(e->d_bad, 0, sizeof(int32_t), st));
+    if (pen) HIPCHECK(hipMemsetAsync(e->seen, 0, (size_t)((B + 31) / 32) * 32 * e->seen_words * sizeof(uint32_t), st));      // as the plain call clears it
     if (lens) {
         SVCHECK(assign_pages_ragged(e, B, lens, max_new, st));
         SVCHECK(prefill_forward_ragged(e, (const bf16_t*)c.embeds, B, lens, st));
@@ -709,19 +724,38 @@ static int lookup_attempt(sv_engine* e, const GenCall& c) {
         e->cached_B = 0;                         // the cache is in no layout sv_decode_step could continue
         LookupArgs la;
         lookup_args(e, B, lk, *sp, max_new, la);
+        // the penalty's seen sets: row b of the B-row layout holds what the first token's bookkeeping left; they go to the per-sequence buffer
+        // BEFORE any row of the B x K1 layout is written (rows b and s * K1 overlap), then every row gets its sequence's set plus its drafts
+        if (pen) HIPCHECK(hipMemcpyAsync(e->lk_seen, e->seen, (size_t)B * e->seen_words * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
         launch_lookup_begin(la, st);
+        LookupSeenArgs ls;
+        ls.seq_seen = e->lk_seen; ls.seq_cols = e->lk_seen_cols; ls.row_seen = e->seen; ls.words = e->seen_words; ls.n_seq = B; ls.K1 = K1; ls.begin = 1;
+        ls.n_emit = la.n_emit; ls.n_draft = la.n_draft; ls.cur_tok = la.cur_tok; ls.out_tok = la.out_tok; ls.ld_out = la.ld_out; ls.done = la.done;
+        if (pen) launch_lookup_seen(ls, st);
+        ls.begin = 0;
         e->lookup_on = true;
         const bool hold = sp->min_new_tokens > 0 && sp->eos_token_id >= 0 && sp->eos_token_id < e->cfg.vocab;
+        const uint32_t* seen = pen ? e->seen : nullptr;
+        const float penalty = pen ? sp->repetition_penalty : 1.f;
+        LookupSampleArgs sa;
+        sa.logits = e->logits; sa.ld = e->Vpad; sa.V = e->cfg.vocab; sa.rows = rows; sa.K1 = K1; sa.n_emit = la.n_emit; sa.done = la.done;
+        sa.temperature = sp->temperature; sa.top_p = sp->top_p; sa.top_k = sp->top_k; sa.seed = sp->seed;
+        sa.seen = seen; sa.seen_words = e->seen_words; sa.penalty = penalty; sa.pval = e->am_val; sa.pidx = e->am_idx;
         const auto one_step = [&]() {
             decode_forward(e, rows, st);
             if (hold) launch_lookup_hold_eos(e->logits, e->Vpad, sp->eos_token_id, la.n_emit, K1, sp->min_new_tokens, rows, st);
-            launch_argmax_partial(e->logits, e->Vpad, e->cfg.vocab, e->am_val, e->am_idx, rows, nullptr, e->seen_words, 1.f, st);
+            if (sample) launch_lookup_sample(sa, st);
+            else launch_argmax_partial(e->logits, e->Vpad, e->cfg.vocab, e->am_val, e->am_idx, rows, seen, e->seen_words, penalty, st);
             launch_lookup_step(la, st);
+            if (pen) launch_lookup_seen(ls, st);
         };
         if (graph_enabled()) {
-            char key[320];
-            snprintf(key, sizeof(key), "B%d|K%d|ng%d.%d|n%d|eos%d|pad%d|ns%d|mn%d|x%d|fo%d|f%p.%d", B, K1 - 1, lk.max_ngram, lk.min_ngram, max_new,
-                     sp->eos_token_id, sp->pad_token_id, sp->n_stop, sp->min_new_tokens, e->exp, e->fused_off ? 1 : 0, (const void*)la.forced, la.forced_ld);
+            char key[480];
+            int kn = snprintf(key, sizeof(key), "B%d|K%d|ng%d.%d|n%d|eos%d|pad%d|ns%d|mn%d|x%d|fo%d|f%p.%d", B, K1 - 1, lk.max_ngram, lk.min_ngram, max_new,
+                              sp->eos_token_id, sp->pad_token_id, sp->n_stop, sp->min_new_tokens, e->exp, e->fused_off ? 1 : 0, (const void*)la.forced, la.forced_ld);
+            // the selection of sv_generate_lookup_sampled is part of the captured step (the seed travels by value in the sampler's arguments)
+            if (sample) kn += snprintf(key + kn, sizeof(key) - kn, "|s.T%a.k%d.p%a.sd%llu", (double)sp->temperature, sp->top_k, (double)sp->top_p, (unsigned long long)sp->seed);
+            if (pen) snprintf(key + kn, sizeof(key) - kn, "|r%a", (double)sp->repetition_penalty);
             if (e->lk_gexec && e->lk_graph_key == key) {
                 gexec = e->lk_gexec;
             } else {
@@ -755,8 +789,8 @@ static int lookup_attempt(sv_engine* e, const GenCall& c) {
         }
     }
     e->h_flags[1] = e->h_flags[10];
-    SVCHECK(report_bad_logits(e, st, "sv_generate_lookup", e->h_flags[11]));
-    if (!e->h_flags[0]) return fail(SV_EHIP, "sv_generate_lookup: the call did not end within its budget (%d steps)", steps);
+    SVCHECK(report_bad_logits(e, st, c.who, e->h_flags[11]));
+    if (!e->h_flags[0]) return fail(SV_EHIP, "%s: the call did not end within its budget (%d steps)", c.who, steps);
     const int n_emit = e->h_flags[1];
     if (n_emit < 1 || n_emit > max_new) return fail(SV_EHIP, "generation bookkeeping failed (n_emitted=%d)", n_emit);
     if (B == 1) SVCHECK(stream_upto(n_emit));
@@ -772,14 +806,14 @@ static int lookup_attempt(sv_engine* e, const GenCall& c) {
     e->timing_graph = gexec ? 1.0 : 0.0;
     return 0;
 }
-extern "C" int sv_generate_lookup(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, int32_t S0, const sv_sampling* sp,
-                                  const sv_lookup* lookup, int64_t* dev_out_tokens, int32_t* n_generated, int32_t* host_counts3, sv_stream stream) {
+// sampled = false: sv_generate_lookup (greedy, no penalty); true: sv_generate_lookup_sampled (the selection of the call's sv_sampling)
+static int lookup_call(const char* who, bool sampled, sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, int32_t S0,
+                       const sv_sampling* sp, const sv_lookup* lookup, int64_t* dev_out_tokens, int32_t* n_generated, int32_t* host_counts3, sv_stream stream) {
     if (!lookup || lookup->num_draft_tokens == 0) {
         if (host_counts3) host_counts3[0] = host_counts3[1] = host_counts3[2] = 0;
         if (host_lens) return sv_generate_ragged(e, dev_embeds_packed, B, host_lens, sp, nullptr, dev_out_tokens, n_generated, stream);
         return sv_generate(e, dev_embeds_packed, B, S0, sp, dev_out_tokens, n_generated, stream);
     }
-    const char* who = "sv_generate_lookup";
     sv_lookup lk = *lookup;
     if (lk.num_draft_tokens < 0 || lk.num_draft_tokens > SV_LOOKUP_MAX_DRAFT)
         return fail(SV_EINVAL, "%s: num_draft_tokens %d unsupported (0..%d)", who, lk.num_draft_tokens, SV_LOOKUP_MAX_DRAFT);
@@ -791,14 +825,27 @@ extern "C" int sv_generate_lookup(sv_engine* e, const void* dev_embeds_packed, i
     if (lk.min_ngram == 0) lk.min_ngram = 1;
     GenCall c{who, GC_ARGS, dev_embeds_packed, B, S0, host_lens, 1, sp, nullptr, nullptr, nullptr, nullptr, dev_out_tokens, n_generated, stream};
     SVCHECK(check_gen_call(c));
-    if (sp->do_sample) return fail(SV_ENOTSUP, "%s: do_sample is not built (verification is greedy: the drafts are compared with the arg-max)", who);
+    if (sp->do_sample && !sampled) return fail(SV_ENOTSUP, "%s: do_sample is not built (verification is greedy: the drafts are compared with the arg-max)", who);
     if (sp->num_beams > 1) return fail(SV_ENOTSUP, "%s: num_beams %d is not built (beam rows reorder their caches)", who, sp->num_beams);
-    if (sp->repetition_penalty > 0.f && sp->repetition_penalty != 1.0f)
+    if (!sampled && sp->repetition_penalty > 0.f && sp->repetition_penalty != 1.0f)
         return fail(SV_ENOTSUP, "%s: repetition_penalty %g is not built (a draft row's penalty depends on the drafts in front of it)", who, sp->repetition_penalty);
     if (sp->on_tokens && B > 1) return fail(SV_ENOTSUP, "%s: streaming (on_tokens) with B %d > 1 is not built (the sequences advance at different rates)", who, B);
     c.lookup = &lk;
     c.counts3 = host_counts3;
     return generate_retry(e, c);
+}
+extern "C" int sv_generate_lookup(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, int32_t S0, const sv_sampling* sp,
+                                  const sv_lookup* lookup, int64_t* dev_out_tokens, int32_t* n_generated, int32_t* host_counts3, sv_stream stream) {
+    return lookup_call("sv_generate_lookup", false, e, dev_embeds_packed, B, host_lens, S0, sp, lookup, dev_out_tokens, n_generated, host_counts3, stream);
+}
+// The same call with the selection its sv_sampling asks for: do_sample with temperature / top_k / top_p / seed, any repetition_penalty.  Row j of
+// sequence s draws with (seed, n_emit_s + j, s) -- the plain call's triple at that column -- over the plain call's logits bits, against the
+// plain call's seen set once the drafts in front of it are accepted: the tokens are sv_generate's / sv_generate_ragged's, bit for bit.
+extern "C" int sv_generate_lookup_sampled(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, int32_t S0,
+                                          const sv_sampling* sp, const sv_lookup* lookup, int64_t* dev_out_tokens, int32_t* n_generated,
+                                          int32_t* host_counts3, sv_stream stream) {
+    return lookup_call("sv_generate_lookup_sampled", true, e, dev_embeds_packed, B, host_lens, S0, sp, lookup, dev_out_tokens, n_generated, host_counts3,
+                       stream);
 }
 
 // lens != nullptr: the ragged form -- S0 is the longest prompt (the budget counts from it), sequence b has lens[b] rows

@@ -247,6 +247,10 @@ struct sv_engine {
     int32_t* lk_state = nullptr;
     int32_t* lk_forced = nullptr;
     int lk_forced_B = 0, lk_forced_ld = 0;
+    // sv_generate_lookup_sampled with a repetition penalty (lookup_seen_kernel): one bitmap of generated ids per SEQUENCE [64][seen_words] and
+    // the columns it covers [64]; e->seen then holds one bitmap per ROW of the step in flight (allocated by the first such call)
+    uint32_t* lk_seen = nullptr;
+    int32_t* lk_seen_cols = nullptr;
     std::string lk_graph_key;
     hipGraph_t lk_graph = nullptr;
     hipGraphExec_t lk_gexec = nullptr;

@@ -343,6 +343,96 @@ extern "C" int sv_op_lookup_hold(float* dev_logits, int32_t ld, int32_t rows, in
     HIPCHECK(hipStreamSynchronize(st));
     return 0;
 }
+// sv_generate_lookup_sampled's draw on caller-given rows (lookup_sampled/lookup_sampled.hip)
+extern "C" int sv_op_lookup_sample(const float* dev_logits, int32_t rows, int32_t V, int32_t ld, int32_t K1, const int32_t* host_n_emit, float temperature,
+                                   int32_t top_k, float top_p, uint64_t seed, const uint32_t* host_seen, int32_t seen_words, float penalty,
+                                   int32_t* host_tokens, float* host_pval8, int32_t* host_pidx8, sv_stream stream) {
+    const char* who = "sv_op_lookup_sample";
+    if (!dev_logits || !host_n_emit || !host_tokens) return fail(SV_EINVAL, "%s: null argument", who);
+    if (rows < 1 || rows > (1 << 16) || K1 < 1 || K1 > SV_LOOKUP_MAX_DRAFT + 1 || rows % K1 != 0 || V < 1 || ld < V)
+        return fail(SV_EINVAL, "%s: bad rows %d / K1 %d / V %d (ld %d)", who, rows, K1, V, ld);
+    if (!(temperature > 0.f) || !(top_p > 0.f)) return fail(SV_EINVAL, "%s: temperature and top_p must be > 0", who);
+    if (host_seen && (seen_words < (V + 31) / 32 || !(penalty > 0.f))) return fail(SV_EINVAL, "%s: seen_words %d below vocab / 32, or penalty <= 0", who, seen_words);
+    const int n_seq = rows / K1;
+    for (int s = 0; s < n_seq; ++s)
+        if (host_n_emit[s] < 0) return fail(SV_EINVAL, "%s: n_emit %d of sequence %d", who, host_n_emit[s], s);
+    hipStream_t st = (hipStream_t)stream;
+    TmpBufs tmp;
+    int32_t *d_n, *d_idx;
+    float* d_val;
+    uint32_t* d_seen = nullptr;
+    SVCHECK(tmp.get(&d_n, (size_t)n_seq));
+    SVCHECK(tmp.get(&d_idx, (size_t)rows * 8));
+    SVCHECK(tmp.get(&d_val, (size_t)rows * 8));
+    HIPCHECK(hipMemcpyAsync(d_n, host_n_emit, (size_t)n_seq * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (host_seen) {
+        SVCHECK(tmp.get(&d_seen, (size_t)rows * seen_words));
+        HIPCHECK(hipMemcpyAsync(d_seen, host_seen, (size_t)rows * seen_words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    }
+    LookupSampleArgs a;
+    a.logits = dev_logits; a.ld = ld; a.V = V; a.rows = rows; a.K1 = K1; a.n_emit = d_n; a.done = nullptr;
+    a.temperature = temperature; a.top_p = top_p; a.top_k = top_k; a.seed = seed;
+    a.seen = d_seen; a.seen_words = seen_words; a.penalty = host_seen ? penalty : 1.f; a.pval = d_val; a.pidx = d_idx;
+    launch_lookup_sample(a, st);
+    HIPCHECK(hipGetLastError());
+    std::vector<float> hv((size_t)rows * 8);
+    std::vector<int32_t> hi((size_t)rows * 8);
+    HIPCHECK(hipMemcpyAsync(hv.data(), d_val, hv.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(hi.data(), d_idx, hi.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    for (int r = 0; r < rows; ++r) {                 // lookup_step_kernel's merge: the largest value, the lowest index on a tie
+        float best = -INFINITY;
+        int32_t nxt = 0x7fffffff;
+        for (int i = 0; i < 8; ++i) {
+            const float ov = hv[(size_t)r * 8 + i];
+            const int32_t oi = hi[(size_t)r * 8 + i];
+            if (ov > best || (ov == best && oi < nxt)) { best = ov; nxt = oi; }
+        }
+        host_tokens[r] = nxt;
+    }
+    if (host_pval8) memcpy(host_pval8, hv.data(), hv.size() * sizeof(float));
+    if (host_pidx8) memcpy(host_pidx8, hi.data(), hi.size() * sizeof(int32_t));
+    return 0;
+}
+// the seen sets of a verification step on given state (lookup_seen_kernel)
+extern "C" int sv_op_lookup_seen(const int32_t* host_hist, int32_t ld, int32_t n_seq, int32_t K1, int32_t words, const int32_t* host_L_before,
+                                 const int32_t* host_L_after, const int32_t* host_n_draft, const int32_t* host_rows, uint32_t* host_seq_seen,
+                                 uint32_t* host_row_seen, sv_stream stream) {
+    const char* who = "sv_op_lookup_seen";
+    if (!host_hist || !host_L_before || !host_L_after || !host_n_draft || !host_rows || !host_seq_seen || !host_row_seen)
+        return fail(SV_EINVAL, "%s: null argument", who);
+    if (n_seq < 1 || n_seq > 64 || K1 < 1 || K1 > SV_LOOKUP_MAX_DRAFT + 1 || words < 1 || words > 16384 || ld < 1)
+        return fail(SV_EINVAL, "%s: bad shape (n_seq %d, K1 %d, words %d, ld %d)", who, n_seq, K1, words, ld);
+    for (int s = 0; s < n_seq; ++s)
+        if (host_L_before[s] < 0 || host_L_after[s] < host_L_before[s] || host_L_after[s] > ld || host_n_draft[s] < 0 || host_n_draft[s] > K1 - 1)
+            return fail(SV_EINVAL, "%s: sequence %d: columns %d..%d of %d, %d live drafts of %d", who, s, host_L_before[s], host_L_after[s], ld,
+                        host_n_draft[s], K1 - 1);
+    hipStream_t st = (hipStream_t)stream;
+    const int rows = n_seq * K1;
+    TmpBufs tmp;
+    int32_t* d_i;      // cols | n_emit | n_draft | rows | hist
+    uint32_t *d_seq, *d_row;
+    const size_t o_emit = (size_t)n_seq, o_nd = 2 * (size_t)n_seq, o_rows = 3 * (size_t)n_seq, o_hist = o_rows + rows, total = o_hist + (size_t)n_seq * ld;
+    SVCHECK(tmp.get(&d_i, total));
+    SVCHECK(tmp.get(&d_seq, (size_t)n_seq * words));
+    SVCHECK(tmp.get(&d_row, (size_t)rows * words));
+    std::vector<int32_t> h(total);
+    for (int s = 0; s < n_seq; ++s) { h[s] = host_L_before[s]; h[o_emit + s] = host_L_after[s]; h[o_nd + s] = host_n_draft[s]; }
+    memcpy(h.data() + o_rows, host_rows, (size_t)rows * sizeof(int32_t));
+    memcpy(h.data() + o_hist, host_hist, (size_t)n_seq * ld * sizeof(int32_t));
+    HIPCHECK(hipMemcpyAsync(d_i, h.data(), total * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_seq, host_seq_seen, (size_t)n_seq * words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemsetAsync(d_row, 0, (size_t)rows * words * sizeof(uint32_t), st));
+    LookupSeenArgs a;
+    a.seq_seen = d_seq; a.seq_cols = d_i; a.row_seen = d_row; a.words = words; a.n_seq = n_seq; a.K1 = K1; a.begin = 0;
+    a.n_emit = d_i + o_emit; a.n_draft = d_i + o_nd; a.cur_tok = d_i + o_rows; a.out_tok = d_i + o_hist; a.ld_out = ld; a.done = nullptr;
+    launch_lookup_seen(a, st);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(host_seq_seen, d_seq, (size_t)n_seq * words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(host_row_seen, d_row, (size_t)rows * words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    return 0;
+}
 
 // SV_MLP_TRACE=1 at sv_create: wall-clock stamps (100 MHz ticks) of the fused MLP launch of the middle layer of the LAST decode step,
 // host_out [blocks][8] = {start, c_fc loop done, tile published, slice complete, end, XCC id, 0, 0}; returns the number of blocks

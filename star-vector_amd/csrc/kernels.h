@@ -643,4 +643,31 @@ void launch_lookup_step(const LookupArgs& a, hipStream_t st);        // accept, 
 // the min-length hold of a verification step: logits[row][eos] = -inf while n_emit[row / K1] + row % K1 < min_new (in front of the argmax)
 void launch_lookup_hold_eos(float* logits, int ld, int eos, const int32_t* n_emit, int K1, int min_new, int rows, hipStream_t st);
 
+// ---- the sampled / penalised selection of a verification step (lookup_sampled/lookup_sampled.hip; sv_generate_lookup_sampled).
+// Row r = s * K1 + j draws one token from its row of `logits` with the plain sampler's own code (sample_row.h) and the triple the plain call
+// uses at that column: (seed, step = n_emit[s] + j, row = s).  The token is handed to lookup_step_kernel in the form it merges: slice 0 of the
+// row's pval / pidx = (0, token), the other slices (-inf, 0x7fffffff); a row without a finite score holds the sentinel in every slice.
+struct LookupSampleArgs {
+    const float* logits; int ld; int V; int rows; int K1;
+    const int32_t* n_emit;                                           // [rows / K1]
+    const int32_t* done;                                             // device scalar or nullptr: nothing is drawn once it is set
+    float temperature, top_p; int top_k; uint64_t seed;
+    const uint32_t* seen; int seen_words; float penalty;             // [rows][seen_words] per ROW (lookup_seen_kernel); nullptr = off
+    float* pval; int32_t* pidx;                                      // [rows][8]
+};
+void launch_lookup_sample(const LookupSampleArgs& a, hipStream_t st);
+// The repetition penalty's seen sets of a verification step, one block per sequence behind lookup_step_kernel:
+//   seq_seen[s] |= { out_tok[s][c] : seq_cols[s] <= c < n_emit[s] }, seq_cols[s] = n_emit[s]          (the ids the step emitted)
+//   row_seen[s * K1 + j] = seq_seen[s] | { cur_tok[s * K1 + 1 .. j] } for j <= n_draft[s], = seq_seen[s] for the dead rows behind
+// begin != 0 (the launch behind lookup_begin_kernel): seq_seen holds the sets the first token's bookkeeping left, nothing is emitted.
+struct LookupSeenArgs {
+    uint32_t* seq_seen; int32_t* seq_cols;                           // [n_seq][words], [n_seq]
+    uint32_t* row_seen;                                              // [n_seq * K1][words]
+    int words, n_seq, K1, begin;
+    const int32_t *n_emit, *n_draft, *cur_tok;                       // as lookup_step_kernel left them
+    const int32_t* out_tok; int ld_out;
+    const int32_t* done;                                             // device scalar or nullptr
+};
+void launch_lookup_seen(const LookupSeenArgs& a, hipStream_t st);
+
 }  // namespace sv

@@ -387,6 +387,40 @@ class HipEngine:
                     raise NotImplementedError(f"generate_lookup: {name}={v!r} is not built with prompt-lookup decoding (greedy verification, tokens only)")
         if refused:
             raise TypeError(f"generate_lookup: unexpected arguments {sorted(refused)}")
+        return self._lookup_call("sv_generate_lookup", embeds, max_length, num_draft_tokens, max_ngram, min_ngram, lengths, eos_token_id,
+                                 pad_token_id, stop_ids, sync_every, on_tokens, min_new_tokens, return_counts)
+
+    def generate_lookup_sampled(self, embeds, max_length: int, num_draft_tokens: int, max_ngram: int = 0, min_ngram: int = 0, lengths=None,
+                                eos_token_id: int = 0, pad_token_id: int = 0, stop_ids: Optional[Sequence[int]] = None, sync_every: int = 0,
+                                on_tokens=None, min_new_tokens: int = 0, do_sample: bool = False, temperature: float = 1.0, top_k: int = 0,
+                                top_p: float = 1.0, seed: int = 0, repetition_penalty: float = 1.0, return_counts: bool = False, **refused):
+        """``generate_lookup`` with the selection the call asks for (sv_generate_lookup_sampled): ``do_sample`` with ``temperature`` / ``top_k`` /
+        ``top_p`` / ``seed``, and any ``repetition_penalty``.  Token-exact per seed: the tokens are those of ``generate`` / ``generate_ragged``
+        with the same arguments bit for bit -- a row draws with the (seed, step, row) triple the plain call uses at its column, and a draft is
+        accepted when it equals the token drawn in front of it.  Everything else as ``generate_lookup``; beam search, processors, per-step
+        outputs, statistics, top-k lists and n_samples > 1 raise NotImplementedError, naming the argument; so does streaming with more than
+        one row."""
+        for name, off in (("num_beams", 1), ("logits_processors", None), ("scores_out", None), ("logits_out", None), ("return_outputs", False),
+                          ("token_stats", False), ("token_topk", None), ("n_samples", 1)):
+            if name in refused:
+                v = refused.pop(name)
+                if v is not None and v != off:
+                    raise NotImplementedError(f"generate_lookup_sampled: {name}={v!r} is not built with prompt-lookup decoding (tokens only, one "
+                                              "sample per prompt, no beams)")
+        if refused:
+            raise TypeError(f"generate_lookup_sampled: unexpected arguments {sorted(refused)}")
+        if do_sample and not (float(temperature) > 0 and float(top_p) > 0):
+            raise ValueError("generate_lookup_sampled: temperature and top_p must be > 0")
+        if repetition_penalty is not None and not float(repetition_penalty) > 0:
+            raise ValueError("generate_lookup_sampled: repetition_penalty has to be a strictly positive float")
+        return self._lookup_call("sv_generate_lookup_sampled", embeds, max_length, num_draft_tokens, max_ngram, min_ngram, lengths, eos_token_id,
+                                 pad_token_id, stop_ids, sync_every, on_tokens, min_new_tokens, return_counts, do_sample=bool(do_sample),
+                                 temperature=float(temperature), top_k=int(top_k or 0), top_p=float(top_p), seed=int(seed),
+                                 repetition_penalty=float(1.0 if repetition_penalty is None else repetition_penalty))
+
+    def _lookup_call(self, entry, embeds, max_length, num_draft_tokens, max_ngram, min_ngram, lengths, eos_token_id, pad_token_id, stop_ids,
+                     sync_every, on_tokens, min_new_tokens, return_counts, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0,
+                     repetition_penalty=1.0):
         lens_arr = None
         if lengths is not None or isinstance(embeds, (list, tuple)):
             x, lens_arr, lens = self._packed(embeds, lengths)
@@ -401,9 +435,9 @@ class HipEngine:
             raise ValueError(f"max_length ({max_length}) must exceed the prompt length ({S0})")
         stops = list(stop_ids) if stop_ids else []
         arr = (C.c_int32 * max(len(stops), 1))(*stops) if stops else None
-        sp = SvSampling(0, 1.0, 1.0, int(max_length), int(eos_token_id), int(pad_token_id), len(stops),
-                        C.cast(arr, C.POINTER(C.c_int32)) if stops else None, 0, int(sync_every), 1.0, 1, 1.0, 0, 0, None, None,
-                        max(int(min_new_tokens or 0), 0))
+        sp = SvSampling(1 if do_sample else 0, temperature, top_p, int(max_length), int(eos_token_id), int(pad_token_id), len(stops),
+                        C.cast(arr, C.POINTER(C.c_int32)) if stops else None, seed & (2 ** 64 - 1), int(sync_every), repetition_penalty, 1, 1.0, 0,
+                        top_k, None, None, max(int(min_new_tokens or 0), 0))
         cb, cb_errors = None, []
         if on_tokens is not None:
             cb, cb_errors = token_callback(on_tokens)
@@ -411,8 +445,7 @@ class HipEngine:
         lk = _lib.SvLookup(int(num_draft_tokens), int(max_ngram), int(min_ngram))
         out = torch.empty(B, max_new, dtype=torch.int64, device=x.device)
         n, counts = C.c_int32(0), (C.c_int32 * 3)()
-        check(self.lib.sv_generate_lookup(self._h, _ptr(x), B, lens_arr, S0, C.byref(sp), C.byref(lk), _ptr(out), C.byref(n), counts, _stream()),
-              "sv_generate_lookup")
+        check(getattr(self.lib, entry)(self._h, _ptr(x), B, lens_arr, S0, C.byref(sp), C.byref(lk), _ptr(out), C.byref(n), counts, _stream()), entry)
         if cb_errors:
             raise cb_errors[0]
         toks = out[:, :n.value]
@@ -421,8 +454,8 @@ class HipEngine:
         return toks
 
     def set_lookup_drafts(self, stream) -> None:
-        """Test surface (sv_debug_set_lookup_drafts): draft j of sequence b of the generate_lookup calls that follow is stream[b][n_emit_b + j]
-        instead of the lookup; ``None`` clears it."""
+        """Test surface (sv_debug_set_lookup_drafts): draft j of sequence b of the generate_lookup / generate_lookup_sampled calls that follow
+        is stream[b][n_emit_b + j] instead of the lookup; ``None`` clears it."""
         if stream is None:
             check(self.lib.sv_debug_set_lookup_drafts(self._h, None, 0, 0), "sv_debug_set_lookup_drafts")
             return
@@ -1913,3 +1946,46 @@ def op_lookup_hold(logits: torch.Tensor, K1: int, eos: int, min_new: int, n_emit
     arr = (C.c_int32 * len(n_emit))(*[int(v) for v in n_emit])
     check(lib.sv_op_lookup_hold(_ptr(x), ld, rows, int(K1), int(eos), int(min_new), arr, _stream()), "sv_op_lookup_hold")
     return x
+
+
+def op_lookup_sample(logits: torch.Tensor, K1: int, n_emit: Sequence[int], temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
+                     seen=None, penalty: float = 1.0, return_slices: bool = False):
+    """The draw of generate_lookup_sampled on caller-given rows (sv_op_lookup_sample): logits [rows, ld] fp32, row s * K1 + j draws with
+    (seed, n_emit[s] + j, s).  ``seen``: per-row sets of ids (one iterable per row) for the repetition ``penalty``.  Returns the id of every
+    row as lookup_step_kernel reads it (0x7fffffff: no finite score); ``return_slices``: also the [rows, 8] values and ids of the hand-over."""
+    lib = _lib.load()
+    x = _need(logits, torch.float32, "logits")
+    rows, ld = x.shape
+    arr = (C.c_int32 * len(n_emit))(*[int(v) for v in n_emit])
+    words, bits = 0, None
+    if seen is not None:
+        words = (ld + 31) // 32
+        bits = (C.c_uint32 * (rows * words))()
+        for r, ids in enumerate(seen):
+            for i in ids:
+                bits[r * words + (int(i) >> 5)] |= 1 << (int(i) & 31)
+    out, pv, pi = (C.c_int32 * rows)(), (C.c_float * (rows * 8))(), (C.c_int32 * (rows * 8))()
+    check(lib.sv_op_lookup_sample(_ptr(x), rows, ld, ld, int(K1), arr, float(temperature), int(top_k), float(top_p), int(seed) & (2 ** 64 - 1), bits, words,
+                                  float(penalty), out, pv, pi, _stream()), "sv_op_lookup_sample")
+    if return_slices:
+        return list(out), [list(pv[r * 8:r * 8 + 8]) for r in range(rows)], [list(pi[r * 8:r * 8 + 8]) for r in range(rows)]
+    return list(out)
+
+
+def op_lookup_seen(hist, L_before: Sequence[int], L_after: Sequence[int], n_draft: Sequence[int], rows, vocab: int, seq_seen=None):
+    """One lookup_seen_kernel launch (sv_op_lookup_seen): hist [n_seq][ld] generated ids, seq_seen the sequences' id sets over columns
+    [0, L_before) (default: empty), rows [n_seq][K1] the next step's ids with n_draft live drafts.  Returns (sequence sets, row sets) as
+    Python sets of ids -- every set bit of the bitmaps, whatever its position."""
+    lib = _lib.load()
+    n_seq, ld, K1 = len(hist), len(hist[0]), len(rows[0])
+    words = (int(vocab) + 31) // 32
+    ia = lambda v: (C.c_int32 * len(v))(*[int(t) for t in v])
+    seq = (C.c_uint32 * (n_seq * words))()
+    for s, ids in enumerate(seq_seen or []):
+        for i in ids:
+            seq[s * words + (int(i) >> 5)] |= 1 << (int(i) & 31)
+    row = (C.c_uint32 * (n_seq * K1 * words))()
+    check(lib.sv_op_lookup_seen(ia([t for h in hist for t in h]), ld, n_seq, K1, words, ia(L_before), ia(L_after), ia(n_draft),
+                                ia([t for r in rows for t in r]), seq, row, _stream()), "sv_op_lookup_seen")
+    unpack = lambda buf, k: {w * 32 + b for w in range(words) for b in range(32) if (buf[k * words + w] >> b) & 1}
+    return [unpack(seq, s) for s in range(n_seq)], [unpack(row, r) for r in range(n_seq * K1)]

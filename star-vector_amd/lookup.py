@@ -2,6 +2,10 @@
 draft, accept, emit -- with no engine and no GPU.  The CPU tests hold this restatement to its invariant (whatever the drafts are, the emitted
 stream is the plain greedy stream); the GPU tests hold the kernels to this restatement.
 
+The second half restates csrc/lookup_sampled/lookup_sampled.hip (sv_generate_lookup_sampled): a CHOOSER that is a function of (sequence,
+column, prefix) stands for the sampler -- its random number is a function of (seed, step = column, row = sequence), its scores a function of
+the prefix -- and SeenSets stands for the repetition penalty's bitmaps as lookup_seen_kernel keeps them.
+
 State of a call over n_seq sequences, as the device keeps it:
     hist[s]      the ids sequence s has generated, at its own column (a list that grows; pads behind an early end)
     n_emit[s]    ids emitted, finished[s], base[s] = prompt length, n_draft[s] = live drafts of the step in flight
@@ -194,4 +198,100 @@ def lookup_greedy(model: Model, n_seq: int, K: int, max_new: int, eos: int = -1,
                 row.append(model(s, prefix, st.hold_eos(s, j if live else 0, min_new)))
             winners.append(row)
         st.step(winners)
+    return st.tokens(), st
+
+
+# ---- sv_generate_lookup_sampled: the call's own selection verifies the drafts ---------------------------------------------------------------
+# (sequence, column, ids in front of the column, seen set or None, EOS barred) -> the id at that column.  Any deterministic function will do:
+# the sampler is one (seed fixed), and so is the arg-max under a repetition penalty.
+Chooser = Callable[[int, int, List[int], Optional[frozenset], bool], int]
+
+
+class SeenSets:
+    """The repetition penalty's seen sets as the device keeps them in lookup mode (lookup_seen_kernel): one set per SEQUENCE, grown by the ids
+    each step emits (columns [cols[s], n_emit[s]) of the history), and from it one set per ROW of the next step: the sequence's set plus the
+    drafts in front of the row, rows 1 .. j; a dead row (j > n_draft) gets row 0's set."""
+
+    def __init__(self, n_seq: int, K: int):
+        self.n_seq, self.K = n_seq, K
+        self.seq = [set() for _ in range(n_seq)]
+        self.cols = [0] * n_seq
+        self.rows = [[set() for _ in range(K + 1)] for _ in range(n_seq)]
+
+    def begin(self, first_sets: Sequence[Sequence[int]], st: LookupState) -> None:
+        """Behind LookupState.begin: first_sets[s] = what the first token's bookkeeping left for sequence s."""
+        self.seq = [set(int(t) for t in x) for x in first_sets]
+        self.cols = list(st.n_emit)
+        self._write_rows(st)
+
+    def step(self, st: LookupState) -> None:
+        """Behind LookupState.step."""
+        for s in range(self.n_seq):
+            for c in range(self.cols[s], st.n_emit[s]):
+                self.seq[s].add(st.hist[s][c])
+            self.cols[s] = st.n_emit[s]
+        self._write_rows(st)
+
+    def _write_rows(self, st: LookupState) -> None:
+        for s in range(self.n_seq):
+            cur = set(self.seq[s])
+            self.rows[s][0] = set(cur)
+            for j in range(1, self.K + 1):
+                if j <= st.n_draft[s]:
+                    cur.add(st.rows[s][j])
+                    self.rows[s][j] = set(cur)
+                else:
+                    self.rows[s][j] = set(self.seq[s])
+
+
+def plain_chosen(chooser: Chooser, n_seq: int, max_new: int, eos: int = -1, pad: int = 0, stop: Sequence[int] = (), min_new: int = 0,
+                 penalty: bool = False):
+    """The plain call with a chooser: plain_greedy's bookkeeping; with `penalty` every emitted id (pads included) joins its row's seen set,
+    as finish_step does."""
+    seen = [set() for _ in range(n_seq)]
+
+    def model(s, prefix, barred):
+        return chooser(s, len(prefix), prefix, frozenset(seen[s]) if penalty else None, barred)
+    hist = [[] for _ in range(n_seq)]
+    unf = [True] * n_seq
+    for t in range(max_new):
+        for s in range(n_seq):
+            tok = model(s, list(hist[s]), t < min_new) if unf[s] else pad
+            hist[s].append(tok)
+            seen[s].add(tok)
+            unf[s] = unf[s] and tok != eos
+        fired = len(stop) > 0 and t + 1 >= len(stop) and hist[0][t + 1 - len(stop):] == list(stop)
+        if fired or not any(unf) or t + 1 >= max_new:
+            break
+    return hist
+
+
+def lookup_chosen(chooser: Chooser, n_seq: int, K: int, max_new: int, eos: int = -1, pad: int = 0, stop: Sequence[int] = (), min_new: int = 0,
+                  max_ngram: int = 3, min_ngram: int = 1, forced=None, prompt_lens: Optional[Sequence[int]] = None, penalty: bool = False):
+    """The lookup call with a chooser: returns (tokens, state).  Row j of sequence s chooses for column n_emit[s] + j, shown the sequence's ids
+    followed by its first j drafts, against the seen set SeenSets keeps for that row.  Both are the plain call's at that column as long as
+    the drafts in front of the row are right -- and only then is the row's choice emitted."""
+    first = plain_chosen(chooser, n_seq, 1, eos, pad, stop, min_new, penalty)
+    st = LookupState(n_seq=n_seq, K=K, max_new=max_new, eos=eos, pad=pad, stop=tuple(stop), max_ngram=max_ngram, min_ngram=min_ngram, forced=forced)
+    toks = [h[0] for h in first]
+    fired = len(stop) == 1 and toks[0] == stop[0]
+    unf = [t != eos for t in toks]
+    if fired or not any(unf) or max_new <= 1:
+        return [[t] for t in toks], st
+    st.begin(toks, prompt_lens or [0] * n_seq, unf)
+    sets = SeenSets(n_seq, K)
+    sets.begin([[t] for t in toks], st)
+    while not st.done:
+        winners = []
+        for s in range(n_seq):
+            ctx = st.hist[s][:st.n_emit[s]]
+            row = []
+            for j in range(K + 1):
+                live = j <= st.n_draft[s]
+                prefix = ctx + st.rows[s][1:j + 1] if live else ctx
+                jj = j if live else 0
+                row.append(chooser(s, st.n_emit[s] + jj, prefix, frozenset(sets.rows[s][j]) if penalty else None, st.hold_eos(s, jj, min_new)))
+            winners.append(row)
+        st.step(winners)
+        sets.step(st)
     return st.tokens(), st

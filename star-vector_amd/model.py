@@ -631,11 +631,16 @@ class HipCausalLM(_EngineModule):
                  share_prompt: bool = True, no_repeat_ngram_size: int = 0, bad_words_ids=None, min_p: Optional[float] = None,
                  output_token_logprobs: bool = False, output_top_logprobs: Optional[int] = None, top_logprobs_source: str = "raw",
                  prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None,
-                 **unused):
+                 prompt_lookup_sampling: bool = False, **unused):
         # top_k: the reference never passes it; its pinned transformers==4.49.0 (pyproject.toml:18) defaults
         # GenerationConfig.top_k to 50, so every do_sample call there is top-k 50 followed by top-p.  Same default here.
         if inputs_embeds is None:
             raise ValueError("inputs_embeds is required (the reference always generates from embeddings)")
+        # prompt_lookup_sampling=True (an extension, opt-in): prompt_lookup_num_tokens may come with do_sample and / or a repetition penalty
+        # (sv_generate_lookup_sampled: the tokens of the same call without drafts, per seed).  Alone it asks for nothing that could be done.
+        if prompt_lookup_sampling and not prompt_lookup_num_tokens:
+            raise ValueError("`prompt_lookup_sampling` needs `prompt_lookup_num_tokens`: it selects how drafted tokens are verified, and "
+                             "without drafts there is nothing to verify")
         # HF structured outputs (return_dict_in_generate): without it output_scores / output_logits are ignored, as HF ignores them
         want = False
         if return_dict_in_generate:
@@ -735,11 +740,13 @@ class HipCausalLM(_EngineModule):
             raise ValueError("`repetition_penalty` has to be a strictly positive float")   # HF's own check
         # HF's prompt lookup decoding (prompt_lookup_num_tokens = K, max_matching_ngram_size): greedy generate that verifies K drafted tokens
         # per step (sv_generate_lookup) -- the tokens are those of the call without it.  What the engine does not build raises, naming it.
+        # With prompt_lookup_sampling the call's own selection verifies the drafts (sv_generate_lookup_sampled): sampling, repetition penalty.
         if prompt_lookup_num_tokens:
             return self._generate_lookup(inputs_embeds, attention_mask, prompt_lookup_num_tokens, max_matching_ngram_size, dict(
                 do_sample=do_sample, num_beams=num_beams, repetition_penalty=repetition_penalty, processors=proc, outputs=want, stats=stats,
                 topk=topk, num_return_sequences=num_return_sequences), max_length, min_length, eos_token_id, pad_token_id, stopping_criteria,
-                streamer, return_dict_in_generate)
+                streamer, return_dict_in_generate,
+                sampling=dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed) if prompt_lookup_sampling else None)
         if attention_mask is not None and not bool((attention_mask == 1).all()):
             # Padded prompts (text2svg with captions of different lengths; the v2 tokenizer pads on the left, llm/starcoder2.py:53).
             # HF masks the padded keys and numbers positions by cumsum(mask), so a padded row behaves exactly like the same row
@@ -841,25 +848,30 @@ class HipCausalLM(_EngineModule):
         return res
 
     def _generate_lookup(self, inputs_embeds, attention_mask, num_tokens, ngram, asked, max_length, min_length, eos_token_id, pad_token_id,
-                         stopping_criteria, streamer, return_dict):
+                         stopping_criteria, streamer, return_dict, sampling=None):
+        # sampling = None: greedy verification (generate_lookup); a dict of the warpers and the seed: the call's own selection
+        # (generate_lookup_sampled), which takes do_sample and a repetition penalty
         K = int(num_tokens)
         if K < 1:
             raise ValueError(f"`prompt_lookup_num_tokens` has to be a positive integer, but is {num_tokens}")
         refused = [name for name, on in (
-            ("do_sample", bool(asked["do_sample"])), ("num_beams > 1", int(asked["num_beams"]) > 1),
-            ("repetition_penalty != 1", asked["repetition_penalty"] is not None and float(asked["repetition_penalty"]) != 1.0),
+            ("do_sample", sampling is None and bool(asked["do_sample"])), ("num_beams > 1", int(asked["num_beams"]) > 1),
+            ("repetition_penalty != 1", sampling is None and asked["repetition_penalty"] is not None and float(asked["repetition_penalty"]) != 1.0),
             ("no_repeat_ngram_size / bad_words_ids / min_p", bool(asked["processors"])), ("output_scores / output_logits", bool(asked["outputs"])),
             ("output_token_logprobs", bool(asked["stats"])), ("output_top_logprobs", bool(asked["topk"])),
             ("num_return_sequences > 1", int(asked["num_return_sequences"]) > 1),
             ("a padded attention_mask", attention_mask is not None and not bool((attention_mask == 1).all())),
             ("a batcher (continuous batching does not draft)", getattr(self, "batcher", None) is not None and not _in_exclusive_job()),
             ("a streamer with more than one row", streamer is not None and inputs_embeds.shape[0] > 1)) if on]
+        if refused and sampling is not None:
+            raise NotImplementedError("prompt_lookup_num_tokens with " + ", ".join(refused) + " is not built: verification of drafted tokens "
+                                      "(sv_generate_lookup_sampled) takes one sample per prompt, without beams, processors or per-step outputs")
         if refused:
             raise NotImplementedError("prompt_lookup_num_tokens with " + ", ".join(refused) + " is not built: greedy verification of drafted "
                                       "tokens (sv_generate_lookup) takes greedy calls without per-step outputs")
         eng = self._engine
-        if not hasattr(eng, "generate_lookup"):
-            raise NotImplementedError("prompt_lookup_num_tokens: this engine has no generate_lookup")
+        if not hasattr(eng, "generate_lookup" if sampling is None else "generate_lookup_sampled"):
+            raise NotImplementedError("prompt_lookup_num_tokens: this engine has no " + ("generate_lookup" if sampling is None else "generate_lookup_sampled"))
         on_tokens = None
         if streamer is not None:
             streamer.put(torch.empty(inputs_embeds.shape[0], 0, dtype=torch.long))
@@ -869,12 +881,18 @@ class HipCausalLM(_EngineModule):
                     streamer.put(tokens[:, c])
         min_new = max(int(min_length or 0) - inputs_embeds.shape[1], 0)
         lock = getattr(eng, "call_lock", None) or contextlib.nullcontext()
+        extra = {}
+        if sampling is not None:      # the values _classic_generate hands the plain call: the tokens must be that call's
+            t, p = sampling["temperature"], sampling["top_p"]
+            rp = asked["repetition_penalty"]
+            extra = dict(do_sample=bool(asked["do_sample"]), temperature=float(t if t is not None else 1.0), top_p=float(p if p is not None else 1.0),
+                         top_k=int(sampling["top_k"] or 0), seed=sampling["seed"], repetition_penalty=float(rp if rp is not None else 1.0))
         with lock:
-            out = eng.generate_lookup(
+            out = (eng.generate_lookup if sampling is None else eng.generate_lookup_sampled)(
                 inputs_embeds.to(torch.bfloat16), max_length=int(max_length), num_draft_tokens=K, max_ngram=int(ngram or 0),
                 eos_token_id=int(self.eos_token_id if eos_token_id is None else eos_token_id),
                 pad_token_id=int(self.pad_token_id if pad_token_id is None else pad_token_id),
-                stop_ids=self._stop_ids(stopping_criteria), on_tokens=on_tokens, **({"min_new_tokens": min_new} if min_new else {}))
+                stop_ids=self._stop_ids(stopping_criteria), on_tokens=on_tokens, **({"min_new_tokens": min_new} if min_new else {}), **extra)
         if streamer is not None:
             streamer.end()
         return generate_output(False, sequences=out) if return_dict else out
@@ -1069,7 +1087,10 @@ class StarVectorStarCoder(nn.Module):
 
     def _get_generation_kwargs(self, base_kwargs):                    # starvector_base.py:223-241
         end_sequence = self.svg_transformer.tokenizer("</svg>", add_special_tokens=False)["input_ids"]
+        # extension, opt-in (HipCausalLM.generate): prompt_lookup_num_tokens together with sampling / a repetition penalty
+        lookup_sampling = {"prompt_lookup_sampling": True} if base_kwargs.get("prompt_lookup_sampling") else {}
         return {
+            **lookup_sampling,
             "inputs_embeds": base_kwargs["inputs_embeds"],
             "attention_mask": base_kwargs["attention_mask"],
             "do_sample": base_kwargs.get("use_nucleus_sampling", True),

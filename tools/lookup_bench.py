@@ -12,7 +12,12 @@ the call ran.  The engine keeps ONE captured verification step, keyed by K and t
 clock when the key changes: every arm is therefore called TWICE back to back and only the second call is timed; `rounds` rounds run all arms in turn.
 Every lookup arm's tokens are compared with the plain call's.  Prints one JSON line per arm and a markdown table.
 
-    python tools/lookup_bench.py [--new 1024] [--rounds 3] [--shared] [--only plain,rejected7]
+--sample: the same arms for SAMPLED decoding (top_k 50, top_p 0.9, a fixed seed; --penalty 1.1 adds the repetition penalty): plain is
+generate(do_sample=True, ...), the lookup arms are generate_lookup_sampled with the same selection, the forced drafts are the plain sampled
+call's own tokens (accepted) and those tokens + 1 (rejected).  --penalty without --sample: greedy under the penalty.  The natural arm's
+acceptance under sampling on random weights says even less than the greedy one.
+
+    python tools/lookup_bench.py [--new 1024] [--rounds 3] [--shared] [--only plain,rejected7] [--sample] [--penalty 1.1]
 """
 import argparse
 import json
@@ -31,6 +36,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--shared", action="store_true", help="exclusive_device off: no fused row-update + c_attn / MLP launches")
     ap.add_argument("--only", default="", help="comma-separated arm names")
+    ap.add_argument("--sample", action="store_true", help="sampled decoding: top_k 50, top_p 0.9, seed 7 (generate_lookup_sampled)")
+    ap.add_argument("--penalty", type=float, default=1.0, help="repetition_penalty of every arm (generate_lookup_sampled)")
     a = ap.parse_args()
     import torch
     import starvector_amd as sva
@@ -40,6 +47,11 @@ def main():
     g = torch.Generator().manual_seed(1)
     x = (torch.randn(1, S0, ec.hidden, generator=g) * 0.5).to(torch.bfloat16).to(torch.device("cuda", eng.device))
     kw = dict(max_length=S0 + a.new, eos_token_id=-1, pad_token_id=49152)
+    sel = dict(do_sample=True, top_k=50, top_p=0.9, temperature=1.0, seed=7) if a.sample else {}
+    if a.penalty != 1.0:
+        sel["repetition_penalty"] = a.penalty
+    kw.update(sel)
+    call_lookup = eng.generate_lookup_sampled if sel else eng.generate_lookup
     plain = eng.generate(x, **kw).cpu()
     stream = plain[0].tolist()
     wrong = [(t + 1) % 49152 for t in stream]
@@ -48,7 +60,7 @@ def main():
         def run():
             eng.set_lookup_drafts(None if forced is None else [forced])
             try:
-                return eng.generate_lookup(x, num_draft_tokens=K, return_counts=True, **kw)
+                return call_lookup(x, num_draft_tokens=K, return_counts=True, **kw)
             finally:
                 eng.set_lookup_drafts(None)
         return run
@@ -75,7 +87,7 @@ def main():
         out = dict(arm=name, new_tokens=a.new, steps=v["steps"], drafted=v["drafted"], accepted=v["accepted"], tokens_equal_plain=v["same"],
                    decode_ms=round(ms, 3), step_us=round(step_us, 1), tokens_per_step=round((a.new - 1) / max(v["steps"], 1), 3),
                    tok_per_s=round(1e3 * (a.new - 1) / ms, 1), step_over_plain=round(step_us / (1e3 * base), 4) if base else None,
-                   exclusive_device=not a.shared, rounds=a.rounds)
+                   exclusive_device=not a.shared, rounds=a.rounds, sample=a.sample, repetition_penalty=a.penalty)
         rows.append(out)
         print(json.dumps(out))
     print("\n| arm | steps | tokens / step | accepted / drafted | step (us) | step / plain step | tok/s | tokens == plain |")
