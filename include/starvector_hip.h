@@ -426,7 +426,7 @@ int  sv_generate_topk(sv_engine* e, const void* dev_embeds_packed, int32_t B, co
  * sv_generate_ragged (host_lens given) / sv_generate.  Streaming works with B == 1.
  * SV_EINVAL before any device work: NULL arguments, num_draft_tokens outside 0..SV_LOOKUP_MAX_DRAFT, max_ngram outside 0..SV_LOOKUP_MAX_NGRAM,
  * min_ngram outside 0..max_ngram.  SV_ENOTSUP, naming the offender: do_sample, num_beams > 1, repetition_penalty != 1, streaming with
- * B > 1, B x (K + 1) > max_batch.  Continuous batching (sv_cb_*) does not draft. */
+ * B > 1, B x (K + 1) > max_batch.  Continuous batching (sv_cb_*) drafts per request once sv_cb_set_lookup has switched it on. */
 #define SV_LOOKUP_MAX_DRAFT 15
 #define SV_LOOKUP_MAX_NGRAM 8
 typedef struct sv_lookup {
@@ -472,7 +472,9 @@ int  sv_forward_topk(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S,
  *   sv_cb_poll     per slot: live flag and number of tokens emitted so far (host arrays of `capacity` >= max_batch entries)
  *   sv_cb_read     tokens [first, first + count) of a slot -> host int64
  *   sv_cb_release  frees a slot and its KV pages (stops it if it is still generating)
- *   sv_cb_reset    releases everything; the engine is back to the classic entry points */
+ *   sv_cb_reset    releases everything; the engine is back to the classic entry points
+ * The batch drafts per request when sv_cb_set_lookup (below) has switched it on: a slot then owns K + 1 rows, a step emits 1 .. K + 1
+ * tokens per live slot, the batch holds max_batch / (K + 1) slots -- and every request's tokens stay exactly what they are without it. */
 typedef struct sv_cb_request {
     int32_t do_sample; float temperature; float top_p; int32_t top_k;     /* as in sv_sampling */
     uint64_t seed;
@@ -540,6 +542,24 @@ int  sv_cb_admit_logprobs(sv_engine* e, const void* dev_embeds_packed, int32_t n
                           const int32_t* host_group, const sv_cb_request* reqs, const sv_cb_logprobs* lps, int32_t* slots_out, sv_stream stream);
 int  sv_cb_read_logprobs(sv_engine* e, int32_t slot, int32_t first, int32_t count, float* host_logprob, int32_t* host_rank, int32_t* host_ids,
                          float* host_lps);
+/* Prompt-lookup drafting for the continuous batch (entry points appended; SV_ABI_VERSION and sv_cb_request are unchanged).  With
+ * num_draft_tokens = K > 0 a slot owns K + 1 decode rows -- rows slot * (K + 1) + j of the step, row j carrying the slot's j-th draft on the
+ * slot's own KV pages, as in sv_generate_lookup -- and a sv_cb_step step is a VERIFICATION step: every live slot emits 1 .. K + 1 tokens, and
+ * sv_cb_poll's step counts advance by that much.  The drafts come from the n-gram lookup over the ids the slot has emitted; a slot never drafts
+ * past its own budget.  The slot's rows are verified one after the other inside the slot's selection block with the plain step's own code
+ * against the slot's current state, so every request's tokens, its finish and its log-prob record are those of the same request in a batch
+ * with drafting off, BIT FOR BIT: greedy and sampled (the draw at a column uses (seed, column) as always), repetition penalty, min_new_tokens,
+ * stop sequence, vLLM semantics with penalties, logit_bias, min_p and stop_any_ids, every admit form.  The cost: the batch holds
+ * max_batch / (K + 1) slots (sv_cb_admit* return SV_EBUSY beyond that, as when slots are short); slot ids, sv_cb_poll's arrays, sv_cb_read and
+ * sv_cb_release stay indexed by slot; the KV pages a request needs are unchanged.
+ * lookup NULL or num_draft_tokens == 0: off (the default; every sv_cb_* call is then exactly what it is without this entry point).
+ * Only while no continuous batch is active (before the first admit, or after sv_cb_reset): SV_ESTATE otherwise.  The setting stays on the engine
+ * across sv_cb_reset.  Defaults and ranges of sv_lookup as in sv_generate_lookup (max_ngram 0 = 3, min_ngram 0 = 1); SV_EINVAL before any device work
+ * for values outside them; SV_ENOTSUP when max_batch / (K + 1) < 1. */
+int  sv_cb_set_lookup(sv_engine* e, const sv_lookup* lookup);
+/* {verification steps, drafts verified, drafts accepted} of a slot since its admit; slot = -1: totals since the batch began (steps summed over
+ * the slots: one per live slot and step).  Host array of 3.  All zero while drafting is off. */
+int  sv_cb_lookup_counts(sv_engine* e, int32_t slot, int32_t* host_counts3);
 
 /* beam scorer: one step consumes dev_logits [batch * num_beams][ld] (row r = request r / num_beams, beam r % num_beams)
  * and reports (host arrays, each batch * num_beams long, may be NULL) the flat parent row, the token and the running

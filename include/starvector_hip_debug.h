@@ -384,6 +384,27 @@ int  sv_op_cb_select(const float* dev_logits, int32_t B, int32_t V, int32_t ld, 
 int  sv_op_cb_logprobs(const float* dev_logits, int32_t B, int32_t V, int32_t ld, const sv_cb_request* reqs, const sv_cb_logprobs* lps,
                        const int32_t* host_history, int32_t ld_hist, const int32_t* host_hist_len, int32_t* host_out, float* host_logprob,
                        int32_t* host_rank, int32_t* host_ids, float* host_lps, int32_t ld_k, sv_stream stream);
+/* Drafting in the continuous batch (sv_cb_set_lookup), test surface.
+ *   sv_debug_cb_set_lookup_drafts  draft j of slot s < n is host_ids[s][step_s + j] (row stride ld, ids inside the vocabulary; nothing beyond
+ *                                  column ld) instead of the lookup; slots >= n draft by the lookup.  host_ids NULL: cleared.  Set before the
+ *                                  admit, while no continuous batch is active (SV_ESTATE otherwise); the kept step graphs are dropped.
+ *   sv_op_cb_lookup_step           ONE launch of cb_lookup_step_kernel (cb_lookup/cb_lookup.hip, the same device code) over n slots of K + 1
+ *                                  rows each on caller-given state.  dev_logits [n * (K + 1)][ld] fp32 (ld a multiple of 4; not modified: the
+ *                                  kernel works on a copy), row s * (K + 1) + j is slot s's row j.  Slot s is request reqs[s] with prompt
+ *                                  length host_base[s], live flag host_live[s] and host_hist_len[s] emitted ids host_history[s][0 ..) (row
+ *                                  stride ld_hist, which must leave room for K + 1 more): its step, counts and repetition set.  host_rows /
+ *                                  host_positions [n * (K + 1)] and host_n_draft [n] are the step in flight (lk_write_rows' layout).
+ *                                  host_forced (may be NULL) [forced_n][forced_ld] as sv_debug_cb_set_lookup_drafts.  All host arrays but
+ *                                  reqs / host_base / host_forced are updated in place; host_counts [n][3] = each slot's {steps, drafted,
+ *                                  accepted} of this launch, host_flags3 = {finished slots, 0, bad}.
+ *                                  lps (may be NULL) [n]: what each slot records; host_logprob / host_rank [n][K + 1] then receive the record
+ *                                  of the columns this launch emitted (NaN / 0 behind them), lists are not returned. */
+int  sv_debug_cb_set_lookup_drafts(sv_engine* e, const int32_t* host_ids, int32_t n, int32_t ld);
+int  sv_op_cb_lookup_step(const float* dev_logits, int32_t n, int32_t K, int32_t V, int32_t ld, const sv_cb_request* reqs,
+                          const sv_cb_logprobs* lps, const int32_t* host_base, int32_t* host_live, int32_t* host_history, int32_t ld_hist,
+                          int32_t* host_hist_len, int32_t* host_rows, int32_t* host_positions, int32_t* host_n_draft, int32_t max_ngram,
+                          int32_t min_ngram, const int32_t* host_forced, int32_t forced_n, int32_t forced_ld, int32_t* host_counts,
+                          int32_t* host_flags3, float* host_logprob, int32_t* host_rank, sv_stream stream);
 /* the kernel of sv_generate_processed's token bans (processors.hip ban_tokens_kernel) on caller-given rows: row b of dev_logits [B][ld] fp32
  * (device, V valid columns) is a row whose generated ids so far are host_hist[b][0 .. host_hist_len[b]) (HOST, row stride ld_hist, ids inside
  * the vocabulary).  The ids lp->no_repeat_ngram_size and lp's bad words ban at that point are set to -inf IN PLACE; every other value is left

@@ -175,6 +175,8 @@ PRODUCT_PROTOTYPES = {
     "sv_cb_reset": (_I, [_P]),
     "sv_cb_admit_logprobs": (_I, [_P, _P, _I, C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(SvCbRequest), C.POINTER(SvCbLogprobs), C.POINTER(_I), _P]),
     "sv_cb_read_logprobs": (_I, [_P, _I, _I, _I, C.POINTER(_F), C.POINTER(_I), C.POINTER(_I), C.POINTER(_F)]),
+    "sv_cb_set_lookup": (_I, [_P, C.POINTER(SvLookup)]),
+    "sv_cb_lookup_counts": (_I, [_P, _I, C.POINTER(_I)]),
     "sv_beam_create": (_I, [C.POINTER(SvBeamConfig), C.POINTER(_P)]),
     "sv_beam_destroy": (_I, [_P]),
     "sv_beam_step": (_I, [_P, _P, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_F), _P]),
@@ -270,6 +272,10 @@ DEBUG_PROTOTYPES = {
     "sv_op_cb_select": (_I, [_P, _I, _I, _I, C.POINTER(SvCbRequest), C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(_I), _P]),
     "sv_op_cb_logprobs": (_I, [_P, _I, _I, _I, C.POINTER(SvCbRequest), C.POINTER(SvCbLogprobs), C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(_I),
                                C.POINTER(_F), C.POINTER(_I), C.POINTER(_I), C.POINTER(_F), _I, _P]),
+    "sv_debug_cb_set_lookup_drafts": (_I, [_P, C.POINTER(_I), _I, _I]),
+    "sv_op_cb_lookup_step": (_I, [_P, _I, _I, _I, _I, C.POINTER(SvCbRequest), C.POINTER(SvCbLogprobs), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _I,
+                                  C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _I, _I, C.POINTER(_I), _I, _I, C.POINTER(_I),
+                                  C.POINTER(_I), C.POINTER(_F), C.POINTER(_I), _P]),
 }
 
 PROTOTYPES = {**PRODUCT_PROTOTYPES, **DEBUG_PROTOTYPES}

@@ -15,6 +15,10 @@ record arrives with the tokens and `_Request.logprobs` holds it.  Requests witho
 
 Every slot has its own sampling parameters, budget, EOS, stop sequence and random stream, so a request's tokens are exactly
 what a solo `HipEngine.generate` call would return for it (tests/test_gpu_serving.py).  No kernels here: host logic only.
+
+``prompt_lookup_num_tokens=K`` switches on prompt-lookup drafting for the whole batch (`HipEngine.cb_set_lookup`): a step verifies up to K
+drafted tokens per request and emits 1 .. K + 1 of them, the tokens of every request stay what they are without it, and the batch holds
+max_batch // (K + 1) requests -- at the reference worker's 5 concurrent requests the other rows of a 32- or 64-row engine are idle anyway.
 """
 from __future__ import annotations
 
@@ -82,10 +86,22 @@ class _Request:
 class ContinuousBatcher:
     """engine: a `HipEngine` (or anything with cb_admit / cb_step / cb_poll / cb_read / cb_release / cb_reset and `.cfg`)."""
 
-    def __init__(self, engine, steps_per_poll: int = 8, device: Optional[int] = None):
+    def __init__(self, engine, steps_per_poll: int = 8, device: Optional[int] = None, prompt_lookup_num_tokens: int = 0,
+                 max_matching_ngram_size: int = 0, min_matching_ngram_size: int = 0):
         self.engine = engine
         self.steps_per_poll = int(steps_per_poll)
         self.device = getattr(engine, "device", 0) if device is None else device
+        # prompt-lookup drafting (sv_cb_set_lookup): K > 0 -- set before the first admit -- makes every step verify up to K drafted tokens per
+        # request; a slot then owns K + 1 decode rows, so the batch holds max_batch // (K + 1) requests and the rest waits in the queue
+        self.lookup_k = int(prompt_lookup_num_tokens or 0)
+        if self.lookup_k < 0:
+            raise ValueError("prompt_lookup_num_tokens must be >= 0")
+        self.slots = int(engine.cfg.max_batch) // (self.lookup_k + 1)
+        if self.lookup_k:
+            if self.slots < 1:
+                raise NotImplementedError(f"prompt_lookup_num_tokens {self.lookup_k} + 1 rows per request exceed max_batch {engine.cfg.max_batch}")
+            engine.cb_reset()
+            engine.cb_set_lookup(self.lookup_k, int(max_matching_ngram_size or 0), int(min_matching_ngram_size or 0))
         self._lock = threading.Condition()
         self._pending: Deque[_Request] = deque()
         self._active: Dict[int, _Request] = {}
@@ -148,6 +164,13 @@ class ContinuousBatcher:
             self._lock.notify_all()
         return req.result(timeout)
 
+    def lookup_counts(self) -> dict:
+        """{steps, drafted, accepted} of the running batch since it began (sv_cb_lookup_counts, slot -1; steps: one per live request and
+        step); zeros while drafting is off.  The engine starts a new batch -- and the totals from zero -- whenever it has run empty and was reset."""
+        if not self.lookup_k:
+            return {"steps": 0, "drafted": 0, "accepted": 0}
+        return self.engine.cb_lookup_counts(-1)
+
     def queue_length(self) -> int:
         with self._lock:
             return len(self._pending) + len(self._active)
@@ -175,7 +198,7 @@ class ContinuousBatcher:
         for r in waiting:
             by_len.setdefault(0 if ragged else int(r.emb.shape[1]), []).append(r)
         for S0, group in by_len.items():
-            room = self.engine.cfg.max_batch - len(self._active)
+            room = self.slots - len(self._active)
             group = group[:room]
             while group:
                 try:
@@ -269,7 +292,7 @@ class ContinuousBatcher:
                             except BaseException as e:
                                 self._finish(head, e)
                             continue
-                    elif self._pending and len(self._active) < self.engine.cfg.max_batch:
+                    elif self._pending and len(self._active) < self.slots:
                         moved = self._admit()
                         if moved == 0 and not self._active:
                             # nothing runs and the head request still does not fit: no release will ever make room.  Reset the

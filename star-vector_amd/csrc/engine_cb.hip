@@ -9,10 +9,16 @@
 // row ("slot") of the batch is a request with its own sampling parameters, budget, EOS and stop sequence, requests join
 // (prefill into free slots while the others keep their KV pages) and leave at any step, and the captured decode step is kept
 // per row bucket.  A request produces the same tokens as when it runs alone through sv_generate.
+// sv_cb_set_lookup (at the end of this file) makes the batch draft: a slot then owns cb_K + 1 decode rows and the step's selection is
+// cb_lookup_step_kernel (cb_lookup/cb_lookup.hip) -- the tokens of every request stay what they are.
 // ------------------------------------------------------------------------------------------------
+// Drafting (sv_cb_set_lookup): a slot owns K1 = cb_K + 1 decode rows, the batch holds max_batch / K1 slots, the bucket is counted in ROWS
+static inline int cb_k1(const sv_engine* e) { return e->cb_K + 1; }
+static inline int cb_slot_cap(const sv_engine* e) { return e->cfg.max_batch / cb_k1(e); }
 static int cb_bucket(const sv_engine* e) {
     int hi = 0;
     for (int s2 = 0; s2 < e->cfg.max_batch; ++s2) if (e->cb_used[s2]) hi = s2 + 1;
+    hi *= cb_k1(e);
     int b = 8;
     while (b < hi) b <<= 1;
     return b > e->cfg.max_batch ? e->cfg.max_batch : b;
@@ -25,6 +31,14 @@ static void cb_step_args(sv_engine* e, CbStepArgs& a, const int32_t* map, bool r
     a.seen = e->seen; a.seen_words = e->seen_words; a.n_live = e->cb_nlive; a.events = e->cb_events; a.bad = e->d_bad;
     a.counts = e->cb_counts; a.ld_counts = e->Vpad; a.bias = e->cb_bias;
     a.lp = record ? e->cb_lp : nullptr;
+}
+// the drafting batch's selection: first = the first token of new requests (block b = slot map[b] on logits row b), else a verification step
+static void cb_lookup_args(sv_engine* e, CbLookupArgs& q, const int32_t* map, bool record, bool first) {
+    const int mb = e->cfg.max_batch;
+    cb_step_args(e, q.st, map, record);
+    q.K = e->cb_K; q.max_ngram = e->cb_max_ngram; q.min_ngram = e->cb_min_ngram; q.first = first ? 1 : 0;
+    q.n_draft = e->cb_lk_state; q.counts = q.n_draft + mb; q.totals = q.counts + 3 * mb;
+    q.forced = e->cb_lk_forced_n > 0 ? e->cb_lk_forced : nullptr; q.forced_n = e->cb_lk_forced_n; q.forced_ld = e->cb_lk_forced_ld;
 }
 
 // ---- per-slot log-prob records (sv_cb_admit_logprobs / sv_cb_read_logprobs) ----
@@ -153,6 +167,7 @@ static int cb_begin(sv_engine* e, hipStream_t st) {
     HIPCHECK(hipMemsetAsync(e->cur_tok, 0, R * sizeof(int32_t), st));
     HIPCHECK(hipMemsetAsync(e->cb_nlive, 0, sizeof(int32_t), st));
     HIPCHECK(hipMemsetAsync(e->cb_events, 0, sizeof(int32_t), st));
+    if (e->cb_K) HIPCHECK(hipMemsetAsync(e->cb_lk_state, 0, ((size_t)4 * e->cfg.max_batch + 3) * sizeof(int32_t), st));      // no drafts in flight, the totals from zero
     for (int s2 = 0; s2 < e->cfg.max_batch; ++s2) SVCHECK(cb_lp_set(e, s2, nullptr, st));      // (every slot is free: nobody records)
     HIPCHECK(hipStreamSynchronize(st));                  // `table` is a host temporary
     e->cb_active = true;
@@ -265,11 +280,12 @@ static int plan_group(sv_engine* e, int U, const int32_t* lens, int n, const int
         p.pos[i] = lens[u] - 1;
         p.fork[5 * (size_t)mb + i] = u;          // logits row of the prompt (u <= i: shared_check_group)
     }
+    const int K1 = cb_k1(e);             // the fork launch indexes block-table ROWS: a slot's first (its K1 rows are copies of one another)
     for (int u = 0, d0 = 0; u < U; ++u) {
         const int o = owner[u];
         for (int k = 0; k < (lens[u] + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS; ++k) p.pf[(size_t)u * mp + k] = p.rows[(size_t)o * mp + k];
-        p.fork[4 * u] = p.slots[o]; p.fork[4 * u + 1] = lens[u]; p.fork[4 * u + 2] = d0; p.fork[4 * u + 3] = n_dst[u];
-        for (int i = 0; i < n; ++i) if (group[i] == u && i != o) p.fork[4 * (size_t)mb + d0++] = p.slots[i];
+        p.fork[4 * u] = p.slots[o] * K1; p.fork[4 * u + 1] = lens[u]; p.fork[4 * u + 2] = d0; p.fork[4 * u + 3] = n_dst[u];
+        for (int i = 0; i < n; ++i) if (group[i] == u && i != o) p.fork[4 * (size_t)mb + d0++] = p.slots[i] * K1;
     }
     return 0;
 }
@@ -283,12 +299,16 @@ static int cb_admit_commit(sv_engine* e, const void* dev_embeds, int U, int S0_a
     const int n = (int)p.slots.size(), mp = e->pages_per_seq;
     const bool any_pen = [&] { for (int i = 0; i < n; ++i) if (reqs[i].repetition_penalty > 0.f && reqs[i].repetition_penalty != 1.0f) return true; return false; }();
     bool nlive_added = false;
+    const int K1 = cb_k1(e);
     const int rc = [&]() -> int {
     for (int i = 0; i < n; ++i) {
         const int s2 = p.slots[i];
-        HIPCHECK(hipMemcpyAsync(e->block_table + (size_t)s2 * mp, p.rows.data() + (size_t)i * mp, mp * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        // drafting: the slot's K1 block-table rows are copies of one another; its rows of cur_tok / positions are written by the first-token launch
+        // from the prompt length kept in the slot (CbSlot::base)
+        for (int j = 0; j < K1; ++j)
+            HIPCHECK(hipMemcpyAsync(e->block_table + ((size_t)s2 * K1 + j) * mp, p.rows.data() + (size_t)i * mp, mp * sizeof(int32_t), hipMemcpyHostToDevice, st));
         HIPCHECK(hipMemcpyAsync(e->cb_slots + s2, &p.hs[i], sizeof(CbSlot), hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(e->positions + s2, &p.pos[i], sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (!e->cb_K) HIPCHECK(hipMemcpyAsync(e->positions + s2, &p.pos[i], sizeof(int32_t), hipMemcpyHostToDevice, st));
         if (reqs[i].semantics == 1) {
             // vLLM mode: the repetition set starts as the prompt ids, the output counts at zero -- before the first-token step below
             HIPCHECK(hipMemcpyAsync(e->seen + (size_t)s2 * e->seen_words, p.seen_rows[i].data(), e->seen_words * sizeof(uint32_t),
@@ -312,9 +332,16 @@ static int cb_admit_commit(sv_engine* e, const void* dev_embeds, int U, int S0_a
         fork_args(e, U, n, f);
         launch_fork_prompt(f, st);
     }
-    CbStepArgs a;
-    cb_step_args(e, a, e->cb_map, p.record);
-    launch_cb_step(a, n, st);                              // first token of every new request, from its prompt's logits (column 0 of its record)
+    // first token of every new request, from its prompt's logits (column 0 of its record)
+    if (e->cb_K) {
+        CbLookupArgs q;                                    // the plain kernel would write cur_tok[slot] / positions[slot]: another slot's rows in this layout
+        cb_lookup_args(e, q, e->cb_map, p.record, true);
+        launch_cb_lookup_step(q, n, st);
+    } else {
+        CbStepArgs a;
+        cb_step_args(e, a, e->cb_map, p.record);
+        launch_cb_step(a, n, st);
+    }
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(st));                    // the plan's vectors are host temporaries
     return 0;
@@ -331,7 +358,8 @@ static int cb_admit_commit(sv_engine* e, const void* dev_embeds, int U, int S0_a
         slots_out[i] = -1;
         // best effort on the device: the slot is dead, records nothing and its block-table row points at the trash page again
         (void)hipMemsetAsync(e->cb_slots + s2, 0, sizeof(CbSlot), st);
-        (void)hipMemcpyAsync(e->block_table + (size_t)s2 * mp, trash.data(), trash.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
+        for (int j = 0; j < K1; ++j)
+            (void)hipMemcpyAsync(e->block_table + ((size_t)s2 * K1 + j) * mp, trash.data(), trash.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
         (void)cb_lp_set(e, s2, nullptr, st);
     }
     for (size_t k = p.taken.size(); k-- > 0;) {             // pages go back in reverse order, no holder left: the free list is as it was
@@ -360,7 +388,7 @@ static int cb_admit_impl(sv_engine* e, const void* dev_embeds, int32_t U, int32_
     AdmitPlan p;
     p.record = [&] { for (int i = 0; lps && i < n; ++i) if (lps[i].enable) return true; return false; }();
     if (p.record) SVCHECK(cb_lp_alloc(e));
-    for (int s2 = 0; s2 < mb && (int)p.slots.size() < n; ++s2) if (!e->cb_used[s2]) p.slots.push_back(s2);
+    for (int s2 = 0; s2 < cb_slot_cap(e) && (int)p.slots.size() < n; ++s2) if (!e->cb_used[s2]) p.slots.push_back(s2);
     p.rows.assign((size_t)n * mp, e->trash_page);
     p.map.resize(n); p.pos.resize(n); p.hs.resize(n); p.hb.resize(n); p.seen_rows.resize(n);
     SVCHECK(group ? plan_group(e, U, lens, n, group, reqs, p) : plan_plain(e, n, S0_all, lens, reqs, p));
@@ -368,6 +396,7 @@ static int cb_admit_impl(sv_engine* e, const void* dev_embeds, int32_t U, int32_
         const int s2 = p.slots[i];
         e->cb_used[s2] = 1;
         cb_fill_slot(reqs[i], p.hs[i], p.hb[i], p.seen_rows[i], e->seen_words);
+        if (e->cb_K) p.hs[i].base = p.pos[i] + 1;        // the prompt length: the drafting selection places the slot's rows from it
         p.map[i] = s2;
         slots_out[i] = s2;
     }
@@ -444,8 +473,20 @@ extern "C" int sv_cb_step(sv_engine* e, int32_t n_steps, int32_t* n_live_out, sv
     const bool record = cb_any_records(e);
     hipGraphExec_t gexec = nullptr;
     int per_launch = 1;
+    // drafting: a verification step -- decode_forward over the row bucket with the K / V pre-write in front of every attention launch (the rows
+    // of a slot see their siblings through the cache, as in sv_generate_lookup), then the per-slot selection over the bucket's Bb / K1 slots.
+    // (the kept graphs carry no drafting setting in their key: sv_cb_set_lookup and sv_debug_cb_set_lookup_drafts drop them)
+    const bool draft = e->cb_K > 0;
+    struct LookupOff { sv_engine* e; ~LookupOff() { e->lookup_on = false; } } lookup_off{e};
+    e->lookup_on = draft;
     const auto one_step = [&]() {
         decode_forward(e, Bb, st);
+        if (draft) {
+            CbLookupArgs q;
+            cb_lookup_args(e, q, nullptr, record, false);
+            launch_cb_lookup_step(q, Bb / cb_k1(e), st);
+            return;
+        }
         CbStepArgs a;
         cb_step_args(e, a, nullptr, record);
         launch_cb_step(a, Bb, st);
@@ -550,10 +591,12 @@ static int cb_release_locked(sv_engine* e, int slot, hipStream_t st) {
     HIPCHECK(hipStreamSynchronize(st));
     if (h.live) add_i32(e->cb_nlive, -1, 1, st);
     HIPCHECK(hipMemsetAsync(e->cb_slots + slot, 0, sizeof(CbSlot), st));
-    HIPCHECK(hipMemsetAsync(e->positions + slot, 0, sizeof(int32_t), st));
-    HIPCHECK(hipMemsetAsync(e->cur_tok + slot, 0, sizeof(int32_t), st));
+    const int K1 = cb_k1(e);                             // the slot's decode rows (1 unless the batch drafts)
+    HIPCHECK(hipMemsetAsync(e->positions + (size_t)slot * K1, 0, K1 * sizeof(int32_t), st));
+    HIPCHECK(hipMemsetAsync(e->cur_tok + (size_t)slot * K1, 0, K1 * sizeof(int32_t), st));
+    if (e->cb_K) HIPCHECK(hipMemsetAsync(e->cb_lk_state + slot, 0, sizeof(int32_t), st));      // no drafts in flight
     SVCHECK(cb_lp_set(e, slot, nullptr, st));            // a free slot records nothing: the next holder starts from enable = 0
-    fill_i32(e->block_table + (size_t)slot * e->pages_per_seq, e->trash_page, e->pages_per_seq, st);
+    fill_i32(e->block_table + (size_t)slot * K1 * e->pages_per_seq, e->trash_page, K1 * e->pages_per_seq, st);
     for (int pg : e->cb_pages[slot]) {
         // a shared prompt page (sv_cb_admit_shared) goes back when its last holder lets go; a private page at once
         if (e->page_refs[pg] > 0 && --e->page_refs[pg] > 0) continue;
@@ -583,5 +626,62 @@ extern "C" int sv_cb_reset(sv_engine* e) {
     HIPCHECK(hipStreamSynchronize(e->gen_stream));
     std::fill(e->page_refs.begin(), e->page_refs.end(), 0);
     e->cb_active = false;
+    return 0;
+}
+
+// ---- drafting (sv_cb_set_lookup / sv_cb_lookup_counts) ----
+namespace sveng {
+int cb_check_lookup(const char* who, const sv_lookup* lookup, sv_lookup& lk) {
+    lk = lookup ? *lookup : sv_lookup{0, 0, 0};
+    if (lk.num_draft_tokens < 0 || lk.num_draft_tokens > SV_LOOKUP_MAX_DRAFT)
+        return fail(SV_EINVAL, "%s: num_draft_tokens %d unsupported (0..%d)", who, lk.num_draft_tokens, SV_LOOKUP_MAX_DRAFT);
+    if (lk.max_ngram < 0 || lk.max_ngram > SV_LOOKUP_MAX_NGRAM)
+        return fail(SV_EINVAL, "%s: max_ngram %d unsupported (1..%d, 0 = 3)", who, lk.max_ngram, SV_LOOKUP_MAX_NGRAM);
+    if (lk.max_ngram == 0) lk.max_ngram = 3;
+    if (lk.min_ngram < 0 || lk.min_ngram > lk.max_ngram)
+        return fail(SV_EINVAL, "%s: min_ngram %d must lie in 1..max_ngram %d (0 = 1)", who, lk.min_ngram, lk.max_ngram);
+    if (lk.min_ngram == 0) lk.min_ngram = 1;
+    return 0;
+}
+void cb_drop_graphs(sv_engine* e) {
+    for (auto& kv : e->cb_graphs) {
+        if (kv.second.second) (void)hipGraphExecDestroy(kv.second.second);
+        if (kv.second.first) (void)hipGraphDestroy(kv.second.first);
+    }
+    e->cb_graphs.clear();
+}
+}  // namespace sveng
+
+extern "C" int sv_cb_set_lookup(sv_engine* e, const sv_lookup* lookup) {
+    sv_lookup lk;
+    SVCHECK(cb_check_lookup("sv_cb_set_lookup", lookup, lk));      // (the checks that need no engine come first)
+    if (!e) return fail(SV_EINVAL, "null engine");
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (e->cb_active) return fail(SV_ESTATE, "sv_cb_set_lookup: a continuous batch is active (the setting changes before the first admit or after sv_cb_reset)");
+    const int K = lk.num_draft_tokens;
+    if (e->cfg.max_batch / (K + 1) < 1)
+        return fail(SV_ENOTSUP, "sv_cb_set_lookup: num_draft_tokens %d + 1 rows per slot exceed engine max_batch %d", K, e->cfg.max_batch);
+    if (K == e->cb_K && (K == 0 || (lk.max_ngram == e->cb_max_ngram && lk.min_ngram == e->cb_min_ngram))) return 0;
+    HIPCHECK(hipSetDevice(e->cfg.device));
+    if (K && !e->cb_lk_state) SVCHECK(dalloc(e, &e->cb_lk_state, (size_t)4 * e->cfg.max_batch + 3));
+    HIPCHECK(hipStreamSynchronize(e->gen_stream));
+    cb_drop_graphs(e);                                   // captured with the other setting
+    e->cb_K = K;
+    if (K) { e->cb_max_ngram = lk.max_ngram; e->cb_min_ngram = lk.min_ngram; }
+    return 0;
+}
+
+extern "C" int sv_cb_lookup_counts(sv_engine* e, int32_t slot, int32_t* host_counts3) {
+    if (!e || !host_counts3) return fail(SV_EINVAL, "sv_cb_lookup_counts: null argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    host_counts3[0] = host_counts3[1] = host_counts3[2] = 0;
+    if (slot < -1 || slot >= e->cfg.max_batch || (slot >= 0 && !(e->cb_active && e->cb_used[slot])))
+        return fail(SV_EINVAL, "sv_cb_lookup_counts: slot %d is not in use (-1 = the batch's totals)", slot);
+    if (!e->cb_active || !e->cb_K) return 0;
+    HIPCHECK(hipSetDevice(e->cfg.device));
+    const int mb = e->cfg.max_batch;
+    const int32_t* src = e->cb_lk_state + mb + (slot < 0 ? 3 * mb : 3 * slot);
+    HIPCHECK(hipMemcpyAsync(host_counts3, src, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, e->gen_stream));
+    HIPCHECK(hipStreamSynchronize(e->gen_stream));
     return 0;
 }

@@ -202,6 +202,13 @@ struct sv_engine {
     // each).  All of it is allocated by the first admit that asks: cb_lp == nullptr on an engine that never did.
     CbLogprobs* cb_lp = nullptr;
     std::vector<CbLogprobs> cb_lp_host;
+    // sv_cb_set_lookup: cb_K > 0 = the batch drafts, a slot owns cb_K + 1 decode rows (kernels.h CbLookupArgs).  cb_lk_state (device, allocated
+    // by the first such setting): n_draft [max_batch] | counts [max_batch][3] | totals [3].  cb_lk_forced (sv_debug_cb_set_lookup_drafts):
+    // [cb_lk_forced_n][cb_lk_forced_ld] on the device (allocated once, [max_batch][max_seq_len]); n = 0: the lookup
+    int cb_K = 0, cb_max_ngram = 3, cb_min_ngram = 1;
+    int32_t* cb_lk_state = nullptr;
+    int32_t* cb_lk_forced = nullptr;
+    int cb_lk_forced_n = 0, cb_lk_forced_ld = 0;
     int trash_page = 0;                       // what the block-table rows of free slots point at
     std::unordered_map<int, std::pair<hipGraph_t, hipGraphExec_t>> cb_graphs;      // one captured step per row bucket
     // sv_generate: the captured decode step is kept while the next call has the same shape and sampling parameters
@@ -320,6 +327,9 @@ int cb_check_logprobs(const sv_cb_request* reqs, const sv_cb_logprobs* lps, int 
 int shared_check_group(const char* who, const int32_t* lens, int n_prompts, const int32_t* group, int n);
 long long shared_page_plan(const int32_t* lens, int n_prompts, const int32_t* group, const int32_t* budgets, int n, int32_t* shared, int32_t* private_);
 int cb_guard(sv_engine* e, const char* who);
+// sv_cb_set_lookup's range checks and defaults (host arithmetic): lk <- the values in force
+int cb_check_lookup(const char* who, const sv_lookup* lookup, sv_lookup& lk);
+void cb_drop_graphs(sv_engine* e);          // the kept step graphs name the drafting setting and the forced-draft buffer: gone when either changes
 int prefill_locked(sv_engine* e, const void* dev_embeds, int B, int S0, int total_len, hipStream_t st, bool set_positions = true);
 // The ragged prompt pass: B sequences of lengths lens[0..B) (host), embeddings packed back to back.  What the dispatch decides for a set of lengths is
 // host arithmetic (ragged_gemm_rows, ragged_blocks: sv_debug_ragged_plan states it for the CPU tests).

@@ -1535,6 +1535,157 @@ extern "C" int sv_op_cb_logprobs(const float* logits, int32_t B, int32_t V, int3
                              ld_k, stream);
 }
 
+// ---- drafting in the continuous batch (sv_cb_set_lookup): forced drafts, and cb_lookup_step_kernel on caller-given state ----
+extern "C" int sv_debug_cb_set_lookup_drafts(sv_engine* e, const int32_t* host_ids, int32_t n, int32_t ld) {
+    if (!e) return fail(SV_EINVAL, "null engine");
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->cb_active) return fail(SV_ESTATE, "sv_debug_cb_set_lookup_drafts: a continuous batch is active (set the drafts before the first admit)");
+    if (host_ids) {
+        if (n < 1 || n > e->cfg.max_batch || ld < 1 || ld > e->cfg.max_seq_len)
+            return fail(SV_EINVAL, "sv_debug_cb_set_lookup_drafts: bad n %d / ld %d (max_batch %d, max_seq_len %d)", n, ld, e->cfg.max_batch, e->cfg.max_seq_len);
+        for (size_t i = 0; i < (size_t)n * ld; ++i)      // a draft is fed to the embedding table
+            if (host_ids[i] < 0 || host_ids[i] >= e->cfg.vocab)
+                return fail(SV_EINVAL, "sv_debug_cb_set_lookup_drafts: id %d outside the vocabulary (%d)", host_ids[i], e->cfg.vocab);
+    }
+    HIPCHECK(hipSetDevice(e->cfg.device));
+    HIPCHECK(hipDeviceSynchronize());                // no step in flight reads the buffer
+    cb_drop_graphs(e);                               // the kept steps carry the buffer and its shape by value
+    e->cb_lk_forced_n = 0; e->cb_lk_forced_ld = 0;
+    if (!host_ids) return 0;
+    if (!e->cb_lk_forced) SVCHECK(dalloc(e, &e->cb_lk_forced, (size_t)e->cfg.max_batch * e->cfg.max_seq_len));
+    HIPCHECK(hipMemcpy(e->cb_lk_forced, host_ids, (size_t)n * ld * sizeof(int32_t), hipMemcpyHostToDevice));
+    e->cb_lk_forced_n = n; e->cb_lk_forced_ld = ld;
+    return 0;
+}
+
+extern "C" int sv_op_cb_lookup_step(const float* logits, int32_t n, int32_t K, int32_t V, int32_t ld, const sv_cb_request* reqs,
+                                    const sv_cb_logprobs* lps, const int32_t* base, int32_t* live, int32_t* history, int32_t ld_hist,
+                                    int32_t* hist_len, int32_t* rows, int32_t* positions, int32_t* n_draft, int32_t max_ngram, int32_t min_ngram,
+                                    const int32_t* forced, int32_t forced_n, int32_t forced_ld, int32_t* counts, int32_t* flags3,
+                                    float* out_logprob, int32_t* out_rank, sv_stream stream) {
+    const char* who = "sv_op_cb_lookup_step";
+    if (!logits || !reqs || !base || !live || !history || !hist_len || !rows || !positions || !n_draft || !counts || !flags3)
+        return fail(SV_EINVAL, "%s: null argument", who);
+    if (n < 1 || n > 256 || V < 1 || ld < V || (ld & 3) || ld_hist < 1) return fail(SV_EINVAL, "%s: bad argument", who);
+    sv_lookup lk_in{K, max_ngram, min_ngram}, lk;
+    SVCHECK(cb_check_lookup(who, &lk_in, lk));
+    if (K < 1) return fail(SV_EINVAL, "%s: num_draft_tokens %d (1..%d)", who, K, SV_LOOKUP_MAX_DRAFT);
+    const int K1 = K + 1;
+    if (forced && (forced_n < 1 || forced_ld < 1)) return fail(SV_EINVAL, "%s: bad forced_n %d / forced_ld %d", who, forced_n, forced_ld);
+    if (lps && (!out_logprob || !out_rank)) return fail(SV_EINVAL, "%s: lps without host_logprob / host_rank", who);
+    if (lps) SVCHECK(cb_check_logprobs(reqs, lps, n, who));
+    for (int s = 0; s < n; ++s) {
+        SVCHECK(cb_check_request(reqs[s], V, s, who));
+        if (hist_len[s] < 0 || hist_len[s] + K1 > ld_hist)
+            return fail(SV_EINVAL, "%s: slot %d: history length %d + %d rows exceed ld_hist %d", who, s, hist_len[s], K1, ld_hist);
+        if (live[s] && hist_len[s] >= reqs[s].max_new_tokens) return fail(SV_EINVAL, "%s: slot %d: live with its budget %d spent", who, s, reqs[s].max_new_tokens);
+        if (n_draft[s] < 0 || n_draft[s] > K) return fail(SV_EINVAL, "%s: slot %d: n_draft %d outside 0..%d", who, s, n_draft[s], K);
+        for (int t = 0; t < hist_len[s]; ++t)
+            if (history[(size_t)s * ld_hist + t] < 0 || history[(size_t)s * ld_hist + t] >= V) return fail(SV_EINVAL, "%s: slot %d: history id outside the vocabulary", who, s);
+        for (int j = 0; j < K1; ++j)
+            if (rows[s * K1 + j] < 0 || rows[s * K1 + j] >= V) return fail(SV_EINVAL, "%s: slot %d: row id outside the vocabulary", who, s);
+    }
+    for (size_t i = 0; forced && i < (size_t)std::min(n, forced_n) * forced_ld; ++i)
+        if (forced[i] < 0 || forced[i] >= V) return fail(SV_EINVAL, "%s: forced id outside the vocabulary", who);
+    const int words = (ld + 31) / 32, R = n * K1;
+    std::vector<CbSlot> hs(n);
+    std::vector<CbBias> hb(n);
+    std::vector<uint32_t> seen((size_t)n * words, 0u), row;
+    std::vector<uint16_t> cnt((size_t)n * ld, 0);
+    for (int s = 0; s < n; ++s) {
+        const sv_cb_request& r = reqs[s];
+        cb_fill_slot(r, hs[s], hb[s], row, words);
+        hs[s].step = hist_len[s]; hs[s].live = live[s] ? 1 : 0; hs[s].base = base[s];
+        const bool track = r.semantics == 1 || (r.repetition_penalty > 0.f && r.repetition_penalty != 1.0f);
+        for (int t = 0; t < hist_len[s]; ++t) {
+            const int id = history[(size_t)s * ld_hist + t];
+            if (track) row[id >> 5] |= 1u << (id & 31);
+            if (r.semantics == 1) cnt[(size_t)s * ld + id] += 1;
+        }
+        std::copy(row.begin(), row.end(), seen.begin() + (size_t)s * words);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    TmpBufs tmp;
+    float *lg, *dlogprob = nullptr, *dlps = nullptr;
+    CbSlot* dslots; CbBias* dbias; uint32_t* dseen; uint16_t* dcnt; CbLogprobs* dlp = nullptr;
+    int32_t *dout, *dcur, *dpos, *dctr, *dstate, *dforced = nullptr, *drank = nullptr, *dids = nullptr;
+    SVCHECK(tmp.get(&lg, (size_t)R * ld));
+    SVCHECK(tmp.get(&dslots, (size_t)n));
+    SVCHECK(tmp.get(&dbias, (size_t)n));
+    SVCHECK(tmp.get(&dseen, seen.size()));
+    SVCHECK(tmp.get(&dcnt, cnt.size()));
+    SVCHECK(tmp.get(&dout, (size_t)n * ld_hist));
+    SVCHECK(tmp.get(&dcur, (size_t)R));
+    SVCHECK(tmp.get(&dpos, (size_t)R));
+    SVCHECK(tmp.get(&dctr, 3));
+    SVCHECK(tmp.get(&dstate, (size_t)4 * n + 3));        // n_draft [n] | counts [n][3] | totals [3]
+    if (forced) SVCHECK(tmp.get(&dforced, (size_t)forced_n * forced_ld));
+    HIPCHECK(hipMemcpyAsync(lg, logits, (size_t)R * ld * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIPCHECK(hipMemcpyAsync(dslots, hs.data(), hs.size() * sizeof(CbSlot), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(dbias, hb.data(), hb.size() * sizeof(CbBias), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(dseen, seen.data(), seen.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(dcnt, cnt.data(), cnt.size() * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(dout, history, (size_t)n * ld_hist * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(dcur, rows, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(dpos, positions, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemsetAsync(dctr, 0, 3 * sizeof(int32_t), st));
+    HIPCHECK(hipMemsetAsync(dstate, 0, ((size_t)4 * n + 3) * sizeof(int32_t), st));
+    HIPCHECK(hipMemcpyAsync(dstate, n_draft, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (forced) HIPCHECK(hipMemcpyAsync(dforced, forced, (size_t)forced_n * forced_ld * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    CbLookupArgs q;
+    CbStepArgs& a = q.st;
+    a.logits = lg; a.ld = ld; a.V = V; a.slots = dslots; a.slot_map = nullptr;
+    a.cur_tok = dcur; a.positions = dpos; a.out_tokens = dout; a.ld_out = ld_hist;
+    a.seen = dseen; a.seen_words = words; a.n_live = dctr; a.events = dctr + 1; a.bad = dctr + 2;
+    a.counts = dcnt; a.ld_counts = ld; a.bias = dbias;
+    q.K = K; q.max_ngram = lk.max_ngram; q.min_ngram = lk.min_ngram; q.first = 0;
+    q.n_draft = dstate; q.counts = dstate + n; q.totals = q.counts + 3 * n;
+    q.forced = dforced; q.forced_n = forced ? forced_n : 0; q.forced_ld = forced_ld;
+    std::vector<CbLogprobs> hl;
+    if (lps) {
+        const size_t cols = (size_t)n * ld_hist;
+        SVCHECK(tmp.get(&dlp, (size_t)n));
+        SVCHECK(tmp.get(&dlogprob, cols));
+        SVCHECK(tmp.get(&drank, cols));
+        SVCHECK(tmp.get(&dids, cols * SV_TOPK_MAX));
+        SVCHECK(tmp.get(&dlps, cols * SV_TOPK_MAX));
+        hl.resize(n);
+        for (int s = 0; s < n; ++s) {
+            CbLogprobs& h = hl[s];
+            h.enable = lps[s].enable ? 1 : 0; h.k = h.enable ? lps[s].k : 0; h.source = h.enable ? lps[s].source : 0; h.pad_ = 0;
+            h.logprob = dlogprob + (size_t)s * ld_hist; h.rank = drank + (size_t)s * ld_hist;
+            h.ids = dids + (size_t)s * ld_hist * SV_TOPK_MAX; h.lps = dlps + (size_t)s * ld_hist * SV_TOPK_MAX;
+        }
+        HIPCHECK(hipMemcpyAsync(dlp, hl.data(), hl.size() * sizeof(CbLogprobs), hipMemcpyHostToDevice, st));
+        a.lp = dlp;
+    }
+    launch_cb_lookup_step(q, n, st);
+    HIPCHECK(hipGetLastError());
+    std::vector<int32_t> ctr(3), state((size_t)4 * n + 3);
+    std::vector<CbSlot> after(n);
+    HIPCHECK(hipMemcpyAsync(history, dout, (size_t)n * ld_hist * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(rows, dcur, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(positions, dpos, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(ctr.data(), dctr, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(state.data(), dstate, state.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(after.data(), dslots, after.size() * sizeof(CbSlot), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    for (int s = 0; s < n; ++s) {
+        const int L0 = hist_len[s], L1 = after[s].step;
+        if (lps) {
+            for (int j = 0; j < K1; ++j) { out_logprob[s * K1 + j] = std::nanf(""); out_rank[s * K1 + j] = 0; }
+            if (lps[s].enable && L1 > L0) {
+                HIPCHECK(hipMemcpy(out_logprob + s * K1, dlogprob + (size_t)s * ld_hist + L0, (size_t)(L1 - L0) * sizeof(float), hipMemcpyDeviceToHost));
+                HIPCHECK(hipMemcpy(out_rank + s * K1, drank + (size_t)s * ld_hist + L0, (size_t)(L1 - L0) * sizeof(int32_t), hipMemcpyDeviceToHost));
+            }
+        }
+        live[s] = after[s].live; hist_len[s] = L1; n_draft[s] = state[s];
+        for (int k = 0; k < 3; ++k) counts[3 * s + k] = state[n + 3 * s + k];
+    }
+    flags3[0] = -ctr[0]; flags3[1] = 0; flags3[2] = ctr[2];
+    return 0;
+}
+
 // ban_tokens_kernel (processors.hip) on caller-given rows and histories: rewrites dev_logits in place
 extern "C" int sv_op_ban_tokens(float* dev_logits, int32_t B, int32_t V, int32_t ld, const int32_t* hist, int32_t ld_hist, const int32_t* hist_len,
                                 const sv_logits_processors* lp, sv_stream stream) {

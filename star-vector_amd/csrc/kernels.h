@@ -520,7 +520,7 @@ struct CbSlot {                  // device-resident, one per slot
     int32_t do_sample; float temperature, top_p; int32_t top_k;
     int32_t eos, pad, min_new; float penalty;
     int32_t n_stop; int32_t stop[SV_CB_MAXSTOP];
-    int32_t pad_[1];
+    int32_t base;                // prompt length: the slot's column c sits at position base + c (set and read by the drafting batch only)
     uint64_t seed;
     // vLLM 0.5.5 sampler semantics (vllm = 1): before the selection the slot's block rewrites its logits row in place with
     // logit_bias (CbBias), the min_tokens hold (eos and every `any` id -> -inf), repetition over the seen bitmap (prompt ids
@@ -559,6 +559,23 @@ struct CbStepArgs {
     const CbLogprobs* lp = nullptr;
 };
 void launch_cb_step(const CbStepArgs& a, int nblocks, hipStream_t st);
+
+// ---- prompt-lookup drafting in the continuous batch (cb_lookup/cb_lookup.hip; sv_cb_set_lookup).  A slot owns K1 = K + 1 decode rows:
+// rows s * K1 + j of cur_tok / positions / the block table and of the step's logits.  Row 0 carries the slot's last emitted id at its position,
+// rows 1 .. n_draft[s] the drafts behind it, the rest are copies of row 0 (lk_write_rows' layout).  One block per slot verifies the rows ONE
+// AFTER THE OTHER with the plain step's own row body (cb_row.h): after every committed token the slot's state is the plain batch's at that
+// column, so the next row is selected exactly as the plain batch would select it -- and it is looked at only if its draft was the token just
+// emitted.  Then the block drafts from the slot's history (lk_draft.h) and writes the rows of the next step.
+// first != 0: the first token of a new request.  Block b works for slot slot_map[b] on logits row b (the prompt pass's), there are no drafts.
+struct CbLookupArgs {
+    CbStepArgs st;                               // as the plain step's; slots, out_tokens, seen, counts, bias, lp indexed by slot
+    int K, max_ngram, min_ngram, first;
+    int32_t* n_draft;                            // [slots] live drafts of the step in flight
+    int32_t* counts;                             // [slots][3] {verification steps, drafts verified, drafts accepted} since the slot's admit
+    int32_t* totals;                             // [3] the same over every slot since the batch began (steps: one per slot and step)
+    const int32_t* forced; int forced_n, forced_ld;      // sv_debug_cb_set_lookup_drafts: draft j of slot s < forced_n is forced[s][step_s + j]
+};
+void launch_cb_lookup_step(const CbLookupArgs& a, int nblocks, hipStream_t st);
 
 // ---- shared prompt pass (fork.hip): one prompt, several samples.  Between the prompt pass and the first selection, on the engine stream:
 //   (a) the partially filled tail page of prompt u (len % 64 != 0) fans out from the row that took the prompt pass to the other rows of the prompt,

@@ -7,6 +7,7 @@
 // The arithmetic of lookup_kv_write is attn_decode_kernel's own (attention.hip), restated here because that kernel's text is pinned by hand;
 // tests/test_gpu_lookup_ops.py holds the two to the same bits.
 #include "../kernels.h"
+#include "lk_draft.h"
 
 namespace sv {
 
@@ -66,55 +67,16 @@ void launch_lookup_hold_eos(float* logits, int ld, int eos, const int32_t* n_emi
 }
 
 #define LK_THREADS 256
-#define LK_MAXK1 16
 #define LK_AM_SPLIT 8           // slices per row of launch_argmax_partial (sampling.hip AM_SPLIT)
 // the rule of sampling.hip's argmax_pair: lowest index wins a tie, NaN never wins
 __device__ __forceinline__ void lk_argmax_pair(float& v, int& i, float ov, int oi) {
     if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
 }
-// block-wide maximum of one int per thread (every thread gets it)
-__device__ __forceinline__ int lk_block_max(int v, int* sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    __syncthreads();                                             // sh may still be read from the round before
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = sh[0];
-    for (int w = 1; w < LK_THREADS / 64; ++w) v = max(v, sh[w]);
-    return v;
-}
-// The drafts of sequence s behind L generated ids (block-uniform result, the ids in sh_draft): at most K, never more than the budget leaves
-// room to emit (a step emits its accepted drafts and one token more).  For n = max_ngram .. min_ngram the LATEST earlier occurrence of the
-// last n ids whose continuation is not empty -- the largest i with hist[i, i + n) == hist[L - n, L) and i + n < L -- gives hist[i + n, ...),
-// cut at L.  Threads stride over i; a block max-reduce picks the largest.
+// The drafts of sequence s behind L generated ids (block-uniform result, the ids in sh_draft): the rule of lk_draft.h, at most K and never
+// more than the call's budget leaves room to emit (a step emits its accepted drafts and one token more).
 __device__ int lk_draft(const LookupArgs& p, int s, int L, int* sh_red, int* sh_draft) {
-    const int tid = threadIdx.x;
-    const int K = min(p.K, p.max_new - L - 1);
-    if (K <= 0) return 0;
-    if (p.forced) {
-        const int nd = max(0, min(K, p.forced_ld - L));
-        if (tid < nd) sh_draft[tid] = p.forced[(size_t)s * p.forced_ld + L + tid];
-        __syncthreads();
-        return nd;
-    }
-    const int32_t* hist = p.out_tok + (size_t)s * p.ld_out;
-    for (int n = p.max_ngram; n >= p.min_ngram; --n) {
-        if (L <= n) continue;
-        int best = -1;
-        for (int i = tid; i + n < L; i += LK_THREADS) {
-            bool m = true;
-            for (int k = 0; k < n; ++k) m = m && hist[i + k] == hist[L - n + k];
-            if (m) best = i;
-        }
-        best = lk_block_max(best, sh_red);
-        if (best >= 0) {
-            const int start = best + n, nd = min(K, L - start);
-            if (tid < nd) sh_draft[tid] = hist[start + tid];
-            __syncthreads();
-            return nd;
-        }
-    }
-    return 0;
+    return lk_draft_ids<LK_THREADS>(p.out_tok + (size_t)s * p.ld_out, L, min(p.K, p.max_new - L - 1), p.max_ngram, p.min_ngram,
+                                    p.forced ? p.forced + (size_t)s * p.forced_ld : nullptr, p.forced_ld, sh_red, sh_draft);
 }
 // the next step's rows of sequence s: row 0 = the last emitted id at its position, rows 1 .. nd the drafts behind it, the rest exact copies of row 0
 __device__ void lk_write_rows(const LookupArgs& p, int s, int last, int pos0, int nd, const int* sh_draft) {

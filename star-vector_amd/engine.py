@@ -823,6 +823,32 @@ class HipEngine:
     def cb_reset(self) -> None:
         check(self.lib.sv_cb_reset(self._h), "sv_cb_reset")
 
+    def cb_set_lookup(self, num_draft_tokens: int, max_ngram: int = 0, min_ngram: int = 0) -> None:
+        """Prompt-lookup drafting for the continuous batch (sv_cb_set_lookup): with num_draft_tokens = K > 0 every slot owns K + 1 decode rows,
+        a `cb_step` step verifies up to K drafted tokens per slot and emits 1 .. K + 1, and the batch holds max_batch // (K + 1) slots.  Every
+        request's tokens, finish and record are those of a batch with drafting off.  0 = off (the default).  Only while no batch is active:
+        before the first admit or after `cb_reset` (RuntimeError otherwise); the setting stays across `cb_reset`."""
+        lk = _lib.SvLookup(int(num_draft_tokens), int(max_ngram), int(min_ngram))
+        check(self.lib.sv_cb_set_lookup(self._h, C.byref(lk)), "sv_cb_set_lookup")
+
+    def cb_lookup_counts(self, slot: int = -1) -> dict:
+        """{steps, drafted, accepted} of a slot since its admit; slot = -1: the batch's totals (steps: one per live slot and step)."""
+        c = (C.c_int32 * 3)()
+        check(self.lib.sv_cb_lookup_counts(self._h, int(slot), c), "sv_cb_lookup_counts")
+        return {"steps": c[0], "drafted": c[1], "accepted": c[2]}
+
+    def cb_set_lookup_drafts(self, streams) -> None:
+        """Test surface (sv_debug_cb_set_lookup_drafts): draft j of slot s < len(streams) of the drafting batch admitted next is
+        streams[s][step_s + j] instead of the lookup (rows of equal length; nothing is drafted beyond them).  None clears it."""
+        if streams is None:
+            check(self.lib.sv_debug_cb_set_lookup_drafts(self._h, None, 0, 0), "sv_debug_cb_set_lookup_drafts")
+            return
+        t = torch.as_tensor(streams, dtype=torch.int32).contiguous()
+        if t.dim() != 2 or t.numel() == 0:
+            raise ValueError("streams must be [n, ld] ids")
+        arr = (C.c_int32 * t.numel())(*t.flatten().tolist())
+        check(self.lib.sv_debug_cb_set_lookup_drafts(self._h, arr, t.shape[0], t.shape[1]), "sv_debug_cb_set_lookup_drafts")
+
     def beam_history(self):
         """(parent beams, tokens), each int32 [n_steps, batch * num_beams], of the last beam-search ``generate``."""
         n, rows = C.c_int32(0), C.c_int32(0)
@@ -1825,6 +1851,64 @@ def op_cb_logprobs(logits, requests: Sequence[dict], logprobs: Sequence, history
     del keep
     return (torch.tensor(list(out), dtype=torch.int32), torch.tensor(list(lp), dtype=torch.float32), torch.tensor(list(rk), dtype=torch.int32),
             torch.tensor(list(ids), dtype=torch.int32).view(B, K), torch.tensor(list(vals), dtype=torch.float32).view(B, K))
+
+
+def op_cb_lookup_step(logits, K: int, requests: Sequence[dict], base, live, history, rows, positions, n_draft, max_ngram: int = 0,
+                      min_ngram: int = 0, forced=None, logprobs: Optional[Sequence] = None):
+    """ONE launch of the drafting batch's selection (cb_lookup_step_kernel; sv_op_cb_lookup_step) on caller-given state: n = len(requests)
+    slots of K + 1 rows, logits fp32 [n * (K + 1), V] (row s * (K + 1) + j = slot s's row j).  Slot s: request requests[s] (the `cb_admit`
+    dict), prompt length base[s], live[s], the ids it has emitted history[s] (a list), and the step in flight rows[s] / positions[s] (K + 1
+    each) with n_draft[s] live drafts.  forced: None or a list of equal-length id lists (slot s < len(forced) drafts forced[s][step + j]).
+    Returns a dict of host lists: live, history, rows, positions, n_draft (the state after the launch), counts [n][3] = {steps, drafted,
+    accepted} of this launch, finished, bad -- and, with `logprobs` (one entry per slot, as `cb_admit` takes them), logprob / rank [n][K + 1]:
+    the record of the columns each slot emitted (NaN / 0 behind them)."""
+    lib = _lib.load()
+    logits = _need(logits, torch.float32, "logits")
+    n, K1 = len(requests), int(K) + 1
+    R, V = logits.shape
+    if R != n * K1:
+        raise ValueError(f"logits must have n * (K + 1) = {n * K1} rows, got {R}")
+    ld = (V + 3) // 4 * 4
+    if ld != V:
+        pad = torch.full((R, ld), -float("inf"), dtype=torch.float32, device=logits.device)
+        pad[:, :V] = logits
+        logits = pad
+    history = [list(map(int, h)) for h in history]
+    if not (len(history) == len(base) == len(live) == len(rows) == len(positions) == len(n_draft) == n):
+        raise ValueError("one entry per slot in base / live / history / rows / positions / n_draft")
+    if any(len(r) != K1 for r in rows) or any(len(r) != K1 for r in positions):
+        raise ValueError("rows / positions hold K + 1 entries per slot")
+    ld_hist = max(len(h) for h in history) + K1
+    hist = (C.c_int32 * (n * ld_hist))()
+    for s, h in enumerate(history):
+        hist[s * ld_hist: s * ld_hist + len(h)] = h
+    lens = (C.c_int32 * n)(*[len(h) for h in history])
+    c_base = (C.c_int32 * n)(*[int(v) for v in base])
+    c_live = (C.c_int32 * n)(*[int(bool(v)) for v in live])
+    c_rows = (C.c_int32 * (n * K1))(*[int(v) for r in rows for v in r])
+    c_pos = (C.c_int32 * (n * K1))(*[int(v) for r in positions for v in r])
+    c_nd = (C.c_int32 * n)(*[int(v) for v in n_draft])
+    c_forced, fn, fld = None, 0, 0
+    if forced is not None:
+        fn, fld = len(forced), len(forced[0])
+        if any(len(f) != fld for f in forced):
+            raise ValueError("forced rows must have equal length")
+        c_forced = (C.c_int32 * (fn * fld))(*[int(v) for f in forced for v in f])
+    arr, keep = cb_requests(requests)
+    lps = cb_logprobs(requests, logprobs) if logprobs is not None else None
+    counts, flags = (C.c_int32 * (3 * n))(), (C.c_int32 * 3)()
+    lp, rk = (C.c_float * (n * K1))(), (C.c_int32 * (n * K1))()
+    check(lib.sv_op_cb_lookup_step(_ptr(logits), n, int(K), V, ld, arr, lps, c_base, c_live, hist, ld_hist, lens, c_rows, c_pos, c_nd, int(max_ngram),
+                                   int(min_ngram), c_forced, fn, fld, counts, flags, lp if lps is not None else None,
+                                   rk if lps is not None else None, _stream()), "sv_op_cb_lookup_step")
+    del keep
+    out = {"live": [int(v) for v in c_live], "history": [list(hist[s * ld_hist: s * ld_hist + lens[s]]) for s in range(n)],
+           "rows": [list(c_rows[s * K1:(s + 1) * K1]) for s in range(n)], "positions": [list(c_pos[s * K1:(s + 1) * K1]) for s in range(n)],
+           "n_draft": list(c_nd), "counts": [list(counts[3 * s:3 * s + 3]) for s in range(n)], "finished": flags[0], "bad": flags[2]}
+    if lps is not None:
+        out["logprob"] = [list(lp[s * K1:(s + 1) * K1]) for s in range(n)]
+        out["rank"] = [list(rk[s * K1:(s + 1) * K1]) for s in range(n)]
+    return out
 
 
 def op_ban_tokens(logits, history, no_repeat_ngram_size=0, bad_words_ids=None):

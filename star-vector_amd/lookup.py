@@ -6,6 +6,10 @@ The second half restates csrc/lookup_sampled/lookup_sampled.hip (sv_generate_loo
 column, prefix) stands for the sampler -- its random number is a function of (seed, step = column, row = sequence), its scores a function of
 the prefix -- and SeenSets stands for the repetition penalty's bitmaps as lookup_seen_kernel keeps them.
 
+The last part restates csrc/cb_lookup/cb_lookup.hip (sv_cb_set_lookup): CbLookupState is the drafting continuous batch -- slots with their own
+budget, EOS, stop sequence and stop_any ids, K + 1 decode rows each, admit / step(chooser) / release -- verified row after row against the
+slot's current state.
+
 State of a call over n_seq sequences, as the device keeps it:
     hist[s]      the ids sequence s has generated, at its own column (a list that grows; pads behind an early end)
     n_emit[s]    ids emitted, finished[s], base[s] = prompt length, n_draft[s] = live drafts of the step in flight
@@ -295,3 +299,151 @@ def lookup_chosen(chooser: Chooser, n_seq: int, K: int, max_new: int, eos: int =
         st.step(winners)
         sets.step(st)
     return st.tokens(), st
+
+
+# ---- sv_cb_set_lookup: drafting in the continuous batch ---------------------------------------------------------------------------------------
+# csrc/cb_lookup/cb_lookup.hip restated.  A slot of the batch owns K1 = K + 1 decode rows, rows s * K1 .. s * K1 + K of cur_tok / positions;
+# its own budget, EOS, stop sequence and stop_any ids; and the three counters {verification steps, drafts verified, drafts accepted}.  One
+# block per slot verifies the slot's rows ONE AFTER THE OTHER: row j is selected against the slot's state after rows 0 .. j - 1 have been
+# committed, and is looked at only if its draft is the token row j - 1 emitted.
+# (slot, column, the ids the row was computed from, hold) -> the id at that column.  `hold` = the column is below the request's min_new (the
+# selection bars EOS -- and, under vLLM semantics, the stop_any ids -- while it is set).
+CbChooser = Callable[[int, int, List[int], bool], int]
+
+
+@dataclass
+class CbRequest:
+    budget: int
+    eos: int = -1
+    stop: Sequence[int] = ()
+    stop_any: Sequence[int] = ()
+    min_new: int = 0
+    base: int = 0                 # prompt length: column c sits at position base + c
+
+
+def cb_plain_stream(slot: int, req: CbRequest, chooser: CbChooser):
+    """The one-token-per-step batch (cb_step_kernel's bookkeeping) for one request: (the ids it emits, still live -- never, once the budget is spent)."""
+    hist: List[int] = []
+    while True:
+        t = len(hist)
+        tok = chooser(slot, t, list(hist), t < req.min_new)
+        hist.append(tok)
+        fin = tok == req.eos or t + 1 >= req.budget or tok in req.stop_any
+        n = len(req.stop)
+        if not fin and n > 0 and t + 1 >= n and hist[t + 1 - n:] == list(req.stop):
+            fin = True
+        if fin:
+            return hist, False
+
+
+class CbLookupState:
+    """The drafting batch as the device keeps it.  Per slot: the request, live, hist (step = len(hist)), n_draft, counts [3]; per batch: the
+    row arrays cur_tok / positions [max_batch], n_live, events, bad, totals [3] (steps: one per live slot and step)."""
+
+    def __init__(self, max_batch: int, K: int, max_ngram: int = 3, min_ngram: int = 1, vocab: int = 1 << 30, forced=None):
+        if K < 1 or max_batch // (K + 1) < 1:
+            raise ValueError(f"K {K} + 1 rows per slot do not fit max_batch {max_batch}")
+        self.max_batch, self.K, self.K1 = max_batch, K, K + 1
+        self.capacity = max_batch // (K + 1)
+        self.max_ngram, self.min_ngram, self.vocab, self.forced = max_ngram, min_ngram, vocab, forced
+        self.req: List[Optional[CbRequest]] = [None] * self.capacity
+        self.live = [False] * self.capacity
+        self.hist: List[List[int]] = [[] for _ in range(self.capacity)]
+        self.n_draft = [0] * self.capacity
+        self.counts = [[0, 0, 0] for _ in range(self.capacity)]
+        self.cur_tok = [0] * max_batch
+        self.positions = [0] * max_batch
+        self.n_live = self.events = self.bad = 0
+        self.totals = [0, 0, 0]
+
+    # -- the layout --
+    def bucket(self) -> int:
+        """rows of the step graph: (highest used slot + 1) * K1, a power of two >= 8, capped at max_batch"""
+        hi = max([s + 1 for s in range(self.capacity) if self.req[s] is not None], default=0) * self.K1
+        b = 8
+        while b < hi:
+            b <<= 1
+        return min(b, self.max_batch)
+
+    def rows_of(self, s: int) -> List[int]:
+        return self.cur_tok[s * self.K1:(s + 1) * self.K1]
+
+    def positions_of(self, s: int) -> List[int]:
+        return self.positions[s * self.K1:(s + 1) * self.K1]
+
+    def _draft(self, s: int) -> List[int]:
+        L, r = len(self.hist[s]), self.req[s]
+        K = min(self.K, r.budget - L - 1)
+        if self.forced is not None and s < len(self.forced):
+            return [int(t) for t in self.forced[s][L:L + max(K, 0)]]
+        return draft(self.hist[s], self.K, self.max_ngram, self.min_ngram, r.budget)
+
+    def _write_rows(self, s: int, drafts: List[int]) -> None:
+        L, nd = len(self.hist[s]), len(drafts)
+        last, pos0 = self.hist[s][-1], self.req[s].base + L - 1
+        for j in range(self.K1):
+            live = 1 <= j <= nd
+            self.cur_tok[s * self.K1 + j] = drafts[j - 1] if live else last
+            self.positions[s * self.K1 + j] = pos0 + (j if live else 0)
+        self.n_draft[s] = nd
+
+    def _commit(self, s: int, tok: int) -> bool:
+        """the plain step's bookkeeping for one token; returns fin"""
+        r = self.req[s]
+        if not 0 <= tok < self.vocab:
+            tok, self.bad = 0, self.bad or 1
+        self.hist[s].append(tok)
+        t1 = len(self.hist[s])
+        fin = tok == r.eos or t1 >= r.budget or tok in r.stop_any
+        n = len(r.stop)
+        if not fin and n > 0 and t1 >= n and self.hist[s][t1 - n:] == list(r.stop):
+            fin = True
+        if fin:
+            self.live[s] = False
+            self.n_live -= 1
+            self.events += 1
+        return fin
+
+    # -- the calls --
+    def admit(self, req: CbRequest, chooser: CbChooser) -> int:
+        """Lowest free slot, or -1 when the batch is full (SV_EBUSY: nothing changes).  The first token comes from the prompt pass's row
+        through the `first` form: no drafts to verify, the slot's K1 rows written, its counters from zero."""
+        free = [s for s in range(self.capacity) if self.req[s] is None]
+        if not free:
+            return -1
+        s = free[0]
+        self.req[s], self.live[s], self.hist[s], self.counts[s] = req, True, [], [0, 0, 0]
+        self.n_live += 1
+        fin = self._commit(s, chooser(s, 0, [], 0 < req.min_new))
+        self._write_rows(s, [] if fin else self._draft(s))
+        return s
+
+    def step(self, chooser: CbChooser) -> None:
+        """One verification step over every live slot.  Row j of a slot was computed from the slot's ids followed by its first j drafts."""
+        for s in range(self.capacity):
+            if self.req[s] is None or not self.live[s]:
+                continue                              # a dead slot is left untouched
+            r, nd, L0 = self.req[s], self.n_draft[s], len(self.hist[s])
+            rows = self.rows_of(s)
+            j = 0
+            while True:
+                col = len(self.hist[s])
+                tok = chooser(s, col, self.hist[s][:L0] + rows[1:j + 1], col < r.min_new)
+                fin = self._commit(s, tok)
+                if fin or j >= nd or rows[j + 1] != self.hist[s][-1]:
+                    break
+                j += 1
+            acc = len(self.hist[s]) - L0 - 1
+            self._write_rows(s, [] if fin else self._draft(s))
+            for c, v in ((self.counts[s], (1, nd, acc)), (self.totals, (1, nd, acc))):
+                for k in range(3):
+                    c[k] += v[k]
+
+    def release(self, s: int) -> None:
+        if self.req[s] is None:
+            raise ValueError(f"slot {s} is not in use")
+        if self.live[s]:
+            self.n_live -= 1
+        self.req[s], self.live[s], self.hist[s], self.n_draft[s] = None, False, [], 0
+        for j in range(self.K1):
+            self.cur_tok[s * self.K1 + j] = self.positions[s * self.K1 + j] = 0

@@ -119,7 +119,7 @@ class ModelWorker:
     def __init__(self, controller_addr: str, worker_addr: str, worker_id: str, no_register: bool, model_path: str = "",
                  model_name: Optional[str] = None, device="cuda", limit_model_concurrency: int = 5, *,
                  model=None, tokenizer=None, image_processor=None, context_len: Optional[int] = None,
-                 continuous_batching: bool = True):
+                 continuous_batching: bool = True, prompt_lookup_num_tokens: int = 0, max_matching_ngram_size: int = 0):
         self.controller_addr, self.worker_addr, self.worker_id = controller_addr, worker_addr, worker_id
         model_path = model_path[:-1] if model_path.endswith("/") else model_path
         if model_name is None:                                         # :46-52
@@ -141,7 +141,10 @@ class ModelWorker:
         eng = getattr(lm, "_engine", None)
         if continuous_batching and lm is not None and eng is not None and hasattr(eng, "cb_admit"):
             from .batching import ContinuousBatcher
-            self.batcher = ContinuousBatcher(eng)
+            # --prompt-lookup-num-tokens K: every decode step verifies up to K tokens drafted from the request's own output (same tokens,
+            # max_batch // (K + 1) requests share the loop: at the default concurrency of 5 the other rows of the engine are idle anyway)
+            kw = dict(prompt_lookup_num_tokens=prompt_lookup_num_tokens, max_matching_ngram_size=max_matching_ngram_size) if prompt_lookup_num_tokens else {}
+            self.batcher = ContinuousBatcher(eng, **kw)
             lm.batcher = self.batcher
         self.limit_model_concurrency = limit_model_concurrency
         self.model_semaphore = None                                    # created on the event loop by the first request
@@ -312,11 +315,18 @@ def main(argv=None):                                                   # :235-26
     p.add_argument("--no-register", action="store_true")
     p.add_argument("--no-continuous-batching", action="store_true",
                    help="run concurrent requests one generate call at a time (the reference's behaviour)")
+    p.add_argument("--prompt-lookup-num-tokens", type=int, default=0,
+                   help="K > 0: prompt-lookup drafting in the continuous batch -- a step verifies up to K drafted tokens per request (same tokens; "
+                        "max_batch // (K + 1) requests share the decode loop); 0 = off")
+    p.add_argument("--max-matching-ngram-size", type=int, default=0, help="longest n-gram the draft lookup matches (0 = 3)")
     args = p.parse_args(argv)
+    if args.prompt_lookup_num_tokens and args.no_continuous_batching:
+        p.error("--prompt-lookup-num-tokens drafts in the continuous batch: drop --no-continuous-batching")
     import uvicorn
     worker = ModelWorker(args.controller_address, args.worker_address, str(uuid.uuid4())[:6], args.no_register,
                          args.model_path, args.model_name, args.device, args.limit_model_concurrency,
-                         continuous_batching=not args.no_continuous_batching)
+                         continuous_batching=not args.no_continuous_batching, prompt_lookup_num_tokens=args.prompt_lookup_num_tokens,
+                         max_matching_ngram_size=args.max_matching_ngram_size)
     uvicorn.run(build_app(worker), host=args.host, port=args.port, log_level="info")
 
 

@@ -246,11 +246,32 @@ class LLM:
     """vLLM's offline `LLM` over the HIP engine.  `model` is a LOCAL checkpoint directory in the reference's format, loaded by
     `StarVectorForCausalLM.from_pretrained` (hub names fail there: no download).  `max_num_seqs` = the engine's batch rows (the
     continuous batch queues anything beyond it), `max_model_len` = its sequence capacity.  `dtype` float16 / float32 run in
-    bfloat16 (with a warning).  `trust_remote_code` is accepted for compatibility (the model code is this package)."""
+    bfloat16 (with a warning).  `trust_remote_code` is accepted for compatibility (the model code is this package).
+
+    Speculative decoding, vLLM 0.5.5's own arguments: ``speculative_model="[ngram]", num_speculative_tokens=K`` (1..15),
+    ``ngram_prompt_lookup_max=n`` (0 / None = 3), ``ngram_prompt_lookup_min=m`` (0 / None = 1) switch on prompt-lookup drafting in the
+    continuous batch (`HipEngine.cb_set_lookup`): every decode step verifies up to K drafted tokens per request, and the engine then
+    runs max_num_seqs // (K + 1) requests at a time.  Any other `speculative_model` raises NotImplementedError (there is no draft model).
+    The draft searches the request's OUTPUT ids only -- the prompt here is `inputs_embeds` (image features and text embeddings), not ids,
+    where vLLM's n-gram worker searches prompt and output.  That changes the acceptance rate, never the tokens: every request returns
+    what it returns without these arguments."""
 
     def __init__(self, model: str, tokenizer=None, dtype: str = "auto", max_model_len: Optional[int] = None,
-                 max_num_seqs: Optional[int] = None, trust_remote_code: bool = False, **kwargs):
+                 max_num_seqs: Optional[int] = None, trust_remote_code: bool = False, speculative_model: Optional[str] = None,
+                 num_speculative_tokens: Optional[int] = None, ngram_prompt_lookup_max: Optional[int] = None,
+                 ngram_prompt_lookup_min: Optional[int] = None, **kwargs):
         from .model import StarVectorForCausalLM
+        self._lookup = {}
+        if speculative_model is not None:
+            if speculative_model != "[ngram]":
+                raise NotImplementedError(f"speculative_model={speculative_model!r} is not built: there is no draft model, only \"[ngram]\" "
+                                          "(prompt-lookup drafting)")
+            if num_speculative_tokens is None or not 1 <= int(num_speculative_tokens) <= 15:
+                raise ValueError(f"num_speculative_tokens must lie in 1..15 with speculative_model=\"[ngram]\", got {num_speculative_tokens}")
+            self._lookup = dict(prompt_lookup_num_tokens=int(num_speculative_tokens), max_matching_ngram_size=int(ngram_prompt_lookup_max or 0),
+                                min_matching_ngram_size=int(ngram_prompt_lookup_min or 0))
+        elif num_speculative_tokens or ngram_prompt_lookup_max or ngram_prompt_lookup_min:
+            raise ValueError("num_speculative_tokens / ngram_prompt_lookup_max / ngram_prompt_lookup_min need speculative_model=\"[ngram]\"")
         dt = str(dtype).replace("torch.", "")
         if dt in ("float16", "half", "float32", "float"):
             warnings.warn(f"dtype={dtype}: the HIP engine computes in bfloat16; weights and inputs are converted", UserWarning)
@@ -340,7 +361,7 @@ class LLM:
         if logprobs is not None:
             for j in jobs:
                 j["params"] = dict(j["params"], logprobs=int(logprobs), logprob_source="processed")
-        batcher = ContinuousBatcher(self.engine)
+        batcher = ContinuousBatcher(self.engine, **getattr(self, "_lookup", {}))
         try:
             handles = []
             for _, grp in itertools.groupby(jobs, key=lambda j: j["input"]):
