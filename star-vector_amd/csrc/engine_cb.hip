@@ -498,13 +498,9 @@ extern "C" int sv_cb_step(sv_engine* e, int32_t n_steps, int32_t* n_live_out, sv
         // records log-probs (the recording kernel: a batch in which nobody asks replays the plain graphs).
         auto capture = [&](int copies, hipGraphExec_t* out) -> int {
             const int key = Bb + 1024 * (copies > 1 ? copies : 0) + (record ? 1 << 24 : 0);
-            auto it = e->cb_graphs.find(key);
-            if (it != e->cb_graphs.end()) { *out = it->second.second; return 0; }
-            hipGraph_t g = nullptr;
-            hipGraphExec_t ge = nullptr;
-            SVCHECK(capture_steps(st, copies, one_step, &g, &ge));
-            if (ge) e->cb_graphs[key] = {g, ge};
-            *out = ge;
+            GraphSlot& slot = e->cb_graphs[key];         // (the map's key says everything: the slot's own stays empty)
+            if (!slot.x) SVCHECK(slot.use("", st, copies, one_step));
+            *out = slot.x;
             return 0;
         };
         if (n_steps >= 2 && n_steps <= graph_steps_cap()) {
@@ -518,11 +514,11 @@ extern "C" int sv_cb_step(sv_engine* e, int32_t n_steps, int32_t* n_live_out, sv
         else one_step();
     }
     // the live count and the give-up / non-finite flag in one round trip
-    HIPCHECK(hipMemcpyAsync(&e->h_flags[3], e->cb_nlive, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPCHECK(hipMemcpyAsync(&e->h_flags[4], e->d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(&e->h_flags[HF_CB_LIVE], e->cb_nlive, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(&e->h_flags[HF_BAD], e->d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
-    *n_live_out = e->h_flags[3];
-    SVCHECK(report_bad_logits(e, st, "sv_cb_step", e->h_flags[4]));
+    *n_live_out = e->h_flags[HF_CB_LIVE];
+    SVCHECK(report_bad_logits(e, st, "sv_cb_step", e->h_flags[HF_BAD]));
     e->timing_graph = gexec ? (double)per_launch : 0.0;
     return 0;
 }
@@ -643,13 +639,7 @@ int cb_check_lookup(const char* who, const sv_lookup* lookup, sv_lookup& lk) {
     if (lk.min_ngram == 0) lk.min_ngram = 1;
     return 0;
 }
-void cb_drop_graphs(sv_engine* e) {
-    for (auto& kv : e->cb_graphs) {
-        if (kv.second.second) (void)hipGraphExecDestroy(kv.second.second);
-        if (kv.second.first) (void)hipGraphDestroy(kv.second.first);
-    }
-    e->cb_graphs.clear();
-}
+void cb_drop_graphs(sv_engine* e) { e->cb_graphs.clear(); }      // (GraphSlot's destructor destroys the handles)
 }  // namespace sveng
 
 extern "C" int sv_cb_set_lookup(sv_engine* e, const sv_lookup* lookup) {

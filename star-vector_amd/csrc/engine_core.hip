@@ -166,6 +166,13 @@ int capture_steps(hipStream_t st, int copies, const std::function<void()>& one_s
     return 0;
 }
 }  // namespace sveng
+int GraphSlot::use(const std::string& k, hipStream_t st, int copies, const std::function<void()>& one_step, bool required) {
+    if (holds(k)) return 0;
+    drop();
+    SVCHECK(capture_steps(st, copies, one_step, &g, &x, required));
+    if (x) key = k;
+    return 0;
+}
 
 static void reg_linear(sv_engine* e, const std::string& base, Linear* l, int N, int K, int Kalign, bool has_bias) {
     l->N = N; l->K = K; l->Npad = round_up(N, 32); l->Kpad = round_up(K, Kalign);
@@ -353,13 +360,8 @@ extern "C" int sv_destroy(sv_engine* e) {
     (void)hipDeviceSynchronize();
     for (void* p : e->allocs) (void)hipFree(p);
     e->beam.destroy();
-    for (auto& kv : e->cb_graphs) { if (kv.second.second) (void)hipGraphExecDestroy(kv.second.second); if (kv.second.first) (void)hipGraphDestroy(kv.second.first); }
-    if (e->gen_gexec) (void)hipGraphExecDestroy(e->gen_gexec);
-    if (e->gen_graph) (void)hipGraphDestroy(e->gen_graph);
-    if (e->gen_gexec_multi) (void)hipGraphExecDestroy(e->gen_gexec_multi);
-    if (e->gen_graph_multi) (void)hipGraphDestroy(e->gen_graph_multi);
-    if (e->lk_gexec) (void)hipGraphExecDestroy(e->lk_gexec);
-    if (e->lk_graph) (void)hipGraphDestroy(e->lk_graph);
+    cb_drop_graphs(e);               // (the kept graphs go before the streams, as they always have; `delete e` finds the slots empty)
+    e->gen_step.drop(); e->gen_multi.drop(); e->lk_step.drop();
     if (e->score_ws) (void)hipFree(e->score_ws);
     if (e->score_chunk_ws) (void)hipFree(e->score_chunk_ws);
     if (e->score_lse_ws) (void)hipFree(e->score_lse_ws);

@@ -1,12 +1,26 @@
-// Host driver, part 3 of 5: sv_generate -- the greedy / sampling loop (one decode step captured as a hipGraph and replayed, the
-// stop state on device), beam search over the same step, and the standalone beam scorer's C ABI (sv_beam_*).
+// Host driver, part 3 of 5: sv_generate* -- the stop state lives on the device, one decode step is captured as a hipGraph and replayed.
+//   sel_mode / sample_and_finish   the selection a call's sv_sampling asks for, and the launches of one step behind the lm_head
+//   generate_beam                  beam search over the same decode step (its graph is a GraphSlot of the call)
+//   GenCall / check_gen_call       one validator behind the C ABI entry points; generate_retry = the optimistic-ownership second attempt
+//   GenFrame                       the call frame of the two non-beam drivers: budget checks, lock + stream ordering + cb_guard, prompt pass + state +
+//                                  first token + its one round trip, the streaming helper, the poll of the device block, report + tokens + timing
+//   lookup_attempt                 B x (K + 1) aliased rows, verification step, kept in e->lk_step; polls after every chunk of 8
+//   generate_attempt               B x G rows, the plain step, kept in e->gen_step (+ e->gen_multi: U steps per launch); polls only when something can end the call
+// and the standalone beam scorer's C ABI (sv_beam_*).  The kept graphs are GraphSlots (engine_internal.h): dropping and replacing is theirs.
 #include "engine_internal.h"
 
+// What a call's sv_sampling asks of the selection, derived once: the repetition penalty is on for a factor > 0 other than 1 (seen = the engine's
+// bitmap then), the min-length hold for min_new_tokens > 0 with an EOS id inside the vocabulary (min_new = 0 when it is off)
+struct SelMode { bool pen; int min_new; uint32_t* seen; };
+static SelMode sel_mode(const sv_engine* e, const sv_sampling& sp) {
+    const bool pen = sp.repetition_penalty > 0.f && sp.repetition_penalty != 1.0f;
+    const bool hold = sp.min_new_tokens > 0 && sp.eos_token_id >= 0 && sp.eos_token_id < e->cfg.vocab;
+    return {pen, hold ? sp.min_new_tokens : 0, pen ? e->seen : nullptr};
+}
 // sample from e->logits into next_tok, then the bookkeeping kernel
 // fused: the lm_head launch in front has already left every row's best (value, lowest index) in e->amax (gemm.hip, SkinnyArgs::amax):
 // no argmax launch, finish_step_kernel decodes the keys
 static FinishArgs make_finish_args(sv_engine* e, int B, const sv_sampling& sp, int max_new, bool fused) {
-    const bool pen = sp.repetition_penalty > 0.f && sp.repetition_penalty != 1.0f;
     FinishArgs f;
     f.pval = sp.do_sample ? nullptr : e->am_val; f.pidx = sp.do_sample ? nullptr : e->am_idx;
     f.amax = fused ? e->amax : nullptr;
@@ -14,20 +28,20 @@ static FinishArgs make_finish_args(sv_engine* e, int B, const sv_sampling& sp, i
     f.out_tokens = e->out_tok; f.ld_out = e->out_ld; f.step = e->d_step; f.done = e->d_done; f.n_emitted = e->d_nemit;
     f.stop_ids = e->d_stop; f.n_stop = sp.n_stop; f.eos = sp.eos_token_id; f.pad = sp.pad_token_id; f.B = B;
     f.max_new = max_new;
-    f.seen = pen ? e->seen : nullptr; f.seen_words = e->seen_words;
+    f.seen = sel_mode(e, sp).seen; f.seen_words = e->seen_words;
     f.V = e->cfg.vocab; f.bad = e->d_bad;
     return f;
 }
 // sv_generate_ex outputs: the step's raw row and processed row, BEFORE suppress_token rewrites the EOS logit in place
 // what: 1 = the raw row, 2 = the processed row, 3 = both (CaptureArgs::what)
 static void capture_step(sv_engine* e, int B, const sv_sampling& sp, hipStream_t st, int what = 3) {
-    const bool pen = sp.repetition_penalty > 0.f && sp.repetition_penalty != 1.0f;
+    const SelMode m = sel_mode(e, sp);
     CaptureArgs c;
     c.desc = e->cap_desc; c.src = e->logits; c.ld_src = e->Vpad; c.V = e->cfg.vocab; c.B = B;
     c.step = e->d_step; c.done = e->d_done;
-    c.seen = pen ? e->seen : nullptr; c.seen_words = e->seen_words; c.penalty = sp.repetition_penalty;
+    c.seen = m.seen; c.seen_words = e->seen_words; c.penalty = sp.repetition_penalty;
     c.eos = sp.eos_token_id;
-    c.min_new = (sp.min_new_tokens > 0 && sp.eos_token_id >= 0 && sp.eos_token_id < e->cfg.vocab) ? sp.min_new_tokens : 0;
+    c.min_new = m.min_new;
     c.do_sample = sp.do_sample ? 1 : 0; c.temperature = sp.temperature; c.top_p = sp.top_p; c.top_k = sp.top_k;
     c.warp = (sp.do_sample && e->cap_host.scores) ? e->cap_warp : nullptr;
     c.minp_log = e->minp_log; c.what = what;
@@ -35,14 +49,14 @@ static void capture_step(sv_engine* e, int B, const sv_sampling& sp, hipStream_t
 }
 // sv_generate_stats: the statistics of the token this step emits (TokenStatsArgs::what: 1 = the raw row's sums, 2 = the outputs, 3 = both)
 static void token_stats_step(sv_engine* e, int B, const sv_sampling& sp, hipStream_t st, int what) {
-    const bool pen = sp.repetition_penalty > 0.f && sp.repetition_penalty != 1.0f;
+    const SelMode m = sel_mode(e, sp);
     TokenStatsArgs a;
     a.desc = e->ts_desc; a.src = e->logits; a.ld_src = e->Vpad; a.V = e->cfg.vocab; a.B = B;
     a.step = e->d_step; a.done = e->d_done; a.unfinished = e->unfinished;
     a.next = e->next_tok; a.pval = sp.do_sample ? nullptr : e->am_val; a.pidx = sp.do_sample ? nullptr : e->am_idx;
-    a.seen = pen ? e->seen : nullptr; a.seen_words = e->seen_words; a.penalty = sp.repetition_penalty;
+    a.seen = m.seen; a.seen_words = e->seen_words; a.penalty = sp.repetition_penalty;
     a.eos = sp.eos_token_id;
-    a.min_new = (sp.min_new_tokens > 0 && sp.eos_token_id >= 0 && sp.eos_token_id < e->cfg.vocab) ? sp.min_new_tokens : 0;
+    a.min_new = m.min_new;
     a.do_sample = sp.do_sample ? 1 : 0; a.temperature = sp.temperature; a.top_p = sp.top_p; a.top_k = sp.top_k;
     a.minp_log = e->minp_log; a.raw = e->ts_raw; a.what = what;
     launch_token_stats(a, st);
@@ -50,14 +64,14 @@ static void token_stats_step(sv_engine* e, int B, const sv_sampling& sp, hipStre
 // sv_generate_topk: the k best ids of this step's distribution and the rank of the emitted token (TokenTopkArgs, kernels.h)
 static_assert(SV_TOPK_MAX == SV_TOPK_MAX_DEV, "topk.h's list length is the ABI's");
 static void token_topk_step(sv_engine* e, int B, const sv_sampling& sp, hipStream_t st, bool want_rank) {
-    const bool pen = sp.repetition_penalty > 0.f && sp.repetition_penalty != 1.0f;
+    const SelMode m = sel_mode(e, sp);
     TokenTopkArgs a;
     a.desc = e->tk_desc; a.src = e->logits; a.ld_src = e->Vpad; a.V = e->cfg.vocab; a.B = B;
     a.step = e->d_step; a.done = e->d_done; a.unfinished = e->unfinished;
     a.next = e->next_tok; a.pval = sp.do_sample ? nullptr : e->am_val; a.pidx = sp.do_sample ? nullptr : e->am_idx;
-    a.seen = pen ? e->seen : nullptr; a.seen_words = e->seen_words; a.penalty = sp.repetition_penalty;
+    a.seen = m.seen; a.seen_words = e->seen_words; a.penalty = sp.repetition_penalty;
     a.eos = sp.eos_token_id;
-    a.min_new = (sp.min_new_tokens > 0 && sp.eos_token_id >= 0 && sp.eos_token_id < e->cfg.vocab) ? sp.min_new_tokens : 0;
+    a.min_new = m.min_new;
     a.do_sample = sp.do_sample ? 1 : 0; a.temperature = sp.temperature; a.top_p = sp.top_p; a.top_k = sp.top_k;
     a.minp_log = e->minp_log; a.k = e->tk_k; a.source = e->tk_source; a.want_rank = want_rank ? 1 : 0;
     launch_token_topk(a, st);
@@ -66,7 +80,8 @@ static void sample_and_finish(sv_engine* e, int B, const sv_sampling& sp, int ma
     if (fused && e->fin_folded) { e->fin_folded = false; return; }      // the lm_head launch in front did the selection AND the bookkeeping (SkinnyArgs::finish)
     // sv_generate_stats: one launch between the selection and the bookkeeping; a step that rewrites the raw row in place (a ban, the min-length
     // hold) takes the raw row's sums in a launch of their own in front of the rewrite (a statistics call never folds: fused is off for it)
-    const bool rewrite = e->ban_ngram > 0 || e->ban_nwords > 0 || (sp.min_new_tokens > 0 && sp.eos_token_id >= 0 && sp.eos_token_id < e->cfg.vocab);
+    const SelMode m = sel_mode(e, sp);
+    const bool rewrite = e->ban_ngram > 0 || e->ban_nwords > 0 || m.min_new > 0;
     const bool ts_split = e->ts_on && rewrite;
     if (ts_split) token_stats_step(e, B, sp, st, 1);
     // sv_generate_topk, source 0 on such a step: the raw list is taken here as well, without the rank (the token is not known yet; a request for
@@ -84,25 +99,31 @@ static void sample_and_finish(sv_engine* e, int B, const sv_sampling& sp, int ma
         launch_ban_tokens(ba, st);
         if (e->cap_on && e->cap_host.scores) capture_step(e, B, sp, st, 2);
     } else if (e->cap_on) capture_step(e, B, sp, st);                   // (a capturing call never folds: fused is off for it)
-    const bool pen = sp.repetition_penalty > 0.f && sp.repetition_penalty != 1.0f;
-    const uint32_t* seen = pen ? e->seen : nullptr;
-    if (sp.min_new_tokens > 0 && sp.eos_token_id >= 0 && sp.eos_token_id < e->cfg.vocab)
-        suppress_token(e->logits, e->Vpad, sp.eos_token_id, e->d_step, sp.min_new_tokens, B, st);
+    if (m.min_new > 0) suppress_token(e->logits, e->Vpad, sp.eos_token_id, e->d_step, m.min_new, B, st);
     if (sp.do_sample) {
         SampleArgs sa;
         sa.logits = e->logits; sa.ld = e->Vpad; sa.V = e->cfg.vocab; sa.B = B; sa.temperature = sp.temperature;
         sa.top_p = sp.top_p; sa.top_k = sp.top_k; sa.seed = sp.seed; sa.step = e->d_step; sa.out = e->next_tok; sa.scratch = e->sample_scratch;
-        sa.seen = seen; sa.seen_words = e->seen_words; sa.penalty = sp.repetition_penalty;
+        sa.seen = m.seen; sa.seen_words = e->seen_words; sa.penalty = sp.repetition_penalty;
         sa.minp_log = e->minp_log;
         launch_sample_top_p(sa, st);
     } else if (!fused) {
-        launch_argmax_partial(e->logits, e->Vpad, e->cfg.vocab, e->am_val, e->am_idx, B, seen, e->seen_words,
+        launch_argmax_partial(e->logits, e->Vpad, e->cfg.vocab, e->am_val, e->am_idx, B, m.seen, e->seen_words,
                               sp.repetition_penalty, st);
     }
     if (e->ts_on) token_stats_step(e, B, sp, st, ts_split ? 2 : 3);
     if (e->tk_on && !tk_front) token_topk_step(e, B, sp, st, e->tk_rank);
     const FinishArgs f = make_finish_args(e, B, sp, max_new, fused);
     launch_finish_step(f, st);
+}
+
+// timing[0] = prompt pass + first token, [1] = the rest of the call (it ends now), [2] = decode steps, timing_graph = steps per graph launch (0: no graph)
+using GenClock = std::chrono::steady_clock;
+static void set_timing(sv_engine* e, GenClock::time_point t0, GenClock::time_point t1, double steps, double per_launch) {
+    e->timing[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    e->timing[1] = std::chrono::duration<double, std::milli>(GenClock::now() - t1).count();
+    e->timing[2] = steps;
+    e->timing_graph = per_launch;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -145,7 +166,7 @@ static int generate_beam(sv_engine* e, const void* dev_embeds, int B, int S0, co
     const int need = (S0 + max_new + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS;
     if (need > e->pages_per_seq) return fail(SV_EINVAL, "sequence length %d exceeds max_seq_len %d", S0 + max_new, c.max_seq_len);
 
-    auto t0 = std::chrono::steady_clock::now();
+    auto t0 = GenClock::now();
     HIPCHECK(hipMemsetAsync(e->d_bad, 0, sizeof(int32_t), st));         // a flag left by an earlier, failed call is not this call's
     BeamConfig bc;
     bc.B = B; bc.nb = nb; bc.V = c.vocab; bc.max_new = max_new; bc.eos = sp->eos_token_id; bc.pad = sp->pad_token_id;
@@ -185,39 +206,33 @@ static int generate_beam(sv_engine* e, const void* dev_embeds, int B, int S0, co
     launch_beam_tail_copy(kv, st);              // the prompt's tail page fans out to beams 1.. (parent = first beam row)
     kv.L_fixed = -1;
     beam_step(e, kv, nb, st);                   // first token: every beam of a request reads the request's logits row
-    HIPCHECK(hipMemcpyAsync(&e->h_flags[0], e->d_done, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(&e->h_flags[HF_DONE], e->d_done, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
-    auto t1 = std::chrono::steady_clock::now();
+    auto t1 = GenClock::now();
 
     int steps = 0;
     const int chunk = sp->sync_every > 0 ? sp->sync_every : 32;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t gexec = nullptr;
-    if (!e->h_flags[0] && graph_enabled())
-        SVCHECK(capture_steps(st, 1, [&]() { decode_forward(e, R, st); beam_step(e, kv, 1, st); }, &graph, &gexec));
-    while (!e->h_flags[0]) {
+    GraphSlot step;                             // this call's own (kv travels by value in it): released on every way out
+    const auto one_step = [&]() { decode_forward(e, R, st); beam_step(e, kv, 1, st); };
+    if (!e->h_flags[HF_DONE] && graph_enabled()) SVCHECK(step.use("", st, 1, one_step));
+    while (!e->h_flags[HF_DONE]) {
         int n = max_new - 1 - steps;
         if (n <= 0) break;
         if (n > chunk) n = chunk;
         for (int i = 0; i < n; ++i) {
-            if (gexec) {
-                HIPCHECK(hipGraphLaunch(gexec, st));
-            } else {
-                decode_forward(e, R, st);
-                beam_step(e, kv, 1, st);
-            }
+            if (step.x) HIPCHECK(hipGraphLaunch(step.x, st));
+            else one_step();
         }
         steps += n;
-        HIPCHECK(hipMemcpyAsync(&e->h_flags[0], e->d_done, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipMemcpyAsync(&e->h_flags[HF_DONE], e->d_done, sizeof(int32_t), hipMemcpyDeviceToHost, st));
         HIPCHECK(hipStreamSynchronize(st));
     }
-    const double gexec_used = gexec ? 1.0 : 0.0;
-    if (gexec) (void)hipGraphExecDestroy(gexec);
-    if (graph) (void)hipGraphDestroy(graph);
+    const double gexec_used = step.x ? 1.0 : 0.0;
+    step.drop();
     // the decode steps of a beam search run the fused MLP launch too: its give-up code must not come back as rc 0 with hypotheses
     // built from void logits
     SVCHECK(check_finite_logits(e, st, "sv_generate (beam search)"));
-    if (!e->h_flags[0]) return fail(SV_EHIP, "beam search did not terminate within its budget");
+    if (!e->h_flags[HF_DONE]) return fail(SV_EHIP, "beam search did not terminate within its budget");
     std::vector<int64_t> toks, bidx;
     std::vector<float> scores;
     int L = 0;
@@ -231,12 +246,8 @@ static int generate_beam(sv_engine* e, const void* dev_embeds, int B, int S0, co
     HIPCHECK(hipMemcpy2DAsync(dev_out_tokens, (size_t)max_new * sizeof(int64_t), toks.data(), (size_t)max_new * sizeof(int64_t),
                               (size_t)L * sizeof(int64_t), B, hipMemcpyHostToDevice, st));
     HIPCHECK(hipStreamSynchronize(st));
-    auto t2 = std::chrono::steady_clock::now();
+    set_timing(e, t0, t1, (double)steps, gexec_used);
     *n_generated = L;
-    e->timing[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    e->timing[1] = std::chrono::duration<double, std::milli>(t2 - t1).count();
-    e->timing[2] = (double)steps;
-    e->timing_graph = gexec_used;
     return 0;
 }
 
@@ -244,9 +255,9 @@ static int generate_beam(sv_engine* e, const void* dev_embeds, int B, int S0, co
 // is then 0 instead of the out-of-range sentinel, so nothing indexes the embedding table out of bounds); the entry points
 // turn it into an error instead of returning made-up tokens.
 int sveng::check_finite_logits(sv_engine* e, hipStream_t st, const char* who) {
-    HIPCHECK(hipMemcpyAsync(&e->h_flags[4], e->d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(&e->h_flags[HF_BAD], e->d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
-    return report_bad_logits(e, st, who, e->h_flags[4]);
+    return report_bad_logits(e, st, who, e->h_flags[HF_BAD]);
 }
 int sveng::report_bad_logits(sv_engine* e, hipStream_t st, const char* who, int what) {
     if (!what) return 0;
@@ -270,11 +281,7 @@ int sveng::report_bad_logits(sv_engine* e, hipStream_t st, const char* who, int 
             // every block resident.  sv_generate runs the failed call again (below); the step-wise entry points report this one failure.
             e->fused_off = true;
             e->xpa_armed = false;
-            for (auto& kv : e->cb_graphs) {      // the continuous-batching step graphs were captured with the fused launches (sv_generate's carry the flag in their key)
-                if (kv.second.second) (void)hipGraphExecDestroy(kv.second.second);
-                if (kv.second.first) (void)hipGraphDestroy(kv.second.first);
-            }
-            e->cb_graphs.clear();
+            cb_drop_graphs(e);                   // the continuous-batching step graphs were captured with the fused launches (sv_generate's carry the flag in their key)
             fprintf(stderr, "[starvector_amd] a fused decode launch gave up waiting (code %d): this GPU is shared -- the engine continues WITHOUT the all-blocks-resident "
                             "launches (same tokens, ~8 %% more time per step); create it with exclusive_device = 0 to start that way\n", what);
         }
@@ -621,6 +628,123 @@ static int shared_prefill_fork(sv_engine* e, const void* dev_embeds, int B, int 
 }
 
 // ------------------------------------------------------------------------------------------------
+// The call frame of the two non-beam drivers (generate_attempt, lookup_attempt): what both do around their decode loops, once.  A driver
+// runs budget(), enter(), its own setup, start(), its loop over poll(), then report() and finish(); the rows it decodes, its step, the key of
+// its kept graph and when it polls are its own.
+// ------------------------------------------------------------------------------------------------
+struct GenFrame {
+    sv_engine* const e;
+    const GenCall& c;
+    const sv_sampling* const sp;
+    const char* const who;            // the name cb_guard and the bad-logits report carry: "sv_generate" (plain) or c.who (lookup)
+    const int B;                      // rows of the prompt pass's layout, of the outputs and of the streaming callback: c.B * c.n_samples
+    const SelMode sel;
+    int max_new = 0;
+    hipStream_t st = nullptr;
+    std::unique_lock<std::mutex> lock;
+    GenClock::time_point t0, t1;
+    // streaming: the columns below `streamed` have been handed to sp->on_tokens -- by this attempt or, for an optimistic call's second attempt, by
+    // its first (e->stream_skip comes in through enter() and is written back on every way out; generate_retry resets it)
+    int streamed = 0;
+    std::vector<int32_t> stream_buf;
+
+    GenFrame(sv_engine* e_, const GenCall& c_, const char* who_) : e(e_), c(c_), sp(c_.sp), who(who_), B(c_.B * c_.n_samples), sel(sel_mode(e_, *c_.sp)) {}
+    ~GenFrame() { if (lock.owns_lock()) e->stream_skip = streamed; }
+    const int32_t* block() const { return e->h_flags + HF_BLOCK; }      // the last poll()'s {step, done, n_emitted, bad}
+    bool done() const { return e->h_flags[HF_DONE] != 0; }
+
+    // the budget checks (no engine state is touched); stop_ids_now: the null check of stop_ids is made here, not by start() behind the prompt pass
+    int budget(bool stop_ids_now) {
+        max_new = sp->max_length - c.S0;     // HF: with inputs_embeds, max_length includes the prompt
+        if (max_new <= 0) return fail(SV_EINVAL, "max_length (%d) must exceed the prompt length (%d)", sp->max_length, c.S0);
+        if (c.S0 + max_new > e->cfg.max_seq_len) return fail(SV_EINVAL, "max_length %d exceeds engine max_seq_len %d", sp->max_length, e->cfg.max_seq_len);
+        if (sp->n_stop < 0 || sp->n_stop > 16) return fail(SV_EINVAL, "stop sequence length %d unsupported (0..16)", sp->n_stop);
+        if (stop_ids_now && sp->n_stop > 0 && !sp->stop_ids) return fail(SV_EINVAL, "n_stop > 0 but stop_ids is null");
+        if (sp->do_sample && !(sp->temperature > 0.f && sp->top_p > 0.f)) return fail(SV_EINVAL, "temperature and top_p must be > 0");
+        return 0;
+    }
+    // the engine's lock for the rest of the call; the engine stream ordered after everything already queued on the caller's
+    int enter() {
+        lock = std::unique_lock<std::mutex>(e->mu);
+        streamed = e->stream_skip;
+        HIPCHECK(hipSetDevice(e->cfg.device));
+        HIPCHECK(hipEventRecord(e->gen_event, (hipStream_t)c.stream));
+        st = e->gen_stream;
+        HIPCHECK(hipStreamWaitEvent(st, e->gen_event, 0));
+        return cb_guard(e, who);
+    }
+    // one copy of the device's {step, done, n_emitted, bad} block -- with lk_state's four words in the same synchronise when a lookup call asks
+    int poll(const int32_t* lk_state = nullptr) {
+        HIPCHECK(hipMemcpyAsync(&e->h_flags[HF_BLOCK], e->d_step, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (lk_state) HIPCHECK(hipMemcpyAsync(&e->h_flags[HF_LOOKUP], lk_state, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));
+        e->h_flags[HF_DONE] = block()[BLK_DONE];
+        return 0;
+    }
+    // The prompt pass, the generation state and the first token (from the prompt pass's logits, by the plain step's own launches), then ONE copy
+    // of the device block: a call that is over after its first token (budget 1, EOS) has everything it needs from this round trip and takes no
+    // other before the tokens go out.  n_amax: the key slots of a folded greedy selection to clear (0: none).
+    int start(int n_amax) {
+        const int32_t Bp = c.B, G = c.n_samples, S0 = c.S0;
+        const int32_t* lens = c.lens;
+        t0 = GenClock::now();
+        HIPCHECK(hipMemsetAsync(e->d_bad, 0, sizeof(int32_t), st));         // a flag left by an earlier, failed call is not this call's
+        if (G > 1) {                             // one prompt pass over the Bp prompts, then the fork launch: B rows from here on
+            SVCHECK(shared_prefill_fork(e, c.embeds, Bp, G, S0, lens, max_new, st));
+        } else if (lens) {                       // pages per sequence for lens[b] + max_new, one ragged prompt pass
+            SVCHECK(assign_pages_ragged(e, B, lens, max_new, st));
+            SVCHECK(prefill_forward_ragged(e, (const bf16_t*)c.embeds, B, lens, st));
+            if (!c.lookup) e->cached_B = B;      // (a lookup call aliases the table below: it says so itself, there)
+            HIPCHECK(hipGetLastError());
+        } else {
+            SVCHECK(prefill_locked(e, c.embeds, B, S0, S0 + max_new, st, false));
+        }
+        // generation state, one launch: positions = S0 - 1 (finish_step adds 1), unfinished = 1, {step, done, n_emitted} = 0, the folded selection's key slots = 0
+        gen_state_init(e->positions, S0 - 1, e->unfinished, B, e->d_step, e->amax, n_amax, st);
+        if (lens) ragged_positions(e, Bp, G, -1, st);        // every row continues at its own prompt's length
+        if (sel.pen) HIPCHECK(hipMemsetAsync(e->seen, 0, (size_t)((B + 31) / 32) * 32 * e->seen_words * sizeof(uint32_t), st));
+        if (sp->n_stop > 0) {
+            if (!sp->stop_ids) return fail(SV_EINVAL, "n_stop > 0 but stop_ids is null");
+            HIPCHECK(hipMemcpyAsync(e->d_stop, sp->stop_ids, sp->n_stop * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        }
+        sample_and_finish(e, B, *sp, max_new, st);
+        SVCHECK(poll());
+        t1 = GenClock::now();
+        return 0;
+    }
+    // streaming: hand the callback the columns [streamed, n_cols_final) of all B rows
+    int stream_upto(int n_cols_final) {
+        if (!sp->on_tokens || n_cols_final <= streamed) return 0;
+        const int n = n_cols_final - streamed;
+        stream_buf.resize((size_t)B * n);
+        HIPCHECK(hipMemcpy2DAsync(stream_buf.data(), (size_t)n * sizeof(int32_t), e->out_tok + streamed,
+                                  (size_t)e->out_ld * sizeof(int32_t), (size_t)n * sizeof(int32_t), B, hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));
+        sp->on_tokens(sp->user_data, stream_buf.data(), B, streamed, n);
+        streamed = n_cols_final;
+        return 0;
+    }
+    // the verdict on the block the last poll() read: a give-up or a non-finite row voids the call (before the last columns go out: a void call
+    // streams nothing more)
+    int report() {
+        e->h_flags[HF_NEMIT] = block()[BLK_NEMIT];
+        return report_bad_logits(e, st, who, block()[BLK_BAD]);
+    }
+    // the rest of the columns to the callback, the tokens to the caller, the timing
+    int finish(double steps, double per_launch) {
+        const int n_emit = e->h_flags[HF_NEMIT];
+        if (n_emit < 1 || n_emit > max_new) return fail(SV_EHIP, "generation bookkeeping failed (n_emitted=%d)", n_emit);
+        SVCHECK(stream_upto(n_emit));
+        tokens_to_i64(e->out_tok, e->out_ld, c.dev_out_tokens, B, n_emit, max_new, st);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipStreamSynchronize(st));
+        set_timing(e, t0, t1, steps, per_launch);
+        *c.n_generated = n_emit;
+        return 0;
+    }
+};
+
+// ------------------------------------------------------------------------------------------------
 // sv_generate_lookup: greedy generate that verifies K drafted tokens per sequence and step (lookup/lookup.hip; DESIGN.md "Prompt-lookup decoding")
 // ------------------------------------------------------------------------------------------------
 static void lookup_args(sv_engine* e, int n_seq, const sv_lookup& lk, const sv_sampling& sp, int max_new, LookupArgs& a) {
@@ -645,73 +769,35 @@ static void lookup_args(sv_engine* e, int n_seq, const sv_lookup& lk, const sv_s
 static int lookup_attempt(sv_engine* e, const GenCall& c) {
     const sv_sampling* sp = c.sp;
     const sv_lookup& lk = *c.lookup;
-    const int32_t B = c.B, S0 = c.S0, K1 = lk.num_draft_tokens + 1;
+    const int32_t B = c.B, K1 = lk.num_draft_tokens + 1;
     const int32_t* lens = c.lens;
     SVCHECK(check_ready(e));
     if ((long long)B * K1 > e->cfg.max_batch || B > 64)
         return fail(SV_ENOTSUP, "%s: B %d x (num_draft_tokens %d + 1) rows exceed engine max_batch %d", c.who, B, K1 - 1, e->cfg.max_batch);
     const int rows = B * K1;
     if (lens) SVCHECK(ragged_check_lens(e, lens, B, c.who, nullptr, nullptr));
-    const int max_new = sp->max_length - S0;
-    if (max_new <= 0) return fail(SV_EINVAL, "max_length (%d) must exceed the prompt length (%d)", sp->max_length, S0);
-    if (S0 + max_new > e->cfg.max_seq_len) return fail(SV_EINVAL, "max_length %d exceeds engine max_seq_len %d", sp->max_length, e->cfg.max_seq_len);
-    if (sp->n_stop < 0 || sp->n_stop > 16) return fail(SV_EINVAL, "stop sequence length %d unsupported (0..16)", sp->n_stop);
-    if (sp->n_stop > 0 && !sp->stop_ids) return fail(SV_EINVAL, "n_stop > 0 but stop_ids is null");
+    GenFrame f(e, c, c.who);
+    SVCHECK(f.budget(true));
     // sv_generate_lookup_sampled: the selection the call asks for (sv_generate_lookup refuses both in front of this driver)
-    const bool sample = sp->do_sample != 0;
-    const bool pen = sp->repetition_penalty > 0.f && sp->repetition_penalty != 1.0f;
-    if (sample && !(sp->temperature > 0.f && sp->top_p > 0.f)) return fail(SV_EINVAL, "temperature and top_p must be > 0");
+    const bool sample = sp->do_sample != 0, pen = f.sel.pen;
+    const int max_new = f.max_new;
     if (pen && (size_t)e->seen_words * sizeof(uint32_t) > 65536)
         return fail(SV_ENOTSUP, "%s: repetition_penalty with a vocabulary of %d ids is not built (a sequence's bitmap must fit 64 KB of LDS)", c.who, e->cfg.vocab);
-    std::lock_guard<std::mutex> lk_mu(e->mu);
-    HIPCHECK(hipSetDevice(e->cfg.device));
-    HIPCHECK(hipEventRecord(e->gen_event, (hipStream_t)c.stream));
-    hipStream_t st = e->gen_stream;
-    HIPCHECK(hipStreamWaitEvent(st, e->gen_event, 0));
-    SVCHECK(cb_guard(e, c.who));
+    SVCHECK(f.enter());
+    hipStream_t st = f.st;
     if (!e->lk_state) SVCHECK(dalloc(e, &e->lk_state, (size_t)4 * e->cfg.max_batch + 8));
     if (pen && !e->lk_seen) {
         SVCHECK(dalloc(e, &e->lk_seen, (size_t)64 * e->seen_words));
         SVCHECK(dalloc(e, &e->lk_seen_cols, (size_t)64));
     }
-
-    auto t0 = std::chrono::steady_clock::now();
-    HIPCHECK(hipMemsetAsync(e->d_bad, 0, sizeof(int32_t), st));
-    if (pen) HIPCHECK(hipMemsetAsync(e->seen, 0, (size_t)((B + 31) / 32) * 32 * e->seen_words * sizeof(uint32_t), st));      // as the plain call clears it
-    if (lens) {
-        SVCHECK(assign_pages_ragged(e, B, lens, max_new, st));
-        SVCHECK(prefill_forward_ragged(e, (const bf16_t*)c.embeds, B, lens, st));
-        HIPCHECK(hipGetLastError());
-    } else {
-        SVCHECK(prefill_locked(e, c.embeds, B, S0, S0 + max_new, st, false));
-    }
-    gen_state_init(e->positions, S0 - 1, e->unfinished, B, e->d_step, e->amax, 0, st);
-    if (lens) ragged_positions(e, B, 1, -1, st);
-    if (sp->n_stop > 0) HIPCHECK(hipMemcpyAsync(e->d_stop, sp->stop_ids, sp->n_stop * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    sample_and_finish(e, B, *sp, max_new, st);       // the first token, from the prompt pass's logits, by the plain call's own launches
-    HIPCHECK(hipMemcpyAsync(&e->h_flags[8], e->d_step, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPCHECK(hipStreamSynchronize(st));
-    e->h_flags[0] = e->h_flags[9];
-    e->h_flags[12] = e->h_flags[13] = e->h_flags[14] = 0; e->h_flags[15] = 1;
-    auto t1 = std::chrono::steady_clock::now();
+    SVCHECK(f.start(0));
+    int32_t* const lkh = e->h_flags + HF_LOOKUP;      // {steps, drafted, accepted, n_emit[0]} as the last poll read them
+    lkh[0] = lkh[1] = lkh[2] = 0; lkh[3] = 1;
 
     struct LookupOff { sv_engine* e; ~LookupOff() { e->lookup_on = false; } } lookup_off{e};
-    int streamed = e->stream_skip;
-    struct SkipSave { sv_engine* e; int* s; ~SkipSave() { e->stream_skip = *s; } } skip_save{e, &streamed};
-    std::vector<int32_t> stream_buf;
-    auto stream_upto = [&](int n_cols_final) -> int {        // (B == 1: the columns below n_emit[0] are final)
-        if (!sp->on_tokens || n_cols_final <= streamed) return 0;
-        const int n = n_cols_final - streamed;
-        stream_buf.resize((size_t)n);
-        HIPCHECK(hipMemcpyAsync(stream_buf.data(), e->out_tok + streamed, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIPCHECK(hipStreamSynchronize(st));
-        sp->on_tokens(sp->user_data, stream_buf.data(), 1, streamed, n);
-        streamed = n_cols_final;
-        return 0;
-    };
     int steps = 0;
     hipGraphExec_t gexec = nullptr;
-    if (!e->h_flags[0]) {
+    if (!f.done()) {
         // rows s * K1 + j of the block table = sequence s's row: the K1 rows of a sequence alias the same pages, tail page included (descending:
         // a row is read before it is overwritten)
         if (e->table_pending) { HIPCHECK(hipEventSynchronize(e->table_ev)); e->table_pending = false; }
@@ -734,8 +820,8 @@ static int lookup_attempt(sv_engine* e, const GenCall& c) {
         if (pen) launch_lookup_seen(ls, st);
         ls.begin = 0;
         e->lookup_on = true;
-        const bool hold = sp->min_new_tokens > 0 && sp->eos_token_id >= 0 && sp->eos_token_id < e->cfg.vocab;
-        const uint32_t* seen = pen ? e->seen : nullptr;
+        const int min_new = f.sel.min_new;
+        const uint32_t* seen = f.sel.seen;
         const float penalty = pen ? sp->repetition_penalty : 1.f;
         LookupSampleArgs sa;
         sa.logits = e->logits; sa.ld = e->Vpad; sa.V = e->cfg.vocab; sa.rows = rows; sa.K1 = K1; sa.n_emit = la.n_emit; sa.done = la.done;
@@ -743,7 +829,7 @@ static int lookup_attempt(sv_engine* e, const GenCall& c) {
         sa.seen = seen; sa.seen_words = e->seen_words; sa.penalty = penalty; sa.pval = e->am_val; sa.pidx = e->am_idx;
         const auto one_step = [&]() {
             decode_forward(e, rows, st);
-            if (hold) launch_lookup_hold_eos(e->logits, e->Vpad, sp->eos_token_id, la.n_emit, K1, sp->min_new_tokens, rows, st);
+            if (min_new > 0) launch_lookup_hold_eos(e->logits, e->Vpad, sp->eos_token_id, la.n_emit, K1, min_new, rows, st);
             if (sample) launch_lookup_sample(sa, st);
             else launch_argmax_partial(e->logits, e->Vpad, e->cfg.vocab, e->am_val, e->am_idx, rows, seen, e->seen_words, penalty, st);
             launch_lookup_step(la, st);
@@ -756,22 +842,15 @@ static int lookup_attempt(sv_engine* e, const GenCall& c) {
             // the selection of sv_generate_lookup_sampled is part of the captured step (the seed travels by value in the sampler's arguments)
             if (sample) kn += snprintf(key + kn, sizeof(key) - kn, "|s.T%a.k%d.p%a.sd%llu", (double)sp->temperature, sp->top_k, (double)sp->top_p, (unsigned long long)sp->seed);
             if (pen) snprintf(key + kn, sizeof(key) - kn, "|r%a", (double)sp->repetition_penalty);
-            if (e->lk_gexec && e->lk_graph_key == key) {
-                gexec = e->lk_gexec;
-            } else {
-                if (e->lk_gexec) { (void)hipGraphExecDestroy(e->lk_gexec); e->lk_gexec = nullptr; }
-                if (e->lk_graph) { (void)hipGraphDestroy(e->lk_graph); e->lk_graph = nullptr; }
-                e->lk_graph_key.clear();
-                SVCHECK(capture_steps(st, 1, one_step, &e->lk_graph, &e->lk_gexec));
-                if (e->lk_gexec) { e->lk_graph_key = key; gexec = e->lk_gexec; }
-            }
+            SVCHECK(e->lk_step.use(key, st, 1, one_step));       // a slot of its own: the plain call's kept graphs stay
+            gexec = e->lk_step.x;
         }
         // The end is data-dependent (a step emits 1 .. K + 1 tokens per sequence), so the device block is polled after EVERY chunk.  Chunk length
         // 8 unless sync_every says otherwise: the steps a chunk runs past the end of the call are wasted (they find *done set and change
         // nothing) -- at most 7 of ~1 ms, where the plain loop's 32 would waste up to 31 -- while a poll idles the GPU for ~0.1 ms, ~1 % of 8 steps.
         // Never more steps than the budget has tokens left: every step emits at least one token per live sequence.
         const int chunk = sp->sync_every > 0 ? sp->sync_every : 8;
-        while (!e->h_flags[0]) {
+        while (!f.done()) {
             int n = max_new - 1 - steps;
             if (n <= 0) break;
             if (n > chunk) n = chunk;
@@ -780,30 +859,15 @@ static int lookup_attempt(sv_engine* e, const GenCall& c) {
                 else one_step();
             }
             steps += n;
-            HIPCHECK(hipMemcpyAsync(&e->h_flags[8], e->d_step, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));      // {step, done, n_emitted, bad}
-            HIPCHECK(hipMemcpyAsync(&e->h_flags[12], e->lk_state, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));   // {steps, drafted, accepted, n_emit[0]}
-            HIPCHECK(hipStreamSynchronize(st));
-            e->h_flags[0] = e->h_flags[9];
-            if (e->h_flags[11]) break;
-            if (!e->h_flags[0] && B == 1) SVCHECK(stream_upto(e->h_flags[15]));
+            SVCHECK(f.poll(e->lk_state));
+            if (f.block()[BLK_BAD]) break;
+            if (!f.done() && B == 1) SVCHECK(f.stream_upto(lkh[3]));      // (B == 1: the columns below n_emit[0] are final)
         }
     }
-    e->h_flags[1] = e->h_flags[10];
-    SVCHECK(report_bad_logits(e, st, c.who, e->h_flags[11]));
-    if (!e->h_flags[0]) return fail(SV_EHIP, "%s: the call did not end within its budget (%d steps)", c.who, steps);
-    const int n_emit = e->h_flags[1];
-    if (n_emit < 1 || n_emit > max_new) return fail(SV_EHIP, "generation bookkeeping failed (n_emitted=%d)", n_emit);
-    if (B == 1) SVCHECK(stream_upto(n_emit));
-    tokens_to_i64(e->out_tok, e->out_ld, c.dev_out_tokens, B, n_emit, max_new, st);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(st));
-    auto t2 = std::chrono::steady_clock::now();
-    *c.n_generated = n_emit;
-    if (c.counts3) { c.counts3[0] = e->h_flags[12]; c.counts3[1] = e->h_flags[13]; c.counts3[2] = e->h_flags[14]; }
-    e->timing[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    e->timing[1] = std::chrono::duration<double, std::milli>(t2 - t1).count();
-    e->timing[2] = (double)e->h_flags[12];
-    e->timing_graph = gexec ? 1.0 : 0.0;
+    SVCHECK(f.report());
+    if (!f.done()) return fail(SV_EHIP, "%s: the call did not end within its budget (%d steps)", c.who, steps);
+    SVCHECK(f.finish((double)lkh[0], gexec ? 1.0 : 0.0));         // (timing[2]: the device's count of steps)
+    if (c.counts3) { c.counts3[0] = lkh[0]; c.counts3[1] = lkh[1]; c.counts3[2] = lkh[2]; }
     return 0;
 }
 // sampled = false: sv_generate_lookup (greedy, no penalty); true: sv_generate_lookup_sampled (the selection of the call's sv_sampling)
@@ -851,13 +915,9 @@ extern "C" int sv_generate_lookup_sampled(sv_engine* e, const void* dev_embeds_p
 // lens != nullptr: the ragged form -- S0 is the longest prompt (the budget counts from it), sequence b has lens[b] rows
 static int generate_attempt(sv_engine* e, const GenCall& c) {
     if (c.lookup) return lookup_attempt(e, c);
-    const void* dev_embeds = c.embeds;
-    const int32_t Bp = c.B, S0 = c.S0, G = c.n_samples;
+    const int32_t Bp = c.B, G = c.n_samples;
     const int32_t* lens = c.lens;
     const sv_sampling* sp = c.sp;
-    const sv_generate_outputs* outs = c.outs;
-    int64_t* dev_out_tokens = c.dev_out_tokens;
-    int32_t* n_generated = c.n_generated;
     SVCHECK(check_ready(e));
     const bool shared = G > 1;
     if (shared && (Bp < 1 || (long long)Bp * G > e->cfg.max_batch))
@@ -867,28 +927,20 @@ static int generate_attempt(sv_engine* e, const GenCall& c) {
         if (Bp > e->cfg.max_batch) return fail(SV_EINVAL, "sv_generate_ragged: bad B=%d (max_batch %d)", Bp, e->cfg.max_batch);
         SVCHECK(ragged_check_lens(e, lens, Bp, shared ? "sv_generate_shared" : "sv_generate_ragged", nullptr, nullptr));
     }
-    if (!sp || !dev_out_tokens || !n_generated) return fail(SV_EINVAL, "sv_generate: null argument");
-    const int max_new = sp->max_length - S0;     // HF: with inputs_embeds, max_length includes the prompt
-    if (max_new <= 0) return fail(SV_EINVAL, "max_length (%d) must exceed the prompt length (%d)", sp->max_length, S0);
-    if (S0 + max_new > e->cfg.max_seq_len) return fail(SV_EINVAL, "max_length %d exceeds engine max_seq_len %d", sp->max_length, e->cfg.max_seq_len);
-    if (sp->n_stop < 0 || sp->n_stop > 16) return fail(SV_EINVAL, "stop sequence length %d unsupported (0..16)", sp->n_stop);
-    if (sp->do_sample && !(sp->temperature > 0.f && sp->top_p > 0.f)) return fail(SV_EINVAL, "temperature and top_p must be > 0");
+    if (!sp || !c.dev_out_tokens || !c.n_generated) return fail(SV_EINVAL, "sv_generate: null argument");
+    GenFrame f(e, c, "sv_generate");
+    SVCHECK(f.budget(false));
+    const int max_new = f.max_new;
     if (sp->num_beams < 0) return fail(SV_EINVAL, "num_beams must be >= 1");
     if (sp->num_beams > 1 && shared)
         return fail(SV_ENOTSUP, "sv_generate_shared: n_samples %d with num_beams %d is not built (several returned sequences under beam search)", G, sp->num_beams);
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIPCHECK(hipSetDevice(e->cfg.device));
-    // order the engine stream after everything already queued on the caller's stream
-    HIPCHECK(hipEventRecord(e->gen_event, (hipStream_t)c.stream));
-    hipStream_t st = e->gen_stream;
-    HIPCHECK(hipStreamWaitEvent(st, e->gen_event, 0));
-
-    SVCHECK(cb_guard(e, "sv_generate"));
+    SVCHECK(f.enter());
+    hipStream_t st = f.st;
     struct ProcOff { sv_engine* e; ~ProcOff() { e->ban_ngram = 0; e->ban_nwords = 0; e->minp_log = -INFINITY; } } proc_off{e};
     SVCHECK(setup_processors(e, sp, c.lp, st));
     const bool ban = e->ban_ngram > 0 || e->ban_nwords > 0;
     struct CapOff { sv_engine* e; ~CapOff() { e->cap_on = false; } } cap_off{e};
-    SVCHECK(setup_capture(e, sp, outs, sp->num_beams > 1 ? B * sp->num_beams : B, max_new, st));
+    SVCHECK(setup_capture(e, sp, c.outs, sp->num_beams > 1 ? B * sp->num_beams : B, max_new, st));
     struct StatsOff { sv_engine* e; ~StatsOff() { e->ts_on = false; } } stats_off{e};
     SVCHECK(setup_token_stats(e, sp, c.stats, B, max_new, st));
     struct TopkOff { sv_engine* e; ~TopkOff() { e->tk_on = false; } } topk_off{e};
@@ -896,21 +948,9 @@ static int generate_attempt(sv_engine* e, const GenCall& c) {
     if (sp->num_beams > 1) {
         if (sp->on_tokens) return fail(SV_EINVAL, "streaming is not supported with beam search (hypotheses are only final at the end; HF refuses too)");
         if (sp->n_stop > 0 && !sp->stop_ids) return fail(SV_EINVAL, "n_stop > 0 but stop_ids is null");
-        return generate_beam(e, dev_embeds, B, S0, lens, sp, max_new, outs, dev_out_tokens, n_generated, st);
+        return generate_beam(e, c.embeds, B, c.S0, lens, sp, max_new, c.outs, c.dev_out_tokens, c.n_generated, st);
     }
 
-    auto t0 = std::chrono::steady_clock::now();
-    HIPCHECK(hipMemsetAsync(e->d_bad, 0, sizeof(int32_t), st));         // a flag left by an earlier, failed call is not this call's
-    if (shared) {                            // one prompt pass over the Bp prompts, then the fork launch: B rows from here on
-        SVCHECK(shared_prefill_fork(e, dev_embeds, Bp, G, S0, lens, max_new, st));
-    } else if (lens) {                       // pages per sequence for lens[b] + max_new, one ragged prompt pass
-        SVCHECK(assign_pages_ragged(e, B, lens, max_new, st));
-        SVCHECK(prefill_forward_ragged(e, (const bf16_t*)dev_embeds, B, lens, st));
-        e->cached_B = B;
-        HIPCHECK(hipGetLastError());
-    } else {
-        SVCHECK(prefill_locked(e, dev_embeds, B, S0, S0 + max_new, st, false));
-    }
     // Plain greedy decode (no repetition penalty, no min_length hold, one row tile, bf16 lm_head with the K split over the waves of a
     // block): the selection rides in the lm_head epilogue of every decode step -- one launch less per step, same tokens bit for bit.
     // SV_EXP_SEPARATE_ARGMAX = the separate argmax launch (A/B).
@@ -918,23 +958,13 @@ static int generate_attempt(sv_engine* e, const GenCall& c) {
     {
         int waves = 1, two = 0;
         skinny_plan(e->lm_head.Npad, e->lm_head.Kpad, 1, e->lm_head.fp8 ? 1 : 0, (B + 31) / 32, &waves, &two);
-        const bool pen = sp->repetition_penalty > 0.f && sp->repetition_penalty != 1.0f;
         // a capturing call (sv_generate_ex) takes the separate selection launch: the capture must read the logits row between the lm_head and
         // the selection, and the tokens are bit-identical either way (tests/test_gpu_e2e.py)
         // (a ban rewrites the logits row between the lm_head and the selection: the separate launch as well)
-        fused_sel = !sp->do_sample && !pen && sp->min_new_tokens <= 0 && B <= 32 && !e->lm_head.fp8 && waves > 1 && !two && !(e->exp & SV_EXP_SEPARATE_ARGMAX) &&
+        fused_sel = !sp->do_sample && !f.sel.pen && sp->min_new_tokens <= 0 && B <= 32 && !e->lm_head.fp8 && waves > 1 && !two && !(e->exp & SV_EXP_SEPARATE_ARGMAX) &&
                     !e->cap_on && !ban && !e->ts_on && !e->tk_on;      // (the statistics / top-k launches read the row and the slice winners between the lm_head and the bookkeeping)
     }
-    // generation state, one launch: positions = S0 - 1 (finish_step adds 1), unfinished = 1, {step, done, n_emitted} = 0, the folded selection's key slots = 0
-    gen_state_init(e->positions, S0 - 1, e->unfinished, B, e->d_step, e->amax, fused_sel ? 64 * SV_AMAX_STRIDE : 0, st);
-    if (lens) ragged_positions(e, Bp, G, -1, st);        // every row continues at its own prompt's length
-    if (sp->repetition_penalty > 0.f && sp->repetition_penalty != 1.0f)
-        HIPCHECK(hipMemsetAsync(e->seen, 0, (size_t)((B + 31) / 32) * 32 * e->seen_words * sizeof(uint32_t), st));
-    if (sp->n_stop > 0) {
-        if (!sp->stop_ids) return fail(SV_EINVAL, "n_stop > 0 but stop_ids is null");
-        HIPCHECK(hipMemcpyAsync(e->d_stop, sp->stop_ids, sp->n_stop * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    }
-    sample_and_finish(e, B, *sp, max_new, st);       // first token from the prefill logits
+    SVCHECK(f.start(fused_sel ? 64 * SV_AMAX_STRIDE : 0));
     struct FusedSel { sv_engine* e; ~FusedSel() { e->greedy_fused = false; e->fin_fold = false; e->fin_folded = false; } } fused_guard{e};
     if (fused_sel) {
         e->greedy_fused = true;                      // read by decode_forward (capture and eager launches below); cleared on every exit
@@ -942,39 +972,12 @@ static int generate_attempt(sv_engine* e, const GenCall& c) {
         e->fin_fold = !(ff && atoi(ff) == 0);
         e->fin_args = make_finish_args(e, B, *sp, max_new, true);
     }
-    // ONE copy of the device's {step, done, n_emitted, bad} block: a call that is over after its first token (budget 1, EOS) has everything
-    // it needs from this round trip and takes no other before the tokens go out
-    HIPCHECK(hipMemcpyAsync(&e->h_flags[8], e->d_step, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPCHECK(hipStreamSynchronize(st));
-    e->h_flags[0] = e->h_flags[9];
-    auto t1 = std::chrono::steady_clock::now();
 
     int steps = 0;
     const int chunk = sp->sync_every > 0 ? sp->sync_every : 32;
-    // streaming: columns [0, steps] are final after every poll (a finished batch may have fewer: n_emitted caps it)
-    int streamed = e->stream_skip;             // (an optimistic call's second attempt: the columns its first attempt delivered)
-    struct SkipSave { sv_engine* e; int* s; ~SkipSave() { e->stream_skip = *s; } } skip_save{e, &streamed};
-    std::vector<int32_t> stream_buf;
-    auto stream_upto = [&](int n_cols_final) -> int {
-        if (!sp->on_tokens || n_cols_final <= streamed) return 0;
-        const int n = n_cols_final - streamed;
-        stream_buf.resize((size_t)B * n);
-        HIPCHECK(hipMemcpy2DAsync(stream_buf.data(), (size_t)n * sizeof(int32_t), e->out_tok + streamed,
-                                  (size_t)e->out_ld * sizeof(int32_t), (size_t)n * sizeof(int32_t), B, hipMemcpyDeviceToHost, st));
-        HIPCHECK(hipStreamSynchronize(st));
-        sp->on_tokens(sp->user_data, stream_buf.data(), B, streamed, n);
-        streamed = n_cols_final;
-        return 0;
-    };
-    const bool use_graph = graph_enabled();
     hipGraphExec_t gexec = nullptr;
     const auto one_step = [&]() { decode_forward(e, B, st); sample_and_finish(e, B, *sp, max_new, st, fused_sel); };
-    auto drop_multi = [&]() {
-        if (e->gen_gexec_multi) { (void)hipGraphExecDestroy(e->gen_gexec_multi); e->gen_gexec_multi = nullptr; }
-        if (e->gen_graph_multi) { (void)hipGraphDestroy(e->gen_graph_multi); e->gen_graph_multi = nullptr; }
-        e->gen_multi_steps = 0;
-    };
-    if (!e->h_flags[0] && use_graph) {
+    if (!f.done() && graph_enabled()) {
         // One decode step is captured as a hipGraph (all kernel arguments are stable device pointers; the step index,
         // positions and stop state live in device memory) and replayed every step.  The instantiated graph is KEPT on the
         // engine and reused by the next call whose batch, budget and sampling parameters are the same (a serving request
@@ -992,27 +995,20 @@ static int generate_attempt(sv_engine* e, const GenCall& c) {
             snprintf(key + strlen(key), sizeof(key) - strlen(key), "|ts");
         if (e->tk_on)        // the top-k launch: k, the source and whether the rank is taken are launch arguments; the buffers are read through tk_desc
             snprintf(key + strlen(key), sizeof(key) - strlen(key), "|tk%d.%d.%d", e->tk_k, e->tk_source, e->tk_rank ? 1 : 0);
-        if (e->gen_gexec && e->gen_graph_key == key) {
-            gexec = e->gen_gexec;
-        } else {
-            if (e->gen_gexec) { (void)hipGraphExecDestroy(e->gen_gexec); e->gen_gexec = nullptr; }
-            if (e->gen_graph) { (void)hipGraphDestroy(e->gen_graph); e->gen_graph = nullptr; }
-            drop_multi();
-            e->gen_graph_key.clear();
-            SVCHECK(capture_steps(st, 1, one_step, &e->gen_graph, &e->gen_gexec));
-            if (e->gen_gexec) {              // (else: plain launches of the SAME kernels)
-                e->gen_graph_key = key;
-                gexec = e->gen_gexec;
-                size_t nn = 0;                     // sv_debug_step_plan: the step's launches, counted on the captured graph itself
-                e->step_nodes = 0;
-                if (hipGraphGetNodes(e->gen_graph, nullptr, &nn) == hipSuccess && nn > 0) {
-                    std::vector<hipGraphNode_t> nodes(nn);
-                    if (hipGraphGetNodes(e->gen_graph, nodes.data(), &nn) == hipSuccess)
-                        for (size_t i = 0; i < nn; ++i) {
-                            hipGraphNodeType ty;
-                            if (hipGraphNodeGetType(nodes[i], &ty) == hipSuccess && ty == hipGraphNodeTypeKernel) ++e->step_nodes;
-                        }
-                }
+        const bool kept = e->gen_step.holds(key);
+        if (!kept) e->gen_multi.drop();          // the multi-step graph is the same step: it goes with the one it copies
+        SVCHECK(e->gen_step.use(key, st, 1, one_step));
+        gexec = e->gen_step.x;                   // (nullptr: plain launches of the SAME kernels)
+        if (gexec && !kept) {
+            size_t nn = 0;                       // sv_debug_step_plan: the step's launches, counted on the freshly captured graph itself
+            e->step_nodes = 0;
+            if (hipGraphGetNodes(e->gen_step.g, nullptr, &nn) == hipSuccess && nn > 0) {
+                std::vector<hipGraphNode_t> nodes(nn);
+                if (hipGraphGetNodes(e->gen_step.g, nodes.data(), &nn) == hipSuccess)
+                    for (size_t i = 0; i < nn; ++i) {
+                        hipGraphNodeType ty;
+                        if (hipGraphNodeGetType(nodes[i], &ty) == hipSuccess && ty == hipGraphNodeTypeKernel) ++e->step_nodes;
+                    }
             }
         }
     }
@@ -1029,21 +1025,16 @@ static int generate_attempt(sv_engine* e, const GenCall& c) {
     if (gexec) {
         U = chunk < graph_steps_cap() ? chunk : graph_steps_cap();
         if (U >= 2 && max_new - 1 >= 4 * U) {
-            if (e->gen_gexec_multi && e->gen_multi_steps == U) {
-                gexec_multi = e->gen_gexec_multi;
-            } else {
-                drop_multi();
-                // (not required: on a failure the one-step graph carries the call, whatever SV_REQUIRE_GRAPH says)
-                (void)capture_steps(st, U, one_step, &e->gen_graph_multi, &e->gen_gexec_multi, false);
-                if (e->gen_gexec_multi) { e->gen_multi_steps = U; gexec_multi = e->gen_gexec_multi; }
-            }
+            // (not required: on a failure the one-step graph carries the call, whatever SV_REQUIRE_GRAPH says)
+            (void)e->gen_multi.use(std::to_string(U), st, U, one_step, false);
+            gexec_multi = e->gen_multi.x;
         }
     }
     // The host looks at the device's done flag after every chunk -- a round trip that leaves the GPU idle for ~0.1 ms -- only when something can
     // END the call before its budget (an EOS id inside the vocabulary, a stop sequence) or wants the columns as they become final (streaming).
     // A fixed-length call (the benchmark's EOS-disabled workload, fixed-length rollouts) has nothing to poll for.
     const bool poll = (sp->eos_token_id >= 0 && sp->eos_token_id < e->cfg.vocab) || sp->n_stop > 0 || sp->on_tokens != nullptr;
-    while (!e->h_flags[0]) {
+    while (!f.done()) {
         int n = max_new - 1 - steps;
         if (n <= 0) break;                       // budget exhausted: the device flag is already set
         if (n > chunk) n = chunk;
@@ -1055,39 +1046,19 @@ static int generate_attempt(sv_engine* e, const GenCall& c) {
                 HIPCHECK(hipGraphLaunch(gexec, st));
                 ++i;
             } else {
-                decode_forward(e, B, st);
-                sample_and_finish(e, B, *sp, max_new, st, fused_sel);
+                one_step();
                 ++i;
             }
         }
         steps += n;
         if (!poll) continue;                     // nothing can end this call before its budget: the next chunk follows without a host round trip
-        HIPCHECK(hipMemcpyAsync(&e->h_flags[8], e->d_step, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));      // {step, done, n_emitted, bad}
-        HIPCHECK(hipStreamSynchronize(st));
-        e->h_flags[0] = e->h_flags[9];
-        if (e->h_flags[11]) break;               // a void step (give-up, non-finite row): nothing of this chunk is handed on; the error is raised below
-        if (!e->h_flags[0]) SVCHECK(stream_upto(steps + 1));      // still running: every column so far is final
+        SVCHECK(f.poll());
+        if (f.block()[BLK_BAD]) break;           // a void step (give-up, non-finite row): nothing of this chunk is handed on; the error is raised below
+        if (!f.done()) SVCHECK(f.stream_upto(steps + 1));      // still running: columns [0, steps] are final (a finished batch may have fewer: n_emitted caps it)
     }
-    const double gexec_used = gexec_multi ? (double)U : gexec ? 1.0 : 0.0;       // steps per graph launch
-    if (steps > 0) {                             // (a call that ended at its first token has the block already)
-        HIPCHECK(hipMemcpyAsync(&e->h_flags[8], e->d_step, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIPCHECK(hipStreamSynchronize(st));
-    }
-    e->h_flags[1] = e->h_flags[10];
-    SVCHECK(report_bad_logits(e, st, "sv_generate", e->h_flags[11]));          // (before the last columns go out: a void call streams nothing more)
-    if (e->h_flags[1] >= 1 && e->h_flags[1] <= max_new) SVCHECK(stream_upto(e->h_flags[1]));
-    const int n_emit = e->h_flags[1];
-    if (n_emit < 1 || n_emit > max_new) return fail(SV_EHIP, "generation bookkeeping failed (n_emitted=%d)", n_emit);
-    tokens_to_i64(e->out_tok, e->out_ld, dev_out_tokens, B, n_emit, max_new, st);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(st));
-    auto t2 = std::chrono::steady_clock::now();
-    *n_generated = n_emit;
-    e->timing[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    e->timing[1] = std::chrono::duration<double, std::milli>(t2 - t1).count();
-    e->timing[2] = (double)steps;
-    e->timing_graph = gexec_used;
-    return 0;
+    if (steps > 0) SVCHECK(f.poll());            // (a call that ended at its first token has the block already)
+    SVCHECK(f.report());
+    return f.finish((double)steps, gexec_multi ? (double)U : gexec ? 1.0 : 0.0);       // steps per graph launch
 }
 
 // ------------------------------------------------------------------------------------------------

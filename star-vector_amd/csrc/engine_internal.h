@@ -75,6 +75,29 @@ struct Slot {
     int part_rows = 0;        // rows of this part (0 = the whole tensor)
 };
 
+// An owned captured decode step: the hipGraph, its instantiation and what it was captured for.  Move-only; the handles go with the slot.
+struct GraphSlot {
+    hipGraph_t g = nullptr;
+    hipGraphExec_t x = nullptr;      // nullptr: nothing kept (the caller runs plain launches of the same kernels)
+    std::string key;
+    GraphSlot() = default;
+    GraphSlot(GraphSlot&& o) noexcept : g(o.g), x(o.x), key(std::move(o.key)) { o.g = nullptr; o.x = nullptr; }
+    ~GraphSlot() { drop(); }
+    void drop() {
+        if (x) (void)hipGraphExecDestroy(x);
+        if (g) (void)hipGraphDestroy(g);
+        g = nullptr; x = nullptr; key.clear();
+    }
+    bool holds(const std::string& k) const { return x && key == k; }
+    // the kept graph if it was captured for `k`; otherwise what the slot holds is dropped and `copies` calls of one_step are captured in its place
+    // (capture_steps, below: a failure that is no error leaves the slot empty).  engine_core.hip
+    int use(const std::string& k, hipStream_t st, int copies, const std::function<void()>& one_step, bool required = true);
+};
+
+// sv_engine::h_flags, the pinned words the device's flags are copied into: the done flag, the emitted count, the continuous batch's live count, the
+// bad-logits code; HF_BLOCK + BLK_* = a snapshot of the device block {step, done, n_emitted, bad}, HF_LOOKUP + 0..3 = lk_state's {steps, drafted,
+// accepted, n_emit[0]}
+enum { HF_DONE = 0, HF_NEMIT = 1, HF_CB_LIVE = 3, HF_BAD = 4, HF_BLOCK = 8, HF_LOOKUP = 12, BLK_STEP = 0, BLK_DONE = 1, BLK_NEMIT = 2, BLK_BAD = 3 };
 struct sv_engine {
     sv_config cfg;
     std::mutex mu;
@@ -144,7 +167,7 @@ struct sv_engine {
     int32_t *cur_tok = nullptr, *next_tok = nullptr, *unfinished = nullptr, *positions = nullptr,
             *out_tok = nullptr, *d_step = nullptr, *d_done = nullptr, *d_nemit = nullptr, *d_stop = nullptr, *d_bad = nullptr;
     int out_ld = 0;
-    int32_t* h_flags = nullptr;   // pinned: [0]=done [1]=n_emitted [4]=bad; [8..11] = a snapshot of the device block {step, done, n_emitted, bad}
+    int32_t* h_flags = nullptr;   // pinned, indexed by HF_* (above)
     int32_t* h_table = nullptr;   // pinned host image of block_table (assign_pages); table_ev = its last upload
     hipEvent_t table_ev = nullptr;
     bool table_pending = false;
@@ -210,16 +233,12 @@ struct sv_engine {
     int32_t* cb_lk_forced = nullptr;
     int cb_lk_forced_n = 0, cb_lk_forced_ld = 0;
     int trash_page = 0;                       // what the block-table rows of free slots point at
-    std::unordered_map<int, std::pair<hipGraph_t, hipGraphExec_t>> cb_graphs;      // one captured step per row bucket
+    std::unordered_map<int, GraphSlot> cb_graphs;      // one captured step per row bucket (cleared by cb_drop_graphs alone)
     // sv_generate: the captured decode step is kept while the next call has the same shape and sampling parameters
-    std::string gen_graph_key;
-    hipGraph_t gen_graph = nullptr;
-    hipGraphExec_t gen_gexec = nullptr;
+    GraphSlot gen_step;
     // the same step SV_GRAPH_STEPS times in ONE graph (engine_generate.hip: a hipGraphLaunch-to-hipGraphLaunch boundary costs 8.6 us of idle GPU per step,
     // a kernel-to-kernel boundary inside a graph nothing measurable -- profiles/step_gaps_r06.log); built for calls long enough to pay for its instantiation
-    hipGraph_t gen_graph_multi = nullptr;
-    hipGraphExec_t gen_gexec_multi = nullptr;
-    int gen_multi_steps = 0;
+    GraphSlot gen_multi;             // key = the step count
     // sv_generate_ex outputs: the device descriptor of the caller's slabs (rewritten for every call, never baked into a graph), its host image,
     // per-row warper thresholds of the sampling capture; cap_on = the current call captures (set and cleared by sv_generate_ex)
     CaptureDesc* cap_desc = nullptr;
@@ -258,9 +277,7 @@ struct sv_engine {
     // the columns it covers [64]; e->seen then holds one bitmap per ROW of the step in flight (allocated by the first such call)
     uint32_t* lk_seen = nullptr;
     int32_t* lk_seen_cols = nullptr;
-    std::string lk_graph_key;
-    hipGraph_t lk_graph = nullptr;
-    hipGraphExec_t lk_gexec = nullptr;
+    GraphSlot lk_step;
     // optional per-kernel HIP-event profiling of the decode step (bench.py roofline leg)
     bool prof_on = false;
     std::vector<hipEvent_t> prof_ev;
@@ -291,7 +308,7 @@ inline int dalloc(sv_engine* e, T** p, size_t count, bool zero = true) {
 }
 void pick_decode_plan(const Linear& l, int MT, int num_cus, bool fp8, bool whole_k, int* splitk, int* col_tiles);
 int check_exp_mask(int mask, const char* who);      // SV_EINVAL (naming the bits) unless mask is a subset of SV_EXP_KNOWN
-// hipGraph capture of decode steps, shared by sv_generate (greedy and beam) and sv_cb_step.  capture_steps: relaxed capture of `copies` calls of
+// hipGraph capture of decode steps, shared by sv_generate (greedy, lookup and beam) and sv_cb_step through GraphSlot::use.  capture_steps: relaxed capture of `copies` calls of
 // one_step on `st` -> *g, instantiated -> *ge.  On failure the sticky HIP error is cleared, both handles are destroyed and nulled, and the
 // result is SV_EHIP if `required` and SV_REQUIRE_GRAPH is set, else 0 with *ge == nullptr: the caller runs plain launches of the same kernels.
 bool graph_enabled();       // SV_NO_GRAPH unset (read per call: the tests switch it inside one process)

@@ -24,11 +24,7 @@ extern "C" int sv_debug_set_exp(sv_engine* e, int32_t mask) {
     std::lock_guard<std::mutex> lk(e->mu);
     e->exp = mask;
     e->xpa_armed = false;                    // another mask may have run plain stores through xp_a: the next step re-arms it
-    for (auto& kv : e->cb_graphs) {          // the continuous-batching step graphs were captured with the old mask
-        if (kv.second.second) (void)hipGraphExecDestroy(kv.second.second);
-        if (kv.second.first) (void)hipGraphDestroy(kv.second.first);
-    }
-    e->cb_graphs.clear();
+    cb_drop_graphs(e);                       // the continuous-batching step graphs were captured with the old mask
     return 0;
 }
 
@@ -37,7 +33,7 @@ extern "C" int sv_debug_exp_known(void) { return SV_EXP_KNOWN; }
 extern "C" int sv_debug_step_plan(sv_engine* e, int32_t* out4) {
     if (!e || !out4) return fail(SV_EINVAL, "sv_debug_step_plan: null argument");
     std::lock_guard<std::mutex> lk(e->mu);
-    out4[0] = e->gen_gexec ? e->step_nodes : 0;
+    out4[0] = e->gen_step.x ? e->step_nodes : 0;
     out4[1] = e->step_rc ? 1 : 0; out4[2] = e->step_sel ? 1 : 0; out4[3] = e->step_mlp ? 1 : 0;
     return 0;
 }

@@ -229,6 +229,45 @@ def test_generate_is_deterministic_graph_equals_eager_and_batch_invariant():
     eng.close()
 
 
+def test_kept_graphs_are_kept_and_replaced_across_plain_sampled_and_lookup_calls():
+    """The engine's graph slots through their keep and replace paths in ONE engine: a greedy call that builds the one-step and a 2-step graph
+    (39 steps >= 4 x sync_every 2), the same call again (both replayed), two sampled calls (another key, then another seed: both plain graphs
+    replaced), a lookup call (a slot of its own), the first call again (captured afresh).  Every call returns the tokens of the same call
+    launched eagerly (SV_NO_GRAPH=1) on the same engine; the last call returns the first one's bit for bit."""
+    cfg = O.OracleConfig.tiny()
+    w = O.make_weights(cfg, seed=21)
+    eng = build_engine(cfg, w, 32, 128)
+    img = bf(O.synthetic_images(3, cfg.image_size, seed=22))
+    prompt = torch.tensor([[7, 11]] * 3, device=dev())
+    emb = torch.cat([eng.adapter(eng.encode_image(img)), eng.embed_tokens(prompt)], 1)
+    kw = dict(max_length=emb.shape[1] + 40, eos_token_id=-1, pad_token_id=cfg.pad_token_id)
+    skw = dict(do_sample=True, temperature=1.0, top_p=0.9, top_k=20)
+    calls = {"greedy": lambda: eng.generate(emb, sync_every=2, **kw),
+             "seed3": lambda: eng.generate(emb, seed=3, **skw, **kw),
+             "seed4": lambda: eng.generate(emb, seed=4, **skw, **kw),
+             "lookup": lambda: eng.generate_lookup(emb, num_draft_tokens=3, **kw)}
+    order = ["greedy", "greedy", "seed3", "seed4", "lookup", "greedy"]
+    os.environ.pop("SV_NO_GRAPH", None)
+    got, steps, nodes = [], [], []
+    for name in order:
+        got.append(calls[name]().cpu())
+        assert eng.last_timing()["graph"], f"{name}: the decode step did not run as a hipGraph replay"
+        steps.append(eng.last_timing()["graph_steps"])
+        nodes.append(eng.step_plan()["graph_kernel_nodes"])
+    assert steps == [2, 2, 1, 1, 1, 2]          # (a sampled call at sync_every 32 and a lookup call launch one step per graph)
+    assert nodes[0] > 0 and nodes[1] == nodes[0] and nodes[5] == nodes[0]
+    os.environ["SV_NO_GRAPH"] = "1"
+    try:
+        eager = {name: call().cpu() for name, call in calls.items()}
+        assert not eng.last_timing()["graph"]
+    finally:
+        os.environ.pop("SV_NO_GRAPH", None)
+    for name, toks in zip(order, got):
+        assert toks.shape == (3, 40) and torch.equal(toks, eager[name]), name
+    assert torch.equal(got[5], got[0]) and not torch.equal(eager["seed3"], eager["seed4"])
+    eng.close()
+
+
 def test_prompts_of_259_rows_are_batch_independent_with_the_per_sequence_remainder():
     """StarVector-1B's dimensions at reduced depth, 224 x 224 images -> 257 vision tokens + 2 prompt ids = 259 prompt rows: the GEMM remainder of every
     sequence (3 of 259 rows, 1 of 257 tokens) runs through the split-K remainder kernel where gemm_seq_form holds (round 6, gemm.hip).  Which kernel computes
