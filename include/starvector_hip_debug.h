@@ -112,7 +112,9 @@ int  sv_debug_skinny_form(void);
  *                             graph counts once, at capture).  Lets a test prove which kernel ran. */
 int  sv_debug_tailsplit_launches(int64_t* count);
 /*   sv_debug_set_gemm_form    process-wide: every big-M GEMM launch takes ONE form -- 0 = 128x128 tiles, 1 = 256x256 tiles (rows not peeled),
-     2 = 256x256 tiles + the row remainder over a multiple of 256 through the one-wave-per-tile tail kernel; -1 = the tuned choice (default).
+     2 = 256x256 tiles + the row remainder over a multiple of 256 through the one-wave-per-tile tail kernel, 3 = every row through that tail
+     kernel (with a sequence structure: the full 256-row tiles' rows of every sequence; the rows a sequence leaves over take the split-K
+     remainder kernel as in every form); -1 = the tuned choice (default).
      The forms give the same bits; the tests compare them through this switch. */
 int  sv_debug_set_gemm_form(int32_t form);
 /*   sv_debug_set_linear_seq_rows  process-wide: the sequence structure sv_op_linear / sv_bench_linear hand to the big-M dispatch from now on --

@@ -12,9 +12,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libstarvector_hip.so")
-SOURCES = ["gemm.hip", "decode_cols.hip", "rowops.hip", "attention.hip", "sampling.hip", "processors.hip", "score.hip", "beam.hip", "fork.hip", "preprocess.hip", os.path.join("lookup", "lookup.hip"),
+SOURCES = ["gemm_pack.hip", "gemm.hip", "mlp_fused.hip", "decode_cols.hip", "rowops.hip", "attention.hip", "sampling.hip", "processors.hip", "score.hip", "beam.hip", "fork.hip", "preprocess.hip", os.path.join("lookup", "lookup.hip"),
            os.path.join("lookup_sampled", "lookup_sampled.hip"), os.path.join("cb_lookup", "cb_lookup.hip"), "engine_core.hip", "engine_forward.hip", "engine_generate.hip", "engine_cb.hip", "engine_ops.hip"]
-HEADERS = ["common.h", "kernels.h", "beam.h", "warp.h", "sample_row.h", "topk.h", "cb_row.h", os.path.join("lookup", "lk_draft.h"), "engine_internal.h", os.path.join("..", "..", "include", "starvector_hip.h"),
+HEADERS = ["common.h", "kernels.h", "skinny_dev.h", "beam.h", "warp.h", "sample_row.h", "topk.h", "cb_row.h", os.path.join("lookup", "lk_draft.h"), "engine_internal.h", os.path.join("..", "..", "include", "starvector_hip.h"),
            os.path.join("..", "..", "include", "starvector_hip_debug.h")]
 # -amdgpu-kernarg-preload-count: leading scalar / pointer kernel parameters arrive in SGPRs with the dispatch (gfx950) instead
 # of through a scalar load at the top of every kernel (the decode step is 172 dependent launches)
@@ -28,6 +28,17 @@ def _hipcc() -> str:
         if c and os.path.exists(c):
             return c
     raise RuntimeError("hipcc not found (ROCm toolchain required to build libstarvector_hip.so)")
+
+
+def _max_jobs() -> int:
+    """compile pool size: MAX_JOBS when set, else the CPUs up to 16 (a shared box shows many more than a job may use)"""
+    try:
+        n = int(os.environ.get("MAX_JOBS", ""))
+        if n > 0:
+            return n
+    except ValueError:
+        pass
+    return min(os.cpu_count() or 4, 16)
 
 
 def _newer(target: str, deps) -> bool:
@@ -69,7 +80,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     if jobs:
         if verbose:
             print(f"[starvector_amd.build] compiling {len(jobs)} HIP source(s) for gfx950", file=sys.stderr)
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as ex:
+        with ThreadPoolExecutor(max_workers=min(len(jobs), _max_jobs())) as ex:
             list(ex.map(compile_one, jobs))
     with open(stamp, "w") as f:
         f.write(flags_now)

@@ -676,7 +676,7 @@ void sveng::decode_forward(sv_engine* e, int B, hipStream_t st) {
             skinny(xo, L.c_attn, SK_OUT_PARTIAL, wsA);
             ru.xp_out = xp_ln;
         }
-        // c_fc + down projection in ONE launch (gemm.hip mlp_fused_kernel): on when the engine owns its GPU (sv_config.exclusive_device);
+        // c_fc + down projection in ONE launch (mlp_fused.hip mlp_fused_kernel): on when the engine owns its GPU (sv_config.exclusive_device);
         // SV_EXP_MLP_FUSED_FORCE forces it on, SV_EXP_MLP_FUSED_OFF off (in-process A/B, tools/ab_exp.py).  It recognises unwritten activations by a pattern
         // that an EARLIER launch of the layer leaves in the buffer: the attention launch (16 bytes per thread: free in a latency-bound
         // kernel), or -- grid too small, or the profiling leg without attention -- the projection kernel (+0.5 us there)

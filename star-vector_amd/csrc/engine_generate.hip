@@ -378,7 +378,7 @@ static int generate_retry(sv_engine* e, const GenCall& c) {
 }
 
 // sv_config.exclusive_device = 2: OPTIMISTIC ownership.  The fused launches run as if the engine owned its GPU; if one gives up (another process
-// holds CUs: the bounded wait of rowops.hip / gemm.hip, never a hang, never tokens) the engine switches them off for good (report_bad_logits) and
+// holds CUs: the bounded wait of rowops.hip / mlp_fused.hip, never a hang, never tokens) the engine switches them off for good (report_bad_logits) and
 // THIS call is run again from its prompt pass.  The kernels with and without the fused launches are bit-identical (tests/test_gpu_e2e.py), the
 // sampler's random stream is a function of (seed, step, row): the second attempt re-derives exactly the columns the first one had already handed
 // to a streaming callback, and skips them.

@@ -148,7 +148,7 @@ struct sv_engine {
     int step_nodes = 0; bool step_rc = false, step_sel = false, step_mlp = false;      // sv_debug_step_plan: the last captured / launched decode step
     bool xpa_armed = false;         // xp_a carries the "not written yet" pattern, put there by a write-through fill of the lm_head launch in front (layer 0 of the next fused step polls it)
     bool rc_fused_ok = false;       // row update + c_attn as one launch (rowops.hip rowln_cattn_kernel) fits this engine: shapes + all blocks resident
-    bool mlp_fused_ok = false;      // the MLP half as one launch (gemm.hip mlp_fused_kernel) fits this engine: shapes + one block per CU
+    bool mlp_fused_ok = false;      // the MLP half as one launch (mlp_fused.hip mlp_fused_kernel) fits this engine: shapes + one block per CU
     long long* attn_trace = nullptr;// SV_ATTN_TRACE=1: wall-clock stamps of the decode attention of the middle layer, [rows * kv heads * splits][16]
     long long* mlp_trace = nullptr; // SV_MLP_TRACE=1: wall-clock stamps of the LAST fused MLP launch, [F / 32][8] (sv_debug_mlp_trace)
     bool only_skinny = false;       // profiling: enqueue only the weight-streaming GEMMs of a step

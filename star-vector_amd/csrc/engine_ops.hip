@@ -488,7 +488,7 @@ extern "C" int sv_debug_occupy_cus(sv_engine* e, int32_t blocks, int32_t lds_byt
 }
 
 extern "C" int sv_debug_set_gemm_form(int32_t form) {
-    if (form < -1 || form > 2) return fail(SV_EINVAL, "sv_debug_set_gemm_form: -1 (tuned), 0 .. 2");
+    if (form < -1 || form > 3) return fail(SV_EINVAL, "sv_debug_set_gemm_form: -1 (tuned), 0 .. 3");
     set_gemm_form(form);
     return 0;
 }

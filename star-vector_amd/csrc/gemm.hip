@@ -23,143 +23,9 @@
 #include <mutex>
 #include <tuple>
 #include <type_traits>
-#include "kernels.h"
+#include "skinny_dev.h"
 
 namespace sv {
-
-// ------------------------------------------------------------------------------------------------
-// weight packing
-// ------------------------------------------------------------------------------------------------
-template <typename SrcT>
-__global__ void pack_weight_kernel(const SrcT* __restrict__ W, bf16_t* __restrict__ Wp, int N, int K,
-                                   int Npad, int Kpad) {
-    const int KS = Kpad >> 4;
-    const size_t total = (size_t)(Npad >> 5) * KS * 64;
-    for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < total;
-         c += (size_t)gridDim.x * blockDim.x) {
-        int lane = (int)(c & 63);
-        size_t t = c >> 6;
-        int ks = (int)(t % KS);
-        int nt = (int)(t / KS);
-        int n = nt * 32 + (lane & 31);
-        int k0 = ks * 16 + (lane >> 5) * 8;
-        float f[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            int k = k0 + e;
-            float v = 0.f;
-            if (n < N && k < K) {
-                if constexpr (sizeof(SrcT) == 4) v = (float)W[(size_t)n * K + k];
-                else v = bf2f((bf16_t)W[(size_t)n * K + k]);
-            }
-            f[e] = v;
-        }
-        *reinterpret_cast<uint4*>(Wp + c * 8) = pack8(f);
-    }
-}
-
-void launch_pack_weight(const void* src, int src_is_f32, bf16_t* dst, int N, int K, int Npad, int Kpad,
-                        hipStream_t st) {
-    size_t total = (size_t)(Npad / 32) * (Kpad / 16) * 64;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 65535) blocks = 65535;
-    if (src_is_f32)
-        pack_weight_kernel<float><<<blocks, 256, 0, st>>>((const float*)src, dst, N, K, Npad, Kpad);
-    else
-        pack_weight_kernel<bf16_t><<<blocks, 256, 0, st>>>((const bf16_t*)src, dst, N, K, Npad, Kpad);
-}
-
-template <typename SrcT>
-__global__ void convert_bf16_kernel(const SrcT* __restrict__ s, bf16_t* __restrict__ d, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        if constexpr (sizeof(SrcT) == 4) d[i] = f2bf((float)s[i]);
-        else d[i] = (bf16_t)s[i];
-    }
-}
-void launch_convert_to_bf16(const void* src, int src_is_f32, bf16_t* dst, size_t n, hipStream_t st) {
-    int blocks = (int)((n + 255) / 256);
-    if (blocks > 8192) blocks = 8192;
-    if (blocks < 1) blocks = 1;
-    if (src_is_f32) convert_bf16_kernel<float><<<blocks, 256, 0, st>>>((const float*)src, dst, n);
-    else convert_bf16_kernel<bf16_t><<<blocks, 256, 0, st>>>((const bf16_t*)src, dst, n);
-}
-
-// ------------------------------------------------------------------------------------------------
-// fp8 (OCP e4m3) weight-only quantisation at load time (BASELINE config 5: fp8 weights).  One scale per output row.
-// ------------------------------------------------------------------------------------------------
-template <typename SrcT>
-__device__ __forceinline__ float ld_as_f32(const SrcT* p) {
-    if constexpr (sizeof(SrcT) == 4) return (float)*p;
-    else return bf2f((bf16_t)*p);
-}
-template <typename SrcT>
-__global__ __launch_bounds__(256) void fp8_row_scale_kernel(const SrcT* __restrict__ src, float* __restrict__ scale, int N,
-                                                            int K, int Npad) {
-    __shared__ float red[4];
-    const int n = blockIdx.x, tid = threadIdx.x;
-    float m = 0.f;
-    if (n < N)
-        for (int k = tid; k < K; k += 256) m = fmaxf(m, fabsf(ld_as_f32(src + (size_t)n * K + k)));
-    m = wave_max(m);
-    if ((tid & 63) == 0) red[tid >> 6] = m;
-    __syncthreads();
-    if (tid == 0) {
-        m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-        scale[n] = m > 0.f ? m / 448.0f : 1.0f;             // e4m3 max normal = 448
-    }
-}
-// one thread = one lane's 16 fp8 bytes (two k-steps) of one (n-tile, k-step pair)
-template <typename SrcT>
-__global__ void pack_weight_fp8_kernel(const SrcT* __restrict__ src, const float* __restrict__ scale, bf16_t* __restrict__ dst_bf16,
-                                       uint8_t* __restrict__ dst_q, int N, int K, int Npad, int Kpad) {
-    const int KS = Kpad >> 4, KS2 = KS >> 1;
-    const size_t total = (size_t)(Npad >> 5) * KS2 * 64;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int lane = (int)(i & 63);
-        const size_t t = i >> 6;
-        const int ks2 = (int)(t % KS2), nt = (int)(t / KS2);
-        const int n = nt * 32 + (lane & 31);
-        const float sc = n < N ? scale[n] : 1.0f;
-        uint32_t words[4];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int ks = 2 * ks2 + h;
-            float f[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int k = 16 * ks + 8 * (lane >> 5) + e;
-                f[e] = (n < N && k < K) ? ld_as_f32(src + (size_t)n * K + k) / sc : 0.f;
-            }
-            int w0 = 0, w1 = 0;
-            w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], w0, false);
-            w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w0, true);
-            w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], w1, false);
-            w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], w1, true);
-            words[2 * h] = (uint32_t)w0;
-            words[2 * h + 1] = (uint32_t)w1;
-            // the same values as bf16 (exact: 3 mantissa bits) for the big-M kernels
-            float q[8];
-            const f32x2 a0 = __builtin_amdgcn_cvt_pk_f32_fp8(w0, false), a1 = __builtin_amdgcn_cvt_pk_f32_fp8(w0, true);
-            const f32x2 a2 = __builtin_amdgcn_cvt_pk_f32_fp8(w1, false), a3 = __builtin_amdgcn_cvt_pk_f32_fp8(w1, true);
-            q[0] = a0[0]; q[1] = a0[1]; q[2] = a1[0]; q[3] = a1[1]; q[4] = a2[0]; q[5] = a2[1]; q[6] = a3[0]; q[7] = a3[1];
-            *reinterpret_cast<uint4*>(dst_bf16 + (((size_t)nt * KS + ks) * 64 + lane) * 8) = pack8(q);
-        }
-        *reinterpret_cast<uint4*>(dst_q + (((size_t)nt * KS2 + ks2) * 64 + lane) * 16) = make_uint4(words[0], words[1], words[2], words[3]);
-    }
-}
-void launch_pack_weight_fp8(const void* src, int src_is_f32, bf16_t* dst_bf16, uint8_t* dst_q, float* scale, int N, int K,
-                            int Npad, int Kpad, hipStream_t st) {
-    const size_t total = (size_t)(Npad / 32) * (Kpad / 32) * 64;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 16384) blocks = 16384;
-    if (src_is_f32) {
-        fp8_row_scale_kernel<float><<<Npad, 256, 0, st>>>((const float*)src, scale, N, K, Npad);
-        pack_weight_fp8_kernel<float><<<blocks, 256, 0, st>>>((const float*)src, scale, dst_bf16, dst_q, N, K, Npad, Kpad);
-    } else {
-        fp8_row_scale_kernel<bf16_t><<<Npad, 256, 0, st>>>((const bf16_t*)src, scale, N, K, Npad);
-        pack_weight_fp8_kernel<bf16_t><<<blocks, 256, 0, st>>>((const bf16_t*)src, scale, dst_bf16, dst_q, N, K, Npad, Kpad);
-    }
-}
 
 // ------------------------------------------------------------------------------------------------
 // big-M GEMM
@@ -168,14 +34,6 @@ void launch_pack_weight_fp8(const void* src, int src_is_f32, bf16_t* dst_bf16, u
 #define GB_N 128
 #define GB_K 64
 #define GB_BUF 32768   // per stage: 16 KiB activations + 16 KiB weights
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __forceinline__ void lds_dma16(const void* g, char* lds_wave_base) {
-    // 16 B per lane; LDS destination = wave-uniform base + lane*16 (hardware), source is per lane
-    __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)lds_wave_base, 16, 0, 0);
-}
 
 // ------------------------------------------------------------------------------------------------
 // Epilogue through LDS (bf16 outputs).  The MFMA accumulator layout is "one output ROW per lane": stored straight from
@@ -741,13 +599,13 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs p, int tiles_m, i
 
 // row tiles of the 128^2 kernel's grid (sequence structure: two per 256 rows of every sequence)
 static int tiles128_m(const GemmArgs& a) { return a.seq_rows ? (a.M / a.seq_rows) * (a.seq_rows / 256) * 2 : (a.M + GB_M - 1) / GB_M; }
+static void launch_gemm128(const GemmArgs& a, hipStream_t st) {
+    dim3 grid((a.N + GB_N - 1) / GB_N, tiles128_m(a));
+    if (a.out_f32) gemm_bf16_kernel<float><<<grid, 256, 2 * GB_BUF, st>>>(a);
+    else gemm_bf16_kernel<bf16_t><<<grid, 256, 2 * GB_BUF, st>>>(a);
+}
 static void launch_gemm256(const GemmArgs& a, hipStream_t st) {
-    if (a.K < 128) {                     // the loop's prologue stages into K-tile 1: a single K-tile goes through the 128^2 kernel (same bits)
-        dim3 grid((a.N + GB_N - 1) / GB_N, tiles128_m(a));
-        if (a.out_f32) gemm_bf16_kernel<float><<<grid, 256, 2 * GB_BUF, st>>>(a);
-        else gemm_bf16_kernel<bf16_t><<<grid, 256, 2 * GB_BUF, st>>>(a);
-        return;
-    }
+    if (a.K < 128) { launch_gemm128(a, st); return; }       // the loop's prologue stages into K-tile 1: a single K-tile goes through the 128^2 kernel (same bits)
     const int tiles_m = a.seq_rows ? (a.M / a.seq_rows) * (a.seq_rows / G2_T) : (a.M + G2_T - 1) / G2_T, tiles_n = (a.N + G2_T - 1) / G2_T;
     if (a.out_f32) gemm256_kernel<float><<<tiles_m * tiles_n, 512, 2 * G2_BUF, st>>>(a, tiles_m, tiles_n);
     else gemm256_kernel<bf16_t><<<tiles_m * tiles_n, 512, 2 * G2_BUF, st>>>(a, tiles_m, tiles_n);
@@ -990,15 +848,6 @@ static double tail_us(int tail, int N, int K) {
     return 7.0 + 4.2e-5 * (double)((N + 31) / 32) * (double)((tail + 31) / 32) * (double)K;
 }
 
-static void launch_gemm_tiles(const GemmArgs& a, hipStream_t st, bool force128 = false) {
-    dim3 grid((a.N + GB_N - 1) / GB_N, tiles128_m(a));
-    bool use256 = false;
-    (void)tiles_us(a.seq_rows ? (int)grid.y * GB_M : a.M, a.N, a.K, a.act, &use256);
-    if (!force128 && use256) { launch_gemm256(a, st); return; }
-    if (a.out_f32) gemm_bf16_kernel<float><<<grid, 256, 2 * GB_BUF, st>>>(a);
-    else gemm_bf16_kernel<bf16_t><<<grid, 256, 2 * GB_BUF, st>>>(a);
-}
-
 // The dispatch decision for an M x N x K big-M GEMM as plain host arithmetic (exported for the CPU tests through
 // sv_debug_gemm_plan): peel the row remainder or not, how the remainder runs, and which tile kernel the main part takes.
 GemmPlan gemm_plan(int M, int N, int K, int act, int tail_on) {
@@ -1020,41 +869,48 @@ GemmPlan gemm_plan(int M, int N, int K, int act, int tail_on) {
     return pl;
 }
 
-// One launch of the chosen configuration: tile kernel (kernel = 0: 128^2, 1: 256^2) and whether the row remainder over a
-// multiple of 256 is peeled into the tail kernel.  Every configuration computes the same bits (same MFMA, operand roles
-// and ascending-k order: tests/test_gpu_ops.py::test_linear_big_m_kernels_agree_bitwise), so the choice is speed only.
-static void launch_gemm_config(const GemmArgs& a, hipStream_t st, int kernel256, bool peel, bool tail_by_tiles) {
-    auto tiles = [&](const GemmArgs& g, bool force128) {
-        dim3 grid((g.N + GB_N - 1) / GB_N, tiles128_m(g));
-        if (kernel256 && !force128) { launch_gemm256(g, st); return; }
-        if (g.out_f32) gemm_bf16_kernel<float><<<grid, 256, 2 * GB_BUF, st>>>(g);
-        else gemm_bf16_kernel<bf16_t><<<grid, 256, 2 * GB_BUF, st>>>(g);
-    };
+// the GemmArgs of rows [r0, r0 + n) of `a`
+static GemmArgs gemm_rows(const GemmArgs& a, size_t r0, int n) {
+    GemmArgs g = a;
+    g.A = a.A + r0 * a.lda;
+    g.R = a.R ? a.R + r0 * a.ldr : nullptr;
+    g.C = a.out_f32 ? (void*)((float*)a.C + r0 * a.ldc) : (void*)((bf16_t*)a.C + r0 * a.ldc);
+    g.M = n;
+    return g;
+}
+// the rows every sequence leaves over its 256-row tiles, through the per-sequence split-K remainder kernel
+static void launch_seq_remainder(const GemmArgs& a, hipStream_t st) {
+    GemmArgs t = a;
+    t.seq_tail = seq_peel_rows(a.seq_rows);
+    t.M = (a.M / a.seq_rows) * t.seq_tail;
+    if (a.tail_mark) a.tail_mark(a.tail_ctx, st);
+    launch_gemm_tailk(t, st);
+}
+
+// One launch of the chosen configuration: tile kernel (kernel256 = false: 128^2, true: 256^2) and whether the row remainder
+// over a multiple of 256 is peeled, into the tail kernel or (tail_by_tiles) a row of 128^2 tiles.  Every configuration
+// computes the same bits (same MFMA, operand roles and ascending-k order:
+// tests/test_gpu_ops.py::test_linear_big_m_kernels_agree_bitwise), so the choice is speed only.
+static void launch_gemm_config(const GemmArgs& a, hipStream_t st, bool kernel256, bool peel, bool tail_by_tiles) {
+    auto tiles = [&](const GemmArgs& g) { if (kernel256) launch_gemm256(g, st); else launch_gemm128(g, st); };
     if (a.seq_rows) {                    // (sanitised by the caller: the rule holds) tiles over the full 256-row tiles of every sequence + the split-K remainder
-        tiles(a, false);
-        GemmArgs t = a;
-        t.seq_tail = seq_peel_rows(a.seq_rows);
-        t.M = (a.M / a.seq_rows) * t.seq_tail;
-        if (a.tail_mark) a.tail_mark(a.tail_ctx, st);
-        launch_gemm_tailk(t, st);
+        tiles(a);
+        launch_seq_remainder(a, st);
         return;
     }
     const int tail = a.M % 256, main_rows = a.M - tail;
-    if (peel && tail > 0 && main_rows > 0) {
-        GemmArgs m = a;
-        m.M = main_rows;
-        tiles(m, false);
-        GemmArgs t = a;
-        t.A = a.A + (size_t)main_rows * a.lda;
-        t.R = a.R ? a.R + (size_t)main_rows * a.ldr : nullptr;
-        t.C = a.out_f32 ? (void*)((float*)a.C + (size_t)main_rows * a.ldc) : (void*)((bf16_t*)a.C + (size_t)main_rows * a.ldc);
-        t.M = tail;
-        if (a.tail_mark) a.tail_mark(a.tail_ctx, st);
-        if (tail_by_tiles) tiles(t, true);
-        else launch_gemm_tail(t, st);
-        return;
-    }
-    tiles(a, false);
+    if (!(peel && tail > 0 && main_rows > 0)) { tiles(a); return; }
+    tiles(gemm_rows(a, 0, main_rows));
+    const GemmArgs t = gemm_rows(a, main_rows, tail);
+    if (a.tail_mark) a.tail_mark(a.tail_ctx, st);
+    if (tail_by_tiles) launch_gemm128(t, st);
+    else launch_gemm_tail(t, st);
+}
+// The untuned choice = the cost model's configuration.  pl is gemm_plan at the rows the tile kernels cover, so pl.main_256 is
+// what tiles_us picks for the main part's own row count (all rows when nothing is peeled); a remainder run as a row of tiles
+// is always 128^2.
+static void launch_gemm_model(const GemmArgs& a, const GemmPlan& pl, hipStream_t st) {
+    launch_gemm_config(a, st, pl.main_256 != 0, pl.peel != 0, pl.tail_by_tiles != 0);
 }
 
 // "Measure, don't guess": the first time a big-M shape shows up (outside a stream capture) the candidate configurations are
@@ -1074,47 +930,61 @@ static std::map<TuneKey, int> g_tune;          // bit 0: 256^2 kernel, bit 1: pe
 struct TuneScratch { void* p = nullptr; size_t bytes = 0; };
 static std::map<int, TuneScratch> g_tune_scratch;      // per device: grow-only scratch output of the timing runs (no hipFree per shape = no device sync)
 
-static int autotune_gemm(const GemmArgs& a, hipStream_t st, const GemmPlan& model) {
-    const int fallback = (model.main_256 ? 1 : 0) | (model.peel ? 2 : 0) | (model.tail_by_tiles ? 4 : 0);
+// The timing runs of both tuners: candidate i is run(i, t) on the real operands (t = `a` writing the scratch output, outside
+// anybody's profile), once to warm up and three times between an event pair; ms[i] = those three runs, 1e30 where the timing
+// failed.  false: nothing can be timed here (the stream is capturing, no scratch, no events).  The caller holds g_tune_mu.
+template <typename Run>
+static bool time_candidates(const GemmArgs& a, hipStream_t st, int n, float* ms, Run run) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return fallback; }
-    const size_t esz = a.out_f32 ? 4 : 2;
-    const size_t need = (size_t)a.M * a.ldc * esz;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return false; }
+    const size_t need = (size_t)a.M * a.ldc * (a.out_f32 ? 4 : 2);
     int dev_id = 0;
-    if (hipGetDevice(&dev_id) != hipSuccess) { (void)hipGetLastError(); return fallback; }
-    TuneScratch& ts = g_tune_scratch[dev_id];           // (the caller holds g_tune_mu)
+    if (hipGetDevice(&dev_id) != hipSuccess) { (void)hipGetLastError(); return false; }
+    TuneScratch& ts = g_tune_scratch[dev_id];
     const bool in_place = a.tune_in_place && !a.R;      // nothing reads C: the timing runs may write it (no scratch: GemmArgs::tune_in_place)
     if (!in_place && need > ts.bytes) {
         void* bigger = nullptr;
-        if (hipMalloc(&bigger, need + need / 2) != hipSuccess) { (void)hipGetLastError(); return fallback; }
+        if (hipMalloc(&bigger, need + need / 2) != hipSuccess) { (void)hipGetLastError(); return false; }
         if (ts.p) (void)hipFree(ts.p);
         ts.p = bigger; ts.bytes = need + need / 2;
     }
-    void* scratch = in_place ? a.C : ts.p;
     hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return fallback;
+    if (hipEventCreate(&e0) != hipSuccess) return false;
+    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return false; }
     GemmArgs t = a;
-    t.C = scratch;
-    t.tail_mark = nullptr;                       // the timing runs are not part of anybody's profile
+    t.C = in_place ? a.C : ts.p;
+    t.tail_mark = nullptr;
+    for (int i = 0; i < n; ++i) {
+        ms[i] = 1e30f;
+        run(i, t);                                           // warm-up
+        (void)hipEventRecord(e0, st);
+        for (int r = 0; r < 3; ++r) run(i, t);
+        (void)hipEventRecord(e1, st);
+        if (hipEventSynchronize(e1) != hipSuccess) { (void)hipGetLastError(); continue; }
+        float v = 0.f;
+        if (hipEventElapsedTime(&v, e0, e1) == hipSuccess) ms[i] = v;
+    }
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    return true;
+}
+
+static int autotune_gemm(const GemmArgs& a, hipStream_t st, const GemmPlan& model) {
+    const int fallback = (model.main_256 ? 1 : 0) | (model.peel ? 2 : 0) | (model.tail_by_tiles ? 4 : 0);
     const int tail = a.M % 256, main_rows = a.M - tail;
     const bool can_peel = !a.seq_rows && tail > 0 && tail <= 96 && main_rows >= 2048;
     const long t256 = (long)(a.seq_rows ? (a.M / a.seq_rows) * (a.seq_rows / 256) : (a.M + 255) / 256) * ((a.N + 255) / 256);
-    int best = fallback;
-    float best_ms = 1e30f;
+    int cfgs[4], n = 0;
     for (int k256 = 0; k256 < 2; ++k256) {
         if (k256 && t256 < 100) continue;               // a 256^2 grid that leaves most CUs idle is never the answer
-        for (int peel = 0; peel < (can_peel ? 2 : 1); ++peel) {
-            const int cfg = k256 | (peel ? 2 : 0) | (peel && model.tail_by_tiles ? 4 : 0);
-            launch_gemm_config(t, st, k256, peel != 0, (cfg & 4) != 0);                 // warm-up
-            (void)hipEventRecord(e0, st);
-            for (int r = 0; r < 3; ++r) launch_gemm_config(t, st, k256, peel != 0, (cfg & 4) != 0);
-            (void)hipEventRecord(e1, st);
-            if (hipEventSynchronize(e1) != hipSuccess) { (void)hipGetLastError(); continue; }
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess && ms < best_ms) { best_ms = ms; best = cfg; }
-        }
+        for (int peel = 0; peel < (can_peel ? 2 : 1); ++peel) cfgs[n++] = k256 | (peel ? 2 : 0) | (peel && model.tail_by_tiles ? 4 : 0);
     }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    float ms[4];
+    if (!time_candidates(a, st, n, ms, [&](int i, const GemmArgs& t) { launch_gemm_config(t, st, cfgs[i] & 1, (cfgs[i] & 2) != 0, (cfgs[i] & 4) != 0); }))
+        return fallback;
+    int best = fallback;
+    float best_ms = 1e30f;
+    for (int i = 0; i < n; ++i)
+        if (ms[i] < best_ms) { best_ms = ms[i]; best = cfgs[i]; }
     if (getenv("SV_GEMM_AUTOTUNE_LOG"))
         fprintf(stderr, "[sv gemm autotune] M %d N %d K %d act %d res %d%s -> %s%s (%.1f us; model said %s%s)\n", a.M, a.N, a.K, a.act,
                 a.R ? 1 : 0, a.seq_rows ? " seq" : "", (best & 1) ? "256^2" : "128^2", (best & 2) ? " + peeled tail" : "", best_ms * 1000.f / 3.f,
@@ -1138,67 +1008,39 @@ static GemmArgs seq_sanitised(const GemmArgs& a0) {
     a.seq_tail = 0;
     return a;
 }
-static void launch_gemm_model(const GemmArgs& a, const GemmPlan& pl, hipStream_t st);
 // every row through the one-wave-per-tile kernel (bit-identical to the tile kernels); with the sequence structure: the full 256-row tiles' rows of
 // every sequence that way, the rows a sequence leaves over through the per-sequence split-K remainder kernel as in every other form
 static void launch_gemm_rows_by_tail(const GemmArgs& a, hipStream_t st) {
     if (!a.seq_rows) { launch_gemm_tail(a, st); return; }
     const int nseq = a.M / a.seq_rows, main = 256 * (a.seq_rows / 256);
-    for (int sq = 0; sq < nseq; ++sq) {
-        GemmArgs m = a;
-        const size_t r0 = (size_t)sq * a.seq_rows;
+    for (int sq = 0; sq < nseq && main > 0; ++sq) {
+        GemmArgs m = gemm_rows(a, (size_t)sq * a.seq_rows, main);
         m.seq_rows = 0;
-        m.A = a.A + r0 * a.lda;
-        m.R = a.R ? a.R + r0 * a.ldr : nullptr;
-        m.C = a.out_f32 ? (void*)((float*)a.C + r0 * a.ldc) : (void*)((bf16_t*)a.C + r0 * a.ldc);
-        m.M = main;
         m.tail_mark = nullptr;
-        if (main > 0) launch_gemm_tail(m, st);
+        launch_gemm_tail(m, st);
     }
-    GemmArgs t = a;
-    t.seq_tail = seq_peel_rows(a.seq_rows);
-    t.M = nseq * t.seq_tail;
-    if (a.tail_mark) a.tail_mark(a.tail_ctx, st);
-    launch_gemm_tailk(t, st);
+    launch_seq_remainder(a, st);
 }
 // the small-M decision, measured: bit 4 (16) = rows by the one-wave-per-tile kernel, 0 = the cost model's tiles
 static int autotune_small(const GemmArgs& a, hipStream_t st, const GemmPlan& model) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return 0; }
-    const size_t esz = a.out_f32 ? 4 : 2;
-    const size_t need = (size_t)a.M * a.ldc * esz;
-    int dev_id = 0;
-    if (hipGetDevice(&dev_id) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    TuneScratch& ts = g_tune_scratch[dev_id];           // (the caller holds g_tune_mu)
-    const bool in_place = a.tune_in_place && !a.R;
-    if (!in_place && need > ts.bytes) {
-        void* bigger = nullptr;
-        if (hipMalloc(&bigger, need + need / 2) != hipSuccess) { (void)hipGetLastError(); return 0; }
-        if (ts.p) (void)hipFree(ts.p);
-        ts.p = bigger; ts.bytes = need + need / 2;
-    }
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return 0;
-    GemmArgs t = a;
-    t.C = in_place ? a.C : ts.p;
-    t.tail_mark = nullptr;
-    float ms[2] = {1e30f, 1e30f};
-    for (int form = 0; form < 2; ++form) {
-        auto run = [&]() { if (form) launch_gemm_rows_by_tail(t, st); else launch_gemm_model(t, model, st); };
-        run();                                               // warm-up
-        (void)hipEventRecord(e0, st);
-        for (int r = 0; r < 3; ++r) run();
-        (void)hipEventRecord(e1, st);
-        if (hipEventSynchronize(e1) != hipSuccess) { (void)hipGetLastError(); continue; }
-        float v = 0.f;
-        if (hipEventElapsedTime(&v, e0, e1) == hipSuccess) ms[form] = v;
-    }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    float ms[2];
+    if (!time_candidates(a, st, 2, ms, [&](int form, const GemmArgs& t) { if (form) launch_gemm_rows_by_tail(t, st); else launch_gemm_model(t, model, st); }))
+        return 0;
     const int best = ms[1] < ms[0] ? 16 : 0;
     if (getenv("SV_GEMM_AUTOTUNE_LOG"))
         fprintf(stderr, "[sv gemm autotune] M %d N %d K %d act %d res %d%s -> %s (tiles %.1f us, one wave per tile %.1f us)\n", a.M, a.N, a.K, a.act, a.R ? 1 : 0,
                 a.seq_rows ? " seq" : "", best ? "one wave per 32 x 32 tile" : "tiles", ms[0] * 1000.f / 3.f, ms[1] * 1000.f / 3.f);
     return best;
+}
+// the remembered configuration of `key`, measured by tune() the first time the key shows up
+template <typename Tune>
+static int tuned_config(const TuneKey& key, Tune tune) {
+    std::lock_guard<std::mutex> lk(g_tune_mu);        // held across the timing runs: one tuner at a time, one scratch
+    auto it = g_tune.find(key);
+    if (it != g_tune.end()) return it->second;
+    const int cfg = tune();
+    g_tune[key] = cfg;
+    return cfg;
 }
 
 void launch_gemm_fixed(const GemmArgs& a0, int kernel256, int peel, hipStream_t st) {
@@ -1207,7 +1049,7 @@ void launch_gemm_fixed(const GemmArgs& a0, int kernel256, int peel, hipStream_t 
     launch_gemm_config(a, st, kernel256 != 0, peel != 0, false);
 }
 
-static std::atomic<int> g_gemm_form{-1};        // test surface (sv_debug_set_gemm_form): -1 = tuned, 0 / 1 = one fixed form
+static std::atomic<int> g_gemm_form{-1};        // test surface (sv_debug_set_gemm_form): -1 = tuned, 0 .. 3 = one fixed form
 void set_gemm_form(int form) { g_gemm_form = form; }
 
 void launch_gemm(const GemmArgs& a0, hipStream_t st) {
@@ -1215,7 +1057,8 @@ void launch_gemm(const GemmArgs& a0, hipStream_t st) {
     if (a.splitk_rows) { launch_gemm_tailk(a, st); return; }       // compact remainder rows (the pruned last prompt layer)
     const int fixed = g_gemm_form.load();
     // forms 0 / 1: one tile kernel, rows not peeled; 2: 256^2 tiles + the row remainder through the tail kernel -- the test surface that puts
-    // every kernel next to the others
+    // every kernel next to the others; 3: every row through launch_gemm_rows_by_tail (the form the small-M tuner may pick, made deterministic)
+    if (fixed == 3) { launch_gemm_rows_by_tail(a, st); return; }
     if (fixed >= 2) { launch_gemm_fixed(a, 1, 1, st); return; }
     if (fixed >= 0) { launch_gemm_fixed(a, fixed, 0, st); return; }
     // a handful of rows (the pruned last layer of a prompt pass: one row per sequence): one wave per 32 x 32 tile with 56 loads in flight
@@ -1228,13 +1071,7 @@ void launch_gemm(const GemmArgs& a0, hipStream_t st) {
         const int tail = a.M % 256;
         const TuneKey key{(a.M + 1023) / 1024, a.seq_rows ? 2 : (tail > 0 && tail <= 96 && a.M - tail >= 2048) ? 1 : 0, a.N, a.K, a.act, a.R ? 1 : 0,
                           a.out_f32, a.cscale ? 1 : 0};
-        int cfg;
-        {
-            std::lock_guard<std::mutex> lk(g_tune_mu);        // held across the timing runs: one tuner at a time, one scratch
-            auto it = g_tune.find(key);
-            if (it != g_tune.end()) cfg = it->second;
-            else { cfg = autotune_gemm(a, st, pl); g_tune[key] = cfg; }
-        }
+        const int cfg = tuned_config(key, [&]() { return autotune_gemm(a, st, pl); });
         launch_gemm_config(a, st, cfg & 1, (cfg & 2) != 0, (cfg & 4) != 0);
         return;
     }
@@ -1245,13 +1082,7 @@ void launch_gemm(const GemmArgs& a0, hipStream_t st) {
     // the big-M forms (the weights' re-reads per row tile decide; no model is trusted here).
     if (tune_on && a.M > 96 && a.M < 1024 && (!a.seq_rows || a.M / a.seq_rows <= 4)) {
         const TuneKey key{-((a.M + 63) / 64), a.seq_rows ? 2 : 0, a.N, a.K, a.act, a.R ? 1 : 0, a.out_f32, a.cscale ? 1 : 0};
-        int cfg;
-        {
-            std::lock_guard<std::mutex> lk(g_tune_mu);
-            auto it = g_tune.find(key);
-            if (it != g_tune.end()) cfg = it->second;
-            else { cfg = autotune_small(a, st, pl); g_tune[key] = cfg; }
-        }
+        const int cfg = tuned_config(key, [&]() { return autotune_small(a, st, pl); });
         if (cfg & 16) { launch_gemm_rows_by_tail(a, st); return; }
     }
     launch_gemm_model(a, pl, st);
@@ -1273,28 +1104,6 @@ void launch_gemm_ragged(const GemmArgs& a0, const int32_t* rows, int n_rows, bf1
     launch_gemm_tailk(t, st);
 }
 
-// the untuned choice: the cost model's tile kernel, its peel decision, the per-sequence remainder
-static void launch_gemm_model(const GemmArgs& a, const GemmPlan& pl, hipStream_t st) {
-    if (a.seq_rows) { launch_gemm_config(a, st, pl.main_256, false, false); return; }
-    const int tail = a.M % 256, main_rows = a.M - tail;
-    const bool peel = pl.peel != 0, tail_by_tiles = pl.tail_by_tiles != 0;
-    if (peel) {
-        GemmArgs m = a;
-        m.M = main_rows;
-        launch_gemm_tiles(m, st);
-        GemmArgs t = a;
-        t.A = a.A + (size_t)main_rows * a.lda;
-        t.R = a.R ? a.R + (size_t)main_rows * a.ldr : nullptr;
-        t.C = a.out_f32 ? (void*)((float*)a.C + (size_t)main_rows * a.ldc) : (void*)((bf16_t*)a.C + (size_t)main_rows * a.ldc);
-        t.M = tail;
-        if (a.tail_mark) a.tail_mark(a.tail_ctx, st);
-        if (tail_by_tiles) launch_gemm_tiles(t, st, true);
-        else launch_gemm_tail(t, st);
-        return;
-    }
-    launch_gemm_tiles(a, st);
-}
-
 // ------------------------------------------------------------------------------------------------
 // skinny GEMM (decode step)
 //   out[m][n] = epi( sum_k x[m][k] W[n][k] ),  M <= 32 rows per tile, HBM-bound weight streaming.
@@ -1311,136 +1120,6 @@ static void launch_gemm_model(const GemmArgs& a, const GemmPlan& pl, hipStream_t
 //   tiles per block came back in round 3 for 33..64 rows, where the activation re-reads do bound the launch:
 //   gemm_skinny_mt2_kernel.)
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) { return pack2bf(lo, hi); }   // common.h: v_cvt_pk_bf16_f32
-
-// 8 e4m3 bytes (one lane's share of a k-step) -> the bf16 MFMA operand.  gfx950 converts two fp8 to a packed bf16 pair in ONE
-// instruction (v_cvt_scalef32_pk_bf16_fp8, scale 1.0: exact, every e4m3 value is a bf16 value); round 2 went through float
-// (v_cvt_pk_f32_fp8 + shift / and-or per pair: 12 VALU instructions per k-step against these 4, next to 2 MFMAs of 8 passes).
-typedef __bf16 sv_bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ u32x4 fp8x8_to_bf16x8(uint32_t lo, uint32_t hi) {
-    const sv_bf16x2 a0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, false), a1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, true);
-    const sv_bf16x2 a2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, false), a3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, true);
-    union { sv_bf16x2 b; uint32_t u; } c0, c1, c2, c3;
-    c0.b = a0; c1.b = a1; c2.b = a2; c3.b = a3;
-    u32x4 wf = {c0.u, c1.u, c2.u, c3.u};
-    return wf;
-}
-
-// one chunk of the weight / activation stream held in registers
-template <int CH>
-struct SkChunk {
-    u32x4 w[CH];
-    u32x4 x[CH];
-};
-
-template <int CH>
-__device__ __forceinline__ void sk_load(SkChunk<CH>& c, const u32x4* wptr, const u32x4* xptr, int ks, int ks_end) {
-#pragma unroll
-    for (int u = 0; u < CH; ++u)
-        if (ks + u < ks_end) c.w[u] = __builtin_nontemporal_load(wptr + (size_t)(ks + u) * 64);   // streamed once
-#pragma unroll
-    for (int u = 0; u < CH; ++u)
-        if (ks + u < ks_end) c.x[u] = xptr[(size_t)(ks + u) * 64];                                 // wave-uniform guard
-}
-
-// the same without guards: the chunk lies inside the wave's k range.  The steady-state loops use this one on purpose: with the
-// wave-uniform guards of sk_load every load sits behind a branch, the compiler's wait-count analysis merges "loaded" and "not
-// loaded" paths and falls back to s_waitcnt vmcnt(0) in front of EVERY chunk's MFMAs -- the wave then waits for the loads it has
-// just issued (two chunks "in flight" were one round trip per chunk pair; found in round 3 from the ISA).
-template <int CH>
-__device__ __forceinline__ void sk_load_full(SkChunk<CH>& c, const u32x4* wptr, const u32x4* xptr, int ks) {
-#pragma unroll
-    for (int u = 0; u < CH; ++u) c.w[u] = __builtin_nontemporal_load(wptr + (size_t)(ks + u) * 64);
-#pragma unroll
-    for (int u = 0; u < CH; ++u) c.x[u] = xptr[(size_t)(ks + u) * 64];
-}
-
-// the bias of this lane's RPW output columns, requested BEFORE the weight stream (the epilogue must not start with a round trip)
-template <int RPW>
-__device__ __forceinline__ void sk_bias(const SkinnyArgs& p, float* bias_d, int r0, int nt, int half, float* fc1 = nullptr) {
-#pragma unroll
-    for (int i = 0; i < RPW; ++i) {
-        bias_d[i] = 0.f;
-        if (fc1) fc1[i] = 0.f;
-        const int r = r0 + i;
-        const int n = nt * 32 + 8 * (r >> 2) + 4 * half + (r & 3);
-        if (p.out_mode == SK_OUT_PACKED_ACT && n < p.N) {
-            if (fc1 && p.fold_c1) { fc1[i] = p.fold_c1[n]; bias_d[i] = p.fold_c2[n]; }
-            else if (p.bias) bias_d[i] = bf2f(p.bias[n]);
-        }
-    }
-}
-// The epilogue operands must have LANDED before the k loop starts: a load that stays pending across the loop makes the compiler's
-// wait-count analysis give up on the loop (an unbounded distance to the oldest pending load) and put s_waitcnt vmcnt(0) at the
-// top of every iteration.  An empty asm that "uses" the values forces the wait here, once, in the prologue.
-template <int RPW>
-__device__ __forceinline__ void sk_settle(float* a, float* b = nullptr) {
-#pragma unroll
-    for (int i = 0; i < RPW; ++i) {
-        asm volatile("" : "+v"(a[i]));
-        if (b) asm volatile("" : "+v"(b[i]));
-    }
-}
-// shared tail of the skinny kernels: v[i] = the reduced accumulator row r0 + i of lane (m, half), i.e. output
-// column n(r) = nt*32 + 8*(r >> 2) + 4*half + (r & 3) of row mt*32 + m; RPW consecutive rows r (RPW in {1, 2, 4, 8, 16})
-// fold: LayerNorm applied algebraically (decode_cols.hip): x = rstd * (acc - mean * c1[n]) + c2[n]; fc1 / fc2 = this lane's RPW
-// values of c1 / c2, (mean, rstd) = the statistics of row m
-struct SkFold { bool on; float mean, rstd; };
-template <int RPW>
-__device__ __forceinline__ void sk_store(const SkinnyArgs& p, float* v, const float* bias_d, int r0, int nt, int mt, int split, int m,
-                                         int half, const SkFold fold = SkFold{false, 0.f, 1.f}, const float* fc1 = nullptr) {
-    constexpr int G = RPW >= 4 ? RPW / 4 : 1;          // groups of (up to) 4 consecutive columns
-    constexpr int W = RPW >= 4 ? 4 : RPW;
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const int r = r0 + 4 * g;
-        const int n0 = nt * 32 + 8 * (r >> 2) + 4 * half + (r & 3);
-        float* vv = v + 4 * g;
-        auto store_f32 = [&](float* dst) {
-            if constexpr (W == 4) *reinterpret_cast<float4*>(dst) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-            else if constexpr (W == 2) *reinterpret_cast<float2*>(dst) = make_float2(vv[0], vv[1]);
-            else dst[0] = vv[0];
-        };
-        // TWO separate stores on purpose: written as one store through `cond ? ws + .. : out_f32 + ..` (or an if / else that only
-        // picks the pointer) hipcc 7.2 keeps the out_f32 base register for both arms and the slab store goes to a null pointer
-        // (seen twice: the fp8 kernel in round 2, this helper in round 3 -- a GPU memory fault at 0x1000).
-        if (p.out_mode == SK_OUT_PARTIAL) {
-            store_f32(p.ws + ((size_t)split * p.MT * 32 + mt * 32 + m) * p.ldws + n0);
-        } else if (p.out_mode == SK_OUT_F32) {
-            if (p.round_bf16) {
-#pragma unroll
-                for (int i = 0; i < W; ++i) vv[i] = bfround(vv[i]);
-            }
-            store_f32(p.out_f32 + ((size_t)mt * 32 + m) * p.ldo + n0);
-        } else {   // SK_OUT_PACKED_ACT
-#pragma unroll
-            for (int i = 0; i < W; ++i) {
-                float x = 0.f;
-                if (n0 + i < p.N) {
-                    // (fold: bias_d carries c2 = sum_k beta_k W[n][k] + bias[n])
-                    x = fold.on ? bfround(fold.rstd * (vv[i] - fold.mean * fc1[4 * g + i]) + bias_d[4 * g + i])
-                                : bfround(vv[i] + bias_d[4 * g + i]);
-                    if (p.act != ACT_NONE) x = sv_act(x, p.act);
-                }
-                vv[i] = x;
-            }
-            bf16_t* dst = p.out_xp + xp_index(mt, p.out_KS, m, n0);
-            if constexpr (W == 4) {
-                uint2 o; o.x = pack2bf(vv[0], vv[1]); o.y = pack2bf(vv[2], vv[3]);
-                *reinterpret_cast<uint2*>(dst) = o;
-            } else if constexpr (W == 2) {
-                *reinterpret_cast<uint32_t*>(dst) = pack2bf(vv[0], vv[1]);
-            } else {
-                dst[0] = f2bf(vv[0]);
-            }
-        }
-    }
-}
-
-// Leading scalar parameters = the few values the first address computation needs: they are PRELOADED into SGPRs by the command
-// processor (build flag -amdgpu-kernarg-preload-count; only scalar / pointer parameters qualify, not a by-value struct), so the
-// weight stream is requested without first waiting for a scalar load of the argument block (a cold K$ miss at every launch).
-struct SkinnyKernarg { const void* W; const bf16_t* x; int KS; int ks_per_split; int flags; SkinnyArgs p; };      // the kernarg segment of the skinny kernels
 // FOLD: the LayerNorm-folded c_fc (decode_cols.hip) -- its own instantiation, so that the statistics registers do not cost the
 // other GEMMs their second block per CU (<= 128 VGPRs)
 // HEAD: the lm_head launch of a step that folds the greedy selection into the epilogue and / or arms the polled buffer of the next
@@ -1623,6 +1302,10 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_skinny_kernel(const bf16_t* W
         }
     }
 }
+// dynamic LDS of the kernels here: the cross-wave reduction buffer [waves][16][64] fp32 is the unit they all share
+constexpr size_t sk_red_bytes(int waves) { return (size_t)waves * 16 * 64 * 4; }
+constexpr size_t sk_stat_bytes(int waves) { return (size_t)waves * 32 * 8; }           // [waves][32] row statistics / selection keys
+constexpr size_t skinny_smem(int waves) { return sk_red_bytes(waves) + sk_stat_bytes(waves) + 16; }
 
 // ------------------------------------------------------------------------------------------------
 // gemm_head_persist_kernel (round 6, fourth session): the lm_head of a <= 32-row decode step as ONE round of blocks that each walk several
@@ -1777,6 +1460,8 @@ __global__ __launch_bounds__(512) void gemm_head_persist_kernel(const bf16_t* Wp
         }
     }
 }
+constexpr size_t head_persist_smem(int row_tiles) { return row_tiles * sk_red_bytes(8) + sk_stat_bytes(8); }      // [MT][8][16][64] fp32 + the keys
+
 // ------------------------------------------------------------------------------------------------
 // gemm_skinny_tailsplit_kernel (round 6, fourth session): the column tiles of a whole-K skinny GEMM that do not fit the first round of blocks.
 // StarVector-8B's c_fc at <= 32 rows is 576 one-tile blocks on 512 block slots (two 8-wave blocks per CU): the second "round" is 64 blocks that each stream
@@ -1870,22 +1555,34 @@ __global__ __launch_bounds__(128) void gemm_skinny_tailsplit_kernel(const bf16_t
 std::atomic<long long> g_tailsplit_launches{0};     // host-side count of tail-split launches (sv_debug_tailsplit_launches)
 long long tailsplit_launches() { return g_tailsplit_launches.load(std::memory_order_relaxed); }
 
+// An A/B switch of the environment, read per call (A/B inside one process; a captured graph keeps its choice): unset = dflt
+static int env_switch(const char* name, int dflt) {
+    const char* ev = getenv(name);
+    return ev ? atoi(ev) : dflt;
+}
+// CUs of the current device (0: the query failed).  Cached per device id; concurrent first calls store the same value.
+static int device_cus() {
+    constexpr int MAXDEV = 64;
+    static std::atomic<int> cached[MAXDEV];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    int cus = dev >= 0 && dev < MAXDEV ? cached[dev].load(std::memory_order_relaxed) : 0;
+    if (cus) return cus;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    if (dev >= 0 && dev < MAXDEV) cached[dev].store(cus, std::memory_order_relaxed);
+    return cus;
+}
+
 // G = blocks of the persistent lm_head launch for `a`; 0: outside the kernel's scope
 static int head_persist_grid(const SkinnyArgs& a) {
     // on by default: the lm_head of a one-row-tile step through gemm_head_persist_kernel where it applies; SV_HEAD_PERSIST=0 = the one-tile kernel
-    // (read per call: A/B in one process; a captured graph keeps its choice)
-    const char* ev = getenv("SV_HEAD_PERSIST");
-    if (ev && atoi(ev) == 0) return 0;
+    if (!env_switch("SV_HEAD_PERSIST", 1)) return 0;
     const int n_tiles = a.Npad / 32;
     if (a.out_mode != SK_OUT_F32 || a.MT < 1 || a.MT > 2 || a.Wq || a.splitk != 1 || a.K / 16 != 128 || n_tiles < 512 || a.fold_c1) return 0;
     if (a.MT == 2 && (a.amax || a.poison)) return 0;      // (the folded selection and the pattern stores belong to one-row-tile steps)
     if (a.N <= (n_tiles - 1) * 32 || a.N > n_tiles * 32) return 0;
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0; hipDeviceProp_t pr;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 0;
-        cus = pr.multiProcessorCount;
-    }
+    const int cus = device_cus();
+    if (!cus) return 0;
     const int G = cus < n_tiles ? cus : n_tiles;
     if (a.poison && (size_t)G * 512 * 16 < a.poison_bytes) return 0;      // the pattern stores are 16 bytes per thread of the grid
     return G;
@@ -1904,275 +1601,9 @@ static bool launch_head_persist(const SkinnyArgs& a_, hipStream_t st) {
     if (skinny_head_folds_finish(a)) f = *a.finish; else a.fin_cnt = nullptr;
     a.finish = nullptr;                                         // (a host address: nothing for the device)
     const int n_tiles = a.Npad / 32;
-    if (a.MT == 2) gemm_head_persist_kernel<2><<<G, 512, 2 * 8 * 16 * 64 * 4 + 8 * 32 * 8, st>>>(a.Wp, a.xp, a.K / 16, a.K / 16, n_tiles, a, f);
-    else gemm_head_persist_kernel<1><<<G, 512, 8 * 16 * 64 * 4 + 8 * 32 * 8, st>>>(a.Wp, a.xp, a.K / 16, a.K / 16, n_tiles, a, f);
+    if (a.MT == 2) gemm_head_persist_kernel<2><<<G, 512, head_persist_smem(2), st>>>(a.Wp, a.xp, a.K / 16, a.K / 16, n_tiles, a, f);
+    else gemm_head_persist_kernel<1><<<G, 512, head_persist_smem(1), st>>>(a.Wp, a.xp, a.K / 16, a.K / 16, n_tiles, a, f);
     return true;
-}
-
-// ------------------------------------------------------------------------------------------------
-// mlp_fused_kernel: the MLP half of a decode layer (gpt_bigcode/modeling_gpt_bigcode.py:645-660: c_fc -> GELU-tanh -> c_proj) as ONE
-// launch of F/32 co-resident blocks (256 for StarVector-1B, one 8-wave block per CU), instead of gemm_skinny_kernel<8, true> (folded
-// c_fc) and gemm_skinny_kernel<8, false> (down projection, split-K slabs) with a kernel boundary between them.  Round 4; on for an
-// engine that owns its GPU (sv_config.exclusive_device), SV_EXP_MLP_FUSED_FORCE / SV_EXP_MLP_FUSED_OFF = forced on / off.  Measured in process on one MI355X,
-// BASELINE config 2: 1079 vs 1111 us per decode step, tokens bit-identical (every version's A/B and wall-clock
-// trace: profiles/mlp_fused_r04_ab.log).
-//
-//   Why it pays (MI355X_MICROARCH.md price list: boundary, prefetch-credit): both GEMMs are pure weight streams (2 x 33.5 MB) and the
-//   WEIGHTS of the second one depend on nothing.  Two launches pay a boundary (1.7-1.9 us) plus the second kernel's cold start; here a
-//   wave requests the first half of its share of the down projection's weights as soon as its c_fc loop has issued its last MFMA, so
-//   HBM keeps streaming under the c_fc reduction, epilogue and publish.
-//
-//   Phase 1  block L = (xcd = L & 7, i = L >> 3): c_fc tile nt1 = split * (T1 / S) + (xcd / S) * (T1 / 8) + i with split = xcd % S --
-//            the 32 GELU output columns of a tile are 2 KiB contiguous in fragment order; they go LDS -> 16-byte sc1 (write-through)
-//            stores.  No flag, no counter, nothing to drain.
-//   Phase 2  the same block owns (tile nt2 = (xcd / S) * (T1 / 8) + i, K slice `split`) of the down projection = exactly the
-//            (tile, slice) the XCD-aware assignment of the slab kernel gives block L.  Wave w needs the c_fc columns of its 16 k-steps
-//            = the tiles of 8 producer blocks; it reads them with sc1 loads (L1 bypass) and recognises "not written yet" by the data
-//            itself: the launch in front fills the buffer with the bf16 pair 0xFFFF'FFFF (two NaNs -- never a finite GELU output), a
-//            k-step that still shows the pattern is re-requested after an s_sleep, BOUNDED (a give-up code in *err, never a hang).
-//   What the traces taught (all of it in profiles/mlp_fused_r04_ab.log):
-//            * one arrival counter per K slice (64 arrivals + 64 pollers per word): 25.5 us per launch against 17.8 for two launches;
-//              one flag word per producer: 17.7 us (the publish store drained behind 24 MB of weight prefetch); in-band pattern: 14.9;
-//              + the first half of the weights requested before the reduction: 13.8 us -- this version.
-//            * a CU's miss queue takes ~64 KiB: a wave that requests more BLOCKS AT ISSUE until the queue drains, and a wave's loads
-//              return IN ORDER -- a poll queued behind 16 KiB of its own weight requests completes after them.  Requesting all 16 KiB
-//              at once, moving the reduction to two "critical-path" waves, and the attention output projection as a phase 0 in front
-//              (a residual-stream ping-pong, 4 launches per layer) were all built, bit-identical, and slower or equal: removed.
-//              Round 5 BUILT the loader wave (a ninth wave per block streams the block's W2 share into LDS with global_load_lds, the
-//              consumers request nothing but polls after the publish): bit-identical, +2.0 ... +2.5 us per layer for every start
-//              trigger / depth tried -- polls issued at the publish find the pattern and every failed poll is a ~2 us round trip beside
-//              the CU's own fill stream; this form's polls ride behind the second half of the weights and arrive when the data is there.
-//              What is left over the 12.2 us that 67 MB + the phase-2 tail take is ~1 us.  profiles/mlp_fused_r05_loader_ab.log; removed.
-//   Results  per-wave k ranges, MFMA order, cross-wave reduction order, fold statistics and epilogues are those of the two kernels it
-//            replaces: bit-identical slabs (tests/test_gpu_e2e.py::test_fused_mlp_launch_equals_the_two_launches_bit_for_bit).
-//   Safety   needs all F/32 blocks resident at once (one per CU): enabled only when #CUs >= F/32 AND the engine owns the device -- two
-//            processes decoding on one GPU could each hold part of the CUs and wait for blocks that cannot be scheduled (then both
-//            give up after the bounded spin and the call fails: never a hang, never wrong tokens).  The pattern is written by the
-//            kernel in front (gemm_cols_resid_kernel, ColsArgs::poison), never by this launch; a NaN pair with the pattern (corrupted
-//            inputs only: arithmetic NaNs are 0x7FC0) ends in the give-up code, i.e. an error from sv_generate.
-// ------------------------------------------------------------------------------------------------
-struct MlpFusedKernarg { const bf16_t* W1; const bf16_t* x1; const bf16_t* W2; int KS1; int KS2; int S; MlpFusedArgs p; };
-// amdgpu_waves_per_eu(2, 2): one 8-wave block per CU is the design point (2 waves per SIMD, 256 VGPRs each); without it the
-// scheduler trades registers for a third wave that can never exist and serialises phase 2's 16 activation loads 3 at a time
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void mlp_fused_kernel(const bf16_t* W1_, const bf16_t* x1_, const bf16_t* W2_, int KS1_, int KS2_, int S_,
-                                                        MlpFusedArgs p_unused) {
-    constexpr int WAVES = 8, CH = 4, NB = 2, RPW = 2, KPW = 16;          // k-steps per wave in BOTH phases (host-checked)
-    extern __shared__ __attribute__((aligned(16))) char sk_smem[];
-    float (*red)[16][64] = reinterpret_cast<float (*)[16][64]>(sk_smem);          // [WAVES][16][64]
-    float2* fst_s = reinterpret_cast<float2*>(sk_smem + (size_t)WAVES * 16 * 64 * 4);      // [WAVES][32] partial row statistics
-    bf16_t* tile_s = reinterpret_cast<bf16_t*>(sk_smem + (size_t)WAVES * 16 * 64 * 4 + (size_t)WAVES * 32 * 8);   // 2 KiB: the c_fc tile
-    int* flag_s = reinterpret_cast<int*>(tile_s + 1024);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int m = lane & 31, half = lane >> 5;
-    const int L = blockIdx.x, xcd = L & 7, ii = L >> 3;
-    const int T1 = gridDim.x, tpg = T1 >> 3;
-    const int split = xcd % S_, grp = xcd / S_;
-    const int nt2 = grp * tpg + ii;
-    const int nt1 = split * (T1 / S_) + nt2;
-    const long long t_start = wall_clock64();             // 100 MHz; only stored when the trace buffer is on (tools/mlp_trace.py)
-
-    // ---- phase 1: folded c_fc, tile nt1 over the whole K1 (gemm_skinny_kernel<8, true>, long-range path) ----
-    const int ks0 = wave * KPW;
-    const u32x4* wptr = reinterpret_cast<const u32x4*>(W1_) + ((size_t)nt1 * KS1_ + ks0) * 64 + lane;
-    const u32x4* xptr = reinterpret_cast<const u32x4*>(x1_) + (size_t)ks0 * 64 + lane;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    SkChunk<CH> ck[NB];
-    float fs1 = 0.f, fs2 = 0.f;
-    auto fold_acc = [&](const u32x4& xv) {
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const float a = __uint_as_float(xv[w] << 16), b = __uint_as_float(xv[w] & 0xffff0000u);
-            fs1 += a + b;
-            fs2 = fmaf(a, a, fmaf(b, b, fs2));
-        }
-    };
-#pragma unroll
-    for (int b = 0; b < NB; ++b) sk_load_full<CH>(ck[b], wptr, xptr, b * CH);
-    const MlpFusedArgs p = sv_late_args<MlpFusedArgs>(offsetof(MlpFusedKernarg, p));
-    float c2v[RPW], c1v[RPW];
-#pragma unroll
-    for (int i = 0; i < RPW; ++i) {
-        const int r = wave * RPW + i;
-        const int n = nt1 * 32 + 8 * (r >> 2) + 4 * half + (r & 3);
-        c1v[i] = n < p.N1 ? p.fold_c1[n] : 0.f;
-        c2v[i] = n < p.N1 ? p.fold_c2[n] : 0.f;
-    }
-    sk_settle<RPW>(c2v, c1v);
-#pragma unroll
-    for (int ks = 0; ks < KPW; ks += NB * CH) {
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-#pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag4(ck[b].w[u]), as_frag4(ck[b].x[u]), acc, 0, 0, 0);
-                fold_acc(ck[b].x[u]);
-            }
-            if (ks + (b + NB) * CH < KPW) {
-                __builtin_amdgcn_sched_barrier(0);
-                sk_load_full<CH>(ck[b], wptr, xptr, ks + (b + NB) * CH);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
-    const long long t_loop1 = wall_clock64();
-    const int ks2 = split * (WAVES * KPW) + wave * KPW;
-    const u32x4* w2ptr = reinterpret_cast<const u32x4*>(W2_) + ((size_t)nt2 * KS2_ + ks2) * 64 + lane;
-    u32x4 w2[KPW];
-    // The down projection's weights of this wave (tile nt2, k-steps split * 128 + wave * 16 .. + 16: 16 KiB) depend on nothing: the first
-    // half is requested NOW, so that the HBM stream does not pause while the block reduces and publishes (third version: requested after
-    // the publish -- HBM idle for 2.5 us); 8 KiB per wave in flight is what the steady state of the stand-alone kernels keeps (all
-    // 16 KiB at once put 24 MB of reads in front of every tile store of the chip: second version, 6 us from loop end to publish).
-    // (round 5 re-measured the alternative "reduce and publish with an empty queue, then the whole 16 KiB share": publish 0.9 us earlier, but the
-    //  MFMAs then wait 2.7 us for the weights -- 1100 vs 1066 us per step; removed.)
-#pragma unroll
-    for (int u = 0; u < 8; ++u) w2[u] = __builtin_nontemporal_load(w2ptr + (size_t)u * 64);
-
-    // K reduction across the waves (wave order) + LayerNorm fold epilogue: gemm_skinny_kernel<8, true>'s, value for value
-    float v[RPW];
-    fs1 += __shfl_xor(fs1, 32, 64);
-    fs2 += __shfl_xor(fs2, 32, 64);
-    if (half == 0) fst_s[wave * 32 + m] = make_float2(fs1, fs2);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) red[wave][r][lane] = acc[r];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < RPW; ++i) {
-        const int r = wave * RPW + i;
-        float t = red[0][r][lane];
-#pragma unroll
-        for (int w = 1; w < WAVES; ++w) t += red[w][r][lane];
-        v[i] = t;
-    }
-    {
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int q = 0; q < WAVES; ++q) { const float2 t = fst_s[q * 32 + m]; s1 += t.x; s2 += t.y; }
-        const float invD = 1.0f / (float)p.fold_D;
-        const float mean = s1 * invD;
-        float var = s2 * invD - mean * mean;
-        var = var > 0.f ? var : 0.f;
-        const float rstd = rsqrtf(var + p.fold_eps);
-        const int r = wave * RPW;
-        const int nl = 8 * (r >> 2) + 4 * half + (r & 3);                 // local column of v[0] (v[1]: + 1)
-        float o[RPW];
-#pragma unroll
-        for (int i = 0; i < RPW; ++i) {
-            float x = 0.f;
-            if (nt1 * 32 + nl + i < p.N1) {
-                x = bfround(rstd * (v[i] - mean * c1v[i]) + c2v[i]);
-                if (p.act != ACT_NONE) x = sv_act(x, p.act);
-            }
-            o[i] = x;
-        }
-        // the tile in fragment order (the image xp_index addresses: [k-step nl >> 4][64 lanes][8])
-        *reinterpret_cast<uint32_t*>(tile_s + (((nl >> 4) * 64 + ((nl >> 3) & 1) * 32 + m) * 8 + (nl & 7))) = pack2bf(o[0], o[1]);
-    }
-    __syncthreads();
-    // ---- hand-off, third version: NO flag and NO counter.  The launch in front of this one (gemm_cols_resid_kernel) fills the whole
-    // activation buffer with the bf16 pair 0xFFFF'FFFF (two NaNs: no finite GELU output has that pattern).  A producer only writes its
-    // 2 KiB tile (write-through 16-byte stores, nothing to wait for); a consumer WAVE polls the 16 KiB it needs itself -- the tiles of
-    // the 8 producers behind its 16 k-steps, not of all 64 producers of the slice -- and re-requests only the k-steps that still
-    // carry the pattern.  History (profiles/mlp_fused_r04_ab.log): one ticket word per K slice: 25.5 us per launch (64 arrivals + 64
-    // pollers per word); one flag word per producer polled by wave 0: 17.7 us = the two launches, with 6 us of "publish" (the store
-    // drained behind 24 MB of weight prefetch) and 4 us of "wait" on the critical path.
-    const __amdgpu_buffer_rsrc_t rs_act = __builtin_amdgcn_make_buffer_rsrc(p.out_xp, 0, (unsigned)((size_t)p.out_KS * 1024), 0x00020000);
-    if (wave < 2) {
-        const u32x4 q = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(tile_s) + tid * 16);
-        __builtin_amdgcn_raw_buffer_store_b128(q, rs_act, nt1 * 2048 + tid * 16, 0, 16);          // sc1: write-through
-    }
-    const long long t_pub = wall_clock64();
-    // second half of the weights (the first half has landed during the reduction), then -- once half of THAT is in -- the activations:
-    // their producers publish at about the same time as this block, and a request that finds the pattern costs a whole extra round trip
-#pragma unroll
-    for (int u = 8; u < 16; ++u) w2[u] = __builtin_nontemporal_load(w2ptr + (size_t)u * 64);
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-
-    // ---- phase 2: down projection (tile nt2, K slice `split`) -> fp32 slab, gemm_skinny_kernel<8, false>'s order ----
-    // (round 5 tried rowln_cattn_kernel's lesson here -- hold the first poll until a fixed time after the block's start: 1007.1 us per step at 10.0 us
-    //  against 1009.8 without, worse from 11 us on: the polls already sit where the data turns up; profiles/rowln_cattn_r05_ab.log)
-    u32x4 x2[KPW];
-#pragma unroll
-    for (int u = 0; u < KPW; ++u) x2[u] = __builtin_amdgcn_raw_buffer_load_b128(rs_act, (ks2 + u) * 1024 + lane * 16, 0, 16);   // sc1: L1 bypass
-    unsigned pending = 0xffffu;                              // k-steps whose activations are not (known to be) complete: wave-uniform
-    int gave_up = 1;
-    // Bounded by WALL CLOCK, not by a poll count (65536 polls of ~2 us each per wave, per layer, per step turned a
-    // co-residency failure into minutes before the host saw it): a wave gives up after spin_ticks (5 ms) -- and at once when another
-    // wave or an earlier launch has already raised the flag (every later layer of a void step then falls through without waiting).
-    for (int it = 0;; ++it) {
-        unsigned still = 0u;
-#pragma unroll
-        for (int u = 0; u < KPW; ++u) {
-            if (pending & (1u << u)) {
-                const bool bad = x2[u][0] == 0xffffffffu || x2[u][1] == 0xffffffffu || x2[u][2] == 0xffffffffu || x2[u][3] == 0xffffffffu;
-                if (__any(bad)) still |= 1u << u;
-            }
-        }
-        pending = still;
-        if (!pending) { gave_up = 0; break; }
-        if ((it & 7) == 7 && (wall_clock64() - t_pub > (long long)p.spin_ticks ||
-                              __hip_atomic_load(p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) break;
-        __builtin_amdgcn_s_sleep(8);
-#pragma unroll
-        for (int u = 0; u < KPW; ++u)
-            if (pending & (1u << u)) x2[u] = __builtin_amdgcn_raw_buffer_load_b128(rs_act, (ks2 + u) * 1024 + lane * 16, 0, 16);
-    }
-    if (gave_up && lane == 0) atomicCAS(p.err, 0, 3);      // the step's result is void; the first code raised survives
-    const long long t_go = wall_clock64();
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int u = 0; u < KPW; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag4(w2[u]), as_frag4(x2[u]), acc, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) red[wave][r][lane] = acc[r];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < RPW; ++i) {
-        const int r = wave * RPW + i;
-        float t = red[0][r][lane];
-#pragma unroll
-        for (int w = 1; w < WAVES; ++w) t += red[w][r][lane];
-        v[i] = t;
-    }
-    {
-        const int r = wave * RPW;
-        const int n0 = nt2 * 32 + 8 * (r >> 2) + 4 * half + (r & 3);
-        *reinterpret_cast<float2*>(p.ws + ((size_t)split * p.rows_ws + m) * p.ldws + n0) = make_float2(v[0], v[1]);
-    }
-    if (p.trace && tid == 0) {                              // block L: start | c_fc loop done | tile published | slice complete | end  (wave 0's clock)
-        long long* q = p.trace + (size_t)L * 8;
-        q[0] = t_start; q[1] = t_loop1; q[2] = t_pub; q[3] = t_go; q[4] = wall_clock64(); { unsigned xcc; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc)); q[5] = (long long)(xcc & 0xf); }
-    }
-}
-static size_t mlp_fused_smem() { return (size_t)8 * 16 * 64 * 4 + (size_t)8 * 32 * 8 + 2048 + 64; }
-
-// 0 = launched; -1 = the shapes are outside the kernel's scope (the caller runs the two launches)
-int launch_mlp_fused(const MlpFusedArgs& a, hipStream_t st) {
-    const int KS1 = a.K1 / 16, KS2 = a.K2 / 16, T1 = a.N1pad / 32, T2 = a.N2pad / 32;
-    if (a.splitk < 1 || 8 % a.splitk || T1 % 8 || KS1 != 8 * 16 || KS2 != a.splitk * 8 * 16) return -1;      // 16 k-steps per wave in both phases
-    if (T2 * a.splitk != T1 || a.K2 != a.N1pad || a.N1 != a.N1pad || a.N2 != a.N2pad) return -1;
-    if (!a.err || !a.fold_c1 || !a.fold_c2) return -1;
-    mlp_fused_kernel<<<T1, 512, mlp_fused_smem(), st>>>(a.W1, a.x1, a.W2, KS1, KS2, a.splitk, a);
-    return 0;
-}
-
-static size_t skinny_smem(int waves) { return (size_t)waves * 16 * 64 * 4 + (size_t)waves * 32 * 8 + 16; }
-
-static int init_mt2_attrs();
-int init_gemm_kernels() {
-    // 16-wave blocks reduce through 64 KiB of LDS: above the default dynamic-LDS limit
-    int r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_kernel<16, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_kernel<16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_kernel<16, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (!r) r = init_mt2_attrs();
-    if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_head_persist_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 8 * 16 * 64 * 4 + 8 * 32 * 8);
-    if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<bf16_t>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 2 * G2_BUF);
-    if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<float>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 2 * G2_BUF);
-    return r;
 }
 
 template <int W>
@@ -2303,6 +1734,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_skinny_fp8_kernel(const uint8
     }
     sk_store<RPW>(p, v, bias_d, wave * RPW, nt, mt, split, m, half);
 }
+constexpr size_t skinny_fp8_smem(int waves) { return sk_red_bytes(waves); }
 
 // Waves per block of the skinny kernels = how K is cut inside a block, i.e. the order in which a row's partial sums are
 // added.  A function of the GEMM (N, K, split-K) ONLY -- never of the number of rows -- so that a row's bits do not depend on
@@ -2330,12 +1762,10 @@ static bool launch_gemm_skinny_fp8(const SkinnyArgs& a, hipStream_t st) {
     if (!(a.out_mode == SK_OUT_PARTIAL || ((a.out_mode == SK_OUT_PACKED_ACT || a.out_mode == SK_OUT_F32) && a.splitk == 1)))
         return false;
     const dim3 grid(a.Npad / 32, a.splitk, a.MT);
-    const int per_split = (a.K / 16) / a.splitk;
-    (void)per_split;
     const int waves = skinny_waves_fp8(a.K / 16, a.splitk);
-    if (waves == 8) gemm_skinny_fp8_kernel<8><<<grid, 512, 8 * 16 * 64 * 4, st>>>(a.Wq, a.xp, a.K / 16, (a.K / 16) / a.splitk, a.xcd_remap, a);
-    else if (waves == 4) gemm_skinny_fp8_kernel<4><<<grid, 256, 4 * 16 * 64 * 4, st>>>(a.Wq, a.xp, a.K / 16, (a.K / 16) / a.splitk, a.xcd_remap, a);
-    else if (waves == 2) gemm_skinny_fp8_kernel<2><<<grid, 128, 2 * 16 * 64 * 4, st>>>(a.Wq, a.xp, a.K / 16, (a.K / 16) / a.splitk, a.xcd_remap, a);
+    if (waves == 8) gemm_skinny_fp8_kernel<8><<<grid, 512, skinny_fp8_smem(8), st>>>(a.Wq, a.xp, a.K / 16, (a.K / 16) / a.splitk, a.xcd_remap, a);
+    else if (waves == 4) gemm_skinny_fp8_kernel<4><<<grid, 256, skinny_fp8_smem(4), st>>>(a.Wq, a.xp, a.K / 16, (a.K / 16) / a.splitk, a.xcd_remap, a);
+    else if (waves == 2) gemm_skinny_fp8_kernel<2><<<grid, 128, skinny_fp8_smem(2), st>>>(a.Wq, a.xp, a.K / 16, (a.K / 16) / a.splitk, a.xcd_remap, a);
     else return false;
     return true;
 }
@@ -2513,6 +1943,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_skinny_mt2_kernel(const void*
         }
     }
 }
+constexpr size_t mt2_smem(int waves) { return 2 * sk_red_bytes(waves); }      // one reduction buffer per row tile
 
 // ------------------------------------------------------------------------------------------------
 // gemm_skinny_mt2x_kernel (round 6): the two-row-tile kernel with the ACTIVATIONS landing in LDS and twice the waves per CU.
@@ -2690,32 +2121,33 @@ __global__ __launch_bounds__(512, CH == 2 ? 4 : 2) void gemm_skinny_mt2x_kernel(
     }
 }
 
-#define MT2X_SMEM(ch) (8 * 2 * (ch) * 2048 + 2 * 3 * 32 * 4)      // the ring / reduction buffer + [NT <= 3][32] scales + biases
+constexpr size_t mt2x_smem(int ch) { return (size_t)8 * 2 * ch * 2048 + 2 * 3 * 32 * 4; }      // the ring / reduction buffer + [NT <= 3][32] scales + biases
+
 std::atomic<int> g_mt2x{1};             // 33..64 rows: 0 = gemm_skinny_mt2_kernel, 1 = the LDS-ring form (chunk depth by block count), 2 / 3 = its CH = 2 / 4 form always
 void set_mt2x(int on) { g_mt2x = on; }
 int get_mt2x() { return g_mt2x.load(std::memory_order_relaxed); }
 
 std::atomic<int> g_op_col_tiles{0};     // op-level entry points only (SkinnyArgs.col_tiles == 0); engines always pass their plan
-static int init_mt2_attrs() {
-    int r = 0;
-    auto set = [&](const void* f, int bytes) { if (!r) r = (int)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); };
-    set(reinterpret_cast<const void*>(&gemm_skinny_mt2_kernel<8, true, 1>), 2 * 8 * 16 * 64 * 4);
-    set(reinterpret_cast<const void*>(&gemm_skinny_mt2_kernel<8, false, 1>), 2 * 8 * 16 * 64 * 4);
-    set(reinterpret_cast<const void*>(&gemm_skinny_mt2_kernel<8, true, 2>), 2 * 8 * 16 * 64 * 4);
-    set(reinterpret_cast<const void*>(&gemm_skinny_mt2_kernel<8, false, 2>), 2 * 8 * 16 * 64 * 4);
-    set(reinterpret_cast<const void*>(&gemm_skinny_mt2_kernel<8, true, 3>), 2 * 8 * 16 * 64 * 4);
-    set(reinterpret_cast<const void*>(&gemm_skinny_mt2_kernel<8, false, 3>), 2 * 8 * 16 * 64 * 4);
-    set(reinterpret_cast<const void*>(&gemm_skinny_mt2x_kernel<true, 1, 2>), MT2X_SMEM(2));
-    set(reinterpret_cast<const void*>(&gemm_skinny_mt2x_kernel<false, 1, 2>), MT2X_SMEM(2));
-    set(reinterpret_cast<const void*>(&gemm_skinny_mt2x_kernel<true, 2, 2>), MT2X_SMEM(2));
-    set(reinterpret_cast<const void*>(&gemm_skinny_mt2x_kernel<false, 2, 2>), MT2X_SMEM(2));
-    set(reinterpret_cast<const void*>(&gemm_skinny_mt2x_kernel<true, 1, 4>), MT2X_SMEM(4));
-    set(reinterpret_cast<const void*>(&gemm_skinny_mt2x_kernel<false, 1, 4>), MT2X_SMEM(4));
-    set(reinterpret_cast<const void*>(&gemm_skinny_mt2x_kernel<true, 2, 4>), MT2X_SMEM(4));
-    set(reinterpret_cast<const void*>(&gemm_skinny_mt2x_kernel<false, 2, 4>), MT2X_SMEM(4));
-    set(reinterpret_cast<const void*>(&gemm_skinny_mt2x_kernel<true, 3, 4>), MT2X_SMEM(4));
-    set(reinterpret_cast<const void*>(&gemm_skinny_mt2x_kernel<false, 3, 4>), MT2X_SMEM(4));
-    return r;
+
+// Every two-row-tile instantiation the library launches, named once: the attribute initialisation walks the table, the launcher looks its row up.
+// depth = k-steps per chunk of the ring form (gemm_skinny_mt2x_kernel, always 8 waves), waves per block of the register form.
+using Mt2Kernel = void (*)(const void*, const bf16_t*, int, int, int, SkinnyArgs);
+struct Mt2Entry { bool ring, fp8; int col_tiles, depth; Mt2Kernel kernel; size_t lds; };
+#define SV_MT2X_ROW(F, NT, CH) {true, F, NT, CH, gemm_skinny_mt2x_kernel<F, NT, CH>, mt2x_smem(CH)}
+#define SV_MT2_ROW(W, F, NT) {false, F, NT, W, gemm_skinny_mt2_kernel<W, F, NT>, mt2_smem(W)}
+static const Mt2Entry g_mt2_table[] = {
+    SV_MT2X_ROW(true, 1, 2), SV_MT2X_ROW(false, 1, 2), SV_MT2X_ROW(true, 2, 2), SV_MT2X_ROW(false, 2, 2),
+    SV_MT2X_ROW(true, 1, 4), SV_MT2X_ROW(false, 1, 4), SV_MT2X_ROW(true, 2, 4), SV_MT2X_ROW(false, 2, 4),
+    SV_MT2X_ROW(true, 3, 4), SV_MT2X_ROW(false, 3, 4),
+    SV_MT2_ROW(8, true, 1), SV_MT2_ROW(8, false, 1), SV_MT2_ROW(8, true, 2), SV_MT2_ROW(8, false, 2),
+    SV_MT2_ROW(8, true, 3), SV_MT2_ROW(8, false, 3), SV_MT2_ROW(4, true, 1), SV_MT2_ROW(4, false, 1),
+};
+#undef SV_MT2X_ROW
+#undef SV_MT2_ROW
+static const Mt2Entry* mt2_entry(bool ring, bool fp8, int col_tiles, int depth) {
+    for (const Mt2Entry& e : g_mt2_table)
+        if (e.ring == ring && e.fp8 == fp8 && e.col_tiles == col_tiles && e.depth == depth) return &e;
+    return nullptr;
 }
 // two-row-tile launch: false when the shape / mode is outside the kernel's scope (the caller falls back to one tile per block)
 static bool launch_gemm_skinny_mt2(const SkinnyArgs& a, hipStream_t st) {
@@ -2728,7 +2160,15 @@ static bool launch_gemm_skinny_mt2(const SkinnyArgs& a, hipStream_t st) {
     // the SAME number of waves (= the same per-wave k ranges and reduction order) as the one-tile kernel of this GEMM
     const int waves = a.Wq ? skinny_waves_fp8(KS, a.splitk) : skinny_waves(a.Npad, KS, a.splitk);
     const void* W = a.Wq ? (const void*)a.Wq : (const void*)a.Wp;
+    const bool f8 = a.Wq != nullptr;
     const int mode = g_mt2x.load(std::memory_order_relaxed);
+    // nt = the instantiation's column tiles per block, gx = blocks along the columns
+    auto launch = [&](bool ring, int nt, int depth, int gx) {
+        const Mt2Entry* e = mt2_entry(ring, f8, nt, depth);
+        if (!e) return false;
+        e->kernel<<<dim3(gx, a.splitk, a.MT / 2), (ring ? 8 : depth) * 64, e->lds, st>>>(W, a.xp, KS, per, n_tiles, a);
+        return true;
+    };
     if (waves == 8 && mode && per % 8 == 0 && (per / 8) % 2 == 0 && per / 8 >= 4) {
         // the LDS-ring form (gemm_skinny_mt2x_kernel).  Column tiles per block = the plan's (the engine's pick_decode_plan; 0: this launcher's
         // default).  Chunk depth: launches that fill 512 block slots take the two-blocks-per-CU form (CH = 2, <= 2 column tiles); the others
@@ -2742,47 +2182,16 @@ static bool launch_gemm_skinny_mt2(const SkinnyArgs& a, hipStream_t st) {
         if (mode == 2) ch = 2; else if (mode == 3) ch = deep_ok ? 4 : 2;
         else ch = (deep_ok && (ct >= 3 || (ct == 2 ? blocks2 : blocks1) < 512)) ? 4 : 2;
         if (ch == 2 && ct > 2) ct = 2;
-        const dim3 grid((n_tiles + ct - 1) / ct, a.splitk, a.MT / 2);
-#define SV_MT2X(F, N_, C_) gemm_skinny_mt2x_kernel<F, N_, C_><<<grid, 512, MT2X_SMEM(C_), st>>>(W, a.xp, KS, per, n_tiles, a)
-        const bool f8 = a.Wq != nullptr;
-        if (ch == 2) {
-            if (ct == 2) { if (f8) SV_MT2X(true, 2, 2); else SV_MT2X(false, 2, 2); }
-            else { if (f8) SV_MT2X(true, 1, 2); else SV_MT2X(false, 1, 2); }
-        } else {
-            if (ct == 3) { if (f8) SV_MT2X(true, 3, 4); else SV_MT2X(false, 3, 4); }
-            else if (ct == 2) { if (f8) SV_MT2X(true, 2, 4); else SV_MT2X(false, 2, 4); }
-            else { if (f8) SV_MT2X(true, 1, 4); else SV_MT2X(false, 1, 4); }
-        }
-#undef SV_MT2X
-        return true;
+        return launch(true, ct, ch, (n_tiles + ct - 1) / ct);
     }
     if (waves == 8) {
         // the engine picks (column tiles, split-K) together (engine_core.hip, pick_decode_plan); on its own (col_tiles = 0: the op-level
         // entry points) the launcher takes two column tiles when half the blocks still cover the chip
         const int ct = a.col_tiles ? a.col_tiles : g_op_col_tiles.load(std::memory_order_relaxed);
-        if (ct == 3) {
-            const dim3 grid((n_tiles + 2) / 3, a.splitk, a.MT / 2);
-            if (a.Wq) gemm_skinny_mt2_kernel<8, true, 3><<<grid, 512, 2 * 8 * 16 * 64 * 4, st>>>(W, a.xp, KS, per, n_tiles, a);
-            else gemm_skinny_mt2_kernel<8, false, 3><<<grid, 512, 2 * 8 * 16 * 64 * 4, st>>>(W, a.xp, KS, per, n_tiles, a);
-            return true;
-        }
-        if (ct == 2 || (ct == 0 && n_tiles * a.splitk >= 512)) {
-            const dim3 grid((n_tiles + 1) / 2, a.splitk, a.MT / 2);
-            if (a.Wq) gemm_skinny_mt2_kernel<8, true, 2><<<grid, 512, 2 * 8 * 16 * 64 * 4, st>>>(W, a.xp, KS, per, n_tiles, a);
-            else gemm_skinny_mt2_kernel<8, false, 2><<<grid, 512, 2 * 8 * 16 * 64 * 4, st>>>(W, a.xp, KS, per, n_tiles, a);
-            return true;
-        }
-        const dim3 grid(n_tiles, a.splitk, a.MT / 2);
-        if (a.Wq) gemm_skinny_mt2_kernel<8, true, 1><<<grid, 512, 2 * 8 * 16 * 64 * 4, st>>>(W, a.xp, KS, per, n_tiles, a);
-        else gemm_skinny_mt2_kernel<8, false, 1><<<grid, 512, 2 * 8 * 16 * 64 * 4, st>>>(W, a.xp, KS, per, n_tiles, a);
-        return true;
+        const int nt = ct == 3 ? 3 : (ct == 2 || (ct == 0 && n_tiles * a.splitk >= 512)) ? 2 : 1;
+        return launch(false, nt, 8, (n_tiles + nt - 1) / nt);
     }
-    if (waves == 4) {
-        const dim3 grid(n_tiles, a.splitk, a.MT / 2);
-        if (a.Wq) gemm_skinny_mt2_kernel<4, true, 1><<<grid, 256, 2 * 4 * 16 * 64 * 4, st>>>(W, a.xp, KS, per, n_tiles, a);
-        else gemm_skinny_mt2_kernel<4, false, 1><<<grid, 256, 2 * 4 * 16 * 64 * 4, st>>>(W, a.xp, KS, per, n_tiles, a);
-        return true;
-    }
+    if (waves == 4) return launch(false, 1, 4, n_tiles);
     return false;       // 16-wave (narrow outputs) and 1/2-wave (tiny K) shapes keep one row tile per block
 }
 
@@ -2796,24 +2205,33 @@ void skinny_plan(int Npad, int K, int splitk, int fp8, int MT, int* waves, int* 
 // false: outside the scope of the tail split (see gemm_skinny_tailsplit_kernel)
 static bool launch_skinny_tailsplit(const SkinnyArgs& a, hipStream_t st) {
     // off by default: the bit-identical split ties with the one launch (profiles/tailsplit_r06_ab.log); SV_TAILSPLIT=1 = on
-    // (read per call: A/B in one process; a captured graph keeps its choice)
-    const char* ev = getenv("SV_TAILSPLIT");
-    if (!ev || !atoi(ev) || !a.tail_ws || !a.tail_cnt) return false;
+    if (!env_switch("SV_TAILSPLIT", 0) || !a.tail_ws || !a.tail_cnt) return false;
     if (a.out_mode != SK_OUT_PACKED_ACT || a.MT != 1 || a.Wq || a.fold_c1 || a.splitk != 1) return false;
     const int KS = a.K / 16, n_tiles = a.Npad / 32;
     if (KS != 8 * 36 || skinny_waves(a.Npad, KS, 1) != 8) return false;      // the one instantiation: the one-tile kernel's 8 ranges of 36 k-steps (K = 4608)
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0; hipDeviceProp_t pr;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return false;
-        cus = pr.multiProcessorCount;
-    }
+    const int cus = device_cus();
+    if (!cus) return false;
     const int slots = 2 * cus, T = n_tiles - slots;           // two 8-wave blocks of the ordinary kernel per CU
     if (T <= 0 || T > SV_TAIL_TILES || 4 * T > slots) return false;
     gemm_skinny_kernel<8, false><<<dim3(slots, 1, 1), 512, skinny_smem(8), st>>>(a.Wp, a.xp, KS, KS, 0, a);
     gemm_skinny_tailsplit_kernel<36><<<4 * T, 128, 0, st>>>(a.Wp, a.xp, KS, slots, 0, a);
     g_tailsplit_launches.fetch_add(1, std::memory_order_relaxed);
     return true;
+}
+
+// hipFuncSetAttribute for the kernels whose dynamic LDS is above the default limit (0 = ok)
+int init_gemm_kernels() {
+    int r = 0;
+    auto set = [&](const void* f, size_t bytes) { if (!r) r = (int)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
+    // 16-wave blocks reduce through 64 KiB of LDS
+    set(reinterpret_cast<const void*>(&gemm_skinny_kernel<16, false>), 96 * 1024);
+    set(reinterpret_cast<const void*>(&gemm_skinny_kernel<16, true>), 96 * 1024);
+    set(reinterpret_cast<const void*>(&gemm_skinny_kernel<16, false, true>), 96 * 1024);
+    for (const Mt2Entry& e : g_mt2_table) set(reinterpret_cast<const void*>(e.kernel), e.lds);
+    set(reinterpret_cast<const void*>(&gemm_head_persist_kernel<2>), head_persist_smem(2));
+    set(reinterpret_cast<const void*>(&gemm256_kernel<bf16_t>), 2 * G2_BUF);
+    set(reinterpret_cast<const void*>(&gemm256_kernel<float>), 2 * G2_BUF);
+    return r;
 }
 
 void launch_gemm_skinny(const SkinnyArgs& a, hipStream_t st) {
@@ -2829,19 +2247,6 @@ void launch_gemm_skinny(const SkinnyArgs& a, hipStream_t st) {
         case 2: launch_sk<2>(a, grid, st); break;
         default: launch_sk<1>(a, grid, st); break;
     }
-}
-
-// f32 -> bf16 through the hardware convert every epilogue uses (test surface)
-__global__ void cvt_bf16_hw_kernel(const float* __restrict__ x, bf16_t* __restrict__ y, size_t n) {
-    const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 2;
-    if (i + 1 < n) {
-        *reinterpret_cast<uint32_t*>(y + i) = cvt_pk_bf16(x[i], x[i + 1]);
-    } else if (i < n) {
-        y[i] = (bf16_t)(cvt_pk_bf16(x[i], 0.f) & 0xffffu);
-    }
-}
-void launch_cvt_bf16_hw(const float* x, bf16_t* y, size_t n, hipStream_t st) {
-    cvt_bf16_hw_kernel<<<(unsigned)((n / 2 + 256) / 256), 256, 0, st>>>(x, y, n);
 }
 
 }  // namespace sv

@@ -68,7 +68,7 @@ void launch_gemm_fixed(const GemmArgs& a, int kernel256, int peel, hipStream_t s
 int get_mt2x();
 void set_mt2x(int on);                // (sv_debug_set_skinny_form / sv_debug_skinny_form) 33..64-row decode GEMMs: 1 = activations through a wave-private LDS ring (gemm_skinny_mt2x_kernel, default), 0 = both operands in registers
 long long tailsplit_launches();        // host-side count of gemm_skinny_tailsplit_kernel launches since load (sv_debug_tailsplit_launches)
-void set_gemm_form(int form);         // -1: tuned (default); 0 / 1: every big-M launch takes that form, rows not peeled
+void set_gemm_form(int form);         // -1: tuned (default); 0 / 1: every big-M launch takes that form, rows not peeled; 2: 256^2 + the remainder peeled; 3: every row through the one-wave-per-tile kernel
 // what launch_gemm decides for a shape (host arithmetic only; tail_on: 0 never peel, 1 cost model, 2 always)
 struct GemmPlan { int peel, tail_rows, tail_by_tiles, main_256; double est_us; };
 GemmPlan gemm_plan(int M, int N, int K, int act, int tail_on);
@@ -137,7 +137,7 @@ int init_gemm_kernels();        // hipFuncSetAttribute for the large-LDS variant
 
 void launch_cvt_bf16_hw(const float* x, bf16_t* y, size_t n, hipStream_t st);
 
-// ---- the MLP half of a decode layer as one launch (gemm.hip: mlp_fused_kernel; round-4 experiment, SV_EXP_MLP_FUSED_FORCE) ----
+// ---- the MLP half of a decode layer as one launch (mlp_fused.hip: mlp_fused_kernel; round-4 experiment, SV_EXP_MLP_FUSED_FORCE) ----
 struct MlpFusedArgs {
     const bf16_t* W1; const bf16_t* x1;      // folded c_fc image W' [N1pad/32][K1/16][64][8], raw residual stream in fragment order
     int N1, N1pad, K1;

@@ -271,7 +271,7 @@ void launch_row_update_ln(const RowUpdateArgs& a, hipStream_t st) {
 //   Two launches today: row_update_ln_kernel (32 blocks: slabs + bias + residual -> h, LayerNorm -> xp; 4.95 us, a chain of latencies
 //   that touches ~1 MB) and gemm_skinny_kernel<8, false> (288 blocks: 9.4 MB of c_attn weights -> 4 fp32 slabs; 5.2 us of which ~1.3 us
 //   stream) with a kernel boundary between them: 10.2 us per layer, 24 % of the decode step, nearly all of it latency.
-//   What round 4 learned about hand-offs inside a launch (gemm.hip, mlp_fused_kernel): the price sits in the CONSUMER CU's own memory
+//   What round 4 learned about hand-offs inside a launch (mlp_fused.hip, mlp_fused_kernel): the price sits in the CONSUMER CU's own memory
 //   queue, and polls must not queue behind weight requests.  This pair is the favourable case: a c_attn block's WHOLE weight share is
 //   4 KiB per wave (K slice 512 = 4 k-steps per wave), so it is requested at t = 0, has landed long before the row update publishes,
 //   and from then on the consumer's queue holds nothing but its polls; the producers are 32 blocks that start first.

@@ -1202,8 +1202,9 @@ def op_linear(x, W, bias=None, residual=None, act="none", out_f32=False):
 
 def set_gemm_form(form: int) -> None:
     """-1: the tuned choice (default); 0 / 1: every big-M GEMM launch of the process takes 128^2 tiles / 256^2 tiles, rows not peeled;
-    2: 256^2 tiles + the row remainder through the tail kernel (sv_debug_set_gemm_form).
-    Same bits every way; test and A/B surface."""
+    2: 256^2 tiles + the row remainder through the tail kernel; 3: every row through the one-wave-per-tile kernel (with a sequence
+    structure: the rows a sequence leaves over its tiles through the split-K remainder kernel as in every form)
+    (sv_debug_set_gemm_form).  Same bits every way; test and A/B surface."""
     check(_lib.load().sv_debug_set_gemm_form(int(form)))
 
 

@@ -2,7 +2,7 @@
 quantiser's two images and float64 restatements of the fp8-weight Linears.  torch only (importable without the engine, runs on any
 device); pinned by itself on the CPU in tests/test_fp8_ops_host.py.
 
-Weight-only quantisation as sv_load_weight does it (csrc/gemm.hip fp8_row_scale_kernel / pack_weight_fp8_kernel): one scale per
+Weight-only quantisation as sv_load_weight does it (csrc/gemm_pack.hip fp8_row_scale_kernel / pack_weight_fp8_kernel): one scale per
 output row, scale[n] = max_k |W[n][k]| / 448 (1 for an all-zero row), q = e4m3_rne(W / scale) with the division in float32."""
 import torch
 

@@ -205,8 +205,8 @@ def test_argument_validation_precedes_any_device_work(lib):
     assert lib.sv_op_pack_weight_fp8(p, 0, 0, 64, p, p, p, None) == -22
     assert lib.sv_op_pack_weight_fp8(p, 1, 33, 64, p, None, p, None) == -22 and lib.sv_op_pack_weight_fp8(p, 1, 33, 64, None, p, p, None) == -22
     # the measurement / A-B surfaces validate before they touch the device as well
-    assert lib.sv_debug_set_gemm_form(3) == -22 and lib.sv_debug_set_gemm_form(-2) == -22
-    assert lib.sv_debug_set_gemm_form(1) == 0 and lib.sv_debug_set_gemm_form(-1) == 0
+    assert lib.sv_debug_set_gemm_form(4) == -22 and lib.sv_debug_set_gemm_form(-2) == -22
+    assert lib.sv_debug_set_gemm_form(1) == 0 and lib.sv_debug_set_gemm_form(3) == 0 and lib.sv_debug_set_gemm_form(-1) == 0
     assert lib.sv_debug_set_linear_seq_rows(-70000) == -22 and lib.sv_debug_set_linear_seq_rows(259) == 0 and lib.sv_debug_set_linear_seq_rows(0) == 0
     buf = (C.c_int64 * 16)()
     assert lib.sv_debug_gemm_trace(100, 256, 256, 0, 1, buf, 1) == -22            # M < one tile

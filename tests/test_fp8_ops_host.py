@@ -62,7 +62,7 @@ def test_designed_rows_have_power_of_two_scales_and_bite(K):
 
 
 def _kernel_maps(Npad, K):
-    """The thread maps of pack_weight_kernel / pack_weight_fp8_kernel as loops, element by element (csrc/gemm.hip)."""
+    """The thread maps of pack_weight_kernel / pack_weight_fp8_kernel as loops, element by element (csrc/gemm_pack.hip)."""
     KS = K // 16
     wp = torch.empty(Npad, K, dtype=torch.long)
     wq = torch.empty(Npad, K, dtype=torch.long)

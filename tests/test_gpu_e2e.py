@@ -1048,7 +1048,7 @@ def test_from_pretrained_reference_format_directory_matches_hf_generate(tmp_path
 
 
 def test_fused_mlp_launch_equals_the_two_launches_bit_for_bit():
-    """Round-4 experiment (SV_EXP bit 128, gemm.hip mlp_fused_kernel): c_fc + GELU + down projection of a decode layer as ONE launch of
+    """Round-4 experiment (SV_EXP bit 128, mlp_fused.hip mlp_fused_kernel): c_fc + GELU + down projection of a decode layer as ONE launch of
     256 co-resident blocks with an in-launch hand-off (write-through stores, one ticket per K slice, bounded polling).  Per-wave k
     ranges, MFMA order, reduction order and epilogues are those of the two kernels it replaces, so logits and tokens must be IDENTICAL
     bit for bit -- at BASELINE config 2's size (the geometry it is built for), eager and under the hipGraph loop."""

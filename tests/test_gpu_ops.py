@@ -216,6 +216,45 @@ def test_linear_rows_a_sequence_leaves_over_its_tiles(B, S, N, K, act, res):
     print(f"[seq remainder] B={B} S={S} N={N} K={K}: per-sequence form {'ON' if form else 'off'}, {B * rem} remainder rows")
 
 
+@pytest.mark.parametrize("B,S,N,K,act,seq", [(1, 130, 72, 192, "gelu_tanh", False),     # four full 32-row tiles + 2 rows, ragged columns, 3 K-tiles
+                                             (2, 258, 1024, 1024, "none", True)])      # per sequence: 256 rows by the tail kernel + 2 by gemm_tailk_kernel
+def test_linear_every_row_through_the_one_wave_per_tile_kernel_is_bitwise_the_tile_kernel(B, S, N, K, act, seq):
+    """Form 3 of sv_debug_set_gemm_form sends every row through launch_gemm_rows_by_tail -- the form the few-hundred-row tuner may
+    pick by its timing, here chosen on purpose: gemm_tail_kernel over all rows, or with the sequence structure over the full 256-row
+    tiles' rows of every sequence with gemm_tailk_kernel on the rows a sequence leaves over.  Bit for bit the 128^2 tile kernel
+    (form 0: same MFMA, operand roles and ascending k; the same remainder kernel), within one rounding pair of the fp32 reference,
+    and a sequence's rows do not depend on the batch around it."""
+    g = torch.Generator().manual_seed(B + S + N + K)
+    M = B * S
+    x = torch.randn(M, K, generator=g).bfloat16()
+    W = (torch.randn(N, K, generator=g) / K ** 0.5).bfloat16()
+    b = (0.1 * torch.randn(N, generator=g)).bfloat16()
+    r = torch.randn(M, N, generator=g).bfloat16()
+    if seq:
+        assert E.gemm_seq_form(S, N, K, act)
+    outs = {}
+    try:
+        E.set_linear_seq_rows(S if seq else 0)
+        for form in (0, 3):
+            E.set_gemm_form(form)
+            outs[form] = E.op_linear(bf(x), bf(W), bf(b), bf(r), act=act).cpu()
+        if seq:
+            y1 = E.op_linear(bf(x[:S].contiguous()), bf(W), bf(b), bf(r[:S].contiguous()), act=act).cpu()      # the first sequence alone, form 3
+    finally:
+        E.set_gemm_form(-1)
+        E.set_linear_seq_rows(0)
+    assert torch.equal(outs[3].view(torch.int16), outs[0].view(torch.int16))
+    ref = x.float() @ W.float().T + b.float()
+    if act != "none":
+        ref = torch.nn.functional.gelu(ref.bfloat16().float(), approximate="tanh")
+    ref = ref.bfloat16().float() + r.float()
+    err = rel_err(outs[3], ref)
+    print(f"[rows by tail] B={B} S={S} N={N} K={K} seq={seq}: rel err {err:.3e} (bound {2.2 * BF16_1ULP:.3e})")
+    assert err <= 2.2 * BF16_1ULP
+    if seq:
+        assert torch.equal(y1.view(torch.int16), outs[3][:S].view(torch.int16))
+
+
 def test_linear_transpose_detecting():
     """A = identity with an ASYMMETRIC weight: catches swapped row/column in the MFMA C layout."""
     K = N = 128

@@ -76,7 +76,7 @@ def _free_run_check(got, o_toks, margin, band, tag):
 @pytest.mark.parametrize("exclusive_device", [False, True])
 def test_config2_batch32_against_gpu_oracle(exclusive_device):
     """BASELINE config 2 as the bench runs it: 32 images, StarVector-1B, bf16, greedy.  exclusive_device = True is the engine
-    configuration bench.py builds (the MLP half of a layer as one launch, gemm.hip mlp_fused_kernel): it meets the oracle here
+    configuration bench.py builds (the MLP half of a layer as one launch, mlp_fused.hip mlp_fused_kernel): it meets the oracle here
     first-hand, not only through its bit-identity with the two-launch layer (tests/test_gpu_e2e.py)."""
     cfg = dataclasses.replace(O.OracleConfig(), eos_token_id=-1)
     w = O.make_weights(cfg, seed=1234)

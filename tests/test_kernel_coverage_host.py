@@ -83,25 +83,29 @@ COVERAGE = {
     # ---- fork.hip
     "fork_tail_copy_kernel": _FORK,                                       # (engine)
     "fork_logits_kernel": _FORK,                                          # (engine)
-    # ---- gemm.hip
+    # ---- gemm_pack.hip
     "pack_weight_kernel": (OPS + "test_linear_mfma", OPS + "test_linear_transpose_detecting"),
     "convert_bf16_kernel": (E2E + "test_against_reference_goldens",),     # (engine) sv_load_weight
     "fp8_row_scale_kernel": _FP8_QUANT + ("test_gpu_fp8.py::test_fp8_skinny_gemm_matches_torch_fake_quant",),
     "pack_weight_fp8_kernel": _FP8_QUANT + ("test_gpu_fp8.py::test_fp8_skinny_gemm_matches_torch_fake_quant",),
-    "gemm_skinny_fp8_kernel": _FP8_DECODE + ("test_gpu_fp8.py::test_fp8_skinny_gemm_matches_torch_fake_quant",),
+    "cvt_bf16_hw_kernel": (OPS + "test_bf16_rounding_is_rne",),
+    # ---- gemm.hip
     "gemm_bf16_kernel": _BIG_M + _FP8_BIG_M,
     "gemm256_kernel": _BIG_M + _FP8_BIG_M,
-    "gemm_tail_kernel": (OPS + "test_remainder_row_kernels_agree_with_the_tile_kernels_bitwise",) + _BIG_M + _FP8_BIG_M[:1],
+    "gemm_tail_kernel": (OPS + "test_remainder_row_kernels_agree_with_the_tile_kernels_bitwise",) + _BIG_M + _FP8_BIG_M[:1] +
+                        (OPS + "test_linear_every_row_through_the_one_wave_per_tile_kernel_is_bitwise_the_tile_kernel",),
     "gemm_tailk_kernel": (OPS + "test_linear_rows_a_sequence_leaves_over_its_tiles",
-                          FP8 + "test_big_m_rows_a_sequence_leaves_over_its_tiles_with_the_column_scale"),
+                          FP8 + "test_big_m_rows_a_sequence_leaves_over_its_tiles_with_the_column_scale",
+                          OPS + "test_linear_every_row_through_the_one_wave_per_tile_kernel_is_bitwise_the_tile_kernel"),
     "gemm_skinny_kernel": _SKINNY,
+    "gemm_skinny_fp8_kernel": _FP8_DECODE + ("test_gpu_fp8.py::test_fp8_skinny_gemm_matches_torch_fake_quant",),
     "gemm_head_persist_kernel": (OPS + "test_lm_head_persistent_blocks_bit_identical_to_one_tile_blocks", OPS + "test_lm_head_persistent_blocks_two_row_tiles",
                                  OPS + "test_lm_head_with_folded_greedy_selection"),
     "gemm_skinny_tailsplit_kernel": (OPS + "test_linear_skinny_tail_split_gives_the_one_launch_bits",) + _SKINNY,
     "gemm_skinny_mt2_kernel": (OPS + "test_linear_skinny_two_row_tiles_per_block_is_bitwise_the_one_tile_kernel",) + _SKINNY + _FP8_DECODE,
     "gemm_skinny_mt2x_kernel": (OPS + "test_linear_skinny_two_row_tiles_per_block_is_bitwise_the_one_tile_kernel",) + _SKINNY + _FP8_DECODE,
+    # ---- mlp_fused.hip
     "mlp_fused_kernel": (E2E + "test_fused_mlp_launch_equals_the_two_launches_bit_for_bit",) + _SKINNY,
-    "cvt_bf16_hw_kernel": (OPS + "test_bf16_rounding_is_rne",),
     # ---- preprocess.hip
     "pp_tables_kernel": _PREPROCESS,
     "pp_horizontal_kernel": _PREPROCESS,
