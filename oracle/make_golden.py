@@ -612,7 +612,7 @@ def run_padding_case():
     """Padded prompts (text2svg with captions of different lengths): HF masks the padded keys and numbers positions by
     cumsum(attention_mask), so generating a padded batch equals generating every row alone with its padding removed --
     for left padding (the v2 tokenizer, llm/starcoder2.py:53), for right padding before the trigger token (the v1 default),
-    GPTBigCode and StarCoder2.  The mirror relies on this to serve padded batches group by group (model.py::_generate_padded)."""
+    GPTBigCode and StarCoder2.  The mirror relies on this to serve padded batches group by group (model.py::_route_padded)."""
     def run(lm, wte, cfg, side):
         lens, n_new = [5, 9, 7], 10
         S, B = max(lens) + 1, len(lens)

@@ -330,6 +330,40 @@ class HipEngine:
             raise ValueError(f"lengths {lens} do not describe the {x.shape[0]} packed rows (each >= 1)")
         return x, (C.c_int32 * len(lens))(*lens), lens
 
+    def _prompt_form(self, embeds, lengths=None):
+        """The prompts of a generate call as (x, ctypes lengths or None, B, S0): a rectangular [B, S0, D] tensor (lengths None), or the ragged
+        form -- a packed [sum(lengths), D] tensor with `lengths`, or a list of [S_i, D] tensors -- where S0 is the longest prompt."""
+        if lengths is not None or isinstance(embeds, (list, tuple)):
+            x, lens_arr, lens = self._packed(embeds, lengths)
+            B, S0, D = len(lens), max(lens), x.shape[1]
+        else:
+            x, lens_arr = _need(embeds, torch.bfloat16, "inputs_embeds"), None
+            B, S0, D = x.shape
+        if D != self.cfg.hidden:
+            raise ValueError("inputs_embeds hidden size mismatch")
+        return x, lens_arr, B, S0
+
+    @staticmethod
+    def _sampling(max_length, S0, stop_ids, on_tokens, *, do_sample, temperature, top_p, eos_token_id, pad_token_id, seed, sync_every,
+                  repetition_penalty, num_beams=1, length_penalty=1.0, early_stopping=False, top_k=0, min_new_tokens=0):
+        """The sv_sampling of a generate call after its budget check: (struct, max_new, what its pointers refer to -- the stop-id array and
+        the streaming callback: keep it alive for the duration of the call --, the list that receives the callback's exception)."""
+        max_new = max_length - S0
+        if max_new <= 0:
+            raise ValueError(f"max_length ({max_length}) must exceed the prompt length ({S0})")
+        stops = list(stop_ids) if stop_ids else []
+        arr = (C.c_int32 * max(len(stops), 1))(*stops) if stops else None
+        sp = SvSampling(int(bool(do_sample)), float(temperature), float(top_p), int(max_length), int(eos_token_id),
+                        int(pad_token_id), len(stops), C.cast(arr, C.POINTER(C.c_int32)) if stops else None,
+                        int(seed) & 0xFFFFFFFFFFFFFFFF, int(sync_every), float(repetition_penalty),
+                        int(num_beams), float(length_penalty), _early_code(early_stopping), int(top_k or 0), None, None,
+                        max(int(min_new_tokens or 0), 0))
+        cb, cb_errors = None, []
+        if on_tokens is not None:
+            cb, cb_errors = token_callback(on_tokens)
+            sp.on_tokens = C.cast(cb, C.c_void_p)
+        return sp, max_new, (arr, cb), cb_errors
+
     def prefill_ragged(self, embeds, lengths=None) -> torch.Tensor:
         """One prompt pass over sequences of different lengths (sv_prefill_ragged): `embeds` a list of [S_i, D] tensors, or a packed
         [sum(lengths), D] tensor with `lengths`.  Returns the last-row logits [B, vocab]; every row's logits and KV entries are the bits
@@ -342,8 +376,7 @@ class HipEngine:
     def generate_ragged(self, embeds, max_length: int, lengths=None, **kw):
         """`generate` over prompts of different lengths in ONE prompt pass (sv_generate_ragged): HF's padded-batch semantics, `max_length`
         counts from the longest prompt, every row gets max_length - max(lengths) new tokens.  Same keywords and return value as `generate`."""
-        x, _arr, lens = self._packed(embeds, lengths)
-        return self.generate(x, max_length, lengths=lens, **kw)
+        return self.generate(embeds if lengths is not None else list(embeds), max_length, lengths=lengths, **kw)
 
     def generate_shared(self, embeds, max_length: int, n_samples: int, lengths=None, **kw):
         """``n_samples`` continuations of every prompt from ONE prompt pass over the un-repeated prompts (sv_generate_shared): ``embeds`` is
@@ -351,10 +384,7 @@ class HipEngine:
         B * n_samples rows, row b * n_samples + j = sample j of prompt b -- bit for bit what ``generate`` / ``generate_ragged`` return for
         the prompts repeated with ``repeat_interleave(n_samples, dim=0)``; the rows of a prompt share its full KV pages.  Same keywords and
         return value as ``generate``."""
-        if lengths is not None or isinstance(embeds, (list, tuple)):
-            x, _arr, lens = self._packed(embeds, lengths)
-            return self.generate(x, max_length, lengths=lens, n_samples=n_samples, **kw)
-        return self.generate(embeds, max_length, n_samples=n_samples, **kw)
+        return self.generate(embeds, max_length, lengths=lengths, n_samples=n_samples, **kw)
 
     def generate_processed(self, embeds, max_length: int, no_repeat_ngram_size: int = 0, bad_words_ids=None, min_p: float = 0.0,
                            lengths=None, n_samples: int = 1, **kw):
@@ -364,10 +394,7 @@ class HipEngine:
         (``lengths``, ``n_samples``); same keywords and return value.  All three off: exactly ``generate``'s tokens.  ValueError beyond the
         limits or with num_beams > 1."""
         lp = logits_processors(no_repeat_ngram_size, bad_words_ids, min_p, vocab=self.cfg.vocab)
-        if lengths is not None or isinstance(embeds, (list, tuple)):
-            x, _arr, lens = self._packed(embeds, lengths)
-            return self.generate(x, max_length, lengths=lens, n_samples=n_samples, logits_processors=lp, **kw)
-        return self.generate(embeds, max_length, n_samples=n_samples, logits_processors=lp, **kw)
+        return self.generate(embeds, max_length, lengths=lengths, n_samples=n_samples, logits_processors=lp, **kw)
 
     def generate_lookup(self, embeds, max_length: int, num_draft_tokens: int, max_ngram: int = 0, min_ngram: int = 0, lengths=None,
                         eos_token_id: int = 0, pad_token_id: int = 0, stop_ids: Optional[Sequence[int]] = None, sync_every: int = 0,
@@ -421,27 +448,11 @@ class HipEngine:
     def _lookup_call(self, entry, embeds, max_length, num_draft_tokens, max_ngram, min_ngram, lengths, eos_token_id, pad_token_id, stop_ids,
                      sync_every, on_tokens, min_new_tokens, return_counts, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0,
                      repetition_penalty=1.0):
-        lens_arr = None
-        if lengths is not None or isinstance(embeds, (list, tuple)):
-            x, lens_arr, lens = self._packed(embeds, lengths)
-            B, S0, D = len(lens), max(lens), x.shape[1]
-        else:
-            x = _need(embeds, torch.bfloat16, "inputs_embeds")
-            B, S0, D = x.shape
-        if D != self.cfg.hidden:
-            raise ValueError("inputs_embeds hidden size mismatch")
-        max_new = max_length - S0
-        if max_new <= 0:
-            raise ValueError(f"max_length ({max_length}) must exceed the prompt length ({S0})")
-        stops = list(stop_ids) if stop_ids else []
-        arr = (C.c_int32 * max(len(stops), 1))(*stops) if stops else None
-        sp = SvSampling(1 if do_sample else 0, temperature, top_p, int(max_length), int(eos_token_id), int(pad_token_id), len(stops),
-                        C.cast(arr, C.POINTER(C.c_int32)) if stops else None, seed & (2 ** 64 - 1), int(sync_every), repetition_penalty, 1, 1.0, 0,
-                        top_k, None, None, max(int(min_new_tokens or 0), 0))
-        cb, cb_errors = None, []
-        if on_tokens is not None:
-            cb, cb_errors = token_callback(on_tokens)
-            sp.on_tokens = C.cast(cb, C.c_void_p)
+        x, lens_arr, B, S0 = self._prompt_form(embeds, lengths)
+        sp, max_new, _keep, cb_errors = self._sampling(
+            max_length, S0, stop_ids, on_tokens, do_sample=do_sample, temperature=temperature, top_p=top_p, eos_token_id=eos_token_id,
+            pad_token_id=pad_token_id, seed=seed, sync_every=sync_every, repetition_penalty=repetition_penalty, top_k=top_k,
+            min_new_tokens=min_new_tokens)
         lk = _lib.SvLookup(int(num_draft_tokens), int(max_ngram), int(min_ngram))
         out = torch.empty(B, max_new, dtype=torch.int64, device=x.device)
         n, counts = C.c_int32(0), (C.c_int32 * 3)()
@@ -604,15 +615,7 @@ class HipEngine:
             tk_req = token_topk_request(token_topk)
             if int(num_beams) > 1:
                 raise ValueError("token_topk with num_beams > 1 is not built (beam search reports sequences_scores; beam rows reorder)")
-        lens_arr = None
-        if lengths is not None:
-            x, lens_arr, lens = self._packed(inputs_embeds, lengths)
-            B, S0, D = len(lens), max(lens), x.shape[1]
-        else:
-            x = _need(inputs_embeds, torch.bfloat16, "inputs_embeds")
-            B, S0, D = x.shape
-        if D != self.cfg.hidden:
-            raise ValueError("inputs_embeds hidden size mismatch")
+        x, lens_arr, B, S0 = self._prompt_form(inputs_embeds, lengths)
         G = int(n_samples)
         if G < 1:
             raise ValueError(f"n_samples must be >= 1, got {n_samples}")
@@ -628,20 +631,10 @@ class HipEngine:
             raise NotImplementedError("n_samples > 1 under beam search (num_beams > 1) is not built")
         if G > 1:
             n_prompts, B = B, B * G                     # B: the decode rows from here on
-        max_new = max_length - S0
-        if max_new <= 0:
-            raise ValueError(f"max_length ({max_length}) must exceed the prompt length ({S0})")
-        stops = list(stop_ids) if stop_ids else []
-        arr = (C.c_int32 * max(len(stops), 1))(*stops) if stops else None
-        sp = SvSampling(int(bool(do_sample)), float(temperature), float(top_p), int(max_length), int(eos_token_id),
-                        int(pad_token_id), len(stops), C.cast(arr, C.POINTER(C.c_int32)) if stops else None,
-                        int(seed) & 0xFFFFFFFFFFFFFFFF, int(sync_every), float(repetition_penalty),
-                        int(num_beams), float(length_penalty), _early_code(early_stopping), int(top_k or 0), None, None,
-                        max(int(min_new_tokens or 0), 0))
-        cb, cb_errors = None, []
-        if on_tokens is not None:
-            cb, cb_errors = token_callback(on_tokens)          # keep a reference alive for the duration of the call
-            sp.on_tokens = C.cast(cb, C.c_void_p)
+        sp, max_new, _keep, cb_errors = self._sampling(
+            max_length, S0, stop_ids, on_tokens, do_sample=do_sample, temperature=temperature, top_p=top_p, eos_token_id=eos_token_id,
+            pad_token_id=pad_token_id, seed=seed, sync_every=sync_every, repetition_penalty=repetition_penalty, num_beams=num_beams,
+            length_penalty=length_penalty, early_stopping=early_stopping, top_k=top_k, min_new_tokens=min_new_tokens)
         out = torch.empty(B, max_new, dtype=torch.int64, device=x.device)
         n = C.c_int32(0)
         # a call that asks for nothing beyond the tokens passes no sv_generate_outputs (and takes no beam-search host buffers)

@@ -19,6 +19,7 @@ from __future__ import annotations
 import json
 import os
 import contextlib
+import dataclasses
 import functools
 import numbers
 import threading
@@ -36,6 +37,29 @@ _EXCLUSIVE = threading.local()
 
 def _in_exclusive_job() -> bool:
     return bool(getattr(_EXCLUSIVE, "active", False))
+
+
+def _exclusive(batcher, fn):
+    """`fn()` as an exclusive job of `batcher`: requests share the engine, the job runs with the engine to itself, in turn (FIFO with
+    the generation requests).  The flag is thread-local: only the scheduler thread running the job sees it."""
+    def job():
+        _EXCLUSIVE.active = True
+        try:
+            return fn()
+        finally:
+            _EXCLUSIVE.active = False
+    return batcher.run_exclusive(job)
+
+
+def _call_lock(engine):
+    """The lock one engine call (or one cb_reset .. cb_reset sequence) holds; engines without one take none."""
+    return getattr(engine, "call_lock", None) or contextlib.nullcontext()
+
+
+def _is_padded(mask) -> bool:
+    """Whether an attention mask marks any padding.  Reading it is a device round trip when the mask lives on the GPU: ask once per call."""
+    return mask is not None and not bool((mask == 1).all())
+
 
 class _GenerateOutput(dict):
     """Stand-in for transformers' Generate*DecoderOnlyOutput when transformers is not importable: the same field names, read as
@@ -441,6 +465,103 @@ class _Backbone(_EngineModule):
         self.embed_tokens = self.wte
 
 
+@dataclasses.dataclass(frozen=True)
+class _GenRequest:
+    """One `HipCausalLM.generate` call after its defaults are resolved and its refusals have passed: what the routes read instead of loose
+    arguments.  A length group of a padded batch runs on a copy (`dataclasses.replace`) with its own lengths and stop."""
+    # the sampling parameters, as the engine takes them
+    do_sample: bool
+    temperature: float
+    top_p: float
+    top_k: int
+    repetition_penalty: float
+    length_penalty: float
+    num_beams: int
+    early_stopping: object             # False | True | "never", handed on as given
+    eos: int
+    pad: int
+    stopping_criteria: object          # resolved by `stop`, where the route first needs it: an unsupported criterion raises there, as before
+    seed: int                          # at most one draw per public call: sub-calls and the exclusive job reuse it
+    max_length: int
+    min_length: int
+    padded: bool                       # the mask has pads (read once)
+    G: int                             # samples per prompt of the shared form (1: inputs_embeds holds one row per returned row)
+    n_return: int                      # num_return_sequences as asked (repeated into the rows where the shared form is not taken)
+    # what the call asked for
+    return_dict: bool
+    output_scores: bool
+    output_logits: bool
+    stats: object                      # False, True or the tuple of statistics names (output_token_logprobs, with return_dict)
+    topk: Optional[dict]               # dict(k=, source=) of output_top_logprobs
+    proc: dict                         # the keywords of HipEngine.generate_processed, {} when no processor is set
+    lookup: Optional[tuple]            # (prompt_lookup_num_tokens, max_matching_ngram_size, prompt_lookup_sampling)
+    streamer: object
+
+    @property
+    def want(self) -> bool:            # the [steps, rows, vocab] slabs (without return_dict HF ignores both arguments)
+        return self.return_dict and bool(self.output_scores or self.output_logits)
+
+    @functools.cached_property
+    def stop(self) -> Optional[List[int]]:
+        return HipCausalLM._stop_ids(self.stopping_criteria)
+
+    def min_new(self, prompt_len: int) -> int:
+        # HF (_prepare_generated_length): with inputs_embeds min_length is reduced by the prompt length -- 0 on the im2svg path
+        # (SURVEY.md 8a-a11), positive only for a text2svg caption shorter than min_length; MinLengthLogitsProcessor then
+        # keeps EOS at -inf for that many new tokens (in beam search HF applies it to the log-probabilities: so does the scorer).
+        return max(self.min_length - prompt_len, 0)
+
+    def engine_kw(self, min_new: int, on_tokens=None, sync_every: Optional[int] = None) -> dict:
+        """The keywords of the engine's `generate` family.  `sync_every` (and with it `on_tokens`) goes down on the routes that stream;
+        `min_new_tokens` only when non-zero."""
+        kw = dict(do_sample=self.do_sample, temperature=self.temperature, top_p=self.top_p, eos_token_id=self.eos, pad_token_id=self.pad,
+                  stop_ids=self.stop, seed=self.seed, repetition_penalty=self.repetition_penalty, num_beams=self.num_beams,
+                  length_penalty=self.length_penalty, early_stopping=self.early_stopping, top_k=self.top_k)
+        if sync_every is not None:
+            kw.update(on_tokens=on_tokens, sync_every=sync_every)
+        if min_new:
+            kw["min_new_tokens"] = min_new
+        return kw
+
+    def cb_request(self, budget: int, min_new: int, row: int = 0) -> dict:
+        """The request dict of `HipEngine.cb_admit` / `ContinuousBatcher.generate` for row `row` of the call: its own seed (the golden-ratio
+        stride, the seeds of the length-group route: same tokens), and the stop sequence on row 0 alone (the reference's stop looks at row 0)."""
+        return dict(max_new_tokens=budget, do_sample=self.do_sample, eos_token_id=self.eos, pad_token_id=self.pad, temperature=self.temperature,
+                    top_p=self.top_p, top_k=self.top_k, repetition_penalty=self.repetition_penalty, min_new_tokens=min_new,
+                    seed=(self.seed + 0x9E3779B97F4A7C15 * row) & (2 ** 63 - 1), stop_ids=self.stop if row == 0 else None)
+
+
+# What is not built, per thing asked for: (asked, the condition it meets, exception, message), walked in this order by `_refuse`.
+_NOT_BUILT = (
+    ("attentions", "always", NotImplementedError, "output_attentions / output_hidden_states are not built: the decode step keeps neither"),
+    ("slabs", "padded", NotImplementedError, "output_scores / output_logits with a padded attention_mask are not built: padded rows "
+                                             "are generated group by group, without HF's common step axis"),
+    ("stats", "beams", NotImplementedError, "output_token_logprobs with num_beams > 1 is not built: beam search reports sequences_scores, and "
+                                            "beam rows reorder"),
+    ("stats", "padded", NotImplementedError, "output_token_logprobs with a padded attention_mask is not built: padded rows run as "
+                                             "continuous-batching slots, which keep no per-token statistics"),
+    ("stats", "batcher", NotImplementedError, "output_token_logprobs with a batcher attached is not built: its requests run as "
+                                              "continuous-batching slots, which keep no per-token statistics"),
+    ("topk", "no_dict", ValueError, "output_top_logprobs needs return_dict_in_generate=True: the lists travel on the returned object"),
+    ("topk", "beams", NotImplementedError, "output_top_logprobs with num_beams > 1 is not built: beam search reports sequences_scores, and "
+                                           "beam rows reorder"),
+    ("topk", "padded", NotImplementedError, "output_top_logprobs with a padded attention_mask is not built: padded rows run as "
+                                            "continuous-batching slots, which keep no per-token lists"),
+    ("topk", "batcher", NotImplementedError, "output_top_logprobs with a batcher attached is not built: its requests run as "
+                                             "continuous-batching slots, which keep no per-token lists"),
+    ("proc", "beams", NotImplementedError, "no_repeat_ngram_size / bad_words_ids / min_p with num_beams > 1 are not built: beam rows reorder "
+                                           "their histories"),
+    ("proc", "padded", NotImplementedError, "no_repeat_ngram_size / bad_words_ids / min_p with a padded attention_mask are not built: padded "
+                                            "rows run as continuous-batching slots, whose requests carry no such processors"),
+)
+
+
+def _refuse(asked: str, cond: dict) -> None:
+    for what, when, exc, message in _NOT_BUILT:
+        if what == asked and cond[when]:
+            raise exc(message)
+
+
 class HipCausalLM(_EngineModule):
     """The object the reference reaches as ``svg_transformer.transformer``: ``.generate(**kwargs)`` with
     the keyword set built at starvector_base.py:228-241 (+ :289-295), ``.transformer.wte``."""
@@ -469,140 +590,344 @@ class HipCausalLM(_EngineModule):
             raise NotImplementedError("one stop sequence is supported (the reference passes exactly one: '</svg>')")
         return stops[0] if stops else None
 
-    def _generate_padded(self, inputs_embeds, attention_mask, kw):
+    def _shared_batcher(self):
+        """The batcher this thread's engine work has to queue behind: None without one, and inside an exclusive job of it (the job has the
+        engine to itself and talks to it directly)."""
+        return None if _in_exclusive_job() else getattr(self, "batcher", None)
+
+    @torch.no_grad()
+    def generate(self, inputs_embeds: torch.Tensor = None, attention_mask: Optional[torch.Tensor] = None,
+                 do_sample: bool = False, top_p: Optional[float] = 1.0, temperature: Optional[float] = 1.0,
+                 num_beams: int = 1, max_length: int = 30, min_length: int = 0, repetition_penalty: float = 1.0,
+                 length_penalty: float = 1.0, use_cache: bool = True, stopping_criteria=None,
+                 early_stopping: bool = False, pad_token_id: Optional[int] = None, eos_token_id: Optional[int] = None,
+                 num_return_sequences: int = 1, top_k: Optional[int] = 50, streamer=None, seed: Optional[int] = None,
+                 return_dict_in_generate: bool = False, output_scores: bool = False, output_logits: bool = False,
+                 share_prompt: bool = True, no_repeat_ngram_size: int = 0, bad_words_ids=None, min_p: Optional[float] = None,
+                 output_token_logprobs: bool = False, output_top_logprobs: Optional[int] = None, top_logprobs_source: str = "raw",
+                 prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None,
+                 prompt_lookup_sampling: bool = False, **unused):
+        # Resolve the call into one `_GenRequest`, refuse what is not built (`_NOT_BUILT`), hand it to its route (`_route_*`).
+        # use_cache is accepted and ignored: the engine always uses its paged KV cache, the results are identical.
+        # top_k: the reference never passes it; its pinned transformers==4.49.0 (pyproject.toml:18) defaults
+        # GenerationConfig.top_k to 50, so every do_sample call there is top-k 50 followed by top-p.  Same default here.
+        if inputs_embeds is None:
+            raise ValueError("inputs_embeds is required (the reference always generates from embeddings)")
+        # prompt_lookup_sampling=True (an extension, opt-in): prompt_lookup_num_tokens may come with do_sample and / or a repetition penalty
+        # (sv_generate_lookup_sampled: the tokens of the same call without drafts, per seed).  Alone it asks for nothing that could be done.
+        if prompt_lookup_sampling and not prompt_lookup_num_tokens:
+            raise ValueError("`prompt_lookup_sampling` needs `prompt_lookup_num_tokens`: it selects how drafted tokens are verified, and "
+                             "without drafts there is nothing to verify")
+        batcher = getattr(self, "batcher", None)
+        padded = _is_padded(attention_mask)
+        cond = dict(always=True, padded=padded, beams=int(num_beams) > 1, batcher=batcher is not None, no_dict=not return_dict_in_generate)
+        # HF structured outputs (return_dict_in_generate): without it output_scores / output_logits are ignored, as HF ignores them
+        if return_dict_in_generate and (unused.get("output_attentions") or unused.get("output_hidden_states")):
+            _refuse("attentions", cond)
+        if return_dict_in_generate and (output_scores or output_logits):
+            _refuse("slabs", cond)
+        # output_token_logprobs (an extension, not an HF argument; read with return_dict_in_generate like output_scores): the returned object
+        # also carries token_logprobs, token_logprobs_processed and token_entropies [rows, n_new], computed inside the decode loop
+        # (sv_generate_stats) -- no [steps, rows, vocab] slab.  Where that route is not built the call raises, it never drops the argument.
+        # True: all three; a tuple of the field names: those alone (generate_im2svg_grpo leaves the processed log-prob out).
+        stats = output_token_logprobs if return_dict_in_generate and output_token_logprobs else False
+        if stats:
+            _refuse("stats", cond)
+        # output_top_logprobs = k (an extension, sv_generate_topk): the returned object also carries top_token_ids / top_logprobs [rows, n_new, k]
+        # -- the k most likely ids of every step and their log-probs, best first -- and token_ranks [rows, n_new], under the distribution
+        # top_logprobs_source names ("raw": that of token_logprobs, "processed": that of token_logprobs_processed).  It raises wherever
+        # output_token_logprobs raises, and without return_dict_in_generate (there is no object to carry the fields): never dropped.
+        topk = None
+        if output_top_logprobs is not None and output_top_logprobs is not False:
+            from .engine import token_topk_request
+            token_topk_request(dict(k=output_top_logprobs, source=top_logprobs_source))      # ValueError: k outside 1..32, an unknown source
+            _refuse("topk", cond)
+            topk = dict(k=int(output_top_logprobs), source=top_logprobs_source)
+        # HF's token-changing processors, on device (sv_generate_processed): NoRepeatNGram, NoBadWords, MinP.  Set = the call goes through
+        # HipEngine.generate_processed; where that route is not built the call raises, it never drops the argument.
+        proc = self._processor_args(no_repeat_ngram_size, bad_words_ids, min_p, do_sample, eos_token_id)
+        if proc:
+            _refuse("proc", cond)
+        # Random stream: HF draws from torch's global generator, so repeated calls differ and torch.manual_seed controls them.
+        # The device sampler is a pure function of (seed, step, row): the per-call seed is therefore DRAWN from torch's
+        # generator (same reproducibility contract), unless the caller pins it with `seed=` (tests, data-parallel ranks).
+        # The draw stands behind the refusals above (a call refused there leaves the generator alone) and in front of the range checks below.
+        if seed is None:
+            seed = self.seed
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, ()).item()) if do_sample else 0
+        num_beams = int(num_beams)
+        if num_beams < 1:
+            raise ValueError("`num_beams` has to be an integer strictly greater than 0")     # HF's own check
+        if num_beams > 8:
+            raise NotImplementedError("num_beams > 8 is not built")
+        num_return_sequences = int(num_return_sequences or 1)
+        if num_return_sequences < 1:
+            raise ValueError("`num_return_sequences` has to be at least 1")
+        if num_return_sequences > 1 and num_beams > 1:
+            # HF expands the inputs (repeat_interleave) and samples every copy independently; the reference forces
+            # num_beams = 1 whenever it asks for several sequences (starvector_base.py:273-276)
+            raise NotImplementedError("num_return_sequences > 1 with beam search is not built "
+                                      "(the reference sets num_beams=1 on this path)")
+        # Several samples of one prompt: where the engine offers the shared call, the un-repeated prompts go down and the engine runs ONE
+        # prompt pass per prompt (sv_generate_shared; a padded batch: sv_cb_admit_shared) -- rows, tokens and random draws are those of the
+        # repeated route, which stays for engines without it and for share_prompt=False (A/B, the equality tests).
+        G = 1
+        if num_return_sequences > 1:
+            eng = self._engine
+            if padded:
+                can = (hasattr(eng, "cb_admit_shared") and inputs_embeds.shape[0] * num_return_sequences <= eng.cfg.max_batch
+                       and self._shared_batcher() is None)
+            else:
+                can = hasattr(eng, "generate_shared")
+            if share_prompt and can:
+                G = num_return_sequences
+            else:
+                inputs_embeds = inputs_embeds.repeat_interleave(num_return_sequences, dim=0)
+                attention_mask = None if attention_mask is None else attention_mask.repeat_interleave(num_return_sequences, dim=0)
+        if repetition_penalty is not None and not repetition_penalty > 0:
+            raise ValueError("`repetition_penalty` has to be a strictly positive float")   # HF's own check
+        one = lambda v: float(v if v is not None else 1.0)                 # None is HF's "off" for these four
+        request = _GenRequest(
+            do_sample=bool(do_sample), temperature=one(temperature), top_p=one(top_p), top_k=int(top_k or 0),
+            repetition_penalty=one(repetition_penalty), length_penalty=one(length_penalty), num_beams=num_beams, early_stopping=early_stopping,
+            eos=int(self.eos_token_id if eos_token_id is None else eos_token_id),
+            pad=int(self.pad_token_id if pad_token_id is None else pad_token_id), stopping_criteria=stopping_criteria,
+            seed=int(seed) & (2 ** 63 - 1), max_length=int(max_length), min_length=int(min_length or 0), padded=padded, G=G,
+            n_return=num_return_sequences, return_dict=bool(return_dict_in_generate), output_scores=output_scores, output_logits=output_logits,
+            stats=stats, topk=topk, proc=proc, streamer=streamer,
+            lookup=(prompt_lookup_num_tokens, max_matching_ngram_size, bool(prompt_lookup_sampling)) if prompt_lookup_num_tokens else None)
+        if request.lookup is not None:
+            return self._route_lookup(request, inputs_embeds)
+        if padded:
+            seqs = self._route_padded(request, inputs_embeds, attention_mask)
+            return generate_output(num_beams > 1, sequences=seqs) if return_dict_in_generate else seqs
+        return self._route_unpadded(request, inputs_embeds)
+
+    # ---- the routes: each takes the request and the embeddings ---------------------------------------------------------------------------------
+    @staticmethod
+    def _streaming(streamer, rows):
+        # HF streamer protocol (generation/streamers.py): put(prompt ids) once -- none with inputs_embeds --, put(next_tokens [rows]) per
+        # step, end().  Returns the engine callback; tokens arrive in bursts of `sync_every` steps: the decode loop does not return to the
+        # host every token.
+        streamer.put(torch.empty(rows, 0, dtype=torch.long))
+
+        def on_tokens(tokens, first_col):
+            for c in range(tokens.shape[1]):
+                streamer.put(tokens[:, c])
+        return on_tokens
+
+    def _route_unpadded(self, r: _GenRequest, inputs_embeds):
+        """An all-real prompt batch: the classic engine call, or -- while a batcher shares the engine with other requests -- a request of
+        its decode loop (one row, nothing beyond tokens asked) or an exclusive job around the classic call (everything else)."""
+        rows, on_tokens = inputs_embeds.shape[0] * r.G, None
+        if r.streamer is not None:
+            if r.num_beams > 1:
+                raise ValueError("`streamer` cannot be used with beam search")          # HF's own check
+            on_tokens = self._streaming(r.streamer, rows)
+        batcher = self._shared_batcher()
+        if batcher is None:
+            out = self._route_classic(r, inputs_embeds, on_tokens)
+        elif r.want or r.proc or r.num_beams > 1 or rows > 1:
+            # beam search / a multi-row HF batch while requests share the engine: run it with the engine to itself, in turn
+            out = _exclusive(batcher, lambda: self._route_classic(r, inputs_embeds, on_tokens))
+        else:
+            out = self._route_batcher_single(r, inputs_embeds, on_tokens)
+        if r.streamer is not None:
+            r.streamer.end()
+        return out
+
+    def _route_batcher_single(self, r: _GenRequest, inputs_embeds, on_tokens):
+        # serving: one request per call (serve/model_worker.py:120-181), many calls in flight -> they share the engine's decode loop
+        # instead of taking turns; the tokens are those of the solo call
+        S0 = inputs_embeds.shape[1]
+        on_chunk = None if on_tokens is None else (lambda toks, first: on_tokens(toks.view(1, -1), first))
+        out = self.batcher.generate(inputs_embeds.to(torch.bfloat16), r.cb_request(r.max_length - S0, r.min_new(S0)), on_chunk)
+        out = out.to(inputs_embeds.device)
+        return generate_output(False, sequences=out) if r.return_dict else out
+
+    def _route_classic(self, r: _GenRequest, inputs_embeds, on_tokens):
+        """HipEngine.generate, generate_shared (G samples per prompt from one prompt pass) or generate_processed (no_repeat_ngram_size /
+        bad_words_ids / min_p; rectangular and shared prompts alike), and HF's output object around what it returns."""
+        eng, beams = self._engine, r.num_beams > 1
+        extra, slabs = {}, {}
+        if r.return_dict and (r.want or beams or r.stats or r.topk):
+            extra, slabs = self._output_slabs(r, inputs_embeds)
+            if r.stats:     # (these keywords go down only when asked for: an engine without them is never handed them)
+                extra["token_stats"] = True if r.stats is True else tuple(r.stats)
+            if r.topk:
+                extra["token_topk"] = r.topk
+        with _call_lock(eng):          # the same lock the slot path holds: a classic generate never lands between its cb_reset / cb_admit
+            call = eng.generate if r.G == 1 else functools.partial(eng.generate_shared, n_samples=r.G)
+            if r.proc:
+                call = functools.partial(eng.generate_processed, n_samples=r.G, **r.proc)
+            kw = r.engine_kw(r.min_new(inputs_embeds.shape[1]), on_tokens, sync_every=8 if r.streamer is not None else 32)
+            out = call(inputs_embeds.to(torch.bfloat16), max_length=r.max_length, **kw, **extra)
+        if not r.return_dict:
+            return out
+        if not extra:
+            return generate_output(False, sequences=out)
+        L = int(out["n_generated"])
+        fields = dict(sequences=out["sequences"],
+                      scores=tuple(slabs["scores_out"][t] for t in range(L)) if "scores_out" in slabs else None,
+                      logits=tuple(slabs["logits_out"][t] for t in range(L)) if "logits_out" in slabs else None)
+        if beams:
+            dev = out["sequences"].device
+            fields["beam_indices"] = out["beam_indices"].to(dev)
+            fields["sequences_scores"] = out["sequences_scores"].to(dev) if r.output_scores else None
+        if not r.stats and not r.topk:
+            return generate_output(beams, **fields)
+        # the extension's three fields beside HF's: HF's output dataclass has no place for them, so the object is the stand-in with the same
+        # field names, read as attributes or as keys
+        res = _GenerateOutput({k: fields.get(k) for k in _DECODER_ONLY_FIELDS})
+        if r.stats:
+            res.update({k: out.get(k) for k in ("token_logprobs", "token_logprobs_processed", "token_entropies")})
+        if r.topk:
+            res.update({k: out.get(k) for k in ("top_token_ids", "top_logprobs", "token_ranks")})
+        return res
+
+    def _route_lookup(self, r: _GenRequest, inputs_embeds):
+        # HF's prompt lookup decoding (prompt_lookup_num_tokens = K, max_matching_ngram_size): greedy generate that verifies K drafted tokens
+        # per step (sv_generate_lookup) -- the tokens are those of the call without it.  With prompt_lookup_sampling the call's own selection
+        # verifies the drafts (sv_generate_lookup_sampled: sampling, a repetition penalty).  What the engine does not build raises, naming it.
+        num_tokens, ngram, sampled = r.lookup
+        K = int(num_tokens)
+        if K < 1:
+            raise ValueError(f"`prompt_lookup_num_tokens` has to be a positive integer, but is {num_tokens}")
+        refused = [name for name, on in (
+            ("do_sample", not sampled and r.do_sample), ("num_beams > 1", r.num_beams > 1),
+            ("repetition_penalty != 1", not sampled and r.repetition_penalty != 1.0),
+            ("no_repeat_ngram_size / bad_words_ids / min_p", bool(r.proc)), ("output_scores / output_logits", r.want),
+            ("output_token_logprobs", bool(r.stats)), ("output_top_logprobs", bool(r.topk)),
+            ("num_return_sequences > 1", r.n_return > 1), ("a padded attention_mask", r.padded),
+            ("a batcher (continuous batching does not draft)", self._shared_batcher() is not None),
+            ("a streamer with more than one row", r.streamer is not None and inputs_embeds.shape[0] > 1)) if on]
+        if refused and sampled:
+            raise NotImplementedError("prompt_lookup_num_tokens with " + ", ".join(refused) + " is not built: verification of drafted tokens "
+                                      "(sv_generate_lookup_sampled) takes one sample per prompt, without beams, processors or per-step outputs")
+        if refused:
+            raise NotImplementedError("prompt_lookup_num_tokens with " + ", ".join(refused) + " is not built: greedy verification of drafted "
+                                      "tokens (sv_generate_lookup) takes greedy calls without per-step outputs")
+        eng, name = self._engine, "generate_lookup_sampled" if sampled else "generate_lookup"
+        if not hasattr(eng, name):
+            raise NotImplementedError("prompt_lookup_num_tokens: this engine has no " + name)
+        on_tokens = self._streaming(r.streamer, inputs_embeds.shape[0]) if r.streamer is not None else None
+        # greedy verification takes the ids, the stop and the hold; the sampled one also the selection of the plain call: the tokens must be that call's
+        names = ("eos_token_id", "pad_token_id", "stop_ids", "min_new_tokens")
+        if sampled:
+            names += ("do_sample", "temperature", "top_p", "top_k", "seed", "repetition_penalty")
+        with _call_lock(eng):
+            kw = r.engine_kw(r.min_new(inputs_embeds.shape[1]))
+            out = getattr(eng, name)(inputs_embeds.to(torch.bfloat16), max_length=r.max_length, num_draft_tokens=K, max_ngram=int(ngram or 0),
+                                     on_tokens=on_tokens, **{k: v for k, v in kw.items() if k in names})
+        if r.streamer is not None:
+            r.streamer.end()
+        return generate_output(False, sequences=out) if r.return_dict else out
+
+    def _route_padded(self, r: _GenRequest, inputs_embeds, attention_mask):
+        # Padded prompts (text2svg with captions of different lengths; the v2 tokenizer pads on the left, llm/starcoder2.py:53).
+        # HF masks the padded keys and numbers positions by cumsum(mask), so a padded row behaves exactly like the same row
+        # with its padding removed (checked against HF for left and right padding, GPTBigCode and StarCoder2).  Rows run as slots of one
+        # decode loop or as one ragged beam search where the engine offers them; else the engine takes rectangular all-ones prompts, so rows
+        # are grouped by their real length and generated group by group.  The streamer is never called here.
         mask = attention_mask.to(torch.bool)
-        G = int(kw.get("n_samples") or 1)               # > 1: the shared form -- inputs_embeds holds the un-repeated prompts, row r samples prompt r // G
-        if G > 1:
-            mask = mask.repeat_interleave(G, dim=0)
+        if r.G > 1:                    # the shared form: inputs_embeds holds the un-repeated prompts, row b samples prompt b // G
+            mask = mask.repeat_interleave(r.G, dim=0)
         B, S = mask.shape[0], inputs_embeds.shape[1]
+        eng = self._engine
         if not bool(mask[:, -1].all()):
             # right padding: only the ragged route takes it (every row runs with its padding removed, wherever the padding sits); the
             # rectangular length-group route continues from the last position and needs a real token there
-            if not hasattr(self._engine, "prefill_ragged"):
+            if not hasattr(eng, "prefill_ragged"):
                 raise ValueError("the last prompt position of every row must be a real token (generation continues from it)")
             if not bool(mask.any(dim=1).all()):
                 raise ValueError("every row needs at least one real prompt position")
-        budget = int(kw["max_length"]) - S                         # HF counts the budget from the PADDED prompt length
+        budget = r.max_length - S                                  # HF counts the budget from the PADDED prompt length
         if budget <= 0:
-            raise ValueError(f"max_length ({kw['max_length']}) must exceed the prompt length ({S})")
+            raise ValueError(f"max_length ({r.max_length}) must exceed the prompt length ({S})")
         lengths = mask.sum(dim=1).tolist()
-        pad = int(self.pad_token_id if kw.get("pad_token_id") is None else kw["pad_token_id"])
-        stop = self._stop_ids(kw.get("stopping_criteria"))
-        eng = self._engine
-        if G > 1 or (int(kw.get("num_beams") or 1) == 1 and hasattr(eng, "cb_admit") and B <= eng.cfg.max_batch
-                and (getattr(self, "batcher", None) is None or _in_exclusive_job())):
-            return self._generate_padded_slots(inputs_embeds, mask, lengths, budget, pad, stop, kw)
-        nb = int(kw.get("num_beams") or 1)
-        if nb > 1 and hasattr(eng, "generate_ragged") and B * nb <= eng.cfg.max_batch:
-            return self._generate_padded_beams(inputs_embeds, mask, lengths, budget, pad, stop, kw)
-        outs, fired_at = [None] * B, None
+        r.stop                                                     # (an unsupported criterion raises here, in front of every engine call)
+        if r.G > 1 or (r.num_beams == 1 and hasattr(eng, "cb_admit") and B <= eng.cfg.max_batch and self._shared_batcher() is None):
+            return self._route_slots(r, inputs_embeds, mask, lengths, budget)
+        if r.num_beams > 1 and hasattr(eng, "generate_ragged") and B * r.num_beams <= eng.cfg.max_batch:
+            return self._route_beams(r, inputs_embeds, mask, lengths, budget)
+        return self._route_groups(r, inputs_embeds, mask, lengths, budget)
+
+    @staticmethod
+    def _hf_padded(outs, length, pad, device):
+        """HF's padded batch from the rows' own token streams: cut at `length` (the step at which row 0's stop ended every row; None:
+        the longest row), finished rows padded."""
+        L = length if length is not None else max(t.shape[0] for t in outs)
+        res = torch.full((len(outs), L), pad, dtype=torch.long, device=device)
+        for b, t in enumerate(outs):
+            k = min(L, t.shape[0])
+            res[b, :k] = t[:k].to(device)
+        return res
+
+    def _route_groups(self, r: _GenRequest, inputs_embeds, mask, lengths, budget):
+        """One unpadded call per group of rows of equal real length, routed as a public unpadded call is (a batcher included)."""
+        B, S = mask.shape[0], inputs_embeds.shape[1]
+        outs, fired_at, stop = [None] * B, None, r.stop
         for n in sorted(set(lengths)):
             rows = [b for b in range(B) if lengths[b] == n]
             emb = torch.stack([inputs_embeds[b][mask[b]] for b in rows], 0)
-            # HF subtracts the PADDED prompt length from min_length as well: the same number of EOS-free steps for every row
-            sub = dict(kw, max_length=n + budget, min_length=n + max(int(kw.get("min_length") or 0) - S, 0))
-            if rows[0] != 0:
-                sub["stopping_criteria"] = None                    # the reference's stop looks at row 0 of the batch only
-            toks = self.generate(inputs_embeds=emb, attention_mask=None, **sub)
+            # HF subtracts the PADDED prompt length from min_length as well: the same number of EOS-free steps for every row.
+            # The reference's stop looks at row 0 of the batch only: the other groups run without it.
+            sub = dataclasses.replace(r, max_length=n + budget, min_length=n + r.min_new(S), padded=False, return_dict=False, streamer=None,
+                                      stopping_criteria=r.stopping_criteria if rows[0] == 0 else None)
+            toks = self._route_unpadded(sub, emb)
             if rows[0] == 0 and stop and toks.shape[1] >= len(stop) and toks[0, -len(stop):].tolist() == list(stop):
                 fired_at = toks.shape[1]                           # row 0 ended the whole batch at this step
             for i, b in enumerate(rows):
                 outs[b] = toks[i]
-        L = fired_at if fired_at is not None else max(t.shape[0] for t in outs)
-        res = torch.full((B, L), pad, dtype=torch.long, device=inputs_embeds.device)
-        for b, t in enumerate(outs):
-            k = min(L, t.shape[0])
-            res[b, :k] = t[:k]
-        return res
+        return self._hf_padded(outs, fired_at, r.pad, inputs_embeds.device)
 
-    def _generate_padded_beams(self, inputs_embeds, mask, lengths, budget, pad, stop, kw):
+    def _route_beams(self, r: _GenRequest, inputs_embeds, mask, lengths, budget):
         """Beam search / beam-sample over a padded batch as ONE ragged engine call (sv_generate_ragged): one prompt pass over the rows
         with their padding removed and one search for all requests, instead of a complete serial generate call per length group.  The
         engine follows HF's padded-batch semantics itself: the budget counts from the longest prompt (so max_length = longest + the budget
-        HF derives from the padded length), the row-0 stop ends every request, finished hypotheses are padded."""
+        HF derives from the padded length), the row-0 stop ends every request, finished hypotheses are padded.  No streaming keywords."""
         eng = self._engine
-        S = inputs_embeds.shape[1]
         seqs = [inputs_embeds[b][mask[b]].to(torch.bfloat16).contiguous() for b in range(inputs_embeds.shape[0])]
-        min_new = max(int(kw.get("min_length") or 0) - S, 0)
+        kw = dict(r.engine_kw(r.min_new(inputs_embeds.shape[1])), early_stopping=r.early_stopping or False)
 
         def call():
-            lock = getattr(eng, "call_lock", None) or contextlib.nullcontext()
-            with lock:
-                return eng.generate_ragged(
-                    seqs, max_length=max(lengths) + budget, do_sample=bool(kw.get("do_sample")),
-                    temperature=float(kw.get("temperature") if kw.get("temperature") is not None else 1.0),
-                    top_p=float(kw.get("top_p") if kw.get("top_p") is not None else 1.0),
-                    eos_token_id=int(self.eos_token_id if kw.get("eos_token_id") is None else kw["eos_token_id"]), pad_token_id=pad,
-                    stop_ids=stop, seed=int(kw.get("seed") or 0), repetition_penalty=float(kw.get("repetition_penalty") or 1.0),
-                    num_beams=int(kw["num_beams"]), length_penalty=float(kw.get("length_penalty") if kw.get("length_penalty") is not None else 1.0),
-                    early_stopping=kw.get("early_stopping") or False, top_k=int(kw.get("top_k") or 0),
-                    **({"min_new_tokens": min_new} if min_new else {}))
-        batcher = getattr(self, "batcher", None)
-        if batcher is not None and not _in_exclusive_job():
-            def job():                            # requests share the engine: the search runs with the engine to itself, in turn
-                _EXCLUSIVE.active = True
-                try:
-                    return call()
-                finally:
-                    _EXCLUSIVE.active = False
-            toks = batcher.run_exclusive(job)
-        else:
-            toks = call()
-        return toks.to(inputs_embeds.device)
+            with _call_lock(eng):
+                return eng.generate_ragged(seqs, max_length=max(lengths) + budget, **kw)
+        batcher = self._shared_batcher()       # requests share the engine: the search runs with the engine to itself, in turn
+        return (call() if batcher is None else _exclusive(batcher, call)).to(inputs_embeds.device)
 
-    def _generate_padded_slots(self, inputs_embeds, mask, lengths, budget, pad, stop, kw):
+    def _route_slots(self, r: _GenRequest, inputs_embeds, mask, lengths, budget):
         """Rows of different real length in ONE decode loop: every row is a slot of the engine's continuous batch (own prompt
         length, positions and KV pages), the prompt pass is ONE ragged pass over all rows where the engine offers it
         (`prefill_ragged`; else prompt passes run per length group: they are rectangular), and all rows then decode
         together -- instead of one full generate call per length group.  HF semantics of the padded batch are restored on
         the host: the reference's row-0 stop ends every row at row 0's step, finished rows are padded."""
         eng = self._engine
-        B, S = mask.shape[0], inputs_embeds.shape[1]
-        eos = int(self.eos_token_id if kw.get("eos_token_id") is None else kw["eos_token_id"])
-        min_new = max(int(kw.get("min_length") or 0) - S, 0)
-        seed = int(kw.get("seed") or 0)
-        base = dict(max_new_tokens=budget, do_sample=bool(kw.get("do_sample")), eos_token_id=eos, pad_token_id=pad,
-                    temperature=float(kw.get("temperature") if kw.get("temperature") is not None else 1.0),
-                    top_p=float(kw.get("top_p") if kw.get("top_p") is not None else 1.0), top_k=int(kw.get("top_k") or 0),
-                    repetition_penalty=float(kw.get("repetition_penalty") or 1.0), min_new_tokens=min_new)
-        slot_of = [None] * B
-        lock = getattr(eng, "call_lock", None) or contextlib.nullcontext()
-        with lock:            # from the first cb_reset to the last: another thread's generate must not reset or admit in between
-            outs, fired_len = self._run_slots(eng, inputs_embeds, mask, lengths, base, seed, stop, slot_of, int(kw.get("n_samples") or 1))
-        L = fired_len if fired_len is not None else max(t.shape[0] for t in outs)
-        res = torch.full((B, L), pad, dtype=torch.long, device=inputs_embeds.device)
-        for b, t in enumerate(outs):
-            k = min(L, t.shape[0])
-            res[b, :k] = t[:k].to(res.device)
-        return res
+        reqs = [r.cb_request(budget, r.min_new(inputs_embeds.shape[1]), row=b) for b in range(mask.shape[0])]
+        with _call_lock(eng):  # from the first cb_reset to the last: another thread's generate must not reset or admit in between
+            outs, fired_len = self._run_slots(eng, inputs_embeds, mask, lengths, reqs, r.stop, r.G)
+        return self._hf_padded(outs, fired_len, r.pad, inputs_embeds.device)
 
     @staticmethod
-    def _run_slots(eng, inputs_embeds, mask, lengths, base, seed, stop, slot_of, n_samples=1):
-        B, G = mask.shape[0], n_samples
+    def _run_slots(eng, inputs_embeds, mask, lengths, reqs, stop, G=1):
+        B = mask.shape[0]
+        row = lambda b: inputs_embeds[b // G][mask[b]].to(torch.bfloat16).contiguous()
         eng.cb_reset()
         try:
             if G > 1:
-                # the shared form: one ragged prompt pass over the B / G prompts, row r is a request of prompt r // G with the seed row r
+                # the shared form: one ragged prompt pass over the B / G prompts, row b is a request of prompt b // G with the seed row b
                 # has on the repeated route (sv_cb_admit_shared): same tokens
-                embs = [inputs_embeds[b // G][mask[b]].to(torch.bfloat16).contiguous() for b in range(0, B, G)]
-                reqs = [dict(base, seed=(seed + 0x9E3779B97F4A7C15 * b) & (2 ** 63 - 1), stop_ids=stop if b == 0 else None)
-                        for b in range(B)]
-                for b, s_ in enumerate(eng.cb_admit_shared(embs, None, [b // G for b in range(B)], reqs)):
-                    slot_of[b] = s_
+                slot_of = list(eng.cb_admit_shared([row(b) for b in range(0, B, G)], None, [b // G for b in range(B)], reqs))
             elif hasattr(eng, "prefill_ragged"):
-                # one ragged prompt pass for all rows; the per-row seeds are those of the length-group route: same tokens
-                embs = [inputs_embeds[b][mask[b]].to(torch.bfloat16).contiguous() for b in range(B)]
-                reqs = [dict(base, seed=(seed + 0x9E3779B97F4A7C15 * b) & (2 ** 63 - 1), stop_ids=stop if b == 0 else None)
-                        for b in range(B)]
-                for b, s_ in enumerate(eng.cb_admit(embs, reqs)):
-                    slot_of[b] = s_
-            for n in ([] if G > 1 or hasattr(eng, "prefill_ragged") else sorted(set(lengths))):
-                rows = [b for b in range(B) if lengths[b] == n]
-                emb = torch.stack([inputs_embeds[b][mask[b]] for b in rows], 0).to(torch.bfloat16).contiguous()
-                reqs = [dict(base, seed=(seed + 0x9E3779B97F4A7C15 * b) & (2 ** 63 - 1), stop_ids=stop if b == 0 else None)
-                        for b in rows]
-                for b, s_ in zip(rows, eng.cb_admit(emb, reqs)):
-                    slot_of[b] = s_
+                slot_of = list(eng.cb_admit([row(b) for b in range(B)], reqs))      # one ragged prompt pass for all rows
+            else:
+                slot_of = [None] * B
+                for n in sorted(set(lengths)):
+                    rows = [b for b in range(B) if lengths[b] == n]
+                    emb = torch.stack([inputs_embeds[b][mask[b]] for b in rows], 0).to(torch.bfloat16).contiguous()
+                    for b, s_ in zip(rows, eng.cb_admit(emb, [reqs[b] for b in rows])):
+                        slot_of[b] = s_
             fired_len = None
             while True:
                 live = eng.cb_step(16)
@@ -619,283 +944,6 @@ class HipCausalLM(_EngineModule):
         finally:
             eng.cb_reset()
         return outs, fired_len
-
-    @torch.no_grad()
-    def generate(self, inputs_embeds: torch.Tensor = None, attention_mask: Optional[torch.Tensor] = None,
-                 do_sample: bool = False, top_p: Optional[float] = 1.0, temperature: Optional[float] = 1.0,
-                 num_beams: int = 1, max_length: int = 30, min_length: int = 0, repetition_penalty: float = 1.0,
-                 length_penalty: float = 1.0, use_cache: bool = True, stopping_criteria=None,
-                 early_stopping: bool = False, pad_token_id: Optional[int] = None, eos_token_id: Optional[int] = None,
-                 num_return_sequences: int = 1, top_k: Optional[int] = 50, streamer=None, seed: Optional[int] = None,
-                 return_dict_in_generate: bool = False, output_scores: bool = False, output_logits: bool = False,
-                 share_prompt: bool = True, no_repeat_ngram_size: int = 0, bad_words_ids=None, min_p: Optional[float] = None,
-                 output_token_logprobs: bool = False, output_top_logprobs: Optional[int] = None, top_logprobs_source: str = "raw",
-                 prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None,
-                 prompt_lookup_sampling: bool = False, **unused):
-        # top_k: the reference never passes it; its pinned transformers==4.49.0 (pyproject.toml:18) defaults
-        # GenerationConfig.top_k to 50, so every do_sample call there is top-k 50 followed by top-p.  Same default here.
-        if inputs_embeds is None:
-            raise ValueError("inputs_embeds is required (the reference always generates from embeddings)")
-        # prompt_lookup_sampling=True (an extension, opt-in): prompt_lookup_num_tokens may come with do_sample and / or a repetition penalty
-        # (sv_generate_lookup_sampled: the tokens of the same call without drafts, per seed).  Alone it asks for nothing that could be done.
-        if prompt_lookup_sampling and not prompt_lookup_num_tokens:
-            raise ValueError("`prompt_lookup_sampling` needs `prompt_lookup_num_tokens`: it selects how drafted tokens are verified, and "
-                             "without drafts there is nothing to verify")
-        # HF structured outputs (return_dict_in_generate): without it output_scores / output_logits are ignored, as HF ignores them
-        want = False
-        if return_dict_in_generate:
-            if unused.get("output_attentions") or unused.get("output_hidden_states"):
-                raise NotImplementedError("output_attentions / output_hidden_states are not built: the decode step keeps neither")
-            want = bool(output_scores or output_logits)
-            if want and attention_mask is not None and not bool((attention_mask == 1).all()):
-                raise NotImplementedError("output_scores / output_logits with a padded attention_mask are not built: padded rows "
-                                          "are generated group by group, without HF's common step axis")
-        outputs = dict(return_dict_in_generate=True, output_scores=output_scores, output_logits=output_logits) \
-            if return_dict_in_generate else {}
-        # output_token_logprobs (an extension, not an HF argument; read with return_dict_in_generate like output_scores): the returned object
-        # also carries token_logprobs, token_logprobs_processed and token_entropies [rows, n_new], computed inside the decode loop
-        # (sv_generate_stats) -- no [steps, rows, vocab] slab.  Where that route is not built the call raises, it never drops the argument.
-        stats = bool(return_dict_in_generate and output_token_logprobs)
-        if stats:
-            if int(num_beams) > 1:
-                raise NotImplementedError("output_token_logprobs with num_beams > 1 is not built: beam search reports sequences_scores, and "
-                                          "beam rows reorder")
-            if attention_mask is not None and not bool((attention_mask == 1).all()):
-                raise NotImplementedError("output_token_logprobs with a padded attention_mask is not built: padded rows run as "
-                                          "continuous-batching slots, which keep no per-token statistics")
-            if getattr(self, "batcher", None) is not None:
-                raise NotImplementedError("output_token_logprobs with a batcher attached is not built: its requests run as "
-                                          "continuous-batching slots, which keep no per-token statistics")
-        # output_top_logprobs = k (an extension, sv_generate_topk): the returned object also carries top_token_ids / top_logprobs [rows, n_new, k]
-        # -- the k most likely ids of every step and their log-probs, best first -- and token_ranks [rows, n_new], under the distribution
-        # top_logprobs_source names ("raw": that of token_logprobs, "processed": that of token_logprobs_processed).  It raises wherever
-        # output_token_logprobs raises, and without return_dict_in_generate (there is no object to carry the fields): never dropped.
-        topk = None
-        if output_top_logprobs is not None and output_top_logprobs is not False:
-            from .engine import token_topk_request
-            token_topk_request(dict(k=output_top_logprobs, source=top_logprobs_source))      # ValueError: k outside 1..32, an unknown source
-            if not return_dict_in_generate:
-                raise ValueError("output_top_logprobs needs return_dict_in_generate=True: the lists travel on the returned object")
-            if int(num_beams) > 1:
-                raise NotImplementedError("output_top_logprobs with num_beams > 1 is not built: beam search reports sequences_scores, and "
-                                          "beam rows reorder")
-            if attention_mask is not None and not bool((attention_mask == 1).all()):
-                raise NotImplementedError("output_top_logprobs with a padded attention_mask is not built: padded rows run as "
-                                          "continuous-batching slots, which keep no per-token lists")
-            if getattr(self, "batcher", None) is not None:
-                raise NotImplementedError("output_top_logprobs with a batcher attached is not built: its requests run as "
-                                          "continuous-batching slots, which keep no per-token lists")
-            topk = dict(k=int(output_top_logprobs), source=top_logprobs_source)
-        # HF's token-changing processors, on device (sv_generate_processed): NoRepeatNGram, NoBadWords, MinP.  Set = the call goes through
-        # HipEngine.generate_processed; where that route is not built the call raises, it never drops the argument.
-        proc = self._processor_args(no_repeat_ngram_size, bad_words_ids, min_p, do_sample, eos_token_id)
-        if proc:
-            if int(num_beams) > 1:
-                raise NotImplementedError("no_repeat_ngram_size / bad_words_ids / min_p with num_beams > 1 are not built: beam rows reorder "
-                                          "their histories")
-            if attention_mask is not None and not bool((attention_mask == 1).all()):
-                raise NotImplementedError("no_repeat_ngram_size / bad_words_ids / min_p with a padded attention_mask are not built: padded "
-                                          "rows run as continuous-batching slots, whose requests carry no such processors")
-        # Random stream: HF draws from torch's global generator, so repeated calls differ and torch.manual_seed controls them.
-        # The device sampler is a pure function of (seed, step, row): the per-call seed is therefore DRAWN from torch's
-        # generator (same reproducibility contract), unless the caller pins it with `seed=` (tests, data-parallel ranks).
-        if seed is None:
-            seed = self.seed
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, ()).item()) if do_sample else 0
-        seed = int(seed) & (2 ** 63 - 1)
-        num_beams = int(num_beams)
-        if num_beams < 1:
-            raise ValueError("`num_beams` has to be an integer strictly greater than 0")     # HF's own check
-        if num_beams > 8:
-            raise NotImplementedError("num_beams > 8 is not built")
-        num_return_sequences = int(num_return_sequences or 1)
-        if num_return_sequences < 1:
-            raise ValueError("`num_return_sequences` has to be at least 1")
-        if num_return_sequences > 1:
-            # HF expands the inputs (repeat_interleave) and samples every copy independently; the reference forces
-            # num_beams = 1 whenever it asks for several sequences (starvector_base.py:273-276)
-            if num_beams > 1:
-                raise NotImplementedError("num_return_sequences > 1 with beam search is not built "
-                                          "(the reference sets num_beams=1 on this path)")
-        # Several samples of one prompt: where the engine offers the shared call, the un-repeated prompts go down and the engine runs ONE
-        # prompt pass per prompt (sv_generate_shared; a padded batch: sv_cb_admit_shared) -- rows, tokens and random draws are those of the
-        # repeated route, which stays for engines without it and for share_prompt=False (A/B, the equality tests).
-        G = 1
-        if num_return_sequences > 1:
-            eng = self._engine
-            padded = attention_mask is not None and not bool((attention_mask == 1).all())
-            rows = inputs_embeds.shape[0] * num_return_sequences
-            if padded:
-                can = (hasattr(eng, "cb_admit_shared") and rows <= eng.cfg.max_batch and not want
-                       and (getattr(self, "batcher", None) is None or _in_exclusive_job()))
-            else:
-                can = hasattr(eng, "generate_shared")
-            if share_prompt and can:
-                G = num_return_sequences
-            else:
-                inputs_embeds = inputs_embeds.repeat_interleave(num_return_sequences, dim=0)
-                attention_mask = None if attention_mask is None else attention_mask.repeat_interleave(num_return_sequences, dim=0)
-        if repetition_penalty is not None and not repetition_penalty > 0:
-            raise ValueError("`repetition_penalty` has to be a strictly positive float")   # HF's own check
-        # HF's prompt lookup decoding (prompt_lookup_num_tokens = K, max_matching_ngram_size): greedy generate that verifies K drafted tokens
-        # per step (sv_generate_lookup) -- the tokens are those of the call without it.  What the engine does not build raises, naming it.
-        # With prompt_lookup_sampling the call's own selection verifies the drafts (sv_generate_lookup_sampled): sampling, repetition penalty.
-        if prompt_lookup_num_tokens:
-            return self._generate_lookup(inputs_embeds, attention_mask, prompt_lookup_num_tokens, max_matching_ngram_size, dict(
-                do_sample=do_sample, num_beams=num_beams, repetition_penalty=repetition_penalty, processors=proc, outputs=want, stats=stats,
-                topk=topk, num_return_sequences=num_return_sequences), max_length, min_length, eos_token_id, pad_token_id, stopping_criteria,
-                streamer, return_dict_in_generate,
-                sampling=dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed) if prompt_lookup_sampling else None)
-        if attention_mask is not None and not bool((attention_mask == 1).all()):
-            # Padded prompts (text2svg with captions of different lengths; the v2 tokenizer pads on the left, llm/starcoder2.py:53).
-            # HF masks the padded keys and numbers positions by cumsum(mask), so a padded row behaves exactly like the same row
-            # with its padding removed (checked against HF for left and right padding, GPTBigCode and StarCoder2).  The engine
-            # takes rectangular all-ones prompts, so rows are grouped by their real length and generated group by group.
-            seqs = self._generate_padded(inputs_embeds, attention_mask, dict(
-                do_sample=do_sample, top_p=top_p, temperature=temperature, num_beams=num_beams, max_length=max_length,
-                min_length=min_length, repetition_penalty=repetition_penalty, length_penalty=length_penalty,
-                use_cache=use_cache, stopping_criteria=stopping_criteria, early_stopping=early_stopping,
-                pad_token_id=pad_token_id, eos_token_id=eos_token_id, top_k=top_k, seed=seed, n_samples=G))
-            return generate_output(num_beams > 1, sequences=seqs) if return_dict_in_generate else seqs
-        S0 = inputs_embeds.shape[1]
-        # HF (_prepare_generated_length): with inputs_embeds min_length is reduced by the prompt length -- 0 on the im2svg path
-        # (SURVEY.md 8a-a11), positive only for a text2svg caption shorter than min_length; MinLengthLogitsProcessor then
-        # keeps EOS at -inf for that many new tokens (in beam search HF applies it to the log-probabilities: so does the scorer).
-        min_new = max(int(min_length or 0) - S0, 0)
-        if not use_cache:
-            pass        # the engine always uses its paged KV cache; results are identical
-        on_tokens = None
-        if streamer is not None:
-            # HF streamer protocol (generation/streamers.py): put(prompt ids) once, put(next_tokens [B]) per step, end().
-            # Tokens arrive in bursts of `sync_every` steps: the decode loop does not return to the host every token.
-            if num_beams > 1:
-                raise ValueError("`streamer` cannot be used with beam search")          # HF's own check
-            streamer.put(torch.empty(inputs_embeds.shape[0] * G, 0, dtype=torch.long))     # no prompt ids with inputs_embeds
-
-            def on_tokens(tokens, first_col):
-                for c in range(tokens.shape[1]):
-                    streamer.put(tokens[:, c])
-        batcher = getattr(self, "batcher", None)
-        if batcher is not None and (want or proc or not (num_beams == 1 and inputs_embeds.shape[0] * G == 1)) and not _in_exclusive_job():
-            # beam search / a multi-row HF batch while requests share the engine: run it with the engine to itself, in turn
-            def call():
-                _EXCLUSIVE.active = True          # thread-local: only the scheduler thread running this job sees it
-                try:
-                    return self.generate(inputs_embeds=inputs_embeds, attention_mask=attention_mask, do_sample=do_sample,
-                                         top_p=top_p, temperature=temperature, num_beams=num_beams, max_length=max_length,
-                                         min_length=min_length, repetition_penalty=repetition_penalty,
-                                         length_penalty=length_penalty, use_cache=use_cache, stopping_criteria=stopping_criteria,
-                                         early_stopping=early_stopping, pad_token_id=pad_token_id, eos_token_id=eos_token_id,
-                                         top_k=top_k, streamer=streamer, seed=seed, num_return_sequences=G, share_prompt=share_prompt,
-                                         no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids, min_p=min_p, **outputs)
-                finally:
-                    _EXCLUSIVE.active = False
-            return batcher.run_exclusive(call)
-        if batcher is not None and num_beams == 1 and inputs_embeds.shape[0] * G == 1 and not _in_exclusive_job():
-            # serving: one request per call (serve/model_worker.py:120-181), many calls in flight -> they share the engine's
-            # decode loop instead of taking turns; the tokens are those of the solo call below
-            def on_chunk(toks, first):
-                if on_tokens is not None:
-                    on_tokens(toks.view(1, -1), first)
-            out = self.batcher.generate(inputs_embeds.to(torch.bfloat16), dict(
-                max_new_tokens=int(max_length) - S0, do_sample=bool(do_sample),
-                temperature=float(temperature if temperature is not None else 1.0),
-                top_p=float(top_p if top_p is not None else 1.0), top_k=int(top_k or 0), seed=seed,
-                eos_token_id=int(self.eos_token_id if eos_token_id is None else eos_token_id),
-                pad_token_id=int(self.pad_token_id if pad_token_id is None else pad_token_id),
-                stop_ids=self._stop_ids(stopping_criteria),
-                repetition_penalty=float(repetition_penalty if repetition_penalty is not None else 1.0),
-                min_new_tokens=min_new), on_chunk if on_tokens is not None else None).to(inputs_embeds.device)
-            if streamer is not None:
-                streamer.end()
-            return generate_output(False, sequences=out) if return_dict_in_generate else out
-        extra, slabs = {}, {}
-        if return_dict_in_generate and (want or num_beams > 1 or stats or topk):
-            extra, slabs = self._output_slabs(inputs_embeds, max_length, num_beams, output_scores, output_logits, G)
-            if stats:       # True: all three; a tuple of the field names: those alone (generate_im2svg_grpo leaves the processed log-prob out)
-                extra["token_stats"] = True if output_token_logprobs is True else tuple(output_token_logprobs)
-            if topk:        # (the keyword goes down only when asked for: an engine without it is never handed it)
-                extra["token_topk"] = topk
-        lock = getattr(self._engine, "call_lock", None) or contextlib.nullcontext()
-        with lock:          # the same lock the slot path holds: a classic generate never lands between its cb_reset / cb_admit
-            out = self._classic_generate(inputs_embeds, max_length, do_sample, temperature, top_p, eos_token_id, pad_token_id,
-                                         stopping_criteria, seed, repetition_penalty, num_beams, length_penalty, early_stopping,
-                                         top_k, on_tokens, streamer, min_new, n_samples=G, processors=proc, **extra)
-        if streamer is not None:
-            streamer.end()
-        if not return_dict_in_generate:
-            return out
-        if not extra:
-            return generate_output(False, sequences=out)
-        L = int(out["n_generated"])
-        fields = dict(sequences=out["sequences"],
-                      scores=tuple(slabs["scores_out"][t] for t in range(L)) if "scores_out" in slabs else None,
-                      logits=tuple(slabs["logits_out"][t] for t in range(L)) if "logits_out" in slabs else None)
-        if num_beams > 1:
-            dev = out["sequences"].device
-            fields["beam_indices"] = out["beam_indices"].to(dev)
-            fields["sequences_scores"] = out["sequences_scores"].to(dev) if output_scores else None
-        if not stats and not topk:
-            return generate_output(num_beams > 1, **fields)
-        # the extension's three fields beside HF's: HF's output dataclass has no place for them, so the object is the stand-in with the same
-        # field names, read as attributes or as keys
-        res = _GenerateOutput({k: fields.get(k) for k in _DECODER_ONLY_FIELDS})
-        if stats:
-            res.update({k: out.get(k) for k in ("token_logprobs", "token_logprobs_processed", "token_entropies")})
-        if topk:
-            res.update({k: out.get(k) for k in ("top_token_ids", "top_logprobs", "token_ranks")})
-        return res
-
-    def _generate_lookup(self, inputs_embeds, attention_mask, num_tokens, ngram, asked, max_length, min_length, eos_token_id, pad_token_id,
-                         stopping_criteria, streamer, return_dict, sampling=None):
-        # sampling = None: greedy verification (generate_lookup); a dict of the warpers and the seed: the call's own selection
-        # (generate_lookup_sampled), which takes do_sample and a repetition penalty
-        K = int(num_tokens)
-        if K < 1:
-            raise ValueError(f"`prompt_lookup_num_tokens` has to be a positive integer, but is {num_tokens}")
-        refused = [name for name, on in (
-            ("do_sample", sampling is None and bool(asked["do_sample"])), ("num_beams > 1", int(asked["num_beams"]) > 1),
-            ("repetition_penalty != 1", sampling is None and asked["repetition_penalty"] is not None and float(asked["repetition_penalty"]) != 1.0),
-            ("no_repeat_ngram_size / bad_words_ids / min_p", bool(asked["processors"])), ("output_scores / output_logits", bool(asked["outputs"])),
-            ("output_token_logprobs", bool(asked["stats"])), ("output_top_logprobs", bool(asked["topk"])),
-            ("num_return_sequences > 1", int(asked["num_return_sequences"]) > 1),
-            ("a padded attention_mask", attention_mask is not None and not bool((attention_mask == 1).all())),
-            ("a batcher (continuous batching does not draft)", getattr(self, "batcher", None) is not None and not _in_exclusive_job()),
-            ("a streamer with more than one row", streamer is not None and inputs_embeds.shape[0] > 1)) if on]
-        if refused and sampling is not None:
-            raise NotImplementedError("prompt_lookup_num_tokens with " + ", ".join(refused) + " is not built: verification of drafted tokens "
-                                      "(sv_generate_lookup_sampled) takes one sample per prompt, without beams, processors or per-step outputs")
-        if refused:
-            raise NotImplementedError("prompt_lookup_num_tokens with " + ", ".join(refused) + " is not built: greedy verification of drafted "
-                                      "tokens (sv_generate_lookup) takes greedy calls without per-step outputs")
-        eng = self._engine
-        if not hasattr(eng, "generate_lookup" if sampling is None else "generate_lookup_sampled"):
-            raise NotImplementedError("prompt_lookup_num_tokens: this engine has no " + ("generate_lookup" if sampling is None else "generate_lookup_sampled"))
-        on_tokens = None
-        if streamer is not None:
-            streamer.put(torch.empty(inputs_embeds.shape[0], 0, dtype=torch.long))
-
-            def on_tokens(tokens, first_col):
-                for c in range(tokens.shape[1]):
-                    streamer.put(tokens[:, c])
-        min_new = max(int(min_length or 0) - inputs_embeds.shape[1], 0)
-        lock = getattr(eng, "call_lock", None) or contextlib.nullcontext()
-        extra = {}
-        if sampling is not None:      # the values _classic_generate hands the plain call: the tokens must be that call's
-            t, p = sampling["temperature"], sampling["top_p"]
-            rp = asked["repetition_penalty"]
-            extra = dict(do_sample=bool(asked["do_sample"]), temperature=float(t if t is not None else 1.0), top_p=float(p if p is not None else 1.0),
-                         top_k=int(sampling["top_k"] or 0), seed=sampling["seed"], repetition_penalty=float(rp if rp is not None else 1.0))
-        with lock:
-            out = (eng.generate_lookup if sampling is None else eng.generate_lookup_sampled)(
-                inputs_embeds.to(torch.bfloat16), max_length=int(max_length), num_draft_tokens=K, max_ngram=int(ngram or 0),
-                eos_token_id=int(self.eos_token_id if eos_token_id is None else eos_token_id),
-                pad_token_id=int(self.pad_token_id if pad_token_id is None else pad_token_id),
-                stop_ids=self._stop_ids(stopping_criteria), on_tokens=on_tokens, **({"min_new_tokens": min_new} if min_new else {}), **extra)
-        if streamer is not None:
-            streamer.end()
-        return generate_output(False, sequences=out) if return_dict else out
 
     def _processor_args(self, no_repeat_ngram_size, bad_words_ids, min_p, do_sample, eos_token_id):
         """HF's own checks of no_repeat_ngram_size / bad_words_ids / min_p (generation/logits_process.py, transformers 4.49), then the
@@ -929,13 +977,13 @@ class HipCausalLM(_EngineModule):
         logits_processors(n, words, min_p or 0.0, vocab=vocab)          # the limits: ValueError here, before any engine call
         return dict(no_repeat_ngram_size=int(n), bad_words_ids=words or None, min_p=float(min_p or 0.0))
 
-    def _output_slabs(self, inputs_embeds, max_length, num_beams, output_scores, output_logits, n_samples=1):
+    def _output_slabs(self, r: _GenRequest, inputs_embeds):
         """[max_new, rows, V] fp32 slabs for output_scores / output_logits on the engine's device, after checking they fit (the engine
         writes step t of every row into slab[t])."""
         eng = self._engine
         B, S0 = inputs_embeds.shape[0], inputs_embeds.shape[1]
-        rows, max_new, V = B * max(int(num_beams), 1) * n_samples, int(max_length) - S0, int(eng.cfg.vocab)
-        names = [n for n, on in (("scores_out", output_scores), ("logits_out", output_logits)) if on]
+        rows, max_new, V = B * r.num_beams * r.G, r.max_length - S0, int(eng.cfg.vocab)
+        names = [n for n, on in (("scores_out", r.output_scores), ("logits_out", r.output_logits)) if on]
         extra = dict(return_outputs=True)
         if not names or max_new <= 0:
             return extra, {}
@@ -973,25 +1021,6 @@ class HipCausalLM(_EngineModule):
         out = stacked.gather(0, indices)
         out[mask] = 0
         return out
-
-    def _classic_generate(self, inputs_embeds, max_length, do_sample, temperature, top_p, eos_token_id, pad_token_id,
-                          stopping_criteria, seed, repetition_penalty, num_beams, length_penalty, early_stopping, top_k,
-                          on_tokens, streamer, min_new, n_samples=1, processors=None, **outputs):
-        # (n_samples > 1: the shared call -- one prompt pass over these prompts, n_samples rows each)
-        call = self._engine.generate if n_samples == 1 else functools.partial(self._engine.generate_shared, n_samples=n_samples)
-        if processors:      # no_repeat_ngram_size / bad_words_ids / min_p: the processed call (rectangular and shared prompts alike)
-            call = functools.partial(self._engine.generate_processed, n_samples=n_samples, **processors)
-        return call(
-            inputs_embeds.to(torch.bfloat16), max_length=int(max_length), do_sample=bool(do_sample),
-            temperature=float(temperature if temperature is not None else 1.0),
-            top_p=float(top_p if top_p is not None else 1.0),
-            eos_token_id=int(self.eos_token_id if eos_token_id is None else eos_token_id),
-            pad_token_id=int(self.pad_token_id if pad_token_id is None else pad_token_id),
-            stop_ids=self._stop_ids(stopping_criteria), seed=seed,
-            repetition_penalty=float(repetition_penalty if repetition_penalty is not None else 1.0),
-            num_beams=num_beams, length_penalty=float(length_penalty if length_penalty is not None else 1.0),
-            early_stopping=early_stopping, top_k=int(top_k or 0), on_tokens=on_tokens,
-            sync_every=8 if streamer is not None else 32, **({"min_new_tokens": min_new} if min_new else {}), **outputs)
 
 
 def completion_mask(new_tokens: torch.Tensor, eos_token_id: int) -> torch.Tensor:
@@ -1125,8 +1154,8 @@ class StarVectorStarCoder(nn.Module):
         """starvector_base.py:297-330, restated by intent: embed(caption ids + <svg-start>) -> generate -> new token ids.
         The snapshot's version cannot run (it passes two positional arguments to _get_generation_kwargs, :321-324, and
         subtracts the prompt length from max_length twice); here `max_length` counts the prompt once, as in im2svg.
-        Captions of different lengths are padded by the tokenizer; the padded rows are generated group by group
-        (HipCausalLM._generate_padded), which reproduces HF's masked generation exactly."""
+        Captions of different lengths are padded by the tokenizer; the padded rows run without their pads
+        (HipCausalLM._route_padded), which reproduces HF's masked generation exactly."""
         device = batch["image"].device if "image" in batch else torch.device("cuda", self._engine_device())
         prompt_tokens = self._tokenize(list(batch["caption"]), kwargs.get("max_length", 30), device, add_special_tokens=False)
         trigger = self._tokenize([self.svg_transformer.svg_start_token] * len(batch["caption"]), None, device,
@@ -1257,7 +1286,7 @@ class StarVectorForCausalLM(nn.Module):
     def _scoring_mask_lead(attention_mask, shape):
         """The mask analysis of the scoring passes (`forward`, `completion_logprobs`): None when no row has leading pads, else the
         number of leading pads per row.  Raises for masks that are not left / right padding."""
-        if attention_mask is None or bool((attention_mask == 1).all()):
+        if not _is_padded(attention_mask):
             return None
         # Right padding (completions padded after their EOS, what a GRPO trainer passes): under the causal mask a real
         # position never sees a later key and HF's positions (cumsum(mask) - 1) equal the plain index for it, so the
@@ -1288,14 +1317,8 @@ class StarVectorForCausalLM(nn.Module):
         if batcher is not None and not _in_exclusive_job():
             # requests share the engine's decode loop: the scoring pass wants the engine to itself (it would fail with SV_ESTATE
             # while slots are live) -> queue it as an exclusive job, FIFO with the generation requests
-            def call():
-                _EXCLUSIVE.active = True
-                try:
-                    return fn()
-                finally:
-                    _EXCLUSIVE.active = False
-            return batcher.run_exclusive(call)
-        with (getattr(self.engine, "call_lock", None) or contextlib.nullcontext()):
+            return _exclusive(batcher, fn)
+        with _call_lock(self.engine):
             return fn()
 
     @torch.no_grad()
@@ -1372,7 +1395,7 @@ class StarVectorForCausalLM(nn.Module):
         if attention_mask is not None:
             pad = ~attention_mask.to(torch.bool)[:, S - n:].to(emb16.device)       # the token itself is padding
             targets[:, :n] = targets[:, :n].masked_fill(pad, -100)
-        if unpadded and attention_mask is not None and not bool((attention_mask == 1).all()):
+        if unpadded and _is_padded(attention_mask):
             return self._completion_logprobs_unpadded(emb16, targets, attention_mask, n, temperature, return_entropy, k)
 
         def score(e16, tg):
