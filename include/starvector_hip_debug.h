@@ -111,6 +111,11 @@ int  sv_debug_skinny_form(void);
  *                             gemm_skinny_tailsplit_kernel: StarVector-8B's c_fc at <= 32 rows); counted on the host at launch (a captured
  *                             graph counts once, at capture).  Lets a test prove which kernel ran. */
 int  sv_debug_tailsplit_launches(int64_t* count);
+/*   sv_debug_cols_rowhalf_launches  how many times, process-wide since the library was loaded, the decode output projection took its row-half
+ *                             form (decode_cols.hip gemm_cols_resid_kernel: 16 rows x 16 columns per block; SV_COLS_ROWHALF=0 = never), and how many
+ *                             row halves those launches ran (one for a step of at most 16 rows, else two); counted on the host at launch (a
+ *                             captured graph counts once, at capture).  Lets a test prove which form ran. */
+int  sv_debug_cols_rowhalf_launches(int64_t* launches, int64_t* halves);
 /*   sv_debug_set_gemm_form    process-wide: every big-M GEMM launch takes ONE form -- 0 = 128x128 tiles, 1 = 256x256 tiles (rows not peeled),
      2 = 256x256 tiles + the row remainder over a multiple of 256 through the one-wave-per-tile tail kernel, 3 = every row through that tail
      kernel (with a sequence structure: the full 256-row tiles' rows of every sequence; the rows a sequence leaves over take the split-K

@@ -196,6 +196,7 @@ DEBUG_PROTOTYPES = {
     "sv_debug_set_skinny_form": (_I, [_I]),
     "sv_debug_skinny_form": (_I, []),
     "sv_debug_tailsplit_launches": (_I, [C.POINTER(C.c_int64)]),
+    "sv_debug_cols_rowhalf_launches": (_I, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sv_debug_set_gemm_form": (_I, [_I]),
     "sv_debug_set_linear_seq_rows": (_I, [_I]),
     "sv_debug_gemm_seq_form": (_I, [_I, _I, _I, _I]),

@@ -701,7 +701,7 @@ void sveng::decode_forward(sv_engine* e, int B, hipStream_t st) {
             // c_fc on the raw h with ln_2 folded into its weights / epilogue: no slabs, no row-update launch (decode_cols.hip)
             ColsArgs ca;
             memset(&ca, 0, sizeof(ca));
-            ca.xp = e->xp_attn; ca.Wp = L.c_proj.Wp; ca.bias = L.c_proj.bias; ca.MT = MT; ca.N = L.c_proj.N; ca.K = L.c_proj.Kpad;
+            ca.xp = e->xp_attn; ca.Wp = L.c_proj.Wp; ca.bias = L.c_proj.bias; ca.MT = MT; ca.M = B; ca.N = L.c_proj.N; ca.K = L.c_proj.Kpad;
             ca.cpb = L.c_proj.cpb; ca.h_xp = e->h_xp; ca.out_KS = D / 16;
             if (fused && !attn_poisons) { ca.poison = e->xp_mlp; ca.poison_bytes = (unsigned)pat_bytes; }
             if (cols_poisons_xpa) { ca.poison2 = e->xp_a; ca.poison2_bytes = xpa_bytes; }

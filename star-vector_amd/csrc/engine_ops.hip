@@ -508,6 +508,13 @@ extern "C" int sv_debug_set_col_tiles(int32_t col_tiles) {
     return 0;
 }
 
+extern "C" int sv_debug_cols_rowhalf_launches(int64_t* launches, int64_t* halves) {
+    if (!launches || !halves) return fail(SV_EINVAL, "sv_debug_cols_rowhalf_launches: null argument");
+    long long l = 0, h = 0;
+    cols_rowhalf_launches(&l, &h);
+    *launches = (int64_t)l; *halves = (int64_t)h;
+    return 0;
+}
 extern "C" int sv_debug_tailsplit_launches(int64_t* count) {
     if (!count) return fail(SV_EINVAL, "sv_debug_tailsplit_launches: null argument");
     *count = (int64_t)tailsplit_launches();
@@ -1078,7 +1085,7 @@ extern "C" int sv_op_decode_proj_fold(const void* x, const void* Wp_, const void
     launch_fold_prepare(Wfp, (const bf16_t*)gamma, (const bf16_t*)beta, (const bf16_t*)bf_, Wff, c1, c2, F, Fpad, D, st);
     ColsArgs ca;
     memset(&ca, 0, sizeof(ca));
-    ca.xp = xp; ca.Wp = Wpp; ca.bias = (const bf16_t*)bp; ca.MT = 1; ca.N = D; ca.K = Kp; ca.cpb = cpb; ca.h_xp = hxp; ca.out_KS = D / 16;
+    ca.xp = xp; ca.Wp = Wpp; ca.bias = (const bf16_t*)bp; ca.MT = 1; ca.M = M; ca.N = D; ca.K = Kp; ca.cpb = cpb; ca.h_xp = hxp; ca.out_KS = D / 16;
     if (launch_gemm_cols(ca, st)) return fail(SV_ENOTSUP, "sv_op_decode_proj_fold: no kernel for this shape");
     SkinnyArgs a;
     memset(&a, 0, sizeof(a));

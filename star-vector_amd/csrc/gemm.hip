@@ -1555,11 +1555,6 @@ __global__ __launch_bounds__(128) void gemm_skinny_tailsplit_kernel(const bf16_t
 std::atomic<long long> g_tailsplit_launches{0};     // host-side count of tail-split launches (sv_debug_tailsplit_launches)
 long long tailsplit_launches() { return g_tailsplit_launches.load(std::memory_order_relaxed); }
 
-// An A/B switch of the environment, read per call (A/B inside one process; a captured graph keeps its choice): unset = dflt
-static int env_switch(const char* name, int dflt) {
-    const char* ev = getenv(name);
-    return ev ? atoi(ev) : dflt;
-}
 // CUs of the current device (0: the query failed).  Cached per device id; concurrent first calls store the same value.
 static int device_cus() {
     constexpr int MAXDEV = 64;

@@ -2,12 +2,18 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <atomic>
 #include "common.h"
 
 namespace sv {
 
 inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
+// An A/B switch of the environment, read per call (A/B inside one process; a captured graph keeps its choice): unset = dflt
+inline int env_switch(const char* name, int dflt) {
+    const char* ev = getenv(name);
+    return ev ? atoi(ev) : dflt;
+}
 
 // ---- weights -----------------------------------------------------------------------------------
 // src: [N][K] row-major (bf16 if src_is_f32==0 else float).  dst: packed [Npad/32][Kpad/16][64][8].
@@ -160,7 +166,9 @@ struct ColsArgs {
     const bf16_t* Wp;                // packed weight [Npad/32][K/16][64][8] (the image the 32-column kernels read)
     const bf16_t* bias;              // [N] or nullptr
     int MT, N, K;                    // K multiple of 32
-    int cpb;                         // output columns per block (<= 32): cols_pick_cpb(N, K)
+    int M;                           // live rows when MT == 1 (0: not known = all 32); rows beyond it need not be written.  The row-half form
+                                     // (one row tile, K <= 2048, N / 16 a multiple of 8: 16 rows x 16 columns per block) launches ceil(M / 16) halves
+    int cpb;                         // output columns per block (<= 32) of the 32-row form: cols_pick_cpb(N, K)
     bf16_t* h_xp; int out_KS;        // residual stream in fragment order, N = 16 * out_KS columns: h = bf(h + bf(x W^T + b)), in place
     void* poison; unsigned poison_bytes; // optional: a buffer the blocks fill with 0xFF bytes (the fused MLP launch behind this one
                                      // recognises unwritten activations by that pattern); a multiple of 16 bytes
@@ -169,6 +177,7 @@ struct ColsArgs {
 };
 int cols_pick_cpb(int N, int K);
 int launch_gemm_cols(const ColsArgs& a, hipStream_t st);        // 0 = ok, -1 = unsupported shape
+void cols_rowhalf_launches(long long* launches, long long* halves);      // host-side counts since load: row-half launches and the row halves they ran
 int init_cols_kernels();
 void launch_fold_prepare(const bf16_t* Wp, const bf16_t* gamma, const bf16_t* beta, const bf16_t* bias, bf16_t* Wf, float* c1, float* c2,
                          int N, int Npad, int K, hipStream_t st);

@@ -1261,6 +1261,13 @@ def tailsplit_launches() -> int:
     return n.value
 
 
+def cols_rowhalf_launches() -> tuple[int, int]:
+    """Process-wide (launches, row halves) of the decode output projection's row-half form (sv_debug_cols_rowhalf_launches)."""
+    n, h = C.c_int64(0), C.c_int64(0)
+    check(_lib.load().sv_debug_cols_rowhalf_launches(C.byref(n), C.byref(h)), "sv_debug_cols_rowhalf_launches")
+    return n.value, h.value
+
+
 def op_linear_skinny(x, W, bias=None, splitk=1):
     lib = _lib.load()
     x = _need(x, torch.bfloat16, "x"); W = _need(W, torch.bfloat16, "W")
