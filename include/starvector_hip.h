@@ -49,6 +49,7 @@ extern "C" {
 #define SV_ABI_VERSION 9
 #define SV_WEIGHT_BF16 0
 #define SV_WEIGHT_FP8_E4M3 1
+#define SV_WEIGHT_MXFP4 2
 
 enum {
     SV_OK = 0,
@@ -100,7 +101,16 @@ typedef struct sv_config {
     int32_t weight_dtype;      /* SV_WEIGHT_BF16 (reference precision) or SV_WEIGHT_FP8_E4M3: decoder Linear weights and the
                                   lm_head are quantised at load to OCP e4m3 with one scale per output row (BASELINE config 5,
                                   "fp8 weights"): the decode step streams half the bytes; activations, accumulation and every
-                                  other tensor stay as they are.  Not a reference numerics mode: see DESIGN.md. */
+                                  other tensor stay as they are.  Not a reference numerics mode: see DESIGN.md.
+                                  SV_WEIGHT_MXFP4: the same tensors quantised at load to OCP MXFP4 -- per output row, blocks of 32
+                                  consecutive k (K zero-padded), one e8m0 scale byte E + 127 per block with E = floor(log2(amax)) - 2
+                                  clamped to [-125, 125] (E = 0, codes 0 for an all-zero block), e2m1 codes = W / 2^E rounded to
+                                  {0, .5, 1, 1.5, 2, 3, 4, 6} with its sign, ties to the even mantissa bit, magnitudes above 6
+                                  saturating; amax is taken from the tensor as handed (fp32 sources are not rounded to bf16 first).
+                                  The decode step streams 4.25 bits per weight.  Every dequantised weight is exactly a bf16 number:
+                                  the engine computes what a bf16 engine computes over dequant(quant(W)), except for the K-summation
+                                  order of the decode GEMMs.  Every decoder K must be a multiple of 128 (else sv_create: SV_ENOTSUP,
+                                  naming the Linear).  Embedding lookups keep the bf16 table.  Not a reference numerics mode. */
     int32_t exclusive_device;  /* != 0: this engine is the only thing launching kernels on its GPU while it decodes (the deployment the
                                   path is built for: one process per GPU).  Enables the decode launches that need ALL their
                                   workgroups resident at once (mlp_fused_kernel: the MLP half of a layer as one launch, 256 blocks, one

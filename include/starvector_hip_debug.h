@@ -36,12 +36,13 @@ extern "C" {
  *   sv_debug_gemm_plan        what the big-M GEMM dispatch does with an M x N x K problem: out5 = {peel the row remainder,
  *                             remainder rows, remainder as a 128^2 tile row (else one wave per 32x32 tile), main part on the
  *                             256^2 kernel, modelled time in us}; every choice computes the same bits */
-/*   sv_debug_skinny_plan      how a decode GEMM (rows <= 64, W [N][K], split-K `splitk`, bf16 or fp8 weights) is launched:
+/*   sv_debug_skinny_plan      how a decode GEMM (rows <= 64, W [N][K], split-K `splitk`, weights of format `wfmt` = SV_WEIGHT_*) is launched:
  *                             out2 = {waves per block = how K is cut inside a block, i.e. the order in which a row's partial
  *                             sums are added -- a function of the GEMM only, never of `rows`; 1 when a block carries two
- *                             32-row tiles (33..64 rows: the weights are streamed once)} */
+ *                             32-row tiles (33..64 rows: the weights are streamed once; never with MXFP4 weights, whose kernel puts
+ *                             the row tiles on grid.z); waves 0: no kernel cuts this K (fp8, MXFP4)} */
 int  sv_debug_resample_coeffs(int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* taps, int32_t cap);
-int  sv_debug_skinny_plan(int32_t rows, int32_t N, int32_t K, int32_t splitk, int32_t fp8, int32_t* out2);
+int  sv_debug_skinny_plan(int32_t rows, int32_t N, int32_t K, int32_t splitk, int32_t wfmt, int32_t* out2);
 /* The A/B switches of an engine: one bit each of the mask that the environment variable SV_EXP sets at sv_create and sv_debug_set_exp sets
  * on a live engine.  Mask 0 is the product path; every switch computes the same tokens unless its line says otherwise.
  * The values are stable: logs under profiles/ name them by number.  star-vector_amd/engine.py mirrors the enum as the IntFlag `Exp`. */
@@ -69,9 +70,10 @@ int  sv_debug_exp_known(void);
 int  sv_debug_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t act, int32_t* out5);
 /*   sv_debug_decode_plan      what sv_create decides for a decoder Linear W [N][K] when the engine decodes `rows` (<= 64) rows at a
  *                             time on a GPU with `num_cus` CUs: out2 = {split-K factor (1 when whole_k: c_fc / lm_head keep the whole
- *                             K for their epilogue), column tiles per block of the two-row-tile kernel (1 for rows <= 32)} -- plain
+ *                             K for their epilogue), column tiles per block of the two-row-tile kernel (1 for rows <= 32) or, for
+ *                             wfmt = SV_WEIGHT_MXFP4, of the MXFP4 decode kernel (1, 2 or 4 at any row count)} -- plain
  *                             host arithmetic (engine_core.hip: pick_splitk / pick_decode_plan), pinned by the CPU tests */
-int  sv_debug_decode_plan(int32_t rows, int32_t N, int32_t K, int32_t fp8, int32_t whole_k, int32_t num_cus, int32_t* out2);
+int  sv_debug_decode_plan(int32_t rows, int32_t N, int32_t K, int32_t wfmt, int32_t whole_k, int32_t num_cus, int32_t* out2);
 /*   sv_debug_attn_plan        the decode attention's context-split constants of an engine: out2 = {the most blocks a sequence's context
  *                             is split over (so that rows x KV heads x splits covers the CUs, <= 8), 32-key groups a block takes
  *                             before another split joins (8 where rows x KV heads alone cover the CUs, else 4)} -- functions of the
@@ -290,6 +292,22 @@ int  sv_op_linear_fp8(const void* x, const void* W, const void* bias, const void
  * k = 16*ks + 8*(l >> 5) + 0..7.  Rows >= N are zero in both images. */
 int  sv_op_pack_weight_fp8(const void* W, int32_t w_is_f32, int32_t N, int32_t K, float* scale_out, void* wq_out, void* wp_out,
                            sv_stream stream);
+/* MXFP4 weights (weight_dtype = SV_WEIGHT_MXFP4, the format stated at sv_config.weight_dtype).  The quantiser on its own, as sv_load_weight runs
+ * it: W [N][K] row-major (bf16; fp32 when w_is_f32 != 0), K % 64 == 0, Npad = N rounded up to 32.  scale_out uint8 [Npad][K/32]: the e8m0 bytes
+ * (127 for all-zero blocks and rows >= N).  w4_out [Npad/32 * K/64 * 1088] bytes: the decode image, groups [Npad/32][K/64] of 1088 bytes --
+ * bytes 0..1023 = [64 lanes][16 B], lane 32*((k/8)&1) + n%32, 32-bit word (k/16)&3 of the lane, code k%8 in nibble k%8 of the word (bits 4*(k%8)..+3:
+ * sign, then the e2m1 index); bytes 1024..1087 = [32 rows][2] scale bytes, row n%32, byte (k/32)&1.  wp_out bf16 [Npad * K]: the dequantised
+ * values in the packed layout of the bf16 weights. */
+int  sv_op_pack_weight_mxfp4(const void* W, int32_t w_is_f32, int32_t N, int32_t K, void* scale_out, void* w4_out, void* wp_out,
+                             sv_stream stream);
+/* sv_op_linear_skinny with the weight quantised that way: y = x . dequant(quant(W))^T + bias, fp32, through gemm_skinny_mxfp4_kernel and fp32
+ * slabs; (K/16/splitk) % 8 == 0; col_tiles = column tiles per block (1, 2, 4: identical bits; 0 = the launcher's default); scale_out uint8
+ * [N][K/32] (device, optional) receives the scale bytes.  M may exceed 32: row tiles ride on grid.z. */
+int  sv_op_linear_skinny_mxfp4(const void* x, const void* W, const void* bias, void* y_f32, void* scale_out, int32_t M, int32_t N, int32_t K,
+                               int32_t splitk, int32_t col_tiles, sv_stream stream);
+/* sv_op_linear_skinny_epi with the weight quantised that way (the SkinnyArgs of an mxfp4 engine's c_fc and lm_head launches); K % 128 == 0 */
+int  sv_op_linear_skinny_epi_mxfp4(const void* x, const void* W, const void* bias, void* y, void* scale_out, int32_t M, int32_t N, int32_t K,
+                                   int32_t act, int32_t out_f32, int32_t col_tiles, sv_stream stream);
 /* the lm_head form with the greedy selection folded into its epilogue (what a plain greedy sv_generate runs per decode step): y_f32 [M][N]
  * (optional, device) = bf16-rounded fp32 logits, host_idx [M] (HOST) = arg-max column per row -- lowest index on ties, NaN never wins,
  * 0x7fffffff when a row has no comparable score; M <= 32 */

@@ -238,6 +238,9 @@ DEBUG_PROTOTYPES = {
     "sv_op_linear_skinny_epi_fp8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "sv_op_linear_fp8": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "sv_op_pack_weight_fp8": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
+    "sv_op_pack_weight_mxfp4": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
+    "sv_op_linear_skinny_mxfp4": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "sv_op_linear_skinny_epi_mxfp4": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "sv_op_lm_head_argmax": (_I, [_P, _P, _P, C.POINTER(_I), _I, _I, _I, _P]),
     "sv_op_decode_proj_fold": (_I, [_P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "sv_bench_linear": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(C.c_double), _P]),

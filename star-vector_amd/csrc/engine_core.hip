@@ -205,7 +205,8 @@ static void reg_ln(sv_engine* e, const std::string& base, LNp* ln, size_t n) {
 // split 2: 288 blocks = one full round + 32 blocks at 2 x 590 KB per busy CU: 45.8 us measured against 31 us for the bytes).
 // Pick the s <= 8 (the slab buffer and the consumers' limit) with the best fill, preferring fewer slabs on near-ties; each
 // block keeps >= 16 k-steps so that its 8 waves still have a stream to pipeline.
-static int pick_splitk(int n_tiles, int KS, int num_cus, bool fp8) {
+static int pick_splitk(int n_tiles, int KS, int num_cus, int wfmt) {
+    const bool fp8 = wfmt == SV_WFMT_FP8;
     // small GEMMs (StarVector-1B's c_attn / attention c_proj: < 40 KB per CU) are one latency-bound round trip per wave: the fill
     // model does not describe them, and more slabs only cost their consumer -> the smallest power of two that reaches one block per CU
     if ((long)n_tiles * KS < 24L * 1024) {
@@ -221,7 +222,7 @@ static int pick_splitk(int n_tiles, int KS, int num_cus, bool fp8) {
         if (KS % s) continue;
         const int per = KS / s;
         if (s > 1 && per < 16) continue;
-        if (per % (fp8 ? 4 : 2)) continue;                       // the kernels cut a block's K over 2..16 waves (fp8: pairs of k-steps)
+        if (per % (wfmt == SV_WFMT_MXFP4 ? 8 : fp8 ? 4 : 2)) continue;      // the kernels cut a block's K over 2..16 waves (fp8: pairs of k-steps, mxfp4: groups of 4)
         const long nb = (long)n_tiles * s;
         const long rounds = (nb + num_cus - 1) / num_cus;
         const double fill = (double)nb / (double)(rounds * num_cus);          // 1 = every CU equally loaded
@@ -231,15 +232,35 @@ static int pick_splitk(int n_tiles, int KS, int num_cus, bool fp8) {
     return best;
 }
 
+// Column tiles per block of the MXFP4 decode GEMM (1, 2, 4: a block re-reads 4 / col_tiles activation bytes out of L2 per weight byte): the
+// largest value that still leaves enough blocks for the chip -- 0.8 blocks per CU for 8-wave blocks, 2 per CU for the 2- / 4-wave blocks of a K
+// that cuts no finer (StarVector-8B's c_attn: a block's few waves then carry col_tiles times the work).  Fitted to the per-launch times of the
+// twenty (Linear, rows) shapes of profiles/mxfp4_weights.md, where it names the fastest value for every shape outside the noise.
+static int mxfp4_col_tiles(int tiles, int KS, int splitk, int MT, int num_cus) {
+    const long need = skinny_waves_mxfp4(KS, splitk) == 8 ? (4L * num_cus + 4) / 5 : 2L * num_cus;
+    for (int ct = 4; ct > 1; ct >>= 1)
+        if ((long)((tiles + ct - 1) / ct) * splitk * MT >= need) return ct;
+    return 1;
+}
+
 // 33..64 rows (two row tiles per block): at that height every block re-reads 2 (bf16) / 4 (fp8) activation bytes per weight byte out
 // of L2 and the L2 -> CU side bounds the launch (tools/diag/mem_mix.hip), so a block may carry two or three column tiles per loaded
 // activation fragment.  (column tiles per block, split-K) are picked together: modelled time = the busiest CU's bytes (weights + activations
 // over its blocks) relative to an even spread, plus the slab cost.  Only shapes the two-row-tile kernel takes are candidates.
-void sveng::pick_decode_plan(const Linear& l, int MT, int num_cus, bool fp8, bool whole_k, int* splitk, int* col_tiles) {
+void sveng::pick_decode_plan(const Linear& l, int MT, int num_cus, int wfmt, bool whole_k, int* splitk, int* col_tiles) {
     const int tiles = l.Npad / 32, KS = l.Kpad / 16;
+    const bool fp8 = wfmt == SV_WFMT_FP8;
     *col_tiles = 1;
+    if (wfmt == SV_WFMT_MXFP4) {
+        // its own kernel at every row count (row tiles on grid.z); a wave's range is whole groups of 4 k-steps, two waves at least: split-K
+        // shrinks until a cut fits (none: sv_create refuses the engine)
+        *splitk = whole_k ? 1 : pick_splitk(tiles, KS, num_cus, wfmt);
+        while (*splitk > 1 && !skinny_waves_mxfp4(KS, *splitk)) --*splitk;
+        *col_tiles = mxfp4_col_tiles(tiles, KS, *splitk, MT, num_cus);
+        return;
+    }
     if (MT != 2 || (long)tiles * KS < 24L * 1024) {
-        *splitk = whole_k ? 1 : pick_splitk(tiles, KS, num_cus, fp8);
+        *splitk = whole_k ? 1 : pick_splitk(tiles, KS, num_cus, wfmt);
         return;
     }
     const double wb = fp8 ? 512.0 : 1024.0, ab = 1024.0 * MT;
@@ -252,14 +273,14 @@ void sveng::pick_decode_plan(const Linear& l, int MT, int num_cus, bool fp8, boo
             const int per = KS / s;
             if (s > 1 && per < 16) continue;
             int waves = 0, two = 0;
-            skinny_plan(l.Npad, l.Kpad, s, fp8 ? 1 : 0, MT, &waves, &two);
+            skinny_plan(l.Npad, l.Kpad, s, wfmt, MT, &waves, &two);
             if (!two || (nt >= 2 && waves != 8)) continue;
             const long nb = (long)((tiles + nt - 1) / nt) * s;
             const long rounds = (nb + num_cus - 1) / num_cus;
             const double cost = (double)rounds * per * (nt * wb + ab) / ideal + 0.015 * s;
             if (cost < best_cost - 1e-9) { best_cost = cost; best_s = s; best_nt = nt; }
         }
-    if (!best_s) { *splitk = whole_k ? 1 : pick_splitk(tiles, KS, num_cus, fp8); return; }
+    if (!best_s) { *splitk = whole_k ? 1 : pick_splitk(tiles, KS, num_cus, wfmt); return; }
     *splitk = best_s;
     *col_tiles = best_nt;
 }
@@ -398,8 +419,8 @@ extern "C" int sv_create(const sv_config* cfg, sv_engine** out) {
     // vit_embed_lnpre_kernel (CLIP token assembly + ln_pre) keeps a row in 4 chunks of 8 columns per lane: wider rows would be cut short
     if (!v2 && c.vit_width > 2048) return fail(SV_EINVAL, "vit_width %d: the CLIP (v1) tower takes vit_width <= 2048", c.vit_width);
     if (v2 && (c.vit_mlp < 64 || c.vit_mlp % 64 || !(c.rope_theta > 1.f))) return fail(SV_EINVAL, "bad vit_mlp / rope_theta");
-    if (c.weight_dtype != SV_WEIGHT_BF16 && c.weight_dtype != SV_WEIGHT_FP8_E4M3)
-        return fail(SV_EINVAL, "weight_dtype must be SV_WEIGHT_BF16 (0) or SV_WEIGHT_FP8_E4M3 (1)");
+    if (c.weight_dtype != SV_WEIGHT_BF16 && c.weight_dtype != SV_WEIGHT_FP8_E4M3 && c.weight_dtype != SV_WEIGHT_MXFP4)
+        return fail(SV_EINVAL, "weight_dtype must be SV_WEIGHT_BF16 (0), SV_WEIGHT_FP8_E4M3 (1) or SV_WEIGHT_MXFP4 (2)");
     if (c.sliding_window < 0 || (!v2 && c.sliding_window != 0))
         return fail(SV_EINVAL, "sliding_window must be >= 0 (and 0 for the GPTBigCode decoder)");
     if (c.max_batch < 1 || c.max_seq_len < 2 || c.max_seq_len > c.n_positions)
@@ -485,16 +506,33 @@ extern "C" int sv_create(const sv_config* cfg, sv_engine** out) {
         // sums in slab order; c_fc keeps the whole K (its bias + GELU epilogue needs the finished sum)
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, c.device) == hipSuccess && prop.multiProcessorCount > 0) e->num_cus = prop.multiProcessorCount;
-        const bool fp8 = c.weight_dtype == SV_WEIGHT_FP8_E4M3;
-        if (fp8) e->lm_head.fp8 = true;                  // decoder Linears + lm_head stream as fp8 at decode time
-        { int sk1 = 1; pick_decode_plan(e->lm_head, (c.max_batch + 31) / 32, e->num_cus, fp8, true, &sk1, &e->lm_head.col_tiles); }
+        const int wfmt = c.weight_dtype;                 // SV_WEIGHT_* == SV_WFMT_*
+        const bool fp8 = wfmt == SV_WFMT_FP8, mx4 = wfmt == SV_WFMT_MXFP4;
+        e->lm_head.wfmt = wfmt;                          // decoder Linears + lm_head stream in the quantised format at decode time
+        { int sk1 = 1; pick_decode_plan(e->lm_head, (c.max_batch + 31) / 32, e->num_cus, wfmt, true, &sk1, &e->lm_head.col_tiles); }
+        if (mx4 && !skinny_waves_mxfp4(e->lm_head.Kpad / 16, 1)) {
+            const int code = fail(SV_ENOTSUP, "mxfp4 weights: lm_head K=%d has no mxfp4 decode kernel (K %% 128 == 0 needed)", e->lm_head.Kpad);
+            sv_destroy(e);
+            return code;
+        }
         const bool plan_log = getenv("SV_GEMM_AUTOTUNE_LOG") && atoi(getenv("SV_GEMM_AUTOTUNE_LOG"));
+        static const char* const lin_names[4] = {"attn.c_attn", "attn.c_proj", "mlp.c_fc", "mlp.c_proj"};
         for (DecLayer& L : e->dec) {
             Linear* ls[4] = {&L.c_attn, &L.c_proj, &L.c_fc, &L.c_proj2};
-            for (Linear* l : ls) {
-                l->fp8 = fp8;
+            for (int li = 0; li < 4; ++li) {
+                Linear* l = ls[li];
+                l->wfmt = wfmt;
                 const int KS = l->Kpad / 16;
-                pick_decode_plan(*l, (c.max_batch + 31) / 32, e->num_cus, fp8, l == &L.c_fc, &l->splitk, &l->col_tiles);
+                pick_decode_plan(*l, (c.max_batch + 31) / 32, e->num_cus, wfmt, l == &L.c_fc, &l->splitk, &l->col_tiles);
+                if (mx4) {
+                    // a wave's range is whole groups of 4 k-steps, two waves at least: shrink split-K until a cut fits
+                    while (l->splitk > 1 && !skinny_waves_mxfp4(KS, l->splitk)) --l->splitk;
+                    if (!skinny_waves_mxfp4(KS, l->splitk)) {
+                        const int code = fail(SV_ENOTSUP, "mxfp4 weights: %s K=%d has no mxfp4 decode kernel (K %% 128 == 0 needed)", lin_names[li], l->Kpad);
+                        sv_destroy(e);
+                        return code;
+                    }
+                }
                 if (fp8) {
                     // the fp8 kernel wants an even number (>= 2 per wave pair) of k-steps per wave: shrink split-K until it fits
                     while (l->splitk > 1 && (KS % l->splitk != 0 || (KS / l->splitk) % 4 != 0)) --l->splitk;
@@ -506,7 +544,7 @@ extern "C" int sv_create(const sv_config* cfg, sv_engine** out) {
                 }
                 if (plan_log && &L == &e->dec[0])
                     fprintf(stderr, "[starvector_hip] decode plan N=%d K=%d rows<=%d %s: split-K %d, column tiles per block %d\n", l->Npad, l->Kpad,
-                            32 * ((c.max_batch + 31) / 32), fp8 ? "fp8" : "bf16", l->splitk, l->col_tiles);
+                            32 * ((c.max_batch + 31) / 32), mx4 ? "mxfp4" : fp8 ? "fp8" : "bf16", l->splitk, l->col_tiles);
             }
         }
         if (plan_log)
@@ -644,7 +682,7 @@ extern "C" int sv_create(const sv_config* cfg, sv_engine** out) {
         // the row update + c_attn launch (rowops.hip): the projection's whole weight share per wave in registers (4 k-steps at
         // StarVector-1B, 9 at StarVector-8B: round 5 carried the launch to the 7-launch layer of the wide model), bf16 weights, one row tile
         const Linear& ca = e->dec[0].c_attn; const Linear& dn = e->dec[0].c_proj2;
-        e->rc_fused_ok = c.weight_dtype == SV_WEIGHT_BF16 && e->MT == 1 && !ca.fp8 &&
+        e->rc_fused_ok = c.weight_dtype == SV_WEIGHT_BF16 && e->MT == 1 && ca.wfmt == SV_WFMT_BF16 &&
                          rowln_cattn_fits(D, ca.Npad, ca.Kpad, ca.splitk, dn.splitk, e->num_cus) && rowln_cattn_resident(D > 2048);
         // narrow rows (StarVector-1B): the first poll 3.9 us after block start; wide rows (StarVector-8B): the weight stream is the timer and the
         // GEMM blocks' hold-back in front of it measured best at 0 (profiles/rowln_cattn_r05_ab.log, section 8)
@@ -678,7 +716,16 @@ extern "C" int sv_load_weight(sv_engine* e, const char* name, const void* dev_pt
     if (s.kind == SLOT_LINEAR_W || s.kind == SLOT_WTE) {
         Linear* l = s.kind == SLOT_WTE ? &e->lm_head : s.lin;
         const bool pack = !(s.kind == SLOT_WTE && e->lm_head_explicit);
-        if (pack && l->fp8) {
+        if (pack && l->wfmt == SV_WFMT_MXFP4) {
+            // MXFP4 weight-only quantisation: 4-bit image for the decode kernel, bf16 image of the dequantised values for the big-M ones
+            const int roff = s.part_rows ? s.row_off : 0, rows = s.part_rows ? s.part_rows : l->N;
+            if (roff % 32) return fail(SV_EINVAL, "weight '%s': part offset %d is not a multiple of 32", name, roff);
+            if (!l->Wp) SVCHECK(dalloc(e, &l->Wp, (size_t)l->Npad * l->Kpad, s.part_rows != 0));
+            if (!l->W4) SVCHECK(dalloc(e, &l->W4, mxfp4_image_bytes(l->Npad, l->Kpad), s.part_rows != 0));
+            const size_t tile0 = (size_t)(roff / 32) * (l->Kpad / 16);
+            launch_pack_weight_mxfp4(dev_ptr, is_f32, l->Wp + tile0 * 512, l->W4 + (size_t)(roff / 32) * (l->Kpad / 64) * SV_MXFP4_GROUP, nullptr, rows,
+                                     l->K, round_up(rows, 32), l->Kpad, st);
+        } else if (pack && l->wfmt == SV_WFMT_FP8) {
             // e4m3 weight-only quantisation: fp8 image for the decode kernels, bf16 image of the same values for the big-M ones
             if (!l->Wp) SVCHECK(dalloc(e, &l->Wp, (size_t)l->Npad * l->Kpad, s.part_rows != 0));
             if (!l->Wq) SVCHECK(dalloc(e, &l->Wq, (size_t)l->Npad * l->Kpad, s.part_rows != 0));

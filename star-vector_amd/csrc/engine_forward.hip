@@ -38,7 +38,7 @@ static void gemm(sv_engine* e, int kind, const bf16_t* A, int lda, const Linear&
     if (e->prof_on) { g.tail_mark = tail_mark_cb; g.tail_ctx = &tc; }
     g.A = A; g.lda = lda; g.Wp = l.Wp; g.bias = l.bias; g.R = R; g.ldr = ldr; g.C = C; g.ldc = ldc;
     g.M = M; g.N = l.N; g.K = l.Kpad; g.act = act; g.out_f32 = out_f32;
-    g.cscale = l.fp8 ? l.wscale : nullptr;
+    g.cscale = l.wfmt == SV_WFMT_FP8 ? l.wscale : nullptr;
     g.seq_rows = (e->exp & SV_EXP_BATCH_REMAINDER) ? 0 : seq_rows;          // A/B: the batch-level remainder of rounds 2-5
     g.splitk_rows = (e->exp & SV_EXP_BATCH_REMAINDER) ? 0 : last_rows;
     g.tune_in_place = tune_in_place;
@@ -54,7 +54,7 @@ static void gemm_ragged(sv_engine* e, int kind, const bf16_t* A, int lda, const 
     if (e->prof_on) { g.tail_mark = tail_mark_cb; g.tail_ctx = &tc; }
     g.A = A; g.lda = lda; g.Wp = l.Wp; g.bias = l.bias; g.R = R; g.ldr = ldr; g.C = C; g.ldc = ldc;
     g.M = M; g.N = l.N; g.K = l.Kpad; g.act = act; g.out_f32 = 0;
-    g.cscale = l.fp8 ? l.wscale : nullptr;
+    g.cscale = l.wfmt == SV_WFMT_FP8 ? l.wscale : nullptr;
     launch_gemm_ragged(g, rows, n_rows, e->rag_rsave, st);
 }
 
@@ -199,7 +199,8 @@ static void lm_head_logits(sv_engine* e, int MT, const bf16_t* xp, hipStream_t s
     memset(&a, 0, sizeof(a));
     if (rc_enabled(e) && MT == 1 && xp != e->xp_a) { a.poison = e->xp_a; a.poison_bytes = (unsigned)((size_t)(e->cfg.hidden / 16) * 1024); }
     e->xpa_armed = a.poison != nullptr && lm_head_covers(e, a.poison_bytes);
-    a.xp = xp; a.Wp = e->lm_head.Wp; a.Wq = e->lm_head.Wq; a.wscale = e->lm_head.wscale; a.MT = MT; a.Npad = e->lm_head.Npad; a.K = e->lm_head.Kpad;
+    a.xp = xp; a.Wp = e->lm_head.Wp; a.Wq = e->lm_head.Wq; a.wscale = e->lm_head.wscale; a.MT = MT;      // (mxfp4: the prompt pass runs the bf16 image, W4 stays null)
+ a.Npad = e->lm_head.Npad; a.K = e->lm_head.Kpad;
     a.splitk = 1; a.out_mode = SK_OUT_F32; a.out_f32 = e->logits; a.ldo = e->Vpad; a.round_bf16 = 1;
     a.N = e->lm_head.N;
     a.col_tiles = e->lm_head.col_tiles;      // the engine's own plan: sv_debug_set_col_tiles never reaches an engine launch
@@ -633,7 +634,7 @@ void sveng::decode_forward(sv_engine* e, int B, hipStream_t st) {
     auto skinny = [&](const bf16_t* xp, const Linear& l, int out_mode, float* ws) {
         SkinnyArgs a;
         memset(&a, 0, sizeof(a));
-        a.xp = xp; a.Wp = l.Wp; a.Wq = l.Wq; a.wscale = l.wscale; a.MT = MT; a.Npad = l.Npad; a.K = l.Kpad; a.N = l.N;
+        a.xp = xp; a.Wp = l.Wp; a.Wq = l.Wq; a.wscale = l.wscale; a.W4 = l.W4; a.MT = MT; a.Npad = l.Npad; a.K = l.Kpad; a.N = l.N;
         a.out_mode = out_mode; a.col_tiles = l.col_tiles;
         if (out_mode == SK_OUT_PARTIAL) {
             a.splitk = l.splitk; a.ws = ws; a.ldws = e->ldws;

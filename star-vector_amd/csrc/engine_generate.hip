@@ -957,11 +957,11 @@ static int generate_attempt(sv_engine* e, const GenCall& c) {
     bool fused_sel = false;
     {
         int waves = 1, two = 0;
-        skinny_plan(e->lm_head.Npad, e->lm_head.Kpad, 1, e->lm_head.fp8 ? 1 : 0, (B + 31) / 32, &waves, &two);
+        skinny_plan(e->lm_head.Npad, e->lm_head.Kpad, 1, e->lm_head.wfmt, (B + 31) / 32, &waves, &two);
         // a capturing call (sv_generate_ex) takes the separate selection launch: the capture must read the logits row between the lm_head and
         // the selection, and the tokens are bit-identical either way (tests/test_gpu_e2e.py)
         // (a ban rewrites the logits row between the lm_head and the selection: the separate launch as well)
-        fused_sel = !sp->do_sample && !f.sel.pen && sp->min_new_tokens <= 0 && B <= 32 && !e->lm_head.fp8 && waves > 1 && !two && !(e->exp & SV_EXP_SEPARATE_ARGMAX) &&
+        fused_sel = !sp->do_sample && !f.sel.pen && sp->min_new_tokens <= 0 && B <= 32 && e->lm_head.wfmt == SV_WFMT_BF16 && waves > 1 && !two && !(e->exp & SV_EXP_SEPARATE_ARGMAX) &&
                     !e->cap_on && !ban && !e->ts_on && !e->tk_on;      // (the statistics / top-k launches read the row and the slice winners between the lm_head and the bookkeeping)
     }
     SVCHECK(f.start(fused_sel ? 64 * SV_AMAX_STRIDE : 0));

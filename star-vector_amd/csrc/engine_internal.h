@@ -48,9 +48,10 @@ using sveng::fail;
 struct Linear {
     bf16_t* Wp = nullptr;
     bf16_t* bias = nullptr;
-    bool fp8 = false;          // decoder weights quantised to e4m3 at load (sv_config.weight_dtype = 1)
-    uint8_t* Wq = nullptr;     //   decode image (launch_pack_weight_fp8); Wp then holds the SAME q values as bf16
-    float* wscale = nullptr;   //   per-output-row scale [Npad]
+    int wfmt = SV_WFMT_BF16;   // weight format (kernels.h SV_WFMT_*): decoder weights quantised at load when sv_config.weight_dtype != 0
+    uint8_t* Wq = nullptr;     //   fp8: decode image (launch_pack_weight_fp8); Wp then holds the SAME q values as bf16
+    float* wscale = nullptr;   //   fp8: per-output-row scale [Npad]
+    uint8_t* W4 = nullptr;     //   mxfp4: decode image (launch_pack_weight_mxfp4); Wp then holds the dequantised values (no scale)
     int N = 0, K = 0, Npad = 0, Kpad = 0;
     int splitk = 1;       // decode-path split-K factor (fp32 slabs summed by the consumer)
     int col_tiles = 1;    // column tiles per block of the two-row-tile decode kernel (33..64 rows; pick_decode_plan)
@@ -306,7 +307,7 @@ template <typename T>
 inline int dalloc(sv_engine* e, T** p, size_t count, bool zero = true) {
     return dev_alloc(e, reinterpret_cast<void**>(p), count * sizeof(T), zero);
 }
-void pick_decode_plan(const Linear& l, int MT, int num_cus, bool fp8, bool whole_k, int* splitk, int* col_tiles);
+void pick_decode_plan(const Linear& l, int MT, int num_cus, int wfmt, bool whole_k, int* splitk, int* col_tiles);
 int check_exp_mask(int mask, const char* who);      // SV_EINVAL (naming the bits) unless mask is a subset of SV_EXP_KNOWN
 // hipGraph capture of decode steps, shared by sv_generate (greedy, lookup and beam) and sv_cb_step through GraphSlot::use.  capture_steps: relaxed capture of `copies` calls of
 // one_step on `st` -> *g, instantiated -> *ge.  On failure the sticky HIP error is cleared, both handles are destroyed and nulled, and the

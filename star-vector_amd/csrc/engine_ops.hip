@@ -48,22 +48,24 @@ extern "C" int sv_debug_rowln_plan(int32_t D, int32_t N, int32_t splitk, int32_t
     return 0;
 }
 
-extern "C" int sv_debug_skinny_plan(int32_t rows, int32_t N, int32_t K, int32_t splitk, int32_t fp8, int32_t* out2) {
-    if (!out2 || rows < 1 || N < 1 || K < 16 || K % 16 || splitk < 1 || (K / 16) % splitk)
+extern "C" int sv_debug_skinny_plan(int32_t rows, int32_t N, int32_t K, int32_t splitk, int32_t wfmt, int32_t* out2) {
+    if (!out2 || rows < 1 || N < 1 || K < 16 || K % 16 || splitk < 1 || (K / 16) % splitk || wfmt < 0 || wfmt > SV_WFMT_MXFP4)
         return fail(SV_EINVAL, "sv_debug_skinny_plan: bad argument");
     int waves = 0, two = 0;
-    skinny_plan(round_up(N, 32), K, splitk, fp8, (rows + 31) / 32, &waves, &two);
+    skinny_plan(round_up(N, 32), K, splitk, wfmt, (rows + 31) / 32, &waves, &two);
     out2[0] = waves; out2[1] = two;
     return 0;
 }
 
-extern "C" int sv_debug_decode_plan(int32_t rows, int32_t N, int32_t K, int32_t fp8, int32_t whole_k, int32_t num_cus, int32_t* out2) {
-    if (!out2 || rows < 1 || rows > 64 || N < 1 || K < 16 || K % 16 || num_cus < 1)
+extern "C" int sv_debug_decode_plan(int32_t rows, int32_t N, int32_t K, int32_t wfmt, int32_t whole_k, int32_t num_cus, int32_t* out2) {
+    const bool fp8 = wfmt == SV_WFMT_FP8;
+    if (!out2 || rows < 1 || rows > 64 || N < 1 || K < 16 || K % 16 || num_cus < 1 || wfmt < 0 || wfmt > SV_WFMT_MXFP4)
         return fail(SV_EINVAL, "sv_debug_decode_plan: bad argument");
     Linear l;
     l.N = N; l.K = K; l.Npad = round_up(N, 32); l.Kpad = K;
     int sk = 1, ct = 1;
-    pick_decode_plan(l, (rows + 31) / 32, num_cus, fp8 != 0, whole_k != 0, &sk, &ct);
+    pick_decode_plan(l, (rows + 31) / 32, num_cus, wfmt, whole_k != 0, &sk, &ct);
+    if (wfmt == SV_WFMT_MXFP4) while (sk > 1 && !skinny_waves_mxfp4(K / 16, sk)) --sk;                  // as sv_create does
     if (fp8) while (sk > 1 && ((K / 16) % sk != 0 || ((K / 16) / sk) % 4 != 0)) --sk;          // as sv_create does
     out2[0] = sk; out2[1] = ct;
     return 0;
@@ -1012,6 +1014,81 @@ extern "C" int sv_op_linear_skinny_epi_fp8(const void* x, const void* W, const v
         return fail(SV_EINVAL, "sv_op_linear_skinny_epi_fp8: bad argument (K %% 64 == 0 required)");
     if (!out_f32 && N % 8) return fail(SV_EINVAL, "sv_op_linear_skinny_epi_fp8: bf16 output needs N %% 8 == 0");
     return op_linear_skinny_epi_run(x, W, bias, y, scale_out, M, N, K, act, out_f32, true, (hipStream_t)stream);
+}
+
+// ---- MXFP4 weights (csrc/mxfp4/mxfp4.hip; the format: kernels.h launch_pack_weight_mxfp4) ----
+// the quantiser on its own, exactly as sv_load_weight calls it: W [N][K] (bf16, or fp32 when w_is_f32) -> scale_out uint8 [Npad][K/32] (the e8m0
+// bytes, Npad = N rounded up to 32), w4_out = the raw decode image (Npad/32 * K/64 * 1088 bytes), wp_out bf16 [Npad * K] = the raw bf16 image
+extern "C" int sv_op_pack_weight_mxfp4(const void* W, int32_t w_is_f32, int32_t N, int32_t K, void* scale_out, void* w4_out, void* wp_out,
+                                       sv_stream stream) {
+    if (!W || !scale_out || !w4_out || !wp_out || N < 1 || K < 64 || K % 64)
+        return fail(SV_EINVAL, "sv_op_pack_weight_mxfp4: bad argument (K %% 64 == 0 required)");
+    hipStream_t st = (hipStream_t)stream;
+    launch_pack_weight_mxfp4(W, w_is_f32 != 0, (bf16_t*)wp_out, (uint8_t*)w4_out, (uint8_t*)scale_out, N, K, round_up(N, 32), K, st);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// the MXFP4 decode GEMM through launch_gemm_skinny, the SkinnyArgs an mxfp4 engine builds: out_mode SK_OUT_PARTIAL (slabs, reduced here with the
+// bias), SK_OUT_PACKED_ACT or SK_OUT_F32 (split-K 1).  col_tiles 0 = the launcher's default.
+static int op_linear_skinny_mxfp4_run(const void* x, const void* W, const void* bias, void* y, void* scale_out, int M, int N, int K, int splitk,
+                                      int col_tiles, int out_mode, int act, hipStream_t st) {
+    TmpBufs tmp;
+    const int Npad = round_up(N, 32), MT = (M + 31) / 32, R = MT * 32;
+    bf16_t *Wp, *xp, *oxp = nullptr;
+    uint8_t *W4, *sc;
+    float* of;
+    SVCHECK(tmp.get(&Wp, (size_t)Npad * K));
+    SVCHECK(tmp.get(&W4, mxfp4_image_bytes(Npad, K)));
+    SVCHECK(tmp.get(&sc, (size_t)Npad * (K / 32)));
+    SVCHECK(tmp.get(&xp, (size_t)R * K));
+    SVCHECK(tmp.get(&of, (size_t)(out_mode == SK_OUT_PARTIAL ? splitk : 1) * R * Npad));
+    HIPCHECK(hipMemsetAsync(xp, 0, (size_t)R * K * 2, st));
+    launch_pack_weight_mxfp4(W, 0, Wp, W4, sc, N, K, Npad, K, st);
+    pack_rows((const bf16_t*)x, K, xp, M, K, st);
+    SkinnyArgs a;
+    memset(&a, 0, sizeof(a));
+    a.xp = xp; a.Wp = Wp; a.W4 = W4; a.MT = MT; a.Npad = Npad; a.K = K; a.splitk = splitk; a.N = N; a.col_tiles = col_tiles; a.out_mode = out_mode;
+    if (out_mode == SK_OUT_PARTIAL) { a.ws = of; a.ldws = Npad; }
+    else if (out_mode == SK_OUT_F32) { a.out_f32 = of; a.ldo = Npad; a.round_bf16 = 1; }
+    else {
+        SVCHECK(tmp.get(&oxp, (size_t)R * Npad));
+        a.bias = (const bf16_t*)bias; a.act = act; a.out_xp = oxp; a.out_KS = Npad / 16;
+    }
+    if (!launch_gemm_skinny_mxfp4(a, st)) return fail(SV_ENOTSUP, "mxfp4 decode GEMM: K=%d with split-K %d has no kernel", K, splitk);
+    if (out_mode == SK_OUT_PARTIAL) reduce_partials(of, splitk, R, Npad, (const bf16_t*)bias, (float*)y, M, N, st);
+    else if (out_mode == SK_OUT_F32) HIPCHECK(hipMemcpy2DAsync(y, (size_t)N * 4, of, (size_t)Npad * 4, (size_t)N * 4, M, hipMemcpyDeviceToDevice, st));
+    else if (N == Npad) unpack_rows(oxp, (bf16_t*)y, N, M, N, st);
+    else {
+        bf16_t* yp;                                   // (row tiles of Npad / 16 k-steps: see op_linear_skinny_epi_run)
+        SVCHECK(tmp.get(&yp, (size_t)M * Npad));
+        unpack_rows(oxp, yp, Npad, M, Npad, st);
+        HIPCHECK(hipMemcpy2DAsync(y, (size_t)N * 2, yp, (size_t)Npad * 2, (size_t)N * 2, M, hipMemcpyDeviceToDevice, st));
+    }
+    if (scale_out) HIPCHECK(hipMemcpyAsync(scale_out, sc, (size_t)N * (K / 32), hipMemcpyDeviceToDevice, st));
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// y fp32 [M][N] = x . dequant(quant(W))^T + bias through fp32 slabs; scale_out uint8 [N][K/32] (optional) returns the scale bytes
+extern "C" int sv_op_linear_skinny_mxfp4(const void* x, const void* W, const void* bias, void* y_f32, void* scale_out, int32_t M, int32_t N,
+                                         int32_t K, int32_t splitk, int32_t col_tiles, sv_stream stream) {
+    if (!x || !W || !y_f32 || M < 1 || N < 1 || K < 64 || K % 64 || splitk < 1 || splitk > 8 || !skinny_waves_mxfp4(K / 16, splitk) ||
+        !(col_tiles == 0 || col_tiles == 1 || col_tiles == 2 || col_tiles == 4))
+        return fail(SV_EINVAL, "sv_op_linear_skinny_mxfp4: bad argument (K %% 64 == 0, (K/16/splitk) %% 8 == 0, col_tiles 0, 1, 2 or 4 required)");
+    return op_linear_skinny_mxfp4_run(x, W, bias, y_f32, scale_out, M, N, K, splitk, col_tiles, SK_OUT_PARTIAL, 0, (hipStream_t)stream);
+}
+
+// the two fused epilogues (split-K 1) as sv_op_linear_skinny_epi states them, the SkinnyArgs of an mxfp4 engine's c_fc and lm_head
+extern "C" int sv_op_linear_skinny_epi_mxfp4(const void* x, const void* W, const void* bias, void* y, void* scale_out, int32_t M, int32_t N,
+                                             int32_t K, int32_t act, int32_t out_f32, int32_t col_tiles, sv_stream stream) {
+    if (!x || !W || !y || M < 1 || N < 1 || K < 64 || K % 64 || !skinny_waves_mxfp4(K / 16, 1) ||
+        !(col_tiles == 0 || col_tiles == 1 || col_tiles == 2 || col_tiles == 4))
+        return fail(SV_EINVAL, "sv_op_linear_skinny_epi_mxfp4: bad argument (K %% 128 == 0, col_tiles 0, 1, 2 or 4 required)");
+    if (!out_f32 && N % 8) return fail(SV_EINVAL, "sv_op_linear_skinny_epi_mxfp4: bf16 output needs N %% 8 == 0");
+    return op_linear_skinny_mxfp4_run(x, W, bias, y, scale_out, M, N, K, 1, col_tiles, out_f32 ? SK_OUT_F32 : SK_OUT_PACKED_ACT, act, (hipStream_t)stream);
 }
 
 // the lm_head form of the decode GEMM with the greedy selection folded into its epilogue (gemm.hip, SkinnyArgs::amax): y_f32 [M][N]

@@ -2190,9 +2190,14 @@ static bool launch_gemm_skinny_mt2(const SkinnyArgs& a, hipStream_t st) {
     return false;       // 16-wave (narrow outputs) and 1/2-wave (tiny K) shapes keep one row tile per block
 }
 
-void skinny_plan(int Npad, int K, int splitk, int fp8, int MT, int* waves, int* two_row_tiles) {
+void skinny_plan(int Npad, int K, int splitk, int wfmt, int MT, int* waves, int* two_row_tiles) {
     const int KS = K / 16;
-    const int w = fp8 ? skinny_waves_fp8(KS, splitk) : skinny_waves(Npad, KS, splitk);
+    if (wfmt == SV_WFMT_MXFP4) {        // its own kernel, row tiles on grid.z
+        *waves = skinny_waves_mxfp4(KS, splitk);
+        *two_row_tiles = 0;
+        return;
+    }
+    const int w = wfmt == SV_WFMT_FP8 ? skinny_waves_fp8(KS, splitk) : skinny_waves(Npad, KS, splitk);
     *waves = w;
     *two_row_tiles = (MT >= 2 && !(MT & 1) && (w == 8 || w == 4) && KS % splitk == 0) ? 1 : 0;
 }
@@ -2230,6 +2235,9 @@ int init_gemm_kernels() {
 }
 
 void launch_gemm_skinny(const SkinnyArgs& a, hipStream_t st) {
+    // MXFP4 weights: their own kernel at every row count.  Outside its scope (sv_create refuses such engines) the launch goes on to the
+    // bf16 kernels below over Wp, which holds exactly the dequantised values.
+    if (a.W4 && launch_gemm_skinny_mxfp4(a, st)) return;
     if (launch_head_persist(a, st)) return;                      // the lm_head of a <= 32-row step: one round of blocks over several column tiles each
     if (launch_gemm_skinny_mt2(a, st)) return;                  // 33..64 rows: two row tiles per block, weights streamed once
     if (a.Wq && launch_gemm_skinny_fp8(a, st)) return;       // fp8 weights: its own kernel (falls through if unsupported)

@@ -26,6 +26,25 @@ void launch_convert_to_bf16(const void* src, int src_is_f32, bf16_t* dst, size_t
 // apply the scale in their epilogue like the decode kernel does), and scale[Npad] (1 for padding rows).
 void launch_pack_weight_fp8(const void* src, int src_is_f32, bf16_t* dst_bf16, uint8_t* dst_q, float* scale, int N, int K,
                             int Npad, int Kpad, hipStream_t st);
+// weight formats of a Linear (sv_config.weight_dtype; skinny_plan / pick_decode_plan take them where they took `fp8`)
+enum { SV_WFMT_BF16 = 0, SV_WFMT_FP8 = 1, SV_WFMT_MXFP4 = 2 };
+// MXFP4 (OCP MX: e2m1 codes, one e8m0 scale byte per 32 consecutive k of an output row) weight-only quantisation (mxfp4/mxfp4.hip).
+// Per block: amax = max |W|; amax == 0: E = 0, codes 0; else E = floor(log2(amax)) - 2 clamped to [-125, 125], scale byte = E + 127;
+// code = W / 2^E rounded to {0, .5, 1, 1.5, 2, 3, 4, 6} with its sign, ties to the even mantissa bit, magnitudes above 6 saturate.
+// Writes
+//  * the decode image W4: groups [Npad/32][Kpad/64] of SV_MXFP4_GROUP = 1088 bytes, a group = one column tile's 64 consecutive k:
+//      bytes [0, 1024)    [64 lanes][16 B], lane = 32 * ((k / 8) & 1) + n % 32 (the bf16 image's lane), a lane's 16 bytes = four k-steps
+//                         (word (k / 16) & 3) of 8 codes each: code k % 8 is nibble k % 8 of the word (byte (k % 8) / 2, low nibble = even k);
+//      bytes [1024, 1088) [32 rows][2] scale bytes: row n % 32, byte (k / 32) & 1 (the two MX blocks of the group);
+//    4.25 bits per weight, scales included;
+//  * the bf16 image of the dequantised values q * 2^E (each exactly a bf16 number) in the usual packed layout, for the big-M kernels
+//    with no column scale;
+//  * scale_plain (optional, test surface): the scale bytes as [Npad][Kpad/32].
+// Kpad % 64 == 0.  Padding rows / columns quantise as zeros (scale byte 127).
+#define SV_MXFP4_GROUP 1088
+inline size_t mxfp4_image_bytes(int Npad, int Kpad) { return (size_t)(Npad / 32) * (Kpad / 64) * SV_MXFP4_GROUP; }
+void launch_pack_weight_mxfp4(const void* src, int src_is_f32, bf16_t* dst_bf16, uint8_t* dst_w4, uint8_t* scale_plain, int N, int K,
+                              int Npad, int Kpad, hipStream_t st);
 
 // ---- big-M MFMA GEMM:  C[M][N] = epi( A[M][K] . W^T + bias ) (+ residual) ----------------------
 struct GemmArgs {
@@ -119,6 +138,9 @@ struct SkinnyArgs {
     // decodes the keys and runs the bookkeeping.  `finish` is a HOST pointer read by the launcher (the struct rides behind SkinnyArgs in that kernel's
     // arguments); nullptr: off.  skinny_head_folds_finish(a) tells the caller whether the launch takes the bookkeeping with it.
     const struct FinishArgs* finish; unsigned* fin_cnt;
+    // MXFP4 image of the same weight (launch_pack_weight_mxfp4) or nullptr: then gemm_skinny_mxfp4_kernel runs (Wp holds the dequantised values);
+    // col_tiles = column tiles per block there (1, 2, 4; 0 = the launcher's default)
+    const uint8_t* W4;
 };
 bool skinny_head_folds_finish(const SkinnyArgs& a);
 #define SV_TAIL_TILES 128
@@ -136,7 +158,12 @@ __host__ __device__ inline int sv_amax_index(unsigned long long key) { return ke
 void launch_gemm_skinny(const SkinnyArgs& a, hipStream_t st);
 // host arithmetic of the launch: waves per block (how K is cut inside a block = the summation order of a row) and whether a
 // block carries two row tiles; a function of the GEMM only for the former (sv_debug_skinny_plan, CPU tests)
-void skinny_plan(int Npad, int K, int splitk, int fp8, int MT, int* waves, int* two_row_tiles);
+// (wfmt: SV_WFMT_*)
+void skinny_plan(int Npad, int K, int splitk, int wfmt, int MT, int* waves, int* two_row_tiles);
+// the MXFP4 decode GEMM (mxfp4/mxfp4.hip): waves per block for (k-steps, split-K), a function of those two only (0: no K cut fits -- a wave's
+// range is whole groups of 4 k-steps); the launcher returns false when the shape / mode is outside the kernel's scope
+int skinny_waves_mxfp4(int KS, int splitk);
+bool launch_gemm_skinny_mxfp4(const SkinnyArgs& a, hipStream_t st);
 extern std::atomic<int> g_op_col_tiles;       // sv_debug_set_col_tiles: what SkinnyArgs.col_tiles == 0 means (0 = the launcher's default)
 
 int init_gemm_kernels();        // hipFuncSetAttribute for the large-LDS variants (0 = ok)

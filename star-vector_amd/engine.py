@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import ctypes as C
 import enum
+import os
 import threading
 from dataclasses import dataclass
 from typing import Dict, Iterable, List, NamedTuple, Optional, Sequence, Tuple
@@ -79,7 +80,8 @@ class EngineConfig:
     vit_mlp: int = 4096
     vit_eps: float = 1e-6
     sliding_window: int = 0          # v2: keys visible to a query (4096 for bigcode/starcoder2-7b); 0 = all
-    weight_dtype: str = "bf16"       # "fp8_e4m3": decoder weights + lm_head quantised at load (per-row scales), BASELINE config 5
+    weight_dtype: str = "bf16"       # "fp8_e4m3": decoder weights + lm_head quantised at load (per-row scales), BASELINE config 5;
+                                     # "mxfp4": the same tensors as OCP MXFP4 (e2m1 codes, one e8m0 scale per 32 k: sv_config.weight_dtype)
     exclusive_device: object = False # False / True / "auto" (2: on until a fused launch gives up, then off for good and the call re-run: sv_config.exclusive_device).
                                      # True: this engine alone launches kernels on its GPU while decoding (one process per GPU): enables the
                                      # all-blocks-resident fused launches (include/starvector_hip.h sv_config.exclusive_device); same tokens
@@ -152,6 +154,26 @@ def _need(t: torch.Tensor, dtype, what: str) -> torch.Tensor:
     return t.contiguous()
 
 
+WEIGHT_DTYPES = {"bf16": 0, "fp8_e4m3": 1, "mxfp4": 2}          # SV_WEIGHT_*
+_WEIGHT_DTYPE_ALIASES = {"fp8": "fp8_e4m3", "bfloat16": "bf16"}
+
+
+def resolve_weight_dtype(weight_dtype=None) -> str:
+    """The canonical name of a decoder weight format: "bf16", "fp8_e4m3" (also "fp8") or "mxfp4".  None = the environment's
+    SV_WEIGHT_DTYPE, else "bf16"."""
+    if weight_dtype is None:
+        weight_dtype = os.environ.get("SV_WEIGHT_DTYPE") or "bf16"
+    name = str(weight_dtype).lower()
+    name = _WEIGHT_DTYPE_ALIASES.get(name, name)
+    if name not in WEIGHT_DTYPES:
+        raise ValueError(f"weight_dtype must be one of {sorted(WEIGHT_DTYPES)} (or 'fp8'), got {weight_dtype!r}")
+    return name
+
+
+def weight_dtype_code(weight_dtype) -> int:
+    return WEIGHT_DTYPES[resolve_weight_dtype(weight_dtype)]
+
+
 def _exclusive_code(v) -> int:
     """sv_config.exclusive_device: 0 (shared GPU), 1 (this engine owns it), 2 ("auto": optimistic, falls back for good at the first give-up)."""
     if isinstance(v, str):
@@ -179,7 +201,7 @@ class HipEngine:
                      _lib.SV_ARCH_V2 if cfg.arch == "v2" else _lib.SV_ARCH_V1, cfg.n_kv_head, cfg.rope_theta,
                      cfg.vit_mlp, cfg.vit_eps if cfg.arch == "v2" else cfg.ln_eps,
                      int(cfg.sliding_window) if cfg.arch == "v2" else 0,
-                     {"bf16": 0, "fp8_e4m3": 1}[cfg.weight_dtype], _exclusive_code(getattr(cfg, "exclusive_device", False)))
+                     weight_dtype_code(cfg.weight_dtype), _exclusive_code(getattr(cfg, "exclusive_device", False)))
         h = C.c_void_p()
         check(self.lib.sv_create(C.byref(c), C.byref(h)), "sv_create")
         self._h = h
@@ -1347,6 +1369,51 @@ def op_pack_weight_fp8(W):
     check(lib.sv_op_pack_weight_fp8(_ptr(W), int(W.dtype == torch.float32), N, K, _ptr(sc), _ptr(wq), _ptr(wp), _stream()),
           "sv_op_pack_weight_fp8")
     return sc, wq, wp
+
+
+def op_pack_weight_mxfp4(W):
+    """The MXFP4 quantiser as sv_load_weight runs it, W [N, K] bf16 or float32: returns the raw images (scale bytes uint8 [Npad, K / 32], the
+    decode image uint8 [Npad / 32 * K / 64 * 1088], the bf16 image [Npad * K]); their layouts are stated in starvector_hip_debug.h."""
+    lib = _lib.load()
+    if W.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("W must be bfloat16 or float32")
+    W = _need(W, W.dtype, "W")
+    N, K = W.shape
+    Npad = (N + 31) // 32 * 32
+    sc = torch.empty(Npad, max(K // 32, 1), dtype=torch.uint8, device=W.device)
+    w4 = torch.empty(Npad // 32 * max(K // 64, 1) * 1088, dtype=torch.uint8, device=W.device)
+    wp = torch.empty(Npad * K, dtype=torch.bfloat16, device=W.device)
+    check(lib.sv_op_pack_weight_mxfp4(_ptr(W), int(W.dtype == torch.float32), N, K, _ptr(sc), _ptr(w4), _ptr(wp), _stream()),
+          "sv_op_pack_weight_mxfp4")
+    return sc, w4, wp
+
+
+def op_linear_skinny_mxfp4(x, W, bias=None, splitk=1, col_tiles=0):
+    """Returns (y fp32 [M, N], scale bytes uint8 [N, K / 32]) of the MXFP4-weight decode GEMM (weights quantised on device); col_tiles =
+    column tiles per block (1, 2, 4: identical bits; 0 = the launcher's default).  M may exceed 32."""
+    lib = _lib.load()
+    x = _need(x, torch.bfloat16, "x"); W = _need(W, torch.bfloat16, "W")
+    M, K = x.shape; N = W.shape[0]
+    y = torch.empty(M, N, dtype=torch.float32, device=x.device)
+    sc = torch.empty(N, max(K // 32, 1), dtype=torch.uint8, device=x.device)
+    b = _need(bias, torch.bfloat16, "bias") if bias is not None else None
+    check(lib.sv_op_linear_skinny_mxfp4(_ptr(x), _ptr(W), _ptr(b), _ptr(y), _ptr(sc), M, N, K, splitk, int(col_tiles), _stream()),
+          "sv_op_linear_skinny_mxfp4")
+    return y, sc
+
+
+def op_linear_skinny_epi_mxfp4(x, W, bias=None, act="none", out_f32=False, col_tiles=0):
+    """`op_linear_skinny_epi` with the weight quantised to MXFP4 on device (an mxfp4 engine's c_fc / lm_head launch): returns
+    (y, scale bytes uint8 [N, K / 32])."""
+    lib = _lib.load()
+    x = _need(x, torch.bfloat16, "x"); W = _need(W, torch.bfloat16, "W")
+    M, K = x.shape; N = W.shape[0]
+    y = torch.empty(M, N, dtype=torch.float32 if out_f32 else torch.bfloat16, device=x.device)
+    sc = torch.empty(N, max(K // 32, 1), dtype=torch.uint8, device=x.device)
+    b = _need(bias, torch.bfloat16, "bias") if bias is not None else None
+    check(lib.sv_op_linear_skinny_epi_mxfp4(_ptr(x), _ptr(W), _ptr(b), _ptr(y), _ptr(sc), M, N, K, _lib.ACT[act], int(out_f32), int(col_tiles),
+                                            _stream()), "sv_op_linear_skinny_epi_mxfp4")
+    return y, sc
 
 
 def op_lm_head_argmax(x, W):

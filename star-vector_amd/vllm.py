@@ -254,13 +254,18 @@ class LLM:
     runs max_num_seqs // (K + 1) requests at a time.  Any other `speculative_model` raises NotImplementedError (there is no draft model).
     The draft searches the request's OUTPUT ids only -- the prompt here is `inputs_embeds` (image features and text embeddings), not ids,
     where vLLM's n-gram worker searches prompt and output.  That changes the acceptance rate, never the tokens: every request returns
-    what it returns without these arguments."""
+    what it returns without these arguments.
+
+    ``quantization="fp8"`` / ``"mxfp4"`` quantise the decoder weights at load (`EngineConfig.weight_dtype`); None = the environment's
+    SV_WEIGHT_DTYPE, else bf16.  Any other string raises ValueError.  Neither is the reference's precision."""
 
     def __init__(self, model: str, tokenizer=None, dtype: str = "auto", max_model_len: Optional[int] = None,
                  max_num_seqs: Optional[int] = None, trust_remote_code: bool = False, speculative_model: Optional[str] = None,
                  num_speculative_tokens: Optional[int] = None, ngram_prompt_lookup_max: Optional[int] = None,
-                 ngram_prompt_lookup_min: Optional[int] = None, **kwargs):
+                 ngram_prompt_lookup_min: Optional[int] = None, quantization: Optional[str] = None, **kwargs):
         from .model import StarVectorForCausalLM
+        if quantization is not None and quantization not in ("fp8", "mxfp4"):
+            raise ValueError(f"quantization must be \"fp8\", \"mxfp4\" or None, got {quantization!r}")
         self._lookup = {}
         if speculative_model is not None:
             if speculative_model != "[ngram]":
@@ -278,6 +283,8 @@ class LLM:
         elif dt not in ("auto", "bfloat16"):
             raise ValueError(f"unsupported dtype={dtype} (bfloat16 / auto, or float16 / float32 converted to bfloat16)")
         load_kw = {}
+        if quantization is not None:
+            load_kw["weight_dtype"] = {"fp8": "fp8_e4m3", "mxfp4": "mxfp4"}[quantization]
         if max_num_seqs is not None:
             load_kw["max_batch"] = int(max_num_seqs)
         if max_model_len is not None:
