@@ -269,7 +269,30 @@ int  sv_prefill_ragged(sv_engine* e, const void* dev_embeds_packed, int32_t B, c
 int  sv_forward_logprobs_ragged(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, const int32_t* host_keep,
                                 const int32_t* dev_targets, float temperature, float* dev_logprob, float* dev_logsumexp, float* dev_entropy,
                                 int32_t* dev_argmax, int32_t k, int32_t* dev_topk_ids, float* dev_topk_logprobs, int32_t* dev_rank, sv_stream stream);
-/* Scoring forward = `StarVectorForCausalLM.forward(vision_embeds, input_ids, ..., num_logits_to_keep)`
+/* sv_forward_logprobs_ragged over sequences that SHARE PREFIXES (GRPO's log-prob pass: G completions per image): every prefix goes through
+ * the decoder once, not once per sequence.  dev_prefix_packed: the P prefixes back to back, [sum(host_prefix_lens)][hidden] bf16;
+ * dev_embeds_packed: the B sequences' OWN rows back to back, [sum(host_lens)][hidden] bf16.  Sequence b stands for the solo sequence
+ * concat(prefix[host_prefix_of[b]], own rows of b) of T_b = Pl + host_lens[b] rows.  host_keep[b] in 1 .. host_lens[b] + 1 = the LAST rows
+ * of that solo sequence that are scored; host_lens[b] + 1 reaches the prefix's last row, the row that predicts the first own token.
+ * dev_targets, the outputs ([sum(host_keep)], lists [sum(host_keep)][k], in sequence order), -100, temperature, k, ties, ranks and the two
+ * failures are those of sv_forward_logprobs_ragged.  Blocks until the pass has finished, under the same lock.
+ * Contract: every output of sequence b's kept rows is BIT-IDENTICAL to sv_forward_topk on the concatenated sequence alone (B = 1,
+ * S = T_b, n_keep = host_keep[b]), whatever the other sequences, their order, the number of sequences per prefix and the lm_head chunk size.
+ * Refusal rule: where a solo run of T_b rows sends its last T_b % 256 (1..3, T_b > 256) rows through the split-K remainder kernel for any of
+ * the four decoder projections and host_lens[b] is smaller than that, a PREFIX row would need different bits for different sharers:
+ * SV_EINVAL naming the sequence, before any device work (score that sequence with sv_forward_logprobs_ragged on its concatenation).
+ * KV cache: no page is assigned or written; afterwards sv_decode_step refuses (SV_ESTATE) until the next prompt pass, which behaves as on
+ * a fresh engine.  The last layer runs over the prefix rows as well (their c_proj / MLP work there is not skipped).
+ * SV_EINVAL before any device work for null pointers, P or B out of range (1 <= P <= B <= max_batch), a host_prefix_of outside 0 .. P - 1,
+ * a prefix no sequence uses, a length < 1, T_b > max_seq_len, a keep outside 1 .. host_lens[b] + 1, and the temperature / k / output rules of
+ * sv_forward_logprobs_ragged.  SV_ESTATE while continuous-batch slots are live.  Weight formats: bf16, fp8 (e4m3) and mxfp4 engines alike
+ * (the contract is against the same engine's solo run); there is no format the call answers with SV_ENOTSUP. */
+int  sv_forward_logprobs_prefixed(sv_engine* e, const void* dev_prefix_packed, int32_t P, const int32_t* host_prefix_lens,
+                                  const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, const int32_t* host_prefix_of,
+                                  const int32_t* host_keep, const int32_t* dev_targets, float temperature, float* dev_logprob,
+                                  float* dev_logsumexp, float* dev_entropy, int32_t* dev_argmax, int32_t k, int32_t* dev_topk_ids,
+                                  float* dev_topk_logprobs, int32_t* dev_rank, sv_stream stream);
+/* Scoring forward =`StarVectorForCausalLM.forward(vision_embeds, input_ids, ..., num_logits_to_keep)`
  * (starvector_arch.py:161-184; GRPO's log-prob pass, inference mode): the decoder over inputs_embeds [B,S,hidden] bf16
  * (all-ones mask) and the lm_head over the LAST n_keep positions of every sequence.
  * dev_logits_bf16: [B, n_keep, vocab] bf16, the dtype the reference's bf16 lm_head returns.  Also leaves the KV cache

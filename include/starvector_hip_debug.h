@@ -142,6 +142,18 @@ int  sv_debug_gemm_seq_form(int32_t S, int32_t N, int32_t K, int32_t act);
      capacity >= 3 * B; q_tile 32 or 128 (grouped-query heads in fours / one head per block). */
 int  sv_debug_ragged_plan(const int32_t* lens, int32_t B, int32_t N, int32_t K, int32_t act, int32_t q_tile, int32_t* rows_out,
                           int32_t* last_out, int32_t capacity, int32_t* out4);
+/*   sv_debug_prefix_plan      what the shared-prefix scoring pass (sv_forward_logprobs_prefixed) decides for P prefixes of lengths prefix_lens[0..P)
+     and B sequences of own lengths lens[0..B) with prefix prefix_of[b], packed prefixes first, at the projection (N, K, act).  Host arithmetic
+     only.  row_pos_out [packed rows]: every packed row's index in its SOLO sequence (j in a prefix, Pl + j in own rows: wpe and RoPE).  rows_out:
+     the packed rows (ascending) that go through the split-K remainder kernel -- own rows only, those with solo index >= T - T % 256 where
+     sv_debug_gemm_seq_form(T, N, K, act) holds for T = Pl + len; a prefix is never listed, not by its own length either.  blocks_out: the
+     {sequence, query tile} pairs of the prefixed attention launch, tiles of q_tile rows counted from solo index 0, from the tile that holds row
+     Pl on.  out4 = {rows listed, blocks listed, the first sequence whose remainder rows would reach into its prefix (len < T % 256 where the form
+     holds: the entry point refuses the call) or -1, packed rows}.  capacity (of each of the three arrays) >= max(packed rows, 3 * B, 2 * blocks).
+     SV_EINVAL for the shapes sv_forward_logprobs_prefixed refuses: P or B out of order, a length < 1, a prefix_of out of range, an unused prefix. */
+int  sv_debug_prefix_plan(const int32_t* prefix_lens, int32_t P, const int32_t* lens, const int32_t* prefix_of, int32_t B, int32_t N,
+                          int32_t K, int32_t act, int32_t q_tile, int32_t* row_pos_out, int32_t* rows_out, int32_t* blocks_out,
+                          int32_t capacity, int32_t* out4);
 /*   sv_debug_shared_plan      the page plan of a shared prompt pass (sv_generate_shared, sv_cb_admit_shared): n requests over n_prompts prompts of
      lengths lens[u], request i samples prompt group[i] with a budget of budgets[i] new tokens.  Host arithmetic only.  shared_out [n]: the leading
      block-table entries of request i that are its prompt's full pages, lens[group[i]] / 64, held ONCE per prompt; private_out [n]: the pages the
@@ -341,6 +353,14 @@ int  sv_op_attention(const void* q, const void* k, const void* v, void* out, int
 int  sv_op_attention_prefill(const void* qkv, int32_t q_off, int32_t k_off, int32_t v_off, int32_t row_stride, void* out, int32_t B,
                              int32_t S, const int32_t* host_lens, int32_t H, int32_t Hkv, int32_t head_dim, int32_t causal,
                              float scale, int32_t window, int32_t last_rows, sv_stream stream);
+/* The PREFIXED form of that kernel on its own (the shared-prefix scoring pass): the packed rows are P prefixes of host_prefix_lens[u] rows
+ * followed by the own rows of B sequences (host_lens[b] >= 1, prefix host_prefix_of[b]); sequence b attends as the solo sequence
+ * concat(prefix, own rows).  Causal, block list from the engine's own planner (the tiles from the one that holds row Pl on).  Only the OWN rows of
+ * `out` [packed rows][H*D] are written: the prefix rows belong to the prefixes' ordinary ragged launch, which this operator does not make.
+ * Every argument is checked before any device work (SV_EINVAL). */
+int  sv_op_attn_prefill_prefixed(const void* qkv, int32_t q_off, int32_t k_off, int32_t v_off, int32_t row_stride, void* out, int32_t P,
+                                 const int32_t* host_prefix_lens, int32_t B, const int32_t* host_lens, const int32_t* host_prefix_of,
+                                 int32_t H, int32_t Hkv, int32_t head_dim, float scale, int32_t window, sv_stream stream);
 int  sv_op_plane_layernorm(const void* x, const void* gamma, const void* beta, void* y, int32_t B,
                            int32_t QD, float eps, sv_stream stream);
 /* the same kernel writing plane b at y + b * y_batch_stride (elements, a multiple of 8, >= QD): the form the engine launches, straight

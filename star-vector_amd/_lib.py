@@ -160,6 +160,8 @@ PRODUCT_PROTOTYPES = {
                                         _P]),
     "sv_forward_topk": (_I, [_P, _P, _I, _I, _I, _P, _F, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "sv_forward_logprobs_ragged": (_I, [_P, _P, _I, C.POINTER(_I), C.POINTER(_I), _P, _F, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "sv_forward_logprobs_prefixed": (_I, [_P, _P, _I, C.POINTER(_I), _P, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _P, _F, _P, _P, _P, _P, _I,
+                                          _P, _P, _P, _P]),
     "sv_cb_admit_shared": (_I, [_P, _P, _I, C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(SvCbRequest), C.POINTER(_I), _P]),
     "sv_cb_admit_ragged": (_I, [_P, _P, _I, C.POINTER(_I), C.POINTER(SvCbRequest), C.POINTER(_I), _P]),
     "sv_forward_logits": (_I, [_P, _P, _I, _I, _I, _P, _P]),
@@ -201,6 +203,8 @@ DEBUG_PROTOTYPES = {
     "sv_debug_set_linear_seq_rows": (_I, [_I]),
     "sv_debug_gemm_seq_form": (_I, [_I, _I, _I, _I]),
     "sv_debug_ragged_plan": (_I, [C.POINTER(_I), _I, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, C.POINTER(_I)]),
+    "sv_debug_prefix_plan": (_I, [C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(_I), _I, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _I,
+                                  C.POINTER(_I)]),
     "sv_debug_prompt_passes": (_I, [_P, C.POINTER(C.c_int64)]),
     "sv_debug_shared_plan": (_I, [C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_int64)]),
     "sv_debug_block_table": (_I, [_P, _I, C.POINTER(_I), _I]),
@@ -248,6 +252,7 @@ DEBUG_PROTOTYPES = {
     "sv_op_cvt_bf16_hw": (_I, [_P, _P, C.c_int64, _P]),
     "sv_op_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "sv_op_attention_prefill": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, C.POINTER(_I), _I, _I, _I, _I, _F, _I, _I, _P]),
+    "sv_op_attn_prefill_prefixed": (_I, [_P, _I, _I, _I, _I, _P, _I, C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(_I), _I, _I, _I, _F, _I, _P]),
     "sv_op_plane_layernorm": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
     "sv_op_plane_layernorm_strided": (_I, [_P, _P, _P, _P, _I, _I, _F, C.c_int64, _P]),
     "sv_op_im2col": (_I, [_P, _P, _I, _I, _I, _I, _P]),

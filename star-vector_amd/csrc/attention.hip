@@ -28,7 +28,10 @@ __device__ __forceinline__ int swap23(int x) { return (x & ~0xC) | ((x & 4) << 1
 // tile pairs cover 257 x 257 scores where 32.3 would do (the 257th key and the 257th row each cost a whole tile).  profiles/SUMMARY_r05.md; removed.)
 // RAG: the ragged form (AttnPrefillArgs::rag_seq / ::rag_blocks) -- block x works for entry x of the host-built (sequence, query tile) list;
 // the sequence's first packed row and its length come from its descriptor, everything below is the rectangular kernel's code with those two values
-template <int D, int HPB, bool RAG = false>
+// PFX (with RAG): the prefixed form (AttnPrefillArgs::rag_prefixed) -- the sequence is concat(prefix, own rows), descriptor {first own packed row, T,
+// first prefix packed row, Pl}.  S = T and every index below stays the solo index; only row_of(s), the packed row of solo index s, differs from
+// row0 + s, and the rows below Pl are not stored.
+template <int D, int HPB, bool RAG = false, bool PFX = false>
 __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnPrefillArgs p) {      // two blocks per CU: <= 256 registers
 
     constexpr int KSTR = D + 8;          // K tile row stride (elements): +16 B pad -> conflict-free b128
@@ -43,7 +46,17 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnPrefillArgs p)
     const int c = lane >> 5;
     int S, qtile;
     size_t row0;                         // first row of the block's sequence in the token-major buffers
-    if constexpr (RAG) {
+    int pl = 0;                          // PFX: rows of the prefix; solo index s lives at packed row (s < pl ? prow : orow) + s
+    long long prow = 0, orow = 0;
+    if constexpr (PFX) {
+        const int sq = p.rag_blocks[2 * blockIdx.x];
+        qtile = p.rag_blocks[2 * blockIdx.x + 1];
+        S = p.rag_seq[4 * sq + 1];
+        pl = p.rag_seq[4 * sq + 3];
+        prow = p.rag_seq[4 * sq + 2];
+        orow = (long long)p.rag_seq[4 * sq] - pl;
+        row0 = 0;
+    } else if constexpr (RAG) {
         const int sq = p.rag_blocks[2 * blockIdx.x];
         qtile = p.rag_blocks[2 * blockIdx.x + 1];
         row0 = (size_t)p.rag_seq[2 * sq];
@@ -72,7 +85,8 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnPrefillArgs p)
     // Q fragments (B operand): lane (q = l&31, c = l>>5) holds Q[q][16 s + 8 c .. +8]
     bf16x8 qf[NKS];
     {
-        const bf16_t* qp = p.q + (row0 + qrow) * p.q_row_stride + (size_t)head * p.q_head_stride + c * 8;
+        const size_t qr = PFX ? (size_t)((qrow < pl ? prow : orow) + qrow) : row0 + qrow;
+        const bf16_t* qp = p.q + qr * p.q_row_stride + (size_t)head * p.q_head_stride + c * 8;
 #pragma unroll
         for (int s = 0; s < NKS; ++s) qf[s] = as_frag(*reinterpret_cast<const uint4*>(qp + s * 16));
     }
@@ -108,13 +122,15 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnPrefillArgs p)
             const int row = idx / (D / 8), ch = idx % (D / 8);
             int key = kt * 64 + row;
             key = key < S ? key : S - 1;
-            kreg[i] = *reinterpret_cast<const u32x4*>(kbase + (size_t)key * p.kv_row_stride + ch * 8);
+            const size_t kr = PFX ? (size_t)((key < pl ? prow : orow) + key) : (size_t)key;      // (PFX: row0 == 0)
+            kreg[i] = *reinterpret_cast<const u32x4*>(kbase + kr * p.kv_row_stride + ch * 8);
         }
         int key = kt * 64 + lane;
         key = key < S ? key : S - 1;
+        const size_t vr = PFX ? (size_t)((key < pl ? prow : orow) + key) : (size_t)key;
 #pragma unroll
         for (int i = 0; i < VPT; ++i)
-            vreg[i] = *reinterpret_cast<const u32x4*>(vbase + (size_t)key * p.kv_row_stride + (wave + 4 * i) * 8);
+            vreg[i] = *reinterpret_cast<const u32x4*>(vbase + vr * p.kv_row_stride + (wave + 4 * i) * 8);
     };
     auto lstore = [&]() __attribute__((always_inline)) {
 #pragma unroll
@@ -231,8 +247,9 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnPrefillArgs p)
 
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = 1.0f / l_tot;
-    if (qabs < S) {
-        bf16_t* op = p.o + (row0 + qabs) * p.o_row_stride + (size_t)head * D;
+    if (qabs < S && (!PFX || qabs >= pl)) {
+        const size_t orw = PFX ? (size_t)(orow + qabs) : row0 + qabs;
+        bf16_t* op = p.o + orw * p.o_row_stride + (size_t)head * D;
 #pragma unroll
         for (int t = 0; t < NDV; ++t)
 #pragma unroll
@@ -253,6 +270,17 @@ void launch_attn_prefill(const AttnPrefillArgs& a_in, hipStream_t st) {
     AttnPrefillArgs a = a_in;
     if (a.rag_blocks) {                  // ragged: one block per listed (sequence, query tile), causal by construction of the caller
         if (a.rag_nblocks < 1) return;
+        if (a.rag_prefixed) {            // the same grid over {first own row, T, first prefix row, Pl} descriptors
+            dim3 grid(a.rag_nblocks, mqa4 ? a.H / 4 : a.H, 1);
+            if (mqa4) {
+                if (a.head_dim == 128) attn_prefill_kernel<128, 4, true, true><<<grid, 256, 0, st>>>(a);
+                else attn_prefill_kernel<64, 4, true, true><<<grid, 256, 0, st>>>(a);
+            } else {
+                if (a.head_dim == 128) attn_prefill_kernel<128, 1, true, true><<<grid, 256, 0, st>>>(a);
+                else attn_prefill_kernel<64, 1, true, true><<<grid, 256, 0, st>>>(a);
+            }
+            return;
+        }
         if (mqa4) {
             dim3 grid(a.rag_nblocks, a.H / 4, 1);
             if (a.head_dim == 128) attn_prefill_kernel<128, 4, true><<<grid, 256, 0, st>>>(a);

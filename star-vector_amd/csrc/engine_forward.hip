@@ -1,6 +1,6 @@
 // Host driver, part 2 of 5: the op graphs -- vision tower, adapter, prompt pass, one decode step -- and the forward entry
 // points of the C ABI (sv_encode_image, sv_adapter, sv_embed_tokens, sv_prefill, sv_forward_logits, sv_forward_logprobs, sv_forward_logprobs_ragged,
-// sv_decode_step).
+// sv_forward_logprobs_prefixed, sv_decode_step).
 #include <algorithm>
 #include <cmath>
 #include "engine_internal.h"
@@ -402,6 +402,32 @@ int sveng::ragged_check_lens(const sv_engine* e, const int32_t* lens, int B, con
     return 0;
 }
 
+// the row-position buffer and the plan image (pinned host + device) of the ragged passes, grown on demand
+static int rag_reserve_row_pos(sv_engine* e, size_t rows) {
+    if (rows <= e->rag_pos_rows) return 0;
+    if (e->rag_row_pos) (void)hipFree(e->rag_row_pos);
+    e->rag_row_pos = nullptr; e->rag_pos_rows = 0;
+    HIPCHECK(hipMalloc(reinterpret_cast<void**>(&e->rag_row_pos), rows * sizeof(int32_t)));
+    e->rag_pos_rows = rows;
+    return 0;
+}
+static int rag_reserve_plan(sv_engine* e, size_t need) {
+    if (need > e->rag_cap) {
+        if (e->rag_pending) { HIPCHECK(hipEventSynchronize(e->rag_ev)); e->rag_pending = false; }
+        if (e->h_rag) (void)hipHostFree(e->h_rag);
+        if (e->d_rag) (void)hipFree(e->d_rag);
+        e->h_rag = nullptr; e->d_rag = nullptr; e->rag_cap = 0;
+        const size_t cap = need + need / 2 + 256;
+        HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&e->h_rag), cap * sizeof(int32_t), hipHostMallocDefault));
+        HIPCHECK(hipMalloc(reinterpret_cast<void**>(&e->d_rag), cap * sizeof(int32_t)));
+        if (!e->rag_ev) HIPCHECK(hipEventCreateWithFlags(&e->rag_ev, hipEventDisableTiming));
+        e->rag_cap = cap;
+    }
+    // pinned image, no stream synchronise: rewritten only after its last upload has completed (an event, normally long past)
+    if (e->rag_pending) { HIPCHECK(hipEventSynchronize(e->rag_ev)); e->rag_pending = false; }
+    return 0;
+}
+
 __global__ void ragged_positions_kernel(int32_t* positions, const int32_t* rag_seq, int n, int rep, int delta) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) positions[i] = rag_seq[2 * (i / rep) + 1] + delta;
@@ -429,12 +455,7 @@ int sveng::prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, con
     SVCHECK(ensure_prefill_ws(e, (size_t)std::max(M, 2 * B)));
     ++e->prompt_passes;
     if (!e->rag_rsave) SVCHECK(dalloc(e, &e->rag_rsave, (size_t)3 * c.max_batch * D));
-    if ((size_t)M > e->rag_pos_rows) {
-        if (e->rag_row_pos) (void)hipFree(e->rag_row_pos);
-        e->rag_row_pos = nullptr; e->rag_pos_rows = 0;
-        HIPCHECK(hipMalloc(reinterpret_cast<void**>(&e->rag_row_pos), (size_t)M * sizeof(int32_t)));
-        e->rag_pos_rows = (size_t)M;
-    }
+    SVCHECK(rag_reserve_row_pos(e, (size_t)M));
     // ---- the plan of this call: descriptors | attention blocks | last-tile blocks | KV-write blocks | remainder rows of the four projections |
     // kept-row descriptors (scoring mode)
     const int qt = attn_prefill_q_tile(c.n_head, nkv);
@@ -455,19 +476,7 @@ int sveng::prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, con
         for (int i = 0; i < 4; ++i) ragged_gemm_rows(lens, B, proj[i]->N, proj[i]->Kpad, acts[i], rows[i], last[i]);
     size_t need = (size_t)2 * B + ab.size() + al.size() + kb.size() + kd.size();
     for (int i = 0; i < 4; ++i) need += rows[i].size() + last[i].size();
-    if (need > e->rag_cap) {
-        if (e->rag_pending) { HIPCHECK(hipEventSynchronize(e->rag_ev)); e->rag_pending = false; }
-        if (e->h_rag) (void)hipHostFree(e->h_rag);
-        if (e->d_rag) (void)hipFree(e->d_rag);
-        e->h_rag = nullptr; e->d_rag = nullptr; e->rag_cap = 0;
-        const size_t cap = need + need / 2 + 256;
-        HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&e->h_rag), cap * sizeof(int32_t), hipHostMallocDefault));
-        HIPCHECK(hipMalloc(reinterpret_cast<void**>(&e->d_rag), cap * sizeof(int32_t)));
-        if (!e->rag_ev) HIPCHECK(hipEventCreateWithFlags(&e->rag_ev, hipEventDisableTiming));
-        e->rag_cap = cap;
-    }
-    // pinned image, no stream synchronise: rewritten only after its last upload has completed (an event, normally long past)
-    if (e->rag_pending) { HIPCHECK(hipEventSynchronize(e->rag_ev)); e->rag_pending = false; }
+    SVCHECK(rag_reserve_plan(e, need));
     size_t off = 0;
     auto put = [&](const std::vector<int32_t>& v) { const size_t o = off; if (!v.empty()) memcpy(e->h_rag + off, v.data(), v.size() * sizeof(int32_t)); off += v.size(); return o; };
     {
@@ -556,6 +565,80 @@ int sveng::prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, con
     prof_mark(e, PK_PF_LMHEAD, st);
     lm_head_logits(e, (B + 31) / 32, e->xp_f, st);
     return 0;
+}
+
+// The shared-prefix scoring pass (sv_forward_logprobs_prefixed; the plan and why the bits hold: prefix/prefix.hip).  prefill_forward_ragged's scoring
+// mode over plan.M packed rows -- the prefixes, then every sequence's own rows -- with two differences: the attention runs as two launches (the
+// prefixes as ordinary ragged sequences, then the prefixed form over the sequences' tiles from the straddling one on), and no K / V page is written.
+// The last layer runs on all packed rows (the prefix rows' c_proj / MLP work there is not skipped).
+static int prefill_forward_prefixed(sv_engine* e, const bf16_t* prefixes, const bf16_t* own, int P, int B, const PrefixPlan& plan,
+                                    const int32_t* keep, const ScoreLogprobs* lp, hipStream_t st) {
+    const sv_config& c = e->cfg;
+    const int D = c.hidden, dh = e->dh, F = c.n_inner, QKV = e->QKV, nkv = e->nkv;
+    const int QD = c.n_head * dh, M = plan.M, MP = plan.MP;
+    SVCHECK(ensure_prefill_ws(e, (size_t)M));
+    ++e->prompt_passes;
+    if (!e->rag_rsave) SVCHECK(dalloc(e, &e->rag_rsave, (size_t)3 * c.max_batch * D));
+    SVCHECK(rag_reserve_row_pos(e, (size_t)M));
+    std::vector<int32_t> kr;
+    prefix_kept_rows(plan, B, keep, kr);
+    const int kept = (int)kr.size();
+    size_t need = plan.seg.size() + plan.pseq.size() + plan.pblocks.size() + plan.sseq.size() + plan.sblocks.size() + kr.size();
+    for (int i = 0; i < 4; ++i) need += plan.rows[i].size();
+    SVCHECK(rag_reserve_plan(e, need));
+    size_t off = 0;
+    auto put = [&](const std::vector<int32_t>& v) { const size_t o = off; if (!v.empty()) memcpy(e->h_rag + off, v.data(), v.size() * sizeof(int32_t)); off += v.size(); return o; };
+    const int32_t* d_seg = e->d_rag + put(plan.seg);
+    const int32_t* d_pseq = e->d_rag + put(plan.pseq);
+    const int32_t* d_pblocks = e->d_rag + put(plan.pblocks);
+    const int32_t* d_sseq = e->d_rag + put(plan.sseq);
+    const int32_t* d_sblocks = e->d_rag + put(plan.sblocks);
+    const int32_t* d_rows[4];
+    for (int i = 0; i < 4; ++i) d_rows[i] = e->d_rag + put(plan.rows[i]);
+    const int32_t* d_kr = e->d_rag + put(kr);
+    HIPCHECK(hipMemcpyAsync(e->d_rag, e->h_rag, off * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipEventRecord(e->rag_ev, st));
+    e->rag_pending = true;
+
+    prof_mark(e, PK_PF_ROWS, st);
+    launch_prefix_row_pos(d_seg, P + B, e->rag_row_pos, st);                // solo indices: wpe (v1) and RoPE (v2)
+    if (e->v2) {
+        HIPCHECK(hipMemcpyAsync(e->ph, prefixes, (size_t)MP * D * sizeof(bf16_t), hipMemcpyDeviceToDevice, st));
+        HIPCHECK(hipMemcpyAsync(e->ph + (size_t)MP * D, own, (size_t)(M - MP) * D * sizeof(bf16_t), hipMemcpyDeviceToDevice, st));
+    } else {
+        launch_dec_embed(prefixes, e->wpe, e->ph, 1, MP, D, st, e->rag_row_pos);
+        launch_dec_embed(own, e->wpe, e->ph + (size_t)MP * D, 1, M - MP, D, st, e->rag_row_pos + MP);
+    }
+    AttnPrefillArgs at;
+    at.q = e->pqkv; at.k = e->pqkv + QD; at.v = e->pqkv + QD + nkv * dh;
+    at.q_row_stride = QKV; at.kv_row_stride = QKV; at.q_head_stride = dh; at.kv_head_stride = nkv > 1 ? dh : 0;
+    at.o = e->pattn; at.o_row_stride = QD; at.B = B; at.S = 0; at.H = c.n_head; at.head_dim = dh;
+    at.kv_group = c.n_head / nkv; at.causal = 1; at.scale = 1.0f / sqrtf((float)dh);
+    at.window = c.sliding_window > 0 ? c.sliding_window : 0;
+    for (int i = 0; i < c.n_layer; ++i) {
+        DecLayer& L = e->dec[i];
+        prof_mark(e, PK_PF_ROWS, st);
+        launch_layernorm_rows(e->ph, D, L.ln1.g, L.ln1.b, e->pln, D, M, D, c.ln_eps, st);
+        gemm_ragged(e, PK_PF_GEMM, e->pln, D, L.c_attn, nullptr, 0, e->pqkv, QKV, M, ACT_NONE, st, d_rows[0], (int)plan.rows[0].size());
+        prof_mark(e, PK_PF_ATTN, st);
+        if (e->v2) launch_rope_prefill(e->pqkv, QKV, M, M, c.n_head + nkv, dh, e->rope_cos, e->rope_sin, st, e->rag_row_pos);
+        at.rag_prefixed = 0; at.rag_seq = d_pseq; at.rag_blocks = d_pblocks; at.rag_nblocks = (int)plan.pblocks.size() / 2;
+        launch_attn_prefill(at, st);
+        at.rag_prefixed = 1; at.rag_seq = d_sseq; at.rag_blocks = d_sblocks; at.rag_nblocks = (int)plan.sblocks.size() / 2;
+        launch_attn_prefill(at, st);
+        gemm_ragged(e, PK_PF_GEMM, e->pattn, QD, L.c_proj, e->ph, D, e->ph, D, M, ACT_NONE, st, d_rows[1], (int)plan.rows[1].size());
+        prof_mark(e, PK_PF_ROWS, st);
+        launch_layernorm_rows(e->ph, D, L.ln2.g, L.ln2.b, e->pln, D, M, D, c.ln_eps, st);
+        gemm_ragged(e, PK_PF_GEMM, e->pln, D, L.c_fc, nullptr, 0, e->pmlp, F, M, ACT_GELU_TANH, st, d_rows[2], (int)plan.rows[2].size());
+        gemm_ragged(e, PK_PF_GEMM, e->pmlp, F, L.c_proj2, e->ph, D, e->ph, D, M, ACT_NONE, st, d_rows[3], (int)plan.rows[3].size());
+    }
+    SVCHECK(ensure_score_ws(e, (size_t)kept, false));
+    bf16_t* hk = e->score_ws;
+    bf16_t* hn = hk + (size_t)kept * D;
+    prof_mark(e, PK_PF_ROWS, st);
+    launch_gather_listed_rows(e->ph, D, d_kr, kept, hk, D, st);           // (keep = len + 1: the prefix's last row, then the own rows -- not contiguous)
+    launch_layernorm_rows(hk, D, e->ln_f.g, e->ln_f.b, hn, D, kept, D, c.ln_eps, st);
+    return score_logprob_chunks(e, hn, (size_t)kept, lp, st);
 }
 
 // Arguments of the decode attention of layer `layer` over the engine's KV pool / block table / positions: the c_attn output
@@ -885,6 +968,7 @@ static void score_row_owner(int row, int B, int n_keep, const int32_t* keep, int
     else while (b + 1 < B && first + keep[b] <= row) first += keep[b++];
     *seq = b; *pos = row - first;
 }
+static int score_flag_report(sv_engine* e, const char* who, int B, int n_keep, const int32_t* keep, hipStream_t st);
 // One scoring-mode prompt pass under the engine lock: pages for exactly the rows given, the pass, positions = the lengths, and -- with lp -- the
 // kernels' flag.  lens == nullptr: B sequences of S rows, the last n_keep kept (into dev_scores or lp); otherwise the ragged pass over (lens, keep).
 static int score_pass(sv_engine* e, const char* who, const void* embeds, int B, int S, int n_keep, const int32_t* lens, const int32_t* keep,
@@ -904,13 +988,16 @@ static int score_pass(sv_engine* e, const char* who, const void* embeds, int B, 
     e->cached_B = B;
     HIPCHECK(hipGetLastError());
     if (!lp) return 0;
-    // the kernel's flag: a target outside the vocabulary (its logprob is NaN) / a row without a finite logit (all of its outputs are NaN)
+    return score_flag_report(e, who, B, n_keep, lens ? keep : nullptr, st);
+}
+// the scoring kernels' flag: a target outside the vocabulary (its logprob is NaN) / a row without a finite logit (all of its outputs are NaN)
+static int score_flag_report(sv_engine* e, const char* who, int B, int n_keep, const int32_t* keep, hipStream_t st) {
     int32_t flag[2] = {0, 0};
     HIPCHECK(hipMemcpyAsync(flag, e->score_chunk_ws + (size_t)e->score_chunk_alloc * e->Vpad, sizeof(flag), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
     if (!(flag[0] & 3)) return 0;
     int seq = 0, pos = 0;
-    score_row_owner(flag[1], B, n_keep, lens ? keep : nullptr, &seq, &pos);
+    score_row_owner(flag[1], B, n_keep, keep, &seq, &pos);
     if (flag[0] & 2)
         return fail(SV_EHIP, "%s: a row of logits had no finite value (NaN / Inf in the weights or inputs?); first at row %d "
                              "(sequence %d, kept position %d)", who, flag[1], seq, pos);
@@ -1005,6 +1092,59 @@ extern "C" int sv_forward_logprobs_ragged(sv_engine* e, const void* dev_embeds_p
     return score_call(e, {"sv_forward_logprobs_ragged", true, dev_embeds_packed, B, 0, 0, host_lens, host_keep, temperature,
                           {dev_targets, 1.0f / temperature, dev_logprob, dev_logsumexp, dev_entropy, dev_argmax, k, dev_topk_ids, dev_topk_logprobs, dev_rank}},
                       stream);
+}
+
+// sv_forward_logprobs_ragged over sequences that share prefixes: every prefix goes through the decoder once (prefill_forward_prefixed)
+extern "C" int sv_forward_logprobs_prefixed(sv_engine* e, const void* dev_prefix_packed, int32_t P, const int32_t* host_prefix_lens,
+                                            const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, const int32_t* host_prefix_of,
+                                            const int32_t* host_keep, const int32_t* dev_targets, float temperature, float* dev_logprob,
+                                            float* dev_logsumexp, float* dev_entropy, int32_t* dev_argmax, int32_t k, int32_t* dev_topk_ids,
+                                            float* dev_topk_logprobs, int32_t* dev_rank, sv_stream stream) {
+    const char* who = "sv_forward_logprobs_prefixed";
+    // (the checks that need no engine come first: they are the same on a machine without a GPU)
+    if (!dev_prefix_packed || !host_prefix_lens || !dev_embeds_packed || !host_lens || !host_prefix_of || !host_keep || !dev_targets)
+        return fail(SV_EINVAL, "%s: null prefixes / embeds / lengths / prefix_of / keep / targets pointer", who);
+    SVCHECK(prefix_check(who, host_prefix_lens, P, host_lens, host_prefix_of, B, host_keep));
+    if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail(SV_EINVAL, "%s: temperature must be finite and > 0", who);
+    if (k < 0 || k > SV_TOPK_MAX) return fail(SV_EINVAL, "%s: k=%d must be in 0..%d", who, k, SV_TOPK_MAX);
+    if (k > 0 && (!dev_topk_ids || !dev_topk_logprobs)) return fail(SV_EINVAL, "%s: k=%d with a null dev_topk_ids / dev_topk_logprobs", who, k);
+    if (k == 0 && !dev_logprob && !dev_logsumexp && !dev_entropy && !dev_argmax) return fail(SV_EINVAL, "%s: every output pointer is null", who);
+    SVCHECK(check_ready(e));
+    if (B > e->cfg.max_batch) return fail(SV_EINVAL, "%s: bad B=%d (max_batch %d)", who, B, e->cfg.max_batch);
+    for (int b = 0; b < B; ++b) {
+        const long long T = (long long)host_prefix_lens[host_prefix_of[b]] + host_lens[b];
+        if (T > e->cfg.max_seq_len)
+            return fail(SV_EINVAL, "%s: length %lld of sequence %d (prefix %d + own %d) out of range (1..max_seq_len %d)", who, T, b,
+                        host_prefix_lens[host_prefix_of[b]], host_lens[b], e->cfg.max_seq_len);
+    }
+    // (every weight format: the pass is the ragged pass's launches -- fp8's column-scale epilogue and the bf16 image of an mxfp4 engine are per row and
+    //  per column --, and tests/test_gpu_prefix_scoring.py holds each format to the contract)
+    const Linear* proj[4] = {&e->dec[0].c_attn, &e->dec[0].c_proj, &e->dec[0].c_fc, &e->dec[0].c_proj2};
+    const PrefixProj pj[4] = {{proj[0]->N, proj[0]->Kpad, ACT_NONE}, {proj[1]->N, proj[1]->Kpad, ACT_NONE}, {proj[2]->N, proj[2]->Kpad, ACT_GELU_TANH},
+                              {proj[3]->N, proj[3]->Kpad, ACT_NONE}};
+    static const char* const proj_name[4] = {"c_attn", "attention c_proj", "c_fc", "MLP c_proj"};
+    PrefixPlan plan;
+    // (SV_EXP_BATCH_REMAINDER: no per-sequence remainder anywhere, as in the ragged pass -- nothing to list and nothing to refuse)
+    prefix_plan(host_prefix_lens, P, host_lens, host_prefix_of, B, attn_prefill_q_tile(e->cfg.n_head, e->nkv), pj,
+                (e->exp & SV_EXP_BATCH_REMAINDER) ? 0 : 4, plan);
+    plan.rows.resize(4);
+    if (plan.refused >= 0) {
+        const int b = plan.refused, pl = host_prefix_lens[host_prefix_of[b]];
+        return fail(SV_EINVAL, "%s: sequence %d (prefix %d + own %d rows): the %d remainder rows of its %d-row solo run at %s would reach into the "
+                    "shared prefix (score it alone: sv_forward_logprobs_ragged on the concatenation)", who, b, pl, host_lens[b],
+                    seq_peel_rows(pl + host_lens[b]), pl + host_lens[b], proj_name[plan.refused_proj]);
+    }
+    ScoreLogprobs lp{dev_targets, 1.0f / temperature, dev_logprob, dev_logsumexp, dev_entropy, dev_argmax, k, dev_topk_ids, dev_topk_logprobs, dev_rank};
+    if (k == 0) { lp.topk_ids = nullptr; lp.topk_logprobs = nullptr; lp.rank = nullptr; }
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIPCHECK(hipSetDevice(e->cfg.device));
+    SVCHECK(cb_guard(e, who));
+    // no page is assigned and none is written: whatever the cache held is void for sv_decode_step from here on (cached_B = 0: SV_ESTATE)
+    e->cached_B = 0;
+    SVCHECK(prefill_forward_prefixed(e, (const bf16_t*)dev_prefix_packed, (const bf16_t*)dev_embeds_packed, P, B, plan, host_keep, &lp, st));
+    HIPCHECK(hipGetLastError());
+    return score_flag_report(e, who, B, 0, host_keep, st);
 }
 
 extern "C" int sv_decode_step(sv_engine* e, const int32_t* dev_tokens, int32_t B, float* dev_logits, sv_stream stream) {

@@ -366,6 +366,25 @@ int prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, const int3
 void ragged_positions(sv_engine* e, int B, int rep, int delta, hipStream_t st);
 // the launch behind it: positions[i] = rag_seq[2 * (i / rep) + 1] + delta for i < n, descriptors {first packed row, length}
 void launch_ragged_positions(int32_t* positions, const int32_t* rag_seq, int n, int rep, int delta, hipStream_t st);
+// The shared-prefix scoring pass (sv_forward_logprobs_prefixed): P prefixes and the own rows of B sequences in ONE packed buffer, prefixes first;
+// sequence b stands for the solo sequence concat(prefix[prefix_of[b]], own rows of b) of T_b = Pl + len_b rows.  Everything the pass decides is
+// host arithmetic (prefix/prefix.hip; sv_debug_prefix_plan states it for the CPU tests).
+struct PrefixPlan {
+    int MP = 0, M = 0;                     // prefix rows | all packed rows (the own rows follow the prefixes, in sequence order)
+    int refused = -1, refused_proj = -1;   // first sequence whose remainder rows would reach into its prefix (and the projection that says so)
+    std::vector<int32_t> seg;              // {first packed row, length, position of its first row} x (P + B): the row-position builder's segments
+    std::vector<int32_t> pseq, pblocks;    // the prefixes as ordinary ragged sequences {first packed row, Pl} | {prefix, query tile}, every tile
+    std::vector<int32_t> sseq, sblocks;    // {first own packed row, T, first prefix packed row, Pl} | {sequence, query tile}: tiles whose last row >= Pl
+    std::vector<std::vector<int32_t>> rows;   // per projection: the packed OWN rows with solo index >= T - seq_peel_rows(T) where gemm_seq_form(T, ...) holds
+};
+struct PrefixProj { int N, K, act; };
+// SV_EINVAL + message (who: ...) for P / B out of order (1 <= P <= B), a length < 1, a prefix_of outside 0..P-1, a prefix no sequence uses, and
+// -- keep != nullptr -- a keep outside 1..len + 1
+int prefix_check(const char* who, const int32_t* prefix_lens, int P, const int32_t* lens, const int32_t* prefix_of, int B, const int32_t* keep);
+void prefix_plan(const int32_t* prefix_lens, int P, const int32_t* lens, const int32_t* prefix_of, int B, int q_tile, const PrefixProj* proj, int n_proj,
+                 PrefixPlan& out);
+// the packed rows of the kept rows, in output order: the last keep[b] solo rows of every sequence (keep = len + 1 starts at its prefix's last row)
+void prefix_kept_rows(const PrefixPlan& plan, int B, const int32_t* keep, std::vector<int32_t>& out);
 // engine_generate.hip
 void fork_args(sv_engine* e, int n_prompts, int n_rows, ForkArgs& f);      // the fork launch over e->fork_desc, the engine's block table, pool and logits
 // validation of a processor set against a vocabulary of V ids (V <= 0: the ids are only checked for >= 0) -- host arithmetic, no device -- and

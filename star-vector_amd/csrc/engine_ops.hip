@@ -1304,6 +1304,52 @@ extern "C" int sv_op_attention_prefill(const void* qkv, int32_t q_off, int32_t k
     return 0;
 }
 
+// attn_prefill_kernel's prefixed form alone, with the descriptors and the block list of the shared-prefix scoring pass (prefix_plan).  As above every
+// access stays inside packed rows * row_stride elements of `qkv` and packed rows * H * head_dim elements of `out`: a solo index below T maps to a row
+// of the sequence's prefix or to one of its own rows, and only own rows are stored.
+extern "C" int sv_op_attn_prefill_prefixed(const void* qkv, int32_t q_off, int32_t k_off, int32_t v_off, int32_t row_stride, void* out, int32_t P,
+                                           const int32_t* host_prefix_lens, int32_t B, const int32_t* host_lens, const int32_t* host_prefix_of,
+                                           int32_t H, int32_t Hkv, int32_t head_dim, float scale, int32_t window, sv_stream stream) {
+    const char* who = "sv_op_attn_prefill_prefixed";
+    if (!qkv || !out || !host_prefix_lens || !host_lens || !host_prefix_of) return fail(SV_EINVAL, "%s: null pointer", who);
+    if (H < 1 || Hkv < 1 || H > 4096) return fail(SV_EINVAL, "%s: bad shape (H %d, Hkv %d)", who, H, Hkv);
+    if (H % Hkv) return fail(SV_EINVAL, "%s: %d query heads are not a multiple of %d KV heads", who, H, Hkv);
+    if (head_dim != 64 && head_dim != 128) return fail(SV_EINVAL, "%s: head_dim %d unsupported (64|128)", who, head_dim);
+    if (q_off < 0 || k_off < 0 || v_off < 0 || row_stride < 8 || (q_off | k_off | v_off | row_stride) % 8)
+        return fail(SV_EINVAL, "%s: offsets %d / %d / %d and row stride %d must be non-negative multiples of 8 elements (16-byte loads)", who,
+                    q_off, k_off, v_off, row_stride);
+    if ((long long)q_off + (long long)H * head_dim > row_stride || (long long)k_off + (long long)Hkv * head_dim > row_stride ||
+        (long long)v_off + (long long)Hkv * head_dim > row_stride)
+        return fail(SV_EINVAL, "%s: q / k / v columns reach beyond the row stride %d", who, row_stride);
+    if (!(scale > 0.f) || std::isinf(scale)) return fail(SV_EINVAL, "%s: scale must be positive and finite", who);
+    if (window < 0) return fail(SV_EINVAL, "%s: window %d < 0", who, window);
+    SVCHECK(prefix_check(who, host_prefix_lens, P, host_lens, host_prefix_of, B, nullptr));
+    long long rows = 0;
+    for (int u = 0; u < P; ++u) rows += host_prefix_lens[u];
+    for (int b = 0; b < B; ++b) rows += host_lens[b];
+    if (rows > (1 << 24) || B > 65535) return fail(SV_EINVAL, "%s: %lld rows / %d sequences: more than this test surface takes", who, rows, B);
+
+    hipStream_t st = (hipStream_t)stream;
+    PrefixPlan pp;
+    prefix_plan(host_prefix_lens, P, host_lens, host_prefix_of, B, attn_prefill_q_tile(H, Hkv), nullptr, 0, pp);
+    std::vector<int32_t> plan(pp.sseq);
+    plan.insert(plan.end(), pp.sblocks.begin(), pp.sblocks.end());
+    TmpBufs tmp;
+    int32_t* d_plan;
+    SVCHECK(tmp.get(&d_plan, plan.size()));
+    HIPCHECK(hipMemcpyAsync(d_plan, plan.data(), plan.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    AttnPrefillArgs a;
+    a.q = (const bf16_t*)qkv + q_off; a.k = (const bf16_t*)qkv + k_off; a.v = (const bf16_t*)qkv + v_off;
+    a.q_row_stride = row_stride; a.kv_row_stride = row_stride; a.q_head_stride = head_dim; a.kv_head_stride = Hkv > 1 ? head_dim : 0;
+    a.o = (bf16_t*)out; a.o_row_stride = H * head_dim; a.B = B; a.S = 0; a.H = H; a.head_dim = head_dim;
+    a.kv_group = H / Hkv; a.causal = 1; a.scale = scale; a.window = window;
+    a.rag_seq = d_plan; a.rag_blocks = d_plan + pp.sseq.size(); a.rag_nblocks = (int)pp.sblocks.size() / 2; a.rag_prefixed = 1;
+    launch_attn_prefill(a, st);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));          // the plan is freed on return
+    return 0;
+}
+
 extern "C" int sv_op_plane_layernorm(const void* x, const void* gamma, const void* beta, void* y, int32_t B, int32_t QD,
                                      float eps, sv_stream stream) {
     if (!x || !gamma || !beta || !y || B < 1 || QD < 8 || QD % 8) return fail(SV_EINVAL, "sv_op_plane_layernorm: bad argument");

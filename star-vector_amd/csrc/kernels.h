@@ -264,6 +264,9 @@ void launch_gather_last_rows(const bf16_t* h, bf16_t* out, int B, int S0, int D,
 void launch_gather_listed_rows(const bf16_t* x, int ldx, const int32_t* rows, int n, bf16_t* out, int D, hipStream_t st);
 // ragged prompt pass: row_pos[first row of b + j] = j for j < len[b], from the descriptors {first packed row, length} [B]
 void launch_ragged_row_pos(const int32_t* rag_seq, int B, int32_t* row_pos, hipStream_t st);
+// shared-prefix scoring pass (prefix/prefix.hip): row_pos[first row of segment i + j] = pos0 of segment i + j for j < its length, from the
+// segment descriptors {first packed row, length, pos0} [n_seg] -- a prefix starts at 0, a sequence's own rows at its prefix's length
+void launch_prefix_row_pos(const int32_t* seg, int n_seg, int32_t* row_pos, hipStream_t st);
 // rag_keep (ragged scoring pass): per-sequence descriptors {first packed row, length, keep, first output row}, rag_rows = sum(keep) output rows;
 // nullptr: the last n_keep rows of B sequences of S0 rows
 void launch_gather_tail_rows(const bf16_t* h, bf16_t* out, int B, int S0, int n_keep, int D, hipStream_t st, const int32_t* rag_keep = nullptr,
@@ -294,6 +297,11 @@ struct AttnPrefillArgs {
     const int32_t* rag_seq = nullptr;
     const int32_t* rag_blocks = nullptr;
     int rag_nblocks = 0;
+    // Prefixed form of the ragged form (the shared-prefix scoring pass): rag_seq [n_seq] = {first OWN packed row, T, first PREFIX packed row, Pl}.
+    // The sequence is the solo sequence concat(prefix, own rows) of T = Pl + len rows: tiles, masks and the window are counted from solo index 0
+    // as above, only the ADDRESS of solo index s changes (s < Pl: prefix row s, else own row s - Pl), and output rows with s < Pl are not stored
+    // (the prefix's own launch writes them).  The caller lists only the query tiles whose last row is >= Pl.
+    int rag_prefixed = 0;
 };
 inline int attn_prefill_q_tile(int n_head, int n_kv_head) { const int g = n_head / (n_kv_head > 0 ? n_kv_head : 1); return (g % 4 == 0 && n_head % 4 == 0) ? 32 : 128; }
 void launch_attn_prefill(const AttnPrefillArgs& a, hipStream_t st);

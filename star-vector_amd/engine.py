@@ -584,6 +584,47 @@ class HipEngine:
                                                   *map(_ptr, res[:4]), top_k, *map(_ptr, lists), _stream()), "sv_forward_logprobs_ragged")
         return res
 
+    def forward_logprobs_prefixed(self, prefixes, seqs, prefix_of, targets, keep, temperature: float = 1.0, entropy: bool = False,
+                                  argmax: bool = False, top_k: int = 0):
+        """`forward_logprobs_ragged` over sequences that share prefixes, every prefix through the decoder ONCE (sv_forward_logprobs_prefixed):
+        `prefixes` and `seqs` are lists of [n, D] bf16 tensors, sequence b stands for cat(prefixes[prefix_of[b]], seqs[b]); keep[b] in
+        1..len_b + 1 = the last rows of that concatenation that are scored (len_b + 1 reaches the prefix's last row, which predicts the first own
+        token); targets: integer [sum(keep)] in sequence order, -100 = ignore.  Returns the result types of `forward_logprobs_ragged`.  Every
+        sequence's slice holds the bits of `forward_logprobs(cat(prefix, seq)[None], targets_b[None], keep[b], ...)` alone.  A sequence whose
+        split-K remainder rows would reach into its prefix is refused (ValueError naming it; `prefix_plan` says so beforehand): score it with
+        `forward_logprobs_ragged` on the concatenation.  Every weight format.  No KV page is written: `decode_step` refuses afterwards."""
+        px, parr, plens = self._packed(prefixes)
+        x, arr, lens = self._packed(seqs)
+        prefix_of, keep = [int(v) for v in prefix_of], [int(v) for v in keep]
+        if len(prefix_of) != len(lens) or any(not 0 <= u < len(plens) for u in prefix_of):
+            raise ValueError(f"prefix_of {prefix_of} must hold one index in 0..{len(plens) - 1} for each of the {len(lens)} sequences")
+        if len(keep) != len(lens) or any(not 1 <= k <= n + 1 for k, n in zip(keep, lens)):
+            raise ValueError(f"keep {keep} must hold one count in 1..length + 1 for each of the lengths {lens}")
+        t, res = self._score_outputs(x, targets, (sum(keep),), "[sum(keep)]", entropy, argmax, top_k)
+        lists = res[4:] if top_k else (None, None, None)
+        ints = lambda v: (C.c_int32 * len(v))(*v)
+        check(self.lib.sv_forward_logprobs_prefixed(self._h, _ptr(px), len(plens), parr, _ptr(x), len(lens), arr, ints(prefix_of), ints(keep), _ptr(t),
+                                                    float(temperature), *map(_ptr, res[:4]), top_k, *map(_ptr, lists), _stream()),
+              "sv_forward_logprobs_prefixed")
+        return res
+
+    def prefix_refused(self, prefix_lengths, lengths, prefix_of) -> List[int]:
+        """The sequences `forward_logprobs_prefixed` would refuse on this engine: those whose split-K remainder rows would reach into their
+        prefix at one of the decoder's four projections (`prefix_plan`; host arithmetic).  Each one is a property of its own (Pl, len) alone."""
+        c = self.cfg
+        D, F, dh = c.hidden, c.n_inner, c.hidden // c.n_head
+        qkv = c.n_head * dh + 2 * max(int(c.n_kv_head), 1) * dh
+        proj = ((qkv, D, "none"), (D, D, "none"), (F, D, "gelu_tanh"), (D, F, "none"))
+        seen: Dict[Tuple[int, int], bool] = {}
+        out = []
+        for b, (n, u) in enumerate(zip(lengths, prefix_of)):
+            key = (int(prefix_lengths[int(u)]), int(n))
+            if key not in seen:
+                seen[key] = any(prefix_plan([key[0]], [key[1]], [0], N, K, act)["refused"] is not None for N, K, act in proj)
+            if seen[key]:
+                out.append(b)
+        return out
+
     def set_score_chunk_rows(self, rows: int) -> None:
         """Rows per lm_head chunk of `forward_logprobs` (a multiple of 256; 0 = default).  Test surface: the outputs do not depend on it."""
         check(self.lib.sv_debug_set_score_chunk_rows(self._h, int(rows)), "sv_debug_set_score_chunk_rows")
@@ -1251,6 +1292,27 @@ def ragged_plan(lengths: Sequence[int], N: int, K: int, act: str = "none", q_til
     return {"rows": list(rows)[: out[0]], "last": list(last)[: out[1]], "attn_blocks": out[2], "kv_blocks": out[3]}
 
 
+def prefix_plan(prefix_lengths: Sequence[int], lengths: Sequence[int], prefix_of: Sequence[int], N: int, K: int, act: str = "none",
+                q_tile: int = 32) -> Dict[str, object]:
+    """What the shared-prefix scoring pass decides at the projection (N, K, act) (sv_debug_prefix_plan; host arithmetic, no GPU), rows packed
+    prefixes first: "row_pos" the solo index of every packed row, "rows" the packed (own) rows that take the split-K remainder kernel,
+    "blocks" the (sequence, query tile) pairs of the prefixed attention launch, "refused" the first sequence whose remainder rows would reach
+    into its prefix (None: the call is taken)."""
+    pl, ln, po = [int(v) for v in prefix_lengths], [int(v) for v in lengths], [int(v) for v in prefix_of]
+    if len(po) != len(ln):
+        raise ValueError("one prefix index per sequence")
+    P, B = len(pl), len(ln)
+    total = sum(max(v, 0) for v in pl + ln)
+    cap = max(total, 3 * B, 2 * sum(max(n, 0) // max(int(q_tile), 1) + 2 for n in ln), 1)      # (a sequence lists at most len / q_tile + 2 tiles)
+    ints = lambda v: (C.c_int32 * max(len(v), 1))(*v)
+    pos, rows, blocks, out = (C.c_int32 * cap)(), (C.c_int32 * cap)(), (C.c_int32 * cap)(), (C.c_int32 * 4)()
+    check(_lib.load().sv_debug_prefix_plan(ints(pl), P, ints(ln), ints(po), B, int(N), int(K), _lib.ACT[act], int(q_tile), pos, rows, blocks, cap, out),
+          "sv_debug_prefix_plan")
+    b = list(blocks)[: 2 * out[1]]
+    return {"row_pos": list(pos)[: out[3]], "rows": list(rows)[: out[0]], "blocks": list(zip(b[0::2], b[1::2])),
+            "refused": None if out[2] < 0 else int(out[2])}
+
+
 def shared_plan(lengths: Sequence[int], group: Sequence[int], budgets: Sequence[int]) -> Dict[str, object]:
     """The page plan of a shared prompt pass (sv_debug_shared_plan; host arithmetic, no GPU): per request the shared and the private
     block-table entries, and the pages the admit takes in all."""
@@ -1501,6 +1563,33 @@ def op_attention_prefill(qkv, q_off, k_off, v_off, n_head, n_kv_head, head_dim, 
     check(lib.sv_op_attention_prefill(_ptr(qkv), int(q_off), int(k_off), int(v_off), stride, _ptr(out), B, S, c_lens, int(n_head),
                                       int(n_kv_head), int(head_dim), int(bool(causal)), float(scale if scale is not None else head_dim ** -0.5),
                                       int(window), int(last_rows), _stream()), "sv_op_attention_prefill")
+    return out
+
+
+def op_attn_prefill_prefixed(qkv, q_off, k_off, v_off, n_head, n_kv_head, head_dim, prefix_lens, lens, prefix_of, *, window=0, scale=None,
+                             out=None):
+    """The prompt-pass attention in its PREFIXED form alone (sv_op_attn_prefill_prefixed): the rows of `qkv` [rows, row_stride] are the prefixes
+    back to back, then every sequence's own rows; sequence b attends as cat(prefix[prefix_of[b]], own rows).  Only the own rows of `out`
+    ([rows, n_head * head_dim], may be handed in pre-filled) are written.  Returns `out`."""
+    lib = _lib.load()
+    if not qkv.is_cuda or qkv.dtype != torch.bfloat16 or qkv.dim() != 2 or not qkv.is_contiguous():
+        raise ValueError("qkv must be a contiguous 2-D bfloat16 CUDA(HIP) tensor [rows, row_stride]")
+    pl, ln, po = [int(v) for v in prefix_lens], [int(v) for v in lens], [int(v) for v in prefix_of]
+    if len(po) != len(ln) or not pl or not ln:
+        raise ValueError("one prefix index per sequence, at least one prefix and one sequence")
+    rows = sum(max(v, 0) for v in pl + ln)
+    stride, width = qkv.shape[1], int(n_head) * int(head_dim)
+    # the kernel addresses rows * row_stride elements of qkv and rows * n_head * head_dim of out: both must lie inside the tensors
+    if rows > qkv.shape[0]:
+        raise ValueError(f"qkv holds {qkv.shape[0]} rows, the call addresses {rows}")
+    if out is None:
+        out = torch.empty(rows, width, dtype=torch.bfloat16, device=qkv.device)
+    elif not out.is_cuda or out.dtype != torch.bfloat16 or not out.is_contiguous() or out.numel() < rows * width:
+        raise ValueError(f"out must be a contiguous bfloat16 CUDA(HIP) tensor of at least {rows} x {width} elements")
+    ints = lambda v: (C.c_int32 * len(v))(*v)
+    check(lib.sv_op_attn_prefill_prefixed(_ptr(qkv), int(q_off), int(k_off), int(v_off), stride, _ptr(out), len(pl), ints(pl), len(ln), ints(ln),
+                                          ints(po), int(n_head), int(n_kv_head), int(head_dim), float(scale if scale is not None else head_dim ** -0.5),
+                                          int(window), _stream()), "sv_op_attn_prefill_prefixed")
     return out
 
 

@@ -1367,7 +1367,8 @@ class StarVectorForCausalLM(nn.Module):
 
     @torch.no_grad()
     def completion_logprobs(self, vision_embeds, input_ids, num_generations, attention_mask, num_logits_to_keep,
-                            temperature: float = 1.0, return_entropy: bool = False, top_logprobs: int = 0, unpadded: bool = False):
+                            temperature: float = 1.0, return_entropy: bool = False, top_logprobs: int = 0, unpadded: bool = False,
+                            share_prefix: bool = False):
         """What a GRPO trainer computes from `forward`'s logits, without the logits: float32 [B, n], out[b, j] = the log-probability
         of input_ids[b, -n + j] given everything before it -- selective_log_softmax(forward(...).logits[:, :-1] / temperature, ids)
         with the softmax in fp32 over the bf16 logits (sv_forward_logprobs: device memory does not grow with B * n * vocab).
@@ -1382,8 +1383,18 @@ class StarVectorForCausalLM(nn.Module):
         equal scoring each row alone without its pads, bit for bit; they are NOT the bits of the padded call (unpadded=False), where a
         right-padded row takes its GEMM kernels by the padded length S, not by its own.  Entries at pads hold the fill values: 0 for log-prob,
         entropy and rank, id -1 / log-prob 0 in the lists.  A mask without pads takes the rectangular call; an engine without
-        `forward_logprobs_ragged` raises NotImplementedError."""
+        `forward_logprobs_ragged` raises NotImplementedError.
+        share_prefix=True (sv_forward_logprobs_prefixed): vision_embeds is [P, Sv, hidden] and is NOT repeated -- row r of input_ids belongs to
+        image r % P (the reference's `repeat` order) and every image's visual rows go through the decoder ONCE, not num_generations times.  Rows
+        are stripped of their right padding as under unpadded=True and go down in one prefixed pass; a mask with left pads (they would lie in
+        the shared prefix) raises ValueError, one with holes NotImplementedError.  A row the entry point would refuse (its split-K remainder rows
+        would reach into the prefix: `HipEngine.prefix_refused`) is scored through `forward_logprobs_ragged` on its concatenation in the same
+        call.  Shapes, fill values and dict keys as above; the values equal each stripped row's solo run bit for bit, hence unpadded=True
+        wherever that call takes the ragged pass."""
         k = int(top_logprobs or 0)
+        if share_prefix:
+            return self._completion_logprobs_shared(vision_embeds, input_ids, num_generations, attention_mask, num_logits_to_keep, temperature,
+                                                    return_entropy, k)
         completion_embeds = self.model._get_embeddings(input_ids)
         inputs_embeds = torch.cat([vision_embeds.repeat(num_generations, 1, 1).to(completion_embeds.dtype),
                                    completion_embeds], dim=1)
@@ -1479,6 +1490,80 @@ class StarVectorForCausalLM(nn.Module):
         if k:
             res = {"logprobs": lp, "top_token_ids": dense(r.top_token_ids, -1, k), "top_logprobs": dense(r.top_logprobs, 0.0, k),
                    "token_ranks": dense(r.token_ranks, 0)}
+            if return_entropy:
+                res["entropies"] = ent
+            return res
+        return (lp, ent) if return_entropy else lp
+
+    def _completion_logprobs_shared(self, vision_embeds, input_ids, num_generations, attention_mask, num_logits_to_keep, temperature,
+                                    return_entropy, k):
+        """`completion_logprobs(share_prefix=True)`: the unpadded pass with every image's visual rows as a shared prefix.  Row b = (prefix b % P,
+        own rows = its completion embeddings up to its last real position); its scored tokens sit at S - n .. end - 1 as in the unpadded pass,
+        so its last c + 1 rows are kept -- c = own length reaches the prefix's last row, which predicts the first completion token."""
+        fn = getattr(self.engine, "forward_logprobs_prefixed", None)
+        if fn is None or getattr(self.engine, "forward_logprobs_ragged", None) is None:
+            raise NotImplementedError("completion_logprobs(share_prefix=True) needs an engine with forward_logprobs_prefixed")
+        own = self.model._get_embeddings(input_ids).to(torch.bfloat16)
+        dev_ = own.device
+        B, L = input_ids.shape
+        P, Sv = vision_embeds.shape[:2]
+        S = Sv + L
+        if B != P * int(num_generations):
+            raise ValueError(f"share_prefix: {B} completions are not num_generations ({num_generations}) x {P} images")
+        n = int(num_logits_to_keep or 0) or L
+        if n < 1 or n > L:
+            raise ValueError(f"num_logits_to_keep ({n}) must be in 1..{L}: every scored token needs a position before it")
+        if attention_mask is None:
+            m = torch.ones(B, S, dtype=torch.bool, device=dev_)
+        else:
+            if tuple(attention_mask.shape) != (B, S):
+                raise ValueError(f"attention_mask {tuple(attention_mask.shape)} does not cover inputs_embeds {(B, S)}")
+            if self._scoring_mask_lead(attention_mask, (B, S)) is not None:
+                raise ValueError("share_prefix: left padding would lie inside the shared visual prefix (right padding only)")
+            m = attention_mask.to(torch.bool).to(dev_)
+        ends = m.sum(1).tolist()                                   # real positions 0 .. end - 1 (no lead, no holes)
+        lens = [e - Sv for e in ends]
+        if min(lens) < 1:
+            raise ValueError(f"share_prefix: rows {[b for b, v in enumerate(lens) if v < 1]} end inside the visual prefix: a row needs one completion token")
+        targets = torch.full((B, n + 1), -100, dtype=torch.int32, device=dev_)
+        targets[:, :n] = input_ids[:, L - n:].to(device=dev_, dtype=torch.int32).masked_fill(~m[:, S - n:], -100)
+        count = [max(0, e - (S - n)) for e in ends]
+        keep = [c + 1 for c in count]
+        row_targets = [torch.cat([targets[b, :c], targets[b, n:]]) for b, c in enumerate(count)]
+        prefixes = [vision_embeds[u].to(torch.bfloat16).to(dev_) for u in range(P)]
+        seqs = [own[b, :lens[b]] for b in range(B)]
+        prefix_of = [b % P for b in range(B)]
+        refused = set(self.engine.prefix_refused([Sv] * P, lens, prefix_of))
+        take = [b for b in range(B) if b not in refused]
+        kw = dict(temperature=temperature, entropy=return_entropy, **({"top_k": k} if k else {}))
+        parts = []                                                 # (rows, result) per engine call
+        if take:
+            used = sorted({prefix_of[b] for b in take})            # (a prefix whose every row is refused stays out of the pass)
+            slot = {u: i for i, u in enumerate(used)}
+            parts.append((take, self._run_scoring(lambda: fn([prefixes[u] for u in used], [seqs[b] for b in take], [slot[prefix_of[b]] for b in take],
+                                                               torch.cat([row_targets[b] for b in take]), [keep[b] for b in take], **kw))))
+        if refused:
+            rest = sorted(refused)
+            cat = [torch.cat([prefixes[prefix_of[b]], seqs[b]]) for b in rest]
+            parts.append((rest, self._run_scoring(lambda: self.engine.forward_logprobs_ragged(cat, torch.cat([row_targets[b] for b in rest]),
+                                                                                              [keep[b] for b in rest], **kw))))
+
+        def dense(name, fill, *tail):
+            out = None
+            for rows, r in parts:
+                packed, first = getattr(r, name), 0
+                if out is None:
+                    out = torch.full((B, n, *tail), fill, dtype=packed.dtype, device=packed.device)
+                for b in rows:                                     # the -100 row behind every sequence's entries is dropped
+                    out[b, :count[b]] = packed[first:first + count[b]]
+                    first += keep[b]
+            return out
+
+        lp = dense("logprobs", 0.0)
+        ent = dense("entropy", 0.0) if return_entropy else None
+        if k:
+            res = {"logprobs": lp, "top_token_ids": dense("top_token_ids", -1, k), "top_logprobs": dense("top_logprobs", 0.0, k),
+                   "token_ranks": dense("token_ranks", 0)}
             if return_entropy:
                 res["entropies"] = ent
             return res
