@@ -1,6 +1,9 @@
 // Host driver, part 2 of 5: the op graphs -- vision tower, adapter, prompt pass, one decode step -- and the forward entry
 // points of the C ABI (sv_encode_image, sv_adapter, sv_embed_tokens, sv_prefill, sv_forward_logits, sv_forward_logprobs, sv_forward_logprobs_ragged,
-// sv_forward_logprobs_prefixed, sv_decode_step).
+// sv_forward_logprobs_prefixed, sv_decode_step).  The prompt pass is two layer loops: prefill_forward (rectangular, B x S0 rows) and
+// prefill_forward_packed (sequences of different lengths, ragged or behind shared prefixes, driven by the lists of one PackedPlan); the fragments that
+// are the same in both -- attention arguments, GEMM arguments, last-row logits, the log-prob tail -- are functions in front of them.  Every scoring
+// entry point with log-probs goes through one ScoreCall / check_score_call / score_pass.
 #include <algorithm>
 #include <cmath>
 #include "engine_internal.h"
@@ -25,37 +28,34 @@ void prof_mark(sv_engine* e, int kind, hipStream_t st) {
 // ------------------------------------------------------------------------------------------------
 // `kind`: the stage this GEMM belongs to in a time-to-first-token profile (sv_profile_ttft; prof_mark is a no-op otherwise); the
 // remainder-row launch of a peeled GEMM is marked PK_GEMM_TAIL through the launcher's hook
-struct TailMarkCtx { sv_engine* e; };
-static void tail_mark_cb(void* c, hipStream_t st) { prof_mark(static_cast<TailMarkCtx*>(c)->e, PK_GEMM_TAIL, st); }
+static void tail_mark_cb(void* e, hipStream_t st) { prof_mark(static_cast<sv_engine*>(e), PK_GEMM_TAIL, st); }
+// the stage mark and the arguments every engine GEMM shares: C [M][l.N] = act(A l.W + bias) + R, bf16 out
+static GemmArgs gemm_args(sv_engine* e, int kind, const bf16_t* A, int lda, const Linear& l, const bf16_t* R, int ldr, void* C, int ldc, int M,
+                          int act, hipStream_t st) {
+    prof_mark(e, kind, st);
+    GemmArgs g;
+    if (e->prof_on) { g.tail_mark = tail_mark_cb; g.tail_ctx = e; }
+    g.A = A; g.lda = lda; g.Wp = l.Wp; g.bias = l.bias; g.R = R; g.ldr = ldr; g.C = C; g.ldc = ldc;
+    g.M = M; g.N = l.N; g.K = l.Kpad; g.act = act; g.out_f32 = 0;
+    g.cscale = l.wfmt == SV_WFMT_FP8 ? l.wscale : nullptr;
+    return g;
+}
 // seq_rows: the M rows are whole sequences of that many rows (vision tokens of an image, prompt rows of a request): where gemm_seq_form holds
 // the rows a sequence leaves over its 256-row tiles go through the split-K remainder kernel (gemm.hip); last_rows: the M rows are the LAST
 // rows of such sequences (compact) and take the kernel they take inside the full problem
 static void gemm(sv_engine* e, int kind, const bf16_t* A, int lda, const Linear& l, const bf16_t* R, int ldr, void* C, int ldc, int M,
                  int act, int out_f32, hipStream_t st, int seq_rows = 0, int last_rows = 0, int tune_in_place = 0) {
-    TailMarkCtx tc{e};
-    prof_mark(e, kind, st);
-    GemmArgs g;
-    if (e->prof_on) { g.tail_mark = tail_mark_cb; g.tail_ctx = &tc; }
-    g.A = A; g.lda = lda; g.Wp = l.Wp; g.bias = l.bias; g.R = R; g.ldr = ldr; g.C = C; g.ldc = ldc;
-    g.M = M; g.N = l.N; g.K = l.Kpad; g.act = act; g.out_f32 = out_f32;
-    g.cscale = l.wfmt == SV_WFMT_FP8 ? l.wscale : nullptr;
+    GemmArgs g = gemm_args(e, kind, A, lda, l, R, ldr, C, ldc, M, act, st);
+    g.out_f32 = out_f32;
     g.seq_rows = (e->exp & SV_EXP_BATCH_REMAINDER) ? 0 : seq_rows;          // A/B: the batch-level remainder of rounds 2-5
     g.splitk_rows = (e->exp & SV_EXP_BATCH_REMAINDER) ? 0 : last_rows;
     g.tune_in_place = tune_in_place;
     launch_gemm(g, st);
 }
-
 // the same GEMM over packed rows of sequences of different lengths: `rows` (device, n_rows of them) take the split-K remainder kernel (launch_gemm_ragged)
 static void gemm_ragged(sv_engine* e, int kind, const bf16_t* A, int lda, const Linear& l, const bf16_t* R, int ldr, void* C, int ldc, int M,
                         int act, hipStream_t st, const int32_t* rows, int n_rows) {
-    TailMarkCtx tc{e};
-    prof_mark(e, kind, st);
-    GemmArgs g;
-    if (e->prof_on) { g.tail_mark = tail_mark_cb; g.tail_ctx = &tc; }
-    g.A = A; g.lda = lda; g.Wp = l.Wp; g.bias = l.bias; g.R = R; g.ldr = ldr; g.C = C; g.ldc = ldc;
-    g.M = M; g.N = l.N; g.K = l.Kpad; g.act = act; g.out_f32 = 0;
-    g.cscale = l.wfmt == SV_WFMT_FP8 ? l.wscale : nullptr;
-    launch_gemm_ragged(g, rows, n_rows, e->rag_rsave, st);
+    launch_gemm_ragged(gemm_args(e, kind, A, lda, l, R, ldr, C, ldc, M, act, st), rows, n_rows, e->rag_rsave, st);
 }
 
 // Context splits of the decode attention: a constant of the engine (sized for the engine's max_batch), NOT of the batch of the
@@ -268,6 +268,41 @@ static int score_logprob_chunks(sv_engine* e, const bf16_t* hn, size_t rows, con
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The prompt pass: two layer loops.  prefill_forward runs the rectangular pass over B x S0 rows with the launchers' arithmetic forms (seq_rows /
+// last_rows, launch_kv_write_prefill, at.S); prefill_forward_packed runs packed sequences of different lengths -- ragged or with shared prefixes --
+// from the lists of a PackedPlan.  What is identical in both is stated once, here.
+// ------------------------------------------------------------------------------------------------
+// the prompt-pass attention over the engine's fused q | k | v rows; the call site adds B / S or the ragged fields
+static AttnPrefillArgs attn_prefill_args(const sv_engine* e) {
+    const sv_config& c = e->cfg;
+    const int dh = e->dh, QKV = e->QKV, nkv = e->nkv, QD = c.n_head * dh;      // QD: width of the query block (= hidden for both model families)
+    AttnPrefillArgs at;
+    at.q = e->pqkv; at.k = e->pqkv + QD; at.v = e->pqkv + QD + nkv * dh;
+    at.q_row_stride = QKV; at.kv_row_stride = QKV; at.q_head_stride = dh; at.kv_head_stride = nkv > 1 ? dh : 0;
+    at.o = e->pattn; at.o_row_stride = QD; at.B = 0; at.S = 0; at.H = c.n_head; at.head_dim = dh;
+    at.kv_group = c.n_head / nkv; at.causal = 1; at.scale = 1.0f / sqrtf((float)dh);
+    at.window = c.sliding_window > 0 ? c.sliding_window : 0;      // StarCoder2: also inside the prompt pass (prompts longer than the window)
+    return at;
+}
+// only the last prompt row of every sequence feeds ln_f + lm_head (HF computes all rows; same result).  gathered: e->hl holds those rows already
+// (the pruned last layer); otherwise they come from the residual stream -- rows S0 - 1 of B sequences of S0 rows, or by rag_seq
+static void last_row_logits(sv_engine* e, int B, int S0, const int32_t* rag_seq, bool gathered, hipStream_t st) {
+    const int D = e->cfg.hidden;
+    prof_mark(e, PK_PF_ROWS, st);
+    if (!gathered) launch_gather_last_rows(e->ph, e->hl, B, S0, D, st, rag_seq);
+    launch_layernorm_rows_packed(e->hl, D, e->ln_f.g, e->ln_f.b, e->xp_f, B, D, e->cfg.ln_eps, st);
+    prof_mark(e, PK_PF_LMHEAD, st);
+    lm_head_logits(e, (B + 31) / 32, e->xp_f, st);
+}
+// the log-prob tail of every scoring pass: `rows` kept rows, gathered into the first half of score_ws, through ln_f and the chunked lm_head
+static int score_kept_rows(sv_engine* e, size_t rows, const ScoreLogprobs* lp, hipStream_t st) {
+    const int D = e->cfg.hidden;
+    bf16_t* hn = e->score_ws + rows * D;
+    launch_layernorm_rows(e->score_ws, D, e->ln_f.g, e->ln_f.b, hn, D, (int)rows, D, e->cfg.ln_eps, st);
+    return score_logprob_chunks(e, hn, rows, lp, st);
+}
+
 int sveng::prefill_forward(sv_engine* e, const bf16_t* embeds, int B, int S0, hipStream_t st, int n_keep,
                            bf16_t* dev_scores, const int32_t* table, const ScoreLogprobs* lp) {
     if (!table) table = e->block_table;           // continuous batching prefills NEW requests through a table of their slots' pages
@@ -281,12 +316,8 @@ int sveng::prefill_forward(sv_engine* e, const bf16_t* embeds, int B, int S0, hi
         HIPCHECK(hipMemcpyAsync(e->ph, embeds, (size_t)M * D * sizeof(bf16_t), hipMemcpyDeviceToDevice, st));
     else
         launch_dec_embed(embeds, e->wpe, e->ph, B, S0, D, st);
-    AttnPrefillArgs at;
-    at.q = e->pqkv; at.k = e->pqkv + QD; at.v = e->pqkv + QD + nkv * dh;
-    at.q_row_stride = QKV; at.kv_row_stride = QKV; at.q_head_stride = dh; at.kv_head_stride = nkv > 1 ? dh : 0;
-    at.o = e->pattn; at.o_row_stride = QD; at.B = B; at.S = S0; at.H = c.n_head; at.head_dim = dh;
-    at.kv_group = c.n_head / nkv; at.causal = 1; at.scale = 1.0f / sqrtf((float)dh);
-    at.window = c.sliding_window > 0 ? c.sliding_window : 0;      // StarCoder2: also inside the prompt pass (prompts longer than the window)
+    AttnPrefillArgs at = attn_prefill_args(e);
+    at.B = B; at.S = S0;
     // The LAST layer of a generation prompt pass (n_keep == 0) is only needed for (a) its K / V rows and (b) the residual stream of
     // the last prompt row, which alone feeds ln_f + lm_head.  So after its attention only the last row of every sequence goes on:
     // attention over the last query tile, then c_proj / ln_2 / c_fc / down-proj on B rows instead of B * S0 (HF computes all rows and
@@ -320,10 +351,7 @@ int sveng::prefill_forward(sv_engine* e, const bf16_t* embeds, int B, int S0, hi
             launch_layernorm_rows(e->hl, D, L.ln2.g, L.ln2.b, ln_l, D, B, D, c.ln_eps, st);
             gemm(e, PK_PF_GEMM, ln_l, D, L.c_fc, nullptr, 0, e->pmlp, F, B, ACT_GELU_TANH, 0, st, S0, 1);
             gemm(e, PK_PF_GEMM, e->pmlp, F, L.c_proj2, e->hl, D, e->hl, D, B, ACT_NONE, 0, st, S0, 1);
-            prof_mark(e, PK_PF_ROWS, st);
-            launch_layernorm_rows_packed(e->hl, D, e->ln_f.g, e->ln_f.b, e->xp_f, B, D, c.ln_eps, st);
-            prof_mark(e, PK_PF_LMHEAD, st);
-            lm_head_logits(e, (B + 31) / 32, e->xp_f, st);
+            last_row_logits(e, B, S0, nullptr, true, st);
             return 0;
         }
         launch_attn_prefill(at, st);
@@ -340,36 +368,32 @@ int sveng::prefill_forward(sv_engine* e, const bf16_t* embeds, int B, int S0, hi
         const size_t rows = (size_t)B * n_keep;
         SVCHECK(ensure_score_ws(e, rows, !lp));
         bf16_t* hk = e->score_ws;
-        bf16_t* hn = hk + rows * D;
-        bf16_t* lg = hn + rows * D;
         prof_mark(e, PK_PF_ROWS, st);
         launch_gather_tail_rows(e->ph, hk, B, S0, n_keep, D, st);
-        launch_layernorm_rows(hk, D, e->ln_f.g, e->ln_f.b, hn, D, (int)rows, D, c.ln_eps, st);
         if (lp) {
-            SVCHECK(score_logprob_chunks(e, hn, rows, lp, st));
+            SVCHECK(score_kept_rows(e, rows, lp, st));
         } else {
+            bf16_t* hn = hk + rows * D;
+            bf16_t* lg = hn + rows * D;
+            launch_layernorm_rows(hk, D, e->ln_f.g, e->ln_f.b, hn, D, (int)rows, D, c.ln_eps, st);
             gemm(e, PK_PF_GEMM, hn, D, e->lm_head, nullptr, 0, lg, e->Vpad, (int)rows, ACT_NONE, 0, st);
             HIPCHECK(hipMemcpy2DAsync(dev_scores, (size_t)c.vocab * sizeof(bf16_t), lg, (size_t)e->Vpad * sizeof(bf16_t),
                                       (size_t)c.vocab * sizeof(bf16_t), rows, hipMemcpyDeviceToDevice, st));
         }
     }
-    // only the last prompt row feeds ln_f + lm_head (HF computes all rows; same result)
-    prof_mark(e, PK_PF_ROWS, st);
-    launch_gather_last_rows(e->ph, e->hl, B, S0, D, st);
-    launch_layernorm_rows_packed(e->hl, D, e->ln_f.g, e->ln_f.b, e->xp_f, B, D, c.ln_eps, st);
-    prof_mark(e, PK_PF_LMHEAD, st);
-    lm_head_logits(e, (B + 31) / 32, e->xp_f, st);
+    last_row_logits(e, B, S0, nullptr, false, st);
     return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
-// The ragged prompt pass: B sequences of lengths lens[b], embeddings packed [sum(lens)][hidden], no padding row computed or stored.
-// Contract: for every sequence the last-row logits and every K / V entry are BIT-IDENTICAL to the sequence alone through prefill_forward
+// The packed prompt pass, ragged form: B sequences of lengths lens[b], embeddings packed [sum(lens)][hidden], no padding row computed or stored.
+// (The prefixed form and why its bits hold: prefix/prefix.hip.)  Contract: for every sequence the last-row logits and every K / V entry are BIT-IDENTICAL to the sequence alone through prefill_forward
 // with S0 = lens[b].  Per stage: LayerNorm is per row; the GEMMs send a row to the split-K remainder kernel exactly when its solo run
 // does (ragged_gemm_rows) and to an ascending-k kernel otherwise; the attention keeps query-tile and key-tile origins at the sequence's
 // first row (ragged_blocks); positions, pages and slots come from the row's own sequence.
 // ------------------------------------------------------------------------------------------------
-void sveng::ragged_gemm_rows(const int32_t* lens, int B, int N, int K, int act, std::vector<int32_t>& rows, std::vector<int32_t>& last) {
+// one projection's PL_ROWS pair
+static void ragged_gemm_rows(const int32_t* lens, int B, int N, int K, int act, std::vector<int32_t>& rows, std::vector<int32_t>& last) {
     rows.clear(); last.clear();
     int r0 = 0;
     for (int b = 0; b < B; ++b) {
@@ -439,206 +463,143 @@ void sveng::launch_ragged_positions(int32_t* positions, const int32_t* rag_seq, 
     ragged_positions_kernel<<<(n + 63) / 64, 64, 0, st>>>(positions, rag_seq, n, rep, delta);
 }
 
-// Scoring mode (keep + lp, sv_forward_logprobs_ragged): the counterpart of prefill_forward(..., n_keep, ..., lp).  The last layer runs on all packed
-// rows with the per-sequence remainder rows of the layers in front -- a solo scoring pass never prunes it either --, the last keep[b] rows of every
-// sequence are gathered into [sum(keep)][D] and go through ln_f and the chunked lm_head + logprob_rows (+ topk_rows) of the rectangular pass.
-int sveng::prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, const int32_t* lens, hipStream_t st, const int32_t* table,
-                                  const int32_t* keep, const ScoreLogprobs* lp) {
+void sveng::ragged_plan(const int32_t* lens, int B, int q_tile, const PlanProj* proj, int n_proj, const int32_t* keep, PackedPlan& out) {
+    out = PackedPlan();
+    out.B = B; out.tail = keep ? PackedPlan::SCORE_TAIL_ROWS : PackedPlan::GENERATE;
+    int r0 = 0;
+    for (int b = 0; b < B; ++b) {
+        const int32_t d[4] = {r0, lens[b], keep ? keep[b] : 0, out.kept};
+        out.list[PL_DESC].insert(out.list[PL_DESC].end(), d, d + 2);
+        if (keep) { out.list[PL_KEPT].insert(out.list[PL_KEPT].end(), d, d + 4); out.kept += keep[b]; }
+        r0 += lens[b];
+    }
+    out.M = out.src_rows[0] = r0;
+    ragged_blocks(lens, B, q_tile, false, out.list[PL_BLOCKS0]);
+    if (!keep) ragged_blocks(lens, B, q_tile, true, out.list[PL_LAST_TILES]);
+    ragged_blocks(lens, B, 32, false, out.list[PL_KV_BLOCKS]);
+    for (int i = 0; i < n_proj; ++i) ragged_gemm_rows(lens, B, proj[i].N, proj[i].K, proj[i].act, out.rows(i), out.last(i));
+}
+// the decoder's four projections as a plan builder asks for them (every layer has the same shapes); returns how many of them get per-sequence
+// remainder rows: none under SV_EXP_BATCH_REMAINDER (as in the rectangular pass: nothing to list and, with prefixes, nothing to refuse)
+static int plan_proj(const sv_engine* e, PlanProj pj[4]) {
+    const DecLayer& L = e->dec[0];
+    pj[0] = {L.c_attn.N, L.c_attn.Kpad, ACT_NONE}; pj[1] = {L.c_proj.N, L.c_proj.Kpad, ACT_NONE};
+    pj[2] = {L.c_fc.N, L.c_fc.Kpad, ACT_GELU_TANH}; pj[3] = {L.c_proj2.N, L.c_proj2.Kpad, ACT_NONE};
+    return (e->exp & SV_EXP_BATCH_REMAINDER) ? 0 : 4;
+}
+// every list of the plan, concatenated in list order into the pinned image, in one upload; off[i] = where list i begins in d_rag
+static int rag_upload_plan(sv_engine* e, const PackedPlan& p, size_t off[PL_COUNT], hipStream_t st) {
+    size_t need = 0;
+    for (int i = 0; i < PL_COUNT; ++i) { off[i] = need; need += p.list[i].size(); }
+    SVCHECK(rag_reserve_plan(e, need));
+    for (int i = 0; i < PL_COUNT; ++i)
+        if (!p.list[i].empty()) memcpy(e->h_rag + off[i], p.list[i].data(), p.list[i].size() * sizeof(int32_t));
+    HIPCHECK(hipMemcpyAsync(e->d_rag, e->h_rag, need * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipEventRecord(e->rag_ev, st));
+    e->rag_pending = true;
+    return 0;
+}
+
+// The packed pass over p.M rows.  A scoring tail (lp) runs the last layer on all packed rows with the per-sequence remainder rows of the layers in
+// front -- a solo scoring pass never prunes it either --, gathers the kept rows into [p.kept][D] and sends them through ln_f and the chunked lm_head +
+// logprob_rows (+ topk_rows) of the rectangular pass.  With prefixes the attention runs as two launches (the prefixes as ordinary ragged sequences,
+// then the prefixed form over the sequences' tiles from the straddling one on); the prefix rows' c_proj / MLP work in the last layer is not skipped.
+int sveng::prefill_forward_packed(sv_engine* e, const PackedPlan& p, const int32_t* table, const ScoreLogprobs* lp, hipStream_t st) {
     if (!table) table = e->block_table;
     const sv_config& c = e->cfg;
     const int D = c.hidden, dh = e->dh, F = c.n_inner, QKV = e->QKV, nkv = e->nkv;
-    const int QD = c.n_head * dh;
-    long long total = 0;
-    for (int b = 0; b < B; ++b) total += lens[b];
-    const int M = (int)total;
+    const int QD = c.n_head * dh, M = p.M, B = p.B;
     // (the pruned last layer keeps [B][QD] + [B][D] compact rows inside the LayerNorm workspace: at least 2 B rows)
     SVCHECK(ensure_prefill_ws(e, (size_t)std::max(M, 2 * B)));
     ++e->prompt_passes;
     if (!e->rag_rsave) SVCHECK(dalloc(e, &e->rag_rsave, (size_t)3 * c.max_batch * D));
     SVCHECK(rag_reserve_row_pos(e, (size_t)M));
-    // ---- the plan of this call: descriptors | attention blocks | last-tile blocks | KV-write blocks | remainder rows of the four projections |
-    // kept-row descriptors (scoring mode)
-    const int qt = attn_prefill_q_tile(c.n_head, nkv);
-    std::vector<int32_t> ab, al, kb, rows[4], last[4], kd;
-    int kept = 0;                                      // scoring mode: {first packed row, length, keep, first output row} per sequence
-    if (keep)
-        for (int b = 0, r0 = 0; b < B; ++b) {
-            const int32_t d[4] = {r0, lens[b], keep[b], kept};
-            kd.insert(kd.end(), d, d + 4);
-            r0 += lens[b]; kept += keep[b];
-        }
-    ragged_blocks(lens, B, qt, false, ab);
-    ragged_blocks(lens, B, qt, true, al);
-    ragged_blocks(lens, B, 32, false, kb);
-    const Linear* proj[4] = {&e->dec[0].c_attn, &e->dec[0].c_proj, &e->dec[0].c_fc, &e->dec[0].c_proj2};
-    const int acts[4] = {ACT_NONE, ACT_NONE, ACT_GELU_TANH, ACT_NONE};
-    if (!(e->exp & SV_EXP_BATCH_REMAINDER))            // set: no per-sequence remainder (as in the rectangular pass)
-        for (int i = 0; i < 4; ++i) ragged_gemm_rows(lens, B, proj[i]->N, proj[i]->Kpad, acts[i], rows[i], last[i]);
-    size_t need = (size_t)2 * B + ab.size() + al.size() + kb.size() + kd.size();
-    for (int i = 0; i < 4; ++i) need += rows[i].size() + last[i].size();
-    SVCHECK(rag_reserve_plan(e, need));
-    size_t off = 0;
-    auto put = [&](const std::vector<int32_t>& v) { const size_t o = off; if (!v.empty()) memcpy(e->h_rag + off, v.data(), v.size() * sizeof(int32_t)); off += v.size(); return o; };
-    {
-        int r0 = 0;
-        for (int b = 0; b < B; ++b) { e->h_rag[2 * b] = r0; e->h_rag[2 * b + 1] = lens[b]; r0 += lens[b]; }
-        off = (size_t)2 * B;
-    }
-    const int32_t* d_seq = e->d_rag;
-    const int32_t* d_ab = e->d_rag + put(ab);
-    const int32_t* d_al = e->d_rag + put(al);
-    const int32_t* d_kb = e->d_rag + put(kb);
-    const int32_t *d_rows[4], *d_last[4];
-    for (int i = 0; i < 4; ++i) { d_rows[i] = e->d_rag + put(rows[i]); d_last[i] = e->d_rag + put(last[i]); }
-    const int32_t* d_keep = e->d_rag + put(kd);
-    HIPCHECK(hipMemcpyAsync(e->d_rag, e->h_rag, off * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipEventRecord(e->rag_ev, st));
-    e->rag_pending = true;
+    size_t off[PL_COUNT];
+    SVCHECK(rag_upload_plan(e, p, off, st));
+    const auto dev = [&](int i) -> const int32_t* { return e->d_rag + off[i]; };
+    const auto len = [&](int i) { return (int)p.list[i].size(); };
+    const int32_t* d_desc = dev(PL_DESC);
 
     prof_mark(e, PK_PF_ROWS, st);
-    if (e->v2) {
-        HIPCHECK(hipMemcpyAsync(e->ph, embeds, (size_t)M * D * sizeof(bf16_t), hipMemcpyDeviceToDevice, st));
-        launch_ragged_row_pos(d_seq, B, e->rag_row_pos, st);                  // rotary positions
-    } else {
-        launch_ragged_row_pos(d_seq, B, e->rag_row_pos, st);                  // learned positions restart at 0 in every sequence
-        launch_dec_embed(embeds, e->wpe, e->ph, 1, M, D, st, e->rag_row_pos);
+    // a row's position is its index in its solo sequence: learned positions (v1) and RoPE (v2).  (Every form keeps the launch order it has always
+    // had: the ragged v2 pass copies its rows first.)
+    const auto row_pos = [&] {
+        if (p.n_seg > 0) launch_prefix_row_pos(d_desc, p.n_seg, e->rag_row_pos, st);
+        else launch_ragged_row_pos(d_desc, B, e->rag_row_pos, st);
+    };
+    const bool pos_first = !e->v2 || p.n_seg > 0;
+    if (pos_first) row_pos();
+    for (int s = 0, r = 0; s < 2 && p.src_rows[s] > 0; r += p.src_rows[s++]) {
+        if (e->v2)      // StarCoder2: no learned positions (rotary), hidden = inputs_embeds
+            HIPCHECK(hipMemcpyAsync(e->ph + (size_t)r * D, p.src[s], (size_t)p.src_rows[s] * D * sizeof(bf16_t), hipMemcpyDeviceToDevice, st));
+        else
+            launch_dec_embed(p.src[s], e->wpe, e->ph + (size_t)r * D, 1, p.src_rows[s], D, st, e->rag_row_pos + r);
     }
-    AttnPrefillArgs at;
-    at.q = e->pqkv; at.k = e->pqkv + QD; at.v = e->pqkv + QD + nkv * dh;
-    at.q_row_stride = QKV; at.kv_row_stride = QKV; at.q_head_stride = dh; at.kv_head_stride = nkv > 1 ? dh : 0;
-    at.o = e->pattn; at.o_row_stride = QD; at.B = B; at.S = 0; at.H = c.n_head; at.head_dim = dh;
-    at.kv_group = c.n_head / nkv; at.causal = 1; at.scale = 1.0f / sqrtf((float)dh);
-    at.window = c.sliding_window > 0 ? c.sliding_window : 0;
-    at.rag_seq = d_seq;
-    const bool prune_last = !keep && !(e->exp & SV_EXP_NO_PRUNE_LAST);
+    if (!pos_first) row_pos();
+    AttnPrefillArgs at = attn_prefill_args(e);
+    at.B = B;
+    const bool prune_last = p.tail == PackedPlan::GENERATE && !(e->exp & SV_EXP_NO_PRUNE_LAST);
     for (int i = 0; i < c.n_layer; ++i) {
         DecLayer& L = e->dec[i];
         prof_mark(e, PK_PF_ROWS, st);
         launch_layernorm_rows(e->ph, D, L.ln1.g, L.ln1.b, e->pln, D, M, D, c.ln_eps, st);
-        gemm_ragged(e, PK_PF_GEMM, e->pln, D, L.c_attn, nullptr, 0, e->pqkv, QKV, M, ACT_NONE, st, d_rows[0], (int)rows[0].size());
+        gemm_ragged(e, PK_PF_GEMM, e->pln, D, L.c_attn, nullptr, 0, e->pqkv, QKV, M, ACT_NONE, st, dev(pl_rows(0)), len(pl_rows(0)));
         prof_mark(e, PK_PF_ATTN, st);
         if (e->v2) launch_rope_prefill(e->pqkv, QKV, M, M, c.n_head + nkv, dh, e->rope_cos, e->rope_sin, st, e->rag_row_pos);
-        for (int kh = 0; kh < nkv; ++kh)
+        for (int kh = 0; kh < (len(PL_KV_BLOCKS) > 0 ? nkv : 0); ++kh)      // (no blocks: the pass writes no page)
             launch_kv_write_prefill_ragged(e->pqkv, QKV, QD + kh * dh, QD + nkv * dh + kh * dh,
                                            e->kv_pool + (size_t)i * e->layer_stride + (size_t)kh * e->kv_head_stride,
-                                           table, e->pages_per_seq, d_seq, d_kb, (int)kb.size() / 2, dh, st);
+                                           table, e->pages_per_seq, d_desc, dev(PL_KV_BLOCKS), len(PL_KV_BLOCKS) / 2, dh, st);
         if (prune_last && i + 1 == c.n_layer) {
             // only the last row of every sequence goes on (see prefill_forward): its query tile, then B compact rows
-            at.rag_blocks = d_al; at.rag_nblocks = (int)al.size() / 2;
+            at.rag_seq = d_desc; at.rag_blocks = dev(PL_LAST_TILES); at.rag_nblocks = len(PL_LAST_TILES) / 2;
             launch_attn_prefill(at, st);
             bf16_t* pa_l = e->pln;
             bf16_t* ln_l = e->pln + (size_t)B * QD;
             prof_mark(e, PK_PF_ROWS, st);
-            launch_gather_last_rows(e->pattn, pa_l, B, 0, QD, st, d_seq);
-            launch_gather_last_rows(e->ph, e->hl, B, 0, D, st, d_seq);
-            gemm_ragged(e, PK_PF_GEMM, pa_l, QD, L.c_proj, e->hl, D, e->hl, D, B, ACT_NONE, st, d_last[1], (int)last[1].size());
+            launch_gather_last_rows(e->pattn, pa_l, B, 0, QD, st, d_desc);
+            launch_gather_last_rows(e->ph, e->hl, B, 0, D, st, d_desc);
+            gemm_ragged(e, PK_PF_GEMM, pa_l, QD, L.c_proj, e->hl, D, e->hl, D, B, ACT_NONE, st, dev(pl_last(1)), len(pl_last(1)));
             prof_mark(e, PK_PF_ROWS, st);
             launch_layernorm_rows(e->hl, D, L.ln2.g, L.ln2.b, ln_l, D, B, D, c.ln_eps, st);
-            gemm_ragged(e, PK_PF_GEMM, ln_l, D, L.c_fc, nullptr, 0, e->pmlp, F, B, ACT_GELU_TANH, st, d_last[2], (int)last[2].size());
-            gemm_ragged(e, PK_PF_GEMM, e->pmlp, F, L.c_proj2, e->hl, D, e->hl, D, B, ACT_NONE, st, d_last[3], (int)last[3].size());
-            prof_mark(e, PK_PF_ROWS, st);
-            launch_layernorm_rows_packed(e->hl, D, e->ln_f.g, e->ln_f.b, e->xp_f, B, D, c.ln_eps, st);
-            prof_mark(e, PK_PF_LMHEAD, st);
-            lm_head_logits(e, (B + 31) / 32, e->xp_f, st);
+            gemm_ragged(e, PK_PF_GEMM, ln_l, D, L.c_fc, nullptr, 0, e->pmlp, F, B, ACT_GELU_TANH, st, dev(pl_last(2)), len(pl_last(2)));
+            gemm_ragged(e, PK_PF_GEMM, e->pmlp, F, L.c_proj2, e->hl, D, e->hl, D, B, ACT_NONE, st, dev(pl_last(3)), len(pl_last(3)));
+            last_row_logits(e, B, 0, d_desc, true, st);
             return 0;
         }
-        at.rag_blocks = d_ab; at.rag_nblocks = (int)ab.size() / 2;
-        launch_attn_prefill(at, st);
-        gemm_ragged(e, PK_PF_GEMM, e->pattn, QD, L.c_proj, e->ph, D, e->ph, D, M, ACT_NONE, st, d_rows[1], (int)rows[1].size());
+        for (int j = 0; j < p.n_attn; ++j) {
+            const int seq = PL_SEQ0 + 2 * j, blocks = PL_BLOCKS0 + 2 * j;
+            at.rag_prefixed = j; at.rag_seq = len(seq) > 0 ? dev(seq) : d_desc; at.rag_blocks = dev(blocks); at.rag_nblocks = len(blocks) / 2;
+            launch_attn_prefill(at, st);
+        }
+        gemm_ragged(e, PK_PF_GEMM, e->pattn, QD, L.c_proj, e->ph, D, e->ph, D, M, ACT_NONE, st, dev(pl_rows(1)), len(pl_rows(1)));
         prof_mark(e, PK_PF_ROWS, st);
         launch_layernorm_rows(e->ph, D, L.ln2.g, L.ln2.b, e->pln, D, M, D, c.ln_eps, st);
-        gemm_ragged(e, PK_PF_GEMM, e->pln, D, L.c_fc, nullptr, 0, e->pmlp, F, M, ACT_GELU_TANH, st, d_rows[2], (int)rows[2].size());
-        gemm_ragged(e, PK_PF_GEMM, e->pmlp, F, L.c_proj2, e->ph, D, e->ph, D, M, ACT_NONE, st, d_rows[3], (int)rows[3].size());
+        gemm_ragged(e, PK_PF_GEMM, e->pln, D, L.c_fc, nullptr, 0, e->pmlp, F, M, ACT_GELU_TANH, st, dev(pl_rows(2)), len(pl_rows(2)));
+        gemm_ragged(e, PK_PF_GEMM, e->pmlp, F, L.c_proj2, e->ph, D, e->ph, D, M, ACT_NONE, st, dev(pl_rows(3)), len(pl_rows(3)));
     }
-    if (keep) {
-        SVCHECK(ensure_score_ws(e, (size_t)kept, false));
-        bf16_t* hk = e->score_ws;
-        bf16_t* hn = hk + (size_t)kept * D;
+    if (p.tail != PackedPlan::GENERATE) {
+        SVCHECK(ensure_score_ws(e, (size_t)p.kept, false));
         prof_mark(e, PK_PF_ROWS, st);
-        launch_gather_tail_rows(e->ph, hk, B, 0, 0, D, st, d_keep, kept);
-        launch_layernorm_rows(hk, D, e->ln_f.g, e->ln_f.b, hn, D, kept, D, c.ln_eps, st);
-        SVCHECK(score_logprob_chunks(e, hn, (size_t)kept, lp, st));
+        if (p.tail == PackedPlan::SCORE_TAIL_ROWS)
+            launch_gather_tail_rows(e->ph, e->score_ws, B, 0, 0, D, st, dev(PL_KEPT), p.kept);
+        else      // (keep = len + 1: the prefix's last row, then the own rows -- not contiguous)
+            launch_gather_listed_rows(e->ph, D, dev(PL_KEPT), p.kept, e->score_ws, D, st);
+        SVCHECK(score_kept_rows(e, (size_t)p.kept, lp, st));
+        if (p.tail == PackedPlan::SCORE_LISTED_ROWS) return 0;
     }
-    prof_mark(e, PK_PF_ROWS, st);
-    launch_gather_last_rows(e->ph, e->hl, B, 0, D, st, d_seq);
-    launch_layernorm_rows_packed(e->hl, D, e->ln_f.g, e->ln_f.b, e->xp_f, B, D, c.ln_eps, st);
-    prof_mark(e, PK_PF_LMHEAD, st);
-    lm_head_logits(e, (B + 31) / 32, e->xp_f, st);
+    last_row_logits(e, B, 0, d_desc, false, st);
     return 0;
 }
 
-// The shared-prefix scoring pass (sv_forward_logprobs_prefixed; the plan and why the bits hold: prefix/prefix.hip).  prefill_forward_ragged's scoring
-// mode over plan.M packed rows -- the prefixes, then every sequence's own rows -- with two differences: the attention runs as two launches (the
-// prefixes as ordinary ragged sequences, then the prefixed form over the sequences' tiles from the straddling one on), and no K / V page is written.
-// The last layer runs on all packed rows (the prefix rows' c_proj / MLP work there is not skipped).
-static int prefill_forward_prefixed(sv_engine* e, const bf16_t* prefixes, const bf16_t* own, int P, int B, const PrefixPlan& plan,
-                                    const int32_t* keep, const ScoreLogprobs* lp, hipStream_t st) {
-    const sv_config& c = e->cfg;
-    const int D = c.hidden, dh = e->dh, F = c.n_inner, QKV = e->QKV, nkv = e->nkv;
-    const int QD = c.n_head * dh, M = plan.M, MP = plan.MP;
-    SVCHECK(ensure_prefill_ws(e, (size_t)M));
-    ++e->prompt_passes;
-    if (!e->rag_rsave) SVCHECK(dalloc(e, &e->rag_rsave, (size_t)3 * c.max_batch * D));
-    SVCHECK(rag_reserve_row_pos(e, (size_t)M));
-    std::vector<int32_t> kr;
-    prefix_kept_rows(plan, B, keep, kr);
-    const int kept = (int)kr.size();
-    size_t need = plan.seg.size() + plan.pseq.size() + plan.pblocks.size() + plan.sseq.size() + plan.sblocks.size() + kr.size();
-    for (int i = 0; i < 4; ++i) need += plan.rows[i].size();
-    SVCHECK(rag_reserve_plan(e, need));
-    size_t off = 0;
-    auto put = [&](const std::vector<int32_t>& v) { const size_t o = off; if (!v.empty()) memcpy(e->h_rag + off, v.data(), v.size() * sizeof(int32_t)); off += v.size(); return o; };
-    const int32_t* d_seg = e->d_rag + put(plan.seg);
-    const int32_t* d_pseq = e->d_rag + put(plan.pseq);
-    const int32_t* d_pblocks = e->d_rag + put(plan.pblocks);
-    const int32_t* d_sseq = e->d_rag + put(plan.sseq);
-    const int32_t* d_sblocks = e->d_rag + put(plan.sblocks);
-    const int32_t* d_rows[4];
-    for (int i = 0; i < 4; ++i) d_rows[i] = e->d_rag + put(plan.rows[i]);
-    const int32_t* d_kr = e->d_rag + put(kr);
-    HIPCHECK(hipMemcpyAsync(e->d_rag, e->h_rag, off * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipEventRecord(e->rag_ev, st));
-    e->rag_pending = true;
-
-    prof_mark(e, PK_PF_ROWS, st);
-    launch_prefix_row_pos(d_seg, P + B, e->rag_row_pos, st);                // solo indices: wpe (v1) and RoPE (v2)
-    if (e->v2) {
-        HIPCHECK(hipMemcpyAsync(e->ph, prefixes, (size_t)MP * D * sizeof(bf16_t), hipMemcpyDeviceToDevice, st));
-        HIPCHECK(hipMemcpyAsync(e->ph + (size_t)MP * D, own, (size_t)(M - MP) * D * sizeof(bf16_t), hipMemcpyDeviceToDevice, st));
-    } else {
-        launch_dec_embed(prefixes, e->wpe, e->ph, 1, MP, D, st, e->rag_row_pos);
-        launch_dec_embed(own, e->wpe, e->ph + (size_t)MP * D, 1, M - MP, D, st, e->rag_row_pos + MP);
-    }
-    AttnPrefillArgs at;
-    at.q = e->pqkv; at.k = e->pqkv + QD; at.v = e->pqkv + QD + nkv * dh;
-    at.q_row_stride = QKV; at.kv_row_stride = QKV; at.q_head_stride = dh; at.kv_head_stride = nkv > 1 ? dh : 0;
-    at.o = e->pattn; at.o_row_stride = QD; at.B = B; at.S = 0; at.H = c.n_head; at.head_dim = dh;
-    at.kv_group = c.n_head / nkv; at.causal = 1; at.scale = 1.0f / sqrtf((float)dh);
-    at.window = c.sliding_window > 0 ? c.sliding_window : 0;
-    for (int i = 0; i < c.n_layer; ++i) {
-        DecLayer& L = e->dec[i];
-        prof_mark(e, PK_PF_ROWS, st);
-        launch_layernorm_rows(e->ph, D, L.ln1.g, L.ln1.b, e->pln, D, M, D, c.ln_eps, st);
-        gemm_ragged(e, PK_PF_GEMM, e->pln, D, L.c_attn, nullptr, 0, e->pqkv, QKV, M, ACT_NONE, st, d_rows[0], (int)plan.rows[0].size());
-        prof_mark(e, PK_PF_ATTN, st);
-        if (e->v2) launch_rope_prefill(e->pqkv, QKV, M, M, c.n_head + nkv, dh, e->rope_cos, e->rope_sin, st, e->rag_row_pos);
-        at.rag_prefixed = 0; at.rag_seq = d_pseq; at.rag_blocks = d_pblocks; at.rag_nblocks = (int)plan.pblocks.size() / 2;
-        launch_attn_prefill(at, st);
-        at.rag_prefixed = 1; at.rag_seq = d_sseq; at.rag_blocks = d_sblocks; at.rag_nblocks = (int)plan.sblocks.size() / 2;
-        launch_attn_prefill(at, st);
-        gemm_ragged(e, PK_PF_GEMM, e->pattn, QD, L.c_proj, e->ph, D, e->ph, D, M, ACT_NONE, st, d_rows[1], (int)plan.rows[1].size());
-        prof_mark(e, PK_PF_ROWS, st);
-        launch_layernorm_rows(e->ph, D, L.ln2.g, L.ln2.b, e->pln, D, M, D, c.ln_eps, st);
-        gemm_ragged(e, PK_PF_GEMM, e->pln, D, L.c_fc, nullptr, 0, e->pmlp, F, M, ACT_GELU_TANH, st, d_rows[2], (int)plan.rows[2].size());
-        gemm_ragged(e, PK_PF_GEMM, e->pmlp, F, L.c_proj2, e->ph, D, e->ph, D, M, ACT_NONE, st, d_rows[3], (int)plan.rows[3].size());
-    }
-    SVCHECK(ensure_score_ws(e, (size_t)kept, false));
-    bf16_t* hk = e->score_ws;
-    bf16_t* hn = hk + (size_t)kept * D;
-    prof_mark(e, PK_PF_ROWS, st);
-    launch_gather_listed_rows(e->ph, D, d_kr, kept, hk, D, st);           // (keep = len + 1: the prefix's last row, then the own rows -- not contiguous)
-    launch_layernorm_rows(hk, D, e->ln_f.g, e->ln_f.b, hn, D, kept, D, c.ln_eps, st);
-    return score_logprob_chunks(e, hn, (size_t)kept, lp, st);
+int sveng::prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, const int32_t* lens, hipStream_t st, const int32_t* table,
+                                  const int32_t* keep, const ScoreLogprobs* lp) {
+    PlanProj pj[4];
+    const int n_proj = plan_proj(e, pj);
+    PackedPlan p;
+    ragged_plan(lens, B, attn_prefill_q_tile(e->cfg.n_head, e->nkv), pj, n_proj, keep, p);
+    p.src[0] = embeds;
+    return prefill_forward_packed(e, p, table, lp, st);
 }
 
 // Arguments of the decode attention of layer `layer` over the engine's KV pool / block table / positions: the c_attn output
@@ -961,82 +922,35 @@ extern "C" int sv_prefill_ragged(sv_engine* e, const void* dev_embeds_packed, in
     return 0;
 }
 
-// the packed kept row a scoring kernel flagged -> (sequence, kept position): n_keep rows per sequence, or the prefix sums of keep
-static void score_row_owner(int row, int B, int n_keep, const int32_t* keep, int* seq, int* pos) {
-    int b = 0, first = 0;
-    if (!keep) { b = row / n_keep; first = b * n_keep; }
-    else while (b + 1 < B && first + keep[b] <= row) first += keep[b++];
-    *seq = b; *pos = row - first;
-}
-static int score_flag_report(sv_engine* e, const char* who, int B, int n_keep, const int32_t* keep, hipStream_t st);
-// One scoring-mode prompt pass under the engine lock: pages for exactly the rows given, the pass, positions = the lengths, and -- with lp -- the
-// kernels' flag.  lens == nullptr: B sequences of S rows, the last n_keep kept (into dev_scores or lp); otherwise the ragged pass over (lens, keep).
-static int score_pass(sv_engine* e, const char* who, const void* embeds, int B, int S, int n_keep, const int32_t* lens, const int32_t* keep,
-                      bf16_t* dev_scores, const ScoreLogprobs* lp, hipStream_t st) {
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIPCHECK(hipSetDevice(e->cfg.device));
-    SVCHECK(cb_guard(e, who));
-    if (lens) {
-        SVCHECK(assign_pages_ragged(e, B, lens, 0, st));
-        SVCHECK(prefill_forward_ragged(e, (const bf16_t*)embeds, B, lens, st, nullptr, keep, lp));
-        ragged_positions(e, B, 1, 0, st);
-    } else {
-        SVCHECK(assign_pages(e, B, S, st));
-        SVCHECK(prefill_forward(e, (const bf16_t*)embeds, B, S, st, n_keep, dev_scores, nullptr, lp));
-        fill_i32(e->positions, S, B, st);
-    }
-    e->cached_B = B;
-    HIPCHECK(hipGetLastError());
-    if (!lp) return 0;
-    return score_flag_report(e, who, B, n_keep, lens ? keep : nullptr, st);
-}
-// the scoring kernels' flag: a target outside the vocabulary (its logprob is NaN) / a row without a finite logit (all of its outputs are NaN)
-static int score_flag_report(sv_engine* e, const char* who, int B, int n_keep, const int32_t* keep, hipStream_t st) {
-    int32_t flag[2] = {0, 0};
-    HIPCHECK(hipMemcpyAsync(flag, e->score_chunk_ws + (size_t)e->score_chunk_alloc * e->Vpad, sizeof(flag), hipMemcpyDeviceToHost, st));
-    HIPCHECK(hipStreamSynchronize(st));
-    if (!(flag[0] & 3)) return 0;
-    int seq = 0, pos = 0;
-    score_row_owner(flag[1], B, n_keep, keep, &seq, &pos);
-    if (flag[0] & 2)
-        return fail(SV_EHIP, "%s: a row of logits had no finite value (NaN / Inf in the weights or inputs?); first at row %d "
-                             "(sequence %d, kept position %d)", who, flag[1], seq, pos);
-    return fail(SV_EINVAL, "%s: a target id outside [0, %d) that is not -100; first at row %d (sequence %d, kept position %d)",
-                who, e->cfg.vocab, flag[1], seq, pos);
-}
-
-extern "C" int sv_forward_logits(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S, int32_t n_keep,
-                                 void* dev_logits_bf16, sv_stream stream) {
-    SVCHECK(check_ready(e));
-    if (!dev_embeds || !dev_logits_bf16) return fail(SV_EINVAL, "sv_forward_logits: null argument");
-    if (B < 1 || B > e->cfg.max_batch) return fail(SV_EINVAL, "sv_forward_logits: bad B=%d (max_batch %d)", B, e->cfg.max_batch);
-    if (S < 1 || S > e->cfg.max_seq_len) return fail(SV_EINVAL, "sv_forward_logits: S=%d out of range (max_seq_len %d)", S, e->cfg.max_seq_len);
-    if (n_keep < 1 || n_keep > S) return fail(SV_EINVAL, "sv_forward_logits: n_keep=%d must be in 1..S", n_keep);
-    return score_pass(e, "sv_forward_logits", dev_embeds, B, S, n_keep, nullptr, nullptr, (bf16_t*)dev_logits_bf16, nullptr, (hipStream_t)stream);
-}
-
-// A scoring call with a ScoreLogprobs, as sv_forward_logprobs / sv_forward_topk (B sequences of S rows, the last n_keep kept) or
-// sv_forward_logprobs_ragged (lens, keep) describes it
+// A scoring call, as sv_forward_logits / sv_forward_logprobs / sv_forward_topk (B sequences of S rows, the last n_keep kept), sv_forward_logprobs_ragged
+// (lens, keep) or sv_forward_logprobs_prefixed (P prefixes in front of lens, prefix_of, keep) describes it
 struct ScoreCall {
     const char* who;
-    bool ragged;
+    enum Form { RECT, RAGGED, PREFIXED } form;
     const void* embeds;
     int32_t B, S, n_keep;
     const int32_t *lens, *keep;
     float temperature;
     ScoreLogprobs lp;
+    const void* prefixes = nullptr;
+    int32_t P = 0;
+    const int32_t *prefix_lens = nullptr, *prefix_of = nullptr;
 };
-// The checks that need no engine (they come first: they are the same on a machine without a GPU).  Every check is stated once; the two forms
-// have always asked in different orders, and which of two violations is reported is part of each one's contract.
+// The checks of a call with a ScoreLogprobs that need no engine (they come first: they are the same on a machine without a GPU).  Every check is
+// stated once; the rectangular and the packed forms have always asked in different orders, and which of two violations is reported is part of each
+// one's contract.
 static int check_score_call(const ScoreCall& c) {
     const char* who = c.who;
     const auto nulls = [&]() -> int {
-        if (c.ragged && (!c.embeds || !c.lens || !c.keep || !c.lp.targets)) return fail(SV_EINVAL, "%s: null embeds / lengths / keep / targets pointer", who);
+        if (c.form == ScoreCall::PREFIXED && (!c.prefixes || !c.prefix_lens || !c.embeds || !c.lens || !c.prefix_of || !c.keep || !c.lp.targets))
+            return fail(SV_EINVAL, "%s: null prefixes / embeds / lengths / prefix_of / keep / targets pointer", who);
+        if (c.form == ScoreCall::RAGGED && (!c.embeds || !c.lens || !c.keep || !c.lp.targets)) return fail(SV_EINVAL, "%s: null embeds / lengths / keep / targets pointer", who);
         if (!c.embeds || !c.lp.targets) return fail(SV_EINVAL, "%s: null embeds / targets", who);
         return 0;
     };
     const auto shape = [&]() -> int {
-        if (!c.ragged) return (c.S < 1 || c.n_keep < 1 || c.n_keep > c.S) ? fail(SV_EINVAL, "%s: n_keep=%d must be in 1..S (S=%d)", who, c.n_keep, c.S) : 0;
+        if (c.form == ScoreCall::RECT) return (c.S < 1 || c.n_keep < 1 || c.n_keep > c.S) ? fail(SV_EINVAL, "%s: n_keep=%d must be in 1..S (S=%d)", who, c.n_keep, c.S) : 0;
+        if (c.form == ScoreCall::PREFIXED) return prefix_check(who, c.prefix_lens, c.P, c.lens, c.prefix_of, c.B, c.keep);
         if (c.B < 1) return fail(SV_EINVAL, "%s: bad B=%d", who, c.B);
         for (int b = 0; b < c.B; ++b) {
             if (c.lens[b] < 1) return fail(SV_EINVAL, "%s: length %d of sequence %d (must be >= 1)", who, c.lens[b], b);
@@ -1057,30 +971,115 @@ static int check_score_call(const ScoreCall& c) {
         if (c.lp.k == 0 && !c.lp.logprob && !c.lp.lse && !c.lp.entropy && !c.lp.argmax) return fail(SV_EINVAL, "%s: every output pointer is null", who);
         return 0;
     };
-    if (c.ragged) { SVCHECK(nulls()); SVCHECK(shape()); SVCHECK(temperature()); SVCHECK(lists()); return outputs(); }
+    if (c.form != ScoreCall::RECT) { SVCHECK(nulls()); SVCHECK(shape()); SVCHECK(temperature()); SVCHECK(lists()); return outputs(); }
     SVCHECK(lists()); SVCHECK(nulls()); SVCHECK(outputs()); SVCHECK(temperature()); return shape();
+}
+
+// the packed kept row a scoring kernel flagged -> (sequence, kept position): n_keep rows per sequence, or the prefix sums of keep
+static void score_row_owner(int row, int B, int n_keep, const int32_t* keep, int* seq, int* pos) {
+    int b = 0, first = 0;
+    if (!keep) { b = row / n_keep; first = b * n_keep; }
+    else while (b + 1 < B && first + keep[b] <= row) first += keep[b++];
+    *seq = b; *pos = row - first;
+}
+// the scoring kernels' flag: a target outside the vocabulary (its logprob is NaN) / a row without a finite logit (all of its outputs are NaN)
+static int score_flag_report(sv_engine* e, const char* who, int B, int n_keep, const int32_t* keep, hipStream_t st) {
+    int32_t flag[2] = {0, 0};
+    HIPCHECK(hipMemcpyAsync(flag, e->score_chunk_ws + (size_t)e->score_chunk_alloc * e->Vpad, sizeof(flag), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    if (!(flag[0] & 3)) return 0;
+    int seq = 0, pos = 0;
+    score_row_owner(flag[1], B, n_keep, keep, &seq, &pos);
+    if (flag[0] & 2)
+        return fail(SV_EHIP, "%s: a row of logits had no finite value (NaN / Inf in the weights or inputs?); first at row %d "
+                             "(sequence %d, kept position %d)", who, flag[1], seq, pos);
+    return fail(SV_EINVAL, "%s: a target id outside [0, %d) that is not -100; first at row %d (sequence %d, kept position %d)",
+                who, e->cfg.vocab, flag[1], seq, pos);
+}
+// One scoring-mode prompt pass under the engine lock, and -- unless the logits go to dev_scores -- the kernels' flag.  The rectangular and the ragged
+// form assign pages for exactly the rows given and leave positions = the lengths.  The prefixed form (`prefixed`: its plan) assigns no page and writes
+// none: whatever the cache held is void for sv_decode_step from here on (cached_B = 0: SV_ESTATE).
+static int score_pass(sv_engine* e, const ScoreCall& c, bf16_t* dev_scores, const PackedPlan* prefixed, hipStream_t st) {
+    const ScoreLogprobs* lp = dev_scores ? nullptr : &c.lp;
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIPCHECK(hipSetDevice(e->cfg.device));
+    SVCHECK(cb_guard(e, c.who));
+    if (c.form == ScoreCall::PREFIXED) {
+        e->cached_B = 0;
+        SVCHECK(prefill_forward_packed(e, *prefixed, nullptr, lp, st));
+    } else if (c.form == ScoreCall::RAGGED) {
+        SVCHECK(assign_pages_ragged(e, c.B, c.lens, 0, st));
+        SVCHECK(prefill_forward_ragged(e, (const bf16_t*)c.embeds, c.B, c.lens, st, nullptr, c.keep, lp));
+        ragged_positions(e, c.B, 1, 0, st);
+        e->cached_B = c.B;
+    } else {
+        SVCHECK(assign_pages(e, c.B, c.S, st));
+        SVCHECK(prefill_forward(e, (const bf16_t*)c.embeds, c.B, c.S, st, c.n_keep, dev_scores, nullptr, lp));
+        fill_i32(e->positions, c.S, c.B, st);
+        e->cached_B = c.B;
+    }
+    HIPCHECK(hipGetLastError());
+    if (!lp) return 0;
+    return score_flag_report(e, c.who, c.B, c.n_keep, c.form == ScoreCall::RECT ? nullptr : c.keep, st);
+}
+
+extern "C" int sv_forward_logits(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S, int32_t n_keep,
+                                 void* dev_logits_bf16, sv_stream stream) {
+    SVCHECK(check_ready(e));
+    if (!dev_embeds || !dev_logits_bf16) return fail(SV_EINVAL, "sv_forward_logits: null argument");
+    if (B < 1 || B > e->cfg.max_batch) return fail(SV_EINVAL, "sv_forward_logits: bad B=%d (max_batch %d)", B, e->cfg.max_batch);
+    if (S < 1 || S > e->cfg.max_seq_len) return fail(SV_EINVAL, "sv_forward_logits: S=%d out of range (max_seq_len %d)", S, e->cfg.max_seq_len);
+    if (n_keep < 1 || n_keep > S) return fail(SV_EINVAL, "sv_forward_logits: n_keep=%d must be in 1..S", n_keep);
+    return score_pass(e, {"sv_forward_logits", ScoreCall::RECT, dev_embeds, B, S, n_keep, nullptr, nullptr, 0.f, {}}, (bf16_t*)dev_logits_bf16, nullptr,
+                      (hipStream_t)stream);
+}
+
+// The engine's side of a prefixed call: every solo sequence fits, and none is refused (prefix/prefix.hip).  Every weight format: the pass is the ragged
+// pass's launches -- fp8's column-scale epilogue and the bf16 image of an mxfp4 engine are per row and per column --, and
+// tests/test_gpu_prefix_scoring.py holds each format to the contract.
+static int prefixed_plan(sv_engine* e, const ScoreCall& c, PackedPlan& plan) {
+    for (int b = 0; b < c.B; ++b) {
+        const long long T = (long long)c.prefix_lens[c.prefix_of[b]] + c.lens[b];
+        if (T > e->cfg.max_seq_len)
+            return fail(SV_EINVAL, "%s: length %lld of sequence %d (prefix %d + own %d) out of range (1..max_seq_len %d)", c.who, T, b,
+                        c.prefix_lens[c.prefix_of[b]], c.lens[b], e->cfg.max_seq_len);
+    }
+    static const char* const proj_name[4] = {"c_attn", "attention c_proj", "c_fc", "MLP c_proj"};
+    PlanProj pj[4];
+    const int n_proj = plan_proj(e, pj);
+    prefix_plan(c.prefix_lens, c.P, c.lens, c.prefix_of, c.B, attn_prefill_q_tile(e->cfg.n_head, e->nkv), pj, n_proj, c.keep, plan);
+    if (plan.refused >= 0) {
+        const int b = plan.refused, pl = c.prefix_lens[c.prefix_of[b]];
+        return fail(SV_EINVAL, "%s: sequence %d (prefix %d + own %d rows): the %d remainder rows of its %d-row solo run at %s would reach into the "
+                    "shared prefix (score it alone: sv_forward_logprobs_ragged on the concatenation)", c.who, b, pl, c.lens[b],
+                    seq_peel_rows(pl + c.lens[b]), pl + c.lens[b], proj_name[plan.refused_proj]);
+    }
+    plan.src[0] = (const bf16_t*)c.prefixes; plan.src[1] = (const bf16_t*)c.embeds;
+    return 0;
 }
 static int score_call(sv_engine* e, ScoreCall c, sv_stream stream) {
     SVCHECK(check_score_call(c));
     SVCHECK(check_ready(e));
     if (c.B < 1 || c.B > e->cfg.max_batch) return fail(SV_EINVAL, "%s: bad B=%d (max_batch %d)", c.who, c.B, e->cfg.max_batch);
-    if (c.ragged) SVCHECK(ragged_check_lens(e, c.lens, c.B, c.who, nullptr, nullptr));
+    PackedPlan prefixed;
+    if (c.form == ScoreCall::PREFIXED) SVCHECK(prefixed_plan(e, c, prefixed));
+    else if (c.form == ScoreCall::RAGGED) SVCHECK(ragged_check_lens(e, c.lens, c.B, c.who, nullptr, nullptr));
     else if (c.S > e->cfg.max_seq_len) return fail(SV_EINVAL, "%s: S=%d out of range (max_seq_len %d)", c.who, c.S, e->cfg.max_seq_len);
     if (c.lp.k == 0) { c.lp.topk_ids = nullptr; c.lp.topk_logprobs = nullptr; c.lp.rank = nullptr; }
-    return score_pass(e, c.who, c.embeds, c.B, c.S, c.n_keep, c.ragged ? c.lens : nullptr, c.keep, nullptr, &c.lp, (hipStream_t)stream);
+    return score_pass(e, c, nullptr, &prefixed, (hipStream_t)stream);
 }
 
 extern "C" int sv_forward_logprobs(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S, int32_t n_keep,
                                    const int32_t* dev_targets, float temperature, float* dev_logprob, float* dev_logsumexp,
                                    float* dev_entropy, int32_t* dev_argmax, sv_stream stream) {
-    return score_call(e, {"sv_forward_logprobs", false, dev_embeds, B, S, n_keep, nullptr, nullptr, temperature,
+    return score_call(e, {"sv_forward_logprobs", ScoreCall::RECT, dev_embeds, B, S, n_keep, nullptr, nullptr, temperature,
                           {dev_targets, 1.0f / temperature, dev_logprob, dev_logsumexp, dev_entropy, dev_argmax}}, stream);
 }
 // k == 0 is sv_forward_logprobs, to the letter
 extern "C" int sv_forward_topk(sv_engine* e, const void* dev_embeds, int32_t B, int32_t S, int32_t n_keep, const int32_t* dev_targets,
                                float temperature, float* dev_logprob, float* dev_logsumexp, float* dev_entropy, int32_t* dev_argmax, int32_t k,
                                int32_t* dev_topk_ids, float* dev_topk_logprobs, int32_t* dev_rank, sv_stream stream) {
-    return score_call(e, {k == 0 ? "sv_forward_logprobs" : "sv_forward_topk", false, dev_embeds, B, S, n_keep, nullptr, nullptr, temperature,
+    return score_call(e, {k == 0 ? "sv_forward_logprobs" : "sv_forward_topk", ScoreCall::RECT, dev_embeds, B, S, n_keep, nullptr, nullptr, temperature,
                           {dev_targets, 1.0f / temperature, dev_logprob, dev_logsumexp, dev_entropy, dev_argmax, k, dev_topk_ids, dev_topk_logprobs, dev_rank}},
                       stream);
 }
@@ -1089,62 +1088,20 @@ extern "C" int sv_forward_logprobs_ragged(sv_engine* e, const void* dev_embeds_p
                                           const int32_t* dev_targets, float temperature, float* dev_logprob, float* dev_logsumexp, float* dev_entropy,
                                           int32_t* dev_argmax, int32_t k, int32_t* dev_topk_ids, float* dev_topk_logprobs, int32_t* dev_rank,
                                           sv_stream stream) {
-    return score_call(e, {"sv_forward_logprobs_ragged", true, dev_embeds_packed, B, 0, 0, host_lens, host_keep, temperature,
+    return score_call(e, {"sv_forward_logprobs_ragged", ScoreCall::RAGGED, dev_embeds_packed, B, 0, 0, host_lens, host_keep, temperature,
                           {dev_targets, 1.0f / temperature, dev_logprob, dev_logsumexp, dev_entropy, dev_argmax, k, dev_topk_ids, dev_topk_logprobs, dev_rank}},
                       stream);
 }
-
-// sv_forward_logprobs_ragged over sequences that share prefixes: every prefix goes through the decoder once (prefill_forward_prefixed)
+// sv_forward_logprobs_ragged over sequences that share prefixes: every prefix goes through the decoder once
 extern "C" int sv_forward_logprobs_prefixed(sv_engine* e, const void* dev_prefix_packed, int32_t P, const int32_t* host_prefix_lens,
                                             const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, const int32_t* host_prefix_of,
                                             const int32_t* host_keep, const int32_t* dev_targets, float temperature, float* dev_logprob,
                                             float* dev_logsumexp, float* dev_entropy, int32_t* dev_argmax, int32_t k, int32_t* dev_topk_ids,
                                             float* dev_topk_logprobs, int32_t* dev_rank, sv_stream stream) {
-    const char* who = "sv_forward_logprobs_prefixed";
-    // (the checks that need no engine come first: they are the same on a machine without a GPU)
-    if (!dev_prefix_packed || !host_prefix_lens || !dev_embeds_packed || !host_lens || !host_prefix_of || !host_keep || !dev_targets)
-        return fail(SV_EINVAL, "%s: null prefixes / embeds / lengths / prefix_of / keep / targets pointer", who);
-    SVCHECK(prefix_check(who, host_prefix_lens, P, host_lens, host_prefix_of, B, host_keep));
-    if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail(SV_EINVAL, "%s: temperature must be finite and > 0", who);
-    if (k < 0 || k > SV_TOPK_MAX) return fail(SV_EINVAL, "%s: k=%d must be in 0..%d", who, k, SV_TOPK_MAX);
-    if (k > 0 && (!dev_topk_ids || !dev_topk_logprobs)) return fail(SV_EINVAL, "%s: k=%d with a null dev_topk_ids / dev_topk_logprobs", who, k);
-    if (k == 0 && !dev_logprob && !dev_logsumexp && !dev_entropy && !dev_argmax) return fail(SV_EINVAL, "%s: every output pointer is null", who);
-    SVCHECK(check_ready(e));
-    if (B > e->cfg.max_batch) return fail(SV_EINVAL, "%s: bad B=%d (max_batch %d)", who, B, e->cfg.max_batch);
-    for (int b = 0; b < B; ++b) {
-        const long long T = (long long)host_prefix_lens[host_prefix_of[b]] + host_lens[b];
-        if (T > e->cfg.max_seq_len)
-            return fail(SV_EINVAL, "%s: length %lld of sequence %d (prefix %d + own %d) out of range (1..max_seq_len %d)", who, T, b,
-                        host_prefix_lens[host_prefix_of[b]], host_lens[b], e->cfg.max_seq_len);
-    }
-    // (every weight format: the pass is the ragged pass's launches -- fp8's column-scale epilogue and the bf16 image of an mxfp4 engine are per row and
-    //  per column --, and tests/test_gpu_prefix_scoring.py holds each format to the contract)
-    const Linear* proj[4] = {&e->dec[0].c_attn, &e->dec[0].c_proj, &e->dec[0].c_fc, &e->dec[0].c_proj2};
-    const PrefixProj pj[4] = {{proj[0]->N, proj[0]->Kpad, ACT_NONE}, {proj[1]->N, proj[1]->Kpad, ACT_NONE}, {proj[2]->N, proj[2]->Kpad, ACT_GELU_TANH},
-                              {proj[3]->N, proj[3]->Kpad, ACT_NONE}};
-    static const char* const proj_name[4] = {"c_attn", "attention c_proj", "c_fc", "MLP c_proj"};
-    PrefixPlan plan;
-    // (SV_EXP_BATCH_REMAINDER: no per-sequence remainder anywhere, as in the ragged pass -- nothing to list and nothing to refuse)
-    prefix_plan(host_prefix_lens, P, host_lens, host_prefix_of, B, attn_prefill_q_tile(e->cfg.n_head, e->nkv), pj,
-                (e->exp & SV_EXP_BATCH_REMAINDER) ? 0 : 4, plan);
-    plan.rows.resize(4);
-    if (plan.refused >= 0) {
-        const int b = plan.refused, pl = host_prefix_lens[host_prefix_of[b]];
-        return fail(SV_EINVAL, "%s: sequence %d (prefix %d + own %d rows): the %d remainder rows of its %d-row solo run at %s would reach into the "
-                    "shared prefix (score it alone: sv_forward_logprobs_ragged on the concatenation)", who, b, pl, host_lens[b],
-                    seq_peel_rows(pl + host_lens[b]), pl + host_lens[b], proj_name[plan.refused_proj]);
-    }
-    ScoreLogprobs lp{dev_targets, 1.0f / temperature, dev_logprob, dev_logsumexp, dev_entropy, dev_argmax, k, dev_topk_ids, dev_topk_logprobs, dev_rank};
-    if (k == 0) { lp.topk_ids = nullptr; lp.topk_logprobs = nullptr; lp.rank = nullptr; }
-    hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIPCHECK(hipSetDevice(e->cfg.device));
-    SVCHECK(cb_guard(e, who));
-    // no page is assigned and none is written: whatever the cache held is void for sv_decode_step from here on (cached_B = 0: SV_ESTATE)
-    e->cached_B = 0;
-    SVCHECK(prefill_forward_prefixed(e, (const bf16_t*)dev_prefix_packed, (const bf16_t*)dev_embeds_packed, P, B, plan, host_keep, &lp, st));
-    HIPCHECK(hipGetLastError());
-    return score_flag_report(e, who, B, 0, host_keep, st);
+    return score_call(e, {"sv_forward_logprobs_prefixed", ScoreCall::PREFIXED, dev_embeds_packed, B, 0, 0, host_lens, host_keep, temperature,
+                          {dev_targets, 1.0f / temperature, dev_logprob, dev_logsumexp, dev_entropy, dev_argmax, k, dev_topk_ids, dev_topk_logprobs, dev_rank},
+                          dev_prefix_packed, P, host_prefix_lens, host_prefix_of},
+                      stream);
 }
 
 extern "C" int sv_decode_step(sv_engine* e, const int32_t* dev_tokens, int32_t B, float* dev_logits, sv_stream stream) {

@@ -172,15 +172,15 @@ struct sv_engine {
     int32_t* h_table = nullptr;   // pinned host image of block_table (assign_pages); table_ev = its last upload
     hipEvent_t table_ev = nullptr;
     bool table_pending = false;
-    // ragged prompt pass (engine_forward.hip, RaggedPlan): the per-sequence descriptors, block lists and remainder-row lists of the call, written into a
-    // pinned host image and uploaded without a stream synchronise like the block table; grown on demand
+    // packed prompt passes (PackedPlan below): the lists of the call's plan, concatenated into a pinned host image and uploaded without a stream
+    // synchronise like the block table (engine_forward.hip::rag_upload_plan); grown on demand
     int32_t *h_rag = nullptr, *d_rag = nullptr;
     size_t rag_cap = 0;                           // int32 elements either holds
     hipEvent_t rag_ev = nullptr;
     bool rag_pending = false;
     int32_t* rag_row_pos = nullptr; size_t rag_pos_rows = 0;      // [packed rows] position of a row inside its sequence
     bf16_t* rag_rsave = nullptr;                  // [3 * max_batch][hidden] residual rows of a GEMM's remainder launch (launch_gemm_ragged)
-    long long prompt_passes = 0;                  // prompt passes run so far, rectangular and ragged (sv_debug_prompt_passes)
+    long long prompt_passes = 0;                  // prompt passes run so far, rectangular and packed (sv_debug_prompt_passes)
     // KV pool
     char* kv_pool = nullptr;
     size_t layer_stride = 0;
@@ -349,42 +349,68 @@ int cb_guard(sv_engine* e, const char* who);
 int cb_check_lookup(const char* who, const sv_lookup* lookup, sv_lookup& lk);
 void cb_drop_graphs(sv_engine* e);          // the kept step graphs name the drafting setting and the forced-draft buffer: gone when either changes
 int prefill_locked(sv_engine* e, const void* dev_embeds, int B, int S0, int total_len, hipStream_t st, bool set_positions = true);
-// The ragged prompt pass: B sequences of lengths lens[0..B) (host), embeddings packed back to back.  What the dispatch decides for a set of lengths is
-// host arithmetic (ragged_gemm_rows, ragged_blocks: sv_debug_ragged_plan states it for the CPU tests).
-//   ragged_gemm_rows  the packed rows the projection (N, K, act) sends through the split-K remainder kernel -- the last seq_peel_rows(len) rows of every
-//                     sequence with gemm_seq_form(len, N, K, act) -- and the sequences whose LAST row is one of them (the pruned last layer's compact rows)
-//   ragged_blocks     {sequence, tile} pairs of `tile` rows counted from each sequence's first row (last_only: each sequence's last tile alone)
-void ragged_gemm_rows(const int32_t* lens, int B, int N, int K, int act, std::vector<int32_t>& rows, std::vector<int32_t>& last);
+// The packed prompt passes (engine_forward.hip::prefill_forward_packed): sequences of different lengths, embeddings packed back to back, no padding row.
+// Two forms share the one layer loop and differ only in the data of a PackedPlan:
+//   ragged    B sequences of lengths lens[0..B) (sv_prefill_ragged, sv_generate_ragged, the CB admit paths, sv_forward_logprobs_ragged)
+//   prefixed  P prefixes and the own rows of B sequences in ONE packed buffer, prefixes first; sequence b stands for the solo sequence
+//             concat(prefix[prefix_of[b]], own rows of b) of T_b = Pl + len_b rows (sv_forward_logprobs_prefixed; why the bits hold: prefix/prefix.hip)
+// Everything a plan decides is host arithmetic: ragged_plan and prefix_plan need no engine (sv_debug_ragged_plan / sv_debug_prefix_plan state them for
+// the CPU tests).  The lists of a plan, in the order they lie in the plan image (sv_engine::h_rag / d_rag):
+enum {
+    PL_DESC,            // ragged: descriptors {first packed row, length} x B | prefixed: segments {first packed row, length, position of its first row} x (P + B)
+    PL_SEQ0, PL_BLOCKS0,   // first attention launch: its sequences (EMPTY: the ragged descriptors) | {sequence, query tile}, every tile
+    PL_SEQ1, PL_BLOCKS1,   // second attention launch (prefixed form): {first own packed row, T, first prefix packed row, Pl} | tiles whose last row >= Pl
+    PL_LAST_TILES,      // {sequence, its last query tile}: the pruned last layer (ragged generation)
+    PL_KV_BLOCKS,       // {sequence, 32-row tile} of the KV write; EMPTY: no page is written (prefixed)
+    PL_ROWS,            // + 2 i: the packed rows projection i sends through the split-K remainder kernel -- the last seq_peel_rows(T) rows of every
+                        //   solo sequence of T rows with gemm_seq_form(T, N, K, act); + 2 i + 1: the sequences whose LAST row is one of them (the pruned
+                        //   last layer's compact rows; ragged only)
+    PL_KEPT = PL_ROWS + 8,   // scoring: ragged {first packed row, length, keep, first output row} x B | prefixed: the kept packed rows, in output order
+    PL_COUNT
+};
+constexpr int pl_rows(int i) { return PL_ROWS + 2 * i; }
+constexpr int pl_last(int i) { return PL_ROWS + 2 * i + 1; }
+// The ragged form's descriptors are the FIRST list: they lie at offset 0 of d_rag and stay valid until the next packed pass -- ragged_positions,
+// the generate drivers (kv.rag_seq = e->d_rag) and the CB admit paths read them there after the pass has returned.
+struct PackedPlan {
+    enum Tail { GENERATE,             // last layer pruned to every sequence's last row, then last-row logits
+                SCORE_TAIL_ROWS,      // gather_tail_rows over PL_KEPT -> ln_f -> chunked lm_head + logprob_rows, then last-row logits
+                SCORE_LISTED_ROWS };  // gather_listed_rows over PL_KEPT -> the same; no last-row logits
+    int M = 0, B = 0;                      // packed rows | sequences
+    const bf16_t* src[2] = {nullptr, nullptr};   // embedding sources, laid back to back in the pass's hidden buffer (set by the caller of the builder)
+    int src_rows[2] = {0, 0};              //   and their rows (ragged: M, 0 | prefixed: prefix rows, own rows)
+    int n_seg = 0;                         // 0: row positions from the ragged descriptors | P + B segments of the prefixed form
+    int n_attn = 1;                        // attention launches per layer; the second one is the prefixed form
+    Tail tail = GENERATE;
+    int kept = 0;                          // kept rows of a scoring tail
+    int refused = -1, refused_proj = -1;   // prefixed: first sequence whose remainder rows would reach into its prefix (and the projection that says so)
+    std::vector<int32_t> list[PL_COUNT];
+    std::vector<int32_t>& rows(int i) { return list[pl_rows(i)]; }
+    std::vector<int32_t>& last(int i) { return list[pl_last(i)]; }
+};
+struct PlanProj { int N, K, act; };        // a projection as the remainder-row rule sees it
+// {sequence, tile} pairs of `tile` rows counted from each sequence's first row (last_only: each sequence's last tile alone)
 void ragged_blocks(const int32_t* lens, int B, int tile, bool last_only, std::vector<int32_t>& out);
+// the ragged form's plan.  keep == nullptr: generation; otherwise scoring -- the last keep[b] (1..lens[b]) rows of every sequence, outputs packed
+// [sum(keep)] in sequence order, no layer pruned.  n_proj = 0: no per-sequence remainder anywhere (SV_EXP_BATCH_REMAINDER)
+void ragged_plan(const int32_t* lens, int B, int q_tile, const PlanProj* proj, int n_proj, const int32_t* keep, PackedPlan& out);
 int ragged_check_lens(const sv_engine* e, const int32_t* lens, int B, const char* who, int* max_len, long long* total);
 int assign_pages_ragged(sv_engine* e, int B, const int32_t* lens, int extra, hipStream_t st);
-// keep + lp (both or neither): the scoring mode -- the last keep[b] (host, 1..lens[b]) rows of every sequence through ln_f, the chunked lm_head and
-// logprob_rows / topk_rows, outputs packed [sum(keep)] in sequence order; no layer is pruned
+int prefill_forward_packed(sv_engine* e, const PackedPlan& p, const int32_t* table, const ScoreLogprobs* lp, hipStream_t st);
+// ragged_plan over (lens, keep) for this engine, then the pass; keep + lp: both (scoring) or neither (generation)
 int prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, const int32_t* lens, hipStream_t st, const int32_t* table = nullptr,
                            const int32_t* keep = nullptr, const ScoreLogprobs* lp = nullptr);
-// positions[i] = lens[i / rep] + delta for i < B * rep, from the descriptors the last prefill_forward_ragged uploaded
+// positions[i] = lens[i / rep] + delta for i < B * rep, from the descriptors the last ragged pass uploaded
 void ragged_positions(sv_engine* e, int B, int rep, int delta, hipStream_t st);
 // the launch behind it: positions[i] = rag_seq[2 * (i / rep) + 1] + delta for i < n, descriptors {first packed row, length}
 void launch_ragged_positions(int32_t* positions, const int32_t* rag_seq, int n, int rep, int delta, hipStream_t st);
-// The shared-prefix scoring pass (sv_forward_logprobs_prefixed): P prefixes and the own rows of B sequences in ONE packed buffer, prefixes first;
-// sequence b stands for the solo sequence concat(prefix[prefix_of[b]], own rows of b) of T_b = Pl + len_b rows.  Everything the pass decides is
-// host arithmetic (prefix/prefix.hip; sv_debug_prefix_plan states it for the CPU tests).
-struct PrefixPlan {
-    int MP = 0, M = 0;                     // prefix rows | all packed rows (the own rows follow the prefixes, in sequence order)
-    int refused = -1, refused_proj = -1;   // first sequence whose remainder rows would reach into its prefix (and the projection that says so)
-    std::vector<int32_t> seg;              // {first packed row, length, position of its first row} x (P + B): the row-position builder's segments
-    std::vector<int32_t> pseq, pblocks;    // the prefixes as ordinary ragged sequences {first packed row, Pl} | {prefix, query tile}, every tile
-    std::vector<int32_t> sseq, sblocks;    // {first own packed row, T, first prefix packed row, Pl} | {sequence, query tile}: tiles whose last row >= Pl
-    std::vector<std::vector<int32_t>> rows;   // per projection: the packed OWN rows with solo index >= T - seq_peel_rows(T) where gemm_seq_form(T, ...) holds
-};
-struct PrefixProj { int N, K, act; };
 // SV_EINVAL + message (who: ...) for P / B out of order (1 <= P <= B), a length < 1, a prefix_of outside 0..P-1, a prefix no sequence uses, and
 // -- keep != nullptr -- a keep outside 1..len + 1
 int prefix_check(const char* who, const int32_t* prefix_lens, int P, const int32_t* lens, const int32_t* prefix_of, int B, const int32_t* keep);
-void prefix_plan(const int32_t* prefix_lens, int P, const int32_t* lens, const int32_t* prefix_of, int B, int q_tile, const PrefixProj* proj, int n_proj,
-                 PrefixPlan& out);
-// the packed rows of the kept rows, in output order: the last keep[b] solo rows of every sequence (keep = len + 1 starts at its prefix's last row)
-void prefix_kept_rows(const PrefixPlan& plan, int B, const int32_t* keep, std::vector<int32_t>& out);
+// the prefixed form's plan (prefix/prefix.hip).  keep != nullptr: PL_KEPT = the last keep[b] solo rows of every sequence (keep = len + 1 starts at its
+// prefix's last row)
+void prefix_plan(const int32_t* prefix_lens, int P, const int32_t* lens, const int32_t* prefix_of, int B, int q_tile, const PlanProj* proj, int n_proj,
+                 const int32_t* keep, PackedPlan& out);
 // engine_generate.hip
 void fork_args(sv_engine* e, int n_prompts, int n_rows, ForkArgs& f);      // the fork launch over e->fork_desc, the engine's block table, pool and logits
 // validation of a processor set against a vocabulary of V ids (V <= 0: the ids are only checked for >= 0) -- host arithmetic, no device -- and

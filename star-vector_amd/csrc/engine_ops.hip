@@ -543,13 +543,13 @@ extern "C" int sv_debug_ragged_plan(const int32_t* lens, int32_t B, int32_t N, i
     if (capacity < 3 * B) return fail(SV_EINVAL, "sv_debug_ragged_plan: capacity %d < 3 * B", capacity);
     for (int b = 0; b < B; ++b)
         if (lens[b] < 1) return fail(SV_EINVAL, "sv_debug_ragged_plan: length %d of sequence %d", lens[b], b);
-    std::vector<int32_t> rows, last, ab, kb;
-    ragged_gemm_rows(lens, B, N, K, act, rows, last);
-    ragged_blocks(lens, B, q_tile, false, ab);
-    ragged_blocks(lens, B, 32, false, kb);
-    for (size_t i = 0; i < rows.size(); ++i) rows_out[i] = rows[i];
-    for (size_t i = 0; i < last.size(); ++i) last_out[i] = last[i];
-    out4[0] = (int32_t)rows.size(); out4[1] = (int32_t)last.size(); out4[2] = (int32_t)ab.size() / 2; out4[3] = (int32_t)kb.size() / 2;
+    PackedPlan pp;
+    const PlanProj pj{N, K, act};
+    ragged_plan(lens, B, q_tile, &pj, 1, nullptr, pp);
+    std::copy(pp.rows(0).begin(), pp.rows(0).end(), rows_out);
+    std::copy(pp.last(0).begin(), pp.last(0).end(), last_out);
+    out4[0] = (int32_t)pp.rows(0).size(); out4[1] = (int32_t)pp.last(0).size();
+    out4[2] = (int32_t)pp.list[PL_BLOCKS0].size() / 2; out4[3] = (int32_t)pp.list[PL_KV_BLOCKS].size() / 2;
     return 0;
 }
 extern "C" int sv_debug_prompt_passes(sv_engine* e, int64_t* out) {
@@ -1330,10 +1330,11 @@ extern "C" int sv_op_attn_prefill_prefixed(const void* qkv, int32_t q_off, int32
     if (rows > (1 << 24) || B > 65535) return fail(SV_EINVAL, "%s: %lld rows / %d sequences: more than this test surface takes", who, rows, B);
 
     hipStream_t st = (hipStream_t)stream;
-    PrefixPlan pp;
-    prefix_plan(host_prefix_lens, P, host_lens, host_prefix_of, B, attn_prefill_q_tile(H, Hkv), nullptr, 0, pp);
-    std::vector<int32_t> plan(pp.sseq);
-    plan.insert(plan.end(), pp.sblocks.begin(), pp.sblocks.end());
+    PackedPlan pp;
+    prefix_plan(host_prefix_lens, P, host_lens, host_prefix_of, B, attn_prefill_q_tile(H, Hkv), nullptr, 0, nullptr, pp);
+    const std::vector<int32_t>&sseq = pp.list[PL_SEQ1], &sblocks = pp.list[PL_BLOCKS1];
+    std::vector<int32_t> plan(sseq);
+    plan.insert(plan.end(), sblocks.begin(), sblocks.end());
     TmpBufs tmp;
     int32_t* d_plan;
     SVCHECK(tmp.get(&d_plan, plan.size()));
@@ -1343,7 +1344,7 @@ extern "C" int sv_op_attn_prefill_prefixed(const void* qkv, int32_t q_off, int32
     a.q_row_stride = row_stride; a.kv_row_stride = row_stride; a.q_head_stride = head_dim; a.kv_head_stride = Hkv > 1 ? head_dim : 0;
     a.o = (bf16_t*)out; a.o_row_stride = H * head_dim; a.B = B; a.S = 0; a.H = H; a.head_dim = head_dim;
     a.kv_group = H / Hkv; a.causal = 1; a.scale = scale; a.window = window;
-    a.rag_seq = d_plan; a.rag_blocks = d_plan + pp.sseq.size(); a.rag_nblocks = (int)pp.sblocks.size() / 2; a.rag_prefixed = 1;
+    a.rag_seq = d_plan; a.rag_blocks = d_plan + sseq.size(); a.rag_nblocks = (int)sblocks.size() / 2; a.rag_prefixed = 1;
     launch_attn_prefill(a, st);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(st));          // the plan is freed on return

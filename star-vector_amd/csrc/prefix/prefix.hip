@@ -8,7 +8,7 @@
 //   * the attention reads a solo index through one indirection (attn_prefill_kernel<.., PFX>), tiles counted from solo index 0;
 //   * the split-K remainder kernel (its own K order) computes the last seq_peel_rows(T_b) rows of a solo run wherever gemm_seq_form(T_b, N, K, act)
 //     holds: those are listed among the OWN rows only.  If they would reach below Pl the prefix row would need different bits for different
-//     sharers: the call is refused (PrefixPlan::refused).  A prefix is never listed by its own length (a 257-row prefix has no peel row here).
+//     sharers: the call is refused (PackedPlan::refused).  A prefix is never listed by its own length (a 257-row prefix has no peel row here).
 #include <algorithm>
 #include "../engine_internal.h"
 
@@ -40,29 +40,33 @@ int sveng::prefix_check(const char* who, const int32_t* prefix_lens, int P, cons
     return 0;
 }
 
-void sveng::prefix_plan(const int32_t* prefix_lens, int P, const int32_t* lens, const int32_t* prefix_of, int B, int q_tile, const PrefixProj* proj,
-                        int n_proj, PrefixPlan& out) {
-    out = PrefixPlan();
-    out.rows.resize((size_t)n_proj);
+// The prefixes travel as ordinary ragged sequences (PL_SEQ0 = {first packed row, Pl}) through the first attention launch, the sequences through the
+// second one in the prefixed form; no K / V page is written and no layer is pruned.
+void sveng::prefix_plan(const int32_t* prefix_lens, int P, const int32_t* lens, const int32_t* prefix_of, int B, int q_tile, const PlanProj* proj,
+                        int n_proj, const int32_t* keep, PackedPlan& out) {
+    out = PackedPlan();
+    out.B = B; out.n_seg = P + B; out.n_attn = 2; out.tail = PackedPlan::SCORE_LISTED_ROWS;
+    std::vector<int32_t>&seg = out.list[PL_DESC], &pseq = out.list[PL_SEQ0], &sseq = out.list[PL_SEQ1], &sblocks = out.list[PL_BLOCKS1],
+                        &kept = out.list[PL_KEPT];
     std::vector<int32_t> prow0((size_t)P);
     int r0 = 0;
     for (int u = 0; u < P; ++u) {
         prow0[u] = r0;
         const int32_t s[3] = {r0, prefix_lens[u], 0};
-        out.seg.insert(out.seg.end(), s, s + 3);
-        out.pseq.push_back(r0); out.pseq.push_back(prefix_lens[u]);
+        seg.insert(seg.end(), s, s + 3);
+        pseq.push_back(r0); pseq.push_back(prefix_lens[u]);
         r0 += prefix_lens[u];
     }
-    out.MP = r0;
-    ragged_blocks(prefix_lens, P, q_tile, false, out.pblocks);
+    out.src_rows[0] = r0;
+    ragged_blocks(prefix_lens, P, q_tile, false, out.list[PL_BLOCKS0]);
     for (int b = 0; b < B; ++b) {
-        const int pl = prefix_lens[prefix_of[b]], T = pl + lens[b];
+        const int p0 = prow0[prefix_of[b]], pl = prefix_lens[prefix_of[b]], T = pl + lens[b];
         const int32_t s[3] = {r0, lens[b], pl};
-        out.seg.insert(out.seg.end(), s, s + 3);
-        const int32_t d[4] = {r0, T, prow0[prefix_of[b]], pl};
-        out.sseq.insert(out.sseq.end(), d, d + 4);
+        seg.insert(seg.end(), s, s + 3);
+        const int32_t d[4] = {r0, T, p0, pl};
+        sseq.insert(sseq.end(), d, d + 4);
         // query tiles counted from solo index 0; the first listed tile is the one that holds row Pl (it may straddle the prefix's end)
-        for (int t = pl / q_tile, n = (T + q_tile - 1) / q_tile; t < n; ++t) { out.sblocks.push_back(b); out.sblocks.push_back(t); }
+        for (int t = pl / q_tile, n = (T + q_tile - 1) / q_tile; t < n; ++t) { sblocks.push_back(b); sblocks.push_back(t); }
         const int r = seq_peel_rows(T);
         for (int i = 0; i < n_proj && r > 0; ++i) {
             if (!gemm_seq_form(T, proj[i].N, proj[i].K, proj[i].act)) continue;
@@ -70,19 +74,13 @@ void sveng::prefix_plan(const int32_t* prefix_lens, int P, const int32_t* lens, 
                 if (out.refused < 0) { out.refused = b; out.refused_proj = i; }
                 continue;
             }
-            for (int j = lens[b] - r; j < lens[b]; ++j) out.rows[i].push_back(r0 + j);
+            for (int j = lens[b] - r; j < lens[b]; ++j) out.rows(i).push_back(r0 + j);
         }
+        for (int s = keep ? T - keep[b] : T; s < T; ++s) kept.push_back(s < pl ? p0 + s : r0 + s - pl);
         r0 += lens[b];
     }
-    out.M = r0;
-}
-
-void sveng::prefix_kept_rows(const PrefixPlan& plan, int B, const int32_t* keep, std::vector<int32_t>& out) {
-    out.clear();
-    for (int b = 0; b < B; ++b) {
-        const int own0 = plan.sseq[4 * b], T = plan.sseq[4 * b + 1], p0 = plan.sseq[4 * b + 2], pl = plan.sseq[4 * b + 3];
-        for (int s = T - keep[b]; s < T; ++s) out.push_back(s < pl ? p0 + s : own0 + s - pl);
-    }
+    out.M = r0; out.src_rows[1] = r0 - out.src_rows[0];
+    out.kept = (int)kept.size();
 }
 
 // the plan for ONE projection (N, K, act): row_pos_out [capacity] the solo index of every packed row, rows_out [capacity] its remainder rows,
@@ -99,15 +97,16 @@ extern "C" int sv_debug_prefix_plan(const int32_t* prefix_lens, int32_t P, const
     for (int u = 0; u < P; ++u) total += prefix_lens[u];
     for (int b = 0; b < B; ++b) total += lens[b];
     if (total > (1 << 24)) return fail(SV_EINVAL, "%s: %lld rows: more than this test surface takes", who, total);
-    PrefixPlan pp;
-    const PrefixProj pj{N, K, act};
-    prefix_plan(prefix_lens, P, lens, prefix_of, B, q_tile, &pj, 1, pp);
-    const size_t need = std::max<size_t>(std::max<size_t>((size_t)pp.M, (size_t)3 * B), pp.sblocks.size());
+    PackedPlan pp;
+    const PlanProj pj{N, K, act};
+    prefix_plan(prefix_lens, P, lens, prefix_of, B, q_tile, &pj, 1, nullptr, pp);
+    const std::vector<int32_t>&seg = pp.list[PL_DESC], &rows = pp.rows(0), &sblocks = pp.list[PL_BLOCKS1];
+    const size_t need = std::max<size_t>(std::max<size_t>((size_t)pp.M, (size_t)3 * B), sblocks.size());
     if ((size_t)(capacity < 0 ? 0 : capacity) < need) return fail(SV_EINVAL, "%s: capacity %d < %zu", who, capacity, need);
-    for (size_t i = 0; i + 2 < pp.seg.size(); i += 3)
-        for (int j = 0; j < pp.seg[i + 1]; ++j) row_pos_out[pp.seg[i] + j] = pp.seg[i + 2] + j;
-    for (size_t i = 0; i < pp.rows[0].size(); ++i) rows_out[i] = pp.rows[0][i];
-    for (size_t i = 0; i < pp.sblocks.size(); ++i) blocks_out[i] = pp.sblocks[i];
-    out4[0] = (int32_t)pp.rows[0].size(); out4[1] = (int32_t)pp.sblocks.size() / 2; out4[2] = pp.refused; out4[3] = pp.M;
+    for (size_t i = 0; i + 2 < seg.size(); i += 3)
+        for (int j = 0; j < seg[i + 1]; ++j) row_pos_out[seg[i] + j] = seg[i + 2] + j;
+    std::copy(rows.begin(), rows.end(), rows_out);
+    std::copy(sblocks.begin(), sblocks.end(), blocks_out);
+    out4[0] = (int32_t)rows.size(); out4[1] = (int32_t)sblocks.size() / 2; out4[2] = pp.refused; out4[3] = pp.M;
     return 0;
 }
