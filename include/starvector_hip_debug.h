@@ -481,6 +481,20 @@ int  sv_debug_set_score_chunk_rows(sv_engine* e, int32_t rows);
 /* temperature -> top-k (0 = off) -> top-p -> one multinomial draw per row */
 int  sv_op_sample(const float* logits, int32_t B, int32_t V, int32_t ld, float temperature, int32_t top_k,
                   float top_p, uint64_t seed, int32_t step, int32_t* out, sv_stream stream);
+/* The per-step output launch of sv_generate_ex (sampling.hip launch_capture_rows: capture_warp_kernel + capture_write_kernel) on caller-given
+ * rows, as step 0 of a one-step call: dev_rows fp32 [B][ld], V valid columns.  dev_seen (may be NULL) uint32 [B][seen_words] with `penalty`:
+ * the repetition set of each row; hold_eos != 0: the min-length hold, eos_token_id at -inf.  do_sample != 0: temperature -> top_k (<= 0: off)
+ * -> top_p -> min_p (0: off) with min_tokens_to_keep 1.  Outputs, each [B][ld_out] fp32 and optional (at least one): dev_logits_out = the raw
+ * row, dev_scores_out = the processed row as HF reports it -- kept ids s / temperature, the rest -inf.  Columns >= V and rows >= B are not
+ * written.  Every argument is checked before any device work (SV_EINVAL). */
+int  sv_op_capture_rows(const float* dev_rows, int32_t B, int32_t V, int32_t ld, const uint32_t* dev_seen, int32_t seen_words, float penalty,
+                        int32_t eos_token_id, int32_t hold_eos, int32_t do_sample, float temperature, int32_t top_k, float top_p, float min_p,
+                        float* dev_scores_out, float* dev_logits_out, int64_t ld_out, sv_stream stream);
+/* The sv_beam_step calls that follow also launch beam_capture_kernel (beam.hip) into the caller's slabs, through the BeamScorer::cap / cap_temp
+ * sv_generate_ex sets: dev_scores / dev_logits fp32 [max_new][batch * num_beams][ld] (each optional), step t writes slab t -- the raw rows and
+ * the processed log-probs the scorer ranks (beam-sample: kept ids lp / temperature with min_tokens_to_keep 2, the rest -inf).  Both NULL:
+ * cleared.  ld >= vocab and 1 <= max_new <= the scorer's (SV_EINVAL); steps >= max_new write nothing.  The slabs must outlive the steps. */
+int  sv_debug_beam_set_capture(sv_beam* b, float* dev_scores, float* dev_logits, int64_t ld, int32_t max_new);
 
 #ifdef __cplusplus
 }

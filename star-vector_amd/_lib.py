@@ -273,6 +273,8 @@ DEBUG_PROTOTYPES = {
     "sv_op_argmax": (_I, [_P, _I, _I, _I, _P, _P]),
     "sv_op_sample_top_p": (_I, [_P, _I, _I, _I, _F, _F, C.c_uint64, _I, _P, _P]),
     "sv_op_sample": (_I, [_P, _I, _I, _I, _F, _I, _F, C.c_uint64, _I, _P, _P]),
+    "sv_op_capture_rows": (_I, [_P, _I, _I, _I, _P, _I, _F, _I, _I, _I, _F, _I, _F, _F, _P, _P, C.c_int64, _P]),
+    "sv_debug_beam_set_capture": (_I, [_P, _P, _P, C.c_int64, _I]),
     "sv_op_logprob_rows": (_I, [_P, _I, _I, _I, _P, _F, _P, _P, _P, _P, C.POINTER(_I), _P]),
     "sv_debug_set_score_chunk_rows": (_I, [_P, _I]),
     "sv_op_topk_rows_bf16": (_I, [_P, _I, _I, _I, _P, _F, _P, _I, _P, _P, _P, _P]),

@@ -1064,7 +1064,7 @@ static int generate_attempt(sv_engine* e, const GenCall& c) {
 // ------------------------------------------------------------------------------------------------
 // C ABI: the beam scorer on its own (parity tests drive it with synthetic logits)
 // ------------------------------------------------------------------------------------------------
-struct sv_beam { BeamScorer s; int device = 0; };
+struct sv_beam { BeamScorer s; int device = 0; CaptureDesc* cap_desc = nullptr; };
 
 extern "C" int sv_beam_create(const sv_beam_config* cfg, sv_beam** out) {
     if (!cfg || !out) return fail(SV_EINVAL, "sv_beam_create: null argument");
@@ -1094,7 +1094,24 @@ extern "C" int sv_beam_destroy(sv_beam* h) {
     if (!h) return 0;
     (void)hipDeviceSynchronize();
     h->s.destroy();
+    if (h->cap_desc) (void)hipFree(h->cap_desc);
     delete h;
+    return 0;
+}
+// test surface (include/starvector_hip_debug.h): the sv_beam_step calls that follow also launch beam_capture_kernel into the caller's slabs,
+// through the BeamScorer::cap / cap_temp the engine sets for sv_generate_ex
+extern "C" int sv_debug_beam_set_capture(sv_beam* h, float* dev_scores, float* dev_logits, int64_t ld, int32_t max_new) {
+    if (!h) return fail(SV_EINVAL, "sv_debug_beam_set_capture: null scorer");
+    if (!dev_scores && !dev_logits) { h->s.cap = nullptr; h->s.cap_temp = 1.f; return 0; }
+    if (ld < h->s.c.V) return fail(SV_EINVAL, "sv_debug_beam_set_capture: ld %lld < vocab %d", (long long)ld, h->s.c.V);
+    if (max_new < 1 || max_new > h->s.c.max_new)
+        return fail(SV_EINVAL, "sv_debug_beam_set_capture: max_new %d outside 1..%d (the scorer's)", max_new, h->s.c.max_new);
+    if (!h->cap_desc) HIPCHECK(hipMalloc(reinterpret_cast<void**>(&h->cap_desc), sizeof(CaptureDesc)));
+    CaptureDesc hd;
+    hd.scores = dev_scores; hd.logits = dev_logits; hd.ld = ld; hd.rows = h->s.R; hd.max_new = max_new;
+    HIPCHECK(hipMemcpy(h->cap_desc, &hd, sizeof(hd), hipMemcpyHostToDevice));
+    h->s.cap = h->cap_desc;
+    h->s.cap_temp = h->s.c.temperature;
     return 0;
 }
 extern "C" int sv_beam_step(sv_beam* h, const float* dev_logits, int32_t ld, int32_t* done, int32_t* host_parent,

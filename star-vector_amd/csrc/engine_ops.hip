@@ -1942,3 +1942,42 @@ extern "C" int sv_op_sample(const float* logits, int32_t B, int32_t V, int32_t l
     HIPCHECK(hipStreamSynchronize(st));
     return 0;
 }
+
+// launch_capture_rows (capture_warp_kernel + capture_write_kernel, sampling.hip) on caller-given rows: the launch sv_generate_ex makes per step,
+// at device step 0 of a one-step call.  The descriptor, the step / done scalars and the per-row thresholds live in temporaries of this call.
+extern "C" int sv_op_capture_rows(const float* dev_rows, int32_t B, int32_t V, int32_t ld, const uint32_t* dev_seen, int32_t seen_words,
+                                  float penalty, int32_t eos_token_id, int32_t hold_eos, int32_t do_sample, float temperature, int32_t top_k,
+                                  float top_p, float min_p, float* dev_scores_out, float* dev_logits_out, int64_t ld_out, sv_stream stream) {
+    const char* who = "sv_op_capture_rows";
+    if (!dev_rows || (!dev_scores_out && !dev_logits_out)) return fail(SV_EINVAL, "%s: null dev_rows, or neither output given", who);
+    if (B < 1 || B > 65535 || V < 1 || ld < V || ld_out < V)
+        return fail(SV_EINVAL, "%s: bad shape (B %d in 1..65535, V %d >= 1, ld %d and ld_out %lld >= V)", who, B, V, ld, (long long)ld_out);
+    if (dev_seen && (seen_words < (V + 31) / 32 || !(penalty > 0.f) || !std::isfinite(penalty)))
+        return fail(SV_EINVAL, "%s: a seen bitmap needs seen_words >= ceil(V / 32) and a finite penalty > 0", who);
+    if (hold_eos && eos_token_id >= V) return fail(SV_EINVAL, "%s: eos_token_id %d outside the vocabulary", who, eos_token_id);
+    if (do_sample && (!(temperature > 0.f) || !std::isfinite(temperature) || !(top_p > 0.f) || !(top_p <= 1.f) || !(min_p >= 0.f) || !(min_p <= 1.f)))
+        return fail(SV_EINVAL, "%s: temperature must be finite and > 0, top_p in (0, 1], min_p in [0, 1]", who);
+    hipStream_t st = (hipStream_t)stream;
+    TmpBufs tmp;
+    CaptureDesc* ddesc;
+    int32_t* scalars;                                                // {step, done}
+    float* warp;
+    SVCHECK(tmp.get(&ddesc, 1));
+    SVCHECK(tmp.get(&scalars, 2));
+    SVCHECK(tmp.get(&warp, (size_t)B * 8));
+    CaptureDesc hd;
+    hd.scores = dev_scores_out; hd.logits = dev_logits_out; hd.ld = ld_out; hd.rows = B; hd.max_new = 1;
+    HIPCHECK(hipMemcpyAsync(ddesc, &hd, sizeof(hd), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemsetAsync(scalars, 0, 2 * sizeof(int32_t), st));
+    CaptureArgs c;
+    c.desc = ddesc; c.src = dev_rows; c.ld_src = ld; c.V = V; c.B = B; c.step = scalars; c.done = scalars + 1;
+    c.seen = dev_seen; c.seen_words = dev_seen ? seen_words : 0; c.penalty = dev_seen ? penalty : 1.f;
+    c.eos = eos_token_id; c.min_new = hold_eos ? 1 : 0;
+    c.do_sample = do_sample ? 1 : 0; c.temperature = do_sample ? temperature : 1.f; c.top_p = do_sample ? top_p : 1.f; c.top_k = top_k;
+    c.warp = (do_sample && dev_scores_out) ? warp : nullptr;
+    c.minp_log = (do_sample && min_p > 0.f) ? logf(min_p) : -INFINITY; c.what = 3;
+    launch_capture_rows(c, st);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));                              // hd and the temporaries are this call's
+    return 0;
+}

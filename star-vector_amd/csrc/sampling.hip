@@ -86,8 +86,12 @@ void launch_sample_top_p(const SampleArgs& a, hipStream_t st) {
 
 // ------------------------------------------------------------------------------------------------
 // sv_generate_ex outputs (HF output_scores / output_logits): the raw row and the processed row of step t = *step, written by a
-// wide grid of 16-byte stores (2 x rows x V fp32 per step).  Sampling first takes the row's TopK -> TopP thresholds with the SAME
-// score functor and warp.h code the sampler's fallback path uses (one 1024-thread block per row, thresholds to p.warp).
+// wide grid of 16-byte stores (2 x rows x V fp32 per step).  Sampling first takes the row's TopK -> TopP thresholds with the sampler's
+// score functor (one 1024-thread block per row, thresholds to p.warp) -- through row_warp_stats<false, true>, i.e. warp.h's
+// row_warp_stats_select<49> / row_warp_stats_regs<49, ONCE> / row_warp_stats_global, NOT the forms the sampler draws through
+// (sample_row_topk, or row_warp_stats<true, true> = regs<16> / regs<52> / global).  That a drawn token has a finite captured score therefore
+// spans two forms: tests/test_gpu_warper_kept_set.py holds each to the float64 reference by exact set equality and
+// test_drawn_support_captured_support_and_reference_are_one_set ties them together.
 // ------------------------------------------------------------------------------------------------
 #define CAP_QPB 1024                       // 16-byte quads per block of the write grid (4096 floats)
 

@@ -1184,7 +1184,9 @@ class HipBeamScorer:
     def __init__(self, batch: int, num_beams: int, vocab: int, max_new: int, eos_token_id: int, pad_token_id: int,
                  length_penalty: float = 1.0, early_stopping=False, repetition_penalty: float = 1.0,
                  stop_ids: Optional[Sequence[int]] = None, do_sample: bool = False, temperature: float = 1.0,
-                 top_p: float = 1.0, top_k: int = 0, seed: int = 0, min_new_tokens: int = 0):
+                 top_p: float = 1.0, top_k: int = 0, seed: int = 0, min_new_tokens: int = 0, capture=None):
+        """``capture``: None, or (scores, logits) -- fp32 [max_new, batch * num_beams, ld >= vocab] tensors of one shape (either may be None):
+        every step also writes its processed log-probs and raw rows there (sv_debug_beam_set_capture: beam_capture_kernel)."""
         self.lib = _lib.load()
         stops = list(stop_ids) if stop_ids else []
         arr = (C.c_int32 * max(len(stops), 1))(*stops) if stops else None
@@ -1197,6 +1199,20 @@ class HipBeamScorer:
         self._h = C.c_void_p()
         self.rows, self.batch, self.vocab, self.max_new = batch * num_beams, batch, vocab, max_new
         check(self.lib.sv_beam_create(C.byref(cfg), C.byref(self._h)), "sv_beam_create")
+        self._capture = None
+        if capture is not None:
+            self.set_capture(*capture)
+
+    def set_capture(self, scores=None, logits=None):
+        """The steps that follow write slab t of ``scores`` / ``logits`` (see ``capture`` above); both None: cleared."""
+        outs = [o for o in (scores, logits) if o is not None]
+        for o in outs:
+            if not o.is_cuda or o.dtype != torch.float32 or o.dim() != 3 or not o.is_contiguous() or o.shape != outs[0].shape or \
+                    o.shape[1] != self.rows:
+                raise ValueError("capture slabs must be contiguous fp32 CUDA tensors [max_new, batch * num_beams, ld] of one shape")
+        ld, steps = (outs[0].shape[2], outs[0].shape[0]) if outs else (0, 0)
+        check(self.lib.sv_debug_beam_set_capture(self._h, _ptr(scores), _ptr(logits), ld, steps), "sv_debug_beam_set_capture")
+        self._capture = (scores, logits)                 # the slabs outlive the steps
 
     def step(self, logits: torch.Tensor):
         x = _need(logits, torch.float32, "logits")
@@ -2142,6 +2158,38 @@ def op_sample_top_p(logits, temperature, top_p, seed, step, top_k=0):
     check(lib.sv_op_sample(_ptr(logits), B, V, V, float(temperature), int(top_k), float(top_p), int(seed), int(step),
                            _ptr(out), _stream()))
     return out
+
+
+def op_capture_rows(rows, valid: Optional[int] = None, do_sample: bool = True, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                    min_p: float = 0.0, seen=None, penalty: float = 1.0, eos_token_id: int = -1, hold_eos: bool = False,
+                    scores_out=None, logits_out=None):
+    """The per-step output launch of generate(output_scores / output_logits) on caller-given fp32 rows [B, ld] (sv_op_capture_rows:
+    capture_warp_kernel + capture_write_kernel), `valid` = V columns (default ld).  ``seen``: per-row sets of ids for the repetition
+    ``penalty``.  scores_out / logits_out: fp32 [>= B, >= V] tensors of one row stride that receive the processed and the raw rows in place
+    (default: fresh [B, V] tensors); columns >= V and rows >= B of them are left as they were.  Returns (scores, logits)."""
+    lib = _lib.load()
+    x = _need(rows, torch.float32, "rows")
+    B, ld = x.shape
+    V = ld if valid is None else int(valid)
+    if scores_out is None and logits_out is None:
+        scores_out = torch.empty(B, V, dtype=torch.float32, device=x.device)
+        logits_out = torch.empty(B, V, dtype=torch.float32, device=x.device)
+    outs = [o for o in (scores_out, logits_out) if o is not None]
+    for o in outs:
+        if o.dtype != torch.float32 or o.dim() != 2 or o.shape[0] < B or o.shape[1] < V or o.stride(1) != 1 or o.stride(0) != outs[0].stride(0):
+            raise ValueError("outputs must be fp32 [>= B, >= V] with unit column stride and one row stride")
+    bits, words = None, 0
+    if seen is not None:
+        words = (V + 31) // 32
+        host = torch.zeros(B, words, dtype=torch.int64)
+        for r, ids in enumerate(seen):
+            for i in ids:
+                host[r, int(i) >> 5] |= 1 << (int(i) & 31)
+        bits = (host - ((host >> 31) << 32)).to(torch.int32).to(x.device)          # the uint32 words, bit for bit
+    check(lib.sv_op_capture_rows(_ptr(x), B, V, x.stride(0), _ptr(bits), words, float(penalty), int(eos_token_id), int(bool(hold_eos)),
+                                 int(bool(do_sample)), float(temperature), int(top_k or 0), float(top_p), float(min_p), _ptr(scores_out),
+                                 _ptr(logits_out), outs[0].stride(0), _stream()), "sv_op_capture_rows")
+    return scores_out, logits_out
 
 
 def op_lookup_draft(hist: Sequence[int], K: int, max_ngram: int = 3, min_ngram: int = 1, max_new: Optional[int] = None) -> List[int]:

@@ -23,6 +23,7 @@ BEAM = "test_gpu_beam.py::"
 LONG = "test_gpu_long_context.py::"
 DH64 = "test_gpu_decoder_head_dim64.py::"
 FP8 = "test_gpu_fp8_ops.py::"
+KEPT = "test_gpu_warper_kept_set.py::"                             # the warper's kept set, exactly, against float64 (tests/warp_rows.py)
 
 _ROW_UPDATE = (ROWS + "test_row_update_residual_mode_sums_the_slabs_in_order", ROWS + "test_row_update_embedding_mode", ROWS + "test_eps_row_update")
 _BIG_M = (OPS + "test_linear_mfma", OPS + "test_linear_big_m_kernels_agree_bitwise",
@@ -60,8 +61,9 @@ COVERAGE = {
     "beam_update_kernel": _BEAM_STEP + (BEAM + "test_beam_scorer_row0_stop_sequence",),
     "beam_reset_kernel": _BEAM_STEP,
     "beam_seen_gather_kernel": (BEAM + "test_beam_scorer_full_vocab_penalty_and_pad_zero",),
-    "beam_row_warp_kernel": (BEAM + "test_beam_sample_scorer_distribution", BEAM + "test_beam_sample_warper_selection_path_at_full_vocabulary"),
-    "beam_capture_kernel": ("test_gpu_generate_outputs.py::test_beam_search_outputs",),
+    "beam_row_warp_kernel": (KEPT + "test_beam_sample_forms_keep_exactly_the_reference_set", BEAM + "test_beam_sample_scorer_distribution",
+                             BEAM + "test_beam_sample_warper_selection_path_at_full_vocabulary"),
+    "beam_capture_kernel": (KEPT + "test_beam_sample_forms_keep_exactly_the_reference_set", "test_gpu_generate_outputs.py::test_beam_search_outputs"),
     "beam_table_reorder_kernel": _BEAM_KV,                                # (engine)
     "beam_tail_copy_kernel": _BEAM_KV,                                    # (engine)
     # ---- decode_cols.hip
@@ -132,9 +134,12 @@ COVERAGE = {
     "argmax_kernel": (OPS + "test_argmax_lowest_index_on_ties",),
     "argmax_merge_kernel": (OPS + "test_argmax_lowest_index_on_ties",),
     "sample_top_p_kernel": (OPS + "test_top_p_sampler_distribution", BEAM + "test_sampler_top_k_then_top_p_distribution",
-                            BEAM + "test_sampler_top_k_selection_at_full_vocabulary"),
-    "capture_warp_kernel": ("test_gpu_generate_outputs.py::test_sampling_topk_topp_graph_and_eager",),     # (engine)
-    "capture_write_kernel": ("test_gpu_generate_outputs.py::test_greedy_penalty_min_length_eos_and_stop",  # (engine)
+                            BEAM + "test_sampler_top_k_selection_at_full_vocabulary", KEPT + "test_sampler_forms_draw_exactly_the_reference_set",
+                            KEPT + "test_drawn_support_captured_support_and_reference_are_one_set"),
+    "capture_warp_kernel": (KEPT + "test_capture_forms_keep_exactly_the_reference_set", KEPT + "test_capture_processors_in_front_of_the_warper",
+                            "test_gpu_generate_outputs.py::test_sampling_topk_topp_graph_and_eager"),
+    "capture_write_kernel": (KEPT + "test_capture_forms_keep_exactly_the_reference_set", KEPT + "test_capture_processors_in_front_of_the_warper",
+                             "test_gpu_generate_outputs.py::test_greedy_penalty_min_length_eos_and_stop",
                              "test_gpu_generate_outputs.py::test_sampling_topk_topp_graph_and_eager"),
     "token_stats_kernel": ("test_gpu_token_stats.py::test_tokens_unaffected_and_values_match_the_capture",  # (engine)
                            "test_gpu_token_stats.py::test_agrees_with_the_scoring_forward"),
@@ -143,7 +148,8 @@ COVERAGE = {
     "finish_step_kernel": (E2E + "test_step_bookkeeping_inside_the_lm_head_launch_equals_the_finish_launch",                               # (engine)
                            E2E + "test_generate_semantics_eos_pad_stop_on_device"),
     "cb_step_kernel": ("test_gpu_vllm_sampling.py::test_op_greedy_processors_match_the_restatement",
-                       "test_gpu_vllm_sampling.py::test_op_distribution_matches_the_restatement", "test_gpu_cb_logprobs.py::test_operator_mixed_rows"),
+                       "test_gpu_vllm_sampling.py::test_op_distribution_matches_the_restatement", "test_gpu_cb_logprobs.py::test_operator_mixed_rows",
+                       KEPT + "test_every_kernel_that_draws_through_sample_row_draws_the_reference_set"),
     # ---- score.hip
     "logprob_rows_kernel": ("test_gpu_token_logprobs.py::test_logprob_rows_operator",),
     "topk_rows_bf16_kernel": ("test_gpu_token_topk.py::test_operator_bf16_rows",),
