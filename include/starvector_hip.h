@@ -188,6 +188,31 @@ void sv_config_default_8b(sv_config* cfg);    /* siglip_384 + starcoder2-7b shap
 int  sv_create(const sv_config* cfg, sv_engine** out);
 int  sv_destroy(sv_engine* e);
 
+/* The KV-cache format, chosen at engine creation (entry points appended; SV_ABI_VERSION and sv_config are unchanged).  sv_create is
+ * sv_create_kv with SV_KV_BF16.
+ *
+ * SV_KV_FP8_E4M3.  For every (token, KV head), K (after RoPE) and V are quantised separately to one scale byte and head_dim one-byte
+ * OCP e4m3 codes.  The rule:
+ *   - amax is taken over the finite ones of the head_dim bf16 values the bf16 cache would have stored;
+ *   - E = floor(log2(amax)) - 7, clamped to [-120, 120]; the scale byte is E + 127.  The scaled maximum then lies in [128, 256): no code
+ *     saturates (the clamp at 120 can let an element above 248 * 2^120 dequantise to 2^128, which bf16 spells Inf);
+ *   - amax = 0 gives E = 0 and codes 0;
+ *   - code = e4m3_rne(x * 2^-E), round to nearest even; the multiply is exact;
+ *   - a non-finite element becomes the NaN code (a request with NaN inputs still ends with SV_EHIP);
+ *   - every dequantised element 2^E * e4m3 is exactly a bf16 number.
+ * The engine computes exactly what the bf16-KV engine computes over a cache holding deq(quant(.)), with one exception: a token's own pass
+ * sees its unquantised K / V -- the prompt pass attends over the unquantised prompt, a decode step takes the new token's K / V in bf16 --
+ * and every later step reads the quantised row.  Slots behind a sequence's position contribute exactly zero whatever codes and scale
+ * bytes they hold.  A page is 64 * head_dim * 2 + 128 bytes (head_dim 128: 16,512 against 32,768) and the pool is sized from that.
+ * Everything an engine serves it serves with either format, and with every weight format, except prompt-lookup drafting:
+ * sv_generate_lookup, sv_generate_lookup_sampled and sv_cb_set_lookup (with drafts) answer SV_ENOTSUP on an SV_KV_FP8_E4M3 engine.
+ * Not a reference numerics mode: the reference keeps its cache in bf16. */
+#define SV_KV_BF16 0
+#define SV_KV_FP8_E4M3 1
+int  sv_create_kv(const sv_config* cfg, int32_t kv_dtype, sv_engine** out);
+/* the engine's KV format, the bytes of one page (64 tokens, one layer, one KV head) and of the whole pool; any pointer may be NULL */
+int  sv_kv_info(sv_engine* e, int32_t* kv_dtype, int64_t* page_bytes, int64_t* pool_bytes);
+
 /* Ingest one tensor of the reference state_dict (device pointer, dtype SV_DTYPE_*).  Linear weights
  * are repacked into MFMA fragment order in library-owned memory; the caller's tensor is only read. */
 int  sv_load_weight(sv_engine* e, const char* name, const void* dev_ptr, int32_t dtype, int32_t ndim,

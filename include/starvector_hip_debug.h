@@ -201,6 +201,10 @@ int  sv_debug_occupy_cus(sv_engine* e, int32_t blocks, int32_t lds_bytes, int32_
 int  sv_debug_gemm_trace(int32_t M, int32_t N, int32_t K, int32_t act, int32_t form, int64_t* host_out, int32_t capacity_blocks);
 int  sv_debug_kv_load(sv_engine* e, int32_t layer, const void* dev_kv, int32_t B, int32_t S, const int32_t* dev_lens,
                       sv_stream stream);
+/*   sv_debug_kv_read     tokens [first, first + count) of decode row `row` of `layer` as the attention will see them: dev_out_bf16
+     [count][2*n_kv*head_dim] (k heads | v heads, the layout sv_debug_kv_load takes).  Works for both KV formats: the bf16 pool's stored bits,
+     the e4m3 pool's deq(quant(.)) through the attention's own widening. */
+int  sv_debug_kv_read(sv_engine* e, int32_t layer, int32_t row, int32_t first, int32_t count, void* dev_out_bf16, sv_stream stream);
 int  sv_debug_attn_decode(sv_engine* e, int32_t layer, const float* dev_qkv_f32, int32_t B, void* dev_out, int32_t advance,
                           sv_stream stream);
 int  sv_debug_attn_decode_slabs(sv_engine* e, int32_t layer, const float* dev_slabs_f32, int32_t splitk, const void* dev_bias, int32_t B,

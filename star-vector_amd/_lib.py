@@ -132,6 +132,8 @@ PRODUCT_PROTOTYPES = {
     "sv_config_default_8b": (None, [C.POINTER(SvConfig)]),
     "sv_create": (_I, [C.POINTER(SvConfig), C.POINTER(_P)]),
     "sv_destroy": (_I, [_P]),
+    "sv_create_kv": (_I, [C.POINTER(SvConfig), _I, C.POINTER(_P)]),
+    "sv_kv_info": (_I, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sv_load_weight": (_I, [_P, C.c_char_p, _P, _I, _I, C.POINTER(C.c_int64), _P]),
     "sv_weights_complete": (_I, [_P]),
     "sv_weight_count": (_I, [_P]),
@@ -219,6 +221,7 @@ DEBUG_PROTOTYPES = {
     "sv_debug_occupy_cus": (_I, [_P, _I, _I, _I]),
     "sv_debug_gemm_trace": (_I, [_I, _I, _I, _I, _I, C.POINTER(C.c_int64), _I]),
     "sv_debug_kv_load": (_I, [_P, _I, _P, _I, _I, _P, _P]),
+    "sv_debug_kv_read": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "sv_debug_attn_decode": (_I, [_P, _I, _P, _I, _P, _I, _P]),
     "sv_debug_attn_decode_slabs": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P]),
     "sv_debug_attn_decode_draft": (_I, [_P, _I, _P, _I, _P, _I, _I, _P, _P]),

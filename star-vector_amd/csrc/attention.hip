@@ -13,6 +13,7 @@
 //    wave-load is one contiguous 1 KiB.  The kernel also finishes the c_attn split-K reduction
 //    (+bias, bf16 round) for its sequence and appends the new token's K/V to the cache.
 #include "kernels.h"
+#include "kv8/kv8_dev.h"
 
 namespace sv {
 
@@ -329,7 +330,9 @@ __device__ __forceinline__ size_t kv_v_offset(int D, int t64, int dv) {
 // stores per thread: 8.7 us per layer for 8.5 MB of traffic.  Tokens of the group behind the prompt get V = 0 (a V column is only ever read for keys the
 // attention admits; zero is what the decode attention leaves behind a sequence's position as well).
 // RAG: block x works for entry x of the host-built {sequence, 32-token group} list; the rows of sequence b start at its descriptor's first packed row
-template <bool RAG>
+// KVF 1: the e4m3 pool (kv8/kv8_dev.h).  K and V rows of the group both go through LDS (rows 0-31 K, 32-63 V), four threads take a row's amax
+// over its finite elements, then the codes leave as whole fragment pieces.  Tokens of the group behind the prompt get code 0 and scale byte 127.
+template <bool RAG, int KVF = 0>
 __global__ __launch_bounds__(256) void kv_write_prefill_kernel(const bf16_t* __restrict__ qkv, int row_stride, int k_off, int v_off,
                                                                char* __restrict__ pool, const int32_t* __restrict__ table,
                                                                int max_pages, int B, int S0, int D, const int32_t* __restrict__ rag_seq,
@@ -345,6 +348,66 @@ __global__ __launch_bounds__(256) void kv_write_prefill_kernel(const bf16_t* __r
     } else {
         b = blockIdx.y; tok0 = blockIdx.x * 32;
         row0 = (size_t)b * S0;
+    }
+    if constexpr (KVF != 0) {
+        uint32_t* sb = reinterpret_cast<uint32_t*>(Vs + 64 * VST);        // [64] scale bytes of the rows
+        const int NC8 = D >> 3;
+        char* page8 = pool + (size_t)table[b * max_pages + (tok0 >> 6)] * kv8_page_bytes(D);
+        for (int i = threadIdx.x; i < 32 * NC8; i += 256) {
+            const int r = i / NC8, ch = i - r * NC8, tok = tok0 + r;
+            uint4 kq = make_uint4(0u, 0u, 0u, 0u), vq = kq;
+            if (tok < S0) {
+                const bf16_t* src = qkv + (row0 + tok) * row_stride;
+                kq = *reinterpret_cast<const uint4*>(src + k_off + ch * 8);
+                vq = *reinterpret_cast<const uint4*>(src + v_off + ch * 8);
+            }
+            *reinterpret_cast<uint4*>(Vs + r * VST + ch * 8) = kq;
+            *reinterpret_cast<uint4*>(Vs + (32 + r) * VST + ch * 8) = vq;
+        }
+        __syncthreads();
+        {
+            const int row = threadIdx.x >> 2, q = threadIdx.x & 3;           // 64 rows x 4 threads
+            uint32_t m = 0u;
+            for (int d = q * (D >> 2); d < (q + 1) * (D >> 2); ++d) {
+                const uint32_t a = kv8_mag(Vs[row * VST + d]);
+                m = a > m ? a : m;
+            }
+            uint32_t o = __shfl_xor(m, 1, 64);
+            m = o > m ? o : m;
+            o = __shfl_xor(m, 2, 64);
+            m = o > m ? o : m;
+            if (q == 0) {
+                const uint32_t byte = kv8_scale_byte(m);
+                const int t64 = (tok0 + (row & 31)) & 63;
+                sb[row] = byte;
+                *reinterpret_cast<unsigned char*>(page8 + (row < 32 ? kv8_kscale_offset(D, t64) : kv8_vscale_offset(D, t64))) = (unsigned char)byte;
+            }
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < 32 * NC8; i += 256) {
+            const int r = i / NC8, ch = i - r * NC8;
+            const uint4 v = *reinterpret_cast<const uint4*>(Vs + r * VST + ch * 8);
+            *reinterpret_cast<uint2*>(page8 + kv8_k_offset(D, (tok0 + r) & 63, ch * 8)) = kv8_code8(v, sb[r]);
+        }
+        const int g8 = (tok0 >> 5) & 1;
+        for (int i = threadIdx.x; i < (D >> 5) * 64; i += 256) {
+            const int t2 = i >> 6, l = i & 63, dl = l & 15, c = l >> 4;
+            uint32_t w[4];
+#pragma unroll
+            for (int tl = 0; tl < 2; ++tl)
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    uint32_t word = 0u;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int ka = 16 * h + 4 * c + r;                   // element e = 4 h + r of the fragment
+                        word |= kv8_code(Vs[(32 + ka) * VST + 16 * (2 * t2 + tl) + dl], sb[32 + ka]) << (8 * r);
+                    }
+                    w[2 * tl + h] = word;
+                }
+            *reinterpret_cast<uint4*>(page8 + (size_t)64 * D + ((size_t)((g8 * (D >> 5) + t2) * 64 + l)) * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+        return;
     }
     const int NC = D >> 3;
     const int page_bytes = kv_page_bytes(D);
@@ -400,17 +463,28 @@ void launch_rope_prefill(bf16_t* qkv, int row_stride, int rows, int S0, int n_he
     rope_prefill_kernel<<<blocks, 256, 0, st>>>(qkv, row_stride, rows, S0, n_heads, head_dim, cos_t, sin_t, row_pos);
 }
 
+static size_t kv8_write_smem(int head_dim) { return (size_t)64 * (head_dim + 8) * 2 + 64 * 4; }   // K and V rows of a 32-token group + 64 scale bytes (as words)
 void launch_kv_write_prefill(const bf16_t* qkv, int row_stride, int k_off, int v_off, char* pool_layer,
                              const int32_t* block_table, int max_pages, int B, int S0, int head_dim,
-                             hipStream_t st) {
+                             hipStream_t st, int kv_fmt) {
     dim3 grid((S0 + 31) / 32, B);
+    if (kv_fmt) {
+        kv_write_prefill_kernel<false, 1><<<grid, 256, kv8_write_smem(head_dim), st>>>(qkv, row_stride, k_off, v_off, pool_layer, block_table,
+                                                                                       max_pages, B, S0, head_dim, nullptr, nullptr);
+        return;
+    }
     kv_write_prefill_kernel<false><<<grid, 256, (size_t)32 * (head_dim + 8) * 2, st>>>(qkv, row_stride, k_off, v_off, pool_layer, block_table,
                                                                                       max_pages, B, S0, head_dim, nullptr, nullptr);
 }
 void launch_kv_write_prefill_ragged(const bf16_t* qkv, int row_stride, int k_off, int v_off, char* pool_layer,
                                     const int32_t* block_table, int max_pages, const int32_t* rag_seq, const int32_t* rag_blocks,
-                                    int n_blocks, int head_dim, hipStream_t st) {
+                                    int n_blocks, int head_dim, hipStream_t st, int kv_fmt) {
     if (n_blocks < 1) return;
+    if (kv_fmt) {
+        kv_write_prefill_kernel<true, 1><<<n_blocks, 256, kv8_write_smem(head_dim), st>>>(qkv, row_stride, k_off, v_off, pool_layer, block_table,
+                                                                                          max_pages, 0, 0, head_dim, rag_seq, rag_blocks);
+        return;
+    }
     kv_write_prefill_kernel<true><<<n_blocks, 256, (size_t)32 * (head_dim + 8) * 2, st>>>(qkv, row_stride, k_off, v_off, pool_layer, block_table,
                                                                                          max_pages, 0, 0, head_dim, rag_seq, rag_blocks);
 }
@@ -471,7 +545,10 @@ struct AttnDecodeKernarg { const float* ws; const bf16_t* bias; const int32_t* p
                            int max_pages; unsigned geom; int ldws; unsigned rows_heads; size_t kv_head_stride; int window;
                            AttnDecodeArgs p; };     // the kernarg segment
 // NS: the slabs a thread requests (4 or 8, the launcher's choice for splitk <= 4 / <= 8): a compile-time count of loads in flight.
-template <int D, int NS>
+// KVF: the pool's format.  0: bf16 fragments, everything as written above.  1: e4m3 codes + one power-of-two scale per key and head (kv8/
+// kv8_dev.h): the two register buffers hold a group's raw codes and scale bytes (half the bytes in flight), a group is widened to the bf16
+// fragments deq(quant(.)) when its turn comes -- exact -- and process() is the bf16 cache's; the append quantises the new token's row.
+template <int D, int NS, int KVF = 0>
 __global__ __launch_bounds__(AD_WAVES * 64) void attn_decode_kernel(const float* ws_, const bf16_t* bias_, const int32_t* positions_, const int32_t* block_table_,
                                                                      char* pool_layer_, int max_pages_, unsigned geom_, int ldws_, unsigned rows_heads_,
                                                                      size_t kv_head_stride_, int window_, AttnDecodeArgs p_unused) {
@@ -566,7 +643,7 @@ __global__ __launch_bounds__(AD_WAVES * 64) void attn_decode_kernel(const float*
     };
 
     const int32_t* table = block_table_ + (size_t)b * max_pages_;
-    const int page_bytes = kv_page_bytes(D);
+    const int page_bytes = KVF != 0 ? kv8_page_bytes(D) : kv_page_bytes(D);
     char* pool = nullptr;
     int tpre = 0;
     auto page_of = [&](int grp) -> int {                   // grp is wave-uniform
@@ -574,7 +651,7 @@ __global__ __launch_bounds__(AD_WAVES * 64) void attn_decode_kernel(const float*
         return pi < 64 ? __builtin_amdgcn_readlane(tpre, pi) : table[pi];
     };
     int L = 0, ngroups = 0, win0 = 0, g0 = 0, act = 1, stride = AD_WAVES, g = 0;
-    KvFrags<D> fa, fb;
+    typename std::conditional<KVF != 0, Kv8Raw<D>, KvFrags<D>>::type fa, fb;
     long long t_kvreq = 0;                             // position + table landed, first KV group requested
     AttnDecodeArgs p;
     // AttnDecodeArgs::poison: every block of the launch stores 16 bytes per thread of the pattern -- the inactive splits before they
@@ -674,6 +751,34 @@ __global__ __launch_bounds__(AD_WAVES * 64) void attn_decode_kernel(const float*
 
     // split 0 appends the new token's K / V to the cache (for FUTURE steps; in this launch every block
     // patches the new token into its fragments from LDS, so no block depends on another block's store)
+    if constexpr (KVF != 0) {
+        // e4m3 pool: the waves of the K row and those of the V row (wave-uniform: D is a multiple of 64) take the row's amax over its finite
+        // elements -- a lane's 16-byte piece of the LDS row, then across the D / 8 pieces -- and every thread writes the code of its column;
+        // the thread of column 0 writes the row's scale byte
+        if (split == 0 && tid < 2 * D) {
+            const bool isv = tid >= D;
+            const uint4 pc = *reinterpret_cast<const uint4*>(kv_new + (isv ? D : 0) + 8 * (lane & (D / 8 - 1)));
+            const uint32_t pw[4] = {pc.x, pc.y, pc.z, pc.w};
+            uint32_t m = 0u;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const uint32_t a0 = kv8_mag(pw[i] & 0xffffu), a1 = kv8_mag(pw[i] >> 16);
+                m = a0 > m ? a0 : m;
+                m = a1 > m ? a1 : m;
+            }
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) {
+                const uint32_t x = __shfl_xor(m, o, 64);
+                m = x > m ? x : m;
+            }
+            const uint32_t byte = kv8_scale_byte(m);
+            char* page = pool + (size_t)table[pos >> 6] * page_bytes;
+            const int t64 = pos & 63;
+            const int d = isv ? tid - D : tid;
+            *reinterpret_cast<unsigned char*>(page + (isv ? kv8_v_offset(D, t64, d) : kv8_k_offset(D, t64, d))) = (unsigned char)kv8_code(kv_new[tid], byte);
+            if (d == 0) *reinterpret_cast<unsigned char*>(page + (isv ? kv8_vscale_offset(D, t64) : kv8_kscale_offset(D, t64))) = (unsigned char)byte;
+        }
+    } else
     if (split == 0 && tid < 2 * D) {
         char* page = pool + (size_t)table[pos >> 6] * page_bytes;
         const int t64 = pos & 63;
@@ -778,11 +883,11 @@ __global__ __launch_bounds__(AD_WAVES * 64) void attn_decode_kernel(const float*
     while (g < ngroups) {
         const int g1 = g + stride;
         if (g1 < ngroups) load_group<D>(fb, pool, page_of(g1), page_bytes, g1, lane);
-        process(fa, g);
+        if constexpr (KVF != 0) { KvFrags<D> w; kv8_widen_group<D>(fa, w); process(w, g); } else process(fa, g);
         if (g1 >= ngroups) break;
         const int g2 = g1 + stride;
         if (g2 < ngroups) load_group<D>(fa, pool, page_of(g2), page_bytes, g2, lane);
-        process(fb, g1);
+        if constexpr (KVF != 0) { KvFrags<D> w; kv8_widen_group<D>(fb, w); process(w, g1); } else process(fb, g1);
         g = g2;
     }
 
@@ -941,9 +1046,11 @@ static size_t attn_decode_smem(int D) {
 // dynamic LDS above the 64 KiB default needs an explicit opt-in.  Done once at engine creation (never
 // inside a stream capture)
 int init_attention_kernels() {
-    const void* k128[2] = {reinterpret_cast<const void*>(&attn_decode_kernel<128, 4>), reinterpret_cast<const void*>(&attn_decode_kernel<128, 8>)};
-    const void* k64[2] = {reinterpret_cast<const void*>(&attn_decode_kernel<64, 4>), reinterpret_cast<const void*>(&attn_decode_kernel<64, 8>)};
-    for (int i = 0; i < 2; ++i) {
+    const void* k128[4] = {reinterpret_cast<const void*>(&attn_decode_kernel<128, 4>), reinterpret_cast<const void*>(&attn_decode_kernel<128, 8>),
+                           reinterpret_cast<const void*>(&attn_decode_kernel<128, 4, 1>), reinterpret_cast<const void*>(&attn_decode_kernel<128, 8, 1>)};
+    const void* k64[4] = {reinterpret_cast<const void*>(&attn_decode_kernel<64, 4>), reinterpret_cast<const void*>(&attn_decode_kernel<64, 8>),
+                          reinterpret_cast<const void*>(&attn_decode_kernel<64, 4, 1>), reinterpret_cast<const void*>(&attn_decode_kernel<64, 8, 1>)};
+    for (int i = 0; i < 4; ++i) {
         hipError_t r = hipFuncSetAttribute(k128[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_decode_smem(128));
         if (r != hipSuccess) return (int)r;
         r = hipFuncSetAttribute(k64[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_decode_smem(64));
@@ -952,13 +1059,13 @@ int init_attention_kernels() {
     return 0;
 }
 
-template <int D, int NS>
+template <int D, int NS, int KVF = 0>
 static void launch_attn_decode_as(const AttnDecodeArgs& a, dim3 grid, size_t smem, hipStream_t st) {
     const int gpb = a.groups_per_block > 0 ? a.groups_per_block : AD_GROUPS_PER_BLOCK;
     // the packed leading parameters (AttnDecodeKernarg): 8 bits each for n_kv, the split cap, the groups per block and splitk, 16 for rows_ws and H
     const unsigned geom = (unsigned)a.n_kv | (unsigned)grid.y << 8 | (unsigned)gpb << 16 | (unsigned)(a.splitk < 1 ? 1 : a.splitk) << 24;
     const unsigned rows_heads = (unsigned)a.rows_ws | (unsigned)a.H << 16;
-    attn_decode_kernel<D, NS><<<grid, AD_WAVES * 64, smem, st>>>(a.ws, a.bias, a.positions, a.block_table, a.pool_layer, a.max_pages, geom, a.ldws, rows_heads,
+    attn_decode_kernel<D, NS, KVF><<<grid, AD_WAVES * 64, smem, st>>>(a.ws, a.bias, a.positions, a.block_table, a.pool_layer, a.max_pages, geom, a.ldws, rows_heads,
                                                                   a.kv_head_stride, a.window, a);
 }
 
@@ -967,6 +1074,16 @@ void launch_attn_decode(const AttnDecodeArgs& a, hipStream_t st) {
     // grid.y = the engine's split cap, not AD_SPLIT: the splits above it never work, and dispatching 8-wave blocks that exit
     // at once is not free (B = 32: 256 of 512 blocks)
     dim3 grid(a.B * a.n_kv, a.max_splits < 1 ? 1 : (a.max_splits > AD_SPLIT ? AD_SPLIT : a.max_splits));
+    if (a.kv_fmt) {
+        if (a.head_dim == 128) {
+            if (a.splitk <= 4) launch_attn_decode_as<128, 4, 1>(a, grid, smem, st);
+            else launch_attn_decode_as<128, 8, 1>(a, grid, smem, st);
+        } else {
+            if (a.splitk <= 4) launch_attn_decode_as<64, 4, 1>(a, grid, smem, st);
+            else launch_attn_decode_as<64, 8, 1>(a, grid, smem, st);
+        }
+        return;
+    }
     if (a.head_dim == 128) {
         if (a.splitk <= 4) launch_attn_decode_as<128, 4>(a, grid, smem, st);
         else launch_attn_decode_as<128, 8>(a, grid, smem, st);

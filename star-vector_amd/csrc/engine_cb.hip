@@ -649,6 +649,8 @@ extern "C" int sv_cb_set_lookup(sv_engine* e, const sv_lookup* lookup) {
     std::lock_guard<std::mutex> lock(e->mu);
     if (e->cb_active) return fail(SV_ESTATE, "sv_cb_set_lookup: a continuous batch is active (the setting changes before the first admit or after sv_cb_reset)");
     const int K = lk.num_draft_tokens;
+    if (K > 0 && e->kv_dtype != SV_KV_BF16)
+        return fail(SV_ENOTSUP, "sv_cb_set_lookup: prompt-lookup drafting is not built for the fp8_e4m3 KV cache (the drafts' K / V pre-write is bf16)");
     if (e->cfg.max_batch / (K + 1) < 1)
         return fail(SV_ENOTSUP, "sv_cb_set_lookup: num_draft_tokens %d + 1 rows per slot exceed engine max_batch %d", K, e->cfg.max_batch);
     if (K == e->cb_K && (K == 0 || (lk.max_ngram == e->cb_max_ngram && lk.min_ngram == e->cb_min_ngram))) return 0;

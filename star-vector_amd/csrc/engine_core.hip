@@ -402,8 +402,26 @@ extern "C" int sv_destroy(sv_engine* e) {
     return 0;
 }
 
+static int create_engine(const sv_config* cfg, int32_t kv_dtype, sv_engine** out);
 extern "C" int sv_create(const sv_config* cfg, sv_engine** out) {
     if (!cfg || !out) return fail(SV_EINVAL, "sv_create: null argument");
+    return create_engine(cfg, SV_KV_BF16, out);
+}
+// sv_create with the KV-cache format chosen (sv_config is pinned at 96 bytes: the format travels beside it)
+extern "C" int sv_create_kv(const sv_config* cfg, int32_t kv_dtype, sv_engine** out) {
+    if (!cfg || !out) return fail(SV_EINVAL, "sv_create_kv: null argument");
+    if (kv_dtype != SV_KV_BF16 && kv_dtype != SV_KV_FP8_E4M3)
+        return fail(SV_EINVAL, "sv_create_kv: kv_dtype %d is not SV_KV_BF16 (0) or SV_KV_FP8_E4M3 (1)", kv_dtype);
+    return create_engine(cfg, kv_dtype, out);
+}
+extern "C" int sv_kv_info(sv_engine* e, int32_t* kv_dtype, int64_t* page_bytes, int64_t* pool_bytes) {
+    if (!e) return fail(SV_EINVAL, "sv_kv_info: null engine");
+    if (kv_dtype) *kv_dtype = e->kv_dtype;
+    if (page_bytes) *page_bytes = e->page_bytes;
+    if (pool_bytes) *pool_bytes = (int64_t)(e->layer_stride * (size_t)e->cfg.n_layer);
+    return 0;
+}
+static int create_engine(const sv_config* cfg, int32_t kv_dtype, sv_engine** out) {
     const sv_config& c = *cfg;
     if (c.image_size % c.patch_size) return fail(SV_EINVAL, "image_size %% patch_size != 0");
     if (c.vit_width % c.vit_heads || c.hidden % c.n_head) return fail(SV_EINVAL, "width %% heads != 0");
@@ -437,6 +455,7 @@ extern "C" int sv_create(const sv_config* cfg, sv_engine** out) {
     sv_engine* e = new sv_engine();
     e->cfg = c;
     e->exp = exp;
+    e->kv_dtype = kv_dtype;
     e->vdh = vdh; e->dh = dh; e->v2 = v2; e->nkv = nkv;
     const int G = c.image_size / c.patch_size;
     e->NP = G * G; e->T = e->NP + (v2 ? 0 : 1);
@@ -607,7 +626,7 @@ extern "C" int sv_create(const sv_config* cfg, sv_engine** out) {
     A(dalloc(e, &e->tail_cnt, (size_t)SV_TAIL_TILES));          // zeroed: the tickets re-arm themselves
     A(dalloc(e, &e->fin_cnt, 64));                               // zeroed: SkinnyArgs::fin_cnt
 
-    e->page_bytes = kv_page_bytes(dh);
+    e->page_bytes = kv_page_bytes_of(e->kv_dtype, dh);
     e->pages_per_seq = (c.max_seq_len + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS;
     e->num_pages = c.max_batch * e->pages_per_seq;
     e->trash_page = e->num_pages;                 // one page past the allocatable ones: free slots of a continuous batch write there

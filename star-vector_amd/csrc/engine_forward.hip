@@ -335,7 +335,7 @@ int sveng::prefill_forward(sv_engine* e, const bf16_t* embeds, int B, int S0, hi
         for (int kh = 0; kh < nkv; ++kh)
             launch_kv_write_prefill(e->pqkv, QKV, QD + kh * dh, QD + nkv * dh + kh * dh,
                                     e->kv_pool + (size_t)i * e->layer_stride + (size_t)kh * e->kv_head_stride,
-                                    table, e->pages_per_seq, B, S0, dh, st);
+                                    table, e->pages_per_seq, B, S0, dh, st, e->kv_dtype);
         if (prune_last && i + 1 == c.n_layer) {
             at.last_rows = 1;
             launch_attn_prefill(at, st);
@@ -549,7 +549,7 @@ int sveng::prefill_forward_packed(sv_engine* e, const PackedPlan& p, const int32
         for (int kh = 0; kh < (len(PL_KV_BLOCKS) > 0 ? nkv : 0); ++kh)      // (no blocks: the pass writes no page)
             launch_kv_write_prefill_ragged(e->pqkv, QKV, QD + kh * dh, QD + nkv * dh + kh * dh,
                                            e->kv_pool + (size_t)i * e->layer_stride + (size_t)kh * e->kv_head_stride,
-                                           table, e->pages_per_seq, d_desc, dev(PL_KV_BLOCKS), len(PL_KV_BLOCKS) / 2, dh, st);
+                                           table, e->pages_per_seq, d_desc, dev(PL_KV_BLOCKS), len(PL_KV_BLOCKS) / 2, dh, st, e->kv_dtype);
         if (prune_last && i + 1 == c.n_layer) {
             // only the last row of every sequence goes on (see prefill_forward): its query tile, then B compact rows
             at.rag_seq = d_desc; at.rag_blocks = dev(PL_LAST_TILES); at.rag_nblocks = len(PL_LAST_TILES) / 2;
@@ -618,6 +618,7 @@ void sveng::attn_decode_args(sv_engine* e, int layer, int B, const float* ws, in
     ad.max_splits = attn_max_splits(e);
     ad.groups_per_block = attn_groups_per_block(e);
     ad.n_kv = e->nkv; ad.kv_head_stride = e->kv_head_stride; ad.rope_cos = e->rope_cos; ad.rope_sin = e->rope_sin;
+    ad.kv_fmt = e->kv_dtype;
 }
 
 // the K / V pre-write of a verification step (lookup/lookup.hip) over exactly what the attention launch `ad` reads

@@ -889,6 +889,7 @@ static int lookup_call(const char* who, bool sampled, sv_engine* e, const void* 
     if (lk.min_ngram == 0) lk.min_ngram = 1;
     GenCall c{who, GC_ARGS, dev_embeds_packed, B, S0, host_lens, 1, sp, nullptr, nullptr, nullptr, nullptr, dev_out_tokens, n_generated, stream};
     SVCHECK(check_gen_call(c));
+    if (e && e->kv_dtype != SV_KV_BF16) return fail(SV_ENOTSUP, "%s: prompt-lookup drafting is not built for the fp8_e4m3 KV cache (the drafts' K / V pre-write is bf16)", who);
     if (sp->do_sample && !sampled) return fail(SV_ENOTSUP, "%s: do_sample is not built (verification is greedy: the drafts are compared with the arg-max)", who);
     if (sp->num_beams > 1) return fail(SV_ENOTSUP, "%s: num_beams %d is not built (beam rows reorder their caches)", who, sp->num_beams);
     if (!sampled && sp->repetition_penalty > 0.f && sp->repetition_penalty != 1.0f)

@@ -185,6 +185,7 @@ struct sv_engine {
     char* kv_pool = nullptr;
     size_t layer_stride = 0;
     int pages_per_seq = 0, num_pages = 0, page_bytes = 0;
+    int kv_dtype = 0;               // SV_KV_BF16 / SV_KV_FP8_E4M3 (sv_create_kv): the format of kv_pool's pages, page_bytes follows from it
     int32_t* block_table = nullptr;
     std::vector<int> free_pages;
     // shared prompt pass (sv_generate_shared / sv_cb_admit_shared): pinned image of the prompt-pass table + the fork launch's descriptors, their

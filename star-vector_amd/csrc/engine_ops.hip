@@ -108,7 +108,7 @@ extern "C" int sv_debug_kv_load(sv_engine* e, int32_t layer, const void* dev_kv,
         for (int kh = 0; kh < nkv; ++kh)
             launch_kv_write_prefill((const bf16_t*)dev_kv, 2 * nkv * dh, kh * dh, nkv * dh + kh * dh,
                                     e->kv_pool + (size_t)layer * e->layer_stride + (size_t)kh * e->kv_head_stride,
-                                    e->block_table, e->pages_per_seq, B, S, dh, st);
+                                    e->block_table, e->pages_per_seq, B, S, dh, st, e->kv_dtype);
     if (dev_lens) HIPCHECK(hipMemcpyAsync(e->positions, dev_lens, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     else fill_i32(e->positions, S, B, st);
     e->cached_B = B;
@@ -158,6 +158,26 @@ static int debug_attn_decode(sv_engine* e, const char* who, int32_t layer, const
     return 0;
 }
 
+// tokens [first, first + count) of decode row `row` of `layer`, as the attention will see them: bf16 [count][2 * n_kv * head_dim] (k heads | v heads),
+// from a pool of either format
+extern "C" int sv_debug_kv_read(sv_engine* e, int32_t layer, int32_t row, int32_t first, int32_t count, void* dev_out_bf16, sv_stream stream) {
+    if (!e || (!dev_out_bf16 && count > 0)) return fail(SV_EINVAL, "sv_debug_kv_read: null argument");
+    const sv_config& c = e->cfg;
+    if (layer < 0 || layer >= c.n_layer || row < 0 || row >= c.max_batch || first < 0 || count < 0 || (long long)first + count > c.max_seq_len)
+        return fail(SV_EINVAL, "sv_debug_kv_read: bad layer %d / row %d / tokens [%d, %d + %d) (max_batch %d, max_seq_len %d)", layer, row, first, first, count,
+                    c.max_batch, c.max_seq_len);
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIPCHECK(hipSetDevice(c.device));
+    hipStream_t st = (hipStream_t)stream;
+    KvReadArgs a;
+    a.pool_layer = e->kv_pool + (size_t)layer * e->layer_stride; a.kv_head_stride = e->kv_head_stride;
+    a.table_row = e->block_table + (size_t)row * e->pages_per_seq;
+    a.n_kv = e->nkv; a.head_dim = e->dh; a.first = first; a.count = count; a.kv_fmt = e->kv_dtype; a.out = (bf16_t*)dev_out_bf16;
+    launch_kv_read(a, st);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
 extern "C" int sv_debug_attn_decode(sv_engine* e, int32_t layer, const float* dev_qkv_f32, int32_t B, void* dev_out, int32_t advance,
                                     sv_stream stream) {
     return debug_attn_decode(e, "sv_debug_attn_decode", layer, dev_qkv_f32, 1, nullptr, B, dev_out, advance, stream);
@@ -179,6 +199,7 @@ extern "C" int sv_debug_attn_decode_draft(sv_engine* e, int32_t layer, const flo
                                           int32_t K1, void* dev_out, sv_stream stream) {
     const char* who = "sv_debug_attn_decode_draft";
     if (!e || !dev_slabs || !dev_out) return fail(SV_EINVAL, "%s: null argument", who);
+    if (e->kv_dtype != SV_KV_BF16) return fail(SV_ENOTSUP, "%s: the K / V pre-write of a verification step is not built for the fp8_e4m3 KV cache", who);
     const sv_config& c = e->cfg;
     if (layer < 0 || layer >= c.n_layer) return fail(SV_EINVAL, "%s: bad layer %d", who, layer);
     if (splitk != 1 && splitk != 2 && splitk != 4 && splitk != 8) return fail(SV_EINVAL, "%s: splitk %d is not 1, 2, 4 or 8", who, splitk);

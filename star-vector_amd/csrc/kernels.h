@@ -310,15 +310,18 @@ void launch_attn_prefill(const AttnPrefillArgs& a, hipStream_t st);
 #define SV_PAGE_TOKENS 64
 struct KvLayout { int head_dim; int page_bytes; };
 __host__ __device__ inline int kv_page_bytes(int head_dim) { return SV_PAGE_TOKENS * head_dim * 2 * 2; }
+// the e4m3 cache (kv_fmt 1 = SV_KV_FP8_E4M3; csrc/kv8/kv8_dev.h): one code per element, one scale byte per token for K and for V
+__host__ __device__ inline int kv8_page_bytes(int head_dim) { return SV_PAGE_TOKENS * head_dim * 2 + 2 * SV_PAGE_TOKENS; }
+inline int kv_page_bytes_of(int kv_fmt, int head_dim) { return kv_fmt ? kv8_page_bytes(head_dim) : kv_page_bytes(head_dim); }
 
 // scatter prefill K/V rows (from the c_attn output) into the paged cache
 void launch_kv_write_prefill(const bf16_t* qkv, int row_stride, int k_off, int v_off, char* pool_layer,
                              const int32_t* block_table, int max_pages, int B, int S0, int head_dim,
-                             hipStream_t st);
+                             hipStream_t st, int kv_fmt = 0);
 // ragged form: rag_blocks [n_blocks] = {sequence, 32-token group of that sequence}; page and slot from the row's own sequence and position
 void launch_kv_write_prefill_ragged(const bf16_t* qkv, int row_stride, int k_off, int v_off, char* pool_layer,
                                     const int32_t* block_table, int max_pages, const int32_t* rag_seq, const int32_t* rag_blocks,
-                                    int n_blocks, int head_dim, hipStream_t st);
+                                    int n_blocks, int head_dim, hipStream_t st, int kv_fmt = 0);
 
 struct AttnDecodeArgs {
     const float* ws; int splitk; int ldws; int rows_ws;   // c_attn output as fp32 split-K slabs [splitk][rows][ldws], summed here in slab order
@@ -342,6 +345,7 @@ struct AttnDecodeArgs {
     void* poison; unsigned poison_bytes;                   // optional: a buffer the launch fills with 0xFF bytes, 16 per thread, before anything else (the
                                                            // "not written yet" pattern of the fused MLP launch later in the layer): this kernel is bound by
                                                            // latencies, a store per thread costs it nothing -- in gemm_cols_resid_kernel it cost 0.5 us
+    int kv_fmt;                                            // the pool's format (host side only: picks the instantiation): 0 bf16, 1 e4m3 + per-key scales
 };
 // in-place rotary embedding of the q and k heads of a prefill c_attn output (rotate_half convention)
 void launch_rope_prefill(bf16_t* qkv, int row_stride, int rows, int S0, int n_heads, int head_dim,
@@ -352,6 +356,10 @@ int launch_xcc_probe(int32_t* out, int blocks, int heavy, hipStream_t st);
 int launch_occupy(int blocks, int lds_bytes, int ticks, hipStream_t st);     // test tenant: pins LDS of `blocks` CUs for ticks x 10 ns
 size_t attn_decode_part_floats(int head_dim);            // floats of `part` per sequence
 int init_attention_kernels();   // returns a hipError_t value (0 = ok)
+// tokens [first, first + count) of one block-table row as the decode attention sees them: out bf16 [count][2 * n_kv * head_dim] (k heads | v heads),
+// either pool format (csrc/kv8/kv8.hip)
+struct KvReadArgs { const char* pool_layer; size_t kv_head_stride; const int32_t* table_row; int n_kv, head_dim, first, count, kv_fmt; bf16_t* out; };
+void launch_kv_read(const KvReadArgs& a, hipStream_t st);
 
 // ---- sampling -----------------------------------------------------------------------------------
 // greedy selection: per-slice winners (pval/pidx: [B][8]) then a merge (standalone, or inside finish_step)

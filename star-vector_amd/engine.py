@@ -85,6 +85,8 @@ class EngineConfig:
     exclusive_device: object = False # False / True / "auto" (2: on until a fused launch gives up, then off for good and the call re-run: sv_config.exclusive_device).
                                      # True: this engine alone launches kernels on its GPU while decoding (one process per GPU): enables the
                                      # all-blocks-resident fused launches (include/starvector_hip.h sv_config.exclusive_device); same tokens
+    kv_dtype: str = "bf16"           # the paged KV cache's format: "bf16", or "fp8_e4m3" -- e4m3 codes and one power-of-two scale per key and
+                                     # head, half the pool and half the decode attention's stream (sv_create_kv; not a reference numerics mode)
 
     @property
     def query_length(self) -> int:
@@ -174,6 +176,39 @@ def weight_dtype_code(weight_dtype) -> int:
     return WEIGHT_DTYPES[resolve_weight_dtype(weight_dtype)]
 
 
+KV_DTYPES = {"bf16": 0, "fp8_e4m3": 1}                           # SV_KV_*
+_KV_DTYPE_ALIASES = {"fp8": "fp8_e4m3", "bfloat16": "bf16", "auto": "bf16"}
+
+
+def resolve_kv_dtype(kv_dtype=None) -> str:
+    """The canonical name of a KV-cache format: "bf16" (also "auto") or "fp8_e4m3" (also "fp8").  None = the environment's SV_KV_DTYPE,
+    else "bf16"."""
+    if kv_dtype is None:
+        kv_dtype = os.environ.get("SV_KV_DTYPE") or "bf16"
+    name = str(kv_dtype).lower()
+    name = _KV_DTYPE_ALIASES.get(name, name)
+    if name not in KV_DTYPES:
+        raise ValueError(f"kv_dtype must be one of {sorted(KV_DTYPES)} (or 'fp8' / 'auto'), got {kv_dtype!r}")
+    return name
+
+
+def kv_dtype_code(kv_dtype) -> int:
+    return KV_DTYPES[resolve_kv_dtype(kv_dtype)]
+
+
+def kv_page_bytes(kv_dtype, head_dim: int) -> int:
+    """Bytes of one KV page (64 tokens of one layer and KV head): bf16 K | V, or e4m3 codes + one scale byte per token for K and for V."""
+    return 64 * head_dim * 2 + 128 if kv_dtype_code(kv_dtype) else 64 * head_dim * 2 * 2
+
+
+def kv_pool_bytes(cfg: "EngineConfig") -> int:
+    """Bytes of the KV pool an engine of this configuration allocates (what sv_kv_info reports): per layer and KV head, the pages of
+    max_batch sequences of max_seq_len tokens and one more (the page free slots of a continuous batch write to)."""
+    pages = cfg.max_batch * ((cfg.max_seq_len + 63) // 64) + 1
+    n_kv = cfg.n_kv_head if cfg.arch == "v2" else 1
+    return cfg.n_layer * n_kv * pages * kv_page_bytes(cfg.kv_dtype, cfg.hidden // cfg.n_head)
+
+
 def _exclusive_code(v) -> int:
     """sv_config.exclusive_device: 0 (shared GPU), 1 (this engine owns it), 2 ("auto": optimistic, falls back for good at the first give-up)."""
     if isinstance(v, str):
@@ -203,7 +238,12 @@ class HipEngine:
                      int(cfg.sliding_window) if cfg.arch == "v2" else 0,
                      weight_dtype_code(cfg.weight_dtype), _exclusive_code(getattr(cfg, "exclusive_device", False)))
         h = C.c_void_p()
-        check(self.lib.sv_create(C.byref(c), C.byref(h)), "sv_create")
+        # the default spelling takes sv_create; any other one ("fp8_e4m3", or "auto" / "bfloat16" for the bf16 cache) sv_create_kv with its code
+        kv_name = getattr(cfg, "kv_dtype", "bf16")
+        if kv_name == "bf16":
+            check(self.lib.sv_create(C.byref(c), C.byref(h)), "sv_create")
+        else:
+            check(self.lib.sv_create_kv(C.byref(c), kv_dtype_code(kv_name), C.byref(h)), "sv_create_kv")
         self._h = h
         self._dev = torch.device("cuda", self.device)
         # One multi-call sequence at a time per engine: a padded batch run as slots (cb_reset ... cb_reset), a classic
@@ -211,6 +251,12 @@ class HipEngine:
         # threads from interleaving their call sequences (thread B's cb_reset would release thread A's slots).
         self.call_lock = threading.RLock()
         self._cb_lp_k = {}                   # slot -> the k its current holder records with (cb_read_logprobs sizes its buffers by it)
+
+    def kv_info(self) -> dict:
+        """The KV cache's format, the bytes of one page (64 tokens of one layer and KV head) and of the whole pool (sv_kv_info)."""
+        fmt, page, pool = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        check(self.lib.sv_kv_info(self._h, C.byref(fmt), C.byref(page), C.byref(pool)), "sv_kv_info")
+        return {"kv_dtype": {v: k for k, v in KV_DTYPES.items()}[fmt.value], "page_bytes": page.value, "pool_bytes": pool.value}
 
     def close(self):
         if getattr(self, "_h", None):
@@ -979,6 +1025,14 @@ class HipEngine:
         check(self.lib.sv_debug_kv_load(self._h, int(layer), _ptr(kv) if S > 0 else C.c_void_p(0), B, S, _ptr(lens), _stream()),
               "sv_debug_kv_load")
         torch.cuda.current_stream().synchronize()          # the caller may free `kv` right away
+
+    def debug_kv_read(self, layer: int, row: int, first: int, count: int) -> torch.Tensor:
+        """Tokens [first, first + count) of decode row `row` of `layer` as the attention will see them (sv_debug_kv_read): bf16
+        [count, 2 * n_kv_head * head_dim] (k heads | v heads), from a pool of either format."""
+        width = 2 * (self.cfg.n_kv_head if self.cfg.arch == "v2" else 1) * (self.cfg.hidden // self.cfg.n_head)
+        out = torch.empty(int(count), width, dtype=torch.bfloat16, device=self._dev)
+        check(self.lib.sv_debug_kv_read(self._h, int(layer), int(row), int(first), int(count), _ptr(out), _stream()), "sv_debug_kv_read")
+        return out
 
     def debug_attn_decode(self, layer: int, qkv: torch.Tensor, advance: bool = True) -> torch.Tensor:
         """One launch of the decode attention of `layer` for the new token whose c_attn output is qkv [B, QKV] float32 (before

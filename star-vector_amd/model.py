@@ -29,7 +29,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 import torch.nn as nn
 
-from .engine import EngineConfig, HipEngine, resolve_weight_dtype
+from .engine import EngineConfig, HipEngine, resolve_kv_dtype, resolve_weight_dtype
 
 # Set while the calling thread runs an exclusive job of a ContinuousBatcher (beam search, multi-row batches): inside it the
 # mirror talks to the engine directly; every OTHER thread keeps going through the batcher's queue.
@@ -103,7 +103,8 @@ class StarVectorConfig:
                  # sub-model configs, and the batch/sequence capacity the KV pool is sized for
                  n_inner: Optional[int] = None, n_positions: Optional[int] = None, added_tokens: Optional[int] = None,
                  vit_width: int = 1024, vit_layers: int = 23, vit_heads: int = 16, patch_size: int = 14,
-                 max_batch: int = 32, exclusive_device: Optional[bool] = None, weight_dtype: Optional[str] = None, **kwargs):
+                 max_batch: int = 32, exclusive_device: Optional[bool] = None, weight_dtype: Optional[str] = None,
+                 kv_cache_dtype: Optional[str] = None, **kwargs):
         self.starcoder_model_name = starcoder_model_name
         self.image_encoder_type = image_encoder_type
         self.adapter_norm = adapter_norm
@@ -135,6 +136,9 @@ class StarVectorConfig:
         # decoder weight format: "bf16" (the reference's precision), "fp8_e4m3" / "fp8", "mxfp4" (EngineConfig.weight_dtype).  None = the
         # environment's SV_WEIGHT_DTYPE, else "bf16"
         self.weight_dtype = resolve_weight_dtype(weight_dtype)
+        # KV-cache format: "bf16" / "auto" (the reference's precision) or "fp8_e4m3" / "fp8" (EngineConfig.kv_dtype).  None = the environment's
+        # SV_KV_DTYPE, else "bf16"
+        self.kv_cache_dtype = resolve_kv_dtype(kv_cache_dtype)
         for k, v in kwargs.items():
             setattr(self, k, v)
 
@@ -181,7 +185,8 @@ class StarVectorConfig:
                                 # everywhere) show W.  `window_semantics` picks which one the engine's window (= number of visible
                                 # keys) mirrors: "flash_attention_2" (default: what the reference runs) or "sdpa".
                                 sliding_window=self._visible_keys(g("sliding_window", 4096), g("window_semantics", "flash_attention_2")),
-                                exclusive_device=self.exclusive_device, weight_dtype=resolve_weight_dtype(self.weight_dtype))
+                                exclusive_device=self.exclusive_device, weight_dtype=resolve_weight_dtype(self.weight_dtype),
+                                kv_dtype=resolve_kv_dtype(getattr(self, "kv_cache_dtype", None)))
         if self.image_encoder_type != "clip":
             raise NotImplementedError(f"image_encoder_type={self.image_encoder_type!r}: v1 is built for the clip branch")
         return EngineConfig(image_size=self.image_size, patch_size=self.patch_size, vit_width=self.vit_width,
@@ -190,7 +195,8 @@ class StarVectorConfig:
                             n_inner=self.n_inner, vocab=self.vocab_size + self.added_tokens,
                             n_positions=self.n_positions, max_batch=self.max_batch,
                             max_seq_len=min(self.max_length, self.n_positions), exclusive_device=self.exclusive_device,
-                            weight_dtype=resolve_weight_dtype(self.weight_dtype))
+                            weight_dtype=resolve_weight_dtype(self.weight_dtype),
+                                kv_dtype=resolve_kv_dtype(getattr(self, "kv_cache_dtype", None)))
 
 
 def config_from_checkpoint(cfg_json: Dict, shapes: Dict[str, tuple]) -> StarVectorConfig:
@@ -1251,6 +1257,10 @@ class StarVectorForCausalLM(nn.Module):
         if ecfg.weight_dtype != "bf16":
             print(f"[starvector_amd] decoder weights quantised to {ecfg.weight_dtype} at load: not the reference's precision "
                   "(accuracy on a real checkpoint is unmeasured)", file=sys.stderr)
+        if ecfg.kv_dtype != "bf16":
+            info = self.engine.kv_info()
+            print(f"[starvector_amd] KV cache kept as {ecfg.kv_dtype} ({info['page_bytes']} bytes per page, pool {info['pool_bytes'] / 2**20:.0f} MiB): "
+                  "not the reference's precision (accuracy on a real checkpoint is unmeasured)", file=sys.stderr)
         if state_dict is not None:
             self.engine.load_state_dict(state_dict)
         if tokenizer is None:

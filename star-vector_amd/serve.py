@@ -120,7 +120,7 @@ class ModelWorker:
                  model_name: Optional[str] = None, device="cuda", limit_model_concurrency: int = 5, *,
                  model=None, tokenizer=None, image_processor=None, context_len: Optional[int] = None,
                  continuous_batching: bool = True, prompt_lookup_num_tokens: int = 0, max_matching_ngram_size: int = 0,
-                 weight_dtype: Optional[str] = None):
+                 weight_dtype: Optional[str] = None, kv_cache_dtype: Optional[str] = None):
         self.controller_addr, self.worker_addr, self.worker_id = controller_addr, worker_addr, worker_id
         model_path = model_path[:-1] if model_path.endswith("/") else model_path
         if model_name is None:                                         # :46-52
@@ -131,7 +131,8 @@ class ModelWorker:
         self.task = "Text2SVG" if "text2svg" in model_name.lower() else "Image2SVG"
         self.device = device
         if model is None:
-            tokenizer, model, image_processor, context_len = load_pretrained_model(model_path, device=device, **({"weight_dtype": weight_dtype} if weight_dtype else {}))
+            tokenizer, model, image_processor, context_len = load_pretrained_model(model_path, device=device, **({"weight_dtype": weight_dtype} if weight_dtype else {}),
+                                                                                        **({"kv_cache_dtype": kv_cache_dtype} if kv_cache_dtype else {}))
         self.tokenizer, self.model, self.image_processor, self.context_len = tokenizer, model, image_processor, context_len
         self.is_multimodal = "starvector" in model_name.lower()       # :66
         # The reference admits `limit_model_concurrency` requests at once and lets their generate calls take turns on the GPU
@@ -322,6 +323,8 @@ def main(argv=None):                                                   # :235-26
     p.add_argument("--max-matching-ngram-size", type=int, default=0, help="longest n-gram the draft lookup matches (0 = 3)")
     p.add_argument("--weight-dtype", type=str, default=None, choices=["bf16", "fp8", "fp8_e4m3", "mxfp4"],
                    help="decoder weight format (default: SV_WEIGHT_DTYPE, else bf16); fp8 / mxfp4 quantise at load and are not the reference's precision")
+    p.add_argument("--kv-cache-dtype", type=str, default=None, choices=["auto", "bf16", "fp8", "fp8_e4m3"],
+                   help="KV-cache format (default: SV_KV_DTYPE, else bf16); fp8 halves the cache and is not the reference's precision")
     args = p.parse_args(argv)
     if args.prompt_lookup_num_tokens and args.no_continuous_batching:
         p.error("--prompt-lookup-num-tokens drafts in the continuous batch: drop --no-continuous-batching")
@@ -329,7 +332,8 @@ def main(argv=None):                                                   # :235-26
     worker = ModelWorker(args.controller_address, args.worker_address, str(uuid.uuid4())[:6], args.no_register,
                          args.model_path, args.model_name, args.device, args.limit_model_concurrency,
                          continuous_batching=not args.no_continuous_batching, prompt_lookup_num_tokens=args.prompt_lookup_num_tokens,
-                         max_matching_ngram_size=args.max_matching_ngram_size, weight_dtype=args.weight_dtype)
+                         max_matching_ngram_size=args.max_matching_ngram_size, weight_dtype=args.weight_dtype,
+                         kv_cache_dtype=args.kv_cache_dtype)
     uvicorn.run(build_app(worker), host=args.host, port=args.port, log_level="info")
 
 

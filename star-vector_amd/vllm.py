@@ -257,13 +257,21 @@ class LLM:
     what it returns without these arguments.
 
     ``quantization="fp8"`` / ``"mxfp4"`` quantise the decoder weights at load (`EngineConfig.weight_dtype`); None = the environment's
-    SV_WEIGHT_DTYPE, else bf16.  Any other string raises ValueError.  Neither is the reference's precision."""
+    SV_WEIGHT_DTYPE, else bf16.  Any other string raises ValueError.  Neither is the reference's precision.
+
+    ``kv_cache_dtype="fp8"`` / ``"fp8_e4m3"`` keeps the paged KV cache as e4m3 codes with one power-of-two scale per key and head
+    (`EngineConfig.kv_dtype`): half the pool and half the decode attention's stream; ``"auto"`` = bf16 (or the environment's SV_KV_DTYPE).
+    Any other string raises ValueError.  Prompt-lookup drafting is not built for it.  Not the reference's precision."""
 
     def __init__(self, model: str, tokenizer=None, dtype: str = "auto", max_model_len: Optional[int] = None,
                  max_num_seqs: Optional[int] = None, trust_remote_code: bool = False, speculative_model: Optional[str] = None,
                  num_speculative_tokens: Optional[int] = None, ngram_prompt_lookup_max: Optional[int] = None,
-                 ngram_prompt_lookup_min: Optional[int] = None, quantization: Optional[str] = None, **kwargs):
+                 ngram_prompt_lookup_min: Optional[int] = None, quantization: Optional[str] = None, kv_cache_dtype: str = "auto", **kwargs):
         from .model import StarVectorForCausalLM
+        if kv_cache_dtype not in ("auto", "fp8", "fp8_e4m3"):
+            raise ValueError(f"kv_cache_dtype must be \"auto\", \"fp8\" or \"fp8_e4m3\", got {kv_cache_dtype!r}")
+        if kv_cache_dtype != "auto" and speculative_model is not None:
+            raise NotImplementedError("speculative_model=\"[ngram]\" with an fp8 KV cache is not built (the drafts' K / V pre-write is bf16)")
         if quantization is not None and quantization not in ("fp8", "mxfp4"):
             raise ValueError(f"quantization must be \"fp8\", \"mxfp4\" or None, got {quantization!r}")
         self._lookup = {}
@@ -285,6 +293,8 @@ class LLM:
         load_kw = {}
         if quantization is not None:
             load_kw["weight_dtype"] = {"fp8": "fp8_e4m3", "mxfp4": "mxfp4"}[quantization]
+        if kv_cache_dtype != "auto":
+            load_kw["kv_cache_dtype"] = "fp8_e4m3"
         if max_num_seqs is not None:
             load_kw["max_batch"] = int(max_num_seqs)
         if max_model_len is not None:

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Decode-step time vs context length (StarVector-1B shapes, B=32): generate N tokens, then profile one
-step by kernel class at the context the generation ended on."""
+step by kernel class at the context the generation ended on.  --kv-dtype / --weight-dtype / --model 8b / --batch: the same sweep with the
+e4m3 KV cache, quantised decoder weights, StarVector-8B shapes (image 384, sliding window 4096) or another batch."""
+import argparse
 import json
 import os
 import sys
@@ -12,15 +14,29 @@ sys.path.insert(0, ROOT)
 import starvector_amd as sva  # noqa: E402
 from bench import synthetic_images  # noqa: E402
 
+ap = argparse.ArgumentParser()
+ap.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8", "fp8_e4m3"], help="KV-cache format (EngineConfig.kv_dtype)")
+ap.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8", "fp8_e4m3", "mxfp4"])
+ap.add_argument("--model", default="1b", choices=["1b", "8b"])
+ap.add_argument("--batch", type=int, default=32)
+ap.add_argument("--new-tokens", type=int, nargs="+", default=[2, 512, 1024, 2048, 4096], help="tokens generated behind the prompt, one row each")
+args = ap.parse_args()
+
 dev = torch.device("cuda", 0)
-B = 32
-eng = sva.HipEngine(sva.EngineConfig(max_batch=B, max_seq_len=259 + 4100))
+B = args.batch
+if args.model == "8b":
+    cfg = sva.EngineConfig.starvector_8b(max_batch=B, max_seq_len=576 + 2 + max(args.new_tokens) + 4)
+else:
+    cfg = sva.EngineConfig(max_batch=B, max_seq_len=259 + max(args.new_tokens) + 4)
+cfg.weight_dtype, cfg.kv_dtype = args.weight_dtype, args.kv_dtype
+eng = sva.HipEngine(cfg)
 eng.load_random_weights(seed=1)
-img = synthetic_images(torch, B, 224, seed=2).to(dev)
+print(json.dumps({"model": args.model, "batch": B, "weight_dtype": cfg.weight_dtype, **eng.kv_info()}), flush=True)
+img = synthetic_images(torch, B, cfg.image_size, seed=2).to(dev)
 prompt = torch.tensor([[7, 11]] * B, dtype=torch.long, device=dev)
 emb = torch.cat([eng.adapter(eng.encode_image(img)), eng.embed_tokens(prompt)], 1)
 S0 = emb.shape[1]
-for n_new in (2, 512, 1024, 2048, 4096):
+for n_new in args.new_tokens:
     eng.generate(emb, max_length=S0 + n_new, eos_token_id=-1, pad_token_id=49152)          # first call of a length: graph capture
     eng.generate(emb, max_length=S0 + n_new, eos_token_id=-1, pad_token_id=49152)
     tm = eng.last_timing()
