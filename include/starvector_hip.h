@@ -294,6 +294,40 @@ int  sv_prefill_ragged(sv_engine* e, const void* dev_embeds_packed, int32_t B, c
 int  sv_forward_logprobs_ragged(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, const int32_t* host_keep,
                                 const int32_t* dev_targets, float temperature, float* dev_logprob, float* dev_logsumexp, float* dev_entropy,
                                 int32_t* dev_argmax, int32_t k, int32_t* dev_topk_ids, float* dev_topk_logprobs, int32_t* dev_rank, sv_stream stream);
+/* ---- prompt rows behind a CACHED context: a second turn, a teacher-forced suffix, a long prompt in bounded pieces.  The engine keeps, on the
+ * host, the number of tokens cached for every row of the cache.  It is known behind sv_prefill, sv_prefill_ragged, sv_prefill_open and
+ * sv_prefill_extend, grows by one per sv_decode_step, and is UNKNOWN behind every other call that assigns pages or runs a prompt pass
+ * (sv_generate*, beam search, the scoring forwards, continuous batching).
+ *   sv_prefill_open      assigns pages for B sequences of host_total_lens[b] (1 .. max_seq_len) tokens each; every context becomes 0; nothing
+ *                        is computed.  Returns when the table is on the device.
+ *   sv_prefill_extend    appends host_lens[b] >= 0 rows to sequence b of the B cached sequences; dev_embeds_packed: the new rows back to back,
+ *                        [sum(host_lens)][hidden] bf16; at least one length > 0, a 0 leaves the sequence and its logits row untouched.  The new
+ *                        rows take positions ctx_b + j; they see the cache for everything before them (an e4m3 cache: its dequantised values)
+ *                        and the unquantised K / V of the rows of this call, as the rows of a one-shot pass see each other.
+ *                        host_total_lens[b] >= ctx_b + host_lens[b] (NULL: exactly that, the free extension) states the length of the sequence
+ *                        the rows belong to: a row takes the GEMM kernel it takes in a one-shot pass over a sequence of THAT many rows.  The
+ *                        last layer's rows and the last-row logits are computed for the sequences this call brings to their total length:
+ *                        dev_logits [B][vocab] fp32 receives their rows, as sv_prefill_ragged writes them; the rows of the others are untouched.
+ *                        Afterwards sv_decode_step and further extensions continue every row at its own position.
+ *                        Contract (bf16 cache): a sequence fed through sv_prefill_open and any number of sv_prefill_extend calls with the same
+ *                        total is BIT-IDENTICAL to sv_prefill_ragged over the whole sequence -- last-row logits, every K / V entry of its
+ *                        pages, every token generated afterwards --, whatever the boundaries and whatever shares the passes.  A free extension is
+ *                        bit-identical to the one-shot pass of the concatenation whenever both send the same rows through the split-K
+ *                        remainder kernel (always, for lengths that leave no 1..3 rows over a multiple of 256).
+ *                        SV_EINVAL before any device work for null pointers, B other than the cached sequences, a negative length, all
+ *                        lengths 0, ctx + len > total, a total beyond the sequence's pages or max_seq_len; SV_ESTATE for unknown contexts or an
+ *                        active continuous batch.
+ *   sv_set_prefill_chunk rows = 0 (the default): off, every call issues the launches it always issued.  rows > 0: a row budget for every prompt
+ *                        pass with a generate tail -- sv_prefill, sv_prefill_ragged, sv_generate*, the shared prompt pass, sv_cb_admit*.  A pass
+ *                        of more packed rows runs as several extension passes of at most `rows` own rows: the sequences are walked in order,
+ *                        each takes what the budget leaves, every sequence's total is its prompt length.  Same logits, same pages, same tokens
+ *                        (bf16 cache: bit for bit; e4m3 cache: a later piece sees the dequantised cache of the earlier ones).  The prompt-pass
+ *                        workspaces are sized by the budget; only the K | V rows gathered from the pages grow with the context.  The scoring
+ *                        forwards are not chunked. */
+int  sv_prefill_open(sv_engine* e, int32_t B, const int32_t* host_total_lens);
+int  sv_prefill_extend(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, const int32_t* host_total_lens,
+                       float* dev_logits, sv_stream stream);
+int  sv_set_prefill_chunk(sv_engine* e, int32_t rows);
 /* sv_forward_logprobs_ragged over sequences that SHARE PREFIXES (GRPO's log-prob pass: G completions per image): every prefix goes through
  * the decoder once, not once per sequence.  dev_prefix_packed: the P prefixes back to back, [sum(host_prefix_lens)][hidden] bf16;
  * dev_embeds_packed: the B sequences' OWN rows back to back, [sum(host_lens)][hidden] bf16.  Sequence b stands for the solo sequence

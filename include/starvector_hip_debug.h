@@ -154,6 +154,18 @@ int  sv_debug_ragged_plan(const int32_t* lens, int32_t B, int32_t N, int32_t K, 
 int  sv_debug_prefix_plan(const int32_t* prefix_lens, int32_t P, const int32_t* lens, const int32_t* prefix_of, int32_t B, int32_t N,
                           int32_t K, int32_t act, int32_t q_tile, int32_t* row_pos_out, int32_t* rows_out, int32_t* blocks_out,
                           int32_t capacity, int32_t* out4);
+/*   sv_debug_extend_plan      what an extension call (sv_prefill_extend, or a prompt pass under sv_set_prefill_chunk) decides for B sequences with
+     ctx[b] cached tokens, lens[b] >= 0 new rows and total lengths totals[b] >= ctx + len (NULL: ctx + len), at the projection (N, K, act), under a
+     row budget (0: one pass).  Host arithmetic only.  out [capacity] int32, *out_n = the values written (or needed, when SV_EINVAL says capacity):
+       n_passes, then per pass:  n_seq, {b, ctx, len, first packed row} x n_seq        the sequences that take part, their context BEFORE the pass
+                                 n_rows, packed row x n_rows                             rows through the split-K remainder kernel: the own rows with solo
+                                                                                         index >= total - total % 256 where sv_debug_gemm_seq_form(total, ..) holds
+                                 n_tiles, {b, tile} x n_tiles                            attention tiles of q_tile rows counted from solo index 0, from the
+                                                                                         tile that holds row ctx on (context-free sequences first)
+                                 n_groups, {b, 32-token group} x n_groups                page groups the writer touches: ctx / 32 .. (ctx + len - 1) / 32
+                                 n_fin, b x n_fin                                        sequences that reach their total: last layer in full + logits */
+int  sv_debug_extend_plan(const int32_t* ctx, const int32_t* lens, const int32_t* totals, int32_t B, int32_t budget, int32_t N, int32_t K,
+                          int32_t act, int32_t q_tile, int32_t* out, int32_t capacity, int32_t* out_n);
 /*   sv_debug_shared_plan      the page plan of a shared prompt pass (sv_generate_shared, sv_cb_admit_shared): n requests over n_prompts prompts of
      lengths lens[u], request i samples prompt group[i] with a budget of budgets[i] new tokens.  Host arithmetic only.  shared_out [n]: the leading
      block-table entries of request i that are its prompt's full pages, lens[group[i]] / 64, held ONCE per prompt; private_out [n]: the pages the
@@ -205,6 +217,9 @@ int  sv_debug_kv_load(sv_engine* e, int32_t layer, const void* dev_kv, int32_t B
      [count][2*n_kv*head_dim] (k heads | v heads, the layout sv_debug_kv_load takes).  Works for both KV formats: the bf16 pool's stored bits,
      the e4m3 pool's deq(quant(.)) through the attention's own widening. */
 int  sv_debug_kv_read(sv_engine* e, int32_t layer, int32_t row, int32_t first, int32_t count, void* dev_out_bf16, sv_stream stream);
+/*   sv_debug_kv_gather   tokens [0, count) of decode row `row` of `layer` through the extension pass's pages -> rows launch (kv_gather_kernel, whole
+     1 KiB fragment loads) -> dev_out_bf16 [count][2*n_kv*head_dim]: bit for bit what sv_debug_kv_read returns for them, either format.  Blocks. */
+int  sv_debug_kv_gather(sv_engine* e, int32_t layer, int32_t row, int32_t count, void* dev_out_bf16, sv_stream stream);
 int  sv_debug_attn_decode(sv_engine* e, int32_t layer, const float* dev_qkv_f32, int32_t B, void* dev_out, int32_t advance,
                           sv_stream stream);
 int  sv_debug_attn_decode_slabs(sv_engine* e, int32_t layer, const float* dev_slabs_f32, int32_t splitk, const void* dev_bias, int32_t B,

@@ -149,6 +149,9 @@ PRODUCT_PROTOTYPES = {
                                   C.POINTER(_F), _P, _P, C.c_int64, _P]),
     "sv_prefill": (_I, [_P, _P, _I, _I, _P, _P]),
     "sv_prefill_ragged": (_I, [_P, _P, _I, C.POINTER(_I), _P, _P]),
+    "sv_prefill_open": (_I, [_P, _I, C.POINTER(_I)]),
+    "sv_prefill_extend": (_I, [_P, _P, _I, C.POINTER(_I), C.POINTER(_I), _P, _P]),
+    "sv_set_prefill_chunk": (_I, [_P, _I]),
     "sv_generate_ragged": (_I, [_P, _P, _I, C.POINTER(_I), C.POINTER(SvSampling), C.POINTER(SvGenerateOutputs), _P, C.POINTER(_I), _P]),
     "sv_generate_shared": (_I, [_P, _P, _I, C.POINTER(_I), _I, _I, C.POINTER(SvSampling), C.POINTER(SvGenerateOutputs), _P, C.POINTER(_I), _P]),
     "sv_generate_processed": (_I, [_P, _P, _I, C.POINTER(_I), _I, _I, C.POINTER(SvSampling), C.POINTER(SvLogitsProcessors),
@@ -208,6 +211,8 @@ DEBUG_PROTOTYPES = {
     "sv_debug_prefix_plan": (_I, [C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(_I), _I, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _I,
                                   C.POINTER(_I)]),
     "sv_debug_prompt_passes": (_I, [_P, C.POINTER(C.c_int64)]),
+    "sv_debug_extend_plan": (_I, [C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, C.POINTER(_I)]),
+    "sv_debug_kv_gather": (_I, [_P, _I, _I, _I, _P, _P]),
     "sv_debug_shared_plan": (_I, [C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_int64)]),
     "sv_debug_block_table": (_I, [_P, _I, C.POINTER(_I), _I]),
     "sv_debug_free_pages": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),

@@ -392,6 +392,7 @@ extern "C" int sv_destroy(sv_engine* e) {
     if (e->h_rag) (void)hipHostFree(e->h_rag);
     if (e->d_rag) (void)hipFree(e->d_rag);
     if (e->rag_row_pos) (void)hipFree(e->rag_row_pos);
+    if (e->gkv) (void)hipFree(e->gkv);
     if (e->rag_ev) (void)hipEventDestroy(e->rag_ev);
     if (e->table_ev) (void)hipEventDestroy(e->table_ev);
     for (hipEvent_t ev : e->prof_ev) (void)hipEventDestroy(ev);

@@ -135,7 +135,10 @@ static int ensure_prefill_ws(sv_engine* e, size_t rows) {
     // previous buffers stay in e->allocs (freed at destroy); growth is rare (max_batch * S0)
     SVCHECK(dalloc(e, &e->ph, rows * D));
     SVCHECK(dalloc(e, &e->pln, rows * D));
-    SVCHECK(dalloc(e, &e->pqkv, rows * (size_t)e->QKV));
+    // 128 zeroed rows in front of the c_attn output: the query tile of an extension pass that straddles a context's end reads up to q_tile - 1 Q rows
+    // in front of a sequence's first own row (extend/extend.hip)
+    SVCHECK(dalloc(e, &e->pqkv, (rows + 128) * (size_t)e->QKV));
+    e->pqkv += (size_t)128 * e->QKV;
     SVCHECK(dalloc(e, &e->pattn, rows * D));
     SVCHECK(dalloc(e, &e->pmlp, rows * c.n_inner));
     e->pf_rows = rows;
@@ -150,6 +153,7 @@ void sveng::reset_free_pages(sv_engine* e) {
 // added mid-flight): lens[b] + extra tokens for sequence b (lens == nullptr: extra tokens each; extra < 0: the whole max_seq_len, as sv_prefill hands out)
 int sveng::assign_pages_ragged(sv_engine* e, int B, const int32_t* lens, int extra, hipStream_t st) {
     reset_free_pages(e);
+    e->ctx_known = false;
     // The table goes up from a PINNED host image without a stream synchronise (the pageable copy + hipStreamSynchronize of rounds 1-5 drained the
     // stream in front of every prompt pass: ~25 us of idle GPU on the way to the first token); the image is rewritten only after the upload
     // before it has completed (an event, normally long past).
@@ -303,9 +307,20 @@ static int score_kept_rows(sv_engine* e, size_t rows, const ScoreLogprobs* lp, h
     return score_logprob_chunks(e, hn, rows, lp, st);
 }
 
+// sv_set_prefill_chunk: a generate-tail prompt pass of more packed rows than the budget runs as extension passes.  (SV_EXP_BATCH_REMAINDER, the A/B
+// arm whose remainder rows depend on the batch, has no per-sequence routing to keep: it stays one pass.)
+static bool chunk_applies(const sv_engine* e, long long rows) {
+    return e->prefill_chunk > 0 && rows > e->prefill_chunk && !(e->exp & SV_EXP_BATCH_REMAINDER);
+}
+
 int sveng::prefill_forward(sv_engine* e, const bf16_t* embeds, int B, int S0, hipStream_t st, int n_keep,
                            bf16_t* dev_scores, const int32_t* table, const ScoreLogprobs* lp) {
     if (!table) table = e->block_table;           // continuous batching prefills NEW requests through a table of their slots' pages
+    e->ctx_known = false;
+    if (n_keep == 0 && chunk_applies(e, (long long)B * S0)) {      // sv_set_prefill_chunk: the same bits from passes of at most that many rows
+        const std::vector<int32_t> lens((size_t)B, S0);
+        return prefill_chunked(e, embeds, B, lens.data(), table, st);
+    }
     const sv_config& c = e->cfg;
     const int D = c.hidden, dh = e->dh, F = c.n_inner, M = B * S0, QKV = e->QKV, nkv = e->nkv;
     const int QD = c.n_head * dh;                      // width of the query block (= D for both model families)
@@ -488,17 +503,18 @@ static int plan_proj(const sv_engine* e, PlanProj pj[4]) {
     return (e->exp & SV_EXP_BATCH_REMAINDER) ? 0 : 4;
 }
 // every list of the plan, concatenated in list order into the pinned image, in one upload; off[i] = where list i begins in d_rag
-static int rag_upload_plan(sv_engine* e, const PackedPlan& p, size_t off[PL_COUNT], hipStream_t st) {
+static int rag_upload_lists(sv_engine* e, const std::vector<int32_t>* list, int n, size_t* off, hipStream_t st) {
     size_t need = 0;
-    for (int i = 0; i < PL_COUNT; ++i) { off[i] = need; need += p.list[i].size(); }
+    for (int i = 0; i < n; ++i) { off[i] = need; need += list[i].size(); }
     SVCHECK(rag_reserve_plan(e, need));
-    for (int i = 0; i < PL_COUNT; ++i)
-        if (!p.list[i].empty()) memcpy(e->h_rag + off[i], p.list[i].data(), p.list[i].size() * sizeof(int32_t));
+    for (int i = 0; i < n; ++i)
+        if (!list[i].empty()) memcpy(e->h_rag + off[i], list[i].data(), list[i].size() * sizeof(int32_t));
     HIPCHECK(hipMemcpyAsync(e->d_rag, e->h_rag, need * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIPCHECK(hipEventRecord(e->rag_ev, st));
     e->rag_pending = true;
     return 0;
 }
+static int rag_upload_plan(sv_engine* e, const PackedPlan& p, size_t off[PL_COUNT], hipStream_t st) { return rag_upload_lists(e, p.list, PL_COUNT, off, st); }
 
 // The packed pass over p.M rows.  A scoring tail (lp) runs the last layer on all packed rows with the per-sequence remainder rows of the layers in
 // front -- a solo scoring pass never prunes it either --, gathers the kept rows into [p.kept][D] and sends them through ln_f and the chunked lm_head +
@@ -506,6 +522,7 @@ static int rag_upload_plan(sv_engine* e, const PackedPlan& p, size_t off[PL_COUN
 // then the prefixed form over the sequences' tiles from the straddling one on); the prefix rows' c_proj / MLP work in the last layer is not skipped.
 int sveng::prefill_forward_packed(sv_engine* e, const PackedPlan& p, const int32_t* table, const ScoreLogprobs* lp, hipStream_t st) {
     if (!table) table = e->block_table;
+    e->ctx_known = false;
     const sv_config& c = e->cfg;
     const int D = c.hidden, dh = e->dh, F = c.n_inner, QKV = e->QKV, nkv = e->nkv;
     const int QD = c.n_head * dh, M = p.M, B = p.B;
@@ -594,12 +611,150 @@ int sveng::prefill_forward_packed(sv_engine* e, const PackedPlan& p, const int32
 
 int sveng::prefill_forward_ragged(sv_engine* e, const bf16_t* embeds, int B, const int32_t* lens, hipStream_t st, const int32_t* table,
                                   const int32_t* keep, const ScoreLogprobs* lp) {
+    if (!keep) {
+        long long rows = 0;
+        for (int b = 0; b < B; ++b) rows += lens[b];
+        if (chunk_applies(e, rows)) return prefill_chunked(e, embeds, B, lens, table ? table : e->block_table, st);
+    }
     PlanProj pj[4];
     const int n_proj = plan_proj(e, pj);
     PackedPlan p;
     ragged_plan(lens, B, attn_prefill_q_tile(e->cfg.n_head, e->nkv), pj, n_proj, keep, p);
     p.src[0] = embeds;
     return prefill_forward_packed(e, p, table, lp, st);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The extension pass: own rows behind a cached context (the plan and why the bits hold: extend/extend.hip)
+// ------------------------------------------------------------------------------------------------
+ExtKvArgs sveng::extend_kv_args(sv_engine* e, int layer, const int32_t* table, const int32_t* xseq, const int32_t* blocks, int n_blocks, bf16_t* gkv) {
+    const int dh = e->dh, nkv = e->nkv, QD = e->cfg.n_head * dh;
+    ExtKvArgs a;
+    a.qkv = e->pqkv; a.row_stride = e->QKV; a.k_off = QD; a.v_off = QD + nkv * dh;
+    a.pool_layer = e->kv_pool + (size_t)layer * e->layer_stride; a.kv_head_stride = e->kv_head_stride; a.table = table; a.max_pages = e->pages_per_seq;
+    a.xseq = xseq; a.blocks = blocks; a.n_blocks = n_blocks; a.head_dim = dh; a.n_kv = nkv; a.kv_fmt = e->kv_dtype;
+    a.gkv = gkv; a.gkv_stride = 2 * nkv * dh;
+    return a;
+}
+
+// the K | V rows of the sequences with a context: the one buffer of an extension pass that grows with the context (hipFree waits for the launches
+// that still read the old one)
+static int reserve_gkv(sv_engine* e, size_t rows) {
+    if (rows <= e->gkv_rows) return 0;
+    if (e->gkv) (void)hipFree(e->gkv);
+    e->gkv = nullptr; e->gkv_rows = 0;
+    HIPCHECK(hipMalloc(reinterpret_cast<void**>(&e->gkv), rows * 2 * e->nkv * e->dh * sizeof(bf16_t)));
+    e->gkv_rows = rows;
+    return 0;
+}
+
+int sveng::extend_forward(sv_engine* e, ExtendPass& p, const bf16_t* embeds, const int32_t* table, hipStream_t st) {
+    if (!table) table = e->block_table;
+    const sv_config& c = e->cfg;
+    const int D = c.hidden, dh = e->dh, F = c.n_inner, QKV = e->QKV, nkv = e->nkv;
+    const int QD = c.n_head * dh, M = p.M, NF = (int)p.fin.size(), KW = 2 * nkv * dh;
+    SVCHECK(ensure_prefill_ws(e, (size_t)std::max(M, 2 * NF)));
+    SVCHECK(reserve_gkv(e, (size_t)p.gkv_rows));
+    ++e->prompt_passes;
+    if (!e->rag_rsave) SVCHECK(dalloc(e, &e->rag_rsave, (size_t)3 * c.max_batch * D));
+    SVCHECK(rag_reserve_row_pos(e, (size_t)M));
+    size_t off[XL_COUNT];
+    SVCHECK(rag_upload_lists(e, p.list, XL_COUNT, off, st));
+    const auto dev = [&](int i) -> const int32_t* { return e->d_rag + off[i]; };
+    const auto len = [&](int i) { return (int)p.list[i].size(); };
+    const auto rows = [&](int i) { return XL_ROWS + 2 * i; };
+    const auto last = [&](int i) { return XL_ROWS + 2 * i + 1; };
+
+    prof_mark(e, PK_PF_ROWS, st);
+    launch_prefix_row_pos(dev(XL_SEG), len(XL_SEG) / 3, e->rag_row_pos, st);      // a row's position is its solo index ctx + j
+    if (e->v2) HIPCHECK(hipMemcpyAsync(e->ph, embeds, (size_t)M * D * sizeof(bf16_t), hipMemcpyDeviceToDevice, st));
+    else launch_dec_embed(embeds, e->wpe, e->ph, 1, M, D, st, e->rag_row_pos);
+    AttnPrefillArgs at = attn_prefill_args(e);
+    // the attention of the sequences with a context: one prefixed launch each over {0, tile} entries, K | V from the sequence's region of gkv -- the
+    // kernel's row index of solo index s is (R - ctx) + s, so the region's row 0 lies at index R - ctx
+    const auto attn_ctx = [&](bool last_only) {
+        AttnPrefillArgs ac = at;
+        ac.rag_prefixed = 1; ac.kv_row_stride = KW; ac.kv_head_stride = nkv > 1 ? dh : 0;
+        for (const ExtendPass::CtxSeq& cs : p.ctx_seqs) {
+            if (last_only && !cs.fin) continue;
+            const bf16_t* kb = e->gkv + ((long long)cs.region - cs.index_row0) * KW;
+            ac.k = kb; ac.v = kb + nkv * dh;
+            ac.rag_seq = dev(XL_CTX_SEQ) + cs.seq_off;
+            ac.rag_blocks = dev(XL_CTX_BLOCKS) + cs.blocks_off + (last_only ? 2 * (cs.n_blocks - 1) : 0);
+            ac.rag_nblocks = last_only ? 1 : cs.n_blocks;
+            launch_attn_prefill(ac, st);
+        }
+    };
+    for (int i = 0; i < c.n_layer; ++i) {
+        DecLayer& L = e->dec[i];
+        prof_mark(e, PK_PF_ROWS, st);
+        launch_layernorm_rows(e->ph, D, L.ln1.g, L.ln1.b, e->pln, D, M, D, c.ln_eps, st);
+        gemm_ragged(e, PK_PF_GEMM, e->pln, D, L.c_attn, nullptr, 0, e->pqkv, QKV, M, ACT_NONE, st, dev(rows(0)), len(rows(0)));
+        prof_mark(e, PK_PF_ATTN, st);
+        if (e->v2) launch_rope_prefill(e->pqkv, QKV, M, M, c.n_head + nkv, dh, e->rope_cos, e->rope_sin, st, e->rag_row_pos);
+        launch_kv_write_extend(extend_kv_args(e, i, table, dev(XL_XSEQ), dev(XL_WRITE), len(XL_WRITE) / 2, e->gkv), st);
+        const bool last_layer = i + 1 == c.n_layer;
+        if (last_layer && NF == 0) break;      // no sequence reaches its total: the last layer owes its K / V rows and nothing else
+        launch_kv_gather(extend_kv_args(e, i, table, dev(XL_XSEQ), dev(XL_GATHER), len(XL_GATHER) / 2, e->gkv), st);
+        at.rag_prefixed = 0; at.rag_seq = dev(XL_PLAIN_SEQ);
+        if (last_layer) {
+            // only the last row of every finishing sequence goes on (see prefill_forward): its query tile, then NF compact rows
+            at.rag_blocks = dev(XL_PLAIN_LAST); at.rag_nblocks = len(XL_PLAIN_LAST) / 2;
+            launch_attn_prefill(at, st);
+            attn_ctx(true);
+            const int32_t* d_fin = dev(XL_FIN);
+            bf16_t* pa_l = e->pln;
+            bf16_t* ln_l = e->pln + (size_t)NF * QD;
+            prof_mark(e, PK_PF_ROWS, st);
+            launch_gather_last_rows(e->pattn, pa_l, NF, 0, QD, st, d_fin);
+            launch_gather_last_rows(e->ph, e->hl, NF, 0, D, st, d_fin);
+            gemm_ragged(e, PK_PF_GEMM, pa_l, QD, L.c_proj, e->hl, D, e->hl, D, NF, ACT_NONE, st, dev(last(1)), len(last(1)));
+            prof_mark(e, PK_PF_ROWS, st);
+            launch_layernorm_rows(e->hl, D, L.ln2.g, L.ln2.b, ln_l, D, NF, D, c.ln_eps, st);
+            gemm_ragged(e, PK_PF_GEMM, ln_l, D, L.c_fc, nullptr, 0, e->pmlp, F, NF, ACT_GELU_TANH, st, dev(last(2)), len(last(2)));
+            gemm_ragged(e, PK_PF_GEMM, e->pmlp, F, L.c_proj2, e->hl, D, e->hl, D, NF, ACT_NONE, st, dev(last(3)), len(last(3)));
+            last_row_logits(e, NF, 0, d_fin, true, st);
+            return 0;
+        }
+        at.rag_blocks = dev(XL_PLAIN_BLOCKS); at.rag_nblocks = len(XL_PLAIN_BLOCKS) / 2;
+        launch_attn_prefill(at, st);
+        attn_ctx(false);
+        gemm_ragged(e, PK_PF_GEMM, e->pattn, QD, L.c_proj, e->ph, D, e->ph, D, M, ACT_NONE, st, dev(rows(1)), len(rows(1)));
+        prof_mark(e, PK_PF_ROWS, st);
+        launch_layernorm_rows(e->ph, D, L.ln2.g, L.ln2.b, e->pln, D, M, D, c.ln_eps, st);
+        gemm_ragged(e, PK_PF_GEMM, e->pln, D, L.c_fc, nullptr, 0, e->pmlp, F, M, ACT_GELU_TANH, st, dev(rows(2)), len(rows(2)));
+        gemm_ragged(e, PK_PF_GEMM, e->pmlp, F, L.c_proj2, e->ph, D, e->ph, D, M, ACT_NONE, st, dev(rows(3)), len(rows(3)));
+    }
+    e->xpa_armed = false;                       // no lm_head launch in front of the step that follows
+    return 0;
+}
+
+int sveng::prefill_chunked(sv_engine* e, const bf16_t* embeds, int B, const int32_t* lens, const int32_t* table, hipStream_t st) {
+    PlanProj pj[4];
+    const int n_proj = plan_proj(e, pj), q_tile = attn_prefill_q_tile(e->cfg.n_head, e->nkv), D = e->cfg.hidden;
+    std::vector<std::vector<int32_t>> take;
+    extend_schedule(lens, B, e->prefill_chunk, take);
+    if (!e->logit_stash) SVCHECK(dalloc(e, &e->logit_stash, (size_t)e->cfg.max_batch * e->Vpad, false));
+    std::vector<int32_t> desc, at((size_t)B, 0);
+    int longest = 0;
+    for (int b = 0, r0 = 0; b < B; r0 += lens[b++]) { desc.push_back(r0); desc.push_back(lens[b]); longest = std::max(longest, lens[b]); }
+    SVCHECK(reserve_gkv(e, (size_t)longest));      // (a pass continues at most one sequence: the one the pass in front cut)
+    size_t row0 = 0;
+    std::vector<ExtendSeq> seqs((size_t)B);
+    for (size_t k = 0; k < take.size(); ++k) {
+        for (int b = 0; b < B; ++b) seqs[b] = {at[b], take[k][b], lens[b]};
+        ExtendPass p;
+        extend_plan(seqs.data(), B, q_tile, pj, n_proj, p);
+        p.list[XL_DESC] = desc;
+        SVCHECK(extend_forward(e, p, embeds + row0 * D, table, st));
+        for (size_t i = 0; i < p.fin.size(); ++i)
+            HIPCHECK(hipMemcpyAsync(e->logit_stash + (size_t)p.fin[i] * e->Vpad, e->logits + i * e->Vpad, (size_t)e->Vpad * sizeof(float),
+                                    hipMemcpyDeviceToDevice, st));
+        row0 += (size_t)p.M;
+        for (int b = 0; b < B; ++b) at[b] += take[k][b];
+    }
+    HIPCHECK(hipMemcpyAsync(e->logits, e->logit_stash, (size_t)B * e->Vpad * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return 0;
 }
 
 // Arguments of the decode attention of layer `layer` over the engine's KV pool / block table / positions: the c_attn output
@@ -876,6 +1031,14 @@ int sveng::cb_guard(sv_engine* e, const char* who) {
     return 0;
 }
 
+// the host-side contexts behind a call that leaves them known: lens[b] (nullptr: `len` each) tokens cached, pages for `cap` tokens
+static void set_contexts(sv_engine* e, int B, const int32_t* lens, int len, int cap) {
+    e->ctx_len.assign((size_t)e->cfg.max_batch, 0);
+    e->ctx_cap.assign((size_t)e->cfg.max_batch, 0);
+    for (int b = 0; b < B; ++b) { e->ctx_len[b] = lens ? lens[b] : len; e->ctx_cap[b] = cap; }
+    e->ctx_known = true;
+}
+
 int sveng::prefill_locked(sv_engine* e, const void* dev_embeds, int B, int S0, int total_len, hipStream_t st, bool set_positions) {
     SVCHECK(cb_guard(e, "prefill"));
     if (!dev_embeds || B < 1 || B > e->cfg.max_batch) return fail(SV_EINVAL, "prefill: bad B=%d (max_batch %d)", B, e->cfg.max_batch);
@@ -897,6 +1060,7 @@ extern "C" int sv_prefill(sv_engine* e, const void* dev_embeds, int32_t B, int32
     hipStream_t st = (hipStream_t)stream;
     SVCHECK(prefill_locked(e, dev_embeds, B, S0, e->cfg.max_seq_len, st));
     SVCHECK(copy_logits_out(e, B, dev_logits, st));
+    set_contexts(e, B, nullptr, S0, e->cfg.max_seq_len);
     return 0;
 }
 
@@ -920,6 +1084,91 @@ extern "C" int sv_prefill_ragged(sv_engine* e, const void* dev_embeds_packed, in
     e->cached_B = B;
     HIPCHECK(hipGetLastError());
     SVCHECK(copy_logits_out(e, B, dev_logits, st));
+    set_contexts(e, B, host_lens, 0, e->cfg.max_seq_len);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// C ABI: many rows behind a cached context (include/starvector_hip.h)
+// ------------------------------------------------------------------------------------------------
+extern "C" int sv_set_prefill_chunk(sv_engine* e, int32_t rows) {
+    if (!e) return fail(SV_EINVAL, "sv_set_prefill_chunk: null engine");
+    if (rows < 0) return fail(SV_EINVAL, "sv_set_prefill_chunk: rows %d (0 = off, or a row budget >= 1)", rows);
+    std::lock_guard<std::mutex> lk(e->mu);
+    e->prefill_chunk = rows;
+    return 0;
+}
+
+extern "C" int sv_prefill_open(sv_engine* e, int32_t B, const int32_t* host_total_lens) {
+    if (!host_total_lens) return fail(SV_EINVAL, "sv_prefill_open: null lengths pointer");
+    if (B < 1) return fail(SV_EINVAL, "sv_prefill_open: bad B=%d", B);
+    for (int b = 0; b < B; ++b)
+        if (host_total_lens[b] < 1) return fail(SV_EINVAL, "sv_prefill_open: total length %d of sequence %d (must be >= 1)", host_total_lens[b], b);
+    SVCHECK(check_ready(e));
+    if (B > e->cfg.max_batch) return fail(SV_EINVAL, "sv_prefill_open: bad B=%d (max_batch %d)", B, e->cfg.max_batch);
+    SVCHECK(ragged_check_lens(e, host_total_lens, B, "sv_prefill_open", nullptr, nullptr));
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIPCHECK(hipSetDevice(e->cfg.device));
+    hipStream_t st = nullptr;                   // (no device work but the table upload and the positions: done when the call returns)
+    SVCHECK(cb_guard(e, "sv_prefill_open"));
+    SVCHECK(assign_pages_ragged(e, B, host_total_lens, 0, st));
+    fill_i32(e->positions, 0, B, st);
+    e->cached_B = B;
+    e->xpa_armed = false;
+    e->dbg_pos_hi = 0;
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));
+    set_contexts(e, B, nullptr, 0, 0);
+    for (int b = 0; b < B; ++b) e->ctx_cap[b] = (host_total_lens[b] + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS * SV_PAGE_TOKENS;
+    return 0;
+}
+
+extern "C" int sv_prefill_extend(sv_engine* e, const void* dev_embeds_packed, int32_t B, const int32_t* host_lens, const int32_t* host_total_lens,
+                                 float* dev_logits, sv_stream stream) {
+    const char* who = "sv_prefill_extend";
+    // (the checks that need no engine come first: they are the same on a machine without a GPU)
+    if (!dev_embeds_packed || !host_lens || !dev_logits) return fail(SV_EINVAL, "%s: null embeds / lengths / logits pointer", who);
+    if (B < 1) return fail(SV_EINVAL, "%s: bad B=%d", who, B);
+    long long rows = 0;
+    for (int b = 0; b < B; ++b) {
+        if (host_lens[b] < 0) return fail(SV_EINVAL, "%s: length %d of sequence %d (must be >= 0)", who, host_lens[b], b);
+        if (host_total_lens && host_total_lens[b] < host_lens[b])
+            return fail(SV_EINVAL, "%s: total length %d of sequence %d is below its %d new rows", who, host_total_lens[b], b, host_lens[b]);
+        rows += host_lens[b];
+    }
+    if (rows == 0) return fail(SV_EINVAL, "%s: every length is 0: nothing to append", who);
+    SVCHECK(check_ready(e));
+    std::lock_guard<std::mutex> lk(e->mu);
+    SVCHECK(cb_guard(e, who));
+    if (B != e->cached_B) return fail(SV_EINVAL, "%s: B=%d but the cache holds %d sequences", who, B, e->cached_B);
+    if (!e->ctx_known)
+        return fail(SV_ESTATE, "%s: the context lengths of the cache are unknown (they are known behind sv_prefill, sv_prefill_ragged, sv_prefill_open, "
+                    "sv_prefill_extend and sv_decode_step)", who);
+    std::vector<ExtendSeq> seqs((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        const int ctx = e->ctx_len[b], T = ctx + host_lens[b], total = host_total_lens ? host_total_lens[b] : T;
+        if (T > total) return fail(SV_EINVAL, "%s: context %d + length %d of sequence %d exceeds its total length %d", who, ctx, host_lens[b], b, total);
+        if (total > e->ctx_cap[b] || total > e->cfg.max_seq_len)
+            return fail(SV_EINVAL, "%s: total length %d of sequence %d exceeds its pages (%d tokens) or max_seq_len %d", who, total, b, e->ctx_cap[b], e->cfg.max_seq_len);
+        seqs[b] = {ctx, host_lens[b], total};
+    }
+    HIPCHECK(hipSetDevice(e->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    PlanProj pj[4];
+    const int n_proj = plan_proj(e, pj);
+    ExtendPass p;
+    extend_plan(seqs.data(), B, attn_prefill_q_tile(e->cfg.n_head, e->nkv), pj, n_proj, p);
+    for (int b = 0; b < B; ++b) p.list[XL_POS].push_back(seqs[b].ctx + seqs[b].len);
+    SVCHECK(extend_forward(e, p, (const bf16_t*)dev_embeds_packed, nullptr, st));
+    size_t pos_off = 0;
+    for (int i = 0; i < XL_POS; ++i) pos_off += p.list[i].size();
+    HIPCHECK(hipMemcpyAsync(e->positions, e->d_rag + pos_off, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    for (size_t i = 0; i < p.fin.size(); ++i)
+        HIPCHECK(hipMemcpyAsync(dev_logits + (size_t)p.fin[i] * e->cfg.vocab, e->logits + i * e->Vpad, (size_t)e->cfg.vocab * sizeof(float),
+                                hipMemcpyDeviceToDevice, st));
+    HIPCHECK(hipGetLastError());
+    for (int b = 0; b < B; ++b) e->ctx_len[b] += host_lens[b];
+    e->dbg_pos_hi = *std::max_element(e->ctx_len.begin(), e->ctx_len.begin() + B);
     return 0;
 }
 
@@ -1117,6 +1366,7 @@ extern "C" int sv_decode_step(sv_engine* e, const int32_t* dev_tokens, int32_t B
     HIPCHECK(hipMemcpyAsync(e->cur_tok, dev_tokens, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     decode_forward(e, B, st);
     add_i32(e->positions, 1, B, st);
+    if (e->ctx_known) for (int b = 0; b < B; ++b) ++e->ctx_len[b];
     SVCHECK(copy_logits_out(e, B, dev_logits, st));
     HIPCHECK(hipGetLastError());
     // the fused MLP launch reports a give-up through d_bad (code 3): logits computed from its unwritten activations are void

@@ -206,7 +206,17 @@ struct sv_engine {
     float* score_lse_ws = nullptr;   // sv_forward_topk without a caller's logsumexp: [score_lse_alloc] fp32, the chunk's lse between the two kernels
     int score_lse_alloc = 0;
     int cached_B = 0;
-    int dbg_pos_hi = 0;             // sv_debug_kv_load / sv_debug_attn_decode: upper bound of positions[] (host side), kept below max_seq_len
+    // extension passes (sv_prefill_open / sv_prefill_extend, chunked prefill; extend/extend.hip).  ctx_known: ctx_len[b] / ctx_cap[b] are the tokens
+    // cached for row b and the tokens its pages hold -- set by sv_prefill, sv_prefill_ragged, sv_debug_kv_load and the two calls, +1 per
+    // sv_decode_step, void after anything else that assigns pages or runs a prompt pass.  prefill_chunk: the row budget of sv_set_prefill_chunk (0: off).
+    // gkv: the K | V rows of the sequences with a context, [gkv_rows][2 * n_kv * head_dim]; logit_stash: [max_batch][Vpad] last-row logits of the
+    // sequences a chunked call finished in an earlier pass
+    bool ctx_known = false;
+    std::vector<int> ctx_len, ctx_cap;
+    int prefill_chunk = 0;
+    bf16_t* gkv = nullptr; size_t gkv_rows = 0;
+    float* logit_stash = nullptr;
+    int dbg_pos_hi = 0;            // sv_debug_kv_load / sv_debug_attn_decode: upper bound of positions[] (host side), kept below max_seq_len
     int num_cus = 256;
     double timing[3] = {0, 0, 0};
     double timing_graph = 0;
@@ -412,6 +422,40 @@ int prefix_check(const char* who, const int32_t* prefix_lens, int P, const int32
 // prefix's last row)
 void prefix_plan(const int32_t* prefix_lens, int P, const int32_t* lens, const int32_t* prefix_of, int B, int q_tile, const PlanProj* proj, int n_proj,
                  const int32_t* keep, PackedPlan& out);
+// The extension pass (extend/extend.hip; the layer loop is engine_forward.hip::extend_forward): sequence b has ctx tokens in its pages, gets len own
+// rows in this pass and is routed as a sequence of total >= ctx + len rows; len == 0: the sequence takes no part in the pass.
+struct ExtendSeq { int ctx, len, total; };
+enum {
+    XL_DESC,            // what the CALLER wants at offset 0 of d_rag behind the pass (a chunked ragged pass: {first packed row, length} x B of the whole call)
+    XL_XSEQ,            // {block-table row, first packed own row, ctx, len, first row of its K | V region or -1, 0} per sequence of the pass (kernels.h ExtKvArgs)
+    XL_SEG,             // {first packed row, len, ctx}: the row positions (launch_prefix_row_pos)
+    XL_WRITE, XL_GATHER,   // {sequence of the pass, 32-token group}: the page writer's groups | the gather's
+    XL_PLAIN_SEQ, XL_PLAIN_BLOCKS, XL_PLAIN_LAST,   // sequences without a context: ragged descriptors {first packed row, len} | their tiles | the last tile of those that finish
+    XL_CTX_SEQ, XL_CTX_BLOCKS,   // sequences with one: {first own packed row, T, R - ctx, ctx} | {0, tile} from the straddling tile on -- one launch each (ExtendPass::CtxSeq)
+    XL_FIN,             // {first packed row, len} of the sequences that reach their total in this pass: the pruned last layer's compact rows
+    XL_POS,             // caller: positions[] behind the pass (sv_prefill_extend)
+    XL_ROWS,            // + 2 i: remainder rows of projection i | + 2 i + 1: the compact rows (indices into XL_FIN) whose last row is one
+    XL_COUNT = XL_ROWS + 8
+};
+struct ExtendPass {
+    struct CtxSeq { int b; long long region; int index_row0; bool fin; int seq_off, blocks_off, n_blocks; };
+    int M = 0, B = 0;
+    long long gkv_rows = 0;
+    std::vector<int32_t> list[XL_COUNT];
+    std::vector<CtxSeq> ctx_seqs;
+    std::vector<int32_t> fin;              // the call's sequence behind every compact row
+    std::vector<int32_t>& rows(int i) { return list[XL_ROWS + 2 * i]; }
+    std::vector<int32_t>& last(int i) { return list[XL_ROWS + 2 * i + 1]; }
+    const std::vector<int32_t>& rows(int i) const { return list[XL_ROWS + 2 * i]; }
+    const std::vector<int32_t>& last(int i) const { return list[XL_ROWS + 2 * i + 1]; }
+};
+void extend_schedule(const int32_t* lens, int B, int budget, std::vector<std::vector<int32_t>>& take);
+void extend_plan(const ExtendSeq* seqs, int B, int q_tile, const PlanProj* proj, int n_proj, ExtendPass& out);
+ExtKvArgs extend_kv_args(sv_engine* e, int layer, const int32_t* table, const int32_t* xseq, const int32_t* blocks, int n_blocks, bf16_t* gkv);
+// one pass over p.M packed own rows `embeds`; p.list[XL_DESC] / [XL_POS] are the caller's.  Last-row logits of compact row i (sequence p.fin[i]) -> row i of e->logits
+int extend_forward(sv_engine* e, ExtendPass& p, const bf16_t* embeds, const int32_t* table, hipStream_t st);
+// a generate-tail prompt pass over B sequences of lens[] rows as passes of at most e->prefill_chunk own rows; leaves e->logits and d_rag as the one-shot pass does
+int prefill_chunked(sv_engine* e, const bf16_t* embeds, int B, const int32_t* lens, const int32_t* table, hipStream_t st);
 // engine_generate.hip
 void fork_args(sv_engine* e, int n_prompts, int n_rows, ForkArgs& f);      // the fork launch over e->fork_desc, the engine's block table, pool and logits
 // validation of a processor set against a vocabulary of V ids (V <= 0: the ids are only checked for >= 0) -- host arithmetic, no device -- and

@@ -114,6 +114,11 @@ extern "C" int sv_debug_kv_load(sv_engine* e, int32_t layer, const void* dev_kv,
     e->cached_B = B;
     e->xpa_armed = false;                       // no lm_head launch in front of the step that follows
     e->dbg_pos_hi = S;                          // dev_lens[b] <= S by contract
+    if (!dev_lens) {                            // (lengths on the device: the host does not know the contexts)
+        e->ctx_len.assign((size_t)c.max_batch, 0); e->ctx_cap.assign((size_t)c.max_batch, 0);
+        for (int b = 0; b < B; ++b) { e->ctx_len[b] = S; e->ctx_cap[b] = c.max_seq_len; }
+        e->ctx_known = true;
+    }
     HIPCHECK(hipGetLastError());
     return 0;
 }
@@ -152,7 +157,7 @@ static int debug_attn_decode(sv_engine* e, const char* who, int32_t layer, const
     attn_decode_args(e, layer, B, e->ws, splitk, bias, e->xp_attn, ad);
     launch_attn_decode(ad, st);
     unpack_rows(e->xp_attn, (bf16_t*)dev_out, c.n_head * e->dh, B, c.n_head * e->dh, st);
-    if (advance) { add_i32(e->positions, 1, B, st); e->dbg_pos_hi += 1; }
+    if (advance) { add_i32(e->positions, 1, B, st); e->dbg_pos_hi += 1; e->ctx_known = false; }
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(st));          // `bias` is freed on return
     return 0;
@@ -243,6 +248,7 @@ extern "C" int sv_debug_attn_decode_draft(sv_engine* e, int32_t layer, const flo
     HIPCHECK(hipMemcpyAsync(e->block_table, e->h_table, (size_t)rows * mp * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemcpyAsync(e->positions, pos0.data(), (size_t)n_seq * sizeof(int32_t), hipMemcpyHostToDevice, st));
     e->dbg_pos_hi += K1;
+    e->ctx_known = false;
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(st));
     return 0;

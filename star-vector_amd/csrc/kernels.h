@@ -360,6 +360,21 @@ int init_attention_kernels();   // returns a hipError_t value (0 = ok)
 // either pool format (csrc/kv8/kv8.hip)
 struct KvReadArgs { const char* pool_layer; size_t kv_head_stride; const int32_t* table_row; int n_kv, head_dim, first, count, kv_fmt; bf16_t* out; };
 void launch_kv_read(const KvReadArgs& a, hipStream_t st);
+// The extension pass's two page kernels (csrc/extend/extend.hip), one layer, grid (n_blocks, n_kv).  xseq: one descriptor per sequence of the pass,
+// {block-table row, first packed own row, ctx, len, first row of its region of gkv or -1, 0}; blocks: {descriptor, 32-token group} x n_blocks.
+//   launch_kv_gather        tokens [0, ctx) of every listed group, pages of either format -> rows region + token of gkv (bf16 [..][gkv_stride]:
+//                           k heads | v heads), as the decode attention sees them
+//   launch_kv_write_extend  the own rows (packed rows of qkv, K at column k_off + head * head_dim, V at v_off + ...) -> pages at positions ctx + j, every
+//                           cached token's bytes kept; and, unquantised, -> rows region + ctx + j of gkv (region -1: no copy)
+struct ExtKvArgs {
+    const bf16_t* qkv; int row_stride, k_off, v_off;
+    char* pool_layer; size_t kv_head_stride; const int32_t* table; int max_pages;
+    const int32_t* xseq; const int32_t* blocks; int n_blocks;
+    int head_dim, n_kv, kv_fmt;
+    bf16_t* gkv; int gkv_stride;
+};
+void launch_kv_gather(const ExtKvArgs& a, hipStream_t st);
+void launch_kv_write_extend(const ExtKvArgs& a, hipStream_t st);
 
 // ---- sampling -----------------------------------------------------------------------------------
 // greedy selection: per-slice winners (pval/pidx: [B][8]) then a merge (standalone, or inside finish_step)

@@ -87,6 +87,8 @@ class EngineConfig:
                                      # all-blocks-resident fused launches (include/starvector_hip.h sv_config.exclusive_device); same tokens
     kv_dtype: str = "bf16"           # the paged KV cache's format: "bf16", or "fp8_e4m3" -- e4m3 codes and one power-of-two scale per key and
                                      # head, half the pool and half the decode attention's stream (sv_create_kv; not a reference numerics mode)
+    prefill_chunk_rows: int = 0      # row budget of the prompt passes (HipEngine.set_prefill_chunk, applied after creation; 0 = the environment's
+                                     # SV_PREFILL_CHUNK_ROWS, else off): same tokens, prompt-pass workspaces bounded by the budget
 
     @property
     def query_length(self) -> int:
@@ -196,6 +198,23 @@ def kv_dtype_code(kv_dtype) -> int:
     return KV_DTYPES[resolve_kv_dtype(kv_dtype)]
 
 
+def prefill_chunk_rows(prefill_chunk_rows=None) -> int:
+    """The row budget of the prompt passes (sv_set_prefill_chunk): 0 = off, n >= 1 = at most n own rows per pass.  None = the environment's
+    SV_PREFILL_CHUNK_ROWS, else 0."""
+    v = prefill_chunk_rows
+    if v is None:
+        v = os.environ.get("SV_PREFILL_CHUNK_ROWS") or 0
+    try:
+        if isinstance(v, (bool, float)):
+            raise ValueError
+        n = int(v)
+    except (TypeError, ValueError):
+        raise ValueError(f"prefill_chunk_rows must be an int >= 0 (0 = off), got {v!r}") from None
+    if n < 0:
+        raise ValueError(f"prefill_chunk_rows must be an int >= 0 (0 = off), got {v!r}")
+    return n
+
+
 def kv_page_bytes(kv_dtype, head_dim: int) -> int:
     """Bytes of one KV page (64 tokens of one layer and KV head): bf16 K | V, or e4m3 codes + one scale byte per token for K and for V."""
     return 64 * head_dim * 2 + 128 if kv_dtype_code(kv_dtype) else 64 * head_dim * 2 * 2
@@ -251,6 +270,9 @@ class HipEngine:
         # threads from interleaving their call sequences (thread B's cb_reset would release thread A's slots).
         self.call_lock = threading.RLock()
         self._cb_lp_k = {}                   # slot -> the k its current holder records with (cb_read_logprobs sizes its buffers by it)
+        rows = prefill_chunk_rows(getattr(cfg, "prefill_chunk_rows", 0) or None)      # 0 in the config: the environment's default, else off
+        if rows:
+            self.set_prefill_chunk(rows)
 
     def kv_info(self) -> dict:
         """The KV cache's format, the bytes of one page (64 tokens of one layer and KV head) and of the whole pool (sv_kv_info)."""
@@ -440,6 +462,38 @@ class HipEngine:
         logits = torch.empty(len(lens), self.cfg.vocab, dtype=torch.float32, device=x.device)
         check(self.lib.sv_prefill_ragged(self._h, _ptr(x), len(lens), arr, _ptr(logits), _stream()), "sv_prefill_ragged")
         return logits
+
+    def prefill_open(self, total_lens) -> None:
+        """Assign pages for sequences of these total lengths; every context becomes 0, nothing is computed (sv_prefill_open)."""
+        tl = [int(v) for v in total_lens]
+        check(self.lib.sv_prefill_open(self._h, len(tl), (C.c_int32 * max(len(tl), 1))(*tl)), "sv_prefill_open")
+
+    def prefill_extend(self, embeds_packed, lens, total_lens=None) -> torch.Tensor:
+        """Append lens[b] >= 0 rows to cached sequence b (sv_prefill_extend): `embeds_packed` the new rows back to back [sum(lens), D] (or a
+        list of [n_i, D] tensors, one per sequence with lens[b] > 0).  `total_lens` states the length of the sequence each belongs to (None: the
+        free extension, context + lens).  Returns logits [B, vocab]: the rows of the sequences this call brings to their total length hold their
+        last-row logits, the other rows are NaN.  `decode_step` and further extensions continue every row at its own position."""
+        ln = [int(v) for v in lens]
+        if isinstance(embeds_packed, (list, tuple)):
+            embeds_packed = torch.cat([t.reshape(-1, t.shape[-1]) for t in embeds_packed], dim=0)
+        x = _need(embeds_packed, torch.bfloat16, "embeds_packed")
+        if x.dim() != 2 or x.shape[1] != self.cfg.hidden or (ln and min(ln) >= 0 and sum(ln) != x.shape[0]):
+            raise ValueError(f"embeds_packed must be [sum(lens) = {sum(ln)}, {self.cfg.hidden}], got {list(x.shape)}")
+        tl = None
+        if total_lens is not None:
+            tl = [int(v) for v in total_lens]
+            if len(tl) != len(ln):
+                raise ValueError("total_lens: one total length per sequence")
+        ints = lambda v: (C.c_int32 * max(len(v), 1))(*v)
+        logits = torch.full((len(ln), self.cfg.vocab), float("nan"), dtype=torch.float32, device=x.device)
+        check(self.lib.sv_prefill_extend(self._h, _ptr(x), len(ln), ints(ln), ints(tl) if tl is not None else None, _ptr(logits), _stream()),
+              "sv_prefill_extend")
+        return logits
+
+    def set_prefill_chunk(self, rows: int) -> None:
+        """Row budget of every prompt pass with a generate tail (sv_set_prefill_chunk): 0 = off; rows > 0: a pass of more packed rows runs as
+        several passes of at most `rows` own rows over the cache, with the same logits, pages and tokens."""
+        check(self.lib.sv_set_prefill_chunk(self._h, prefill_chunk_rows(rows)), "sv_set_prefill_chunk")
 
     def generate_ragged(self, embeds, max_length: int, lengths=None, **kw):
         """`generate` over prompts of different lengths in ONE prompt pass (sv_generate_ragged): HF's padded-batch semantics, `max_length`
@@ -1034,6 +1088,14 @@ class HipEngine:
         check(self.lib.sv_debug_kv_read(self._h, int(layer), int(row), int(first), int(count), _ptr(out), _stream()), "sv_debug_kv_read")
         return out
 
+    def debug_kv_gather(self, layer: int, row: int, count: int) -> torch.Tensor:
+        """Tokens [0, count) of decode row `row` of `layer` through the extension pass's pages -> rows launch (sv_debug_kv_gather): the
+        layout and the bits of `debug_kv_read(layer, row, 0, count)`."""
+        width = 2 * (self.cfg.n_kv_head if self.cfg.arch == "v2" else 1) * (self.cfg.hidden // self.cfg.n_head)
+        out = torch.empty(int(count), width, dtype=torch.bfloat16, device=self._dev)
+        check(self.lib.sv_debug_kv_gather(self._h, int(layer), int(row), int(count), _ptr(out), _stream()), "sv_debug_kv_gather")
+        return out
+
     def debug_attn_decode(self, layer: int, qkv: torch.Tensor, advance: bool = True) -> torch.Tensor:
         """One launch of the decode attention of `layer` for the new token whose c_attn output is qkv [B, QKV] float32 (before
         RoPE); returns [B, n_head * head_dim] bf16 and (advance) steps the positions, so repeated calls walk the sequence."""
@@ -1360,6 +1422,38 @@ def ragged_plan(lengths: Sequence[int], N: int, K: int, act: str = "none", q_til
     check(_lib.load().sv_debug_ragged_plan((C.c_int32 * max(B, 1))(*lens), B, int(N), int(K), _lib.ACT[act], int(q_tile), rows, last, cap, out),
           "sv_debug_ragged_plan")
     return {"rows": list(rows)[: out[0]], "last": list(last)[: out[1]], "attn_blocks": out[2], "kv_blocks": out[3]}
+
+
+def extend_plan(contexts: Sequence[int], lengths: Sequence[int], totals: Optional[Sequence[int]], N: int, K: int, act: str = "none",
+                q_tile: int = 32, budget: int = 0) -> List[Dict[str, object]]:
+    """What an extension call decides at the projection (N, K, act) under a row budget (sv_debug_extend_plan; host arithmetic, no GPU): one
+    dict per pass -- "seqs" [(b, context before the pass, rows, first packed row)], "rows" the packed rows that take the split-K remainder
+    kernel, "tiles" [(b, query tile)] of the attention, "groups" [(b, 32-token group)] the page writer touches, "fin" the sequences that reach
+    their total length."""
+    cx, ln = [int(v) for v in contexts], [int(v) for v in lengths]
+    tl = None if totals is None else [int(v) for v in totals]
+    if len(cx) != len(ln) or (tl is not None and len(tl) != len(ln)):
+        raise ValueError("one context, length and total per sequence")
+    ints = lambda v: (C.c_int32 * max(len(v), 1))(*v)
+    n = C.c_int32(0)
+    args = (ints(cx), ints(ln), ints(tl) if tl is not None else None, len(ln), int(budget), int(N), int(K), _lib.ACT[act], int(q_tile))
+    lib = _lib.load()
+    rc = lib.sv_debug_extend_plan(*args, (C.c_int32 * 1)(), 0, C.byref(n))
+    if rc != 0 and n.value == 0:
+        check(rc, "sv_debug_extend_plan")
+    out = (C.c_int32 * n.value)()
+    check(lib.sv_debug_extend_plan(*args, out, n.value, C.byref(n)), "sv_debug_extend_plan")
+    o, i, passes = list(out), 1, []
+
+    def take(width):
+        nonlocal i
+        cnt = o[i]
+        vals = o[i + 1: i + 1 + cnt * width]
+        i += 1 + cnt * width
+        return vals if width == 1 else [tuple(vals[j: j + width]) for j in range(0, len(vals), width)]
+    for _ in range(o[0]):
+        passes.append({"seqs": take(4), "rows": take(1), "tiles": take(2), "groups": take(2), "fin": take(1)})
+    return passes
 
 
 def prefix_plan(prefix_lengths: Sequence[int], lengths: Sequence[int], prefix_of: Sequence[int], N: int, K: int, act: str = "none",

@@ -29,7 +29,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 import torch.nn as nn
 
-from .engine import EngineConfig, HipEngine, resolve_kv_dtype, resolve_weight_dtype
+from .engine import EngineConfig, HipEngine, prefill_chunk_rows as resolve_prefill_chunk_rows, resolve_kv_dtype, resolve_weight_dtype
 
 # Set while the calling thread runs an exclusive job of a ContinuousBatcher (beam search, multi-row batches): inside it the
 # mirror talks to the engine directly; every OTHER thread keeps going through the batcher's queue.
@@ -104,7 +104,7 @@ class StarVectorConfig:
                  n_inner: Optional[int] = None, n_positions: Optional[int] = None, added_tokens: Optional[int] = None,
                  vit_width: int = 1024, vit_layers: int = 23, vit_heads: int = 16, patch_size: int = 14,
                  max_batch: int = 32, exclusive_device: Optional[bool] = None, weight_dtype: Optional[str] = None,
-                 kv_cache_dtype: Optional[str] = None, **kwargs):
+                 kv_cache_dtype: Optional[str] = None, prefill_chunk_rows: Optional[int] = None, **kwargs):
         self.starcoder_model_name = starcoder_model_name
         self.image_encoder_type = image_encoder_type
         self.adapter_norm = adapter_norm
@@ -139,6 +139,8 @@ class StarVectorConfig:
         # KV-cache format: "bf16" / "auto" (the reference's precision) or "fp8_e4m3" / "fp8" (EngineConfig.kv_dtype).  None = the environment's
         # SV_KV_DTYPE, else "bf16"
         self.kv_cache_dtype = resolve_kv_dtype(kv_cache_dtype)
+        # row budget of the prompt passes (EngineConfig.prefill_chunk_rows; 0 = off).  None = the environment's SV_PREFILL_CHUNK_ROWS, else 0
+        self.prefill_chunk_rows = resolve_prefill_chunk_rows(prefill_chunk_rows)
         for k, v in kwargs.items():
             setattr(self, k, v)
 
@@ -186,7 +188,8 @@ class StarVectorConfig:
                                 # keys) mirrors: "flash_attention_2" (default: what the reference runs) or "sdpa".
                                 sliding_window=self._visible_keys(g("sliding_window", 4096), g("window_semantics", "flash_attention_2")),
                                 exclusive_device=self.exclusive_device, weight_dtype=resolve_weight_dtype(self.weight_dtype),
-                                kv_dtype=resolve_kv_dtype(getattr(self, "kv_cache_dtype", None)))
+                                kv_dtype=resolve_kv_dtype(getattr(self, "kv_cache_dtype", None)),
+                                prefill_chunk_rows=resolve_prefill_chunk_rows(getattr(self, "prefill_chunk_rows", None)))
         if self.image_encoder_type != "clip":
             raise NotImplementedError(f"image_encoder_type={self.image_encoder_type!r}: v1 is built for the clip branch")
         return EngineConfig(image_size=self.image_size, patch_size=self.patch_size, vit_width=self.vit_width,
@@ -196,7 +199,8 @@ class StarVectorConfig:
                             n_positions=self.n_positions, max_batch=self.max_batch,
                             max_seq_len=min(self.max_length, self.n_positions), exclusive_device=self.exclusive_device,
                             weight_dtype=resolve_weight_dtype(self.weight_dtype),
-                                kv_dtype=resolve_kv_dtype(getattr(self, "kv_cache_dtype", None)))
+                                kv_dtype=resolve_kv_dtype(getattr(self, "kv_cache_dtype", None)),
+                                prefill_chunk_rows=resolve_prefill_chunk_rows(getattr(self, "prefill_chunk_rows", None)))
 
 
 def config_from_checkpoint(cfg_json: Dict, shapes: Dict[str, tuple]) -> StarVectorConfig:

@@ -120,7 +120,7 @@ class ModelWorker:
                  model_name: Optional[str] = None, device="cuda", limit_model_concurrency: int = 5, *,
                  model=None, tokenizer=None, image_processor=None, context_len: Optional[int] = None,
                  continuous_batching: bool = True, prompt_lookup_num_tokens: int = 0, max_matching_ngram_size: int = 0,
-                 weight_dtype: Optional[str] = None, kv_cache_dtype: Optional[str] = None):
+                 weight_dtype: Optional[str] = None, kv_cache_dtype: Optional[str] = None, prefill_chunk_rows: Optional[int] = None):
         self.controller_addr, self.worker_addr, self.worker_id = controller_addr, worker_addr, worker_id
         model_path = model_path[:-1] if model_path.endswith("/") else model_path
         if model_name is None:                                         # :46-52
@@ -132,7 +132,8 @@ class ModelWorker:
         self.device = device
         if model is None:
             tokenizer, model, image_processor, context_len = load_pretrained_model(model_path, device=device, **({"weight_dtype": weight_dtype} if weight_dtype else {}),
-                                                                                        **({"kv_cache_dtype": kv_cache_dtype} if kv_cache_dtype else {}))
+                                                                                        **({"kv_cache_dtype": kv_cache_dtype} if kv_cache_dtype else {}),
+                                                                                        **({"prefill_chunk_rows": prefill_chunk_rows} if prefill_chunk_rows is not None else {}))
         self.tokenizer, self.model, self.image_processor, self.context_len = tokenizer, model, image_processor, context_len
         self.is_multimodal = "starvector" in model_name.lower()       # :66
         # The reference admits `limit_model_concurrency` requests at once and lets their generate calls take turns on the GPU
@@ -325,7 +326,12 @@ def main(argv=None):                                                   # :235-26
                    help="decoder weight format (default: SV_WEIGHT_DTYPE, else bf16); fp8 / mxfp4 quantise at load and are not the reference's precision")
     p.add_argument("--kv-cache-dtype", type=str, default=None, choices=["auto", "bf16", "fp8", "fp8_e4m3"],
                    help="KV-cache format (default: SV_KV_DTYPE, else bf16); fp8 halves the cache and is not the reference's precision")
+    p.add_argument("--prefill-chunk-rows", type=int, default=None,
+                   help="row budget of a prompt pass (default: SV_PREFILL_CHUNK_ROWS, else 0 = off): longer prompt passes run in pieces over the KV "
+                        "cache with the same tokens, and the prompt-pass workspaces are sized by the budget")
     args = p.parse_args(argv)
+    if args.prefill_chunk_rows is not None and args.prefill_chunk_rows < 0:
+        p.error("--prefill-chunk-rows must be >= 0")
     if args.prompt_lookup_num_tokens and args.no_continuous_batching:
         p.error("--prompt-lookup-num-tokens drafts in the continuous batch: drop --no-continuous-batching")
     import uvicorn
@@ -333,7 +339,7 @@ def main(argv=None):                                                   # :235-26
                          args.model_path, args.model_name, args.device, args.limit_model_concurrency,
                          continuous_batching=not args.no_continuous_batching, prompt_lookup_num_tokens=args.prompt_lookup_num_tokens,
                          max_matching_ngram_size=args.max_matching_ngram_size, weight_dtype=args.weight_dtype,
-                         kv_cache_dtype=args.kv_cache_dtype)
+                         kv_cache_dtype=args.kv_cache_dtype, prefill_chunk_rows=args.prefill_chunk_rows)
     uvicorn.run(build_app(worker), host=args.host, port=args.port, log_level="info")
 
 
