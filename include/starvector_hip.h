@@ -652,6 +652,27 @@ int  sv_cb_set_lookup(sv_engine* e, const sv_lookup* lookup);
 /* {verification steps, drafts verified, drafts accepted} of a slot since its admit; slot = -1: totals since the batch began (steps summed over
  * the slots: one per live slot and step).  Host array of 3.  All zero while drafting is off. */
 int  sv_cb_lookup_counts(sv_engine* e, int32_t slot, int32_t* host_counts3);
+/* A prefix cache for the continuous batch (entry points appended; SV_ABI_VERSION and every struct are unchanged).  Off by default; with it off
+ * every sv_cb_* call issues exactly the launches and takes exactly the pages it takes without these entry points.  With it on, every admit form
+ * (sv_cb_admit, _ragged, _shared, _logprobs; with or without sv_cb_set_lookup and sv_set_prefill_chunk) first digests the full 64-row pages of its
+ * prompts on the device (one launch, one copy to the host), chains the digests into keys -- a key stands for "these exact rows at these exact
+ * positions behind exactly this prefix" -- and looks them up in a table of the prompt pages earlier admits of this batch computed.  A prompt of L
+ * rows reuses h = min(leading pages found, (L - 1) / 64) pages: they enter the block-table rows of its slots read-only (held once per slot, as
+ * shared prompt pages are), only the other pages leave the free list, and the prompt pass computes rows 64 h .. L - 1 behind the cached context.
+ * After the pass every full prompt page, computed or reused, stands in the table under its key (a key already present keeps its page; the partial
+ * tail page never enters).  A released slot's cached pages stay resident while no admit needs them: pages without a holder are evicted least
+ * recently released first when the free list is short, pages with a holder never; SV_EBUSY only when free + evictable pages are short, so an
+ * admit never fails with the cache on where it succeeds with it off.  A failed admit registers nothing and gives back the holders it added.
+ * The contract: on a bf16-KV engine everything of a request -- every token, its finish, its log-prob record, the K / V bytes of its own pages --
+ * is bit for bit what the same request returns with the cache off, whatever was cached before and whatever is evicted meanwhile.
+ * Keys are 128 bits and a hit is not verified against the rows.  The table lives until sv_cb_reset (sv_load_weight drops it too).
+ * sv_cb_set_prefix_cache: only while no continuous batch is active (SV_ESTATE otherwise); the setting stays across sv_cb_reset.  SV_ENOTSUP on an
+ * fp8_e4m3 KV engine (a pass behind cached pages sees the dequantised cache, a one-shot pass the unquantised rows: the tokens could differ) and
+ * while the A/B arm SV_EXP_BATCH_REMAINDER is selected.
+ * sv_cb_prefix_cache_info: host array of 5 = {full prompt pages looked up, pages reused, pages resident in the table, of those without a holder,
+ * evictions} since the batch began; all 0 while off. */
+int  sv_cb_set_prefix_cache(sv_engine* e, int32_t enable);
+int  sv_cb_prefix_cache_info(sv_engine* e, int64_t* host_out5);
 
 /* beam scorer: one step consumes dev_logits [batch * num_beams][ld] (row r = request r / num_beams, beam r % num_beams)
  * and reports (host arrays, each batch * num_beams long, may be NULL) the flat parent row, the token and the running

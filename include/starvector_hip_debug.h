@@ -220,6 +220,16 @@ int  sv_debug_kv_read(sv_engine* e, int32_t layer, int32_t row, int32_t first, i
 /*   sv_debug_kv_gather   tokens [0, count) of decode row `row` of `layer` through the extension pass's pages -> rows launch (kv_gather_kernel, whole
      1 KiB fragment loads) -> dev_out_bf16 [count][2*n_kv*head_dim]: bit for bit what sv_debug_kv_read returns for them, either format.  Blocks. */
 int  sv_debug_kv_gather(sv_engine* e, int32_t layer, int32_t row, int32_t count, void* dev_out_bf16, sv_stream stream);
+/*   sv_debug_page_digests  the prefix cache's digest launch on its own (page_digest_kernel; no engine): n prompts of bf16 rows of `hidden`
+     elements packed back to back in dev_embeds_packed (16-byte aligned), host_lens [n] their lengths or NULL = n x S0 rows; host_out
+     [n][max_pages][2] uint64 = the digest of page k of prompt u for k < len_u / 64, zeros beyond.  Blocks.
+     sv_debug_prefix_hit    host arithmetic, no device: chains the n_pages = L / 64 digests host_digests [n_pages][2] of a prompt of L rows into its
+     keys (host_keys_out [n_pages][2], may be NULL) and returns in *h_out the pages an admit reuses against a table holding the n_table keys
+     host_table_keys [n_table][2]: min(leading keys found, (L - 1) / 64). */
+int  sv_debug_page_digests(const void* dev_embeds_packed, int32_t n, const int32_t* host_lens, int32_t S0, int32_t hidden, int32_t max_pages,
+                           uint64_t* host_out, sv_stream stream);
+int  sv_debug_prefix_hit(const uint64_t* host_digests, int32_t n_pages, int32_t L, const uint64_t* host_table_keys, int32_t n_table,
+                         uint64_t* host_keys_out, int32_t* h_out);
 int  sv_debug_attn_decode(sv_engine* e, int32_t layer, const float* dev_qkv_f32, int32_t B, void* dev_out, int32_t advance,
                           sv_stream stream);
 int  sv_debug_attn_decode_slabs(sv_engine* e, int32_t layer, const float* dev_slabs_f32, int32_t splitk, const void* dev_bias, int32_t B,

@@ -184,6 +184,8 @@ PRODUCT_PROTOTYPES = {
     "sv_cb_read_logprobs": (_I, [_P, _I, _I, _I, C.POINTER(_F), C.POINTER(_I), C.POINTER(_I), C.POINTER(_F)]),
     "sv_cb_set_lookup": (_I, [_P, C.POINTER(SvLookup)]),
     "sv_cb_lookup_counts": (_I, [_P, _I, C.POINTER(_I)]),
+    "sv_cb_set_prefix_cache": (_I, [_P, _I]),
+    "sv_cb_prefix_cache_info": (_I, [_P, C.POINTER(C.c_int64)]),
     "sv_beam_create": (_I, [C.POINTER(SvBeamConfig), C.POINTER(_P)]),
     "sv_beam_destroy": (_I, [_P]),
     "sv_beam_step": (_I, [_P, _P, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_F), _P]),
@@ -213,6 +215,8 @@ DEBUG_PROTOTYPES = {
     "sv_debug_prompt_passes": (_I, [_P, C.POINTER(C.c_int64)]),
     "sv_debug_extend_plan": (_I, [C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _I, _I, _I, _I, _I, _I, C.POINTER(_I), _I, C.POINTER(_I)]),
     "sv_debug_kv_gather": (_I, [_P, _I, _I, _I, _P, _P]),
+    "sv_debug_page_digests": (_I, [_P, _I, C.POINTER(_I), _I, _I, _I, C.POINTER(C.c_uint64), _P]),
+    "sv_debug_prefix_hit": (_I, [C.POINTER(C.c_uint64), _I, _I, C.POINTER(C.c_uint64), _I, C.POINTER(C.c_uint64), C.POINTER(_I)]),
     "sv_debug_shared_plan": (_I, [C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(_I), _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_int64)]),
     "sv_debug_block_table": (_I, [_P, _I, C.POINTER(_I), _I]),
     "sv_debug_free_pages": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),

@@ -19,6 +19,10 @@ what a solo `HipEngine.generate` call would return for it (tests/test_gpu_servin
 ``prompt_lookup_num_tokens=K`` switches on prompt-lookup drafting for the whole batch (`HipEngine.cb_set_lookup`): a step verifies up to K
 drafted tokens per request and emits 1 .. K + 1 of them, the tokens of every request stay what they are without it, and the batch holds
 max_batch // (K + 1) requests -- at the reference worker's 5 concurrent requests the other rows of a 32- or 64-row engine are idle anyway.
+
+``prefix_cache=True`` switches on the engine's prefix cache for the batch (`HipEngine.cb_set_prefix_cache`): the full KV pages of a prompt stay
+findable -- by digests of its embedding rows -- after its request has left, and a later request with the same leading rows (the same image
+again, the next part of a group that did not fit at once, the next temperature of a sweep) computes only what lies behind them.  Same tokens.
 """
 from __future__ import annotations
 
@@ -87,7 +91,7 @@ class ContinuousBatcher:
     """engine: a `HipEngine` (or anything with cb_admit / cb_step / cb_poll / cb_read / cb_release / cb_reset and `.cfg`)."""
 
     def __init__(self, engine, steps_per_poll: int = 8, device: Optional[int] = None, prompt_lookup_num_tokens: int = 0,
-                 max_matching_ngram_size: int = 0, min_matching_ngram_size: int = 0):
+                 max_matching_ngram_size: int = 0, min_matching_ngram_size: int = 0, prefix_cache: bool = False):
         self.engine = engine
         self.steps_per_poll = int(steps_per_poll)
         self.device = getattr(engine, "device", 0) if device is None else device
@@ -102,6 +106,12 @@ class ContinuousBatcher:
                 raise NotImplementedError(f"prompt_lookup_num_tokens {self.lookup_k} + 1 rows per request exceed max_batch {engine.cfg.max_batch}")
             engine.cb_reset()
             engine.cb_set_lookup(self.lookup_k, int(max_matching_ngram_size or 0), int(min_matching_ngram_size or 0))
+        # the prefix cache (sv_cb_set_prefix_cache), set before the first admit like the drafting: a prompt whose leading rows an earlier
+        # request of the batch brought reuses that request's full KV pages and computes only the rows behind them -- the same tokens
+        self.prefix_cache = bool(prefix_cache)
+        if self.prefix_cache:
+            engine.cb_reset()
+            engine.cb_set_prefix_cache(True)
         self._lock = threading.Condition()
         self._pending: Deque[_Request] = deque()
         self._active: Dict[int, _Request] = {}
@@ -170,6 +180,12 @@ class ContinuousBatcher:
         if not self.lookup_k:
             return {"steps": 0, "drafted": 0, "accepted": 0}
         return self.engine.cb_lookup_counts(-1)
+
+    def prefix_cache_info(self) -> dict:
+        """`HipEngine.cb_prefix_cache_info` of the running batch; zeros while the cache is off."""
+        if not self.prefix_cache:
+            return {"lookups": 0, "reused": 0, "resident": 0, "unheld": 0, "evictions": 0}
+        return self.engine.cb_prefix_cache_info()
 
     def queue_length(self) -> int:
         with self._lock:

@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libstarvector_hip.so")
 SOURCES = ["gemm_pack.hip", "gemm.hip", "mlp_fused.hip", "decode_cols.hip", "rowops.hip", "attention.hip", "sampling.hip", "processors.hip", "score.hip", "beam.hip", "fork.hip", "preprocess.hip", os.path.join("lookup", "lookup.hip"),
-           os.path.join("lookup_sampled", "lookup_sampled.hip"), os.path.join("cb_lookup", "cb_lookup.hip"), os.path.join("mxfp4", "mxfp4.hip"), os.path.join("prefix", "prefix.hip"), os.path.join("kv8", "kv8.hip"), os.path.join("extend", "extend.hip"), "engine_core.hip", "engine_forward.hip", "engine_generate.hip", "engine_cb.hip", "engine_ops.hip"]
+           os.path.join("lookup_sampled", "lookup_sampled.hip"), os.path.join("cb_lookup", "cb_lookup.hip"), os.path.join("mxfp4", "mxfp4.hip"), os.path.join("prefix", "prefix.hip"), os.path.join("kv8", "kv8.hip"), os.path.join("extend", "extend.hip"), os.path.join("prefix_cache", "prefix_cache.hip"), "engine_core.hip", "engine_forward.hip", "engine_generate.hip", "engine_cb.hip", "engine_ops.hip"]
 HEADERS = ["common.h", "kernels.h", "skinny_dev.h", "beam.h", "warp.h", "sample_row.h", "topk.h", "cb_row.h", os.path.join("lookup", "lk_draft.h"), os.path.join("kv8", "kv8_dev.h"), "engine_internal.h", os.path.join("..", "..", "include", "starvector_hip.h"),
            os.path.join("..", "..", "include", "starvector_hip_debug.h")]
 # -amdgpu-kernarg-preload-count: leading scalar / pointer kernel parameters arrive in SGPRs with the dispatch (gfx950) instead

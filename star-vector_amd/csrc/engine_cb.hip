@@ -153,9 +153,130 @@ void cb_fill_slot(const sv_cb_request& r, CbSlot& h, CbBias& bias, std::vector<u
 }
 }  // namespace sveng
 
+// ------------------------------------------------------------------------------------------------
+// The prefix cache (sv_cb_set_prefix_cache; keys and digests: prefix_cache/prefix_cache.hip).  Host bookkeeping over the page pool:
+//   * pc_table maps the chained key of a full prompt page to the page that holds its K / V.  A registered page's page_refs entry is its exact
+//     holder count (a private page, 0 elsewhere, becomes 1 when it is registered; cb_release_locked treats both alike).
+//   * a registered page whose last holder lets go joins the back of pc_lru instead of the free list; an admit that is short of free pages evicts
+//     from the front.  Pages with a holder are never evicted.
+//   * nothing here touches the device: a cached page is read by later prompt passes and never written (kv_write_extend_kernel starts at ctx).
+// ------------------------------------------------------------------------------------------------
+static void pc_lru_remove(sv_engine* e, int pg) {
+    if (!e->pc_in_lru[pg]) return;
+    e->pc_lru.erase(e->pc_lru_it[pg]);
+    e->pc_in_lru[pg] = 0;
+}
+static void pc_lru_push(sv_engine* e, int pg) {
+    e->pc_lru.push_back(pg);
+    e->pc_lru_it[pg] = std::prev(e->pc_lru.end());
+    e->pc_in_lru[pg] = 1;
+}
+static void pc_unregister(sv_engine* e, int pg) {
+    e->pc_table.erase(e->pc_key_of[pg]);
+    e->pc_reg[pg] = 0;
+}
+void sveng::pc_drop(sv_engine* e) {
+    // (pages nobody holds are free again; held ones simply stop being findable and go to the free list when their slots release them)
+    for (int pg : e->pc_lru) { e->pc_in_lru[pg] = 0; e->free_pages.push_back(pg); }
+    e->pc_lru.clear();
+    e->pc_table.clear();
+    std::fill(e->pc_reg.begin(), e->pc_reg.end(), 0);
+}
+
+// What the cache decides for the U prompts of an admit, before any page moves: the keys of every full page and the pages found in the table as
+// it stood before the call.
+struct PcAdmit {
+    std::vector<std::vector<PcKey>> keys;            // [U][len / 64]
+    std::vector<std::vector<int>> pages;             // [U][h]: the reused pages
+    std::vector<int> holders;                        // a page once per holder this admit added (a failed admit takes them back)
+    bool any_hit = false;
+    int h(int u) const { return (int)pages[u].size(); }
+};
+
+// the digest launch over the admit's prompts, the copy to the host (the admit is synchronous anyway), the chains and the walk
+static int pc_lookup(sv_engine* e, const void* dev_embeds, int U, int S0_all, const int32_t* lens, PcAdmit& pc, hipStream_t st) {
+    const int mp = e->pages_per_seq;
+    pc.keys.assign(U, {}); pc.pages.assign(U, {});
+    int most = 0;
+    std::vector<int32_t> desc;
+    for (int u = 0, r0 = 0; u < U; ++u) {
+        const int len = lens ? lens[u] : S0_all;
+        most = std::max(most, len / SV_PAGE_TOKENS);
+        desc.push_back(r0); desc.push_back(len);
+        r0 += len;
+    }
+    if (most == 0) return 0;      // no prompt has a full page
+    if (lens) HIPCHECK(hipMemcpyAsync(e->pc_desc, desc.data(), desc.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    SVCHECK(pc_launch_digests((const bf16_t*)dev_embeds, U, lens ? e->pc_desc : nullptr, S0_all, e->cfg.hidden, mp, e->pc_dig, st));
+    std::vector<uint64_t> dig((size_t)U * mp * 2);
+    HIPCHECK(hipMemcpyAsync(dig.data(), e->pc_dig, dig.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    for (int u = 0; u < U; ++u) {
+        const int len = lens ? lens[u] : S0_all;
+        PcKey key = pc_key0();
+        int matched = 0;
+        std::vector<int> found;
+        for (int k = 0; k < len / SV_PAGE_TOKENS; ++k) {
+            const uint64_t* d = dig.data() + 2 * ((size_t)u * mp + k);
+            key = pc_chain(key, PcKey{d[0], d[1]});
+            pc.keys[u].push_back(key);
+            if (matched != k) continue;
+            const auto it = e->pc_table.find(key);
+            if (it != e->pc_table.end()) { ++matched; found.push_back(it->second); }
+        }
+        found.resize((size_t)pc_hit_pages(matched, len));
+        pc.pages[u] = std::move(found);
+        pc.any_hit = pc.any_hit || !pc.pages[u].empty();
+    }
+    return 0;
+}
+
+// Room for an admit that takes `need` pages from the free list and reuses pc's pages: SV_EBUSY -- nothing has moved -- when the free pages and the
+// evictable ones (cached, no holder, not reused by this admit) are short; otherwise the reused pages leave the LRU list and the oldest others are
+// evicted until the free list holds `need`.  pc == nullptr (the cache is off): the free list alone decides, as ever.
+static bool pc_make_room(sv_engine* e, size_t need, const PcAdmit* pc) {
+    if (!pc) return need <= e->free_pages.size();
+    size_t keep = 0;
+    std::vector<char> seen((size_t)e->num_pages + 1, 0);
+    for (const std::vector<int>& v : pc->pages)
+        for (int pg : v) if (e->pc_in_lru[pg] && !seen[pg]) { seen[pg] = 1; ++keep; }
+    if (e->free_pages.size() + (e->pc_lru.size() - keep) < need) return false;
+    for (const std::vector<int>& v : pc->pages) for (int pg : v) pc_lru_remove(e, pg);
+    while (e->free_pages.size() < need) {
+        const int pg = e->pc_lru.front();
+        pc_lru_remove(e, pg);
+        pc_unregister(e, pg);
+        e->free_pages.push_back(pg);
+        ++e->pc_evictions;
+    }
+    return true;
+}
+
+// after a successful prompt pass: every full prompt page, computed or reused, under its key -- a key already present keeps its page
+static void pc_register(sv_engine* e, const PcAdmit& pc, const std::vector<int32_t>& pf) {
+    const int mp = e->pages_per_seq;
+    for (size_t u = 0; u < pc.keys.size(); ++u) {
+        e->pc_lookups += (long long)pc.keys[u].size();
+        e->pc_reused += pc.h((int)u);
+        for (size_t k = 0; k < pc.keys[u].size(); ++k) {
+            const int pg = pf[u * mp + k];
+            if (!e->pc_table.emplace(pc.keys[u][k], pg).second) continue;
+            e->pc_key_of[pg] = pc.keys[u][k];
+            e->pc_reg[pg] = 1;
+            if (e->page_refs[pg] == 0) e->page_refs[pg] = 1;      // a private page: its one slot is its holder
+        }
+    }
+}
+
 static int cb_begin(sv_engine* e, hipStream_t st) {
     if (e->cb_active) return 0;
     reset_free_pages(e);
+    e->pc_table.clear(); e->pc_lru.clear();
+    e->pc_key_of.assign((size_t)e->num_pages + 1, PcKey{0, 0});
+    e->pc_reg.assign((size_t)e->num_pages + 1, 0);
+    e->pc_in_lru.assign((size_t)e->num_pages + 1, 0);
+    e->pc_lru_it.assign((size_t)e->num_pages + 1, e->pc_lru.end());
+    e->pc_lookups = e->pc_reused = e->pc_evictions = 0;
     std::fill(e->cb_used.begin(), e->cb_used.end(), 0);
     for (auto& v : e->cb_pages) v.clear();
     e->page_refs.assign((size_t)e->num_pages + 1, 0);
@@ -188,6 +309,9 @@ struct AdmitPlan {
     std::vector<CbBias> hb;
     std::vector<std::vector<uint32_t>> seen_rows;
     bool record = false;                             // some request records log-probs
+    PcAdmit* pc = nullptr;                           // the prefix cache's decisions for the prompts (nullptr: the cache is off)
+    // page k of prompt u comes from the cache: it gets one more holder
+    int reuse(sv_engine* e, int u, int k) { const int pg = pc->pages[u][k]; ++e->page_refs[pg]; pc->holders.push_back(pg); return pg; }
     int take(sv_engine* e) { const int pg = e->free_pages.back(); e->free_pages.pop_back(); taken.push_back(pg); return pg; }
 };
 
@@ -195,16 +319,17 @@ struct AdmitPlan {
 static int plan_plain(sv_engine* e, int n, int S0_all, const int32_t* lens, const sv_cb_request* reqs, AdmitPlan& p) {
     const int mp = e->pages_per_seq;
     auto need_of = [&](int i) { return ((lens ? lens[i] : S0_all) + reqs[i].max_new_tokens + SV_PAGE_TOKENS - 1) / SV_PAGE_TOKENS; };
+    const auto hit_of = [&](int i) { return p.pc ? p.pc->h(i) : 0; };      // leading pages the cache supplies
     size_t need_pages = 0;
-    for (int i = 0; i < n; ++i) need_pages += (size_t)need_of(i);
-    if ((int)p.slots.size() < n || need_pages > e->free_pages.size())
+    for (int i = 0; i < n; ++i) need_pages += (size_t)(need_of(i) - hit_of(i));
+    if ((int)p.slots.size() < n || !pc_make_room(e, need_pages, p.pc))
         return fail(SV_EBUSY, "sv_cb_admit: %d requests need %d slots / %zu KV pages, %zu / %zu are free (release finished slots first)",
-                    n, n, need_pages, p.slots.size(), e->free_pages.size());
+                    n, n, need_pages, p.slots.size(), e->free_pages.size() + e->pc_lru.size());
     for (int i = 0; i < n; ++i) {
         p.pos[i] = (lens ? lens[i] : S0_all) - 1;
         std::vector<int>& held = e->cb_pages[p.slots[i]];
         held.clear();
-        for (int k = 0; k < need_of(i); ++k) held.push_back(p.rows[(size_t)i * mp + k] = p.take(e));
+        for (int k = 0; k < need_of(i); ++k) held.push_back(p.rows[(size_t)i * mp + k] = k < hit_of(i) ? p.reuse(e, i, k) : p.take(e));
     }
     p.pf = p.rows;      // prompt i is written through the pages of request i
     return 0;
@@ -256,16 +381,17 @@ static int plan_group(sv_engine* e, int U, const int32_t* lens, int n, const int
     const int mp = e->pages_per_seq, mb = e->cfg.max_batch;
     std::vector<int32_t> budgets(n), n_sh(n), n_pv(n);
     for (int i = 0; i < n; ++i) budgets[i] = reqs[i].max_new_tokens;
-    const size_t need_pages = (size_t)shared_page_plan(lens, U, group, budgets.data(), n, n_sh.data(), n_pv.data());
-    if ((int)p.slots.size() < n || need_pages > e->free_pages.size())
+    size_t need_pages = (size_t)shared_page_plan(lens, U, group, budgets.data(), n, n_sh.data(), n_pv.data());
+    for (int u = 0; p.pc && u < U; ++u) need_pages -= (size_t)p.pc->h(u);      // the leading pages the cache supplies
+    if ((int)p.slots.size() < n || !pc_make_room(e, need_pages, p.pc))
         return fail(SV_EBUSY, "sv_cb_admit_shared: %d requests over %d prompts need %d slots / %zu KV pages, %zu / %zu are free (release finished slots first)",
-                    n, U, n, need_pages, p.slots.size(), e->free_pages.size());
+                    n, U, n, need_pages, p.slots.size(), e->free_pages.size() + e->pc_lru.size());
     p.pf.assign((size_t)U * mp, e->trash_page);
     p.fork.assign(6 * (size_t)mb, 0);
     std::vector<std::vector<int>> prompt_pages(U);
     std::vector<int> owner(U, -1), n_dst(U, 0);
     for (int u = 0; u < U; ++u)
-        for (int k = 0; k < lens[u] / SV_PAGE_TOKENS; ++k) prompt_pages[u].push_back(p.take(e));
+        for (int k = 0; k < lens[u] / SV_PAGE_TOKENS; ++k) prompt_pages[u].push_back(p.pc && k < p.pc->h(u) ? p.pc->pages[u][k] : p.take(e));
     for (int i = 0; i < n; ++i) {
         const int u = group[i];
         std::vector<int>& held = e->cb_pages[p.slots[i]];
@@ -273,6 +399,7 @@ static int plan_group(sv_engine* e, int U, const int32_t* lens, int n, const int
         for (int k = 0; k < n_sh[i]; ++k) {
             held.push_back(p.rows[(size_t)i * mp + k] = prompt_pages[u][k]);
             ++e->page_refs[prompt_pages[u][k]];
+            if (p.pc && k < p.pc->h(u)) p.pc->holders.push_back(prompt_pages[u][k]);
         }
         for (int k = 0; k < n_pv[i]; ++k) held.push_back(p.rows[(size_t)i * mp + n_sh[i] + k] = p.take(e));
         if (owner[u] < 0) owner[u] = i;          // the prompt pass writes prompt u through the pages of its first request
@@ -288,6 +415,26 @@ static int plan_group(sv_engine* e, int U, const int32_t* lens, int n, const int
         for (int i = 0; i < n; ++i) if (group[i] == u && i != o) p.fork[4 * (size_t)mb + d0++] = p.slots[i] * K1;
     }
     return 0;
+}
+
+// The prompt pass of an admit in which the cache supplies the first h_u pages of some prompts: prompt u runs as an extension with ctx = 64 h_u,
+// len = L_u - 64 h_u, total = L_u (h_u = 0: as a sequence without a context, the bits of the one-shot pass) through cb_table_pf.  The own rows are
+// no longer contiguous in the caller's buffer: they are compacted into pc_ws, one copy per prompt.  The chunk budget, if set, counts own rows.
+static int pc_prompt_pass(sv_engine* e, const bf16_t* embeds, int U, int S0_all, const int32_t* lens, const PcAdmit& pc, hipStream_t st) {
+    const size_t D = (size_t)e->cfg.hidden;
+    std::vector<int32_t> L((size_t)U), ctx((size_t)U);
+    size_t own = 0;
+    for (int u = 0; u < U; ++u) { L[u] = lens ? lens[u] : S0_all; ctx[u] = SV_PAGE_TOKENS * pc.h(u); own += (size_t)(L[u] - ctx[u]); }
+    if (own > e->pc_ws_rows) {
+        if (e->pc_ws) (void)hipFree(e->pc_ws);      // (waits for the launches that still read it)
+        e->pc_ws = nullptr; e->pc_ws_rows = 0;
+        HIPCHECK(hipMalloc(reinterpret_cast<void**>(&e->pc_ws), own * D * sizeof(bf16_t)));
+        e->pc_ws_rows = own;
+    }
+    for (size_t u = 0, src = 0, dst = 0; u < (size_t)U; src += L[u], dst += L[u] - ctx[u], ++u)
+        HIPCHECK(hipMemcpyAsync(e->pc_ws + dst * D, embeds + (src + ctx[u]) * D, (size_t)(L[u] - ctx[u]) * D * sizeof(bf16_t), hipMemcpyDeviceToDevice, st));
+    e->ctx_known = false;
+    return prefill_chunked(e, e->pc_ws, U, L.data(), e->cb_table_pf, st, ctx.data());
 }
 
 // The device side of an admit: the slots' state, ONE prompt pass over the U new prompts (their pages through cb_table_pf; rectangular when
@@ -325,7 +472,8 @@ static int cb_admit_commit(sv_engine* e, const void* dev_embeds, int U, int S0_a
     if (!p.fork.empty()) HIPCHECK(hipMemcpyAsync(e->fork_desc, p.fork.data(), p.fork.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     add_i32(e->cb_nlive, n, 1, st);
     nlive_added = true;
-    if (lens) SVCHECK(prefill_forward_ragged(e, (const bf16_t*)dev_embeds, U, lens, st, e->cb_table_pf));
+    if (p.pc && p.pc->any_hit) SVCHECK(pc_prompt_pass(e, (const bf16_t*)dev_embeds, U, S0_all, lens, *p.pc, st));
+    else if (lens) SVCHECK(prefill_forward_ragged(e, (const bf16_t*)dev_embeds, U, lens, st, e->cb_table_pf));
     else SVCHECK(prefill_forward(e, (const bf16_t*)dev_embeds, U, S0_all, st, 0, nullptr, e->cb_table_pf));
     if (!p.fork.empty()) {
         ForkArgs f;
@@ -346,7 +494,10 @@ static int cb_admit_commit(sv_engine* e, const void* dev_embeds, int U, int S0_a
     HIPCHECK(hipStreamSynchronize(st));                    // the plan's vectors are host temporaries
     return 0;
     }();
-    if (!rc) return 0;
+    if (!rc) {
+        if (p.pc) pc_register(e, *p.pc, p.pf);
+        return 0;
+    }
     const std::string why = g_err;                          // keep the first error's text
     (void)hipStreamSynchronize(st);
     (void)hipGetLastError();
@@ -365,6 +516,10 @@ static int cb_admit_commit(sv_engine* e, const void* dev_embeds, int U, int S0_a
     for (size_t k = p.taken.size(); k-- > 0;) {             // pages go back in reverse order, no holder left: the free list is as it was
         e->page_refs[p.taken[k]] = 0;
         e->free_pages.push_back(p.taken[k]);
+    }
+    for (size_t k = 0; p.pc && k < p.pc->holders.size(); ++k) {      // the reused pages lose the holders this admit added
+        const int pg = p.pc->holders[k];
+        if (--e->page_refs[pg] == 0 && e->pc_reg[pg]) pc_lru_push(e, pg);
     }
     if (nlive_added) add_i32(e->cb_nlive, -n, 1, st);
     (void)hipStreamSynchronize(st);
@@ -385,7 +540,15 @@ static int cb_admit_impl(sv_engine* e, const void* dev_embeds, int32_t U, int32_
     HIPCHECK(hipStreamWaitEvent(st, e->gen_event, 0));
     SVCHECK(cb_begin(e, st));
     if (group && !e->fork_desc) SVCHECK(dalloc(e, &e->fork_desc, 6 * (size_t)mb));
+    PcAdmit pc;
     AdmitPlan p;
+    if (e->pc_on) {
+        if (e->exp & SV_EXP_BATCH_REMAINDER)
+            return fail(SV_ENOTSUP, "sv_cb_admit: the prefix cache is on and the A/B arm SV_EXP_BATCH_REMAINDER is selected (its remainder rows depend on the batch)");
+        if (((uintptr_t)dev_embeds & 15) != 0) return fail(SV_EINVAL, "sv_cb_admit: the prefix cache reads the prompt rows in 16-byte pieces: align dev_embeds to 16 bytes");
+        SVCHECK(pc_lookup(e, dev_embeds, U, S0_all, lens, pc, st));
+        p.pc = &pc;
+    }
     p.record = [&] { for (int i = 0; lps && i < n; ++i) if (lps[i].enable) return true; return false; }();
     if (p.record) SVCHECK(cb_lp_alloc(e));
     for (int s2 = 0; s2 < cb_slot_cap(e) && (int)p.slots.size() < n; ++s2) if (!e->cb_used[s2]) p.slots.push_back(s2);
@@ -596,6 +759,7 @@ static int cb_release_locked(sv_engine* e, int slot, hipStream_t st) {
     for (int pg : e->cb_pages[slot]) {
         // a shared prompt page (sv_cb_admit_shared) goes back when its last holder lets go; a private page at once
         if (e->page_refs[pg] > 0 && --e->page_refs[pg] > 0) continue;
+        if (e->pc_reg[pg]) { pc_lru_push(e, pg); continue; }      // a cached prompt page without a holder waits in the LRU list
         e->free_pages.push_back(pg);
     }
     e->cb_pages[slot].clear();
@@ -621,6 +785,7 @@ extern "C" int sv_cb_reset(sv_engine* e) {
         if (e->cb_used[s2]) SVCHECK(cb_release_locked(e, s2, e->gen_stream));
     HIPCHECK(hipStreamSynchronize(e->gen_stream));
     std::fill(e->page_refs.begin(), e->page_refs.end(), 0);
+    pc_drop(e);
     e->cb_active = false;
     return 0;
 }
@@ -675,5 +840,34 @@ extern "C" int sv_cb_lookup_counts(sv_engine* e, int32_t slot, int32_t* host_cou
     const int32_t* src = e->cb_lk_state + mb + (slot < 0 ? 3 * mb : 3 * slot);
     HIPCHECK(hipMemcpyAsync(host_counts3, src, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, e->gen_stream));
     HIPCHECK(hipStreamSynchronize(e->gen_stream));
+    return 0;
+}
+
+// ---- the prefix cache's switch and counters (sv_cb_set_prefix_cache / sv_cb_prefix_cache_info) ----
+extern "C" int sv_cb_set_prefix_cache(sv_engine* e, int32_t enable) {
+    if (!e) return fail(SV_EINVAL, "null engine");
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (e->cb_active) return fail(SV_ESTATE, "sv_cb_set_prefix_cache: a continuous batch is active (the setting changes before the first admit or after sv_cb_reset)");
+    if (!enable) { e->pc_on = false; return 0; }
+    if (e->kv_dtype != SV_KV_BF16)
+        return fail(SV_ENOTSUP, "sv_cb_set_prefix_cache: not built for the fp8_e4m3 KV cache (a prompt pass behind cached pages sees the dequantised cache, a "
+                                "one-shot pass the unquantised rows: the tokens would not be those of the same request with the cache off)");
+    if (e->exp & SV_EXP_BATCH_REMAINDER)
+        return fail(SV_ENOTSUP, "sv_cb_set_prefix_cache: the A/B arm SV_EXP_BATCH_REMAINDER is selected (its remainder rows depend on the batch)");
+    if (e->cfg.hidden % 8 != 0) return fail(SV_ENOTSUP, "sv_cb_set_prefix_cache: hidden %d is no multiple of 8 (the digest reads 16-byte pieces)", e->cfg.hidden);
+    HIPCHECK(hipSetDevice(e->cfg.device));
+    if (!e->pc_dig) SVCHECK(dalloc(e, &e->pc_dig, (size_t)e->cfg.max_batch * e->pages_per_seq * 2));
+    if (!e->pc_desc) SVCHECK(dalloc(e, &e->pc_desc, (size_t)2 * e->cfg.max_batch));
+    e->pc_on = true;
+    return 0;
+}
+
+extern "C" int sv_cb_prefix_cache_info(sv_engine* e, int64_t* host_out5) {
+    if (!e || !host_out5) return fail(SV_EINVAL, "sv_cb_prefix_cache_info: null argument");
+    std::lock_guard<std::mutex> lock(e->mu);
+    for (int i = 0; i < 5; ++i) host_out5[i] = 0;
+    if (!e->pc_on || !e->cb_active) return 0;
+    host_out5[0] = e->pc_lookups; host_out5[1] = e->pc_reused; host_out5[2] = (int64_t)e->pc_table.size(); host_out5[3] = (int64_t)e->pc_lru.size();
+    host_out5[4] = e->pc_evictions;
     return 0;
 }

@@ -393,6 +393,7 @@ extern "C" int sv_destroy(sv_engine* e) {
     if (e->d_rag) (void)hipFree(e->d_rag);
     if (e->rag_row_pos) (void)hipFree(e->rag_row_pos);
     if (e->gkv) (void)hipFree(e->gkv);
+    if (e->pc_ws) (void)hipFree(e->pc_ws);
     if (e->rag_ev) (void)hipEventDestroy(e->rag_ev);
     if (e->table_ev) (void)hipEventDestroy(e->table_ev);
     for (hipEvent_t ev : e->prof_ev) (void)hipEventDestroy(ev);
@@ -731,6 +732,7 @@ extern "C" int sv_load_weight(sv_engine* e, const char* name, const void* dev_pt
     for (int i = 0; i < ndim; ++i) numel *= (size_t)shape[i];
     if (numel != s.numel)
         return fail(SV_EINVAL, "weight '%s': %zu elements given, %zu expected", name, numel, s.numel);
+    pc_drop(e);                              // cached prompt pages were computed with the old weights
     hipStream_t st = (hipStream_t)stream;
     const int is_f32 = dtype == SV_DTYPE_F32;
     if (s.kind == SLOT_LINEAR_W || s.kind == SLOT_WTE) {

@@ -729,16 +729,23 @@ int sveng::extend_forward(sv_engine* e, ExtendPass& p, const bf16_t* embeds, con
     return 0;
 }
 
-int sveng::prefill_chunked(sv_engine* e, const bf16_t* embeds, int B, const int32_t* lens, const int32_t* table, hipStream_t st) {
+int sveng::prefill_chunked(sv_engine* e, const bf16_t* embeds, int B, const int32_t* lens, const int32_t* table, hipStream_t st, const int32_t* ctx0) {
     PlanProj pj[4];
     const int n_proj = plan_proj(e, pj), q_tile = attn_prefill_q_tile(e->cfg.n_head, e->nkv), D = e->cfg.hidden;
-    std::vector<std::vector<int32_t>> take;
-    extend_schedule(lens, B, e->prefill_chunk, take);
-    if (!e->logit_stash) SVCHECK(dalloc(e, &e->logit_stash, (size_t)e->cfg.max_batch * e->Vpad, false));
-    std::vector<int32_t> desc, at((size_t)B, 0);
+    // the own rows of every sequence: all of it, or what lies behind its cached context (ctx0: the prefix cache's reused pages)
+    std::vector<int32_t> own(lens, lens + B), desc, at((size_t)B, 0);
+    long long rows = 0;
+    size_t region = 0;
     int longest = 0;
-    for (int b = 0, r0 = 0; b < B; r0 += lens[b++]) { desc.push_back(r0); desc.push_back(lens[b]); longest = std::max(longest, lens[b]); }
-    SVCHECK(reserve_gkv(e, (size_t)longest));      // (a pass continues at most one sequence: the one the pass in front cut)
+    for (int b = 0, r0 = 0; b < B; r0 += own[b++]) {
+        if (ctx0) { own[b] -= ctx0[b]; at[b] = ctx0[b]; if (ctx0[b] > 0) region += (size_t)lens[b]; }
+        desc.push_back(r0); desc.push_back(lens[b]); longest = std::max(longest, lens[b]); rows += own[b];
+    }
+    std::vector<std::vector<int32_t>> take;
+    extend_schedule(own.data(), B, chunk_applies(e, rows) ? e->prefill_chunk : 0, take);
+    const bool stash = take.size() > 1;        // one pass: every sequence finishes in it, compact row i is sequence i
+    if (stash && !e->logit_stash) SVCHECK(dalloc(e, &e->logit_stash, (size_t)e->cfg.max_batch * e->Vpad, false));
+    SVCHECK(reserve_gkv(e, region + (size_t)longest));      // (a pass continues the sequences that came with a context and at most one more: the one the pass in front cut)
     size_t row0 = 0;
     std::vector<ExtendSeq> seqs((size_t)B);
     for (size_t k = 0; k < take.size(); ++k) {
@@ -747,13 +754,13 @@ int sveng::prefill_chunked(sv_engine* e, const bf16_t* embeds, int B, const int3
         extend_plan(seqs.data(), B, q_tile, pj, n_proj, p);
         p.list[XL_DESC] = desc;
         SVCHECK(extend_forward(e, p, embeds + row0 * D, table, st));
-        for (size_t i = 0; i < p.fin.size(); ++i)
+        for (size_t i = 0; stash && i < p.fin.size(); ++i)
             HIPCHECK(hipMemcpyAsync(e->logit_stash + (size_t)p.fin[i] * e->Vpad, e->logits + i * e->Vpad, (size_t)e->Vpad * sizeof(float),
                                     hipMemcpyDeviceToDevice, st));
         row0 += (size_t)p.M;
         for (int b = 0; b < B; ++b) at[b] += take[k][b];
     }
-    HIPCHECK(hipMemcpyAsync(e->logits, e->logit_stash, (size_t)B * e->Vpad * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (stash) HIPCHECK(hipMemcpyAsync(e->logits, e->logit_stash, (size_t)B * e->Vpad * sizeof(float), hipMemcpyDeviceToDevice, st));
     return 0;
 }
 

@@ -3,12 +3,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <list>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -99,6 +101,12 @@ struct GraphSlot {
 // bad-logits code; HF_BLOCK + BLK_* = a snapshot of the device block {step, done, n_emitted, bad}, HF_LOOKUP + 0..3 = lk_state's {steps, drafted,
 // accepted, n_emit[0]}
 enum { HF_DONE = 0, HF_NEMIT = 1, HF_CB_LIVE = 3, HF_BAD = 4, HF_BLOCK = 8, HF_LOOKUP = 12, BLK_STEP = 0, BLK_DONE = 1, BLK_NEMIT = 2, BLK_BAD = 3 };
+// a prefix-cache key / page digest: two 64-bit lanes (prefix_cache/prefix_cache.hip)
+struct PcKey {
+    uint64_t a, b;
+    bool operator==(const PcKey& o) const { return a == o.a && b == o.b; }
+};
+struct PcKeyHash { size_t operator()(const PcKey& k) const { return (size_t)(k.a ^ (k.b * 0x9E3779B97F4A7C15ull)); } };
 struct sv_engine {
     sv_config cfg;
     std::mutex mu;
@@ -245,6 +253,21 @@ struct sv_engine {
     int32_t* cb_lk_forced = nullptr;
     int cb_lk_forced_n = 0, cb_lk_forced_ld = 0;
     int trash_page = 0;                       // what the block-table rows of free slots point at
+    // sv_cb_set_prefix_cache (prefix_cache/prefix_cache.hip; the table: engine_cb.hip).  pc_on stays across sv_cb_reset; everything else lives from
+    // cb_begin to sv_cb_reset.  pc_table: chained key -> page.  A registered page's page_refs entry is its exact holder count; one without a holder
+    // sits in pc_lru (front = least recently released) instead of the free list.  pc_dig [max_batch][pages_per_seq] digests and pc_desc
+    // [2 * max_batch] descriptors are device memory of the engine (allocated by the first enable), pc_ws the compacted own rows of an admit with hits
+    bool pc_on = false;
+    std::unordered_map<PcKey, int, PcKeyHash> pc_table;
+    std::vector<PcKey> pc_key_of;                 // [num_pages + 1] the key a registered page stands under
+    std::vector<char> pc_reg;                     // [num_pages + 1] page is in pc_table
+    std::list<int> pc_lru;
+    std::vector<std::list<int>::iterator> pc_lru_it;
+    std::vector<char> pc_in_lru;
+    long long pc_lookups = 0, pc_reused = 0, pc_evictions = 0;
+    uint64_t* pc_dig = nullptr;
+    int32_t* pc_desc = nullptr;
+    bf16_t* pc_ws = nullptr; size_t pc_ws_rows = 0;
     std::unordered_map<int, GraphSlot> cb_graphs;      // one captured step per row bucket (cleared by cb_drop_graphs alone)
     // sv_generate: the captured decode step is kept while the next call has the same shape and sampling parameters
     GraphSlot gen_step;
@@ -454,8 +477,18 @@ void extend_plan(const ExtendSeq* seqs, int B, int q_tile, const PlanProj* proj,
 ExtKvArgs extend_kv_args(sv_engine* e, int layer, const int32_t* table, const int32_t* xseq, const int32_t* blocks, int n_blocks, bf16_t* gkv);
 // one pass over p.M packed own rows `embeds`; p.list[XL_DESC] / [XL_POS] are the caller's.  Last-row logits of compact row i (sequence p.fin[i]) -> row i of e->logits
 int extend_forward(sv_engine* e, ExtendPass& p, const bf16_t* embeds, const int32_t* table, hipStream_t st);
-// a generate-tail prompt pass over B sequences of lens[] rows as passes of at most e->prefill_chunk own rows; leaves e->logits and d_rag as the one-shot pass does
-int prefill_chunked(sv_engine* e, const bf16_t* embeds, int B, const int32_t* lens, const int32_t* table, hipStream_t st);
+// a generate-tail prompt pass over B sequences of lens[] rows as passes of at most e->prefill_chunk own rows (one pass when the budget does not
+// apply); leaves e->logits and d_rag as the one-shot pass does.  ctx0 != nullptr: sequence b already has ctx0[b] < lens[b] tokens in its pages (the
+// prefix cache's reused pages) and `embeds` packs only the lens[b] - ctx0[b] own rows of every sequence; the budget counts own rows
+int prefill_chunked(sv_engine* e, const bf16_t* embeds, int B, const int32_t* lens, const int32_t* table, hipStream_t st, const int32_t* ctx0 = nullptr);
+// prefix_cache/prefix_cache.hip: the page digests of an admit and the host arithmetic of the keys
+//   digests: one launch over n packed prompts (lens == nullptr: n x S0 rows) -> dev_out [n][max_pages] digests, entry (u, k) written for k < len_u / 64;
+//            dev_desc: room for 2 * n int32 (the {first packed row, len} descriptors, uploaded from host_desc -- which must outlive the copy)
+int pc_launch_digests(const bf16_t* embeds, int n, const int32_t* dev_desc, int S0, int hidden, int max_pages, uint64_t* dev_out, hipStream_t st);
+PcKey pc_chain(const PcKey& prev, const PcKey& digest);      // key_k = mix(key_{k-1}, digest_k)
+PcKey pc_key0();                                             // key_{-1}
+inline int pc_hit_pages(int matched, int L) { return std::min(matched, (L - 1) / SV_PAGE_TOKENS); }      // at least one own row is always computed
+void pc_drop(sv_engine* e);      // engine_cb.hip: the table is empty again; cached pages nobody holds go back to the free list
 // engine_generate.hip
 void fork_args(sv_engine* e, int n_prompts, int n_rows, ForkArgs& f);      // the fork launch over e->fork_desc, the engine's block table, pool and logits
 // validation of a processor set against a vocabulary of V ids (V <= 0: the ids are only checked for >= 0) -- host arithmetic, no device -- and

@@ -993,6 +993,21 @@ class HipEngine:
         check(self.lib.sv_cb_lookup_counts(self._h, int(slot), c), "sv_cb_lookup_counts")
         return {"steps": c[0], "drafted": c[1], "accepted": c[2]}
 
+    def cb_set_prefix_cache(self, on: bool) -> None:
+        """The continuous batch's prefix cache (sv_cb_set_prefix_cache): with it on, an admit reuses the full 64-row KV pages earlier admits of
+        the batch computed for the same leading prompt rows -- found by digests of the embedding rows, kept resident after their requests were
+        released while no admit needs the pages -- and computes only the rows behind them.  Every request's tokens, finish and record are
+        those of a batch with the cache off.  Off by default.  Only while no batch is active (RuntimeError otherwise); the setting stays
+        across `cb_reset`, the cached pages do not.  NotImplementedError on an fp8 KV cache."""
+        check(self.lib.sv_cb_set_prefix_cache(self._h, 1 if on else 0), "sv_cb_set_prefix_cache")
+
+    def cb_prefix_cache_info(self) -> dict:
+        """{lookups: full prompt pages looked up, reused, resident: pages in the table, unheld: of those without a holder, evictions} since
+        the batch began (sv_cb_prefix_cache_info); all zero while the cache is off."""
+        c = (C.c_int64 * 5)()
+        check(self.lib.sv_cb_prefix_cache_info(self._h, c), "sv_cb_prefix_cache_info")
+        return {"lookups": c[0], "reused": c[1], "resident": c[2], "unheld": c[3], "evictions": c[4]}
+
     def cb_set_lookup_drafts(self, streams) -> None:
         """Test surface (sv_debug_cb_set_lookup_drafts): draft j of slot s < len(streams) of the drafting batch admitted next is
         streams[s][step_s + j] instead of the lookup (rows of equal length; nothing is drafted beyond them).  None clears it."""

@@ -120,7 +120,8 @@ class ModelWorker:
                  model_name: Optional[str] = None, device="cuda", limit_model_concurrency: int = 5, *,
                  model=None, tokenizer=None, image_processor=None, context_len: Optional[int] = None,
                  continuous_batching: bool = True, prompt_lookup_num_tokens: int = 0, max_matching_ngram_size: int = 0,
-                 weight_dtype: Optional[str] = None, kv_cache_dtype: Optional[str] = None, prefill_chunk_rows: Optional[int] = None):
+                 weight_dtype: Optional[str] = None, kv_cache_dtype: Optional[str] = None, prefill_chunk_rows: Optional[int] = None,
+                 enable_prefix_caching: bool = False):
         self.controller_addr, self.worker_addr, self.worker_id = controller_addr, worker_addr, worker_id
         model_path = model_path[:-1] if model_path.endswith("/") else model_path
         if model_name is None:                                         # :46-52
@@ -147,6 +148,8 @@ class ModelWorker:
             # --prompt-lookup-num-tokens K: every decode step verifies up to K tokens drafted from the request's own output (same tokens,
             # max_batch // (K + 1) requests share the loop: at the default concurrency of 5 the other rows of the engine are idle anyway)
             kw = dict(prompt_lookup_num_tokens=prompt_lookup_num_tokens, max_matching_ngram_size=max_matching_ngram_size) if prompt_lookup_num_tokens else {}
+            if enable_prefix_caching:      # --enable-prefix-caching: a repeated image reuses its earlier request's full KV pages (same tokens)
+                kw["prefix_cache"] = True
             self.batcher = ContinuousBatcher(eng, **kw)
             lm.batcher = self.batcher
         self.limit_model_concurrency = limit_model_concurrency
@@ -326,12 +329,18 @@ def main(argv=None):                                                   # :235-26
                    help="decoder weight format (default: SV_WEIGHT_DTYPE, else bf16); fp8 / mxfp4 quantise at load and are not the reference's precision")
     p.add_argument("--kv-cache-dtype", type=str, default=None, choices=["auto", "bf16", "fp8", "fp8_e4m3"],
                    help="KV-cache format (default: SV_KV_DTYPE, else bf16); fp8 halves the cache and is not the reference's precision")
+    p.add_argument("--enable-prefix-caching", action="store_true",
+                   help="keep the KV pages of finished requests' prompts and reuse them for later requests with the same leading prompt rows (same tokens)")
     p.add_argument("--prefill-chunk-rows", type=int, default=None,
                    help="row budget of a prompt pass (default: SV_PREFILL_CHUNK_ROWS, else 0 = off): longer prompt passes run in pieces over the KV "
                         "cache with the same tokens, and the prompt-pass workspaces are sized by the budget")
     args = p.parse_args(argv)
     if args.prefill_chunk_rows is not None and args.prefill_chunk_rows < 0:
         p.error("--prefill-chunk-rows must be >= 0")
+    if args.enable_prefix_caching and args.no_continuous_batching:
+        p.error("--enable-prefix-caching needs continuous batching")
+    if args.enable_prefix_caching and args.kv_cache_dtype in ("fp8", "fp8_e4m3"):
+        p.error("--enable-prefix-caching is not built for an fp8 KV cache")
     if args.prompt_lookup_num_tokens and args.no_continuous_batching:
         p.error("--prompt-lookup-num-tokens drafts in the continuous batch: drop --no-continuous-batching")
     import uvicorn
@@ -339,7 +348,8 @@ def main(argv=None):                                                   # :235-26
                          args.model_path, args.model_name, args.device, args.limit_model_concurrency,
                          continuous_batching=not args.no_continuous_batching, prompt_lookup_num_tokens=args.prompt_lookup_num_tokens,
                          max_matching_ngram_size=args.max_matching_ngram_size, weight_dtype=args.weight_dtype,
-                         kv_cache_dtype=args.kv_cache_dtype, prefill_chunk_rows=args.prefill_chunk_rows)
+                         kv_cache_dtype=args.kv_cache_dtype, prefill_chunk_rows=args.prefill_chunk_rows,
+                         enable_prefix_caching=args.enable_prefix_caching)
     uvicorn.run(build_app(worker), host=args.host, port=args.port, log_level="info")
 
 

@@ -261,17 +261,27 @@ class LLM:
 
     ``kv_cache_dtype="fp8"`` / ``"fp8_e4m3"`` keeps the paged KV cache as e4m3 codes with one power-of-two scale per key and head
     (`EngineConfig.kv_dtype`): half the pool and half the decode attention's stream; ``"auto"`` = bf16 (or the environment's SV_KV_DTYPE).
-    Any other string raises ValueError.  Prompt-lookup drafting is not built for it.  Not the reference's precision."""
+    Any other string raises ValueError.  Prompt-lookup drafting is not built for it.  Not the reference's precision.
+
+    ``enable_prefix_caching=True`` (vLLM's keyword) switches on the continuous batch's prefix cache (`HipEngine.cb_set_prefix_cache`): within a
+    `generate` call a prompt whose leading rows an earlier request brought -- the same image again, the part of a group of n samples that did
+    not fit at once -- reuses that request's full KV pages.  The keys are digests of the prompt's embedding rows, not token ids; the tokens are
+    those without the argument.  NotImplementedError together with an fp8 ``kv_cache_dtype``."""
 
     def __init__(self, model: str, tokenizer=None, dtype: str = "auto", max_model_len: Optional[int] = None,
                  max_num_seqs: Optional[int] = None, trust_remote_code: bool = False, speculative_model: Optional[str] = None,
                  num_speculative_tokens: Optional[int] = None, ngram_prompt_lookup_max: Optional[int] = None,
-                 ngram_prompt_lookup_min: Optional[int] = None, quantization: Optional[str] = None, kv_cache_dtype: str = "auto", **kwargs):
+                 ngram_prompt_lookup_min: Optional[int] = None, quantization: Optional[str] = None, kv_cache_dtype: str = "auto",
+                 enable_prefix_caching: bool = False, **kwargs):
         from .model import StarVectorForCausalLM
         if kv_cache_dtype not in ("auto", "fp8", "fp8_e4m3"):
             raise ValueError(f"kv_cache_dtype must be \"auto\", \"fp8\" or \"fp8_e4m3\", got {kv_cache_dtype!r}")
         if kv_cache_dtype != "auto" and speculative_model is not None:
             raise NotImplementedError("speculative_model=\"[ngram]\" with an fp8 KV cache is not built (the drafts' K / V pre-write is bf16)")
+        if enable_prefix_caching and kv_cache_dtype != "auto":
+            raise NotImplementedError("enable_prefix_caching with an fp8 KV cache is not built (a prompt pass behind cached pages sees the dequantised "
+                                      "cache: the tokens would not be those without the cache)")
+        self._prefix_cache = bool(enable_prefix_caching)
         if quantization is not None and quantization not in ("fp8", "mxfp4"):
             raise ValueError(f"quantization must be \"fp8\", \"mxfp4\" or None, got {quantization!r}")
         self._lookup = {}
@@ -378,7 +388,7 @@ class LLM:
         if logprobs is not None:
             for j in jobs:
                 j["params"] = dict(j["params"], logprobs=int(logprobs), logprob_source="processed")
-        batcher = ContinuousBatcher(self.engine, **getattr(self, "_lookup", {}))
+        batcher = ContinuousBatcher(self.engine, **getattr(self, "_lookup", {}), **(dict(prefix_cache=True) if getattr(self, "_prefix_cache", False) else {}))
         try:
             handles = []
             for _, grp in itertools.groupby(jobs, key=lambda j: j["input"]):
